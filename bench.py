@@ -15,9 +15,14 @@ max over ranks). Rank 0 prints ONE JSON line.
 `value` is what a caller of `run_pca` gets: the rate of steps that return U, sigma and V as host arrays, as the reference's
 signature does (scan-rs/src/dim_red/mod.rs:47); `config.device_resident_cells_per_s` is the rate with U and V left in HBM
 (scanrs_pca_result_device) for device-side consumers, `config.first_call_s` the cold create -> normalize -> run_pca on a
-fresh handle (the transposed copy and the tile layouts of the hybrid product are built there). Also reported: roofline — HBM roofline of the dominant kernel, algorithmic bytes per
-launch / average launch duration measured with HIP events on the library's stream; cpu_baseline — the CPU oracle
-(port of the reference's serial schedule) on 1 core and on all cores, bounded samples, rank 0 at N = 1 only.
+fresh handle (the transposed copy and the tile layouts of the hybrid product are built there).
+
+A plain run sets up, warms up, times the K steps and prints the line; everything else is measured with `--full` only:
+the device-resident rate (a second pass of K steps with per-launch HIP events), the step with fresh result arrays,
+RandSvd, IRLBA, the replicated / sharded split, the heavy-tailed profile, roofline — HBM roofline of the dominant kernel,
+algorithmic bytes per launch / average launch duration measured with HIP events on the library's stream — and
+cpu_baseline — the CPU oracle (port of the reference's serial schedule) on 1 core and on all cores, bounded samples,
+rank 0 at N = 1 only. `--dump-outputs DIR` writes U, sigma and V of the last timed step as .npy files.
 """
 import argparse
 import json
@@ -39,6 +44,18 @@ KERNEL_SOURCES = ("scan-rs_amd/csrc/tiles.hip", "scan-rs_amd/csrc/tiles_dense.in
 
 
 SHARDED_KERNEL_PREFIXES = ("spmm_", "tile_weights", "row_reduce", "col_moments", "col_sums", "materialize_map_values")  # work over the rank's own cells only
+DUMP_BYTES = 60_000_000  # --dump-outputs: all files together stay under 64 MB, .npy headers included; U may take half of it
+DUMP_SEED = 20240917
+
+
+def dump_rows(n_rows, row_bytes, budget):
+    """Rows of an n_rows-row factor that --dump-outputs writes: None (all of them) when they fit the budget, otherwise a sample
+    drawn from a fixed seed, sorted - the same rows in every run with the same arguments."""
+    import numpy as np
+
+    if n_rows * row_bytes <= budget:
+        return None
+    return np.sort(np.random.default_rng(DUMP_SEED).choice(n_rows, size=budget // row_bytes, replace=False))
 
 
 def split_replicated_sharded(ms_full, ms_part, frac):
@@ -104,7 +121,16 @@ def parse():
     ap.add_argument("--opt", action="append", default=[], metavar="KEY=VALUE", help="scanrs_mat_set_option on the handle (experiments)")
     ap.add_argument("--sqz-bench", action="store_true",
                     help="instead: the reference's only benchmark (sqz/benches/my_benchmark.rs): u32 CSR / CSC 1000 x 10000 times 10000 x 16")
-    return ap.parse_args()
+    ap.add_argument("--full", action="store_true",
+                    help="also measure everything besides the headline figure: device-resident rate, fresh result arrays, RandSvd, IRLBA, "
+                         "replicated / sharded split, heavy-tailed profile, roofline, CPU baseline (each still switched off by its --no-* option)")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed steps write U, sigma and V of the last one as DIR/{u,s,v}.npy (float64); a factor whose rows "
+                         f"exceed its share of {DUMP_BYTES // 10**6} MB is written as a fixed seeded sample of its rows, in row order")
+    args = ap.parse_args()
+    if args.steps < 1:
+        ap.error("--steps must be at least 1")
+    return args
 
 
 class Watchdog:
@@ -466,7 +492,7 @@ def main():
     barrier()
     # Timed region: exactly K steps between barriers, each returning host arrays like run_pca. The per-launch HIP events
     # that feed the roofline leg put a marker packet before and after every launch of a step, which costs a few percent of
-    # wall time, so by default they are recorded in a second pass of K steps right after the timed one (same inputs, same
+    # wall time, so with --full they are recorded in a second pass of K steps right after the timed one (same inputs, same
     # launches, results left in HBM: that pass is also the device-resident rate); --events-in-timed-region records them
     # inside the timed steps instead.
     mat.profile_reset()
@@ -480,18 +506,45 @@ def main():
     barrier()
     elapsed = time.perf_counter() - t0
     elapsed_local = elapsed
-    events_elapsed = None
-    dbg("device-resident steps")
-    mat.profile_enable(not args.events_in_timed_region)
-    barrier()
-    t0 = time.perf_counter()
-    for _ in range(args.steps):
-        step()
-    barrier()
-    events_elapsed = time.perf_counter() - t0
     mat.profile_enable(False)
+    if args.dump_outputs:
+        # what the last timed step handed its caller: U (genes x k), sigma, V (cells x k). V's rows are sampled by their global
+        # cell index and gathered on rank 0 in cell order, so the files do not depend on the number of ranks.
+        dbg("dump outputs")
+        if args.no_host_delivery:
+            res = sa.pca_result_device(mat)
+            u_all = torch.as_tensor(sa.DevArray(res.d_u, args.genes * res.ld_u), device=dev).view(args.genes, res.ld_u)[:, : res.k]
+            v_loc = torch.as_tensor(sa.DevArray(res.d_v, n_local * res.ld_v), device=dev).view(n_local, res.ld_v)[:, : res.k]
+        else:
+            u_all, v_loc = torch.from_numpy(out_u), torch.from_numpy(out_v)
+        u_rows = dump_rows(args.genes, 8 * args.k, DUMP_BYTES // 2)
+        u_bytes = 8 * args.k * (args.genes if u_rows is None else len(u_rows))
+        v_rows = dump_rows(args.cells, 8 * args.k, DUMP_BYTES - u_bytes - 8 * args.k)
+        if v_rows is not None:
+            v_loc = v_loc[torch.as_tensor(v_rows[(v_rows >= lo) & (v_rows < hi)] - lo, device=v_loc.device)]
+        v_dump = [v_loc.cpu().numpy()]
+        if dist is not None:
+            parts = [None] * world if rank == 0 else None
+            dist.gather_object(v_dump[0], parts, dst=0)
+            v_dump = parts
+        if rank == 0:
+            os.makedirs(args.dump_outputs, exist_ok=True)
+            u_dump = u_all if u_rows is None else u_all[torch.as_tensor(u_rows, device=u_all.device)]
+            for name, a in (("u", u_dump.cpu().numpy()), ("s", sig), ("v", np.concatenate(v_dump))):
+                np.save(os.path.join(args.dump_outputs, f"{name}.npy"), np.ascontiguousarray(a, dtype=np.float64))
+    events_elapsed = None
+    if args.full:
+        dbg("device-resident steps")
+        mat.profile_enable(not args.events_in_timed_region)
+        barrier()
+        t0 = time.perf_counter()
+        for _ in range(args.steps):
+            step()
+        barrier()
+        events_elapsed = time.perf_counter() - t0
+        mat.profile_enable(False)
     fresh_ms = None
-    if not args.no_host_delivery:  # the same step handing out NEW host arrays every time (the Python wrapper's default form)
+    if args.full and not args.no_host_delivery:  # the same step handing out NEW host arrays every time (the Python wrapper's default form)
         barrier()
         t0 = time.perf_counter()
         for _ in range(args.steps):
@@ -504,9 +557,10 @@ def main():
         t = torch.tensor([elapsed], dtype=torch.float64)
         dist.all_reduce(t, op=dist.ReduceOp.MAX)
         elapsed = float(t.item())
-        t = torch.tensor([events_elapsed], dtype=torch.float64)
-        dist.all_reduce(t, op=dist.ReduceOp.MAX)
-        events_elapsed = float(t.item())
+        if events_elapsed is not None:
+            t = torch.tensor([events_elapsed], dtype=torch.float64)
+            dist.all_reduce(t, op=dist.ReduceOp.MAX)
+            events_elapsed = float(t.item())
         nn = torch.tensor([nnz_local], dtype=torch.int64)
         gl = [torch.zeros(1, dtype=torch.int64) for _ in range(world)]
         dist.all_gather(gl, nn)
@@ -548,11 +602,13 @@ def main():
 
     # the factors of the timed steps are reachable: PcaResult in HBM (Missing #4 of the round-1 verdict)
     res = sa.pca_result_device(mat)
-    v_t = torch.as_tensor(sa.DevArray(res.d_v, n_local * res.ld_v), device=dev).view(n_local, res.ld_v)[:, : res.k]
-    vnorm = (v_t * v_t).sum(dim=0).cpu()
-    if dist is not None:
-        dist.all_reduce(vnorm)
-    v_col_norm_err = float((vnorm - 1.0).abs().max().item())
+    v_col_norm_err = None
+    if args.full:
+        v_t = torch.as_tensor(sa.DevArray(res.d_v, n_local * res.ld_v), device=dev).view(n_local, res.ld_v)[:, : res.k]
+        vnorm = (v_t * v_t).sum(dim=0).cpu()
+        if dist is not None:
+            dist.all_reduce(vnorm)
+        v_col_norm_err = float((vnorm - 1.0).abs().max().item())
 
     knn_ms = None
     if args.also_knn and world == 1:
@@ -563,7 +619,7 @@ def main():
 
     randsvd_ms = None
     randsvd_kernels = irlba_kernels = None
-    if not args.no_randsvd and world == 1:
+    if args.full and not args.no_randsvd and world == 1:
         import ctypes
 
         s_out = np.zeros(args.k)
@@ -584,7 +640,7 @@ def main():
         mat.profile_enable(False)
 
     irlba_ms = irlba_mprod = None
-    if not args.no_irlba and world == 1:
+    if args.full and not args.no_irlba and world == 1:
         import ctypes
 
         s_out = np.zeros(args.k)
@@ -611,7 +667,7 @@ def main():
     # The same step on a second matrix with HALF the cells (same model, same genes): t(1/2) against t(1) gives the term that shrinks
     # with the cell range and the one that does not - the floor of the step on 8 GPUs is replicated + sharded / 8 + the exchanges.
     split = None
-    if world == 1 and not args.no_split_probe and args.cells >= 4096:
+    if args.full and world == 1 and not args.no_split_probe and args.cells >= 4096:
         dbg("split probe")
         hc = args.cells // 2
         pip_, pix_, pvv_ = synth_counts_torch(hc, args.genes, args.density, args.seed, dev)
@@ -650,7 +706,7 @@ def main():
     # most genes in almost none (sqz/src/lib.rs:5-8). tools/pass_bench.py's model of that (Gamma(0.1) gene rates, one profile shared by
     # all clusters: ~2 900 genes above 10 % detection holding 3/4 of the nonzeros) at the same shape and density, same step.
     heavy = None
-    if world == 1 and not args.no_heavy_tailed:
+    if args.full and world == 1 and not args.no_heavy_tailed:
         dbg("heavy-tailed profile")
         hip_, hix_, hvv_ = synth_counts_torch(args.cells, args.genes, args.density, args.seed, dev, gene_shape=0.1, shared_profile=1.0)
         per_gene = torch.bincount(hix_.long(), minlength=args.genes).float() / args.cells
@@ -681,7 +737,7 @@ def main():
 
     # ---- roofline of the dominant kernel -------------------------------------------------------------------
     roof = None
-    if prof:
+    if args.full and prof:
         # the dominant kernel of the critical path: the overflow gather of the hybrid product ("_ov") and the dense kernels the
         # solver queues on its second stream run BESIDE the sparse passes (their event durations are stretched by the sharing)
         side = ("spmm_gather2d_ov", "gemm_tiled", "gram_tiled", "gemm_skinny", "allreduce")
@@ -801,13 +857,19 @@ def main():
 
     # ---- CPU baseline: the oracle (the reference's serial schedule) on bounded samples: 1 core, then all cores -------
     cpu = None
-    if rank == 0 and world == 1 and not args.no_cpu_baseline:
+    if rank == 0 and world == 1 and args.full and not args.no_cpu_baseline:
         sys.path.insert(0, os.path.join(ROOT, "oracle"))
         import scanrs_oracle as so
-        from threadpoolctl import threadpool_limits
+        import scipy.linalg  # noqa: F401  (the LAPACK of the oracle's dense steps: loaded now so that threadpool_info sees its pool)
+        from threadpoolctl import threadpool_info, threadpool_limits
 
         so.build()
-        nproc = os.cpu_count() or 1
+        # the cores this process may use: its CPU affinity, and no more than OMP_NUM_THREADS where the host sets it
+        nproc = len(os.sched_getaffinity(0)) if hasattr(os, "sched_getaffinity") else (os.cpu_count() or 1)
+        if os.environ.get("OMP_NUM_THREADS", "").isdigit():
+            nproc = max(1, min(nproc, int(os.environ["OMP_NUM_THREADS"])))
+        # OpenBLAS cannot grow its thread pool past the size it started with (asked for more, it crashes in the next LAPACK call)
+        blas_pool = min([p["num_threads"] for p in threadpool_info() if p["user_api"] == "blas"] or [nproc])
 
         def cpu_run(nc, threads, lapack_threads):
             ip, ix, vv = synth_counts_torch(args.cells, args.genes, args.density, args.seed, dev, 0, nc)
@@ -840,7 +902,7 @@ def main():
         if nproc > 1:
             nca = min(args.cpu_cells_all, args.cells)
             nth = nproc if nproc <= 64 else nproc // 2  # one thread per physical core on an SMT-2 host
-            nla = min(32, nth)
+            nla = min(32, nth, blas_pool)
             ta = cpu_run(nca, nth, nla)
             cpu["all_cores"] = {
                 "value": round(nca / ta, 2), "unit": "cells/s", "cores": nth, "kind": "port",
@@ -850,7 +912,7 @@ def main():
             }
 
     if rank == 0:
-        ar_ms = sum(v["total_ms"] for k, v in prof.items() if k.startswith("allreduce")) / args.steps if prof else 0.0
+        ar_ms = sum(v["total_ms"] for k, v in prof.items() if k.startswith("allreduce")) / args.steps if prof else None  # per-launch events: --full
         out = {
             "metric": f"cells/sec for top-{args.k} PCA on {args.cells}x{args.genes} @{args.density:.0%} nnz; achieved HBM GB/s vs roofline",
             "value": round(value, 1),
@@ -874,8 +936,8 @@ def main():
                                     "fresh_result_arrays_ms_per_step: new host arrays per step; device_resident_*: the same steps with U, V "
                                     "left in HBM (scanrs_pca_result_device)") if not args.no_host_delivery else "--no-host-delivery: U, V left in HBM in every step",
                 "fresh_result_arrays_ms_per_step": round(fresh_ms, 2) if fresh_ms is not None else None,
-                "device_resident_cells_per_s": round(args.cells * args.steps / events_elapsed, 1),
-                "device_resident_ms_per_step": round(events_elapsed / args.steps * 1e3, 2),
+                "device_resident_cells_per_s": round(args.cells * args.steps / events_elapsed, 1) if events_elapsed else None,
+                "device_resident_ms_per_step": round(events_elapsed / args.steps * 1e3, 2) if events_elapsed else None,
                 "v_col_norm_err_device_result": v_col_norm_err,
                 "first_call_s": round(t_setup, 3),
                 "first_call_cells_per_s": round(args.cells / t_setup, 1),
@@ -894,12 +956,12 @@ def main():
                 "sigma_top3": [round(float(x), 6) for x in (sig[:3] if sig is not None else [])],
                 "per_rank_ms_per_step": [round(x, 2) for x in rank_ms],
                 "per_rank_nnz": nnz_ranks,
-                "per_rank_sharded_kernel_ms_per_step": [round(x, 2) for x in rank_sharded_kernel_ms],
-                "allreduce_ms_per_step_rank0": round(ar_ms, 3),
+                "per_rank_sharded_kernel_ms_per_step": [round(x, 2) for x in rank_sharded_kernel_ms] if prof else None,
+                "allreduce_ms_per_step_rank0": round(ar_ms, 3) if prof else None,
                 "rccl": {"source": rccl_seen["source"], "nranks_seen_per_rank": [int(x[3]) for x in rank_ar],
-                         "allreduce_ms_per_step_per_rank": [round(x[0], 3) for x in rank_ar],
-                         "allreduce_calls_per_step_per_rank": [round(x[1], 1) for x in rank_ar],
-                         "allreduce_bytes_per_step_per_rank": [int(x[2]) for x in rank_ar]},
+                         "allreduce_ms_per_step_per_rank": [round(x[0], 3) for x in rank_ar] if prof else None,
+                         "allreduce_calls_per_step_per_rank": [round(x[1], 1) for x in rank_ar] if prof else None,
+                         "allreduce_bytes_per_step_per_rank": [int(x[2]) for x in rank_ar] if prof else None},
             },
             "roofline": roof,
             "cpu_baseline": cpu,

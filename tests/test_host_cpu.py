@@ -204,10 +204,11 @@ def test_rccl_hook_serves_the_exchange_steps(tmp_path):
         assert v["rand_s_rel"] < 1e-8 and v["rand_u_abs"] < 1e-6 and v["rand_v_abs"] < 1e-6, v
 
 
-def _bench_line(extra_env, launcher, tmp_path, gpus, shape=("--cells", "6000", "--genes", "1500", "--density", "0.04", "--k", "8"), timeout=900):
+def _bench_line(extra_env, launcher, tmp_path, gpus, shape=("--cells", "6000", "--genes", "1500", "--density", "0.04", "--k", "8"), timeout=900,
+                extra=("--full",)):
     env = dict(os.environ)
     env.update(extra_env)
-    args = ["--gpus", str(gpus), "--steps", "1", "--warmup", "1", *shape, "--no-cpu-baseline"]
+    args = ["--gpus", str(gpus), "--steps", "1", "--warmup", "1", *shape, "--no-cpu-baseline", *extra]
     cmd = [sys.executable] + launcher + [os.path.join(ROOT, "bench.py")] + args
     r = subprocess.run(cmd, env=env, capture_output=True, text=True, timeout=timeout, cwd=str(tmp_path))
     assert r.returncode == 0, r.stdout[-2000:] + r.stderr[-4000:]
@@ -281,6 +282,42 @@ def test_bench_four_ranks_at_200k_cells_within_a_hard_timeout(tmp_path):
     assert d["n_gpus"] == 4 and len(d["config"]["per_rank_nnz"]) == 4
     assert "transport" in d["config"] and d["config"]["allreduce_ms_per_step_rank0"] > 0
     assert d["config"]["v_col_norm_err_device_result"] < 1e-9
+
+
+@pytest.mark.gpu
+def test_bench_plain_run_dumps_the_factors_of_its_last_step(tmp_path):
+    """A plain run (no --full) prints the headline line without the other legs and, with --dump-outputs, writes U, sigma and V of
+    its last timed step: sigma as in the line, V's columns unit vectors, and the same factors from one rank and from two ranks."""
+    one = _bench_line({}, [], tmp_path, 1, extra=("--dump-outputs", str(tmp_path / "d1")))
+    two = _bench_line({"SCANRS_BENCH_SHARED_GPU": "1"}, [], tmp_path, 2, extra=("--dump-outputs", str(tmp_path / "d2")))
+    for d in (one, two):
+        assert d["steps"] == 1 and d["ms_per_step"] > 0 and d["value"] > 0 and d["unit"] == "cells/s" and d["higher_is_better"] is True
+        assert d["roofline"] is None and d["cpu_baseline"] is None and d["config"]["device_resident_cells_per_s"] is None
+    u, s, v = (np.load(tmp_path / "d1" / f"{n}.npy") for n in ("u", "s", "v"))
+    assert u.shape == (1500, 8) and s.shape == (8,) and v.shape == (6000, 8) and u.dtype == s.dtype == v.dtype == np.float64
+    assert np.max(np.abs(s[:3] - np.array(one["config"]["sigma_top3"]))) <= 1e-6
+    assert np.max(np.abs(np.sum(v * v, axis=0) - 1.0)) < 1e-9 and np.max(np.abs(np.sum(u * u, axis=0) - 1.0)) < 1e-9
+    u2, s2, v2 = (np.load(tmp_path / "d2" / f"{n}.npy") for n in ("u", "s", "v"))
+    assert np.max(np.abs(s2 - s) / s) < 1e-9
+    sign = np.sign(np.sum(u * u2, axis=0))
+    assert np.max(np.abs(u2 * sign - u)) < 1e-6 and np.max(np.abs(v2 * sign - v)) < 1e-6
+
+
+def test_bench_dump_sample_is_fixed_and_within_its_budget():
+    """--dump-outputs writes a factor whole when it fits its budget, otherwise the same sorted sample of rows in every run."""
+    import importlib.util
+
+    spec = importlib.util.spec_from_file_location("bench_mod", os.path.join(ROOT, "bench.py"))
+    bench = importlib.util.module_from_spec(spec)
+    spec.loader.exec_module(bench)
+    assert bench.dump_rows(1000, 400, 400_000) is None
+    rows = bench.dump_rows(1_000_000, 400, 40_000_000)
+    assert len(rows) == 100_000 and np.all(np.diff(rows) > 0) and 0 <= rows[0] and rows[-1] < 1_000_000
+    assert np.array_equal(rows, bench.dump_rows(1_000_000, 400, 40_000_000))
+    # the default workload (33 k genes, 1 M cells, k = 50): U whole, V sampled, all three files under 64 MB
+    assert bench.dump_rows(33_000, 400, bench.DUMP_BYTES // 2) is None
+    v_rows = bench.dump_rows(1_000_000, 400, bench.DUMP_BYTES - 33_000 * 400 - 400)
+    assert 33_000 * 400 + 400 + len(v_rows) * 400 + 3 * 128 < 64_000_000
 
 
 def test_bench_watchdog_names_the_stage(tmp_path):

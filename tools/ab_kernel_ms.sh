@@ -3,7 +3,7 @@
 # (bench.py's own per-kernel accounting) for the library in each directory (SCANRS_AMD_LIB).
 KEY=$1; shift
 for L in "$@"; do
-  SCANRS_AMD_LIB=$PWD/$L/libscanrs_amd.so python3 bench.py --steps 4 --warmup 2 --no-cpu-baseline --no-heavy-tailed --no-randsvd --no-irlba --no-split-probe > /tmp/ab.json 2>/tmp/ab.err
+  SCANRS_AMD_LIB=$PWD/$L/libscanrs_amd.so python3 bench.py --full --steps 4 --warmup 2 --no-cpu-baseline --no-heavy-tailed --no-randsvd --no-irlba --no-split-probe > /tmp/ab.json 2>/tmp/ab.err
   python3 - "$L" "$KEY" <<'PY'
 import json, sys
 d = json.loads([l for l in open("/tmp/ab.json") if l.startswith("{")][-1])
