@@ -491,6 +491,51 @@ int scanrs_host_sym_eig(const double *a, int n, double *w, double *z);
 /* the k leading eigenpairs only: w[0..k) descending, z row-major n x k */
 int scanrs_host_sym_eig_topk(const double *a, int n, int k, double *w, double *z);
 
+/* ---- sSeq differential expression (diff-exp/src/diff_exp.rs, dist.rs; NbExactBackend::LogSpace) ----------------------------
+ * Rows of the handle are genes and columns are cells (the reference's feature x barcode matrix; use scanrs_mat_t on a cell-major
+ * handle). DE reads the stored u32 counts and ignores the handle's map and offset. Labels are one int16 per cell: the group
+ * 0 .. n_groups - 1 (n_groups <= 8192) or -1 for a cell in no group. Sharded handles return SCANRS_ERR_ARGUMENT. Outputs of
+ * several tests are row-major genes x n_tests arrays. Checkpoints of `snoop`: 0.0, 0.1, 0.6, 0.75, 0.9, 0.95, 1.0
+ * (diff_exp.rs:137-300); a set cancel flag returns SCANRS_ERR_CANCELLED. */
+
+/* `compute_sseq_params` (diff_exp.rs:458-500). cell_indices (n_sel entries, or NULL for every cell): only those cells get a
+ * size factor, the rest 0. umi_counts (one per selected cell, or NULL): replaces the per-cell totals. Size factors are the
+ * totals over their interpolated median (stat.rs:116). Outputs: size_factors (cols), gene_means, gene_variances, use_genes,
+ * gene_moment_phi, gene_phi (rows each), zeta_hat and delta (one each). */
+int scanrs_sseq_params(scanrs_mat *m, double zeta_quintile, const uint64_t *cell_indices, uint64_t n_sel, const double *umi_counts,
+                       double *size_factors, double *gene_means, double *gene_variances, uint8_t *use_genes, double *gene_moment_phi,
+                       double *zeta_hat, double *delta, double *gene_phi);
+/* `sseq_params_from_moments` (diff_exp.rs:377-456), host only: n entries of mean_g / var_g; n_genes drives the (G-1), (G-2)
+ * denominators of delta. */
+int scanrs_sseq_params_from_moments(const double *mean_g, const double *var_g, uint64_t n, double sum_size_factors, double n_cells,
+                                    double n_genes, double zeta_quintile, uint8_t *use_genes, double *gene_moment_phi, double *zeta_hat,
+                                    double *delta, double *gene_phi);
+/* one pass over the nonzeros: sums[gene * n_groups + group] of the counts (u64, exact); cells_per_group (may be NULL) */
+int scanrs_mat_group_sums(scanrs_mat *m, const int16_t *labels, uint32_t n_groups, uint64_t *sums, uint64_t *cells_per_group);
+/* `sseq_differential_expression` (diff_exp.rs:122-175) from labels. mode 0: each group against all other labelled cells
+ * (n_tests = n_groups; Cell Ranger's per-cluster DE, utils.rs:77-117); mode 1: group 0 against group 1 (n_tests = 1).
+ * size_factors (cols), gene_means, gene_phi, use_genes (rows): the SSeqParams fields. A side's size factor is the sum of
+ * size_factors over its cells. Outputs (rows x n_tests): the DiffExpResult fields sums_in, sums_out, p_values,
+ * adjusted_p_values, log2_fold_change, normalized_mean_in, normalized_mean_out. */
+int scanrs_sseq_de(scanrs_mat *m, const int16_t *labels, uint32_t n_groups, int mode, const double *size_factors, const double *gene_means,
+                   const double *gene_phi, const uint8_t *use_genes, uint64_t big_count, const scanrs_snoop *snoop, uint64_t *sums_in,
+                   uint64_t *sums_out, double *p, double *p_adj, double *log2fc, double *mean_in, double *mean_out);
+/* `sseq_de_from_sums` (diff_exp.rs:177-300) on the device: sums_a / sums_b (n_genes x n_tests), the sides' size factors
+ * sf_a / sf_b (n_tests each). Needs a gfx950 device. Checkpoints 0.75 .. 1.0 only. */
+int scanrs_sseq_de_from_sums(uint64_t n_genes, uint32_t n_tests, const uint64_t *sums_a, const uint64_t *sums_b, const double *sf_a,
+                             const double *sf_b, const double *gene_means, const double *gene_phi, const uint8_t *use_genes,
+                             uint64_t big_count, const scanrs_snoop *snoop, double *p, double *p_adj, double *log2fc, double *mean_in,
+                             double *mean_out);
+/* the shared math on the host (no device needed; the kernels run the same special functions): `nb_exact_test`
+ * (dist.rs:74-118), `nb_asymptotic_test` (:226-257), `log_prob_all` (:259-310, n + 1 values), `adjusted_pvalue_bh` (:22-50,
+ * out[i] belongs to p[i]), and the regularised incomplete beta function and its inverse in p */
+int scanrs_host_nb_exact_test(uint64_t x_a, uint64_t x_b, double sf_a, double sf_b, double mu, double phi, double *p);
+int scanrs_host_nb_asymptotic_test(uint64_t x_a, uint64_t x_b, double sf_a, double sf_b, double mu, double phi, double *p);
+int scanrs_host_nb_log_prob_all(uint64_t n, double sf_a, double sf_b, double mu, double r, double *out);
+int scanrs_host_adjusted_pvalue_bh(const double *p, uint64_t n, double *out);
+int scanrs_host_betainc(double a, double b, double x, double *out);
+int scanrs_host_betaincinv(double a, double b, double p, double *out);
+
 /* ---- 10x HDF5 ingestion (hdf5-io/src/matrix.rs, analysis.rs). Host-side; no device needed.
  * The files are parsed by the library's own reader (csrc/h5lite.cpp) — no libhdf5 dependency. Failures are
  * SCANRS_ERR_IO with the reason in scanrs_last_error(). ------------------------------------------------------------ */

@@ -406,6 +406,72 @@ inline Array2 get_differential_expression(const std::string &analysis_h5, const 
 }
 } // namespace hdf5_io
 
+namespace diff_exp {
+// sSeq differential expression (diff-exp/src/diff_exp.rs): genes = rows, cells = cols of the handle; raw u32 counts
+constexpr uint64_t BIG_COUNT_DEFAULT = 900;
+constexpr double ZETA_QUINTILE_DEFAULT = 0.995;
+struct SSeqParams { // diff_exp.rs:19-40
+    uint32_t num_cells = 0, num_genes = 0;
+    std::vector<double> size_factors, gene_means, gene_variances;
+    std::vector<uint8_t> use_genes;
+    std::vector<double> gene_moment_phi;
+    double zeta_hat = 0.0, delta = 0.0;
+    std::vector<double> gene_phi;
+};
+struct DiffExpResult { // diff_exp.rs:42-65 (genes_tested / common_* are the params' use_genes / gene_means / gene_phi)
+    std::vector<uint64_t> sums_in, sums_out;
+    std::vector<double> normalized_mean_in, normalized_mean_out, p_values, adjusted_p_values, log2_fold_change;
+};
+inline SSeqParams compute_sseq_params(const AdaptiveMat &m, double zeta_quintile = ZETA_QUINTILE_DEFAULT,
+                                      const std::vector<uint64_t> *cell_indices = nullptr, const std::vector<double> *umi_counts = nullptr) {
+    SSeqParams p;
+    const uint64_t g = m.rows(), c = m.cols();
+    p.num_genes = (uint32_t)g;
+    p.num_cells = (uint32_t)(cell_indices ? cell_indices->size() : c);
+    p.size_factors.resize(c);
+    p.gene_means.resize(g);
+    p.gene_variances.resize(g);
+    p.use_genes.resize(g);
+    p.gene_moment_phi.resize(g);
+    p.gene_phi.resize(g);
+    check(scanrs_sseq_params(m.raw(), zeta_quintile, cell_indices ? cell_indices->data() : nullptr, cell_indices ? cell_indices->size() : 0,
+                             umi_counts ? umi_counts->data() : nullptr, p.size_factors.data(), p.gene_means.data(), p.gene_variances.data(),
+                             p.use_genes.data(), p.gene_moment_phi.data(), &p.zeta_hat, &p.delta, p.gene_phi.data()));
+    return p;
+}
+// one result per test: labels per cell (-1 = in no group); mode 0 each group against the rest, mode 1 group 0 against group 1
+inline std::vector<DiffExpResult> sseq_de(const AdaptiveMat &m, const std::vector<int16_t> &labels, uint32_t n_groups, int mode,
+                                          const SSeqParams &p, uint64_t big_count = BIG_COUNT_DEFAULT, Snoop *snoop = nullptr) {
+    const uint64_t g = m.rows();
+    const uint32_t t = mode == 0 ? n_groups : 1;
+    std::vector<uint64_t> si(g * t), so(g * t);
+    std::vector<double> pv(g * t), pa(g * t), l2(g * t), mi(g * t), mo(g * t);
+    scanrs_snoop sn = detail::make_snoop(snoop);
+    check(scanrs_sseq_de(m.raw(), labels.data(), n_groups, mode, p.size_factors.data(), p.gene_means.data(), p.gene_phi.data(), p.use_genes.data(),
+                         big_count, snoop ? &sn : nullptr, si.data(), so.data(), pv.data(), pa.data(), l2.data(), mi.data(), mo.data()));
+    std::vector<DiffExpResult> out(t);
+    for (uint32_t j = 0; j < t; j++) {
+        DiffExpResult &r = out[j];
+        for (uint64_t i = 0; i < g; i++) {
+            const uint64_t o = i * t + j;
+            r.sums_in.push_back(si[o]);
+            r.sums_out.push_back(so[o]);
+            r.p_values.push_back(pv[o]);
+            r.adjusted_p_values.push_back(pa[o]);
+            r.log2_fold_change.push_back(l2[o]);
+            r.normalized_mean_in.push_back(mi[o]);
+            r.normalized_mean_out.push_back(mo[o]);
+        }
+    }
+    return out;
+}
+inline std::vector<uint64_t> group_sums(const AdaptiveMat &m, const std::vector<int16_t> &labels, uint32_t n_groups) { // genes x n_groups
+    std::vector<uint64_t> s(m.rows() * n_groups);
+    check(scanrs_mat_group_sums(m.raw(), labels.data(), n_groups, s.data(), nullptr));
+    return s;
+}
+} // namespace diff_exp
+
 namespace mtx {
 // scan_rs::mtx::load_mtx (scan-rs/src/mtx.rs:10-51): the CSR arrays; `.to_device()` is the AdaptiveMat the reference returns
 inline hdf5_io::FeatureBarcodeMatrix read_mtx(const std::string &path) {

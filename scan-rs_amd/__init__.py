@@ -923,4 +923,13 @@ EXPORTED_SYMBOLS = [
     "scanrs_h5_matrix_shape", "scanrs_h5_matrix_arrays", "scanrs_h5_matrix_n_strings", "scanrs_h5_matrix_string", "scanrs_h5_matrix_removed",
     "scanrs_h5_read_umi_counts", "scanrs_h5_get_clustering_keys", "scanrs_h5_get_clustering", "scanrs_h5_get_differential_expression",
     "scanrs_h5_read_f64", "scanrs_h5_read_strings", "scanrs_h5_member_names", "scanrs_mtx_read", "scanrs_mat_create_from_file",
+    "scanrs_sseq_params", "scanrs_sseq_params_from_moments", "scanrs_mat_group_sums", "scanrs_sseq_de", "scanrs_sseq_de_from_sums",
+    "scanrs_host_nb_exact_test", "scanrs_host_nb_asymptotic_test", "scanrs_host_nb_log_prob_all", "scanrs_host_adjusted_pvalue_bh",
+    "scanrs_host_betainc", "scanrs_host_betaincinv",
 ]
+
+# sSeq differential expression (sseq.py)
+from .sseq import (  # noqa: E402
+    DiffExpResult, SSeqParams, compute_sseq_params, diff_exp_table, group_sums, labels_from_clustering, sseq_de_from_sums, sseq_de_one_vs_rest,
+    sseq_differential_expression, sseq_params_from_moments,
+)

@@ -557,4 +557,46 @@ void allreduce_u64(Storage &st, unsigned long long *d, uint64_t count);
 bool rows_sharded(const scanrs_mat *m);
 bool cols_sharded(const scanrs_mat *m);
 
+// ---- sseq.hip / sseq_host.cpp: sSeq differential expression (diff-exp/src/diff_exp.rs, dist.rs) --------------------------------
+constexpr uint32_t SSEQ_CHUNK_THREADS = 256, SSEQ_TERMS_PER_THREAD = 8, SSEQ_CHUNK = SSEQ_CHUNK_THREADS * SSEQ_TERMS_PER_THREAD;
+constexpr uint32_t SSEQ_MAX_GROUPS = 8192; // one wave's LDS row of u64 group sums fills 64 KB
+struct SseqExactTest {       // one exact test: terms k = 0 .. n, chunks chunk0 .. (next test's chunk0)
+    uint64_t n, xa;
+    double sar, sbr, add_total; // sf_a / φ, sf_b / φ, the constant of log_prob_all
+    uint64_t chunk0, out;       // first chunk; index of the p-value in the output
+};
+struct SseqAsymTest {
+    uint64_t xa, xb;
+    double sf_a, sf_b, mu, phi;
+    uint64_t out;
+};
+uint32_t sseq_max_count(Storage &st, const SparseCopy &cp);
+void launch_sseq_cell_totals(Storage &st, const SparseCopy &cp, bool gene_major, uint64_t n_cells, unsigned long long *d_tot);
+// sums: genes x n_groups; with d_mom also Σ x/sf and Σ (x/sf)² over the labelled cells as 128-bit fixed point (genes x 4 u64)
+void launch_sseq_group_pass(Storage &st, const SparseCopy &cp, bool gene_major, uint64_t n_genes, const int16_t *d_labels, uint32_t n_groups,
+                            unsigned long long *d_sums, const double *d_sf, double scale1, double scale2, unsigned long long *d_mom,
+                            uint32_t *d_bad);
+void launch_sseq_exact(hipStream_t s, const SseqExactTest *d_tests, uint32_t n_tests, uint64_t n_chunks, double *d_obs, double4 *d_part,
+                       double *d_p);
+void launch_sseq_asymptotic(hipStream_t s, const SseqAsymTest *d_tests, uint32_t n_tests, double *d_p);
+// host side (sseq_host.cpp); `cp` is the resident copy, gene_major when its outer vectors are the genes (the view's rows)
+void sseq_params(Storage &st, const SparseCopy &cp, bool gene_major, uint64_t genes, uint64_t cells, double zeta_quintile,
+                 const uint64_t *cell_indices, uint64_t n_sel, const double *umi_counts, double *size_factors, double *gene_means,
+                 double *gene_variances, uint8_t *use_genes, double *gene_moment_phi, double *zeta_hat, double *delta, double *gene_phi);
+void sseq_params_from_moments(const double *mean_g, const double *var_g, uint64_t n, double sum_size_factors, double n_cells, double n_genes,
+                              double zeta_quintile, uint8_t *use_genes, double *gene_moment_phi, double *zeta_hat, double *delta,
+                              double *gene_phi);
+void sseq_group_sums(Storage &st, const SparseCopy &cp, bool gene_major, uint64_t genes, uint64_t cells, const int16_t *labels,
+                     uint32_t n_groups, uint64_t *sums, uint64_t *cells_per_group);
+void sseq_de_matrix(Storage &st, const SparseCopy &cp, bool gene_major, uint64_t genes, uint64_t cells, const int16_t *labels,
+                    uint32_t n_groups, int mode, const double *size_factors, const double *gene_means, const double *gene_phi,
+                    const uint8_t *use_genes, uint64_t big_count, const scanrs_snoop *snoop, uint64_t *sums_in, uint64_t *sums_out, double *p,
+                    double *p_adj, double *log2fc, double *mean_in, double *mean_out);
+// the tests, BH, log2 fold change and normalized means from per-gene sums (genes x n_tests, row-major)
+void sseq_de_sums(hipStream_t s, uint64_t genes, uint32_t n_tests, const uint64_t *sums_a, const uint64_t *sums_b, const double *sf_a,
+                  const double *sf_b, const double *gene_means, const double *gene_phi, const uint8_t *use_genes, uint64_t big_count,
+                  const scanrs_snoop *snoop, double *p, double *p_adj, double *log2fc, double *mean_in, double *mean_out);
+double sseq_host_exact_test(uint64_t xa, uint64_t xb, double sf_a, double sf_b, double mu, double phi);
+void sseq_host_bh(const double *p, uint64_t n, double *out);
+
 } // namespace scanrs

@@ -1,0 +1,354 @@
+// HIP kernels of sSeq differential expression (diff-exp/src/diff_exp.rs, dist.rs) + their launchers. Host logic: sseq_host.cpp.
+//
+//   sseq_gene_major_kernel   one pass over the nonzeros of the gene-major copy: a wave owns a gene, gathers the labels of its
+//                            cells and adds the counts into a per-wave LDS row of n_groups u64 sums (integer LDS atomics);
+//                            optionally Σ x/sf_c and Σ (x/sf_c)² over the labelled cells (the moments of compute_sseq_params)
+//   sseq_cell_major_kernel   the same sums from the cell-major copy: a wave owns a cell (one label), the sums are scattered
+//                            over the genes with u64 global atomics
+//   sseq_cell_totals_kernel  per-cell count totals (size factors) from either copy
+//   sseq_exact_*_kernel      the exact NB test (dist.rs:74-118, 259-310) over a flat list of fixed-size term chunks
+//   sseq_asymptotic_kernel   the beta approximation (dist.rs:226-257), one thread per test
+//
+// No float atomics. The moments are accumulated as 128-bit FIXED-POINT integers (two u64 words, carry counted
+// with an integer atomic): every term x/sf_c is rounded once to a quantum of 2^-E (E chosen per launch from a bound of the
+// sums, so that every sum fits below 2^126), and the integer sum is exact, so the result depends neither on the order in
+// which the waves arrive nor on which copy of the matrix was walked: both orientations give the same bits.
+#include "common.hpp"
+#include "special.hpp"
+
+namespace scanrs {
+
+struct U128 {
+    unsigned long long lo, hi;
+};
+__device__ __forceinline__ U128 to_fixed(double t, double scale) {
+    const double y = t * scale; // scale is a power of two: exact
+    const double hd = floor(y * 5.421010862427522e-20); // 2^-64
+    const double ld = rint(y - hd * 18446744073709551616.0); // exact difference; < 2^64, rounded only below 2^53
+    return U128{(unsigned long long)ld, (unsigned long long)hd};
+}
+__device__ __forceinline__ void add128(U128 &a, U128 b) {
+    a.lo += b.lo;
+    a.hi += b.hi + (a.lo < b.lo ? 1ull : 0ull);
+}
+__device__ __forceinline__ void atomic_add128(unsigned long long *p, U128 b) {
+    const unsigned long long old = atomicAdd(p, b.lo);
+    const unsigned long long carry = old + b.lo < old ? 1ull : 0ull;
+    if (b.hi + carry) atomicAdd(p + 1, b.hi + carry);
+}
+__device__ __forceinline__ U128 shfl_down128(U128 v, int off) {
+    return U128{(unsigned long long)__shfl_down((long long)v.lo, off), (unsigned long long)__shfl_down((long long)v.hi, off)};
+}
+
+// d_mom (rows x 4 u64): [lo, hi] of Σ x/sf, [lo, hi] of Σ (x/sf)²; d_bad: per gene, a term was not finite (sf = 0 with x > 0)
+template <bool MOM>
+__global__ __launch_bounds__(256) void sseq_gene_major_kernel(const uint64_t *__restrict__ indptr, const uint32_t *__restrict__ indices,
+                                                              const uint32_t *__restrict__ values, uint64_t n_genes,
+                                                              const int16_t *__restrict__ labels, uint32_t n_groups,
+                                                              unsigned long long *__restrict__ sums, const double *__restrict__ sf,
+                                                              double scale1, double scale2, unsigned long long *__restrict__ mom,
+                                                              uint32_t *__restrict__ bad) {
+    extern __shared__ unsigned long long gm_acc[]; // [wave][group]
+    const uint32_t lane = threadIdx.x & 63u, wave = threadIdx.x >> 6, n_waves = blockDim.x >> 6;
+    unsigned long long *acc = gm_acc + (size_t)wave * n_groups;
+    for (uint64_t g0 = (uint64_t)blockIdx.x * n_waves; g0 < n_genes; g0 += (uint64_t)gridDim.x * n_waves) {
+        const uint64_t g = g0 + wave;
+        for (uint32_t j = lane; j < n_groups; j += 64) acc[j] = 0ull;
+        __syncthreads();
+        U128 s1{0, 0}, s2{0, 0};
+        uint32_t nonfinite = 0;
+        if (g < n_genes) {
+            const uint64_t p0 = indptr[g], p1 = indptr[g + 1];
+            for (uint64_t p = p0 + lane; p < p1; p += 64) {
+                const uint32_t c = indices[p];
+                const int l = labels[c];
+                if (l < 0) continue;
+                const uint32_t x = values[p];
+                atomicAdd(&acc[l], (unsigned long long)x);
+                if (MOM) {
+                    const double t = (double)x / sf[c];
+                    if (!isfinite(t)) {
+                        nonfinite = 1;
+                        continue;
+                    }
+                    add128(s1, to_fixed(t, scale1));
+                    add128(s2, to_fixed(t * t, scale2));
+                }
+            }
+        }
+        __syncthreads();
+        if (g < n_genes) {
+            for (uint32_t j = lane; j < n_groups; j += 64) sums[g * n_groups + j] = acc[j];
+            if (MOM) {
+                for (int off = 32; off > 0; off >>= 1) {
+                    add128(s1, shfl_down128(s1, off));
+                    add128(s2, shfl_down128(s2, off));
+                    nonfinite |= (uint32_t)__shfl_down((int)nonfinite, off);
+                }
+                if (lane == 0) {
+                    mom[g * 4 + 0] = s1.lo;
+                    mom[g * 4 + 1] = s1.hi;
+                    mom[g * 4 + 2] = s2.lo;
+                    mom[g * 4 + 3] = s2.hi;
+                    bad[g] = nonfinite;
+                }
+            }
+        }
+    }
+}
+
+// sums and mom are zeroed by the launcher
+template <bool MOM>
+__global__ __launch_bounds__(256) void sseq_cell_major_kernel(const uint64_t *__restrict__ indptr, const uint32_t *__restrict__ indices,
+                                                              const uint32_t *__restrict__ values, uint64_t n_cells,
+                                                              const int16_t *__restrict__ labels, uint32_t n_groups,
+                                                              unsigned long long *__restrict__ sums, const double *__restrict__ sf,
+                                                              double scale1, double scale2, unsigned long long *__restrict__ mom,
+                                                              uint32_t *__restrict__ bad) {
+    const uint32_t lane = threadIdx.x & 63u, n_waves = blockDim.x >> 6;
+    for (uint64_t c = (uint64_t)blockIdx.x * n_waves + (threadIdx.x >> 6); c < n_cells; c += (uint64_t)gridDim.x * n_waves) {
+        const int l = labels[c];
+        if (l < 0) continue; // uniform over the wave
+        const double sfc = MOM ? sf[c] : 1.0;
+        const uint64_t p0 = indptr[c], p1 = indptr[c + 1];
+        for (uint64_t p = p0 + lane; p < p1; p += 64) {
+            const uint32_t g = indices[p], x = values[p];
+            atomicAdd(&sums[(uint64_t)g * n_groups + l], (unsigned long long)x);
+            if (MOM) {
+                const double t = (double)x / sfc;
+                if (!isfinite(t)) {
+                    bad[g] = 1u;
+                    continue;
+                }
+                atomic_add128(&mom[(uint64_t)g * 4 + 0], to_fixed(t, scale1));
+                atomic_add128(&mom[(uint64_t)g * 4 + 2], to_fixed(t * t, scale2));
+            }
+        }
+    }
+}
+
+// per-cell totals: from the cell-major copy a wave sums its cell; from the gene-major copy the counts are scattered (u64 atomics)
+__global__ __launch_bounds__(256) void sseq_cell_totals_kernel(const uint64_t *__restrict__ indptr, const uint32_t *__restrict__ indices,
+                                                               const uint32_t *__restrict__ values, uint64_t n_outer, int outer_is_cell,
+                                                               unsigned long long *__restrict__ tot) {
+    const uint32_t lane = threadIdx.x & 63u, n_waves = blockDim.x >> 6;
+    for (uint64_t o = (uint64_t)blockIdx.x * n_waves + (threadIdx.x >> 6); o < n_outer; o += (uint64_t)gridDim.x * n_waves) {
+        const uint64_t p0 = indptr[o], p1 = indptr[o + 1];
+        unsigned long long s = 0;
+        for (uint64_t p = p0 + lane; p < p1; p += 64) {
+            if (outer_is_cell)
+                s += values[p];
+            else
+                atomicAdd(&tot[indices[p]], (unsigned long long)values[p]);
+        }
+        if (outer_is_cell) {
+            for (int off = 32; off > 0; off >>= 1) s += (unsigned long long)__shfl_down((long long)s, off);
+            if (lane == 0) tot[o] = s;
+        }
+    }
+}
+
+__global__ void sseq_max_u32_kernel(const uint32_t *__restrict__ v, uint64_t n, uint32_t *__restrict__ out) {
+    uint32_t m = 0;
+    for (uint64_t i = (uint64_t)blockIdx.x * blockDim.x + threadIdx.x; i < n; i += (uint64_t)gridDim.x * blockDim.x) m = max(m, v[i]);
+    for (int off = 32; off > 0; off >>= 1) m = max(m, (uint32_t)__shfl_xor((int)m, off));
+    if ((threadIdx.x & 63u) == 0) atomicMax(out, m);
+}
+
+// ---- exact test --------------------------------------------------------------------------------------------------------------
+// The terms k = 0 .. n of every test are cut into chunks of SSEQ_CHUNK; chunk c of the launch belongs to the test whose
+// chunk0 <= c < next chunk0. A workgroup computes one chunk's (max, Σ exp(t - max)) for all terms and for the extreme terms
+// (t <= the observed term) with a fixed reduction tree; the combine kernel folds a test's chunks in chunk order. A test's
+// result depends only on its own inputs: not on the grid, nor on the other tests of the launch.
+__device__ __forceinline__ double wave_max(double v) {
+    for (int off = 32; off > 0; off >>= 1) v = fmax(v, __shfl_xor(v, off));
+    return v;
+}
+__device__ __forceinline__ double wave_sum(double v) {
+    for (int off = 32; off > 0; off >>= 1) v += __shfl_xor(v, off);
+    return v;
+}
+
+__global__ void sseq_exact_obs_kernel(const SseqExactTest *__restrict__ tests, uint32_t n_tests, double *__restrict__ obs) {
+    const uint32_t i = blockIdx.x * blockDim.x + threadIdx.x;
+    if (i >= n_tests) return;
+    const SseqExactTest t = tests[i];
+    obs[i] = special::nb_term(t.xa, t.n, t.sar, t.sbr, t.add_total);
+}
+
+__global__ __launch_bounds__(SSEQ_CHUNK_THREADS) void sseq_exact_chunk_kernel(const SseqExactTest *__restrict__ tests, uint32_t n_tests,
+                                                                               const double *__restrict__ obs, uint64_t n_chunks,
+                                                                               double4 *__restrict__ part) {
+    __shared__ double red[SSEQ_CHUNK_THREADS / 64][2];
+    const uint32_t tid = threadIdx.x, lane = tid & 63u, wave = tid >> 6;
+    for (uint64_t c = blockIdx.x; c < n_chunks; c += gridDim.x) {
+        // the test owning chunk c: last i with chunk0 <= c
+        uint32_t lo = 0, hi = n_tests;
+        while (hi - lo > 1) {
+            const uint32_t mid = (lo + hi) >> 1;
+            if (tests[mid].chunk0 <= c)
+                lo = mid;
+            else
+                hi = mid;
+        }
+        const SseqExactTest t = tests[lo];
+        const double o = obs[lo];
+        const uint64_t k0 = (c - t.chunk0) * SSEQ_CHUNK;
+        double v[SSEQ_TERMS_PER_THREAD];
+        double m_all = -INFINITY, m_ext = -INFINITY;
+#pragma unroll
+        for (uint32_t j = 0; j < SSEQ_TERMS_PER_THREAD; j++) {
+            const uint64_t k = k0 + (uint64_t)j * SSEQ_CHUNK_THREADS + tid;
+            v[j] = k <= t.n ? special::nb_term(k, t.n, t.sar, t.sbr, t.add_total) : NAN;
+            if (k <= t.n) {
+                m_all = fmax(m_all, v[j]);
+                if (v[j] <= o) m_ext = fmax(m_ext, v[j]);
+            }
+        }
+        m_all = wave_max(m_all);
+        m_ext = wave_max(m_ext);
+        if (lane == 0) {
+            red[wave][0] = m_all;
+            red[wave][1] = m_ext;
+        }
+        __syncthreads();
+        m_all = red[0][0];
+        m_ext = red[0][1];
+        for (uint32_t w = 1; w < SSEQ_CHUNK_THREADS / 64; w++) {
+            m_all = fmax(m_all, red[w][0]);
+            m_ext = fmax(m_ext, red[w][1]);
+        }
+        __syncthreads();
+        double s_all = 0.0, s_ext = 0.0;
+#pragma unroll
+        for (uint32_t j = 0; j < SSEQ_TERMS_PER_THREAD; j++) {
+            const uint64_t k = k0 + (uint64_t)j * SSEQ_CHUNK_THREADS + tid;
+            if (k <= t.n) {
+                s_all += exp(v[j] - m_all);
+                if (v[j] <= o) s_ext += exp(v[j] - m_ext);
+            }
+        }
+        s_all = wave_sum(s_all);
+        s_ext = wave_sum(s_ext);
+        if (lane == 0) {
+            red[wave][0] = s_all;
+            red[wave][1] = s_ext;
+        }
+        __syncthreads();
+        if (tid == 0) {
+            s_all = red[0][0];
+            s_ext = red[0][1];
+            for (uint32_t w = 1; w < SSEQ_CHUNK_THREADS / 64; w++) {
+                s_all += red[w][0];
+                s_ext += red[w][1];
+            }
+            part[c] = make_double4(m_all, s_all, m_ext, s_ext);
+        }
+        __syncthreads();
+    }
+}
+
+// log-sum-exp of a test's chunks, folded in chunk order; p = exp(lse_ext - lse_all) (dist.rs:114-117)
+__global__ void sseq_exact_combine_kernel(const SseqExactTest *__restrict__ tests, uint32_t n_tests, uint64_t n_chunks,
+                                          const double4 *__restrict__ part, double *__restrict__ p_out) {
+    const uint32_t i = blockIdx.x * blockDim.x + threadIdx.x;
+    if (i >= n_tests) return;
+    const uint64_t c0 = tests[i].chunk0, c1 = i + 1 < n_tests ? tests[i + 1].chunk0 : n_chunks;
+    double ma = -INFINITY, sa = 0.0, me = -INFINITY, se = 0.0;
+    for (uint64_t c = c0; c < c1; c++) {
+        const double4 q = part[c];
+        if (q.y > 0.0) {
+            const double m = fmax(ma, q.x);
+            sa = (sa > 0.0 ? sa * exp(ma - m) : 0.0) + q.y * exp(q.x - m);
+            ma = m;
+        }
+        if (q.w > 0.0) {
+            const double m = fmax(me, q.z);
+            se = (se > 0.0 ? se * exp(me - m) : 0.0) + q.w * exp(q.z - m);
+            me = m;
+        }
+    }
+    const double lse_all = log(sa) + ma, lse_ext = log(se) + me;
+    p_out[tests[i].out] = exp(lse_ext - lse_all);
+}
+
+__global__ void sseq_asymptotic_kernel(const SseqAsymTest *__restrict__ tests, uint32_t n_tests, double *__restrict__ p_out) {
+    const uint32_t i = blockIdx.x * blockDim.x + threadIdx.x;
+    if (i >= n_tests) return;
+    const SseqAsymTest t = tests[i];
+    p_out[t.out] = special::nb_asymptotic(t.xa, t.xb, t.sf_a, t.sf_b, t.mu, t.phi);
+}
+
+// ---- launchers -----------------------------------------------------------------------------------------------------------------
+static inline uint32_t blocks_for(uint64_t items, uint32_t per_block, uint32_t cap) {
+    return (uint32_t)std::max<uint64_t>(1, std::min<uint64_t>(cap, (items + per_block - 1) / per_block));
+}
+
+uint32_t sseq_max_count(Storage &st, const SparseCopy &cp) {
+    uint32_t *d = st.scratch.get<uint32_t>("sseq_max", 1);
+    SCANRS_HIP(hipMemsetAsync(d, 0, 4, st.stream));
+    if (cp.nnz) hipLaunchKernelGGL(sseq_max_u32_kernel, dim3(blocks_for(cp.nnz, 256, 4096)), dim3(256), 0, st.stream, cp.values.p, cp.nnz, d);
+    SCANRS_HIP(hipGetLastError());
+    return d2h_value(d, st.stream, __func__, __FILE__, __LINE__);
+}
+
+void launch_sseq_cell_totals(Storage &st, const SparseCopy &cp, bool gene_major, uint64_t n_cells, unsigned long long *d_tot) {
+    SCANRS_HIP(hipMemsetAsync(d_tot, 0, std::max<uint64_t>(1, n_cells) * 8, st.stream));
+    if (cp.n_outer)
+        hipLaunchKernelGGL(sseq_cell_totals_kernel, dim3(blocks_for(cp.n_outer, 4, 16384)), dim3(256), 0, st.stream, cp.indptr.p, cp.indices.p,
+                           cp.values.p, cp.n_outer, gene_major ? 0 : 1, d_tot);
+    SCANRS_HIP(hipGetLastError());
+}
+
+void launch_sseq_group_pass(Storage &st, const SparseCopy &cp, bool gene_major, uint64_t n_genes, const int16_t *d_labels, uint32_t n_groups,
+                            unsigned long long *d_sums, const double *d_sf, double scale1, double scale2, unsigned long long *d_mom,
+                            uint32_t *d_bad) {
+    const bool mom = d_mom != nullptr;
+    if (mom) {
+        SCANRS_HIP(hipMemsetAsync(d_mom, 0, std::max<uint64_t>(1, n_genes) * 32, st.stream));
+        SCANRS_HIP(hipMemsetAsync(d_bad, 0, std::max<uint64_t>(1, n_genes) * 4, st.stream));
+    }
+    if (gene_major) {
+        // a wave's LDS row holds n_groups u64: up to 4 waves per workgroup within 64 KB
+        const uint32_t waves = (uint32_t)std::max<uint64_t>(1, std::min<uint64_t>(4, 8192 / std::max<uint32_t>(1, n_groups)));
+        const size_t lds = (size_t)waves * n_groups * 8;
+        const dim3 grid(blocks_for(n_genes, waves, 16384)), block(64 * waves);
+        if (mom)
+            hipLaunchKernelGGL(sseq_gene_major_kernel<true>, grid, block, lds, st.stream, cp.indptr.p, cp.indices.p, cp.values.p, n_genes, d_labels,
+                               n_groups, d_sums, d_sf, scale1, scale2, d_mom, d_bad);
+        else
+            hipLaunchKernelGGL(sseq_gene_major_kernel<false>, grid, block, lds, st.stream, cp.indptr.p, cp.indices.p, cp.values.p, n_genes, d_labels,
+                               n_groups, d_sums, d_sf, scale1, scale2, d_mom, d_bad);
+    } else {
+        SCANRS_HIP(hipMemsetAsync(d_sums, 0, std::max<uint64_t>(1, n_genes * n_groups) * 8, st.stream));
+        const dim3 grid(blocks_for(cp.n_outer, 4, 16384)), block(256);
+        if (cp.n_outer) {
+            if (mom)
+                hipLaunchKernelGGL(sseq_cell_major_kernel<true>, grid, block, 0, st.stream, cp.indptr.p, cp.indices.p, cp.values.p, cp.n_outer, d_labels,
+                                   n_groups, d_sums, d_sf, scale1, scale2, d_mom, d_bad);
+            else
+                hipLaunchKernelGGL(sseq_cell_major_kernel<false>, grid, block, 0, st.stream, cp.indptr.p, cp.indices.p, cp.values.p, cp.n_outer,
+                                   d_labels, n_groups, d_sums, d_sf, scale1, scale2, d_mom, d_bad);
+        }
+    }
+    SCANRS_HIP(hipGetLastError());
+}
+
+void launch_sseq_exact(hipStream_t s, const SseqExactTest *d_tests, uint32_t n_tests, uint64_t n_chunks, double *d_obs, double4 *d_part,
+                       double *d_p) {
+    if (!n_tests) return;
+    hipLaunchKernelGGL(sseq_exact_obs_kernel, dim3((n_tests + 255) / 256), dim3(256), 0, s, d_tests, n_tests, d_obs);
+    hipLaunchKernelGGL(sseq_exact_chunk_kernel, dim3(blocks_for(n_chunks, 1, 65536)), dim3(SSEQ_CHUNK_THREADS), 0, s, d_tests, n_tests,
+                       (const double *)d_obs, n_chunks, d_part);
+    hipLaunchKernelGGL(sseq_exact_combine_kernel, dim3((n_tests + 63) / 64), dim3(64), 0, s, d_tests, n_tests, n_chunks,
+                       (const double4 *)d_part, d_p);
+    SCANRS_HIP(hipGetLastError());
+}
+
+void launch_sseq_asymptotic(hipStream_t s, const SseqAsymTest *d_tests, uint32_t n_tests, double *d_p) {
+    if (!n_tests) return;
+    hipLaunchKernelGGL(sseq_asymptotic_kernel, dim3((n_tests + 63) / 64), dim3(64), 0, s, d_tests, n_tests, d_p);
+    SCANRS_HIP(hipGetLastError());
+}
+
+} // namespace scanrs

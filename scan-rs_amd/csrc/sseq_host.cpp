@@ -1,0 +1,374 @@
+// Host logic of sSeq differential expression (diff-exp/src/diff_exp.rs, dist.rs, stat.rs): size factors, the parameters from
+// the moments, the split of the tests between the exact and the asymptotic branch, BH, log2 fold change and normalized means.
+// The passes over the nonzeros and the tests themselves run on the device (sseq.hip).
+#include "common.hpp"
+#include "special.hpp"
+
+#include <algorithm>
+#include <cmath>
+#include <cstring>
+#include <vector>
+
+// the reference's host arithmetic is not contracted: fused multiply-adds here would move the parameters off its bits
+#pragma clang fp contract(off)
+
+namespace scanrs {
+
+static void sseq_progress(const scanrs_snoop *sn, double p) {
+    // CancelProgress::set_progress_check (snoop/src/lib.rs:45-57)
+    if (!sn) return;
+    if (sn->cancel && __atomic_load_n(sn->cancel, __ATOMIC_RELAXED)) fail(SCANRS_ERR_CANCELLED, "cancellation error");
+    if (sn->progress) sn->progress(sn->ctx, p);
+}
+
+template <typename T>
+static void h2d(T *d, const T *h, size_t n, hipStream_t s) {
+    if (n) SCANRS_HIP(hipMemcpyAsync(d, h, n * sizeof(T), hipMemcpyHostToDevice, s));
+}
+
+// ---- stat.rs ----------------------------------------------------------------------------------------------------------------
+// percentile_of_sorted (stat.rs:140-162): linear interpolation between the neighbouring ranks
+static double percentile_of_sorted(const std::vector<double> &s, double pct) {
+    if (s.empty()) fail(SCANRS_ERR_ARGUMENT, "percentile of an empty list");
+    if (s.size() == 1) return s[0];
+    if (pct == 100.0) return s.back();
+    const double length = (double)(s.size() - 1);
+    const double rank = (pct / 100.0) * length;
+    const double l_rank = std::floor(rank);
+    const double d = rank - l_rank;
+    const size_t n = (size_t)l_rank;
+    return s[n] + (s[n + 1] - s[n]) * d;
+}
+static double percentile(std::vector<double> v, double pct) {
+    std::stable_sort(v.begin(), v.end(), [](double a, double b) { return a < b; });
+    return percentile_of_sorted(v, pct);
+}
+// Statistics::sum (stat.rs:49-80): the partials of Shewchuk's exact summation, added up in order at the end
+static double exact_sum(const std::vector<double> &v) {
+    std::vector<double> partials;
+    for (double x0 : v) {
+        double x = x0;
+        size_t j = 0;
+        for (size_t i = 0; i < partials.size(); i++) {
+            double y = partials[i];
+            if (std::fabs(x) < std::fabs(y)) std::swap(x, y);
+            const double hi = x + y;
+            const double lo = y - (hi - x);
+            if (lo != 0.0) partials[j++] = lo;
+            x = hi;
+        }
+        if (j >= partials.size()) {
+            partials.push_back(x);
+        } else {
+            partials[j] = x;
+            partials.resize(j + 1);
+        }
+    }
+    double s = 0.0;
+    for (double p : partials) s += p;
+    return s;
+}
+
+// ---- dist.rs (host forms; the device runs the same special.hpp) ----------------------------------------------------------------
+double sseq_host_exact_test(uint64_t xa, uint64_t xb, double sf_a, double sf_b, double mu, double phi) {
+    if (xa + xb == 0) return 1.0;
+    if (phi == 0.0) return 1.0;
+    if (sf_a == 0.0 || sf_b == 0.0) return 1.0;
+    const uint64_t n = xa + xb;
+    const double r = 1.0 / phi, sar = sf_a * r, sbr = sf_b * r;
+    const double add = special::nb_add_total(n, sf_a, sf_b, mu, r);
+    const double obs = special::nb_term(xa, n, sar, sbr, add);
+    std::vector<double> t(n + 1);
+    double max_all = -INFINITY, max_ext = -INFINITY;
+    for (uint64_t k = 0; k <= n; k++) {
+        t[k] = special::nb_term(k, n, sar, sbr, add);
+        if (t[k] <= obs) max_ext = std::max(max_ext, t[k]);
+        max_all = std::max(max_all, t[k]);
+    }
+    double sum_all = 0.0, sum_ext = 0.0;
+    for (double x : t) {
+        if (x <= obs) sum_ext += std::exp(x - max_ext);
+        sum_all += std::exp(x - max_all);
+    }
+    return std::exp((std::log(sum_ext) + max_ext) - (std::log(sum_all) + max_all));
+}
+
+// adjusted_pvalue_bh (dist.rs:22-50): descending, NaNs in front (stable), q = min(1, running min of p n/(n - rank))
+void sseq_host_bh(const double *p, uint64_t n, double *out) {
+    std::vector<uint64_t> ord(n);
+    for (uint64_t i = 0; i < n; i++) ord[i] = i;
+    std::stable_sort(ord.begin(), ord.end(), [&](uint64_t ia, uint64_t ib) {
+        const double a = p[ia], b = p[ib];
+        if (std::isnan(a) || std::isnan(b)) return std::isnan(a) && !std::isnan(b);
+        return a > b;
+    });
+    const double len = (double)n;
+    double mn = std::numeric_limits<double>::max();
+    for (uint64_t idx = 0; idx < n; idx++) {
+        double v = p[ord[idx]] * (len / (len - (double)idx));
+        if (v < mn) mn = v;
+        out[ord[idx]] = std::min(mn, 1.0);
+    }
+}
+
+// ---- diff_exp.rs:377-456 ------------------------------------------------------------------------------------------------------
+void sseq_params_from_moments(const double *mean_g, const double *var_g, uint64_t n, double sum_size_factors, double n_cells, double n_genes,
+                              double zeta_quintile, uint8_t *use_genes, double *gene_moment_phi, double *zeta_hat, double *delta,
+                              double *gene_phi) {
+    std::vector<double> used;
+    for (uint64_t i = 0; i < n; i++) {
+        use_genes[i] = var_g[i] > 0.0;
+        double res = 0.0;
+        if (use_genes[i]) {
+            res = std::max(0.0, (n_cells * var_g[i] - mean_g[i] * sum_size_factors) / (mean_g[i] * mean_g[i] * sum_size_factors));
+            used.push_back(res);
+        }
+        gene_moment_phi[i] = res;
+    }
+    double zh = 0.0, dl = 0.0;
+    if (!used.empty()) {
+        zh = percentile(used, 100.0 * zeta_quintile);
+        const double mean_phi = exact_sum(used) / (double)used.size();
+        double a = 0.0, b = 0.0;
+        for (double x : used) a += (x - mean_phi) * (x - mean_phi);
+        for (double x : used) b += (x - zh) * (x - zh);
+        dl = (a / (n_genes - 1.0)) / (b / (n_genes - 2.0));
+    }
+    bool cond = false;
+    for (double x : used) cond = cond || x > 0.0;
+    for (uint64_t i = 0; i < n; i++) gene_phi[i] = (cond && var_g[i] > 0.0) ? (1.0 - dl) * gene_moment_phi[i] + dl * zh : 0.0;
+    *zeta_hat = zh;
+    *delta = dl;
+}
+
+// ---- the group pass -------------------------------------------------------------------------------------------------------------
+static void check_labels(const int16_t *labels, uint64_t cells, uint32_t n_groups) {
+    if (n_groups == 0 || n_groups > SSEQ_MAX_GROUPS) fail(SCANRS_ERR_ARGUMENT, "n_groups must be in 1 .. %u", SSEQ_MAX_GROUPS);
+    for (uint64_t c = 0; c < cells; c++)
+        if (labels[c] < -1 || labels[c] >= (int)n_groups) fail(SCANRS_ERR_ARGUMENT, "label %d of cell %llu is outside -1 .. n_groups - 1", (int)labels[c], (unsigned long long)c);
+}
+
+static double fixed_scale(double bound) {
+    // a power of two with bound * scale < 2^124 (sums of up to 2^124 fit the 128-bit accumulators with room for the rounding)
+    if (!(bound > 0.0) || !std::isfinite(bound)) return 1.0;
+    return std::ldexp(1.0, 124 - std::ilogb(bound) - 1);
+}
+static double from_fixed(const unsigned long long *w, double scale) {
+    return ((double)w[1] * 18446744073709551616.0 + (double)w[0]) / scale;
+}
+
+void sseq_group_sums(Storage &st, const SparseCopy &cp, bool gene_major, uint64_t genes, uint64_t cells, const int16_t *labels,
+                     uint32_t n_groups, uint64_t *sums, uint64_t *cells_per_group) {
+    check_labels(labels, cells, n_groups);
+    int16_t *d_lab = st.scratch.get<int16_t>("sseq_labels", std::max<uint64_t>(1, cells));
+    unsigned long long *d_sums = st.scratch.get<unsigned long long>("sseq_sums", std::max<uint64_t>(1, genes * n_groups));
+    h2d(d_lab, labels, cells, st.stream);
+    launch_sseq_group_pass(st, cp, gene_major, genes, d_lab, n_groups, d_sums, nullptr, 1.0, 1.0, nullptr, nullptr);
+    if (genes) SCANRS_D2H(sums, d_sums, genes * n_groups * 8, st.stream);
+    SCANRS_SYNC(st.stream);
+    if (cells_per_group) {
+        std::fill(cells_per_group, cells_per_group + n_groups, 0);
+        for (uint64_t c = 0; c < cells; c++)
+            if (labels[c] >= 0) cells_per_group[labels[c]]++;
+    }
+}
+
+// ---- compute_sseq_params (diff_exp.rs:458-500) ----------------------------------------------------------------------------------
+void sseq_params(Storage &st, const SparseCopy &cp, bool gene_major, uint64_t genes, uint64_t cells, double zeta_quintile,
+                 const uint64_t *cell_indices, uint64_t n_sel, const double *umi_counts, double *size_factors, double *gene_means,
+                 double *gene_variances, uint8_t *use_genes, double *gene_moment_phi, double *zeta_hat, double *delta, double *gene_phi) {
+    if (cell_indices)
+        for (uint64_t i = 0; i < n_sel; i++)
+            if (cell_indices[i] >= cells) fail(SCANRS_ERR_ARGUMENT, "cell index %llu out of range", (unsigned long long)cell_indices[i]);
+    const uint64_t m = cell_indices ? n_sel : cells;
+    if (m == 0) fail(SCANRS_ERR_ARGUMENT, "no cells");
+    // size_factors (diff_exp.rs:314-332): per-cell totals (or umi_counts, one per selected cell) over their interpolated median
+    std::vector<double> counts(m);
+    if (umi_counts) {
+        for (uint64_t i = 0; i < m; i++) counts[i] = umi_counts[i];
+    } else {
+        unsigned long long *d_tot = st.scratch.get<unsigned long long>("sseq_totals", std::max<uint64_t>(1, cells));
+        launch_sseq_cell_totals(st, cp, gene_major, cells, d_tot);
+        std::vector<unsigned long long> tot(cells);
+        if (cells) SCANRS_D2H(tot.data(), d_tot, cells * 8, st.stream);
+        SCANRS_SYNC(st.stream);
+        for (uint64_t i = 0; i < m; i++) counts[i] = (double)tot[cell_indices ? cell_indices[i] : i];
+    }
+    const double median = percentile(counts, 50.0);
+    std::vector<double> sf(cells, 0.0);
+    for (uint64_t i = 0; i < m; i++) sf[cell_indices ? cell_indices[i] : i] = counts[i] / median;
+    // the moments of the size-normalized matrix (SizeNormalized: NaN factors read as 0) over the selected cells
+    std::vector<int16_t> lab(cells, cell_indices ? (int16_t)-1 : (int16_t)0);
+    if (cell_indices)
+        for (uint64_t i = 0; i < n_sel; i++) lab[cell_indices[i]] = 0;
+    std::vector<double> sf_dev(cells);
+    double max_inv = 0.0;
+    for (uint64_t c = 0; c < cells; c++) {
+        sf_dev[c] = std::isnan(sf[c]) ? 0.0 : sf[c];
+        if (lab[c] == 0 && sf_dev[c] > 0.0) max_inv = std::max(max_inv, 1.0 / sf_dev[c]);
+    }
+    const double max_count = (double)sseq_max_count(st, cp);
+    const double b1 = (double)m * max_count * max_inv;
+    const double scale1 = fixed_scale(b1), scale2 = fixed_scale(b1 * max_count * max_inv);
+    int16_t *d_lab = st.scratch.get<int16_t>("sseq_labels", std::max<uint64_t>(1, cells));
+    double *d_sf = st.scratch.get<double>("sseq_sf", std::max<uint64_t>(1, cells));
+    unsigned long long *d_sums = st.scratch.get<unsigned long long>("sseq_sums", std::max<uint64_t>(1, genes));
+    unsigned long long *d_mom = st.scratch.get<unsigned long long>("sseq_mom", std::max<uint64_t>(1, genes * 4));
+    uint32_t *d_bad = st.scratch.get<uint32_t>("sseq_bad", std::max<uint64_t>(1, genes));
+    h2d(d_lab, lab.data(), cells, st.stream);
+    h2d(d_sf, sf_dev.data(), cells, st.stream);
+    launch_sseq_group_pass(st, cp, gene_major, genes, d_lab, 1, d_sums, d_sf, scale1, scale2, d_mom, d_bad);
+    std::vector<unsigned long long> mom(genes * 4);
+    std::vector<uint32_t> bad(genes);
+    if (genes) {
+        SCANRS_D2H(mom.data(), d_mom, genes * 32, st.stream);
+        SCANRS_D2H(bad.data(), d_bad, genes * 4, st.stream);
+    }
+    SCANRS_SYNC(st.stream);
+    const double md = (double)m;
+    std::vector<double> mean(genes), var(genes);
+    for (uint64_t g = 0; g < genes; g++) {
+        // V[X] = E[X^2] - E[X]^2 (sqz/src/mat.rs:333-380)
+        mean[g] = from_fixed(&mom[g * 4], scale1) / md;
+        var[g] = from_fixed(&mom[g * 4 + 2], scale2) / md - mean[g] * mean[g];
+        if (bad[g]) {
+            mean[g] = INFINITY;
+            var[g] = NAN;
+        }
+    }
+    double sum_sf = 0.0;
+    for (double v : sf)
+        if (v != 0.0) sum_sf += 1.0 / v;
+    sseq_params_from_moments(mean.data(), var.data(), genes, sum_sf, md, (double)genes, zeta_quintile, use_genes, gene_moment_phi, zeta_hat,
+                             delta, gene_phi);
+    memcpy(size_factors, sf.data(), cells * 8);
+    memcpy(gene_means, mean.data(), genes * 8);
+    memcpy(gene_variances, var.data(), genes * 8);
+}
+
+// ---- sseq_de_from_sums_with_cancellation (diff_exp.rs:190-300) ------------------------------------------------------------------
+void sseq_de_sums(hipStream_t s, uint64_t genes, uint32_t n_tests, const uint64_t *sums_a, const uint64_t *sums_b, const double *sf_a,
+                  const double *sf_b, const double *gene_means, const double *gene_phi, const uint8_t *use_genes, uint64_t big_count,
+                  const scanrs_snoop *snoop, double *p, double *p_adj, double *log2fc, double *mean_in, double *mean_out) {
+    const uint64_t total = genes * n_tests;
+    std::vector<SseqExactTest> ex;
+    std::vector<SseqAsymTest> as;
+    uint64_t n_chunks = 0;
+    for (uint64_t g = 0; g < genes; g++) {
+        for (uint32_t j = 0; j < n_tests; j++) {
+            const uint64_t o = g * n_tests + j, xa = sums_a[o], xb = sums_b[o];
+            const double fa = sf_a[j], fb = sf_b[j], mu = gene_means[g], phi = gene_phi[g];
+            if (use_genes[g] && xa > big_count && xb > big_count) {
+                as.push_back(SseqAsymTest{xa, xb, fa, fb, mu, phi, o});
+                continue;
+            }
+            // nb_exact_test's early returns (dist.rs:76-86)
+            if (xa + xb == 0 || phi == 0.0 || fa == 0.0 || fb == 0.0) {
+                p[o] = 1.0;
+                continue;
+            }
+            const uint64_t n = xa + xb;
+            const double r = 1.0 / phi;
+            ex.push_back(SseqExactTest{n, xa, fa * r, fb * r, special::nb_add_total(n, fa, fb, mu, r), n_chunks, o});
+            n_chunks += (n + SSEQ_CHUNK) / SSEQ_CHUNK; // n + 1 terms
+        }
+    }
+    if (ex.size() > 0xFFFFFFFFull || as.size() > 0xFFFFFFFFull) fail(SCANRS_ERR_ARGUMENT, "too many tests in one call");
+    if (!ex.empty() || !as.empty()) {
+        DevBuf<double> d_p(total);
+        DevBuf<SseqExactTest> d_ex(std::max<size_t>(1, ex.size()));
+        DevBuf<SseqAsymTest> d_as(std::max<size_t>(1, as.size()));
+        DevBuf<double> d_obs(std::max<size_t>(1, ex.size()));
+        DevBuf<double4> d_part(std::max<uint64_t>(1, n_chunks));
+        h2d(d_ex.p, ex.data(), ex.size(), s);
+        h2d(d_as.p, as.data(), as.size(), s);
+        launch_sseq_exact(s, d_ex.p, (uint32_t)ex.size(), n_chunks, d_obs.p, d_part.p, d_p.p);
+        launch_sseq_asymptotic(s, d_as.p, (uint32_t)as.size(), d_p.p);
+        std::vector<double> pd(total);
+        SCANRS_D2H(pd.data(), d_p.p, total * 8, s);
+        SCANRS_SYNC(s);
+        for (const auto &t : ex) p[t.out] = pd[t.out];
+        for (const auto &t : as) p[t.out] = pd[t.out];
+    }
+    sseq_progress(snoop, 0.75);
+    // BH over the tested genes only
+    std::vector<double> pv, q;
+    for (uint32_t j = 0; j < n_tests; j++) {
+        pv.clear();
+        for (uint64_t g = 0; g < genes; g++) {
+            p_adj[g * n_tests + j] = p[g * n_tests + j];
+            if (use_genes[g]) pv.push_back(p[g * n_tests + j]);
+        }
+        q.resize(pv.size());
+        sseq_host_bh(pv.data(), pv.size(), q.data());
+        uint64_t k = 0;
+        for (uint64_t g = 0; g < genes; g++)
+            if (use_genes[g]) p_adj[g * n_tests + j] = q[k++];
+    }
+    sseq_progress(snoop, 0.9);
+    for (uint64_t g = 0; g < genes; g++)
+        for (uint32_t j = 0; j < n_tests; j++) {
+            const uint64_t o = g * n_tests + j;
+            log2fc[o] = std::log2((double)(1 + sums_a[o]) / (1.0 + sf_a[j])) - std::log2((double)(1 + sums_b[o]) / (1.0 + sf_b[j]));
+        }
+    sseq_progress(snoop, 0.95);
+    for (uint64_t g = 0; g < genes; g++)
+        for (uint32_t j = 0; j < n_tests; j++) {
+            const uint64_t o = g * n_tests + j;
+            mean_in[o] = sf_a[j] == 0.0 ? 0.0 : (double)sums_a[o] / sf_a[j];
+            mean_out[o] = sf_b[j] == 0.0 ? 0.0 : (double)sums_b[o] / sf_b[j];
+        }
+    sseq_progress(snoop, 1.0);
+}
+
+// ---- sseq_differential_expression (diff_exp.rs:122-175) over labels ---------------------------------------------------------------
+// mode 0: every group against all other labelled cells (Cell Ranger's per-cluster DE); mode 1: group 0 against group 1
+void sseq_de_matrix(Storage &st, const SparseCopy &cp, bool gene_major, uint64_t genes, uint64_t cells, const int16_t *labels,
+                    uint32_t n_groups, int mode, const double *size_factors, const double *gene_means, const double *gene_phi,
+                    const uint8_t *use_genes, uint64_t big_count, const scanrs_snoop *snoop, uint64_t *sums_in, uint64_t *sums_out, double *p,
+                    double *p_adj, double *log2fc, double *mean_in, double *mean_out) {
+    if (mode != 0 && mode != 1) fail(SCANRS_ERR_ARGUMENT, "mode must be 0 (one against the rest) or 1 (group 0 against group 1)");
+    if (mode == 1 && n_groups < 2) fail(SCANRS_ERR_ARGUMENT, "mode 1 needs groups 0 and 1");
+    check_labels(labels, cells, n_groups);
+    const uint32_t n_tests = mode == 0 ? n_groups : 1;
+    sseq_progress(snoop, 0.0);
+    // the size factors of each side: sums over its cells in cell order (the reference's fold over cond_a / cond_b)
+    std::vector<double> fa(n_tests, 0.0), fb(n_tests, 0.0);
+    for (uint32_t j = 0; j < n_tests; j++) {
+        for (uint64_t c = 0; c < cells; c++) {
+            const int l = labels[c];
+            if (l < 0) continue;
+            if (mode == 0) {
+                if (l == (int)j)
+                    fa[j] += size_factors[c];
+                else
+                    fb[j] += size_factors[c];
+            } else {
+                if (l == 0) fa[j] += size_factors[c];
+                if (l == 1) fb[j] += size_factors[c];
+            }
+        }
+    }
+    sseq_progress(snoop, 0.1);
+    std::vector<uint64_t> sums(genes * n_groups);
+    sseq_group_sums(st, cp, gene_major, genes, cells, labels, n_groups, sums.data(), nullptr);
+    for (uint64_t g = 0; g < genes; g++) {
+        const uint64_t *row = &sums[g * n_groups];
+        if (mode == 0) {
+            uint64_t all = 0;
+            for (uint32_t j = 0; j < n_groups; j++) all += row[j];
+            for (uint32_t j = 0; j < n_groups; j++) {
+                sums_in[g * n_tests + j] = row[j];
+                sums_out[g * n_tests + j] = all - row[j];
+            }
+        } else {
+            sums_in[g] = row[0];
+            sums_out[g] = row[1];
+        }
+    }
+    sseq_progress(snoop, 0.6);
+    sseq_de_sums(st.stream, genes, n_tests, sums_in, sums_out, fa.data(), fb.data(), gene_means, gene_phi, use_genes, big_count, snoop, p, p_adj,
+                 log2fc, mean_in, mean_out);
+}
+
+} // namespace scanrs
