@@ -346,6 +346,9 @@ int scanrs_mat_set_spmm_path(scanrs_mat *m, int path);
  *                       device (no host round trip per orthonormalisation; falls back to the host path by itself when a
  *                       factorization does not converge within the queued passes); 0: host factorizations
  *   "d2h_threads" (4)   host threads that empty the pinned ring of a large result download
+ *   "merge_fused" (1)   scanrs_merge_clusters: per-cell totals plus ONE grouped pass over the nonzeros per call (per gene-major tile of
+ *                       1536 clusters), every candidate from those sums; 0: compute_sseq_params on the union and the pairwise DE for
+ *                       every candidate, as the reference calls them (A/B and test baseline). Same labels; p-values agree to ~1e-12
  *   "tile_spare_cus" (1) the persistent tile kernel launches as many workgroups as its number of item rounds needs (3 977 equal items:
  *                       16 rounds on 256 workgroups and on 249); the CUs left over serve the side streams during the pass (0: one per CU)
  *   "spmv_row_table" (1) Ix1 products over many short outer vectors (IRLBA's A v on the cell-major copy): a map that depends on the count
@@ -535,6 +538,54 @@ int scanrs_host_nb_log_prob_all(uint64_t n, double sf_a, double sf_b, double mu,
 int scanrs_host_adjusted_pvalue_bh(const double *p, uint64_t n, double *out);
 int scanrs_host_betainc(double a, double b, double x, double *out);
 int scanrs_host_betaincinv(double a, double b, double p, double *out);
+
+/* ---- merge_clusters (scan-rs/src/merge_clusters.rs, linkage.rs, stats.rs) ---------------------------------------------------
+ * Labels are one int16 per cell with values 0 .. K-1, every value present, K <= 8192; anything else returns SCANRS_ERR_ARGUMENT
+ * naming the first bad cell or the first missing label (the reference reads a leaf index as a label, which only means something
+ * for contiguous labels). Scores are n x d f64, row-major with leading dimension ld >= d (elements); a NaN among them returns
+ * SCANRS_ERR_ARGUMENT (the reference panics in n64). */
+
+/* `pdist` (linkage.rs:14-26): x m x d row-major; out m (m - 1) / 2 Euclidean distances, pairs (i, j > i) in row order, each
+ * summed over the dimensions in order then sqrt. Host only. */
+int scanrs_host_pdist(const double *x, uint64_t m, uint32_t d, double *out);
+/* `linkage(x, &Complete)` (linkage.rs:43-47, nn_chain :72-158, sort_by_column, relabel :160-216): z is (m - 1) x 4 f64 row-major in
+ * the reference's layout [a, b, distance, size], rows by (distance, row). m >= 1; distances that are NaN are refused. Host only. */
+int scanrs_host_linkage_complete(const double *x, uint64_t m, uint32_t d, double *z);
+/* `relabel_by_size` (merge_clusters.rs:43-56): labels ordered by count, largest first, equal counts in ascending label order
+ * (any int16 values). Host only. */
+int scanrs_host_relabel_by_size(const int16_t *labels, uint64_t n, int16_t *out);
+/* `medioids` (merge_clusters.rs:20-40): centers[i * d + j] is the median (`median_mut`, stats.rs:13-39: the middle of the sorted
+ * list, the mean of the two middle values for an even count) of column j over the cells labelled i; labels 0 .. k-1, each present.
+ * Exact radix select on the device (cluster.hip); ±0.0 may stand for each other. pca is a host array of n rows of ld elements. */
+int scanrs_cluster_medoids(const double *pca, uint64_t n, uint32_t ld, uint32_t d, const int16_t *labels, uint32_t k, double *centers);
+/* the same on scores already in device memory, e.g. scanrs_pca_result_device's *d_v / *ld_v; centers is a host array */
+int scanrs_cluster_medoids_device(const double *d_pca, uint64_t n, uint32_t ld, uint32_t d, const int16_t *labels, uint32_t k, double *centers);
+
+/* What scanrs_merge_clusters evaluated. The caller sets capacity and the four arrays (NULL when capacity is 0); entry i is the i-th
+ * candidate in the reference's evaluation order: the two leaves (labels of that round, leaf0 < leaf1), the number of genes with
+ * adjusted p < 0.05, and the smallest adjusted p (NaN values skipped; NaN when there is none). Entries past capacity are counted,
+ * not stored. */
+typedef struct {
+    uint64_t capacity;
+    int16_t *leaf0, *leaf1;
+    uint64_t *n_de;
+    double *min_p_adj;
+    uint64_t n_candidates, n_rounds, n_merges; /* out: candidates evaluated, rounds of the loop (the last merges nothing), merges */
+    uint64_t n_passes;                         /* out: passes over the nonzeros */
+} scanrs_merge_trace;
+
+/* `merge_clusters(fbm, pca, labels)` (merge_clusters.rs:59-138): merge, one pair per round, clusters that are adjacent under complete
+ * linkage of their medoids and have no gene with BH-adjusted p < 0.05 between them; labels_out gets `relabel_by_size` of the result.
+ * Rows of the handle are genes, columns are the n cells; DE reads the stored u32 counts and ignores map and offset (as scanrs_sseq_*
+ * does); sharded handles are refused. pca (n x d, leading dimension ld) is a host array, or device memory when pca_is_device != 0
+ * (PcaResultDevice.d_v / ld_v). n = 0 gives an empty result; a set cancel flag of `snoop` is read before every candidate
+ * (SCANRS_ERR_CANCELLED; no progress is reported, as in the reference). trace may be NULL.
+ * Handle option "merge_fused" (default 1): the per-cell totals, then ONE pass over the nonzeros that gathers per (gene, cluster)
+ * Σ x, Σ x/u_c and Σ (x/u_c)² (u_c the cell's total; 128-bit fixed point) makes each candidate's params and sums an O(genes)
+ * combination (a union whose median total is 0 takes the literal route); 0: every candidate runs compute_sseq_params on the union
+ * and the pairwise DE on the device, call for call as the reference (the A/B baseline). */
+int scanrs_merge_clusters(scanrs_mat *m, const double *pca, int pca_is_device, uint32_t ld, uint32_t d, const int16_t *labels,
+                          int16_t *labels_out, const scanrs_snoop *snoop, scanrs_merge_trace *trace);
 
 /* ---- 10x HDF5 ingestion (hdf5-io/src/matrix.rs, analysis.rs). Host-side; no device needed.
  * The files are parsed by the library's own reader (csrc/h5lite.cpp) — no libhdf5 dependency. Failures are

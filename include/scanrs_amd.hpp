@@ -472,6 +472,68 @@ inline std::vector<uint64_t> group_sums(const AdaptiveMat &m, const std::vector<
 }
 } // namespace diff_exp
 
+namespace cluster {
+// merge_clusters (scan-rs/src/merge_clusters.rs), linkage.rs, median_mut (stats.rs): labels 0 .. K-1, every value present
+inline std::vector<double> pdist(const std::vector<double> &x, uint64_t m, uint32_t d) { // linkage.rs:14-26
+    std::vector<double> out(m > 1 ? m * (m - 1) / 2 : 0);
+    check(scanrs_host_pdist(x.data(), m, d, out.data()));
+    return out;
+}
+inline std::vector<double> linkage(const std::vector<double> &x, uint64_t m, uint32_t d) { // Complete: (m - 1) x 4, linkage.rs:43-158
+    std::vector<double> z(m > 1 ? (m - 1) * 4 : 0);
+    check(scanrs_host_linkage_complete(x.data(), m, d, z.data()));
+    return z;
+}
+inline std::vector<int16_t> relabel_by_size(const std::vector<int16_t> &labels) { // merge_clusters.rs:43-56
+    std::vector<int16_t> out(labels.size());
+    check(scanrs_host_relabel_by_size(labels.data(), labels.size(), out.data()));
+    return out;
+}
+// merge_clusters.rs:20-40: k x d medians; pca n x d with leading dimension ld (host array)
+inline std::vector<double> medioids(const double *pca, uint64_t n, uint32_t ld, uint32_t d, const std::vector<int16_t> &labels, uint32_t k) {
+    std::vector<double> out((size_t)k * d);
+    check(scanrs_cluster_medoids(pca, n, ld, d, labels.data(), k, out.data()));
+    return out;
+}
+inline std::vector<double> medioids_device(const double *d_pca, uint64_t n, uint32_t ld, uint32_t d, const std::vector<int16_t> &labels,
+                                           uint32_t k) {
+    std::vector<double> out((size_t)k * d);
+    check(scanrs_cluster_medoids_device(d_pca, n, ld, d, labels.data(), k, out.data()));
+    return out;
+}
+struct MergeCandidate {
+    int16_t leaf0, leaf1;
+    uint64_t n_de;
+    double min_p_adj;
+};
+struct MergeTrace {
+    std::vector<MergeCandidate> candidates;
+    uint64_t n_candidates = 0, n_rounds = 0, n_merges = 0, n_passes = 0;
+};
+// merge_clusters.rs:59-138: pca is cells x d (leading dimension ld), in device memory when pca_is_device
+inline std::vector<int16_t> merge_clusters(const AdaptiveMat &m, const double *pca, bool pca_is_device, uint32_t ld, uint32_t d,
+                                           const std::vector<int16_t> &labels, MergeTrace *trace = nullptr, Snoop *snoop = nullptr,
+                                           uint64_t capacity = 4096) {
+    std::vector<int16_t> out(labels.size());
+    scanrs_snoop sn = detail::make_snoop(snoop);
+    std::vector<int16_t> l0(capacity), l1(capacity);
+    std::vector<uint64_t> nde(capacity);
+    std::vector<double> mp(capacity);
+    scanrs_merge_trace t{capacity, l0.data(), l1.data(), nde.data(), mp.data(), 0, 0, 0, 0};
+    check(scanrs_merge_clusters(m.raw(), pca, pca_is_device ? 1 : 0, ld, d, labels.data(), out.data(), snoop ? &sn : nullptr,
+                                trace ? &t : nullptr));
+    if (trace) {
+        trace->candidates.clear();
+        for (uint64_t i = 0; i < t.n_candidates && i < capacity; i++) trace->candidates.push_back({l0[i], l1[i], nde[i], mp[i]});
+        trace->n_candidates = t.n_candidates;
+        trace->n_rounds = t.n_rounds;
+        trace->n_merges = t.n_merges;
+        trace->n_passes = t.n_passes;
+    }
+    return out;
+}
+} // namespace cluster
+
 namespace mtx {
 // scan_rs::mtx::load_mtx (scan-rs/src/mtx.rs:10-51): the CSR arrays; `.to_device()` is the AdaptiveMat the reference returns
 inline hdf5_io::FeatureBarcodeMatrix read_mtx(const std::string &path) {

@@ -926,6 +926,8 @@ EXPORTED_SYMBOLS = [
     "scanrs_sseq_params", "scanrs_sseq_params_from_moments", "scanrs_mat_group_sums", "scanrs_sseq_de", "scanrs_sseq_de_from_sums",
     "scanrs_host_nb_exact_test", "scanrs_host_nb_asymptotic_test", "scanrs_host_nb_log_prob_all", "scanrs_host_adjusted_pvalue_bh",
     "scanrs_host_betainc", "scanrs_host_betaincinv",
+    "scanrs_host_pdist", "scanrs_host_linkage_complete", "scanrs_host_relabel_by_size", "scanrs_cluster_medoids", "scanrs_cluster_medoids_device",
+    "scanrs_merge_clusters",
 ]
 
 # sSeq differential expression (sseq.py)
@@ -933,3 +935,6 @@ from .sseq import (  # noqa: E402
     DiffExpResult, SSeqParams, compute_sseq_params, diff_exp_table, group_sums, labels_from_clustering, sseq_de_from_sums, sseq_de_one_vs_rest,
     sseq_differential_expression, sseq_params_from_moments,
 )
+
+# merge_clusters, linkage and medoids (cluster.py)
+from .cluster import MergeTrace, linkage, medioids, merge_clusters, pdist, relabel_by_size  # noqa: E402

@@ -361,6 +361,7 @@ struct Storage {
     int tile_hint = 0;                    // > 0 while a solver that repeats the same products is running (svd_bk, svd_rand)
     int tile_overlap = 1;                 // hybrid product: 1 = the overflow gather runs beside the tile kernel (own stream); 0 = after it (measurement)
     int panel_precision = 0;              // 0: f64 panels (default); 1: gathered panels rounded to f32, f64 sums (opt-in)
+    int merge_fused = 1;                  // merge_clusters: 1 = one grouped pass per call, candidates from its sums; 0 = params + pairwise DE per candidate (the reference's calls)
     size_t l2_tile_bytes = 3584u << 10;   // panel slice per step of the L2-blocked gather (4 MB L2 per XCD): whole 1024-row base tiles up to 3.5 MB — 4 tiles (3.2 MB) at 100 columns, 3 (2.9 MB) at 122; measured 40.55 / 39.71 ms per pass against 41.30 / 40.23 with 3 tiles and 40.86 / 39.61 with 5, and 4 tiles of 122 columns (3.9 MB) lose 1.8 ms
     int spmm_order = 1;                   // L2-blocked gather: launch outer vectors longest first: 0 never, 1 auto, 2 always (SCANRS_SPMM_ORDER)
     uint32_t hot_segment = 512;           // ... and give a workgroup to vectors with >= this many nonzeros per step (0 = never)
@@ -598,5 +599,27 @@ void sseq_de_sums(hipStream_t s, uint64_t genes, uint32_t n_tests, const uint64_
                   const scanrs_snoop *snoop, double *p, double *p_adj, double *log2fc, double *mean_in, double *mean_out);
 double sseq_host_exact_test(uint64_t xa, uint64_t xb, double sf_a, double sf_b, double mu, double phi);
 void sseq_host_bh(const double *p, uint64_t n, double *out);
+
+// ---- cluster.hip / cluster_host.cpp: merge_clusters (scan-rs/src/merge_clusters.rs, linkage.rs) ---------------------------------
+constexpr uint32_t MERGE_MAX_CLUSTERS = 8192;
+constexpr uint32_t MERGE_TILE_CLUSTERS = 1536; // clusters of one gene-major tile: a wave's LDS row of 5 u64 each fills 60 KB
+// exact medians of every (cluster, column): d_perm lists the cells cluster by cluster, d_off (n_clusters + 1) their segments;
+// d_keys holds n x cols_per_tile u64; d_nan_cell gets the smallest cell index holding a NaN (or all ones); d_out n_clusters x d
+void launch_medoids(hipStream_t s, const double *d_scores, uint64_t n, uint32_t ld, uint32_t d, const uint32_t *d_perm, const uint64_t *d_off,
+                    uint32_t n_clusters, unsigned long long *d_keys, uint32_t cols_per_tile, unsigned long long *d_nan_cell, double *d_out);
+// the fused pass of merge_clusters: d_out (n_clusters x genes x 5 u64) = Σ x, Σ x/u (lo, hi), Σ (x/u)² (lo, hi) per (cluster, gene);
+// returns the passes over the nonzeros it made (gene-major: one per tile of MERGE_TILE_CLUSTERS clusters)
+uint32_t launch_merge_pass(Storage &st, const SparseCopy &cp, bool gene_major, uint64_t n_genes, const int16_t *d_labels, uint32_t n_clusters,
+                           const unsigned long long *d_tot, double scale1, double scale2, unsigned long long *d_out);
+uint32_t merge_tile_clusters(uint32_t n_clusters);
+// host side (cluster_host.cpp)
+void cluster_pdist(const double *x, uint64_t m, uint32_t d, double *out);
+void cluster_linkage_complete(const double *x, uint64_t m, uint32_t d, double *z);
+void cluster_relabel_by_size(const int16_t *labels, uint64_t n, int16_t *out);
+void cluster_check_labels(const int16_t *labels, uint64_t n, uint32_t k);
+uint32_t cluster_count_labels(const int16_t *labels, uint64_t n); // K of a valid labelling (checked)
+void cluster_medoids(hipStream_t s, const double *d_scores, uint64_t n, uint32_t ld, uint32_t d, const int16_t *labels, uint32_t k, double *centers);
+void merge_clusters_run(Storage &st, const SparseCopy &cp, bool gene_major, uint64_t genes, uint64_t cells, const double *d_scores, uint32_t ld,
+                        uint32_t d, const int16_t *labels, int16_t *labels_out, const scanrs_snoop *snoop, scanrs_merge_trace *trace);
 
 } // namespace scanrs

@@ -14,31 +14,10 @@
 // sums, so that every sum fits below 2^126), and the integer sum is exact, so the result depends neither on the order in
 // which the waves arrive nor on which copy of the matrix was walked: both orientations give the same bits.
 #include "common.hpp"
+#include "fixed128.hpp"
 #include "special.hpp"
 
 namespace scanrs {
-
-struct U128 {
-    unsigned long long lo, hi;
-};
-__device__ __forceinline__ U128 to_fixed(double t, double scale) {
-    const double y = t * scale; // scale is a power of two: exact
-    const double hd = floor(y * 5.421010862427522e-20); // 2^-64
-    const double ld = rint(y - hd * 18446744073709551616.0); // exact difference; < 2^64, rounded only below 2^53
-    return U128{(unsigned long long)ld, (unsigned long long)hd};
-}
-__device__ __forceinline__ void add128(U128 &a, U128 b) {
-    a.lo += b.lo;
-    a.hi += b.hi + (a.lo < b.lo ? 1ull : 0ull);
-}
-__device__ __forceinline__ void atomic_add128(unsigned long long *p, U128 b) {
-    const unsigned long long old = atomicAdd(p, b.lo);
-    const unsigned long long carry = old + b.lo < old ? 1ull : 0ull;
-    if (b.hi + carry) atomicAdd(p + 1, b.hi + carry);
-}
-__device__ __forceinline__ U128 shfl_down128(U128 v, int off) {
-    return U128{(unsigned long long)__shfl_down((long long)v.lo, off), (unsigned long long)__shfl_down((long long)v.hi, off)};
-}
 
 // d_mom (rows x 4 u64): [lo, hi] of Σ x/sf, [lo, hi] of Σ (x/sf)²; d_bad: per gene, a term was not finite (sf = 0 with x > 0)
 template <bool MOM>

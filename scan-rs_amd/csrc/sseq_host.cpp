@@ -2,6 +2,7 @@
 // the moments, the split of the tests between the exact and the asymptotic branch, BH, log2 fold change and normalized means.
 // The passes over the nonzeros and the tests themselves run on the device (sseq.hip).
 #include "common.hpp"
+#include "fixed128.hpp"
 #include "special.hpp"
 
 #include <algorithm>
@@ -146,15 +147,6 @@ static void check_labels(const int16_t *labels, uint64_t cells, uint32_t n_group
     if (n_groups == 0 || n_groups > SSEQ_MAX_GROUPS) fail(SCANRS_ERR_ARGUMENT, "n_groups must be in 1 .. %u", SSEQ_MAX_GROUPS);
     for (uint64_t c = 0; c < cells; c++)
         if (labels[c] < -1 || labels[c] >= (int)n_groups) fail(SCANRS_ERR_ARGUMENT, "label %d of cell %llu is outside -1 .. n_groups - 1", (int)labels[c], (unsigned long long)c);
-}
-
-static double fixed_scale(double bound) {
-    // a power of two with bound * scale < 2^124 (sums of up to 2^124 fit the 128-bit accumulators with room for the rounding)
-    if (!(bound > 0.0) || !std::isfinite(bound)) return 1.0;
-    return std::ldexp(1.0, 124 - std::ilogb(bound) - 1);
-}
-static double from_fixed(const unsigned long long *w, double scale) {
-    return ((double)w[1] * 18446744073709551616.0 + (double)w[0]) / scale;
 }
 
 void sseq_group_sums(Storage &st, const SparseCopy &cp, bool gene_major, uint64_t genes, uint64_t cells, const int16_t *labels,
