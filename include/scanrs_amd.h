@@ -44,6 +44,7 @@ enum {
     SCANRS_ERR_DEVICE = 4,    /* no gfx950 device / HIP failure / out of memory */
     SCANRS_ERR_NUMERICAL = 5, /* LAPACK-style failure (`?` on qr()/svddc_into()) */
     SCANRS_ERR_ARGUMENT = 6,  /* null pointer, bad enum, unsupported combination */
+    SCANRS_ERR_INVALID = 6,   /* the same code under the name the select calls use: an index outside the matrix (the reference panics) */
     SCANRS_ERR_IO = 7         /* file missing / not HDF5 / truncated / a format feature this reader does not parse */
 };
 
@@ -159,6 +160,39 @@ int scanrs_mat_mean_var_axis(scanrs_mat *m, int axis, double *mean, double *var)
 
 /* to_dense (mat.rs:188-205, low_rank_offset.rs:55-57): rows x cols f64, small matrices / tests. */
 int scanrs_mat_to_dense(scanrs_mat *m, double *out);
+
+/* ---- select_rows / select_cols / partition_on_thresholds / to_csmat (sqz/src/mat.rs:207-241, 766-888, 1004-1071) ------------------
+ * All four read the stored counts. The first three work on a handle whose map is the identity (as created, or after
+ * scanrs_mat_reset_map) and that has no offset; a composed map, an offset or a sharded handle (scanrs_mat_set_shard*) returns
+ * SCANRS_ERR_ARGUMENT with the reason in scanrs_last_error() (the reference clones the map verbatim and would index its per-axis
+ * vectors with the new positions; that is not reproduced). Transposed views work: rows of the view are columns of the stored matrix,
+ * and a result's storage flag is the view's (scanrs_mat_storage). Every result is a fresh, independent handle with its own
+ * storage, default options and the identity map, made on the device from the handle's own storage (no transposed copy is built, nothing
+ * goes through the host); the source may be freed first. Free results with scanrs_mat_free.
+ *
+ * `select_rows` / `select_cols` (mat.rs:1004-1071): idx holds n_idx valid positions of that axis in any order, repeats allowed. Row i
+ * of select_rows is source row idx[i]; the other dimension and the storage flag are unchanged; the inner indices of every outer
+ * vector ascend. An index outside the matrix returns SCANRS_ERR_INVALID (the reference panics). n_idx = 0 gives a matrix with an
+ * empty dimension, as scanrs_mat_create accepts one. */
+int scanrs_mat_select_rows(scanrs_mat *m, const uint64_t *idx, uint64_t n_idx, scanrs_mat **out);
+int scanrs_mat_select_cols(scanrs_mat *m, const uint64_t *idx, uint64_t n_idx, scanrs_mat **out);
+/* `partition_on_thresholds(row_threshold, col_threshold)` (mat.rs:766-888); each threshold may be NULL (None), and
+ * `partition_on_threshold(t)` is both pointing at t. A round: if a column threshold is given, the column sums over the rows not yet
+ * excluded, and every column with sum < threshold joins the excluded columns; then the same for the rows over the columns not yet
+ * excluded (the columns as just updated); rounds repeat until one adds nothing. Sums are exact u64 integers converted to f64 for the
+ * comparison (a NaN threshold excludes nothing). One flag per round comes back to the host. Outputs, the reference's 4-tuple:
+ * *filtered = kept rows x kept columns, *residual = kept rows x excluded columns (ascending source order), both with the view's
+ * storage flag; either pointer may be NULL, then that matrix is not built. selected_rows / selected_cols: caller's arrays of rows /
+ * cols entries, filled with the kept positions (ascending) and their counts. When everything is excluded the matrices have empty
+ * dimensions. The counter "partition_rounds" (scanrs_mat_get_counter on m) holds the rounds of the last call, the final round that
+ * changes nothing included. */
+int scanrs_mat_partition_on_thresholds(scanrs_mat *m, const double *row_threshold, const double *col_threshold, scanrs_mat **filtered,
+                                       scanrs_mat **residual, uint64_t *selected_rows, uint64_t *n_selected_rows, uint64_t *selected_cols,
+                                       uint64_t *n_selected_cols);
+/* `base_mat_csc` / `to_csmat` of the stored counts (mat.rs:207-241, 257-259): indptr (outer dimension + 1 entries), indices and values
+ * (scanrs_mat_nnz entries each) in the handle's own storage flag (scanrs_mat_storage: for CSR the outer dimension is the rows). The
+ * map is not applied. */
+int scanrs_mat_to_csmat(scanrs_mat *m, uint64_t *indptr, uint32_t *indices, uint32_t *values);
 
 /* ---- products: `Dot` impls (mat.rs:1074-1170, low_rank_offset.rs:68-96, prod.rs) -- */
 
@@ -417,7 +451,8 @@ int scanrs_mat_set_option(scanrs_mat *m, const char *key, double value);
  * thread of "side_build"), "t_start_panel_us", "t_delivery_us" (U, V to host arrays); process-wide: "t_alloc_us" / "alloc_calls"
  * (hipMalloc). The tile layouts of the handle (both orientations, summed): "tile_positions" = record positions the tile kernel works
  * per pair of passes, "tile_served_nonzeros" = nonzeros among them (the rest is padding), "tile_overflow_nonzeros" = nonzeros left
- * to the overflow gather. */
+ * to the overflow gather. "partition_rounds" = rounds of the last scanrs_mat_partition_on_thresholds on this handle, the final round
+ * that changes nothing included. */
 int scanrs_mat_get_counter(scanrs_mat *m, const char *key, uint64_t *value);
 /* Process-wide options of the entry points that take no handle:
  *   "h5_threads" (8)               threads that inflate the chunks of a large filtered HDF5 read

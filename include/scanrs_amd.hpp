@@ -172,12 +172,64 @@ class AdaptiveMat {
         check(scanrs_mat_rdot(h_, lhs.data.data(), (uint32_t)lhs.rows, out.data.data()));
         return out;
     }
+    // select_rows / select_cols (mat.rs:1004-1071): any order, repeats allowed; identity map, no offset, not sharded
+    AdaptiveMat select_rows(const std::vector<uint64_t> &idx) const {
+        scanrs_mat *h = nullptr;
+        check(scanrs_mat_select_rows(h_, idx.data(), idx.size(), &h));
+        return AdaptiveMat(h);
+    }
+    AdaptiveMat select_cols(const std::vector<uint64_t> &idx) const {
+        scanrs_mat *h = nullptr;
+        check(scanrs_mat_select_cols(h_, idx.data(), idx.size(), &h));
+        return AdaptiveMat(h);
+    }
+    // partition_on_thresholds (mat.rs:766-888): (filtered, residual, selected_rows, selected_cols); nullptr = None
+    struct Partition;
+    Partition partition_on_thresholds(const double *row_threshold, const double *col_threshold) const;
+    Partition partition_on_threshold(double threshold) const;
+    // to_csmat of the stored counts (mat.rs:207-241) in the handle's storage flag
+    struct CsMat {
+        int storage = SCANRS_CSR;
+        uint64_t rows = 0, cols = 0;
+        std::vector<uint64_t> indptr;
+        std::vector<uint32_t> indices, data;
+    };
+    CsMat to_csmat() const {
+        CsMat c;
+        check(scanrs_mat_storage(h_, &c.storage));
+        c.rows = rows();
+        c.cols = cols();
+        c.indptr.resize((c.storage == SCANRS_CSR ? c.rows : c.cols) + 1);
+        c.indices.resize(nnz());
+        c.data.resize(nnz());
+        check(scanrs_mat_to_csmat(h_, c.indptr.data(), c.indices.data(), c.data.data()));
+        return c;
+    }
     Array2 to_dense() const {
         Array2 out(rows(), cols());
         check(scanrs_mat_to_dense(h_, out.data.data()));
         return out;
     }
 };
+
+struct AdaptiveMat::Partition {
+    AdaptiveMat filtered, residual;
+    std::vector<uint64_t> selected_rows, selected_cols;
+};
+inline AdaptiveMat::Partition AdaptiveMat::partition_on_thresholds(const double *row_threshold, const double *col_threshold) const {
+    Partition p;
+    p.selected_rows.resize(rows());
+    p.selected_cols.resize(cols());
+    uint64_t nr = 0, nc = 0;
+    scanrs_mat *f = nullptr, *r = nullptr;
+    check(scanrs_mat_partition_on_thresholds(h_, row_threshold, col_threshold, &f, &r, p.selected_rows.data(), &nr, p.selected_cols.data(), &nc));
+    p.filtered = AdaptiveMat(f);
+    p.residual = AdaptiveMat(r);
+    p.selected_rows.resize(nr);
+    p.selected_cols.resize(nc);
+    return p;
+}
+inline AdaptiveMat::Partition AdaptiveMat::partition_on_threshold(double threshold) const { return partition_on_thresholds(&threshold, &threshold); }
 
 // normalize(mat, norm) -> LowRankOffset (normalization.rs:46-69); consumes `mat` like the reference.
 inline AdaptiveMat normalize(AdaptiveMat mat, Normalization norm) {

@@ -392,6 +392,63 @@ class AdaptiveMat:
         _check(_lib.scanrs_mat_to_dense(self._h, _p(out)))
         return out
 
+    # -- select / partition / download (mat.rs:207-241, 766-888, 1004-1071) --------------
+    def _select(self, fn, idx) -> "AdaptiveMat":
+        idx = np.ascontiguousarray(np.asarray(idx).reshape(-1), dtype=np.int64)
+        if idx.size and int(idx.min()) < 0:
+            raise ScanrsError(6, "index out of range: negative index")
+        idx = idx.astype(np.uint64)
+        h = ctypes.c_void_p()
+        _check(fn(self._h, _p(idx), ctypes.c_uint64(idx.shape[0]), ctypes.byref(h)))
+        return AdaptiveMat(h.value)
+
+    def select_rows(self, idx) -> "AdaptiveMat":
+        """`select_rows` (mat.rs:1041-1071): row i of the result is row idx[i]; any order, repeats allowed. A fresh handle."""
+        return self._select(_lib.scanrs_mat_select_rows, idx)
+
+    def select_cols(self, idx) -> "AdaptiveMat":
+        """`select_cols` (mat.rs:1004-1038)."""
+        return self._select(_lib.scanrs_mat_select_cols, idx)
+
+    def partition_on_thresholds(self, row_threshold: Optional[float], col_threshold: Optional[float], filtered: bool = True,
+                                residual: bool = True):
+        """`partition_on_thresholds` (mat.rs:774-888): (filtered, residual, selected_rows, selected_cols); a threshold may be None.
+        filtered=False / residual=False: that matrix is not built (None in its place)."""
+        rows, cols = self.shape()
+        sel_r, sel_c = np.zeros(max(rows, 1), dtype=np.uint64), np.zeros(max(cols, 1), dtype=np.uint64)
+        n_r, n_c = ctypes.c_uint64(), ctypes.c_uint64()
+        rt = None if row_threshold is None else ctypes.byref(ctypes.c_double(row_threshold))
+        ct = None if col_threshold is None else ctypes.byref(ctypes.c_double(col_threshold))
+        hf, hr = ctypes.c_void_p(), ctypes.c_void_p()
+        _check(_lib.scanrs_mat_partition_on_thresholds(self._h, rt, ct, ctypes.byref(hf) if filtered else None,
+                                                       ctypes.byref(hr) if residual else None, _p(sel_r), ctypes.byref(n_r), _p(sel_c),
+                                                       ctypes.byref(n_c)))
+        f = AdaptiveMat(hf.value) if filtered else None
+        r = AdaptiveMat(hr.value) if residual else None
+        return f, r, sel_r[: n_r.value].astype(np.int64), sel_c[: n_c.value].astype(np.int64)
+
+    def partition_on_threshold(self, threshold: float):
+        """`partition_on_threshold` (mat.rs:768-770)."""
+        return self.partition_on_thresholds(threshold, threshold)
+
+    def to_csmat(self):
+        """`to_csmat` of the stored counts (mat.rs:207-241): (indptr u64, indices u32, data u32) in the handle's storage flag."""
+        rows, cols = self.shape()
+        n_outer = rows if self.storage() == CSR else cols
+        nnz = self.nnz()
+        indptr = np.zeros(n_outer + 1, dtype=np.uint64)
+        indices, data = np.zeros(nnz, dtype=np.uint32), np.zeros(nnz, dtype=np.uint32)
+        _check(_lib.scanrs_mat_to_csmat(self._h, _p(indptr), _p(indices), _p(data)))
+        return indptr, indices, data
+
+    def to_scipy(self):
+        """The stored counts as scipy.sparse csr_matrix / csc_matrix (by the storage flag)."""
+        import scipy.sparse as sp
+
+        indptr, indices, data = self.to_csmat()
+        cls = sp.csr_matrix if self.storage() == CSR else sp.csc_matrix
+        return cls((data, indices.astype(np.int64), indptr.astype(np.int64)), shape=tuple(self.shape()))
+
     # -- products ----------------------------------------------------------------------------------
     def dot(self, rhs):
         """`self.dot(&rhs)` (mat.rs:1074-1112, low_rank_offset.rs:68-81)."""
@@ -928,6 +985,7 @@ EXPORTED_SYMBOLS = [
     "scanrs_host_betainc", "scanrs_host_betaincinv",
     "scanrs_host_pdist", "scanrs_host_linkage_complete", "scanrs_host_relabel_by_size", "scanrs_cluster_medoids", "scanrs_cluster_medoids_device",
     "scanrs_merge_clusters",
+    "scanrs_mat_select_rows", "scanrs_mat_select_cols", "scanrs_mat_partition_on_thresholds", "scanrs_mat_to_csmat",
 ]
 
 # sSeq differential expression (sseq.py)

@@ -1272,6 +1272,66 @@ static void create_common(uint64_t rows, uint64_t cols, int storage, const uint6
     *out = m;
 }
 
+// A handle around a copy that was made on the device (select / partition): its buffers are adopted, not copied, and nothing goes
+// through the host. The copy comes from the library's own kernels (indices in range and ascending, no zeros), so the validation of
+// scanrs_mat_create_device has nothing to find; everything else is as create_common leaves it.
+static scanrs_mat *adopt_copy(uint64_t rows, uint64_t cols, int storage, SparseCopy &&made) {
+    auto st = std::make_shared<Storage>();
+    {
+        std::lock_guard<std::mutex> lk(g_storages_mu);
+        g_storages.insert(st.get());
+    }
+    st->rows = rows;
+    st->cols = cols;
+    st->storage = storage;
+    SCANRS_HIP(hipStreamCreate(&st->stream));
+    st->scratch.stream = st->stream;
+    SparseCopy &cp = st->primary;
+    cp.n_outer = made.n_outer;
+    cp.n_inner = made.n_inner;
+    cp.nnz = made.nnz;
+    cp.max_value = made.nnz ? std::max(made.max_value, 1u) : 0u;
+    cp.indptr = std::move(made.indptr);
+    cp.indices = std::move(made.indices);
+    cp.values = std::move(made.values);
+    if ((storage == SCANRS_CSR ? rows : cols) != cp.n_outer || (storage == SCANRS_CSR ? cols : rows) != cp.n_inner)
+        fail(SCANRS_ERR_SHAPE, "internal: adopted copy does not match the handle's shape");
+    CurrentHandle cur(st.get());
+    cp.build_items(st->stream);
+    auto *m = new scanrs_mat();
+    m->st = st;
+    return m;
+}
+
+// select / partition work on the stored counts under the identity map (the reference clones the map verbatim and would index its
+// per-axis vectors with the NEW positions; that is not reproduced)
+static void need_plain_unsharded(const scanrs_mat *m, const char *what) {
+    if (!map_is_raw(m))
+        fail(SCANRS_ERR_ARGUMENT, "%s: the handle's map is not the identity (a scaling or a function has been composed); call scanrs_mat_reset_map first", what);
+    if (m->off_rank) fail(SCANRS_ERR_ARGUMENT, "%s: the handle has a low-rank offset (center / scale_and_center / normalize); call scanrs_mat_reset_map first", what);
+    if (m->st->shard.active()) fail(SCANRS_ERR_ARGUMENT, "%s of a sharded handle (scanrs_mat_set_shard*) is not supported", what);
+}
+
+static void select_axis(scanrs_mat *m, bool rows_axis, const uint64_t *idx, uint64_t n_idx, scanrs_mat **out) {
+    if (!m || !out) fail(SCANRS_ERR_ARGUMENT, "null argument");
+    *out = nullptr;
+    need_device();
+    need_plain_unsharded(m, rows_axis ? "select_rows" : "select_cols");
+    Storage &st = *m->st;
+    const bool outer_is_view_rows = (st.storage == SCANRS_CSR) != m->transposed;
+    const int view_storage = m->transposed ? 1 - st.storage : st.storage;
+    SparseCopy made;
+    {
+        CurrentHandle cur(&st);
+        if (rows_axis == outer_is_view_rows)
+            select_outer(st, st.primary, idx, n_idx, made);
+        else
+            select_inner(st, st.primary, idx, n_idx, made);
+        device_free_flush();
+    }
+    *out = adopt_copy(rows_axis ? n_idx : m->rows(), rows_axis ? m->cols() : n_idx, view_storage, std::move(made));
+}
+
 // radix select of the k-th smallest (0-based, global rank) of a u32 device array spread over ranks
 static uint32_t select_kth(Storage &st, const uint32_t *d, uint64_t n_local, uint64_t kth) {
     unsigned long long *hist = st.scratch.get<unsigned long long>("select_hist", 4096);
@@ -2302,6 +2362,8 @@ int scanrs_mat_get_counter(scanrs_mat *m, const char *key, uint64_t *value) {
         const std::string k(key);
         if (k == "bk_host_retries")
             *value = m->st->bk_host_retries;
+        else if (k == "partition_rounds") // rounds of the last scanrs_mat_partition_on_thresholds on this handle
+            *value = m->st->partition_rounds;
         else if (k == "t_layout_us") // first-call accounting: host time of the calling thread in tile layout builds ...
             *value = m->st->t_layout_us;
         else if (k == "t_side_wait_us") // ... waiting for the helper thread that builds the second orientation
@@ -2629,6 +2691,70 @@ int scanrs_merge_clusters(scanrs_mat *m, const double *pca, int pca_is_device, u
             scores = d_pca.p;
         }
         merge_clusters_run(st, cp, gm, m->rows(), cells, scores, ld, d, labels, labels_out, snoop, trace);
+    });
+}
+} // extern "C"
+
+// ---- select_rows / select_cols / partition_on_thresholds / to_csmat (select_host.cpp / select.hip) --------------------------------------
+extern "C" {
+int scanrs_mat_select_rows(scanrs_mat *m, const uint64_t *idx, uint64_t n_idx, scanrs_mat **out) {
+    return guard([&] { select_axis(m, true, idx, n_idx, out); });
+}
+int scanrs_mat_select_cols(scanrs_mat *m, const uint64_t *idx, uint64_t n_idx, scanrs_mat **out) {
+    return guard([&] { select_axis(m, false, idx, n_idx, out); });
+}
+int scanrs_mat_partition_on_thresholds(scanrs_mat *m, const double *row_threshold, const double *col_threshold, scanrs_mat **filtered,
+                                       scanrs_mat **residual, uint64_t *selected_rows, uint64_t *n_selected_rows, uint64_t *selected_cols,
+                                       uint64_t *n_selected_cols) {
+    return guard([&] {
+        if (filtered) *filtered = nullptr;
+        if (residual) *residual = nullptr;
+        if (!m || !selected_rows || !n_selected_rows || !selected_cols || !n_selected_cols) fail(SCANRS_ERR_ARGUMENT, "null argument");
+        need_device();
+        need_plain_unsharded(m, "partition_on_thresholds");
+        Storage &st = *m->st;
+        const bool outer_is_view_rows = (st.storage == SCANRS_CSR) != m->transposed;
+        const int view_storage = m->transposed ? 1 - st.storage : st.storage;
+        SparseCopy f, r;
+        std::vector<uint8_t> ex_outer, ex_inner;
+        {
+            CurrentHandle cur(&st);
+            st.partition_rounds = partition_on_thresholds(st, st.primary, outer_is_view_rows ? row_threshold : col_threshold,
+                                                          outer_is_view_rows ? col_threshold : row_threshold, outer_is_view_rows, ex_outer, ex_inner,
+                                                          filtered ? &f : nullptr, residual ? &r : nullptr);
+            device_free_flush();
+        }
+        const std::vector<uint8_t> &ex_rows = outer_is_view_rows ? ex_outer : ex_inner, &ex_cols = outer_is_view_rows ? ex_inner : ex_outer;
+        uint64_t nr = 0, nc = 0;
+        for (uint64_t i = 0; i < ex_rows.size(); i++)
+            if (!ex_rows[i]) selected_rows[nr++] = i;
+        for (uint64_t i = 0; i < ex_cols.size(); i++)
+            if (!ex_cols[i]) selected_cols[nc++] = i;
+        *n_selected_rows = nr;
+        *n_selected_cols = nc;
+        scanrs_mat *hf = filtered ? adopt_copy(nr, nc, view_storage, std::move(f)) : nullptr;
+        try {
+            if (residual) *residual = adopt_copy(nr, ex_cols.size() - nc, view_storage, std::move(r));
+        } catch (...) {
+            scanrs_mat_free(hf);
+            throw;
+        }
+        if (filtered) *filtered = hf;
+    });
+}
+int scanrs_mat_to_csmat(scanrs_mat *m, uint64_t *indptr, uint32_t *indices, uint32_t *values) {
+    return guard([&] {
+        if (!m || !indptr) fail(SCANRS_ERR_ARGUMENT, "null argument");
+        Storage &st = *m->st;
+        const SparseCopy &cp = st.primary; // a transposed view's storage flag is the other one: the same arrays
+        if (cp.nnz && (!indices || !values)) fail(SCANRS_ERR_ARGUMENT, "null indices/values");
+        CurrentHandle cur(&st);
+        SCANRS_D2H(indptr, cp.indptr.p, (cp.n_outer + 1) * 8, st.stream);
+        if (cp.nnz) {
+            SCANRS_D2H(indices, cp.indices.p, cp.nnz * 4, st.stream);
+            SCANRS_D2H(values, cp.values.p, cp.nnz * 4, st.stream);
+        }
+        SCANRS_SYNC(st.stream);
     });
 }
 } // extern "C"

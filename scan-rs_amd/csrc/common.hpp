@@ -361,6 +361,7 @@ struct Storage {
     int tile_hint = 0;                    // > 0 while a solver that repeats the same products is running (svd_bk, svd_rand)
     int tile_overlap = 1;                 // hybrid product: 1 = the overflow gather runs beside the tile kernel (own stream); 0 = after it (measurement)
     int panel_precision = 0;              // 0: f64 panels (default); 1: gathered panels rounded to f32, f64 sums (opt-in)
+    uint64_t partition_rounds = 0;        // rounds of the last scanrs_mat_partition_on_thresholds on this handle, the final one that changes nothing included (scanrs_mat_get_counter)
     int merge_fused = 1;                  // merge_clusters: 1 = one grouped pass per call, candidates from its sums; 0 = params + pairwise DE per candidate (the reference's calls)
     size_t l2_tile_bytes = 3584u << 10;   // panel slice per step of the L2-blocked gather (4 MB L2 per XCD): whole 1024-row base tiles up to 3.5 MB — 4 tiles (3.2 MB) at 100 columns, 3 (2.9 MB) at 122; measured 40.55 / 39.71 ms per pass against 41.30 / 40.23 with 3 tiles and 40.86 / 39.61 with 5, and 4 tiles of 122 columns (3.9 MB) lose 1.8 ms
     int spmm_order = 1;                   // L2-blocked gather: launch outer vectors longest first: 0 never, 1 auto, 2 always (SCANRS_SPMM_ORDER)
@@ -621,5 +622,31 @@ uint32_t cluster_count_labels(const int16_t *labels, uint64_t n); // K of a vali
 void cluster_medoids(hipStream_t s, const double *d_scores, uint64_t n, uint32_t ld, uint32_t d, const int16_t *labels, uint32_t k, double *centers);
 void merge_clusters_run(Storage &st, const SparseCopy &cp, bool gene_major, uint64_t genes, uint64_t cells, const double *d_scores, uint32_t ld,
                         uint32_t d, const int16_t *labels, int16_t *labels_out, const scanrs_snoop *snoop, scanrs_merge_trace *trace);
+
+// ---- select.hip / select_host.cpp: select_rows, select_cols, partition_on_thresholds (sqz/src/mat.rs:730-888, 1004-1071) ---------
+void launch_sel_outer_sums(hipStream_t s, const SparseCopy &cp, const uint8_t *excl_outer, const uint8_t *excl_inner, unsigned long long *out);
+void launch_sel_inner_sums(hipStream_t s, const SparseCopy &cp, const uint8_t *pick, uint8_t want, bool subtract, const uint8_t *excl_inner,
+                           unsigned long long *sums);
+void launch_sel_mark(hipStream_t s, const unsigned long long *sums, uint64_t n, double threshold, uint8_t *excl, uint8_t *newly, uint32_t *flag);
+void select_scan_offsets(hipStream_t s, unsigned long long *d, uint64_t n); // in place: n lengths (+ one spare entry) -> n + 1 offsets
+void launch_part_count(hipStream_t s, const SparseCopy &cp, const int32_t *pos_a, const int32_t *pos_b, const int32_t *remap, bool cols_inner,
+                       unsigned long long *len_a, unsigned long long *len_b);
+void launch_part_fill(hipStream_t s, const SparseCopy &cp, const int32_t *pos_a, const int32_t *pos_b, const int32_t *remap, bool cols_inner,
+                      const uint64_t *ip_a, uint32_t *idx_a, uint32_t *val_a, const uint64_t *ip_b, uint32_t *idx_b, uint32_t *val_b);
+void launch_gather_len(hipStream_t s, const SparseCopy &cp, const uint32_t *d_idx, uint64_t n_idx, unsigned long long *len);
+void launch_gather_copy(hipStream_t s, const SparseCopy &cp, const uint32_t *d_idx, uint64_t n_idx, const uint64_t *ip_out, uint32_t *idx_out,
+                        uint32_t *val_out);
+void launch_expand_count(hipStream_t s, const SparseCopy &cp, const uint32_t *inv_ptr, unsigned long long *len);
+void launch_expand_fill(hipStream_t s, const SparseCopy &cp, const uint32_t *inv_ptr, const uint32_t *inv_pos, const uint64_t *ip_out,
+                        uint32_t *idx_out, uint32_t *val_out);
+// host side (select_host.cpp). `out` receives indptr / indices / values, the dimensions and nnz of the new matrix in cp's orientation
+// (no work items: the handle that adopts it builds them). idx: n_idx valid positions of the named axis, any order, repeats allowed.
+void select_outer(Storage &st, const SparseCopy &cp, const uint64_t *idx, uint64_t n_idx, SparseCopy &out);
+void select_inner(Storage &st, const SparseCopy &cp, const uint64_t *idx, uint64_t n_idx, SparseCopy &out);
+// thr_outer / thr_inner: nullable thresholds of the two axes of cp; cols_inner: the view's columns are cp's inner positions (their
+// step comes first in a round). excl_outer / excl_inner: the final masks (host). filtered / residual may be null (not built).
+// Returns the number of rounds.
+uint64_t partition_on_thresholds(Storage &st, const SparseCopy &cp, const double *thr_outer, const double *thr_inner, bool cols_inner,
+                                 std::vector<uint8_t> &excl_outer, std::vector<uint8_t> &excl_inner, SparseCopy *filtered, SparseCopy *residual);
 
 } // namespace scanrs
