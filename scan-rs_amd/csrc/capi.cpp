@@ -1,999 +1,13 @@
-// extern "C" boundary + operator-level host logic (the sqz::AdaptiveMat / LowRankOffset /
-// scan-rs::normalization surface). See include/scanrs_amd.h for the reference citations per entry point.
+// The operator layer (the sqz::AdaptiveMat / LowRankOffset / scan-rs::normalization surface: creation, map and offset, products,
+// normalisation, select) and its extern "C" boundary, with the options and counters; the sSeq and merge_clusters entry points sit
+// next to their host logic. See include/scanrs_amd.h for the reference citations per entry point.
 #include <algorithm>
-#include <atomic>
 #include <cmath>
-#include <cstdlib>
-#include <condition_variable>
-#include <map>
-#include <mutex>
-#include <thread>
 #include <vector>
 
 #include "common.hpp"
-#include "special.hpp"
 
 namespace scanrs {
-
-// ---- errors ---------------------------------------------------------------------------------
-static thread_local char g_err[512] = "";
-void set_error(const char *fmt, ...) {
-    va_list ap;
-    va_start(ap, fmt);
-    vsnprintf(g_err, sizeof(g_err), fmt, ap);
-    va_end(ap);
-}
-void fail(int code, const char *fmt, ...) {
-    va_list ap;
-    va_start(ap, fmt);
-    vsnprintf(g_err, sizeof(g_err), fmt, ap);
-    va_end(ap);
-    throw Failure{code};
-}
-
-uint32_t next_map_op_id() {
-    static std::atomic<uint32_t> next{1};
-    return next.fetch_add(1, std::memory_order_relaxed);
-}
-
-// SCANRS_TRACE=1: phase timings (with the synchronisations they need); SCANRS_TRACE=2: stage markers only — one line per host
-// step of the solvers, nothing synchronised: where a call that does not return is standing.
-static int trace_level() {
-    static int v = -1;
-    if (v < 0) {
-        const char *e = getenv("SCANRS_TRACE");
-        v = !e ? 0 : (e[0] == '2' ? 2 : 1);
-    }
-    return v;
-}
-bool trace_on() { return trace_level() == 1; }
-
-// the calling thread's last stage marks (what a timed-out wait reports)
-namespace {
-struct StageRing {
-    static constexpr int N = 16;
-    struct Rec {
-        char what[40];
-        long a, b;
-        std::chrono::steady_clock::time_point t;
-    } rec[N];
-    unsigned n = 0;
-};
-thread_local StageRing tl_stages;
-thread_local const Storage *tl_handle = nullptr;
-thread_local const Storage *tl_dying = nullptr; // scanrs_mat_free: the storage whose members are being destroyed on this thread (its streams are drained)
-
-std::atomic<double> g_sync_timeout_s{120.0};
-} // namespace
-// set by a bounded wait that gave up (timeout_report); cleared only when the whole device has been seen idle again (device_recovered)
-std::atomic<bool> g_device_lost{false};
-bool device_lost() { return g_device_lost.load(std::memory_order_acquire); }
-// the handles of this process (registered by Storage's constructor): "is every stream the library owns idle?" walks them
-static std::mutex g_storages_mu;
-static std::set<const Storage *> g_storages;
-static std::atomic<int> g_storages_dying{0}; // handles inside their destructor: out of the set (nobody may walk their members), their streams possibly still draining
-static hipStream_t storage_side_stream(const Storage &st); // the helper thread's stream, if a helper exists (defined behind SideBuild)
-static bool storage_streams_idle(const Storage *st);
-static bool all_library_streams_idle() {
-    std::lock_guard<std::mutex> lk(g_storages_mu);
-    if (g_storages_dying.load(std::memory_order_acquire) > 0) return false;
-    for (const Storage *st : g_storages)
-        if (!storage_streams_idle(st)) return false;
-    return true;
-}
-
-void stage_mark(const char *what, long a, long b) {
-    StageRing::Rec &r = tl_stages.rec[tl_stages.n++ % StageRing::N];
-    strncpy(r.what, what, sizeof(r.what) - 1);
-    r.what[sizeof(r.what) - 1] = 0;
-    r.a = a;
-    r.b = b;
-    r.t = std::chrono::steady_clock::now();
-    if (trace_level() != 2) return;
-    fprintf(stderr, "[scanrs stage] %.3f %s %ld %ld\n", std::chrono::duration<double, std::milli>(r.t.time_since_epoch()).count(), what, a, b);
-    fflush(stderr);
-}
-double sync_timeout_s() { return g_sync_timeout_s.load(std::memory_order_relaxed); }
-void set_sync_timeout_s(double s) { g_sync_timeout_s.store(s, std::memory_order_relaxed); }
-void *landing_slot(size_t bytes) {
-    static char *ring = nullptr;
-    static std::atomic<size_t> head{0};
-    static std::once_flag once;
-    constexpr size_t RING = 1u << 20;
-    std::call_once(once, [] {
-        void *p = nullptr;
-        if (hipHostMalloc(&p, RING, hipHostMallocDefault) != hipSuccess) {
-            (void)hipGetLastError();
-            p = malloc(RING); // pageable, but still a place that no stack frame owns
-        }
-        ring = static_cast<char *>(p);
-    });
-    const size_t need = (bytes + 7) & ~(size_t)7;
-    if (!ring || need > 4096) fail(SCANRS_ERR_DEVICE, "no landing slot of %zu bytes", bytes);
-    size_t at = head.fetch_add(need, std::memory_order_relaxed) % RING;
-    if (at + need > RING) at = head.fetch_add(need, std::memory_order_relaxed) % RING; // (a slot never straddles the end: the next one does not either)
-    if (at + need > RING) at = 0;
-    return ring + at;
-}
-namespace {
-// Pinned staging areas of 8 MB for the array copies (histograms, factor verdicts, axis sums, small panels). A copy takes one for
-// itself for as long as it waits and hands it back afterwards: the pool's mutex is held only to take and to give (one
-// area under one mutex held across the wait made every handle and shard thread queue behind the stream with the longest backlog).
-// An area whose wait timed out is NOT given back - the abandoned copy may still land in it. Never unmapped.
-struct LandingPool {
-    std::mutex mu;
-    std::vector<char *> idle;
-    static constexpr size_t BYTES = 8u << 20;
-};
-LandingPool &landing_pool() {
-    static LandingPool *a = new LandingPool(); // never destroyed
-    return *a;
-}
-struct LandingLease {
-    char *p = nullptr;
-    bool keep = true; // cleared when the lease ends in order: a timed-out wait unwinds past `done()` and the area stays out of the pool
-    LandingLease() {
-        LandingPool &g = landing_pool();
-        {
-            std::lock_guard<std::mutex> lk(g.mu);
-            if (!g.idle.empty()) {
-                p = g.idle.back();
-                g.idle.pop_back();
-            }
-        }
-        if (!p) {
-            void *q = nullptr;
-            if (hipHostMalloc(&q, LandingPool::BYTES, hipHostMallocPortable) != hipSuccess) {
-                (void)hipGetLastError();
-                q = malloc(LandingPool::BYTES);
-            }
-            p = static_cast<char *>(q);
-        }
-    }
-    void done() { keep = false; }
-    ~LandingLease() {
-        if (!p || keep) return;
-        LandingPool &g = landing_pool();
-        std::lock_guard<std::mutex> lk(g.mu);
-        g.idle.push_back(p);
-    }
-};
-} // namespace
-void d2h_landed_2d(void *dst, const void *dsrc, size_t src_pitch, size_t row_bytes, size_t rows, hipStream_t s, const char *func, const char *file, int line) {
-    if (!rows || !row_bytes) return;
-    LandingLease a;
-    if (!a.p) fail(SCANRS_ERR_DEVICE, "no host staging area for device-to-host copies");
-    if (row_bytes > LandingPool::BYTES) fail(SCANRS_ERR_ARGUMENT, "a row of %zu bytes does not fit the host staging area", row_bytes);
-    const size_t rows_per = std::max<size_t>(1, LandingPool::BYTES / row_bytes);
-    for (size_t r0 = 0; r0 < rows; r0 += rows_per) {
-        const size_t nr = std::min(rows_per, rows - r0);
-        const char *src = static_cast<const char *>(dsrc) + r0 * src_pitch;
-        if (src_pitch == row_bytes)
-            SCANRS_HIP(hipMemcpyAsync(a.p, src, nr * row_bytes, hipMemcpyDeviceToHost, s));
-        else
-            SCANRS_HIP(hipMemcpy2DAsync(a.p, row_bytes, src, src_pitch, row_bytes, nr, hipMemcpyDeviceToHost, s));
-        wait_stream(s, func, file, line);
-        memcpy(static_cast<char *>(dst) + r0 * row_bytes, a.p, nr * row_bytes);
-    }
-    a.done();
-}
-void d2h_landed(void *dst, const void *dsrc, size_t bytes, hipStream_t s, const char *func, const char *file, int line) {
-    if (!bytes) return;
-    const size_t piece = std::min<size_t>(bytes, 1u << 20);
-    const size_t whole = bytes / piece;
-    d2h_landed_2d(dst, dsrc, piece, piece, whole, s, func, file, line);
-    if (bytes > whole * piece)
-        d2h_landed_2d(static_cast<char *>(dst) + whole * piece, static_cast<const char *>(dsrc) + whole * piece, bytes - whole * piece, bytes - whole * piece, 1, s, func, file, line);
-}
-static bool device_recovered();
-CurrentHandle::CurrentHandle(const Storage *st, bool waits_only) : prev(tl_handle) {
-    if (!waits_only && device_lost() && !device_recovered())
-        fail(SCANRS_ERR_DEVICE, "a device wait of this process timed out earlier (sync_timeout_s) and the device has not been seen idle since: the library "
-                                "does not queue new work or reuse memory that kernels may still be using (scanrs_mat_sync waits for a handle's streams)");
-    tl_handle = st;
-}
-CurrentHandle::~CurrentHandle() { tl_handle = prev; }
-
-// Poll `query` (hipSuccess: done, hipErrorNotReady: not yet, anything else: a device error) until the deadline. Spins for the
-// first 200 us, then sleeps 20 us per round (about 70 us with the kernel's timer slack), 200 us per round once a second has passed.
-// (Until round 6 the long rounds began after 5 ms: svd_bk's waits for the coefficients' verdict, the projection and the Gram matrix last
-// 15-35 ms with the device idle until the host reacts — half a round of 250 us lost at each.)
-template <typename Q>
-static hipError_t poll_until(Q &&query, double timeout_s, double *waited_s) {
-    const auto t0 = std::chrono::steady_clock::now();
-    for (;;) {
-        const hipError_t e = query();
-        if (e != hipErrorNotReady) return e;
-        const double el = std::chrono::duration<double>(std::chrono::steady_clock::now() - t0).count();
-        if (el > timeout_s) {
-            if (waited_s) *waited_s = el;
-            return hipErrorNotReady;
-        }
-        if (el < 200e-6)
-            std::this_thread::yield();
-        else
-            std::this_thread::sleep_for(std::chrono::microseconds(el < 1.0 ? 20 : 200));
-    }
-}
-// "auto scanrs_mat_sync(scanrs_mat *)::(anonymous class)::operator()() const" -> "scanrs_mat_sync": most waits sit inside the lambda
-// an entry point hands to guard(), whose own __func__ is "operator()"
-static std::string short_func(const char *pretty) {
-    std::string s(pretty ? pretty : "?");
-    for (const char *cut : {"::(anonymous class)", "::<lambda", "::(lambda"}) {
-        const size_t at = s.find(cut);
-        if (at != std::string::npos) s.resize(at);
-    }
-    const size_t paren = s.find('(');
-    if (paren != std::string::npos) s.resize(paren);
-    const size_t sp = s.rfind(' ');
-    if (sp != std::string::npos) s = s.substr(sp + 1);
-    return s.empty() ? std::string("?") : s;
-}
-static const char *base_name(const char *file) {
-    const char *b = strrchr(file, '/');
-    return b ? b + 1 : file;
-}
-// message + stderr dump of a wait that ran into its deadline; `busy` = query of one named stream (may be null on the CPU test path)
-static void timeout_report(const char *kind, const char *pretty_func, const char *file, int line, double waited, hipStream_t waited_stream) {
-    const std::string fn = short_func(pretty_func);
-    const char *func = fn.c_str();
-    char where[160] = "";
-    if (tl_handle) { // which of the handle's streams still have work (hipStreamQuery never blocks)
-        const Storage &st = *tl_handle;
-        struct {
-            const char *name;
-            hipStream_t s;
-        } streams[] = {{"main", st.stream}, {"aux", st.aux_stream}, {"aux2", st.aux2_stream}, {"overflow", st.ov_stream}};
-        size_t off = 0;
-        for (auto &x : streams) {
-            if (!x.s) continue;
-            const hipError_t q = hipStreamQuery(x.s);
-            off += (size_t)snprintf(where + off, sizeof(where) - off, "%s%s%s=%s", off ? ", " : "", x.s == waited_stream ? "*" : "", x.name,
-                                    q == hipSuccess ? "idle" : q == hipErrorNotReady ? "busy" : hipGetErrorString(q));
-            if (off >= sizeof(where)) break;
-        }
-        (void)hipGetLastError();
-    }
-    char stages[200] = "";
-    {
-        size_t off = 0;
-        const unsigned n = tl_stages.n, first = n > 4 ? n - 4 : 0;
-        const auto now = std::chrono::steady_clock::now();
-        for (unsigned i = first; i < n && off < sizeof(stages); i++) {
-            const StageRing::Rec &r = tl_stages.rec[i % StageRing::N];
-            off += (size_t)snprintf(stages + off, sizeof(stages) - off, "%s%s(%ld) -%.1fs", off ? " > " : "", r.what, r.a,
-                                    std::chrono::duration<double>(now - r.t).count());
-        }
-    }
-    fprintf(stderr, "[scanrs] device wait timed out: %s in %s (%s:%d) after %.1f s; streams: %s; last stages: %s\n", kind, func, base_name(file), line,
-            waited, where[0] ? where : "n/a", stages[0] ? stages : "none");
-    { // the whole ring on stderr
-        const unsigned n = tl_stages.n, first = n > StageRing::N ? n - StageRing::N : 0;
-        const auto now = std::chrono::steady_clock::now();
-        for (unsigned i = first; i < n; i++) {
-            const StageRing::Rec &r = tl_stages.rec[i % StageRing::N];
-            fprintf(stderr, "[scanrs]   stage %-36s %ld %ld  %.3f s ago\n", r.what, r.a, r.b, std::chrono::duration<double>(now - r.t).count());
-        }
-        fflush(stderr);
-    }
-    // From here on the library must assume that kernels and copies of this process are still running: nothing they may touch is
-    // reused or freed (device_free_flush leaks), and every later entry point fails fast until device_recovered() has seen the device idle.
-    g_device_lost.store(true, std::memory_order_release);
-    fail(SCANRS_ERR_DEVICE, "device wait timed out after %.1f s (sync_timeout_s): %s in %s (%s:%d); streams: %s; last stages: %s", waited, kind, func,
-         base_name(file), line, where[0] ? where : "n/a", stages[0] ? stages : "none");
-}
-void wait_stream(hipStream_t s, const char *func, const char *file, int line) {
-    double waited = 0.0;
-    const hipError_t e = poll_until([&] { return hipStreamQuery(s); }, sync_timeout_s(), &waited);
-    if (e == hipSuccess) return;
-    if (e == hipErrorNotReady) timeout_report("stream synchronisation", func, file, line, waited, s);
-    fail(SCANRS_ERR_DEVICE, "stream synchronisation failed: %s in %s (%s:%d)", hipGetErrorString(e), short_func(func).c_str(), base_name(file), line);
-}
-void wait_event(hipEvent_t ev, const char *func, const char *file, int line) {
-    double waited = 0.0;
-    const hipError_t e = poll_until([&] { return hipEventQuery(ev); }, sync_timeout_s(), &waited);
-    if (e == hipSuccess) return;
-    if (e == hipErrorNotReady) timeout_report("event wait", func, file, line, waited, nullptr);
-    fail(SCANRS_ERR_DEVICE, "event wait failed: %s in %s (%s:%d)", hipGetErrorString(e), short_func(func).c_str(), base_name(file), line);
-}
-void wait_device(const char *func, const char *file, int line) {
-    // the null stream of a process is ordered behind every blocking stream: querying it covers "everything queued so far"
-    wait_stream(nullptr, func, file, line);
-}
-bool wait_stream_quiet(hipStream_t s) noexcept {
-    const hipError_t e = poll_until([&] { return hipStreamQuery(s); }, sync_timeout_s(), nullptr);
-    if (e != hipSuccess) (void)hipGetLastError();
-    return e == hipSuccess;
-}
-bool wait_event_quiet(hipEvent_t ev) noexcept {
-    const hipError_t e = poll_until([&] { return hipEventQuery(ev); }, sync_timeout_s(), nullptr);
-    if (e != hipSuccess) (void)hipGetLastError();
-    return e == hipSuccess;
-}
-
-template <typename F>
-static int guard(F &&f) {
-    try {
-        f();
-        return SCANRS_OK;
-    } catch (const Failure &e) {
-        return e.code;
-    } catch (const std::bad_alloc &) {
-        set_error("out of host memory");
-        return SCANRS_ERR_DEVICE;
-    } catch (const std::exception &e) {
-        set_error("internal error: %s", e.what());
-        return SCANRS_ERR_DEVICE;
-    }
-}
-
-static bool device_ok() {
-    static int cached = -1;
-    if (cached < 0) {
-        int n = 0;
-        if (hipGetDeviceCount(&n) != hipSuccess || n <= 0) {
-            cached = 0;
-        } else {
-            hipDeviceProp_t p;
-            int dev = 0;
-            (void)hipGetDevice(&dev);
-            cached = (hipGetDeviceProperties(&p, dev) == hipSuccess && strncmp(p.gcnArchName, "gfx950", 6) == 0) ? 1 : 0;
-        }
-    }
-    return cached == 1;
-}
-// After a timed-out wait: is the device idle again? Non-blocking questions only (hipDeviceSynchronize would be an unbounded wait): the
-// null stream is ordered behind every blocking stream, and the library's own streams - the overflow gather's and the helper
-// thread's are non-blocking, the legacy stream says nothing about them - are asked one by one through the handles of
-// this process. Clears the flag when all of them report idle twice in a row 10 ms apart.
-static bool device_recovered() {
-    if (!device_lost()) return true;
-    for (int i = 0; i < 2; i++) {
-        if (hipStreamQuery(nullptr) != hipSuccess) {
-            (void)hipGetLastError();
-            return false;
-        }
-        if (!all_library_streams_idle()) return false;
-        std::this_thread::sleep_for(std::chrono::milliseconds(10));
-    }
-    g_device_lost.store(false, std::memory_order_release);
-    return true;
-}
-static void need_device() {
-    if (!device_ok())
-        fail(SCANRS_ERR_DEVICE, "no gfx950 (MI355X) device is usable from this process; scanrs_amd has no CPU fallback");
-    if (!device_recovered())
-        fail(SCANRS_ERR_DEVICE, "a device wait of this process timed out earlier (sync_timeout_s) and the device has not been seen idle since: the library "
-                                "does not queue new work or reuse memory that kernels may still be using");
-}
-
-// ---- device memory: allocation with retry, deferred frees, block cache (common.hpp) ------------------------------------
-namespace {
-struct Block {
-    void *p;
-    size_t size; // what hipMalloc was asked for
-    int dev;
-};
-struct Reserve { // one large allocation made ahead of time (scanrs_reserve_device_memory) that later requests are carved from
-    char *base;
-    size_t size;
-    int dev;
-    std::map<size_t, size_t> holes; // offset -> length of every unused stretch, neighbours merged: released blocks are reusable at any size
-    size_t unused() const {
-        size_t n = 0;
-        for (auto &h : holes) n += h.second;
-        return n;
-    }
-    bool owns(const void *p) const { return (const char *)p >= base && (const char *)p < base + size; }
-    // best fit (the smallest hole that holds it: the big holes stay whole for the big requests); nullptr when none does
-    void *take(size_t want) {
-        auto best = holes.end();
-        for (auto it = holes.begin(); it != holes.end(); ++it)
-            if (it->second >= want && (best == holes.end() || it->second < best->second)) best = it;
-        if (best == holes.end()) return nullptr;
-        const size_t off = best->first, len = best->second;
-        holes.erase(best);
-        if (len > want) holes.emplace(off + want, len - want);
-        return base + off;
-    }
-    void give(void *p, size_t len) {
-        size_t off = (size_t)((char *)p - base);
-        auto next = holes.lower_bound(off);
-        if (next != holes.begin()) {
-            auto prev = std::prev(next);
-            if (prev->first + prev->second == off) {
-                off = prev->first;
-                len += prev->second;
-                holes.erase(prev);
-            }
-        }
-        if (next != holes.end() && off + len == next->first) {
-            len += next->second;
-            holes.erase(next);
-        }
-        holes.emplace(off, len);
-    }
-};
-struct DeadBlock {
-    void *p;
-    const Storage *owner; // the handle that was current on the releasing thread (nullptr: none)
-    hipEvent_t ev[5];     // recorded at the release on every stream of the owner: work queued before the release is done when they are
-    int n_ev;
-    int ev_dev;           // the device those events belong to (an event records only on streams of the device it was created on)
-};
-struct DeviceMemory {
-    std::mutex mu;
-    std::vector<DeadBlock> dead;                        // released by their owners, waiting for their release events
-    std::map<int, std::vector<hipEvent_t>> release_events; // spare events by device (created once, reused; ADVICE r5: one pool for all devices handed a shard thread another device's event)
-    size_t ownerless = 0;                               // entries of `dead` without an owner: they wait for a moment at which every library stream is idle
-    std::map<void *, std::pair<size_t, int>> live;      // every block handed out: pointer -> (size, device)
-    std::vector<Reserve> reserves;                      // blocks carved from a reserve go back into it (Reserve::give), never to the driver one by one
-    std::multimap<std::pair<int, size_t>, void *> idle; // cached blocks by (device, size)
-    size_t idle_bytes = 0;
-    double cache_fraction = 0.5; // of the device's memory; 0: no cache (every released block goes back to the driver)
-};
-DeviceMemory &devmem() {
-    static DeviceMemory *g = new DeviceMemory(); // never destroyed: handles freed by static destructors of the host program still find it
-    return *g;
-}
-std::atomic<uint64_t> g_alloc_us{0}, g_alloc_calls{0};
-constexpr size_t CACHE_MIN = 1u << 20; // smaller blocks go straight back
-size_t round_block(size_t bytes) { return bytes >= CACHE_MIN ? (bytes + (2u << 20) - 1) & ~((size_t)(2u << 20) - 1) : bytes; }
-} // namespace
-// A released block may be handed out again once everything that was queued BEFORE the release, on any stream of the releasing handle
-// (main, the two auxiliary ones, the overflow gather's, the helper thread's), has run: one event per such stream, recorded here. Work
-// queued later cannot name the block. (hipFree used to give this guarantee by waiting for the whole device; ADVICE r4: a process-wide
-// list flushed by whoever saw its own main stream idle did not.)
-void device_free_later(void *p, size_t) {
-    if (!p) return;
-    DeadBlock db{p, tl_handle, {nullptr, nullptr, nullptr, nullptr, nullptr}, 0, 0};
-    DeviceMemory &g = devmem();
-    (void)hipGetDevice(&db.ev_dev); // (the handle's streams live on the device that is current on the thread that works for it)
-    if (!tl_handle && tl_dying) {
-        db.owner = tl_dying; // a member of a handle that is being destroyed: its destructor has drained every stream that could name the block
-    } else if (const Storage *st = tl_handle) {
-        hipStream_t list[5] = {st->stream, st->aux_stream, st->aux2_stream, st->ov_stream, storage_side_stream(*st)};
-        for (hipStream_t q : list) {
-            if (!q) continue;
-            hipEvent_t e = nullptr;
-            {
-                std::lock_guard<std::mutex> lk(g.mu);
-                auto &pool = g.release_events[db.ev_dev];
-                if (!pool.empty()) {
-                    e = pool.back();
-                    pool.pop_back();
-                }
-            }
-            if ((!e && hipEventCreateWithFlags(&e, hipEventDisableTiming) != hipSuccess) || hipEventRecord(e, q) != hipSuccess) {
-                (void)hipGetLastError();
-                if (e) (void)hipEventDestroy(e);
-                db.owner = nullptr; // no proof of completion for this one: it waits for a device-wide idle point
-                continue;
-            }
-            db.ev[db.n_ev++] = e;
-        }
-    }
-    std::lock_guard<std::mutex> lk(g.mu);
-    if (!db.owner) g.ownerless++;
-    g.dead.push_back(db);
-}
-// every stream a handle queues work on (main, the two auxiliary ones, the overflow gather's, the helper thread's) has run dry
-static bool storage_streams_idle(const Storage *st) {
-    if (!st) return true;
-    hipStream_t list[5] = {st->stream, st->aux_stream, st->aux2_stream, st->ov_stream, nullptr};
-    list[4] = storage_side_stream(*st);
-    for (hipStream_t q : list) {
-        if (!q) continue;
-        if (hipStreamQuery(q) != hipSuccess) {
-            (void)hipGetLastError();
-            return false;
-        }
-    }
-    return true;
-}
-// Released blocks of 1 MB and more are kept for the next allocation of about their size instead of going back to the driver:
-// VRAM that was just freed is scrubbed in the background and an allocation that lands on it waits for the scrubber — seconds for
-// the tens of GB a handle holds (the second and third handle of one process took 2.4 / 4.1 s for their first PCA instead of 0.4).
-// At most `device_cache_fraction` (default one half) of the device's memory is kept; scanrs_release_cached_memory() and a failed
-// allocation empty the cache.
-// Moves released blocks to the cache (or back to the driver): those whose release events have completed (device_free_later); with
-// `owner_gone` also every block of that (destroyed) handle; with `everything` (the caller has just seen the whole device idle) all.
-static void device_free_flush_impl(const Storage *owner, bool owner_gone, bool everything, bool cache_only = false) noexcept {
-    DeviceMemory &g = devmem();
-    if (device_lost()) return; // kernels of a timed-out call may still use them: leaked on purpose
-    std::vector<Block> to_free;
-    // Blocks released while no handle was current carry no events (every reset_map + normalize cycle stranded the old map
-    // arrays until an out-of-memory retry wiped the cache). They may go once every stream of the library has been seen idle: work
-    // queued before their release is done then, work queued later cannot name them. (Asked outside the lock: the handles' own mutex.)
-    bool ownerless_done = everything;
-    if (!ownerless_done && !cache_only) {
-        bool any = false;
-        {
-            std::lock_guard<std::mutex> lk(g.mu);
-            any = g.ownerless > 0;
-        }
-        if (any) {
-            ownerless_done = hipStreamQuery(nullptr) == hipSuccess && all_library_streams_idle();
-            if (!ownerless_done) (void)hipGetLastError();
-        }
-    }
-    {
-        std::lock_guard<std::mutex> lk(g.mu);
-        if (g.dead.empty()) return;
-        size_t cap = 0;
-        if (g.cache_fraction > 0.0) {
-            size_t fr = 0, tot = 0;
-            if (hipMemGetInfo(&fr, &tot) == hipSuccess) cap = (size_t)((double)tot * g.cache_fraction);
-        }
-        std::vector<DeadBlock> keep;
-        for (DeadBlock &db : g.dead) {
-            // done with: its release events have all completed / its owner is gone (streams drained by the destructor) / the caller has
-            // just seen the whole device idle. A block released outside any handle waits for the last case.
-            bool done = everything || (owner_gone && db.owner == owner) || (ownerless_done && db.owner == nullptr);
-            if (!done && db.owner != nullptr) {
-                done = true;
-                for (int i = 0; i < db.n_ev && done; i++) {
-                    const hipError_t e = hipEventQuery(db.ev[i]);
-                    if (e != hipSuccess) {
-                        (void)hipGetLastError();
-                        done = false;
-                    }
-                }
-            }
-            if (!done) {
-                keep.push_back(db);
-                continue;
-            }
-            void *p = db.p;
-            auto it = g.live.find(p);
-            if (!db.owner && g.ownerless) g.ownerless--;
-            if (it == g.live.end()) { // not ours (cannot happen)
-                for (int i = 0; i < db.n_ev; i++) g.release_events[db.ev_dev].push_back(db.ev[i]);
-                continue;
-            }
-            const Block b{p, it->second.first, it->second.second};
-            Reserve *home = nullptr;
-            for (Reserve &r : g.reserves)
-                if (r.owns(p)) home = &r;
-            size_t idle_dev = 0; // what the cache holds for THIS block's device (the limit is a share of one device's memory)
-            for (auto ii = g.idle.lower_bound(std::make_pair(b.dev, (size_t)0)); ii != g.idle.end() && ii->first.first == b.dev; ++ii) idle_dev += ii->first.second;
-            const bool to_cache = home || (b.size >= CACHE_MIN && idle_dev + b.size <= cap);
-            if (!to_cache && cache_only) { // in the middle of a call: hipFree would wait for the whole device, the block stays on the list
-                if (!db.owner) g.ownerless++;
-                keep.push_back(db);
-                continue;
-            }
-            for (int i = 0; i < db.n_ev; i++) g.release_events[db.ev_dev].push_back(db.ev[i]);
-            g.live.erase(it);
-            if (home) {
-                home->give(p, b.size);
-            } else if (to_cache) {
-                g.idle.emplace(std::make_pair(b.dev, b.size), p);
-                g.idle_bytes += b.size;
-            } else {
-                to_free.push_back(b);
-            }
-        }
-        g.dead.swap(keep);
-    }
-    if (to_free.empty()) return;
-    const auto t0 = std::chrono::steady_clock::now();
-    size_t bytes = 0;
-    for (auto &b : to_free) {
-        (void)hipFree(b.p);
-        bytes += b.size;
-    }
-    if (trace_on())
-        fprintf(stderr, "[scanrs trace] released %zu buffers, %.2f GB, in %.2f ms\n", to_free.size(), (double)bytes / 1e9,
-                std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t0).count());
-}
-void device_free_flush() noexcept { device_free_flush_impl(tl_handle, false, false); }
-// the handle at `owner` has been destroyed (its streams were drained by its destructor): its blocks can go
-void device_free_flush_owner_gone(const void *owner) noexcept { device_free_flush_impl(static_cast<const Storage *>(owner), true, false); }
-void device_cache_release() noexcept {
-    // every owner's blocks: only behind a wait for the whole device (bounded like every other wait; if it does not come, nothing is released)
-    {
-        bool idle = false;
-        if (!device_lost()) {
-            // (the other shard threads of a single-process multi-GPU run rarely all pause at the instant of ONE question: polled, bounded)
-            const hipError_t e = poll_until([&] {
-                const hipError_t q = hipStreamQuery(nullptr);
-                if (q != hipSuccess) return q;
-                return all_library_streams_idle() ? hipSuccess : hipErrorNotReady;
-            }, sync_timeout_s(), nullptr);
-            if (e != hipSuccess) (void)hipGetLastError();
-            idle = e == hipSuccess;
-        }
-        if (!idle) return;
-        device_free_flush_impl(nullptr, false, true);
-    }
-    DeviceMemory &g = devmem();
-    std::vector<void *> take;
-    {
-        std::lock_guard<std::mutex> lk(g.mu);
-        for (auto it = g.idle.begin(); it != g.idle.end();) {
-            take.push_back(it->second);
-            g.idle_bytes -= it->first.second;
-            it = g.idle.erase(it);
-        }
-        for (auto it = g.reserves.begin(); it != g.reserves.end();) { // a reserve nothing is handed out from any more goes back whole
-            if (it->unused() == it->size) {
-                take.push_back(it->base);
-                it = g.reserves.erase(it);
-            } else {
-                ++it;
-            }
-        }
-    }
-    for (void *p : take) (void)hipFree(p);
-}
-void device_reserve(size_t bytes) {
-    if (!bytes) return;
-    DeviceMemory &g = devmem();
-    int dev = 0;
-    (void)hipGetDevice(&dev);
-    void *p = nullptr;
-    const hipError_t e = hipMalloc(&p, bytes);
-    if (e != hipSuccess) {
-        (void)hipGetLastError();
-        fail(SCANRS_ERR_DEVICE, "reserving %.2f GB of device memory failed: %s", (double)bytes / 1e9, hipGetErrorString(e));
-    }
-    std::lock_guard<std::mutex> lk(g.mu);
-    Reserve r{(char *)p, bytes, dev, {}};
-    r.holes.emplace(0, bytes);
-    g.reserves.push_back(std::move(r));
-}
-void device_cache_set_fraction(double f) {
-    DeviceMemory &g = devmem();
-    {
-        std::lock_guard<std::mutex> lk(g.mu);
-        g.cache_fraction = f;
-    }
-    if (f <= 0.0) device_cache_release();
-}
-size_t device_cache_bytes() { // cached blocks of the CURRENT device (a single-process multi-GPU program has one cache per device in the same map)
-    DeviceMemory &g = devmem();
-    device_free_flush_impl(nullptr, false, false, true); // released blocks whose events have completed count
-    int dev = 0;
-    (void)hipGetDevice(&dev);
-    std::lock_guard<std::mutex> lk(g.mu);
-    size_t n = 0;
-    for (auto it = g.idle.lower_bound(std::make_pair(dev, (size_t)0)); it != g.idle.end() && it->first.first == dev; ++it) n += it->first.second;
-    return n;
-}
-// what scanrs_reserve_device_memory set aside on this device and nobody has been handed yet
-size_t device_reserve_unused_bytes() {
-    DeviceMemory &g = devmem();
-    device_free_flush_impl(nullptr, false, false, true);
-    int dev = 0;
-    (void)hipGetDevice(&dev);
-    std::lock_guard<std::mutex> lk(g.mu);
-    size_t n = 0;
-    for (const Reserve &r : g.reserves)
-        if (r.dev == dev) n += r.unused();
-    return n;
-}
-// SCANRS_TRACE: what the library holds on the device, block by block (>= 256 MB), and what its reserves have left
-static void device_memory_report(const char *why) {
-    DeviceMemory &g = devmem();
-    std::lock_guard<std::mutex> lk(g.mu);
-    std::vector<size_t> big;
-    size_t live = 0, dead = 0;
-    for (auto &kv : g.live) {
-        live += kv.second.first;
-        if (kv.second.first >= (256u << 20)) big.push_back(kv.second.first);
-    }
-    for (auto &db : g.dead) {
-        auto it = g.live.find(db.p);
-        if (it != g.live.end()) dead += it->second.first;
-    }
-    std::sort(big.begin(), big.end(), std::greater<size_t>());
-    fprintf(stderr, "[scanrs trace] device memory (%s): %.2f GB in %zu blocks (%.2f GB of them released, waiting for their events), %.2f GB cached; blocks of 256 MB and more:", why,
-            (double)live / 1e9, g.live.size(), (double)dead / 1e9, (double)g.idle_bytes / 1e9);
-    for (size_t b : big) fprintf(stderr, " %.2f", (double)b / 1e9);
-    fprintf(stderr, "\n");
-    for (const Reserve &r : g.reserves) {
-        fprintf(stderr, "[scanrs trace]   reserve of %.2f GB on device %d, unused %.2f GB in %zu stretches:", (double)r.size / 1e9, r.dev, (double)r.unused() / 1e9, r.holes.size());
-        for (auto &h : r.holes) fprintf(stderr, " %.2f", (double)h.second / 1e9);
-        fprintf(stderr, "\n");
-    }
-}
-size_t device_live_bytes() {
-    DeviceMemory &g = devmem();
-    std::lock_guard<std::mutex> lk(g.mu);
-    size_t n = 0;
-    for (auto &kv : g.live) n += kv.second.first;
-    return n;
-}
-void *device_alloc(size_t bytes) {
-    DeviceMemory &g = devmem();
-    const size_t want = round_block(bytes);
-    int dev = 0;
-    (void)hipGetDevice(&dev);
-    if (want >= CACHE_MIN) { // a cached block of this size, or up to 1/8 larger
-        bool any_dead;
-        {
-            std::lock_guard<std::mutex> lk(g.mu);
-            any_dead = !g.dead.empty();
-        }
-        if (any_dead) device_free_flush_impl(nullptr, false, false, true); // blocks whose release events have completed join the cache first
-        std::lock_guard<std::mutex> lk(g.mu);
-        auto it = g.idle.lower_bound(std::make_pair(dev, want));
-        if (it != g.idle.end() && it->first.first == dev && it->first.second <= want + want / 8) {
-            void *p = it->second;
-            g.live[p] = std::make_pair(it->first.second, dev);
-            g.idle_bytes -= it->first.second;
-            g.idle.erase(it);
-            return p;
-        }
-    }
-    if (want >= CACHE_MIN) { // carve from a reserve made ahead of time
-        std::lock_guard<std::mutex> lk(g.mu);
-        for (Reserve &r : g.reserves) {
-            if (r.dev != dev) continue;
-            if (void *p = r.take(want)) {
-                g.live[p] = std::make_pair(want, dev);
-                return p;
-            }
-        }
-    }
-    if (want >= (1u << 30) && trace_on()) device_memory_report("no cached block and no reserve holds the request, asking the driver");
-    void *p = nullptr;
-    const auto t0 = std::chrono::steady_clock::now();
-    hipError_t e = hipMalloc(&p, want);
-    if (e == hipErrorOutOfMemory || e == hipErrorMemoryAllocation) { // cached blocks and buffers waiting for their release may be all that stands in the way
-        (void)hipGetLastError();
-        device_cache_release();
-        e = hipMalloc(&p, want);
-    }
-    const double us = std::chrono::duration<double, std::micro>(std::chrono::steady_clock::now() - t0).count();
-    g_alloc_us.fetch_add((uint64_t)us, std::memory_order_relaxed);
-    g_alloc_calls.fetch_add(1, std::memory_order_relaxed);
-    if (e != hipSuccess) {
-        (void)hipGetLastError();
-        fail(SCANRS_ERR_DEVICE, "hipMalloc of %.3f GB failed: %s", (double)want / 1e9, hipGetErrorString(e));
-    }
-    if (us > 2000.0 && trace_on()) fprintf(stderr, "[scanrs trace]   hipMalloc of %.2f GB took %.1f ms\n", (double)want / 1e9, us / 1e3);
-    {
-        std::lock_guard<std::mutex> lk(g.mu);
-        g.live[p] = std::make_pair(want, dev);
-    }
-    return p;
-}
-uint64_t device_alloc_us() { return g_alloc_us.load(std::memory_order_relaxed); }
-uint64_t device_alloc_calls() { return g_alloc_calls.load(std::memory_order_relaxed); }
-
-// ---- Profile -----------------------------------------------------------------------------------
-hipEvent_t Profile::take() {
-    if (!pool.empty()) {
-        hipEvent_t e = pool.back();
-        pool.pop_back();
-        return e;
-    }
-    hipEvent_t e;
-    SCANRS_HIP(hipEventCreate(&e));
-    return e;
-}
-void Profile::begin(hipStream_t s, const char *name, double bytes, double onchip) {
-    Rec r{name, take(), take(), bytes, onchip};
-    SCANRS_HIP(hipEventRecord(r.a, s));
-    pending.push_back(r);
-}
-void Profile::end(hipStream_t s) {
-    if (pending.empty()) return;
-    (void)hipEventRecord(pending.back().b, s);
-}
-void Profile::resolve() {
-    for (auto &r : pending) {
-        float ms = 0.f;
-        if (wait_event_quiet(r.b) && hipEventElapsedTime(&ms, r.a, r.b) == hipSuccess) {
-            auto &st = stats[r.name];
-            st.launches++;
-            st.ms += ms;
-            st.bytes += r.bytes;
-            st.onchip += r.onchip;
-        }
-        pool.push_back(r.a);
-        pool.push_back(r.b);
-    }
-    pending.clear();
-}
-void Profile::reset() {
-    resolve();
-    stats.clear();
-}
-Profile::~Profile() {
-    for (auto &r : pending) {
-        (void)hipEventDestroy(r.a);
-        (void)hipEventDestroy(r.b);
-    }
-    for (auto e : pool) (void)hipEventDestroy(e);
-}
-
-// ---- Storage -------------------------------------------------------------------------------------
-// ---- pinned host staging buffers, kept across handles ------------------------------------------------------------------------
-// A handle stages its seeded start panel (26 MB) and the delivery of V (ring of 8 x 8 MB) through pinned memory; pinning 64 MB costs
-// 5-8 ms, once per handle until round 4. Buffers go back to a small pool when their handle dies, and scanrs_init() pins the first
-// one ahead of the first call (portable: usable from every device of a single-process multi-GPU program).
-namespace {
-struct PinnedPool {
-    std::mutex mu;
-    std::vector<std::pair<void *, size_t>> idle;
-    size_t idle_bytes = 0;
-};
-PinnedPool &pinned_pool() {
-    static PinnedPool *p = new PinnedPool(); // never destroyed: handles may outlive static destruction order
-    return *p;
-}
-} // namespace
-void *pinned_take(size_t bytes, size_t *got) {
-    PinnedPool &g = pinned_pool();
-    {
-        std::lock_guard<std::mutex> lk(g.mu);
-        int best = -1;
-        for (int i = 0; i < (int)g.idle.size(); i++)
-            if (g.idle[i].second >= bytes && (best < 0 || g.idle[i].second < g.idle[best].second)) best = i;
-        if (best >= 0) {
-            void *p = g.idle[best].first;
-            *got = g.idle[best].second;
-            g.idle_bytes -= *got;
-            g.idle.erase(g.idle.begin() + best);
-            return p;
-        }
-    }
-    void *p = nullptr;
-    SCANRS_HIP(hipHostMalloc(&p, bytes, hipHostMallocPortable));
-    *got = bytes;
-    return p;
-}
-void pinned_give(void *p, size_t bytes) noexcept {
-    if (!p) return;
-    PinnedPool &g = pinned_pool();
-    {
-        std::lock_guard<std::mutex> lk(g.mu);
-        if (g.idle.size() < 4 && g.idle_bytes + bytes <= ((size_t)1 << 30)) {
-            g.idle.emplace_back(p, bytes);
-            g.idle_bytes += bytes;
-            return;
-        }
-    }
-    (void)hipHostFree(p);
-}
-
-struct Storage::SideBuild {
-    std::thread th;
-    hipStream_t stream = nullptr;
-    // what the helper makes, in this order: [copy of `first` if it does not exist] -> layout of `first` -> [copy of `second`] -> layout
-    // of `second`; a waiter needs one copy (or its layout) and waits for that stage only
-    const SparseCopy *order[2] = {nullptr, nullptr};
-    bool want_layout[2] = {false, false};
-    std::mutex mu;
-    std::condition_variable cv;
-    bool copy_done[2] = {false, false}, layout_done[2] = {false, false}; // by position in `order`
-    bool finished = false;
-    int code = SCANRS_OK;
-    std::string err;
-    double ms = 0.0;
-};
-static hipStream_t storage_side_stream(const Storage &st) { return st.side ? st.side->stream : nullptr; }
-// Waits until the helper has finished with `target` (nullptr: with everything) and rethrows its failure. `need_layout` false: the
-// copy itself is enough (a reader of the triplet).
-void Storage::side_join_if(const SparseCopy *target, bool need_layout) {
-    if (!side) return;
-    SideBuild *sb = side;
-    const auto t0 = std::chrono::steady_clock::now();
-    bool all = target == nullptr;
-    {
-        std::unique_lock<std::mutex> lk(sb->mu);
-        if (target) {
-            int pos = sb->order[0] == target ? 0 : sb->order[1] == target ? 1 : -1;
-            if (pos < 0) return; // the helper does not touch this copy
-            const double dl = sync_timeout_s() * 4.0; // builds are many device waits long; each of them is bounded by itself
-            const bool ok = sb->cv.wait_for(lk, std::chrono::duration<double>(dl), [&] {
-                return sb->finished || sb->code != SCANRS_OK || (need_layout ? sb->layout_done[pos] : sb->copy_done[pos]);
-            });
-            if (!ok) fail(SCANRS_ERR_DEVICE, "the helper thread that builds the second orientation did not finish a stage within %.0f s", dl);
-            all = sb->finished || sb->code != SCANRS_OK;
-        }
-    }
-    if (all) { // the helper is done (or failed): take it down
-        {
-            std::lock_guard<std::mutex> lk(g_storages_mu); // (all_library_streams_idle reads `side` under this mutex: it sees the helper's stream or nothing, never a destroyed one)
-            side = nullptr;
-        }
-        if (sb->th.joinable()) sb->th.join();
-        if (sb->stream) (void)hipStreamDestroy(sb->stream);
-        const int code = sb->code;
-        const std::string err = sb->err;
-        if (trace_on()) fprintf(stderr, "[scanrs trace] side build: %.3f ms on the helper thread\n", sb->ms);
-        delete sb;
-        t_side_wait_us += (uint64_t)std::chrono::duration<double, std::micro>(std::chrono::steady_clock::now() - t0).count();
-        if (code != SCANRS_OK && std::uncaught_exceptions() == 0) fail(code, "%s", err.c_str());
-        return;
-    }
-    t_side_wait_us += (uint64_t)std::chrono::duration<double, std::micro>(std::chrono::steady_clock::now() - t0).count();
-}
-Storage::~Storage() {
-    // Out of the set of handles FIRST (another thread's all_library_streams_idle walked a storage whose streams were
-    // already destroyed); while this destructor drains the streams the process counts as busy.
-    {
-        std::lock_guard<std::mutex> lk(g_storages_mu);
-        g_storages.erase(this);
-        g_storages_dying.fetch_add(1, std::memory_order_acq_rel);
-    }
-    struct Done {
-        ~Done() { g_storages_dying.fetch_sub(1, std::memory_order_acq_rel); }
-    } done_;
-    if (side) {
-        try {
-            side_join_if(nullptr, true);
-        } catch (const Failure &) {
-        }
-    }
-    if (host_stage) pinned_give(host_stage, host_stage_bytes);
-    if (aux_stream) {
-        (void)wait_stream_quiet(aux_stream);
-        (void)hipStreamDestroy(aux_stream);
-    }
-    if (aux2_stream) {
-        (void)wait_stream_quiet(aux2_stream);
-        (void)hipStreamDestroy(aux2_stream);
-    }
-    if (ov_stream) {
-        (void)wait_stream_quiet(ov_stream);
-        (void)hipStreamDestroy(ov_stream);
-    }
-    if (ev_in) (void)hipEventDestroy(ev_in);
-    if (ev_ov) (void)hipEventDestroy(ev_ov);
-    if (stream) {
-        (void)wait_stream_quiet(stream);
-        (void)hipStreamDestroy(stream);
-    }
-}
-// Four streams per handle: the main stream (sparse products: the persistent tile kernel must get its CUs first) at the default
-// priority, the overflow gather (fills the registers the tile kernel leaves) and the two auxiliary streams (dense work nothing
-// waits for until the end of the iterations) at the lowest.
-static int stream_priority(int level) {
-    int least = 0, greatest = 0;
-    (void)hipDeviceGetStreamPriorityRange(&least, &greatest); // numerically greatest <= least
-    (void)level;
-    return least;
-}
-hipStream_t Storage::aux() {
-    if (!overlap) return stream;
-    if (!aux_stream) {
-        // lowest priority: at the end of a persistent tile kernel the NEXT one (main stream) gets the CUs first and this stream's
-        // dense kernels fill what its tail and the overflow gather's tail leave — at equal priority a 2-3 ms projection GEMM that
-        // became runnable at the same moment held the next sparse product back by its whole duration
-        SCANRS_HIP(hipStreamCreateWithPriority(&aux_stream, hipStreamDefault, stream_priority(2)));
-    }
-    return aux_stream;
-}
-hipStream_t Storage::aux2() {
-    if (!overlap) return stream;
-    if (!aux2_stream) SCANRS_HIP(hipStreamCreateWithPriority(&aux2_stream, hipStreamDefault, stream_priority(2)));
-    return aux2_stream;
-}
-hipStream_t Storage::ov() {
-    if (!ov_stream) {
-        // lowest priority: the persistent tile kernel's workgroups are placed first, the gather fills what is left of a CU
-        SCANRS_HIP(hipStreamCreateWithPriority(&ov_stream, hipStreamNonBlocking, stream_priority(1)));
-        SCANRS_HIP(hipEventCreateWithFlags(&ev_in, hipEventDisableTiming));
-        SCANRS_HIP(hipEventCreateWithFlags(&ev_ov, hipEventDisableTiming));
-    }
-    return ov_stream;
-}
-SparseCopy &Storage::copy_with_outer_rows(bool outer_rows) {
-    const bool primary_outer_rows = storage == SCANRS_CSR;
-    if (outer_rows == primary_outer_rows) return primary;
-    side_join_if(&other, false); // a helper thread may be building it right now
-    if (!has_other) {
-        build_transposed_copy(*this, primary, other);
-        has_other = true;
-    }
-    other_settled = true;
-    return other;
-}
 
 // One exchange step. With the library's own transport (scanrs_mat_set_shard_comm) the collective is enqueued on the
 // handle's stream; the host hook form synchronises first (the hook's runtime knows nothing of our stream).
@@ -1111,10 +125,7 @@ void prepare_second_orientation(scanrs_mat *m, bool transpose_second, bool solve
     }
     sb->order[n] = second;
     sb->want_layout[n] = second_layout;
-    {
-        std::lock_guard<std::mutex> lk(g_storages_mu);
-        st.side = sb;
-    }
+    registry_set_side(st, sb);
     Storage *stp = &st;
     sb->th = std::thread([stp, sb, dev] {
         const auto t0 = std::chrono::steady_clock::now();
@@ -1143,7 +154,7 @@ void prepare_second_orientation(scanrs_mat *m, bool transpose_second, bool solve
         } catch (const Failure &e) {
             std::lock_guard<std::mutex> lk(sb->mu);
             sb->code = e.code;
-            sb->err = g_err; // this thread's message buffer
+            sb->err = scanrs_last_error(); // this thread's message buffer
         } catch (const std::exception &e) {
             std::lock_guard<std::mutex> lk(sb->mu);
             sb->code = SCANRS_ERR_DEVICE;
@@ -1205,6 +216,19 @@ static std::shared_ptr<DevBuf<double>> upload_vec(Storage &st, const double *h, 
     return b;
 }
 
+static std::shared_ptr<Storage> new_storage(uint64_t rows, uint64_t cols, int storage) {
+    auto st = std::make_shared<Storage>();
+    registry_add(st.get());
+    st->rows = rows;
+    st->cols = cols;
+    st->storage = storage;
+    // a blocking stream: legacy null-stream copies (ours and the host program's, e.g. torch's default
+    // stream that produced a device-resident input) stay ordered with the kernels launched here
+    SCANRS_HIP(hipStreamCreate(&st->stream));
+    st->scratch.stream = st->stream;
+    return st;
+}
+
 static void create_common(uint64_t rows, uint64_t cols, int storage, const uint64_t *indptr, const uint32_t *indices,
                           const uint32_t *values, bool device_src, scanrs_mat **out, bool sort_first = false) {
     Tick tick("create: upload + validate");
@@ -1215,18 +239,7 @@ static void create_common(uint64_t rows, uint64_t cols, int storage, const uint6
     if (storage != SCANRS_CSR && storage != SCANRS_CSC) fail(SCANRS_ERR_ARGUMENT, "storage must be 0 (CSR) or 1 (CSC)");
     if (!indptr) fail(SCANRS_ERR_ARGUMENT, "null indptr");
     if (rows > 0xFFFFFFFFull || cols > 0xFFFFFFFFull) fail(SCANRS_ERR_SHAPE, "dimensions must fit in u32 (AdaptiveVec limit)");
-    auto st = std::make_shared<Storage>();
-    {
-        std::lock_guard<std::mutex> lk(g_storages_mu);
-        g_storages.insert(st.get());
-    }
-    st->rows = rows;
-    st->cols = cols;
-    st->storage = storage;
-    // a blocking stream: legacy null-stream copies (ours and the host program's, e.g. torch's default
-    // stream that produced a device-resident input) stay ordered with the kernels launched here
-    SCANRS_HIP(hipStreamCreate(&st->stream));
-    st->scratch.stream = st->stream;
+    auto st = new_storage(rows, cols, storage);
     SparseCopy &cp = st->primary;
     cp.n_outer = storage == SCANRS_CSR ? rows : cols;
     cp.n_inner = storage == SCANRS_CSR ? cols : rows;
@@ -1276,16 +289,7 @@ static void create_common(uint64_t rows, uint64_t cols, int storage, const uint6
 // through the host. The copy comes from the library's own kernels (indices in range and ascending, no zeros), so the validation of
 // scanrs_mat_create_device has nothing to find; everything else is as create_common leaves it.
 static scanrs_mat *adopt_copy(uint64_t rows, uint64_t cols, int storage, SparseCopy &&made) {
-    auto st = std::make_shared<Storage>();
-    {
-        std::lock_guard<std::mutex> lk(g_storages_mu);
-        g_storages.insert(st.get());
-    }
-    st->rows = rows;
-    st->cols = cols;
-    st->storage = storage;
-    SCANRS_HIP(hipStreamCreate(&st->stream));
-    st->scratch.stream = st->stream;
+    auto st = new_storage(rows, cols, storage);
     SparseCopy &cp = st->primary;
     cp.n_outer = made.n_outer;
     cp.n_inner = made.n_inner;
@@ -1523,12 +527,47 @@ static void binom_impl(scanrs_mat *m, int kind) {
     SCANRS_SYNC(st.stream);
 }
 
+// Upload of an n_in x l panel (`in_is_l_by_n`: given as l x n_in, transposed on the way), `product(dX, ld, dY)`, download of the
+// n_out x l result (transposed back likewise). The caller has made the handle current.
+template <typename T, typename Product>
+static void dot_through_scratch(scanrs_mat *m, bool transpose, const T *h_in, uint32_t l, T *h_out, bool in_is_l_by_n, const char *key_in,
+                                const char *key_out, Product &&product) {
+    Storage &st = *m->st;
+    const uint64_t n_in = transpose ? m->rows() : m->cols();
+    const uint64_t n_out = transpose ? m->cols() : m->rows();
+    if (l == 0) return;
+    const uint32_t ld = even_up(l);
+    T *dX = st.scratch.get<T>(key_in, std::max<uint64_t>(1, n_in) * ld);
+    T *dY = st.scratch.get<T>(key_out, std::max<uint64_t>(1, n_out) * ld);
+    SCANRS_HIP(hipMemsetAsync(dX, 0, std::max<uint64_t>(1, n_in) * ld * sizeof(T), st.stream));
+    std::vector<T> tmp;
+    const T *src = h_in;
+    if (in_is_l_by_n) {
+        tmp.resize((size_t)n_in * l);
+        for (uint32_t i = 0; i < l; i++)
+            for (uint64_t j = 0; j < n_in; j++) tmp[j * l + i] = h_in[(size_t)i * n_in + j];
+        src = tmp.data();
+    }
+    if (n_in)
+        SCANRS_HIP(hipMemcpy2DAsync(dX, (size_t)ld * sizeof(T), src, (size_t)l * sizeof(T), (size_t)l * sizeof(T), n_in, hipMemcpyHostToDevice, st.stream));
+    SCANRS_SYNC(st.stream);
+    product(dX, ld, dY);
+    std::vector<T> res((size_t)n_out * l);
+    SCANRS_D2H_2D(res.data(), dY, (size_t)ld * sizeof(T), (size_t)l * sizeof(T), n_out, st.stream);
+    SCANRS_SYNC(st.stream);
+    if (in_is_l_by_n) {
+        for (uint64_t j = 0; j < n_out; j++)
+            for (uint32_t i = 0; i < l; i++) h_out[(size_t)i * n_out + j] = res[j * l + i];
+    } else if (!res.empty()) {
+        memcpy(h_out, res.data(), res.size() * sizeof(T));
+    }
+}
+
 } // namespace scanrs
 
 // =================================================================================================
 extern "C" {
 
-const char *scanrs_last_error(void) { return g_err; }
 int scanrs_device_available(void) {
     try {
         return device_ok() ? 1 : 0;
@@ -1608,12 +647,11 @@ void scanrs_mat_free(scanrs_mat *m) {
     if (!m) return;
     const Storage *owner = m->st.get();
     const bool last = m->st.use_count() == 1;
-    tl_dying = last ? owner : nullptr;
-    const Storage *prev = tl_handle;
-    if (!last) tl_handle = owner; // a view's own buffers (map arrays, offset): release events on the storage's streams, which live on
-    delete m;
-    tl_handle = prev;
-    tl_dying = nullptr;
+    {
+        DyingHandle dying(last ? owner : nullptr);
+        CurrentHandle cur(last ? current_handle() : owner, true); // a view's own buffers (map arrays, offset): release events on the storage's streams, which live on
+        delete m;
+    }
     // the handle's buffers (when this was the last view of its storage): its streams were drained by the destructor, nobody else queued work on them
     if (last) device_free_flush_owner_gone(owner);
 }
@@ -1848,36 +886,9 @@ int scanrs_mat_to_dense(scanrs_mat *m, double *out) {
 static void dot_host(scanrs_mat *m, bool transpose, const double *h_in, uint32_t l, double *h_out, bool in_is_l_by_n) {
     // transpose = false: out[rows x l] = A * in[cols x l].   transpose = true (rdot): lhs is l x rows, out is l x cols:
     // computed as (A^T lhs^T)^T exactly like ArrayBase::dot(&AdaptiveMat) (sqz/src/mat.rs:1124-1132).
-    Storage &st = *m->st;
-    CurrentHandle cur(&st);
-    const uint64_t n_in = transpose ? m->rows() : m->cols();
-    const uint64_t n_out = transpose ? m->cols() : m->rows();
-    if (l == 0) return;
-    const uint32_t ld = even_up(l);
-    double *dX = st.scratch.get<double>("dot_in", std::max<uint64_t>(1, n_in) * ld);
-    double *dY = st.scratch.get<double>("dot_out", std::max<uint64_t>(1, n_out) * ld);
-    SCANRS_HIP(hipMemsetAsync(dX, 0, std::max<uint64_t>(1, n_in) * ld * 8, st.stream));
-    std::vector<double> tmp;
-    const double *src = h_in;
-    if (in_is_l_by_n) {
-        tmp.resize((size_t)n_in * l);
-        for (uint32_t i = 0; i < l; i++)
-            for (uint64_t j = 0; j < n_in; j++) tmp[j * l + i] = h_in[(size_t)i * n_in + j];
-        src = tmp.data();
-    }
-    if (n_in)
-        SCANRS_HIP(hipMemcpy2DAsync(dX, (size_t)ld * 8, src, (size_t)l * 8, (size_t)l * 8, n_in, hipMemcpyHostToDevice, st.stream));
-    SCANRS_SYNC(st.stream);
-    mat_apply(m, transpose, dX, ld, l, dY, ld);
-    std::vector<double> res((size_t)n_out * l);
-    SCANRS_D2H_2D(res.data(), dY, (size_t)ld * 8, (size_t)l * 8, n_out, st.stream);
-    SCANRS_SYNC(st.stream);
-    if (in_is_l_by_n) {
-        for (uint64_t j = 0; j < n_out; j++)
-            for (uint32_t i = 0; i < l; i++) h_out[(size_t)i * n_out + j] = res[j * l + i];
-    } else if (!res.empty()) {
-        memcpy(h_out, res.data(), res.size() * 8);
-    }
+    CurrentHandle cur(m->st.get());
+    dot_through_scratch(m, transpose, h_in, l, h_out, in_is_l_by_n, "dot_in", "dot_out",
+                        [&](const double *dX, uint32_t ld, double *dY) { mat_apply(m, transpose, dX, ld, l, dY, ld); });
 }
 
 int scanrs_mat_dot(scanrs_mat *m, const double *rhs, uint32_t l, double *out) {
@@ -1898,35 +909,8 @@ static void dot_host_u32(scanrs_mat *m, bool transpose, const uint32_t *h_in, ui
     Storage &st = *m->st;
     CurrentHandle cur(&st);
     if (st.shard.active()) fail(SCANRS_ERR_ARGUMENT, "u32 products are not sharded");
-    const uint64_t n_in = transpose ? m->rows() : m->cols();
-    const uint64_t n_out = transpose ? m->cols() : m->rows();
-    if (l == 0) return;
-    const uint32_t ld = even_up(l);
-    uint32_t *dX = st.scratch.get<uint32_t>("dotu_in", std::max<uint64_t>(1, n_in) * ld);
-    uint32_t *dY = st.scratch.get<uint32_t>("dotu_out", std::max<uint64_t>(1, n_out) * ld);
-    SCANRS_HIP(hipMemsetAsync(dX, 0, std::max<uint64_t>(1, n_in) * ld * 4, st.stream));
-    std::vector<uint32_t> tmp;
-    const uint32_t *src = h_in;
-    if (transpose) {
-        tmp.resize((size_t)n_in * l);
-        for (uint32_t i = 0; i < l; i++)
-            for (uint64_t j = 0; j < n_in; j++) tmp[j * l + i] = h_in[(size_t)i * n_in + j];
-        src = tmp.data();
-    }
-    if (n_in)
-        SCANRS_HIP(hipMemcpy2DAsync(dX, (size_t)ld * 4, src, (size_t)l * 4, (size_t)l * 4, n_in, hipMemcpyHostToDevice, st.stream));
-    SCANRS_SYNC(st.stream);
-    SparseCopy &cp = copy_outer_view_rows(m, !transpose);
-    launch_spmm_u32(st, cp, dX, ld, l, dY, ld);
-    std::vector<uint32_t> res((size_t)n_out * l);
-    SCANRS_D2H_2D(res.data(), dY, (size_t)ld * 4, (size_t)l * 4, n_out, st.stream);
-    SCANRS_SYNC(st.stream);
-    if (transpose) {
-        for (uint64_t j = 0; j < n_out; j++)
-            for (uint32_t i = 0; i < l; i++) h_out[(size_t)i * n_out + j] = res[j * l + i];
-    } else if (!res.empty()) {
-        memcpy(h_out, res.data(), res.size() * 4);
-    }
+    dot_through_scratch(m, transpose, h_in, l, h_out, transpose, "dotu_in", "dotu_out",
+                        [&](const uint32_t *dX, uint32_t ld, uint32_t *dY) { launch_spmm_u32(st, copy_outer_view_rows(m, !transpose), dX, ld, l, dY, ld); });
 }
 int scanrs_mat_dot_u32(scanrs_mat *m, const uint32_t *rhs, uint32_t l, uint32_t *out) {
     return guard([&] {
@@ -2217,6 +1201,10 @@ int scanrs_mat_set_spmm_path(scanrs_mat *m, int path) {
         m->st->spmm_path = path;
     });
 }
+static void set_sync_timeout_checked(double value) {
+    if (!(value > 0.0) || !std::isfinite(value)) fail(SCANRS_ERR_ARGUMENT, "sync_timeout_s must be a positive number of seconds");
+    set_sync_timeout_s(value);
+}
 int scanrs_set_global_option(const char *key, double value) {
     return guard([&] {
         if (!key) fail(SCANRS_ERR_ARGUMENT, "null key");
@@ -2238,8 +1226,7 @@ int scanrs_set_global_option(const char *key, double value) {
             if (!(value >= 0.0) || value > 1.0) fail(SCANRS_ERR_ARGUMENT, "device_cache_fraction must be in [0, 1]");
             device_cache_set_fraction(value);
         } else if (k == "sync_timeout_s") { // deadline of every host-side wait for the device (common.hpp, "bounded waits")
-            if (!(value > 0.0) || !std::isfinite(value)) fail(SCANRS_ERR_ARGUMENT, "sync_timeout_s must be a positive number of seconds");
-            set_sync_timeout_s(value);
+            set_sync_timeout_checked(value);
         } else
             fail(SCANRS_ERR_ARGUMENT, "unknown global option '%s'", key);
     });
@@ -2340,8 +1327,7 @@ int scanrs_mat_set_option(scanrs_mat *m, const char *key, double value) {
         } else if (k == "d2h_threads") {
             st.d2h_threads = as_u32(1, 256);
         } else if (k == "sync_timeout_s") { // process-wide (the waits have no handle): same as scanrs_set_global_option
-            if (!(value > 0.0) || !std::isfinite(value)) fail(SCANRS_ERR_ARGUMENT, "sync_timeout_s must be a positive number of seconds");
-            set_sync_timeout_s(value);
+            set_sync_timeout_checked(value);
         } else if (k == "tile_spare_cus") {
             st.tile_spare_cus = value != 0.0;
         } else if (k == "spmv_row_table") {
@@ -2433,72 +1419,8 @@ int scanrs_mat_chol_rinv(scanrs_mat *m, const double *g, uint32_t n, uint64_t ro
 }
 
 // ---- host-only utilities exposed for the CPU test-suite (no device needed) --------------------------------------------
-// The bounded wait on an event that is never signalled: the library's own poll loop (poll_until + the timeout report) over a
-// query that always answers "not ready" — no HIP call is made, so it runs without a device. Returns SCANRS_ERR_DEVICE after
-// `timeout_s` with the message a real stuck wait would leave in scanrs_last_error().
 int scanrs_debug_arena_selftest(uint32_t rounds, uint64_t seed) {
-    return guard([&] {
-        constexpr size_t UNIT = 2u << 20;
-        Reserve r{reinterpret_cast<char *>((uintptr_t)1 << 40), 512 * UNIT, 0, {}};
-        r.holes.emplace(0, r.size);
-        std::map<char *, size_t> live; // base -> length
-        uint64_t z = seed * 0x9E3779B97F4A7C15ull + 1;
-        auto rnd = [&]() {
-            z ^= z << 13;
-            z ^= z >> 7;
-            z ^= z << 17;
-            return z;
-        };
-        auto check = [&]() {
-            size_t held = 0;
-            char *prev_end = r.base;
-            for (auto &b : live) {
-                if (b.first < prev_end || b.first + b.second > r.base + r.size) fail(SCANRS_ERR_NUMERICAL, "arena selftest: a live block overlaps its neighbour or leaves the range");
-                prev_end = b.first + b.second;
-                held += b.second;
-            }
-            if (held + r.unused() != r.size) fail(SCANRS_ERR_NUMERICAL, "arena selftest: %zu bytes held + %zu unused != %zu", held, r.unused(), r.size);
-            size_t end_prev = (size_t)-1;
-            for (auto &h : r.holes) {
-                if (h.second == 0 || h.first == end_prev) fail(SCANRS_ERR_NUMERICAL, "arena selftest: an empty hole, or two holes that should have merged");
-                end_prev = h.first + h.second;
-                for (auto &b : live) // no hole inside a live block
-                    if (r.base + h.first < b.first + b.second && b.first < r.base + h.first + h.second) fail(SCANRS_ERR_NUMERICAL, "arena selftest: a hole overlaps a live block");
-            }
-        };
-        for (uint32_t i = 0; i < rounds; i++) {
-            if (live.empty() || (rnd() % 3u) != 0u) {
-                const size_t want = (1 + rnd() % 40) * UNIT;
-                if (void *p = r.take(want)) {
-                    live[static_cast<char *>(p)] = want;
-                } else { // no hole holds it: then no hole may be that large
-                    for (auto &h : r.holes)
-                        if (h.second >= want) fail(SCANRS_ERR_NUMERICAL, "arena selftest: a request was refused although a hole holds it");
-                }
-            } else {
-                auto it = live.begin();
-                std::advance(it, (long)(rnd() % live.size()));
-                r.give(it->first, it->second);
-                live.erase(it);
-            }
-            check();
-        }
-        while (!live.empty()) {
-            r.give(live.begin()->first, live.begin()->second);
-            live.erase(live.begin());
-            check();
-        }
-        if (r.holes.size() != 1 || r.holes.begin()->first != 0 || r.holes.begin()->second != r.size) fail(SCANRS_ERR_NUMERICAL, "arena selftest: the arena is not whole at the end");
-    });
-}
-int scanrs_debug_wait_never(double timeout_s) {
-    return guard([&] {
-        if (!(timeout_s > 0.0)) fail(SCANRS_ERR_ARGUMENT, "timeout must be positive");
-        stage_mark("debug: injected wait", 1, 0);
-        double waited = 0.0;
-        const hipError_t e = poll_until([] { return hipErrorNotReady; }, timeout_s, &waited);
-        if (e == hipErrorNotReady) timeout_report("event wait (injected: never signalled)", "scanrs_debug_wait_never", __FILE__, __LINE__, waited, nullptr);
-    });
+    return guard([&] { reserve_selftest(rounds, seed); });
 }
 int scanrs_host_chol_upper(double *g, int n) { return chol_upper(g, n) ? 0 : SCANRS_ERR_NUMERICAL; }
 int scanrs_host_inv_upper(double *r, int n) {
@@ -2510,189 +1432,6 @@ int scanrs_host_sym_eig_topk(const double *a, int n, int k, double *w, double *z
     return sym_eig_topk(a, n, k, w, z) ? 0 : SCANRS_ERR_NUMERICAL;
 }
 
-} // extern "C"
-
-// ---- sSeq differential expression (sseq_host.cpp / sseq.hip) ---------------------------------------------------------------------------
-namespace scanrs {
-// the copy DE walks: the gene-major one when it is resident, else the cell-major one (no transposition is built for DE)
-static SparseCopy &sseq_resident_copy(scanrs_mat *m, bool *gene_major) {
-    Storage &st = *m->st;
-    if (st.shard.active()) fail(SCANRS_ERR_ARGUMENT, "differential expression of a sharded handle is not supported");
-    const bool want_base_rows = !m->transposed; // genes = view rows
-    const bool primary_rows = st.storage == SCANRS_CSR;
-    if (primary_rows == want_base_rows) {
-        *gene_major = true;
-        return st.primary;
-    }
-    if (st.other_settled) {
-        *gene_major = true;
-        return st.other;
-    }
-    *gene_major = false;
-    return st.primary;
-}
-} // namespace scanrs
-
-extern "C" {
-int scanrs_sseq_params(scanrs_mat *m, double zeta_quintile, const uint64_t *cell_indices, uint64_t n_sel, const double *umi_counts,
-                       double *size_factors, double *gene_means, double *gene_variances, uint8_t *use_genes, double *gene_moment_phi,
-                       double *zeta_hat, double *delta, double *gene_phi) {
-    return guard([&] {
-        if (!m || !size_factors || !gene_means || !gene_variances || !use_genes || !gene_moment_phi || !zeta_hat || !delta || !gene_phi)
-            fail(SCANRS_ERR_ARGUMENT, "null argument");
-        if (!(zeta_quintile >= 0.0 && zeta_quintile <= 1.0)) fail(SCANRS_ERR_ARGUMENT, "zeta_quintile must be in [0, 1]");
-        CurrentHandle cur(m->st.get());
-        bool gm = false;
-        SparseCopy &cp = sseq_resident_copy(m, &gm);
-        sseq_params(*m->st, cp, gm, m->rows(), m->cols(), zeta_quintile, cell_indices, n_sel, umi_counts, size_factors, gene_means,
-                    gene_variances, use_genes, gene_moment_phi, zeta_hat, delta, gene_phi);
-    });
-}
-int scanrs_sseq_params_from_moments(const double *mean_g, const double *var_g, uint64_t n, double sum_size_factors, double n_cells,
-                                    double n_genes, double zeta_quintile, uint8_t *use_genes, double *gene_moment_phi, double *zeta_hat,
-                                    double *delta, double *gene_phi) {
-    return guard([&] {
-        if ((n && (!mean_g || !var_g || !use_genes || !gene_moment_phi || !gene_phi)) || !zeta_hat || !delta)
-            fail(SCANRS_ERR_ARGUMENT, "null argument");
-        sseq_params_from_moments(mean_g, var_g, n, sum_size_factors, n_cells, n_genes, zeta_quintile, use_genes, gene_moment_phi, zeta_hat,
-                                 delta, gene_phi);
-    });
-}
-int scanrs_mat_group_sums(scanrs_mat *m, const int16_t *labels, uint32_t n_groups, uint64_t *sums, uint64_t *cells_per_group) {
-    return guard([&] {
-        if (!m || !labels || !sums) fail(SCANRS_ERR_ARGUMENT, "null argument");
-        CurrentHandle cur(m->st.get());
-        bool gm = false;
-        SparseCopy &cp = sseq_resident_copy(m, &gm);
-        sseq_group_sums(*m->st, cp, gm, m->rows(), m->cols(), labels, n_groups, sums, cells_per_group);
-    });
-}
-int scanrs_sseq_de(scanrs_mat *m, const int16_t *labels, uint32_t n_groups, int mode, const double *size_factors, const double *gene_means,
-                   const double *gene_phi, const uint8_t *use_genes, uint64_t big_count, const scanrs_snoop *snoop, uint64_t *sums_in,
-                   uint64_t *sums_out, double *p, double *p_adj, double *log2fc, double *mean_in, double *mean_out) {
-    return guard([&] {
-        if (!m || !labels || !size_factors || !gene_means || !gene_phi || !use_genes || !sums_in || !sums_out || !p || !p_adj || !log2fc ||
-            !mean_in || !mean_out)
-            fail(SCANRS_ERR_ARGUMENT, "null argument");
-        CurrentHandle cur(m->st.get());
-        bool gm = false;
-        SparseCopy &cp = sseq_resident_copy(m, &gm);
-        sseq_de_matrix(*m->st, cp, gm, m->rows(), m->cols(), labels, n_groups, mode, size_factors, gene_means, gene_phi, use_genes, big_count,
-                       snoop, sums_in, sums_out, p, p_adj, log2fc, mean_in, mean_out);
-    });
-}
-int scanrs_sseq_de_from_sums(uint64_t n_genes, uint32_t n_tests, const uint64_t *sums_a, const uint64_t *sums_b, const double *sf_a,
-                             const double *sf_b, const double *gene_means, const double *gene_phi, const uint8_t *use_genes,
-                             uint64_t big_count, const scanrs_snoop *snoop, double *p, double *p_adj, double *log2fc, double *mean_in,
-                             double *mean_out) {
-    return guard([&] {
-        if (n_genes && n_tests &&
-            (!sums_a || !sums_b || !sf_a || !sf_b || !gene_means || !gene_phi || !use_genes || !p || !p_adj || !log2fc || !mean_in || !mean_out))
-            fail(SCANRS_ERR_ARGUMENT, "null argument");
-        need_device();
-        sseq_de_sums(nullptr, n_genes, n_tests, sums_a, sums_b, sf_a, sf_b, gene_means, gene_phi, use_genes, big_count, snoop, p, p_adj, log2fc,
-                     mean_in, mean_out);
-    });
-}
-int scanrs_host_nb_exact_test(uint64_t x_a, uint64_t x_b, double sf_a, double sf_b, double mu, double phi, double *p) {
-    return guard([&] {
-        if (!p) fail(SCANRS_ERR_ARGUMENT, "null argument");
-        *p = sseq_host_exact_test(x_a, x_b, sf_a, sf_b, mu, phi);
-    });
-}
-int scanrs_host_nb_asymptotic_test(uint64_t x_a, uint64_t x_b, double sf_a, double sf_b, double mu, double phi, double *p) {
-    return guard([&] {
-        if (!p) fail(SCANRS_ERR_ARGUMENT, "null argument");
-        *p = special::nb_asymptotic(x_a, x_b, sf_a, sf_b, mu, phi);
-    });
-}
-int scanrs_host_nb_log_prob_all(uint64_t n, double sf_a, double sf_b, double mu, double r, double *out) {
-    return guard([&] {
-        if (!out) fail(SCANRS_ERR_ARGUMENT, "null argument");
-        const double add = special::nb_add_total(n, sf_a, sf_b, mu, r);
-        for (uint64_t k = 0; k <= n; k++) out[k] = special::nb_term(k, n, sf_a * r, sf_b * r, add);
-    });
-}
-int scanrs_host_adjusted_pvalue_bh(const double *p, uint64_t n, double *out) {
-    return guard([&] {
-        if (n && (!p || !out)) fail(SCANRS_ERR_ARGUMENT, "null argument");
-        sseq_host_bh(p, n, out);
-    });
-}
-int scanrs_host_betainc(double a, double b, double x, double *out) {
-    return guard([&] {
-        if (!out) fail(SCANRS_ERR_ARGUMENT, "null argument");
-        *out = special::betainc(a, b, x);
-    });
-}
-int scanrs_host_betaincinv(double a, double b, double p, double *out) {
-    return guard([&] {
-        if (!out) fail(SCANRS_ERR_ARGUMENT, "null argument");
-        *out = special::betaincinv(a, b, p);
-    });
-}
-} // extern "C"
-
-// ---- merge_clusters (cluster_host.cpp / cluster.hip) ------------------------------------------------------------------------------------
-extern "C" {
-int scanrs_host_pdist(const double *x, uint64_t m, uint32_t d, double *out) {
-    return guard([&] {
-        if (m > 1 && (!out || (!x && d))) fail(SCANRS_ERR_ARGUMENT, "null argument");
-        cluster_pdist(x, m, d, out);
-    });
-}
-int scanrs_host_linkage_complete(const double *x, uint64_t m, uint32_t d, double *z) {
-    return guard([&] {
-        if ((!x && d) || (!z && m > 1)) fail(SCANRS_ERR_ARGUMENT, "null argument");
-        cluster_linkage_complete(x, m, d, z);
-    });
-}
-int scanrs_host_relabel_by_size(const int16_t *labels, uint64_t n, int16_t *out) {
-    return guard([&] {
-        if (n && (!labels || !out)) fail(SCANRS_ERR_ARGUMENT, "null argument");
-        cluster_relabel_by_size(labels, n, out);
-    });
-}
-int scanrs_cluster_medoids(const double *pca, uint64_t n, uint32_t ld, uint32_t d, const int16_t *labels, uint32_t k, double *centers) {
-    return guard([&] {
-        if (n && (!pca || !labels || (!centers && d))) fail(SCANRS_ERR_ARGUMENT, "null argument");
-        if (ld < d) fail(SCANRS_ERR_ARGUMENT, "ld must be at least d");
-        need_device();
-        DevBuf<double> d_pca(std::max<uint64_t>(1, n * ld));
-        if (n) SCANRS_HIP(hipMemcpyAsync(d_pca.p, pca, n * ld * 8, hipMemcpyHostToDevice, nullptr));
-        cluster_medoids(nullptr, d_pca.p, n, ld, d, labels, k, centers);
-    });
-}
-int scanrs_cluster_medoids_device(const double *d_pca, uint64_t n, uint32_t ld, uint32_t d, const int16_t *labels, uint32_t k, double *centers) {
-    return guard([&] {
-        if (n && (!d_pca || !labels || (!centers && d))) fail(SCANRS_ERR_ARGUMENT, "null argument");
-        need_device();
-        cluster_medoids(nullptr, d_pca, n, ld, d, labels, k, centers);
-    });
-}
-int scanrs_merge_clusters(scanrs_mat *m, const double *pca, int pca_is_device, uint32_t ld, uint32_t d, const int16_t *labels,
-                          int16_t *labels_out, const scanrs_snoop *snoop, scanrs_merge_trace *trace) {
-    return guard([&] {
-        if (!m) fail(SCANRS_ERR_ARGUMENT, "null handle");
-        const uint64_t cells = m->cols();
-        if (cells && (!pca || !labels || !labels_out)) fail(SCANRS_ERR_ARGUMENT, "null argument");
-        if (trace && trace->capacity && (!trace->leaf0 || !trace->leaf1 || !trace->n_de || !trace->min_p_adj))
-            fail(SCANRS_ERR_ARGUMENT, "trace arrays are null");
-        if (ld < d) fail(SCANRS_ERR_ARGUMENT, "ld must be at least d");
-        CurrentHandle cur(m->st.get());
-        bool gm = false;
-        SparseCopy &cp = sseq_resident_copy(m, &gm);
-        Storage &st = *m->st;
-        DevBuf<double> d_pca;
-        const double *scores = pca;
-        if (!pca_is_device && cells) {
-            d_pca.alloc(cells * ld);
-            SCANRS_HIP(hipMemcpyAsync(d_pca.p, pca, cells * ld * 8, hipMemcpyHostToDevice, st.stream));
-            scores = d_pca.p;
-        }
-        merge_clusters_run(st, cp, gm, m->rows(), cells, scores, ld, d, labels, labels_out, snoop, trace);
-    });
-}
 } // extern "C"
 
 // ---- select_rows / select_cols / partition_on_thresholds / to_csmat (select_host.cpp / select.hip) --------------------------------------

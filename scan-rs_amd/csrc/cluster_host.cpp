@@ -449,3 +449,66 @@ void merge_clusters_run(Storage &st, const SparseCopy &cp, bool gene_major, uint
 }
 
 } // namespace scanrs
+
+// ---- the extern "C" entry points ------------------------------------------------------------------------------------------------------
+using namespace scanrs;
+extern "C" {
+int scanrs_host_pdist(const double *x, uint64_t m, uint32_t d, double *out) {
+    return guard([&] {
+        if (m > 1 && (!out || (!x && d))) fail(SCANRS_ERR_ARGUMENT, "null argument");
+        cluster_pdist(x, m, d, out);
+    });
+}
+int scanrs_host_linkage_complete(const double *x, uint64_t m, uint32_t d, double *z) {
+    return guard([&] {
+        if ((!x && d) || (!z && m > 1)) fail(SCANRS_ERR_ARGUMENT, "null argument");
+        cluster_linkage_complete(x, m, d, z);
+    });
+}
+int scanrs_host_relabel_by_size(const int16_t *labels, uint64_t n, int16_t *out) {
+    return guard([&] {
+        if (n && (!labels || !out)) fail(SCANRS_ERR_ARGUMENT, "null argument");
+        cluster_relabel_by_size(labels, n, out);
+    });
+}
+int scanrs_cluster_medoids(const double *pca, uint64_t n, uint32_t ld, uint32_t d, const int16_t *labels, uint32_t k, double *centers) {
+    return guard([&] {
+        if (n && (!pca || !labels || (!centers && d))) fail(SCANRS_ERR_ARGUMENT, "null argument");
+        if (ld < d) fail(SCANRS_ERR_ARGUMENT, "ld must be at least d");
+        need_device();
+        DevBuf<double> d_pca(std::max<uint64_t>(1, n * ld));
+        if (n) SCANRS_HIP(hipMemcpyAsync(d_pca.p, pca, n * ld * 8, hipMemcpyHostToDevice, nullptr));
+        cluster_medoids(nullptr, d_pca.p, n, ld, d, labels, k, centers);
+    });
+}
+int scanrs_cluster_medoids_device(const double *d_pca, uint64_t n, uint32_t ld, uint32_t d, const int16_t *labels, uint32_t k, double *centers) {
+    return guard([&] {
+        if (n && (!d_pca || !labels || (!centers && d))) fail(SCANRS_ERR_ARGUMENT, "null argument");
+        need_device();
+        cluster_medoids(nullptr, d_pca, n, ld, d, labels, k, centers);
+    });
+}
+int scanrs_merge_clusters(scanrs_mat *m, const double *pca, int pca_is_device, uint32_t ld, uint32_t d, const int16_t *labels,
+                          int16_t *labels_out, const scanrs_snoop *snoop, scanrs_merge_trace *trace) {
+    return guard([&] {
+        if (!m) fail(SCANRS_ERR_ARGUMENT, "null handle");
+        const uint64_t cells = m->cols();
+        if (cells && (!pca || !labels || !labels_out)) fail(SCANRS_ERR_ARGUMENT, "null argument");
+        if (trace && trace->capacity && (!trace->leaf0 || !trace->leaf1 || !trace->n_de || !trace->min_p_adj))
+            fail(SCANRS_ERR_ARGUMENT, "trace arrays are null");
+        if (ld < d) fail(SCANRS_ERR_ARGUMENT, "ld must be at least d");
+        CurrentHandle cur(m->st.get());
+        bool gm = false;
+        SparseCopy &cp = sseq_resident_copy(m, &gm);
+        Storage &st = *m->st;
+        DevBuf<double> d_pca;
+        const double *scores = pca;
+        if (!pca_is_device && cells) {
+            d_pca.alloc(cells * ld);
+            SCANRS_HIP(hipMemcpyAsync(d_pca.p, pca, cells * ld * 8, hipMemcpyHostToDevice, st.stream));
+            scores = d_pca.p;
+        }
+        merge_clusters_run(st, cp, gm, m->rows(), cells, scores, ld, d, labels, labels_out, snoop, trace);
+    });
+}
+} // extern "C"

@@ -2,6 +2,7 @@
 #pragma once
 #include <atomic>
 #include <chrono>
+#include <condition_variable>
 #include <cstring>
 #include <cstdio>
 #include <cstdint>
@@ -10,7 +11,10 @@
 #include <map>
 #include <set>
 #include <memory>
+#include <mutex>
+#include <new>
 #include <string>
+#include <thread>
 #include <utility>
 #include <vector>
 
@@ -59,11 +63,46 @@ struct CurrentHandle {
     explicit CurrentHandle(const Storage *st, bool waits_only = false);
     ~CurrentHandle();
 };
+#define SCANRS_LOCAL __attribute__((visibility("hidden"))) // shared between the library's own files, not an exported symbol
+SCANRS_LOCAL const Storage *current_handle(); // what the innermost CurrentHandle of this thread holds (nullptr: none)
+// scanrs_mat_free: the storage whose members are being destroyed on this thread (its streams are drained by its destructor)
+struct SCANRS_LOCAL DyingHandle {
+    explicit DyingHandle(const Storage *st);
+    ~DyingHandle();
+};
+SCANRS_LOCAL const Storage *dying_handle();
+SCANRS_LOCAL bool device_ok();        // a gfx950 device is usable from this process
+SCANRS_LOCAL bool device_recovered(); // after a timed-out wait: has the whole device been seen idle again? (clears device_lost)
+SCANRS_LOCAL void need_device();      // fails unless device_ok() and device_recovered()
+// The handles of this process (runtime.cpp). A handle leaves FIRST in its destructor; while its RegistryLeave lives the process counts as busy.
+SCANRS_LOCAL void registry_add(const Storage *st);
+struct SCANRS_LOCAL RegistryLeave {
+    explicit RegistryLeave(const Storage *st);
+    ~RegistryLeave();
+};
+SCANRS_LOCAL bool all_library_streams_idle();
+SCANRS_LOCAL bool wait_all_idle_quiet() noexcept; // the null stream and every library stream idle within the deadline (polled, nothing thrown)
+
+template <typename F>
+static int guard(F &&f) {
+    try {
+        f();
+        return SCANRS_OK;
+    } catch (const Failure &e) {
+        return e.code;
+    } catch (const std::bad_alloc &) {
+        set_error("out of host memory");
+        return SCANRS_ERR_DEVICE;
+    } catch (const std::exception &e) {
+        set_error("internal error: %s", e.what());
+        return SCANRS_ERR_DEVICE;
+    }
+}
 #define SCANRS_SYNC(stream) ::scanrs::wait_stream((stream), __PRETTY_FUNCTION__, __FILE__, __LINE__)
 // A few bytes from the device whose landing place outlives a timed-out wait (copies into stack variables of a frame that a
 // timeout unwinds would land in whatever lives there later): the copy goes into a slot of a process-wide pinned ring and is read from
 // there behind the wait; when the wait gives up, the slot is simply not read.
-void *landing_slot(size_t bytes); // capi.cpp: 8-byte aligned, from a pinned ring of 1 MB that is never unmapped
+void *landing_slot(size_t bytes); // runtime.cpp: 8-byte aligned, from a pinned ring of 1 MB that is never unmapped
 // Device -> host for arrays: through a pinned staging area that is never unmapped, in pieces of at most 8 MB, each piece waited for
 // (bounded) before it is copied on into `dst`. If a wait gives up, the copy still in flight lands in the staging area — not in a
 // vector or a caller's array whose frame has unwound meanwhile. `src_pitch` / `row_bytes` / `rows`: a 2-D copy into a
@@ -77,7 +116,6 @@ inline T d2h_value(const T *d, hipStream_t s, const char *func, const char *file
     T *slot = static_cast<T *>(landing_slot(sizeof(T)));
     const hipError_t e = hipMemcpyAsync(slot, d, sizeof(T), hipMemcpyDeviceToHost, s);
     if (e != hipSuccess) ::scanrs::fail(SCANRS_ERR_DEVICE, "hipMemcpyAsync failed: %s (%s:%d)", hipGetErrorString(e), file, line);
-    void wait_stream(hipStream_t s, const char *func, const char *file, int line);
     wait_stream(s, func, file, line);
     return *slot;
 }
@@ -112,6 +150,8 @@ void device_cache_set_fraction(double f);
 size_t device_cache_bytes();
 size_t device_live_bytes();
 size_t device_reserve_unused_bytes();
+SCANRS_LOCAL void device_memory_report(const char *why); // SCANRS_TRACE: what the library holds on the device, block by block, on stderr
+SCANRS_LOCAL void reserve_selftest(uint32_t rounds, uint64_t seed); // scanrs_debug_arena_selftest (device_memory.cpp: the arena's take / give, no device)
 void library_warm_up(); // kernels.hip: loads every code object of the library (one empty launch per translation unit)
 uint64_t device_alloc_us();
 uint64_t device_alloc_calls();
@@ -273,7 +313,7 @@ struct ShardInfo {
 };
 
 // Storage shared by a handle and its views (AdaptiveMat::view / t share `&[AdaptiveVec]`).
-// Pinned host staging buffers, kept across handles (capi.cpp): take the smallest idle one of at least `bytes` or pin a new one.
+// Pinned host staging buffers, kept across handles (device_memory.cpp): take the smallest idle one of at least `bytes` or pin a new one.
 void *pinned_take(size_t bytes, size_t *got);
 void pinned_give(void *p, size_t bytes) noexcept;
 
@@ -315,7 +355,7 @@ struct Storage {
     // grow-only pinned host staging buffer (seeded start panels): no page faults, DMA-speed uploads
     void *host_stage = nullptr;
     size_t host_stage_bytes = 0;
-    // (from / back to a small process-wide pool, capi.cpp: pinning 64 MB takes several ms, and scanrs_init can do it ahead of the first call)
+    // (from / back to a small process-wide pool, device_memory.cpp: pinning 64 MB takes several ms, and scanrs_init can do it ahead of the first call)
     void *pinned(size_t bytes) {
         if (bytes > host_stage_bytes) {
             if (host_stage) pinned_give(host_stage, host_stage_bytes);
@@ -386,12 +426,36 @@ struct Storage {
     // the copy whose outer dimension is the base matrix's rows (true) or cols (false)
     SparseCopy &copy_with_outer_rows(bool outer_rows);
 };
+struct Storage::SideBuild {
+    std::thread th;
+    hipStream_t stream = nullptr;
+    // what the helper makes, in this order: [copy of `first` if it does not exist] -> layout of `first` -> [copy of `second`] -> layout
+    // of `second`; a waiter needs one copy (or its layout) and waits for that stage only
+    const SparseCopy *order[2] = {nullptr, nullptr};
+    bool want_layout[2] = {false, false};
+    std::mutex mu;
+    std::condition_variable cv;
+    bool copy_done[2] = {false, false}, layout_done[2] = {false, false}; // by position in `order`
+    bool finished = false;
+    int code = SCANRS_OK;
+    std::string err;
+    double ms = 0.0;
+};
+SCANRS_LOCAL void registry_set_side(Storage &st, Storage::SideBuild *sb); // st.side = sb under the registry's mutex: all_library_streams_idle sees the helper's stream or nothing, never a destroyed one
+// THE list of the streams a handle queues work on: f(name, stream) for each one that exists, in this order. The deferred frees
+// (one release event per stream), "is the handle idle?" and the destructor's drain all rest on it: a new stream goes here.
+template <class F>
+void for_each_stream(const Storage &st, F &&f) {
+    const std::pair<const char *, hipStream_t> all[] = {{"main", st.stream}, {"aux", st.aux_stream}, {"aux2", st.aux2_stream}, {"overflow", st.ov_stream}, {"helper", st.side ? st.side->stream : nullptr}};
+    for (const auto &x : all)
+        if (x.second) f(x.first, x.second);
+}
 
 // ---- lazy map (sqz::MatrixMap chain) ------------------------------------------------------
 enum { OP_INTO = 0, OP_SCALE_AXIS = 1, OP_LN_1P = 2, OP_LOG2_1P = 3, OP_LOG10_1P = 4, OP_SQUARE = 5, OP_BINOM_DEV = 6, OP_BINOM_PEARSON = 7 };
 constexpr int MAX_OPS = 8; // SparseCopy::fsig_* are sized to this
 
-uint32_t next_map_op_id(); // capi.cpp: never reused (1 ..), identifies a link and the arrays it holds
+uint32_t next_map_op_id(); // runtime.cpp: never reused (1 ..), identifies a link and the arrays it holds
 struct MapOp {
     int kind = OP_INTO;
     int axis = 0;
@@ -598,6 +662,8 @@ void sseq_de_matrix(Storage &st, const SparseCopy &cp, bool gene_major, uint64_t
 void sseq_de_sums(hipStream_t s, uint64_t genes, uint32_t n_tests, const uint64_t *sums_a, const uint64_t *sums_b, const double *sf_a,
                   const double *sf_b, const double *gene_means, const double *gene_phi, const uint8_t *use_genes, uint64_t big_count,
                   const scanrs_snoop *snoop, double *p, double *p_adj, double *log2fc, double *mean_in, double *mean_out);
+// the copy DE walks: the gene-major one when it is resident, else the cell-major one (shared with merge_clusters)
+SCANRS_LOCAL SparseCopy &sseq_resident_copy(scanrs_mat *m, bool *gene_major);
 double sseq_host_exact_test(uint64_t xa, uint64_t xb, double sf_a, double sf_b, double mu, double phi);
 void sseq_host_bh(const double *p, uint64_t n, double *out);
 

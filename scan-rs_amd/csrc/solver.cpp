@@ -984,10 +984,7 @@ static int pca_bk_impl(scanrs_mat *m, uint32_t k, double k_multiplier, uint32_t 
                     st.side_join_if(nullptr, true); // the helper thread that builds the second orientation, if it still runs
                 } catch (const Failure &) {
                 }
-                (void)wait_stream_quiet(st.stream);
-                if (st.aux_stream) (void)wait_stream_quiet(st.aux_stream);
-                if (st.aux2_stream) (void)wait_stream_quiet(st.aux2_stream);
-                if (st.ov_stream) (void)wait_stream_quiet(st.ov_stream);
+                for_each_stream(st, [](const char *, hipStream_t q) { (void)wait_stream_quiet(q); });
             }
         }
     } drain{c.st};

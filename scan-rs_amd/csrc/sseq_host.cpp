@@ -363,4 +363,126 @@ void sseq_de_matrix(Storage &st, const SparseCopy &cp, bool gene_major, uint64_t
                  log2fc, mean_in, mean_out);
 }
 
+// the copy DE walks: the gene-major one when it is resident, else the cell-major one (no transposition is built for DE)
+SparseCopy &sseq_resident_copy(scanrs_mat *m, bool *gene_major) {
+    Storage &st = *m->st;
+    if (st.shard.active()) fail(SCANRS_ERR_ARGUMENT, "differential expression of a sharded handle is not supported");
+    const bool want_base_rows = !m->transposed; // genes = view rows
+    const bool primary_rows = st.storage == SCANRS_CSR;
+    if (primary_rows == want_base_rows) {
+        *gene_major = true;
+        return st.primary;
+    }
+    if (st.other_settled) {
+        *gene_major = true;
+        return st.other;
+    }
+    *gene_major = false;
+    return st.primary;
+}
+
 } // namespace scanrs
+
+// ---- the extern "C" entry points. NOT under this file's contract(off): special.hpp's inline functions are compiled with the default contraction
+// (included above the pragma); a wrapper that feeds them a product (scanrs_host_nb_log_prob_all: sf * r) must contract with them as the device code does
+#pragma clang fp contract(fast)
+using namespace scanrs;
+extern "C" {
+int scanrs_sseq_params(scanrs_mat *m, double zeta_quintile, const uint64_t *cell_indices, uint64_t n_sel, const double *umi_counts,
+                       double *size_factors, double *gene_means, double *gene_variances, uint8_t *use_genes, double *gene_moment_phi,
+                       double *zeta_hat, double *delta, double *gene_phi) {
+    return guard([&] {
+        if (!m || !size_factors || !gene_means || !gene_variances || !use_genes || !gene_moment_phi || !zeta_hat || !delta || !gene_phi)
+            fail(SCANRS_ERR_ARGUMENT, "null argument");
+        if (!(zeta_quintile >= 0.0 && zeta_quintile <= 1.0)) fail(SCANRS_ERR_ARGUMENT, "zeta_quintile must be in [0, 1]");
+        CurrentHandle cur(m->st.get());
+        bool gm = false;
+        SparseCopy &cp = sseq_resident_copy(m, &gm);
+        sseq_params(*m->st, cp, gm, m->rows(), m->cols(), zeta_quintile, cell_indices, n_sel, umi_counts, size_factors, gene_means,
+                    gene_variances, use_genes, gene_moment_phi, zeta_hat, delta, gene_phi);
+    });
+}
+int scanrs_sseq_params_from_moments(const double *mean_g, const double *var_g, uint64_t n, double sum_size_factors, double n_cells,
+                                    double n_genes, double zeta_quintile, uint8_t *use_genes, double *gene_moment_phi, double *zeta_hat,
+                                    double *delta, double *gene_phi) {
+    return guard([&] {
+        if ((n && (!mean_g || !var_g || !use_genes || !gene_moment_phi || !gene_phi)) || !zeta_hat || !delta)
+            fail(SCANRS_ERR_ARGUMENT, "null argument");
+        sseq_params_from_moments(mean_g, var_g, n, sum_size_factors, n_cells, n_genes, zeta_quintile, use_genes, gene_moment_phi, zeta_hat,
+                                 delta, gene_phi);
+    });
+}
+int scanrs_mat_group_sums(scanrs_mat *m, const int16_t *labels, uint32_t n_groups, uint64_t *sums, uint64_t *cells_per_group) {
+    return guard([&] {
+        if (!m || !labels || !sums) fail(SCANRS_ERR_ARGUMENT, "null argument");
+        CurrentHandle cur(m->st.get());
+        bool gm = false;
+        SparseCopy &cp = sseq_resident_copy(m, &gm);
+        sseq_group_sums(*m->st, cp, gm, m->rows(), m->cols(), labels, n_groups, sums, cells_per_group);
+    });
+}
+int scanrs_sseq_de(scanrs_mat *m, const int16_t *labels, uint32_t n_groups, int mode, const double *size_factors, const double *gene_means,
+                   const double *gene_phi, const uint8_t *use_genes, uint64_t big_count, const scanrs_snoop *snoop, uint64_t *sums_in,
+                   uint64_t *sums_out, double *p, double *p_adj, double *log2fc, double *mean_in, double *mean_out) {
+    return guard([&] {
+        if (!m || !labels || !size_factors || !gene_means || !gene_phi || !use_genes || !sums_in || !sums_out || !p || !p_adj || !log2fc ||
+            !mean_in || !mean_out)
+            fail(SCANRS_ERR_ARGUMENT, "null argument");
+        CurrentHandle cur(m->st.get());
+        bool gm = false;
+        SparseCopy &cp = sseq_resident_copy(m, &gm);
+        sseq_de_matrix(*m->st, cp, gm, m->rows(), m->cols(), labels, n_groups, mode, size_factors, gene_means, gene_phi, use_genes, big_count,
+                       snoop, sums_in, sums_out, p, p_adj, log2fc, mean_in, mean_out);
+    });
+}
+int scanrs_sseq_de_from_sums(uint64_t n_genes, uint32_t n_tests, const uint64_t *sums_a, const uint64_t *sums_b, const double *sf_a,
+                             const double *sf_b, const double *gene_means, const double *gene_phi, const uint8_t *use_genes,
+                             uint64_t big_count, const scanrs_snoop *snoop, double *p, double *p_adj, double *log2fc, double *mean_in,
+                             double *mean_out) {
+    return guard([&] {
+        if (n_genes && n_tests &&
+            (!sums_a || !sums_b || !sf_a || !sf_b || !gene_means || !gene_phi || !use_genes || !p || !p_adj || !log2fc || !mean_in || !mean_out))
+            fail(SCANRS_ERR_ARGUMENT, "null argument");
+        need_device();
+        sseq_de_sums(nullptr, n_genes, n_tests, sums_a, sums_b, sf_a, sf_b, gene_means, gene_phi, use_genes, big_count, snoop, p, p_adj, log2fc,
+                     mean_in, mean_out);
+    });
+}
+int scanrs_host_nb_exact_test(uint64_t x_a, uint64_t x_b, double sf_a, double sf_b, double mu, double phi, double *p) {
+    return guard([&] {
+        if (!p) fail(SCANRS_ERR_ARGUMENT, "null argument");
+        *p = sseq_host_exact_test(x_a, x_b, sf_a, sf_b, mu, phi);
+    });
+}
+int scanrs_host_nb_asymptotic_test(uint64_t x_a, uint64_t x_b, double sf_a, double sf_b, double mu, double phi, double *p) {
+    return guard([&] {
+        if (!p) fail(SCANRS_ERR_ARGUMENT, "null argument");
+        *p = special::nb_asymptotic(x_a, x_b, sf_a, sf_b, mu, phi);
+    });
+}
+int scanrs_host_nb_log_prob_all(uint64_t n, double sf_a, double sf_b, double mu, double r, double *out) {
+    return guard([&] {
+        if (!out) fail(SCANRS_ERR_ARGUMENT, "null argument");
+        const double add = special::nb_add_total(n, sf_a, sf_b, mu, r);
+        for (uint64_t k = 0; k <= n; k++) out[k] = special::nb_term(k, n, sf_a * r, sf_b * r, add);
+    });
+}
+int scanrs_host_adjusted_pvalue_bh(const double *p, uint64_t n, double *out) {
+    return guard([&] {
+        if (n && (!p || !out)) fail(SCANRS_ERR_ARGUMENT, "null argument");
+        sseq_host_bh(p, n, out);
+    });
+}
+int scanrs_host_betainc(double a, double b, double x, double *out) {
+    return guard([&] {
+        if (!out) fail(SCANRS_ERR_ARGUMENT, "null argument");
+        *out = special::betainc(a, b, x);
+    });
+}
+int scanrs_host_betaincinv(double a, double b, double p, double *out) {
+    return guard([&] {
+        if (!out) fail(SCANRS_ERR_ARGUMENT, "null argument");
+        *out = special::betaincinv(a, b, p);
+    });
+}
+} // extern "C"
