@@ -194,6 +194,35 @@ int scanrs_mat_partition_on_thresholds(scanrs_mat *m, const double *row_threshol
  * map is not applied. */
 int scanrs_mat_to_csmat(scanrs_mat *m, uint64_t *indptr, uint32_t *indices, uint32_t *values);
 
+/* ---- to_adaptive: the stored counts as sqz::AdaptiveVec encodings (sqz/src/mat.rs:92-124, sqz/src/vec.rs:1086-1160) -----------------
+ * The way back into the caller's own type: what scanrs_mat_create_adaptive takes, made on the device from the handle's own
+ * storage (about half the bytes of the triplet of scanrs_mat_to_csmat for single-cell counts, and no AdaptiveVec::new per vector on
+ * the caller's side). Bit for bit what the reference's constructors build: `choose_storage` (vec.rs:1086-1131, including the S8
+ * branch that does not lower min_size), Dense3 / Dense4 / DenseW / SimpleSparse / CompressedIndexSparse::construct. Integer work
+ * without atomics: two calls return the same bytes.
+ *
+ * Like scanrs_mat_to_csmat it reads the stored counts: a composed map or an offset is ignored, a transposed view exports the same
+ * vectors under the other storage flag (scanrs_mat_storage), a sharded handle exports its own shard. The export owns two host
+ * arenas (one device-to-host copy each; pinned memory from the library's pool from 1 MB on, plain heap memory below that) and the table of scanrs_adaptive_vec whose pointers lead into them, each aligned for
+ * its element type; the device arenas are released before the call returns. */
+typedef struct scanrs_adaptive_export scanrs_adaptive_export;
+/* AdaptiveMat::from_csmat / AdaptiveVec::new per outer vector (mat.rs:92-124, vec.rs:1086-1160), run on the device.
+ * force_kind: -1 = choose_storage, 0..7 = that encoding for every vector (the `kind` codes of scanrs_adaptive_vec); anything else is
+ * SCANRS_ERR_ARGUMENT. A matrix without outer vectors and empty vectors are valid. Free the result with
+ * scanrs_adaptive_export_free. */
+int scanrs_mat_to_adaptive(scanrs_mat *m, int force_kind, scanrs_adaptive_export **out);
+/* n_vecs: the outer dimension. total_bytes: the sum of the reference's mem_size() — data + 8 per fallback entry (+ index bytes + 4
+ * per block start for S*; 8 per entry for V). kind_counts[k]: vectors of encoding k. Each output pointer may be NULL. */
+int scanrs_adaptive_export_info(const scanrs_adaptive_export *e, uint64_t *n_vecs, uint64_t *total_bytes, uint64_t kind_counts[8]);
+/* The table (n_vecs entries), borrowed until scanrs_adaptive_export_free; it can be passed straight to
+ * scanrs_mat_create_adaptive(rows, cols, storage, vecs, n_vecs, ...). */
+int scanrs_adaptive_export_vecs(const scanrs_adaptive_export *e, const scanrs_adaptive_vec **vecs);
+void scanrs_adaptive_export_free(scanrs_adaptive_export *e); /* NULL is a no-op */
+/* Host side of the header both compile: the kind AdaptiveVec::new would pick for a vector of length `len` with these n stored
+ * values, and the reference's second result, the smallest size estimate seen before the S8 and V branches (min_size may be NULL).
+ * Needs no device. */
+int scanrs_host_choose_storage(uint64_t len, const uint32_t *values, uint64_t n, int *kind, uint64_t *min_size);
+
 /* ---- products: `Dot` impls (mat.rs:1074-1170, low_rank_offset.rs:68-96, prod.rs) -- */
 
 /* self.dot(rhs): rhs is cols x l, out is rows x l (includes the offset u*(v*rhs) when set). */

@@ -6,6 +6,7 @@
 //   snoop::CancelProgress                  -> scanrs::Snoop         (snoop/src/lib.rs:20-58)
 // `anyhow::Error` becomes scanrs::Error (code + the reference's message), `CancellationError` its subclass.
 #pragma once
+#include <array>
 #include <atomic>
 #include <cstdint>
 #include <functional>
@@ -69,6 +70,56 @@ struct PcaResult { // (u, d, v): dim_red/mod.rs:47
     std::vector<double> s;
     Array2 v;
 };
+
+// The stored counts as AdaptiveVec encodings (scanrs_mat_to_adaptive): owns the host arenas and the table pointing into them
+class AdaptiveExport {
+    scanrs_adaptive_export *e_ = nullptr;
+
+  public:
+    AdaptiveExport() = default;
+    explicit AdaptiveExport(scanrs_adaptive_export *e) : e_(e) {}
+    AdaptiveExport(const AdaptiveExport &) = delete;
+    AdaptiveExport &operator=(const AdaptiveExport &) = delete;
+    AdaptiveExport(AdaptiveExport &&o) noexcept : e_(o.e_) { o.e_ = nullptr; }
+    AdaptiveExport &operator=(AdaptiveExport &&o) noexcept {
+        if (this != &o) {
+            scanrs_adaptive_export_free(e_);
+            e_ = o.e_;
+            o.e_ = nullptr;
+        }
+        return *this;
+    }
+    ~AdaptiveExport() { scanrs_adaptive_export_free(e_); }
+    uint64_t n_vecs() const {
+        uint64_t n = 0;
+        check(scanrs_adaptive_export_info(e_, &n, nullptr, nullptr));
+        return n;
+    }
+    uint64_t total_bytes() const { // sum of AdaptiveVec::mem_size
+        uint64_t b = 0;
+        check(scanrs_adaptive_export_info(e_, nullptr, &b, nullptr));
+        return b;
+    }
+    std::array<uint64_t, 8> kind_counts() const { // D3, D4, D8, D16, V, S3, S4, S8
+        std::array<uint64_t, 8> k{};
+        check(scanrs_adaptive_export_info(e_, nullptr, nullptr, k.data()));
+        return k;
+    }
+    // n_vecs() entries, valid while this object lives; what AdaptiveMat::from_adaptive_vecs / scanrs_mat_create_adaptive take
+    const scanrs_adaptive_vec *vecs() const {
+        const scanrs_adaptive_vec *v = nullptr;
+        check(scanrs_adaptive_export_vecs(e_, &v));
+        return v;
+    }
+};
+
+// AdaptiveVec::choose_storage (vec.rs:1086-1131) on the host: (kind code, min_size)
+inline std::pair<int, uint64_t> choose_storage(uint64_t len, const std::vector<uint32_t> &values) {
+    int kind = 0;
+    uint64_t min_size = 0;
+    check(scanrs_host_choose_storage(len, values.data(), values.size(), &kind, &min_size));
+    return {kind, min_size};
+}
 
 // Device-resident AdaptiveMat; plays LowRankOffset once an offset is installed.
 class AdaptiveMat {
@@ -204,6 +255,13 @@ class AdaptiveMat {
         c.data.resize(nnz());
         check(scanrs_mat_to_csmat(h_, c.indptr.data(), c.indices.data(), c.data.data()));
         return c;
+    }
+    // AdaptiveMat::from_csmat backwards (mat.rs:92-124, vec.rs:1086-1160): one encoded AdaptiveVec per outer vector of the stored
+    // counts, made on the device. force_kind -1: choose_storage; 0..7: that encoding for every vector
+    AdaptiveExport to_adaptive(int force_kind = -1) const {
+        scanrs_adaptive_export *e = nullptr;
+        check(scanrs_mat_to_adaptive(h_, force_kind, &e));
+        return AdaptiveExport(e);
     }
     Array2 to_dense() const {
         Array2 out(rows(), cols());

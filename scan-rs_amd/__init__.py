@@ -174,6 +174,18 @@ def find_nn(v, k: int, tree_points, include_self: bool):
     return out
 
 
+ADAPTIVE_KINDS = ("D3", "D4", "D8", "D16", "V", "S3", "S4", "S8")  # `enum AdaptiveVec` (vec.rs:1029-1053): the `kind` codes
+
+
+def choose_storage(length: int, values):
+    """`AdaptiveVec::choose_storage(len, values)` (vec.rs:1086-1131) on the host: (kind code, min_size)."""
+    v = np.ascontiguousarray(values, dtype=np.uint32)
+    kind, min_size = ctypes.c_int(), ctypes.c_uint64()
+    _check(_lib.scanrs_host_choose_storage(ctypes.c_uint64(int(length)), _p(v), ctypes.c_uint64(v.shape[0]), ctypes.byref(kind),
+                                           ctypes.byref(min_size)))
+    return int(kind.value), int(min_size.value)
+
+
 class AdaptiveVecDesc(ctypes.Structure):
     """`scanrs_adaptive_vec` (include/scanrs_amd.h): one sqz::AdaptiveVec by its encoded buffers."""
     _fields_ = [("kind", ctypes.c_uint32), ("len", ctypes.c_uint64), ("n_units", ctypes.c_uint64), ("data", ctypes.c_void_p),
@@ -449,6 +461,62 @@ class AdaptiveMat:
         cls = sp.csr_matrix if self.storage() == CSR else sp.csc_matrix
         return cls((data, indices.astype(np.int64), indptr.astype(np.int64)), shape=tuple(self.shape()))
 
+    # -- back into sqz's own type: the AdaptiveVec encodings (mat.rs:92-124, vec.rs:1086-1160) ----
+    def _export(self, kind):
+        if isinstance(kind, str):
+            if kind not in ADAPTIVE_KINDS:
+                raise ScanrsError(6, f"unknown AdaptiveVec encoding {kind!r}")
+            kind = ADAPTIVE_KINDS.index(kind)
+        e = ctypes.c_void_p()
+        _check(_lib.scanrs_mat_to_adaptive(self._h, ctypes.c_int(-1 if kind is None else int(kind)), ctypes.byref(e)))
+        return e
+
+    def adaptive_info(self, kind=None):
+        """(total_bytes, kind_counts) of `to_adaptive_vecs(kind)`: the sum of `AdaptiveVec::mem_size` and how many outer vectors
+        took each of the eight encodings (order of ADAPTIVE_KINDS)."""
+        e = self._export(kind)
+        try:
+            total, counts = ctypes.c_uint64(), (ctypes.c_uint64 * 8)()
+            _check(_lib.scanrs_adaptive_export_info(e, None, ctypes.byref(total), counts))
+            return int(total.value), [int(c) for c in counts]
+        finally:
+            _lib.scanrs_adaptive_export_free(e)
+
+    def to_adaptive_vecs(self, kind=None):
+        """`AdaptiveMat::from_csmat` backwards (mat.rs:92-124): the stored counts as one encoded `AdaptiveVec` per outer vector
+        (`AdaptiveVec::new`, vec.rs:1086-1160), encoded on the device. kind=None: `choose_storage`; a code 0..7 or a name of
+        ADAPTIVE_KINDS: that encoding for every vector. Returns the mappings `from_adaptive_vecs` takes (kind, len, n_units, data,
+        fallback_indexes, fallback_values, index_bytes, block_starts), numpy copies in the reference's in-memory layout; pieces an
+        encoding does not have are None."""
+        e = self._export(kind)
+        try:
+            n, table = ctypes.c_uint64(), ctypes.POINTER(AdaptiveVecDesc)()
+            _check(_lib.scanrs_adaptive_export_info(e, ctypes.byref(n), None, None))
+            _check(_lib.scanrs_adaptive_export_vecs(e, ctypes.byref(table)))
+
+            def arr(ptr, count, dt):
+                if not count:
+                    return np.zeros(0, dtype=dt)
+                return np.ctypeslib.as_array(ctypes.cast(ptr, ctypes.POINTER(np.ctypeslib.as_ctypes_type(dt))), shape=(count,)).copy()
+
+            out = []
+            for i in range(int(n.value)):
+                d = table[i]
+                k = int(d.kind)
+                v = dict(kind=k, len=int(d.len), n_units=int(d.n_units), data=None, index_bytes=None, block_starts=None)
+                v["fallback_indexes"] = arr(d.fallback_indexes, d.n_fallback, np.uint32)
+                v["fallback_values"] = arr(d.fallback_values, d.n_fallback, np.uint32)
+                if k != 4:
+                    dt = np.uint64 if k in (0, 5) else np.uint16 if k == 3 else np.uint8
+                    v["data"] = arr(d.data, d.data_bytes // np.dtype(dt).itemsize, dt)
+                if k >= 5:
+                    v["index_bytes"] = arr(d.index_bytes, d.n_units, np.uint8)
+                    v["block_starts"] = arr(d.block_starts, d.n_block_starts, np.uint32)
+                out.append(v)
+            return out
+        finally:
+            _lib.scanrs_adaptive_export_free(e)
+
     # -- products ----------------------------------------------------------------------------------
     def dot(self, rhs):
         """`self.dot(&rhs)` (mat.rs:1074-1112, low_rank_offset.rs:68-81)."""
@@ -597,6 +665,8 @@ _lib.scanrs_debug_wait_never.argtypes = [ctypes.c_double]
 _lib.scanrs_debug_wait_never.restype = ctypes.c_int
 _lib.scanrs_reserve_device_memory.argtypes = [ctypes.c_uint64]
 _lib.scanrs_reserve_device_memory.restype = ctypes.c_int
+_lib.scanrs_adaptive_export_free.argtypes = [ctypes.c_void_p]
+_lib.scanrs_adaptive_export_free.restype = None
 
 
 def set_global_option(key: str, value: float):
@@ -986,6 +1056,8 @@ EXPORTED_SYMBOLS = [
     "scanrs_host_pdist", "scanrs_host_linkage_complete", "scanrs_host_relabel_by_size", "scanrs_cluster_medoids", "scanrs_cluster_medoids_device",
     "scanrs_merge_clusters",
     "scanrs_mat_select_rows", "scanrs_mat_select_cols", "scanrs_mat_partition_on_thresholds", "scanrs_mat_to_csmat",
+    "scanrs_mat_to_adaptive", "scanrs_adaptive_export_info", "scanrs_adaptive_export_vecs", "scanrs_adaptive_export_free",
+    "scanrs_host_choose_storage",
 ]
 
 # sSeq differential expression (sseq.py)

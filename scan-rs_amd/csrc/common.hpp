@@ -272,7 +272,10 @@ void tile_layout_free(TileLayout *t);
 void tile_layout_forget_weights(TileLayout *t);
 void tile_layout_stats(const TileLayout *t, uint64_t out[3]); // positions per pass, served nonzeros, overflow nonzeros
 
-// A compressed orientation: n_outer vectors over n_inner positions.
+// A compressed orientation: n_outer vectors over n_inner positions. The three arrays are DevBuf allocations of their own: each starts
+// on (at least) a 16-byte boundary and has DevBuf::SLACK readable bytes behind its last entry. select.hip and encode.hip rely on both
+// (16-byte loads that begin at a multiple of 4 / 8 entries and may run past nnz); a copy around borrowed or offset pointers would
+// have to keep them.
 struct SparseCopy {
     uint64_t n_outer = 0, n_inner = 0, nnz = 0;
     DevBuf<uint64_t> indptr;
@@ -610,6 +613,16 @@ void knn_device(const double *d_queries, uint32_t ld_q, uint64_t n_q, const doub
 // decode.hip
 uint64_t decode_adaptive_vectors(const scanrs_adaptive_vec *vecs, uint64_t n_vecs, uint64_t vec_len, DevBuf<uint64_t> &indptr,
                                  DevBuf<uint32_t> &indices, DevBuf<uint32_t> &values);
+// encode.hip: the encoders (the inverse direction). One entry per outer vector: its encoding, stored entries and fallback entries;
+// byte_off / word_off (n_outer + 1 entries) place its pieces in the two device arenas: `data` (padded to 8 bytes), then index_bytes
+// (S*) in d_bytes; fallback indexes, fallback values, then block_starts (S*) in d_words.
+struct EncodedVec {      // written by the plan kernel, read by the emit kernels and, as it is, by the host
+    uint32_t kind, n;    // encoding, stored entries
+    uint32_t n_fb, _pad; // fallback entries
+    uint64_t fb_base;    // the plan's own bookkeeping: entries before the vector's first that reach its marker
+};
+void encode_adaptive_vectors(Storage &st, const SparseCopy &cp, int force_kind, std::vector<EncodedVec> &vecs, std::vector<uint64_t> &byte_off,
+                             std::vector<uint64_t> &word_off, DevBuf<uint64_t> &d_bytes, DevBuf<uint32_t> &d_words);
 // comm.cpp
 struct LocalGroup;
 void comm_allreduce(Storage &st, scanrs_comm *c, void *d, uint64_t count, int dtype); // dtype 0 = f64, 1 = u64; on st.stream
