@@ -537,6 +537,42 @@ int scanrs_mat_sync(scanrs_mat *m);
 int scanrs_mat_chol_rinv(scanrs_mat *m, const double *g, uint32_t n, uint64_t rows, int pass, double *rinv, int *done, int *status,
                          double *err, double *shift);
 
+/* ---- the dense f64-MFMA products, one kernel at a time. For tests. ------------------------------------------------------------
+ * The solvers reach the Gram kernels (C = X^T Y) and the GEMM kernels (Out = beta Cin + alpha X W) through two dispatchers that
+ * pick a kernel from the shape; these entry points run one product on host arrays and can force the kernel. Routes: */
+#define SCANRS_DENSE_GRAM_WAVE 1       /* one wave per 32 x 32 tile of C */
+#define SCANRS_DENSE_GRAM_VEC 2        /* one vector (m = 1) against at most 128 columns, streaming */
+#define SCANRS_DENSE_GRAM_TILED 3      /* 128 x 128 LDS tiles; symmetric form when Y is X */
+#define SCANRS_DENSE_GEMM_WAVE 1       /* one wave per 16 rows x 16 / 32 / 64 columns */
+#define SCANRS_DENSE_GEMM_TILED 2      /* 128 x 128 LDS tiles */
+#define SCANRS_DENSE_GEMM_SKINNY_LDS 3 /* 256 x 64 LDS tiles */
+#define SCANRS_DENSE_GEMM_DIRECT 4     /* operands straight from memory, W transposed and zero-padded first */
+/* What the dispatcher would choose (host only, no device needed). kind 0: Gram of X (rows x n, ld ldx) and Y (rows x m, ld ldy),
+ * flag = a skip flag is set (a queued orthonormalisation). kind 1: GEMM X (rows x n, ld ldx) times W (n x m), ldy ignored,
+ * x_aligned16 = X starts on a 16-byte boundary, flag = the handle's "gemm_direct" option; odd ldx answers SCANRS_ERR_ARGUMENT as
+ * the dispatcher does. side != 0: queued on a side stream under "dense_side_no_lds". *nt: 16-column MFMA tiles per wave (GEMM_WAVE:
+ * 1, 2 or 4; GEMM_DIRECT: 1..7; else 0); *groups: column groups of the GEMM launch (Gram: 0). */
+int scanrs_debug_dense_route(int kind, uint32_t n, uint32_t m, uint64_t rows, uint32_t ldx, uint32_t ldy, int x_aligned16, int side,
+                             int flag, int *route, uint32_t *nt, uint32_t *groups);
+/* C (n x mcols, ld = mcols; read first, so that what the kernels leave untouched keeps the caller's values) = X^T Y over `rows` rows.
+ * x: rows_alloc x ldx, y: rows_alloc x ldy host arrays, uploaded whole (rows_alloc >= rows: the surplus rows are there for the kernels
+ * not to read). y == NULL: Y is X itself, the same device pointer (needs mcols == n, ldy == ldx). route 0: the dispatcher's choice;
+ * else that kernel, or SCANRS_ERR_ARGUMENT when its own preconditions fail (GRAM_VEC: mcols == 1, n <= 128, no skip; GRAM_TILED: even
+ * ldx, ldy). skip != 0: the call runs with the handle's skip flag pointing at a device int that holds 1. */
+int scanrs_debug_dense_gram(scanrs_mat *m, int route, const double *x, uint32_t ldx, uint32_t n, const double *y, uint32_t ldy,
+                            uint32_t mcols, uint64_t rows, uint64_t rows_alloc, int skip, double *c);
+/* out (rows_alloc x ldo; read first, written back whole) = beta cin + alpha X W. x: rows_alloc x ldx (even), w: n x ldw,
+ * cin: rows_alloc x ldc or NULL (then beta must be 0). x_skew 0 / 1: X's device base is moved by that many doubles inside its
+ * allocation (1: not 16-byte aligned). in_place: Cin is the device buffer of Out (ldc == ldo; cin ignored). route as above
+ * (GEMM_DIRECT: X aligned, n >= 16, rows >= 64, mcols <= 4096). The host arrays x and out must not overlap. */
+int scanrs_debug_dense_gemm(scanrs_mat *m, int route, const double *x, int x_skew, uint32_t ldx, uint32_t n, const double *w, uint32_t ldw,
+                            uint32_t mcols, uint64_t rows, uint64_t rows_alloc, double alpha, double beta, const double *cin, uint32_t ldc,
+                            double *out, uint32_t ldo, int in_place, int skip);
+/* w (rank x ldw; read first, written back whole) = B^T X with b: n x rank, x: n x ldx (ldx even, >= l rounded up to even). xc (n x ldc,
+ * or NULL; needs l and ldc even): the compact copy of X's first l columns the same kernel writes; read first, written back whole. */
+int scanrs_debug_weighted_colsum(scanrs_mat *m, const double *b, uint32_t rank, const double *x, uint32_t ldx, uint64_t n, uint32_t l,
+                                 double *w, uint32_t ldw, double *xc, uint32_t ldc);
+
 /* Diagnostics of the bounded waits (no device needed): runs the library's wait loop on an event that is never signalled and
  * returns SCANRS_ERR_DEVICE once `timeout_s` seconds have passed, with the report a real stuck wait leaves behind. */
 int scanrs_debug_wait_never(double timeout_s);

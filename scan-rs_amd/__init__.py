@@ -648,6 +648,50 @@ class AdaptiveMat:
                                          ctypes.byref(done), ctypes.byref(status), ctypes.byref(err), ctypes.byref(shift)))
         return rinv, int(done.value), int(status.value), float(err.value), float(shift.value)
 
+    def debug_dense_gram(self, x, n: int, y, mcols: int, rows: int, c, route: int = 0, skip: bool = False):
+        """C = X^T Y through one Gram kernel (scanrs_debug_dense_gram). x, y: (rows_alloc, ld) arrays whose first `rows` rows and
+        n / mcols columns are the operands (y None: Y is X itself); c: the (n, mcols) buffer the kernels write into. Returns the
+        buffer as it comes back."""
+        x = _f64(x)
+        y = None if y is None else _f64(y)
+        c = np.array(c, dtype=np.float64, order="C")
+        if c.shape != (n, mcols) or (y is not None and y.shape[0] != x.shape[0]):
+            raise ValueError("c must be n x mcols, x and y must hold the same number of rows")
+        _check(_lib.scanrs_debug_dense_gram(self._h, ctypes.c_int(route), _p(x), ctypes.c_uint32(x.shape[1]), ctypes.c_uint32(n), _p(y),
+                                            ctypes.c_uint32(x.shape[1] if y is None else y.shape[1]), ctypes.c_uint32(mcols),
+                                            ctypes.c_uint64(rows), ctypes.c_uint64(x.shape[0]), ctypes.c_int(int(skip)), _p(c)))
+        return c
+
+    def debug_dense_gemm(self, x, n: int, w, mcols: int, rows: int, out, alpha: float = 1.0, beta: float = 0.0, cin=None,
+                         in_place: bool = False, route: int = 0, x_skew: int = 0, skip: bool = False):
+        """Out = beta Cin + alpha X W through one GEMM kernel (scanrs_debug_dense_gemm). x: (rows_alloc, ldx), w: (n, ldw),
+        out: (rows_alloc, ldo), cin: (rows_alloc, ldc) or None; in_place: Cin is Out's device buffer. Returns the whole out buffer."""
+        x, w = _f64(x), _f64(w)
+        cin = None if cin is None else _f64(cin)
+        out = np.array(out, dtype=np.float64, order="C")
+        if out.shape[0] != x.shape[0] or w.shape[0] != n or (cin is not None and cin.shape[0] != x.shape[0]):
+            raise ValueError("x, out and cin must hold the same number of rows, w must hold n")
+        ldc = out.shape[1] if in_place else (cin.shape[1] if cin is not None else 0)
+        _check(_lib.scanrs_debug_dense_gemm(self._h, ctypes.c_int(route), _p(x), ctypes.c_int(x_skew), ctypes.c_uint32(x.shape[1]),
+                                            ctypes.c_uint32(n), _p(w), ctypes.c_uint32(w.shape[1]), ctypes.c_uint32(mcols), ctypes.c_uint64(rows),
+                                            ctypes.c_uint64(x.shape[0]), ctypes.c_double(alpha), ctypes.c_double(beta), _p(cin),
+                                            ctypes.c_uint32(ldc), _p(out), ctypes.c_uint32(out.shape[1]), ctypes.c_int(int(in_place)),
+                                            ctypes.c_int(int(skip))))
+        return out
+
+    def debug_weighted_colsum(self, b, x, l: int, w, xc=None):
+        """w = B^T X[:, :l] (scanrs_debug_weighted_colsum). b: (n, rank), x: (n, ldx), w: (rank, ldw), xc: (n, ldc) or None.
+        Returns (w, xc) as the buffers come back."""
+        b, x = _f64(b), _f64(x)
+        w = np.array(w, dtype=np.float64, order="C")
+        xc = None if xc is None else np.array(xc, dtype=np.float64, order="C")
+        if b.shape[0] != x.shape[0] or w.shape[0] != b.shape[1] or (xc is not None and xc.shape[0] != x.shape[0]):
+            raise ValueError("b, x and xc must hold the same number of rows, w one row per column of b")
+        _check(_lib.scanrs_debug_weighted_colsum(self._h, _p(b), ctypes.c_uint32(b.shape[1]), _p(x), ctypes.c_uint32(x.shape[1]),
+                                                 ctypes.c_uint64(x.shape[0]), ctypes.c_uint32(l), _p(w), ctypes.c_uint32(w.shape[1]), _p(xc),
+                                                 ctypes.c_uint32(0 if xc is None else xc.shape[1])))
+        return w, xc
+
     def target_umi(self) -> float:
         t = ctypes.c_double()
         _check(_lib.scanrs_mat_target_umi(self._h, ctypes.byref(t)))
@@ -667,6 +711,21 @@ _lib.scanrs_reserve_device_memory.argtypes = [ctypes.c_uint64]
 _lib.scanrs_reserve_device_memory.restype = ctypes.c_int
 _lib.scanrs_adaptive_export_free.argtypes = [ctypes.c_void_p]
 _lib.scanrs_adaptive_export_free.restype = None
+
+
+GRAM_WAVE, GRAM_VEC, GRAM_TILED = 1, 2, 3  # SCANRS_DENSE_GRAM_*
+GEMM_WAVE, GEMM_TILED, GEMM_SKINNY_LDS, GEMM_DIRECT = 1, 2, 3, 4  # SCANRS_DENSE_GEMM_*
+
+
+def debug_dense_route(kind: str, n: int, m: int, rows: int, ldx: int, ldy: int = 0, x_aligned16: bool = True, side: bool = False,
+                      flag: bool = False):
+    """What the dense dispatcher would choose (scanrs_debug_dense_route, host only): (route, nt, groups). kind "gram": flag = a skip
+    flag is set; kind "gemm": flag = the "gemm_direct" option."""
+    route, nt, groups = ctypes.c_int(), ctypes.c_uint32(), ctypes.c_uint32()
+    _check(_lib.scanrs_debug_dense_route(ctypes.c_int({"gram": 0, "gemm": 1}[kind]), ctypes.c_uint32(n), ctypes.c_uint32(m), ctypes.c_uint64(rows),
+                                         ctypes.c_uint32(ldx), ctypes.c_uint32(ldy), ctypes.c_int(int(x_aligned16)), ctypes.c_int(int(side)),
+                                         ctypes.c_int(int(flag)), ctypes.byref(route), ctypes.byref(nt), ctypes.byref(groups)))
+    return int(route.value), int(nt.value), int(groups.value)
 
 
 def set_global_option(key: str, value: float):
@@ -1045,7 +1104,7 @@ EXPORTED_SYMBOLS = [
     "scanrs_pca_bk", "scanrs_pca_rand", "scanrs_pca_irlba", "scanrs_pca_result_device", "scanrs_knn_device", "scanrs_omega_fill", "scanrs_mat_set_shard", "scanrs_mat_set_shard_comm", "scanrs_comm_get_unique_id", "scanrs_comm_create", "scanrs_comm_free",
     "scanrs_multi_create", "scanrs_multi_free", "scanrs_multi_n_shards", "scanrs_multi_shard", "scanrs_multi_normalize", "scanrs_multi_pca_bk", "scanrs_multi_pca_rand", "scanrs_multi_pca_irlba", "scanrs_multi_log_normalize",
     "scanrs_plan_shards", "scanrs_profile_enable", "scanrs_profile_reset", "scanrs_profile_get", "scanrs_mat_sync", "scanrs_mat_set_spmm_path", "scanrs_mat_set_option", "scanrs_set_global_option", "scanrs_mat_set_panel_precision",
-    "scanrs_mat_chol_rinv", "scanrs_mat_get_counter", "scanrs_host_chol_upper", "scanrs_host_inv_upper", "scanrs_host_sym_eig", "scanrs_host_sym_eig_topk", "scanrs_debug_wait_never", "scanrs_debug_barrier_alone", "scanrs_debug_arena_selftest", "scanrs_init", "scanrs_release_cached_memory", "scanrs_cached_memory_bytes", "scanrs_reserve_device_memory", "scanrs_device_memory_in_use",
+    "scanrs_mat_chol_rinv", "scanrs_mat_get_counter", "scanrs_host_chol_upper", "scanrs_host_inv_upper", "scanrs_host_sym_eig", "scanrs_host_sym_eig_topk", "scanrs_debug_wait_never", "scanrs_debug_barrier_alone", "scanrs_debug_arena_selftest", "scanrs_debug_dense_route", "scanrs_debug_dense_gram", "scanrs_debug_dense_gemm", "scanrs_debug_weighted_colsum", "scanrs_init", "scanrs_release_cached_memory", "scanrs_cached_memory_bytes", "scanrs_reserve_device_memory", "scanrs_device_memory_in_use",
     "scanrs_h5_read_csc_matrix", "scanrs_h5_read_adaptive_csr_matrix", "scanrs_h5_read_matrix_metadata", "scanrs_h5_matrix_free",
     "scanrs_h5_matrix_shape", "scanrs_h5_matrix_arrays", "scanrs_h5_matrix_n_strings", "scanrs_h5_matrix_string", "scanrs_h5_matrix_removed",
     "scanrs_h5_read_umi_counts", "scanrs_h5_get_clustering_keys", "scanrs_h5_get_clustering", "scanrs_h5_get_differential_expression",

@@ -1418,6 +1418,117 @@ int scanrs_mat_chol_rinv(scanrs_mat *m, const double *g, uint32_t n, uint64_t ro
     });
 }
 
+// ---- the dense products one kernel at a time (tests): host arrays in, the WHOLE output buffer back, padding included -----------
+} // extern "C"
+namespace {
+constexpr uint64_t DBG_MAX_ELEMS = 1ull << 26; // doubles per uploaded array (512 MB)
+uint64_t dbg_count(uint64_t rows, uint32_t ld) {
+    if (rows == 0 || ld == 0 || rows > DBG_MAX_ELEMS / ld) fail(SCANRS_ERR_ARGUMENT, "array of %llu x %u doubles: empty or too large", (unsigned long long)rows, ld);
+    return rows * ld;
+}
+double *dbg_upload(Storage &st, const char *key, const double *h, uint64_t count, uint64_t skew = 0) {
+    double *d = st.scratch.get<double>(key, count + 2) + skew;
+    SCANRS_HIP(hipMemcpyAsync(d, h, count * 8, hipMemcpyHostToDevice, st.stream));
+    return d;
+}
+// Storage::skip_flag pointing at a device int that holds 1 for the lifetime of the object; restored also when an error unwinds
+struct DbgSkip {
+    Storage &st;
+    const int *saved;
+    DbgSkip(Storage &s, bool on) : st(s), saved(s.skip_flag) {
+        if (!on) return;
+        int *flag = st.scratch.get<int>("dbg_skip", 1);
+        const int one = 1;
+        SCANRS_HIP(hipMemcpyAsync(flag, &one, sizeof one, hipMemcpyHostToDevice, st.stream));
+        st.skip_flag = flag;
+    }
+    ~DbgSkip() { st.skip_flag = saved; }
+};
+} // namespace
+extern "C" {
+int scanrs_debug_dense_route(int kind, uint32_t n, uint32_t m, uint64_t rows, uint32_t ldx, uint32_t ldy, int x_aligned16, int side, int flag,
+                             int *route, uint32_t *nt, uint32_t *groups) {
+    return guard([&] {
+        if (!route || !nt || !groups) fail(SCANRS_ERR_ARGUMENT, "null argument");
+        if (kind == 0) {
+            *route = gram_route(n, m, rows, ldx, ldy, side != 0, flag != 0);
+            *nt = *groups = 0;
+        } else if (kind == 1) {
+            if (ldx & 1u) fail(SCANRS_ERR_ARGUMENT, "gemm: ldx must be even");
+            const GemmPlan p = gemm_route(x_aligned16 != 0, ldx, n, m, rows, side != 0, flag != 0);
+            *route = p.route;
+            *nt = p.nt;
+            *groups = p.groups;
+        } else {
+            fail(SCANRS_ERR_ARGUMENT, "kind must be 0 (Gram) or 1 (GEMM)");
+        }
+    });
+}
+int scanrs_debug_dense_gram(scanrs_mat *m, int route, const double *x, uint32_t ldx, uint32_t n, const double *y, uint32_t ldy, uint32_t mcols,
+                            uint64_t rows, uint64_t rows_alloc, int skip, double *c) {
+    return guard([&] {
+        if (!m || !x || !c) fail(SCANRS_ERR_ARGUMENT, "null argument");
+        if (n == 0 || mcols == 0 || rows == 0 || rows_alloc < rows || ldx < n || ldy < mcols) fail(SCANRS_ERR_ARGUMENT, "bad shape");
+        if (!y && (mcols != n || ldy != ldx)) fail(SCANRS_ERR_ARGUMENT, "y == NULL (Y is X) needs mcols == n and ldy == ldx");
+        need_device();
+        Storage &st = *m->st;
+        CurrentHandle cur(&st);
+        const uint64_t nx = dbg_count(rows_alloc, ldx), ny = dbg_count(rows_alloc, ldy), nc = dbg_count(n, mcols);
+        const double *dX = dbg_upload(st, "dbg_X", x, nx);
+        const double *dY = y ? dbg_upload(st, "dbg_Y", y, ny) : dX;
+        double *dC = dbg_upload(st, "dbg_C", c, nc);
+        {
+            DbgSkip sk(st, skip != 0);
+            launch_gram_route(st, route, dX, ldx, n, dY, ldy, mcols, rows, dC);
+        }
+        SCANRS_D2H(c, dC, nc * 8, st.stream);
+    });
+}
+int scanrs_debug_dense_gemm(scanrs_mat *m, int route, const double *x, int x_skew, uint32_t ldx, uint32_t n, const double *w, uint32_t ldw,
+                            uint32_t mcols, uint64_t rows, uint64_t rows_alloc, double alpha, double beta, const double *cin, uint32_t ldc, double *out,
+                            uint32_t ldo, int in_place, int skip) {
+    return guard([&] {
+        if (!m || !x || !w || !out) fail(SCANRS_ERR_ARGUMENT, "null argument");
+        if (n == 0 || mcols == 0 || rows == 0 || rows_alloc < rows || ldx < n || ldw < mcols || ldo < mcols) fail(SCANRS_ERR_ARGUMENT, "bad shape");
+        if (x_skew != 0 && x_skew != 1) fail(SCANRS_ERR_ARGUMENT, "x_skew must be 0 or 1");
+        if (in_place ? ldc != ldo : (cin ? ldc < mcols : beta != 0.0)) fail(SCANRS_ERR_ARGUMENT, "cin: in place needs ldc == ldo, a separate one ldc >= mcols, none beta == 0");
+        const uint64_t nx = dbg_count(rows_alloc, ldx), nw = dbg_count(n, ldw), no = dbg_count(rows_alloc, ldo);
+        const uint64_t ncin = (!in_place && cin) ? dbg_count(rows_alloc, ldc) : 0;
+        if (x < out + no && out < x + nx) fail(SCANRS_ERR_ARGUMENT, "out overlaps x");
+        need_device();
+        Storage &st = *m->st;
+        CurrentHandle cur(&st);
+        const double *dX = dbg_upload(st, "dbg_X", x, nx, (uint64_t)x_skew);
+        const double *dW = dbg_upload(st, "dbg_W", w, nw);
+        double *dOut = dbg_upload(st, "dbg_Out", out, no);
+        const double *dCin = in_place ? dOut : (cin ? dbg_upload(st, "dbg_Cin", cin, ncin) : nullptr);
+        {
+            DbgSkip sk(st, skip != 0);
+            launch_gemm_route(st, route, dX, ldx, n, dW, ldw, mcols, rows, alpha, beta, dCin, ldc, dOut, ldo);
+        }
+        SCANRS_D2H(out, dOut, no * 8, st.stream);
+    });
+}
+int scanrs_debug_weighted_colsum(scanrs_mat *m, const double *b, uint32_t rank, const double *x, uint32_t ldx, uint64_t n, uint32_t l, double *w,
+                                 uint32_t ldw, double *xc, uint32_t ldc) {
+    return guard([&] {
+        if (!m || !b || !x || !w) fail(SCANRS_ERR_ARGUMENT, "null argument");
+        if (rank == 0 || l == 0 || n == 0 || ldw < l || (ldx & 1u) || ldx < even_up(l)) fail(SCANRS_ERR_ARGUMENT, "bad shape (ldx even and >= l rounded up to even)");
+        if (xc && ((l & 1u) || (ldc & 1u) || ldc < l)) fail(SCANRS_ERR_ARGUMENT, "xc needs l and ldc even, ldc >= l");
+        need_device();
+        Storage &st = *m->st;
+        CurrentHandle cur(&st);
+        const uint64_t nb = dbg_count(n, rank), nx = dbg_count(n, ldx), nw = dbg_count(rank, ldw), nxc = xc ? dbg_count(n, ldc) : 0;
+        const double *dB = dbg_upload(st, "dbg_B", b, nb);
+        const double *dX = dbg_upload(st, "dbg_X", x, nx);
+        double *dW = dbg_upload(st, "dbg_W", w, nw);
+        double *dXc = xc ? dbg_upload(st, "dbg_Xc", xc, nxc) : nullptr;
+        launch_weighted_colsum(st, dB, rank, dX, ldx, n, l, dW, ldw, dXc, ldc);
+        SCANRS_D2H(w, dW, nw * 8, st.stream);
+        if (xc) SCANRS_D2H(xc, dXc, nxc * 8, st.stream);
+    });
+}
+
 // ---- host-only utilities exposed for the CPU test-suite (no device needed) --------------------------------------------
 int scanrs_debug_arena_selftest(uint32_t rounds, uint64_t seed) {
     return guard([&] { reserve_selftest(rounds, seed); });

@@ -535,6 +535,24 @@ void launch_gram(Storage &st, const double *X, uint32_t ldx, uint32_t n, const d
 // Out[rows x m] = beta * Cin + alpha * X[rows x n] * W[n x m]   (W device, row-major ld = ldw). Cin may equal Out.
 void launch_gemm_nn(Storage &st, const double *X, uint32_t ldx, uint32_t n, const double *W, uint32_t ldw, uint32_t m,
                     uint64_t rows, double alpha, double beta, const double *Cin, uint32_t ldc, double *Out, uint32_t ldo);
+// Which kernel a dense product goes to, as pure host functions of the shape (dense.hip; the values are the SCANRS_DENSE_* constants of
+// scanrs_amd.h). launch_gram / launch_gemm_nn call them; the *_route launchers take a route (0: the dispatcher's) and refuse a forced
+// kernel whose own preconditions fail (tests: scanrs_debug_dense_*).
+enum GramRoute { GRAM_AUTO = 0, GRAM_WAVE = 1, GRAM_VEC = 2, GRAM_TILED = 3 };
+enum GemmRoute { GEMM_AUTO = 0, GEMM_WAVE = 1, GEMM_TILED = 2, GEMM_SKINNY_LDS = 3, GEMM_DIRECT = 4 };
+struct GemmPlan {
+    GemmRoute route;
+    uint32_t nt;     // MFMA column tiles per wave: NJ of gemm_nn_kernel, NT of gemm_skinny_direct_kernel (LDS forms: 0)
+    uint32_t groups; // column groups (grid.y)
+};
+inline uint32_t gemm_wave_nj(uint32_t m) { return m <= 16u ? 1u : m <= 32u ? 2u : 4u; } // 16-column MFMA tiles per wave of gemm_nn_kernel
+// side: the product is queued on a side stream while dense_side_no_lds is set (register-only forms)
+GramRoute gram_route(uint32_t n, uint32_t m, uint64_t rows, uint32_t ldx, uint32_t ldy, bool side, bool skip_flag_set);
+GemmPlan gemm_route(bool x_aligned16, uint32_t ldx, uint32_t n, uint32_t m, uint64_t rows, bool side, bool gemm_direct);
+void launch_gram_route(Storage &st, int route, const double *X, uint32_t ldx, uint32_t n, const double *Y, uint32_t ldy, uint32_t m,
+                       uint64_t rows, double *C);
+void launch_gemm_route(Storage &st, int route, const double *X, uint32_t ldx, uint32_t n, const double *W, uint32_t ldw, uint32_t m,
+                       uint64_t rows, double alpha, double beta, const double *Cin, uint32_t ldc, double *Out, uint32_t ldo);
 // dense.hip: LDS-tiled MFMA versions for big panels
 bool gram_tiled_ok(uint32_t n, uint32_t m, uint64_t rows);
 bool gemm_tiled_ok(uint32_t n, uint32_t m, uint64_t rows);
@@ -545,6 +563,8 @@ void launch_gemm_direct(Storage &st, const double *X, uint32_t ldx, uint32_t n, 
                         double alpha, double beta, const double *Cin, uint32_t ldc, double *Out, uint32_t ldo);
 void launch_gemm_tiled(Storage &st, const double *X, uint32_t ldx, uint32_t n, const double *W, uint32_t ldw, uint32_t m,
                        uint64_t rows, double alpha, double beta, const double *Cin, uint32_t ldc, double *Out, uint32_t ldo);
+void launch_gemm_skinny_lds(Storage &st, const double *X, uint32_t ldx, uint32_t n, const double *W, uint32_t ldw, uint32_t m,
+                            uint64_t rows, double alpha, double beta, const double *Cin, uint32_t ldc, double *Out, uint32_t ldo);
 void launch_col_scale_dev(Storage &st, double *dst, uint32_t ldd, const double *src, uint32_t lds, uint64_t rows, const double *nsq);
 void launch_col_axpy_dev(Storage &st, double *y, uint32_t ldy, const double *x, uint32_t ldx, uint64_t rows, const double *nsq);
 void launch_col_scale(Storage &st, double *dst, uint32_t ldd, const double *src, uint32_t lds, uint64_t rows, double alpha);

@@ -591,15 +591,50 @@ void launch_gram_tiled(Storage &st, const double *X, uint32_t ldx, uint32_t n, c
 // 10^6 x 500 -> 500 in 11.3 ms = 44 TF against 22 ms through the LDS tiles; groups of 112 there: 12.5 ms). Measured against the LDS-tiled
 // kernels (profiles/microbench/gemm_skinny_probe.hip): 10^6 x 500 -> 50: 1.50 ms (2.5); 10^6 x 400 -> 100: 2.08 (3.6); 33 k x 400 -> 100:
 // 0.11 (0.29); 33 k x 100 -> 100: 0.045 (0.06-0.13).
+static bool gemm_direct_shape_ok(uint32_t ldx, uint32_t n, uint32_t m, uint64_t rows) {
+    return m >= 1u && m <= 4096u && n >= 16u && rows >= 64u && ldx % 2u == 0;
+}
 bool gemm_direct_ok(const double *X, uint32_t ldx, uint32_t n, uint32_t m, uint64_t rows) {
-    return m >= 1u && m <= 4096u && n >= 16u && rows >= 64u && ldx % 2u == 0 && (reinterpret_cast<uintptr_t>(X) & 15u) == 0;
+    return gemm_direct_shape_ok(ldx, n, m, rows) && (reinterpret_cast<uintptr_t>(X) & 15u) == 0;
+}
+// up to 112 columns in ONE group (7 MFMA column tiles per wave, X read once: 10^6 x 400 -> 100 in 2.08 ms against 2.40 in two groups of
+// 64); 113-128 columns in two groups
+static void gemm_direct_plan(uint32_t m, uint32_t *nt, uint32_t *groups) {
+    *groups = m <= 112u ? 1u : (m + 63u) / 64u;
+    *nt = ((m + 15u) / 16u + *groups - 1u) / *groups;
+}
+
+// The dispatch of launch_gram (kernels.hip): one vector against a narrow panel streams (gram_vec_kernel; its reducer has no skip test,
+// so not inside a queued orthonormalisation); big panels with even leading dimensions (16-byte pair loads) go through the LDS tiles
+// unless the product runs on a side stream beside the persistent tile kernel, which holds all of every CU's LDS; the rest one wave
+// per 32 x 32 tile.
+GramRoute gram_route(uint32_t n, uint32_t m, uint64_t rows, uint32_t ldx, uint32_t ldy, bool side, bool skip_flag_set) {
+    if (m == 1u && n <= 128u && rows >= 4096u && !skip_flag_set) return GRAM_VEC;
+    if (!side && gram_tiled_ok(n, m, rows) && !(ldx & 1u) && !(ldy & 1u)) return GRAM_TILED;
+    return GRAM_WAVE;
+}
+// The dispatch of launch_gemm_nn: straight from memory when X can be read in 16-byte pieces; else the LDS tiles for big panels (the
+// 256 x 64 form when the last — or only — 128-column tile would be at most half full), else one wave per 16 rows.
+GemmPlan gemm_route(bool x_aligned16, uint32_t ldx, uint32_t n, uint32_t m, uint64_t rows, bool side, bool gemm_direct) {
+    GemmPlan p{GEMM_WAVE, 0u, 0u};
+    if (gemm_direct && x_aligned16 && gemm_direct_shape_ok(ldx, n, m, rows)) {
+        p.route = GEMM_DIRECT;
+        gemm_direct_plan(m, &p.nt, &p.groups);
+    } else if (!side && gemm_tiled_ok(n, m, rows)) {
+        const bool skinny = (m - 1u) % DT < SK_C;
+        p.route = skinny ? GEMM_SKINNY_LDS : GEMM_TILED;
+        p.groups = skinny ? (m + SK_C - 1u) / SK_C : (m + DT - 1u) / DT;
+    } else {
+        p.nt = gemm_wave_nj(m);
+        p.groups = (m + 16u * p.nt - 1u) / (16u * p.nt);
+    }
+    return p;
 }
 void launch_gemm_direct(Storage &st, const double *X, uint32_t ldx, uint32_t n, const double *W, uint32_t ldw, uint32_t m, uint64_t rows,
                         double alpha, double beta, const double *Cin, uint32_t ldc, double *Out, uint32_t ldo) {
-    // up to 112 columns in ONE group (7 MFMA column tiles per wave, X read once: 10^6 x 400 -> 100 in 2.08 ms against 2.40 in two groups of
-    // 64); 113-128 columns in two groups
-    const uint32_t n_pad = (n + 15u) / 16u * 16u, groups = m <= 112u ? 1u : (m + 63u) / 64u, nt = ((m + 15u) / 16u + groups - 1u) / groups,
-                   m_pad = nt * 16u * groups;
+    uint32_t nt, groups;
+    gemm_direct_plan(m, &nt, &groups);
+    const uint32_t n_pad = (n + 15u) / 16u * 16u, m_pad = nt * 16u * groups;
     double *Wt = st.scratch.get<double>(st.skey("skinny_wt"), (size_t)n_pad * m_pad);
     if (st.prof.on) st.prof.begin(st.stream, "gemm_skinny_mfma_f64", (double)rows * (n + m) * 8.0 + (double)n * m * 8.0);
     hipLaunchKernelGGL(skinny_wt_kernel, dim3((n_pad * m_pad + 255u) / 256u), dim3(256), 0, st.stream, W, ldw, n, m, n_pad, m_pad, Wt, st.skip_flag);
@@ -623,18 +658,20 @@ void launch_gemm_direct(Storage &st, const double *X, uint32_t ldx, uint32_t n, 
 
 void launch_gemm_tiled(Storage &st, const double *X, uint32_t ldx, uint32_t n, const double *W, uint32_t ldw, uint32_t m,
                        uint64_t rows, double alpha, double beta, const double *Cin, uint32_t ldc, double *Out, uint32_t ldo) {
-    if ((m - 1u) % DT < SK_C) { // the last (or only) 128-column tile would be at most half full
-        if (st.prof.on) st.prof.begin(st.stream, "gemm_skinny_mfma_f64", (double)rows * (n + m) * 8.0 + (double)n * m * 8.0);
-        hipLaunchKernelGGL(gemm_skinny_kernel, dim3((unsigned)((rows + SK_R - 1) / SK_R), (m + SK_C - 1) / SK_C), dim3(256), 0, st.stream, X,
-                           ldx, n, W, ldw, m, rows, alpha, beta, Cin, ldc, Out, ldo, st.skip_flag);
-        if (st.prof.on) st.prof.end(st.stream);
-        SCANRS_HIP(hipGetLastError());
-        return;
-    }
     if (st.prof.on) st.prof.begin(st.stream, "gemm_tiled_mfma_f64", (double)rows * (n + m) * 8.0 + (double)n * m * 8.0);
     if (trace_on()) fprintf(stderr, "[scanrs trace] gemm_tiled rows=%llu n=%u m=%u ldx=%u ldw=%u beta=%g\n", (unsigned long long)rows, n, m, ldx, ldw, beta);
     hipLaunchKernelGGL(gemm_tiled_kernel, dim3((unsigned)((rows + DT - 1) / DT), (m + DT - 1) / DT), dim3(256), 0, st.stream, X, ldx,
                        n, W, ldw, m, rows, alpha, beta, Cin, ldc, Out, ldo, st.skip_flag);
+    if (st.prof.on) st.prof.end(st.stream);
+    SCANRS_HIP(hipGetLastError());
+}
+
+// the 256 x 64 LDS form (gemm_route: the last, or only, 128-column tile would be at most half full)
+void launch_gemm_skinny_lds(Storage &st, const double *X, uint32_t ldx, uint32_t n, const double *W, uint32_t ldw, uint32_t m,
+                            uint64_t rows, double alpha, double beta, const double *Cin, uint32_t ldc, double *Out, uint32_t ldo) {
+    if (st.prof.on) st.prof.begin(st.stream, "gemm_skinny_mfma_f64", (double)rows * (n + m) * 8.0 + (double)n * m * 8.0);
+    hipLaunchKernelGGL(gemm_skinny_kernel, dim3((unsigned)((rows + SK_R - 1) / SK_R), (m + SK_C - 1) / SK_C), dim3(256), 0, st.stream, X,
+                       ldx, n, W, ldw, m, rows, alpha, beta, Cin, ldc, Out, ldo, st.skip_flag);
     if (st.prof.on) st.prof.end(st.stream);
     SCANRS_HIP(hipGetLastError());
 }

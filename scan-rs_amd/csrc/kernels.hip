@@ -2238,28 +2238,28 @@ void launch_weighted_colsum(Storage &st, const double *B, uint32_t rank, const d
     SCANRS_HIP(hipGetLastError());
 }
 
-void launch_gram(Storage &st, const double *X, uint32_t ldx, uint32_t n, const double *Y, uint32_t ldy, uint32_t m,
-                 uint64_t rows, double *C) {
-    if (n == 0 || m == 0) return;
-    if (m == 1u && n <= 128u && rows >= 4096u && !st.skip_flag) { // one vector against a narrow panel: the streaming form (gram_vec_kernel)
-        const uint32_t blocks = (uint32_t)std::min<uint64_t>(1024, (rows + 255) / 256);
-        const uint64_t rpb = (rows + blocks - 1) / blocks;
-        double *slab = st.scratch.get<double>(st.skey("gram_slab"), (size_t)blocks * n);
-        ProfScope ps(st, "gram_vec_f64", (double)rows * (n + 1) * 8.0);
-        hipLaunchKernelGGL(gram_vec_kernel, dim3(blocks), dim3(256), 0, st.stream, X, ldx, n, Y, ldy, rows, rpb, slab, st.skip_flag);
-        // (the blocks' partials in block order, four groups of 64 threads with eight loads in flight each: the plain ordered loop of
-        // gram_finish_kernel walks 1 024 partials one load at a time)
-        hipLaunchKernelGGL(weighted_colsum_finish_kernel, grid1((uint64_t)n, 64), dim3(256), 0, st.stream, slab, blocks, 1u, n, C, n);
-        SCANRS_HIP(hipGetLastError());
-        return;
-    }
+static bool on_side_stream(const Storage &st) {
     // work queued on a side stream runs beside the persistent tile kernel of a sparse pass, which holds all of every CU's LDS: a
-    // kernel that needs LDS waits for the end of the pass; the register-only MFMA kernels below fit the registers the tile kernel leaves
-    const bool side = st.dense_side_no_lds && ((st.aux_stream && st.stream == st.aux_stream) || (st.aux2_stream && st.stream == st.aux2_stream));
-    if (!side && gram_tiled_ok(n, m, rows) && !(ldx & 1u) && !(ldy & 1u)) {
-        launch_gram_tiled(st, X, ldx, n, Y, ldy, m, rows, C);
-        return;
-    }
+    // kernel that needs LDS waits for the end of the pass; the register-only MFMA kernels fit the registers the tile kernel leaves
+    return st.dense_side_no_lds && ((st.aux_stream && st.stream == st.aux_stream) || (st.aux2_stream && st.stream == st.aux2_stream));
+}
+
+// one vector against a narrow panel: the streaming form (gram_vec_kernel)
+static void launch_gram_vec(Storage &st, const double *X, uint32_t ldx, uint32_t n, const double *Y, uint32_t ldy, uint64_t rows, double *C) {
+    const uint32_t blocks = (uint32_t)std::min<uint64_t>(1024, (rows + 255) / 256);
+    const uint64_t rpb = (rows + blocks - 1) / blocks;
+    double *slab = st.scratch.get<double>(st.skey("gram_slab"), (size_t)blocks * n);
+    ProfScope ps(st, "gram_vec_f64", (double)rows * (n + 1) * 8.0);
+    hipLaunchKernelGGL(gram_vec_kernel, dim3(blocks), dim3(256), 0, st.stream, X, ldx, n, Y, ldy, rows, rpb, slab, st.skip_flag);
+    // (the blocks' partials in block order, four groups of 64 threads with eight loads in flight each: the plain ordered loop of
+    // gram_finish_kernel walks 1 024 partials one load at a time)
+    hipLaunchKernelGGL(weighted_colsum_finish_kernel, grid1((uint64_t)n, 64), dim3(256), 0, st.stream, slab, blocks, 1u, n, C, n);
+    SCANRS_HIP(hipGetLastError());
+}
+
+// one wave per (32 x 32 tile of C, row slice)
+static void launch_gram_wave(Storage &st, const double *X, uint32_t ldx, uint32_t n, const double *Y, uint32_t ldy, uint32_t m,
+                             uint64_t rows, double *C) {
     const uint32_t tiles_n = (n + 31u) / 32u, tiles_m = (m + 31u) / 32u;
     const uint64_t tiles = (uint64_t)tiles_n * tiles_m;
     // aim for ~8k waves, at least 64 rows per slice
@@ -2280,27 +2280,40 @@ void launch_gram(Storage &st, const double *X, uint32_t ldx, uint32_t n, const d
     SCANRS_HIP(hipGetLastError());
 }
 
-void launch_gemm_nn(Storage &st, const double *X, uint32_t ldx, uint32_t n, const double *W, uint32_t ldw, uint32_t m,
-                    uint64_t rows, double alpha, double beta, const double *Cin, uint32_t ldc, double *Out,
-                    uint32_t ldo) {
-    if (rows == 0 || m == 0) return;
-    if (ldx & 1u) fail(SCANRS_ERR_ARGUMENT, "gemm: ldx must be even");
-    if (st.gemm_direct && gemm_direct_ok(X, ldx, n, m, rows)) {
-        launch_gemm_direct(st, X, ldx, n, W, ldw, m, rows, alpha, beta, Cin, ldc, Out, ldo);
-        return;
+void launch_gram_route(Storage &st, int route, const double *X, uint32_t ldx, uint32_t n, const double *Y, uint32_t ldy, uint32_t m,
+                       uint64_t rows, double *C) {
+    if (n == 0 || m == 0) return;
+    if (route == GRAM_AUTO) {
+        route = gram_route(n, m, rows, ldx, ldy, on_side_stream(st), st.skip_flag != nullptr);
+    } else if (route == GRAM_VEC) { // a forced kernel: its own preconditions, not the thresholds
+        if (m != 1u || n > 128u || st.skip_flag) fail(SCANRS_ERR_ARGUMENT, "gram_vec: one vector, at most 128 panel columns, no skip flag");
+    } else if (route == GRAM_TILED) {
+        if ((ldx & 1u) || (ldy & 1u)) fail(SCANRS_ERR_ARGUMENT, "gram_tiled: ldx and ldy must be even");
+    } else if (route != GRAM_WAVE) {
+        fail(SCANRS_ERR_ARGUMENT, "unknown Gram route %d", route);
     }
-    const bool side = st.dense_side_no_lds && ((st.aux_stream && st.stream == st.aux_stream) || (st.aux2_stream && st.stream == st.aux2_stream));
-    if (!side && gemm_tiled_ok(n, m, rows)) {
-        launch_gemm_tiled(st, X, ldx, n, W, ldw, m, rows, alpha, beta, Cin, ldc, Out, ldo);
-        return;
-    }
+    if (route == GRAM_VEC)
+        launch_gram_vec(st, X, ldx, n, Y, ldy, rows, C);
+    else if (route == GRAM_TILED)
+        launch_gram_tiled(st, X, ldx, n, Y, ldy, m, rows, C);
+    else
+        launch_gram_wave(st, X, ldx, n, Y, ldy, m, rows, C);
+}
+void launch_gram(Storage &st, const double *X, uint32_t ldx, uint32_t n, const double *Y, uint32_t ldy, uint32_t m,
+                 uint64_t rows, double *C) {
+    launch_gram_route(st, GRAM_AUTO, X, ldx, n, Y, ldy, m, rows, C);
+}
+
+// one wave per 16 rows x 16 NJ columns
+static void launch_gemm_wave(Storage &st, uint32_t nj, const double *X, uint32_t ldx, uint32_t n, const double *W, uint32_t ldw, uint32_t m,
+                             uint64_t rows, double alpha, double beta, const double *Cin, uint32_t ldc, double *Out, uint32_t ldo) {
     const uint64_t waves = (rows + 15) / 16;
     ProfScope ps(st, "gemm_nn_mfma_f64", (double)rows * (n + m) * 8.0 + (double)n * m * 8.0);
     const dim3 block(256);
-    if (m <= 16) {
+    if (nj == 1u) {
         hipLaunchKernelGGL((gemm_nn_kernel<1>), dim3((unsigned)((waves + 3) / 4), (m + 15u) / 16u), block, 0, st.stream, X,
                            ldx, n, W, ldw, m, rows, alpha, beta, Cin, ldc, Out, ldo, st.skip_flag);
-    } else if (m <= 32) {
+    } else if (nj == 2u) {
         hipLaunchKernelGGL((gemm_nn_kernel<2>), dim3((unsigned)((waves + 3) / 4), (m + 31u) / 32u), block, 0, st.stream, X,
                            ldx, n, W, ldw, m, rows, alpha, beta, Cin, ldc, Out, ldo, st.skip_flag);
     } else {
@@ -2308,6 +2321,33 @@ void launch_gemm_nn(Storage &st, const double *X, uint32_t ldx, uint32_t n, cons
                            ldx, n, W, ldw, m, rows, alpha, beta, Cin, ldc, Out, ldo, st.skip_flag);
     }
     SCANRS_HIP(hipGetLastError());
+}
+
+void launch_gemm_route(Storage &st, int route, const double *X, uint32_t ldx, uint32_t n, const double *W, uint32_t ldw, uint32_t m,
+                       uint64_t rows, double alpha, double beta, const double *Cin, uint32_t ldc, double *Out, uint32_t ldo) {
+    if (rows == 0 || m == 0) return;
+    if (ldx & 1u) fail(SCANRS_ERR_ARGUMENT, "gemm: ldx must be even");
+    const bool aligned = (reinterpret_cast<uintptr_t>(X) & 15u) == 0;
+    if (route == GEMM_AUTO) {
+        route = gemm_route(aligned, ldx, n, m, rows, on_side_stream(st), st.gemm_direct != 0).route;
+    } else if (route == GEMM_DIRECT) { // a forced kernel: its own preconditions, not the dispatcher's choice
+        if (!gemm_direct_ok(X, ldx, n, m, rows)) fail(SCANRS_ERR_ARGUMENT, "gemm_direct: needs X 16-byte aligned, n >= 16, rows >= 64, m <= 4096");
+    } else if (route != GEMM_WAVE && route != GEMM_TILED && route != GEMM_SKINNY_LDS) {
+        fail(SCANRS_ERR_ARGUMENT, "unknown GEMM route %d", route);
+    }
+    if (route == GEMM_DIRECT)
+        launch_gemm_direct(st, X, ldx, n, W, ldw, m, rows, alpha, beta, Cin, ldc, Out, ldo);
+    else if (route == GEMM_TILED)
+        launch_gemm_tiled(st, X, ldx, n, W, ldw, m, rows, alpha, beta, Cin, ldc, Out, ldo);
+    else if (route == GEMM_SKINNY_LDS)
+        launch_gemm_skinny_lds(st, X, ldx, n, W, ldw, m, rows, alpha, beta, Cin, ldc, Out, ldo);
+    else
+        launch_gemm_wave(st, gemm_wave_nj(m), X, ldx, n, W, ldw, m, rows, alpha, beta, Cin, ldc, Out, ldo);
+}
+void launch_gemm_nn(Storage &st, const double *X, uint32_t ldx, uint32_t n, const double *W, uint32_t ldw, uint32_t m,
+                    uint64_t rows, double alpha, double beta, const double *Cin, uint32_t ldc, double *Out,
+                    uint32_t ldo) {
+    launch_gemm_route(st, GEMM_AUTO, X, ldx, n, W, ldw, m, rows, alpha, beta, Cin, ldc, Out, ldo);
 }
 
 // one column with a scalar that arrives as a kernel argument (IRLBA's normalisations and three-term updates, irlba.rs:137-160: the
