@@ -594,7 +594,7 @@ int scanrs_host_sym_eig(const double *a, int n, double *w, double *z);
 /* the k leading eigenpairs only: w[0..k) descending, z row-major n x k */
 int scanrs_host_sym_eig_topk(const double *a, int n, int k, double *w, double *z);
 
-/* ---- sSeq differential expression (diff-exp/src/diff_exp.rs, dist.rs; NbExactBackend::LogSpace) ----------------------------
+/* ---- sSeq differential expression (diff-exp/src/diff_exp.rs, dist.rs; NbExactBackend::LogSpace and ::Ratio) ----------------
  * Rows of the handle are genes and columns are cells (the reference's feature x barcode matrix; use scanrs_mat_t on a cell-major
  * handle). DE reads the stored u32 counts and ignores the handle's map and offset. Labels are one int16 per cell: the group
  * 0 .. n_groups - 1 (n_groups <= 8192) or -1 for a cell in no group. Sharded handles return SCANRS_ERR_ARGUMENT. Outputs of
@@ -629,11 +629,40 @@ int scanrs_sseq_de_from_sums(uint64_t n_genes, uint32_t n_tests, const uint64_t 
                              const double *sf_b, const double *gene_means, const double *gene_phi, const uint8_t *use_genes,
                              uint64_t big_count, const scanrs_snoop *snoop, double *p, double *p_adj, double *log2fc, double *mean_in,
                              double *mean_out);
+/* `NbExactBackend` (dist.rs:52-68): the kernel of the exact branch. LogSpace is the log-sum-exp over per-term lnΓ values; Ratio is
+ * the mode-anchored ratio recurrence `nb_exact_test_ratio` (dist.rs:116-215): one division and a few multiplies per term. */
+enum { SCANRS_NB_EXACT_LOGSPACE = 0, SCANRS_NB_EXACT_RATIO = 1 };
+/* `sseq_differential_expression_with_cancellation_backend` (diff_exp.rs:125-161) from labels: scanrs_sseq_de with the exact
+ * test's backend; any other value of `backend` returns SCANRS_ERR_ARGUMENT. scanrs_sseq_de is this call with LogSpace.
+ * It also takes mode 2, the shared-control shape: every group 1 .. n_groups-1 against group 0 (n_tests = n_groups - 1, test j
+ * is group j + 1 as side a and group 0 as side b; needs n_groups >= 2). The control's sums and size factor are computed once;
+ * every test equals the mode 1 call of its two groups bit for bit. (scanrs_sseq_de refuses mode 2.)
+ * Ratio on the device differs from dist.rs:199-203 in one deliberate way: the reference falls back to LogSpace only when the
+ * observed term U[x_a] is 0 or not finite; here a test whose U[x_a] is not finite or below 2^-970 falls back, in the same call,
+ * and gets exactly the p-value that backend = LogSpace gives it. For 0 < U[x_a] < 2^-970 the terms at and below U[x_a] sink
+ * into the denormals and the serial partition loses its bits (at U[x_a] = 4.9e-324 the serial restatement returns 5.9e-323
+ * where LogSpace returns 0). Elsewhere the device sums the reference's terms in a fixed tree rather than serially. */
+int scanrs_sseq_de_backend(scanrs_mat *m, const int16_t *labels, uint32_t n_groups, int mode, const double *size_factors,
+                           const double *gene_means, const double *gene_phi, const uint8_t *use_genes, uint64_t big_count, int backend,
+                           const scanrs_snoop *snoop, uint64_t *sums_in, uint64_t *sums_out, double *p, double *p_adj, double *log2fc,
+                           double *mean_in, double *mean_out);
+/* `sseq_de_from_sums_with_cancellation` (diff_exp.rs:208-300) on the device: scanrs_sseq_de_from_sums with the exact test's
+ * backend (Cell Ranger's batched shared-control path passes Ratio, diff_exp.rs:172-175); scanrs_sseq_de_from_sums is this call
+ * with LogSpace. Any other value of `backend` returns SCANRS_ERR_ARGUMENT. */
+int scanrs_sseq_de_from_sums_backend(uint64_t n_genes, uint32_t n_tests, const uint64_t *sums_a, const uint64_t *sums_b, const double *sf_a,
+                                     const double *sf_b, const double *gene_means, const double *gene_phi, const uint8_t *use_genes,
+                                     uint64_t big_count, int backend, const scanrs_snoop *snoop, double *p, double *p_adj, double *log2fc,
+                                     double *mean_in, double *mean_out);
 /* the shared math on the host (no device needed; the kernels run the same special functions): `nb_exact_test`
  * (dist.rs:74-118), `nb_asymptotic_test` (:226-257), `log_prob_all` (:259-310, n + 1 values), `adjusted_pvalue_bh` (:22-50,
  * out[i] belongs to p[i]), and the regularised incomplete beta function and its inverse in p */
 int scanrs_host_nb_exact_test(uint64_t x_a, uint64_t x_b, double sf_a, double sf_b, double mu, double phi, double *p);
 int scanrs_host_nb_asymptotic_test(uint64_t x_a, uint64_t x_b, double sf_a, double sf_b, double mu, double phi, double *p);
+/* `nb_exact_test_ratio` (dist.rs:155-215), host only, line for line: the three guards (exactly 1.0), the scan for the anchor, the
+ * two sweeps, the serial sums, and the fallback to scanrs_host_nb_exact_test when the observed term is 0 or not finite. */
+int scanrs_host_nb_exact_test_ratio(uint64_t x_a, uint64_t x_b, double sf_a, double sf_b, double mu, double phi, double *p);
+/* `nb_exact_ratio_step` (dist.rs:124-126), host only: T(k+1)/T(k) = (sa_r + k)(n - k) / ((k + 1)(sb_r + n - k - 1)) */
+int scanrs_host_nb_exact_ratio_step(double k, double n, double sa_r, double sb_r, double *out);
 int scanrs_host_nb_log_prob_all(uint64_t n, double sf_a, double sf_b, double mu, double r, double *out);
 int scanrs_host_adjusted_pvalue_bh(const double *p, uint64_t n, double *out);
 int scanrs_host_betainc(double a, double b, double x, double *out);

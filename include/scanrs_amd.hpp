@@ -520,6 +520,7 @@ namespace diff_exp {
 // sSeq differential expression (diff-exp/src/diff_exp.rs): genes = rows, cells = cols of the handle; raw u32 counts
 constexpr uint64_t BIG_COUNT_DEFAULT = 900;
 constexpr double ZETA_QUINTILE_DEFAULT = 0.995;
+enum class NbExactBackend : int { LogSpace = SCANRS_NB_EXACT_LOGSPACE, Ratio = SCANRS_NB_EXACT_RATIO }; // dist.rs:52-68
 struct SSeqParams { // diff_exp.rs:19-40
     uint32_t num_cells = 0, num_genes = 0;
     std::vector<double> size_factors, gene_means, gene_variances;
@@ -549,16 +550,19 @@ inline SSeqParams compute_sseq_params(const AdaptiveMat &m, double zeta_quintile
                              p.use_genes.data(), p.gene_moment_phi.data(), &p.zeta_hat, &p.delta, p.gene_phi.data()));
     return p;
 }
-// one result per test: labels per cell (-1 = in no group); mode 0 each group against the rest, mode 1 group 0 against group 1
+// one result per test: labels per cell (-1 = in no group); mode 0 each group against the rest, mode 1 group 0 against group 1,
+// mode 2 each group 1 .. n_groups - 1 against group 0 (a shared control); backend: the exact test's kernel (diff_exp.rs:125-161)
 inline std::vector<DiffExpResult> sseq_de(const AdaptiveMat &m, const std::vector<int16_t> &labels, uint32_t n_groups, int mode,
-                                          const SSeqParams &p, uint64_t big_count = BIG_COUNT_DEFAULT, Snoop *snoop = nullptr) {
+                                          const SSeqParams &p, uint64_t big_count = BIG_COUNT_DEFAULT, Snoop *snoop = nullptr,
+                                          NbExactBackend backend = NbExactBackend::LogSpace) {
     const uint64_t g = m.rows();
-    const uint32_t t = mode == 0 ? n_groups : 1;
+    const uint32_t t = mode == 0 ? n_groups : mode == 2 && n_groups > 0 ? n_groups - 1 : 1;
     std::vector<uint64_t> si(g * t), so(g * t);
     std::vector<double> pv(g * t), pa(g * t), l2(g * t), mi(g * t), mo(g * t);
     scanrs_snoop sn = detail::make_snoop(snoop);
-    check(scanrs_sseq_de(m.raw(), labels.data(), n_groups, mode, p.size_factors.data(), p.gene_means.data(), p.gene_phi.data(), p.use_genes.data(),
-                         big_count, snoop ? &sn : nullptr, si.data(), so.data(), pv.data(), pa.data(), l2.data(), mi.data(), mo.data()));
+    check(scanrs_sseq_de_backend(m.raw(), labels.data(), n_groups, mode, p.size_factors.data(), p.gene_means.data(), p.gene_phi.data(),
+                                 p.use_genes.data(), big_count, (int)backend, snoop ? &sn : nullptr, si.data(), so.data(), pv.data(), pa.data(),
+                                 l2.data(), mi.data(), mo.data()));
     std::vector<DiffExpResult> out(t);
     for (uint32_t j = 0; j < t; j++) {
         DiffExpResult &r = out[j];
@@ -573,6 +577,33 @@ inline std::vector<DiffExpResult> sseq_de(const AdaptiveMat &m, const std::vecto
             r.normalized_mean_out.push_back(mo[o]);
         }
     }
+    return out;
+}
+// sseq_de_from_sums (diff_exp.rs:177-198) for one test: per-gene sums of the two sides and their size factors
+inline DiffExpResult sseq_de_from_sums(const std::vector<uint64_t> &sums_a, const std::vector<uint64_t> &sums_b, double size_factor_a,
+                                       double size_factor_b, const SSeqParams &p, NbExactBackend backend = NbExactBackend::LogSpace,
+                                       uint64_t big_count = BIG_COUNT_DEFAULT, Snoop *snoop = nullptr) {
+    const uint64_t g = sums_a.size();
+    DiffExpResult r;
+    r.sums_in = sums_a;
+    r.sums_out = sums_b;
+    for (auto *v : {&r.p_values, &r.adjusted_p_values, &r.log2_fold_change, &r.normalized_mean_in, &r.normalized_mean_out}) v->resize(g);
+    scanrs_snoop sn = detail::make_snoop(snoop);
+    check(scanrs_sseq_de_from_sums_backend(g, 1, sums_a.data(), sums_b.data(), &size_factor_a, &size_factor_b, p.gene_means.data(),
+                                           p.gene_phi.data(), p.use_genes.data(), big_count, (int)backend, snoop ? &sn : nullptr, r.p_values.data(),
+                                           r.adjusted_p_values.data(), r.log2_fold_change.data(), r.normalized_mean_in.data(),
+                                           r.normalized_mean_out.data()));
+    return r;
+}
+// nb_exact_test_ratio (dist.rs:155-215) and nb_exact_ratio_step (dist.rs:124-126) on the host
+inline double host_nb_exact_test_ratio(uint64_t x_a, uint64_t x_b, double sf_a, double sf_b, double mu, double phi) {
+    double p = 0.0;
+    check(scanrs_host_nb_exact_test_ratio(x_a, x_b, sf_a, sf_b, mu, phi, &p));
+    return p;
+}
+inline double host_nb_exact_ratio_step(double k, double n, double sa_r, double sb_r) {
+    double out = 0.0;
+    check(scanrs_host_nb_exact_ratio_step(k, n, sa_r, sb_r, &out));
     return out;
 }
 inline std::vector<uint64_t> group_sums(const AdaptiveMat &m, const std::vector<int16_t> &labels, uint32_t n_groups) { // genes x n_groups

@@ -1110,6 +1110,7 @@ EXPORTED_SYMBOLS = [
     "scanrs_h5_read_umi_counts", "scanrs_h5_get_clustering_keys", "scanrs_h5_get_clustering", "scanrs_h5_get_differential_expression",
     "scanrs_h5_read_f64", "scanrs_h5_read_strings", "scanrs_h5_member_names", "scanrs_mtx_read", "scanrs_mat_create_from_file",
     "scanrs_sseq_params", "scanrs_sseq_params_from_moments", "scanrs_mat_group_sums", "scanrs_sseq_de", "scanrs_sseq_de_from_sums",
+    "scanrs_sseq_de_backend", "scanrs_sseq_de_from_sums_backend", "scanrs_host_nb_exact_test_ratio", "scanrs_host_nb_exact_ratio_step",
     "scanrs_host_nb_exact_test", "scanrs_host_nb_asymptotic_test", "scanrs_host_nb_log_prob_all", "scanrs_host_adjusted_pvalue_bh",
     "scanrs_host_betainc", "scanrs_host_betaincinv",
     "scanrs_host_pdist", "scanrs_host_linkage_complete", "scanrs_host_relabel_by_size", "scanrs_cluster_medoids", "scanrs_cluster_medoids_device",
@@ -1121,8 +1122,9 @@ EXPORTED_SYMBOLS = [
 
 # sSeq differential expression (sseq.py)
 from .sseq import (  # noqa: E402
-    DiffExpResult, SSeqParams, compute_sseq_params, diff_exp_table, group_sums, labels_from_clustering, sseq_de_from_sums, sseq_de_one_vs_rest,
-    sseq_differential_expression, sseq_params_from_moments,
+    NB_EXACT_LOGSPACE, NB_EXACT_RATIO, DiffExpResult, SSeqParams, compute_sseq_params, diff_exp_table, group_sums, host_nb_exact_ratio_step,
+    host_nb_exact_test_ratio, labels_from_clustering, sseq_de_from_sums, sseq_de_one_vs_rest, sseq_de_vs_control, sseq_differential_expression,
+    sseq_params_from_moments,
 )
 
 # merge_clusters, linkage and medoids (cluster.py)

@@ -669,6 +669,12 @@ struct SseqAsymTest {
     double sf_a, sf_b, mu, phi;
     uint64_t out;
 };
+struct SseqRatioTest {       // one exact test of the Ratio backend (sseq_ratio.inc): ceil(anchor / SSEQ_CHUNK) chunks below the anchor, then
+    uint64_t n, xa, anchor;  // ceil((n - anchor) / SSEQ_CHUNK) above it; anchor: the first k whose step is below 1, else n (dist.rs:178-184)
+    double sar, sbr;
+    uint64_t chunk0, out;
+};
+constexpr double SSEQ_RATIO_FALLBACK = -1.0; // written in place of a p-value: the test has to go through the LogSpace kernels
 uint32_t sseq_max_count(Storage &st, const SparseCopy &cp);
 void launch_sseq_cell_totals(Storage &st, const SparseCopy &cp, bool gene_major, uint64_t n_cells, unsigned long long *d_tot);
 // sums: genes x n_groups; with d_mom also Σ x/sf and Σ (x/sf)² over the labelled cells as 128-bit fixed point (genes x 4 u64)
@@ -678,6 +684,8 @@ void launch_sseq_group_pass(Storage &st, const SparseCopy &cp, bool gene_major, 
 void launch_sseq_exact(hipStream_t s, const SseqExactTest *d_tests, uint32_t n_tests, uint64_t n_chunks, double *d_obs, double4 *d_part,
                        double *d_p);
 void launch_sseq_asymptotic(hipStream_t s, const SseqAsymTest *d_tests, uint32_t n_tests, double *d_p);
+void launch_sseq_ratio(hipStream_t s, const SseqRatioTest *d_tests, uint32_t n_tests, uint64_t n_chunks, double *d_obs, double *d_scale,
+                       double2 *d_part, double *d_p);
 // host side (sseq_host.cpp); `cp` is the resident copy, gene_major when its outer vectors are the genes (the view's rows)
 void sseq_params(Storage &st, const SparseCopy &cp, bool gene_major, uint64_t genes, uint64_t cells, double zeta_quintile,
                  const uint64_t *cell_indices, uint64_t n_sel, const double *umi_counts, double *size_factors, double *gene_means,
@@ -690,14 +698,17 @@ void sseq_group_sums(Storage &st, const SparseCopy &cp, bool gene_major, uint64_
 void sseq_de_matrix(Storage &st, const SparseCopy &cp, bool gene_major, uint64_t genes, uint64_t cells, const int16_t *labels,
                     uint32_t n_groups, int mode, const double *size_factors, const double *gene_means, const double *gene_phi,
                     const uint8_t *use_genes, uint64_t big_count, const scanrs_snoop *snoop, uint64_t *sums_in, uint64_t *sums_out, double *p,
-                    double *p_adj, double *log2fc, double *mean_in, double *mean_out);
+                    double *p_adj, double *log2fc, double *mean_in, double *mean_out, int backend = SCANRS_NB_EXACT_LOGSPACE);
 // the tests, BH, log2 fold change and normalized means from per-gene sums (genes x n_tests, row-major)
 void sseq_de_sums(hipStream_t s, uint64_t genes, uint32_t n_tests, const uint64_t *sums_a, const uint64_t *sums_b, const double *sf_a,
                   const double *sf_b, const double *gene_means, const double *gene_phi, const uint8_t *use_genes, uint64_t big_count,
-                  const scanrs_snoop *snoop, double *p, double *p_adj, double *log2fc, double *mean_in, double *mean_out);
+                  const scanrs_snoop *snoop, double *p, double *p_adj, double *log2fc, double *mean_in, double *mean_out,
+                  int backend = SCANRS_NB_EXACT_LOGSPACE);
 // the copy DE walks: the gene-major one when it is resident, else the cell-major one (shared with merge_clusters)
 SCANRS_LOCAL SparseCopy &sseq_resident_copy(scanrs_mat *m, bool *gene_major);
 double sseq_host_exact_test(uint64_t xa, uint64_t xb, double sf_a, double sf_b, double mu, double phi);
+double sseq_host_exact_test_ratio(uint64_t xa, uint64_t xb, double sf_a, double sf_b, double mu, double phi);
+uint64_t sseq_ratio_anchor(uint64_t n, double sar, double sbr);
 void sseq_host_bh(const double *p, uint64_t n, double *out);
 
 // ---- cluster.hip / cluster_host.cpp: merge_clusters (scan-rs/src/merge_clusters.rs, linkage.rs) ---------------------------------

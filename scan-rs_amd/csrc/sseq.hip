@@ -8,6 +8,7 @@
 //   sseq_cell_totals_kernel  per-cell count totals (size factors) from either copy
 //   sseq_exact_*_kernel      the exact NB test (dist.rs:74-118, 259-310) over a flat list of fixed-size term chunks
 //   sseq_asymptotic_kernel   the beta approximation (dist.rs:226-257), one thread per test
+//   sseq_ratio_*_kernel      the Ratio backend of the exact test (dist.rs:116-215): sseq_ratio.inc
 //
 // No float atomics. The moments are accumulated as 128-bit FIXED-POINT integers (two u64 words, carry counted
 // with an integer atomic): every term x/sf_c is rounded once to a quantum of 2^-E (E chosen per launch from a bound of the
@@ -331,3 +332,5 @@ void launch_sseq_asymptotic(hipStream_t s, const SseqAsymTest *d_tests, uint32_t
 }
 
 } // namespace scanrs
+
+#include "sseq_ratio.inc"

@@ -94,6 +94,55 @@ double sseq_host_exact_test(uint64_t xa, uint64_t xb, double sf_a, double sf_b, 
     return std::exp((std::log(sum_ext) + max_ext) - (std::log(sum_all) + max_all));
 }
 
+// nb_exact_ratio_step (dist.rs:124-126)
+static inline double ratio_step(double k, double n, double sa_r, double sb_r) { return (sa_r + k) * (n - k) / ((k + 1.0) * (sb_r + n - k - 1.0)); }
+
+// nb_exact_test_ratio (dist.rs:155-215), line for line
+double sseq_host_exact_test_ratio(uint64_t xa, uint64_t xb, double sf_a, double sf_b, double mu, double phi) {
+    if (xa + xb == 0) return 1.0;
+    if (phi == 0.0) return 1.0;
+    if (sf_a == 0.0 || sf_b == 0.0) return 1.0;
+    const uint64_t n = xa + xb;
+    const double nn = (double)n;
+    const double r = 1.0 / phi;
+    const double sa_r = sf_a * r, sb_r = sf_b * r;
+    uint64_t mode = n;
+    for (uint64_t k = 0; k < n; k++)
+        if (ratio_step((double)k, nn, sa_r, sb_r) < 1.0) {
+            mode = k;
+            break;
+        }
+    std::vector<double> u(n + 1, 0.0);
+    u[mode] = 1.0;
+    for (uint64_t k = mode; k < n; k++) u[k + 1] = u[k] * ratio_step((double)k, nn, sa_r, sb_r);
+    for (uint64_t k = mode; k-- > 0;) u[k] = u[k + 1] / ratio_step((double)k, nn, sa_r, sb_r);
+    const double u_obs = u[xa];
+    if (u_obs == 0.0 || !std::isfinite(u_obs)) return sseq_host_exact_test(xa, xb, sf_a, sf_b, mu, phi);
+    double sum_all = 0.0, sum_ext = 0.0;
+    for (double v : u) {
+        sum_all += v;
+        if (v <= u_obs) sum_ext += v;
+    }
+    return sum_ext / sum_all;
+}
+
+// The anchor of nb_exact_test_ratio (dist.rs:178-184: the first k in 0 .. n-1 with step(k) < 1, else n) without the scan.
+// step(k) < 1  <=>  (sa_r + k)(n - k) < (k + 1)(sb_r + n - k - 1)  <=>  n (sa_r - 1) - (sb_r - 1) < k (sa_r + sb_r - 2): the k^2 and
+// k n terms cancel. With B = sa_r + sb_r - 2 > 0 the steps cross 1 once, downwards, behind k = A / B; with B <= 0 they are below
+// 1 on a prefix of the range only, so the answer is 0 or n and the f64 predicate at k = 0 decides. For B > 0 the f64 predicate at
+// the neighbours moves the closed form onto the reference's rounding. The anchor fixes the range of the terms, not the result.
+uint64_t sseq_ratio_anchor(uint64_t n, double sa_r, double sb_r) {
+    const double nn = (double)n;
+    auto below = [&](uint64_t k) { return ratio_step((double)k, nn, sa_r, sb_r) < 1.0; };
+    const double a = nn * (sa_r - 1.0) - (sb_r - 1.0), b = sa_r + sb_r - 2.0;
+    if (!(b > 0.0)) return below(0) ? 0 : n;
+    const double q = a / b;
+    uint64_t k = !(q >= 0.0) ? 0 : q >= nn ? n : std::min<uint64_t>(n, (uint64_t)std::floor(q) + 1);
+    for (int i = 0; i < 64 && k > 0 && below(k - 1); i++) k--;
+    for (int i = 0; i < 64 && k < n && !below(k); i++) k++;
+    return k;
+}
+
 // adjusted_pvalue_bh (dist.rs:22-50): descending, NaNs in front (stable), q = min(1, running min of p n/(n - rank))
 void sseq_host_bh(const double *p, uint64_t n, double *out) {
     std::vector<uint64_t> ord(n);
@@ -241,11 +290,23 @@ void sseq_params(Storage &st, const SparseCopy &cp, bool gene_major, uint64_t ge
 // ---- sseq_de_from_sums_with_cancellation (diff_exp.rs:190-300) ------------------------------------------------------------------
 void sseq_de_sums(hipStream_t s, uint64_t genes, uint32_t n_tests, const uint64_t *sums_a, const uint64_t *sums_b, const double *sf_a,
                   const double *sf_b, const double *gene_means, const double *gene_phi, const uint8_t *use_genes, uint64_t big_count,
-                  const scanrs_snoop *snoop, double *p, double *p_adj, double *log2fc, double *mean_in, double *mean_out) {
+                  const scanrs_snoop *snoop, double *p, double *p_adj, double *log2fc, double *mean_in, double *mean_out, int backend) {
+    if (backend != SCANRS_NB_EXACT_LOGSPACE && backend != SCANRS_NB_EXACT_RATIO)
+        fail(SCANRS_ERR_ARGUMENT, "backend must be SCANRS_NB_EXACT_LOGSPACE (0) or SCANRS_NB_EXACT_RATIO (1)");
+    const bool ratio = backend == SCANRS_NB_EXACT_RATIO;
     const uint64_t total = genes * n_tests;
     std::vector<SseqExactTest> ex;
     std::vector<SseqAsymTest> as;
-    uint64_t n_chunks = 0;
+    std::vector<SseqRatioTest> rt;
+    uint64_t n_chunks = 0, n_rchunks = 0;
+    // one LogSpace test; a test's chunks and its result depend on its own inputs only, so a test that falls back from Ratio gets the bits
+    // that backend = LogSpace gives it
+    auto push_exact = [&](uint64_t o, uint32_t j, uint64_t g) {
+        const uint64_t xa = sums_a[o], n = xa + sums_b[o];
+        const double fa = sf_a[j], fb = sf_b[j], r = 1.0 / gene_phi[g];
+        ex.push_back(SseqExactTest{n, xa, fa * r, fb * r, special::nb_add_total(n, fa, fb, gene_means[g], r), n_chunks, o});
+        n_chunks += (n + SSEQ_CHUNK) / SSEQ_CHUNK; // n + 1 terms
+    };
     for (uint64_t g = 0; g < genes; g++) {
         for (uint32_t j = 0; j < n_tests; j++) {
             const uint64_t o = g * n_tests + j, xa = sums_a[o], xb = sums_b[o];
@@ -259,13 +320,36 @@ void sseq_de_sums(hipStream_t s, uint64_t genes, uint32_t n_tests, const uint64_
                 p[o] = 1.0;
                 continue;
             }
+            if (!ratio) {
+                push_exact(o, j, g);
+                continue;
+            }
             const uint64_t n = xa + xb;
-            const double r = 1.0 / phi;
-            ex.push_back(SseqExactTest{n, xa, fa * r, fb * r, special::nb_add_total(n, fa, fb, mu, r), n_chunks, o});
-            n_chunks += (n + SSEQ_CHUNK) / SSEQ_CHUNK; // n + 1 terms
+            const double r = 1.0 / phi, sar = fa * r, sbr = fb * r;
+            const uint64_t anchor = sseq_ratio_anchor(n, sar, sbr);
+            rt.push_back(SseqRatioTest{n, xa, anchor, sar, sbr, n_rchunks, o});
+            n_rchunks += (anchor + SSEQ_CHUNK - 1) / SSEQ_CHUNK + (n - anchor + SSEQ_CHUNK - 1) / SSEQ_CHUNK; // n >= 1: at least one
         }
     }
-    if (ex.size() > 0xFFFFFFFFull || as.size() > 0xFFFFFFFFull) fail(SCANRS_ERR_ARGUMENT, "too many tests in one call");
+    if (ex.size() > 0xFFFFFFFFull || as.size() > 0xFFFFFFFFull || rt.size() > 0xFFFFFFFFull) fail(SCANRS_ERR_ARGUMENT, "too many tests in one call");
+    if (!rt.empty()) {
+        // Ratio: the tests it can partition get their p-value; the others come back as SSEQ_RATIO_FALLBACK and join the LogSpace list
+        DevBuf<double> d_p(total);
+        DevBuf<SseqRatioTest> d_rt(rt.size());
+        DevBuf<double> d_obs(rt.size()), d_scale(n_rchunks);
+        DevBuf<double2> d_part(n_rchunks);
+        h2d(d_rt.p, rt.data(), rt.size(), s);
+        launch_sseq_ratio(s, d_rt.p, (uint32_t)rt.size(), n_rchunks, d_obs.p, d_scale.p, d_part.p, d_p.p);
+        std::vector<double> pd(total);
+        SCANRS_D2H(pd.data(), d_p.p, total * 8, s);
+        SCANRS_SYNC(s);
+        for (const auto &t : rt) {
+            if (pd[t.out] == SSEQ_RATIO_FALLBACK)
+                push_exact(t.out, (uint32_t)(t.out % n_tests), t.out / n_tests);
+            else
+                p[t.out] = pd[t.out];
+        }
+    }
     if (!ex.empty() || !as.empty()) {
         DevBuf<double> d_p(total);
         DevBuf<SseqExactTest> d_ex(std::max<size_t>(1, ex.size()));
@@ -314,19 +398,32 @@ void sseq_de_sums(hipStream_t s, uint64_t genes, uint32_t n_tests, const uint64_
 }
 
 // ---- sseq_differential_expression (diff_exp.rs:122-175) over labels ---------------------------------------------------------------
-// mode 0: every group against all other labelled cells (Cell Ranger's per-cluster DE); mode 1: group 0 against group 1
+// mode 0: every group against all other labelled cells (Cell Ranger's per-cluster DE); mode 1: group 0 against group 1;
+// mode 2: every group 1 .. n_groups - 1 against group 0 (a shared control: its sums and size factor are computed once)
 void sseq_de_matrix(Storage &st, const SparseCopy &cp, bool gene_major, uint64_t genes, uint64_t cells, const int16_t *labels,
                     uint32_t n_groups, int mode, const double *size_factors, const double *gene_means, const double *gene_phi,
                     const uint8_t *use_genes, uint64_t big_count, const scanrs_snoop *snoop, uint64_t *sums_in, uint64_t *sums_out, double *p,
-                    double *p_adj, double *log2fc, double *mean_in, double *mean_out) {
-    if (mode != 0 && mode != 1) fail(SCANRS_ERR_ARGUMENT, "mode must be 0 (one against the rest) or 1 (group 0 against group 1)");
-    if (mode == 1 && n_groups < 2) fail(SCANRS_ERR_ARGUMENT, "mode 1 needs groups 0 and 1");
+                    double *p_adj, double *log2fc, double *mean_in, double *mean_out, int backend) {
+    if (mode != 0 && mode != 1 && mode != 2)
+        fail(SCANRS_ERR_ARGUMENT, "mode must be 0 (one against the rest), 1 (group 0 against group 1) or 2 (each group against group 0)");
+    if (mode != 0 && n_groups < 2) fail(SCANRS_ERR_ARGUMENT, "mode %d needs groups 0 and 1", mode);
+    if (backend != SCANRS_NB_EXACT_LOGSPACE && backend != SCANRS_NB_EXACT_RATIO)
+        fail(SCANRS_ERR_ARGUMENT, "backend must be SCANRS_NB_EXACT_LOGSPACE (0) or SCANRS_NB_EXACT_RATIO (1)");
     check_labels(labels, cells, n_groups);
-    const uint32_t n_tests = mode == 0 ? n_groups : 1;
+    const uint32_t n_tests = mode == 0 ? n_groups : mode == 1 ? 1 : n_groups - 1;
     sseq_progress(snoop, 0.0);
     // the size factors of each side: sums over its cells in cell order (the reference's fold over cond_a / cond_b)
     std::vector<double> fa(n_tests, 0.0), fb(n_tests, 0.0);
-    for (uint32_t j = 0; j < n_tests; j++) {
+    if (mode == 2) {
+        double control = 0.0;
+        for (uint64_t c = 0; c < cells; c++) {
+            const int l = labels[c];
+            if (l == 0) control += size_factors[c];
+            if (l > 0) fa[l - 1] += size_factors[c];
+        }
+        std::fill(fb.begin(), fb.end(), control);
+    }
+    for (uint32_t j = 0; mode != 2 && j < n_tests; j++) {
         for (uint64_t c = 0; c < cells; c++) {
             const int l = labels[c];
             if (l < 0) continue;
@@ -353,14 +450,19 @@ void sseq_de_matrix(Storage &st, const SparseCopy &cp, bool gene_major, uint64_t
                 sums_in[g * n_tests + j] = row[j];
                 sums_out[g * n_tests + j] = all - row[j];
             }
-        } else {
+        } else if (mode == 1) {
             sums_in[g] = row[0];
             sums_out[g] = row[1];
+        } else {
+            for (uint32_t j = 0; j < n_tests; j++) {
+                sums_in[g * n_tests + j] = row[j + 1];
+                sums_out[g * n_tests + j] = row[0];
+            }
         }
     }
     sseq_progress(snoop, 0.6);
     sseq_de_sums(st.stream, genes, n_tests, sums_in, sums_out, fa.data(), fb.data(), gene_means, gene_phi, use_genes, big_count, snoop, p, p_adj,
-                 log2fc, mean_in, mean_out);
+                 log2fc, mean_in, mean_out, backend);
 }
 
 // the copy DE walks: the gene-major one when it is resident, else the cell-major one (no transposition is built for DE)
@@ -421,9 +523,10 @@ int scanrs_mat_group_sums(scanrs_mat *m, const int16_t *labels, uint32_t n_group
         sseq_group_sums(*m->st, cp, gm, m->rows(), m->cols(), labels, n_groups, sums, cells_per_group);
     });
 }
-int scanrs_sseq_de(scanrs_mat *m, const int16_t *labels, uint32_t n_groups, int mode, const double *size_factors, const double *gene_means,
-                   const double *gene_phi, const uint8_t *use_genes, uint64_t big_count, const scanrs_snoop *snoop, uint64_t *sums_in,
-                   uint64_t *sums_out, double *p, double *p_adj, double *log2fc, double *mean_in, double *mean_out) {
+int scanrs_sseq_de_backend(scanrs_mat *m, const int16_t *labels, uint32_t n_groups, int mode, const double *size_factors,
+                           const double *gene_means, const double *gene_phi, const uint8_t *use_genes, uint64_t big_count, int backend,
+                           const scanrs_snoop *snoop, uint64_t *sums_in, uint64_t *sums_out, double *p, double *p_adj, double *log2fc,
+                           double *mean_in, double *mean_out) {
     return guard([&] {
         if (!m || !labels || !size_factors || !gene_means || !gene_phi || !use_genes || !sums_in || !sums_out || !p || !p_adj || !log2fc ||
             !mean_in || !mean_out)
@@ -432,26 +535,55 @@ int scanrs_sseq_de(scanrs_mat *m, const int16_t *labels, uint32_t n_groups, int 
         bool gm = false;
         SparseCopy &cp = sseq_resident_copy(m, &gm);
         sseq_de_matrix(*m->st, cp, gm, m->rows(), m->cols(), labels, n_groups, mode, size_factors, gene_means, gene_phi, use_genes, big_count,
-                       snoop, sums_in, sums_out, p, p_adj, log2fc, mean_in, mean_out);
+                       snoop, sums_in, sums_out, p, p_adj, log2fc, mean_in, mean_out, backend);
     });
+}
+int scanrs_sseq_de(scanrs_mat *m, const int16_t *labels, uint32_t n_groups, int mode, const double *size_factors, const double *gene_means,
+                   const double *gene_phi, const uint8_t *use_genes, uint64_t big_count, const scanrs_snoop *snoop, uint64_t *sums_in,
+                   uint64_t *sums_out, double *p, double *p_adj, double *log2fc, double *mean_in, double *mean_out) {
+    if (mode != 0 && mode != 1)
+        return guard([&] { fail(SCANRS_ERR_ARGUMENT, "mode must be 0 (one against the rest) or 1 (group 0 against group 1)"); });
+    return scanrs_sseq_de_backend(m, labels, n_groups, mode, size_factors, gene_means, gene_phi, use_genes, big_count, SCANRS_NB_EXACT_LOGSPACE,
+                                  snoop, sums_in, sums_out, p, p_adj, log2fc, mean_in, mean_out);
 }
 int scanrs_sseq_de_from_sums(uint64_t n_genes, uint32_t n_tests, const uint64_t *sums_a, const uint64_t *sums_b, const double *sf_a,
                              const double *sf_b, const double *gene_means, const double *gene_phi, const uint8_t *use_genes,
                              uint64_t big_count, const scanrs_snoop *snoop, double *p, double *p_adj, double *log2fc, double *mean_in,
                              double *mean_out) {
+    return scanrs_sseq_de_from_sums_backend(n_genes, n_tests, sums_a, sums_b, sf_a, sf_b, gene_means, gene_phi, use_genes, big_count,
+                                            SCANRS_NB_EXACT_LOGSPACE, snoop, p, p_adj, log2fc, mean_in, mean_out);
+}
+int scanrs_sseq_de_from_sums_backend(uint64_t n_genes, uint32_t n_tests, const uint64_t *sums_a, const uint64_t *sums_b, const double *sf_a,
+                                     const double *sf_b, const double *gene_means, const double *gene_phi, const uint8_t *use_genes,
+                                     uint64_t big_count, int backend, const scanrs_snoop *snoop, double *p, double *p_adj, double *log2fc,
+                                     double *mean_in, double *mean_out) {
     return guard([&] {
         if (n_genes && n_tests &&
             (!sums_a || !sums_b || !sf_a || !sf_b || !gene_means || !gene_phi || !use_genes || !p || !p_adj || !log2fc || !mean_in || !mean_out))
             fail(SCANRS_ERR_ARGUMENT, "null argument");
+        if (backend != SCANRS_NB_EXACT_LOGSPACE && backend != SCANRS_NB_EXACT_RATIO)
+            fail(SCANRS_ERR_ARGUMENT, "backend must be SCANRS_NB_EXACT_LOGSPACE (0) or SCANRS_NB_EXACT_RATIO (1)");
         need_device();
         sseq_de_sums(nullptr, n_genes, n_tests, sums_a, sums_b, sf_a, sf_b, gene_means, gene_phi, use_genes, big_count, snoop, p, p_adj, log2fc,
-                     mean_in, mean_out);
+                     mean_in, mean_out, backend);
     });
 }
 int scanrs_host_nb_exact_test(uint64_t x_a, uint64_t x_b, double sf_a, double sf_b, double mu, double phi, double *p) {
     return guard([&] {
         if (!p) fail(SCANRS_ERR_ARGUMENT, "null argument");
         *p = sseq_host_exact_test(x_a, x_b, sf_a, sf_b, mu, phi);
+    });
+}
+int scanrs_host_nb_exact_test_ratio(uint64_t x_a, uint64_t x_b, double sf_a, double sf_b, double mu, double phi, double *p) {
+    return guard([&] {
+        if (!p) fail(SCANRS_ERR_ARGUMENT, "null argument");
+        *p = sseq_host_exact_test_ratio(x_a, x_b, sf_a, sf_b, mu, phi);
+    });
+}
+int scanrs_host_nb_exact_ratio_step(double k, double n, double sa_r, double sb_r, double *out) {
+    return guard([&] {
+        if (!out) fail(SCANRS_ERR_ARGUMENT, "null argument");
+        *out = ratio_step(k, n, sa_r, sb_r);
     });
 }
 int scanrs_host_nb_asymptotic_test(uint64_t x_a, uint64_t x_b, double sf_a, double sf_b, double mu, double phi, double *p) {

@@ -1,4 +1,4 @@
-"""sSeq differential expression (diff-exp/src/diff_exp.rs, dist.rs; NbExactBackend::LogSpace) over the count-matrix handle.
+"""sSeq differential expression (diff-exp/src/diff_exp.rs, dist.rs; both NbExactBackends) over the count-matrix handle.
 
 Rows of the handle are genes, columns are cells (the reference's feature x barcode matrix); a cell-major handle is used
 through ``.t()``. DE reads the stored u32 counts and ignores the handle's map and offset. The passes over the nonzeros and
@@ -16,6 +16,8 @@ from . import AdaptiveMat, ScanrsError, _check, _lib, _p
 
 BIG_COUNT_DEFAULT = 900  # diff_exp.rs:15
 ZETA_QUINTILE_DEFAULT = 0.995  # diff_exp.rs:17
+NB_EXACT_LOGSPACE = 0  # NbExactBackend::LogSpace (dist.rs:52-68), the default
+NB_EXACT_RATIO = 1  # NbExactBackend::Ratio: nb_exact_test_ratio (dist.rs:116-215)
 
 _u64, _f64c, _u32 = ctypes.c_uint64, ctypes.c_double, ctypes.c_uint32
 
@@ -125,20 +127,26 @@ def _results(params, sums_in, sums_out, p, padj, l2, mi, mo) -> List[DiffExpResu
                           l2[:, j].copy()) for j in range(p.shape[1])]
 
 
-def _de_matrix(mat, labels, n_groups, mode, params, big_count, snoop):
+def _backend(backend) -> int:
+    if isinstance(backend, (bool, np.bool_)) or not isinstance(backend, (int, np.integer)) or int(backend) not in (NB_EXACT_LOGSPACE, NB_EXACT_RATIO):
+        raise ScanrsError(6, "backend must be NB_EXACT_LOGSPACE (0) or NB_EXACT_RATIO (1)")
+    return int(backend)
+
+
+def _de_matrix(mat, labels, n_groups, mode, params, big_count, snoop, backend=NB_EXACT_LOGSPACE):
     genes, cells = mat.shape()
     lab = _labels(labels, cells)
     mean, phi, use = _params_arrays(params, genes)
     sf = np.ascontiguousarray(params.size_factors, dtype=np.float64)
     if len(sf) != cells:
         raise ScanrsError(6, "params.size_factors needs one value per cell of the matrix")
-    t = n_groups if mode == 0 else 1
+    t = n_groups if mode == 0 else 1 if mode == 1 else max(n_groups - 1, 0)
     si, so = np.zeros((genes, t), dtype=np.uint64), np.zeros((genes, t), dtype=np.uint64)
     p, padj, l2, mi, mo = (np.zeros((genes, t)) for _ in range(5))
     sn, _keep = _snoop_arg(snoop)
     bc = BIG_COUNT_DEFAULT if big_count is None else int(big_count)
-    _check(_lib.scanrs_sseq_de(mat._h, _p(lab), _u32(n_groups), ctypes.c_int(mode), _p(sf), _p(mean), _p(phi), _p(use), _u64(bc), sn, _p(si), _p(so),
-                               _p(p), _p(padj), _p(l2), _p(mi), _p(mo)))
+    _check(_lib.scanrs_sseq_de_backend(mat._h, _p(lab), _u32(n_groups), ctypes.c_int(mode), _p(sf), _p(mean), _p(phi), _p(use), _u64(bc),
+                                       ctypes.c_int(_backend(backend)), sn, _p(si), _p(so), _p(p), _p(padj), _p(l2), _p(mi), _p(mo)))
     return _results(params, si, so, p, padj, l2, mi, mo)
 
 
@@ -154,32 +162,51 @@ def _index_list(v, cells: int, name: str) -> np.ndarray:
 
 
 def sseq_differential_expression(mat: AdaptiveMat, cond_a: Sequence[int], cond_b: Sequence[int], params: SSeqParams, big_count: Optional[int] = None,
-                                 snoop=None) -> DiffExpResult:
+                                 snoop=None, backend: int = NB_EXACT_LOGSPACE) -> DiffExpResult:
     """`sseq_differential_expression` (diff_exp.rs:68-175): cells of cond_a against cells of cond_b. The lists must be sorted,
-    free of duplicates and disjoint (the reference assumes sorted lists without checking)."""
+    free of duplicates and disjoint (the reference assumes sorted lists without checking). backend: the exact test's kernel
+    (`sseq_differential_expression_backend`, diff_exp.rs:125-161)."""
     genes, cells = mat.shape()
     a, b = _index_list(cond_a, cells, "cond_a"), _index_list(cond_b, cells, "cond_b")
     if np.intersect1d(a, b).size:
         raise ScanrsError(6, "cond_a and cond_b overlap")
     lab = np.full(cells, -1, dtype=np.int16)
     lab[a], lab[b] = 0, 1
-    return _de_matrix(mat, lab, 2, 1, params, big_count, snoop)[0]
+    return _de_matrix(mat, lab, 2, 1, params, big_count, snoop, backend)[0]
 
 
 def sseq_de_one_vs_rest(mat: AdaptiveMat, labels, params: SSeqParams, big_count: Optional[int] = None, n_groups: Optional[int] = None,
-                        snoop=None) -> List[DiffExpResult]:
+                        snoop=None, backend: int = NB_EXACT_LOGSPACE) -> List[DiffExpResult]:
     """Every group against all other labelled cells (Cell Ranger's per-cluster DE over `initial_cluster_assignments`,
     diff-exp/src/utils.rs:77-117). labels: per cell, the group 0 .. n_groups - 1 or -1 (in no group)."""
     lab = np.asarray(labels)
     if n_groups is None:
         n_groups = int(lab.max()) + 1 if lab.size else 0
-    return _de_matrix(mat, lab, n_groups, 0, params, big_count, snoop)
+    return _de_matrix(mat, lab, n_groups, 0, params, big_count, snoop, backend)
+
+
+def sseq_de_vs_control(mat: AdaptiveMat, labels, params: SSeqParams, control: int = 0, big_count: Optional[int] = None,
+                       n_groups: Optional[int] = None, snoop=None, backend: int = NB_EXACT_LOGSPACE) -> List[DiffExpResult]:
+    """Every other group against the group `control` (the shared-control shape of Cell Ranger's batched DE): one pass over the
+    nonzeros, the control's sums and size factor computed once. Returns one DiffExpResult per group other than the control, in
+    group order; each equals `sseq_differential_expression(mat, cells of the group, cells of the control, ...)` bit for bit.
+    labels: per cell, the group 0 .. n_groups - 1 or -1 (in no group)."""
+    lab = np.asarray(labels)
+    if n_groups is None:
+        n_groups = int(lab.max()) + 1 if lab.size else 0
+    if not 0 <= int(control) < n_groups:
+        raise ScanrsError(6, f"control must be a group 0 .. {n_groups - 1}")
+    if control != 0:
+        # the library tests against group 0: the control becomes group 0 and the groups below it move up by one
+        lab = np.where(lab == control, 0, np.where((lab >= 0) & (lab < control), lab + 1, lab))
+    return _de_matrix(mat, lab, n_groups, 2, params, big_count, snoop, backend)
 
 
 def sseq_de_from_sums(feature_sums_a, feature_sums_b, size_factor_a, size_factor_b, params: SSeqParams, big_count: Optional[int] = None,
-                      snoop=None):
+                      snoop=None, backend: int = NB_EXACT_LOGSPACE):
     """`sseq_de_from_sums` (diff_exp.rs:177-300) on the device. 1-d sums with scalar size factors give one DiffExpResult;
-    2-d (genes x tests) sums with one size factor per test give a list."""
+    2-d (genes x tests) sums with one size factor per test give a list. backend: the exact test's kernel; Cell Ranger's
+    batched path passes NB_EXACT_RATIO (diff_exp.rs:172-175)."""
     sa, sb = np.asarray(feature_sums_a, dtype=np.uint64), np.asarray(feature_sums_b, dtype=np.uint64)
     single = sa.ndim == 1
     sa, sb = np.ascontiguousarray(sa.reshape(len(sa), -1)), np.ascontiguousarray(sb.reshape(len(sb), -1))
@@ -194,8 +221,8 @@ def sseq_de_from_sums(feature_sums_a, feature_sums_b, size_factor_a, size_factor
     p, padj, l2, mi, mo = (np.zeros((genes, t)) for _ in range(5))
     sn, _keep = _snoop_arg(snoop)
     bc = BIG_COUNT_DEFAULT if big_count is None else int(big_count)
-    _check(_lib.scanrs_sseq_de_from_sums(_u64(genes), _u32(t), _p(sa), _p(sb), _p(fa), _p(fb), _p(mean), _p(phi), _p(use), _u64(bc), sn, _p(p),
-                                         _p(padj), _p(l2), _p(mi), _p(mo)))
+    _check(_lib.scanrs_sseq_de_from_sums_backend(_u64(genes), _u32(t), _p(sa), _p(sb), _p(fa), _p(fb), _p(mean), _p(phi), _p(use), _u64(bc),
+                                                 ctypes.c_int(_backend(backend)), sn, _p(p), _p(padj), _p(l2), _p(mi), _p(mo)))
     res = _results(params, sa, sb, p, padj, l2, mi, mo)
     return res[0] if single else res
 
@@ -218,6 +245,21 @@ def labels_from_clustering(clusters) -> np.ndarray:
 def host_nb_exact_test(x_a, x_b, size_factor_a, size_factor_b, mu, phi) -> float:
     out = _f64c()
     _check(_lib.scanrs_host_nb_exact_test(_u64(x_a), _u64(x_b), _f64c(size_factor_a), _f64c(size_factor_b), _f64c(mu), _f64c(phi), ctypes.byref(out)))
+    return out.value
+
+
+def host_nb_exact_test_ratio(x_a, x_b, size_factor_a, size_factor_b, mu, phi) -> float:
+    """`nb_exact_test_ratio` (dist.rs:155-215) on the host, line for line."""
+    out = _f64c()
+    _check(_lib.scanrs_host_nb_exact_test_ratio(_u64(x_a), _u64(x_b), _f64c(size_factor_a), _f64c(size_factor_b), _f64c(mu), _f64c(phi),
+                                                ctypes.byref(out)))
+    return out.value
+
+
+def host_nb_exact_ratio_step(k, n, sa_r, sb_r) -> float:
+    """`nb_exact_ratio_step` (dist.rs:124-126)."""
+    out = _f64c()
+    _check(_lib.scanrs_host_nb_exact_ratio_step(_f64c(k), _f64c(n), _f64c(sa_r), _f64c(sb_r), ctypes.byref(out)))
     return out.value
 
 

@@ -2,7 +2,11 @@
 cell-major): ms for the parameters, the group pass and the tests, the exact-branch term count and the split between the
 branches, and the group pass's one-pass bytes (8 nnz + 2 cells) against HBM. One JSON line.
 
-    python tools/de_bench.py [--cells 1000000] [--genes 33000] [--groups 20] [--reps 3]
+    python tools/de_bench.py [--cells 1000000] [--genes 33000] [--groups 20] [--reps 3] [--backend {logspace,ratio}]
+
+With --control-conditions N the labels are a shared control instead: group 0 holds half the cells, the other half is spread
+over N conditions, and every condition is tested against the control (mode 2, sseq_de_vs_control). The line then carries the
+exact tests, their terms, the tests Ratio hands to LogSpace, and the ms of the tests and of the whole call for the backend.
 """
 import argparse
 import json
@@ -26,7 +30,10 @@ def main():
     ap.add_argument("--density", type=float, default=0.03)
     ap.add_argument("--groups", type=int, default=20)
     ap.add_argument("--reps", type=int, default=3)
+    ap.add_argument("--backend", choices=("logspace", "ratio"), default="logspace")
+    ap.add_argument("--control-conditions", type=int, default=0)
     a = ap.parse_args()
+    backend = sa.NB_EXACT_RATIO if a.backend == "ratio" else sa.NB_EXACT_LOGSPACE
     import torch
 
     dev = torch.device("cuda", 0)
@@ -35,6 +42,10 @@ def main():
     nnz = int(ix.numel())
     m = sa.AdaptiveMat.from_device(a.genes, a.cells, sa.CSC, ip.data_ptr(), ix.data_ptr(), vv.data_ptr())
     labels = np.random.default_rng(0).integers(0, a.groups, a.cells).astype(np.int16)
+    if a.control_conditions:
+        labels = np.zeros(a.cells, dtype=np.int16)
+        other = np.random.default_rng(0).permutation(a.cells)[: a.cells // 2]
+        labels[other] = 1 + np.random.default_rng(1).integers(0, a.control_conditions, len(other))
 
     def timed(f):
         best, out = float("inf"), None
@@ -45,12 +56,14 @@ def main():
         return best, out
 
     t_params, params = timed(lambda: sa.compute_sseq_params(m))
+    if a.control_conditions:
+        return control_leg(a, m, labels, params, t_params, backend, timed, nnz)
     t_pass, (sums, cnt) = timed(lambda: sa.group_sums(m, labels, a.groups))
     allsum = sums.sum(axis=1)
     sf_a = np.array([params.size_factors[labels == j].sum() for j in range(a.groups)])
     sf_b = params.size_factors.sum() - sf_a
     rest = allsum[:, None] - sums
-    t_tests, _ = timed(lambda: sa.sseq_de_from_sums(sums, rest, sf_a, sf_b, params))
+    t_tests, _ = timed(lambda: sa.sseq_de_from_sums(sums, rest, sf_a, sf_b, params, backend=backend))
     big = 900
     use = params.use_genes[:, None]
     asym = use & (sums > big) & (rest > big)
@@ -58,12 +71,59 @@ def main():
     exact = ~asym & ~trivial
     terms = int(((sums + rest + 1) * exact).sum())
     one_pass = 8.0 * nnz + 2.0 * a.cells
+    extra = {} if backend == sa.NB_EXACT_LOGSPACE else {"backend": a.backend, "ratio_fallback_tests": ratio_fallbacks(sums, rest, sf_a, sf_b, params, exact)}
     print(json.dumps({
-        "cells": a.cells, "genes": a.genes, "nnz": nnz, "groups": a.groups,
+        "cells": a.cells, "genes": a.genes, "nnz": nnz, "groups": a.groups, **extra,
         "params_ms": round(t_params, 2), "group_pass_ms": round(t_pass, 2), "tests_ms": round(t_tests, 2),
         "tests": int(a.genes * a.groups), "exact_tests": int(exact.sum()), "asymptotic_tests": int(asym.sum()), "early_return_tests": int((trivial & ~asym).sum()),
         "exact_terms": terms,
         "group_pass_bytes": one_pass, "group_pass_hbm_floor_ms": round(one_pass / HBM_BYTES_PER_S * 1e3, 3),
+    }))
+
+
+def ratio_fallbacks(xa, xb, sf_a, sf_b, params, exact):
+    """The exact tests whose observed term lies below 2^-970 of the anchor's, which the Ratio backend hands to LogSpace: counted
+    here from the closed form of the terms in log space (a test within rounding of the threshold may be counted either way)."""
+    from scipy.special import gammaln
+
+    n_fall = 0
+    for j in range(xa.shape[1]):  # test by test: a few arrays of one value per gene at a time
+        e = np.flatnonzero(exact[:, j])
+        if not e.size:
+            continue
+        k, n = xa[e, j].astype(np.float64), (xa[e, j] + xb[e, j]).astype(np.float64)
+        sar, sbr = sf_a[j] / params.gene_phi[e], sf_b[j] / params.gene_phi[e]
+        # the anchor: the first k with step(k) < 1, n (sar - 1) - (sbr - 1) < k (sar + sbr - 2), else n
+        aa, bb = n * (sar - 1.0) - (sbr - 1.0), sar + sbr - 2.0
+        with np.errstate(all="ignore"):
+            anchor = np.where(bb > 0, np.clip(np.floor(aa / bb) + 1.0, 0.0, n), np.where(aa < 0, 0.0, n))
+
+        def ln_term(kk):
+            return gammaln(sar + kk) + gammaln(sbr + n - kk) - gammaln(kk + 1.0) - gammaln(n - kk + 1.0)
+
+        n_fall += int(np.count_nonzero(ln_term(k) - ln_term(anchor) < -970.0 * np.log(2.0)))
+    return n_fall
+
+
+def control_leg(a, m, labels, params, t_params, backend, timed, nnz):
+    groups = a.control_conditions + 1
+    t_pass, (sums, cnt) = timed(lambda: sa.group_sums(m, labels, groups))
+    sf = np.bincount(labels, weights=params.size_factors, minlength=groups)
+    xa, xb = np.ascontiguousarray(sums[:, 1:]), np.repeat(sums[:, :1], groups - 1, axis=1)
+    sf_a, sf_b = sf[1:], np.full(groups - 1, sf[0])
+    t_tests, _ = timed(lambda: sa.sseq_de_from_sums(xa, xb, sf_a, sf_b, params, backend=backend))
+    t_call, _ = timed(lambda: sa.sseq_de_vs_control(m, labels, params, n_groups=groups, backend=backend))
+    use = params.use_genes[:, None]
+    asym = use & (xa > 900) & (xb > 900)
+    trivial = ((xa + xb) == 0) | (params.gene_phi[:, None] == 0) | (sf_a[None, :] == 0) | (sf_b[None, :] == 0)
+    exact = ~asym & ~trivial
+    print(json.dumps({
+        "cells": a.cells, "genes": a.genes, "nnz": nnz, "control_conditions": a.control_conditions, "control_cells": int(cnt[0]),
+        "backend": a.backend, "params_ms": round(t_params, 2), "group_pass_ms": round(t_pass, 2),
+        "tests_ms": round(t_tests, 2), "vs_control_call_ms": round(t_call, 2),
+        "tests": int(a.genes * (groups - 1)), "exact_tests": int(exact.sum()), "asymptotic_tests": int(asym.sum()),
+        "early_return_tests": int((trivial & ~asym).sum()), "exact_terms": int(((xa + xb + 1) * exact).sum()),
+        "ratio_fallback_tests": ratio_fallbacks(xa, xb, sf_a, sf_b, params, exact) if backend == sa.NB_EXACT_RATIO else 0,
     }))
 
 
