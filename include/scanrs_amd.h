@@ -481,7 +481,8 @@ int scanrs_mat_set_option(scanrs_mat *m, const char *key, double value);
  * (hipMalloc). The tile layouts of the handle (both orientations, summed): "tile_positions" = record positions the tile kernel works
  * per pair of passes, "tile_served_nonzeros" = nonzeros among them (the rest is padding), "tile_overflow_nonzeros" = nonzeros left
  * to the overflow gather. "partition_rounds" = rounds of the last scanrs_mat_partition_on_thresholds on this handle, the final round
- * that changes nothing included. */
+ * that changes nothing included. "de_pairs_passes" / "de_pairs_literal" = the last scanrs_sseq_de_pairs on this handle: its passes over
+ * the nonzeros and its pairs on the literal route. */
 int scanrs_mat_get_counter(scanrs_mat *m, const char *key, uint64_t *value);
 /* Process-wide options of the entry points that take no handle:
  *   "h5_threads" (8)               threads that inflate the chunks of a large filtered HDF5 read
@@ -653,6 +654,37 @@ int scanrs_sseq_de_from_sums_backend(uint64_t n_genes, uint32_t n_tests, const u
                                      const double *sf_b, const double *gene_means, const double *gene_phi, const uint8_t *use_genes,
                                      uint64_t big_count, int backend, const scanrs_snoop *snoop, double *p, double *p_adj, double *log2fc,
                                      double *mean_in, double *mean_out);
+/* Batched pairwise DE with per-pair parameters: the shape of merge_clusters.rs' candidates and of the shared-control batched path that
+ * the doc comment of `sseq_params_from_moments` describes (diff_exp.rs:361-376: n_cells is "the cell count m = na + nb",
+ * sum_size_factors "Σ(1/size_factor) over the test cells"). With A = the cells labelled pair_a[j] and B = those labelled pair_b[j],
+ * test j is `compute_sseq_params(mat, zeta_quintile, Some(sorted A ∪ B), None)` (diff_exp.rs:458-490) followed by
+ * `sseq_differential_expression_with_cancellation_backend(mat, A, B, params, big_count, backend)` (diff_exp.rs:125-161). All pairs
+ * share two passes over the nonzeros (per-cell totals, then one grouped pass; from a gene-major copy one grouped pass per 1536
+ * groups), and every pair's parameters are combined on the device from its two groups' integer sums: with u_c the total of cell c
+ * and m_S the interpolated median total of the union, sf_c = u_c / m_S, Σ x/sf_c = m_S Σ x/u_c and Σ (x/sf_c)² = m_S² Σ (x/u_c)².
+ * A pair's result depends on its own two groups only: not on the other pairs, the storage flag, or the copy that was walked.
+ * Against the two reference calls the moments differ by the rounding of the sums (means to 1e-12, p-values to 1e-9 relative).
+ * Labels as in scanrs_sseq_de (-1 .. n_groups - 1, n_groups <= 8192); outputs genes x n_pairs row-major. SCANRS_ERR_ARGUMENT: a
+ * group index >= n_groups, pair_a[j] == pair_b[j], a pair whose union has no cell, n_pairs = 0, a bad backend, a sharded handle. A
+ * pair with exactly one empty side is valid: that side's size factor is 0 and every p is 1, as in the reference. A pair whose
+ * union has a median total of 0 (no finite size factor) runs the two reference calls themselves in the same call (`literal`).
+ * Checkpoints of `snoop`: 0.0, 0.1 (totals and pair headers), 0.6 (grouped pass and parameters), 0.75, 0.9, 0.95, 1.0.
+ * Counters (scanrs_mat_get_counter): "de_pairs_passes" = passes over the nonzeros in the last call (2, or 1 + the tiles of groups of a
+ * gene-major copy, plus 4 per literal pair); "de_pairs_literal" = pairs that took the literal route.
+ * `params` (may be NULL) receives what each pair was tested with. */
+typedef struct {            /* every pointer may be NULL; arrays genes x n_pairs row-major, or n_pairs */
+    double *gene_means, *gene_variances, *gene_moment_phi, *gene_phi;
+    uint8_t *use_genes;
+    double *zeta_hat, *delta, *sf_a, *sf_b, *median_total, *sum_size_factors;
+    uint64_t *n_cells_a, *n_cells_b;
+    uint8_t *literal;       /* 1: the pair took the literal route (median total 0) */
+} scanrs_sseq_pair_params;
+int scanrs_sseq_de_pairs(scanrs_mat *m, const int16_t *labels, uint32_t n_groups, const uint32_t *pair_a, const uint32_t *pair_b,
+                         uint32_t n_pairs, double zeta_quintile, uint64_t big_count, int backend, const scanrs_snoop *snoop,
+                         uint64_t *sums_in, uint64_t *sums_out, double *p, double *p_adj, double *log2fc, double *mean_in,
+                         double *mean_out, scanrs_sseq_pair_params *params /* may be NULL */);
+/* percentile_of_sorted(.., 50) (stat.rs:140-162) of the union of two ascending lists; host only */
+int scanrs_host_union_median(const double *a, uint64_t n_a, const double *b, uint64_t n_b, double *out);
 /* the shared math on the host (no device needed; the kernels run the same special functions): `nb_exact_test`
  * (dist.rs:74-118), `nb_asymptotic_test` (:226-257), `log_prob_all` (:259-310, n + 1 values), `adjusted_pvalue_bh` (:22-50,
  * out[i] belongs to p[i]), and the regularised incomplete beta function and its inverse in p */

@@ -595,6 +595,63 @@ inline DiffExpResult sseq_de_from_sums(const std::vector<uint64_t> &sums_a, cons
                                            r.normalized_mean_out.data()));
     return r;
 }
+// scanrs_sseq_de_pairs: test j is compute_sseq_params over the union of groups pairs[j].first and .second (diff_exp.rs:458-490), then
+// the first group against the second (diff_exp.rs:125-161): merge_clusters.rs' candidates, batched (see diff_exp.rs:361-376)
+struct PairParams : SSeqParams { // size_factors stays empty, as in sseq_params_from_moments
+    double size_factor_a = 0.0, size_factor_b = 0.0, median_total = 0.0, sum_size_factors = 0.0;
+    uint64_t num_cells_a = 0, num_cells_b = 0;
+    bool literal = false; // the union's median total was 0: the pair ran the two reference calls themselves
+};
+inline std::pair<std::vector<DiffExpResult>, std::vector<PairParams>> sseq_de_pairs(
+    const AdaptiveMat &m, const std::vector<int16_t> &labels, uint32_t n_groups, const std::vector<std::pair<uint32_t, uint32_t>> &pairs,
+    double zeta_quintile = ZETA_QUINTILE_DEFAULT, uint64_t big_count = BIG_COUNT_DEFAULT, NbExactBackend backend = NbExactBackend::LogSpace,
+    Snoop *snoop = nullptr) {
+    const uint64_t g = m.rows();
+    const uint32_t t = (uint32_t)pairs.size();
+    std::vector<uint32_t> pa(t), pb(t);
+    for (uint32_t j = 0; j < t; j++) pa[j] = pairs[j].first, pb[j] = pairs[j].second;
+    std::vector<uint64_t> si(g * t), so(g * t), na(t), nb(t);
+    std::vector<double> pv(g * t), pq(g * t), l2(g * t), mi(g * t), mo(g * t), mean(g * t), var(g * t), mm(g * t), phi(g * t);
+    std::vector<double> zh(t), dl(t), fa(t), fb(t), med(t), ssf(t);
+    std::vector<uint8_t> use(g * t), lit(t);
+    scanrs_sseq_pair_params pp = {mean.data(), var.data(), mm.data(), phi.data(), use.data(), zh.data(), dl.data(), fa.data(),
+                                  fb.data(), med.data(), ssf.data(), na.data(), nb.data(), lit.data()};
+    scanrs_snoop sn = detail::make_snoop(snoop);
+    check(scanrs_sseq_de_pairs(m.raw(), labels.data(), n_groups, pa.data(), pb.data(), t, zeta_quintile, big_count, (int)backend,
+                               snoop ? &sn : nullptr, si.data(), so.data(), pv.data(), pq.data(), l2.data(), mi.data(), mo.data(), &pp));
+    std::vector<DiffExpResult> out(t);
+    std::vector<PairParams> prm(t);
+    for (uint32_t j = 0; j < t; j++) {
+        DiffExpResult &r = out[j];
+        PairParams &q = prm[j];
+        q.num_genes = (uint32_t)g;
+        q.num_cells = (uint32_t)(na[j] + nb[j]);
+        q.zeta_hat = zh[j], q.delta = dl[j], q.size_factor_a = fa[j], q.size_factor_b = fb[j], q.median_total = med[j];
+        q.sum_size_factors = ssf[j], q.num_cells_a = na[j], q.num_cells_b = nb[j], q.literal = lit[j] != 0;
+        for (uint64_t i = 0; i < g; i++) {
+            const uint64_t o = i * t + j;
+            r.sums_in.push_back(si[o]);
+            r.sums_out.push_back(so[o]);
+            r.p_values.push_back(pv[o]);
+            r.adjusted_p_values.push_back(pq[o]);
+            r.log2_fold_change.push_back(l2[o]);
+            r.normalized_mean_in.push_back(mi[o]);
+            r.normalized_mean_out.push_back(mo[o]);
+            q.gene_means.push_back(mean[o]);
+            q.gene_variances.push_back(var[o]);
+            q.use_genes.push_back(use[o]);
+            q.gene_moment_phi.push_back(mm[o]);
+            q.gene_phi.push_back(phi[o]);
+        }
+    }
+    return {std::move(out), std::move(prm)};
+}
+// percentile_of_sorted(.., 50) (stat.rs:140-162) of the union of two ascending lists, on the host
+inline double host_union_median(const std::vector<double> &a, const std::vector<double> &b) {
+    double out = 0.0;
+    check(scanrs_host_union_median(a.data(), a.size(), b.data(), b.size(), &out));
+    return out;
+}
 // nb_exact_test_ratio (dist.rs:155-215) and nb_exact_ratio_step (dist.rs:124-126) on the host
 inline double host_nb_exact_test_ratio(uint64_t x_a, uint64_t x_b, double sf_a, double sf_b, double mu, double phi) {
     double p = 0.0;

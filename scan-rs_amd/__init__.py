@@ -1112,7 +1112,7 @@ EXPORTED_SYMBOLS = [
     "scanrs_sseq_params", "scanrs_sseq_params_from_moments", "scanrs_mat_group_sums", "scanrs_sseq_de", "scanrs_sseq_de_from_sums",
     "scanrs_sseq_de_backend", "scanrs_sseq_de_from_sums_backend", "scanrs_host_nb_exact_test_ratio", "scanrs_host_nb_exact_ratio_step",
     "scanrs_host_nb_exact_test", "scanrs_host_nb_asymptotic_test", "scanrs_host_nb_log_prob_all", "scanrs_host_adjusted_pvalue_bh",
-    "scanrs_host_betainc", "scanrs_host_betaincinv",
+    "scanrs_host_betainc", "scanrs_host_betaincinv", "scanrs_sseq_de_pairs", "scanrs_host_union_median",
     "scanrs_host_pdist", "scanrs_host_linkage_complete", "scanrs_host_relabel_by_size", "scanrs_cluster_medoids", "scanrs_cluster_medoids_device",
     "scanrs_merge_clusters",
     "scanrs_mat_select_rows", "scanrs_mat_select_cols", "scanrs_mat_partition_on_thresholds", "scanrs_mat_to_csmat",
@@ -1123,8 +1123,8 @@ EXPORTED_SYMBOLS = [
 # sSeq differential expression (sseq.py)
 from .sseq import (  # noqa: E402
     NB_EXACT_LOGSPACE, NB_EXACT_RATIO, DiffExpResult, SSeqParams, compute_sseq_params, diff_exp_table, group_sums, host_nb_exact_ratio_step,
-    host_nb_exact_test_ratio, labels_from_clustering, sseq_de_from_sums, sseq_de_one_vs_rest, sseq_de_vs_control, sseq_differential_expression,
-    sseq_params_from_moments,
+    host_nb_exact_test_ratio, host_union_median, labels_from_clustering, sseq_de_each_vs_control, sseq_de_from_sums, sseq_de_one_vs_rest, sseq_de_pairs,
+    sseq_de_vs_control, sseq_differential_expression, sseq_params_from_moments,
 )
 
 # merge_clusters, linkage and medoids (cluster.py)

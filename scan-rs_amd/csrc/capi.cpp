@@ -1350,6 +1350,10 @@ int scanrs_mat_get_counter(scanrs_mat *m, const char *key, uint64_t *value) {
             *value = m->st->bk_host_retries;
         else if (k == "partition_rounds") // rounds of the last scanrs_mat_partition_on_thresholds on this handle
             *value = m->st->partition_rounds;
+        else if (k == "de_pairs_passes") // the last scanrs_sseq_de_pairs on this handle: passes over the nonzeros ...
+            *value = m->st->de_pairs_passes;
+        else if (k == "de_pairs_literal") // ... and pairs that took the literal route
+            *value = m->st->de_pairs_literal;
         else if (k == "t_layout_us") // first-call accounting: host time of the calling thread in tile layout builds ...
             *value = m->st->t_layout_us;
         else if (k == "t_side_wait_us") // ... waiting for the helper thread that builds the second orientation

@@ -405,6 +405,7 @@ struct Storage {
     int tile_overlap = 1;                 // hybrid product: 1 = the overflow gather runs beside the tile kernel (own stream); 0 = after it (measurement)
     int panel_precision = 0;              // 0: f64 panels (default); 1: gathered panels rounded to f32, f64 sums (opt-in)
     uint64_t partition_rounds = 0;        // rounds of the last scanrs_mat_partition_on_thresholds on this handle, the final one that changes nothing included (scanrs_mat_get_counter)
+    uint64_t de_pairs_passes = 0, de_pairs_literal = 0; // the last scanrs_sseq_de_pairs on this handle: passes over the nonzeros, pairs on the literal route (scanrs_mat_get_counter)
     int merge_fused = 1;                  // merge_clusters: 1 = one grouped pass per call, candidates from its sums; 0 = params + pairwise DE per candidate (the reference's calls)
     size_t l2_tile_bytes = 3584u << 10;   // panel slice per step of the L2-blocked gather (4 MB L2 per XCD): whole 1024-row base tiles up to 3.5 MB — 4 tiles (3.2 MB) at 100 columns, 3 (2.9 MB) at 122; measured 40.55 / 39.71 ms per pass against 41.30 / 40.23 with 3 tiles and 40.86 / 39.61 with 5, and 4 tiles of 122 columns (3.9 MB) lose 1.8 ms
     int spmm_order = 1;                   // L2-blocked gather: launch outer vectors longest first: 0 never, 1 auto, 2 always (SCANRS_SPMM_ORDER)
@@ -704,12 +705,40 @@ void sseq_de_sums(hipStream_t s, uint64_t genes, uint32_t n_tests, const uint64_
                   const double *sf_b, const double *gene_means, const double *gene_phi, const uint8_t *use_genes, uint64_t big_count,
                   const scanrs_snoop *snoop, double *p, double *p_adj, double *log2fc, double *mean_in, double *mean_out,
                   int backend = SCANRS_NB_EXACT_LOGSPACE);
+// the same with the parameters read per (gene, test): gene_means / gene_phi / use_genes at [g * stride_g + j * stride_j]. (1, 0) is
+// sseq_de_sums (one set of parameters for every test), (n_tests, 1) a genes x n_tests array (scanrs_sseq_de_pairs)
+void sseq_de_sums_strided(hipStream_t s, uint64_t genes, uint32_t n_tests, const uint64_t *sums_a, const uint64_t *sums_b, const double *sf_a,
+                          const double *sf_b, const double *gene_means, const double *gene_phi, const uint8_t *use_genes, uint64_t stride_g,
+                          uint64_t stride_j, uint64_t big_count, const scanrs_snoop *snoop, double *p, double *p_adj, double *log2fc,
+                          double *mean_in, double *mean_out, int backend);
 // the copy DE walks: the gene-major one when it is resident, else the cell-major one (shared with merge_clusters)
 SCANRS_LOCAL SparseCopy &sseq_resident_copy(scanrs_mat *m, bool *gene_major);
 double sseq_host_exact_test(uint64_t xa, uint64_t xb, double sf_a, double sf_b, double mu, double phi);
 double sseq_host_exact_test_ratio(uint64_t xa, uint64_t xb, double sf_a, double sf_b, double mu, double phi);
 uint64_t sseq_ratio_anchor(uint64_t n, double sar, double sbr);
 void sseq_host_bh(const double *p, uint64_t n, double *out);
+
+// ---- sseq_pairs.hip / sseq_pairs_host.cpp: batched pairwise DE with per-pair parameters (diff_exp.rs:361-376, merge_clusters.rs) ----
+struct SseqPairHeader {  // one pair (a, b) of groups: what its tests need besides the per-gene accumulators
+    double m_s;          // interpolated median total of the union (percentile_of_sorted(.., 50), stat.rs:140-162)
+    double n_s, sum_sf;  // cells of the union; Σ 1/sf_c over its cells with a total = m_S Σ 1/u_c
+    double sf_a, sf_b;   // Σ_A u / m_S, Σ_B u / m_S
+    uint64_t n_a, n_b;
+    uint32_t a, b, literal, pad; // literal: m_S == 0, the pair takes compute_sseq_params + mode 1 DE
+};
+// d_tot[perm[i]] -> d_sorted[i], each group's segment [off[g], off[g + 1]) sorted ascending; d_stats (n_groups x 3 u64): Σ u, Σ 1/u (lo, hi)
+void launch_pairs_group_stats(hipStream_t s, const unsigned long long *d_tot, const uint32_t *d_perm, const uint32_t *d_off, uint32_t n_groups,
+                              uint64_t n_labelled, double scale, unsigned long long *d_gathered, unsigned long long *d_sorted,
+                              unsigned long long *d_stats, DevBuf<char> &sort_tmp);
+void launch_pairs_headers(hipStream_t s, const unsigned long long *d_sorted, const uint32_t *d_off, const unsigned long long *d_stats,
+                          const uint32_t *d_pair_a, const uint32_t *d_pair_b, uint32_t n_pairs, double scale, SseqPairHeader *d_hdr);
+// per (gene, pair), genes x n_pairs row-major: the moments of the union, use_genes, the method-of-moments dispersion, both sides' sums
+void launch_pairs_moments(hipStream_t s, const unsigned long long *d_acc, const SseqPairHeader *d_hdr, uint64_t genes, uint32_t n_pairs,
+                          double scale, double *d_mean, double *d_var, uint8_t *d_use, double *d_phi_mm, unsigned long long *d_sums_a,
+                          unsigned long long *d_sums_b);
+// per pair: zeta_hat, delta (d_zd: n_pairs x 2) and gene_phi (diff_exp.rs:409-441)
+void launch_pairs_shrink(hipStream_t s, const double *d_phi_mm, const uint8_t *d_use, uint64_t genes, uint32_t n_pairs, double pct, double *d_zd,
+                         double *d_phi);
 
 // ---- cluster.hip / cluster_host.cpp: merge_clusters (scan-rs/src/merge_clusters.rs, linkage.rs) ---------------------------------
 constexpr uint32_t MERGE_MAX_CLUSTERS = 8192;

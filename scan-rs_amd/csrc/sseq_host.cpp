@@ -288,9 +288,12 @@ void sseq_params(Storage &st, const SparseCopy &cp, bool gene_major, uint64_t ge
 }
 
 // ---- sseq_de_from_sums_with_cancellation (diff_exp.rs:190-300) ------------------------------------------------------------------
-void sseq_de_sums(hipStream_t s, uint64_t genes, uint32_t n_tests, const uint64_t *sums_a, const uint64_t *sums_b, const double *sf_a,
-                  const double *sf_b, const double *gene_means, const double *gene_phi, const uint8_t *use_genes, uint64_t big_count,
-                  const scanrs_snoop *snoop, double *p, double *p_adj, double *log2fc, double *mean_in, double *mean_out, int backend) {
+// the parameters of test j of gene g are read at [g * stride_g + j * stride_j]: (1, 0) for one SSeqParams shared by every test
+void sseq_de_sums_strided(hipStream_t s, uint64_t genes, uint32_t n_tests, const uint64_t *sums_a, const uint64_t *sums_b, const double *sf_a,
+                          const double *sf_b, const double *gene_means, const double *gene_phi, const uint8_t *use_genes, uint64_t stride_g,
+                          uint64_t stride_j, uint64_t big_count, const scanrs_snoop *snoop, double *p, double *p_adj, double *log2fc,
+                          double *mean_in, double *mean_out, int backend) {
+    auto at = [&](uint64_t g, uint32_t j) { return g * stride_g + j * stride_j; };
     if (backend != SCANRS_NB_EXACT_LOGSPACE && backend != SCANRS_NB_EXACT_RATIO)
         fail(SCANRS_ERR_ARGUMENT, "backend must be SCANRS_NB_EXACT_LOGSPACE (0) or SCANRS_NB_EXACT_RATIO (1)");
     const bool ratio = backend == SCANRS_NB_EXACT_RATIO;
@@ -303,15 +306,15 @@ void sseq_de_sums(hipStream_t s, uint64_t genes, uint32_t n_tests, const uint64_
     // that backend = LogSpace gives it
     auto push_exact = [&](uint64_t o, uint32_t j, uint64_t g) {
         const uint64_t xa = sums_a[o], n = xa + sums_b[o];
-        const double fa = sf_a[j], fb = sf_b[j], r = 1.0 / gene_phi[g];
-        ex.push_back(SseqExactTest{n, xa, fa * r, fb * r, special::nb_add_total(n, fa, fb, gene_means[g], r), n_chunks, o});
+        const double fa = sf_a[j], fb = sf_b[j], r = 1.0 / gene_phi[at(g, j)];
+        ex.push_back(SseqExactTest{n, xa, fa * r, fb * r, special::nb_add_total(n, fa, fb, gene_means[at(g, j)], r), n_chunks, o});
         n_chunks += (n + SSEQ_CHUNK) / SSEQ_CHUNK; // n + 1 terms
     };
     for (uint64_t g = 0; g < genes; g++) {
         for (uint32_t j = 0; j < n_tests; j++) {
             const uint64_t o = g * n_tests + j, xa = sums_a[o], xb = sums_b[o];
-            const double fa = sf_a[j], fb = sf_b[j], mu = gene_means[g], phi = gene_phi[g];
-            if (use_genes[g] && xa > big_count && xb > big_count) {
+            const double fa = sf_a[j], fb = sf_b[j], mu = gene_means[at(g, j)], phi = gene_phi[at(g, j)];
+            if (use_genes[at(g, j)] && xa > big_count && xb > big_count) {
                 as.push_back(SseqAsymTest{xa, xb, fa, fb, mu, phi, o});
                 continue;
             }
@@ -373,13 +376,13 @@ void sseq_de_sums(hipStream_t s, uint64_t genes, uint32_t n_tests, const uint64_
         pv.clear();
         for (uint64_t g = 0; g < genes; g++) {
             p_adj[g * n_tests + j] = p[g * n_tests + j];
-            if (use_genes[g]) pv.push_back(p[g * n_tests + j]);
+            if (use_genes[at(g, j)]) pv.push_back(p[g * n_tests + j]);
         }
         q.resize(pv.size());
         sseq_host_bh(pv.data(), pv.size(), q.data());
         uint64_t k = 0;
         for (uint64_t g = 0; g < genes; g++)
-            if (use_genes[g]) p_adj[g * n_tests + j] = q[k++];
+            if (use_genes[at(g, j)]) p_adj[g * n_tests + j] = q[k++];
     }
     sseq_progress(snoop, 0.9);
     for (uint64_t g = 0; g < genes; g++)
@@ -395,6 +398,13 @@ void sseq_de_sums(hipStream_t s, uint64_t genes, uint32_t n_tests, const uint64_
             mean_out[o] = sf_b[j] == 0.0 ? 0.0 : (double)sums_b[o] / sf_b[j];
         }
     sseq_progress(snoop, 1.0);
+}
+
+void sseq_de_sums(hipStream_t s, uint64_t genes, uint32_t n_tests, const uint64_t *sums_a, const uint64_t *sums_b, const double *sf_a,
+                  const double *sf_b, const double *gene_means, const double *gene_phi, const uint8_t *use_genes, uint64_t big_count,
+                  const scanrs_snoop *snoop, double *p, double *p_adj, double *log2fc, double *mean_in, double *mean_out, int backend) {
+    sseq_de_sums_strided(s, genes, n_tests, sums_a, sums_b, sf_a, sf_b, gene_means, gene_phi, use_genes, 1, 0, big_count, snoop, p, p_adj, log2fc,
+                         mean_in, mean_out, backend);
 }
 
 // ---- sseq_differential_expression (diff_exp.rs:122-175) over labels ---------------------------------------------------------------

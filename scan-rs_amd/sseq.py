@@ -202,6 +202,80 @@ def sseq_de_vs_control(mat: AdaptiveMat, labels, params: SSeqParams, control: in
     return _de_matrix(mat, lab, n_groups, 2, params, big_count, snoop, backend)
 
 
+class _PairParams(ctypes.Structure):
+    """`scanrs_sseq_pair_params` (include/scanrs_amd.h)."""
+
+    _fields_ = [(n, ctypes.c_void_p) for n in ("gene_means", "gene_variances", "gene_moment_phi", "gene_phi", "use_genes", "zeta_hat", "delta", "sf_a",
+                                               "sf_b", "median_total", "sum_size_factors", "n_cells_a", "n_cells_b", "literal")]
+
+
+def sseq_de_pairs(mat: AdaptiveMat, labels, pairs, zeta_quintile: float = ZETA_QUINTILE_DEFAULT, big_count: Optional[int] = None,
+                  n_groups: Optional[int] = None, backend: int = NB_EXACT_LOGSPACE, snoop=None):
+    """Batched pairwise DE with per-pair parameters: for every (a, b) of `pairs`, `compute_sseq_params(mat, zeta_quintile, cells of
+    a ∪ b)` (diff_exp.rs:458-490) and then the cells of group a against those of group b (diff_exp.rs:125-161), as merge_clusters.rs
+    runs its candidates and as diff_exp.rs:361-376 describes the shared-control batched path. All pairs share two passes over the
+    nonzeros; each pair's parameters are combined on the device from its two groups' integer sums. Returns
+    `(List[DiffExpResult], List[SSeqParams])`, one of each per pair; `size_factors` is left empty, as in
+    `sseq_params_from_moments`, and the pair's scalars are attached to its params: `size_factor_a`, `size_factor_b`,
+    `median_total`, `sum_size_factors`, `num_cells_a`, `num_cells_b`, `literal` (the union's median total was 0 and the pair ran
+    the two reference calls themselves). labels: per cell, the group 0 .. n_groups - 1 or -1 (in no group)."""
+    genes, cells = mat.shape()
+    lab = _labels(labels, cells)
+    if n_groups is None:
+        n_groups = int(lab.max()) + 1 if lab.size else 0
+    pr = np.asarray(pairs, dtype=np.int64)
+    if pr.size == 0:
+        pr = pr.reshape(0, 2)
+    if pr.ndim != 2 or pr.shape[1] != 2:
+        raise ScanrsError(6, "pairs must be a list of (group a, group b)")
+    if pr.size and (pr.min() < 0 or pr.max() > 0xFFFFFFFF):
+        raise ScanrsError(6, "pairs hold a group number outside 0 .. n_groups - 1")
+    pa, pb = np.ascontiguousarray(pr[:, 0], dtype=np.uint32), np.ascontiguousarray(pr[:, 1], dtype=np.uint32)
+    t = len(pa)
+    si, so = np.zeros((genes, t), dtype=np.uint64), np.zeros((genes, t), dtype=np.uint64)
+    p, padj, l2, mi, mo, mean, var, phi_mm, phi = (np.zeros((genes, t)) for _ in range(9))
+    use, lit = np.zeros((genes, t), dtype=np.uint8), np.zeros(t, dtype=np.uint8)
+    zh, dl, fa, fb, med, ssf = (np.zeros(t) for _ in range(6))
+    na, nb = np.zeros(t, dtype=np.uint64), np.zeros(t, dtype=np.uint64)
+    pp = _PairParams(*(a.ctypes.data for a in (mean, var, phi_mm, phi, use, zh, dl, fa, fb, med, ssf, na, nb, lit)))
+    sn, _keep = _snoop_arg(snoop)
+    bc = BIG_COUNT_DEFAULT if big_count is None else int(big_count)
+    _check(_lib.scanrs_sseq_de_pairs(mat._h, _p(lab), _u32(n_groups), _p(pa), _p(pb), _u32(t), _f64c(zeta_quintile), _u64(bc),
+                                     ctypes.c_int(_backend(backend)), sn, _p(si), _p(so), _p(p), _p(padj), _p(l2), _p(mi), _p(mo), ctypes.byref(pp)))
+    results, params = [], []
+    for j in range(t):
+        prm = SSeqParams(int(na[j] + nb[j]), genes, np.zeros(0), mean[:, j].copy(), var[:, j].copy(), use[:, j].astype(bool), phi_mm[:, j].copy(),
+                         float(zh[j]), float(dl[j]), phi[:, j].copy())
+        prm.size_factor_a, prm.size_factor_b = float(fa[j]), float(fb[j])
+        prm.median_total, prm.sum_size_factors = float(med[j]), float(ssf[j])
+        prm.num_cells_a, prm.num_cells_b, prm.literal = int(na[j]), int(nb[j]), bool(lit[j])
+        params.append(prm)
+        results.append(DiffExpResult(prm.use_genes.copy(), si[:, j].copy(), so[:, j].copy(), prm.gene_means.copy(), prm.gene_phi.copy(), mi[:, j].copy(),
+                                     mo[:, j].copy(), p[:, j].copy(), padj[:, j].copy(), l2[:, j].copy()))
+    return results, params
+
+
+def sseq_de_each_vs_control(mat: AdaptiveMat, labels, control: int = 0, zeta_quintile: float = ZETA_QUINTILE_DEFAULT, big_count: Optional[int] = None,
+                            n_groups: Optional[int] = None, backend: int = NB_EXACT_LOGSPACE, snoop=None):
+    """Every other group against the group `control`, each test with the parameters of its own union (`sseq_de_pairs` over the
+    pairs (g, control), g ascending). Returns `(List[DiffExpResult], List[SSeqParams])`, one per group other than the control."""
+    lab = np.asarray(labels)
+    if n_groups is None:
+        n_groups = int(lab.max()) + 1 if lab.size else 0
+    if not 0 <= int(control) < n_groups:
+        raise ScanrsError(6, f"control must be a group 0 .. {n_groups - 1}")
+    pairs = [(g, int(control)) for g in range(n_groups) if g != int(control)]
+    return sseq_de_pairs(mat, lab, pairs, zeta_quintile, big_count, n_groups, backend, snoop)
+
+
+def host_union_median(a, b) -> float:
+    """`percentile_of_sorted(.., 50)` (stat.rs:140-162) of the union of two ascending lists, from the two ranks it reads."""
+    a, b = np.ascontiguousarray(a, dtype=np.float64), np.ascontiguousarray(b, dtype=np.float64)
+    out = _f64c()
+    _check(_lib.scanrs_host_union_median(_p(a) if len(a) else None, _u64(len(a)), _p(b) if len(b) else None, _u64(len(b)), ctypes.byref(out)))
+    return out.value
+
+
 def sseq_de_from_sums(feature_sums_a, feature_sums_b, size_factor_a, size_factor_b, params: SSeqParams, big_count: Optional[int] = None,
                       snoop=None, backend: int = NB_EXACT_LOGSPACE):
     """`sseq_de_from_sums` (diff_exp.rs:177-300) on the device. 1-d sums with scalar size factors give one DiffExpResult;

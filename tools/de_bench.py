@@ -7,6 +7,10 @@ branches, and the group pass's one-pass bytes (8 nnz + 2 cells) against HBM. One
 With --control-conditions N the labels are a shared control instead: group 0 holds half the cells, the other half is spread
 over N conditions, and every condition is tested against the control (mode 2, sseq_de_vs_control). The line then carries the
 exact tests, their terms, the tests Ratio hands to LogSpace, and the ms of the tests and of the whole call for the backend.
+With --per-pair-params that leg also times the same tests with the parameters of each pair's own union: `pairs_call_ms` for one
+sseq_de_each_vs_control call (its "de_pairs_passes" / "de_pairs_literal" counters beside it), and `literal_loop_ms` for the calls it
+replaces, compute_sseq_params(cell_indices = union) + sseq_differential_expression per pair, timed once on the first
+`literal_loop_pairs` (at most 20) conditions.
 """
 import argparse
 import json
@@ -32,6 +36,7 @@ def main():
     ap.add_argument("--reps", type=int, default=3)
     ap.add_argument("--backend", choices=("logspace", "ratio"), default="logspace")
     ap.add_argument("--control-conditions", type=int, default=0)
+    ap.add_argument("--per-pair-params", action="store_true", help="with --control-conditions: also time sseq_de_pairs and the per-pair literal calls")
     a = ap.parse_args()
     backend = sa.NB_EXACT_RATIO if a.backend == "ratio" else sa.NB_EXACT_LOGSPACE
     import torch
@@ -117,7 +122,20 @@ def control_leg(a, m, labels, params, t_params, backend, timed, nnz):
     asym = use & (xa > 900) & (xb > 900)
     trivial = ((xa + xb) == 0) | (params.gene_phi[:, None] == 0) | (sf_a[None, :] == 0) | (sf_b[None, :] == 0)
     exact = ~asym & ~trivial
+    pairs = {}
+    if a.per_pair_params:
+        t_pairs, _ = timed(lambda: sa.sseq_de_each_vs_control(m, labels, control=0, n_groups=groups, backend=backend))
+        n_lit = min(20, groups - 1)
+        control = np.flatnonzero(labels == 0)
+        t0 = time.perf_counter()
+        for g in range(1, n_lit + 1):
+            cond = np.flatnonzero(labels == g)
+            pp = sa.compute_sseq_params(m, cell_indices=np.sort(np.concatenate([cond, control])))
+            sa.sseq_differential_expression(m, cond, control, pp, backend=backend)
+        pairs = {"pairs_call_ms": round(t_pairs, 2), "de_pairs_passes": m.counter("de_pairs_passes"), "de_pairs_literal": m.counter("de_pairs_literal"),
+                 "literal_loop_ms": round((time.perf_counter() - t0) * 1e3, 2), "literal_loop_pairs": n_lit}
     print(json.dumps({
+        **pairs,
         "cells": a.cells, "genes": a.genes, "nnz": nnz, "control_conditions": a.control_conditions, "control_cells": int(cnt[0]),
         "backend": a.backend, "params_ms": round(t_params, 2), "group_pass_ms": round(t_pass, 2),
         "tests_ms": round(t_tests, 2), "vs_control_call_ms": round(t_call, 2),
