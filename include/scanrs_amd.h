@@ -158,6 +158,9 @@ int scanrs_mat_sum_axis_f64(scanrs_mat *m, int axis, double *out);
 int scanrs_mat_mean_axis(scanrs_mat *m, int axis, double *out);
 int scanrs_mat_mean_var_axis(scanrs_mat *m, int axis, double *mean, double *var);
 
+/* var_axis (mat.rs:409-411): mean_var_axis(axis).1, the same bits. */
+int scanrs_mat_var_axis(scanrs_mat *m, int axis, double *var);
+
 /* to_dense (mat.rs:188-205, low_rank_offset.rs:55-57): rows x cols f64, small matrices / tests. */
 int scanrs_mat_to_dense(scanrs_mat *m, double *out);
 
@@ -263,6 +266,46 @@ typedef struct {
     scanrs_progress_fn progress;
     void *ctx;
 } scanrs_snoop;
+
+/* ---- statistics over a list of columns: sum_rows / sum_cols / sum_rows_dual / mean_rows / mean_var_rows -------------------------------
+ * sqz/src/mat.rs: sum_rows::<O>(cols) :449-481, sum_cols::<O>(cols) :414-446, sum_rows_dual[_with_cancellation]::<O>(cols1, cols2)
+ * :484-583, mean_rows(cols) :279-282, mean_var_rows(cols) :333-374 — what the reference's own DE is written in (diff_exp.rs:143 calls
+ * sum_rows_dual_with_cancellation::<u64>, :317 sum_cols::<f64>, :469 and :524 mean_var_rows, :574-575 sum_rows::<u64>).
+ * Rows and columns are the view's (scanrs_mat_t swaps them); every call works on a CSR handle, a CSC handle and a transposed view.
+ *
+ * A list holds n indices of view columns, STRICTLY ASCENDING and in range ("must be sorted", mat.rs:413 / :448; a repeated index is
+ * refused as scanrs_sseq_params refuses it): anything else returns SCANRS_ERR_ARGUMENT, with the list's name in scanrs_last_error(),
+ * before any device work. An empty list (n = 0, the pointer may be NULL) is valid: sums are 0, means and variances NaN (0.0 / 0.0, as
+ * in the reference). cols1 and cols2 of the dual forms may overlap; a column in both counts in both results.
+ *   sum_rows      out[r] (rows entries) = the sum of row r over the listed columns
+ *   sum_cols      out[i] (n entries)    = the sum of column cols[i] over all rows
+ *   sum_rows_dual out1 / out2 (rows entries each) = sum_rows over cols1 / cols2, from one walk over the matrix
+ *   mean_rows     sum_rows_f64 / n;  mean_var_rows: mean and E[x^2] - E[x]^2 of the mapped values over the listed columns
+ * The _u64 results are defined on the raw counts: a handle whose map is not the identity is refused (as scanrs_mat_sum_axis_u32);
+ * they are exact (three counts of 4294967295 in a row give 12884901885). The f64 results apply the handle's map per nonzero (stored
+ * zeros and absent entries contribute nothing; a low-rank offset is left out, as scanrs_mat_mean_var_axis leaves it out). They use no
+ * floating-point atomics and are bit-reproducible: two calls give identical arrays, also after other calls on the handle and on a
+ * fresh handle. A sharded handle returns SCANRS_ERR_ARGUMENT.
+ * The kernel form follows the copy that exists: a masked walk when the result axis is the copy's outer
+ * dimension, a walk over the listed vectors when the listed columns are outer vectors; integer results whose copy does not exist are
+ * scattered from the other copy with 64-bit integer atomics instead of building it (handle option "subset_scatter"), f64 results
+ * build it on demand as scanrs_mat_mean_var_axis does. Counters "subset_masked_passes" / "subset_scatter_passes".
+ * `snoop` of the dual forms may be NULL. A cancel flag that is already set returns SCANRS_ERR_CANCELLED before anything is queued;
+ * otherwise the flag is read between launches; a cancelled call leaves out1 / out2 untouched. Progress is nondecreasing, starts at
+ * 0.0 and ends at 1.0 (mat.rs:519, :581).
+ * NOT provided: sum_cols_diff (mat.rs:612-722). Nothing in the reference calls it, its norm_factors branches are recurrences that
+ * read like defects ((acc + v m) / f folded along the vector; an integer division by a truncated factor), and its CSC branch
+ * accumulates in u32. (Declared here, behind scanrs_snoop, which the dual forms take.) */
+int scanrs_mat_sum_rows_u64(scanrs_mat *m, const uint64_t *cols, uint64_t n, uint64_t *out);
+int scanrs_mat_sum_rows_f64(scanrs_mat *m, const uint64_t *cols, uint64_t n, double *out);
+int scanrs_mat_sum_cols_u64(scanrs_mat *m, const uint64_t *cols, uint64_t n, uint64_t *out);
+int scanrs_mat_sum_cols_f64(scanrs_mat *m, const uint64_t *cols, uint64_t n, double *out);
+int scanrs_mat_sum_rows_dual_u64(scanrs_mat *m, const uint64_t *cols1, uint64_t n1, const uint64_t *cols2, uint64_t n2,
+                                 const scanrs_snoop *snoop, uint64_t *out1, uint64_t *out2);
+int scanrs_mat_sum_rows_dual_f64(scanrs_mat *m, const uint64_t *cols1, uint64_t n1, const uint64_t *cols2, uint64_t n2,
+                                 const scanrs_snoop *snoop, double *out1, double *out2);
+int scanrs_mat_mean_rows(scanrs_mat *m, const uint64_t *cols, uint64_t n, double *out);
+int scanrs_mat_mean_var_rows(scanrs_mat *m, const uint64_t *cols, uint64_t n, double *mean, double *var);
 
 /* BkSvd::run_pca_cancellable / svd_bk (dim_red/bk_svd.rs:41-146).
  * omega: optional explicit start panel in the reference's own layout
@@ -412,6 +455,10 @@ int scanrs_mat_set_spmm_path(scanrs_mat *m, int path);
  *   "merge_fused" (1)   scanrs_merge_clusters: per-cell totals plus ONE grouped pass over the nonzeros per call (per gene-major tile of
  *                       1536 clusters), every candidate from those sums; 0: compute_sseq_params on the union and the pairwise DE for
  *                       every candidate, as the reference calls them (A/B and test baseline). Same labels; p-values agree to ~1e-12
+ *   "subset_scatter" (1) integer sums over a column list (scanrs_mat_sum_rows_u64, _sum_cols_u64, _sum_rows_dual_u64) whose result axis is
+ *                       the outer dimension of a copy that does not exist yet: 1 = scattered into the result with 64-bit integer atomics
+ *                       from the copy that exists (exact in any order; no transposed copy is built); 0 = the missing copy is built
+ *                       and walked without atomics. Same results.
  *   "tile_spare_cus" (1) the persistent tile kernel launches as many workgroups as its number of item rounds needs (3 977 equal items:
  *                       16 rounds on 256 workgroups and on 249); the CUs left over serve the side streams during the pass (0: one per CU)
  *   "spmv_row_table" (1) Ix1 products over many short outer vectors (IRLBA's A v on the cell-major copy): a map that depends on the count
@@ -482,7 +529,9 @@ int scanrs_mat_set_option(scanrs_mat *m, const char *key, double value);
  * per pair of passes, "tile_served_nonzeros" = nonzeros among them (the rest is padding), "tile_overflow_nonzeros" = nonzeros left
  * to the overflow gather. "partition_rounds" = rounds of the last scanrs_mat_partition_on_thresholds on this handle, the final round
  * that changes nothing included. "de_pairs_passes" / "de_pairs_literal" = the last scanrs_sseq_de_pairs on this handle: its passes over
- * the nonzeros and its pairs on the literal route. */
+ * the nonzeros and its pairs on the literal route. "subset_masked_passes" / "subset_scatter_passes" = sums over a column list made on
+ * this handle so far: from the copy whose outer dimension is the result axis (masked walk or listed vectors, no atomics) / through the
+ * integer scatter from the other copy ("subset_scatter"). */
 int scanrs_mat_get_counter(scanrs_mat *m, const char *key, uint64_t *value);
 /* Process-wide options of the entry points that take no handle:
  *   "h5_threads" (8)               threads that inflate the chunks of a large filtered HDF5 read

@@ -125,6 +125,16 @@ inline std::pair<int, uint64_t> choose_storage(uint64_t len, const std::vector<u
 class AdaptiveMat {
     scanrs_mat *h_ = nullptr;
     explicit AdaptiveMat(scanrs_mat *h) : h_(h) {}
+    static scanrs_snoop snoop_of(Snoop *s) {
+        scanrs_snoop sn;
+        sn.cancel = s ? reinterpret_cast<const volatile uint8_t *>(&s->cancelled) : nullptr;
+        sn.progress = [](void *ctx, double f) {
+            auto *sp = static_cast<Snoop *>(ctx);
+            if (sp && sp->on_progress) sp->on_progress(f);
+        };
+        sn.ctx = s;
+        return sn;
+    }
 
   public:
     AdaptiveMat() = default;
@@ -209,6 +219,63 @@ class AdaptiveMat {
         std::vector<double> out(axis == 0 ? cols() : rows());
         check(scanrs_mat_mean_axis(h_, axis, out.data()));
         return out;
+    }
+    std::pair<std::vector<double>, std::vector<double>> mean_var_axis(int axis) const { // mat.rs:285-330
+        std::vector<double> mean(axis == 0 ? cols() : rows()), var(mean.size());
+        check(scanrs_mat_mean_var_axis(h_, axis, mean.data(), var.data()));
+        return {mean, var};
+    }
+    std::vector<double> var_axis(int axis) const { // mat.rs:409-411
+        std::vector<double> out(axis == 0 ? cols() : rows());
+        check(scanrs_mat_var_axis(h_, axis, out.data()));
+        return out;
+    }
+    // statistics over a list of columns (mat.rs:279-282, 333-374, 414-583): strictly ascending indices. The u64 forms read the raw
+    // counts (exact), the f64 forms the mapped values (bit-reproducible)
+    std::vector<uint64_t> sum_rows_u64(const std::vector<uint64_t> &cols_) const { // mat.rs:449-481
+        std::vector<uint64_t> out(rows());
+        check(scanrs_mat_sum_rows_u64(h_, cols_.data(), cols_.size(), out.data()));
+        return out;
+    }
+    std::vector<double> sum_rows(const std::vector<uint64_t> &cols_) const {
+        std::vector<double> out(rows());
+        check(scanrs_mat_sum_rows_f64(h_, cols_.data(), cols_.size(), out.data()));
+        return out;
+    }
+    std::vector<uint64_t> sum_cols_u64(const std::vector<uint64_t> &cols_) const { // mat.rs:414-446: one entry per listed column
+        std::vector<uint64_t> out(cols_.size());
+        check(scanrs_mat_sum_cols_u64(h_, cols_.data(), cols_.size(), out.data()));
+        return out;
+    }
+    std::vector<double> sum_cols(const std::vector<uint64_t> &cols_) const {
+        std::vector<double> out(cols_.size());
+        check(scanrs_mat_sum_cols_f64(h_, cols_.data(), cols_.size(), out.data()));
+        return out;
+    }
+    // sum_rows_dual / sum_rows_dual_with_cancellation (mat.rs:484-583): both lists in one walk; they may overlap
+    std::pair<std::vector<uint64_t>, std::vector<uint64_t>> sum_rows_dual_u64(const std::vector<uint64_t> &cols1, const std::vector<uint64_t> &cols2,
+                                                                            Snoop *snoop = nullptr) const {
+        std::vector<uint64_t> a(rows()), b(rows());
+        scanrs_snoop sn = snoop_of(snoop);
+        check(scanrs_mat_sum_rows_dual_u64(h_, cols1.data(), cols1.size(), cols2.data(), cols2.size(), snoop ? &sn : nullptr, a.data(), b.data()));
+        return {a, b};
+    }
+    std::pair<std::vector<double>, std::vector<double>> sum_rows_dual(const std::vector<uint64_t> &cols1, const std::vector<uint64_t> &cols2,
+                                                                      Snoop *snoop = nullptr) const {
+        std::vector<double> a(rows()), b(rows());
+        scanrs_snoop sn = snoop_of(snoop);
+        check(scanrs_mat_sum_rows_dual_f64(h_, cols1.data(), cols1.size(), cols2.data(), cols2.size(), snoop ? &sn : nullptr, a.data(), b.data()));
+        return {a, b};
+    }
+    std::vector<double> mean_rows(const std::vector<uint64_t> &cols_) const { // mat.rs:279-282
+        std::vector<double> out(rows());
+        check(scanrs_mat_mean_rows(h_, cols_.data(), cols_.size(), out.data()));
+        return out;
+    }
+    std::pair<std::vector<double>, std::vector<double>> mean_var_rows(const std::vector<uint64_t> &cols_) const { // mat.rs:333-374
+        std::vector<double> mean(rows()), var(rows());
+        check(scanrs_mat_mean_var_rows(h_, cols_.data(), cols_.size(), mean.data(), var.data()));
+        return {mean, var};
     }
     // Dot impls: self.dot(rhs) and lhs.dot(self)
     Array2 dot(const Array2 &rhs) const {

@@ -398,6 +398,78 @@ class AdaptiveMat:
         _check(_lib.scanrs_mat_mean_var_axis(self._h, ctypes.c_int(axis), _p(mean), _p(var)))
         return mean, var
 
+    def var_axis(self, axis: int):
+        """`var_axis` (mat.rs:409-411): `mean_var_axis(axis)[1]`, the same bits."""
+        if axis not in (0, 1):
+            raise ScanrsError(6, "axis must be 0 or 1")
+        out = np.zeros(self.cols() if axis == 0 else self.rows())
+        _check(_lib.scanrs_mat_var_axis(self._h, ctypes.c_int(axis), _p(out)))
+        return out
+
+    # -- statistics over a list of columns (mat.rs:279-282, 333-374, 414-583) ---------------
+    @staticmethod
+    def _col_list(cols):
+        cols = np.ascontiguousarray(np.asarray(cols).reshape(-1), dtype=np.int64)
+        if cols.size and int(cols.min()) < 0:
+            raise ScanrsError(6, "index out of range: negative index")
+        return cols.astype(np.uint64)
+
+    @staticmethod
+    def _sum_dtype(dtype):
+        dt = np.dtype(dtype)
+        if dt not in (np.dtype(np.uint64), np.dtype(np.uint32), np.dtype(np.float64)):
+            raise ScanrsError(6, "dtype must be np.uint64, np.uint32 or np.float64")
+        return dt
+
+    @staticmethod
+    def _narrow(out, dt):
+        # u32 results are computed in 64 bits and narrowed; the reference's u32 accumulator panics on overflow in a debug build
+        if dt != np.dtype(np.uint32):
+            return out
+        if out.size and int(out.max()) > 0xFFFFFFFF:
+            raise OverflowError(f"a sum of {int(out.max())} does not fit in uint32")
+        return out.astype(np.uint32)
+
+    def _sums_over(self, fn_u64, fn_f64, cols, dtype, n_out):
+        dt, cols = self._sum_dtype(dtype), self._col_list(cols)
+        out = np.zeros(n_out(cols), dtype=np.float64 if dt == np.dtype(np.float64) else np.uint64)
+        _check((fn_f64 if dt == np.dtype(np.float64) else fn_u64)(self._h, _p(cols), ctypes.c_uint64(cols.shape[0]), _p(out)))
+        return self._narrow(out, dt)
+
+    def sum_rows(self, cols, dtype=np.float64):
+        """`sum_rows::<O>(cols)` (mat.rs:449-481): per row, the sum over the listed columns (strictly ascending). Integer dtypes read
+        the raw counts (exact), float64 the mapped values."""
+        return self._sums_over(_lib.scanrs_mat_sum_rows_u64, _lib.scanrs_mat_sum_rows_f64, cols, dtype, lambda c: self.rows())
+
+    def sum_cols(self, cols, dtype=np.float64):
+        """`sum_cols::<O>(cols)` (mat.rs:414-446): per listed column, in list order, the sum over all rows."""
+        return self._sums_over(_lib.scanrs_mat_sum_cols_u64, _lib.scanrs_mat_sum_cols_f64, cols, dtype, lambda c: c.shape[0])
+
+    def sum_rows_dual(self, cols1, cols2, dtype=np.float64, snoop=None):
+        """`sum_rows_dual` / `sum_rows_dual_with_cancellation` (mat.rs:484-583): `sum_rows` over two lists from one walk; the lists
+        may overlap."""
+        dt, c1, c2 = self._sum_dtype(dtype), self._col_list(cols1), self._col_list(cols2)
+        is_f = dt == np.dtype(np.float64)
+        o1, o2 = (np.zeros(self.rows(), dtype=np.float64 if is_f else np.uint64) for _ in range(2))
+        sn, _keep = _snoop_arg(snoop)
+        fn = _lib.scanrs_mat_sum_rows_dual_f64 if is_f else _lib.scanrs_mat_sum_rows_dual_u64
+        _check(fn(self._h, _p(c1), ctypes.c_uint64(c1.shape[0]), _p(c2), ctypes.c_uint64(c2.shape[0]), sn, _p(o1), _p(o2)))
+        return self._narrow(o1, dt), self._narrow(o2, dt)
+
+    def mean_rows(self, cols):
+        """`mean_rows(cols)` (mat.rs:279-282); an empty list gives NaN."""
+        cols = self._col_list(cols)
+        out = np.zeros(self.rows())
+        _check(_lib.scanrs_mat_mean_rows(self._h, _p(cols), ctypes.c_uint64(cols.shape[0]), _p(out)))
+        return out
+
+    def mean_var_rows(self, cols):
+        """`mean_var_rows(cols)` (mat.rs:333-374): per row, mean and E[x^2] - E[x]^2 of the mapped values over the listed columns."""
+        cols = self._col_list(cols)
+        mean, var = np.zeros(self.rows()), np.zeros(self.rows())
+        _check(_lib.scanrs_mat_mean_var_rows(self._h, _p(cols), ctypes.c_uint64(cols.shape[0]), _p(mean), _p(var)))
+        return mean, var
+
     def to_dense(self):
         r, c = self.shape()
         out = np.zeros((r, c))
@@ -1118,6 +1190,8 @@ EXPORTED_SYMBOLS = [
     "scanrs_mat_select_rows", "scanrs_mat_select_cols", "scanrs_mat_partition_on_thresholds", "scanrs_mat_to_csmat",
     "scanrs_mat_to_adaptive", "scanrs_adaptive_export_info", "scanrs_adaptive_export_vecs", "scanrs_adaptive_export_free",
     "scanrs_host_choose_storage",
+    "scanrs_mat_sum_rows_u64", "scanrs_mat_sum_rows_f64", "scanrs_mat_sum_cols_u64", "scanrs_mat_sum_cols_f64", "scanrs_mat_sum_rows_dual_u64",
+    "scanrs_mat_sum_rows_dual_f64", "scanrs_mat_mean_rows", "scanrs_mat_mean_var_rows", "scanrs_mat_var_axis",
 ]
 
 # sSeq differential expression (sseq.py)

@@ -857,6 +857,14 @@ int scanrs_mat_mean_var_axis(scanrs_mat *m, int axis, double *mean, double *var)
     });
 }
 
+int scanrs_mat_var_axis(scanrs_mat *m, int axis, double *var) {
+    // sqz/src/mat.rs:409-411: mean_var_axis(axis).1 — through that very entry point, so the variances are the same bits
+    if (!m || !var || (axis != 0 && axis != 1)) return guard([&] { fail(SCANRS_ERR_ARGUMENT, !m || !var ? "null argument" : "axis must be 0 or 1"); });
+    std::vector<double> mean;
+    const int rc = guard([&] { mean.resize(std::max<uint64_t>(1, axis == 1 ? m->rows() : m->cols())); });
+    return rc != SCANRS_OK ? rc : scanrs_mat_mean_var_axis(m, axis, mean.data(), var);
+}
+
 int scanrs_mat_to_dense(scanrs_mat *m, double *out) {
     return guard([&] {
         if (!m || !out) fail(SCANRS_ERR_ARGUMENT, "null argument");
@@ -1324,6 +1332,8 @@ int scanrs_mat_set_option(scanrs_mat *m, const char *key, double value) {
             st.device_factor = value != 0.0;
         } else if (k == "merge_fused") {
             st.merge_fused = (int)as_u32(0, 1);
+        } else if (k == "subset_scatter") {
+            st.subset_scatter = (int)as_u32(0, 1);
         } else if (k == "d2h_threads") {
             st.d2h_threads = as_u32(1, 256);
         } else if (k == "sync_timeout_s") { // process-wide (the waits have no handle): same as scanrs_set_global_option
@@ -1354,6 +1364,10 @@ int scanrs_mat_get_counter(scanrs_mat *m, const char *key, uint64_t *value) {
             *value = m->st->de_pairs_passes;
         else if (k == "de_pairs_literal") // ... and pairs that took the literal route
             *value = m->st->de_pairs_literal;
+        else if (k == "subset_masked_passes") // sums over a column list on this handle: made from the copy whose outer dimension is the result axis ...
+            *value = m->st->subset_masked_passes;
+        else if (k == "subset_scatter_passes") // ... and through the integer scatter from the other copy
+            *value = m->st->subset_scatter_passes;
         else if (k == "t_layout_us") // first-call accounting: host time of the calling thread in tile layout builds ...
             *value = m->st->t_layout_us;
         else if (k == "t_side_wait_us") // ... waiting for the helper thread that builds the second orientation

@@ -406,6 +406,8 @@ struct Storage {
     int panel_precision = 0;              // 0: f64 panels (default); 1: gathered panels rounded to f32, f64 sums (opt-in)
     uint64_t partition_rounds = 0;        // rounds of the last scanrs_mat_partition_on_thresholds on this handle, the final one that changes nothing included (scanrs_mat_get_counter)
     uint64_t de_pairs_passes = 0, de_pairs_literal = 0; // the last scanrs_sseq_de_pairs on this handle: passes over the nonzeros, pairs on the literal route (scanrs_mat_get_counter)
+    int subset_scatter = 1;               // integer sums over a column list when only the other orientation exists: 1 = scattered into the result with 64-bit integer atomics from the copy that exists, 0 = the missing copy is built (subset_host.cpp)
+    uint64_t subset_masked_passes = 0, subset_scatter_passes = 0; // sums over a column list made so far on this handle: from the copy whose outer dimension is the result axis / through the integer scatter (scanrs_mat_get_counter)
     int merge_fused = 1;                  // merge_clusters: 1 = one grouped pass per call, candidates from its sums; 0 = params + pairwise DE per candidate (the reference's calls)
     size_t l2_tile_bytes = 3584u << 10;   // panel slice per step of the L2-blocked gather (4 MB L2 per XCD): whole 1024-row base tiles up to 3.5 MB — 4 tiles (3.2 MB) at 100 columns, 3 (2.9 MB) at 122; measured 40.55 / 39.71 ms per pass against 41.30 / 40.23 with 3 tiles and 40.86 / 39.61 with 5, and 4 tiles of 122 columns (3.9 MB) lose 1.8 ms
     int spmm_order = 1;                   // L2-blocked gather: launch outer vectors longest first: 0 never, 1 auto, 2 always (SCANRS_SPMM_ORDER)
@@ -787,5 +789,20 @@ void select_inner(Storage &st, const SparseCopy &cp, const uint64_t *idx, uint64
 // Returns the number of rounds.
 uint64_t partition_on_thresholds(Storage &st, const SparseCopy &cp, const double *thr_outer, const double *thr_inner, bool cols_inner,
                                  std::vector<uint8_t> &excl_outer, std::vector<uint8_t> &excl_inner, SparseCopy *filtered, SparseCopy *residual);
+
+// ---- subset.hip / subset_host.cpp: sum_rows, sum_cols, sum_rows_dual, mean_rows, mean_var_rows (sqz/src/mat.rs:279-282, 333-374, 414-583) ----
+// d_list: n distinct positions (u32) on the device. mode 0: u64 sums of the raw counts, 1: f64 sums of the mapped values, 2: f64 sum and
+// sum of squares (one list). Results: d_out[k * stride + position], k = the list (or 0 = sum, 1 = sum of squares).
+void launch_subset_code(Storage &st, const uint32_t *d_list, uint64_t n, uint8_t bit, uint8_t *d_code); // d_code[list[i]] |= bit
+void launch_subset_pos(Storage &st, const uint32_t *d_list, uint64_t n, uint32_t *d_pos);               // d_pos[list[i]] = i
+// masked walk over cp's work items; d_slab: 2 values per slab row of cp (cp.n_slab rows), d_code: one byte per inner position
+void launch_subset_reduce(Storage &st, const SparseCopy &cp, const DevMap &map, int mode, int n_sets, const uint8_t *d_code, void *d_out,
+                          uint64_t stride, void *d_slab);
+void launch_subset_finish(Storage &st, const SparseCopy &cp, int mode, int n_k, const void *d_slab, void *d_out, uint64_t stride);
+// d_out[d_pos[inner]] += count over all of cp (d_out zeroed by the caller; d_pos: 0xFFFFFFFF where not listed)
+void launch_subset_inner_scatter(Storage &st, const SparseCopy &cp, const uint32_t *d_pos, unsigned long long *d_out);
+// the listed outer vectors of cp: d_out[i] = sum of vector d_list[i] (mode 0 or 1) / d_out[inner] += count (d_out zeroed by the caller)
+void launch_subset_listed(Storage &st, const SparseCopy &cp, const DevMap &map, int mode, const uint32_t *d_list, uint64_t n, void *d_out);
+void launch_subset_listed_scatter(Storage &st, const SparseCopy &cp, const uint32_t *d_list, uint64_t n, unsigned long long *d_out);
 
 } // namespace scanrs
