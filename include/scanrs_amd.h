@@ -390,6 +390,8 @@ void scanrs_multi_free(scanrs_multi *mm);
 int scanrs_multi_n_shards(const scanrs_multi *mm, uint32_t *n);
 /* shard i: its handle (owned by mm; use it from a thread whose current device is *device), its range of outer vectors */
 int scanrs_multi_shard(scanrs_multi *mm, uint32_t i, scanrs_mat **shard, int *device, uint64_t *outer_begin, uint64_t *outer_end);
+/* scanrs_comm_info of shard i's communicator: the exchange steps of this shard so far (calls, payload bytes) */
+int scanrs_multi_comm_info(scanrs_multi *mm, uint32_t i, uint32_t *nranks, uint32_t *rank, uint64_t *n_allreduce, uint64_t *allreduce_bytes);
 int scanrs_multi_normalize(scanrs_multi *mm, int normalization, const uint32_t *size_factors);
 int scanrs_multi_pca_bk(scanrs_multi *mm, uint32_t k, double k_multiplier, uint32_t n_iter, uint64_t seed, const double *omega,
                         const scanrs_snoop *snoop, double *u, double *s, double *v);
@@ -399,6 +401,21 @@ int scanrs_multi_log_normalize(scanrs_multi *mm, double umi_count_sum, int log_f
 /* v0 (optional) spans ALL columns of the matrix. */
 int scanrs_multi_pca_irlba(scanrs_multi *mm, uint32_t nu, double tol, uint32_t max_iter, const double *v0, const scanrs_snoop *snoop,
                            double *u, double *s, double *v, uint32_t *mprod);
+/* sSeq differential expression over the shards (see "Sharded handles" in the sSeq section below): scanrs_sseq_params,
+ * scanrs_mat_group_sums and scanrs_sseq_de_backend (modes 0, 1 and 2, both backends) with the handle replaced by `mm, transposed`.
+ * The cells must be the sharded dimension: a genes x cells matrix created CSC with transposed = 0, or a cells x genes matrix created
+ * CSR with transposed = 1 (every shard then runs through scanrs_mat_t); anything else returns SCANRS_ERR_ARGUMENT. All per-cell
+ * arguments span the whole matrix; the outputs are those of the unsharded call, bit for bit (shard 0 writes them, the other shards
+ * write the same values into scratch of the call). Every shard polls the cancel flag of `snoop`, only shard 0 reports progress. */
+int scanrs_multi_sseq_params(scanrs_multi *mm, int transposed, double zeta_quintile, const uint64_t *cell_indices, uint64_t n_sel,
+                             const double *umi_counts, double *size_factors, double *gene_means, double *gene_variances,
+                             uint8_t *use_genes, double *gene_moment_phi, double *zeta_hat, double *delta, double *gene_phi);
+int scanrs_multi_group_sums(scanrs_multi *mm, int transposed, const int16_t *labels, uint32_t n_groups, uint64_t *sums,
+                            uint64_t *cells_per_group);
+int scanrs_multi_sseq_de(scanrs_multi *mm, int transposed, const int16_t *labels, uint32_t n_groups, int mode, const double *size_factors,
+                         const double *gene_means, const double *gene_phi, const uint8_t *use_genes, uint64_t big_count, int backend,
+                         const scanrs_snoop *snoop, uint64_t *sums_in, uint64_t *sums_out, double *p, double *p_adj, double *log2fc,
+                         double *mean_in, double *mean_out);
 /* nnz-balanced contiguous partition of the outer dimension: bounds has world+1 entries. */
 int scanrs_plan_shards(const uint64_t *indptr, uint64_t n_outer, uint32_t world, uint64_t *bounds);
 
@@ -529,7 +546,8 @@ int scanrs_mat_set_option(scanrs_mat *m, const char *key, double value);
  * per pair of passes, "tile_served_nonzeros" = nonzeros among them (the rest is padding), "tile_overflow_nonzeros" = nonzeros left
  * to the overflow gather. "partition_rounds" = rounds of the last scanrs_mat_partition_on_thresholds on this handle, the final round
  * that changes nothing included. "de_pairs_passes" / "de_pairs_literal" = the last scanrs_sseq_de_pairs on this handle: its passes over
- * the nonzeros and its pairs on the literal route. "subset_masked_passes" / "subset_scatter_passes" = sums over a column list made on
+ * the nonzeros and its pairs on the literal route. "de_shard_tests" / "de_shard_allreduces" = the last sSeq DE call on this handle: the
+ * tests this rank launched on the device, and the exchange steps of a sharded handle (0 on an unsharded one). "subset_masked_passes" / "subset_scatter_passes" = sums over a column list made on
  * this handle so far: from the copy whose outer dimension is the result axis (masked walk or listed vectors, no atomics) / through the
  * integer scatter from the other copy ("subset_scatter"). */
 int scanrs_mat_get_counter(scanrs_mat *m, const char *key, uint64_t *value);
@@ -647,9 +665,28 @@ int scanrs_host_sym_eig_topk(const double *a, int n, int k, double *w, double *z
 /* ---- sSeq differential expression (diff-exp/src/diff_exp.rs, dist.rs; NbExactBackend::LogSpace and ::Ratio) ----------------
  * Rows of the handle are genes and columns are cells (the reference's feature x barcode matrix; use scanrs_mat_t on a cell-major
  * handle). DE reads the stored u32 counts and ignores the handle's map and offset. Labels are one int16 per cell: the group
- * 0 .. n_groups - 1 (n_groups <= 8192) or -1 for a cell in no group. Sharded handles return SCANRS_ERR_ARGUMENT. Outputs of
+ * 0 .. n_groups - 1 (n_groups <= 8192) or -1 for a cell in no group. Outputs of
  * several tests are row-major genes x n_tests arrays. Checkpoints of `snoop`: 0.0, 0.1, 0.6, 0.75, 0.9, 0.95, 1.0
- * (diff_exp.rs:137-300); a set cancel flag returns SCANRS_ERR_CANCELLED. */
+ * (diff_exp.rs:137-300); a set cancel flag returns SCANRS_ERR_CANCELLED.
+ *
+ * Sharded handles (scanrs_mat_set_shard[_comm], the shards of scanrs_multi_*). scanrs_sseq_params, scanrs_mat_group_sums,
+ * scanrs_sseq_de and scanrs_sseq_de_backend (modes 0, 1 and 2, both backends) serve a handle whose CELLS - the view's columns - are
+ * the sharded dimension: a genes x cells CSC handle, or scanrs_mat_t of a cells x genes CSR one. A handle sharded over the genes
+ * returns SCANRS_ERR_ARGUMENT. On a sharded handle every per-cell argument and output spans the WHOLE matrix, not the local slice:
+ * labels, size_factors (input and output) and umi_counts have outer_global entries (umi_counts one per selected cell) and
+ * cell_indices holds global indices. Every rank passes the same values and receives the same complete outputs; each rank uploads
+ * only its slice [outer_begin, outer_begin + local columns) to the device. Every output equals the call on one unsharded handle of
+ * the whole matrix bit for bit, for any number of shards and any transport: all sums that cross the shards are integers and travel
+ * as u64 sum all-reduces (dtype 1 of scanrs_allreduce_fn; no floating-point all-reduce is used) - the per-cell totals
+ * (outer_global u64 of device scratch per rank), the largest count, the group sums, and the 128-bit fixed-point moments as 32-bit
+ * limbs - and the host folds (median, size-factor sums) run replicated over the global arrays in cell order. The tests are split
+ * over the ranks by gene, rank r launching those of genes [G r / W, G (r + 1) / W), and their p-values are gathered by one more u64
+ * all-reduce over the bit patterns; BH, log2 fold change and the means are replicated. Every rank polls its `snoop` at the same
+ * checkpoints and must see the same cancel flag; scanrs_multi_sseq_de lets only shard 0 report progress. Counters
+ * (scanrs_mat_get_counter): "de_shard_tests" = the tests this rank launched on the device in the last DE call (an unsharded
+ * handle: all of them), "de_shard_allreduces" = the exchange steps of the last params / group sums / DE call.
+ * What stays refused on a sharded handle (SCANRS_ERR_ARGUMENT, "sharded" in scanrs_last_error()): scanrs_sseq_de_pairs,
+ * scanrs_merge_clusters and the statistics over a column list (scanrs_mat_sum_rows and its kin). */
 
 /* `compute_sseq_params` (diff_exp.rs:458-500). cell_indices (n_sel entries, or NULL for every cell): only those cells get a
  * size factor, the rest 0. umi_counts (one per selected cell, or NULL): replaces the per-cell totals. Size factors are the

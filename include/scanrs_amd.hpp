@@ -464,6 +464,13 @@ class MultiMat {
     ~MultiMat() { scanrs_multi_free(h_); }
     size_t rows() const { return rows_; }
     size_t cols() const { return cols_; }
+    scanrs_multi *raw() const { return h_; }
+    // payload bytes of the sum all-reduces that went through shard i's communicator so far (scanrs_multi_comm_info)
+    uint64_t allreduce_bytes(uint32_t i = 0) const {
+        uint64_t b = 0;
+        check(scanrs_multi_comm_info(h_, i, nullptr, nullptr, nullptr, &b));
+        return b;
+    }
     void normalize(Normalization norm) { check(scanrs_multi_normalize(h_, (int)norm, nullptr)); }
     PcaResult run_pca(const BkSvd &cfg, size_t k) {
         PcaResult r{Array2(rows_, k), std::vector<double>(k), Array2(cols_, k)};
@@ -630,6 +637,59 @@ inline std::vector<DiffExpResult> sseq_de(const AdaptiveMat &m, const std::vecto
     check(scanrs_sseq_de_backend(m.raw(), labels.data(), n_groups, mode, p.size_factors.data(), p.gene_means.data(), p.gene_phi.data(),
                                  p.use_genes.data(), big_count, (int)backend, snoop ? &sn : nullptr, si.data(), so.data(), pv.data(), pa.data(),
                                  l2.data(), mi.data(), mo.data()));
+    std::vector<DiffExpResult> out(t);
+    for (uint32_t j = 0; j < t; j++) {
+        DiffExpResult &r = out[j];
+        for (uint64_t i = 0; i < g; i++) {
+            const uint64_t o = i * t + j;
+            r.sums_in.push_back(si[o]);
+            r.sums_out.push_back(so[o]);
+            r.p_values.push_back(pv[o]);
+            r.adjusted_p_values.push_back(pa[o]);
+            r.log2_fold_change.push_back(l2[o]);
+            r.normalized_mean_in.push_back(mi[o]);
+            r.normalized_mean_out.push_back(mo[o]);
+        }
+    }
+    return out;
+}
+// The same two calls over the shards of a MultiMat (scanrs_multi_sseq_params, scanrs_multi_sseq_de): the cells must be the sharded
+// dimension - a genes x cells CSC matrix, or a cells x genes CSR one with transposed = true. Arguments and results span the whole
+// matrix and equal those of an unsharded handle bit for bit.
+inline SSeqParams compute_sseq_params(const MultiMat &m, bool transposed = false, double zeta_quintile = ZETA_QUINTILE_DEFAULT,
+                                      const std::vector<uint64_t> *cell_indices = nullptr, const std::vector<double> *umi_counts = nullptr) {
+    SSeqParams p;
+    const uint64_t g = transposed ? m.cols() : m.rows(), c = transposed ? m.rows() : m.cols();
+    p.num_genes = (uint32_t)g;
+    p.num_cells = (uint32_t)(cell_indices ? cell_indices->size() : c);
+    p.size_factors.resize(c);
+    p.gene_means.resize(g);
+    p.gene_variances.resize(g);
+    p.use_genes.resize(g);
+    p.gene_moment_phi.resize(g);
+    p.gene_phi.resize(g);
+    check(scanrs_multi_sseq_params(m.raw(), transposed ? 1 : 0, zeta_quintile, cell_indices ? cell_indices->data() : nullptr,
+                                   cell_indices ? cell_indices->size() : 0, umi_counts ? umi_counts->data() : nullptr, p.size_factors.data(),
+                                   p.gene_means.data(), p.gene_variances.data(), p.use_genes.data(), p.gene_moment_phi.data(), &p.zeta_hat, &p.delta,
+                                   p.gene_phi.data()));
+    return p;
+}
+inline std::vector<uint64_t> group_sums(const MultiMat &m, bool transposed, const std::vector<int16_t> &labels, uint32_t n_groups) {
+    std::vector<uint64_t> sums((transposed ? m.cols() : m.rows()) * n_groups);
+    check(scanrs_multi_group_sums(m.raw(), transposed ? 1 : 0, labels.data(), n_groups, sums.data(), nullptr));
+    return sums;
+}
+inline std::vector<DiffExpResult> sseq_de(const MultiMat &m, bool transposed, const std::vector<int16_t> &labels, uint32_t n_groups, int mode,
+                                          const SSeqParams &p, uint64_t big_count = BIG_COUNT_DEFAULT, Snoop *snoop = nullptr,
+                                          NbExactBackend backend = NbExactBackend::LogSpace) {
+    const uint64_t g = transposed ? m.cols() : m.rows();
+    const uint32_t t = mode == 0 ? n_groups : mode == 2 && n_groups > 0 ? n_groups - 1 : 1;
+    std::vector<uint64_t> si(g * t), so(g * t);
+    std::vector<double> pv(g * t), pa(g * t), l2(g * t), mi(g * t), mo(g * t);
+    scanrs_snoop sn = detail::make_snoop(snoop);
+    check(scanrs_multi_sseq_de(m.raw(), transposed ? 1 : 0, labels.data(), n_groups, mode, p.size_factors.data(), p.gene_means.data(),
+                               p.gene_phi.data(), p.use_genes.data(), big_count, (int)backend, snoop ? &sn : nullptr, si.data(), so.data(), pv.data(),
+                               pa.data(), l2.data(), mi.data(), mo.data()));
     std::vector<DiffExpResult> out(t);
     for (uint32_t j = 0; j < t; j++) {
         DiffExpResult &r = out[j];

@@ -322,6 +322,7 @@ class AdaptiveMat:
         _check(_lib.scanrs_mat_view(self._h, ctypes.byref(h)))
         v = AdaptiveMat(h.value)
         v._keep = self._keep
+        v._outer_global = getattr(self, "_outer_global", None)
         return v
 
     def t(self) -> "AdaptiveMat":
@@ -329,6 +330,7 @@ class AdaptiveMat:
         _check(_lib.scanrs_mat_t(self._h, ctypes.byref(h)))
         v = AdaptiveMat(h.value)
         v._keep = self._keep
+        v._outer_global = getattr(self, "_outer_global", None)
         return v
 
     # -- lazy maps --------------------------------------------------------------------------
@@ -656,6 +658,7 @@ class AdaptiveMat:
             _lib.scanrs_mat_set_shard(
                 self._h, ctypes.c_uint32(rank), ctypes.c_uint32(world), ctypes.c_uint64(outer_begin),
                 ctypes.c_uint64(outer_global), cb if cb is not None else ctypes.cast(None, _ALLREDUCE_FN), None))
+        self._outer_global = int(outer_global)
         return self
 
     def set_shard_comm(self, comm: "Comm", outer_begin: int, outer_global: int):
@@ -664,6 +667,7 @@ class AdaptiveMat:
         _check(_lib.scanrs_mat_set_shard_comm(self._h, comm._c, ctypes.c_uint32(comm.rank), ctypes.c_uint32(comm.world),
                                               ctypes.c_uint64(outer_begin), ctypes.c_uint64(outer_global)))
         self._keep.append(comm)
+        self._outer_global = int(outer_global)
         return self
 
     def profile_enable(self, on: bool = True):
@@ -1036,6 +1040,20 @@ class MultiMat:
                                                ctypes.c_int(log_fn), _p(sf)))
         return self
 
+    def comm_info(self, shard: int = 0) -> dict:
+        """`scanrs_comm_info` of shard `shard`'s communicator: the sum all-reduces that went through it so far."""
+        n, r = ctypes.c_uint32(), ctypes.c_uint32()
+        calls, nbytes = ctypes.c_uint64(), ctypes.c_uint64()
+        _check(_lib.scanrs_multi_comm_info(self._h, ctypes.c_uint32(shard), ctypes.byref(n), ctypes.byref(r), ctypes.byref(calls), ctypes.byref(nbytes)))
+        return {"nranks": int(n.value), "rank": int(r.value), "allreduce_calls": int(calls.value), "allreduce_bytes": int(nbytes.value)}
+
+    def counter(self, key: str, shard: int = 0) -> int:
+        """`scanrs_mat_get_counter` of shard `shard` (e.g. "de_shard_tests", "de_shard_allreduces")."""
+        h, v = ctypes.c_void_p(), ctypes.c_uint64()
+        _check(_lib.scanrs_multi_shard(self._h, ctypes.c_uint32(shard), ctypes.byref(h), None, None, None))
+        _check(_lib.scanrs_mat_get_counter(h, key.encode(), ctypes.byref(v)))
+        return int(v.value)
+
     def run_pca_irlba(self, k: int, tol: float = 1e-4, max_iter: int = 50, v0=None):
         u, s, v = np.zeros((self.rows, k)), np.zeros(k), np.zeros((self.cols, k))
         v0c = None if v0 is None else _f64(v0)
@@ -1174,7 +1192,7 @@ EXPORTED_SYMBOLS = [
     "scanrs_mat_dot", "scanrs_mat_rdot", "scanrs_mat_dot_u32", "scanrs_mat_rdot_u32", "scanrs_mat_dot_device",
     "scanrs_normalize", "scanrs_log_normalize", "scanrs_log1p_normalize_fixed_point", "scanrs_mat_target_umi",
     "scanrs_pca_bk", "scanrs_pca_rand", "scanrs_pca_irlba", "scanrs_pca_result_device", "scanrs_knn_device", "scanrs_omega_fill", "scanrs_mat_set_shard", "scanrs_mat_set_shard_comm", "scanrs_comm_get_unique_id", "scanrs_comm_create", "scanrs_comm_free",
-    "scanrs_multi_create", "scanrs_multi_free", "scanrs_multi_n_shards", "scanrs_multi_shard", "scanrs_multi_normalize", "scanrs_multi_pca_bk", "scanrs_multi_pca_rand", "scanrs_multi_pca_irlba", "scanrs_multi_log_normalize",
+    "scanrs_multi_create", "scanrs_multi_free", "scanrs_multi_n_shards", "scanrs_multi_shard", "scanrs_multi_normalize", "scanrs_multi_pca_bk", "scanrs_multi_pca_rand", "scanrs_multi_pca_irlba", "scanrs_multi_log_normalize", "scanrs_multi_sseq_params", "scanrs_multi_group_sums", "scanrs_multi_sseq_de", "scanrs_multi_comm_info",
     "scanrs_plan_shards", "scanrs_profile_enable", "scanrs_profile_reset", "scanrs_profile_get", "scanrs_mat_sync", "scanrs_mat_set_spmm_path", "scanrs_mat_set_option", "scanrs_set_global_option", "scanrs_mat_set_panel_precision",
     "scanrs_mat_chol_rinv", "scanrs_mat_get_counter", "scanrs_host_chol_upper", "scanrs_host_inv_upper", "scanrs_host_sym_eig", "scanrs_host_sym_eig_topk", "scanrs_debug_wait_never", "scanrs_debug_barrier_alone", "scanrs_debug_arena_selftest", "scanrs_debug_dense_route", "scanrs_debug_dense_gram", "scanrs_debug_dense_gemm", "scanrs_debug_weighted_colsum", "scanrs_init", "scanrs_release_cached_memory", "scanrs_cached_memory_bytes", "scanrs_reserve_device_memory", "scanrs_device_memory_in_use",
     "scanrs_h5_read_csc_matrix", "scanrs_h5_read_adaptive_csr_matrix", "scanrs_h5_read_matrix_metadata", "scanrs_h5_matrix_free",

@@ -1364,6 +1364,10 @@ int scanrs_mat_get_counter(scanrs_mat *m, const char *key, uint64_t *value) {
             *value = m->st->de_pairs_passes;
         else if (k == "de_pairs_literal") // ... and pairs that took the literal route
             *value = m->st->de_pairs_literal;
+        else if (k == "de_shard_tests") // the last scanrs_sseq_de* on this handle: the tests this rank launched on the device (unsharded: all of them) ...
+            *value = m->st->de_shard_tests;
+        else if (k == "de_shard_allreduces") // ... and the exchange steps of the last params / group sums / DE call (unsharded: 0)
+            *value = m->st->de_shard_allreduces;
         else if (k == "subset_masked_passes") // sums over a column list on this handle: made from the copy whose outer dimension is the result axis ...
             *value = m->st->subset_masked_passes;
         else if (k == "subset_scatter_passes") // ... and through the integer scatter from the other copy

@@ -498,6 +498,7 @@ int scanrs_merge_clusters(scanrs_mat *m, const double *pca, int pca_is_device, u
             fail(SCANRS_ERR_ARGUMENT, "trace arrays are null");
         if (ld < d) fail(SCANRS_ERR_ARGUMENT, "ld must be at least d");
         CurrentHandle cur(m->st.get());
+        sseq_refuse_sharded(m, "merge_clusters");
         bool gm = false;
         SparseCopy &cp = sseq_resident_copy(m, &gm);
         Storage &st = *m->st;

@@ -405,6 +405,7 @@ struct Storage {
     int tile_overlap = 1;                 // hybrid product: 1 = the overflow gather runs beside the tile kernel (own stream); 0 = after it (measurement)
     int panel_precision = 0;              // 0: f64 panels (default); 1: gathered panels rounded to f32, f64 sums (opt-in)
     uint64_t partition_rounds = 0;        // rounds of the last scanrs_mat_partition_on_thresholds on this handle, the final one that changes nothing included (scanrs_mat_get_counter)
+    uint64_t de_shard_tests = 0, de_shard_allreduces = 0; // the last DE call on this handle: tests this rank launched on the device, exchange steps (scanrs_mat_get_counter)
     uint64_t de_pairs_passes = 0, de_pairs_literal = 0; // the last scanrs_sseq_de_pairs on this handle: passes over the nonzeros, pairs on the literal route (scanrs_mat_get_counter)
     int subset_scatter = 1;               // integer sums over a column list when only the other orientation exists: 1 = scattered into the result with 64-bit integer atomics from the copy that exists, 0 = the missing copy is built (subset_host.cpp)
     uint64_t subset_masked_passes = 0, subset_scatter_passes = 0; // sums over a column list made so far on this handle: from the copy whose outer dimension is the result axis / through the integer scatter (scanrs_mat_get_counter)
@@ -684,6 +685,10 @@ void launch_sseq_cell_totals(Storage &st, const SparseCopy &cp, bool gene_major,
 void launch_sseq_group_pass(Storage &st, const SparseCopy &cp, bool gene_major, uint64_t n_genes, const int16_t *d_labels, uint32_t n_groups,
                             unsigned long long *d_sums, const double *d_sf, double scale1, double scale2, unsigned long long *d_mom,
                             uint32_t *d_bad);
+// sharded handles: the two 128-bit sums and the bad flag of every gene as u64 limbs (genes x SSEQ_LIMB_STRIDE) for the u64 all-reduce, and back
+constexpr uint32_t SSEQ_LIMB_STRIDE = 9;
+void launch_sseq_mom_split(Storage &st, const unsigned long long *d_mom, const uint32_t *d_bad, uint64_t n_genes, unsigned long long *d_limbs);
+void launch_sseq_mom_join(Storage &st, const unsigned long long *d_limbs, uint64_t n_genes, unsigned long long *d_mom, uint32_t *d_bad);
 void launch_sseq_exact(hipStream_t s, const SseqExactTest *d_tests, uint32_t n_tests, uint64_t n_chunks, double *d_obs, double4 *d_part,
                        double *d_p);
 void launch_sseq_asymptotic(hipStream_t s, const SseqAsymTest *d_tests, uint32_t n_tests, double *d_p);
@@ -712,9 +717,11 @@ void sseq_de_sums(hipStream_t s, uint64_t genes, uint32_t n_tests, const uint64_
 void sseq_de_sums_strided(hipStream_t s, uint64_t genes, uint32_t n_tests, const uint64_t *sums_a, const uint64_t *sums_b, const double *sf_a,
                           const double *sf_b, const double *gene_means, const double *gene_phi, const uint8_t *use_genes, uint64_t stride_g,
                           uint64_t stride_j, uint64_t big_count, const scanrs_snoop *snoop, double *p, double *p_adj, double *log2fc,
-                          double *mean_in, double *mean_out, int backend);
-// the copy DE walks: the gene-major one when it is resident, else the cell-major one (shared with merge_clusters)
+                          double *mean_in, double *mean_out, int backend, Storage *shard = nullptr);
+// the copy DE walks: the gene-major one when it is resident, else the cell-major one (shared with merge_clusters). A sharded handle is
+// served when its cells (the view's columns) are the sharded dimension; sseq_refuse_sharded is for the entry points that do not serve one.
 SCANRS_LOCAL SparseCopy &sseq_resident_copy(scanrs_mat *m, bool *gene_major);
+SCANRS_LOCAL void sseq_refuse_sharded(const scanrs_mat *m, const char *what);
 double sseq_host_exact_test(uint64_t xa, uint64_t xb, double sf_a, double sf_b, double mu, double phi);
 double sseq_host_exact_test_ratio(uint64_t xa, uint64_t xb, double sf_a, double sf_b, double mu, double phi);
 uint64_t sseq_ratio_anchor(uint64_t n, double sar, double sbr);

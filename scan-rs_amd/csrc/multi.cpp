@@ -153,6 +153,11 @@ int scanrs_multi_shard(scanrs_multi *mm, uint32_t i, scanrs_mat **shard, int *de
     return SCANRS_OK;
 }
 
+int scanrs_multi_comm_info(scanrs_multi *mm, uint32_t i, uint32_t *nranks, uint32_t *rank, uint64_t *n_allreduce, uint64_t *allreduce_bytes) {
+    if (!mm || i >= mm->comms.size()) return SCANRS_ERR_ARGUMENT;
+    return scanrs_comm_info(mm->comms[i], nranks, rank, n_allreduce, allreduce_bytes);
+}
+
 int scanrs_multi_normalize(scanrs_multi *mm, int normalization, const uint32_t *size_factors) {
     if (!mm) return SCANRS_ERR_ARGUMENT;
     return fan_out(mm, [&](size_t i) {
@@ -243,6 +248,104 @@ int scanrs_multi_log_normalize(scanrs_multi *mm, double umi_count_sum, int log_f
         const uint32_t *sf = size_factors;
         if (sf && mm->storage == SCANRS_CSC) sf += mm->bounds[i];
         return scanrs_log_normalize(mm->shards[i], umi_count_sum, log_fn, sf);
+    });
+}
+
+// ---- sSeq differential expression over the shards -----------------------------------------------------------------
+// The calls of the handle (scanrs_sseq_params, scanrs_mat_group_sums, scanrs_sseq_de_backend) on every shard at once. The cells must
+// be the sharded dimension: a genes x cells CSC matrix, or a cells x genes CSR one with transposed = 1 (every shard then goes through
+// scanrs_mat_t). Every shard gets the same global arguments and computes the same complete outputs; shard 0 writes the caller's
+// arrays, the others write into scratch of the call.
+namespace {
+
+struct ShardView { // the handle a shard's DE call runs on: the shard itself, or its transposed view for the length of the call
+    scanrs_mat *h = nullptr;
+    bool owned = false;
+    int open(scanrs_multi *mm, size_t i, int transposed) {
+        if (!transposed) {
+            h = mm->shards[i];
+            return SCANRS_OK;
+        }
+        owned = true;
+        return scanrs_mat_t(mm->shards[i], &h);
+    }
+    ~ShardView() {
+        if (owned && h) scanrs_mat_free(h);
+    }
+};
+
+int bad_argument(const char *msg) {
+    set_error("%s", msg);
+    return SCANRS_ERR_ARGUMENT;
+}
+
+} // namespace
+
+int scanrs_multi_sseq_params(scanrs_multi *mm, int transposed, double zeta_quintile, const uint64_t *cell_indices, uint64_t n_sel,
+                             const double *umi_counts, double *size_factors, double *gene_means, double *gene_variances, uint8_t *use_genes,
+                             double *gene_moment_phi, double *zeta_hat, double *delta, double *gene_phi) {
+    if (!mm || !size_factors || !gene_means || !gene_variances || !use_genes || !gene_moment_phi || !zeta_hat || !delta || !gene_phi)
+        return bad_argument("null argument");
+    const uint64_t genes = transposed ? mm->cols : mm->rows, cells = transposed ? mm->rows : mm->cols;
+    return fan_out(mm, [&](size_t i) {
+        ShardView v;
+        if (const int rc = v.open(mm, i, transposed)) return rc;
+        if (i == 0)
+            return scanrs_sseq_params(v.h, zeta_quintile, cell_indices, n_sel, umi_counts, size_factors, gene_means, gene_variances, use_genes,
+                                      gene_moment_phi, zeta_hat, delta, gene_phi);
+        const uint64_t gs = genes + 1; // never an empty vector
+        std::vector<double> sf(cells + 1), f64(4 * gs);
+        std::vector<uint8_t> use(gs);
+        double zh = 0.0, dl = 0.0;
+        return scanrs_sseq_params(v.h, zeta_quintile, cell_indices, n_sel, umi_counts, sf.data(), &f64[0], &f64[gs], use.data(), &f64[2 * gs], &zh,
+                                  &dl, &f64[3 * gs]);
+    });
+}
+
+int scanrs_multi_group_sums(scanrs_multi *mm, int transposed, const int16_t *labels, uint32_t n_groups, uint64_t *sums, uint64_t *cells_per_group) {
+    if (!mm || !labels || !sums) return bad_argument("null argument");
+    if (n_groups == 0 || n_groups > SSEQ_MAX_GROUPS) return bad_argument("n_groups must be in 1 .. 8192");
+    const uint64_t genes = transposed ? mm->cols : mm->rows;
+    return fan_out(mm, [&](size_t i) {
+        ShardView v;
+        if (const int rc = v.open(mm, i, transposed)) return rc;
+        if (i == 0) return scanrs_mat_group_sums(v.h, labels, n_groups, sums, cells_per_group);
+        std::vector<uint64_t> spare(genes * n_groups + 1);
+        return scanrs_mat_group_sums(v.h, labels, n_groups, spare.data(), nullptr);
+    });
+}
+
+int scanrs_multi_sseq_de(scanrs_multi *mm, int transposed, const int16_t *labels, uint32_t n_groups, int mode, const double *size_factors,
+                         const double *gene_means, const double *gene_phi, const uint8_t *use_genes, uint64_t big_count, int backend,
+                         const scanrs_snoop *snoop, uint64_t *sums_in, uint64_t *sums_out, double *p, double *p_adj, double *log2fc,
+                         double *mean_in, double *mean_out) {
+    if (mode != 0 && mode != 1 && mode != 2)
+        return bad_argument("mode must be 0 (one against the rest), 1 (group 0 against group 1) or 2 (each group against group 0)");
+    if (backend != SCANRS_NB_EXACT_LOGSPACE && backend != SCANRS_NB_EXACT_RATIO)
+        return bad_argument("backend must be SCANRS_NB_EXACT_LOGSPACE (0) or SCANRS_NB_EXACT_RATIO (1)");
+    if (!mm || !labels || !size_factors || !gene_means || !gene_phi || !use_genes || !sums_in || !sums_out || !p || !p_adj || !log2fc || !mean_in ||
+        !mean_out)
+        return bad_argument("null argument");
+    if (n_groups == 0 || n_groups > SSEQ_MAX_GROUPS) return bad_argument("n_groups must be in 1 .. 8192");
+    const uint64_t genes = transposed ? mm->cols : mm->rows;
+    const uint64_t total = genes * (mode == 0 ? n_groups : mode == 1 ? 1 : n_groups - 1);
+    return fan_out(mm, [&](size_t i) {
+        ShardView v;
+        if (const int rc = v.open(mm, i, transposed)) return rc;
+        scanrs_snoop sn;
+        const scanrs_snoop *psn = nullptr;
+        if (snoop) { // every shard polls the cancel flag at the same points; only shard 0 reports progress
+            sn = *snoop;
+            if (i != 0) sn.progress = nullptr;
+            psn = &sn;
+        }
+        if (i == 0)
+            return scanrs_sseq_de_backend(v.h, labels, n_groups, mode, size_factors, gene_means, gene_phi, use_genes, big_count, backend, psn, sums_in,
+                                          sums_out, p, p_adj, log2fc, mean_in, mean_out);
+        std::vector<uint64_t> u64(2 * total + 2);
+        std::vector<double> f64(5 * total + 5);
+        return scanrs_sseq_de_backend(v.h, labels, n_groups, mode, size_factors, gene_means, gene_phi, use_genes, big_count, backend, psn, &u64[0],
+                                      &u64[total + 1], &f64[0], &f64[total + 1], &f64[2 * (total + 1)], &f64[3 * (total + 1)], &f64[4 * (total + 1)]);
     });
 }
 

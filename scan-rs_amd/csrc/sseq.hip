@@ -6,6 +6,7 @@
 //   sseq_cell_major_kernel   the same sums from the cell-major copy: a wave owns a cell (one label), the sums are scattered
 //                            over the genes with u64 global atomics
 //   sseq_cell_totals_kernel  per-cell count totals (size factors) from either copy
+//   sseq_mom_split / _join   the 128-bit moments as 32-bit limbs around the u64 all-reduce of a sharded handle
 //   sseq_exact_*_kernel      the exact NB test (dist.rs:74-118, 259-310) over a flat list of fixed-size term chunks
 //   sseq_asymptotic_kernel   the beta approximation (dist.rs:226-257), one thread per test
 //   sseq_ratio_*_kernel      the Ratio backend of the exact test (dist.rs:116-215): sseq_ratio.inc
@@ -133,6 +134,44 @@ __global__ void sseq_max_u32_kernel(const uint32_t *__restrict__ v, uint64_t n, 
     for (uint64_t i = (uint64_t)blockIdx.x * blockDim.x + threadIdx.x; i < n; i += (uint64_t)gridDim.x * blockDim.x) m = max(m, v[i]);
     for (int off = 32; off > 0; off >>= 1) m = max(m, (uint32_t)__shfl_xor((int)m, off));
     if ((threadIdx.x & 63u) == 0) atomicMax(out, m);
+}
+
+// ---- the moments across shards ---------------------------------------------------------------------------------------------------
+// A sum all-reduce of u64 words would lose the carries between the two words of a 128-bit sum. Each rank therefore splits its two
+// sums per gene into 32-bit limbs held in u64 (limbs: genes x SSEQ_LIMB_STRIDE: 4 limbs of Σ x/sf, 4 of Σ (x/sf)², the bad flag);
+// the limbs of up to 2^31 ranks add up without overflow, and the join propagates the carries. The scale of the launch keeps the
+// sum over ALL cells below 2^126 (fixed128.hpp), so the top limb's carry is zero and the join is exact.
+__global__ void sseq_mom_split_kernel(const unsigned long long *__restrict__ mom, const uint32_t *__restrict__ bad, uint64_t n_genes,
+                                      unsigned long long *__restrict__ limbs) {
+    const uint64_t g = (uint64_t)blockIdx.x * blockDim.x + threadIdx.x;
+    if (g >= n_genes) return;
+    unsigned long long *out = limbs + g * SSEQ_LIMB_STRIDE;
+#pragma unroll
+    for (uint32_t w = 0; w < 4; w++) {
+        const unsigned long long v = mom[g * 4 + w];
+        out[2 * w] = v & 0xFFFFFFFFull;
+        out[2 * w + 1] = v >> 32;
+    }
+    out[8] = bad[g] ? 1ull : 0ull;
+}
+
+__global__ void sseq_mom_join_kernel(const unsigned long long *__restrict__ limbs, uint64_t n_genes, unsigned long long *__restrict__ mom,
+                                     uint32_t *__restrict__ bad) {
+    const uint64_t g = (uint64_t)blockIdx.x * blockDim.x + threadIdx.x;
+    if (g >= n_genes) return;
+    const unsigned long long *in = limbs + g * SSEQ_LIMB_STRIDE;
+#pragma unroll
+    for (uint32_t s = 0; s < 2; s++) {
+        unsigned long long c = 0, r[4];
+#pragma unroll
+        for (uint32_t k = 0; k < 4; k++) {
+            c = (c >> 32) + in[4 * s + k]; // carry < 2^32 and a limb sum < 2^63: no overflow
+            r[k] = c & 0xFFFFFFFFull;
+        }
+        mom[g * 4 + 2 * s] = r[0] | (r[1] << 32);
+        mom[g * 4 + 2 * s + 1] = r[2] | (r[3] << 32);
+    }
+    bad[g] = in[8] ? 1u : 0u;
 }
 
 // ---- exact test --------------------------------------------------------------------------------------------------------------
@@ -311,6 +350,18 @@ void launch_sseq_group_pass(Storage &st, const SparseCopy &cp, bool gene_major, 
                                    d_labels, n_groups, d_sums, d_sf, scale1, scale2, d_mom, d_bad);
         }
     }
+    SCANRS_HIP(hipGetLastError());
+}
+
+void launch_sseq_mom_split(Storage &st, const unsigned long long *d_mom, const uint32_t *d_bad, uint64_t n_genes, unsigned long long *d_limbs) {
+    if (!n_genes) return;
+    hipLaunchKernelGGL(sseq_mom_split_kernel, dim3((uint32_t)((n_genes + 255) / 256)), dim3(256), 0, st.stream, d_mom, d_bad, n_genes, d_limbs);
+    SCANRS_HIP(hipGetLastError());
+}
+
+void launch_sseq_mom_join(Storage &st, const unsigned long long *d_limbs, uint64_t n_genes, unsigned long long *d_mom, uint32_t *d_bad) {
+    if (!n_genes) return;
+    hipLaunchKernelGGL(sseq_mom_join_kernel, dim3((uint32_t)((n_genes + 255) / 256)), dim3(256), 0, st.stream, d_limbs, n_genes, d_mom, d_bad);
     SCANRS_HIP(hipGetLastError());
 }
 

@@ -27,6 +27,39 @@ static void h2d(T *d, const T *h, size_t n, hipStream_t s) {
     if (n) SCANRS_HIP(hipMemcpyAsync(d, h, n * sizeof(T), hipMemcpyHostToDevice, s));
 }
 
+// ---- sharded handles ---------------------------------------------------------------------------------------------
+// The cells are the sharded dimension: the copy holds the cells [begin, begin + n_local) of `global`, and every per-cell argument
+// spans the whole matrix. All sums that cross the shards are integers and go through allreduce_u64: they come out bit for bit as
+// the sums of the unsharded handle, whatever the number of shards and whichever transport carries them.
+struct CellRange {
+    uint64_t begin, n_local, global;
+};
+static CellRange cell_range(const Storage &st, uint64_t cells_local) {
+    if (!st.shard.active()) return CellRange{0, cells_local, cells_local};
+    return CellRange{st.shard.outer_begin, cells_local, st.shard.outer_global};
+}
+// one exchange step (counter "de_shard_allreduces")
+static void exchange_u64(Storage &st, unsigned long long *d, uint64_t count) {
+    if (!st.shard.active() || count == 0) return;
+    allreduce_u64(st, d, count);
+    st.de_shard_allreduces++;
+}
+// the largest count of the whole matrix: the all-reduce only sums, so every rank puts its maximum into its own slot of a zeroed array
+static uint32_t sseq_max_count_global(Storage &st, const SparseCopy &cp) {
+    const uint32_t mine = sseq_max_count(st, cp);
+    if (!st.shard.active()) return mine;
+    const uint32_t world = st.shard.world;
+    unsigned long long *d = st.scratch.get<unsigned long long>("sseq_max_world", world);
+    std::vector<unsigned long long> slots(world, 0ull);
+    slots[st.shard.rank] = mine;
+    h2d(d, slots.data(), world, st.stream);
+    SCANRS_SYNC(st.stream); // `slots` is pageable and goes out of use below
+    exchange_u64(st, d, world);
+    SCANRS_D2H(slots.data(), d, world * 8, st.stream);
+    SCANRS_SYNC(st.stream);
+    return (uint32_t)*std::max_element(slots.begin(), slots.end());
+}
+
 // ---- stat.rs ----------------------------------------------------------------------------------------------------------------
 // percentile_of_sorted (stat.rs:140-162): linear interpolation between the neighbouring ranks
 static double percentile_of_sorted(const std::vector<double> &s, double pct) {
@@ -200,16 +233,18 @@ static void check_labels(const int16_t *labels, uint64_t cells, uint32_t n_group
 
 void sseq_group_sums(Storage &st, const SparseCopy &cp, bool gene_major, uint64_t genes, uint64_t cells, const int16_t *labels,
                      uint32_t n_groups, uint64_t *sums, uint64_t *cells_per_group) {
-    check_labels(labels, cells, n_groups);
-    int16_t *d_lab = st.scratch.get<int16_t>("sseq_labels", std::max<uint64_t>(1, cells));
+    const CellRange cr = cell_range(st, cells); // labels: one per cell of the whole matrix; the device gets this rank's slice
+    check_labels(labels, cr.global, n_groups);
+    int16_t *d_lab = st.scratch.get<int16_t>("sseq_labels", std::max<uint64_t>(1, cr.n_local));
     unsigned long long *d_sums = st.scratch.get<unsigned long long>("sseq_sums", std::max<uint64_t>(1, genes * n_groups));
-    h2d(d_lab, labels, cells, st.stream);
+    h2d(d_lab, labels + cr.begin, cr.n_local, st.stream);
     launch_sseq_group_pass(st, cp, gene_major, genes, d_lab, n_groups, d_sums, nullptr, 1.0, 1.0, nullptr, nullptr);
+    exchange_u64(st, d_sums, genes * n_groups);
     if (genes) SCANRS_D2H(sums, d_sums, genes * n_groups * 8, st.stream);
     SCANRS_SYNC(st.stream);
     if (cells_per_group) {
         std::fill(cells_per_group, cells_per_group + n_groups, 0);
-        for (uint64_t c = 0; c < cells; c++)
+        for (uint64_t c = 0; c < cr.global; c++)
             if (labels[c] >= 0) cells_per_group[labels[c]]++;
     }
 }
@@ -218,6 +253,10 @@ void sseq_group_sums(Storage &st, const SparseCopy &cp, bool gene_major, uint64_
 void sseq_params(Storage &st, const SparseCopy &cp, bool gene_major, uint64_t genes, uint64_t cells, double zeta_quintile,
                  const uint64_t *cell_indices, uint64_t n_sel, const double *umi_counts, double *size_factors, double *gene_means,
                  double *gene_variances, uint8_t *use_genes, double *gene_moment_phi, double *zeta_hat, double *delta, double *gene_phi) {
+    // sharded: `cells` from here on is the whole matrix (cell_indices, umi_counts and size_factors span it); the host folds below run
+    // replicated over the global arrays in cell order, the device gets the slice [cr.begin, cr.begin + cr.n_local)
+    const CellRange cr = cell_range(st, cells);
+    cells = cr.global;
     if (cell_indices)
         for (uint64_t i = 0; i < n_sel; i++)
             if (cell_indices[i] >= cells) fail(SCANRS_ERR_ARGUMENT, "cell index %llu out of range", (unsigned long long)cell_indices[i]);
@@ -229,7 +268,9 @@ void sseq_params(Storage &st, const SparseCopy &cp, bool gene_major, uint64_t ge
         for (uint64_t i = 0; i < m; i++) counts[i] = umi_counts[i];
     } else {
         unsigned long long *d_tot = st.scratch.get<unsigned long long>("sseq_totals", std::max<uint64_t>(1, cells));
-        launch_sseq_cell_totals(st, cp, gene_major, cells, d_tot);
+        if (st.shard.active()) SCANRS_HIP(hipMemsetAsync(d_tot, 0, std::max<uint64_t>(1, cells) * 8, st.stream)); // the other ranks' slices
+        launch_sseq_cell_totals(st, cp, gene_major, cr.n_local, d_tot + cr.begin);
+        exchange_u64(st, d_tot, cells);
         std::vector<unsigned long long> tot(cells);
         if (cells) SCANRS_D2H(tot.data(), d_tot, cells * 8, st.stream);
         SCANRS_SYNC(st.stream);
@@ -248,17 +289,25 @@ void sseq_params(Storage &st, const SparseCopy &cp, bool gene_major, uint64_t ge
         sf_dev[c] = std::isnan(sf[c]) ? 0.0 : sf[c];
         if (lab[c] == 0 && sf_dev[c] > 0.0) max_inv = std::max(max_inv, 1.0 / sf_dev[c]);
     }
-    const double max_count = (double)sseq_max_count(st, cp);
+    const double max_count = (double)sseq_max_count_global(st, cp);
     const double b1 = (double)m * max_count * max_inv;
     const double scale1 = fixed_scale(b1), scale2 = fixed_scale(b1 * max_count * max_inv);
-    int16_t *d_lab = st.scratch.get<int16_t>("sseq_labels", std::max<uint64_t>(1, cells));
-    double *d_sf = st.scratch.get<double>("sseq_sf", std::max<uint64_t>(1, cells));
+    int16_t *d_lab = st.scratch.get<int16_t>("sseq_labels", std::max<uint64_t>(1, cr.n_local));
+    double *d_sf = st.scratch.get<double>("sseq_sf", std::max<uint64_t>(1, cr.n_local));
     unsigned long long *d_sums = st.scratch.get<unsigned long long>("sseq_sums", std::max<uint64_t>(1, genes));
     unsigned long long *d_mom = st.scratch.get<unsigned long long>("sseq_mom", std::max<uint64_t>(1, genes * 4));
     uint32_t *d_bad = st.scratch.get<uint32_t>("sseq_bad", std::max<uint64_t>(1, genes));
-    h2d(d_lab, lab.data(), cells, st.stream);
-    h2d(d_sf, sf_dev.data(), cells, st.stream);
+    h2d(d_lab, lab.data() + cr.begin, cr.n_local, st.stream);
+    h2d(d_sf, sf_dev.data() + cr.begin, cr.n_local, st.stream);
     launch_sseq_group_pass(st, cp, gene_major, genes, d_lab, 1, d_sums, d_sf, scale1, scale2, d_mom, d_bad);
+    if (st.shard.active() && genes) {
+        // the scales come from bounds of the sums over ALL cells (m, the global maximum count, the global 1 / sf): every rank rounds its
+        // terms to the same quantum and the joined limbs are the 128-bit sums of the unsharded pass
+        unsigned long long *d_limbs = st.scratch.get<unsigned long long>("sseq_limbs", genes * SSEQ_LIMB_STRIDE);
+        launch_sseq_mom_split(st, d_mom, d_bad, genes, d_limbs);
+        exchange_u64(st, d_limbs, genes * SSEQ_LIMB_STRIDE);
+        launch_sseq_mom_join(st, d_limbs, genes, d_mom, d_bad);
+    }
     std::vector<unsigned long long> mom(genes * 4);
     std::vector<uint32_t> bad(genes);
     if (genes) {
@@ -292,12 +341,20 @@ void sseq_params(Storage &st, const SparseCopy &cp, bool gene_major, uint64_t ge
 void sseq_de_sums_strided(hipStream_t s, uint64_t genes, uint32_t n_tests, const uint64_t *sums_a, const uint64_t *sums_b, const double *sf_a,
                           const double *sf_b, const double *gene_means, const double *gene_phi, const uint8_t *use_genes, uint64_t stride_g,
                           uint64_t stride_j, uint64_t big_count, const scanrs_snoop *snoop, double *p, double *p_adj, double *log2fc,
-                          double *mean_in, double *mean_out, int backend) {
+                          double *mean_in, double *mean_out, int backend, Storage *shard) {
     auto at = [&](uint64_t g, uint32_t j) { return g * stride_g + j * stride_j; };
     if (backend != SCANRS_NB_EXACT_LOGSPACE && backend != SCANRS_NB_EXACT_RATIO)
         fail(SCANRS_ERR_ARGUMENT, "backend must be SCANRS_NB_EXACT_LOGSPACE (0) or SCANRS_NB_EXACT_RATIO (1)");
     const bool ratio = backend == SCANRS_NB_EXACT_RATIO;
     const uint64_t total = genes * n_tests;
+    // A sharded handle: rank r builds and launches the tests of the genes [G r / W, G (r + 1) / W) only and leaves the rest
+    // of its device p array zero; one u64 all-reduce over the bit patterns then gathers them (each element is written by exactly one
+    // rank: the sum is a copy). Every rank classifies every test, so the tests settled on the host stay replicated.
+    const bool sharded = shard && shard->shard.active();
+    const uint64_t g_lo = sharded ? genes * shard->shard.rank / shard->shard.world : 0;
+    const uint64_t g_hi = sharded ? genes * (shard->shard.rank + 1) / shard->shard.world : genes;
+    std::vector<uint64_t> elsewhere; // outputs of the tests that other ranks launch
+    uint64_t n_mine = 0;
     std::vector<SseqExactTest> ex;
     std::vector<SseqAsymTest> as;
     std::vector<SseqRatioTest> rt;
@@ -314,13 +371,19 @@ void sseq_de_sums_strided(hipStream_t s, uint64_t genes, uint32_t n_tests, const
         for (uint32_t j = 0; j < n_tests; j++) {
             const uint64_t o = g * n_tests + j, xa = sums_a[o], xb = sums_b[o];
             const double fa = sf_a[j], fb = sf_b[j], mu = gene_means[at(g, j)], phi = gene_phi[at(g, j)];
-            if (use_genes[at(g, j)] && xa > big_count && xb > big_count) {
-                as.push_back(SseqAsymTest{xa, xb, fa, fb, mu, phi, o});
+            const bool asym = use_genes[at(g, j)] && xa > big_count && xb > big_count;
+            // nb_exact_test's early returns (dist.rs:76-86)
+            if (!asym && (xa + xb == 0 || phi == 0.0 || fa == 0.0 || fb == 0.0)) {
+                p[o] = 1.0;
                 continue;
             }
-            // nb_exact_test's early returns (dist.rs:76-86)
-            if (xa + xb == 0 || phi == 0.0 || fa == 0.0 || fb == 0.0) {
-                p[o] = 1.0;
+            if (g < g_lo || g >= g_hi) {
+                elsewhere.push_back(o);
+                continue;
+            }
+            n_mine++;
+            if (asym) {
+                as.push_back(SseqAsymTest{xa, xb, fa, fb, mu, phi, o});
                 continue;
             }
             if (!ratio) {
@@ -335,9 +398,13 @@ void sseq_de_sums_strided(hipStream_t s, uint64_t genes, uint32_t n_tests, const
         }
     }
     if (ex.size() > 0xFFFFFFFFull || as.size() > 0xFFFFFFFFull || rt.size() > 0xFFFFFFFFull) fail(SCANRS_ERR_ARGUMENT, "too many tests in one call");
+    if (shard) shard->de_shard_tests = n_mine;
+    // one p array for both stages: a test that falls back from Ratio is overwritten by its LogSpace result
+    DevBuf<double> d_p;
+    if (!rt.empty() || !ex.empty() || !as.empty() || (sharded && total)) d_p.alloc(total);
+    if (sharded && total) SCANRS_HIP(hipMemsetAsync(d_p.p, 0, total * 8, s));
     if (!rt.empty()) {
         // Ratio: the tests it can partition get their p-value; the others come back as SSEQ_RATIO_FALLBACK and join the LogSpace list
-        DevBuf<double> d_p(total);
         DevBuf<SseqRatioTest> d_rt(rt.size());
         DevBuf<double> d_obs(rt.size()), d_scale(n_rchunks);
         DevBuf<double2> d_part(n_rchunks);
@@ -354,7 +421,6 @@ void sseq_de_sums_strided(hipStream_t s, uint64_t genes, uint32_t n_tests, const
         }
     }
     if (!ex.empty() || !as.empty()) {
-        DevBuf<double> d_p(total);
         DevBuf<SseqExactTest> d_ex(std::max<size_t>(1, ex.size()));
         DevBuf<SseqAsymTest> d_as(std::max<size_t>(1, as.size()));
         DevBuf<double> d_obs(std::max<size_t>(1, ex.size()));
@@ -368,6 +434,15 @@ void sseq_de_sums_strided(hipStream_t s, uint64_t genes, uint32_t n_tests, const
         SCANRS_SYNC(s);
         for (const auto &t : ex) p[t.out] = pd[t.out];
         for (const auto &t : as) p[t.out] = pd[t.out];
+    }
+    if (sharded && total) {
+        static_assert(sizeof(double) == sizeof(unsigned long long), "p-values travel as their bit patterns");
+        allreduce_u64(*shard, reinterpret_cast<unsigned long long *>(d_p.p), total);
+        shard->de_shard_allreduces++;
+        std::vector<double> pd(total);
+        SCANRS_D2H(pd.data(), d_p.p, total * 8, s);
+        SCANRS_SYNC(s);
+        for (const uint64_t o : elsewhere) p[o] = pd[o];
     }
     sseq_progress(snoop, 0.75);
     // BH over the tested genes only
@@ -419,6 +494,8 @@ void sseq_de_matrix(Storage &st, const SparseCopy &cp, bool gene_major, uint64_t
     if (mode != 0 && n_groups < 2) fail(SCANRS_ERR_ARGUMENT, "mode %d needs groups 0 and 1", mode);
     if (backend != SCANRS_NB_EXACT_LOGSPACE && backend != SCANRS_NB_EXACT_RATIO)
         fail(SCANRS_ERR_ARGUMENT, "backend must be SCANRS_NB_EXACT_LOGSPACE (0) or SCANRS_NB_EXACT_RATIO (1)");
+    const uint64_t cells_local = cells;
+    cells = cell_range(st, cells_local).global; // labels and size_factors span the whole matrix; the folds below run replicated
     check_labels(labels, cells, n_groups);
     const uint32_t n_tests = mode == 0 ? n_groups : mode == 1 ? 1 : n_groups - 1;
     sseq_progress(snoop, 0.0);
@@ -450,7 +527,7 @@ void sseq_de_matrix(Storage &st, const SparseCopy &cp, bool gene_major, uint64_t
     }
     sseq_progress(snoop, 0.1);
     std::vector<uint64_t> sums(genes * n_groups);
-    sseq_group_sums(st, cp, gene_major, genes, cells, labels, n_groups, sums.data(), nullptr);
+    sseq_group_sums(st, cp, gene_major, genes, cells_local, labels, n_groups, sums.data(), nullptr);
     for (uint64_t g = 0; g < genes; g++) {
         const uint64_t *row = &sums[g * n_groups];
         if (mode == 0) {
@@ -471,14 +548,15 @@ void sseq_de_matrix(Storage &st, const SparseCopy &cp, bool gene_major, uint64_t
         }
     }
     sseq_progress(snoop, 0.6);
-    sseq_de_sums(st.stream, genes, n_tests, sums_in, sums_out, fa.data(), fb.data(), gene_means, gene_phi, use_genes, big_count, snoop, p, p_adj,
-                 log2fc, mean_in, mean_out, backend);
+    sseq_de_sums_strided(st.stream, genes, n_tests, sums_in, sums_out, fa.data(), fb.data(), gene_means, gene_phi, use_genes, 1, 0, big_count, snoop,
+                         p, p_adj, log2fc, mean_in, mean_out, backend, &st);
 }
 
 // the copy DE walks: the gene-major one when it is resident, else the cell-major one (no transposition is built for DE)
 SparseCopy &sseq_resident_copy(scanrs_mat *m, bool *gene_major) {
     Storage &st = *m->st;
-    if (st.shard.active()) fail(SCANRS_ERR_ARGUMENT, "differential expression of a sharded handle is not supported");
+    if (st.shard.active() && !cols_sharded(m))
+        fail(SCANRS_ERR_ARGUMENT, "differential expression of a sharded handle needs the cells (the view's columns) as the sharded dimension: this handle is sharded over the genes");
     const bool want_base_rows = !m->transposed; // genes = view rows
     const bool primary_rows = st.storage == SCANRS_CSR;
     if (primary_rows == want_base_rows) {
@@ -491,6 +569,10 @@ SparseCopy &sseq_resident_copy(scanrs_mat *m, bool *gene_major) {
     }
     *gene_major = false;
     return st.primary;
+}
+
+void sseq_refuse_sharded(const scanrs_mat *m, const char *what) {
+    if (m->st->shard.active()) fail(SCANRS_ERR_ARGUMENT, "%s of a sharded handle is not supported", what);
 }
 
 } // namespace scanrs
@@ -510,6 +592,7 @@ int scanrs_sseq_params(scanrs_mat *m, double zeta_quintile, const uint64_t *cell
         CurrentHandle cur(m->st.get());
         bool gm = false;
         SparseCopy &cp = sseq_resident_copy(m, &gm);
+        m->st->de_shard_tests = m->st->de_shard_allreduces = 0;
         sseq_params(*m->st, cp, gm, m->rows(), m->cols(), zeta_quintile, cell_indices, n_sel, umi_counts, size_factors, gene_means,
                     gene_variances, use_genes, gene_moment_phi, zeta_hat, delta, gene_phi);
     });
@@ -530,6 +613,7 @@ int scanrs_mat_group_sums(scanrs_mat *m, const int16_t *labels, uint32_t n_group
         CurrentHandle cur(m->st.get());
         bool gm = false;
         SparseCopy &cp = sseq_resident_copy(m, &gm);
+        m->st->de_shard_tests = m->st->de_shard_allreduces = 0;
         sseq_group_sums(*m->st, cp, gm, m->rows(), m->cols(), labels, n_groups, sums, cells_per_group);
     });
 }
@@ -544,6 +628,7 @@ int scanrs_sseq_de_backend(scanrs_mat *m, const int16_t *labels, uint32_t n_grou
         CurrentHandle cur(m->st.get());
         bool gm = false;
         SparseCopy &cp = sseq_resident_copy(m, &gm);
+        m->st->de_shard_tests = m->st->de_shard_allreduces = 0;
         sseq_de_matrix(*m->st, cp, gm, m->rows(), m->cols(), labels, n_groups, mode, size_factors, gene_means, gene_phi, use_genes, big_count,
                        snoop, sums_in, sums_out, p, p_adj, log2fc, mean_in, mean_out, backend);
     });

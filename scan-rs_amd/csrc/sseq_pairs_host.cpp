@@ -254,6 +254,7 @@ int scanrs_sseq_de_pairs(scanrs_mat *m, const int16_t *labels, uint32_t n_groups
             fail(SCANRS_ERR_ARGUMENT, "null argument");
         if (!(zeta_quintile >= 0.0 && zeta_quintile <= 1.0)) fail(SCANRS_ERR_ARGUMENT, "zeta_quintile must be in [0, 1]");
         CurrentHandle cur(m->st.get());
+        sseq_refuse_sharded(m, "batched pairwise differential expression");
         bool gm = false;
         SparseCopy &cp = sseq_resident_copy(m, &gm);
         sseq_de_pairs(*m->st, cp, gm, m->rows(), m->cols(), labels, n_groups, pair_a, pair_b, n_pairs, zeta_quintile, big_count, backend, snoop,

@@ -3,6 +3,11 @@
 Rows of the handle are genes, columns are cells (the reference's feature x barcode matrix); a cell-major handle is used
 through ``.t()``. DE reads the stored u32 counts and ignores the handle's map and offset. The passes over the nonzeros and
 the tests run on the device through ``include/scanrs_amd.h``; the O(genes) finishing steps run in the library's host code.
+
+``compute_sseq_params``, ``group_sums``, ``sseq_differential_expression``, ``sseq_de_one_vs_rest`` and ``sseq_de_vs_control`` also
+take a ``MultiMat`` (or a sharded ``AdaptiveMat``) whose cells are the sharded dimension: a genes x cells CSC ``MultiMat``, or a
+cells x genes CSR one with ``transposed=True``. All per-cell arguments then span the whole matrix and every result equals the
+unsharded call bit for bit.
 """
 from __future__ import annotations
 
@@ -12,7 +17,7 @@ from typing import List, Optional, Sequence
 
 import numpy as np
 
-from . import AdaptiveMat, ScanrsError, _check, _lib, _p
+from . import AdaptiveMat, MultiMat, ScanrsError, _check, _lib, _p
 
 BIG_COUNT_DEFAULT = 900  # diff_exp.rs:15
 ZETA_QUINTILE_DEFAULT = 0.995  # diff_exp.rs:17
@@ -54,9 +59,24 @@ class DiffExpResult:
     log2_fold_change: np.ndarray
 
 
-def compute_sseq_params(mat: AdaptiveMat, zeta_quintile: float = ZETA_QUINTILE_DEFAULT, cell_indices=None, umi_counts=None) -> SSeqParams:
-    """`compute_sseq_params` (diff_exp.rs:458-500)."""
+def _shape(mat, transposed: bool):
+    """(genes, cells) of the WHOLE matrix: of a MultiMat (transposed: created cells x genes), of a handle, or of a sharded handle,
+    whose own column count is its slice of the cells."""
+    if isinstance(mat, MultiMat):
+        return (mat.cols, mat.rows) if transposed else (mat.rows, mat.cols)
+    if transposed:
+        raise ScanrsError(6, "transposed is for a MultiMat; use .t() on an AdaptiveMat")
     genes, cells = mat.shape()
+    # a sharded handle (set_shard*) whose outer vectors are the view's columns holds a slice of the cells; one sharded over the genes is
+    # refused by the library
+    if getattr(mat, "_outer_global", None) is not None and mat.storage() == 1:
+        cells = mat._outer_global
+    return genes, cells
+
+
+def compute_sseq_params(mat, zeta_quintile: float = ZETA_QUINTILE_DEFAULT, cell_indices=None, umi_counts=None, transposed: bool = False) -> SSeqParams:
+    """`compute_sseq_params` (diff_exp.rs:458-500). mat: an AdaptiveMat or a MultiMat (see the module's docstring)."""
+    genes, cells = _shape(mat, transposed)
     ci = None if cell_indices is None else np.ascontiguousarray(cell_indices, dtype=np.uint64)
     n_sel = cells if ci is None else len(ci)
     um = None
@@ -67,8 +87,12 @@ def compute_sseq_params(mat: AdaptiveMat, zeta_quintile: float = ZETA_QUINTILE_D
     sf, mean, var, phi_mm, phi = (np.zeros(cells), np.zeros(genes), np.zeros(genes), np.zeros(genes), np.zeros(genes))
     use = np.zeros(genes, dtype=np.uint8)
     zh, dl = _f64c(), _f64c()
-    _check(_lib.scanrs_sseq_params(mat._h, _f64c(zeta_quintile), _p(ci), _u64(0 if ci is None else len(ci)), _p(um), _p(sf), _p(mean), _p(var),
-                                   _p(use), _p(phi_mm), ctypes.byref(zh), ctypes.byref(dl), _p(phi)))
+    args = (_f64c(zeta_quintile), _p(ci), _u64(0 if ci is None else len(ci)), _p(um), _p(sf), _p(mean), _p(var), _p(use), _p(phi_mm),
+            ctypes.byref(zh), ctypes.byref(dl), _p(phi))
+    if isinstance(mat, MultiMat):
+        _check(_lib.scanrs_multi_sseq_params(mat._h, ctypes.c_int(int(transposed)), *args))
+    else:
+        _check(_lib.scanrs_sseq_params(mat._h, *args))
     return SSeqParams(n_sel, genes, sf, mean, var, use.astype(bool), phi_mm, zh.value, dl.value, phi)
 
 
@@ -93,14 +117,17 @@ def _labels(labels, cells: int) -> np.ndarray:
     return np.ascontiguousarray(lab, dtype=np.int16)
 
 
-def group_sums(mat: AdaptiveMat, labels, n_groups: int):
+def group_sums(mat, labels, n_groups: int, transposed: bool = False):
     """Per (gene, group) u64 count sums in one pass over the nonzeros (sum_rows / sum_rows_dual, sqz/src/mat.rs:449-610,
     generalised to many groups) and the number of cells per group. labels: per cell, -1 = in no group."""
-    genes, cells = mat.shape()
+    genes, cells = _shape(mat, transposed)
     lab = _labels(labels, cells)
     sums = np.zeros((genes, n_groups), dtype=np.uint64)
     cnt = np.zeros(n_groups, dtype=np.uint64)
-    _check(_lib.scanrs_mat_group_sums(mat._h, _p(lab), _u32(n_groups), _p(sums), _p(cnt)))
+    if isinstance(mat, MultiMat):
+        _check(_lib.scanrs_multi_group_sums(mat._h, ctypes.c_int(int(transposed)), _p(lab), _u32(n_groups), _p(sums), _p(cnt)))
+    else:
+        _check(_lib.scanrs_mat_group_sums(mat._h, _p(lab), _u32(n_groups), _p(sums), _p(cnt)))
     return sums, cnt
 
 
@@ -133,8 +160,8 @@ def _backend(backend) -> int:
     return int(backend)
 
 
-def _de_matrix(mat, labels, n_groups, mode, params, big_count, snoop, backend=NB_EXACT_LOGSPACE):
-    genes, cells = mat.shape()
+def _de_matrix(mat, labels, n_groups, mode, params, big_count, snoop, backend=NB_EXACT_LOGSPACE, transposed=False):
+    genes, cells = _shape(mat, transposed)
     lab = _labels(labels, cells)
     mean, phi, use = _params_arrays(params, genes)
     sf = np.ascontiguousarray(params.size_factors, dtype=np.float64)
@@ -145,8 +172,12 @@ def _de_matrix(mat, labels, n_groups, mode, params, big_count, snoop, backend=NB
     p, padj, l2, mi, mo = (np.zeros((genes, t)) for _ in range(5))
     sn, _keep = _snoop_arg(snoop)
     bc = BIG_COUNT_DEFAULT if big_count is None else int(big_count)
-    _check(_lib.scanrs_sseq_de_backend(mat._h, _p(lab), _u32(n_groups), ctypes.c_int(mode), _p(sf), _p(mean), _p(phi), _p(use), _u64(bc),
-                                       ctypes.c_int(_backend(backend)), sn, _p(si), _p(so), _p(p), _p(padj), _p(l2), _p(mi), _p(mo)))
+    args = (_p(lab), _u32(n_groups), ctypes.c_int(mode), _p(sf), _p(mean), _p(phi), _p(use), _u64(bc), ctypes.c_int(_backend(backend)), sn, _p(si),
+            _p(so), _p(p), _p(padj), _p(l2), _p(mi), _p(mo))
+    if isinstance(mat, MultiMat):
+        _check(_lib.scanrs_multi_sseq_de(mat._h, ctypes.c_int(int(transposed)), *args))
+    else:
+        _check(_lib.scanrs_sseq_de_backend(mat._h, *args))
     return _results(params, si, so, p, padj, l2, mi, mo)
 
 
@@ -161,32 +192,32 @@ def _index_list(v, cells: int, name: str) -> np.ndarray:
     return a
 
 
-def sseq_differential_expression(mat: AdaptiveMat, cond_a: Sequence[int], cond_b: Sequence[int], params: SSeqParams, big_count: Optional[int] = None,
-                                 snoop=None, backend: int = NB_EXACT_LOGSPACE) -> DiffExpResult:
+def sseq_differential_expression(mat, cond_a: Sequence[int], cond_b: Sequence[int], params: SSeqParams, big_count: Optional[int] = None,
+                                 snoop=None, backend: int = NB_EXACT_LOGSPACE, transposed: bool = False) -> DiffExpResult:
     """`sseq_differential_expression` (diff_exp.rs:68-175): cells of cond_a against cells of cond_b. The lists must be sorted,
     free of duplicates and disjoint (the reference assumes sorted lists without checking). backend: the exact test's kernel
     (`sseq_differential_expression_backend`, diff_exp.rs:125-161)."""
-    genes, cells = mat.shape()
+    genes, cells = _shape(mat, transposed)
     a, b = _index_list(cond_a, cells, "cond_a"), _index_list(cond_b, cells, "cond_b")
     if np.intersect1d(a, b).size:
         raise ScanrsError(6, "cond_a and cond_b overlap")
     lab = np.full(cells, -1, dtype=np.int16)
     lab[a], lab[b] = 0, 1
-    return _de_matrix(mat, lab, 2, 1, params, big_count, snoop, backend)[0]
+    return _de_matrix(mat, lab, 2, 1, params, big_count, snoop, backend, transposed)[0]
 
 
-def sseq_de_one_vs_rest(mat: AdaptiveMat, labels, params: SSeqParams, big_count: Optional[int] = None, n_groups: Optional[int] = None,
-                        snoop=None, backend: int = NB_EXACT_LOGSPACE) -> List[DiffExpResult]:
+def sseq_de_one_vs_rest(mat, labels, params: SSeqParams, big_count: Optional[int] = None, n_groups: Optional[int] = None,
+                        snoop=None, backend: int = NB_EXACT_LOGSPACE, transposed: bool = False) -> List[DiffExpResult]:
     """Every group against all other labelled cells (Cell Ranger's per-cluster DE over `initial_cluster_assignments`,
     diff-exp/src/utils.rs:77-117). labels: per cell, the group 0 .. n_groups - 1 or -1 (in no group)."""
     lab = np.asarray(labels)
     if n_groups is None:
         n_groups = int(lab.max()) + 1 if lab.size else 0
-    return _de_matrix(mat, lab, n_groups, 0, params, big_count, snoop, backend)
+    return _de_matrix(mat, lab, n_groups, 0, params, big_count, snoop, backend, transposed)
 
 
-def sseq_de_vs_control(mat: AdaptiveMat, labels, params: SSeqParams, control: int = 0, big_count: Optional[int] = None,
-                       n_groups: Optional[int] = None, snoop=None, backend: int = NB_EXACT_LOGSPACE) -> List[DiffExpResult]:
+def sseq_de_vs_control(mat, labels, params: SSeqParams, control: int = 0, big_count: Optional[int] = None,
+                       n_groups: Optional[int] = None, snoop=None, backend: int = NB_EXACT_LOGSPACE, transposed: bool = False) -> List[DiffExpResult]:
     """Every other group against the group `control` (the shared-control shape of Cell Ranger's batched DE): one pass over the
     nonzeros, the control's sums and size factor computed once. Returns one DiffExpResult per group other than the control, in
     group order; each equals `sseq_differential_expression(mat, cells of the group, cells of the control, ...)` bit for bit.
@@ -199,7 +230,7 @@ def sseq_de_vs_control(mat: AdaptiveMat, labels, params: SSeqParams, control: in
     if control != 0:
         # the library tests against group 0: the control becomes group 0 and the groups below it move up by one
         lab = np.where(lab == control, 0, np.where((lab >= 0) & (lab < control), lab + 1, lab))
-    return _de_matrix(mat, lab, n_groups, 2, params, big_count, snoop, backend)
+    return _de_matrix(mat, lab, n_groups, 2, params, big_count, snoop, backend, transposed)
 
 
 class _PairParams(ctypes.Structure):

@@ -3,6 +3,14 @@ cell-major): ms for the parameters, the group pass and the tests, the exact-bran
 branches, and the group pass's one-pass bytes (8 nnz + 2 cells) against HBM. One JSON line.
 
     python tools/de_bench.py [--cells 1000000] [--genes 33000] [--groups 20] [--reps 3] [--backend {logspace,ratio}]
+                             [--shards N [--devices a,b,...]]
+
+The line carries `one_vs_rest_call_ms`, every repeat of the whole sseq_de_one_vs_rest call on the single handle. With --shards N a
+second JSON line follows: the same matrix cut over N shards of a MultiMat (`--devices`: one id per shard, default all on device
+0, which measures the overhead of the scheme, not a speed-up), the repeats of its sseq_de_one_vs_rest call, its grouped pass
+(group_sums), the rest of the call (the test stage: the split tests, the gather of the p-values and the replicated host steps),
+the tests each shard launched, the exchange steps and bytes per shard from scanrs_comm_info, and whether every field equals the
+single handle's bit for bit.
 
 With --control-conditions N the labels are a shared control instead: group 0 holds half the cells, the other half is spread
 over N conditions, and every condition is tested against the control (mode 2, sseq_de_vs_control). The line then carries the
@@ -37,6 +45,8 @@ def main():
     ap.add_argument("--backend", choices=("logspace", "ratio"), default="logspace")
     ap.add_argument("--control-conditions", type=int, default=0)
     ap.add_argument("--per-pair-params", action="store_true", help="with --control-conditions: also time sseq_de_pairs and the per-pair literal calls")
+    ap.add_argument("--shards", type=int, default=0, help="also run one-vs-rest DE over this many shards of a MultiMat")
+    ap.add_argument("--devices", type=str, default="", help="with --shards: comma-separated device id per shard (default: all on device 0)")
     a = ap.parse_args()
     backend = sa.NB_EXACT_RATIO if a.backend == "ratio" else sa.NB_EXACT_LOGSPACE
     import torch
@@ -69,6 +79,11 @@ def main():
     sf_b = params.size_factors.sum() - sf_a
     rest = allsum[:, None] - sums
     t_tests, _ = timed(lambda: sa.sseq_de_from_sums(sums, rest, sf_a, sf_b, params, backend=backend))
+    calls, whole = [], None
+    for _ in range(a.reps):
+        t0 = time.perf_counter()
+        whole = sa.sseq_de_one_vs_rest(m, labels, params, n_groups=a.groups, backend=backend)
+        calls.append(round((time.perf_counter() - t0) * 1e3, 2))
     big = 900
     use = params.use_genes[:, None]
     asym = use & (sums > big) & (rest > big)
@@ -79,11 +94,46 @@ def main():
     extra = {} if backend == sa.NB_EXACT_LOGSPACE else {"backend": a.backend, "ratio_fallback_tests": ratio_fallbacks(sums, rest, sf_a, sf_b, params, exact)}
     print(json.dumps({
         "cells": a.cells, "genes": a.genes, "nnz": nnz, "groups": a.groups, **extra,
-        "params_ms": round(t_params, 2), "group_pass_ms": round(t_pass, 2), "tests_ms": round(t_tests, 2),
+        "params_ms": round(t_params, 2), "group_pass_ms": round(t_pass, 2), "tests_ms": round(t_tests, 2), "one_vs_rest_call_ms": calls,
         "tests": int(a.genes * a.groups), "exact_tests": int(exact.sum()), "asymptotic_tests": int(asym.sum()), "early_return_tests": int((trivial & ~asym).sum()),
         "exact_terms": terms,
         "group_pass_bytes": one_pass, "group_pass_hbm_floor_ms": round(one_pass / HBM_BYTES_PER_S * 1e3, 3),
-    }))
+    }), flush=True)
+    if a.shards:
+        sharded_leg(a, (ip, ix, vv), labels, params, whole, backend, timed)
+
+
+def sharded_leg(a, triplet, labels, params, whole, backend, timed):
+    devices = [int(d) for d in a.devices.split(",")] if a.devices else [0] * a.shards
+    if len(devices) != a.shards:
+        raise SystemExit("--devices needs one id per shard")
+    ip, ix, vv = (t.cpu().numpy() for t in triplet)  # MultiMat takes the whole matrix from the host once
+    t0 = time.perf_counter()
+    mm = sa.MultiMat(a.genes, a.cells, sa.CSC, ip, ix, vv, a.shards, devices=devices)
+    t_create = (time.perf_counter() - t0) * 1e3
+    t_params, p2 = timed(lambda: sa.compute_sseq_params(mm))
+    t_pass, _ = timed(lambda: sa.group_sums(mm, labels, a.groups))
+    before = [mm.comm_info(i) for i in range(a.shards)]
+    calls, res = [], None
+    for _ in range(a.reps):
+        t0 = time.perf_counter()
+        res = sa.sseq_de_one_vs_rest(mm, labels, params, n_groups=a.groups, backend=backend)
+        calls.append(round((time.perf_counter() - t0) * 1e3, 2))
+    after = [mm.comm_info(i) for i in range(a.shards)]
+    fields = ("sums_in", "sums_out", "p_values", "adjusted_p_values", "log2_fold_change", "normalized_mean_in", "normalized_mean_out")
+    same = all(np.array_equal(getattr(r, f), getattr(w, f), equal_nan=f not in ("sums_in", "sums_out")) for r, w in zip(res, whole) for f in fields)
+    same = same and all(np.array_equal(getattr(p2, f), getattr(params, f), equal_nan=True)
+                        for f in ("size_factors", "gene_means", "gene_variances", "gene_moment_phi", "gene_phi"))
+    print(json.dumps({
+        "shards": a.shards, "devices": devices, "cells_per_shard": [hi - lo for _, lo, hi in mm.shard_ranges()], "create_ms": round(t_create, 2),
+        "sharded_params_ms": round(t_params, 2), "sharded_group_pass_ms": round(t_pass, 2), "sharded_call_ms": calls,
+        "sharded_test_stage_ms": round(min(calls) - t_pass, 2),
+        "de_shard_tests": [mm.counter("de_shard_tests", i) for i in range(a.shards)],
+        "de_shard_allreduces": [mm.counter("de_shard_allreduces", i) for i in range(a.shards)],
+        "exchange_bytes_per_call": [(y["allreduce_bytes"] - x["allreduce_bytes"]) // a.reps for x, y in zip(before, after)],
+        "equals_single_handle_bits": bool(same),
+    }), flush=True)
+    mm.close()
 
 
 def ratio_fallbacks(xa, xb, sf_a, sf_b, params, exact):
