@@ -168,7 +168,11 @@ int scanrs_mat_to_dense(scanrs_mat *m, double *out);
  * All four read the stored counts. The first three work on a handle whose map is the identity (as created, or after
  * scanrs_mat_reset_map) and that has no offset; a composed map, an offset or a sharded handle (scanrs_mat_set_shard*) returns
  * SCANRS_ERR_ARGUMENT with the reason in scanrs_last_error() (the reference clones the map verbatim and would index its per-axis
- * vectors with the new positions; that is not reproduced). Transposed views work: rows of the view are columns of the stored matrix,
+ * vectors with the new positions; that is not reproduced). A sharded handle is served by the collective entry points
+ * scanrs_mat_select_rows_sharded / scanrs_mat_select_cols_sharded / scanrs_mat_partition_on_thresholds_sharded below, and a
+ * scanrs_multi by scanrs_multi_select_rows / _select_cols / _partition_on_thresholds. Unchanged: the column-list statistics,
+ * scanrs_sseq_de_pairs and scanrs_merge_clusters stay refused on a sharded handle, and scanrs_mat_to_adaptive exports a rank's own
+ * shard only. Transposed views work: rows of the view are columns of the stored matrix,
  * and a result's storage flag is the view's (scanrs_mat_storage). Every result is a fresh, independent handle with its own
  * storage, default options and the identity map, made on the device from the handle's own storage (no transposed copy is built, nothing
  * goes through the host); the source may be freed first. Free results with scanrs_mat_free.
@@ -192,6 +196,45 @@ int scanrs_mat_select_cols(scanrs_mat *m, const uint64_t *idx, uint64_t n_idx, s
 int scanrs_mat_partition_on_thresholds(scanrs_mat *m, const double *row_threshold, const double *col_threshold, scanrs_mat **filtered,
                                        scanrs_mat **residual, uint64_t *selected_rows, uint64_t *n_selected_rows, uint64_t *selected_cols,
                                        uint64_t *n_selected_cols);
+/* The same three calls on a sharded handle (scanrs_mat_set_shard / scanrs_mat_set_shard_comm, the shards of a scanrs_multi). They are
+ * COLLECTIVE: every rank calls them with the same arguments. The plain functions above stay as they are and keep refusing a sharded
+ * handle. On a handle that is not sharded these give what the plain ones give. The convention is that of the sharded sSeq calls:
+ * every argument and output that runs along the sharded dimension spans the WHOLE matrix, and is the same on every rank. The sharded
+ * dimension is the outer dimension of the stored matrix: the rows of a handle created CSR, the columns of one created CSC, and the
+ * other one of its transposed view. scanrs_mat_shape of a sharded handle keeps reporting the LOCAL count along that dimension and
+ * the full extent along the other; scanrs_mat_shard_info gives the rest, and the caller sizes selected_rows / selected_cols with
+ * outer_global entries along the sharded dimension and the shape's extent along the other. The preconditions of the plain functions
+ * stand, with the same messages (identity map, no offset, dimensions below 2^31 - 1, taken over the global extent); transposed
+ * views work as they do unsharded.
+ *
+ * Results: fresh independent handles (default options, identity map, own storage) made on the device from the rank's own shard,
+ * already bound as rank r of the same world on the same transport as the source (the scanrs_comm, or the host hook and its ctx, which
+ * must outlive them too), sharded over the same physical dimension, with their own outer_begin / outer_global. scanrs_normalize, the
+ * solvers, scanrs_sseq_*, scanrs_mat_group_sums and these calls accept them, by collective calls on all ranks. A rank may end up
+ * with no outer vector at all: a valid empty shard. Nothing is rebalanced.
+ *
+ * select: a list along the replicated (inner) dimension may be in any order, with repeats; every rank selects from its shard, the
+ * ranges stay, nothing is exchanged. A list along the sharded dimension holds global positions and must not descend (repeats are
+ * allowed): rank r takes the run of entries inside its range, the result's outer_begin is the number of entries below that range,
+ * its outer_global is n_idx; nothing is exchanged. A list that descends returns SCANRS_ERR_ARGUMENT naming the first offending entry
+ * (moving vectors between ranks is not supported); an index outside the global extent returns SCANRS_ERR_INVALID. Both are found on
+ * every rank before any collective step.
+ *
+ * partition: the rounds of scanrs_mat_partition_on_thresholds with the sums along the replicated dimension all-reduced (u64, exact),
+ * so the kept lists, both matrices (shards concatenated in rank order) and "partition_rounds" equal the unsharded call's bit for
+ * bit whatever the cut. selected_rows / selected_cols are the global kept lists. *filtered and *residual follow the same rule: each
+ * rank holds the part made from its own outer vectors. Every exchange is a u64 sum (the host hook sees dtype 1 only). The counter
+ * "partition_allreduces" (scanrs_mat_get_counter on m) holds the exchange steps of the last call: per round one for the sums when the
+ * replicated dimension has a threshold and one for the round's flag when the sharded dimension has one, plus one for the mask of the
+ * sharded dimension at the end. */
+int scanrs_mat_select_rows_sharded(scanrs_mat *m, const uint64_t *idx, uint64_t n_idx, scanrs_mat **out);
+int scanrs_mat_select_cols_sharded(scanrs_mat *m, const uint64_t *idx, uint64_t n_idx, scanrs_mat **out);
+int scanrs_mat_partition_on_thresholds_sharded(scanrs_mat *m, const double *row_threshold, const double *col_threshold,
+                                               scanrs_mat **filtered, scanrs_mat **residual, uint64_t *selected_rows,
+                                               uint64_t *n_selected_rows, uint64_t *selected_cols, uint64_t *n_selected_cols);
+/* Where a handle lies in a sharded matrix: its rank and world, the global position of its first outer vector and the global extent
+ * of the sharded dimension. A handle that is not sharded: 0, 1, 0 and its own outer extent. Any pointer may be NULL. */
+int scanrs_mat_shard_info(const scanrs_mat *m, uint32_t *rank, uint32_t *world, uint64_t *outer_begin, uint64_t *outer_global);
 /* `base_mat_csc` / `to_csmat` of the stored counts (mat.rs:207-241, 257-259): indptr (outer dimension + 1 entries), indices and values
  * (scanrs_mat_nnz entries each) in the handle's own storage flag (scanrs_mat_storage: for CSR the outer dimension is the rows). The
  * map is not applied. */
@@ -416,6 +459,22 @@ int scanrs_multi_sseq_de(scanrs_multi *mm, int transposed, const int16_t *labels
                          const double *gene_means, const double *gene_phi, const uint8_t *use_genes, uint64_t big_count, int backend,
                          const scanrs_snoop *snoop, uint64_t *sums_in, uint64_t *sums_out, double *p, double *p_adj, double *log2fc,
                          double *mean_in, double *mean_out);
+/* The shape of the WHOLE matrix, its nonzeros over all shards and its storage flag. Any pointer may be NULL. */
+int scanrs_multi_shape(const scanrs_multi *mm, uint64_t *rows, uint64_t *cols, uint64_t *nnz, int *storage);
+/* scanrs_mat_to_csmat of the whole matrix, the shards concatenated: indptr (outer dimension + 1), indices and values (nnz each). */
+int scanrs_multi_to_csmat(scanrs_multi *mm, uint64_t *indptr, uint32_t *indices, uint32_t *values);
+/* select_rows / select_cols / partition_on_thresholds over the shards: scanrs_mat_select_rows_sharded, _select_cols_sharded and
+ * _partition_on_thresholds_sharded (see the select section) on every shard at once, with the arguments and lists of the whole
+ * matrix (selected_rows / selected_cols: rows / cols entries). A list along the sharded dimension (the rows of a CSR matrix, the
+ * columns of a CSC one) must not descend. Every result is a new scanrs_multi on the same devices with the same number of shards,
+ * with a group and communicators of its own: the source and its results may be freed in either order (scanrs_multi_free). The
+ * shards are NOT rebalanced after a filter: each holds what is left of its own outer vectors, possibly none. On any failure nothing
+ * is leaked and *out / *filtered / *residual are NULL. filtered / residual may be NULL (that matrix is not built). */
+int scanrs_multi_select_rows(scanrs_multi *mm, const uint64_t *idx, uint64_t n_idx, scanrs_multi **out);
+int scanrs_multi_select_cols(scanrs_multi *mm, const uint64_t *idx, uint64_t n_idx, scanrs_multi **out);
+int scanrs_multi_partition_on_thresholds(scanrs_multi *mm, const double *row_threshold, const double *col_threshold,
+                                         scanrs_multi **filtered, scanrs_multi **residual, uint64_t *selected_rows,
+                                         uint64_t *n_selected_rows, uint64_t *selected_cols, uint64_t *n_selected_cols);
 /* nnz-balanced contiguous partition of the outer dimension: bounds has world+1 entries. */
 int scanrs_plan_shards(const uint64_t *indptr, uint64_t n_outer, uint32_t world, uint64_t *bounds);
 
@@ -545,7 +604,8 @@ int scanrs_mat_set_option(scanrs_mat *m, const char *key, double value);
  * (hipMalloc). The tile layouts of the handle (both orientations, summed): "tile_positions" = record positions the tile kernel works
  * per pair of passes, "tile_served_nonzeros" = nonzeros among them (the rest is padding), "tile_overflow_nonzeros" = nonzeros left
  * to the overflow gather. "partition_rounds" = rounds of the last scanrs_mat_partition_on_thresholds on this handle, the final round
- * that changes nothing included. "de_pairs_passes" / "de_pairs_literal" = the last scanrs_sseq_de_pairs on this handle: its passes over
+ * that changes nothing included; "partition_allreduces" = the exchange steps of the last scanrs_mat_partition_on_thresholds_sharded
+ * (0 on an unsharded handle). "de_pairs_passes" / "de_pairs_literal" = the last scanrs_sseq_de_pairs on this handle: its passes over
  * the nonzeros and its pairs on the literal route. "de_shard_tests" / "de_shard_allreduces" = the last sSeq DE call on this handle: the
  * tests this rank launched on the device, and the exchange steps of a sharded handle (0 on an unsharded one). "subset_masked_passes" / "subset_scatter_passes" = sums over a column list made on
  * this handle so far: from the copy whose outer dimension is the result axis (masked walk or listed vectors, no atomics) / through the

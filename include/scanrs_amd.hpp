@@ -305,6 +305,29 @@ class AdaptiveMat {
     struct Partition;
     Partition partition_on_thresholds(const double *row_threshold, const double *col_threshold) const;
     Partition partition_on_threshold(double threshold) const;
+    // The collective forms for a sharded handle (scanrs_mat_*_sharded): every rank calls them with the same arguments; lists along
+    // the sharded dimension span the whole matrix (a selection list there must not descend). The results are bound as this rank of
+    // the same world. On an unsharded handle they are the plain calls.
+    struct ShardInfo {
+        uint32_t rank = 0, world = 1;
+        uint64_t outer_begin = 0, outer_global = 0;
+    };
+    ShardInfo shard_info() const {
+        ShardInfo i;
+        check(scanrs_mat_shard_info(h_, &i.rank, &i.world, &i.outer_begin, &i.outer_global));
+        return i;
+    }
+    AdaptiveMat select_rows_sharded(const std::vector<uint64_t> &idx) const {
+        scanrs_mat *h = nullptr;
+        check(scanrs_mat_select_rows_sharded(h_, idx.data(), idx.size(), &h));
+        return AdaptiveMat(h);
+    }
+    AdaptiveMat select_cols_sharded(const std::vector<uint64_t> &idx) const {
+        scanrs_mat *h = nullptr;
+        check(scanrs_mat_select_cols_sharded(h_, idx.data(), idx.size(), &h));
+        return AdaptiveMat(h);
+    }
+    Partition partition_on_thresholds_sharded(const double *row_threshold, const double *col_threshold) const;
     // to_csmat of the stored counts (mat.rs:207-241) in the handle's storage flag
     struct CsMat {
         int storage = SCANRS_CSR;
@@ -355,6 +378,22 @@ inline AdaptiveMat::Partition AdaptiveMat::partition_on_thresholds(const double 
     return p;
 }
 inline AdaptiveMat::Partition AdaptiveMat::partition_on_threshold(double threshold) const { return partition_on_thresholds(&threshold, &threshold); }
+inline AdaptiveMat::Partition AdaptiveMat::partition_on_thresholds_sharded(const double *row_threshold, const double *col_threshold) const {
+    const ShardInfo si = shard_info();
+    int storage = SCANRS_CSR;
+    check(scanrs_mat_storage(h_, &storage));
+    Partition p; // the lists of the sharded dimension have outer_global entries: the rows of a CSR handle, the columns of a CSC one
+    p.selected_rows.resize((storage == SCANRS_CSR ? si.outer_global : rows()) + 1); // (+ 1: never a null array)
+    p.selected_cols.resize((storage == SCANRS_CSR ? cols() : si.outer_global) + 1);
+    uint64_t nr = 0, nc = 0;
+    scanrs_mat *f = nullptr, *r = nullptr;
+    check(scanrs_mat_partition_on_thresholds_sharded(h_, row_threshold, col_threshold, &f, &r, p.selected_rows.data(), &nr, p.selected_cols.data(), &nc));
+    p.filtered = AdaptiveMat(f);
+    p.residual = AdaptiveMat(r);
+    p.selected_rows.resize(nr);
+    p.selected_cols.resize(nc);
+    return p;
+}
 
 // normalize(mat, norm) -> LowRankOffset (normalization.rs:46-69); consumes `mat` like the reference.
 inline AdaptiveMat normalize(AdaptiveMat mat, Normalization norm) {
@@ -459,12 +498,63 @@ class MultiMat {
         : rows_(rows), cols_(cols) {
         check(scanrs_multi_create(rows, cols, storage, indptr, indices, values, n_shards, devices, &h_));
     }
+    MultiMat() = default;
+    // takes over a handle (the results of select_rows / select_cols / partition_on_thresholds)
+    explicit MultiMat(scanrs_multi *h) : h_(h) {
+        if (!h) return;
+        uint64_t r = 0, c = 0;
+        check(scanrs_multi_shape(h, &r, &c, nullptr, nullptr));
+        rows_ = r;
+        cols_ = c;
+    }
     MultiMat(const MultiMat &) = delete;
     MultiMat &operator=(const MultiMat &) = delete;
+    MultiMat(MultiMat &&o) noexcept : h_(o.h_), rows_(o.rows_), cols_(o.cols_) { o.h_ = nullptr; }
+    MultiMat &operator=(MultiMat &&o) noexcept {
+        if (this != &o) {
+            scanrs_multi_free(h_);
+            h_ = o.h_;
+            rows_ = o.rows_;
+            cols_ = o.cols_;
+            o.h_ = nullptr;
+        }
+        return *this;
+    }
     ~MultiMat() { scanrs_multi_free(h_); }
     size_t rows() const { return rows_; }
     size_t cols() const { return cols_; }
     scanrs_multi *raw() const { return h_; }
+    uint64_t nnz() const {
+        uint64_t n = 0;
+        check(scanrs_multi_shape(h_, nullptr, nullptr, &n, nullptr));
+        return n;
+    }
+    // the whole matrix, shards concatenated (scanrs_multi_to_csmat)
+    AdaptiveMat::CsMat to_csmat() const {
+        AdaptiveMat::CsMat c;
+        uint64_t n = 0;
+        check(scanrs_multi_shape(h_, &c.rows, &c.cols, &n, &c.storage));
+        c.indptr.resize((c.storage == SCANRS_CSR ? c.rows : c.cols) + 1);
+        c.indices.resize(n);
+        c.data.resize(n);
+        check(scanrs_multi_to_csmat(h_, c.indptr.data(), c.indices.data(), c.data.data()));
+        return c;
+    }
+    // select_rows / select_cols / partition_on_thresholds over the shards (scanrs_multi_select_*): new MultiMat objects on
+    // the same devices, shards not rebalanced. A list along the sharded dimension must not descend.
+    MultiMat select_rows(const std::vector<uint64_t> &idx) const {
+        scanrs_multi *h = nullptr;
+        check(scanrs_multi_select_rows(h_, idx.data(), idx.size(), &h));
+        return MultiMat(h);
+    }
+    MultiMat select_cols(const std::vector<uint64_t> &idx) const {
+        scanrs_multi *h = nullptr;
+        check(scanrs_multi_select_cols(h_, idx.data(), idx.size(), &h));
+        return MultiMat(h);
+    }
+    struct Partition;
+    Partition partition_on_thresholds(const double *row_threshold, const double *col_threshold) const;
+    Partition partition_on_threshold(double threshold) const;
     // payload bytes of the sum all-reduces that went through shard i's communicator so far (scanrs_multi_comm_info)
     uint64_t allreduce_bytes(uint32_t i = 0) const {
         uint64_t b = 0;
@@ -479,6 +569,25 @@ class MultiMat {
         return r;
     }
 };
+
+struct MultiMat::Partition {
+    MultiMat filtered, residual;
+    std::vector<uint64_t> selected_rows, selected_cols;
+};
+inline MultiMat::Partition MultiMat::partition_on_thresholds(const double *row_threshold, const double *col_threshold) const {
+    Partition p;
+    p.selected_rows.resize(rows_ + 1); // (+ 1: never a null array)
+    p.selected_cols.resize(cols_ + 1);
+    uint64_t nr = 0, nc = 0;
+    scanrs_multi *f = nullptr, *r = nullptr;
+    check(scanrs_multi_partition_on_thresholds(h_, row_threshold, col_threshold, &f, &r, p.selected_rows.data(), &nr, p.selected_cols.data(), &nc));
+    p.filtered = MultiMat(f);
+    p.residual = MultiMat(r);
+    p.selected_rows.resize(nr);
+    p.selected_cols.resize(nc);
+    return p;
+}
+inline MultiMat::Partition MultiMat::partition_on_threshold(double threshold) const { return partition_on_thresholds(&threshold, &threshold); }
 
 // ---- hdf5-io crate (hdf5-io/src/matrix.rs, analysis.rs): 10x files -> host arrays, parsed by the library itself ----
 namespace hdf5_io {

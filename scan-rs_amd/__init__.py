@@ -517,6 +517,51 @@ class AdaptiveMat:
         """`partition_on_threshold` (mat.rs:768-770)."""
         return self.partition_on_thresholds(threshold, threshold)
 
+    # -- the collective forms for a sharded handle (DESIGN.md §7h) -------------------------
+    def shard_info(self) -> dict:
+        """`scanrs_mat_shard_info`: rank, world, outer_begin, outer_global (an unsharded handle: 0, 1, 0 and its own outer extent)."""
+        r, w, b, g = ctypes.c_uint32(), ctypes.c_uint32(), ctypes.c_uint64(), ctypes.c_uint64()
+        _check(_lib.scanrs_mat_shard_info(self._h, ctypes.byref(r), ctypes.byref(w), ctypes.byref(b), ctypes.byref(g)))
+        return {"rank": int(r.value), "world": int(w.value), "outer_begin": int(b.value), "outer_global": int(g.value)}
+
+    def _global_shape(self):
+        """[rows, cols] of the whole matrix: the local shape with the sharded (stored outer) dimension replaced by outer_global."""
+        shape = self.shape()
+        shape[0 if self.storage() == CSR else 1] = self.shard_info()["outer_global"]
+        return shape
+
+    def _bound_like_self(self, result):
+        if result is not None:
+            result._keep.extend(self._keep)  # the transport (host hook or Comm) the result is bound to
+            result._outer_global = result.shard_info()["outer_global"]
+        return result
+
+    def select_rows_sharded(self, idx) -> "AdaptiveMat":
+        """`scanrs_mat_select_rows_sharded`: collective `select_rows` of a sharded handle. A list along the sharded dimension holds
+        global positions and must not descend. On an unsharded handle: `select_rows`."""
+        return self._bound_like_self(self._select(_lib.scanrs_mat_select_rows_sharded, idx))
+
+    def select_cols_sharded(self, idx) -> "AdaptiveMat":
+        """`scanrs_mat_select_cols_sharded` (see `select_rows_sharded`)."""
+        return self._bound_like_self(self._select(_lib.scanrs_mat_select_cols_sharded, idx))
+
+    def partition_on_thresholds_sharded(self, row_threshold: Optional[float], col_threshold: Optional[float], filtered: bool = True,
+                                        residual: bool = True):
+        """`scanrs_mat_partition_on_thresholds_sharded`: collective `partition_on_thresholds` of a sharded handle. The kept lists are
+        those of the whole matrix, the same on every rank; the two matrices are this rank's shards of the results."""
+        rows, cols = self._global_shape()
+        sel_r, sel_c = np.zeros(max(rows, 1), dtype=np.uint64), np.zeros(max(cols, 1), dtype=np.uint64)
+        n_r, n_c = ctypes.c_uint64(), ctypes.c_uint64()
+        rt = None if row_threshold is None else ctypes.byref(ctypes.c_double(row_threshold))
+        ct = None if col_threshold is None else ctypes.byref(ctypes.c_double(col_threshold))
+        hf, hr = ctypes.c_void_p(), ctypes.c_void_p()
+        _check(_lib.scanrs_mat_partition_on_thresholds_sharded(self._h, rt, ct, ctypes.byref(hf) if filtered else None,
+                                                               ctypes.byref(hr) if residual else None, _p(sel_r), ctypes.byref(n_r), _p(sel_c),
+                                                               ctypes.byref(n_c)))
+        f = self._bound_like_self(AdaptiveMat(hf.value)) if filtered else None
+        r = self._bound_like_self(AdaptiveMat(hr.value)) if residual else None
+        return f, r, sel_r[: n_r.value].astype(np.int64), sel_c[: n_c.value].astype(np.int64)
+
     def to_csmat(self):
         """`to_csmat` of the stored counts (mat.rs:207-241): (indptr u64, indices u32, data u32) in the handle's storage flag."""
         rows, cols = self.shape()
@@ -1006,6 +1051,84 @@ class MultiMat:
         _check(_lib.scanrs_multi_create(ctypes.c_uint64(rows), ctypes.c_uint64(cols), ctypes.c_int(storage), _p(ip), _p(ix), _p(vv),
                                         ctypes.c_uint32(n_shards), dv, ctypes.byref(self._h)))
 
+    @classmethod
+    def _from_handle(cls, handle) -> "MultiMat":
+        """Takes over a `scanrs_multi` handle (the results of select_rows / select_cols / partition_on_thresholds)."""
+        self = cls.__new__(cls)
+        self._h = ctypes.c_void_p(handle)
+        n, st = ctypes.c_uint32(), ctypes.c_int()
+        r, c = ctypes.c_uint64(), ctypes.c_uint64()
+        _check(_lib.scanrs_multi_n_shards(self._h, ctypes.byref(n)))
+        _check(_lib.scanrs_multi_shape(self._h, ctypes.byref(r), ctypes.byref(c), None, ctypes.byref(st)))
+        self.rows, self.cols, self.storage, self.n_shards = int(r.value), int(c.value), int(st.value), int(n.value)
+        return self
+
+    def shape(self):
+        """[rows, cols] of the whole matrix (`scanrs_multi_shape`)."""
+        r, c = ctypes.c_uint64(), ctypes.c_uint64()
+        _check(_lib.scanrs_multi_shape(self._h, ctypes.byref(r), ctypes.byref(c), None, None))
+        return [int(r.value), int(c.value)]
+
+    def nnz(self) -> int:
+        n = ctypes.c_uint64()
+        _check(_lib.scanrs_multi_shape(self._h, None, None, ctypes.byref(n), None))
+        return int(n.value)
+
+    def to_csmat(self):
+        """`scanrs_multi_to_csmat`: (indptr u64, indices u32, data u32) of the whole matrix, the shards concatenated."""
+        rows, cols = self.shape()
+        nnz = self.nnz()
+        indptr = np.zeros((rows if self.storage == CSR else cols) + 1, dtype=np.uint64)
+        indices, data = np.zeros(nnz, dtype=np.uint32), np.zeros(nnz, dtype=np.uint32)
+        _check(_lib.scanrs_multi_to_csmat(self._h, _p(indptr), _p(indices), _p(data)))
+        return indptr, indices, data
+
+    def to_scipy(self):
+        """The stored counts of the whole matrix as scipy.sparse csr_matrix / csc_matrix (by the storage flag)."""
+        import scipy.sparse as sp
+
+        indptr, indices, data = self.to_csmat()
+        cls = sp.csr_matrix if self.storage == CSR else sp.csc_matrix
+        return cls((data, indices.astype(np.int64), indptr.astype(np.int64)), shape=tuple(self.shape()))
+
+    def _select(self, fn, idx) -> "MultiMat":
+        idx = np.ascontiguousarray(np.asarray(idx).reshape(-1), dtype=np.int64)
+        if idx.size and int(idx.min()) < 0:
+            raise ScanrsError(6, "index out of range: negative index")
+        idx = idx.astype(np.uint64)
+        h = ctypes.c_void_p()
+        _check(fn(self._h, _p(idx), ctypes.c_uint64(idx.shape[0]), ctypes.byref(h)))
+        return MultiMat._from_handle(h.value)
+
+    def select_rows(self, idx) -> "MultiMat":
+        """`scanrs_multi_select_rows`: a new MultiMat on the same devices (shards not rebalanced). A list along the sharded dimension
+        (the rows of a CSR matrix, the columns of a CSC one) must not descend; along the other any order, repeats allowed."""
+        return self._select(_lib.scanrs_multi_select_rows, idx)
+
+    def select_cols(self, idx) -> "MultiMat":
+        """`scanrs_multi_select_cols` (see `select_rows`)."""
+        return self._select(_lib.scanrs_multi_select_cols, idx)
+
+    def partition_on_thresholds(self, row_threshold: Optional[float], col_threshold: Optional[float], filtered: bool = True,
+                                residual: bool = True):
+        """`scanrs_multi_partition_on_thresholds`: (filtered, residual, selected_rows, selected_cols) as `AdaptiveMat.partition_on_thresholds`
+        gives them, the two matrices as MultiMat objects; every output equals the unsharded call's."""
+        rows, cols = self.shape()
+        sel_r, sel_c = np.zeros(max(rows, 1), dtype=np.uint64), np.zeros(max(cols, 1), dtype=np.uint64)
+        n_r, n_c = ctypes.c_uint64(), ctypes.c_uint64()
+        rt = None if row_threshold is None else ctypes.byref(ctypes.c_double(row_threshold))
+        ct = None if col_threshold is None else ctypes.byref(ctypes.c_double(col_threshold))
+        hf, hr = ctypes.c_void_p(), ctypes.c_void_p()
+        _check(_lib.scanrs_multi_partition_on_thresholds(self._h, rt, ct, ctypes.byref(hf) if filtered else None,
+                                                         ctypes.byref(hr) if residual else None, _p(sel_r), ctypes.byref(n_r), _p(sel_c),
+                                                         ctypes.byref(n_c)))
+        f = MultiMat._from_handle(hf.value) if filtered else None
+        r = MultiMat._from_handle(hr.value) if residual else None
+        return f, r, sel_r[: n_r.value].astype(np.int64), sel_c[: n_c.value].astype(np.int64)
+
+    def partition_on_threshold(self, threshold: float):
+        return self.partition_on_thresholds(threshold, threshold)
+
     def shard_ranges(self):
         out = []
         for i in range(self.n_shards):
@@ -1206,6 +1329,8 @@ EXPORTED_SYMBOLS = [
     "scanrs_host_pdist", "scanrs_host_linkage_complete", "scanrs_host_relabel_by_size", "scanrs_cluster_medoids", "scanrs_cluster_medoids_device",
     "scanrs_merge_clusters",
     "scanrs_mat_select_rows", "scanrs_mat_select_cols", "scanrs_mat_partition_on_thresholds", "scanrs_mat_to_csmat",
+    "scanrs_mat_select_rows_sharded", "scanrs_mat_select_cols_sharded", "scanrs_mat_partition_on_thresholds_sharded", "scanrs_mat_shard_info",
+    "scanrs_multi_shape", "scanrs_multi_to_csmat", "scanrs_multi_select_rows", "scanrs_multi_select_cols", "scanrs_multi_partition_on_thresholds",
     "scanrs_mat_to_adaptive", "scanrs_adaptive_export_info", "scanrs_adaptive_export_vecs", "scanrs_adaptive_export_free",
     "scanrs_host_choose_storage",
     "scanrs_mat_sum_rows_u64", "scanrs_mat_sum_rows_f64", "scanrs_mat_sum_cols_u64", "scanrs_mat_sum_cols_f64", "scanrs_mat_sum_rows_dual_u64",

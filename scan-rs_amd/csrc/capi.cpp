@@ -309,31 +309,55 @@ static scanrs_mat *adopt_copy(uint64_t rows, uint64_t cols, int storage, SparseC
 
 // select / partition work on the stored counts under the identity map (the reference clones the map verbatim and would index its
 // per-axis vectors with the NEW positions; that is not reproduced)
-static void need_plain_unsharded(const scanrs_mat *m, const char *what) {
+static void need_plain(const scanrs_mat *m, const char *what) {
     if (!map_is_raw(m))
         fail(SCANRS_ERR_ARGUMENT, "%s: the handle's map is not the identity (a scaling or a function has been composed); call scanrs_mat_reset_map first", what);
     if (m->off_rank) fail(SCANRS_ERR_ARGUMENT, "%s: the handle has a low-rank offset (center / scale_and_center / normalize); call scanrs_mat_reset_map first", what);
-    if (m->st->shard.active()) fail(SCANRS_ERR_ARGUMENT, "%s of a sharded handle (scanrs_mat_set_shard*) is not supported", what);
+}
+// the plain entry points are not collective calls: a sharded handle goes through the *_sharded ones (collective: true)
+static void need_plain_unsharded(const scanrs_mat *m, const char *what, bool collective = false) {
+    need_plain(m, what);
+    if (!collective && m->st->shard.active())
+        fail(SCANRS_ERR_ARGUMENT, "%s of a sharded handle (scanrs_mat_set_shard*) is not supported; the collective scanrs_mat_%s_sharded serves one", what, what);
 }
 
-static void select_axis(scanrs_mat *m, bool rows_axis, const uint64_t *idx, uint64_t n_idx, scanrs_mat **out) {
+// a result of a collective select / partition: rank r of the same world on the same transport as its source, over its own range
+static void bind_like(const Storage &src, scanrs_mat *result, uint64_t outer_begin, uint64_t outer_global) {
+    ShardInfo &sh = result->st->shard;
+    sh = src.shard;
+    sh.outer_begin = outer_begin;
+    sh.outer_global = outer_global;
+}
+// rows / cols of the handle that adopts a copy made under the storage flag `view_storage`
+static uint64_t made_rows(const SparseCopy &c, int view_storage) { return view_storage == SCANRS_CSR ? c.n_outer : c.n_inner; }
+static uint64_t made_cols(const SparseCopy &c, int view_storage) { return view_storage == SCANRS_CSR ? c.n_inner : c.n_outer; }
+
+static void select_axis(scanrs_mat *m, bool rows_axis, const uint64_t *idx, uint64_t n_idx, scanrs_mat **out, bool collective = false) {
     if (!m || !out) fail(SCANRS_ERR_ARGUMENT, "null argument");
     *out = nullptr;
     need_device();
-    need_plain_unsharded(m, rows_axis ? "select_rows" : "select_cols");
+    need_plain_unsharded(m, rows_axis ? "select_rows" : "select_cols", collective);
     Storage &st = *m->st;
     const bool outer_is_view_rows = (st.storage == SCANRS_CSR) != m->transposed;
     const int view_storage = m->transposed ? 1 - st.storage : st.storage;
+    const bool sharded = st.shard.active();
+    uint64_t out_begin = st.shard.outer_begin, out_global = st.shard.outer_global; // a list along the replicated dimension leaves the ranges alone
     SparseCopy made;
     {
         CurrentHandle cur(&st);
-        if (rows_axis == outer_is_view_rows)
-            select_outer(st, st.primary, idx, n_idx, made);
-        else
+        if (rows_axis != outer_is_view_rows) {
             select_inner(st, st.primary, idx, n_idx, made);
+        } else if (sharded) {
+            select_outer_sharded(st, st.primary, idx, n_idx, made, &out_begin);
+            out_global = n_idx;
+        } else {
+            select_outer(st, st.primary, idx, n_idx, made);
+        }
         device_free_flush();
     }
-    *out = adopt_copy(rows_axis ? n_idx : m->rows(), rows_axis ? m->cols() : n_idx, view_storage, std::move(made));
+    scanrs_mat *h = adopt_copy(made_rows(made, view_storage), made_cols(made, view_storage), view_storage, std::move(made));
+    if (sharded) bind_like(st, h, out_begin, out_global);
+    *out = h;
 }
 
 // radix select of the k-th smallest (0-based, global rank) of a u32 device array spread over ranks
@@ -1358,8 +1382,10 @@ int scanrs_mat_get_counter(scanrs_mat *m, const char *key, uint64_t *value) {
         const std::string k(key);
         if (k == "bk_host_retries")
             *value = m->st->bk_host_retries;
-        else if (k == "partition_rounds") // rounds of the last scanrs_mat_partition_on_thresholds on this handle
+        else if (k == "partition_rounds") // rounds of the last scanrs_mat_partition_on_thresholds[_sharded] on this handle
             *value = m->st->partition_rounds;
+        else if (k == "partition_allreduces") // ... and its exchange steps (an unsharded handle: 0)
+            *value = m->st->partition_allreduces;
         else if (k == "de_pairs_passes") // the last scanrs_sseq_de_pairs on this handle: passes over the nonzeros ...
             *value = m->st->de_pairs_passes;
         else if (k == "de_pairs_literal") // ... and pairs that took the literal route
@@ -1575,43 +1601,94 @@ int scanrs_mat_select_rows(scanrs_mat *m, const uint64_t *idx, uint64_t n_idx, s
 int scanrs_mat_select_cols(scanrs_mat *m, const uint64_t *idx, uint64_t n_idx, scanrs_mat **out) {
     return guard([&] { select_axis(m, false, idx, n_idx, out); });
 }
+// the plain entry point and the collective one of a sharded handle: the lists along the sharded dimension span the whole matrix
+static void partition_entry(scanrs_mat *m, const double *row_threshold, const double *col_threshold, scanrs_mat **filtered, scanrs_mat **residual,
+                            uint64_t *selected_rows, uint64_t *n_selected_rows, uint64_t *selected_cols, uint64_t *n_selected_cols, bool collective) {
+    if (filtered) *filtered = nullptr;
+    if (residual) *residual = nullptr;
+    if (!m || !selected_rows || !n_selected_rows || !selected_cols || !n_selected_cols) fail(SCANRS_ERR_ARGUMENT, "null argument");
+    need_device();
+    need_plain_unsharded(m, "partition_on_thresholds", collective);
+    Storage &st = *m->st;
+    const bool outer_is_view_rows = (st.storage == SCANRS_CSR) != m->transposed;
+    const int view_storage = m->transposed ? 1 - st.storage : st.storage;
+    const bool sharded = st.shard.active();
+    SparseCopy f, r;
+    std::vector<uint8_t> ex_outer, ex_inner;
+    PartitionShard ps;
+    {
+        CurrentHandle cur(&st);
+        st.partition_allreduces = 0;
+        st.partition_rounds = partition_on_thresholds(st, st.primary, outer_is_view_rows ? row_threshold : col_threshold,
+                                                      outer_is_view_rows ? col_threshold : row_threshold, outer_is_view_rows, ex_outer, ex_inner,
+                                                      filtered ? &f : nullptr, residual ? &r : nullptr, sharded ? &ps : nullptr);
+        st.partition_allreduces = ps.allreduces;
+        device_free_flush();
+    }
+    const std::vector<uint8_t> &ex_outer_all = sharded ? ps.excl_outer_all : ex_outer;
+    const std::vector<uint8_t> &ex_rows = outer_is_view_rows ? ex_outer_all : ex_inner, &ex_cols = outer_is_view_rows ? ex_inner : ex_outer_all;
+    uint64_t nr = 0, nc = 0;
+    for (uint64_t i = 0; i < ex_rows.size(); i++)
+        if (!ex_rows[i]) selected_rows[nr++] = i;
+    for (uint64_t i = 0; i < ex_cols.size(); i++)
+        if (!ex_cols[i]) selected_cols[nc++] = i;
+    *n_selected_rows = nr;
+    *n_selected_cols = nc;
+    scanrs_mat *hf = filtered ? adopt_copy(made_rows(f, view_storage), made_cols(f, view_storage), view_storage, std::move(f)) : nullptr;
+    scanrs_mat *hr = nullptr;
+    try {
+        if (residual) hr = adopt_copy(made_rows(r, view_storage), made_cols(r, view_storage), view_storage, std::move(r));
+    } catch (...) {
+        scanrs_mat_free(hf);
+        throw;
+    }
+    if (sharded) {
+        // where this rank's results lie: the kept (excluded) outer vectors below its own first one, and their number in the whole matrix.
+        // The residual holds the kept rows x the excluded columns: the excluded outer vectors when the columns are the outer dimension.
+        uint64_t kept_below = 0, kept_all = 0;
+        for (uint64_t o = 0; o < ex_outer_all.size(); o++) {
+            if (ex_outer_all[o]) continue;
+            kept_all++;
+            if (o < st.shard.outer_begin) kept_below++;
+        }
+        const uint64_t gone_below = st.shard.outer_begin - kept_below, gone_all = ex_outer_all.size() - kept_all;
+        if (hf) bind_like(st, hf, kept_below, kept_all);
+        if (hr) bind_like(st, hr, outer_is_view_rows ? kept_below : gone_below, outer_is_view_rows ? kept_all : gone_all);
+    }
+    if (residual) *residual = hr;
+    if (filtered) *filtered = hf;
+}
 int scanrs_mat_partition_on_thresholds(scanrs_mat *m, const double *row_threshold, const double *col_threshold, scanrs_mat **filtered,
                                        scanrs_mat **residual, uint64_t *selected_rows, uint64_t *n_selected_rows, uint64_t *selected_cols,
                                        uint64_t *n_selected_cols) {
     return guard([&] {
-        if (filtered) *filtered = nullptr;
-        if (residual) *residual = nullptr;
-        if (!m || !selected_rows || !n_selected_rows || !selected_cols || !n_selected_cols) fail(SCANRS_ERR_ARGUMENT, "null argument");
-        need_device();
-        need_plain_unsharded(m, "partition_on_thresholds");
-        Storage &st = *m->st;
-        const bool outer_is_view_rows = (st.storage == SCANRS_CSR) != m->transposed;
-        const int view_storage = m->transposed ? 1 - st.storage : st.storage;
-        SparseCopy f, r;
-        std::vector<uint8_t> ex_outer, ex_inner;
-        {
-            CurrentHandle cur(&st);
-            st.partition_rounds = partition_on_thresholds(st, st.primary, outer_is_view_rows ? row_threshold : col_threshold,
-                                                          outer_is_view_rows ? col_threshold : row_threshold, outer_is_view_rows, ex_outer, ex_inner,
-                                                          filtered ? &f : nullptr, residual ? &r : nullptr);
-            device_free_flush();
-        }
-        const std::vector<uint8_t> &ex_rows = outer_is_view_rows ? ex_outer : ex_inner, &ex_cols = outer_is_view_rows ? ex_inner : ex_outer;
-        uint64_t nr = 0, nc = 0;
-        for (uint64_t i = 0; i < ex_rows.size(); i++)
-            if (!ex_rows[i]) selected_rows[nr++] = i;
-        for (uint64_t i = 0; i < ex_cols.size(); i++)
-            if (!ex_cols[i]) selected_cols[nc++] = i;
-        *n_selected_rows = nr;
-        *n_selected_cols = nc;
-        scanrs_mat *hf = filtered ? adopt_copy(nr, nc, view_storage, std::move(f)) : nullptr;
-        try {
-            if (residual) *residual = adopt_copy(nr, ex_cols.size() - nc, view_storage, std::move(r));
-        } catch (...) {
-            scanrs_mat_free(hf);
-            throw;
-        }
-        if (filtered) *filtered = hf;
+        partition_entry(m, row_threshold, col_threshold, filtered, residual, selected_rows, n_selected_rows, selected_cols, n_selected_cols, false);
+    });
+}
+// The collective forms: every rank of a sharded handle calls them with the same arguments; on an unsharded handle they are
+// the plain calls.
+int scanrs_mat_select_rows_sharded(scanrs_mat *m, const uint64_t *idx, uint64_t n_idx, scanrs_mat **out) {
+    return guard([&] { select_axis(m, true, idx, n_idx, out, true); });
+}
+int scanrs_mat_select_cols_sharded(scanrs_mat *m, const uint64_t *idx, uint64_t n_idx, scanrs_mat **out) {
+    return guard([&] { select_axis(m, false, idx, n_idx, out, true); });
+}
+int scanrs_mat_partition_on_thresholds_sharded(scanrs_mat *m, const double *row_threshold, const double *col_threshold, scanrs_mat **filtered,
+                                               scanrs_mat **residual, uint64_t *selected_rows, uint64_t *n_selected_rows,
+                                               uint64_t *selected_cols, uint64_t *n_selected_cols) {
+    return guard([&] {
+        partition_entry(m, row_threshold, col_threshold, filtered, residual, selected_rows, n_selected_rows, selected_cols, n_selected_cols, true);
+    });
+}
+int scanrs_mat_shard_info(const scanrs_mat *m, uint32_t *rank, uint32_t *world, uint64_t *outer_begin, uint64_t *outer_global) {
+    return guard([&] {
+        if (!m) fail(SCANRS_ERR_ARGUMENT, "null argument");
+        const Storage &st = *m->st;
+        const bool sharded = st.shard.active();
+        if (rank) *rank = sharded ? st.shard.rank : 0u;
+        if (world) *world = sharded ? st.shard.world : 1u;
+        if (outer_begin) *outer_begin = sharded ? st.shard.outer_begin : 0ull;
+        if (outer_global) *outer_global = sharded ? st.shard.outer_global : st.primary.n_outer;
     });
 }
 int scanrs_mat_to_csmat(scanrs_mat *m, uint64_t *indptr, uint32_t *indices, uint32_t *values) {

@@ -404,6 +404,7 @@ struct Storage {
     int tile_hint = 0;                    // > 0 while a solver that repeats the same products is running (svd_bk, svd_rand)
     int tile_overlap = 1;                 // hybrid product: 1 = the overflow gather runs beside the tile kernel (own stream); 0 = after it (measurement)
     int panel_precision = 0;              // 0: f64 panels (default); 1: gathered panels rounded to f32, f64 sums (opt-in)
+    uint64_t partition_allreduces = 0;    // exchange steps of the last scanrs_mat_partition_on_thresholds_sharded on this handle (an unsharded one: 0)
     uint64_t partition_rounds = 0;        // rounds of the last scanrs_mat_partition_on_thresholds on this handle, the final one that changes nothing included (scanrs_mat_get_counter)
     uint64_t de_shard_tests = 0, de_shard_allreduces = 0; // the last DE call on this handle: tests this rank launched on the device, exchange steps (scanrs_mat_get_counter)
     uint64_t de_pairs_passes = 0, de_pairs_literal = 0; // the last scanrs_sseq_de_pairs on this handle: passes over the nonzeros, pairs on the literal route (scanrs_mat_get_counter)
@@ -793,9 +794,18 @@ void select_outer(Storage &st, const SparseCopy &cp, const uint64_t *idx, uint64
 void select_inner(Storage &st, const SparseCopy &cp, const uint64_t *idx, uint64_t n_idx, SparseCopy &out);
 // thr_outer / thr_inner: nullable thresholds of the two axes of cp; cols_inner: the view's columns are cp's inner positions (their
 // step comes first in a round). excl_outer / excl_inner: the final masks (host). filtered / residual may be null (not built).
-// Returns the number of rounds.
+// Returns the number of rounds. sh (a sharded handle): cp is the rank's shard; excl_outer, filtered and residual stay
+// local, excl_inner is replicated, and sh receives what the call learned about the whole outer dimension.
+struct PartitionShard {
+    std::vector<uint8_t> excl_outer_all; // the outer mask of the whole matrix (outer_global entries), the same on every rank
+    uint64_t allreduces = 0;             // exchange steps of the call
+};
 uint64_t partition_on_thresholds(Storage &st, const SparseCopy &cp, const double *thr_outer, const double *thr_inner, bool cols_inner,
-                                 std::vector<uint8_t> &excl_outer, std::vector<uint8_t> &excl_inner, SparseCopy *filtered, SparseCopy *residual);
+                                 std::vector<uint8_t> &excl_outer, std::vector<uint8_t> &excl_inner, SparseCopy *filtered, SparseCopy *residual,
+                                 PartitionShard *sh = nullptr);
+// the outer-axis selection of a sharded handle: idx holds positions of the WHOLE outer dimension, non-decreasing; this rank takes the
+// run that falls into [outer_begin, outer_begin + cp.n_outer). *out_begin: the entries below the rank's range (the result's outer_begin)
+void select_outer_sharded(Storage &st, const SparseCopy &cp, const uint64_t *idx, uint64_t n_idx, SparseCopy &out, uint64_t *out_begin);
 
 // ---- subset.hip / subset_host.cpp: sum_rows, sum_cols, sum_rows_dual, mean_rows, mean_var_rows (sqz/src/mat.rs:279-282, 333-374, 414-583) ----
 // d_list: n distinct positions (u32) on the device. mode 0: u64 sums of the raw counts, 1: f64 sums of the mapped values, 2: f64 sum and

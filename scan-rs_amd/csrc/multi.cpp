@@ -349,4 +349,161 @@ int scanrs_multi_sseq_de(scanrs_multi *mm, int transposed, const int16_t *labels
     });
 }
 
+// ---- select_rows / select_cols / partition_on_thresholds over the shards -------------------------------------------------
+// The collective entry points of the handle (scanrs_mat_*_sharded) on every shard at once. Every result is a new scanrs_multi on the
+// same devices with as many shards, the ranges its shards ended up with (nothing is rebalanced), and a group and communicators of its
+// own: the source and its results may be freed in either order.
+namespace {
+
+void free_shards(scanrs_multi *mm, std::vector<scanrs_mat *> &made) {
+    for (size_t i = 0; i < made.size(); i++) {
+        if (!made[i]) continue;
+        (void)hipSetDevice(mm->devices[i]);
+        scanrs_mat_free(made[i]);
+        made[i] = nullptr;
+    }
+}
+
+// takes over `made` (one result handle per shard of src, bound to src's communicators); on failure everything in it is freed
+int multi_adopt(scanrs_multi *src, std::vector<scanrs_mat *> &made, scanrs_multi **out) {
+    try {
+        auto mm = std::make_unique<scanrs_multi>();
+        const uint32_t n = (uint32_t)made.size();
+        mm->storage = src->storage;
+        mm->devices = src->devices;
+        mm->bounds.assign(n + 1, 0);
+        uint64_t outer_all = 0, inner = 0;
+        for (uint32_t i = 0; i < n; i++) {
+            uint64_t begin = 0, all = 0, r = 0, c = 0;
+            if (scanrs_mat_shard_info(made[i], nullptr, nullptr, &begin, &all) != SCANRS_OK || scanrs_mat_shape(made[i], &r, &c) != SCANRS_OK)
+                throw Failure{SCANRS_ERR_ARGUMENT};
+            const uint64_t local = mm->storage == SCANRS_CSR ? r : c;
+            if (begin != mm->bounds[i] || (i && all != outer_all)) fail(SCANRS_ERR_DEVICE, "internal: the result shards do not tile the outer dimension");
+            mm->bounds[i + 1] = begin + local;
+            outer_all = all;
+            inner = mm->storage == SCANRS_CSR ? c : r;
+        }
+        if (mm->bounds[n] != outer_all) fail(SCANRS_ERR_DEVICE, "internal: the result shards do not tile the outer dimension");
+        mm->rows = mm->storage == SCANRS_CSR ? outer_all : inner;
+        mm->cols = mm->storage == SCANRS_CSR ? inner : outer_all;
+        mm->group = local_group_make(n);
+        for (uint32_t i = 0; i < n; i++) mm->comms.push_back(comm_make_local(mm->group, i));
+        for (uint32_t i = 0; i < n; i++)
+            if (scanrs_mat_set_shard_comm(made[i], mm->comms[i], i, n, mm->bounds[i], outer_all) != SCANRS_OK) {
+                for (auto *c : mm->comms) scanrs_comm_free(c);
+                throw Failure{SCANRS_ERR_ARGUMENT};
+            }
+        mm->shards = std::move(made);
+        made.clear();
+        *out = mm.release();
+        return SCANRS_OK;
+    } catch (const Failure &e) {
+        free_shards(src, made);
+        return e.code;
+    } catch (const std::exception &e) {
+        free_shards(src, made);
+        set_error("internal error: %s", e.what());
+        return SCANRS_ERR_DEVICE;
+    }
+}
+
+int multi_select(scanrs_multi *mm, bool rows_axis, const uint64_t *idx, uint64_t n_idx, scanrs_multi **out) {
+    if (!out) return bad_argument("null output handle");
+    *out = nullptr;
+    if (!mm) return bad_argument("null handle");
+    std::vector<scanrs_mat *> made(mm->shards.size(), nullptr);
+    const int rc = fan_out(mm, [&](size_t i) {
+        return rows_axis ? scanrs_mat_select_rows_sharded(mm->shards[i], idx, n_idx, &made[i]) : scanrs_mat_select_cols_sharded(mm->shards[i], idx, n_idx, &made[i]);
+    });
+    if (rc != SCANRS_OK) {
+        const std::string msg = scanrs_last_error(); // (freeing handles must not replace the message)
+        free_shards(mm, made);
+        set_error("%s", msg.c_str());
+        return rc;
+    }
+    return multi_adopt(mm, made, out);
+}
+
+} // namespace
+
+int scanrs_multi_shape(const scanrs_multi *mm, uint64_t *rows, uint64_t *cols, uint64_t *nnz, int *storage) {
+    if (!mm) return bad_argument("null handle");
+    if (rows) *rows = mm->rows;
+    if (cols) *cols = mm->cols;
+    if (storage) *storage = mm->storage;
+    if (nnz) {
+        *nnz = 0;
+        for (auto *h : mm->shards) {
+            uint64_t x = 0;
+            if (const int rc = scanrs_mat_nnz(h, &x)) return rc;
+            *nnz += x;
+        }
+    }
+    return SCANRS_OK;
+}
+
+int scanrs_multi_to_csmat(scanrs_multi *mm, uint64_t *indptr, uint32_t *indices, uint32_t *values) {
+    if (!mm || !indptr) return bad_argument("null argument");
+    const size_t n = mm->shards.size();
+    std::vector<uint64_t> first(n + 1, 0); // the place of every shard's first nonzero in the whole matrix
+    for (size_t i = 0; i < n; i++) {
+        uint64_t x = 0;
+        if (const int rc = scanrs_mat_nnz(mm->shards[i], &x)) return rc;
+        first[i + 1] = first[i] + x;
+    }
+    if (first[n] && (!indices || !values)) return bad_argument("null indices/values");
+    indptr[mm->bounds[n]] = first[n];
+    return fan_out(mm, [&](size_t i) {
+        const uint64_t lo = mm->bounds[i], hi = mm->bounds[i + 1];
+        std::vector<uint64_t> ip(hi - lo + 1);
+        const bool some = first[i + 1] > first[i];
+        if (const int rc = scanrs_mat_to_csmat(mm->shards[i], ip.data(), some ? indices + first[i] : nullptr, some ? values + first[i] : nullptr)) return rc;
+        for (uint64_t o = lo; o < hi; o++) indptr[o] = ip[o - lo] + first[i];
+        return (int)SCANRS_OK;
+    });
+}
+
+int scanrs_multi_select_rows(scanrs_multi *mm, const uint64_t *idx, uint64_t n_idx, scanrs_multi **out) { return multi_select(mm, true, idx, n_idx, out); }
+int scanrs_multi_select_cols(scanrs_multi *mm, const uint64_t *idx, uint64_t n_idx, scanrs_multi **out) { return multi_select(mm, false, idx, n_idx, out); }
+
+int scanrs_multi_partition_on_thresholds(scanrs_multi *mm, const double *row_threshold, const double *col_threshold, scanrs_multi **filtered,
+                                         scanrs_multi **residual, uint64_t *selected_rows, uint64_t *n_selected_rows, uint64_t *selected_cols,
+                                         uint64_t *n_selected_cols) {
+    if (filtered) *filtered = nullptr;
+    if (residual) *residual = nullptr;
+    if (!mm) return bad_argument("null handle");
+    if (!selected_rows || !n_selected_rows || !selected_cols || !n_selected_cols) return bad_argument("null argument");
+    const size_t n = mm->shards.size();
+    std::vector<scanrs_mat *> made_f(n, nullptr), made_r(n, nullptr);
+    int rc = fan_out(mm, [&](size_t i) {
+        scanrs_mat **pf = filtered ? &made_f[i] : nullptr, **pr = residual ? &made_r[i] : nullptr;
+        if (i == 0)
+            return scanrs_mat_partition_on_thresholds_sharded(mm->shards[i], row_threshold, col_threshold, pf, pr, selected_rows, n_selected_rows,
+                                                              selected_cols, n_selected_cols);
+        std::vector<uint64_t> sr(mm->rows + 1), sc(mm->cols + 1); // every shard computes the same complete lists
+        uint64_t nr = 0, nc = 0;
+        return scanrs_mat_partition_on_thresholds_sharded(mm->shards[i], row_threshold, col_threshold, pf, pr, sr.data(), &nr, sc.data(), &nc);
+    });
+    if (rc != SCANRS_OK) {
+        const std::string msg = scanrs_last_error();
+        free_shards(mm, made_f);
+        free_shards(mm, made_r);
+        set_error("%s", msg.c_str());
+        return rc;
+    }
+    scanrs_multi *hf = nullptr, *hr = nullptr;
+    if (filtered) rc = multi_adopt(mm, made_f, &hf);
+    if (rc == SCANRS_OK && residual) rc = multi_adopt(mm, made_r, &hr);
+    if (rc != SCANRS_OK) {
+        const std::string msg = scanrs_last_error();
+        scanrs_multi_free(hf);
+        free_shards(mm, made_r);
+        set_error("%s", msg.c_str());
+        return rc;
+    }
+    if (filtered) *filtered = hf;
+    if (residual) *residual = hr;
+    return SCANRS_OK;
+}
+
 } // extern "C"

@@ -55,6 +55,23 @@ void select_outer(Storage &st, const SparseCopy &cp, const uint64_t *idx, uint64
     SCANRS_SYNC(st.stream); // the index list is released on return
 }
 
+void select_outer_sharded(Storage &st, const SparseCopy &cp, const uint64_t *idx, uint64_t n_idx, SparseCopy &out, uint64_t *out_begin) {
+    // the list and the rank's own range decide everything, and every rank sees the same list: the refusals below come on every rank,
+    // before any device work, and no exchange is needed
+    checked_indices(idx, n_idx, st.shard.outer_global, "outer vectors");
+    for (uint64_t i = 1; i < n_idx; i++)
+        if (idx[i] < idx[i - 1])
+            fail(SCANRS_ERR_ARGUMENT,
+                 "the list along the sharded dimension must not descend: entry %llu is %llu after %llu (moving vectors between ranks is not supported)",
+                 (unsigned long long)i, (unsigned long long)idx[i], (unsigned long long)idx[i - 1]);
+    const uint64_t lo = st.shard.outer_begin, hi = lo + cp.n_outer;
+    const uint64_t *first = std::lower_bound(idx, idx + n_idx, lo), *last = std::lower_bound(first, idx + n_idx, hi);
+    std::vector<uint64_t> local(first, last);
+    for (uint64_t &x : local) x -= lo;
+    *out_begin = (uint64_t)(first - idx);
+    select_outer(st, cp, local.data(), local.size(), out);
+}
+
 void select_inner(Storage &st, const SparseCopy &cp, const uint64_t *idx, uint64_t n_idx, SparseCopy &out) {
     const std::vector<uint32_t> h = checked_indices(idx, n_idx, cp.n_inner, "positions on that axis");
     start_copy(st, cp, out, cp.n_outer, n_idx);
@@ -83,13 +100,25 @@ void select_inner(Storage &st, const SparseCopy &cp, const uint64_t *idx, uint64
 }
 
 uint64_t partition_on_thresholds(Storage &st, const SparseCopy &cp, const double *thr_outer, const double *thr_inner, bool cols_inner,
-                                 std::vector<uint8_t> &excl_outer, std::vector<uint8_t> &excl_inner, SparseCopy *filtered, SparseCopy *residual) {
+                                 std::vector<uint8_t> &excl_outer, std::vector<uint8_t> &excl_inner, SparseCopy *filtered, SparseCopy *residual,
+                                 PartitionShard *sh) {
     hipStream_t s = st.stream;
     const uint64_t no = cp.n_outer, ni = cp.n_inner;
-    if (no >= 0x7FFFFFFFull || ni >= 0x7FFFFFFFull) fail(SCANRS_ERR_SHAPE, "partition_on_thresholds needs dimensions below 2^31 - 1");
+    // sh: cp is this rank's shard of outer_global outer vectors. The inner positions, their mask and the round's flag are
+    // replicated: every rank marks them from the same reduced sums. The outer vectors, their sums and their mask stay local.
+    const uint64_t no_all = sh ? st.shard.outer_global : no;
+    if (no_all >= 0x7FFFFFFFull || ni >= 0x7FFFFFFFull) fail(SCANRS_ERR_SHAPE, "partition_on_thresholds needs dimensions below 2^31 - 1");
+    if (sh) sh->allreduces = 0;
+    auto exchange = [&](unsigned long long *d, uint64_t count) {
+        if (!count) return;
+        allreduce_u64(st, d, count);
+        sh->allreduces++;
+    };
     DevBuf<uint8_t> d_eo(std::max<uint64_t>(1, no)), d_ei(std::max<uint64_t>(1, ni)), d_no(std::max<uint64_t>(1, no)), d_ni(std::max<uint64_t>(1, ni));
     DevBuf<unsigned long long> d_so(std::max<uint64_t>(1, no)), d_si(std::max<uint64_t>(1, ni));
-    DevBuf<uint32_t> d_flag(1);
+    DevBuf<unsigned long long> d_sr; // sharded: the reduced copy of the inner sums (d_si keeps this rank's own, for the subtraction)
+    if (sh && thr_inner) d_sr.alloc(std::max<uint64_t>(1, ni));
+    DevBuf<uint32_t> d_flag(2); // (8 bytes: a sharded call sums the flag over the ranks as one u64)
     SCANRS_HIP(hipMemsetAsync(d_eo.p, 0, d_eo.n, s));
     SCANRS_HIP(hipMemsetAsync(d_ei.p, 0, d_ei.n, s));
     SCANRS_HIP(hipMemsetAsync(d_no.p, 0, d_no.n, s));
@@ -112,11 +141,17 @@ uint64_t partition_on_thresholds(Storage &st, const SparseCopy &cp, const double
             launch_sel_inner_sums(s, cp, d_no.p, 1, true, d_ei.p, d_si.p);
         }
         SCANRS_HIP(hipMemsetAsync(d_no.p, 0, d_no.n, s));
-        launch_sel_mark(s, d_si.p, ni, *thr_inner, d_ei.p, d_ni.p, d_flag.p);
+        const unsigned long long *sums = d_si.p;
+        if (sh) {
+            if (ni) SCANRS_HIP(hipMemcpyAsync(d_sr.p, d_si.p, ni * 8, hipMemcpyDeviceToDevice, s));
+            exchange(d_sr.p, ni);
+            sums = d_sr.p;
+        }
+        launch_sel_mark(s, sums, ni, *thr_inner, d_ei.p, d_ni.p, d_flag.p);
     };
     uint64_t rounds = 0;
     for (;;) { // mat.rs:783-806: columns first, then rows over the columns as just updated, until a round adds nothing
-        SCANRS_HIP(hipMemsetAsync(d_flag.p, 0, 4, s));
+        SCANRS_HIP(hipMemsetAsync(d_flag.p, 0, 8, s));
         if (cols_inner) {
             step_inner();
             step_outer();
@@ -125,6 +160,9 @@ uint64_t partition_on_thresholds(Storage &st, const SparseCopy &cp, const double
             step_inner();
         }
         rounds++;
+        // the outer marks are local news: the ranks agree on the flag before they read it, and so stop in the same round (the inner
+        // marks come from replicated sums and set the same flag everywhere)
+        if (sh && thr_outer) exchange(reinterpret_cast<unsigned long long *>(d_flag.p), 1);
         if (!SCANRS_D2H_VALUE(d_flag.p, s)) break; // the one value a round sends back
     }
     excl_outer.assign(no, 0);
@@ -132,6 +170,18 @@ uint64_t partition_on_thresholds(Storage &st, const SparseCopy &cp, const double
     if (no) SCANRS_D2H(excl_outer.data(), d_eo.p, no, s);
     if (ni) SCANRS_D2H(excl_inner.data(), d_ei.p, ni, s);
     SCANRS_SYNC(s);
+    if (sh) {
+        // the outer mask of the whole matrix: every rank puts its bytes at its place in a zero-filled array of u64 words; one
+        // contributor per byte, so the sum is a copy (no carries)
+        const uint64_t words = (no_all + 7) / 8;
+        DevBuf<unsigned long long> d_all(std::max<uint64_t>(1, words));
+        SCANRS_HIP(hipMemsetAsync(d_all.p, 0, words * 8, s));
+        if (no) SCANRS_HIP(hipMemcpyAsync(reinterpret_cast<uint8_t *>(d_all.p) + st.shard.outer_begin, d_eo.p, no, hipMemcpyDeviceToDevice, s));
+        exchange(d_all.p, words);
+        sh->excl_outer_all.assign(no_all, 0);
+        if (no_all) SCANRS_D2H(sh->excl_outer_all.data(), d_all.p, no_all, s);
+        SCANRS_SYNC(s);
+    }
     if (!filtered && !residual) return rounds;
 
     // where every vector and every inner position goes (part_count_kernel / part_fill_kernel)

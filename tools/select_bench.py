@@ -4,7 +4,11 @@ time of `--reps` runs after one warm-up (every call returns synchronised), the b
 shapes, GB/s and the share of the MI355X HBM peak, and beside it the host route that was the only way before these calls existed
 (scipy slicing of the same matrix + AdaptiveMat.from_csmat), timed once in the same process. One JSON line per storage.
 
-    python tools/select_bench.py [--cells 1000000] [--genes 33000] [--storages csc,csr] [--reps 5] [--no-host]
+    python tools/select_bench.py [--cells 1000000] [--genes 33000] [--storages csc,csr] [--reps 5] [--no-host] [--shards N]
+
+--shards N: the partition rows and the select rows of the table through a MultiMat of N shards, all on device 0 (on
+one device this measures the overhead of the scheme, not a speed-up), with the rounds, the exchange steps and the bytes that went
+through shard 0's communicator per call, and a check that the concatenated results equal the single handle's arrays.
 """
 import argparse
 import json
@@ -40,6 +44,55 @@ def entry(ms, nbytes, host_ms=None, **extra):
         e["faster_than_host_route"] = bool(ms < host_ms)
     e.update(extra)
     return e
+
+
+def same_arrays(a, b):
+    return bool(all(np.array_equal(x, y) for x, y in zip(a, b)))
+
+
+def sharded_cases(m, mm, storage, a, row_q, col_q, lists):
+    """The rows of the table through the MultiMat mm, each against the same call on the single handle m."""
+    out = {}
+
+    def comm_delta(fn):
+        before = mm.comm_info(0)
+        r = fn()
+        after = mm.comm_info(0)
+        return r, after["allreduce_calls"] - before["allreduce_calls"], after["allreduce_bytes"] - before["allreduce_bytes"]
+
+    for name, (row_t, col_t) in (("partition_quantile_0.1", (row_q, col_q)), ("partition_on_threshold_3", (3.0, 3.0))):
+        t_rounds = timed(lambda: mm.partition_on_thresholds(row_t, col_t, filtered=False, residual=False), a.reps)
+        alloc0 = (m.counter("t_alloc_us"), m.counter("alloc_calls"))  # process-wide: what the calls below spend in hipMalloc
+        t_all = timed(lambda: mm.partition_on_thresholds(row_t, col_t), a.reps)
+        alloc_ms, alloc_calls = (m.counter("t_alloc_us") - alloc0[0]) / 1e3 / (a.reps + 1), (m.counter("alloc_calls") - alloc0[1]) / (a.reps + 1)
+        (f, r, sr, sc), calls, nbytes = comm_delta(lambda: mm.partition_on_thresholds(row_t, col_t))
+        sf, sr_, ssr, ssc = m.partition_on_thresholds(row_t, col_t)
+        same = bool(np.array_equal(sr, ssr) and np.array_equal(sc, ssc)) and same_arrays(f.to_csmat(), sf.to_csmat()) and same_arrays(r.to_csmat(), sr_.to_csmat())
+        out[name] = {
+            "ms": round(t_all, 3), "rounds_only_ms": round(t_rounds, 3), "hipmalloc_ms_per_call": round(alloc_ms, 3),
+            "hipmalloc_calls_per_call": round(alloc_calls, 1), "rounds": mm.counter("partition_rounds"),
+            "rounds_single_handle": m.counter("partition_rounds"), "exchange_steps": mm.counter("partition_allreduces"),
+            "comm_calls": int(calls), "comm_bytes": int(nbytes), "result_shard_ranges": [[lo, hi] for _, lo, hi in f.shard_ranges()],
+            "equals_single_handle": same,
+        }
+        f.close()
+        r.close()
+        del sf, sr_
+    rows_outer = storage == sa.CSR
+    for name, fn_m, fn_s, idx, on_sharded_axis in (
+            ("select_rows_2000_ascending", mm.select_rows, m.select_rows, lists[0], rows_outer),
+            ("select_rows_2000_shuffled", mm.select_rows, m.select_rows, lists[1], rows_outer),
+            ("select_cols_every_second", mm.select_cols, m.select_cols, lists[2], not rows_outer)):
+        if on_sharded_axis and np.any(np.diff(idx) < 0):
+            out[name] = {"refused": "a list along the sharded dimension must not descend"}
+            continue
+        ms = timed(lambda: fn_m(idx), a.reps)
+        got, calls, nbytes = comm_delta(lambda: fn_m(idx))
+        want = fn_s(idx)
+        out[name] = {"ms": round(ms, 3), "comm_calls": int(calls), "comm_bytes": int(nbytes), "equals_single_handle": same_arrays(got.to_csmat(), want.to_csmat())}
+        got.close()
+        del want
+    return out
 
 
 def host_upload(m, storage):
@@ -80,6 +133,7 @@ def main():
     ap.add_argument("--reps", type=int, default=5)
     ap.add_argument("--select-genes", type=int, default=2000)
     ap.add_argument("--no-host", action="store_true", help="skip the host routes (device numbers only)")
+    ap.add_argument("--shards", type=int, default=0, help="run the table through a MultiMat of this many shards, all on device 0")
     a = ap.parse_args()
     import scipy.sparse as sp
     import torch
@@ -96,10 +150,13 @@ def main():
     csc = sp.csc_matrix((data, indices.astype(np.int32), indptr.astype(np.int64)), shape=(a.genes, a.cells))
     csc.has_sorted_indices = True
     del indptr, indices, data
-    csr = csc.tocsr()
-    csr.sort_indices()
     nnz = int(csc.nnz)
-    row_sums, col_sums = np.asarray(csr.sum(axis=1)).ravel(), np.asarray(csc.sum(axis=0)).ravel()
+    csr = None  # the gene-major orientation on the host: for the CSR handle and for the host routes
+    if "csr" in a.storages.split(",") or not (a.no_host or a.shards):
+        csr = csc.tocsr()
+        csr.sort_indices()
+    row_sums = np.bincount(csc.indices, weights=csc.data, minlength=a.genes)  # (exact: every sum is far below 2^53)
+    col_sums = np.asarray(csc.sum(axis=0)).ravel()
     row_q, col_q = (float(np.quantile(s.astype(np.float64), 0.1, method="midpoint")) for s in (row_sums, col_sums))
     rng = np.random.default_rng(a.seed)
     genes_sorted = np.sort(rng.choice(a.genes, min(a.select_genes, a.genes), replace=False))
@@ -111,6 +168,16 @@ def main():
         host, other = (csr, csc) if storage == sa.CSR else (csc, csr)
         m = base if storage == sa.CSC else host_upload(csr, sa.CSR)
         out = {"storage": name, "cells": a.cells, "genes": a.genes, "nnz": nnz, "hbm_peak_GB_per_s": HBM_BYTES_PER_S / 1e9, "reps": a.reps}
+        if a.shards:
+            mm = sa.MultiMat(a.genes, a.cells, storage, host.indptr, host.indices, host.data, a.shards, devices=[0] * a.shards)
+            out["shards"] = a.shards
+            out["shard_ranges"] = [[lo, hi] for _, lo, hi in mm.shard_ranges()]
+            out.update(sharded_cases(m, mm, storage, a, row_q, col_q, (genes_sorted, genes_shuffled, every_second)))
+            mm.close()
+            print(json.dumps(out), flush=True)
+            if m is not base:
+                del m
+            continue
 
         def partition_case(row_t, col_t):
             t_rounds = timed(lambda: m.partition_on_thresholds(row_t, col_t, filtered=False, residual=False), a.reps)
