@@ -171,7 +171,8 @@ int scanrs_mat_to_dense(scanrs_mat *m, double *out);
  * vectors with the new positions; that is not reproduced). A sharded handle is served by the collective entry points
  * scanrs_mat_select_rows_sharded / scanrs_mat_select_cols_sharded / scanrs_mat_partition_on_thresholds_sharded below, and a
  * scanrs_multi by scanrs_multi_select_rows / _select_cols / _partition_on_thresholds. Unchanged: the column-list statistics,
- * scanrs_sseq_de_pairs and scanrs_merge_clusters stay refused on a sharded handle, and scanrs_mat_to_adaptive exports a rank's own
+ * scanrs_sseq_de_pairs and scanrs_merge_clusters stay refused on a sharded handle (their collective forms are
+ * scanrs_sseq_de_pairs_sharded and scanrs_merge_clusters_sharded), and scanrs_mat_to_adaptive exports a rank's own
  * shard only. Transposed views work: rows of the view are columns of the stored matrix,
  * and a result's storage flag is the view's (scanrs_mat_storage). Every result is a fresh, independent handle with its own
  * storage, default options and the identity map, made on the device from the handle's own storage (no transposed copy is built, nothing
@@ -600,8 +601,9 @@ int scanrs_mat_set_option(scanrs_mat *m, const char *key, double value);
  * per pair of passes, "tile_served_nonzeros" = nonzeros among them (the rest is padding), "tile_overflow_nonzeros" = nonzeros left
  * to the overflow gather. "partition_rounds" = rounds of the last scanrs_mat_partition_on_thresholds on this handle, the final round
  * that changes nothing included; "partition_allreduces" = the exchange steps of the last scanrs_mat_partition_on_thresholds_sharded
- * (0 on an unsharded handle). "de_pairs_passes" / "de_pairs_literal" = the last scanrs_sseq_de_pairs on this handle: its passes over
- * the nonzeros and its pairs on the literal route. "de_shard_tests" / "de_shard_allreduces" = the last sSeq DE call on this handle: the
+ * (0 on an unsharded handle). "de_pairs_passes" / "de_pairs_literal" = the last scanrs_sseq_de_pairs[_sharded] on this handle: its passes over
+ * the nonzeros and its pairs on the literal route. "de_shard_tests" / "de_shard_allreduces" = the last sSeq DE call (scanrs_sseq_de_pairs_sharded,
+ * scanrs_merge_clusters_sharded and scanrs_cluster_medoids_sharded included) on this handle: the
  * tests this rank launched on the device, and the exchange steps of a sharded handle (0 on an unsharded one). "subset_masked_passes" / "subset_scatter_passes" = sums over a column list made on
  * this handle so far: from the copy whose outer dimension is the result axis (masked walk or listed vectors, no atomics) / through the
  * integer scatter from the other copy ("subset_scatter"). */
@@ -741,7 +743,8 @@ int scanrs_host_sym_eig_topk(const double *a, int n, int k, double *w, double *z
  * (scanrs_mat_get_counter): "de_shard_tests" = the tests this rank launched on the device in the last DE call (an unsharded
  * handle: all of them), "de_shard_allreduces" = the exchange steps of the last params / group sums / DE call.
  * What stays refused on a sharded handle (SCANRS_ERR_ARGUMENT, "sharded" in scanrs_last_error()): scanrs_sseq_de_pairs,
- * scanrs_merge_clusters and the statistics over a column list (scanrs_mat_sum_rows and its kin). */
+ * scanrs_merge_clusters and the statistics over a column list (scanrs_mat_sum_rows and its kin). The first two are served through
+ * collective entry points of their own, scanrs_sseq_de_pairs_sharded and scanrs_merge_clusters_sharded (declared beside them). */
 
 /* `compute_sseq_params` (diff_exp.rs:458-500). cell_indices (n_sel entries, or NULL for every cell): only those cells get a
  * size factor, the rest 0. umi_counts (one per selected cell, or NULL): replaces the per-cell totals. Size factors are the
@@ -824,6 +827,28 @@ int scanrs_sseq_de_pairs(scanrs_mat *m, const int16_t *labels, uint32_t n_groups
                          uint32_t n_pairs, double zeta_quintile, uint64_t big_count, int backend, const scanrs_snoop *snoop,
                          uint64_t *sums_in, uint64_t *sums_out, double *p, double *p_adj, double *log2fc, double *mean_in,
                          double *mean_out, scanrs_sseq_pair_params *params /* may be NULL */);
+/* scanrs_sseq_de_pairs over a sharded matrix. scanrs_sseq_de_pairs_sharded is COLLECTIVE: every rank of the handle's
+ * communicator (or host hook) calls it with the same arguments, which are those of scanrs_sseq_de_pairs. The CELLS must be the sharded
+ * dimension (a handle sharded over the genes returns SCANRS_ERR_ARGUMENT), `labels` spans the WHOLE matrix (outer_global entries; each
+ * rank uploads only its own slice), and every rank receives the same complete outputs. All argument checks run before the first
+ * exchange and depend on the global arguments only. Every output, the per-pair parameters included, equals scanrs_sseq_de_pairs on
+ * one unsharded handle of the whole matrix bit for bit, for any number of shards and any transport: only u64 sums cross the shards
+ * (dtype 1 of scanrs_allreduce_fn) - the per-cell totals, the grouped accumulators (Σ x as it is, the two 128-bit moments as two
+ * 32-bit halves of the low word plus the high word, in tiles of 2^20 (group, gene) entries through a fixed scratch of 56 MiB) and
+ * the bit patterns of the p-values, whose tests are split over the ranks by gene as in scanrs_sseq_de. The group statistics, the pair
+ * headers and the per-pair parameters run replicated on every rank from the reduced integers; a literal pair runs the sharded
+ * scanrs_sseq_params + scanrs_sseq_de calls on every rank. Counters: "de_shard_allreduces" = the exchange steps of the last call
+ * (2 + the accumulator tiles + 5 per literal pair), "de_shard_tests" = the tests this rank launched. On an unsharded handle the call
+ * is scanrs_sseq_de_pairs. scanrs_multi_sseq_de_pairs runs the collective call on every shard of a scanrs_multi from one process
+ * (transposed != 0: the matrix was created cells x genes); shard 0 writes the caller's arrays and reports progress. */
+int scanrs_sseq_de_pairs_sharded(scanrs_mat *m, const int16_t *labels, uint32_t n_groups, const uint32_t *pair_a, const uint32_t *pair_b,
+                                 uint32_t n_pairs, double zeta_quintile, uint64_t big_count, int backend, const scanrs_snoop *snoop,
+                                 uint64_t *sums_in, uint64_t *sums_out, double *p, double *p_adj, double *log2fc, double *mean_in,
+                                 double *mean_out, scanrs_sseq_pair_params *params /* may be NULL */);
+int scanrs_multi_sseq_de_pairs(scanrs_multi *mm, int transposed, const int16_t *labels, uint32_t n_groups, const uint32_t *pair_a,
+                               const uint32_t *pair_b, uint32_t n_pairs, double zeta_quintile, uint64_t big_count, int backend,
+                               const scanrs_snoop *snoop, uint64_t *sums_in, uint64_t *sums_out, double *p, double *p_adj, double *log2fc,
+                               double *mean_in, double *mean_out, scanrs_sseq_pair_params *params /* may be NULL */);
 /* percentile_of_sorted(.., 50) (stat.rs:140-162) of the union of two ascending lists; host only */
 int scanrs_host_union_median(const double *a, uint64_t n_a, const double *b, uint64_t n_b, double *out);
 /* the shared math on the host (no device needed; the kernels run the same special functions): `nb_exact_test`
@@ -888,6 +913,30 @@ typedef struct {
  * and the pairwise DE on the device, call for call as the reference (the A/B baseline). */
 int scanrs_merge_clusters(scanrs_mat *m, const double *pca, int pca_is_device, uint32_t ld, uint32_t d, const int16_t *labels,
                           int16_t *labels_out, const scanrs_snoop *snoop, scanrs_merge_trace *trace);
+/* merge_clusters and the medoids over a sharded matrix. scanrs_merge_clusters_sharded and
+ * scanrs_cluster_medoids_sharded are COLLECTIVE: every rank of the handle's communicator (or host hook) calls them with the same
+ * arguments, those of scanrs_merge_clusters and of scanrs_cluster_medoids (the handle of the latter only carries the transport and the
+ * rank's range of cells). The CELLS must be the sharded dimension; `labels` spans the WHOLE matrix, and so does a host `pca`
+ * (outer_global x ld, pca_is_device = 0), of which each rank uploads only its own rows; with pca_is_device != 0 the pointer holds the
+ * rank's OWN cells only (local columns x ld, e.g. *d_v of scanrs_pca_result_device). labels_out, the trace and the centers are
+ * complete and the same on every rank, and equal the unsharded call's bit for bit: only u64 sums cross the shards (dtype 1). A
+ * median is selected exactly over the ranks: each of the 8 radix rounds adds the local keys that match the current prefix into
+ * 256-bin integer histograms per (cluster, column, wanted rank), all-reduces the table (at most 4096 (cluster, column) pairs = 16 MiB
+ * at a time) and picks the bucket on every rank; the first cell holding a NaN is the minimum over one slot per rank. The fused route
+ * gathers the totals and reduces the grouped accumulators as scanrs_sseq_de_pairs_sharded does; the candidates then run replicated,
+ * their tests split over the ranks by gene (one exchange per candidate); the literal route is the sharded scanrs_sseq_params +
+ * scanrs_sseq_de. Every rank polls the cancel flag before the same candidates. Counters: "de_shard_allreduces" = the exchange steps
+ * of the last call, "de_shard_tests" = the tests this rank launched. On an unsharded handle the calls are the plain ones.
+ * scanrs_multi_merge_clusters / scanrs_multi_cluster_medoids run the collective calls on every shard of a scanrs_multi from one
+ * process; pca is a host array over all cells. */
+int scanrs_merge_clusters_sharded(scanrs_mat *m, const double *pca, int pca_is_device, uint32_t ld, uint32_t d, const int16_t *labels,
+                                  int16_t *labels_out, const scanrs_snoop *snoop, scanrs_merge_trace *trace);
+int scanrs_cluster_medoids_sharded(scanrs_mat *m, const double *pca, int pca_is_device, uint32_t ld, uint32_t d, const int16_t *labels,
+                                   uint32_t k, double *centers);
+int scanrs_multi_merge_clusters(scanrs_multi *mm, int transposed, const double *pca, uint32_t ld, uint32_t d, const int16_t *labels,
+                                int16_t *labels_out, const scanrs_snoop *snoop, scanrs_merge_trace *trace);
+int scanrs_multi_cluster_medoids(scanrs_multi *mm, int transposed, const double *pca, uint32_t ld, uint32_t d, const int16_t *labels,
+                                 uint32_t k, double *centers);
 
 /* ---- 10x HDF5 ingestion (hdf5-io/src/matrix.rs, analysis.rs). Host-side; no device needed.
  * The files are parsed by the library's own reader (csrc/h5lite.cpp) — no libhdf5 dependency. Failures are

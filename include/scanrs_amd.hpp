@@ -838,11 +838,11 @@ struct PairParams : SSeqParams { // size_factors stays empty, as in sseq_params_
     uint64_t num_cells_a = 0, num_cells_b = 0;
     bool literal = false; // the union's median total was 0: the pair ran the two reference calls themselves
 };
-inline std::pair<std::vector<DiffExpResult>, std::vector<PairParams>> sseq_de_pairs(
-    const AdaptiveMat &m, const std::vector<int16_t> &labels, uint32_t n_groups, const std::vector<std::pair<uint32_t, uint32_t>> &pairs,
-    double zeta_quintile = ZETA_QUINTILE_DEFAULT, uint64_t big_count = BIG_COUNT_DEFAULT, NbExactBackend backend = NbExactBackend::LogSpace,
-    Snoop *snoop = nullptr) {
-    const uint64_t g = m.rows();
+// `call` is one of the three entry points with the handle bound: (labels, n_groups, pair_a, pair_b, n_pairs, ..., params) -> code
+template <typename Call>
+inline std::pair<std::vector<DiffExpResult>, std::vector<PairParams>> sseq_de_pairs_with(
+    Call &&call, uint64_t g, const std::vector<int16_t> &labels, uint32_t n_groups, const std::vector<std::pair<uint32_t, uint32_t>> &pairs,
+    double zeta_quintile, uint64_t big_count, NbExactBackend backend, Snoop *snoop) {
     const uint32_t t = (uint32_t)pairs.size();
     std::vector<uint32_t> pa(t), pb(t);
     for (uint32_t j = 0; j < t; j++) pa[j] = pairs[j].first, pb[j] = pairs[j].second;
@@ -853,8 +853,8 @@ inline std::pair<std::vector<DiffExpResult>, std::vector<PairParams>> sseq_de_pa
     scanrs_sseq_pair_params pp = {mean.data(), var.data(), mm.data(), phi.data(), use.data(), zh.data(), dl.data(), fa.data(),
                                   fb.data(), med.data(), ssf.data(), na.data(), nb.data(), lit.data()};
     scanrs_snoop sn = detail::make_snoop(snoop);
-    check(scanrs_sseq_de_pairs(m.raw(), labels.data(), n_groups, pa.data(), pb.data(), t, zeta_quintile, big_count, (int)backend,
-                               snoop ? &sn : nullptr, si.data(), so.data(), pv.data(), pq.data(), l2.data(), mi.data(), mo.data(), &pp));
+    check(call(labels.data(), n_groups, pa.data(), pb.data(), t, zeta_quintile, big_count, (int)backend, snoop ? &sn : nullptr, si.data(), so.data(),
+               pv.data(), pq.data(), l2.data(), mi.data(), mo.data(), &pp));
     std::vector<DiffExpResult> out(t);
     std::vector<PairParams> prm(t);
     for (uint32_t j = 0; j < t; j++) {
@@ -881,6 +881,30 @@ inline std::pair<std::vector<DiffExpResult>, std::vector<PairParams>> sseq_de_pa
         }
     }
     return {std::move(out), std::move(prm)};
+}
+inline std::pair<std::vector<DiffExpResult>, std::vector<PairParams>> sseq_de_pairs(
+    const AdaptiveMat &m, const std::vector<int16_t> &labels, uint32_t n_groups, const std::vector<std::pair<uint32_t, uint32_t>> &pairs,
+    double zeta_quintile = ZETA_QUINTILE_DEFAULT, uint64_t big_count = BIG_COUNT_DEFAULT, NbExactBackend backend = NbExactBackend::LogSpace,
+    Snoop *snoop = nullptr) {
+    return sseq_de_pairs_with([&](auto... a) { return scanrs_sseq_de_pairs(m.raw(), a...); }, m.rows(), labels, n_groups, pairs, zeta_quintile,
+                              big_count, backend, snoop);
+}
+// The collective form on one sharded handle (every rank calls it with the same arguments; labels span the whole matrix), and the same
+// over the shards of a MultiMat from one process (scanrs_sseq_de_pairs_sharded, scanrs_multi_sseq_de_pairs): the cells
+// must be the sharded dimension, and every output equals the unsharded call's bit for bit.
+inline std::pair<std::vector<DiffExpResult>, std::vector<PairParams>> sseq_de_pairs_sharded(
+    const AdaptiveMat &m, const std::vector<int16_t> &labels, uint32_t n_groups, const std::vector<std::pair<uint32_t, uint32_t>> &pairs,
+    double zeta_quintile = ZETA_QUINTILE_DEFAULT, uint64_t big_count = BIG_COUNT_DEFAULT, NbExactBackend backend = NbExactBackend::LogSpace,
+    Snoop *snoop = nullptr) {
+    return sseq_de_pairs_with([&](auto... a) { return scanrs_sseq_de_pairs_sharded(m.raw(), a...); }, m.rows(), labels, n_groups, pairs,
+                              zeta_quintile, big_count, backend, snoop);
+}
+inline std::pair<std::vector<DiffExpResult>, std::vector<PairParams>> sseq_de_pairs(
+    const MultiMat &m, bool transposed, const std::vector<int16_t> &labels, uint32_t n_groups,
+    const std::vector<std::pair<uint32_t, uint32_t>> &pairs, double zeta_quintile = ZETA_QUINTILE_DEFAULT, uint64_t big_count = BIG_COUNT_DEFAULT,
+    NbExactBackend backend = NbExactBackend::LogSpace, Snoop *snoop = nullptr) {
+    return sseq_de_pairs_with([&](auto... a) { return scanrs_multi_sseq_de_pairs(m.raw(), transposed ? 1 : 0, a...); },
+                              transposed ? m.cols() : m.rows(), labels, n_groups, pairs, zeta_quintile, big_count, backend, snoop);
 }
 // percentile_of_sorted(.., 50) (stat.rs:140-162) of the union of two ascending lists, on the host
 inline double host_union_median(const std::vector<double> &a, const std::vector<double> &b) {
@@ -944,18 +968,16 @@ struct MergeTrace {
     std::vector<MergeCandidate> candidates;
     uint64_t n_candidates = 0, n_rounds = 0, n_merges = 0, n_passes = 0;
 };
-// merge_clusters.rs:59-138: pca is cells x d (leading dimension ld), in device memory when pca_is_device
-inline std::vector<int16_t> merge_clusters(const AdaptiveMat &m, const double *pca, bool pca_is_device, uint32_t ld, uint32_t d,
-                                           const std::vector<int16_t> &labels, MergeTrace *trace = nullptr, Snoop *snoop = nullptr,
-                                           uint64_t capacity = 4096) {
+// `call` is one of the three entry points with the handle and the scores bound: (labels, labels_out, snoop, trace) -> code
+template <typename Call>
+inline std::vector<int16_t> merge_clusters_with(Call &&call, const std::vector<int16_t> &labels, MergeTrace *trace, Snoop *snoop, uint64_t capacity) {
     std::vector<int16_t> out(labels.size());
     scanrs_snoop sn = detail::make_snoop(snoop);
     std::vector<int16_t> l0(capacity), l1(capacity);
     std::vector<uint64_t> nde(capacity);
     std::vector<double> mp(capacity);
     scanrs_merge_trace t{capacity, l0.data(), l1.data(), nde.data(), mp.data(), 0, 0, 0, 0};
-    check(scanrs_merge_clusters(m.raw(), pca, pca_is_device ? 1 : 0, ld, d, labels.data(), out.data(), snoop ? &sn : nullptr,
-                                trace ? &t : nullptr));
+    check(call(labels.data(), out.data(), snoop ? &sn : nullptr, trace ? &t : nullptr));
     if (trace) {
         trace->candidates.clear();
         for (uint64_t i = 0; i < t.n_candidates && i < capacity; i++) trace->candidates.push_back({l0[i], l1[i], nde[i], mp[i]});
@@ -964,6 +986,40 @@ inline std::vector<int16_t> merge_clusters(const AdaptiveMat &m, const double *p
         trace->n_merges = t.n_merges;
         trace->n_passes = t.n_passes;
     }
+    return out;
+}
+// merge_clusters.rs:59-138: pca is cells x d (leading dimension ld), in device memory when pca_is_device
+inline std::vector<int16_t> merge_clusters(const AdaptiveMat &m, const double *pca, bool pca_is_device, uint32_t ld, uint32_t d,
+                                           const std::vector<int16_t> &labels, MergeTrace *trace = nullptr, Snoop *snoop = nullptr,
+                                           uint64_t capacity = 4096) {
+    return merge_clusters_with([&](auto... a) { return scanrs_merge_clusters(m.raw(), pca, pca_is_device ? 1 : 0, ld, d, a...); }, labels, trace,
+                               snoop, capacity);
+}
+// The collective forms on one sharded handle (every rank calls them with the same arguments; labels span the whole matrix, and so does a
+// host pca; a device pca holds the rank's own cells), and the same over the shards of a MultiMat from one process (pca: a host array
+// over all cells). The cells must be the sharded dimension; results equal the unsharded call's bit for bit.
+inline std::vector<int16_t> merge_clusters_sharded(const AdaptiveMat &m, const double *pca, bool pca_is_device, uint32_t ld, uint32_t d,
+                                                   const std::vector<int16_t> &labels, MergeTrace *trace = nullptr, Snoop *snoop = nullptr,
+                                                   uint64_t capacity = 4096) {
+    return merge_clusters_with([&](auto... a) { return scanrs_merge_clusters_sharded(m.raw(), pca, pca_is_device ? 1 : 0, ld, d, a...); }, labels,
+                               trace, snoop, capacity);
+}
+inline std::vector<int16_t> merge_clusters(const MultiMat &m, bool transposed, const double *pca, uint32_t ld, uint32_t d,
+                                           const std::vector<int16_t> &labels, MergeTrace *trace = nullptr, Snoop *snoop = nullptr,
+                                           uint64_t capacity = 4096) {
+    return merge_clusters_with([&](auto... a) { return scanrs_multi_merge_clusters(m.raw(), transposed ? 1 : 0, pca, ld, d, a...); }, labels, trace,
+                               snoop, capacity);
+}
+inline std::vector<double> cluster_medoids_sharded(const AdaptiveMat &m, const double *pca, bool pca_is_device, uint32_t ld, uint32_t d,
+                                                   const std::vector<int16_t> &labels, uint32_t k) {
+    std::vector<double> out((size_t)k * d);
+    check(scanrs_cluster_medoids_sharded(m.raw(), pca, pca_is_device ? 1 : 0, ld, d, labels.data(), k, out.data()));
+    return out;
+}
+inline std::vector<double> cluster_medoids(const MultiMat &m, bool transposed, const double *pca, uint32_t ld, uint32_t d,
+                                           const std::vector<int16_t> &labels, uint32_t k) {
+    std::vector<double> out((size_t)k * d);
+    check(scanrs_multi_cluster_medoids(m.raw(), transposed ? 1 : 0, pca, ld, d, labels.data(), k, out.data()));
     return out;
 }
 } // namespace cluster

@@ -1177,6 +1177,14 @@ class MultiMat:
         _check(_lib.scanrs_mat_get_counter(h, key.encode(), ctypes.byref(v)))
         return int(v.value)
 
+    def set_option(self, key: str, value: float):
+        """`scanrs_mat_set_option` on every shard (e.g. "merge_fused")."""
+        for i in range(self.n_shards):
+            h = ctypes.c_void_p()
+            _check(_lib.scanrs_multi_shard(self._h, ctypes.c_uint32(i), ctypes.byref(h), None, None, None))
+            _check(_lib.scanrs_mat_set_option(h, key.encode(), ctypes.c_double(value)))
+        return self
+
     def run_pca_irlba(self, k: int, tol: float = 1e-4, max_iter: int = 50, v0=None):
         u, s, v = np.zeros((self.rows, k)), np.zeros(k), np.zeros((self.cols, k))
         v0c = None if v0 is None else _f64(v0)
@@ -1316,6 +1324,7 @@ EXPORTED_SYMBOLS = [
     "scanrs_normalize", "scanrs_log_normalize", "scanrs_log1p_normalize_fixed_point", "scanrs_mat_target_umi",
     "scanrs_pca_bk", "scanrs_pca_rand", "scanrs_pca_irlba", "scanrs_pca_result_device", "scanrs_knn_device", "scanrs_omega_fill", "scanrs_mat_set_shard", "scanrs_mat_set_shard_comm", "scanrs_comm_get_unique_id", "scanrs_comm_create", "scanrs_comm_free",
     "scanrs_multi_create", "scanrs_multi_free", "scanrs_multi_n_shards", "scanrs_multi_shard", "scanrs_multi_normalize", "scanrs_multi_pca_bk", "scanrs_multi_pca_rand", "scanrs_multi_pca_irlba", "scanrs_multi_log_normalize", "scanrs_multi_sseq_params", "scanrs_multi_group_sums", "scanrs_multi_sseq_de", "scanrs_multi_comm_info",
+    "scanrs_sseq_de_pairs_sharded", "scanrs_merge_clusters_sharded", "scanrs_cluster_medoids_sharded", "scanrs_multi_sseq_de_pairs", "scanrs_multi_merge_clusters", "scanrs_multi_cluster_medoids",
     "scanrs_plan_shards", "scanrs_profile_enable", "scanrs_profile_reset", "scanrs_profile_get", "scanrs_mat_sync", "scanrs_mat_set_spmm_path", "scanrs_mat_set_option", "scanrs_set_global_option", "scanrs_mat_set_panel_precision",
     "scanrs_mat_chol_rinv", "scanrs_mat_get_counter", "scanrs_host_chol_upper", "scanrs_host_inv_upper", "scanrs_host_sym_eig", "scanrs_host_sym_eig_topk", "scanrs_debug_wait_never", "scanrs_debug_barrier_alone", "scanrs_debug_arena_selftest", "scanrs_debug_dense_route", "scanrs_debug_dense_gram", "scanrs_debug_dense_gemm", "scanrs_debug_weighted_colsum", "scanrs_init", "scanrs_release_cached_memory", "scanrs_cached_memory_bytes", "scanrs_reserve_device_memory", "scanrs_device_memory_in_use",
     "scanrs_h5_read_csc_matrix", "scanrs_h5_read_adaptive_csr_matrix", "scanrs_h5_read_matrix_metadata", "scanrs_h5_matrix_free",
@@ -1341,8 +1350,10 @@ EXPORTED_SYMBOLS = [
 from .sseq import (  # noqa: E402
     NB_EXACT_LOGSPACE, NB_EXACT_RATIO, DiffExpResult, SSeqParams, compute_sseq_params, diff_exp_table, group_sums, host_nb_exact_ratio_step,
     host_nb_exact_test_ratio, host_union_median, labels_from_clustering, sseq_de_each_vs_control, sseq_de_from_sums, sseq_de_one_vs_rest, sseq_de_pairs,
-    sseq_de_vs_control, sseq_differential_expression, sseq_params_from_moments,
+    sseq_de_pairs_sharded, sseq_de_vs_control, sseq_differential_expression, sseq_params_from_moments,
 )
 
 # merge_clusters, linkage and medoids (cluster.py)
-from .cluster import MergeTrace, linkage, medioids, merge_clusters, pdist, relabel_by_size  # noqa: E402
+from .cluster import (  # noqa: E402
+    MergeTrace, cluster_medoids, cluster_medoids_sharded, linkage, medioids, merge_clusters, merge_clusters_sharded, pdist, relabel_by_size,
+)

@@ -4,6 +4,10 @@ medoids (`medioids`, with `median_mut` of stats.rs) and relabel_by_size.
 Labels are int16 values 0 .. K-1 with every value present, K <= 8192. The scores are cells x d f64: a numpy array or the
 `PcaResultDevice` of a handle's last PCA (its `v` stays in device memory). pdist, linkage and relabel_by_size run on the host;
 the medoids and the merge's passes and tests run on the device through ``include/scanrs_amd.h``.
+
+``merge_clusters`` and ``cluster_medoids`` also take a ``MultiMat`` whose cells are the sharded dimension (``transposed=True`` for one
+created cells x genes): labels and scores then span the whole matrix and the results equal the unsharded call's bit for bit (DESIGN.md
+§7i). ``merge_clusters_sharded`` and ``cluster_medoids_sharded`` are the collective forms on one sharded handle.
 """
 from __future__ import annotations
 
@@ -13,7 +17,7 @@ from typing import List, Optional
 
 import numpy as np
 
-from . import AdaptiveMat, PcaResultDevice, ScanrsError, _check, _lib, _p
+from . import AdaptiveMat, MultiMat, PcaResultDevice, ScanrsError, _check, _lib, _p
 
 _u64, _u32 = ctypes.c_uint64, ctypes.c_uint32
 
@@ -119,14 +123,76 @@ def medioids(pca, labels, n_clusters: Optional[int] = None) -> np.ndarray:
     return out
 
 
-def merge_clusters(mat: AdaptiveMat, pca, labels, trace: bool = False, snoop=None, capacity: int = 4096):
+def _cells(mat, transposed: bool, collective: bool):
+    """(cells of the WHOLE matrix, cells this handle holds)."""
+    if isinstance(mat, MultiMat):
+        n = mat.rows if transposed else mat.cols
+        return n, n
+    if transposed:
+        raise ScanrsError(6, "transposed is for a MultiMat; use .t() on an AdaptiveMat")
+    local = mat.shape()[1]
+    if collective and getattr(mat, "_outer_global", None) is not None and mat.storage() == 1:
+        return mat._outer_global, local
+    return local, local
+
+
+def cluster_medoids(mat, pca, labels, n_clusters: Optional[int] = None, transposed: bool = False) -> np.ndarray:
+    """`medioids` over the cells of a matrix: mat is an AdaptiveMat (then this is `medioids(pca, labels)`) or a MultiMat, whose shards
+    each key their own cells' scores and select the medians by exchanging integer histograms. pca: a cells x d host array
+    over all cells."""
+    if not isinstance(mat, MultiMat):
+        if transposed:
+            raise ScanrsError(6, "transposed is for a MultiMat; use .t() on an AdaptiveMat")
+        return medioids(pca, labels, n_clusters)
+    return _medoids_on(mat, pca, labels, n_clusters, transposed, False)
+
+
+def cluster_medoids_sharded(mat: AdaptiveMat, pca, labels, n_clusters: Optional[int] = None) -> np.ndarray:
+    """`cluster_medoids` on one sharded handle: COLLECTIVE, every rank calls it with the same labels (over the whole matrix). pca: a host
+    array over all cells, or a PcaResultDevice holding the rank's own cells."""
+    return _medoids_on(mat, pca, labels, n_clusters, False, True)
+
+
+def _medoids_on(mat, pca, labels, n_clusters, transposed, collective):
+    cells, local = _cells(mat, transposed, collective)
+    ptr, on_dev, n, ld, d, keep = _scores(pca)
+    if n != (local if on_dev else cells):
+        raise ScanrsError(6, f"the scores have {n} rows for {local if on_dev else cells} cells")
+    lab = _labels(labels, cells)
+    k = int(lab.max()) + 1 if n_clusters is None and lab.size else int(n_clusters or 0)
+    out = np.zeros((k, d))
+    if isinstance(mat, MultiMat):
+        if on_dev:
+            raise ScanrsError(6, "a MultiMat takes the scores as a host array over all cells")
+        _check(_lib.scanrs_multi_cluster_medoids(mat._h, ctypes.c_int(int(transposed)), ptr, _u32(ld), _u32(d), _p(lab), _u32(k), _p(out)))
+    else:
+        _check(_lib.scanrs_cluster_medoids_sharded(mat._h, ptr, ctypes.c_int(on_dev), _u32(ld), _u32(d), _p(lab), _u32(k), _p(out)))
+    del keep
+    return out
+
+
+def merge_clusters(mat, pca, labels, trace: bool = False, snoop=None, capacity: int = 4096, transposed: bool = False):
     """`merge_clusters(fbm, pca, labels)` (merge_clusters.rs:59-138). Rows of `mat` are genes, columns are cells; pca is a
     cells x d array or a PcaResultDevice. Returns the merged labels (relabel_by_size), and with trace=True also a MergeTrace
-    (at most `capacity` entries are kept; the totals count all)."""
-    genes, cells = mat.shape()
+    (at most `capacity` entries are kept; the totals count all). mat: an AdaptiveMat, or a MultiMat whose cells are the sharded
+    dimension (`transposed=True` for one created cells x genes; pca then is a host array over all cells); a sharded AdaptiveMat is
+    refused, `merge_clusters_sharded` is the collective form for one."""
+    return _merge(mat, pca, labels, trace, snoop, capacity, transposed, False)
+
+
+def merge_clusters_sharded(mat: AdaptiveMat, pca, labels, trace: bool = False, snoop=None, capacity: int = 4096):
+    """`merge_clusters` on one sharded handle: COLLECTIVE, every rank calls it with the same labels (over the whole matrix). pca: a host
+    array over all cells, or a PcaResultDevice holding the rank's own cells. Every rank gets the complete labels and trace."""
+    return _merge(mat, pca, labels, trace, snoop, capacity, False, True)
+
+
+def _merge(mat, pca, labels, trace, snoop, capacity, transposed, collective):
+    cells, local = _cells(mat, transposed, collective)
     ptr, on_dev, n, ld, d, keep = _scores(pca)
-    if n != cells:
-        raise ScanrsError(6, f"the scores have {n} rows for {cells} cells")
+    if n != (local if on_dev else cells):
+        raise ScanrsError(6, f"the scores have {n} rows for {local if on_dev else cells} cells")
+    if isinstance(mat, MultiMat) and on_dev:
+        raise ScanrsError(6, "a MultiMat takes the scores as a host array over all cells")
     lab = _labels(labels, cells)
     out = np.zeros(cells, dtype=np.int16)
     tr, st = None, None
@@ -136,8 +202,13 @@ def merge_clusters(mat: AdaptiveMat, pca, labels, trace: bool = False, snoop=Non
         st = _MergeTrace(cap, tr.leaf0.ctypes.data, tr.leaf1.ctypes.data, tr.n_de.ctypes.data, tr.min_p_adj.ctypes.data, 0, 0, 0, 0)
     sn_keep = None if snoop is None else snoop._struct()
     sn = None if sn_keep is None else ctypes.byref(sn_keep)
-    _check(_lib.scanrs_merge_clusters(mat._h, ptr, ctypes.c_int(on_dev), _u32(ld), _u32(d), _p(lab), _p(out), sn,
-                                      None if st is None else ctypes.byref(st)))
+    tail = (_u32(ld), _u32(d), _p(lab), _p(out), sn, None if st is None else ctypes.byref(st))
+    if isinstance(mat, MultiMat):
+        _check(_lib.scanrs_multi_merge_clusters(mat._h, ctypes.c_int(int(transposed)), ptr, *tail))
+    elif collective:
+        _check(_lib.scanrs_merge_clusters_sharded(mat._h, ptr, ctypes.c_int(on_dev), *tail))
+    else:
+        _check(_lib.scanrs_merge_clusters(mat._h, ptr, ctypes.c_int(on_dev), *tail))
     del keep
     if not trace:
         return out

@@ -5,6 +5,8 @@
 //   medoid_select_kernel      exact median of each (cluster, column) segment by radix select: 8 rounds of 8-bit digits from the
 //                             top, one LDS histogram per wanted rank (⌊(n-1)/2⌋ and ⌊n/2⌋), integer counts only: the result
 //                             is the sorted list's element and does not depend on launch timing
+//   medoid_dist_*_kernel      the same medians when a segment's cells lie on several ranks: per radix round a local
+//                             histogram per (cluster, column, wanted rank), a u64 all-reduce between the kernels, a replicated pick
 //   merge_gene_major_kernel   the fused pass of a merge run from the gene-major copy: a wave owns a gene, and a per-wave LDS row
 //                             of a tile of clusters gathers Σ x (u64) and Σ x/u_c, Σ (x/u_c)² (128-bit fixed point, u_c the
 //                             cell's total) with integer LDS atomics
@@ -113,6 +115,94 @@ __global__ __launch_bounds__(MEDOID_THREADS) void medoid_select_kernel(const uns
     }
 }
 
+// ---- medoids over shards ---------------------------------------------------------------------------------------------
+// The cells of a (cluster, column) segment lie on several ranks, so no workgroup holds a segment alone: a radix round is a local
+// histogram (medoid_dist_hist_kernel), a u64 all-reduce of the table on the host's side, and a pick that every rank repeats on the same
+// integers (medoid_dist_pick_kernel). Pair p = jj * n_clusters + cluster within a column tile; state[4 p + h] is the prefix of wanted
+// rank h (0: ⌊(len-1)/2⌋, 1: ⌊len/2⌋ of the GLOBAL segment), state[4 p + 2 + h] what remains of the rank inside the prefix's bucket.
+constexpr uint32_t MEDOID_DIST_THREADS = 256, MEDOID_DIST_WAVES = MEDOID_DIST_THREADS / 64;
+
+__global__ void medoid_dist_init_kernel(const uint64_t *__restrict__ len, uint32_t n_clusters, uint32_t n_pairs, unsigned long long *__restrict__ state) {
+    const uint32_t p = blockIdx.x * blockDim.x + threadIdx.x;
+    if (p >= n_pairs) return;
+    const uint64_t l = len[p % n_clusters]; // >= 1: the host checks that every cluster has a cell
+    state[4ull * p] = state[4ull * p + 1] = 0ull;
+    state[4ull * p + 2] = (l - 1) / 2;
+    state[4ull * p + 3] = l / 2;
+}
+
+// block b: pair p0 + b; the rank's own part of its segment is keys[jj * n + off[k] .. off[k + 1]). A histogram per wave in LDS (integer
+// atomics; waves do not contend for a bin), summed in a fixed order into hist[b * 512 + h * 256 + digit]
+__global__ __launch_bounds__(MEDOID_DIST_THREADS) void medoid_dist_hist_kernel(const unsigned long long *__restrict__ keys, uint64_t n,
+                                                                               const uint64_t *__restrict__ off, uint32_t n_clusters, uint32_t p0,
+                                                                               int shift, const unsigned long long *__restrict__ state,
+                                                                               unsigned long long *__restrict__ hist) {
+    __shared__ uint32_t h[MEDOID_DIST_WAVES][2][256];
+    const uint32_t p = p0 + blockIdx.x, k = p % n_clusters, jj = p / n_clusters, tid = threadIdx.x, wave = tid >> 6;
+    for (uint32_t i = tid; i < MEDOID_DIST_WAVES * 512; i += MEDOID_DIST_THREADS) (&h[0][0][0])[i] = 0u;
+    __syncthreads();
+    const uint64_t b = off[k], len = off[k + 1] - b;
+    const unsigned long long *seg = keys + (uint64_t)jj * n + b;
+    const unsigned long long hi_mask = shift == 56 ? 0ull : ~0ull << (shift + 8);
+    const unsigned long long q0 = state[4ull * p], q1 = state[4ull * p + 1];
+    for (uint64_t i = tid; i < len; i += MEDOID_DIST_THREADS) {
+        const unsigned long long key = seg[i];
+        const uint32_t digit = (uint32_t)(key >> shift) & 255u;
+        if ((key & hi_mask) == q0) atomicAdd(&h[wave][0][digit], 1u);
+        if ((key & hi_mask) == q1) atomicAdd(&h[wave][1][digit], 1u);
+    }
+    __syncthreads();
+    for (uint32_t i = tid; i < 512; i += MEDOID_DIST_THREADS) {
+        unsigned long long c = 0ull;
+#pragma unroll
+        for (uint32_t w = 0; w < MEDOID_DIST_WAVES; w++) c += (&h[w][0][0])[i];
+        hist[(uint64_t)blockIdx.x * 512 + i] = c;
+    }
+}
+
+// block b (two waves): pair p0 + b; wave h finds the bucket of wanted rank h in the reduced histogram, as medoid_select_kernel does
+__global__ __launch_bounds__(128) void medoid_dist_pick_kernel(const unsigned long long *__restrict__ hist, uint32_t p0, int shift,
+                                                               unsigned long long *__restrict__ state) {
+    const uint32_t p = p0 + blockIdx.x, wave = threadIdx.x >> 6, lane = threadIdx.x & 63u;
+    const unsigned long long *hb = hist + (uint64_t)blockIdx.x * 512 + wave * 256;
+    const uint64_t c0 = hb[4 * lane], c1 = hb[4 * lane + 1], c2 = hb[4 * lane + 2], c3 = hb[4 * lane + 3];
+    const uint64_t local = c0 + c1 + c2 + c3;
+    uint64_t incl = local;
+    for (int o = 1; o < 64; o <<= 1) {
+        const uint64_t v = (uint64_t)__shfl_up((long long)incl, o);
+        if ((int)lane >= o) incl += v;
+    }
+    const uint64_t excl = incl - local, r = state[4ull * p + 2 + wave];
+    if (excl <= r && r < incl) { // exactly one lane: the counts of a prefix's buckets add up to more than the remaining rank
+        uint64_t cum = excl;
+        uint32_t d = 0;
+        if (cum + c0 <= r) {
+            cum += c0;
+            d = 1;
+            if (cum + c1 <= r) {
+                cum += c1;
+                d = 2;
+                if (cum + c2 <= r) {
+                    cum += c2;
+                    d = 3;
+                }
+            }
+        }
+        state[4ull * p + 2 + wave] = r - cum;
+        state[4ull * p + wave] |= (unsigned long long)(4 * lane + d) << shift;
+    }
+}
+
+// after the 8 rounds the prefix is the key itself: median_mut (stats.rs:13-39) as medoid_select_kernel writes it
+__global__ void medoid_dist_finish_kernel(const unsigned long long *__restrict__ state, const uint64_t *__restrict__ len, uint32_t n_clusters,
+                                          uint32_t n_pairs, uint32_t j0, double *__restrict__ out, uint32_t ldo) {
+    const uint32_t p = blockIdx.x * blockDim.x + threadIdx.x;
+    if (p >= n_pairs) return;
+    const uint32_t k = p % n_clusters, jj = p / n_clusters;
+    const double lo = from_order_key(state[4ull * p]), hi = from_order_key(state[4ull * p + 1]);
+    out[(uint64_t)k * ldo + j0 + jj] = (len[k] & 1) ? hi : (hi + lo) / 2.0;
+}
+
 // ---- the fused pass --------------------------------------------------------------------------------------------------------------
 __device__ __forceinline__ void merge_terms(uint32_t x, unsigned long long u, double scale1, double scale2, U128 &t1, U128 &t2) {
     const double t = (double)x / (double)u;
@@ -201,6 +291,37 @@ void launch_medoids(hipStream_t s, const double *d_scores, uint64_t n, uint32_t 
                            d_out, d);
         SCANRS_HIP(hipGetLastError());
     }
+}
+
+void launch_medoid_keys(hipStream_t s, const double *d_scores, uint64_t n, uint32_t ld, uint32_t j0, uint32_t jt, const uint32_t *d_perm,
+                        unsigned long long *d_keys, unsigned long long *d_nan_cell) {
+    if (!n || !jt) return;
+    hipLaunchKernelGGL(medoid_gather_kernel, dim3(grid_for(n * jt, 256, 65536)), dim3(256), 0, s, d_scores, n, ld, j0, jt, d_perm, d_keys, d_nan_cell);
+    SCANRS_HIP(hipGetLastError());
+}
+
+void launch_medoid_dist_init(hipStream_t s, const uint64_t *d_len, uint32_t n_clusters, uint32_t jt, unsigned long long *d_state) {
+    const uint32_t n_pairs = n_clusters * jt;
+    hipLaunchKernelGGL(medoid_dist_init_kernel, dim3((n_pairs + 255) / 256), dim3(256), 0, s, d_len, n_clusters, n_pairs, d_state);
+    SCANRS_HIP(hipGetLastError());
+}
+
+void launch_medoid_dist_hist(hipStream_t s, const unsigned long long *d_keys, uint64_t n, const uint64_t *d_off, uint32_t n_clusters, uint32_t p0,
+                             uint32_t np, int shift, const unsigned long long *d_state, unsigned long long *d_hist) {
+    hipLaunchKernelGGL(medoid_dist_hist_kernel, dim3(np), dim3(MEDOID_DIST_THREADS), 0, s, d_keys, n, d_off, n_clusters, p0, shift, d_state, d_hist);
+    SCANRS_HIP(hipGetLastError());
+}
+
+void launch_medoid_dist_pick(hipStream_t s, const unsigned long long *d_hist, uint32_t p0, uint32_t np, int shift, unsigned long long *d_state) {
+    hipLaunchKernelGGL(medoid_dist_pick_kernel, dim3(np), dim3(128), 0, s, d_hist, p0, shift, d_state);
+    SCANRS_HIP(hipGetLastError());
+}
+
+void launch_medoid_dist_finish(hipStream_t s, const unsigned long long *d_state, const uint64_t *d_len, uint32_t n_clusters, uint32_t j0, uint32_t jt,
+                               double *d_out, uint32_t ldo) {
+    const uint32_t n_pairs = n_clusters * jt;
+    hipLaunchKernelGGL(medoid_dist_finish_kernel, dim3((n_pairs + 255) / 256), dim3(256), 0, s, d_state, d_len, n_clusters, n_pairs, j0, d_out, ldo);
+    SCANRS_HIP(hipGetLastError());
 }
 
 uint32_t merge_tile_clusters(uint32_t n_clusters) {

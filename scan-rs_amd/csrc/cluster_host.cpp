@@ -172,8 +172,8 @@ static uint32_t medoid_cols_per_tile(uint64_t n, uint32_t d) {
 
 struct MedoidScratch {
     DevBuf<uint32_t> perm;
-    DevBuf<uint64_t> off;
-    DevBuf<unsigned long long> keys, nan_cell;
+    DevBuf<uint64_t> off, len;
+    DevBuf<unsigned long long> keys, nan_cell, state, hist, slots;
     DevBuf<double> out;
 };
 
@@ -202,6 +202,72 @@ static void medoids_on(hipStream_t s, MedoidScratch &ms, const double *d_scores,
     SCANRS_D2H(&nan_cell, ms.nan_cell.p, 8, s);
     SCANRS_D2H(centers, ms.out.p, (size_t)k * d * 8, s);
     SCANRS_SYNC(s);
+    if (nan_cell != ~0ull) fail(SCANRS_ERR_ARGUMENT, "the scores of cell %llu hold a NaN", nan_cell);
+}
+
+// The medoids of a sharded handle: d_scores holds the rank's own cells [cr.begin, cr.begin + cr.n_local), labels span the
+// whole matrix. Every rank walks the same column tiles, pair tiles and rounds (they depend on the global sizes only), so the exchange
+// steps pair up; the centers come out complete on every rank.
+static void medoids_dist(Storage &st, MedoidScratch &ms, const double *d_scores, const SseqCellRange &cr, uint32_t ld, uint32_t d,
+                         const int16_t *labels, uint32_t k, double *centers) {
+    if (cr.global == 0 || d == 0) return;
+    const hipStream_t s = st.stream;
+    const uint64_t n = cr.n_local;
+    // the clusters' global sizes (the wanted ranks), and this rank's cells cluster by cluster
+    std::vector<uint64_t> len(k, 0), off(k + 1, 0);
+    for (uint64_t c = 0; c < cr.global; c++) len[labels[c]]++;
+    const int16_t *lab = labels + cr.begin;
+    for (uint64_t c = 0; c < n; c++) off[lab[c] + 1]++;
+    for (uint32_t j = 0; j < k; j++) off[j + 1] += off[j];
+    std::vector<uint32_t> perm(std::max<uint64_t>(1, n));
+    {
+        std::vector<uint64_t> pos(off.begin(), off.end() - 1);
+        for (uint64_t c = 0; c < n; c++) perm[pos[lab[c]]++] = (uint32_t)c;
+    }
+    const uint32_t cpt = medoid_cols_per_tile(cr.global, d); // from the global count: the same tiles on every rank
+    const uint32_t hist_pairs = (uint32_t)std::min<uint64_t>(MEDOID_HIST_PAIRS, (uint64_t)k * cpt);
+    const uint32_t world = st.shard.world;
+    if (ms.perm.n < perm.size()) ms.perm.alloc(perm.size());
+    if (ms.off.n < k + 1) ms.off.alloc(k + 1);
+    if (ms.len.n < k) ms.len.alloc(k);
+    if (ms.keys.n < std::max<uint64_t>(1, n * cpt)) ms.keys.alloc(std::max<uint64_t>(1, n * cpt));
+    if (ms.state.n < (size_t)k * cpt * 4) ms.state.alloc((size_t)k * cpt * 4);
+    if (ms.hist.n < (size_t)hist_pairs * 512) ms.hist.alloc((size_t)hist_pairs * 512);
+    if (ms.slots.n < world) ms.slots.alloc(world);
+    if (ms.nan_cell.n < 1) ms.nan_cell.alloc(1);
+    if (ms.out.n < (size_t)k * d) ms.out.alloc((size_t)k * d);
+    h2d(ms.perm.p, perm.data(), n, s);
+    h2d(ms.off.p, off.data(), k + 1, s);
+    h2d(ms.len.p, len.data(), k, s);
+    SCANRS_HIP(hipMemsetAsync(ms.nan_cell.p, 0xFF, 8, s));
+    for (uint32_t j0 = 0; j0 < d; j0 += cpt) {
+        const uint32_t jt = std::min(cpt, d - j0), n_pairs = k * jt;
+        launch_medoid_keys(s, d_scores, n, ld, j0, jt, ms.perm.p, ms.keys.p, ms.nan_cell.p);
+        launch_medoid_dist_init(s, ms.len.p, k, jt, ms.state.p);
+        for (int shift = 56; shift >= 0; shift -= 8)
+            for (uint32_t p0 = 0; p0 < n_pairs; p0 += hist_pairs) {
+                const uint32_t np = std::min(hist_pairs, n_pairs - p0);
+                launch_medoid_dist_hist(s, ms.keys.p, n, ms.off.p, k, p0, np, shift, ms.state.p, ms.hist.p);
+                sseq_exchange_u64(st, ms.hist.p, (uint64_t)np * 512);
+                launch_medoid_dist_pick(s, ms.hist.p, p0, np, shift, ms.state.p);
+            }
+        launch_medoid_dist_finish(s, ms.state.p, ms.len.p, k, j0, jt, ms.out.p, d);
+    }
+    // the first cell holding a NaN: the transport only sums, so every rank puts its own first one (+ 1; 0 = none) into its slot
+    unsigned long long nan_local = 0;
+    SCANRS_D2H(&nan_local, ms.nan_cell.p, 8, s);
+    SCANRS_SYNC(s);
+    std::vector<unsigned long long> slots(world, 0ull);
+    slots[st.shard.rank] = nan_local == ~0ull ? 0ull : cr.begin + nan_local + 1;
+    h2d(ms.slots.p, slots.data(), world, s);
+    SCANRS_SYNC(s); // `slots` is pageable and is overwritten below
+    sseq_exchange_u64(st, ms.slots.p, world);
+    SCANRS_D2H(slots.data(), ms.slots.p, world * 8, s);
+    SCANRS_D2H(centers, ms.out.p, (size_t)k * d * 8, s);
+    SCANRS_SYNC(s);
+    unsigned long long nan_cell = ~0ull;
+    for (unsigned long long v : slots)
+        if (v) nan_cell = std::min(nan_cell, v - 1);
     if (nan_cell != ~0ull) fail(SCANRS_ERR_ARGUMENT, "the scores of cell %llu hold a NaN", nan_cell);
 }
 
@@ -271,8 +337,16 @@ void summarize(const std::vector<double> &padj, Candidate &cd) {
 } // namespace
 
 void merge_clusters_run(Storage &st, const SparseCopy &cp, bool gene_major, uint64_t genes, uint64_t cells, const double *d_scores, uint32_t ld,
-                        uint32_t d, const int16_t *labels_in, int16_t *labels_out, const scanrs_snoop *snoop, scanrs_merge_trace *trace) {
+                        uint32_t d, const int16_t *labels_in, int16_t *labels_out, const scanrs_snoop *snoop, scanrs_merge_trace *trace,
+                        bool collective) {
     if (trace) trace->n_candidates = trace->n_rounds = trace->n_merges = trace->n_passes = 0;
+    // a sharded handle (collective only): the copy and d_scores hold the cells [cr.begin, cr.begin + cr.n_local); `cells` is from
+    // here on the whole matrix: labels span it and the loop below runs replicated on every rank, on identical data
+    const SseqCellRange cr = collective ? sseq_cell_range(st, cells) : SseqCellRange{0, cells, cells};
+    const uint64_t cells_local = cr.n_local;
+    const bool dist = collective && st.shard.active();
+    cells = cr.global;
+    uint64_t shard_tests = 0;
     if (cells == 0) return;
     if (ld < d) fail(SCANRS_ERR_ARGUMENT, "ld must be at least d");
     if (cells > 0xFFFFFFFFull) fail(SCANRS_ERR_ARGUMENT, "at most 2^32 - 1 cells");
@@ -287,13 +361,16 @@ void merge_clusters_run(Storage &st, const SparseCopy &cp, bool gene_major, uint
     std::vector<double> cell_tot;
     const double scale = fixed_scale((double)cells); // Σ x/u_c, Σ (x/u_c)², Σ 1/u_c of a cluster: at most one per cell
     if (fused) {
-        unsigned long long *d_tot = st.scratch.get<unsigned long long>("merge_totals", cells);
-        launch_sseq_cell_totals(st, cp, gene_major, cells, d_tot);
+        unsigned long long *d_tot = st.scratch.get<unsigned long long>("merge_totals", cells + 1);
+        if (dist) SCANRS_HIP(hipMemsetAsync(d_tot, 0, cells * 8, s)); // the other ranks' slices
+        launch_sseq_cell_totals(st, cp, gene_major, cells_local, d_tot + cr.begin);
+        if (dist) sseq_exchange_u64(st, d_tot, cells); // one contributor per element: the sum is a copy
         passes++;
-        int16_t *d_lab = st.scratch.get<int16_t>("merge_labels", cells);
-        h2d(d_lab, labels.data(), cells, s);
+        int16_t *d_lab = st.scratch.get<int16_t>("merge_labels", std::max<uint64_t>(1, cells_local));
+        h2d(d_lab, labels.data() + cr.begin, cells_local, s);
         DevBuf<unsigned long long> d_acc(std::max<uint64_t>(1, (uint64_t)k * genes * 5));
-        passes += launch_merge_pass(st, cp, gene_major, genes, d_lab, k, d_tot, scale, scale, d_acc.p);
+        passes += launch_merge_pass(st, cp, gene_major, genes, d_lab, k, d_tot + cr.begin, scale, scale, d_acc.p);
+        if (dist) sseq_reduce_group_acc(st, d_acc.p, (uint64_t)k * genes); // every rank now holds the unsharded integers
         std::vector<unsigned long long> tot(cells), acc((uint64_t)k * genes * 5);
         SCANRS_D2H(tot.data(), d_tot, cells * 8, s);
         if (genes) SCANRS_D2H(acc.data(), d_acc.p, acc.size() * 8, s);
@@ -334,12 +411,13 @@ void merge_clusters_run(Storage &st, const SparseCopy &cp, bool gene_major, uint
             if (lab3[c] >= 0) union_idx.push_back(c);
         }
         double zh = 0.0, dl = 0.0;
-        sseq_params(st, cp, gene_major, genes, cells, ZETA_QUINTILE, union_idx.data(), union_idx.size(), nullptr, sf.data(), mean.data(), var.data(),
+        sseq_params(st, cp, gene_major, genes, cells_local, ZETA_QUINTILE, union_idx.data(), union_idx.size(), nullptr, sf.data(), mean.data(), var.data(),
                     use.data(), phi_mm.data(), &zh, &dl, phi.data());
         std::vector<uint64_t> si(genes * 1), so(genes * 1);
-        sseq_de_matrix(st, cp, gene_major, genes, cells, lab3.data(), 2, 1, sf.data(), mean.data(), phi.data(), use.data(), BIG_COUNT, nullptr,
+        sseq_de_matrix(st, cp, gene_major, genes, cells_local, lab3.data(), 2, 1, sf.data(), mean.data(), phi.data(), use.data(), BIG_COUNT, nullptr,
                        si.data(), so.data(), p.data(), padj.data(), l2.data(), mi.data(), mo.data());
         passes += 4; // totals, max count, moments, group sums
+        shard_tests += st.de_shard_tests;
         summarize(padj, cd);
     };
     // the fused route: the union's params and both sides' sums from the clusters' accumulators (O(genes)), then the tests
@@ -366,8 +444,14 @@ void merge_clusters_run(Storage &st, const SparseCopy &cp, bool gene_major, uint
         sseq_params_from_moments(mean.data(), var.data(), genes, sum_sf, n_s, (double)genes, ZETA_QUINTILE, use.data(), phi_mm.data(), &zh, &dl,
                                  phi.data());
         const double fa = (double)A.u_sum / m_s, fb = (double)B.u_sum / m_s;
-        sseq_de_sums(s, genes, 1, sa.data(), sb.data(), &fa, &fb, mean.data(), phi.data(), use.data(), BIG_COUNT, nullptr, p.data(), padj.data(),
-                     l2.data(), mi.data(), mo.data());
+        if (dist) { // the tests split over the ranks by gene, gathered by one exchange (§7g)
+            sseq_de_sums_strided(s, genes, 1, sa.data(), sb.data(), &fa, &fb, mean.data(), phi.data(), use.data(), 1, 0, BIG_COUNT, nullptr, p.data(),
+                                 padj.data(), l2.data(), mi.data(), mo.data(), SCANRS_NB_EXACT_LOGSPACE, &st);
+            shard_tests += st.de_shard_tests;
+        } else {
+            sseq_de_sums(s, genes, 1, sa.data(), sb.data(), &fa, &fb, mean.data(), phi.data(), use.data(), BIG_COUNT, nullptr, p.data(), padj.data(),
+                         l2.data(), mi.data(), mo.data());
+        }
         summarize(padj, cd);
     };
 
@@ -375,7 +459,10 @@ void merge_clusters_run(Storage &st, const SparseCopy &cp, bool gene_major, uint
         n_rounds++;
         // bins are the labels 0 .. k-1 in order; centers row i belongs to label i
         centers.assign((size_t)k * d, 0.0);
-        medoids_on(s, ms, d_scores, cells, ld, d, labels.data(), k, centers.data());
+        if (dist)
+            medoids_dist(st, ms, d_scores, cr, ld, d, labels.data(), k, centers.data());
+        else
+            medoids_on(s, ms, d_scores, cells, ld, d, labels.data(), k, centers.data());
         z.assign((size_t)(k - 1) * 4, 0.0);
         cluster_linkage_complete(centers.data(), k, d, z.data());
         const double max_label = (double)(k - 1);
@@ -446,6 +533,7 @@ void merge_clusters_run(Storage &st, const SparseCopy &cp, bool gene_major, uint
         trace->n_merges = n_merges;
         trace->n_passes = passes;
     }
+    if (dist) st.de_shard_tests = shard_tests;
 }
 
 } // namespace scanrs
@@ -510,6 +598,60 @@ int scanrs_merge_clusters(scanrs_mat *m, const double *pca, int pca_is_device, u
             scores = d_pca.p;
         }
         merge_clusters_run(st, cp, gm, m->rows(), cells, scores, ld, d, labels, labels_out, snoop, trace);
+    });
+}
+int scanrs_merge_clusters_sharded(scanrs_mat *m, const double *pca, int pca_is_device, uint32_t ld, uint32_t d, const int16_t *labels,
+                                  int16_t *labels_out, const scanrs_snoop *snoop, scanrs_merge_trace *trace) {
+    return guard([&] {
+        if (!m) fail(SCANRS_ERR_ARGUMENT, "null handle");
+        CurrentHandle cur(m->st.get());
+        bool gm = false;
+        SparseCopy &cp = sseq_resident_copy(m, &gm); // refuses a handle sharded over the genes
+        Storage &st = *m->st;
+        const SseqCellRange cr = sseq_cell_range(st, m->cols());
+        if (cr.global && (!pca || !labels || !labels_out)) fail(SCANRS_ERR_ARGUMENT, "null argument");
+        if (trace && trace->capacity && (!trace->leaf0 || !trace->leaf1 || !trace->n_de || !trace->min_p_adj))
+            fail(SCANRS_ERR_ARGUMENT, "trace arrays are null");
+        if (ld < d) fail(SCANRS_ERR_ARGUMENT, "ld must be at least d");
+        st.de_shard_tests = st.de_shard_allreduces = 0;
+        // host scores span the whole matrix and only this rank's rows go to the device; device scores are the rank's own rows already
+        DevBuf<double> d_pca;
+        const double *scores = pca;
+        if (!pca_is_device && cr.global) {
+            d_pca.alloc(std::max<uint64_t>(1, cr.n_local * ld));
+            if (cr.n_local) SCANRS_HIP(hipMemcpyAsync(d_pca.p, pca + cr.begin * ld, cr.n_local * ld * 8, hipMemcpyHostToDevice, st.stream));
+            scores = d_pca.p;
+        }
+        merge_clusters_run(st, cp, gm, m->rows(), cr.n_local, scores, ld, d, labels, labels_out, snoop, trace, true);
+    });
+}
+int scanrs_cluster_medoids_sharded(scanrs_mat *m, const double *pca, int pca_is_device, uint32_t ld, uint32_t d, const int16_t *labels,
+                                   uint32_t k, double *centers) {
+    return guard([&] {
+        if (!m) fail(SCANRS_ERR_ARGUMENT, "null handle");
+        CurrentHandle cur(m->st.get());
+        bool gm = false;
+        (void)sseq_resident_copy(m, &gm); // refuses a handle sharded over the genes
+        Storage &st = *m->st;
+        const SseqCellRange cr = sseq_cell_range(st, m->cols());
+        if (cr.global && (!pca || !labels || (!centers && d))) fail(SCANRS_ERR_ARGUMENT, "null argument");
+        if (ld < d) fail(SCANRS_ERR_ARGUMENT, "ld must be at least d");
+        if (cr.global > 0xFFFFFFFFull) fail(SCANRS_ERR_ARGUMENT, "at most 2^32 - 1 cells");
+        if (cr.global == 0 && k == 0) return;
+        cluster_check_labels(labels, cr.global, k);
+        st.de_shard_tests = st.de_shard_allreduces = 0;
+        DevBuf<double> d_pca;
+        const double *scores = pca;
+        if (!pca_is_device && cr.global) {
+            d_pca.alloc(std::max<uint64_t>(1, cr.n_local * ld));
+            if (cr.n_local) SCANRS_HIP(hipMemcpyAsync(d_pca.p, pca + cr.begin * ld, cr.n_local * ld * 8, hipMemcpyHostToDevice, st.stream));
+            scores = d_pca.p;
+        }
+        MedoidScratch ms;
+        if (st.shard.active())
+            medoids_dist(st, ms, scores, cr, ld, d, labels, k, centers);
+        else
+            medoids_on(st.stream, ms, scores, cr.global, ld, d, labels, k, centers);
     });
 }
 } // extern "C"

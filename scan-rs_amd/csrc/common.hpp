@@ -744,6 +744,28 @@ void launch_pairs_moments(hipStream_t s, const unsigned long long *d_acc, const 
 // per pair: zeta_hat, delta (d_zd: n_pairs x 2) and gene_phi (diff_exp.rs:409-441)
 void launch_pairs_shrink(hipStream_t s, const double *d_phi_mm, const uint8_t *d_use, uint64_t genes, uint32_t n_pairs, double pct, double *d_zd,
                          double *d_phi);
+// sharded handles: a tile of `ne` (group, gene) entries of the grouped accumulators (5 u64 each; the tile starts at an even
+// entry) as SSEQ_ACC_PLANES planes of u64 that add up without overflow over the ranks (planes x ne rounded up to even), and back with the
+// carries propagated. sseq_reduce_group_acc all-reduces the whole table in tiles of SSEQ_ACC_TILE entries through a scratch of
+// SSEQ_ACC_PLANES x SSEQ_ACC_TILE u64 (56 MiB, whatever the table's size) and returns the exchange steps it made (counted in
+// de_shard_allreduces); on an unsharded handle it does nothing.
+constexpr uint32_t SSEQ_ACC_PLANES = 7;
+constexpr uint64_t SSEQ_ACC_TILE = 1ull << 20;
+void launch_pairs_acc_split(hipStream_t s, const unsigned long long *d_acc_tile, uint64_t ne, unsigned long long *d_planes);
+void launch_pairs_acc_join(hipStream_t s, const unsigned long long *d_planes, uint64_t ne, unsigned long long *d_acc_tile);
+uint64_t sseq_reduce_group_acc(Storage &st, unsigned long long *d_acc, uint64_t n_entries);
+// the cells of a handle as its DE calls see them: [begin, begin + n_local) of `global` (an unsharded handle: all of them)
+struct SseqCellRange {
+    uint64_t begin, n_local, global;
+};
+SseqCellRange sseq_cell_range(const Storage &st, uint64_t cells_local);
+// one u64 all-reduce of a sharded handle, counted in de_shard_allreduces (nothing on an unsharded handle)
+void sseq_exchange_u64(Storage &st, unsigned long long *d, uint64_t count);
+// the batched pairwise DE (sseq_pairs_host.cpp). collective: a sharded handle is served (cells = the rank's own), labels span the whole matrix
+void sseq_de_pairs(Storage &st, const SparseCopy &cp, bool gene_major, uint64_t genes, uint64_t cells, const int16_t *labels, uint32_t n_groups,
+                   const uint32_t *pair_a, const uint32_t *pair_b, uint32_t n_pairs, double zeta_quintile, uint64_t big_count, int backend,
+                   const scanrs_snoop *snoop, uint64_t *sums_in, uint64_t *sums_out, double *p, double *p_adj, double *log2fc, double *mean_in,
+                   double *mean_out, scanrs_sseq_pair_params *params, bool collective = false);
 
 // ---- cluster.hip / cluster_host.cpp: merge_clusters (scan-rs/src/merge_clusters.rs, linkage.rs) ---------------------------------
 constexpr uint32_t MERGE_MAX_CLUSTERS = 8192;
@@ -757,6 +779,19 @@ void launch_medoids(hipStream_t s, const double *d_scores, uint64_t n, uint32_t 
 uint32_t launch_merge_pass(Storage &st, const SparseCopy &cp, bool gene_major, uint64_t n_genes, const int16_t *d_labels, uint32_t n_clusters,
                            const unsigned long long *d_tot, double scale1, double scale2, unsigned long long *d_out);
 uint32_t merge_tile_clusters(uint32_t n_clusters);
+// distributed exact medians: the cells of a (cluster, column) segment lie on several ranks, so a radix round is a local
+// histogram per (pair, wanted rank), one u64 all-reduce of the table and a replicated pick. Pair p = jj * n_clusters + cluster of a column
+// tile; d_state holds 4 u64 per pair (prefix and remaining rank of ⌊(len-1)/2⌋ and ⌊len/2⌋); d_hist 512 u64 per pair of a tile of at most
+// MEDOID_HIST_PAIRS pairs (16 MiB, whatever the number of clusters and columns). d_len: the clusters' GLOBAL cell counts.
+constexpr uint32_t MEDOID_HIST_PAIRS = 4096;
+void launch_medoid_keys(hipStream_t s, const double *d_scores, uint64_t n, uint32_t ld, uint32_t j0, uint32_t jt, const uint32_t *d_perm,
+                        unsigned long long *d_keys, unsigned long long *d_nan_cell);
+void launch_medoid_dist_init(hipStream_t s, const uint64_t *d_len, uint32_t n_clusters, uint32_t jt, unsigned long long *d_state);
+void launch_medoid_dist_hist(hipStream_t s, const unsigned long long *d_keys, uint64_t n, const uint64_t *d_off, uint32_t n_clusters, uint32_t p0,
+                             uint32_t np, int shift, const unsigned long long *d_state, unsigned long long *d_hist);
+void launch_medoid_dist_pick(hipStream_t s, const unsigned long long *d_hist, uint32_t p0, uint32_t np, int shift, unsigned long long *d_state);
+void launch_medoid_dist_finish(hipStream_t s, const unsigned long long *d_state, const uint64_t *d_len, uint32_t n_clusters, uint32_t j0, uint32_t jt,
+                               double *d_out, uint32_t ldo);
 // host side (cluster_host.cpp)
 void cluster_pdist(const double *x, uint64_t m, uint32_t d, double *out);
 void cluster_linkage_complete(const double *x, uint64_t m, uint32_t d, double *z);
@@ -765,7 +800,8 @@ void cluster_check_labels(const int16_t *labels, uint64_t n, uint32_t k);
 uint32_t cluster_count_labels(const int16_t *labels, uint64_t n); // K of a valid labelling (checked)
 void cluster_medoids(hipStream_t s, const double *d_scores, uint64_t n, uint32_t ld, uint32_t d, const int16_t *labels, uint32_t k, double *centers);
 void merge_clusters_run(Storage &st, const SparseCopy &cp, bool gene_major, uint64_t genes, uint64_t cells, const double *d_scores, uint32_t ld,
-                        uint32_t d, const int16_t *labels, int16_t *labels_out, const scanrs_snoop *snoop, scanrs_merge_trace *trace);
+                        uint32_t d, const int16_t *labels, int16_t *labels_out, const scanrs_snoop *snoop, scanrs_merge_trace *trace,
+                        bool collective = false);
 
 // ---- select.hip / select_host.cpp: select_rows, select_cols, partition_on_thresholds (sqz/src/mat.rs:730-888, 1004-1071) ---------
 void launch_sel_outer_sums(hipStream_t s, const SparseCopy &cp, const uint8_t *excl_outer, const uint8_t *excl_inner, unsigned long long *out);

@@ -349,6 +349,83 @@ int scanrs_multi_sseq_de(scanrs_multi *mm, int transposed, const int16_t *labels
     });
 }
 
+// ---- sseq_de_pairs, merge_clusters and the medoids over the shards ------------------------------------------------------
+// The collective calls of the handle (scanrs_*_sharded) on every shard at once, under §7g's convention: global arguments, complete
+// outputs on every shard, shard 0 writes the caller's arrays (and the trace), the others write into scratch of the call.
+namespace {
+
+// every shard polls the cancel flag at the same points; only shard 0 reports progress
+const scanrs_snoop *shard_snoop(const scanrs_snoop *snoop, size_t i, scanrs_snoop &sn) {
+    if (!snoop) return nullptr;
+    sn = *snoop;
+    if (i != 0) sn.progress = nullptr;
+    return &sn;
+}
+
+} // namespace
+
+int scanrs_multi_sseq_de_pairs(scanrs_multi *mm, int transposed, const int16_t *labels, uint32_t n_groups, const uint32_t *pair_a,
+                               const uint32_t *pair_b, uint32_t n_pairs, double zeta_quintile, uint64_t big_count, int backend,
+                               const scanrs_snoop *snoop, uint64_t *sums_in, uint64_t *sums_out, double *p, double *p_adj, double *log2fc,
+                               double *mean_in, double *mean_out, scanrs_sseq_pair_params *params) {
+    if (backend != SCANRS_NB_EXACT_LOGSPACE && backend != SCANRS_NB_EXACT_RATIO)
+        return bad_argument("backend must be SCANRS_NB_EXACT_LOGSPACE (0) or SCANRS_NB_EXACT_RATIO (1)");
+    if (!(zeta_quintile >= 0.0 && zeta_quintile <= 1.0)) return bad_argument("zeta_quintile must be in [0, 1]");
+    if (!mm || !labels || (n_pairs && (!pair_a || !pair_b)) || !sums_in || !sums_out || !p || !p_adj || !log2fc || !mean_in || !mean_out)
+        return bad_argument("null argument");
+    if (n_pairs == 0) return bad_argument("n_pairs must be at least 1");
+    if (n_groups == 0 || n_groups > SSEQ_MAX_GROUPS) return bad_argument("n_groups must be in 1 .. 8192");
+    const uint64_t genes = transposed ? mm->cols : mm->rows;
+    const uint64_t total = genes * n_pairs;
+    return fan_out(mm, [&](size_t i) {
+        ShardView v;
+        if (const int rc = v.open(mm, i, transposed)) return rc;
+        scanrs_snoop sn;
+        const scanrs_snoop *psn = shard_snoop(snoop, i, sn);
+        if (i == 0)
+            return scanrs_sseq_de_pairs_sharded(v.h, labels, n_groups, pair_a, pair_b, n_pairs, zeta_quintile, big_count, backend, psn, sums_in,
+                                                sums_out, p, p_adj, log2fc, mean_in, mean_out, params);
+        std::vector<uint64_t> u64(2 * total + 2);
+        std::vector<double> f64(5 * total + 5);
+        return scanrs_sseq_de_pairs_sharded(v.h, labels, n_groups, pair_a, pair_b, n_pairs, zeta_quintile, big_count, backend, psn, &u64[0],
+                                            &u64[total + 1], &f64[0], &f64[total + 1], &f64[2 * (total + 1)], &f64[3 * (total + 1)],
+                                            &f64[4 * (total + 1)], nullptr);
+    });
+}
+
+int scanrs_multi_cluster_medoids(scanrs_multi *mm, int transposed, const double *pca, uint32_t ld, uint32_t d, const int16_t *labels, uint32_t k,
+                                 double *centers) {
+    if (!mm) return bad_argument("null handle");
+    const uint64_t cells = transposed ? mm->rows : mm->cols;
+    if (cells && (!pca || !labels || (!centers && d))) return bad_argument("null argument");
+    if (ld < d) return bad_argument("ld must be at least d");
+    return fan_out(mm, [&](size_t i) {
+        ShardView v;
+        if (const int rc = v.open(mm, i, transposed)) return rc;
+        if (i == 0) return scanrs_cluster_medoids_sharded(v.h, pca, 0, ld, d, labels, k, centers);
+        std::vector<double> spare((size_t)k * d + 1);
+        return scanrs_cluster_medoids_sharded(v.h, pca, 0, ld, d, labels, k, spare.data());
+    });
+}
+
+int scanrs_multi_merge_clusters(scanrs_multi *mm, int transposed, const double *pca, uint32_t ld, uint32_t d, const int16_t *labels,
+                                int16_t *labels_out, const scanrs_snoop *snoop, scanrs_merge_trace *trace) {
+    if (!mm) return bad_argument("null handle");
+    const uint64_t cells = transposed ? mm->rows : mm->cols;
+    if (cells && (!pca || !labels || !labels_out)) return bad_argument("null argument");
+    if (trace && trace->capacity && (!trace->leaf0 || !trace->leaf1 || !trace->n_de || !trace->min_p_adj)) return bad_argument("trace arrays are null");
+    if (ld < d) return bad_argument("ld must be at least d");
+    return fan_out(mm, [&](size_t i) {
+        ShardView v;
+        if (const int rc = v.open(mm, i, transposed)) return rc;
+        scanrs_snoop sn;
+        const scanrs_snoop *psn = shard_snoop(snoop, i, sn);
+        if (i == 0) return scanrs_merge_clusters_sharded(v.h, pca, 0, ld, d, labels, labels_out, psn, trace);
+        std::vector<int16_t> spare(cells + 1);
+        return scanrs_merge_clusters_sharded(v.h, pca, 0, ld, d, labels, spare.data(), psn, nullptr);
+    });
+}
+
 // ---- select_rows / select_cols / partition_on_thresholds over the shards -------------------------------------------------
 // The collective entry points of the handle (scanrs_mat_*_sharded) on every shard at once. Every result is a new scanrs_multi on the
 // same devices with as many shards, the ranges its shards ended up with (nothing is rebalanced), and a group and communicators of its

@@ -44,6 +44,11 @@ static void exchange_u64(Storage &st, unsigned long long *d, uint64_t count) {
     allreduce_u64(st, d, count);
     st.de_shard_allreduces++;
 }
+SseqCellRange sseq_cell_range(const Storage &st, uint64_t cells_local) {
+    const CellRange cr = cell_range(st, cells_local);
+    return SseqCellRange{cr.begin, cr.n_local, cr.global};
+}
+void sseq_exchange_u64(Storage &st, unsigned long long *d, uint64_t count) { exchange_u64(st, d, count); }
 // the largest count of the whole matrix: the all-reduce only sums, so every rank puts its maximum into its own slot of a zeroed array
 static uint32_t sseq_max_count_global(Storage &st, const SparseCopy &cp) {
     const uint32_t mine = sseq_max_count(st, cp);

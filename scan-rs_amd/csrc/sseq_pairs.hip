@@ -12,6 +12,8 @@
 //   pairs_shrink_kernel        one workgroup per pair: zeta_hat = the interpolated percentile of the used dispersions by radix select
 //                              on order-preserving keys (two ranks, integer histograms, as medoid_select_kernel), their mean and the two
 //                              sums of squared deviations in a fixed order, delta and gene_phi (diff_exp.rs:409-441)
+//   pairs_acc_split / _join    the grouped accumulators of a sharded handle as u64 planes that a sum all-reduce cannot overflow, and
+//                              back with the carries propagated; also used by merge_clusters' fused route
 //
 // No float atomics. A pair's numbers come from its own two groups only, through integer sums and fixed reduction trees: they do not
 // depend on the other pairs of the call, on launch timing, or on which copy of the matrix the passes walked.
@@ -278,7 +280,101 @@ __global__ __launch_bounds__(PAIRS_THREADS) void pairs_shrink_kernel(const doubl
     }
 }
 
+// ---- the grouped accumulators across shards ----------------------------------------------------------------------------
+// Every rank holds partial sums of the (group, gene) table: 5 u64 per entry, [Σ x, Σ x/u lo, hi, Σ (x/u)² lo, hi]. Σ x reduces as it
+// is; a u64 sum of the low words would lose their carries. A tile of entries is therefore written as SSEQ_ACC_PLANES planes of u64
+// that cannot overflow under a sum over up to 2^31 ranks: Σ x, then for each moment the two 32-bit halves of lo and hi whole (the
+// scale of the pass keeps the sum over ALL cells below 2^126, so the hi words of the ranks add up below 2^62). After the all-reduce
+// the join propagates the carries of the halves into hi. Both kernels are streams: a workgroup moves SSEQ_ACC_BLOCK entries, the
+// 40-byte entries go through LDS so that every global access is a 16-byte one at consecutive addresses, and a thread owns two
+// neighbouring entries, which makes the plane accesses 16 bytes wide as well. No atomics.
+constexpr uint32_t SSEQ_ACC_BLOCK = 512; // entries per workgroup of 256 threads: 20 KB of LDS
+constexpr unsigned long long LIMB_MASK = 0xFFFFFFFFull;
+
+// acc: the tile's first entry (an even entry of the table: 16-byte aligned); planes: SSEQ_ACC_PLANES x ne_pad, ne_pad = ne rounded up to even
+__global__ __launch_bounds__(256) void pairs_acc_split_kernel(const unsigned long long *__restrict__ acc, uint64_t ne, uint64_t ne_pad,
+                                                              unsigned long long *__restrict__ planes) {
+    __shared__ ulonglong2 stage[SSEQ_ACC_BLOCK * 5 / 2];
+    const uint32_t tid = threadIdx.x;
+    const uint64_t e0 = (uint64_t)blockIdx.x * SSEQ_ACC_BLOCK;
+    const uint64_t n_words = (ne - e0 < SSEQ_ACC_BLOCK ? ne - e0 : SSEQ_ACC_BLOCK) * 5; // ne > e0: the launcher sizes the grid
+    const unsigned long long *src = acc + e0 * 5;
+    for (uint32_t i = tid; i < SSEQ_ACC_BLOCK * 5 / 2; i += 256) {
+        ulonglong2 v = make_ulonglong2(0ull, 0ull); // the entries behind the table's end read as zeros
+        if (2ull * i + 1 < n_words)
+            v = reinterpret_cast<const ulonglong2 *>(src)[i];
+        else if (2ull * i < n_words)
+            v.x = src[2ull * i];
+        stage[i] = v;
+    }
+    __syncthreads();
+    const uint64_t e = e0 + 2ull * tid;
+    if (e >= ne_pad) return;
+    const unsigned long long *w = reinterpret_cast<const unsigned long long *>(stage) + 10u * tid; // entries e and e + 1
+    ulonglong2 out[SSEQ_ACC_PLANES];
+    out[0] = make_ulonglong2(w[0], w[5]);
+#pragma unroll
+    for (uint32_t m = 0; m < 2; m++) {
+        const unsigned long long lo_a = w[1 + 2 * m], lo_b = w[6 + 2 * m];
+        out[1 + 3 * m] = make_ulonglong2(lo_a & LIMB_MASK, lo_b & LIMB_MASK);
+        out[2 + 3 * m] = make_ulonglong2(lo_a >> 32, lo_b >> 32);
+        out[3 + 3 * m] = make_ulonglong2(w[2 + 2 * m], w[7 + 2 * m]);
+    }
+#pragma unroll
+    for (uint32_t p = 0; p < SSEQ_ACC_PLANES; p++) *reinterpret_cast<ulonglong2 *>(planes + p * ne_pad + e) = out[p];
+}
+
+__global__ __launch_bounds__(256) void pairs_acc_join_kernel(const unsigned long long *__restrict__ planes, uint64_t ne, uint64_t ne_pad,
+                                                             unsigned long long *__restrict__ acc) {
+    __shared__ ulonglong2 stage[SSEQ_ACC_BLOCK * 5 / 2];
+    const uint32_t tid = threadIdx.x;
+    const uint64_t e0 = (uint64_t)blockIdx.x * SSEQ_ACC_BLOCK;
+    const uint64_t e = e0 + 2ull * tid;
+    if (e < ne_pad) {
+        ulonglong2 in[SSEQ_ACC_PLANES];
+#pragma unroll
+        for (uint32_t p = 0; p < SSEQ_ACC_PLANES; p++) in[p] = *reinterpret_cast<const ulonglong2 *>(planes + p * ne_pad + e);
+        unsigned long long *w = reinterpret_cast<unsigned long long *>(stage) + 10u * tid;
+        w[0] = in[0].x;
+        w[5] = in[0].y;
+#pragma unroll
+        for (uint32_t m = 0; m < 2; m++) {
+            // a sum of low halves is below 2^63 and its carry below 2^31: no step overflows
+            const unsigned long long ca = (in[1 + 3 * m].x >> 32) + in[2 + 3 * m].x, cb = (in[1 + 3 * m].y >> 32) + in[2 + 3 * m].y;
+            w[1 + 2 * m] = (in[1 + 3 * m].x & LIMB_MASK) | (ca << 32);
+            w[2 + 2 * m] = in[3 + 3 * m].x + (ca >> 32);
+            w[6 + 2 * m] = (in[1 + 3 * m].y & LIMB_MASK) | (cb << 32);
+            w[7 + 2 * m] = in[3 + 3 * m].y + (cb >> 32);
+        }
+    }
+    __syncthreads();
+    const uint64_t n_words = (ne - e0 < SSEQ_ACC_BLOCK ? ne - e0 : SSEQ_ACC_BLOCK) * 5;
+    unsigned long long *dst = acc + e0 * 5;
+    for (uint32_t i = tid; i < SSEQ_ACC_BLOCK * 5 / 2; i += 256) {
+        if (2ull * i + 1 < n_words)
+            reinterpret_cast<ulonglong2 *>(dst)[i] = stage[i];
+        else if (2ull * i < n_words)
+            dst[2ull * i] = stage[i].x;
+    }
+}
+
 // ---- launchers -------------------------------------------------------------------------------------------------------------------
+void launch_pairs_acc_split(hipStream_t s, const unsigned long long *d_acc_tile, uint64_t ne, unsigned long long *d_planes) {
+    if (!ne) return;
+    const uint64_t ne_pad = (ne + 1) & ~1ull;
+    hipLaunchKernelGGL(pairs_acc_split_kernel, dim3((uint32_t)((ne + SSEQ_ACC_BLOCK - 1) / SSEQ_ACC_BLOCK)), dim3(256), 0, s, d_acc_tile, ne, ne_pad,
+                       d_planes);
+    SCANRS_HIP(hipGetLastError());
+}
+
+void launch_pairs_acc_join(hipStream_t s, const unsigned long long *d_planes, uint64_t ne, unsigned long long *d_acc_tile) {
+    if (!ne) return;
+    const uint64_t ne_pad = (ne + 1) & ~1ull;
+    hipLaunchKernelGGL(pairs_acc_join_kernel, dim3((uint32_t)((ne + SSEQ_ACC_BLOCK - 1) / SSEQ_ACC_BLOCK)), dim3(256), 0, s, d_planes, ne, ne_pad,
+                       d_acc_tile);
+    SCANRS_HIP(hipGetLastError());
+}
+
 static inline uint32_t pairs_grid(uint64_t items, uint32_t per_block, uint32_t cap) {
     return (uint32_t)std::max<uint64_t>(1, std::min<uint64_t>(cap, (items + per_block - 1) / per_block));
 }

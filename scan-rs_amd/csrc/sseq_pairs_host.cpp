@@ -58,6 +58,20 @@ double sseq_union_median(const double *a, uint64_t na, const double *b, uint64_t
     return lo + (hi - lo) * dd;
 }
 
+// the grouped accumulators of a sharded handle, all-reduced in tiles through a scratch of fixed size (sseq_pairs.hip)
+uint64_t sseq_reduce_group_acc(Storage &st, unsigned long long *d_acc, uint64_t n_entries) {
+    if (!st.shard.active() || n_entries == 0) return 0;
+    unsigned long long *d_planes = st.scratch.get<unsigned long long>("sseq_acc_planes", SSEQ_ACC_PLANES * std::min<uint64_t>(SSEQ_ACC_TILE, n_entries + 1));
+    uint64_t steps = 0;
+    for (uint64_t e0 = 0; e0 < n_entries; e0 += SSEQ_ACC_TILE, steps++) {
+        const uint64_t ne = std::min<uint64_t>(SSEQ_ACC_TILE, n_entries - e0), ne_pad = (ne + 1) & ~1ull;
+        launch_pairs_acc_split(st.stream, d_acc + e0 * 5, ne, d_planes);
+        sseq_exchange_u64(st, d_planes, SSEQ_ACC_PLANES * ne_pad);
+        launch_pairs_acc_join(st.stream, d_planes, ne, d_acc + e0 * 5);
+    }
+    return steps;
+}
+
 namespace {
 struct PairOut { // where the caller wants the results: genes x n_pairs each
     uint64_t *sums_in, *sums_out;
@@ -80,7 +94,12 @@ struct LiteralPair { // a pair that took the literal route: its columns, scatter
 void sseq_de_pairs(Storage &st, const SparseCopy &cp, bool gene_major, uint64_t genes, uint64_t cells, const int16_t *labels, uint32_t n_groups,
                    const uint32_t *pair_a, const uint32_t *pair_b, uint32_t n_pairs, double zeta_quintile, uint64_t big_count, int backend,
                    const scanrs_snoop *snoop, uint64_t *sums_in, uint64_t *sums_out, double *p, double *p_adj, double *log2fc, double *mean_in,
-                   double *mean_out, scanrs_sseq_pair_params *params) {
+                   double *mean_out, scanrs_sseq_pair_params *params, bool collective) {
+    // a sharded handle (collective only): the copy holds the cells [cr.begin, cr.begin + cr.n_local) and `cells` is from here on
+    // the whole matrix: labels span it, the host folds run replicated, the device gets this rank's slice of the labels
+    const SseqCellRange cr = collective ? sseq_cell_range(st, cells) : SseqCellRange{0, cells, cells};
+    const uint64_t cells_local = cr.n_local;
+    cells = cr.global;
     if (backend != SCANRS_NB_EXACT_LOGSPACE && backend != SCANRS_NB_EXACT_RATIO)
         fail(SCANRS_ERR_ARGUMENT, "backend must be SCANRS_NB_EXACT_LOGSPACE (0) or SCANRS_NB_EXACT_RATIO (1)");
     if (n_pairs == 0) fail(SCANRS_ERR_ARGUMENT, "n_pairs must be at least 1");
@@ -110,13 +129,16 @@ void sseq_de_pairs(Storage &st, const SparseCopy &cp, bool gene_major, uint64_t 
     pairs_progress(snoop, 0.0);
 
     // pass 1: per-cell totals; then every group's sorted totals and integer sums, and the pairs' headers
+    // (the scale comes from the GLOBAL cell count: every rank of a sharded handle rounds every term to the same quantum)
     const double scale = fixed_scale((double)cells); // Σ x/u_c, Σ (x/u_c)², Σ 1/u_c of a group: at most one per cell
     const uint64_t total = genes * n_pairs;
-    unsigned long long *d_tot = st.scratch.get<unsigned long long>("sseq_totals", std::max<uint64_t>(1, cells));
-    launch_sseq_cell_totals(st, cp, gene_major, cells, d_tot);
+    unsigned long long *d_tot = st.scratch.get<unsigned long long>("sseq_totals", cells + 1);
+    if (cells_local != cells) SCANRS_HIP(hipMemsetAsync(d_tot, 0, cells * 8, s)); // the other ranks' slices
+    launch_sseq_cell_totals(st, cp, gene_major, cells_local, d_tot + cr.begin);
+    if (collective) sseq_exchange_u64(st, d_tot, cells); // one contributor per element: the sum is a copy
     passes++;
-    int16_t *d_lab = st.scratch.get<int16_t>("sseq_labels", std::max<uint64_t>(1, cells));
-    pairs_h2d(d_lab, labels, cells, s);
+    int16_t *d_lab = st.scratch.get<int16_t>("sseq_labels", std::max<uint64_t>(1, cells_local));
+    pairs_h2d(d_lab, labels + cr.begin, cells_local, s);
     DevBuf<uint32_t> d_perm(perm.size()), d_off(off.size()), d_pa(n_pairs), d_pb(n_pairs);
     DevBuf<unsigned long long> d_gathered(perm.size()), d_sorted(perm.size()), d_stats((size_t)n_groups * 3);
     DevBuf<SseqPairHeader> d_hdr(n_pairs);
@@ -134,7 +156,8 @@ void sseq_de_pairs(Storage &st, const SparseCopy &cp, bool gene_major, uint64_t 
 
     // pass 2: the grouped pass (one per tile of groups from the gene-major copy), then the parameters of every pair
     DevBuf<unsigned long long> d_acc(std::max<uint64_t>(1, (uint64_t)n_groups * genes * 5));
-    passes += launch_merge_pass(st, cp, gene_major, genes, d_lab, n_groups, d_tot, scale, scale, d_acc.p);
+    passes += launch_merge_pass(st, cp, gene_major, genes, d_lab, n_groups, d_tot + cr.begin, scale, scale, d_acc.p);
+    if (collective) sseq_reduce_group_acc(st, d_acc.p, (uint64_t)n_groups * genes); // from here on every rank holds the unsharded integers
     DevBuf<double> d_mean(std::max<uint64_t>(1, total)), d_var(std::max<uint64_t>(1, total)), d_phi_mm(std::max<uint64_t>(1, total)),
         d_phi(std::max<uint64_t>(1, total)), d_zd((size_t)n_pairs * 2);
     DevBuf<uint8_t> d_use(std::max<uint64_t>(1, total));
@@ -158,6 +181,7 @@ void sseq_de_pairs(Storage &st, const SparseCopy &cp, bool gene_major, uint64_t 
 
     // a union whose median total is 0 has no finite size factors: such a pair runs the reference's own calls (as merge_clusters does)
     std::vector<LiteralPair> lit;
+    uint64_t lit_tests = 0; // tests this rank launched for the literal pairs
     {
         std::vector<int16_t> lab3;
         std::vector<uint64_t> union_idx;
@@ -178,9 +202,9 @@ void sseq_de_pairs(Storage &st, const SparseCopy &cp, bool gene_major, uint64_t 
             L.si.assign(genes, 0);
             L.so.assign(genes, 0);
             L.use.assign(genes, 0);
-            sseq_params(st, cp, gene_major, genes, cells, zeta_quintile, union_idx.data(), union_idx.size(), nullptr, sf.data(), L.mean.data(),
+            sseq_params(st, cp, gene_major, genes, cells_local, zeta_quintile, union_idx.data(), union_idx.size(), nullptr, sf.data(), L.mean.data(),
                         L.var.data(), L.use.data(), L.phi_mm.data(), &L.zh, &L.dl, L.phi.data());
-            sseq_de_matrix(st, cp, gene_major, genes, cells, lab3.data(), 2, 1, sf.data(), L.mean.data(), L.phi.data(), L.use.data(), big_count,
+            sseq_de_matrix(st, cp, gene_major, genes, cells_local, lab3.data(), 2, 1, sf.data(), L.mean.data(), L.phi.data(), L.use.data(), big_count,
                            nullptr, L.si.data(), L.so.data(), L.p.data(), L.padj.data(), L.l2.data(), L.mi.data(), L.mo.data(), backend);
             for (uint64_t c = 0; c < cells; c++) { // the sides' size factors and Σ 1/sf as those two calls take them
                 if (lab3[c] == 0) L.fa += sf[c];
@@ -188,6 +212,7 @@ void sseq_de_pairs(Storage &st, const SparseCopy &cp, bool gene_major, uint64_t 
                 if (sf[c] != 0.0) L.sum_sf += 1.0 / sf[c];
             }
             passes += 4; // totals, max count, moments, group sums
+            lit_tests += st.de_shard_tests;
         }
     }
     pairs_progress(snoop, 0.6);
@@ -198,7 +223,8 @@ void sseq_de_pairs(Storage &st, const SparseCopy &cp, bool gene_major, uint64_t 
         fb[j] = hdr[j].sf_b;
     }
     sseq_de_sums_strided(s, genes, n_pairs, sums_in, sums_out, fa.data(), fb.data(), mean.data(), phi.data(), use.data(), n_pairs, 1, big_count, snoop,
-                         p, p_adj, log2fc, mean_in, mean_out, backend);
+                         p, p_adj, log2fc, mean_in, mean_out, backend, collective ? &st : nullptr);
+    if (collective) st.de_shard_tests += lit_tests;
 
     for (const LiteralPair &L : lit) {
         const uint32_t j = L.j;
@@ -259,6 +285,22 @@ int scanrs_sseq_de_pairs(scanrs_mat *m, const int16_t *labels, uint32_t n_groups
         SparseCopy &cp = sseq_resident_copy(m, &gm);
         sseq_de_pairs(*m->st, cp, gm, m->rows(), m->cols(), labels, n_groups, pair_a, pair_b, n_pairs, zeta_quintile, big_count, backend, snoop,
                       sums_in, sums_out, p, p_adj, log2fc, mean_in, mean_out, params);
+    });
+}
+int scanrs_sseq_de_pairs_sharded(scanrs_mat *m, const int16_t *labels, uint32_t n_groups, const uint32_t *pair_a, const uint32_t *pair_b,
+                                 uint32_t n_pairs, double zeta_quintile, uint64_t big_count, int backend, const scanrs_snoop *snoop, uint64_t *sums_in,
+                                 uint64_t *sums_out, double *p, double *p_adj, double *log2fc, double *mean_in, double *mean_out,
+                                 scanrs_sseq_pair_params *params) {
+    return guard([&] {
+        if (!m || !labels || (n_pairs && (!pair_a || !pair_b)) || !sums_in || !sums_out || !p || !p_adj || !log2fc || !mean_in || !mean_out)
+            fail(SCANRS_ERR_ARGUMENT, "null argument");
+        if (!(zeta_quintile >= 0.0 && zeta_quintile <= 1.0)) fail(SCANRS_ERR_ARGUMENT, "zeta_quintile must be in [0, 1]");
+        CurrentHandle cur(m->st.get());
+        bool gm = false;
+        SparseCopy &cp = sseq_resident_copy(m, &gm); // refuses a handle sharded over the genes
+        m->st->de_shard_tests = m->st->de_shard_allreduces = 0;
+        sseq_de_pairs(*m->st, cp, gm, m->rows(), m->cols(), labels, n_groups, pair_a, pair_b, n_pairs, zeta_quintile, big_count, backend, snoop,
+                      sums_in, sums_out, p, p_adj, log2fc, mean_in, mean_out, params, true);
     });
 }
 int scanrs_host_union_median(const double *a, uint64_t n_a, const double *b, uint64_t n_b, double *out) {

@@ -7,7 +7,8 @@ the tests run on the device through ``include/scanrs_amd.h``; the O(genes) finis
 ``compute_sseq_params``, ``group_sums``, ``sseq_differential_expression``, ``sseq_de_one_vs_rest`` and ``sseq_de_vs_control`` also
 take a ``MultiMat`` (or a sharded ``AdaptiveMat``) whose cells are the sharded dimension: a genes x cells CSC ``MultiMat``, or a
 cells x genes CSR one with ``transposed=True``. All per-cell arguments then span the whole matrix and every result equals the
-unsharded call bit for bit.
+unsharded call bit for bit. ``sseq_de_pairs`` and ``sseq_de_each_vs_control`` take a ``MultiMat`` in the same way
+(DESIGN.md §7i); on a sharded ``AdaptiveMat`` they stay refused, and ``sseq_de_pairs_sharded`` is the collective form every rank calls.
 """
 from __future__ import annotations
 
@@ -240,8 +241,8 @@ class _PairParams(ctypes.Structure):
                                                "sf_b", "median_total", "sum_size_factors", "n_cells_a", "n_cells_b", "literal")]
 
 
-def sseq_de_pairs(mat: AdaptiveMat, labels, pairs, zeta_quintile: float = ZETA_QUINTILE_DEFAULT, big_count: Optional[int] = None,
-                  n_groups: Optional[int] = None, backend: int = NB_EXACT_LOGSPACE, snoop=None):
+def sseq_de_pairs(mat, labels, pairs, zeta_quintile: float = ZETA_QUINTILE_DEFAULT, big_count: Optional[int] = None,
+                  n_groups: Optional[int] = None, backend: int = NB_EXACT_LOGSPACE, snoop=None, transposed: bool = False):
     """Batched pairwise DE with per-pair parameters: for every (a, b) of `pairs`, `compute_sseq_params(mat, zeta_quintile, cells of
     a ∪ b)` (diff_exp.rs:458-490) and then the cells of group a against those of group b (diff_exp.rs:125-161), as merge_clusters.rs
     runs its candidates and as diff_exp.rs:361-376 describes the shared-control batched path. All pairs share two passes over the
@@ -249,8 +250,27 @@ def sseq_de_pairs(mat: AdaptiveMat, labels, pairs, zeta_quintile: float = ZETA_Q
     `(List[DiffExpResult], List[SSeqParams])`, one of each per pair; `size_factors` is left empty, as in
     `sseq_params_from_moments`, and the pair's scalars are attached to its params: `size_factor_a`, `size_factor_b`,
     `median_total`, `sum_size_factors`, `num_cells_a`, `num_cells_b`, `literal` (the union's median total was 0 and the pair ran
-    the two reference calls themselves). labels: per cell, the group 0 .. n_groups - 1 or -1 (in no group)."""
-    genes, cells = mat.shape()
+    the two reference calls themselves). labels: per cell, the group 0 .. n_groups - 1 or -1 (in no group).
+    mat: an AdaptiveMat, or a MultiMat whose cells are the sharded dimension (`transposed=True` for one created cells x genes): labels
+    then span the whole matrix and every output equals the unsharded call's bit for bit. A sharded AdaptiveMat is
+    refused; `sseq_de_pairs_sharded` is the collective form for one."""
+    return _de_pairs(mat, labels, pairs, zeta_quintile, big_count, n_groups, backend, snoop, transposed, False)
+
+
+def sseq_de_pairs_sharded(mat: AdaptiveMat, labels, pairs, zeta_quintile: float = ZETA_QUINTILE_DEFAULT, big_count: Optional[int] = None,
+                          n_groups: Optional[int] = None, backend: int = NB_EXACT_LOGSPACE, snoop=None):
+    """`sseq_de_pairs` on one sharded handle (set_shard with a host hook, or set_shard_comm): COLLECTIVE, every rank calls it with the same
+    arguments; labels span the whole matrix and every rank gets the complete results. On an unsharded handle it is `sseq_de_pairs`."""
+    return _de_pairs(mat, labels, pairs, zeta_quintile, big_count, n_groups, backend, snoop, False, True)
+
+
+def _de_pairs(mat, labels, pairs, zeta_quintile, big_count, n_groups, backend, snoop, transposed, collective):
+    if isinstance(mat, MultiMat) or collective:
+        genes, cells = _shape(mat, transposed)
+    else:
+        if transposed:
+            raise ScanrsError(6, "transposed is for a MultiMat; use .t() on an AdaptiveMat")
+        genes, cells = mat.shape()
     lab = _labels(labels, cells)
     if n_groups is None:
         n_groups = int(lab.max()) + 1 if lab.size else 0
@@ -271,8 +291,14 @@ def sseq_de_pairs(mat: AdaptiveMat, labels, pairs, zeta_quintile: float = ZETA_Q
     pp = _PairParams(*(a.ctypes.data for a in (mean, var, phi_mm, phi, use, zh, dl, fa, fb, med, ssf, na, nb, lit)))
     sn, _keep = _snoop_arg(snoop)
     bc = BIG_COUNT_DEFAULT if big_count is None else int(big_count)
-    _check(_lib.scanrs_sseq_de_pairs(mat._h, _p(lab), _u32(n_groups), _p(pa), _p(pb), _u32(t), _f64c(zeta_quintile), _u64(bc),
-                                     ctypes.c_int(_backend(backend)), sn, _p(si), _p(so), _p(p), _p(padj), _p(l2), _p(mi), _p(mo), ctypes.byref(pp)))
+    args = (_p(lab), _u32(n_groups), _p(pa), _p(pb), _u32(t), _f64c(zeta_quintile), _u64(bc), ctypes.c_int(_backend(backend)), sn, _p(si), _p(so),
+            _p(p), _p(padj), _p(l2), _p(mi), _p(mo), ctypes.byref(pp))
+    if isinstance(mat, MultiMat):
+        _check(_lib.scanrs_multi_sseq_de_pairs(mat._h, ctypes.c_int(int(transposed)), *args))
+    elif collective:
+        _check(_lib.scanrs_sseq_de_pairs_sharded(mat._h, *args))
+    else:
+        _check(_lib.scanrs_sseq_de_pairs(mat._h, *args))
     results, params = [], []
     for j in range(t):
         prm = SSeqParams(int(na[j] + nb[j]), genes, np.zeros(0), mean[:, j].copy(), var[:, j].copy(), use[:, j].astype(bool), phi_mm[:, j].copy(),
@@ -286,17 +312,18 @@ def sseq_de_pairs(mat: AdaptiveMat, labels, pairs, zeta_quintile: float = ZETA_Q
     return results, params
 
 
-def sseq_de_each_vs_control(mat: AdaptiveMat, labels, control: int = 0, zeta_quintile: float = ZETA_QUINTILE_DEFAULT, big_count: Optional[int] = None,
-                            n_groups: Optional[int] = None, backend: int = NB_EXACT_LOGSPACE, snoop=None):
+def sseq_de_each_vs_control(mat, labels, control: int = 0, zeta_quintile: float = ZETA_QUINTILE_DEFAULT, big_count: Optional[int] = None,
+                            n_groups: Optional[int] = None, backend: int = NB_EXACT_LOGSPACE, snoop=None, transposed: bool = False):
     """Every other group against the group `control`, each test with the parameters of its own union (`sseq_de_pairs` over the
-    pairs (g, control), g ascending). Returns `(List[DiffExpResult], List[SSeqParams])`, one per group other than the control."""
+    pairs (g, control), g ascending). Returns `(List[DiffExpResult], List[SSeqParams])`, one per group other than the control.
+    mat: an AdaptiveMat or a MultiMat, as for `sseq_de_pairs`."""
     lab = np.asarray(labels)
     if n_groups is None:
         n_groups = int(lab.max()) + 1 if lab.size else 0
     if not 0 <= int(control) < n_groups:
         raise ScanrsError(6, f"control must be a group 0 .. {n_groups - 1}")
     pairs = [(g, int(control)) for g in range(n_groups) if g != int(control)]
-    return sseq_de_pairs(mat, lab, pairs, zeta_quintile, big_count, n_groups, backend, snoop)
+    return sseq_de_pairs(mat, lab, pairs, zeta_quintile, big_count, n_groups, backend, snoop, transposed)
 
 
 def host_union_median(a, b) -> float:

@@ -18,7 +18,9 @@ exact tests, their terms, the tests Ratio hands to LogSpace, and the ms of the t
 With --per-pair-params that leg also times the same tests with the parameters of each pair's own union: `pairs_call_ms` for one
 sseq_de_each_vs_control call (its "de_pairs_passes" / "de_pairs_literal" counters beside it), and `literal_loop_ms` for the calls it
 replaces, compute_sseq_params(cell_indices = union) + sseq_differential_expression per pair, timed once on the first
-`literal_loop_pairs` (at most 20) conditions.
+`literal_loop_pairs` (at most 20) conditions. With --shards N as well, a second JSON line follows: the sseq_de_each_vs_control call over
+N shards of a MultiMat, the tests each shard launched, the exchange steps, the communicator's calls and bytes per call
+(scanrs_multi_comm_info), and whether every field of the results and of the per-pair parameters equals the single handle's bit for bit.
 """
 import argparse
 import json
@@ -45,7 +47,8 @@ def main():
     ap.add_argument("--backend", choices=("logspace", "ratio"), default="logspace")
     ap.add_argument("--control-conditions", type=int, default=0)
     ap.add_argument("--per-pair-params", action="store_true", help="with --control-conditions: also time sseq_de_pairs and the per-pair literal calls")
-    ap.add_argument("--shards", type=int, default=0, help="also run one-vs-rest DE over this many shards of a MultiMat")
+    ap.add_argument("--no-literal-loop", action="store_true", help="with --per-pair-params: skip the loop of literal calls")
+    ap.add_argument("--shards", type=int, default=0, help="also run one-vs-rest DE (with --control-conditions --per-pair-params: sseq_de_each_vs_control) over this many shards of a MultiMat")
     ap.add_argument("--devices", type=str, default="", help="with --shards: comma-separated device id per shard (default: all on device 0)")
     a = ap.parse_args()
     backend = sa.NB_EXACT_RATIO if a.backend == "ratio" else sa.NB_EXACT_LOGSPACE
@@ -72,7 +75,7 @@ def main():
 
     t_params, params = timed(lambda: sa.compute_sseq_params(m))
     if a.control_conditions:
-        return control_leg(a, m, labels, params, t_params, backend, timed, nnz)
+        return control_leg(a, m, labels, params, t_params, backend, timed, nnz, (ip, ix, vv))
     t_pass, (sums, cnt) = timed(lambda: sa.group_sums(m, labels, a.groups))
     allsum = sums.sum(axis=1)
     sf_a = np.array([params.size_factors[labels == j].sum() for j in range(a.groups)])
@@ -160,7 +163,41 @@ def ratio_fallbacks(xa, xb, sf_a, sf_b, params, exact):
     return n_fall
 
 
-def control_leg(a, m, labels, params, t_params, backend, timed, nnz):
+PAIR_RESULT_FIELDS = ("sums_in", "sums_out", "p_values", "adjusted_p_values", "log2_fold_change", "normalized_mean_in", "normalized_mean_out")
+PAIR_PARAM_FIELDS = ("gene_means", "gene_variances", "gene_moment_phi", "gene_phi", "use_genes", "zeta_hat", "delta", "size_factor_a", "size_factor_b",
+                     "median_total", "sum_size_factors", "num_cells_a", "num_cells_b", "literal")
+
+
+def sharded_pairs_leg(a, triplet, labels, groups, backend, single):
+    devices = [int(d) for d in a.devices.split(",")] if a.devices else [0] * a.shards
+    if len(devices) != a.shards:
+        raise SystemExit("--devices needs one id per shard")
+    ip, ix, vv = (t.cpu().numpy() for t in triplet)  # MultiMat takes the whole matrix from the host once
+    t0 = time.perf_counter()
+    mm = sa.MultiMat(a.genes, a.cells, sa.CSC, ip, ix, vv, a.shards, devices=devices)
+    t_create = (time.perf_counter() - t0) * 1e3
+    before = [mm.comm_info(i) for i in range(a.shards)]
+    calls, got = [], None
+    for _ in range(a.reps):
+        t0 = time.perf_counter()
+        got = sa.sseq_de_each_vs_control(mm, labels, control=0, n_groups=groups, backend=backend)
+        calls.append(round((time.perf_counter() - t0) * 1e3, 2))
+    after = [mm.comm_info(i) for i in range(a.shards)]
+    same = all(np.array_equal(np.asarray(getattr(r, f)), np.asarray(getattr(w, f)), equal_nan=True)
+               for fields, i in ((PAIR_RESULT_FIELDS, 0), (PAIR_PARAM_FIELDS, 1)) for r, w in zip(got[i], single[i]) for f in fields)
+    print(json.dumps({
+        "shards": a.shards, "devices": devices, "cells_per_shard": [hi - lo for _, lo, hi in mm.shard_ranges()], "create_ms": round(t_create, 2),
+        "sharded_pairs_call_ms": calls,
+        "de_shard_tests": [mm.counter("de_shard_tests", i) for i in range(a.shards)],
+        "de_shard_allreduces": [mm.counter("de_shard_allreduces", i) for i in range(a.shards)],
+        "comm_calls_per_call": [(y["allreduce_calls"] - x["allreduce_calls"]) // a.reps for x, y in zip(before, after)],
+        "comm_bytes_per_call": [(y["allreduce_bytes"] - x["allreduce_bytes"]) // a.reps for x, y in zip(before, after)],
+        "equals_single_handle_bits": bool(same),
+    }), flush=True)
+    mm.close()
+
+
+def control_leg(a, m, labels, params, t_params, backend, timed, nnz, triplet):
     groups = a.control_conditions + 1
     t_pass, (sums, cnt) = timed(lambda: sa.group_sums(m, labels, groups))
     sf = np.bincount(labels, weights=params.size_factors, minlength=groups)
@@ -172,10 +209,10 @@ def control_leg(a, m, labels, params, t_params, backend, timed, nnz):
     asym = use & (xa > 900) & (xb > 900)
     trivial = ((xa + xb) == 0) | (params.gene_phi[:, None] == 0) | (sf_a[None, :] == 0) | (sf_b[None, :] == 0)
     exact = ~asym & ~trivial
-    pairs = {}
+    pairs, single = {}, None
     if a.per_pair_params:
-        t_pairs, _ = timed(lambda: sa.sseq_de_each_vs_control(m, labels, control=0, n_groups=groups, backend=backend))
-        n_lit = min(20, groups - 1)
+        t_pairs, single = timed(lambda: sa.sseq_de_each_vs_control(m, labels, control=0, n_groups=groups, backend=backend))
+        n_lit = 0 if a.no_literal_loop else min(20, groups - 1)
         control = np.flatnonzero(labels == 0)
         t0 = time.perf_counter()
         for g in range(1, n_lit + 1):
@@ -192,7 +229,9 @@ def control_leg(a, m, labels, params, t_params, backend, timed, nnz):
         "tests": int(a.genes * (groups - 1)), "exact_tests": int(exact.sum()), "asymptotic_tests": int(asym.sum()),
         "early_return_tests": int((trivial & ~asym).sum()), "exact_terms": int(((xa + xb + 1) * exact).sum()),
         "ratio_fallback_tests": ratio_fallbacks(xa, xb, sf_a, sf_b, params, exact) if backend == sa.NB_EXACT_RATIO else 0,
-    }))
+    }), flush=True)
+    if a.shards and a.per_pair_params:
+        sharded_pairs_leg(a, triplet, labels, groups, backend, single)
 
 
 if __name__ == "__main__":

@@ -3,7 +3,13 @@ clustering (the generator's 20 clusters) over-split into 40 labels, scores on th
 the literal one (handle option merge_fused), passes over the nonzeros, candidates, rounds, merges, ms per candidate, the
 medoids' ms, and the fused pass's bytes against HBM peak. One JSON line.
 
-    python tools/merge_bench.py [--cells 1000000] [--genes 33000] [--splits 2] [--no-literal]
+    python tools/merge_bench.py [--cells 1000000] [--genes 33000] [--splits 2] [--no-literal] [--shards N [--devices a,b,...]]
+
+With --shards N a second JSON line follows: the same matrix cut over N shards of a MultiMat (`--devices`: one id per shard, default
+all on device 0, which measures the overhead of the scheme, not a speed-up), scores as a host array over all cells: ms of the fused
+merge_clusters call and of cluster_medoids, the exchange steps of each, the medoids' ms per radix round, the communicator's calls and
+bytes per call (scanrs_multi_comm_info), the tests each shard launched, and whether labels and trace equal the single handle's bit
+for bit.
 """
 import argparse
 import json
@@ -41,6 +47,8 @@ def main():
     ap.add_argument("--splits", type=int, default=2, help="labels per planted cluster")
     ap.add_argument("--dims", type=int, default=10)
     ap.add_argument("--no-literal", action="store_true")
+    ap.add_argument("--shards", type=int, default=0, help="also run the fused route over this many shards of a MultiMat")
+    ap.add_argument("--devices", type=str, default="", help="with --shards: comma-separated device id per shard (default: all on device 0)")
     a = ap.parse_args()
     import torch
 
@@ -93,7 +101,46 @@ def main():
             "max_rel_diff_min_p": float(np.nanmax(np.abs(tr_f.min_p_adj - tr_l.min_p_adj) / np.maximum(tr_l.min_p_adj, 1e-300)))
             if tr_f.n_candidates == tr_l.n_candidates and tr_f.n_candidates else None,
         })
-    print(json.dumps(res))
+    print(json.dumps(res), flush=True)
+    if a.shards:
+        m.set_option("merge_fused", 1)
+        sharded_leg(a, (ip, ix, vv), scores.cpu().numpy(), labels, out_f, tr_f)
+
+
+def sharded_leg(a, triplet, scores, labels, out_single, tr_single):
+    devices = [int(d) for d in a.devices.split(",")] if a.devices else [0] * a.shards
+    if len(devices) != a.shards:
+        raise SystemExit("--devices needs one id per shard")
+    ip, ix, vv = (t.cpu().numpy() for t in triplet)  # MultiMat takes the whole matrix from the host once
+    t0 = time.perf_counter()
+    mm = sa.MultiMat(a.genes, a.cells, sa.CSC, ip, ix, vv, a.shards, devices=devices)
+    t_create = (time.perf_counter() - t0) * 1e3
+    sa.cluster_medoids(mm, scores, labels)  # warm
+    t0 = time.perf_counter()
+    sa.cluster_medoids(mm, scores, labels)
+    t_med = (time.perf_counter() - t0) * 1e3
+    med_steps = mm.counter("de_shard_allreduces", 0)
+    sa.merge_clusters(mm, scores, labels)  # warm
+    before = [mm.comm_info(i) for i in range(a.shards)]
+    t0 = time.perf_counter()
+    out, tr = sa.merge_clusters(mm, scores, labels, trace=True)
+    t_merge = (time.perf_counter() - t0) * 1e3
+    after = [mm.comm_info(i) for i in range(a.shards)]
+    same = bool(np.array_equal(out, out_single)) and all(
+        getattr(tr, f).tobytes() == getattr(tr_single, f).tobytes() for f in ("leaf0", "leaf1", "n_de", "min_p_adj")) and (
+        tr.n_candidates, tr.n_rounds, tr.n_merges, tr.n_passes) == (tr_single.n_candidates, tr_single.n_rounds, tr_single.n_merges, tr_single.n_passes)
+    print(json.dumps({
+        "shards": a.shards, "devices": devices, "cells_per_shard": [hi - lo for _, lo, hi in mm.shard_ranges()], "create_ms": round(t_create, 2),
+        "sharded_fused_ms": round(t_merge, 1), "candidates": tr.n_candidates, "rounds": tr.n_rounds, "merges": tr.n_merges,
+        "sharded_medoids_ms": round(t_med, 2), "medoid_exchange_steps": med_steps,
+        "medoid_ms_per_radix_round": round(t_med / max(1, med_steps - 1), 3),
+        "de_shard_tests": [mm.counter("de_shard_tests", i) for i in range(a.shards)],
+        "de_shard_allreduces": [mm.counter("de_shard_allreduces", i) for i in range(a.shards)],
+        "comm_calls_per_call": [y["allreduce_calls"] - x["allreduce_calls"] for x, y in zip(before, after)],
+        "comm_bytes_per_call": [y["allreduce_bytes"] - x["allreduce_bytes"] for x, y in zip(before, after)],
+        "equals_single_handle_bits": same,
+    }), flush=True)
+    mm.close()
 
 
 if __name__ == "__main__":
