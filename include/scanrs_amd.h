@@ -612,7 +612,8 @@ int scanrs_mat_get_counter(scanrs_mat *m, const char *key, uint64_t *value);
  *   "h5_threads" (8)               threads that inflate the chunks of a large filtered HDF5 read
  *   "eig_threads" (4)              host team of the Rayleigh-Ritz eigensolver for matrices of 768+ rows (1, 2 or 4)
  *   "knn_exhaustive" (0)           1: never use the bf16-MFMA filter of scanrs_knn*
- *   "knn_filter_min_points" (32768), "knn_ratio" (4), "knn_stats" (0)   tuning / statistics of that filter
+ *   "knn_filter_min_points" (32768), "knn_ratio" (4), "knn_stats" (0)   tuning / statistics of that filter (the figures
+ *                                  "knn_stats" prints are also returned by scanrs_debug_knn_last_stats)
  *   "sync_timeout_s" (120)         BOUNDED WAITS: no call of this library blocks on the device without a deadline. Every wait for
  *                                  a stream or an event (and every barrier between the shard threads of scanrs_multi_*) is a poll
  *                                  with this deadline in seconds; when it passes, the call returns SCANRS_ERR_DEVICE and
@@ -697,6 +698,29 @@ int scanrs_debug_dense_gemm(scanrs_mat *m, int route, const double *x, int x_ske
  * or NULL; needs l and ldc even): the compact copy of X's first l columns the same kernel writes; read first, written back whole. */
 int scanrs_debug_weighted_colsum(scanrs_mat *m, const double *b, uint32_t rank, const double *x, uint32_t ldx, uint64_t n, uint32_t l,
                                  double *w, uint32_t ldw, double *xc, uint32_t ldc);
+
+/* ---- the bf16-MFMA filter of scanrs_knn* / scanrs_find_nn (knn.hip). For tests. -------------------------------------------------
+ * The filtered search (default from "knn_filter_min_points" points on, d <= 58, k <= 64, at least 256 queries, max |coordinate|
+ * inside the magnitude window and every coordinate finite) promises the result of the exhaustive f64 kernel: per round, a query's
+ * candidate list must hold every point whose f64 distance is <= the query's threshold tau, and little else.
+ * scanrs_debug_knn_filter runs the operand preparation, the threshold kernel and ONE pass of the filter kernel, the kernels
+ * the search itself launches, on host arrays: queries n_q x d, points n_p x d (row-major), tau[n_q] (squared distances; +inf =
+ * everything passes), over rows 0, stride, 2 stride, ... of the points. cnt[n_q]: candidates found (a value > cap: the list
+ * overflowed and the search would redo that query exhaustively); cand[n_q x cap]: the lists, row indices of `points` in no
+ * particular order, slots that were not written = UINT32_MAX. SCANRS_ERR_ARGUMENT when d > 58 or the input is outside the window. */
+int scanrs_debug_knn_filter(const double *queries, uint64_t n_q, const double *points, uint64_t n_p, uint32_t d, const double *tau,
+                            uint64_t stride, uint32_t *cnt, uint32_t *cand);
+/* What the last scanrs_knn / scanrs_knn_device / scanrs_find_nn of the process did (no device needed). *filtered: 1 = it went
+ * through the filter; then *first_stride = the stride of the subset ranked exactly first and *n_rounds filter rounds followed, of
+ * which the first `capacity` are reported: strides[i], points[i] = points of that subset, cand_sum[i] / cand_max[i] = sum and
+ * maximum of the candidate counters over the queries (an overflowed list counts with what its counter reached), overflowed[i] =
+ * queries redone exhaustively. Not filtered: *n_rounds = 0. The "knn_stats" option prints the same figures on stderr. */
+int scanrs_debug_knn_last_stats(int *filtered, uint64_t *first_stride, uint32_t *n_rounds, uint32_t capacity, uint64_t *strides,
+                                uint64_t *points, uint64_t *cand_sum, uint32_t *cand_max, uint32_t *overflowed);
+/* The filter's constants (host only): the margin gamma, the list capacity, the largest d and k and the smallest query count it
+ * takes, and the magnitude window coord_min <= max |coordinate| <= coord_max outside of which the exhaustive kernel answers. */
+int scanrs_debug_knn_filter_params(double *gamma, uint32_t *cap, uint32_t *dmax, uint32_t *k_max, uint64_t *nq_min, double *coord_min,
+                                   double *coord_max);
 
 /* Diagnostics of the bounded waits (no device needed): runs the library's wait loop on an event that is never signalled and
  * returns SCANRS_ERR_DEVICE once `timeout_s` seconds have passed, with the report a real stuck wait leaves behind. */

@@ -849,6 +849,45 @@ def debug_dense_route(kind: str, n: int, m: int, rows: int, ldx: int, ldy: int =
     return int(route.value), int(nt.value), int(groups.value)
 
 
+def debug_knn_filter_params() -> dict:
+    """The constants of the kNN filter (scanrs_debug_knn_filter_params, host only): gamma, cap, dmax, k_max, nq_min and the magnitude
+    window coord_min <= max |coordinate| <= coord_max."""
+    gamma, cmin, cmax = ctypes.c_double(), ctypes.c_double(), ctypes.c_double()
+    cap, dmax, k_max, nq_min = ctypes.c_uint32(), ctypes.c_uint32(), ctypes.c_uint32(), ctypes.c_uint64()
+    _check(_lib.scanrs_debug_knn_filter_params(ctypes.byref(gamma), ctypes.byref(cap), ctypes.byref(dmax), ctypes.byref(k_max),
+                                               ctypes.byref(nq_min), ctypes.byref(cmin), ctypes.byref(cmax)))
+    return {"gamma": gamma.value, "cap": int(cap.value), "dmax": int(dmax.value), "k_max": int(k_max.value), "nq_min": int(nq_min.value),
+            "coord_min": cmin.value, "coord_max": cmax.value}
+
+
+def debug_knn_filter(queries, points, tau, stride: int = 1):
+    """One pass of the kNN filter (scanrs_debug_knn_filter) over rows 0, stride, ... of `points` with the thresholds `tau` (squared
+    distances): (cnt[n_q], cand[n_q, cap]); a list is valid up to min(cnt, cap), unwritten slots hold UINT32_MAX."""
+    q, p = _f64(np.atleast_2d(queries)), _f64(np.atleast_2d(points))
+    t = _f64(tau).reshape(-1)
+    if q.shape[1] != p.shape[1] or t.shape[0] != q.shape[0]:
+        raise ScanrsError(1, "Dimension mismatch")
+    cap = debug_knn_filter_params()["cap"]
+    cnt, cand = np.zeros(q.shape[0], dtype=np.uint32), np.zeros((q.shape[0], cap), dtype=np.uint32)
+    _check(_lib.scanrs_debug_knn_filter(_p(q), ctypes.c_uint64(q.shape[0]), _p(p), ctypes.c_uint64(p.shape[0]), ctypes.c_uint32(q.shape[1]),
+                                        _p(t), ctypes.c_uint64(int(stride)), _p(cnt), _p(cand)))
+    return cnt, cand
+
+
+def debug_knn_last_stats() -> dict:
+    """What the last knn / knn_device / find_nn of the process did (scanrs_debug_knn_last_stats): {"filtered", "first_stride",
+    "rounds": [{"stride", "points", "cand_sum", "cand_max", "overflowed"}, ...]}."""
+    cap = 64
+    filtered, first, n = ctypes.c_int(), ctypes.c_uint64(), ctypes.c_uint32()
+    st, pts, cs = (np.zeros(cap, dtype=np.uint64) for _ in range(3))
+    cm, ov = (np.zeros(cap, dtype=np.uint32) for _ in range(2))
+    _check(_lib.scanrs_debug_knn_last_stats(ctypes.byref(filtered), ctypes.byref(first), ctypes.byref(n), ctypes.c_uint32(cap), _p(st), _p(pts),
+                                            _p(cs), _p(cm), _p(ov)))
+    rounds = [{"stride": int(st[i]), "points": int(pts[i]), "cand_sum": int(cs[i]), "cand_max": int(cm[i]), "overflowed": int(ov[i])}
+              for i in range(min(int(n.value), cap))]
+    return {"filtered": bool(filtered.value), "first_stride": int(first.value), "rounds": rounds}
+
+
 def set_global_option(key: str, value: float):
     """Process-wide options of the entry points that take no handle (include/scanrs_amd.h, scanrs_set_global_option)."""
     _check(_lib.scanrs_set_global_option(key.encode(), ctypes.c_double(value)))
@@ -1326,7 +1365,7 @@ EXPORTED_SYMBOLS = [
     "scanrs_multi_create", "scanrs_multi_free", "scanrs_multi_n_shards", "scanrs_multi_shard", "scanrs_multi_normalize", "scanrs_multi_pca_bk", "scanrs_multi_pca_rand", "scanrs_multi_pca_irlba", "scanrs_multi_log_normalize", "scanrs_multi_sseq_params", "scanrs_multi_group_sums", "scanrs_multi_sseq_de", "scanrs_multi_comm_info",
     "scanrs_sseq_de_pairs_sharded", "scanrs_merge_clusters_sharded", "scanrs_cluster_medoids_sharded", "scanrs_multi_sseq_de_pairs", "scanrs_multi_merge_clusters", "scanrs_multi_cluster_medoids",
     "scanrs_plan_shards", "scanrs_profile_enable", "scanrs_profile_reset", "scanrs_profile_get", "scanrs_mat_sync", "scanrs_mat_set_spmm_path", "scanrs_mat_set_option", "scanrs_set_global_option", "scanrs_mat_set_panel_precision",
-    "scanrs_mat_chol_rinv", "scanrs_mat_get_counter", "scanrs_host_chol_upper", "scanrs_host_inv_upper", "scanrs_host_sym_eig", "scanrs_host_sym_eig_topk", "scanrs_debug_wait_never", "scanrs_debug_barrier_alone", "scanrs_debug_arena_selftest", "scanrs_debug_dense_route", "scanrs_debug_dense_gram", "scanrs_debug_dense_gemm", "scanrs_debug_weighted_colsum", "scanrs_init", "scanrs_release_cached_memory", "scanrs_cached_memory_bytes", "scanrs_reserve_device_memory", "scanrs_device_memory_in_use",
+    "scanrs_mat_chol_rinv", "scanrs_mat_get_counter", "scanrs_host_chol_upper", "scanrs_host_inv_upper", "scanrs_host_sym_eig", "scanrs_host_sym_eig_topk", "scanrs_debug_wait_never", "scanrs_debug_barrier_alone", "scanrs_debug_arena_selftest", "scanrs_debug_dense_route", "scanrs_debug_dense_gram", "scanrs_debug_dense_gemm", "scanrs_debug_weighted_colsum", "scanrs_debug_knn_filter", "scanrs_debug_knn_last_stats", "scanrs_debug_knn_filter_params", "scanrs_init", "scanrs_release_cached_memory", "scanrs_cached_memory_bytes", "scanrs_reserve_device_memory", "scanrs_device_memory_in_use",
     "scanrs_h5_read_csc_matrix", "scanrs_h5_read_adaptive_csr_matrix", "scanrs_h5_read_matrix_metadata", "scanrs_h5_matrix_free",
     "scanrs_h5_matrix_shape", "scanrs_h5_matrix_arrays", "scanrs_h5_matrix_n_strings", "scanrs_h5_matrix_string", "scanrs_h5_matrix_removed",
     "scanrs_h5_read_umi_counts", "scanrs_h5_get_clustering_keys", "scanrs_h5_get_clustering", "scanrs_h5_get_differential_expression",

@@ -1115,6 +1115,41 @@ int scanrs_find_nn(const double *queries, uint64_t n_q, const double *points, ui
         knn_host(queries, n_q, points, n_p, d, k, include_self == 0, out);
     });
 }
+int scanrs_debug_knn_filter(const double *queries, uint64_t n_q, const double *points, uint64_t n_p, uint32_t d, const double *tau,
+                            uint64_t stride, uint32_t *cnt, uint32_t *cand) {
+    return guard([&] {
+        if (!queries || !points || !tau || !cnt || !cand) fail(SCANRS_ERR_ARGUMENT, "null argument");
+        need_device();
+        knn_filter_debug(queries, n_q, points, n_p, d, tau, stride, cnt, cand);
+    });
+}
+int scanrs_debug_knn_last_stats(int *filtered, uint64_t *first_stride, uint32_t *n_rounds, uint32_t capacity, uint64_t *strides, uint64_t *points,
+                                uint64_t *cand_sum, uint32_t *cand_max, uint32_t *overflowed) {
+    return guard([&] {
+        if (!filtered || !first_stride || !n_rounds) fail(SCANRS_ERR_ARGUMENT, "null argument");
+        if (capacity && (!strides || !points || !cand_sum || !cand_max || !overflowed)) fail(SCANRS_ERR_ARGUMENT, "null array");
+        bool f = false;
+        std::vector<uint64_t> st, np, cs;
+        std::vector<uint32_t> cm, ov;
+        knn_last_stats(f, *first_stride, st, np, cs, cm, ov);
+        *filtered = f ? 1 : 0;
+        *n_rounds = (uint32_t)st.size();
+        for (uint32_t i = 0; i < capacity && i < st.size(); i++) {
+            strides[i] = st[i];
+            points[i] = np[i];
+            cand_sum[i] = cs[i];
+            cand_max[i] = cm[i];
+            overflowed[i] = ov[i];
+        }
+    });
+}
+int scanrs_debug_knn_filter_params(double *gamma, uint32_t *cap, uint32_t *dmax, uint32_t *k_max, uint64_t *nq_min, double *coord_min,
+                                   double *coord_max) {
+    return guard([&] {
+        if (!gamma || !cap || !dmax || !k_max || !nq_min || !coord_min || !coord_max) fail(SCANRS_ERR_ARGUMENT, "null argument");
+        knn_filter_params(*gamma, *cap, *dmax, *k_max, *nq_min, *coord_min, *coord_max);
+    });
+}
 
 // ---- multi-GPU ----------------------------------------------------------------------------------------------------
 int scanrs_mat_set_shard(scanrs_mat *m, uint32_t rank, uint32_t world, uint64_t outer_begin, uint64_t outer_global,

@@ -630,6 +630,13 @@ void knn_host(const double *queries, uint64_t n_q, const double *points, uint64_
 // the same with both point sets already in device memory (row-major, leading dimensions in elements); `out` is a host array
 void knn_device(const double *d_queries, uint32_t ld_q, uint64_t n_q, const double *d_points, uint32_t ld_p, uint64_t n_p, uint32_t d,
                 uint32_t k, bool skip_same_index, uint32_t *out);
+// for tests (scanrs_debug_knn_*): what the last knn_device of the process did, one entry per filter round (nothing when it did not go
+// through the filter); the filter's constants; one filter pass on host arrays
+void knn_last_stats(bool &filtered, uint64_t &first_stride, std::vector<uint64_t> &strides, std::vector<uint64_t> &points,
+                    std::vector<uint64_t> &cand_sum, std::vector<uint32_t> &cand_max, std::vector<uint32_t> &overflowed);
+void knn_filter_params(double &gamma, uint32_t &cap, uint32_t &dmax, uint32_t &k_max, uint64_t &nq_min, double &coord_min, double &coord_max);
+void knn_filter_debug(const double *queries, uint64_t n_q, const double *points, uint64_t n_p, uint32_t d, const double *tau, uint64_t stride,
+                      uint32_t *cnt, uint32_t *cand);
 // decode.hip
 uint64_t decode_adaptive_vectors(const scanrs_adaptive_vec *vecs, uint64_t n_vecs, uint64_t vec_len, DevBuf<uint64_t> &indptr,
                                  DevBuf<uint32_t> &indices, DevBuf<uint32_t> &values);

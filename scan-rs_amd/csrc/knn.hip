@@ -6,15 +6,20 @@
 //    wave-uniform in SGPRs (scalar loads), the squared distance as the reference forms it (sum of squared differences,
 //    nn.rs:14-21 — not the |p|^2 + |q|^2 - 2 p.q expansion, whose cancellation would reorder near neighbours), a sorted k-list
 //    per thread in private memory. f64 vector FMA bound: n_q x n x d multiply-adds (8 s at 10^6 x 50).
-//  * the filtered form (>= 32768 points): the distance matrix is GEMM-shaped, so its bulk runs on the matrix cores
+//  * the filtered form (>= 32768 points, max |coordinate| inside the magnitude window): the distance matrix is GEMM-shaped, so its bulk runs on the matrix cores
 //    (v_mfma_f32_32x32x16_bf16) as a FILTER with a rigorous error margin, and only the few pairs that pass are ranked, by the
-//    exact f64 distance above (kf_* kernels below: 0.49 s at 10^6 x 50, k = 15, identical output).
+//    exact f64 distance above (kf_* kernels below: 0.54 s at 10^6 x 50, k = 15, identical output; `python tools/knn_bench.py
+//    1000000 50 15`, same MI355X: 479 ms with the margin 0.0021 this file had until it was re-derived, 102 candidates per query in
+//    the last round; 536 ms and 158 candidates with 0.00395. Subtracting a common centre before kf_prep_* would shrink the
+//    |q|^2 + |p|^2 the margin is relative to and win that back: not done yet).
 // Ties keep ascending index order (the rule of the reference's own test oracle, `exhaustive_knn`, nn.rs:112-137; the ball
 // tree's order among exactly equidistant points is a property of that crate).
 #include <hip/hip_runtime.h>
 
 #include <cfloat>
 #include <cmath>
+#include <cstring>
+#include <mutex>
 #include <vector>
 
 #include "common.hpp"
@@ -120,10 +125,39 @@ void exhaustive(const double *dq, uint32_t ldq, uint64_t n_q, const double *dp, 
 // The distance matrix is GEMM-shaped work, so its bulk goes to bf16 MFMA (v_mfma_f32_32x32x16_bf16) — but only as a
 // FILTER whose error is bounded rigorously; every neighbour that is returned was ranked by the exact f64 distance
 // (sum of squared differences in coordinate order, nn.rs:14-21), ties by index, exactly as the exhaustive kernel does.
-//   d^2(q, p) = |q|^2 + |p|^2 - 2 G,  G = q.p.  With coordinates rounded to bf16 (relative error 2^-9 each) and f32
-//   accumulation, |G~ - G| <= 2^-8 * 1.02 * |q| |p| <= gamma (|q|^2 + |p|^2), gamma = 2^-9 * 1.02 + slack = 0.0021.
-//   If tau_q is an upper bound of q's true k-th distance, every true neighbour satisfies
-//       G~ + A_q - N_p >= 0,   A_q = tau_q / 2 - |q|^2 (1/2 - gamma),   N_p = |p|^2 (1/2 - gamma).
+//   d^2(q, p) = |q|^2 + |p|^2 - 2 G,  G = q.p, and with tau_q an upper bound of q's (computed) k-th distance a true neighbour
+//   has T = G + tau_q / 2 - (|q|^2 + |p|^2) / 2 = (tau_q - d^2) / 2 >= 0. The tile computes
+//       T~ = G~ + A_q - N_p,   A_q = tau_q / 2 - |q|^2 (1/2 - gamma),   N_p = |p|^2 (1/2 - gamma),
+//   i.e. T plus the margin gamma (|q|^2 + |p|^2), and the margin has to cover every error of T~ (write S = |q|^2 + |p|^2):
+//    * operands. A coordinate goes f64 -> f32 (relative 2^-24) -> bf16. bf16 has 8 significant bits, so round to nearest has
+//      unit roundoff u = 2^-8 (NOT 2^-9): x~ = x (1 + e), |e| <= eps = 2^-8 (1 + 2^-15). Per coordinate
+//      |q~_j p~_j - q_j p_j| <= (2 eps + eps^2) |q_j p_j|, and with Cauchy-Schwarz sum |q_j p_j| <= |q| |p| <= S / 2:
+//      |sum q~_j p~_j - G| <= (eps + eps^2 / 2) S = 0.0039140 S   (2^-8 (1 + 2^-9) = 0.0039139 is the floor no bf16 filter of
+//      this form gets under).
+//    * accumulation. The products of two bf16 are exact in f32; the 64 operand slots of a row (4 chained 32x32x16 MFMAs) are
+//      summed in f32 in an order the hardware does not document. Allowing every slot an error of 2 ulp of the running (or the
+//      largest) magnitude, whatever the order: <= eta (sum of |terms|), eta = 64 * 2 * 2^-24 = 2^-17 ... taken as 2^-16.
+//      The terms are the products (<= (1 + eps)^2 S / 2), the three pieces of A (|A| <= tau / 2 + |q|^2 / 2) and of N
+//      (<= |p|^2 / 2), pieces summing to <= (1 + 2^-7) of their value. With tau = d^2 + 2 T and d^2 <= 2 S:
+//      sum |terms| <= 2.02 S + 1.01 T, so this error is <= 2.02 * 2^-16 S = 0.0000309 S, plus 1.01 eta T which T itself absorbs.
+//    * A and N. Both are formed in f64 (|q|^2, |p|^2 by an fma chain: 58 * 2^-53 relative), converted to f32 (2^-24) and split
+//      into three bf16 pieces (split3: residual <= 2^-24 |v|); the shaves (1 - 4e-7) / (1 + 4e-7) = 6.7 * 2^-24 push those
+//      2 * 2^-24 the safe way (N down, A up), so they cost nothing here; tau is the f64 distance the rerank kernel computed,
+//      and "true neighbour" means the same computed distance (<= 1e-14 S apart from the exact one).
+//   Sum: 0.0039140 + 0.0000309 = 0.0039449 < gamma = 0.00395 (the rest, 5e-6 S, is slack). The same bound read the other way
+//   limits what passes: no candidate has d^2 > tau_q + 4 gamma S.
+//   All of this is RELATIVE error analysis: it holds while no operand, product, piece or sum overflows or falls into the
+//   f32 / bf16 subnormal range (which the matrix cores may flush). Hence the magnitude window on M = max |coordinate| of
+//   queries and points (kf_maxabs_kernel, one pass): KF_COORD_MIN <= M <= KF_COORD_MAX, every coordinate finite; outside it
+//   knn_filtered declines and the exhaustive kernel answers.
+//    * upper end 2^46: |p|^2 <= 58 M^2, tau <= 232 M^2, so |A| <= 116 M^2 = 5.8e29 stays under KF_A_PASS = 9e29, the value
+//      "everything passes" (tau = +inf) is clamped to, which itself stays under the 1e30 of the sentinel rows: a sentinel row
+//      fails every test (9e29 - 1e30 < 0) and a real point passes the clamp (9e29 - |G~| - N >= 9e29 - 87 M^2 > 0).
+//    * lower end 2^-48: single coordinates may still be tiny (or 0), so values below 2^-126 cannot be excluded; each such
+//      value (a coordinate, a product, a piece of A or N, a partial sum) is off by at most 2^-126 absolutely if flushed, in
+//      total <= 2^-126 (116 (1 + eps) M + 64 + 64 + 8) < 2^-118 (M + 1). A_q carries that as an absolute slack
+//      2^-117 (M + 1), so completeness holds for every pair; the window only keeps the slack negligible against
+//      gamma S for points of norm ~M (2^-117 against 0.004 * 2^-95 at the lower end), i.e. keeps the filter selective.
 // A_q and N_p ride in spare k-slots of the operands (three bf16 pieces each, against 1.0 on the other side), so the
 // accumulator tile IS the test value and the epilogue is one max-tree per tile plus a rare append to the query's
 // candidate list. tau_q comes from exact searches on nested strided subsets (every 256th point exhaustively, then every
@@ -132,7 +166,12 @@ void exhaustive(const double *dq, uint32_t ldq, uint64_t n_q, const double *dp, 
 constexpr uint32_t KF_DP = 64;     // operand row: 58 coordinates + 6 augmentation slots
 constexpr uint32_t KF_DMAX = 58;
 constexpr uint32_t KF_CAP = 1024;  // candidates per query and round
-constexpr double KF_GAMMA = 0.0021;
+constexpr uint32_t KF_KMAX = 64;   // largest k and smallest query count the filter takes
+constexpr uint64_t KF_NQ_MIN = 256;
+constexpr double KF_GAMMA = 0.00395;
+constexpr double KF_COORD_MIN = 0x1p-48, KF_COORD_MAX = 0x1p46; // the magnitude window of max |coordinate|
+constexpr float KF_SENTINEL = 1e30f; // N of a sentinel point row, -A of a sentinel query row
+constexpr double KF_A_PASS = 9e29;   // A of "everything passes": above every legitimate A, below the sentinel
 
 typedef __bf16 bf16x8 __attribute__((ext_vector_type(8)));
 typedef float f32x16 __attribute__((ext_vector_type(16)));
@@ -164,7 +203,7 @@ __global__ void kf_prep_points_kernel(const double *__restrict__ P, uint32_t ld,
         row[j] = to_bf16((float)x);
     }
     // N rounded DOWN (it is subtracted): shave a few ulps before the split
-    float nf = r < n ? (float)(nn * (0.5 - KF_GAMMA) * (1.0 - 4e-7)) : 1e30f;
+    float nf = r < n ? (float)(nn * (0.5 - KF_GAMMA) * (1.0 - 4e-7)) : KF_SENTINEL;
     uint16_t h, m, l;
     split3(-nf, h, m, l);
     row[KF_DP - 6] = row[KF_DP - 5] = row[KF_DP - 4] = 0x3F80; // 1.0
@@ -186,21 +225,22 @@ __global__ void kf_prep_queries_kernel(const double *__restrict__ Q, uint32_t ld
     }
     if (r < n) qn[r] = nn;
     uint16_t h, m, l;
-    split3(-1e30f, h, m, l); // until a threshold is set nothing passes (and never for sentinel rows)
+    split3(-KF_SENTINEL, h, m, l); // until a threshold is set nothing passes (and never for sentinel rows)
     row[KF_DP - 6] = h;
     row[KF_DP - 5] = m;
     row[KF_DP - 4] = l;
     row[KF_DP - 3] = row[KF_DP - 2] = row[KF_DP - 1] = 0x3F80;
 }
-__global__ void kf_set_threshold_kernel(const double *__restrict__ tau, const double *__restrict__ qn, uint64_t n,
+// slack: the absolute error bound 2^-117 (M + 1) of values the matrix cores may flush (see the derivation above)
+__global__ void kf_set_threshold_kernel(const double *__restrict__ tau, const double *__restrict__ qn, uint64_t n, double slack,
                                         uint16_t *__restrict__ Qb, uint32_t *__restrict__ cnt) {
     const uint64_t r = (uint64_t)blockIdx.x * blockDim.x + threadIdx.x;
     if (r >= n) return;
     cnt[r] = 0;
     double a = 0.5 * tau[r] - qn[r] * (0.5 - KF_GAMMA);
-    a += fabs(a) * 4e-7 + 1e-300; // rounded UP
-    float af = a > 1e30 ? 1e30f : (float)a; // tau = +inf (fewer than k neighbours so far): everything passes
-    if (!(af == af)) af = 1e30f;
+    a += fabs(a) * 4e-7 + slack; // rounded UP
+    float af = a > KF_A_PASS ? (float)KF_A_PASS : (float)a; // tau = +inf (fewer than k neighbours so far): everything passes
+    if (!(af == af)) af = (float)KF_A_PASS;
     uint16_t h, m, l;
     split3(af, h, m, l);
     uint16_t *row = Qb + r * KF_DP;
@@ -209,12 +249,28 @@ __global__ void kf_set_threshold_kernel(const double *__restrict__ tau, const do
     row[KF_DP - 4] = l;
 }
 
+// max |x| over an n x d matrix as the bit pattern of the double: for non-negative doubles the unsigned order of the bits is the
+// numerical order, +inf sorts above every finite value and NaN above +inf, so one atomicMax also reports non-finite input
+__global__ __launch_bounds__(256) void kf_maxabs_kernel(const double *__restrict__ X, uint32_t ld, uint64_t n, uint32_t d,
+                                                        unsigned long long *__restrict__ out) {
+    unsigned long long m = 0ull;
+    const uint64_t total = n * d, step = (uint64_t)gridDim.x * blockDim.x;
+    for (uint64_t e = (uint64_t)blockIdx.x * blockDim.x + threadIdx.x; e < total; e += step)
+        m = max(m, (unsigned long long)__double_as_longlong(fabs(X[(e / d) * ld + (e % d)])));
+#pragma unroll
+    for (int off = 32; off >= 1; off >>= 1) m = max(m, (unsigned long long)__shfl_xor((long long)m, off, 64));
+    if ((threadIdx.x & 63u) == 0 && m) atomicMax(out, m);
+}
+
 // One wave: 128 queries (4 row blocks of 32) x 32 points per step; the 4 waves of a workgroup share the query tile and take
 // every fourth 32-point block. Points are rows t * stride of Pb, t < n_sub; t >= n_sub reads the sentinel row. A passing
 // (query, point) pair is parked in a per-wave LDS buffer (LDS atomic for the position, ~100 clk) and the buffer is flushed to the
 // queries' global candidate lists in batches: with about one passing pair per tile a returning GLOBAL atomic per pair would
-// stall the wave for a memory round trip every tile (and drain the prefetched point blocks with it).
-constexpr uint32_t KF_BUF = 512; // parked pairs per wave
+// stall the wave for a memory round trip every tile (and drain the prefetched point blocks with it). The buffer holds a whole
+// 32 x 32 block of pairs and is flushed when the next block's pairs (at most 16 per lane that has one) might not fit, so no pair
+// is ever dropped: where a large share of all pairs passes (a small or tightly clustered point set) a query still overflows only
+// when its own list does.
+constexpr uint32_t KF_BUF = 1024; // parked pairs per wave = the pairs of one 32 x 32 block
 __device__ __forceinline__ void kf_flush(uint32_t lane, uint32_t n, const uint2 *buf, uint32_t *__restrict__ cand, uint32_t *__restrict__ cnt) {
     for (uint32_t e = lane; e < n; e += 64u) {
         const uint2 qp = buf[e];
@@ -231,6 +287,7 @@ __global__ __launch_bounds__(256, 2) void kf_filter_kernel(const uint16_t *__res
     const uint32_t r = lane & 31u, h = lane >> 5;
     const uint64_t q0 = (uint64_t)blockIdx.x * 128u;
     if (lane == 0) park_n[wave] = 0u;
+    uint32_t parked = 0u; // wave-uniform upper bound of park_n[wave]
     bf16x8 a[4][4];
 #pragma unroll
     for (int rb = 0; rb < 4; rb++)
@@ -279,7 +336,18 @@ __global__ __launch_bounds__(256, 2) void kf_filter_kernel(const uint16_t *__res
                     float mx = acc[e][0];
 #pragma unroll
                     for (int i = 1; i < 16; i++) mx = fmaxf(mx, acc[e][i]);
-                    if (__builtin_amdgcn_ballot_w64(mx >= 0.0f) == 0) continue; // no pair of this 32 x 32 block passes
+                    const uint64_t lanes = __builtin_amdgcn_ballot_w64(mx >= 0.0f);
+                    if (lanes == 0) continue; // no pair of this 32 x 32 block passes
+                    const uint32_t room = 16u * (uint32_t)__popcll(lanes); // at most this many pairs follow (<= 1024 = KF_BUF)
+                    if (parked + room > KF_BUF) {
+                        parked = park_n[wave]; // the exact count
+                        if (parked + room > KF_BUF) { // make room first
+                            kf_flush(lane, parked, park[wave], cand, cnt);
+                            if (lane == 0) park_n[wave] = 0u;
+                            parked = 0u;
+                        }
+                    }
+                    parked += room;
 #pragma unroll
                     for (int i = 0; i < 16; i++) {
                         if (acc[e][i] >= 0.0f) { // sentinel rows (queries past n_q, points past the subset) never get here: their A / N slots are -/+1e30
@@ -288,15 +356,10 @@ __global__ __launch_bounds__(256, 2) void kf_filter_kernel(const uint16_t *__res
                             if (pos < KF_BUF)
                                 park[wave][pos] = make_uint2(q, pr);
                             else
-                                atomicMax(&cnt[q], KF_CAP + 1u); // more than KF_BUF pairs in one tile (heavy ties): that query goes to the exhaustive kernel
+                                atomicMax(&cnt[q], KF_CAP + 1u); // cannot happen (room was made above); if it did, the query would go to the exhaustive kernel
                         }
                     }
                 }
-            }
-            const uint32_t parked = min(park_n[wave], KF_BUF);
-            if (parked > KF_BUF - 128u) { // wave-uniform
-                kf_flush(lane, parked, park[wave], cand, cnt);
-                if (lane == 0) park_n[wave] = 0u;
             }
         }
     }
@@ -305,22 +368,17 @@ __global__ __launch_bounds__(256, 2) void kf_filter_kernel(const uint16_t *__res
 
 // exact f64 ranking of a query's candidates: one wave per query, a candidate per lane (the same fma chain over the coordinates as
 // knn_kernel), then k rounds of a wave-wide lexicographic (distance, index) minimum. Writes the k neighbours (UINT32_MAX padded)
-// and tau = the k-th distance (+inf when fewer than k exist). Overflowed lists are flagged and left to the exhaustive kernel.
+// and tau = the k-th distance (+inf when fewer than k exist). Overflowed lists (cnt > KF_CAP) are left to the exhaustive kernel.
 constexpr uint32_t KF_PER_LANE = KF_CAP / 64u;
 __global__ __launch_bounds__(256) void kf_rerank_kernel(const double *__restrict__ Q, uint32_t ldq, uint64_t n_q, const double *__restrict__ P,
                                                         uint32_t ldp, uint32_t d, uint32_t k, int skip_same_index,
                                                         const uint32_t *__restrict__ cand, const uint32_t *__restrict__ cnt,
-                                                        uint32_t *__restrict__ out, double *__restrict__ tau,
-                                                        uint32_t *__restrict__ overflow) {
+                                                        uint32_t *__restrict__ out, double *__restrict__ tau) {
     const uint32_t lane = threadIdx.x & 63u;
     const uint64_t q = (uint64_t)blockIdx.x * 4u + (threadIdx.x >> 6);
     if (q >= n_q) return;
     const uint32_t c = cnt[q];
-    if (c > KF_CAP) {
-        if (lane == 0) overflow[q] = 1u;
-        return;
-    }
-    if (lane == 0) overflow[q] = 0u;
+    if (c > KF_CAP) return; // the host reads cnt and redoes this query exhaustively
     double dist[KF_PER_LANE];
     uint32_t idx[KF_PER_LANE];
     const double *__restrict__ qr = Q + q * ldq;
@@ -426,18 +484,74 @@ __global__ void kf_scatter_result_kernel(const uint32_t *__restrict__ res, const
     out[(uint64_t)rows[e / k] * k + (e % k)] = res[e];
 }
 
+// what the last scanrs_knn* / scanrs_find_nn call of the process did (scanrs_debug_knn_last_stats)
+struct KfRound {
+    uint64_t stride, points, cand_sum;
+    uint32_t cand_max, overflowed;
+};
+struct KnnLastStats {
+    bool filtered = false;
+    uint64_t first_stride = 0; // stride of the subset that round 0 ranks exactly
+    std::vector<KfRound> rounds;
+};
+std::mutex g_stats_mutex;
+KnnLastStats g_last_stats;
+
+// the bf16 operands of one filtered search
+struct KfOperands {
+    DevBuf<uint16_t> Qb, Pb;
+    DevBuf<double> qn;
+    uint64_t nq_rows = 0;
+    double slack = 0.0; // absolute part of the margin, 2^-117 (M + 1)
+};
+// false: a coordinate is not finite or max |coordinate| lies outside the magnitude window; nothing has been prepared
+bool kf_prepare(hipStream_t s, const double *dq, uint32_t ldq, uint64_t n_q, const double *dp, uint32_t ldp, uint64_t n_p, uint32_t d,
+                KfOperands &op) {
+    DevBuf<unsigned long long> mx(1);
+    SCANRS_HIP(hipMemsetAsync(mx.p, 0, 8, s));
+    auto reduce = [&](const double *x, uint32_t ld, uint64_t n) {
+        const uint64_t blocks = std::min<uint64_t>((n * d + 255) / 256, 2048);
+        hipLaunchKernelGGL(kf_maxabs_kernel, dim3((unsigned)blocks), dim3(256), 0, s, x, ld, n, d, mx.p);
+    };
+    reduce(dp, ldp, n_p);
+    if (dq != dp || ldq != ldp || n_q > n_p) reduce(dq, ldq, n_q);
+    unsigned long long bits = 0;
+    SCANRS_HIP(hipMemcpyAsync(&bits, mx.p, 8, hipMemcpyDeviceToHost, s));
+    SCANRS_SYNC(s);
+    double m;
+    memcpy(&m, &bits, 8);
+    if (!(m >= KF_COORD_MIN && m <= KF_COORD_MAX)) return false; // NaN and +inf fail the comparison too
+    op.slack = 0x1p-117 * (m + 1.0);
+    op.nq_rows = (n_q + 127) / 128 * 128;
+    const uint64_t np_rows = n_p + 1; // one sentinel row behind the points
+    op.Qb.alloc(op.nq_rows * KF_DP);
+    op.Pb.alloc(np_rows * KF_DP);
+    op.qn.alloc(n_q);
+    hipLaunchKernelGGL(kf_prep_points_kernel, dim3((unsigned)((np_rows + 255) / 256)), dim3(256), 0, s, dp, ldp, n_p, np_rows, d, op.Pb.p);
+    hipLaunchKernelGGL(kf_prep_queries_kernel, dim3((unsigned)((op.nq_rows + 255) / 256)), dim3(256), 0, s, dq, ldq, n_q, op.nq_rows, d, op.Qb.p,
+                       op.qn.p);
+    return true;
+}
+// one pass of the filter over rows 0, st, 2 st, ... of the points with the thresholds tau: cnt (n_q) and the lists cand (n_q x KF_CAP)
+void kf_filter_pass(hipStream_t s, const KfOperands &op, const double *tau, uint64_t n_q, uint64_t n_p, uint64_t st, uint32_t *cand,
+                    uint32_t *cnt) {
+    const uint64_t n_sub = (n_p + st - 1) / st;
+    hipLaunchKernelGGL(kf_set_threshold_kernel, dim3((unsigned)((n_q + 255) / 256)), dim3(256), 0, s, tau, op.qn.p, n_q, op.slack, op.Qb.p, cnt);
+    hipLaunchKernelGGL(kf_filter_kernel, dim3((unsigned)(op.nq_rows / 128)), dim3(256), 0, s, op.Qb.p, n_q, op.Pb.p, n_sub, st, n_p, cand, cnt);
+}
+
 bool knn_filtered(const double *dq, uint32_t ldq, uint64_t n_q, const double *dp, uint32_t ldp, uint64_t n_p, uint32_t d, uint32_t k,
-                  int skip, uint32_t *dout) {
+                  int skip, uint32_t *dout, KnnLastStats &stats) {
     const GlobalOptions &go = global_options(); // scanrs_set_global_option (read per call: tests flip them)
     const bool off = go.knn_exhaustive != 0;
     const uint64_t min_points = go.knn_filter_min_points;
-    if (off || d > KF_DMAX || n_p < min_points || k > 64 || n_q < 256) return false;
+    if (off || d > KF_DMAX || n_p < min_points || k > KF_KMAX || n_q < KF_NQ_MIN) return false;
     hipStream_t s = 0;
     // nested strided subsets S_0 < S_1 < ... < all points: S_0 (at most KF_CAP points) is ranked exactly for every query, which gives
     // an upper bound tau of the k-th distance; every further subset is `ratio` times denser and goes through the filter with the
     // previous tau, which lets about k * ratio * (volume inflation of the margin) pairs per query through.
     const uint64_t ratio = std::max<uint64_t>(2, go.knn_ratio); // default 4: 1M x 50, k = 15: 487 ms at 4, 553 at 8, 606 at 16 (fewer passes, but longer candidate lists and the first overflows)
-    const bool stats = go.knn_stats != 0;
+    const bool print_stats = go.knn_stats != 0;
     std::vector<uint64_t> strides;
     uint64_t st0 = 1;
     while ((n_p + st0 - 1) / st0 > KF_CAP) st0 *= 2;
@@ -446,44 +560,39 @@ bool knn_filtered(const double *dq, uint32_t ldq, uint64_t n_q, const double *dp
         strides.push_back(st);
     }
     if (strides.empty()) return false;
-    const uint64_t nq_rows = (n_q + 127) / 128 * 128, np_rows = n_p + 1; // one sentinel row behind the points
-    DevBuf<uint16_t> Qb(nq_rows * KF_DP), Pb(np_rows * KF_DP);
-    DevBuf<double> qn(n_q), tau(n_q);
-    DevBuf<uint32_t> cnt(n_q), cand(n_q * KF_CAP), ovf(n_q);
-    hipLaunchKernelGGL(kf_prep_points_kernel, dim3((unsigned)((np_rows + 255) / 256)), dim3(256), 0, s, dp, ldp, n_p, np_rows, d, Pb.p);
-    hipLaunchKernelGGL(kf_prep_queries_kernel, dim3((unsigned)((nq_rows + 255) / 256)), dim3(256), 0, s, dq, ldq, n_q, nq_rows, d, Qb.p, qn.p);
+    KfOperands op;
+    if (!kf_prepare(s, dq, ldq, n_q, dp, ldp, n_p, d, op)) return false; // outside the magnitude window: the exhaustive kernel answers
+    stats.first_stride = st0;
+    DevBuf<double> tau(n_q);
+    DevBuf<uint32_t> cnt(n_q), cand(n_q * KF_CAP);
     { // round 0: exact ranking of the coarsest subset
         const uint32_t n0 = (uint32_t)((n_p + st0 - 1) / st0);
         hipLaunchKernelGGL(kf_fill_all_kernel, dim3((unsigned)((n_q * n0 + 255) / 256)), dim3(256), 0, s, n_q, n0, st0, cand.p, cnt.p);
         hipLaunchKernelGGL(kf_rerank_kernel, dim3((unsigned)((n_q + 3) / 4)), dim3(256), 0, s, dq, ldq, n_q, dp, ldp, d, k, skip, cand.p, cnt.p,
-                           dout, tau.p, ovf.p);
+                           dout, tau.p);
     }
+    std::vector<uint32_t> h_cnt(n_q);
     for (uint64_t st : strides) {
         const uint64_t n_sub = (n_p + st - 1) / st;
-        hipLaunchKernelGGL(kf_set_threshold_kernel, dim3((unsigned)((n_q + 255) / 256)), dim3(256), 0, s, tau.p, qn.p, n_q, Qb.p, cnt.p);
-        hipLaunchKernelGGL(kf_filter_kernel, dim3((unsigned)(nq_rows / 128)), dim3(256), 0, s, Qb.p, n_q, Pb.p, n_sub, st, n_p, cand.p, cnt.p);
+        kf_filter_pass(s, op, tau.p, n_q, n_p, st, cand.p, cnt.p);
         hipLaunchKernelGGL(kf_rerank_kernel, dim3((unsigned)((n_q + 3) / 4)), dim3(256), 0, s, dq, ldq, n_q, dp, ldp, d, k, skip, cand.p, cnt.p,
-                           dout, tau.p, ovf.p);
+                           dout, tau.p);
         SCANRS_HIP(hipGetLastError());
-        if (stats) {
-            std::vector<uint32_t> hc(n_q);
-            SCANRS_HIP(hipMemcpy(hc.data(), cnt.p, n_q * 4, hipMemcpyDeviceToHost));
-            double sum = 0;
-            uint32_t mx = 0, over = 0;
-            for (uint32_t c : hc) {
-                sum += c;
-                mx = std::max(mx, c);
-                over += c > KF_CAP;
-            }
-            fprintf(stderr, "[scanrs knn] stride %llu: %llu points, candidates per query mean %.1f max %u, %u lists overflowed\n",
-                    (unsigned long long)st, (unsigned long long)n_sub, sum / (double)n_q, mx, over);
-        }
         // overflowed lists (rare: heavy ties, adversarial clusters): those queries are redone exhaustively on this subset
-        std::vector<uint32_t> h_ovf(n_q);
-        SCANRS_HIP(hipMemcpy(h_ovf.data(), ovf.p, n_q * 4, hipMemcpyDeviceToHost));
+        SCANRS_HIP(hipMemcpy(h_cnt.data(), cnt.p, n_q * 4, hipMemcpyDeviceToHost));
+        KfRound rd{st, n_sub, 0, 0, 0};
         std::vector<uint32_t> rows;
-        for (uint64_t q = 0; q < n_q; q++)
-            if (h_ovf[q]) rows.push_back((uint32_t)q);
+        for (uint64_t q = 0; q < n_q; q++) {
+            const uint32_t c = h_cnt[q];
+            rd.cand_sum += c; // an overflowed list counts with what its counter reached
+            rd.cand_max = std::max(rd.cand_max, c);
+            if (c > KF_CAP) rows.push_back((uint32_t)q);
+        }
+        rd.overflowed = (uint32_t)rows.size();
+        stats.rounds.push_back(rd);
+        if (print_stats)
+            fprintf(stderr, "[scanrs knn] stride %llu: %llu points, candidates per query mean %.1f max %u, %u lists overflowed\n",
+                    (unsigned long long)st, (unsigned long long)n_sub, (double)rd.cand_sum / (double)n_q, rd.cand_max, rd.overflowed);
         if (!rows.empty()) {
             const uint64_t m = rows.size();
             DevBuf<uint32_t> d_rows(m), res(m * k);
@@ -524,10 +633,58 @@ bool knn_filtered(const double *dq, uint32_t ldq, uint64_t n_q, const double *dp
         }
     }
     SCANRS_SYNC(s);
+    stats.filtered = true;
     return true;
 }
 
 } // namespace
+
+void knn_last_stats(bool &filtered, uint64_t &first_stride, std::vector<uint64_t> &strides, std::vector<uint64_t> &points,
+                    std::vector<uint64_t> &cand_sum, std::vector<uint32_t> &cand_max, std::vector<uint32_t> &overflowed) {
+    std::lock_guard<std::mutex> lock(g_stats_mutex);
+    filtered = g_last_stats.filtered;
+    first_stride = g_last_stats.first_stride;
+    for (const KfRound &r : g_last_stats.rounds) {
+        strides.push_back(r.stride);
+        points.push_back(r.points);
+        cand_sum.push_back(r.cand_sum);
+        cand_max.push_back(r.cand_max);
+        overflowed.push_back(r.overflowed);
+    }
+}
+
+void knn_filter_params(double &gamma, uint32_t &cap, uint32_t &dmax, uint32_t &k_max, uint64_t &nq_min, double &coord_min, double &coord_max) {
+    gamma = KF_GAMMA;
+    cap = KF_CAP;
+    dmax = KF_DMAX;
+    k_max = KF_KMAX;
+    nq_min = KF_NQ_MIN;
+    coord_min = KF_COORD_MIN;
+    coord_max = KF_COORD_MAX;
+}
+
+// scanrs_debug_knn_filter: the operands, thresholds and ONE filter pass of knn_filtered (the same kf_prepare / kf_filter_pass) on host arrays
+void knn_filter_debug(const double *queries, uint64_t n_q, const double *points, uint64_t n_p, uint32_t d, const double *tau, uint64_t stride,
+                      uint32_t *cnt, uint32_t *cand) {
+    if (n_q == 0 || n_p == 0 || stride == 0) fail(SCANRS_ERR_ARGUMENT, "knn filter: empty input or stride 0");
+    if (d == 0 || d > KF_DMAX) fail(SCANRS_ERR_ARGUMENT, "knn filter: 1 <= dimensions <= 58");
+    if (n_p > 0xFFFFFFFEull || n_q > 0xFFFFFFFFull / KF_CAP) fail(SCANRS_ERR_SHAPE, "knn filter: too many points or queries");
+    hipStream_t s = 0;
+    DevBuf<double> dq(n_q * d), dp(n_p * d), dtau(n_q);
+    DevBuf<uint32_t> dcnt(n_q), dcand(n_q * KF_CAP);
+    SCANRS_HIP(hipMemcpy(dq.p, queries, n_q * d * 8, hipMemcpyHostToDevice));
+    SCANRS_HIP(hipMemcpy(dp.p, points, n_p * d * 8, hipMemcpyHostToDevice));
+    SCANRS_HIP(hipMemcpy(dtau.p, tau, n_q * 8, hipMemcpyHostToDevice));
+    SCANRS_HIP(hipMemsetAsync(dcand.p, 0xFF, n_q * KF_CAP * 4, s)); // slots the pass does not write read UINT32_MAX
+    KfOperands op;
+    if (!kf_prepare(s, dq.p, d, n_q, dp.p, d, n_p, d, op))
+        fail(SCANRS_ERR_ARGUMENT, "knn filter: a coordinate is not finite or max |coordinate| is outside the magnitude window");
+    kf_filter_pass(s, op, dtau.p, n_q, n_p, stride, dcand.p, dcnt.p);
+    SCANRS_HIP(hipGetLastError());
+    SCANRS_SYNC(s);
+    SCANRS_HIP(hipMemcpy(cnt, dcnt.p, n_q * 4, hipMemcpyDeviceToHost));
+    SCANRS_HIP(hipMemcpy(cand, dcand.p, n_q * KF_CAP * 4, hipMemcpyDeviceToHost));
+}
 
 void knn_device(const double *d_queries, uint32_t ld_q, uint64_t n_q, const double *d_points, uint32_t ld_p, uint64_t n_p, uint32_t d,
                 uint32_t k, bool skip_same_index, uint32_t *out) {
@@ -539,10 +696,15 @@ void knn_device(const double *d_queries, uint32_t ld_q, uint64_t n_q, const doub
     DevBuf<uint32_t> dout;
     dout.alloc(n_q * k);
     const int skip = skip_same_index ? 1 : 0;
-    if (!knn_filtered(d_queries, ld_q, n_q, d_points, ld_p, n_p, d, k, skip, dout.p))
+    KnnLastStats stats;
+    if (!knn_filtered(d_queries, ld_q, n_q, d_points, ld_p, n_p, d, k, skip, dout.p, stats)) {
+        stats = KnnLastStats(); // declined (possibly after the magnitude check): nothing of the filter ran
         exhaustive(d_queries, ld_q, n_q, d_points, ld_p, n_p, d, k, skip, dout.p);
+    }
     SCANRS_HIP(hipGetLastError());
     SCANRS_HIP(hipMemcpy(out, dout.p, n_q * k * 4, hipMemcpyDeviceToHost));
+    std::lock_guard<std::mutex> lock(g_stats_mutex);
+    g_last_stats = std::move(stats);
 }
 
 // queries (n_q x d) against points (n_p x d), both row-major host arrays; out n_q x k.
