@@ -329,7 +329,7 @@ typedef struct {
  * they are exact (three counts of 4294967295 in a row give 12884901885). The f64 results apply the handle's map per nonzero (stored
  * zeros and absent entries contribute nothing; a low-rank offset is left out, as scanrs_mat_mean_var_axis leaves it out). They use no
  * floating-point atomics and are bit-reproducible: two calls give identical arrays, also after other calls on the handle and on a
- * fresh handle. A sharded handle returns SCANRS_ERR_ARGUMENT.
+ * fresh handle. A sharded handle returns SCANRS_ERR_ARGUMENT from these plain calls; the collective *_sharded forms below serve it.
  * The kernel form follows the copy that exists: a masked walk when the result axis is the copy's outer
  * dimension, a walk over the listed vectors when the listed columns are outer vectors; integer results whose copy does not exist are
  * scattered from the other copy with 64-bit integer atomics instead of building it (handle option "subset_scatter"), f64 results
@@ -350,6 +350,47 @@ int scanrs_mat_sum_rows_dual_f64(scanrs_mat *m, const uint64_t *cols1, uint64_t 
                                  const scanrs_snoop *snoop, double *out1, double *out2);
 int scanrs_mat_mean_rows(scanrs_mat *m, const uint64_t *cols, uint64_t n, double *out);
 int scanrs_mat_mean_var_rows(scanrs_mat *m, const uint64_t *cols, uint64_t n, double *mean, double *var);
+
+/* The same eight calls on a sharded handle (scanrs_mat_set_shard / scanrs_mat_set_shard_comm, the shards of a scanrs_multi; DESIGN.md
+ * section 7k). They are COLLECTIVE: every rank calls them with the same arguments. On a handle that is not sharded they are the plain
+ * calls: the same kernels, the same bits. The convention is that of the sharded sSeq and select calls: the sharded dimension is the
+ * outer dimension of the stored matrix (the other one of a transposed view); a list along it holds GLOBAL indices and is checked
+ * against the global extent, with the plain calls' rules and messages; an output along it spans the WHOLE matrix (outer_global
+ * entries); every output is complete and identical on every rank. An offset is left out, as above. Only u64 sum all-reduces cross
+ * the shards (dtype 1 of scanrs_allreduce_fn), so no result depends on the cut into shards, the number of ranks or the transport:
+ *   - A result that runs ALONG the sharded dimension (sum_rows, sum_rows_dual, mean_rows, mean_var_rows when the view's rows are
+ *     sharded; sum_cols when its columns are) is owned by one rank, which computes it with the plain kernels on its own storage from
+ *     its part of the list; one all-reduce over the bit patterns of a zero-filled array of the whole extent copies it to everyone.
+ *     Under a map that holds the same numbers these results equal the unsharded call's bit for bit.
+ *   - A sum that CROSSES the shards (the sum_rows family when the view's columns are sharded - genes x cells with lists of cells, the
+ *     scanrs_multi shape; sum_cols when its rows are). u64: the partial sums are added by one all-reduce, exact, the unsharded call's
+ *     bits. f64: fixed point. Every mapped value x is rounded ONCE to a quantum q = 1 / scale that all ranks share, and the sum of
+ *     squares takes the f64 product x * x, rounded once to a quantum of its own; the rounded terms are added as signed 128-bit
+ *     integers (two's complement, so terms of either sign are served) and cross the shards as 32-bit limbs; the host converts the
+ *     integer sum to f64 (one rounding) and divides by the scale (exact). No floating-point addition lies between a term and that
+ *     conversion. THE QUANTUM: scale = 2^(123 - ilogb(bound)), bound = M x T, where M is the largest finite |x| over the listed
+ *     nonzeros of ALL shards (found by a pre-pass; rank r's value travels as a bit pattern in slot r of a zeroed world-long u64
+ *     array, the host takes the maximum) and T the largest number of terms a result can have: the length of the list for the
+ *     sum_rows family (the longer list of a dual call; both sums share the quantum), the global number of rows for sum_cols. The sum
+ *     of squares uses bound = (M x M) x T. Every sum then stays below 2^124 and the result is within T / 2 quanta - below 2^-90 of
+ *     the bound - of the exact sum of the f64 terms. A bound of 0 (nothing listed) gives scale 1; bounds below 2^-877 give 2^1000.
+ *     A result that met a term that is not finite is returned as NaN, in that result alone: the one place where a value can differ
+ *     in KIND from the unsharded call, which would propagate an infinity. (So is a sum of squares whose bound overflows f64.)
+ * mean_rows and mean_var_rows divide on the host as the plain calls do. `snoop` of the dual forms: every rank polls its snoop at
+ * the same checkpoints and must see the same flag; a cancelled call leaves out1 / out2 untouched on every rank.
+ * Counter "subset_allreduces" = the exchange steps of the last of these calls on the handle: 0 on an unsharded handle and for
+ * outputs without entries, 1 for results along the sharded dimension and for u64 sums that cross the shards, 2 for f64 sums that
+ * cross them (the pre-pass's maximum, then the limbs: 5 u64 per 128-bit sum and result). */
+int scanrs_mat_sum_rows_u64_sharded(scanrs_mat *m, const uint64_t *cols, uint64_t n, uint64_t *out);
+int scanrs_mat_sum_rows_f64_sharded(scanrs_mat *m, const uint64_t *cols, uint64_t n, double *out);
+int scanrs_mat_sum_cols_u64_sharded(scanrs_mat *m, const uint64_t *cols, uint64_t n, uint64_t *out);
+int scanrs_mat_sum_cols_f64_sharded(scanrs_mat *m, const uint64_t *cols, uint64_t n, double *out);
+int scanrs_mat_sum_rows_dual_u64_sharded(scanrs_mat *m, const uint64_t *cols1, uint64_t n1, const uint64_t *cols2, uint64_t n2,
+                                         const scanrs_snoop *snoop, uint64_t *out1, uint64_t *out2);
+int scanrs_mat_sum_rows_dual_f64_sharded(scanrs_mat *m, const uint64_t *cols1, uint64_t n1, const uint64_t *cols2, uint64_t n2,
+                                         const scanrs_snoop *snoop, double *out1, double *out2);
+int scanrs_mat_mean_rows_sharded(scanrs_mat *m, const uint64_t *cols, uint64_t n, double *out);
+int scanrs_mat_mean_var_rows_sharded(scanrs_mat *m, const uint64_t *cols, uint64_t n, double *mean, double *var);
 
 /* BkSvd::run_pca_cancellable / svd_bk (dim_red/bk_svd.rs:41-146).
  * omega: optional explicit start panel in the reference's own layout
@@ -460,6 +501,21 @@ int scanrs_multi_sseq_de(scanrs_multi *mm, int transposed, const int16_t *labels
                          const double *gene_means, const double *gene_phi, const uint8_t *use_genes, uint64_t big_count, int backend,
                          const scanrs_snoop *snoop, uint64_t *sums_in, uint64_t *sums_out, double *p, double *p_adj, double *log2fc,
                          double *mean_in, double *mean_out);
+/* The statistics over a list of columns over the shards: scanrs_mat_sum_rows_u64_sharded ... scanrs_mat_mean_var_rows_sharded (see
+ * the column-list section) on every shard at once, with the handle replaced by `mm, transposed` (transposed != 0: every shard runs
+ * through scanrs_mat_t; rows and columns are then those of the transposed matrix). Either dimension may be the sharded one. Lists
+ * and outputs span the whole matrix; shard 0 writes the caller's arrays, the other shards write the same values into scratch of the
+ * call. Every shard polls the cancel flag of `snoop`, only shard 0 reports progress. */
+int scanrs_multi_sum_rows_u64(scanrs_multi *mm, int transposed, const uint64_t *cols, uint64_t n, uint64_t *out);
+int scanrs_multi_sum_rows_f64(scanrs_multi *mm, int transposed, const uint64_t *cols, uint64_t n, double *out);
+int scanrs_multi_sum_cols_u64(scanrs_multi *mm, int transposed, const uint64_t *cols, uint64_t n, uint64_t *out);
+int scanrs_multi_sum_cols_f64(scanrs_multi *mm, int transposed, const uint64_t *cols, uint64_t n, double *out);
+int scanrs_multi_sum_rows_dual_u64(scanrs_multi *mm, int transposed, const uint64_t *cols1, uint64_t n1, const uint64_t *cols2, uint64_t n2,
+                                   const scanrs_snoop *snoop, uint64_t *out1, uint64_t *out2);
+int scanrs_multi_sum_rows_dual_f64(scanrs_multi *mm, int transposed, const uint64_t *cols1, uint64_t n1, const uint64_t *cols2, uint64_t n2,
+                                   const scanrs_snoop *snoop, double *out1, double *out2);
+int scanrs_multi_mean_rows(scanrs_multi *mm, int transposed, const uint64_t *cols, uint64_t n, double *out);
+int scanrs_multi_mean_var_rows(scanrs_multi *mm, int transposed, const uint64_t *cols, uint64_t n, double *mean, double *var);
 /* The shape of the WHOLE matrix, its nonzeros over all shards and its storage flag. Any pointer may be NULL. */
 int scanrs_multi_shape(const scanrs_multi *mm, uint64_t *rows, uint64_t *cols, uint64_t *nnz, int *storage);
 /* scanrs_mat_to_csmat of the whole matrix, the shards concatenated: indptr (outer dimension + 1), indices and values (nnz each). */
@@ -606,7 +662,8 @@ int scanrs_mat_set_option(scanrs_mat *m, const char *key, double value);
  * scanrs_merge_clusters_sharded and scanrs_cluster_medoids_sharded included) on this handle: the
  * tests this rank launched on the device, and the exchange steps of a sharded handle (0 on an unsharded one). "subset_masked_passes" / "subset_scatter_passes" = sums over a column list made on
  * this handle so far: from the copy whose outer dimension is the result axis (masked walk or listed vectors, no atomics) / through the
- * integer scatter from the other copy ("subset_scatter"). */
+ * integer scatter from the other copy ("subset_scatter"); "subset_allreduces" = the exchange steps of the last
+ * scanrs_mat_sum_rows_u64_sharded or kin on this handle (0 on an unsharded one). */
 int scanrs_mat_get_counter(scanrs_mat *m, const char *key, uint64_t *value);
 /* Process-wide options of the entry points that take no handle:
  *   "h5_threads" (8)               threads that inflate the chunks of a large filtered HDF5 read
@@ -766,9 +823,10 @@ int scanrs_host_sym_eig_topk(const double *a, int n, int k, double *w, double *z
  * checkpoints and must see the same cancel flag; scanrs_multi_sseq_de lets only shard 0 report progress. Counters
  * (scanrs_mat_get_counter): "de_shard_tests" = the tests this rank launched on the device in the last DE call (an unsharded
  * handle: all of them), "de_shard_allreduces" = the exchange steps of the last params / group sums / DE call.
- * What stays refused on a sharded handle (SCANRS_ERR_ARGUMENT, "sharded" in scanrs_last_error()): scanrs_sseq_de_pairs,
- * scanrs_merge_clusters and the statistics over a column list (scanrs_mat_sum_rows and its kin). The first two are served through
- * collective entry points of their own, scanrs_sseq_de_pairs_sharded and scanrs_merge_clusters_sharded (declared beside them). */
+ * What stays refused on a sharded handle (SCANRS_ERR_ARGUMENT, "sharded" in scanrs_last_error()) are the PLAIN calls
+ * scanrs_sseq_de_pairs, scanrs_merge_clusters and the statistics over a column list (scanrs_mat_sum_rows_u64 and its kin). All of
+ * them are served through collective entry points of their own: scanrs_sseq_de_pairs_sharded, scanrs_merge_clusters_sharded and
+ * scanrs_mat_sum_rows_u64_sharded ... scanrs_mat_mean_var_rows_sharded (declared beside them). */
 
 /* `compute_sseq_params` (diff_exp.rs:458-500). cell_indices (n_sel entries, or NULL for every cell): only those cells get a
  * size factor, the rest 0. umi_counts (one per selected cell, or NULL): replaces the per-cell totals. Size factors are the

@@ -472,6 +472,43 @@ class AdaptiveMat:
         _check(_lib.scanrs_mat_mean_var_rows(self._h, _p(cols), ctypes.c_uint64(cols.shape[0]), _p(mean), _p(var)))
         return mean, var
 
+    # -- the same over a sharded handle: collective, global lists, complete outputs on every rank ----
+    def _rows_all(self) -> int:
+        """The view's rows over all shards (an unsharded handle: its own)."""
+        return self._global_shape()[0]
+
+    def sum_rows_sharded(self, cols, dtype=np.float64):
+        """`scanrs_mat_sum_rows_*_sharded`: `sum_rows` over a sharded handle; every rank calls it with the same (global) list."""
+        return self._sums_over(_lib.scanrs_mat_sum_rows_u64_sharded, _lib.scanrs_mat_sum_rows_f64_sharded, cols, dtype, lambda c: self._rows_all())
+
+    def sum_cols_sharded(self, cols, dtype=np.float64):
+        """`scanrs_mat_sum_cols_*_sharded` (see `sum_rows_sharded`)."""
+        return self._sums_over(_lib.scanrs_mat_sum_cols_u64_sharded, _lib.scanrs_mat_sum_cols_f64_sharded, cols, dtype, lambda c: c.shape[0])
+
+    def sum_rows_dual_sharded(self, cols1, cols2, dtype=np.float64, snoop=None):
+        """`scanrs_mat_sum_rows_dual_*_sharded` (see `sum_rows_sharded`)."""
+        dt, c1, c2 = self._sum_dtype(dtype), self._col_list(cols1), self._col_list(cols2)
+        is_f = dt == np.dtype(np.float64)
+        o1, o2 = (np.zeros(self._rows_all(), dtype=np.float64 if is_f else np.uint64) for _ in range(2))
+        sn, _keep = _snoop_arg(snoop)
+        fn = _lib.scanrs_mat_sum_rows_dual_f64_sharded if is_f else _lib.scanrs_mat_sum_rows_dual_u64_sharded
+        _check(fn(self._h, _p(c1), ctypes.c_uint64(c1.shape[0]), _p(c2), ctypes.c_uint64(c2.shape[0]), sn, _p(o1), _p(o2)))
+        return self._narrow(o1, dt), self._narrow(o2, dt)
+
+    def mean_rows_sharded(self, cols):
+        """`scanrs_mat_mean_rows_sharded` (see `sum_rows_sharded`)."""
+        cols = self._col_list(cols)
+        out = np.zeros(self._rows_all())
+        _check(_lib.scanrs_mat_mean_rows_sharded(self._h, _p(cols), ctypes.c_uint64(cols.shape[0]), _p(out)))
+        return out
+
+    def mean_var_rows_sharded(self, cols):
+        """`scanrs_mat_mean_var_rows_sharded` (see `sum_rows_sharded`)."""
+        cols = self._col_list(cols)
+        mean, var = np.zeros(self._rows_all()), np.zeros(self._rows_all())
+        _check(_lib.scanrs_mat_mean_var_rows_sharded(self._h, _p(cols), ctypes.c_uint64(cols.shape[0]), _p(mean), _p(var)))
+        return mean, var
+
     def to_dense(self):
         r, c = self.shape()
         out = np.zeros((r, c))
@@ -1168,6 +1205,91 @@ class MultiMat:
     def partition_on_threshold(self, threshold: float):
         return self.partition_on_thresholds(threshold, threshold)
 
+    # -- statistics over a list of columns (`scanrs_multi_sum_rows_u64` ... `scanrs_multi_mean_var_rows`): the dtypes and
+    # results of the AdaptiveMat methods; `transposed`: of the transposed matrix
+    def _view_rows(self, transposed: bool) -> int:
+        return self.shape()[1 if transposed else 0]
+
+    def _sums_over(self, fn_u64, fn_f64, cols, dtype, n_out, transposed):
+        dt, cols = AdaptiveMat._sum_dtype(dtype), AdaptiveMat._col_list(cols)
+        is_f = dt == np.dtype(np.float64)
+        out = np.zeros(n_out(cols), dtype=np.float64 if is_f else np.uint64)
+        _check((fn_f64 if is_f else fn_u64)(self._h, ctypes.c_int(int(transposed)), _p(cols), ctypes.c_uint64(cols.shape[0]), _p(out)))
+        return AdaptiveMat._narrow(out, dt)
+
+    def sum_rows(self, cols, dtype=np.float64, transposed: bool = False):
+        return self._sums_over(_lib.scanrs_multi_sum_rows_u64, _lib.scanrs_multi_sum_rows_f64, cols, dtype,
+                               lambda c: self._view_rows(transposed), transposed)
+
+    def sum_cols(self, cols, dtype=np.float64, transposed: bool = False):
+        return self._sums_over(_lib.scanrs_multi_sum_cols_u64, _lib.scanrs_multi_sum_cols_f64, cols, dtype, lambda c: c.shape[0], transposed)
+
+    def sum_rows_dual(self, cols1, cols2, dtype=np.float64, snoop=None, transposed: bool = False):
+        dt, c1, c2 = AdaptiveMat._sum_dtype(dtype), AdaptiveMat._col_list(cols1), AdaptiveMat._col_list(cols2)
+        is_f = dt == np.dtype(np.float64)
+        o1, o2 = (np.zeros(self._view_rows(transposed), dtype=np.float64 if is_f else np.uint64) for _ in range(2))
+        sn, _keep = _snoop_arg(snoop)
+        fn = _lib.scanrs_multi_sum_rows_dual_f64 if is_f else _lib.scanrs_multi_sum_rows_dual_u64
+        _check(fn(self._h, ctypes.c_int(int(transposed)), _p(c1), ctypes.c_uint64(c1.shape[0]), _p(c2), ctypes.c_uint64(c2.shape[0]), sn,
+                  _p(o1), _p(o2)))
+        return AdaptiveMat._narrow(o1, dt), AdaptiveMat._narrow(o2, dt)
+
+    def mean_rows(self, cols, transposed: bool = False):
+        cols = AdaptiveMat._col_list(cols)
+        out = np.zeros(self._view_rows(transposed))
+        _check(_lib.scanrs_multi_mean_rows(self._h, ctypes.c_int(int(transposed)), _p(cols), ctypes.c_uint64(cols.shape[0]), _p(out)))
+        return out
+
+    def mean_var_rows(self, cols, transposed: bool = False):
+        cols = AdaptiveMat._col_list(cols)
+        mean, var = np.zeros(self._view_rows(transposed)), np.zeros(self._view_rows(transposed))
+        _check(_lib.scanrs_multi_mean_var_rows(self._h, ctypes.c_int(int(transposed)), _p(cols), ctypes.c_uint64(cols.shape[0]), _p(mean),
+                                               _p(var)))
+        return mean, var
+
+    def compose_scale_axis(self, axis: int, factors):
+        """`compose_map(ScaleAxis::new(Axis(axis), factors))` on every shard (`scanrs_mat_compose_scale_axis`); `factors` spans the whole
+        matrix, every shard takes its slice along the sharded dimension."""
+        f = _f64(factors)
+        if axis not in (0, 1) or f.shape[0] != self.shape()[axis]:
+            raise ScanrsError(1, "Dimension mismatch")
+        sharded_axis = 0 if self.storage == CSR else 1
+        for i, (_dev, lo, hi) in enumerate(self.shard_ranges()):
+            h = ctypes.c_void_p()
+            _check(_lib.scanrs_multi_shard(self._h, ctypes.c_uint32(i), ctypes.byref(h), None, None, None))
+            part = np.ascontiguousarray(f[lo:hi]) if axis == sharded_axis else f
+            if part.shape[0] == 0:
+                part = np.zeros(1)  # (a shard without vectors: nothing is read)
+            _check(_lib.scanrs_mat_compose_scale_axis(h, ctypes.c_int(axis), _p(part)))
+        return self
+
+    def _with_shard(self, i: int, fn):
+        """fn(shard i as an AdaptiveMat); the handle stays the MultiMat's own."""
+        h = ctypes.c_void_p()
+        _check(_lib.scanrs_multi_shard(self._h, ctypes.c_uint32(i), ctypes.byref(h), None, None, None))
+        b = AdaptiveMat(h.value)
+        try:
+            return fn(b)
+        finally:
+            b._h = ctypes.c_void_p()  # borrowed: nothing is freed
+
+    def profile_enable(self, on: bool = True):
+        """`scanrs_profile_enable` / `scanrs_profile_reset` on every shard; `profile_get(shard)` reads one shard's kernel classes."""
+        for i in range(self.n_shards):
+            self._with_shard(i, lambda b: (b.profile_enable(on), b.profile_reset()))
+        return self
+
+    def profile_get(self, shard: int = 0) -> dict:
+        return self._with_shard(shard, lambda b: b.profile_get())
+
+    def reset_map(self):
+        """`scanrs_mat_reset_map` on every shard."""
+        for i in range(self.n_shards):
+            h = ctypes.c_void_p()
+            _check(_lib.scanrs_multi_shard(self._h, ctypes.c_uint32(i), ctypes.byref(h), None, None, None))
+            _check(_lib.scanrs_mat_reset_map(h))
+        return self
+
     def shard_ranges(self):
         out = []
         for i in range(self.n_shards):
@@ -1383,6 +1505,10 @@ EXPORTED_SYMBOLS = [
     "scanrs_host_choose_storage",
     "scanrs_mat_sum_rows_u64", "scanrs_mat_sum_rows_f64", "scanrs_mat_sum_cols_u64", "scanrs_mat_sum_cols_f64", "scanrs_mat_sum_rows_dual_u64",
     "scanrs_mat_sum_rows_dual_f64", "scanrs_mat_mean_rows", "scanrs_mat_mean_var_rows", "scanrs_mat_var_axis",
+    "scanrs_mat_sum_rows_u64_sharded", "scanrs_mat_sum_rows_f64_sharded", "scanrs_mat_sum_cols_u64_sharded", "scanrs_mat_sum_cols_f64_sharded",
+    "scanrs_mat_sum_rows_dual_u64_sharded", "scanrs_mat_sum_rows_dual_f64_sharded", "scanrs_mat_mean_rows_sharded", "scanrs_mat_mean_var_rows_sharded",
+    "scanrs_multi_sum_rows_u64", "scanrs_multi_sum_rows_f64", "scanrs_multi_sum_cols_u64", "scanrs_multi_sum_cols_f64",
+    "scanrs_multi_sum_rows_dual_u64", "scanrs_multi_sum_rows_dual_f64", "scanrs_multi_mean_rows", "scanrs_multi_mean_var_rows",
 ]
 
 # sSeq differential expression (sseq.py)

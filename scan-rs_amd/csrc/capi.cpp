@@ -1431,6 +1431,8 @@ int scanrs_mat_get_counter(scanrs_mat *m, const char *key, uint64_t *value) {
             *value = m->st->subset_masked_passes;
         else if (k == "subset_scatter_passes") // ... and through the integer scatter from the other copy
             *value = m->st->subset_scatter_passes;
+        else if (k == "subset_allreduces") // the exchange steps of the last sharded sum over a column list (an unsharded handle: 0)
+            *value = m->st->subset_allreduces;
         else if (k == "t_layout_us") // first-call accounting: host time of the calling thread in tile layout builds ...
             *value = m->st->t_layout_us;
         else if (k == "t_side_wait_us") // ... waiting for the helper thread that builds the second orientation

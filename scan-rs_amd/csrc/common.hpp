@@ -405,6 +405,7 @@ struct Storage {
     uint64_t de_pairs_passes = 0, de_pairs_literal = 0; // the last scanrs_sseq_de_pairs on this handle: passes over the nonzeros, pairs on the literal route (scanrs_mat_get_counter)
     int subset_scatter = 1;               // integer sums over a column list when only the other orientation exists: 1 = scattered into the result with 64-bit integer atomics from the copy that exists, 0 = the missing copy is built (subset_host.cpp)
     uint64_t subset_masked_passes = 0, subset_scatter_passes = 0; // sums over a column list made so far on this handle: from the copy whose outer dimension is the result axis / through the integer scatter (scanrs_mat_get_counter)
+    uint64_t subset_allreduces = 0;       // exchange steps of the last scanrs_mat_sum_rows_*_sharded (and kin) on this handle (an unsharded one: 0)
     int merge_fused = 1;                  // merge_clusters: 1 = one grouped pass per call, candidates from its sums; 0 = params + pairwise DE per candidate (the reference's calls)
     size_t l2_tile_bytes = 3584u << 10;   // panel slice per step of the L2-blocked gather (4 MB L2 per XCD): whole 1024-row base tiles up to 3.5 MB — 4 tiles (3.2 MB) at 100 columns, 3 (2.9 MB) at 122; measured 40.55 / 39.71 ms per pass against 41.30 / 40.23 with 3 tiles and 40.86 / 39.61 with 5, and 4 tiles of 122 columns (3.9 MB) lose 1.8 ms
     int spmm_order = 1;                   // L2-blocked gather: launch outer vectors longest first: 0 never, 1 auto, 2 always (SCANRS_SPMM_ORDER)
@@ -859,5 +860,21 @@ void launch_subset_inner_scatter(Storage &st, const SparseCopy &cp, const uint32
 // the listed outer vectors of cp: d_out[i] = sum of vector d_list[i] (mode 0 or 1) / d_out[inner] += count (d_out zeroed by the caller)
 void launch_subset_listed(Storage &st, const SparseCopy &cp, const DevMap &map, int mode, const uint32_t *d_list, uint64_t n, void *d_out);
 void launch_subset_listed_scatter(Storage &st, const SparseCopy &cp, const uint32_t *d_list, uint64_t n, unsigned long long *d_out);
+// The fixed-point forms of the two f64 walks, for sums that cross the shards: every term is rounded once to the quantum
+// 1 / scale (fixed128.hpp, signed) and summed in 128-bit integers. d_fx: 4 u64 per result (lo, hi of the first sum, lo, hi of the
+// second: list 2 of a dual call under scale1, or the sum of squares of mode 2 under scale2), d_bad: one flag per result (a term was not
+// finite, or did not fit the quantum). d_slab: 5 u64 per slab row of cp. Both arrays are written for every result.
+void launch_subset_reduce_fx(Storage &st, const SparseCopy &cp, const DevMap &map, int mode, int n_sets, const uint8_t *d_code, double scale1,
+                             double scale2, unsigned long long *d_fx, uint32_t *d_bad, unsigned long long *d_slab);
+void launch_subset_listed_fx(Storage &st, const SparseCopy &cp, const DevMap &map, const uint32_t *d_list, uint64_t n, double scale1,
+                             unsigned long long *d_fx, uint32_t *d_bad);
+// the pre-pass of the quantum: *d_max (zeroed by the caller) = the bit pattern of the largest finite |mapped value| over the listed
+// nonzeros: the masked walk (positions with a nonzero byte in d_code) or the listed vectors
+void launch_subset_reduce_max(Storage &st, const SparseCopy &cp, const DevMap &map, const uint8_t *d_code, unsigned long long *d_max);
+void launch_subset_listed_max(Storage &st, const SparseCopy &cp, const DevMap &map, const uint32_t *d_list, uint64_t n, unsigned long long *d_max);
+// n_sums (1 or 2) 128-bit sums and the flag of every result as 32-bit limbs held in u64 (n x (4 n_sums + 1)) around the u64 all-reduce,
+// and back (the kin of launch_sseq_mom_split / _join)
+void launch_subset_fx_split(Storage &st, const unsigned long long *d_fx, const uint32_t *d_bad, uint64_t n, int n_sums, unsigned long long *d_limbs);
+void launch_subset_fx_join(Storage &st, const unsigned long long *d_limbs, uint64_t n, int n_sums, unsigned long long *d_fx, uint32_t *d_bad);
 
 } // namespace scanrs

@@ -36,6 +36,23 @@ inline double fixed_scale(double bound) {
 SCANRS_FX_HD inline double from_fixed(const unsigned long long *w, double scale) {
     return ((double)w[1] * 18446744073709551616.0 + (double)w[0]) / scale;
 }
+// The signed form (subset.hip: the mapped values of the residual maps and of negative scale factors): the magnitude is rounded as
+// to_fixed rounds it (rint is symmetric about zero) and a negative term is held as its two's complement, so that sums of mixed signs
+// stay plain 128-bit additions (add128, shfl_down128, the limbs of an all-reduce). A sum below 2^127 in magnitude comes back with
+// its sign.
+SCANRS_FX_HD inline U128 to_fixed_signed(double t, double scale) {
+    U128 v = to_fixed(fabs(t), scale);
+    if (t < 0.0) {
+        v.lo = ~v.lo + 1ull;
+        v.hi = ~v.hi + (v.lo == 0ull ? 1ull : 0ull);
+    }
+    return v;
+}
+SCANRS_FX_HD inline double from_fixed_signed(const unsigned long long *w, double scale) {
+    if (!(w[1] >> 63)) return from_fixed(w, scale);
+    const unsigned long long n[2] = {~w[0] + 1ull, ~w[1] + (w[0] == 0ull ? 1ull : 0ull)};
+    return -from_fixed(n, scale);
+}
 
 #if defined(__HIPCC__) || defined(__CUDACC__)
 // p[0] = lo, p[1] = hi, in global memory or LDS; the carry of each addition is added by the lane that made it

@@ -503,6 +503,73 @@ int multi_select(scanrs_multi *mm, bool rows_axis, const uint64_t *idx, uint64_t
 
 } // namespace
 
+// ---- the statistics over a list of columns over the shards ----------------------------------------------------------------
+// The collective calls of the handle (scanrs_mat_sum_rows_u64_sharded and kin) on every shard at once: global lists, complete outputs
+// on every shard; shard 0 writes the caller's arrays, the others write into scratch of the call.
+namespace {
+
+// f(handle, out_a, out_b, snoop) on every shard; n_res: the entries (8 bytes each) of an output
+extern "C++" template <typename F>
+int multi_subset(scanrs_multi *mm, int transposed, void *out_a, void *out_b, bool two, uint64_t n_res, const scanrs_snoop *snoop, F &&f) {
+    if (!mm) return bad_argument("null handle");
+    if (n_res && (!out_a || (two && !out_b))) return bad_argument("null argument");
+    return fan_out(mm, [&](size_t i) {
+        ShardView v;
+        if (const int rc = v.open(mm, i, transposed)) return rc;
+        scanrs_snoop sn;
+        const scanrs_snoop *psn = shard_snoop(snoop, i, sn);
+        if (i == 0) return (int)f(v.h, out_a, out_b, psn);
+        std::vector<uint64_t> spare(2 * (n_res + 1));
+        return (int)f(v.h, static_cast<void *>(&spare[0]), static_cast<void *>(&spare[n_res + 1]), psn);
+    });
+}
+uint64_t view_rows(const scanrs_multi *mm, int transposed) { return !mm ? 0 : transposed ? mm->cols : mm->rows; }
+
+} // namespace
+
+int scanrs_multi_sum_rows_u64(scanrs_multi *mm, int transposed, const uint64_t *cols, uint64_t n, uint64_t *out) {
+    return multi_subset(mm, transposed, out, nullptr, false, view_rows(mm, transposed), nullptr, [&](scanrs_mat *h, void *a, void *, const scanrs_snoop *) {
+        return scanrs_mat_sum_rows_u64_sharded(h, cols, n, static_cast<uint64_t *>(a));
+    });
+}
+int scanrs_multi_sum_rows_f64(scanrs_multi *mm, int transposed, const uint64_t *cols, uint64_t n, double *out) {
+    return multi_subset(mm, transposed, out, nullptr, false, view_rows(mm, transposed), nullptr, [&](scanrs_mat *h, void *a, void *, const scanrs_snoop *) {
+        return scanrs_mat_sum_rows_f64_sharded(h, cols, n, static_cast<double *>(a));
+    });
+}
+int scanrs_multi_sum_cols_u64(scanrs_multi *mm, int transposed, const uint64_t *cols, uint64_t n, uint64_t *out) {
+    return multi_subset(mm, transposed, out, nullptr, false, n, nullptr, [&](scanrs_mat *h, void *a, void *, const scanrs_snoop *) {
+        return scanrs_mat_sum_cols_u64_sharded(h, cols, n, static_cast<uint64_t *>(a));
+    });
+}
+int scanrs_multi_sum_cols_f64(scanrs_multi *mm, int transposed, const uint64_t *cols, uint64_t n, double *out) {
+    return multi_subset(mm, transposed, out, nullptr, false, n, nullptr, [&](scanrs_mat *h, void *a, void *, const scanrs_snoop *) {
+        return scanrs_mat_sum_cols_f64_sharded(h, cols, n, static_cast<double *>(a));
+    });
+}
+int scanrs_multi_sum_rows_dual_u64(scanrs_multi *mm, int transposed, const uint64_t *cols1, uint64_t n1, const uint64_t *cols2, uint64_t n2,
+                                   const scanrs_snoop *snoop, uint64_t *out1, uint64_t *out2) {
+    return multi_subset(mm, transposed, out1, out2, true, view_rows(mm, transposed), snoop, [&](scanrs_mat *h, void *a, void *b, const scanrs_snoop *sn) {
+        return scanrs_mat_sum_rows_dual_u64_sharded(h, cols1, n1, cols2, n2, sn, static_cast<uint64_t *>(a), static_cast<uint64_t *>(b));
+    });
+}
+int scanrs_multi_sum_rows_dual_f64(scanrs_multi *mm, int transposed, const uint64_t *cols1, uint64_t n1, const uint64_t *cols2, uint64_t n2,
+                                   const scanrs_snoop *snoop, double *out1, double *out2) {
+    return multi_subset(mm, transposed, out1, out2, true, view_rows(mm, transposed), snoop, [&](scanrs_mat *h, void *a, void *b, const scanrs_snoop *sn) {
+        return scanrs_mat_sum_rows_dual_f64_sharded(h, cols1, n1, cols2, n2, sn, static_cast<double *>(a), static_cast<double *>(b));
+    });
+}
+int scanrs_multi_mean_rows(scanrs_multi *mm, int transposed, const uint64_t *cols, uint64_t n, double *out) {
+    return multi_subset(mm, transposed, out, nullptr, false, view_rows(mm, transposed), nullptr, [&](scanrs_mat *h, void *a, void *, const scanrs_snoop *) {
+        return scanrs_mat_mean_rows_sharded(h, cols, n, static_cast<double *>(a));
+    });
+}
+int scanrs_multi_mean_var_rows(scanrs_multi *mm, int transposed, const uint64_t *cols, uint64_t n, double *mean, double *var) {
+    return multi_subset(mm, transposed, mean, var, true, view_rows(mm, transposed), nullptr, [&](scanrs_mat *h, void *a, void *b, const scanrs_snoop *) {
+        return scanrs_mat_mean_var_rows_sharded(h, cols, n, static_cast<double *>(a), static_cast<double *>(b));
+    });
+}
+
 int scanrs_multi_shape(const scanrs_multi *mm, uint64_t *rows, uint64_t *cols, uint64_t *nnz, int *storage) {
     if (!mm) return bad_argument("null handle");
     if (rows) *rows = mm->rows;
