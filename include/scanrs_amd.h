@@ -671,6 +671,8 @@ int scanrs_mat_get_counter(scanrs_mat *m, const char *key, uint64_t *value);
  *   "knn_exhaustive" (0)           1: never use the bf16-MFMA filter of scanrs_knn*
  *   "knn_filter_min_points" (32768), "knn_ratio" (4), "knn_stats" (0)   tuning / statistics of that filter (the figures
  *                                  "knn_stats" prints are also returned by scanrs_debug_knn_last_stats)
+ *   "knn_block_rows" (262144)      rows of the point set that scanrs_knn_sharded exchanges and searches at a time (at most
+ *                                  256 MiB of exchange buffer at d = 128; the result does not depend on it)
  *   "sync_timeout_s" (120)         BOUNDED WAITS: no call of this library blocks on the device without a deadline. Every wait for
  *                                  a stream or an event (and every barrier between the shard threads of scanrs_multi_*) is a poll
  *                                  with this deadline in seconds; when it passes, the call returns SCANRS_ERR_DEVICE and
@@ -1019,6 +1021,37 @@ int scanrs_multi_merge_clusters(scanrs_multi *mm, int transposed, const double *
                                 int16_t *labels_out, const scanrs_snoop *snoop, scanrs_merge_trace *trace);
 int scanrs_multi_cluster_medoids(scanrs_multi *mm, int transposed, const double *pca, uint32_t ld, uint32_t d, const int16_t *labels,
                                  uint32_t k, double *centers);
+
+/* ---- knn over sharded and multi-GPU score matrices ----------------------------------------------------------------
+ * knn(v, k) / find_nn (nn.rs:38-83) where the scores stay sharded: every rank owns the queries of its own cells, the point set
+ * passes by in global blocks of "knn_block_rows" rows (each block reaches every rank through ONE u64 all-reduce of the rows' bit
+ * patterns into a zeroed buffer; only dtype 1 crosses the shards), every block is searched with the kernels of scanrs_knn (the
+ * filter where its conditions hold for the rank's queries and the block, seeded with what the query already holds) and merged into
+ * the query's running list by (squared distance, global index). The answer is the k smallest pairs under that total order with the
+ * same fma chain as scanrs_knn, so it EQUALS scanrs_knn of the whole point set bit for bit, whatever the cut; the self exclusion
+ * compares global rows.
+ * scanrs_knn_sharded (nn.rs:38-83): COLLECTIVE, every rank calls it with the same d and k. The handle carries the transport and the
+ * rank's range of cells only (the columns of the view must be the sharded dimension). points: a host array over all outer_global
+ * cells (leading dimension ld; each rank uploads its own rows), or with points_is_device != 0 the rank's own rows in device memory,
+ * e.g. *d_v / *ld_v of scanrs_pca_result_device. out: host, n_local x k GLOBAL indices, nearest first, padded with UINT32_MAX when
+ * fewer than k other points exist globally; sq_dist (may be null): n_local x k squared distances, +inf in padded slots. Limits of
+ * scanrs_knn: k <= 128, d <= 128, n <= 2^32 - 2. A coordinate that is not finite is refused with SCANRS_ERR_ARGUMENT on every rank,
+ * naming the first such global row (with a NaN the order is not total); ranks that disagree on n, d or k get SCANRS_ERR_ARGUMENT
+ * from the first exchange, which carries four integers per rank. On an unsharded handle the call is scanrs_knn / scanrs_knn_device
+ * on the given points. Counters (scanrs_mat_get_counter), reset by every call, 0 from an unsharded handle: "knn_blocks" = the blocks
+ * searched, "knn_allreduces" = the exchange steps (blocks + 1). scanrs_debug_knn_last_stats describes the last block searched.
+ * scanrs_multi_knn (nn.rs:38-83) runs the collective call on every shard of a scanrs_multi from one process; out / sq_dist cover all
+ * cells in global order. points: a host array over all cells, or NULL: every shard searches the factor along the sharded dimension
+ * that its last scanrs_multi_pca_bk / _rand left on its device (V of a genes x cells CSC matrix; ld and d are ignored, d is that
+ * call's k). SCANRS_ERR_ARGUMENT when no PCA has run, or where that factor is not kept per shard (it then has other than the
+ * shard's own rows on the device: pass the scores as a host array).
+ * scanrs_host_knn_merge (nn.rs:38-83; host only): the merge rule itself. Two lists of k (squared distance, index) entries, ascending by
+ * (distance, index), padded with (+inf, UINT32_MAX), sharing no index, give the first k of their union in the same form. k <= 128. */
+int scanrs_knn_sharded(scanrs_mat *m, const double *points, int points_is_device, uint32_t ld, uint32_t d, uint32_t k, uint32_t *out,
+                       double *sq_dist);
+int scanrs_multi_knn(scanrs_multi *mm, const double *points, uint32_t ld, uint32_t d, uint32_t k, uint32_t *out, double *sq_dist);
+int scanrs_host_knn_merge(uint32_t k, const double *da, const uint32_t *ia, const double *db, const uint32_t *ib, double *dout,
+                          uint32_t *iout);
 
 /* ---- 10x HDF5 ingestion (hdf5-io/src/matrix.rs, analysis.rs). Host-side; no device needed.
  * The files are parsed by the library's own reader (csrc/h5lite.cpp) — no libhdf5 dependency. Failures are

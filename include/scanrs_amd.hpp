@@ -1024,6 +1024,33 @@ inline std::vector<double> cluster_medoids(const MultiMat &m, bool transposed, c
 }
 } // namespace cluster
 
+// nn::knn (nn.rs:38-83) where the scores stay sharded: global indices, equal to `knn` of the whole point set bit for bit
+struct KnnResult {
+    std::vector<uint32_t> indices; // rows x k, nearest first, UINT32_MAX padded
+    std::vector<double> sq_dist;   // rows x k when asked for, +inf in padded slots
+};
+// COLLECTIVE on one sharded handle: points is a host array over all cells, or the rank's own n_local rows in device memory
+inline KnnResult knn_sharded(const AdaptiveMat &m, uint64_t n_local, const double *points, bool points_is_device, uint32_t ld, uint32_t d, size_t k,
+                             bool with_sq_dist = false) {
+    KnnResult r;
+    r.indices.assign((size_t)n_local * k, 0u);
+    if (with_sq_dist) r.sq_dist.assign((size_t)n_local * k, 0.0);
+    check(scanrs_knn_sharded(m.raw(), points, points_is_device ? 1 : 0, ld, d, (uint32_t)k, r.indices.data(), with_sq_dist ? r.sq_dist.data() : nullptr));
+    return r;
+}
+// over the shards of a MultiMat from one process; points == nullptr: the scores its last run_pca left on the devices
+inline KnnResult knn(const MultiMat &m, uint64_t cells, const double *points, uint32_t ld, uint32_t d, size_t k, bool with_sq_dist = false) {
+    KnnResult r;
+    r.indices.assign((size_t)cells * k, 0u);
+    if (with_sq_dist) r.sq_dist.assign((size_t)cells * k, 0.0);
+    check(scanrs_multi_knn(m.raw(), points, ld, d, (uint32_t)k, r.indices.data(), with_sq_dist ? r.sq_dist.data() : nullptr));
+    return r;
+}
+// the merge rule of that search on the host: two sorted, padded lists of k entries that share no index -> the first k of their union
+inline void host_knn_merge(uint32_t k, const double *da, const uint32_t *ia, const double *db, const uint32_t *ib, double *dout, uint32_t *iout) {
+    check(scanrs_host_knn_merge(k, da, ia, db, ib, dout, iout));
+}
+
 namespace mtx {
 // scan_rs::mtx::load_mtx (scan-rs/src/mtx.rs:10-51): the CSR arrays; `.to_device()` is the AdaptiveMat the reference returns
 inline hdf5_io::FeatureBarcodeMatrix read_mtx(const std::string &path) {

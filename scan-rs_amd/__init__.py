@@ -752,6 +752,33 @@ class AdaptiveMat:
         self._outer_global = int(outer_global)
         return self
 
+    def knn_sharded(self, points, k: int, device: bool = False, return_sq_dist: bool = False):
+        """`nn::knn` over a sharded point set (`scanrs_knn_sharded`, nn.rs:38-83; DESIGN.md §7l): COLLECTIVE, every rank calls it with
+        the same k. The handle gives the transport and the rank's range of cells (its columns). points: a host array over ALL cells, or
+        with device=True the rank's own rows in device memory: a PcaResultDevice (its d_v / ld_v / k) or a tuple (address, ld, d).
+        Returns the (n_local x k) u32 GLOBAL indices of the rank's cells, nearest first, UINT32_MAX padded - what `knn` of the whole
+        point set returns for those rows, bit for bit - and with return_sq_dist also the squared distances (+inf in padded slots).
+        On an unsharded handle it is `knn` / `knn_device` of the given points."""
+        n_local = int(self.shape()[1])
+        keep = None
+        if device:
+            if isinstance(points, PcaResultDevice):
+                ptr, ld, d = points.d_v, int(points.ld_v), int(points.k)
+            else:
+                ptr, ld, d = points
+            ptr = ctypes.c_void_p(int(ptr) if ptr else None)
+        elif points is None:
+            ptr, ld, d = None, 0, 0
+        else:
+            keep = _f64(np.atleast_2d(points))
+            ptr, ld, d = _p(keep), int(keep.shape[1]), int(keep.shape[1])
+        out = np.zeros((n_local, k), dtype=np.uint32)
+        sq = np.zeros((n_local, k)) if return_sq_dist else None
+        _check(_lib.scanrs_knn_sharded(self._h, ptr, ctypes.c_int(1 if device else 0), ctypes.c_uint32(ld), ctypes.c_uint32(d),
+                                       ctypes.c_uint32(k), _p(out), _p(sq)))
+        del keep
+        return (out, sq) if return_sq_dist else out
+
     def profile_enable(self, on: bool = True):
         _check(_lib.scanrs_profile_enable(self._h, ctypes.c_int(int(on))))
 
@@ -1324,6 +1351,21 @@ class MultiMat:
                                                ctypes.c_int(log_fn), _p(sf)))
         return self
 
+    def knn(self, k: int, points=None, return_sq_dist: bool = False):
+        """`nn::knn` over the shards (`scanrs_multi_knn`, nn.rs:38-83; DESIGN.md §7l): (cells x k) u32 global indices, nearest first,
+        equal to `knn` of the whole point set bit for bit; the cells are the sharded dimension. points: a host array over all cells,
+        or None: every shard searches the scores its last run_pca_bk / run_pca_rand left on its device (V of a genes x cells CSC
+        matrix). With return_sq_dist also the squared distances."""
+        cells = self.cols if self.storage == CSC else self.rows
+        pts = None if points is None else _f64(np.atleast_2d(points))
+        d = 0 if pts is None else int(pts.shape[1])
+        if pts is not None and pts.shape[0] != cells:
+            raise ScanrsError(6, f"the points have {pts.shape[0]} rows for {cells} cells")
+        out = np.zeros((cells, k), dtype=np.uint32)
+        sq = np.zeros((cells, k)) if return_sq_dist else None
+        _check(_lib.scanrs_multi_knn(self._h, _p(pts), ctypes.c_uint32(d), ctypes.c_uint32(d), ctypes.c_uint32(k), _p(out), _p(sq)))
+        return (out, sq) if return_sq_dist else out
+
     def comm_info(self, shard: int = 0) -> dict:
         """`scanrs_comm_info` of shard `shard`'s communicator: the sum all-reduces that went through it so far."""
         n, r = ctypes.c_uint32(), ctypes.c_uint32()
@@ -1390,6 +1432,21 @@ def pca_result_device(matrix: "AdaptiveMat") -> PcaResultDevice:
                                          ctypes.byref(k)))
     r, c = matrix.shape()
     return PcaResultDevice(d_u.value, ld_u.value, d_v.value, ld_v.value, k.value, r, c)
+
+
+def host_knn_merge(da, ia, db, ib):
+    """The merge rule of the sharded kNN on the host (`scanrs_host_knn_merge`; scan-rs_amd/csrc/knn_merge.hpp): two lists of k
+    (squared distance, index) entries, each ascending by (distance, index) and padded with (+inf, UINT32_MAX), sharing no index ->
+    the first k of their union in the same form, as (distances f64, indices u32)."""
+    da, db = _f64(np.asarray(da).reshape(-1)), _f64(np.asarray(db).reshape(-1))
+    ia = np.ascontiguousarray(np.asarray(ia).reshape(-1), dtype=np.uint32)
+    ib = np.ascontiguousarray(np.asarray(ib).reshape(-1), dtype=np.uint32)
+    k = int(da.shape[0])
+    if not (ia.shape[0] == k and db.shape[0] == k and ib.shape[0] == k):
+        raise ScanrsError(6, "the four lists must have the same length k")
+    dout, iout = np.zeros(k), np.zeros(k, dtype=np.uint32)
+    _check(_lib.scanrs_host_knn_merge(ctypes.c_uint32(k), _p(da), _p(ia), _p(db), _p(ib), _p(dout), _p(iout)))
+    return dout, iout
 
 
 def knn_device(d_points: int, n: int, ld: int, d: int, k: int):
@@ -1483,7 +1540,7 @@ EXPORTED_SYMBOLS = [
     "scanrs_mat_sum_axis_f64", "scanrs_mat_mean_axis", "scanrs_mat_mean_var_axis", "scanrs_mat_to_dense",
     "scanrs_mat_dot", "scanrs_mat_rdot", "scanrs_mat_dot_u32", "scanrs_mat_rdot_u32", "scanrs_mat_dot_device",
     "scanrs_normalize", "scanrs_log_normalize", "scanrs_log1p_normalize_fixed_point", "scanrs_mat_target_umi",
-    "scanrs_pca_bk", "scanrs_pca_rand", "scanrs_pca_irlba", "scanrs_pca_result_device", "scanrs_knn_device", "scanrs_omega_fill", "scanrs_mat_set_shard", "scanrs_mat_set_shard_comm", "scanrs_comm_get_unique_id", "scanrs_comm_create", "scanrs_comm_free",
+    "scanrs_pca_bk", "scanrs_pca_rand", "scanrs_pca_irlba", "scanrs_pca_result_device", "scanrs_knn_device", "scanrs_knn_sharded", "scanrs_multi_knn", "scanrs_host_knn_merge", "scanrs_omega_fill", "scanrs_mat_set_shard", "scanrs_mat_set_shard_comm", "scanrs_comm_get_unique_id", "scanrs_comm_create", "scanrs_comm_free",
     "scanrs_multi_create", "scanrs_multi_free", "scanrs_multi_n_shards", "scanrs_multi_shard", "scanrs_multi_normalize", "scanrs_multi_pca_bk", "scanrs_multi_pca_rand", "scanrs_multi_pca_irlba", "scanrs_multi_log_normalize", "scanrs_multi_sseq_params", "scanrs_multi_group_sums", "scanrs_multi_sseq_de", "scanrs_multi_comm_info",
     "scanrs_sseq_de_pairs_sharded", "scanrs_merge_clusters_sharded", "scanrs_cluster_medoids_sharded", "scanrs_multi_sseq_de_pairs", "scanrs_multi_merge_clusters", "scanrs_multi_cluster_medoids",
     "scanrs_plan_shards", "scanrs_profile_enable", "scanrs_profile_reset", "scanrs_profile_get", "scanrs_mat_sync", "scanrs_mat_set_spmm_path", "scanrs_mat_set_option", "scanrs_set_global_option", "scanrs_mat_set_panel_precision",

@@ -1115,6 +1115,53 @@ int scanrs_find_nn(const double *queries, uint64_t n_q, const double *points, ui
         knn_host(queries, n_q, points, n_p, d, k, include_self == 0, out);
     });
 }
+// knn over a sharded handle: COLLECTIVE. The handle carries the transport and the rank's range of cells only.
+int scanrs_knn_sharded(scanrs_mat *m, const double *points, int points_is_device, uint32_t ld, uint32_t d, uint32_t k, uint32_t *out,
+                       double *sq_dist) {
+    return guard([&] {
+        if (!m) fail(SCANRS_ERR_ARGUMENT, "null handle");
+        CurrentHandle cur(m->st.get());
+        Storage &st = *m->st;
+        st.knn_blocks = st.knn_allreduces = 0;
+        const uint64_t n_local = m->cols();
+        if (!st.shard.active()) { // scanrs_knn / scanrs_knn_device on the given points
+            if ((!points && n_local) || (!out && n_local && k)) fail(SCANRS_ERR_ARGUMENT, "null argument");
+            need_device();
+            if (points_is_device || !n_local) {
+                knn_device(points, ld, n_local, points, ld, n_local, d, k, true, out, sq_dist);
+            } else {
+                if (ld < d) fail(SCANRS_ERR_ARGUMENT, "knn: leading dimension smaller than the number of coordinates");
+                DevBuf<double> dp(n_local * ld);
+                SCANRS_HIP(hipMemcpy(dp.p, points, n_local * ld * 8, hipMemcpyHostToDevice));
+                knn_device(dp.p, ld, n_local, dp.p, ld, n_local, d, k, true, out, sq_dist);
+            }
+            return;
+        }
+        if (!cols_sharded(m)) fail(SCANRS_ERR_ARGUMENT, "knn_sharded: the cells (the columns of this view) must be the sharded dimension");
+        const uint64_t begin = st.shard.outer_begin, n = st.shard.outer_global;
+        if ((!points && (points_is_device ? n_local : n)) || (!out && n_local && k)) fail(SCANRS_ERR_ARGUMENT, "null argument");
+        // host points span all the cells and only this rank's rows go to the device; device points are the rank's own rows already
+        DevBuf<double> d_pts;
+        const double *pts = points;
+        if (!points_is_device) {
+            d_pts.alloc(std::max<uint64_t>(1, n_local * ld));
+            if (n_local && ld >= d) {
+                SCANRS_HIP(hipMemcpyAsync(d_pts.p, points + begin * ld, ((n_local - 1) * ld + d) * 8, hipMemcpyHostToDevice, st.stream));
+                SCANRS_SYNC(st.stream); // the caller's array may be pageable
+            }
+            pts = d_pts.p;
+        }
+        knn_sharded(st, pts, ld, begin, n_local, n, d, k, out, sq_dist);
+        device_free_flush();
+    });
+}
+int scanrs_host_knn_merge(uint32_t k, const double *da, const uint32_t *ia, const double *db, const uint32_t *ib, double *dout, uint32_t *iout) {
+    return guard([&] {
+        if (k && (!da || !ia || !db || !ib || !dout || !iout)) fail(SCANRS_ERR_ARGUMENT, "null argument");
+        if (k > 128) fail(SCANRS_ERR_ARGUMENT, "knn: k must not exceed 128");
+        knn_host_merge(k, da, ia, db, ib, dout, iout);
+    });
+}
 int scanrs_debug_knn_filter(const double *queries, uint64_t n_q, const double *points, uint64_t n_p, uint32_t d, const double *tau,
                             uint64_t stride, uint32_t *cnt, uint32_t *cand) {
     return guard([&] {
@@ -1287,6 +1334,8 @@ int scanrs_set_global_option(const char *key, double value) {
             go.knn_filter_min_points = (unsigned long long)std::max(0.0, value);
         else if (k == "knn_ratio")
             go.knn_ratio = (unsigned long long)std::max(2.0, value);
+        else if (k == "knn_block_rows")
+            go.knn_block_rows = (unsigned long long)std::max(1.0, value);
         else if (k == "knn_stats")
             go.knn_stats = value != 0.0;
         else if (k == "device_cache_fraction") { // share of the device's memory that released blocks may occupy while they wait for reuse
@@ -1431,6 +1480,10 @@ int scanrs_mat_get_counter(scanrs_mat *m, const char *key, uint64_t *value) {
             *value = m->st->subset_masked_passes;
         else if (k == "subset_scatter_passes") // ... and through the integer scatter from the other copy
             *value = m->st->subset_scatter_passes;
+        else if (k == "knn_blocks") // the last scanrs_knn_sharded on this handle: the blocks of the point set it searched ...
+            *value = m->st->knn_blocks;
+        else if (k == "knn_allreduces") // ... and its exchange steps (an unsharded handle: 0)
+            *value = m->st->knn_allreduces;
         else if (k == "subset_allreduces") // the exchange steps of the last sharded sum over a column list (an unsharded handle: 0)
             *value = m->st->subset_allreduces;
         else if (k == "t_layout_us") // first-call accounting: host time of the calling thread in tile layout builds ...

@@ -405,6 +405,7 @@ struct Storage {
     uint64_t de_pairs_passes = 0, de_pairs_literal = 0; // the last scanrs_sseq_de_pairs on this handle: passes over the nonzeros, pairs on the literal route (scanrs_mat_get_counter)
     int subset_scatter = 1;               // integer sums over a column list when only the other orientation exists: 1 = scattered into the result with 64-bit integer atomics from the copy that exists, 0 = the missing copy is built (subset_host.cpp)
     uint64_t subset_masked_passes = 0, subset_scatter_passes = 0; // sums over a column list made so far on this handle: from the copy whose outer dimension is the result axis / through the integer scatter (scanrs_mat_get_counter)
+    uint64_t knn_blocks = 0, knn_allreduces = 0; // the last scanrs_knn_sharded on this handle: blocks of the point set searched, exchange steps (an unsharded one: 0)
     uint64_t subset_allreduces = 0;       // exchange steps of the last scanrs_mat_sum_rows_*_sharded (and kin) on this handle (an unsharded one: 0)
     int merge_fused = 1;                  // merge_clusters: 1 = one grouped pass per call, candidates from its sums; 0 = params + pairwise DE per candidate (the reference's calls)
     size_t l2_tile_bytes = 3584u << 10;   // panel slice per step of the L2-blocked gather (4 MB L2 per XCD): whole 1024-row base tiles up to 3.5 MB — 4 tiles (3.2 MB) at 100 columns, 3 (2.9 MB) at 122; measured 40.55 / 39.71 ms per pass against 41.30 / 40.23 with 3 tiles and 40.86 / 39.61 with 5, and 4 tiles of 122 columns (3.9 MB) lose 1.8 ms
@@ -630,7 +631,13 @@ void knn_host(const double *queries, uint64_t n_q, const double *points, uint64_
               uint32_t *out);
 // the same with both point sets already in device memory (row-major, leading dimensions in elements); `out` is a host array
 void knn_device(const double *d_queries, uint32_t ld_q, uint64_t n_q, const double *d_points, uint32_t ld_p, uint64_t n_p, uint32_t d,
-                uint32_t k, bool skip_same_index, uint32_t *out);
+                uint32_t k, bool skip_same_index, uint32_t *out, double *sq_dist = nullptr); // sq_dist: host, n_q x k squared distances (+inf in padded slots), or nullptr
+// The collective search of a sharded handle, on the handle's stream: d_pts holds the rank's own rows [begin, begin + n_local)
+// of the n global ones; out / sq_dist are host arrays over the rank's rows and hold GLOBAL indices. Counts st.knn_blocks / knn_allreduces.
+void knn_sharded(Storage &st, const double *d_pts, uint32_t ld, uint64_t begin, uint64_t n_local, uint64_t n, uint32_t d, uint32_t k,
+                 uint32_t *out, double *sq_dist);
+// the merge rule of that search on host arrays (knn_merge.hpp; scanrs_host_knn_merge)
+void knn_host_merge(uint32_t k, const double *da, const uint32_t *ia, const double *db, const uint32_t *ib, double *dout, uint32_t *iout);
 // for tests (scanrs_debug_knn_*): what the last knn_device of the process did, one entry per filter round (nothing when it did not go
 // through the filter); the filter's constants; one filter pass on host arrays
 void knn_last_stats(bool &filtered, uint64_t &first_stride, std::vector<uint64_t> &strides, std::vector<uint64_t> &points,

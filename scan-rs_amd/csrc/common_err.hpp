@@ -19,6 +19,7 @@ struct GlobalOptions {
     int knn_exhaustive = 0;                   // 1: never use the bf16-MFMA filter of the k nearest neighbour search
     unsigned long long knn_filter_min_points = 32768; // point sets below this are ranked exhaustively
     unsigned long long knn_ratio = 4;         // density ratio between two subsets of the filter
+    unsigned long long knn_block_rows = 262144; // rows of the point set a sharded search exchanges and searches at a time
     int knn_stats = 0;                        // 1: filter statistics on stderr
 };
 GlobalOptions &global_options();

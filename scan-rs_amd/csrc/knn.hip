@@ -12,6 +12,9 @@
 //    1000000 50 15`, same MI355X: 479 ms with the margin 0.0021 this file had until it was re-derived, 102 candidates per query in
 //    the last round; 536 ms and 158 candidates with 0.00395. Subtracting a common centre before kf_prep_* would shrink the
 //    |q|^2 + |p|^2 the margin is relative to and win that back: not done yet).
+//  * over a sharded point set (knn_sharded at the end of this file): the points pass by in global blocks, each block
+//    searched by the two forms above (seeded with what the query already holds) and merged into a running list per query by
+//    (squared distance, global index) - knn_merge.hpp. Equal to the search of the whole set bit for bit, whatever the cut.
 // Ties keep ascending index order (the rule of the reference's own test oracle, `exhaustive_knn`, nn.rs:112-137; the ball
 // tree's order among exactly equidistant points is a property of that crate).
 #include <hip/hip_runtime.h>
@@ -23,6 +26,7 @@
 #include <vector>
 
 #include "common.hpp"
+#include "knn_merge.hpp"
 
 namespace scanrs {
 
@@ -33,7 +37,8 @@ constexpr uint32_t KMAX = 128;
 template <int DMAX, int THREADS>
 __global__ __launch_bounds__(THREADS) void knn_kernel(const double *__restrict__ queries, uint64_t n_q, const double *__restrict__ points,
                                                      uint64_t n_p, uint32_t d, uint32_t k, int skip_same_index, uint64_t skip_stride,
-                                                     uint32_t *__restrict__ out) {
+                                                     uint64_t p_off, uint64_t q_off, uint32_t *__restrict__ out,
+                                                     double *__restrict__ out_d) {
     const uint64_t qi = (uint64_t)blockIdx.x * THREADS + threadIdx.x;
     const bool live = qi < n_q;
     double q[DMAX];
@@ -53,7 +58,8 @@ __global__ __launch_bounds__(THREADS) void knn_kernel(const double *__restrict__
             const double t = pt[j] - q[j];
             s = fma(t, t, s);
         }
-        if (!live || (skip_same_index && pi * skip_stride == qi)) continue; // candidate pi is row pi * skip_stride of the full set
+        // candidate pi is row pi * skip_stride of the point set, whose row 0 is global row p_off; query qi is global row q_off + qi
+        if (!live || (skip_same_index && p_off + pi * skip_stride == q_off + qi)) continue;
         if (have == k && !(s < worst)) continue;
         // sorted insertion; equal distances stay in index order because candidates arrive in index order
         uint32_t pos = have < k ? have : k - 1u;
@@ -69,6 +75,8 @@ __global__ __launch_bounds__(THREADS) void knn_kernel(const double *__restrict__
     }
     if (!live) return;
     for (uint32_t i = 0; i < k; i++) out[qi * k + i] = i < have ? best_i[i] : 0xFFFFFFFFu; // T::max_value() padding, nn.rs:66
+    if (out_d)
+        for (uint32_t i = 0; i < k; i++) out_d[qi * k + i] = i < have ? best_d[i] : INFINITY;
 }
 
 // dst row r = src row r * row_stride, zero-padded to dmax columns
@@ -83,7 +91,7 @@ __global__ void pad_points_kernel(const double *__restrict__ src, uint32_t ld, u
 
 template <int DMAX, int THREADS>
 void launch(const double *dq, uint32_t ldq, uint64_t n_q, const double *dp, uint32_t ldp, uint64_t n_p, uint32_t d, uint32_t k, int skip,
-            uint32_t *dout, hipStream_t s, uint64_t p_stride = 1) {
+            uint32_t *dout, hipStream_t s, uint64_t p_stride, uint64_t p_off, uint64_t q_off, double *ddist) {
     // p_stride > 1: the candidates are rows 0, p_stride, 2 p_stride, ... of dp (n_p of them); indices written are subset-local
     // zero-padded (n x DMAX) copies: the candidate's coordinates arrive as whole scalar-cache lines, the query's as one run per thread
     DevBuf<double> pp, qp;
@@ -97,25 +105,28 @@ void launch(const double *dq, uint32_t ldq, uint64_t n_q, const double *dp, uint
         q = qp.p;
     }
     const dim3 grid((unsigned)((n_q + THREADS - 1) / THREADS)), block(THREADS);
-    hipLaunchKernelGGL((knn_kernel<DMAX, THREADS>), grid, block, 0, s, q, n_q, pp.p, n_p, (uint32_t)DMAX, k, skip, p_stride, dout);
+    hipLaunchKernelGGL((knn_kernel<DMAX, THREADS>), grid, block, 0, s, q, n_q, pp.p, n_p, (uint32_t)DMAX, k, skip, p_stride, p_off, q_off, dout,
+                       ddist);
     SCANRS_SYNC(s); // the padded copies are released on return
 }
 
-// exhaustive search of every query against rows 0, p_stride, 2 p_stride, ... of the point set (n_sub of them); subset-local indices
-void exhaustive(const double *dq, uint32_t ldq, uint64_t n_q, const double *dp, uint32_t ldp, uint64_t n_sub, uint32_t d, uint32_t k,
-                int skip, uint32_t *dout, uint64_t p_stride = 1) {
+// exhaustive search of every query against rows 0, p_stride, 2 p_stride, ... of the point set (n_sub of them); subset-local indices.
+// p_off / q_off: the global rows of point row 0 and of query 0 (what the self exclusion compares); ddist: the k squared distances
+// beside the indices (+inf in padded slots), or nullptr
+void exhaustive(hipStream_t s, const double *dq, uint32_t ldq, uint64_t n_q, const double *dp, uint32_t ldp, uint64_t n_sub, uint32_t d,
+                uint32_t k, int skip, uint32_t *dout, uint64_t p_stride = 1, uint64_t p_off = 0, uint64_t q_off = 0, double *ddist = nullptr) {
     if (d <= 8)
-        launch<8, 256>(dq, ldq, n_q, dp, ldp, n_sub, d, k, skip, dout, 0, p_stride);
+        launch<8, 256>(dq, ldq, n_q, dp, ldp, n_sub, d, k, skip, dout, s, p_stride, p_off, q_off, ddist);
     else if (d <= 16)
-        launch<16, 256>(dq, ldq, n_q, dp, ldp, n_sub, d, k, skip, dout, 0, p_stride);
+        launch<16, 256>(dq, ldq, n_q, dp, ldp, n_sub, d, k, skip, dout, s, p_stride, p_off, q_off, ddist);
     else if (d <= 32)
-        launch<32, 256>(dq, ldq, n_q, dp, ldp, n_sub, d, k, skip, dout, 0, p_stride);
+        launch<32, 256>(dq, ldq, n_q, dp, ldp, n_sub, d, k, skip, dout, s, p_stride, p_off, q_off, ddist);
     else if (d <= 52) // top-50 PCA scores, the default of scan-rs-cmd (tools/src/bin/cmd.rs:46-48)
-        launch<52, 256>(dq, ldq, n_q, dp, ldp, n_sub, d, k, skip, dout, 0, p_stride);
+        launch<52, 256>(dq, ldq, n_q, dp, ldp, n_sub, d, k, skip, dout, s, p_stride, p_off, q_off, ddist);
     else if (d <= 64)
-        launch<64, 256>(dq, ldq, n_q, dp, ldp, n_sub, d, k, skip, dout, 0, p_stride);
+        launch<64, 256>(dq, ldq, n_q, dp, ldp, n_sub, d, k, skip, dout, s, p_stride, p_off, q_off, ddist);
     else
-        launch<128, 64>(dq, ldq, n_q, dp, ldp, n_sub, d, k, skip, dout, 0, p_stride);
+        launch<128, 64>(dq, ldq, n_q, dp, ldp, n_sub, d, k, skip, dout, s, p_stride, p_off, q_off, ddist);
     SCANRS_HIP(hipGetLastError());
 }
 
@@ -371,9 +382,9 @@ __global__ __launch_bounds__(256, 2) void kf_filter_kernel(const uint16_t *__res
 // and tau = the k-th distance (+inf when fewer than k exist). Overflowed lists (cnt > KF_CAP) are left to the exhaustive kernel.
 constexpr uint32_t KF_PER_LANE = KF_CAP / 64u;
 __global__ __launch_bounds__(256) void kf_rerank_kernel(const double *__restrict__ Q, uint32_t ldq, uint64_t n_q, const double *__restrict__ P,
-                                                        uint32_t ldp, uint32_t d, uint32_t k, int skip_same_index,
-                                                        const uint32_t *__restrict__ cand, const uint32_t *__restrict__ cnt,
-                                                        uint32_t *__restrict__ out, double *__restrict__ tau) {
+                                                        uint32_t ldp, uint32_t d, uint32_t k, int skip_same_index, uint64_t p_off,
+                                                        uint64_t q_off, const uint32_t *__restrict__ cand, const uint32_t *__restrict__ cnt,
+                                                        uint32_t *__restrict__ out, double *__restrict__ out_d, double *__restrict__ tau) {
     const uint32_t lane = threadIdx.x & 63u;
     const uint64_t q = (uint64_t)blockIdx.x * 4u + (threadIdx.x >> 6);
     if (q >= n_q) return;
@@ -389,7 +400,7 @@ __global__ __launch_bounds__(256) void kf_rerank_kernel(const double *__restrict
         idx[u] = 0xFFFFFFFFu;
         if (j < c) {
             const uint32_t p = cand[q * KF_CAP + j];
-            if (!(skip_same_index && (uint64_t)p == q)) {
+            if (!(skip_same_index && p_off + p == q_off + q)) { // global rows: the offsets are 0 unless the points are one block of a sharded set
                 const double *__restrict__ pr = P + (uint64_t)p * ldp;
                 double s = 0.0;
                 for (uint32_t t = 0; t < d; t++) {
@@ -424,9 +435,13 @@ __global__ __launch_bounds__(256) void kf_rerank_kernel(const double *__restrict
             }
         }
         if (lane == 0) out[q * k + it] = wi;
+        if (lane == 0 && out_d) out_d[q * k + it] = wi == 0xFFFFFFFFu ? INFINITY : wd;
         if (wi == 0xFFFFFFFFu) { // fewer than k candidates: the rest is padding
             for (uint32_t r2 = it + 1; r2 < k; r2++)
-                if (lane == 0) out[q * k + r2] = 0xFFFFFFFFu;
+                if (lane == 0) {
+                    out[q * k + r2] = 0xFFFFFFFFu;
+                    if (out_d) out_d[q * k + r2] = INFINITY;
+                }
             kth = DBL_MAX;
             break;
         }
@@ -477,11 +492,19 @@ __global__ void kf_gather_rows_kernel(const double *__restrict__ src, uint32_t l
     if (e >= n * d) return;
     dst[e] = src[(uint64_t)rows[e / d] * ld + (e % d)];
 }
-__global__ void kf_scatter_result_kernel(const uint32_t *__restrict__ res, const uint32_t *__restrict__ rows, uint64_t n, uint32_t k,
-                                         uint32_t *__restrict__ out) {
+template <typename T>
+__global__ void kf_scatter_result_kernel(const T *__restrict__ res, const uint32_t *__restrict__ rows, uint64_t n, uint32_t k,
+                                         T *__restrict__ out) {
     const uint64_t e = (uint64_t)blockIdx.x * blockDim.x + threadIdx.x;
     if (e >= n * k) return;
     out[(uint64_t)rows[e / k] * k + (e % k)] = res[e];
+}
+// a seeded search (one block of a sharded point set): no threshold above the k-th distance the query already holds
+// from the blocks before (seed[q * seed_ld]; +inf while it holds fewer than k)
+__global__ void kf_seed_kernel(double *__restrict__ tau, const double *__restrict__ seed, uint64_t seed_ld, uint64_t n) {
+    const uint64_t q = (uint64_t)blockIdx.x * blockDim.x + threadIdx.x;
+    if (q >= n) return;
+    tau[q] = fmin(tau[q], seed[q * seed_ld]);
 }
 
 // what the last scanrs_knn* / scanrs_find_nn call of the process did (scanrs_debug_knn_last_stats)
@@ -498,55 +521,120 @@ std::mutex g_stats_mutex;
 KnnLastStats g_last_stats;
 
 // the bf16 operands of one filtered search
-struct KfOperands {
-    DevBuf<uint16_t> Qb, Pb;
+// the query side: prepared with the points for one search, or once for all the blocks a sharded search passes by (kf_prepare_queries)
+struct KfQueries {
+    DevBuf<uint16_t> Qb;
     DevBuf<double> qn;
     uint64_t nq_rows = 0;
+    double maxabs = 0.0; // max |coordinate| of the queries (NaN: one of them is not finite)
+};
+struct KfOperands {
+    KfQueries own;
+    const KfQueries *q = nullptr; // &own, or the caller's
+    DevBuf<uint16_t> Pb;
     double slack = 0.0; // absolute part of the margin, 2^-117 (M + 1)
 };
-// false: a coordinate is not finite or max |coordinate| lies outside the magnitude window; nothing has been prepared
-bool kf_prepare(hipStream_t s, const double *dq, uint32_t ldq, uint64_t n_q, const double *dp, uint32_t ldp, uint64_t n_p, uint32_t d,
-                KfOperands &op) {
+// max |coordinate| of up to two matrices in one pass and one wait; NaN when a coordinate is not finite
+double kf_maxabs(hipStream_t s, const double *a, uint32_t lda, uint64_t na, const double *b, uint32_t ldb, uint64_t nb, uint32_t d) {
     DevBuf<unsigned long long> mx(1);
     SCANRS_HIP(hipMemsetAsync(mx.p, 0, 8, s));
     auto reduce = [&](const double *x, uint32_t ld, uint64_t n) {
         const uint64_t blocks = std::min<uint64_t>((n * d + 255) / 256, 2048);
         hipLaunchKernelGGL(kf_maxabs_kernel, dim3((unsigned)blocks), dim3(256), 0, s, x, ld, n, d, mx.p);
     };
-    reduce(dp, ldp, n_p);
-    if (dq != dp || ldq != ldp || n_q > n_p) reduce(dq, ldq, n_q);
-    unsigned long long bits = 0;
-    SCANRS_HIP(hipMemcpyAsync(&bits, mx.p, 8, hipMemcpyDeviceToHost, s));
-    SCANRS_SYNC(s);
+    if (na) reduce(a, lda, na);
+    if (nb) reduce(b, ldb, nb);
+    const unsigned long long bits = SCANRS_D2H_VALUE(mx.p, s);
     double m;
     memcpy(&m, &bits, 8);
-    if (!(m >= KF_COORD_MIN && m <= KF_COORD_MAX)) return false; // NaN and +inf fail the comparison too
+    return m <= DBL_MAX ? m : NAN; // +inf and the NaN patterns sort above every finite value
+}
+void kf_launch_prep_queries(hipStream_t s, const double *dq, uint32_t ldq, uint64_t n_q, uint32_t d, KfQueries &qs) {
+    qs.nq_rows = (n_q + 127) / 128 * 128;
+    qs.Qb.alloc(qs.nq_rows * KF_DP);
+    qs.qn.alloc(n_q);
+    hipLaunchKernelGGL(kf_prep_queries_kernel, dim3((unsigned)((qs.nq_rows + 255) / 256)), dim3(256), 0, s, dq, ldq, n_q, qs.nq_rows, d, qs.Qb.p,
+                       qs.qn.p);
+}
+// the query side alone, for a search whose points arrive in blocks: its max-abs pass and its operands are made once
+void kf_prepare_queries(hipStream_t s, const double *dq, uint32_t ldq, uint64_t n_q, uint32_t d, KfQueries &qs) {
+    qs.maxabs = kf_maxabs(s, dq, ldq, n_q, nullptr, 0, 0, d);
+    if (qs.maxabs <= KF_COORD_MAX) kf_launch_prep_queries(s, dq, ldq, n_q, d, qs); // (false for NaN: nothing is prepared, no block is filtered)
+}
+// false: a coordinate is not finite or max |coordinate| lies outside the magnitude window; nothing has been prepared.
+// shared: the query side prepared earlier by kf_prepare_queries (nullptr: it is prepared here)
+bool kf_prepare(hipStream_t s, const double *dq, uint32_t ldq, uint64_t n_q, const double *dp, uint32_t ldp, uint64_t n_p, uint32_t d,
+                KfOperands &op, const KfQueries *shared = nullptr) {
+    const bool own_queries = !shared && (dq != dp || ldq != ldp || n_q > n_p);
+    double m = kf_maxabs(s, dp, ldp, n_p, dq, ldq, own_queries ? n_q : 0, d);
+    if (shared) m = shared->maxabs > m ? shared->maxabs : (shared->maxabs == shared->maxabs ? m : NAN);
+    if (!(m >= KF_COORD_MIN && m <= KF_COORD_MAX)) return false; // NaN fails the comparison too
     op.slack = 0x1p-117 * (m + 1.0);
-    op.nq_rows = (n_q + 127) / 128 * 128;
     const uint64_t np_rows = n_p + 1; // one sentinel row behind the points
-    op.Qb.alloc(op.nq_rows * KF_DP);
     op.Pb.alloc(np_rows * KF_DP);
-    op.qn.alloc(n_q);
     hipLaunchKernelGGL(kf_prep_points_kernel, dim3((unsigned)((np_rows + 255) / 256)), dim3(256), 0, s, dp, ldp, n_p, np_rows, d, op.Pb.p);
-    hipLaunchKernelGGL(kf_prep_queries_kernel, dim3((unsigned)((op.nq_rows + 255) / 256)), dim3(256), 0, s, dq, ldq, n_q, op.nq_rows, d, op.Qb.p,
-                       op.qn.p);
+    if (shared) {
+        op.q = shared;
+    } else {
+        kf_launch_prep_queries(s, dq, ldq, n_q, d, op.own);
+        op.q = &op.own;
+    }
     return true;
 }
 // one pass of the filter over rows 0, st, 2 st, ... of the points with the thresholds tau: cnt (n_q) and the lists cand (n_q x KF_CAP)
 void kf_filter_pass(hipStream_t s, const KfOperands &op, const double *tau, uint64_t n_q, uint64_t n_p, uint64_t st, uint32_t *cand,
                     uint32_t *cnt) {
     const uint64_t n_sub = (n_p + st - 1) / st;
-    hipLaunchKernelGGL(kf_set_threshold_kernel, dim3((unsigned)((n_q + 255) / 256)), dim3(256), 0, s, tau, op.qn.p, n_q, op.slack, op.Qb.p, cnt);
-    hipLaunchKernelGGL(kf_filter_kernel, dim3((unsigned)(op.nq_rows / 128)), dim3(256), 0, s, op.Qb.p, n_q, op.Pb.p, n_sub, st, n_p, cand, cnt);
+    hipLaunchKernelGGL(kf_set_threshold_kernel, dim3((unsigned)((n_q + 255) / 256)), dim3(256), 0, s, tau, op.q->qn.p, n_q, op.slack, op.q->Qb.p, cnt);
+    hipLaunchKernelGGL(kf_filter_kernel, dim3((unsigned)(op.q->nq_rows / 128)), dim3(256), 0, s, op.q->Qb.p, n_q, op.Pb.p, n_sub, st, n_p, cand, cnt);
 }
 
-bool knn_filtered(const double *dq, uint32_t ldq, uint64_t n_q, const double *dp, uint32_t ldp, uint64_t n_p, uint32_t d, uint32_t k,
-                  int skip, uint32_t *dout, KnnLastStats &stats) {
+// The copies of a search. The entry points on stream 0 keep the blocking copies they have always made; a search on a handle's own
+// (non-blocking) stream queues them there and waits for that stream alone, bounded like every wait of the library.
+void kf_d2h(hipStream_t s, void *dst, const void *src, size_t bytes) {
+    if (!s) {
+        SCANRS_HIP(hipMemcpy(dst, src, bytes, hipMemcpyDeviceToHost));
+        return;
+    }
+    SCANRS_D2H(dst, src, bytes, s);
+    SCANRS_SYNC(s);
+}
+void kf_h2d(hipStream_t s, void *dst, const void *src, size_t bytes) {
+    if (!s) {
+        SCANRS_HIP(hipMemcpy(dst, src, bytes, hipMemcpyHostToDevice));
+        return;
+    }
+    SCANRS_HIP(hipMemcpyAsync(dst, src, bytes, hipMemcpyHostToDevice, s));
+    SCANRS_SYNC(s); // the source is pageable and the caller's again on return
+}
+void kf_d2d(hipStream_t s, void *dst, const void *src, size_t bytes) {
+    if (!s)
+        SCANRS_HIP(hipMemcpy(dst, src, bytes, hipMemcpyDeviceToDevice));
+    else
+        SCANRS_HIP(hipMemcpyAsync(dst, src, bytes, hipMemcpyDeviceToDevice, s));
+}
+
+// where a search stands in a larger one (all defaults: the points are the whole set and the queries its rows, as in scanrs_knn)
+struct KnnPlace {
+    uint64_t p_off = 0, q_off = 0;   // the global rows of point row 0 and of query 0: the self exclusion compares global rows
+    const double *seed = nullptr;    // seeded search: per query the k-th distance it already holds, element q * seed_ld
+    uint64_t seed_ld = 0;
+    const KfQueries *queries = nullptr; // the query side prepared once for all blocks
+};
+// Round 0 of a seeded search only tightens a threshold the earlier blocks have set already, and it is paid once per block: its
+// exactly ranked subset is a quarter of what an unseeded search ranks, one more filter round in exchange.
+constexpr uint64_t KF_SEED_N0 = KF_CAP / 4;
+
+bool knn_filtered(hipStream_t s, const double *dq, uint32_t ldq, uint64_t n_q, const double *dp, uint32_t ldp, uint64_t n_p, uint32_t d,
+                  uint32_t k, int skip, uint32_t *dout, double *ddist, KnnLastStats &stats, const KnnPlace &pl) {
     const GlobalOptions &go = global_options(); // scanrs_set_global_option (read per call: tests flip them)
     const bool off = go.knn_exhaustive != 0;
     const uint64_t min_points = go.knn_filter_min_points;
     if (off || d > KF_DMAX || n_p < min_points || k > KF_KMAX || n_q < KF_NQ_MIN) return false;
-    hipStream_t s = 0;
+    const uint64_t n0_max = pl.seed ? KF_SEED_N0 : KF_CAP;
+    auto seed_tau = [&](double *tau) {
+        if (pl.seed) hipLaunchKernelGGL(kf_seed_kernel, dim3((unsigned)((n_q + 255) / 256)), dim3(256), 0, s, tau, pl.seed, pl.seed_ld, n_q);
+    };
     // nested strided subsets S_0 < S_1 < ... < all points: S_0 (at most KF_CAP points) is ranked exactly for every query, which gives
     // an upper bound tau of the k-th distance; every further subset is `ratio` times denser and goes through the filter with the
     // previous tau, which lets about k * ratio * (volume inflation of the margin) pairs per query through.
@@ -554,32 +642,34 @@ bool knn_filtered(const double *dq, uint32_t ldq, uint64_t n_q, const double *dp
     const bool print_stats = go.knn_stats != 0;
     std::vector<uint64_t> strides;
     uint64_t st0 = 1;
-    while ((n_p + st0 - 1) / st0 > KF_CAP) st0 *= 2;
+    while ((n_p + st0 - 1) / st0 > n0_max) st0 *= 2;
     for (uint64_t st = st0; st > 1;) {
         st = st / ratio > 0 ? st / ratio : 1;
         strides.push_back(st);
     }
     if (strides.empty()) return false;
     KfOperands op;
-    if (!kf_prepare(s, dq, ldq, n_q, dp, ldp, n_p, d, op)) return false; // outside the magnitude window: the exhaustive kernel answers
+    if (!kf_prepare(s, dq, ldq, n_q, dp, ldp, n_p, d, op, pl.queries)) return false; // outside the magnitude window: the exhaustive kernel answers
     stats.first_stride = st0;
     DevBuf<double> tau(n_q);
     DevBuf<uint32_t> cnt(n_q), cand(n_q * KF_CAP);
     { // round 0: exact ranking of the coarsest subset
         const uint32_t n0 = (uint32_t)((n_p + st0 - 1) / st0);
         hipLaunchKernelGGL(kf_fill_all_kernel, dim3((unsigned)((n_q * n0 + 255) / 256)), dim3(256), 0, s, n_q, n0, st0, cand.p, cnt.p);
-        hipLaunchKernelGGL(kf_rerank_kernel, dim3((unsigned)((n_q + 3) / 4)), dim3(256), 0, s, dq, ldq, n_q, dp, ldp, d, k, skip, cand.p, cnt.p,
-                           dout, tau.p);
+        hipLaunchKernelGGL(kf_rerank_kernel, dim3((unsigned)((n_q + 3) / 4)), dim3(256), 0, s, dq, ldq, n_q, dp, ldp, d, k, skip, pl.p_off, pl.q_off,
+                           cand.p, cnt.p, dout, ddist, tau.p);
+        seed_tau(tau.p);
     }
     std::vector<uint32_t> h_cnt(n_q);
     for (uint64_t st : strides) {
         const uint64_t n_sub = (n_p + st - 1) / st;
         kf_filter_pass(s, op, tau.p, n_q, n_p, st, cand.p, cnt.p);
-        hipLaunchKernelGGL(kf_rerank_kernel, dim3((unsigned)((n_q + 3) / 4)), dim3(256), 0, s, dq, ldq, n_q, dp, ldp, d, k, skip, cand.p, cnt.p,
-                           dout, tau.p);
+        hipLaunchKernelGGL(kf_rerank_kernel, dim3((unsigned)((n_q + 3) / 4)), dim3(256), 0, s, dq, ldq, n_q, dp, ldp, d, k, skip, pl.p_off, pl.q_off,
+                           cand.p, cnt.p, dout, ddist, tau.p);
+        seed_tau(tau.p);
         SCANRS_HIP(hipGetLastError());
         // overflowed lists (rare: heavy ties, adversarial clusters): those queries are redone exhaustively on this subset
-        SCANRS_HIP(hipMemcpy(h_cnt.data(), cnt.p, n_q * 4, hipMemcpyDeviceToHost));
+        kf_d2h(s, h_cnt.data(), cnt.p, n_q * 4);
         KfRound rd{st, n_sub, 0, 0, 0};
         std::vector<uint32_t> rows;
         for (uint64_t q = 0; q < n_q; q++) {
@@ -597,38 +687,54 @@ bool knn_filtered(const double *dq, uint32_t ldq, uint64_t n_q, const double *dp
             const uint64_t m = rows.size();
             DevBuf<uint32_t> d_rows(m), res(m * k);
             DevBuf<double> qsel(m * d), tsel(m);
-            SCANRS_HIP(hipMemcpy(d_rows.p, rows.data(), m * 4, hipMemcpyHostToDevice));
+            kf_h2d(s, d_rows.p, rows.data(), m * 4);
             hipLaunchKernelGGL(kf_gather_rows_kernel, dim3((unsigned)((m * d + 255) / 256)), dim3(256), 0, s, dq, ldq, d, d_rows.p, m, qsel.p);
             // the self-exclusion rule compares row numbers, which the gathered copy has lost: search for k + 1 and drop the query's own row on the host
             const uint32_t kk = std::min<uint32_t>(k + (skip ? 1u : 0u), KMAX);
             DevBuf<uint32_t> res2(m * kk);
-            exhaustive(qsel.p, d, m, dp, ldp, n_sub, d, kk, 0, res2.p, st);
+            DevBuf<double> dist2, dres;
+            if (ddist) {
+                dist2.alloc(m * kk);
+                dres.alloc(m * k);
+            }
+            exhaustive(s, qsel.p, d, m, dp, ldp, n_sub, d, kk, 0, res2.p, st, 0, 0, dist2.p);
             std::vector<uint32_t> h_res(m * kk), h_out(m * k);
-            SCANRS_HIP(hipMemcpy(h_res.data(), res2.p, m * kk * 4, hipMemcpyDeviceToHost));
+            std::vector<double> h_dist(ddist ? m * kk : 0), h_dout(ddist ? m * k : 0);
+            kf_d2h(s, h_res.data(), res2.p, m * kk * 4);
+            if (ddist) kf_d2h(s, h_dist.data(), dist2.p, m * kk * 8);
             for (uint64_t i = 0; i < m; i++) {
                 uint32_t w = 0;
                 for (uint32_t j = 0; j < kk && w < k; j++) {
                     const uint32_t t = h_res[i * kk + j];
                     const uint64_t prow = t == 0xFFFFFFFFu ? 0xFFFFFFFFull : (uint64_t)t * st;
-                    if (skip && prow == rows[i]) continue;
+                    if (skip && t != 0xFFFFFFFFu && pl.p_off + prow == pl.q_off + rows[i]) continue; // the query's own (global) row
+                    if (ddist) h_dout[i * k + w] = t == 0xFFFFFFFFu ? INFINITY : h_dist[i * kk + j];
                     h_out[i * k + w++] = t == 0xFFFFFFFFu ? 0xFFFFFFFFu : (uint32_t)prow;
                 }
-                for (; w < k; w++) h_out[i * k + w] = 0xFFFFFFFFu;
+                for (; w < k; w++) {
+                    if (ddist) h_dout[i * k + w] = INFINITY;
+                    h_out[i * k + w] = 0xFFFFFFFFu;
+                }
             }
-            SCANRS_HIP(hipMemcpy(res.p, h_out.data(), m * k * 4, hipMemcpyHostToDevice));
-            hipLaunchKernelGGL(kf_scatter_result_kernel, dim3((unsigned)((m * k + 255) / 256)), dim3(256), 0, s, res.p, d_rows.p, m, k, dout);
+            kf_h2d(s, res.p, h_out.data(), m * k * 4);
+            hipLaunchKernelGGL(kf_scatter_result_kernel<uint32_t>, dim3((unsigned)((m * k + 255) / 256)), dim3(256), 0, s, res.p, d_rows.p, m, k, dout);
+            if (ddist) {
+                kf_h2d(s, dres.p, h_dout.data(), m * k * 8);
+                hipLaunchKernelGGL(kf_scatter_result_kernel<double>, dim3((unsigned)((m * k + 255) / 256)), dim3(256), 0, s, dres.p, d_rows.p, m, k, ddist);
+            }
             // their thresholds for the next round: exact distance to the k-th neighbour just found (row indices now)
             if (st != 1) {
                 DevBuf<uint32_t> nb(n_q * k);
-                SCANRS_HIP(hipMemcpy(nb.p, dout, n_q * k * 4, hipMemcpyDeviceToDevice));
+                kf_d2d(s, nb.p, dout, n_q * k * 4);
                 DevBuf<double> tau2(n_q);
                 hipLaunchKernelGGL(kf_tau0_kernel, dim3((unsigned)((n_q + 255) / 256)), dim3(256), 0, s, dq, ldq, n_q, dp, ldp, d, k, (uint64_t)1, nb.p,
                                    tau2.p);
                 std::vector<double> h_t(n_q), h_t2(n_q);
-                SCANRS_HIP(hipMemcpy(h_t.data(), tau.p, n_q * 8, hipMemcpyDeviceToHost));
-                SCANRS_HIP(hipMemcpy(h_t2.data(), tau2.p, n_q * 8, hipMemcpyDeviceToHost));
+                kf_d2h(s, h_t.data(), tau.p, n_q * 8);
+                kf_d2h(s, h_t2.data(), tau2.p, n_q * 8);
                 for (uint32_t rq : rows) h_t[rq] = h_t2[rq];
-                SCANRS_HIP(hipMemcpy(tau.p, h_t.data(), n_q * 8, hipMemcpyHostToDevice));
+                kf_h2d(s, tau.p, h_t.data(), n_q * 8);
+                seed_tau(tau.p);
             }
         }
     }
@@ -687,24 +793,192 @@ void knn_filter_debug(const double *queries, uint64_t n_q, const double *points,
 }
 
 void knn_device(const double *d_queries, uint32_t ld_q, uint64_t n_q, const double *d_points, uint32_t ld_p, uint64_t n_p, uint32_t d,
-                uint32_t k, bool skip_same_index, uint32_t *out) {
+                uint32_t k, bool skip_same_index, uint32_t *out, double *sq_dist) {
     if (k == 0 || n_q == 0) return;
     if (k > KMAX) fail(SCANRS_ERR_ARGUMENT, "knn: k must not exceed 128");
     if (d == 0 || d > 128) fail(SCANRS_ERR_ARGUMENT, "knn: 1 <= dimensions <= 128");
     if (ld_q < d || ld_p < d) fail(SCANRS_ERR_ARGUMENT, "knn: leading dimension smaller than the number of coordinates");
     if (n_p > 0xFFFFFFFEull) fail(SCANRS_ERR_SHAPE, "knn: too many points for u32 indices");
     DevBuf<uint32_t> dout;
+    DevBuf<double> ddist;
     dout.alloc(n_q * k);
+    if (sq_dist) ddist.alloc(n_q * k);
     const int skip = skip_same_index ? 1 : 0;
     KnnLastStats stats;
-    if (!knn_filtered(d_queries, ld_q, n_q, d_points, ld_p, n_p, d, k, skip, dout.p, stats)) {
+    if (!knn_filtered(0, d_queries, ld_q, n_q, d_points, ld_p, n_p, d, k, skip, dout.p, ddist.p, stats, KnnPlace())) {
         stats = KnnLastStats(); // declined (possibly after the magnitude check): nothing of the filter ran
-        exhaustive(d_queries, ld_q, n_q, d_points, ld_p, n_p, d, k, skip, dout.p);
+        exhaustive(0, d_queries, ld_q, n_q, d_points, ld_p, n_p, d, k, skip, dout.p, 1, 0, 0, ddist.p);
     }
     SCANRS_HIP(hipGetLastError());
     SCANRS_HIP(hipMemcpy(out, dout.p, n_q * k * 4, hipMemcpyDeviceToHost));
+    if (sq_dist) SCANRS_HIP(hipMemcpy(sq_dist, ddist.p, n_q * k * 8, hipMemcpyDeviceToHost));
     std::lock_guard<std::mutex> lock(g_stats_mutex);
     g_last_stats = std::move(stats);
+}
+
+// ---------------------------------------------------------------------------------------------------------------------
+// The search over a sharded point set: every rank owns the queries of its own cells, the point set passes by in
+// global blocks that one u64 all-reduce hands to every rank (each slot of the zeroed buffer has one writer, so the sum is the bit
+// pattern itself), each block is searched with the machinery above, seeded with what the query already holds, and its list is merged
+// into the query's running list by (squared distance, global index). The result does not depend on the cut: it is the k smallest
+// pairs under that total order, and the distance is the same fma chain everywhere.
+namespace {
+
+__global__ void ks_fill_kernel(double *__restrict__ x, uint64_t n, double v) {
+    const uint64_t e = (uint64_t)blockIdx.x * blockDim.x + threadIdx.x;
+    if (e < n) x[e] = v;
+}
+// the first local row that holds a coordinate which is not finite (an integer minimum; ~0 stays when there is none)
+__global__ __launch_bounds__(256) void ks_scan_kernel(const double *__restrict__ X, uint32_t ld, uint64_t n, uint32_t d,
+                                                      unsigned long long *__restrict__ first) {
+    const uint64_t total = n * d, step = (uint64_t)gridDim.x * blockDim.x;
+    for (uint64_t e = (uint64_t)blockIdx.x * blockDim.x + threadIdx.x; e < total; e += step) {
+        const uint64_t r = e / d;
+        const double x = X[r * ld + (e % d)];
+        if (!(fabs(x) <= DBL_MAX)) atomicMin(first, (unsigned long long)r);
+    }
+}
+// what the ranks agree on before the first block: four slots per rank of a zeroed array, n, d, k and (first bad global row + 1)
+__global__ void ks_header_kernel(unsigned long long *__restrict__ slots, uint32_t rank, uint64_t n, uint32_t d, uint32_t k, uint64_t begin,
+                                 const unsigned long long *__restrict__ first) {
+    if (blockIdx.x != 0 || threadIdx.x != 0) return;
+    unsigned long long *mine = slots + 4ull * rank;
+    mine[0] = n;
+    mine[1] = d;
+    mine[2] = k;
+    mine[3] = *first == ~0ull ? 0ull : begin + *first + 1ull;
+}
+// the bit patterns of n_rows rows of this rank into their place of the block buffer (rows x d, no padding)
+__global__ void ks_pack_kernel(const double *__restrict__ src, uint32_t ld, uint32_t d, uint64_t n_rows, unsigned long long *__restrict__ dst) {
+    const uint64_t e = (uint64_t)blockIdx.x * blockDim.x + threadIdx.x;
+    if (e >= n_rows * d) return;
+    dst[e] = (unsigned long long)__double_as_longlong(src[(e / d) * ld + (e % d)]);
+}
+// running list (+) block list -> running list: one wave per query, both lists staged in LDS (the block's indices become global
+// there), every lane places its entries by the rule of knn_merge.hpp. No atomics, nothing that depends on an order of arrival.
+__global__ __launch_bounds__(256) void ks_merge_kernel(uint64_t n_q, uint32_t k, const double *__restrict__ rd, const uint32_t *__restrict__ ri,
+                                                       const double *__restrict__ bd, const uint32_t *__restrict__ bi, uint32_t b_off,
+                                                       double *__restrict__ od, uint32_t *__restrict__ oi) {
+    __shared__ double sd[4][2 * KMAX];
+    __shared__ uint32_t si[4][2 * KMAX];
+    const uint32_t lane = threadIdx.x & 63u, w = threadIdx.x >> 6;
+    const uint64_t q = (uint64_t)blockIdx.x * 4u + w;
+    const bool live = q < n_q;
+    if (live)
+        for (uint32_t e = lane; e < k; e += 64u) {
+            sd[w][e] = rd[q * k + e];
+            si[w][e] = ri[q * k + e];
+            const uint32_t t = bi[q * k + e];
+            sd[w][KMAX + e] = bd[q * k + e];
+            si[w][KMAX + e] = t == 0xFFFFFFFFu ? t : t + b_off;
+        }
+    __syncthreads();
+    if (!live) return;
+    for (uint32_t e = lane; e < 2u * k; e += 64u)
+        knn_merge::place(k, sd[w], si[w], sd[w] + KMAX, si[w] + KMAX, e, od + q * k, oi + q * k);
+}
+
+} // namespace
+
+void knn_sharded(Storage &st, const double *d_pts, uint32_t ld, uint64_t begin, uint64_t n_local, uint64_t n, uint32_t d, uint32_t k,
+                 uint32_t *out, double *sq_dist) {
+    const hipStream_t s = st.stream;
+    const uint32_t world = st.shard.world, rank = st.shard.rank;
+    auto exchange = [&](unsigned long long *p, uint64_t count) {
+        allreduce_u64(st, p, count);
+        st.knn_allreduces++;
+    };
+    // 1. The ranks agree: the same n, d, k everywhere (a rank that differs would bring another count to a later exchange), and no
+    //    coordinate that is not finite (with a NaN the order is not total and a blockwise merge could differ from one pass).
+    const bool scannable = n_local && d && ld >= d && d_pts;
+    DevBuf<unsigned long long> first(1), slots(4ull * world);
+    SCANRS_HIP(hipMemsetAsync(first.p, 0xFF, 8, s));
+    SCANRS_HIP(hipMemsetAsync(slots.p, 0, 32ull * world, s));
+    if (scannable)
+        hipLaunchKernelGGL(ks_scan_kernel, dim3((unsigned)std::min<uint64_t>((n_local * d + 255) / 256, 2048)), dim3(256), 0, s, d_pts, ld, n_local, d,
+                           first.p);
+    hipLaunchKernelGGL(ks_header_kernel, dim3(1), dim3(64), 0, s, slots.p, rank, n, d, k, begin, first.p);
+    exchange(slots.p, 4ull * world);
+    std::vector<unsigned long long> h(4ull * world);
+    SCANRS_D2H(h.data(), slots.p, 32ull * world, s);
+    SCANRS_SYNC(s);
+    unsigned long long bad = 0;
+    for (uint32_t r = 0; r < world; r++) {
+        if (h[4 * r] != n || h[4 * r + 1] != d || h[4 * r + 2] != k)
+            fail(SCANRS_ERR_ARGUMENT, "knn_sharded: the ranks disagree (rank %u: n %llu, d %llu, k %llu; rank %u: n %llu, d %u, k %u)", r, h[4 * r],
+                 h[4 * r + 1], h[4 * r + 2], rank, (unsigned long long)n, d, k);
+        if (h[4 * r + 3] && (!bad || h[4 * r + 3] < bad)) bad = h[4 * r + 3];
+    }
+    if (k > KMAX) fail(SCANRS_ERR_ARGUMENT, "knn: k must not exceed 128");
+    if (d == 0 || d > 128) fail(SCANRS_ERR_ARGUMENT, "knn: 1 <= dimensions <= 128");
+    if (n > 0xFFFFFFFEull) fail(SCANRS_ERR_SHAPE, "knn: too many points for u32 indices");
+    if (bad) fail(SCANRS_ERR_ARGUMENT, "knn_sharded: row %llu of the points holds a coordinate that is not finite", bad - 1);
+    if (ld < d) fail(SCANRS_ERR_ARGUMENT, "knn: leading dimension smaller than the number of coordinates");
+    if (k == 0 || n == 0) return;
+
+    // 2. The running lists, sorted, padded with (+inf, UINT32_MAX); two copies: a merge reads one and writes the other.
+    const uint64_t n_list = std::max<uint64_t>(1, n_local * k);
+    DevBuf<double> rd[2] = {DevBuf<double>(n_list), DevBuf<double>(n_list)}, bdist(n_list);
+    DevBuf<uint32_t> ri[2] = {DevBuf<uint32_t>(n_list), DevBuf<uint32_t>(n_list)}, bidx(n_list);
+    int cur = 0;
+    hipLaunchKernelGGL(ks_fill_kernel, dim3((unsigned)((n_list + 255) / 256)), dim3(256), 0, s, rd[0].p, n_list, (double)INFINITY);
+    SCANRS_HIP(hipMemsetAsync(ri[0].p, 0xFF, n_list * 4, s));
+
+    // 3. The query side of the filter, once for all blocks - when a block can take the filter at all (the tests of knn_filtered).
+    const GlobalOptions &go = global_options();
+    const uint64_t block_rows = std::max<uint64_t>(1, go.knn_block_rows);
+    const uint64_t largest = std::min(block_rows, n);
+    KfQueries qs;
+    const bool may_filter = !go.knn_exhaustive && d <= KF_DMAX && k <= KF_KMAX && n_local >= KF_NQ_MIN && largest >= go.knn_filter_min_points;
+    if (may_filter) kf_prepare_queries(s, d_pts, ld, n_local, d, qs);
+
+    // 4. The blocks. The cut is global, so every rank walks the same blocks and the exchange steps pair up.
+    DevBuf<unsigned long long> xbuf(largest * d);
+    KnnLastStats stats;
+    for (uint64_t b0 = 0; b0 < n; b0 += block_rows) {
+        const uint64_t rows = std::min(block_rows, n - b0);
+        SCANRS_HIP(hipMemsetAsync(xbuf.p, 0, rows * d * 8, s));
+        const uint64_t lo = std::max(b0, begin), hi = std::min(b0 + rows, begin + n_local);
+        if (lo < hi)
+            hipLaunchKernelGGL(ks_pack_kernel, dim3((unsigned)(((hi - lo) * d + 255) / 256)), dim3(256), 0, s, d_pts + (lo - begin) * ld, ld, d, hi - lo,
+                               xbuf.p + (lo - b0) * d);
+        exchange(xbuf.p, rows * d);
+        st.knn_blocks++;
+        if (!n_local) continue;
+        const double *blk = reinterpret_cast<const double *>(xbuf.p);
+        if (st.prof.on) st.prof.begin(s, "knn_search", (double)(rows + n_local) * d * 8.0);
+        KnnPlace pl;
+        pl.p_off = b0;
+        pl.q_off = begin;
+        pl.seed = rd[cur].p + (k - 1);
+        pl.seed_ld = k;
+        pl.queries = may_filter ? &qs : nullptr;
+        stats = KnnLastStats();
+        if (!knn_filtered(s, d_pts, ld, n_local, blk, d, rows, d, k, 1, bidx.p, bdist.p, stats, pl)) {
+            stats = KnnLastStats();
+            exhaustive(s, d_pts, ld, n_local, blk, d, rows, d, k, 1, bidx.p, 1, b0, begin, bdist.p);
+        }
+        if (st.prof.on) st.prof.end(s);
+        if (st.prof.on) st.prof.begin(s, "knn_merge", (double)n_local * k * 36.0);
+        hipLaunchKernelGGL(ks_merge_kernel, dim3((unsigned)((n_local + 3) / 4)), dim3(256), 0, s, n_local, k, rd[cur].p, ri[cur].p, bdist.p, bidx.p,
+                           (uint32_t)b0, rd[1 - cur].p, ri[1 - cur].p);
+        if (st.prof.on) st.prof.end(s);
+        SCANRS_HIP(hipGetLastError());
+        cur = 1 - cur;
+    }
+    if (n_local) {
+        SCANRS_D2H(out, ri[cur].p, n_local * k * 4, s);
+        if (sq_dist) SCANRS_D2H(sq_dist, rd[cur].p, n_local * k * 8, s);
+    }
+    SCANRS_SYNC(s);
+    if (n_local) {
+        std::lock_guard<std::mutex> lock(g_stats_mutex);
+        g_last_stats = std::move(stats);
+    }
+}
+
+void knn_host_merge(uint32_t k, const double *da, const uint32_t *ia, const double *db, const uint32_t *ib, double *dout, uint32_t *iout) {
+    for (uint32_t e = 0; e < 2u * k; e++) knn_merge::place(k, da, ia, db, ib, e, dout, iout);
 }
 
 // queries (n_q x d) against points (n_p x d), both row-major host arrays; out n_q x k.

@@ -426,6 +426,37 @@ int scanrs_multi_merge_clusters(scanrs_multi *mm, int transposed, const double *
     });
 }
 
+// ---- knn over the shards (nn.rs:38-83) -----------------------------------------------------------------------------------
+// scanrs_knn_sharded on every shard at once. The cells are the sharded dimension (the columns of a CSC matrix, the rows of a CSR
+// one, which goes through its transposed view); every shard writes its own rows of the caller's arrays. points == NULL: every shard
+// searches the factor along the sharded dimension that its last scanrs_multi_pca_bk / _rand left on its device (V of a genes x cells
+// CSC matrix, U of a cells x genes CSR one), where that factor has the shard's own rows.
+int scanrs_multi_knn(scanrs_multi *mm, const double *points, uint32_t ld, uint32_t d, uint32_t k, uint32_t *out, double *sq_dist) {
+    if (!mm) return bad_argument("null handle");
+    const uint64_t cells = mm->bounds.back();
+    if (cells && k && !out) return bad_argument("null argument");
+    const int transposed = mm->storage == SCANRS_CSR;
+    return fan_out(mm, [&](size_t i) {
+        ShardView v;
+        if (const int rc = v.open(mm, i, transposed)) return rc;
+        const uint64_t lo = mm->bounds[i], n_loc = mm->bounds[i + 1] - lo;
+        uint32_t *o = out ? out + lo * k : nullptr;
+        double *sq = sq_dist ? sq_dist + lo * k : nullptr;
+        if (points) return scanrs_knn_sharded(v.h, points, 0, ld, d, k, o, sq);
+        const double *du = nullptr, *dv = nullptr;
+        uint32_t ldu = 0, ldv = 0, kk = 0;
+        if (const int rc = scanrs_pca_result_device(mm->shards[i], &du, &ldu, &dv, &ldv, &kk)) return rc; // "no PCA result on this handle yet"
+        const Storage::PcaDev &r = mm->shards[i]->st->pca_dev;
+        const uint64_t rows = transposed ? r.rows_u : r.rows_v;
+        if (rows != n_loc) {
+            set_error("multi_knn: the factor along the sharded dimension is not kept per shard (%llu rows on the device for %llu cells): pass the scores as a host array",
+                      (unsigned long long)rows, (unsigned long long)n_loc);
+            return (int)SCANRS_ERR_ARGUMENT;
+        }
+        return scanrs_knn_sharded(v.h, transposed ? du : dv, 1, transposed ? ldu : ldv, kk, k, o, sq);
+    });
+}
+
 // ---- select_rows / select_cols / partition_on_thresholds over the shards -------------------------------------------------
 // The collective entry points of the handle (scanrs_mat_*_sharded) on every shard at once. Every result is a new scanrs_multi on the
 // same devices with as many shards, the ranges its shards ended up with (nothing is rebalanced), and a group and communicators of its
