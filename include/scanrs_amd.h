@@ -535,6 +535,43 @@ int scanrs_multi_partition_on_thresholds(scanrs_multi *mm, const double *row_thr
 /* nnz-balanced contiguous partition of the outer dimension: bounds has world+1 entries. */
 int scanrs_plan_shards(const uint64_t *indptr, uint64_t n_outer, uint32_t world, uint64_t *bounds);
 
+/* ---- cell-sharded scanrs_multi from feature-major input --------------------
+ * scanrs_multi_create cuts the OUTER dimension of its triplet, and everything after it (normalize, the DE calls, kNN) needs the
+ * cells to be the sharded dimension - while the matrix the reference holds is feature-major: genes x cells CSR, one AdaptiveVec per
+ * gene (load_mtx, scan-rs/src/mtx.rs:10-51; read_adaptive_csr_matrix, hdf5-io/src/matrix.rs:119-192; tools/src/bin/cmd.rs:61-70).
+ * These constructors take the matrix in that orientation and shard its INNER dimension: the result is a scanrs_multi of the same
+ * rows x cols whose storage flag is the OTHER one (a genes x cells CSR triplet gives a genes x cells CSC multi with the cells
+ * sharded, a cells x genes CSC triplet a cells x genes CSR one). It equals scanrs_multi_create of the host-transposed triplet in
+ * every respect: the same shard ranges (scanrs_plan_shards over the stored entries per inner position, stored zeros counted), the
+ * same arrays in every shard bit for bit (indices ascending, stored zeros dropped), communicators of its own; every scanrs_multi_*
+ * call works on it unchanged. Nothing is transposed on the host and every nonzero crosses the host link once: the outer vectors are
+ * dealt in n_shards contiguous slabs by nonzeros (scanrs_plan_shards on the given indptr), shard s uploads slab s only -
+ * 8 z + 8 (n + 1) bytes for n vectors with z entries - and the shards exchange their pieces on the devices.
+ * Validation is scanrs_mat_create's (same codes and messages: an index out of range or not strictly ascending, indptr[0] != 0, null
+ * arrays, dimensions beyond u32) and runs on every slab before anything is indexed by an inner index; n_shards, devices and peer
+ * access are checked as in scanrs_multi_create (`devices` may repeat an id). On any failure nothing is leaked and *out is NULL.
+ * Not served: the one-process-per-GPU forms (RCCL, host hook: their only transport is a sum all-reduce), rebalancing an existing
+ * scanrs_multi, and to_adaptive of a whole scanrs_multi. */
+/* AdaptiveMat::new from a triplet (sqz/src/mat.rs:68-124), sharded over the inner dimension */
+int scanrs_multi_create_inner(uint64_t rows, uint64_t cols, int storage, const uint64_t *indptr, const uint32_t *indices,
+                              const uint32_t *values, uint32_t n_shards, const int *devices, scanrs_multi **out);
+/* The same from the table scanrs_mat_create_adaptive takes (AdaptiveMat::new(rows, cols, storage, Vec<AdaptiveVec>), mat.rs:68-90;
+ * what read_adaptive_csr_matrix returns, hdf5-io/src/matrix.rs:119-192). n_vecs is the outer dimension. The slabs are cut by the
+ * entries the vectors store (n_units); the compressed buffers of a slab are what is uploaded, and the slab is expanded on its device.
+ * The result holds the nonzeros (the decoder skips stored zeros, vec.rs:96-117). */
+int scanrs_multi_create_adaptive_inner(uint64_t rows, uint64_t cols, int storage, const scanrs_adaptive_vec *vecs, uint64_t n_vecs,
+                                       uint32_t n_shards, const int *devices, scanrs_multi **out);
+/* (scanrs_multi_create_from_file: with the readers, below) */
+/* What the constructor did: slab_bounds (n_shards + 1: the outer vectors of every slab), moved (n_shards x n_shards:
+ * moved[s * n + d] = the stored entries of slab s whose inner index lies in shard d's range, stored zeros included) and
+ * uploaded_bytes (one entry per shard; the AdaptiveVec form reports its compressed bytes). Any pointer may be NULL.
+ * SCANRS_ERR_ARGUMENT on a scanrs_multi that no inner-sharding constructor made. */
+int scanrs_multi_create_info(const scanrs_multi *mm, uint64_t *slab_bounds, uint64_t *moved, uint64_t *uploaded_bytes);
+/* The same plan from host arrays, no device: slab_bounds and bounds (world + 1 entries each: the slabs of the outer dimension, the
+ * shards of the inner one) and moved (world x world), validated as above. Any output may be NULL. */
+int scanrs_host_plan_inner(const uint64_t *indptr, const uint32_t *indices, uint64_t n_outer, uint64_t n_inner, uint32_t world,
+                           uint64_t *slab_bounds, uint64_t *bounds, uint64_t *moved);
+
 /* ---- measurement ------------------------------------------------------------------------- */
 
 /* Per-kernel-class HIP-event timing on the handle's stream (bench.py roofline leg). */
@@ -1086,6 +1123,11 @@ int scanrs_h5_matrix_removed(const scanrs_h5_matrix *m, const uint64_t **removed
  * barcodes / feature tables / removed set; free it with scanrs_h5_matrix_free. Needs a gfx950 device. */
 int scanrs_mat_create_from_file(const char *path, const char *retain_feature_like, int64_t shrink_row, scanrs_mat **out,
                                 scanrs_h5_matrix **meta);
+/* scanrs_mat_create_from_file's multi-GPU form (cmd.rs:61-70): read_adaptive_csr_matrix for a path ending in ".h5"
+ * (hdf5-io/src/matrix.rs:119-192), load_mtx otherwise (scan-rs/src/mtx.rs:10-51), then scanrs_multi_create_inner on the CSR arrays.
+ * `meta` (optional) as in scanrs_mat_create_from_file. */
+int scanrs_multi_create_from_file(const char *path, const char *retain_feature_like, int64_t shrink_row, uint32_t n_shards,
+                                  const int *devices, scanrs_multi **out, scanrs_h5_matrix **meta);
 
 /* `load_mtx` (scan-rs/src/mtx.rs:10-51): gzipped MatrixMarket coordinate file -> CSR arrays in the same handle type
  * (no string tables; scanrs_h5_matrix_arrays / _shape / _free apply). Comments '%', header "NROW NCOL NNZ", 1-based

@@ -507,6 +507,46 @@ class MultiMat {
         rows_ = r;
         cols_ = c;
     }
+    // Cell-sharded from feature-major input: the matrix in the reference's own orientation (genes x cells CSR, one vector per
+    // gene), its INNER dimension sharded over the devices. The result has the same rows x cols and the other storage flag and equals
+    // MultiMat(host-transposed triplet) bit for bit; nothing is transposed on the host, every nonzero is uploaded once.
+    // scanrs_multi_create_inner (AdaptiveMat::from_csmat, sqz/src/mat.rs:92-124)
+    static MultiMat from_csmat_inner(size_t rows, size_t cols, int storage, const uint64_t *indptr, const uint32_t *indices, const uint32_t *values,
+                                     uint32_t n_shards, const int *devices = nullptr) {
+        scanrs_multi *h = nullptr;
+        check(scanrs_multi_create_inner(rows, cols, storage, indptr, indices, values, n_shards, devices, &h));
+        return MultiMat(h);
+    }
+    // scanrs_multi_create_adaptive_inner (AdaptiveMat::new(rows, cols, storage, Vec<AdaptiveVec>), mat.rs:68-90): one entry per outer vector
+    static MultiMat from_adaptive_vecs_inner(size_t rows, size_t cols, int storage, const scanrs_adaptive_vec *vecs, size_t n_vecs, uint32_t n_shards,
+                                             const int *devices = nullptr) {
+        scanrs_multi *h = nullptr;
+        check(scanrs_multi_create_adaptive_inner(rows, cols, storage, vecs, n_vecs, n_shards, devices, &h));
+        return MultiMat(h);
+    }
+    // scanrs_multi_create_from_file (cmd.rs:61-70): read_adaptive_csr_matrix for ".h5" (hdf5-io/src/matrix.rs:119-192), load_mtx otherwise (mtx.rs:10-51)
+    static MultiMat from_file(const std::string &path, uint32_t n_shards, const int *devices = nullptr, const char *retain_feature_like = nullptr,
+                              int64_t shrink_row = -1) {
+        scanrs_multi *h = nullptr;
+        check(scanrs_multi_create_from_file(path.c_str(), retain_feature_like, shrink_row, n_shards, devices, &h, nullptr));
+        return MultiMat(h);
+    }
+    uint32_t n_shards() const {
+        uint32_t n = 0;
+        check(scanrs_multi_n_shards(h_, &n));
+        return n;
+    }
+    // what an inner-sharding constructor did (scanrs_multi_create_info): the slabs of the outer vectors, moved[s * n + d] = stored entries
+    // of slab s in shard d's range, bytes uploaded per shard. Error on a MultiMat that no such constructor made.
+    struct CreateInfo {
+        std::vector<uint64_t> slab_bounds, moved, uploaded_bytes;
+    };
+    CreateInfo create_info() const {
+        const uint32_t n = n_shards();
+        CreateInfo c{std::vector<uint64_t>(n + 1), std::vector<uint64_t>((size_t)n * n), std::vector<uint64_t>(n)};
+        check(scanrs_multi_create_info(h_, c.slab_bounds.data(), c.moved.data(), c.uploaded_bytes.data()));
+        return c;
+    }
     MultiMat(const MultiMat &) = delete;
     MultiMat &operator=(const MultiMat &) = delete;
     MultiMat(MultiMat &&o) noexcept : h_(o.h_), rows_(o.rows_), cols_(o.cols_) { o.h_ = nullptr; }
@@ -589,6 +629,17 @@ inline MultiMat::Partition MultiMat::partition_on_thresholds(const double *row_t
 }
 inline MultiMat::Partition MultiMat::partition_on_threshold(double threshold) const { return partition_on_thresholds(&threshold, &threshold); }
 
+// scanrs_host_plan_inner (host only, no device): the plan of the inner-sharding constructors for a feature-major triplet
+struct InnerPlan {
+    std::vector<uint64_t> slab_bounds, bounds, moved; // world + 1, world + 1, world x world
+};
+inline InnerPlan host_plan_inner(const uint64_t *indptr, const uint32_t *indices, uint64_t n_outer, uint64_t n_inner, uint32_t world) {
+    InnerPlan p{std::vector<uint64_t>(world + 1), std::vector<uint64_t>(world + 1), std::vector<uint64_t>((size_t)world * world + 1)};
+    check(scanrs_host_plan_inner(indptr, indices, n_outer, n_inner, world, p.slab_bounds.data(), p.bounds.data(), p.moved.data()));
+    p.moved.resize((size_t)world * world);
+    return p;
+}
+
 // ---- hdf5-io crate (hdf5-io/src/matrix.rs, analysis.rs): 10x files -> host arrays, parsed by the library itself ----
 namespace hdf5_io {
 static const char *const FEATURE_TYPE_GENE_EXPRESSION = "Gene Expression"; // matrix.rs:14
@@ -603,6 +654,10 @@ struct FeatureBarcodeMatrix {
     std::vector<uint32_t> indices, values;
     std::vector<uint64_t> removed_features; // ascending (the BTreeSet of the reference)
     AdaptiveMat to_device() const { return AdaptiveMat::from_csmat(rows, cols, storage, indptr.data(), indices.data(), values.data()); }
+    // over n_shards devices with the barcodes sharded (MultiMat::from_csmat_inner: the matrix is feature-major, its inner dimension is cut)
+    MultiMat to_devices(uint32_t n_shards, const int *devices = nullptr) const {
+        return MultiMat::from_csmat_inner(rows, cols, (int)storage, indptr.data(), indices.data(), values.data(), n_shards, devices);
+    }
 };
 
 namespace detail {

@@ -194,6 +194,39 @@ class AdaptiveVecDesc(ctypes.Structure):
                 ("n_block_starts", ctypes.c_uint64)]
 
 
+def _adaptive_table(vecs):
+    """The `scanrs_adaptive_vec` table of one mapping per outer vector (see `AdaptiveMat.from_adaptive_vecs`): (n, table, arrays
+    that must outlive the call)."""
+    n = len(vecs)
+    table = (AdaptiveVecDesc * max(n, 1))()
+    keep = []  # arrays must outlive the call
+
+    def arr(a, dt):
+        if a is None:
+            return None, 0
+        a = np.ascontiguousarray(a, dtype=dt)
+        keep.append(a)
+        return a.ctypes.data_as(ctypes.c_void_p), a.shape[0]
+
+    for i, v in enumerate(vecs):
+        d = table[i]
+        d.kind, d.len, d.n_units = int(v["kind"]), int(v["len"]), int(v["n_units"])
+        data = v.get("data")
+        if data is not None:
+            data = np.ascontiguousarray(data)
+            keep.append(data)
+            d.data, d.data_bytes = data.ctypes.data_as(ctypes.c_void_p), data.nbytes
+        fi, nfi = arr(v.get("fallback_indexes"), np.uint32)
+        fv, nfv = arr(v.get("fallback_values"), np.uint32)
+        if nfi != nfv:
+            raise ScanrsError(6, "fallback indexes / values differ in length")
+        d.fallback_indexes, d.fallback_values, d.n_fallback = fi, fv, nfi
+        ib, _ = arr(v.get("index_bytes"), np.uint8)
+        bs, nbs = arr(v.get("block_starts"), np.uint32)
+        d.index_bytes, d.block_starts, d.n_block_starts = ib, bs, nbs
+    return n, table, keep
+
+
 class AdaptiveMat:
     """Device-resident `sqz::AdaptiveMat<N, D, M>` (sqz/src/mat.rs:34-42). Once a low-rank
     offset is installed (`center`, `scale_and_center`, `normalize`) the same object plays
@@ -226,33 +259,7 @@ class AdaptiveMat:
         """`AdaptiveMat::new(rows, cols, storage, Vec<AdaptiveVec>)` (mat.rs:68-90): `vecs` is one mapping per outer
         vector with the fields of `scanrs_adaptive_vec` (kind, len, n_units, data, fallback_indexes, fallback_values,
         index_bytes, block_starts) holding numpy arrays in the reference's in-memory layout; decoded on the device."""
-        n = len(vecs)
-        table = (AdaptiveVecDesc * max(n, 1))()
-        keep = []  # arrays must outlive the call
-
-        def arr(a, dt):
-            if a is None:
-                return None, 0
-            a = np.ascontiguousarray(a, dtype=dt)
-            keep.append(a)
-            return a.ctypes.data_as(ctypes.c_void_p), a.shape[0]
-
-        for i, v in enumerate(vecs):
-            d = table[i]
-            d.kind, d.len, d.n_units = int(v["kind"]), int(v["len"]), int(v["n_units"])
-            data = v.get("data")
-            if data is not None:
-                data = np.ascontiguousarray(data)
-                keep.append(data)
-                d.data, d.data_bytes = data.ctypes.data_as(ctypes.c_void_p), data.nbytes
-            fi, nfi = arr(v.get("fallback_indexes"), np.uint32)
-            fv, nfv = arr(v.get("fallback_values"), np.uint32)
-            if nfi != nfv:
-                raise ScanrsError(6, "fallback indexes / values differ in length")
-            d.fallback_indexes, d.fallback_values, d.n_fallback = fi, fv, nfi
-            ib, _ = arr(v.get("index_bytes"), np.uint8)
-            bs, nbs = arr(v.get("block_starts"), np.uint32)
-            d.index_bytes, d.block_starts, d.n_block_starts = ib, bs, nbs
+        n, table, _keep = _adaptive_table(vecs)
         h = ctypes.c_void_p()
         _check(_lib.scanrs_mat_create_adaptive(ctypes.c_uint64(rows), ctypes.c_uint64(cols), ctypes.c_int(storage), table,
                                               ctypes.c_uint64(n), ctypes.byref(h)))
@@ -1166,6 +1173,76 @@ class MultiMat:
         self.rows, self.cols, self.storage, self.n_shards = int(r.value), int(c.value), int(st.value), int(n.value)
         return self
 
+    @staticmethod
+    def _devices_arg(n_shards: int, devices):
+        if devices is None:
+            return None
+        devices = [int(d) for d in devices]
+        if len(devices) != int(n_shards):
+            raise ScanrsError(6, "one device id per shard is required")
+        return (ctypes.c_int * max(len(devices), 1))(*devices)
+
+    @classmethod
+    def from_csmat_inner(cls, rows, cols, storage, indptr, indices, data, n_shards: int, devices=None) -> "MultiMat":
+        """`scanrs_multi_create_inner`: the matrix in the reference's own orientation (genes x cells CSR, mat.rs:68-124),
+        its INNER dimension sharded over the devices. The result has the same rows x cols and the OTHER storage flag (cells sharded),
+        and equals `MultiMat` of the host-transposed triplet bit for bit; nothing is transposed on the host and every nonzero is
+        uploaded once. `devices` may repeat an id."""
+        ip = np.ascontiguousarray(indptr, dtype=np.uint64)
+        ix = np.ascontiguousarray(indices, dtype=np.uint32)
+        vv = np.ascontiguousarray(data, dtype=np.uint32)
+        n_outer = rows if storage == CSR else cols
+        if ip.shape[0] != n_outer + 1:
+            raise ScanrsError(6, "indptr length does not match the outer dimension")
+        if ix.shape[0] != vv.shape[0] or int(ip[-1]) != ix.shape[0]:
+            raise ScanrsError(6, "indices/data length does not match indptr")
+        h = ctypes.c_void_p()
+        _check(_lib.scanrs_multi_create_inner(ctypes.c_uint64(rows), ctypes.c_uint64(cols), ctypes.c_int(storage), _p(ip), _p(ix), _p(vv),
+                                              ctypes.c_uint32(n_shards), cls._devices_arg(n_shards, devices), ctypes.byref(h)))
+        return cls._from_handle(h.value)
+
+    @classmethod
+    def from_adaptive_vecs_inner(cls, rows, cols, storage, vecs, n_shards: int, devices=None) -> "MultiMat":
+        """`scanrs_multi_create_adaptive_inner`: the same from the mappings `AdaptiveMat.from_adaptive_vecs` takes, one per outer
+        vector (mat.rs:68-90; what read_adaptive_csr_matrix holds, hdf5-io/src/matrix.rs:119-192). The compressed buffers of a slab are
+        uploaded and expanded on its device."""
+        n, table, _keep = _adaptive_table(vecs)
+        h = ctypes.c_void_p()
+        _check(_lib.scanrs_multi_create_adaptive_inner(ctypes.c_uint64(rows), ctypes.c_uint64(cols), ctypes.c_int(storage), table, ctypes.c_uint64(n),
+                                                       ctypes.c_uint32(n_shards), cls._devices_arg(n_shards, devices), ctypes.byref(h)))
+        return cls._from_handle(h.value)
+
+    @classmethod
+    def from_file(cls, path, n_shards: int, devices=None, retain_feature_like=None, shrink_row=None) -> "MultiMat":
+        """`scanrs_multi_create_from_file` (cmd.rs:61-70): a 10x `.h5` through `read_adaptive_csr_matrix`, anything else through
+        `load_mtx`, then `from_csmat_inner` on the CSR arrays: genes x cells, CSC, the cells sharded."""
+        h = ctypes.c_void_p()
+        rfl = None if retain_feature_like is None else str(retain_feature_like).encode()
+        _check(_lib.scanrs_multi_create_from_file(str(path).encode(), rfl, ctypes.c_int64(-1 if shrink_row is None else int(shrink_row)),
+                                                  ctypes.c_uint32(n_shards), cls._devices_arg(n_shards, devices), ctypes.byref(h), None))
+        return cls._from_handle(h.value)
+
+    def create_info(self) -> dict:
+        """`scanrs_multi_create_info`: what the inner-sharding constructor did. slab_bounds (n_shards + 1: the outer vectors every
+        shard uploaded), moved (n_shards x n_shards: stored entries of slab s that lie in shard d's range, stored zeros included) and
+        uploaded_bytes per shard. ScanrsError on a MultiMat that no such constructor made."""
+        n = self.n_shards
+        sb, mv, up = np.zeros(n + 1, dtype=np.uint64), np.zeros((n, n), dtype=np.uint64), np.zeros(n, dtype=np.uint64)
+        _check(_lib.scanrs_multi_create_info(self._h, _p(sb), _p(mv), _p(up)))
+        return {"slab_bounds": sb, "moved": mv, "uploaded_bytes": up}
+
+    def shard_csmat(self, i: int):
+        """`scanrs_mat_to_csmat` of shard i: (indptr u64, indices u32, data u32) of its own outer vectors."""
+        h = ctypes.c_void_p()
+        _check(_lib.scanrs_multi_shard(self._h, ctypes.c_uint32(i), ctypes.byref(h), None, None, None))
+        r, c, nnz = ctypes.c_uint64(), ctypes.c_uint64(), ctypes.c_uint64()
+        _check(_lib.scanrs_mat_shape(h, ctypes.byref(r), ctypes.byref(c)))
+        _check(_lib.scanrs_mat_nnz(h, ctypes.byref(nnz)))
+        indptr = np.zeros((r.value if self.storage == CSR else c.value) + 1, dtype=np.uint64)
+        indices, data = np.zeros(nnz.value, dtype=np.uint32), np.zeros(nnz.value, dtype=np.uint32)
+        _check(_lib.scanrs_mat_to_csmat(h, _p(indptr), _p(indices), _p(data)))
+        return indptr, indices, data
+
     def shape(self):
         """[rows, cols] of the whole matrix (`scanrs_multi_shape`)."""
         r, c = ctypes.c_uint64(), ctypes.c_uint64()
@@ -1504,6 +1581,22 @@ def plan_shards(indptr, world: int) -> np.ndarray:
 
 
 # host-side dense helpers (checked by the CPU test-suite)
+def host_plan_inner(indptr, indices, n_inner: int, world: int):
+    """`scanrs_host_plan_inner` (host only, no device): the plan of the inner-sharding constructors for a feature-major triplet.
+    Returns (slab_bounds, bounds, moved): the slabs of the outer vectors, the shard ranges of the inner dimension (world + 1
+    entries each) and the world x world table of stored entries of slab s that lie in shard d's range."""
+    ip = np.ascontiguousarray(indptr, dtype=np.uint64)
+    ix = np.ascontiguousarray(indices, dtype=np.uint32)
+    if ip.shape[0] < 1 or int(ip[-1]) != ix.shape[0]:
+        raise ScanrsError(6, "indices length does not match indptr")
+    world = int(world)
+    sb, bd = np.zeros(max(world, 0) + 1, dtype=np.uint64), np.zeros(max(world, 0) + 1, dtype=np.uint64)
+    mv = np.zeros((max(world, 1), max(world, 1)), dtype=np.uint64)
+    _check(_lib.scanrs_host_plan_inner(_p(ip), _p(ix), ctypes.c_uint64(ip.shape[0] - 1), ctypes.c_uint64(n_inner), ctypes.c_uint32(world),
+                                       _p(sb), _p(bd), _p(mv)))
+    return sb, bd, mv
+
+
 def host_chol_upper(g):
     g = _f64(g).copy()
     _check(_lib.scanrs_host_chol_upper(_p(g), ctypes.c_int(g.shape[0])))
@@ -1543,7 +1636,7 @@ EXPORTED_SYMBOLS = [
     "scanrs_pca_bk", "scanrs_pca_rand", "scanrs_pca_irlba", "scanrs_pca_result_device", "scanrs_knn_device", "scanrs_knn_sharded", "scanrs_multi_knn", "scanrs_host_knn_merge", "scanrs_omega_fill", "scanrs_mat_set_shard", "scanrs_mat_set_shard_comm", "scanrs_comm_get_unique_id", "scanrs_comm_create", "scanrs_comm_free",
     "scanrs_multi_create", "scanrs_multi_free", "scanrs_multi_n_shards", "scanrs_multi_shard", "scanrs_multi_normalize", "scanrs_multi_pca_bk", "scanrs_multi_pca_rand", "scanrs_multi_pca_irlba", "scanrs_multi_log_normalize", "scanrs_multi_sseq_params", "scanrs_multi_group_sums", "scanrs_multi_sseq_de", "scanrs_multi_comm_info",
     "scanrs_sseq_de_pairs_sharded", "scanrs_merge_clusters_sharded", "scanrs_cluster_medoids_sharded", "scanrs_multi_sseq_de_pairs", "scanrs_multi_merge_clusters", "scanrs_multi_cluster_medoids",
-    "scanrs_plan_shards", "scanrs_profile_enable", "scanrs_profile_reset", "scanrs_profile_get", "scanrs_mat_sync", "scanrs_mat_set_spmm_path", "scanrs_mat_set_option", "scanrs_set_global_option", "scanrs_mat_set_panel_precision",
+    "scanrs_plan_shards", "scanrs_multi_create_inner", "scanrs_multi_create_adaptive_inner", "scanrs_multi_create_from_file", "scanrs_multi_create_info", "scanrs_host_plan_inner", "scanrs_profile_enable", "scanrs_profile_reset", "scanrs_profile_get", "scanrs_mat_sync", "scanrs_mat_set_spmm_path", "scanrs_mat_set_option", "scanrs_set_global_option", "scanrs_mat_set_panel_precision",
     "scanrs_mat_chol_rinv", "scanrs_mat_get_counter", "scanrs_host_chol_upper", "scanrs_host_inv_upper", "scanrs_host_sym_eig", "scanrs_host_sym_eig_topk", "scanrs_debug_wait_never", "scanrs_debug_barrier_alone", "scanrs_debug_arena_selftest", "scanrs_debug_dense_route", "scanrs_debug_dense_gram", "scanrs_debug_dense_gemm", "scanrs_debug_weighted_colsum", "scanrs_debug_knn_filter", "scanrs_debug_knn_last_stats", "scanrs_debug_knn_filter_params", "scanrs_init", "scanrs_release_cached_memory", "scanrs_cached_memory_bytes", "scanrs_reserve_device_memory", "scanrs_device_memory_in_use",
     "scanrs_h5_read_csc_matrix", "scanrs_h5_read_adaptive_csr_matrix", "scanrs_h5_read_matrix_metadata", "scanrs_h5_matrix_free",
     "scanrs_h5_matrix_shape", "scanrs_h5_matrix_arrays", "scanrs_h5_matrix_n_strings", "scanrs_h5_matrix_string", "scanrs_h5_matrix_removed",

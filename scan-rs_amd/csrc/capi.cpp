@@ -216,7 +216,7 @@ static std::shared_ptr<DevBuf<double>> upload_vec(Storage &st, const double *h, 
     return b;
 }
 
-static std::shared_ptr<Storage> new_storage(uint64_t rows, uint64_t cols, int storage) {
+std::shared_ptr<Storage> new_storage(uint64_t rows, uint64_t cols, int storage) {
     auto st = std::make_shared<Storage>();
     registry_add(st.get());
     st->rows = rows;
@@ -1486,7 +1486,16 @@ int scanrs_mat_get_counter(scanrs_mat *m, const char *key, uint64_t *value) {
             *value = m->st->knn_allreduces;
         else if (k == "subset_allreduces") // the exchange steps of the last sharded sum over a column list (an unsharded handle: 0)
             *value = m->st->subset_allreduces;
-        else if (k == "t_layout_us") // first-call accounting: host time of the calling thread in tile layout builds ...
+        else if (k.rfind("reshard_", 0) == 0 && k.size() > 11 && k.compare(k.size() - 3, 3, "_us") == 0) {
+            // a shard made by an inner-sharding constructor (multi.cpp): wall clock of its thread in the phases upload, count (validation
+            // and the histogram), split, exchange, transpose
+            static const char *const phases[5] = {"upload", "count", "split", "exchange", "transpose"};
+            int which = -1;
+            for (int i = 0; i < 5; i++)
+                if (k == std::string("reshard_") + phases[i] + "_us") which = i;
+            if (which < 0) fail(SCANRS_ERR_ARGUMENT, "unknown counter '%s'", key);
+            *value = m->st->reshard_us[which];
+        } else if (k == "t_layout_us") // first-call accounting: host time of the calling thread in tile layout builds ...
             *value = m->st->t_layout_us;
         else if (k == "t_side_wait_us") // ... waiting for the helper thread that builds the second orientation
             *value = m->st->t_side_wait_us;

@@ -403,6 +403,7 @@ struct Storage {
     uint64_t partition_rounds = 0;        // rounds of the last scanrs_mat_partition_on_thresholds on this handle, the final one that changes nothing included (scanrs_mat_get_counter)
     uint64_t de_shard_tests = 0, de_shard_allreduces = 0; // the last DE call on this handle: tests this rank launched on the device, exchange steps (scanrs_mat_get_counter)
     uint64_t de_pairs_passes = 0, de_pairs_literal = 0; // the last scanrs_sseq_de_pairs on this handle: passes over the nonzeros, pairs on the literal route (scanrs_mat_get_counter)
+    uint64_t reshard_us[5] = {0, 0, 0, 0, 0}; // a shard of scanrs_multi_create_inner and kin: its thread's wall clock in upload, count, split, exchange, transpose (scanrs_mat_get_counter)
     int subset_scatter = 1;               // integer sums over a column list when only the other orientation exists: 1 = scattered into the result with 64-bit integer atomics from the copy that exists, 0 = the missing copy is built (subset_host.cpp)
     uint64_t subset_masked_passes = 0, subset_scatter_passes = 0; // sums over a column list made so far on this handle: from the copy whose outer dimension is the result axis / through the integer scatter (scanrs_mat_get_counter)
     uint64_t knn_blocks = 0, knn_allreduces = 0; // the last scanrs_knn_sharded on this handle: blocks of the point set searched, exchange steps (an unsharded one: 0)
@@ -647,7 +648,7 @@ void knn_filter_debug(const double *queries, uint64_t n_q, const double *points,
                       uint32_t *cnt, uint32_t *cand);
 // decode.hip
 uint64_t decode_adaptive_vectors(const scanrs_adaptive_vec *vecs, uint64_t n_vecs, uint64_t vec_len, DevBuf<uint64_t> &indptr,
-                                 DevBuf<uint32_t> &indices, DevBuf<uint32_t> &values);
+                                 DevBuf<uint32_t> &indices, DevBuf<uint32_t> &values, uint64_t *uploaded_bytes = nullptr);
 // encode.hip: the encoders (the inverse direction). One entry per outer vector: its encoding, stored entries and fallback entries;
 // byte_off / word_off (n_outer + 1 entries) place its pieces in the two device arenas: `data` (padded to 8 bytes), then index_bytes
 // (S*) in d_bytes; fallback indexes, fallback values, then block_starts (S*) in d_words.
@@ -658,6 +659,21 @@ struct EncodedVec {      // written by the plan kernel, read by the emit kernels
 };
 void encode_adaptive_vectors(Storage &st, const SparseCopy &cp, int force_kind, std::vector<EncodedVec> &vecs, std::vector<uint64_t> &byte_off,
                              std::vector<uint64_t> &word_off, DevBuf<uint64_t> &d_bytes, DevBuf<uint32_t> &d_words);
+// reshard.hip / reshard_host.cpp: the inner-sharding constructors of multi.cpp. A slab: a run of the caller's outer vectors.
+void launch_reshard_count(hipStream_t s, const SparseCopy &slab, uint32_t *d_counts); // d_counts[j] += stored entries at inner position j (zeroed by the caller)
+// d_start ((world + 1) x slab.n_outer): where destination d's run of every vector begins; d_moved[d] += the runs' lengths (zeroed by the caller)
+void launch_reshard_split(hipStream_t s, const SparseCopy &slab, const uint64_t *d_bounds, uint32_t world, uint64_t *d_start,
+                          unsigned long long *d_moved);
+// the destination's side, reading a source's slab in place: rows d / d + 1 of its start table, the kept entries per run, then the copy
+void launch_reshard_len(hipStream_t s, const uint64_t *d_from, const uint64_t *d_to, const uint32_t *d_values, uint64_t n_vec, bool has_zeros,
+                        unsigned long long *d_len);
+void launch_reshard_pull(hipStream_t s, const uint64_t *d_from, const uint64_t *d_to, const uint32_t *d_indices, const uint32_t *d_values,
+                         uint64_t n_vec, uint32_t rebase, const uint64_t *d_out_ptr, uint32_t *d_out_idx, uint32_t *d_out_val);
+void reshard_check_frame(uint64_t n_outer, uint64_t n_inner, const uint64_t *indptr, const uint32_t *indices, bool values_given);
+void reshard_host_plan(const uint64_t *indptr, const uint32_t *indices, uint64_t n_outer, uint64_t n_inner, uint32_t world, uint64_t *slab_bounds,
+                       uint64_t *bounds, uint64_t *moved);
+// capi.cpp: a registered Storage with its main stream on the current device (what every handle starts from)
+SCANRS_LOCAL std::shared_ptr<Storage> new_storage(uint64_t rows, uint64_t cols, int storage);
 // comm.cpp
 struct LocalGroup;
 void comm_allreduce(Storage &st, scanrs_comm *c, void *d, uint64_t count, int dtype); // dtype 0 = f64, 1 = u64; on st.stream

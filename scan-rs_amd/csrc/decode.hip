@@ -187,9 +187,10 @@ static void upload(DevBuf<T> &dst, const std::vector<T> &src) {
 
 } // namespace
 
-// Expands the vectors into a device triplet (freshly allocated DevBufs). Returns the number of nonzeros.
+// Expands the vectors into a device triplet (freshly allocated DevBufs). Returns the number of nonzeros; uploaded_bytes (optional):
+// the bytes of the compressed buffers and their descriptors that were copied to the device.
 uint64_t decode_adaptive_vectors(const scanrs_adaptive_vec *vecs, uint64_t n_vecs, uint64_t vec_len, DevBuf<uint64_t> &indptr,
-                                 DevBuf<uint32_t> &indices, DevBuf<uint32_t> &values) {
+                                 DevBuf<uint32_t> &indices, DevBuf<uint32_t> &values, uint64_t *uploaded_bytes) {
     std::vector<AVDesc> desc(n_vecs);
     uint64_t n_bytes = 0, n_words = 0, n_chunks = 0;
     auto align8 = [](uint64_t x) { return (x + 7ull) & ~7ull; };
@@ -270,6 +271,7 @@ uint64_t decode_adaptive_vectors(const scanrs_adaptive_vec *vecs, uint64_t n_vec
     upload(d_desc, desc);
     upload(d_bytes, hb);
     upload(d_words, hw);
+    if (uploaded_bytes) *uploaded_bytes = desc.size() * sizeof(AVDesc) + hb.size() + hw.size() * 4; // everything that crosses the host link
     DevBuf<unsigned long long> counts, offs, bad;
     counts.alloc(n_chunks + 1);
     offs.alloc(n_chunks + 1);

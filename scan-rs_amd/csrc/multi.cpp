@@ -3,7 +3,8 @@
 // and run_pca once. Here the outer vectors are range-partitioned by nonzeros over `n_shards` devices, every shard is an
 // ordinary scanrs_mat handle on its own device driven by its own host thread for the duration of a call, and the
 // exchange steps go through the library's single-process group (comm.cpp). Several shards may share one device
-// (`devices` repeats an id): that is how a 1-GPU box exercises the whole path.
+// (`devices` repeats an id): that is how a 1-GPU box exercises the whole path. A matrix that arrives feature-major (the reference's
+// own orientation) is sharded over its INNER dimension by the constructors further down (scanrs_multi_create_inner).
 #include <functional>
 #include <thread>
 
@@ -17,6 +18,11 @@ struct scanrs_multi {
     std::vector<scanrs_mat *> shards;
     std::vector<scanrs_comm *> comms;
     std::shared_ptr<scanrs::LocalGroup> group;
+    // what an inner-sharding constructor did (scanrs_multi_create_info); null on every other scanrs_multi
+    struct InnerInfo {
+        std::vector<uint64_t> slab_bounds, moved, uploaded;
+    };
+    std::shared_ptr<InnerInfo> inner;
 };
 
 using namespace scanrs;
@@ -64,6 +70,38 @@ int fan_out(scanrs_multi *mm, F &&f) {
     return first;
 }
 
+int bad_argument(const char *msg) {
+    set_error("%s", msg);
+    return SCANRS_ERR_ARGUMENT;
+}
+
+// the devices of a new scanrs_multi (`devices` null: 0 .. n_shards-1; ids may repeat), peer access between every pair of distinct ones,
+// the group and one communicator per shard
+void bind_devices(scanrs_multi *mm, uint32_t n_shards, const int *devices) {
+    int n_dev = 0;
+    if (hipGetDeviceCount(&n_dev) != hipSuccess || n_dev <= 0) fail(SCANRS_ERR_DEVICE, "no gfx950 (MI355X) device is usable from this process");
+    for (uint32_t i = 0; i < n_shards; i++) {
+        const int d = devices ? devices[i] : (int)i;
+        if (d < 0 || d >= n_dev) fail(SCANRS_ERR_ARGUMENT, "device %d of shard %u does not exist (%d visible)", d, i, n_dev);
+        mm->devices.push_back(d);
+    }
+    // peer access between every pair of distinct devices (the one-shot all-reduce reads peers' partial sums in place)
+    for (uint32_t i = 0; i < n_shards; i++)
+        for (uint32_t j = 0; j < n_shards; j++) {
+            if (mm->devices[i] == mm->devices[j]) continue;
+            int can = 0;
+            SCANRS_HIP(hipDeviceCanAccessPeer(&can, mm->devices[i], mm->devices[j]));
+            if (!can) fail(SCANRS_ERR_DEVICE, "devices %d and %d cannot map each other's memory", mm->devices[i], mm->devices[j]);
+            SCANRS_HIP(hipSetDevice(mm->devices[i]));
+            const hipError_t e = hipDeviceEnablePeerAccess(mm->devices[j], 0);
+            if (e != hipSuccess && e != hipErrorPeerAccessAlreadyEnabled) SCANRS_HIP(e);
+            (void)hipGetLastError();
+        }
+    mm->group = local_group_make(n_shards);
+    mm->shards.assign(n_shards, nullptr);
+    for (uint32_t i = 0; i < n_shards; i++) mm->comms.push_back(comm_make_local(mm->group, i));
+}
+
 } // namespace
 
 extern "C" {
@@ -75,35 +113,14 @@ int scanrs_multi_create(uint64_t rows, uint64_t cols, int storage, const uint64_
         *out = nullptr;
         if (!indptr || n_shards == 0 || n_shards > 16) fail(SCANRS_ERR_ARGUMENT, "1 <= n_shards <= 16 and a triplet are required");
         if (storage != SCANRS_CSR && storage != SCANRS_CSC) fail(SCANRS_ERR_ARGUMENT, "storage must be 0 (CSR) or 1 (CSC)");
-        int n_dev = 0;
-        if (hipGetDeviceCount(&n_dev) != hipSuccess || n_dev <= 0) fail(SCANRS_ERR_DEVICE, "no gfx950 (MI355X) device is usable from this process");
         auto mm = std::make_unique<scanrs_multi>();
         mm->rows = rows;
         mm->cols = cols;
         mm->storage = storage;
-        for (uint32_t i = 0; i < n_shards; i++) {
-            const int d = devices ? devices[i] : (int)i;
-            if (d < 0 || d >= n_dev) fail(SCANRS_ERR_ARGUMENT, "device %d of shard %u does not exist (%d visible)", d, i, n_dev);
-            mm->devices.push_back(d);
-        }
+        bind_devices(mm.get(), n_shards, devices);
         const uint64_t n_outer = storage == SCANRS_CSR ? rows : cols;
         mm->bounds.resize(n_shards + 1);
         if (scanrs_plan_shards(indptr, n_outer, n_shards, mm->bounds.data()) != SCANRS_OK) throw Failure{SCANRS_ERR_ARGUMENT};
-        // peer access between every pair of distinct devices (the one-shot all-reduce reads peers' partial sums in place)
-        for (uint32_t i = 0; i < n_shards; i++)
-            for (uint32_t j = 0; j < n_shards; j++) {
-                if (mm->devices[i] == mm->devices[j]) continue;
-                int can = 0;
-                SCANRS_HIP(hipDeviceCanAccessPeer(&can, mm->devices[i], mm->devices[j]));
-                if (!can) fail(SCANRS_ERR_DEVICE, "devices %d and %d cannot map each other's memory", mm->devices[i], mm->devices[j]);
-                SCANRS_HIP(hipSetDevice(mm->devices[i]));
-                const hipError_t e = hipDeviceEnablePeerAccess(mm->devices[j], 0);
-                if (e != hipSuccess && e != hipErrorPeerAccessAlreadyEnabled) SCANRS_HIP(e);
-                (void)hipGetLastError();
-            }
-        mm->group = local_group_make(n_shards);
-        mm->shards.assign(n_shards, nullptr);
-        for (uint32_t i = 0; i < n_shards; i++) mm->comms.push_back(comm_make_local(mm->group, i));
         scanrs_multi *raw = mm.get();
         const int rc = fan_out(raw, [&](size_t i) {
             const uint64_t lo = raw->bounds[i], hi = raw->bounds[i + 1];
@@ -126,6 +143,298 @@ int scanrs_multi_create(uint64_t rows, uint64_t cols, int storage, const uint64_
         set_error("internal error: %s", e.what());
         return SCANRS_ERR_DEVICE;
     }
+}
+
+// ---- the inner-sharding constructors (mat.rs:68-124, hdf5-io/src/matrix.rs:119-192, mtx.rs:10-51, cmd.rs:61-70) -----------
+// The matrix arrives in the reference's orientation (genes x cells CSR: one vector per gene) and the shards of the result own ranges of
+// its INNER dimension (the cells), stored the other way round. Nothing is transposed on the host and every nonzero is uploaded once:
+//   1  the outer vectors are dealt in n_shards slabs by nonzeros; shard s uploads slab s, validates it (validate_copy, before any
+//      kernel indexes by an inner index) and counts its stored entries per inner position;
+//   2  the counts are summed on the host, scanned, and scanrs_plan_shards gives `bounds`: exactly what scanrs_multi_create plans for
+//      the transposed triplet; every shard then finds, per vector and destination, the run of entries that belongs to it
+//      (launch_reshard_split: indices ascend inside a vector, so a run lies between two lower bounds);
+//   3  every destination reads its runs out of every source's slab in slab order (in place: the same device's memory, or a peer's
+//      through the peer mapping), the index rebased and stored zeros dropped: the CSR of ALL outer vectors x its own inner range;
+//   4  the slabs are released, and build_transposed_copy (stable: inner indices ascend) makes the shard's stored orientation.
+// The phases are separate fan_outs: the join of the shard threads is the barrier between them, and a failing shard ends its phase.
+} // extern "C"
+
+namespace {
+
+struct InnerShard { // what shard s holds on its device while the constructor runs
+    SparseCopy slab; // its slab as uploaded: slab.n_outer vectors over all n_inner positions, stored zeros still in
+    uint64_t zeros = 0;
+    DevBuf<uint32_t> counts;
+    std::vector<uint32_t> h_counts;
+    DevBuf<uint64_t> start; // (n_shards + 1) x slab.n_outer (launch_reshard_split)
+    SparseCopy piece;       // all outer vectors x the shard's own inner range
+    void drop_slab() {
+        slab = SparseCopy();
+        counts.release();
+        start.release();
+    }
+};
+
+// wall clock of a phase on a shard's thread, added to Storage::reshard_us[which] (every phase ends on an idle stream)
+struct PhaseClock {
+    uint64_t &slot;
+    std::chrono::steady_clock::time_point t0 = std::chrono::steady_clock::now();
+    explicit PhaseClock(uint64_t &s) : slot(s) {}
+    ~PhaseClock() { slot += (uint64_t)std::chrono::duration<double, std::micro>(std::chrono::steady_clock::now() - t0).count(); }
+};
+
+// slab [lo, hi) of shard s onto the current device (the arrays of `slab`, nnz; n_outer / n_inner are set); `uploaded`: bytes that crossed the host link
+using SlabLoader = std::function<void(size_t s, uint64_t lo, uint64_t hi, Storage &st, SparseCopy &slab, uint64_t &uploaded)>;
+
+int create_inner(uint64_t rows, uint64_t cols, int storage, const std::vector<uint64_t> &slab_bounds, const SlabLoader &load, uint32_t n_shards,
+                 const int *devices, scanrs_multi **out) {
+    const uint64_t n_outer = storage == SCANRS_CSR ? rows : cols, n_inner = storage == SCANRS_CSR ? cols : rows;
+    const int out_storage = storage == SCANRS_CSR ? SCANRS_CSC : SCANRS_CSR; // the same rows x cols, stored the other way round
+    auto mm = std::make_unique<scanrs_multi>();
+    mm->rows = rows;
+    mm->cols = cols;
+    mm->storage = out_storage;
+    bind_devices(mm.get(), n_shards, devices);
+    mm->bounds.assign(n_shards + 1, 0);
+    mm->inner = std::make_shared<scanrs_multi::InnerInfo>();
+    scanrs_multi::InnerInfo &info = *mm->inner;
+    info.slab_bounds = slab_bounds;
+    info.moved.assign((size_t)n_shards * n_shards, 0);
+    info.uploaded.assign(n_shards, 0);
+    std::vector<InnerShard> work(n_shards);
+    scanrs_multi *raw = mm.get();
+    jump_tables_prefetch(); // as scanrs_mat_create does: the seeded start panel's tables, off the first PCA's path
+
+    // 1: upload, validate, count
+    int rc = fan_out(raw, [&](size_t s) {
+        return guard([&] {
+            need_device();
+            auto stp = new_storage(0, 0, out_storage); // (its shape is known once `bounds` is)
+            auto *h = new scanrs_mat();
+            h->st = stp;
+            raw->shards[s] = h; // from here on scanrs_multi_free takes the storage down
+            Storage &st = *h->st;
+            CurrentHandle cur(&st);
+            InnerShard &w = work[s];
+            w.slab.n_outer = slab_bounds[s + 1] - slab_bounds[s];
+            w.slab.n_inner = n_inner;
+            {
+                PhaseClock clock(st.reshard_us[0]);
+                load(s, slab_bounds[s], slab_bounds[s + 1], st, w.slab, info.uploaded[s]);
+            }
+            PhaseClock clock(st.reshard_us[1]);
+            uint64_t bad = 0;
+            validate_copy(st, w.slab, &w.zeros, &bad);
+            if (bad) fail(SCANRS_ERR_ARGUMENT, "indices must be in range and strictly ascending within each outer vector (%llu violations)", (unsigned long long)bad);
+            w.counts.alloc(std::max<uint64_t>(1, n_inner));
+            SCANRS_HIP(hipMemsetAsync(w.counts.p, 0, std::max<uint64_t>(1, n_inner) * 4, st.stream));
+            launch_reshard_count(st.stream, w.slab, w.counts.p);
+            w.h_counts.assign(n_inner, 0);
+            if (n_inner) SCANRS_D2H(w.h_counts.data(), w.counts.p, n_inner * 4, st.stream);
+            SCANRS_SYNC(st.stream);
+            w.counts.release();
+        });
+    });
+
+    // the plan: the transposed indptr from the summed counts, cut as scanrs_multi_create would cut it
+    if (rc == SCANRS_OK)
+        rc = guard([&] {
+            std::vector<uint64_t> tip(n_inner + 1, 0);
+            for (uint32_t s = 0; s < n_shards; s++) {
+                const std::vector<uint32_t> &c = work[s].h_counts;
+                for (uint64_t j = 0; j < n_inner; j++) tip[j + 1] += c[j];
+                std::vector<uint32_t>().swap(work[s].h_counts);
+            }
+            for (uint64_t j = 0; j < n_inner; j++) tip[j + 1] += tip[j];
+            if (scanrs_plan_shards(tip.data(), n_inner, n_shards, raw->bounds.data()) != SCANRS_OK) throw Failure{SCANRS_ERR_ARGUMENT};
+        });
+
+    // 2: the runs of every (vector, destination)
+    if (rc == SCANRS_OK)
+        rc = fan_out(raw, [&](size_t s) {
+            return guard([&] {
+                Storage &st = *raw->shards[s]->st;
+                CurrentHandle cur(&st);
+                InnerShard &w = work[s];
+                PhaseClock clock(st.reshard_us[2]);
+                const uint64_t nv = w.slab.n_outer;
+                DevBuf<uint64_t> d_bounds(n_shards + 1), d_moved(n_shards);
+                SCANRS_HIP(hipMemcpyAsync(d_bounds.p, raw->bounds.data(), (n_shards + 1) * 8, hipMemcpyHostToDevice, st.stream));
+                SCANRS_HIP(hipMemsetAsync(d_moved.p, 0, n_shards * 8, st.stream));
+                w.start.alloc(std::max<uint64_t>(1, (uint64_t)(n_shards + 1) * nv));
+                launch_reshard_split(st.stream, w.slab, d_bounds.p, n_shards, w.start.p, reinterpret_cast<unsigned long long *>(d_moved.p));
+                SCANRS_D2H(&info.moved[s * n_shards], d_moved.p, n_shards * 8, st.stream);
+                SCANRS_SYNC(st.stream); // the table is complete before any destination reads it (the join below publishes it)
+            });
+        });
+
+    // 3: every destination gathers its runs from every slab, in slab order
+    if (rc == SCANRS_OK)
+        rc = fan_out(raw, [&](size_t d) {
+            return guard([&] {
+                Storage &st = *raw->shards[d]->st;
+                CurrentHandle cur(&st);
+                SparseCopy &pc = work[d].piece;
+                PhaseClock clock(st.reshard_us[3]);
+                const uint64_t lo = raw->bounds[d], hi = raw->bounds[d + 1];
+                pc.n_outer = n_outer;
+                pc.n_inner = hi - lo;
+                pc.indptr.alloc(n_outer + 1); // lengths, then (scanned in place) offsets
+                SCANRS_HIP(hipMemsetAsync(pc.indptr.p, 0, (n_outer + 1) * 8, st.stream));
+                for (uint32_t s = 0; s < n_shards; s++) {
+                    const InnerShard &src = work[s];
+                    const uint64_t nv = src.slab.n_outer;
+                    launch_reshard_len(st.stream, src.start.p + d * nv, src.start.p + (d + 1) * nv, src.slab.values.p, nv, src.zeros != 0,
+                                       reinterpret_cast<unsigned long long *>(pc.indptr.p + slab_bounds[s]));
+                }
+                select_scan_offsets(st.stream, reinterpret_cast<unsigned long long *>(pc.indptr.p), n_outer);
+                pc.nnz = SCANRS_D2H_VALUE(pc.indptr.p + n_outer, st.stream);
+                pc.indices.alloc(std::max<uint64_t>(1, pc.nnz));
+                pc.values.alloc(std::max<uint64_t>(1, pc.nnz));
+                for (uint32_t s = 0; s < n_shards && pc.nnz; s++) {
+                    const InnerShard &src = work[s];
+                    const uint64_t nv = src.slab.n_outer;
+                    launch_reshard_pull(st.stream, src.start.p + d * nv, src.start.p + (d + 1) * nv, src.slab.indices.p, src.slab.values.p, nv, (uint32_t)lo,
+                                        pc.indptr.p + slab_bounds[s], pc.indices.p, pc.values.p);
+                }
+                SCANRS_SYNC(st.stream); // nobody's slab is released before every destination has read it (the join below)
+            });
+        });
+
+    // 4: the slab goes, then the shard's stored orientation is built and bound
+    if (rc == SCANRS_OK)
+        rc = fan_out(raw, [&](size_t d) {
+            return guard([&] {
+                scanrs_mat *h = raw->shards[d];
+                Storage &st = *h->st;
+                CurrentHandle cur(&st);
+                InnerShard &w = work[d];
+                PhaseClock clock(st.reshard_us[4]);
+                w.drop_slab();
+                device_free_flush(); // the stream is idle here
+                SparseCopy &pc = w.piece;
+                pc.max_value = pc.nnz ? std::max(sseq_max_count(st, pc), 1u) : 0u; // sizes the sort keys of the transposition
+                if (pc.nnz) pc.build_items(st.stream);
+                build_transposed_copy(st, pc, st.primary);
+                w.piece = SparseCopy();
+                const uint64_t lo = raw->bounds[d], n_loc = raw->bounds[d + 1] - lo;
+                st.rows = out_storage == SCANRS_CSR ? n_loc : rows;
+                st.cols = out_storage == SCANRS_CSR ? cols : n_loc;
+                device_free_flush();
+                if (const int rc2 = scanrs_mat_set_shard_comm(h, raw->comms[d], (uint32_t)d, n_shards, lo, n_inner)) throw Failure{rc2};
+            });
+        });
+
+    // whatever is left of the temporaries goes back under the handle that made it (a failure; nothing after a success)
+    const std::string msg = rc == SCANRS_OK ? std::string() : std::string(scanrs_last_error());
+    for (uint32_t s = 0; s < n_shards; s++) {
+        (void)hipSetDevice(raw->devices[s]);
+        CurrentHandle cur(raw->shards[s] && raw->shards[s]->st ? raw->shards[s]->st.get() : nullptr, true);
+        work[s].drop_slab();
+        work[s].piece = SparseCopy();
+    }
+    if (rc != SCANRS_OK) {
+        scanrs_multi_free(mm.release());
+        set_error("%s", msg.c_str());
+        return rc;
+    }
+    *out = mm.release();
+    return SCANRS_OK;
+}
+
+// the checks every inner-sharding constructor inherits from scanrs_multi_create
+void check_inner_frame(uint32_t n_shards, int storage, scanrs_multi **out) {
+    if (!out) fail(SCANRS_ERR_ARGUMENT, "null output handle");
+    *out = nullptr;
+    if (n_shards == 0 || n_shards > 16) fail(SCANRS_ERR_ARGUMENT, "1 <= n_shards <= 16 and a triplet are required");
+    if (storage != SCANRS_CSR && storage != SCANRS_CSC) fail(SCANRS_ERR_ARGUMENT, "storage must be 0 (CSR) or 1 (CSC)");
+}
+
+} // namespace
+
+extern "C" {
+
+int scanrs_multi_create_inner(uint64_t rows, uint64_t cols, int storage, const uint64_t *indptr, const uint32_t *indices, const uint32_t *values,
+                              uint32_t n_shards, const int *devices, scanrs_multi **out) {
+    return guard([&] {
+        check_inner_frame(n_shards, storage, out);
+        const uint64_t n_outer = storage == SCANRS_CSR ? rows : cols, n_inner = storage == SCANRS_CSR ? cols : rows;
+        reshard_check_frame(n_outer, n_inner, indptr, indices, values != nullptr);
+        std::vector<uint64_t> sb(n_shards + 1);
+        if (scanrs_plan_shards(indptr, n_outer, n_shards, sb.data()) != SCANRS_OK) throw Failure{SCANRS_ERR_ARGUMENT};
+        const SlabLoader load = [&](size_t, uint64_t lo, uint64_t hi, Storage &st, SparseCopy &slab, uint64_t &uploaded) {
+            const uint64_t nv = hi - lo, z = indptr[hi] - indptr[lo];
+            std::vector<uint64_t> ip(nv + 1);
+            for (uint64_t o = lo; o <= hi; o++) ip[o - lo] = indptr[o] - indptr[lo];
+            slab.nnz = z;
+            slab.indptr.alloc(nv + 1);
+            slab.indices.alloc(std::max<uint64_t>(1, z));
+            slab.values.alloc(std::max<uint64_t>(1, z));
+            SCANRS_HIP(hipMemcpyAsync(slab.indptr.p, ip.data(), (nv + 1) * 8, hipMemcpyHostToDevice, st.stream));
+            if (z) {
+                SCANRS_HIP(hipMemcpyAsync(slab.indices.p, indices + indptr[lo], z * 4, hipMemcpyHostToDevice, st.stream));
+                SCANRS_HIP(hipMemcpyAsync(slab.values.p, values + indptr[lo], z * 4, hipMemcpyHostToDevice, st.stream));
+            }
+            SCANRS_SYNC(st.stream); // `ip` and the caller's (possibly pageable) arrays are done with
+            uploaded = 8 * z + 8 * (nv + 1);
+        };
+        if (const int rc = create_inner(rows, cols, storage, sb, load, n_shards, devices, out)) throw Failure{rc};
+    });
+}
+
+int scanrs_multi_create_adaptive_inner(uint64_t rows, uint64_t cols, int storage, const scanrs_adaptive_vec *vecs, uint64_t n_vecs, uint32_t n_shards,
+                                       const int *devices, scanrs_multi **out) {
+    return guard([&] {
+        check_inner_frame(n_shards, storage, out);
+        const uint64_t n_outer = storage == SCANRS_CSR ? rows : cols, n_inner = storage == SCANRS_CSR ? cols : rows;
+        if (n_outer > 0xFFFFFFFFull || n_inner > 0xFFFFFFFFull) fail(SCANRS_ERR_SHAPE, "dimensions must fit in u32 (AdaptiveVec limit)");
+        if (n_vecs != n_outer) fail(SCANRS_ERR_SHAPE, "one AdaptiveVec per outer vector is required");
+        if (n_vecs > 0 && !vecs) fail(SCANRS_ERR_ARGUMENT, "null vector table");
+        // the slabs are cut by the entries the vectors store (n_units: every field of a dense encoding, the entries of a sparse one);
+        // the nonzeros themselves are known only once a slab has been expanded on its device
+        std::vector<uint64_t> units(n_vecs + 1, 0), sb(n_shards + 1);
+        for (uint64_t i = 0; i < n_vecs; i++) units[i + 1] = units[i] + vecs[i].n_units;
+        if (scanrs_plan_shards(units.data(), n_vecs, n_shards, sb.data()) != SCANRS_OK) throw Failure{SCANRS_ERR_ARGUMENT};
+        const SlabLoader load = [&](size_t, uint64_t lo, uint64_t hi, Storage &, SparseCopy &slab, uint64_t &uploaded) {
+            slab.nnz = decode_adaptive_vectors(vecs + lo, hi - lo, n_inner, slab.indptr, slab.indices, slab.values, &uploaded);
+            ::scanrs::wait_device(__PRETTY_FUNCTION__, __FILE__, __LINE__); // the decoder works on the null stream
+        };
+        if (const int rc = create_inner(rows, cols, storage, sb, load, n_shards, devices, out)) throw Failure{rc};
+    });
+}
+
+int scanrs_multi_create_from_file(const char *path, const char *retain_feature_like, int64_t shrink_row, uint32_t n_shards, const int *devices,
+                                  scanrs_multi **out, scanrs_h5_matrix **meta) {
+    if (out) *out = nullptr;
+    if (meta) *meta = nullptr;
+    if (!path || !out) return bad_argument("null argument");
+    const size_t n = strlen(path);
+    const bool is_h5 = n > 3 && strcmp(path + n - 3, ".h5") == 0;
+    scanrs_h5_matrix *h = nullptr;
+    int rc = is_h5 ? scanrs_h5_read_adaptive_csr_matrix(path, retain_feature_like, shrink_row, &h) : scanrs_mtx_read(path, &h);
+    if (rc != SCANRS_OK) return rc;
+    uint64_t rows = 0, cols = 0, nnz = 0;
+    int storage = 0;
+    const uint64_t *ip = nullptr;
+    const uint32_t *ix = nullptr, *vv = nullptr;
+    (void)scanrs_h5_matrix_shape(h, &rows, &cols, &nnz, &storage);
+    (void)scanrs_h5_matrix_arrays(h, &ip, &ix, &vv);
+    rc = scanrs_multi_create_inner(rows, cols, storage, ip, ix, vv, n_shards, devices, out);
+    if (rc == SCANRS_OK && meta)
+        *meta = h;
+    else
+        scanrs_h5_matrix_free(h);
+    return rc;
+}
+
+int scanrs_multi_create_info(const scanrs_multi *mm, uint64_t *slab_bounds, uint64_t *moved, uint64_t *uploaded_bytes) {
+    if (!mm) return bad_argument("null handle");
+    if (!mm->inner) return bad_argument("create_info: this scanrs_multi was not made by an inner-sharding constructor (scanrs_multi_create_inner and kin)");
+    const scanrs_multi::InnerInfo &info = *mm->inner;
+    if (slab_bounds) std::copy(info.slab_bounds.begin(), info.slab_bounds.end(), slab_bounds);
+    if (moved) std::copy(info.moved.begin(), info.moved.end(), moved);
+    if (uploaded_bytes) std::copy(info.uploaded.begin(), info.uploaded.end(), uploaded_bytes);
+    return SCANRS_OK;
 }
 
 void scanrs_multi_free(scanrs_multi *mm) {
@@ -273,11 +582,6 @@ struct ShardView { // the handle a shard's DE call runs on: the shard itself, or
         if (owned && h) scanrs_mat_free(h);
     }
 };
-
-int bad_argument(const char *msg) {
-    set_error("%s", msg);
-    return SCANRS_ERR_ARGUMENT;
-}
 
 } // namespace
 

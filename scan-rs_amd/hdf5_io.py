@@ -8,7 +8,7 @@ from typing import List, Optional, Set, Tuple
 
 import numpy as np
 
-from . import CSC, CSR, AdaptiveMat, _check, _lib
+from . import CSC, CSR, AdaptiveMat, MultiMat, _check, _lib
 
 FEATURE_TYPE_GENE_EXPRESSION = "Gene Expression"  # matrix.rs:14
 
@@ -46,6 +46,11 @@ class FeatureBarcodeMatrix:
     def to_device(self) -> AdaptiveMat:
         """Upload as the `AdaptiveMat` the solvers take (needs a gfx950 device)."""
         return AdaptiveMat.from_csmat(self.rows, self.cols, self.storage, self.indptr, self.indices, self.values)
+
+    def to_devices(self, n_shards: int, devices=None) -> MultiMat:
+        """Upload as a `MultiMat` over `n_shards` devices with the barcodes sharded (`MultiMat.from_csmat_inner`: the matrix is
+        feature-major, so its inner dimension is cut; nothing is transposed on the host). `devices` may repeat an id."""
+        return MultiMat.from_csmat_inner(self.rows, self.cols, self.storage, self.indptr, self.indices, self.values, n_shards, devices)
 
 
 def _strings(h, what: int) -> List[str]:

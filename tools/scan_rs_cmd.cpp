@@ -3,6 +3,8 @@
 //   scan-rs-cmd INPUT.mtx[.gz] -o OUT_DIR -n {cellranger|cellranger8|seuratlog|binomialdeviance|binomialpearson} -d NUM_PCS
 // (INPUT may also be a 10x feature-barcode matrix .h5 — read through the hdf5-io mirror; the reference CLI takes mtx only)
 // writes svd_u.csv.gz, svd_d.csv.gz, svd_v.csv.gz exactly as cmd.rs:83-86 does.
+// --gpus N [--devices a,b,c]: the same run over N shards of one process (MultiMat, the barcodes sharded straight from the feature-major
+// file); device ids may repeat, the default is 0 .. N-1. Without --gpus nothing changes.
 #include <algorithm>
 #include <charconv>
 #include <cstdio>
@@ -37,6 +39,8 @@ static void array_to_csv(const double *a, size_t rows, size_t cols, const std::s
 int main(int argc, char **argv) {
     std::string input, out_dir = ".", norm = "cellranger";
     size_t num_pcs = 10;
+    bool multi = false;
+    std::string gpus_arg, devices_arg;
     for (int i = 1; i < argc; i++) {
         const std::string a = argv[i];
         auto next = [&]() -> std::string {
@@ -52,8 +56,13 @@ int main(int argc, char **argv) {
             norm = next();
         else if (a == "-d" || a == "--num_pcs")
             num_pcs = strtoull(next().c_str(), nullptr, 10);
+        else if (a == "--gpus") {
+            multi = true;
+            gpus_arg = next();
+        } else if (a == "--devices")
+            devices_arg = next();
         else if (a == "-h" || a == "--help") {
-            printf("scan-rs-cmd INPUT -o OUT_DIR -n NORMALIZATION -d NUM_PCS\n");
+            printf("scan-rs-cmd INPUT -o OUT_DIR -n NORMALIZATION -d NUM_PCS [--gpus N [--devices a,b,c]]\n");
             return 0;
         } else
             input = a;
@@ -62,8 +71,49 @@ int main(int argc, char **argv) {
         fprintf(stderr, "error: the following required arguments were not provided: <INPUT>\n");
         return 2;
     }
+    // --gpus N: 1 .. 16 shards; --devices: exactly N comma-separated ids (they may repeat)
+    std::vector<int> devices;
+    uint32_t n_shards = 0;
+    if (multi || !devices_arg.empty()) {
+        auto whole_number = [](const std::string &t, long &v) {
+            if (t.empty() || t.size() > 9 || t.find_first_not_of("0123456789") != std::string::npos) return false;
+            v = strtol(t.c_str(), nullptr, 10);
+            return true;
+        };
+        long n = 0;
+        if (!multi || !whole_number(gpus_arg, n) || n < 1 || n > 16) {
+            fprintf(stderr, "Error: --gpus takes a number of shards from 1 to 16%s\n", multi ? "" : " (--devices needs it)");
+            return 1;
+        }
+        n_shards = (uint32_t)n;
+        for (size_t at = 0; !devices_arg.empty() && at <= devices_arg.size();) {
+            const size_t comma = std::min(devices_arg.find(',', at), devices_arg.size());
+            long d = 0;
+            if (!whole_number(devices_arg.substr(at, comma - at), d)) {
+                fprintf(stderr, "Error: --devices takes comma-separated device ids, got '%s'\n", devices_arg.c_str());
+                return 1;
+            }
+            devices.push_back((int)d);
+            at = comma + 1;
+        }
+        if (!devices.empty() && devices.size() != n_shards) {
+            fprintf(stderr, "Error: --devices names %zu devices for --gpus %u\n", devices.size(), n_shards);
+            return 1;
+        }
+    }
     try {
         const Normalization normalization = normalization_from_str(norm);
+        if (multi) {
+            // load -> MultiMat with the barcodes sharded -> normalize -> BkSvd, every step on all shards at once
+            MultiMat mm = MultiMat::from_file(input, n_shards, devices.empty() ? nullptr : devices.data());
+            mkdir(out_dir.c_str(), 0777);
+            mm.normalize(normalization);
+            const PcaResult r = mm.run_pca(BkSvd(), num_pcs);
+            array_to_csv(r.u.data.data(), r.u.rows, r.u.cols, out_dir + "/svd_u.csv.gz");
+            array_to_csv(r.s.data(), num_pcs, 1, out_dir + "/svd_d.csv.gz");
+            array_to_csv(r.v.data.data(), r.v.rows, r.v.cols, out_dir + "/svd_v.csv.gz");
+            return 0;
+        }
         // extension over cmd.rs: a 10x feature-barcode .h5 is read the way diff-exp/src/utils.rs:42 reads it
         // (hdf5_io::matrix::read_adaptive_csr_matrix, all feature types, no count filter)
         const bool is_h5 = input.size() > 3 && input.compare(input.size() - 3, 3, ".h5") == 0;
