@@ -617,7 +617,9 @@ int scanrs_mat_set_spmm_path(scanrs_mat *m, int path);
  *                       walk the copy whose outer vectors are the summed-over axis — a table of the map at counts 1..8 per outer
  *                       vector instead of one logarithm per nonzero, sums scattered into LDS as 64-bit fixed point (order-
  *                       independent, so bit-reproducible). Taken when that copy exists and the matrix is large; 2: whenever
- *                       eligible; 0: never. Results agree with the ordinary pass to ~1e-13 relative.
+ *                       eligible; 0: never. Eligible is what scanrs_host_col_moments_plan accepts: then, for EVERY slice, sum and
+ *                       mean are within 1e-12 relative of the exact values and the variance within 1e-10 S2/m (S2 = the slice's sum
+ *                       of squares, m = the extent of the summed-over axis); every other map takes the ordinary pass.
  *   "device_factor" (1) svd_bk: the b x b Cholesky factors of CholeskyQR and the coefficient bookkeeping of qr(K) stay on the
  *                       device (no host round trip per orthonormalisation; falls back to the host path by itself when a
  *                       factorization does not converge within the queued passes); 0: host factorizations
@@ -1089,6 +1091,27 @@ int scanrs_knn_sharded(scanrs_mat *m, const double *points, int points_is_device
 int scanrs_multi_knn(scanrs_multi *mm, const double *points, uint32_t ld, uint32_t d, uint32_t k, uint32_t *out, double *sq_dist);
 int scanrs_host_knn_merge(uint32_t k, const double *da, const uint32_t *ia, const double *db, const uint32_t *ib, double *dout,
                           uint32_t *iout);
+
+/* ---- the plan of the fixed-point column moments (option "col_moments"; host only, no device) -----------------------------------
+ * The route adds, per slice, the terms f of the map as 64-bit integers rint(f 2^e1) (and rint(f^2 2^e2)): one quantum q = 2^-e for
+ * the whole matrix, so every term is off by at most q/2 ABSOLUTE. The plan decides from global numbers whether that is good enough
+ * for every slice, and chooses e1 / e2. Inputs: max_count, the largest stored count; the links of the map in order, kinds[i] = 1
+ * (ScaleAxis) or 2 / 3 / 4 (ln, log2, log10 of 1 + x); for a ScaleAxis link on_summed_axis[i] != 0 when its factors belong to the
+ * positions that are summed over, fmin_pos[i] its smallest factor > 0 and fmax[i] its largest factor (a link that holds a negative or
+ * non-finite factor: pass such a value as fmax); n_outer = positions summed over, n_inner = slices, n_wg = workgroups the
+ * positions are dealt over (min(compute units, ceil(n_outer / 64))), mode 1 = sums only, 2 = sums and sums of squares. The rule:
+ *   - refused: a link of another kind, a ScaleAxis link on the other axis or with a negative / non-finite factor or with no positive
+ *     factor, no logarithm in the chain, n_outer = 0, n_inner = 0 (a zero factor beside positive ones is fine: its terms are exactly 0);
+ *   - x = the chain applied to max_count under every link's fmax (no term is larger), v_min = the chain applied to count 1 under every
+ *     link's fmin_pos (no nonzero term is smaller), each widened by 1e-4 for the roundings of the bound itself;
+ *   - e1 = the largest exponent with x 2^e1 <= 2^50 and ceil(n_outer / n_wg) x 2^e1 <= 2^62; e2 the same for x^2;
+ *   - accepted when v_min 2^e1 >= 2^40 and (mode 2) v_min^2 2^e2 >= 2^33: a slice of n terms sums to at least n v_min and is off by at
+ *     most n q/2, so its sum is right to 2^-41 = 4.6e-13 relative and its sum of squares to 2^-34 = 5.9e-11, which keeps sum and mean
+ *     within 1e-12 relative and the variance within 1e-10 S2/m.
+ * accept = 1 / 0; e1, e2 are meaningful when accepted. */
+int scanrs_host_col_moments_plan(uint32_t max_count, uint32_t n_links, const int *kinds, const int *on_summed_axis, const double *fmin_pos,
+                                 const double *fmax, uint64_t n_outer, uint64_t n_inner, uint32_t n_wg, int mode, int *accept, int *e1,
+                                 int *e2);
 
 /* ---- 10x HDF5 ingestion (hdf5-io/src/matrix.rs, analysis.rs). Host-side; no device needed.
  * The files are parsed by the library's own reader (csrc/h5lite.cpp) — no libhdf5 dependency. Failures are

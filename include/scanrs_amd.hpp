@@ -1105,6 +1105,23 @@ inline KnnResult knn(const MultiMat &m, uint64_t cells, const double *points, ui
 inline void host_knn_merge(uint32_t k, const double *da, const uint32_t *ia, const double *db, const uint32_t *ib, double *dout, uint32_t *iout) {
     check(scanrs_host_knn_merge(k, da, ia, db, ib, dout, iout));
 }
+// the plan of the fixed-point column moments (option "col_moments") on the host: accepted or not, and the two exponents
+struct ColMomentsPlan {
+    bool accept = false;
+    int e1 = 0, e2 = 0;
+};
+inline ColMomentsPlan host_col_moments_plan(uint32_t max_count, const std::vector<int> &kinds, const std::vector<int> &on_summed_axis,
+                                            const std::vector<double> &fmin_pos, const std::vector<double> &fmax, uint64_t n_outer, uint64_t n_inner,
+                                            uint32_t n_wg, int mode) {
+    if (on_summed_axis.size() != kinds.size() || fmin_pos.size() != kinds.size() || fmax.size() != kinds.size())
+        throw Error(SCANRS_ERR_ARGUMENT, "host_col_moments_plan: one entry per link in every list");
+    ColMomentsPlan p;
+    int accept = 0;
+    check(scanrs_host_col_moments_plan(max_count, (uint32_t)kinds.size(), kinds.data(), on_summed_axis.data(), fmin_pos.data(), fmax.data(), n_outer,
+                                       n_inner, n_wg, mode, &accept, &p.e1, &p.e2));
+    p.accept = accept != 0;
+    return p;
+}
 
 namespace mtx {
 // scan_rs::mtx::load_mtx (scan-rs/src/mtx.rs:10-51): the CSR arrays; `.to_device()` is the AdaptiveMat the reference returns

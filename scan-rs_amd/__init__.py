@@ -1526,6 +1526,33 @@ def host_knn_merge(da, ia, db, ib):
     return dout, iout
 
 
+def host_col_moments_plan(max_count: int, links, n_outer: int, n_inner: int, n_wg: int, mode: int):
+    """The plan of the fixed-point column moments on the host (`scanrs_host_col_moments_plan`; scan-rs_amd/csrc/col_moments_plan.hpp,
+    the source kernels.hip decides by). `links`: the map's links in order, each `(FN_LN_1P | FN_LOG2_1P | FN_LOG10_1P,)` or
+    `("scale", fmin_pos, fmax)` / `("scale", fmin_pos, fmax, on_summed_axis)` with the link's smallest positive and its largest
+    factor. Returns (accept, e1, e2): the terms are added as rint(f * 2**e1) and rint(f * f * 2**e2)."""
+    kinds, on, lo, hi = [], [], [], []
+    for l in links:
+        if l[0] == "scale":
+            kinds.append(1)
+            lo.append(float(l[1]))
+            hi.append(float(l[2]))
+            on.append(int(bool(l[3])) if len(l) > 3 else 1)
+        else:
+            kinds.append(int(l[0]))
+            lo.append(0.0)
+            hi.append(0.0)
+            on.append(1)
+    n = len(kinds)
+    ka, oa = (ctypes.c_int * max(n, 1))(*kinds), (ctypes.c_int * max(n, 1))(*on)
+    la, ha = (ctypes.c_double * max(n, 1))(*lo), (ctypes.c_double * max(n, 1))(*hi)
+    acc, e1, e2 = ctypes.c_int(), ctypes.c_int(), ctypes.c_int()
+    _check(_lib.scanrs_host_col_moments_plan(ctypes.c_uint32(int(max_count)), ctypes.c_uint32(n), ka, oa, la, ha, ctypes.c_uint64(int(n_outer)),
+                                             ctypes.c_uint64(int(n_inner)), ctypes.c_uint32(int(n_wg)), ctypes.c_int(int(mode)),
+                                             ctypes.byref(acc), ctypes.byref(e1), ctypes.byref(e2)))
+    return bool(acc.value), int(e1.value), int(e2.value)
+
+
 def knn_device(d_points: int, n: int, ld: int, d: int, k: int):
     """`nn::knn` on scores that already live in device memory (e.g. PcaResultDevice.d_v / ld_v): (n x k) u32 host array."""
     out = np.zeros((n, k), dtype=np.uint32)
@@ -1652,7 +1679,7 @@ EXPORTED_SYMBOLS = [
     "scanrs_mat_select_rows_sharded", "scanrs_mat_select_cols_sharded", "scanrs_mat_partition_on_thresholds_sharded", "scanrs_mat_shard_info",
     "scanrs_multi_shape", "scanrs_multi_to_csmat", "scanrs_multi_select_rows", "scanrs_multi_select_cols", "scanrs_multi_partition_on_thresholds",
     "scanrs_mat_to_adaptive", "scanrs_adaptive_export_info", "scanrs_adaptive_export_vecs", "scanrs_adaptive_export_free",
-    "scanrs_host_choose_storage",
+    "scanrs_host_choose_storage", "scanrs_host_col_moments_plan",
     "scanrs_mat_sum_rows_u64", "scanrs_mat_sum_rows_f64", "scanrs_mat_sum_cols_u64", "scanrs_mat_sum_cols_f64", "scanrs_mat_sum_rows_dual_u64",
     "scanrs_mat_sum_rows_dual_f64", "scanrs_mat_mean_rows", "scanrs_mat_mean_var_rows", "scanrs_mat_var_axis",
     "scanrs_mat_sum_rows_u64_sharded", "scanrs_mat_sum_rows_f64_sharded", "scanrs_mat_sum_cols_u64_sharded", "scanrs_mat_sum_cols_f64_sharded",

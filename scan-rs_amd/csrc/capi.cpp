@@ -6,6 +6,7 @@
 #include <vector>
 
 #include "common.hpp"
+#include "col_moments_plan.hpp"
 
 namespace scanrs {
 
@@ -1160,6 +1161,19 @@ int scanrs_host_knn_merge(uint32_t k, const double *da, const uint32_t *ia, cons
         if (k && (!da || !ia || !db || !ib || !dout || !iout)) fail(SCANRS_ERR_ARGUMENT, "null argument");
         if (k > 128) fail(SCANRS_ERR_ARGUMENT, "knn: k must not exceed 128");
         knn_host_merge(k, da, ia, db, ib, dout, iout);
+    });
+}
+int scanrs_host_col_moments_plan(uint32_t max_count, uint32_t n_links, const int *kinds, const int *on_summed_axis, const double *fmin_pos,
+                                 const double *fmax, uint64_t n_outer, uint64_t n_inner, uint32_t n_wg, int mode, int *accept, int *e1, int *e2) {
+    return guard([&] {
+        if (!accept || !e1 || !e2 || (n_links && (!kinds || !on_summed_axis || !fmin_pos || !fmax))) fail(SCANRS_ERR_ARGUMENT, "null argument");
+        if (n_links > 64) fail(SCANRS_ERR_ARGUMENT, "col_moments_plan: at most 64 links");
+        std::vector<col_moments::Link> links(n_links);
+        for (uint32_t i = 0; i < n_links; i++) links[i] = {kinds[i], on_summed_axis[i], fmin_pos[i], fmax[i]};
+        const col_moments::Plan p = col_moments::plan(max_count, links.data(), (int)n_links, n_outer, n_inner, n_wg, mode);
+        *accept = p.ok ? 1 : 0;
+        *e1 = p.e1;
+        *e2 = p.e2;
     });
 }
 int scanrs_debug_knn_filter(const double *queries, uint64_t n_q, const double *points, uint64_t n_p, uint32_t d, const double *tau,

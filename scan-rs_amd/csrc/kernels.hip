@@ -12,6 +12,7 @@
 // Wave = 64 lanes everywhere. One wave works one `Item` (<= ITEM_NNZ nonzeros of one outer vector).
 #include "common.hpp"
 #include "device_map.hpp"
+#include "col_moments_plan.hpp"
 
 #include <algorithm>
 #include <rocprim/rocprim.hpp>
@@ -2448,8 +2449,10 @@ void launch_fill_f64(Storage &st, double *p, uint64_t n, double v) {
 // and a block of cells; the nonzeros of a cell inside the range are a contiguous run: bounds table) as 64-bit FIXED-POINT
 // numbers with integer atomics: integer addition is associative, so the result does not depend on the order in which the waves
 // arrive (float atomics would make it depend on timing), and with the scale chosen per launch from a bound of the values
-// (col_moments_plan) a workgroup's sums cannot overflow and round each term below 2^-30 of the largest value; the partial sums
-// of the workgroups are added in double, in workgroup order.
+// (col_moments_plan.hpp) a workgroup's sums cannot overflow. Every term is rounded to that one quantum, an absolute error: the
+// plan accepts a map only when the quantum is below 2^-40 of the SMALLEST nonzero term any slice can hold (2^-33 for the
+// squares), so that every slice's sums are right to 4.6e-13 (5.9e-11) relative, not only those of the slices that hold large
+// values; every other map takes the ordinary pass. The partial sums of the workgroups are added in double, in workgroup order.
 constexpr uint32_t CM_RANGE_SHIFT = 13; // inner positions per range: 8192 x 2 x 8 B = 128 KB of LDS
 constexpr uint32_t CM_TAB = 8;          // counts 1 .. 8 come from the per-cell table
 constexpr uint32_t CM_NV = 4;           // cells per wave and trip (their bounds, their segments' loads side by side)
@@ -2555,7 +2558,8 @@ __global__ void max_u32_kernel(const uint32_t *__restrict__ v, uint64_t n, uint3
     for (int off = 32; off > 0; off >>= 1) m = max(m, (uint32_t)__shfl_xor((int)m, off));
     if ((threadIdx.x & 63u) == 0) atomicMax(out, m);
 }
-// [0] = smallest, [1] = largest value as order-preserving bit patterns of non-negative doubles; [2] != 0: a negative or non-finite value
+// [0] = smallest POSITIVE, [1] = largest value as order-preserving bit patterns of non-negative doubles (zeros take part in neither:
+// [0] stays ~0 when no factor is positive, [1] stays +0.0 when all are zero); [2] != 0: a negative or non-finite value
 __global__ void minmax_nonneg_kernel(const double *__restrict__ v, uint64_t n, unsigned long long *__restrict__ out) {
     unsigned long long lo = ~0ull, hi = 0ull;
     int bad = 0;
@@ -2563,7 +2567,7 @@ __global__ void minmax_nonneg_kernel(const double *__restrict__ v, uint64_t n, u
         const double x = v[i];
         if (!(x >= 0.0) || !isfinite(x)) {
             bad = 1;
-        } else {
+        } else if (x > 0.0) {
             const unsigned long long b = (unsigned long long)__double_as_longlong(x);
             lo = b < lo ? b : lo;
             hi = b > hi ? b : hi;
@@ -2576,7 +2580,8 @@ __global__ void minmax_nonneg_kernel(const double *__restrict__ v, uint64_t n, u
 
 // Can the per-inner sums of `map` over `cp` (outer = the summed-over axis) take col_moments_kernel? Every link must be a
 // ScaleAxis over the OUTER position with non-negative finite factors or a logarithm (then the value is non-negative and grows
-// with the count and with the factors: its largest possible value follows from the largest count and the largest factors).
+// with the count and with the factors: its largest and its smallest possible value follow from the counts' and the factors'
+// extremes). The device supplies those extremes; the decision and the exponents are col_moments_plan.hpp's.
 // Returns the fixed-point scales in s1 / s2; false = use the ordinary pass.
 static bool col_moments_plan(Storage &st, SparseCopy &cp, const DevMap &map, int mode, uint32_t n_wg, double &s1, double &s2) {
     bool has_log = false;
@@ -2598,41 +2603,30 @@ static bool col_moments_plan(Storage &st, SparseCopy &cp, const DevMap &map, int
         const uint32_t h = SCANRS_D2H_VALUE(d, st.stream);
         cp.max_value = std::max(h, 1u);
     }
-    double x = (double)cp.max_value;
+    std::vector<col_moments::Link> links((size_t)map.n);
     unsigned long long *d = st.scratch.get<unsigned long long>("cm_minmax", 3);
     for (int i = 0; i < map.n; i++) {
-        const int k = map.ops[i].kind;
-        if (k == OP_SCALE_AXIS) {
-            const unsigned long long init[3] = {~0ull, 0ull, 0ull};
-            SCANRS_HIP(hipMemcpyAsync(d, init, sizeof init, hipMemcpyHostToDevice, st.stream));
-            hipLaunchKernelGGL(minmax_nonneg_kernel, dim3(512), dim3(256), 0, st.stream, map.ops[i].a, cp.n_outer, d);
-            struct H3 {
-                unsigned long long v[3];
-            };
-            const H3 h3 = SCANRS_D2H_VALUE(reinterpret_cast<const H3 *>(d), st.stream);
-            const unsigned long long *h = h3.v;
-            if (h[2]) return false;
-            double amax;
-            memcpy(&amax, &h[1], 8);
-            x *= amax;
-        } else if (k == OP_LN_1P) {
-            x = std::log1p(x);
-        } else if (k == OP_LOG2_1P) {
-            x = std::log2(1.0 + x);
-        } else {
-            x = std::log10(1.0 + x);
-        }
-        if (!std::isfinite(x)) return false;
+        col_moments::Link &l = links[(size_t)i];
+        l.kind = map.ops[i].kind;
+        l.on_summed_axis = 1;
+        l.fmin_pos = l.fmax = 0.0;
+        if (l.kind != OP_SCALE_AXIS) continue;
+        const unsigned long long init[3] = {~0ull, 0ull, 0ull};
+        SCANRS_HIP(hipMemcpyAsync(d, init, sizeof init, hipMemcpyHostToDevice, st.stream));
+        hipLaunchKernelGGL(minmax_nonneg_kernel, dim3(512), dim3(256), 0, st.stream, map.ops[i].a, cp.n_outer, d);
+        struct H3 {
+            unsigned long long v[3];
+        };
+        const H3 h3 = SCANRS_D2H_VALUE(reinterpret_cast<const H3 *>(d), st.stream);
+        const unsigned long long *h = h3.v;
+        if (h[2]) return false;
+        memcpy(&l.fmax, &h[1], 8);
+        if (h[0] != ~0ull) memcpy(&l.fmin_pos, &h[0], 8);
     }
-    // a workgroup adds at most cells_per_wg values of at most x (x^2): keep the sums below 2^62 and the terms' rounding at 2^-30 of x or finer
-    const double cells = std::ceil((double)cp.n_outer / n_wg);
-    const double b1 = std::max(x, 1e-300) * cells * 1.0001, b2 = std::max(x * x, 1e-300) * cells * 1.0001;
-    // ... and every term below 2^51 (the kernel's conversion)
-    const int e1 = std::min(62 - (int)std::ceil(std::log2(b1)), 50 - (int)std::ceil(std::log2(std::max(x, 1e-300) * 1.0001)));
-    const int e2 = std::min(62 - (int)std::ceil(std::log2(b2)), 50 - (int)std::ceil(std::log2(std::max(x * x, 1e-300) * 1.0001)));
-    if (e1 > 1000 || e2 > 1000 || (double)e1 + std::log2(std::max(x, 1e-300)) < 30.0 || (mode == 2 && (double)e2 + std::log2(std::max(x * x, 1e-300)) < 30.0)) return false;
-    s1 = std::ldexp(1.0, e1);
-    s2 = std::ldexp(1.0, e2);
+    const col_moments::Plan p = col_moments::plan(cp.max_value, links.data(), map.n, cp.n_outer, cp.n_inner, n_wg, mode);
+    if (!p.ok) return false;
+    s1 = std::ldexp(1.0, p.e1);
+    s2 = std::ldexp(1.0, p.e2);
     return true;
 }
 static uint32_t ensure_bounds(Storage &st, SparseCopy &cp, hipStream_t s);
