@@ -3,10 +3,11 @@
 //
 //   lgamma_pos      ln Γ(z), z > 0: Stirling's series (8 terms) at z >= 15, the recurrence Γ(z+1) = z Γ(z) below
 //   log_beta_pf     ln[x^a y^b / B(a, b)], y = 1 - x, without the cancellation of three large ln Γ values: for a, b >= 15
-//                   the Stirling form a ln(x/x0) + b ln(y/y0) + ½ ln(ab/(2π(a+b))) - (δ(a)+δ(b)-δ(a+b)), x0 = a/(a+b);
-//                   for one large and one small parameter the large pair's ln Γ difference from the same series
-//   betainc         regularised incomplete beta I_x(a, b): continued fraction (modified Lentz) on the side of the mean
-//                   where it converges, the symmetry I_x(a,b) = 1 - I_{1-x}(b,a) on the other
+//                   the Stirling form a ln(x/x0) + b ln(y/y0) + ½ ln(ab/(2π(a+b))) - (δ(a)+δ(b)-δ(a+b)), x0 = a/(a+b), its two
+//                   logarithms taken as log1p(u) - u of one shared numerator; for one large and one small parameter the large
+//                   pair's ln Γ difference from the same series
+//   betainc         regularised incomplete beta I_x(a, b): continued fraction (DiDonato & Morris, modified Lentz) on the side of
+//                   the mean where it converges, the symmetry I_x(a,b) = 1 - I_{1-x}(b,a) on the other
 //   betaincinv      x with I_x(a, b) = p: Newton steps on the density, kept inside a shrinking bracket (bisection when a
 //                   step would leave it; geometric halving while the lower end is still 0)
 //   nb_term         ln of one term of the exact test's conditional distribution (dist.rs:259-310, written per term)
@@ -69,53 +70,76 @@ SCANRS_HD inline double log_beta(double a, double b) {
            stirling_tail(ab);
 }
 
-// ln[x^a y^b / B(a, b)] with y = 1 - x given separately (no rounding of 1 - x near 1)
-SCANRS_HD inline double log_beta_pf(double a, double b, double x, double y) {
-    if (a >= STIRLING_MIN && b >= STIRLING_MIN) {
-        const double ab = a + b;
-        // a ln(x/x0) + b ln(y/y0): (x - x0)/x0 = (x (a+b) - a)/a
-        const double u = fma(x, ab, -a) / a, v = fma(y, ab, -b) / b;
-        return a * log1p(u) + b * log1p(v) + 0.5 * log(a * b / ab) - LN_SQRT_2PI - (stirling_tail(a) + stirling_tail(b) - stirling_tail(ab));
+// log1p(z) - z, z > -1, without the cancellation at small z: with w = z/(2+z), log1p(z) = 2 atanh(w) and 2w - z = -z w, so
+// log1p(z) - z = w (2 w^2 (1/3 + w^2/5 + w^4/7 + ...) - z); |w| <= 1/3 where the series is used
+SCANRS_HD inline double log1pmx(double z) {
+    if (fabs(z) > 0.5) return log1p(z) - z;
+    const double w = z / (2.0 + z), w2 = w * w;
+    double s = 0.0, p = 1.0;
+    for (int k = 3; k < 45; k += 2) {
+        const double t = p / k;
+        s += t;
+        if (t < 1e-17 * s) break;
+        p *= w2;
     }
-    return a * log(x) + b * log(y) - log_beta(a, b);
+    return w * (2.0 * w2 * s - z);
 }
 
-// continued fraction of I_x(a, b) (modified Lentz)
-SCANRS_HD inline double betacf(double a, double b, double x) {
+// n = x (a+b) - a = -[y (a+b) - b], y = 1 - x: the distance of x from x0 = a/(a+b) in units of 1/(a+b), the one number through which
+// the prefactor and the continued fraction see x near x0. It takes a + b as the exact pair ab + ab_lo and one rounding in the fma;
+// formed from a rounded 1 - x or a rounded a + b it is off by (a+b) ulp, and ln of the prefactor with it.
+SCANRS_HD inline double beta_excess(double a, double b, double x) {
+    const double ab = a + b, t = ab - a, ab_lo = (a - (ab - t)) + (b - t);
+    return fma(x, ab, -a) + x * ab_lo;
+}
+
+// ln[x^a y^b / B(a, b)], y = 1 - x, from x and n = beta_excess(a, b, x): every caller's x is the given number, its 1 - x the rounded one
+SCANRS_HD inline double log_beta_pf(double a, double b, double x, double n) {
+    if (a >= STIRLING_MIN && b >= STIRLING_MIN) {
+        // a ln(x/x0) + b ln(y/y0): (x - x0)/x0 = n/a = u and (y - y0)/y0 = -n/b = v, so the first-order terms a u + b v cancel exactly
+        // and a [log1p(u) - u] + b [log1p(v) - v] is left, two terms of one sign
+        const double ab = a + b;
+        const double u = n / a, v = -n / b;
+        // far below x0 (or y0) the logarithm is taken of x/x0 (or y/y0; y is exact there, x > 1/2) itself: u rounds to -1 once x/x0 < 1e-16
+        const double su = u > -0.5 ? log1pmx(u) : log(x * ab / a) - u;
+        const double sv = v > -0.5 ? log1pmx(v) : log((1.0 - x) * ab / b) - v;
+        return a * su + b * sv + 0.5 * log(a * b / ab) - LN_SQRT_2PI - (stirling_tail(a) + stirling_tail(b) - stirling_tail(ab));
+    }
+    // 1 - x is exact for x >= 1/2; below, log1p(-x) spares its rounding, which b multiplies
+    return a * log(x) + b * (x < 0.5 ? log1p(-x) : log(1.0 - x)) - log_beta(a, b);
+}
+
+// I_x(a, b) = x^a y^b / B(a, b) / betacf: the continued fraction b_0 + a_1/(b_1 + a_2/(b_2 + ...)) of DiDonato & Morris (ACM TOMS 18, 1992),
+// the even part of the classical fraction, by modified Lentz; n = beta_excess(a, b, x). The classical fraction's partial
+// denominators 1 - (a+m)(a+b+m) x / ((a+2m)(a+2m+1)) each cancel to ~1/a next to x0, and its value (up to ~a for b << a) multiplies what
+// they lose; here that difference is written out, a y - b x = -n, and no term cancels.
+SCANRS_HD inline double betacf(double a, double b, double x, double n) {
     const double tiny = 1e-300, eps = 1e-16;
-    const double qab = a + b, qap = a + 1.0, qam = a - 1.0;
-    double c = 1.0, d = 1.0 - qab * x / qap;
-    if (fabs(d) < tiny) d = tiny;
-    d = 1.0 / d;
-    double h = d;
+    double f = a * (1.0 - n) / (a + 1.0);
+    if (fabs(f) < tiny) f = tiny;
+    double c = f, d = 0.0;
     for (int m = 1; m <= 200000; m++) {
-        const double m2 = 2.0 * m;
-        double aa = m * (b - m) * x / ((qam + m2) * (a + m2));
-        d = 1.0 + aa * d;
+        const double den = a + 2.0 * m - 1.0;
+        const double am = (a + m - 1.0) * (a + b + m - 1.0) * m * (b - m) * x * x / (den * den);
+        const double bm = m + m * (b - m) * x / den + (a + m) * (1.0 - n + m * (2.0 - x)) / (den + 2.0);
+        d = bm + am * d;
         if (fabs(d) < tiny) d = tiny;
-        c = 1.0 + aa / c;
+        c = bm + am / c;
         if (fabs(c) < tiny) c = tiny;
         d = 1.0 / d;
-        h *= d * c;
-        aa = -(a + m) * (qab + m) * x / ((a + m2) * (qap + m2));
-        d = 1.0 + aa * d;
-        if (fabs(d) < tiny) d = tiny;
-        c = 1.0 + aa / c;
-        if (fabs(c) < tiny) c = tiny;
-        d = 1.0 / d;
-        const double del = d * c;
-        h *= del;
+        const double del = c * d;
+        f *= del;
         if (fabs(del - 1.0) < eps) break;
     }
-    return h;
+    return f;
 }
 
 SCANRS_HD inline double betainc(double a, double b, double x) {
     if (!(x > 0.0)) return 0.0;
     if (!(x < 1.0)) return 1.0;
-    const double y = 1.0 - x;
-    if (x * (a + b + 2.0) < a + 1.0) return exp(log_beta_pf(a, b, x, y)) * betacf(a, b, x) / a;
-    return 1.0 - exp(log_beta_pf(a, b, x, y)) * betacf(b, a, y) / b;
+    const double y = 1.0 - x, n = beta_excess(a, b, x);
+    if (x * (a + b + 2.0) < a + 1.0) return exp(log_beta_pf(a, b, x, n)) / betacf(a, b, x, n);
+    return 1.0 - exp(log_beta_pf(a, b, x, n)) / betacf(b, a, y, -n);
 }
 
 SCANRS_HD inline double betaincinv(double a, double b, double p) {
@@ -132,10 +156,12 @@ SCANRS_HD inline double betaincinv(double a, double b, double p) {
         else
             hi = x;
         // density x^(a-1) (1-x)^(b-1) / B(a, b)
-        const double dens = exp(log_beta_pf(a, b, x, 1.0 - x)) / (x * (1.0 - x));
+        const double dens = exp(log_beta_pf(a, b, x, beta_excess(a, b, x))) / (x * (1.0 - x));
         double xn = x - f / dens;
-        if (!(xn > lo && xn < hi)) xn = lo > 0.0 ? 0.5 * (lo + hi) : hi * 0.0625;
+        // settled: before the bracket is asked, since a step that rounds to nothing leaves xn = x, which IS the bracket's end now and
+        // not inside it; halving from there creeps back towards x and stops some ulp short of it
         if (fabs(xn - x) <= 1e-15 * x) return xn;
+        if (!(xn > lo && xn < hi)) xn = lo > 0.0 ? 0.5 * (lo + hi) : hi * 0.0625;
         if (hi - lo <= 1e-16 * hi) return xn;
         x = xn;
     }

@@ -1,4 +1,10 @@
-"""sSeq differential expression on the device (scan-rs_amd/csrc/sseq.hip) against the CPU restatement tests/sseq_ref.py."""
+"""sSeq differential expression on the device (scan-rs_amd/csrc/sseq.hip) against the CPU restatement tests/sseq_ref.py, and its
+asymptotic branch (sseq_asymptotic_kernel) against the high-precision values of tests/golden/sseq_asym_table.json (section 9; the
+cases, regimes and bounds are those of tests/test_sseq_asym_cpu.py).
+
+Measured on an MI355X: the device's worst relative error against the reference is of the host's size in every regime (the table in
+tests/test_sseq_asym_cpu.py; 6.7e-14 against 4.7e-14 in mixed-M/tail is the largest difference), 1.9e-13 at most (stirling-S/tail);
+host against device 768 ulp at most. The six tests of section 9 take 0.4 s together."""
 import os
 import sys
 
@@ -12,6 +18,7 @@ ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 TESTS = os.path.dirname(os.path.abspath(__file__))
 if TESTS not in sys.path:
     sys.path.insert(0, TESTS)
+import sseq_asym_cases as acases  # noqa: E402
 import sseq_ref as ref  # noqa: E402
 
 FIELDS = ("sums_in", "sums_out", "p_values", "adjusted_p_values", "log2_fold_change", "normalized_mean_in", "normalized_mean_out")
@@ -299,3 +306,147 @@ def test_one_vs_rest_at_100k_cells(sa):
         # BH over every tested gene, from the device's p-values
         idx = np.flatnonzero(params.use_genes)
         np.testing.assert_allclose(got[j].adjusted_p_values[idx], ref.adjusted_pvalue_bh(got[j].p_values[idx]), rtol=1e-15)
+
+
+# ---- 9. asymptotic test battery ---------------------------------------------------------------------------------------------------------
+ASYM_BLOCK = 64  # threads per block of sseq_asymptotic_kernel
+# Host and device run one source with their own log, log1p, exp and fma contraction. First measured: 768 ulp at most, at p = 9.8e-201,
+# where one ulp of ln p (|ln p| = 460) is 512 ulp of p; about half of the 295 cases were bit-equal. Held to 4 x that (never below 4 ulp).
+ASYM_HOST_DEVICE_ULP = 4 * 768
+
+
+def _asym_params(sa, rows, use=True):
+    mu, phi = np.array([r["mu"] for r in rows]), np.array([r["phi"] for r in rows])
+    return sa.SSeqParams(0, len(rows), np.zeros(0), mu, np.ones(len(rows)), np.full(len(rows), use), phi, 0.0, 0.0, phi)
+
+
+def _asym_call(sa, rows, **kw):
+    """p-values of rows that share one (sf_a, sf_b), one gene per row, in ONE call"""
+    assert len({(r["sf_a"], r["sf_b"]) for r in rows}) == 1
+    kw.setdefault("big_count", 0)
+    res = sa.sseq_de_from_sums([r["x_a"] for r in rows], [r["x_b"] for r in rows], rows[0]["sf_a"], rows[0]["sf_b"], _asym_params(sa, rows), **kw)
+    return res.p_values
+
+
+def _asym_groups(rows):
+    return [[i for i, r in enumerate(rows) if r["group"] == g] for g in sorted({r["group"] for r in rows})]
+
+
+def _asym_battery(sa, rows, **kw):
+    """one call per (sf_a, sf_b) group: sseq_de_from_sums takes one size factor per test and side"""
+    p = np.zeros(len(rows))
+    for idx in _asym_groups(rows):
+        p[idx] = _asym_call(sa, [rows[i] for i in idx], **kw)
+    return p
+
+
+def _ulps(a, b):
+    """distance of positive doubles in units of the last place"""
+    return np.abs(np.asarray(a, dtype=np.float64).view(np.int64) - np.asarray(b, dtype=np.float64).view(np.int64))
+
+
+@pytest.fixture(scope="module")
+def asym(sa):
+    rows = acases.load_table()["nb"]
+    assert len(_asym_groups(rows)) == 5 and min(len(g) for g in _asym_groups(rows)) > ASYM_BLOCK // 2
+    return rows, _asym_battery(sa, rows)
+
+
+def test_asym_battery_matches_the_series(sa, asym):
+    rows, p = asym
+    keys = acases.nb_keys(rows)
+    err, tie_route = acases.nb_errors(rows, p)
+    yard, _ = acases.nb_errors(rows, [r["scipy"] for r in rows])
+    _, bound = acases.report("nb_asymptotic on the device", keys, err, yard)
+    assert tie_route <= 0.02 * len(rows)
+    bad = [(k, e, r) for k, e, r in zip(keys, err, rows) if not e <= bound[k]]
+    assert not bad, (len(bad), max(bad, key=lambda t: t[1]))
+
+
+def test_asym_battery_device_against_host(sa, asym):
+    rows, p = asym
+    host = np.array([sa.sseq.host_nb_asymptotic_test(r["x_a"], r["x_b"], r["sf_a"], r["sf_b"], r["mu"], r["phi"]) for r in rows])
+    # a case at the median may take the other side on the other machine: both sides are in the table
+    near = np.array([r["distance"] < acases.TIE_DISTANCE for r in rows])
+    d = _ulps(p, host)
+    for i in np.flatnonzero(near & (d > ASYM_HOST_DEVICE_ULP)):
+        sides = [float(rows[i]["p_lower"]), float(rows[i]["p_upper"])]
+        assert min(abs(p[i] - v) / v for v in sides) < 1e-12 and min(abs(host[i] - v) / v for v in sides) < 1e-12
+        d[i] = 0
+    i = int(np.argmax(d))
+    print(f"\nhost against device: {int(d[i])} ulp at most (p = {p[i]!r}, {rows[i]['tag']}), {int(np.sum(d == 0))} of {len(rows)} cases bit-equal")
+    assert d[i] <= ASYM_HOST_DEVICE_ULP
+
+
+def test_asym_result_does_not_depend_on_the_batch(sa, asym):
+    rows, p = asym
+    again = _asym_battery(sa, rows)
+    assert again.tobytes() == p.tobytes()
+    for idx in _asym_groups(rows):
+        # every case alone
+        for i in idx:
+            assert _asym_call(sa, [rows[i]])[0] == p[i], rows[i]
+    # one test more than a block, against the same tests inside two full blocks
+    sub = [r for r in rows if r["group"] == 2]
+    assert len(sub) >= ASYM_BLOCK + 1
+    wide = sub + sub
+    wide = wide[:2 * ASYM_BLOCK]
+    full = _asym_call(sa, wide)
+    odd = _asym_call(sa, wide[:ASYM_BLOCK + 1])
+    assert odd.tobytes() == full[:ASYM_BLOCK + 1].tobytes()
+    assert full.tobytes() == np.array([p[rows.index(r)] for r in wide]).tobytes()
+
+
+def test_asym_branch_is_taken_only_above_big_count_on_tested_genes(sa, asym):
+    rows, p = asym
+    sub = [r for r in rows if r["x_a"] + r["x_b"] == 3001 and min(r["x_a"], r["x_b"]) > 1 and r["group"] == 2][:6]
+    assert len(sub) >= 3
+    xa, xb = [r["x_a"] for r in sub], [r["x_b"] for r in sub]
+    fa, fb = sub[0]["sf_a"], sub[0]["sf_b"]
+    exact = sa.sseq_de_from_sums(xa, xb, fa, fb, _asym_params(sa, sub), big_count=2 ** 62).p_values
+    asymp = np.array([p[rows.index(r)] for r in sub])
+    # big_count = 2^62 is the exact test by definition; the restatement agrees with it as far as gammaln at sf / phi ~ 1e8 carries
+    # (1e-8 absolute in every term's logarithm), and that is far closer than the beta approximation is to either
+    e = np.array([ref.nb_exact_test(r["x_a"], r["x_b"], fa, fb, r["mu"], r["phi"]) for r in sub])
+    np.testing.assert_allclose(exact, e, rtol=1e-6)
+    assert (exact != asymp).all() and (np.abs(asymp - e) > 1e-3 * e).any()
+    # use_genes false: the exact test, whatever the sums (diff_exp.rs:262)
+    unused = sa.sseq_de_from_sums(xa, xb, fa, fb, _asym_params(sa, sub, use=False), big_count=0).p_values
+    assert unused.tobytes() == exact.tobytes()
+    # `>` big_count on both sides: a sum equal to big_count keeps the exact test, one above it on both sides leaves it
+    for k, r in enumerate(sub):
+        one = _asym_params(sa, [r])
+        for big, want in ((r["x_a"], exact[k]), (r["x_b"], exact[k]), (min(r["x_a"], r["x_b"]) - 1, asymp[k])):
+            got = sa.sseq_de_from_sums([r["x_a"]], [r["x_b"]], fa, fb, one, big_count=big).p_values[0]
+            assert got == want, (r, big)
+
+
+def test_asym_bits_do_not_depend_on_the_backend(sa, asym):
+    rows, p = asym
+    assert _asym_battery(sa, rows, backend=sa.NB_EXACT_RATIO).tobytes() == p.tobytes()
+    assert _asym_battery(sa, rows, backend=sa.NB_EXACT_LOGSPACE).tobytes() == p.tobytes()
+
+
+def test_asym_rows_through_the_matrix_routes(sa, asym):
+    """A dozen battery rows as a 4-cell matrix (two cells per side, the counts split between them, u32): the matrix route on one
+    handle and on a MultiMat with the cells sharded gives the bits of the sums route. sseq_de_pairs computes mu and phi of every
+    pair from the matrix itself and so cannot be handed the battery's rows."""
+    rows, p = asym
+    sub = [r for r in rows if r["group"] == 2 and max(r["x_a"], r["x_b"]) < 2 ** 32 and min(r["x_a"], r["x_b"]) > 1][:12]
+    assert len(sub) == 12
+    m = np.array([[r["x_a"] // 2, r["x_a"] - r["x_a"] // 2, r["x_b"] // 2, r["x_b"] - r["x_b"] // 2] for r in sub], dtype=np.uint32)
+    params = _asym_params(sa, sub)
+    fa, fb = sub[0]["sf_a"], sub[0]["sf_b"]
+    params.size_factors = np.array([fa / 2, fa / 2, fb / 2, fb / 2])
+    assert fa / 2 + fa / 2 == fa and fb / 2 + fb / 2 == fb
+    want = np.array([p[rows.index(r)] for r in sub])
+    s = sparse.csc_matrix(m)
+    s.sort_indices()
+    ip, ix, vv = s.indptr.astype(np.uint64), s.indices.astype(np.uint32), s.data.astype(np.uint32)
+    one = sa.sseq_differential_expression(sa.AdaptiveMat.from_csmat(12, 4, sa.CSC, ip, ix, vv), [0, 1], [2, 3], params, big_count=0)
+    np.testing.assert_array_equal(one.sums_in, [r["x_a"] for r in sub])
+    np.testing.assert_array_equal(one.sums_out, [r["x_b"] for r in sub])
+    assert one.p_values.tobytes() == want.tobytes()
+    multi = sa.sseq_differential_expression(sa.MultiMat(12, 4, sa.CSC, ip, ix, vv, 2, devices=[0, 0]), [0, 1], [2, 3], params, big_count=0)
+    for f in FIELDS:
+        assert getattr(multi, f).tobytes() == getattr(one, f).tobytes(), f
