@@ -550,8 +550,8 @@ int scanrs_plan_shards(const uint64_t *indptr, uint64_t n_outer, uint32_t world,
  * Validation is scanrs_mat_create's (same codes and messages: an index out of range or not strictly ascending, indptr[0] != 0, null
  * arrays, dimensions beyond u32) and runs on every slab before anything is indexed by an inner index; n_shards, devices and peer
  * access are checked as in scanrs_multi_create (`devices` may repeat an id). On any failure nothing is leaked and *out is NULL.
- * Not served: the one-process-per-GPU forms (RCCL, host hook: their only transport is a sum all-reduce), rebalancing an existing
- * scanrs_multi, and to_adaptive of a whole scanrs_multi. */
+ * Not served: the one-process-per-GPU forms (RCCL, host hook: their only transport is a sum all-reduce) and to_adaptive of a whole
+ * scanrs_multi. (An existing scanrs_multi is cut anew by scanrs_multi_rebalance, below.) */
 /* AdaptiveMat::new from a triplet (sqz/src/mat.rs:68-124), sharded over the inner dimension */
 int scanrs_multi_create_inner(uint64_t rows, uint64_t cols, int storage, const uint64_t *indptr, const uint32_t *indices,
                               const uint32_t *values, uint32_t n_shards, const int *devices, scanrs_multi **out);
@@ -571,6 +571,47 @@ int scanrs_multi_create_info(const scanrs_multi *mm, uint64_t *slab_bounds, uint
  * shards of the inner one) and moved (world x world), validated as above. Any output may be NULL. */
 int scanrs_host_plan_inner(const uint64_t *indptr, const uint32_t *indices, uint64_t n_outer, uint64_t n_inner, uint32_t world,
                            uint64_t *slab_bounds, uint64_t *bounds, uint64_t *moved);
+
+/* ---- rebalance and any-order outer selection of a scanrs_multi -----------
+ * One primitive moves outer vectors between shards: "the outer vectors idx[0 .. n_idx) of the WHOLE matrix, in that order, as a freshly
+ * balanced scanrs_multi". It lifts the two restrictions of the scanrs_multi_select_* block above, which stay as they are for those
+ * calls: scanrs_multi_gather_outer takes a list along the sharded dimension in ANY order (descending, shuffled, with repeats), and
+ * scanrs_multi_rebalance - the identity list - cuts the unbalanced result of a filter anew by nonzeros. Another n_shards or other
+ * `devices` re-shard the matrix. The result equals scanrs_multi_create(rows', cols', storage, T, n_shards, devices) for the selected
+ * triplet T (outer vector j of T = vector idx[j] of the source; inner dimension and storage flag unchanged) in every respect: the same
+ * bounds (scanrs_plan_shards over T's indptr), every shard's indptr, indices and values bit for bit, the largest count and the work
+ * items scanrs_mat_create leaves on a handle, a group and communicators of its own (source and result may be freed in either order).
+ * The source is not modified. No nonzero crosses the host link: the sources' indptr arrays go down, the destinations' slices of the
+ * list go up (host_bytes, below), and every destination copies its vectors out of the sources' device arrays in place, through the
+ * peer mapping where the devices differ (peer access is enabled from every destination device to every source device).
+ * Preconditions, those of scanrs_multi_select_rows: identity map, no offset (scanrs_mat_reset_map), dimensions below 2^31 - 1.
+ * Refusals, all before any device work: an index beyond the outer extent SCANRS_ERR_INVALID; a null list with n_idx > 0, n_shards
+ * outside 1 .. 16 or a device that does not exist SCANRS_ERR_ARGUMENT; each message names the argument. On any failure nothing is
+ * leaked and *out is NULL. n_idx == 0 gives what scanrs_multi_create gives for a matrix without outer vectors: a valid scanrs_multi
+ * of empty shards.
+ * Still out of scope: to_adaptive of a whole scanrs_multi, and the one-process-per-GPU forms (RCCL, host hook), whose only transport
+ * is a sum all-reduce. */
+/* the outer vectors idx[0..n_idx) of the WHOLE matrix (global positions along the sharded = stored outer dimension; any order,
+ * repeats allowed), in list order, as a new scanrs_multi over n_shards shards on `devices` (null: 0..n_shards-1; ids may repeat) */
+int scanrs_multi_gather_outer(scanrs_multi *mm, const uint64_t *idx, uint64_t n_idx, uint32_t n_shards, const int *devices,
+                              scanrs_multi **out);
+/* the identity list: the same matrix, cut anew by nonzeros. n_shards = 0: as many shards as mm has, on mm's devices. */
+int scanrs_multi_rebalance(scanrs_multi *mm, uint32_t n_shards, const int *devices, scanrs_multi **out);
+/* nonzeros per shard (n_shards entries) and max/mean of them (1 for a matrix without nonzeros); works on every scanrs_multi.
+ * Either output may be NULL. */
+int scanrs_multi_balance(const scanrs_multi *mm, uint64_t *shard_nnz, double *imbalance);
+/* what the call that made `mm` did: the source's shard count, bounds (n_shards + 1), moved (n_src x n_shards nonzeros, source-major:
+ * moved[s * n_shards + d] came from source shard s to shard d) and host_bytes (n_shards entries: the bytes that crossed the host link
+ * in either direction - 4 per vector of the shard's slice of the list up, 8 for the one total that comes back, and the download of
+ * source shard s's indptr, 8 (n_s + 1) bytes, charged to entry s mod n_shards). Any pointer may be NULL. SCANRS_ERR_ARGUMENT on a
+ * scanrs_multi these calls did not make. Per shard, scanrs_mat_get_counter "regather_plan_us" / "regather_pull_us" /
+ * "regather_finish_us": wall clock of the phases. */
+int scanrs_multi_gather_info(const scanrs_multi *mm, uint32_t *n_src, uint64_t *bounds, uint64_t *moved, uint64_t *host_bytes);
+/* the same plan on the host, no device: from the source's global indptr (n_outer + 1), its bounds (n_src + 1) and the list:
+ * out_indptr (n_idx + 1: the selected matrix's), bounds (n_dst + 1) and moved (n_src x n_dst). Any output may be NULL. */
+int scanrs_host_plan_gather(const uint64_t *indptr, uint64_t n_outer, const uint64_t *src_bounds, uint32_t n_src,
+                            const uint64_t *idx, uint64_t n_idx, uint32_t n_dst, uint64_t *out_indptr, uint64_t *bounds,
+                            uint64_t *moved);
 
 /* ---- measurement ------------------------------------------------------------------------- */
 
@@ -702,7 +743,9 @@ int scanrs_mat_set_option(scanrs_mat *m, const char *key, double value);
  * tests this rank launched on the device, and the exchange steps of a sharded handle (0 on an unsharded one). "subset_masked_passes" / "subset_scatter_passes" = sums over a column list made on
  * this handle so far: from the copy whose outer dimension is the result axis (masked walk or listed vectors, no atomics) / through the
  * integer scatter from the other copy ("subset_scatter"); "subset_allreduces" = the exchange steps of the last
- * scanrs_mat_sum_rows_u64_sharded or kin on this handle (0 on an unsharded one). */
+ * scanrs_mat_sum_rows_u64_sharded or kin on this handle (0 on an unsharded one). "regather_plan_us" / "regather_pull_us" /
+ * "regather_finish_us" = on a shard made by scanrs_multi_gather_outer / scanrs_multi_rebalance, the wall clock of the plan (one phase,
+ * the same on every shard) and of the shard's own thread in pull and finish. */
 int scanrs_mat_get_counter(scanrs_mat *m, const char *key, uint64_t *value);
 /* Process-wide options of the entry points that take no handle:
  *   "h5_threads" (8)               threads that inflate the chunks of a large filtered HDF5 read

@@ -592,6 +592,46 @@ class MultiMat {
         check(scanrs_multi_select_cols(h_, idx.data(), idx.size(), &h));
         return MultiMat(h);
     }
+    // Outer vectors move between shards. gather_outer (scanrs_multi_gather_outer): the outer vectors idx of the whole matrix
+    // in list order - any order, repeats allowed - as a freshly balanced MultiMat over n_shards shards on `devices` (null: 0 .. n_shards-1);
+    // it equals MultiMat(selected triplet) bit for bit, and no nonzero crosses the host link. rebalance (scanrs_multi_rebalance): the
+    // identity list; n_shards = 0: as many shards as this one, on its devices.
+    MultiMat gather_outer(const std::vector<uint64_t> &idx, uint32_t n_shards, const int *devices = nullptr) const {
+        scanrs_multi *h = nullptr;
+        check(scanrs_multi_gather_outer(h_, idx.data(), idx.size(), n_shards, devices, &h));
+        return MultiMat(h);
+    }
+    MultiMat rebalance(uint32_t n_shards = 0, const int *devices = nullptr) const {
+        scanrs_multi *h = nullptr;
+        check(scanrs_multi_rebalance(h_, n_shards, devices, &h));
+        return MultiMat(h);
+    }
+    // scanrs_multi_balance: the nonzeros of every shard and max / mean of them
+    struct Balance {
+        std::vector<uint64_t> shard_nnz;
+        double imbalance = 1.0;
+    };
+    Balance balance() const {
+        Balance b{std::vector<uint64_t>(n_shards()), 1.0};
+        check(scanrs_multi_balance(h_, b.shard_nnz.data(), &b.imbalance));
+        return b;
+    }
+    // scanrs_multi_gather_info: what gather_outer / rebalance did. moved[s * n_shards + d]: nonzeros from source shard s to shard d;
+    // host_bytes: what crossed the host link per shard (metadata only). Error on a MultiMat these calls did not make.
+    struct GatherInfo {
+        uint32_t n_src = 0;
+        std::vector<uint64_t> bounds, moved, host_bytes;
+    };
+    GatherInfo gather_info() const {
+        const uint32_t n = n_shards();
+        GatherInfo g;
+        check(scanrs_multi_gather_info(h_, &g.n_src, nullptr, nullptr, nullptr));
+        g.bounds.resize(n + 1);
+        g.moved.resize((size_t)g.n_src * n);
+        g.host_bytes.resize(n);
+        check(scanrs_multi_gather_info(h_, nullptr, g.bounds.data(), g.moved.data(), g.host_bytes.data()));
+        return g;
+    }
     struct Partition;
     Partition partition_on_thresholds(const double *row_threshold, const double *col_threshold) const;
     Partition partition_on_threshold(double threshold) const;
@@ -637,6 +677,21 @@ inline InnerPlan host_plan_inner(const uint64_t *indptr, const uint32_t *indices
     InnerPlan p{std::vector<uint64_t>(world + 1), std::vector<uint64_t>(world + 1), std::vector<uint64_t>((size_t)world * world + 1)};
     check(scanrs_host_plan_inner(indptr, indices, n_outer, n_inner, world, p.slab_bounds.data(), p.bounds.data(), p.moved.data()));
     p.moved.resize((size_t)world * world);
+    return p;
+}
+
+// scanrs_host_plan_gather (host only, no device): the plan of MultiMat::gather_outer / rebalance from the source's global indptr, its
+// shard bounds and the list
+struct GatherPlan {
+    std::vector<uint64_t> indptr, bounds, moved; // n_idx + 1 (the selected matrix's), n_dst + 1, n_src x n_dst
+};
+inline GatherPlan host_plan_gather(const uint64_t *indptr, uint64_t n_outer, const std::vector<uint64_t> &src_bounds, const std::vector<uint64_t> &idx,
+                                   uint32_t n_dst) {
+    const uint32_t n_src = src_bounds.empty() ? 0u : (uint32_t)(src_bounds.size() - 1);
+    GatherPlan p{std::vector<uint64_t>(idx.size() + 1), std::vector<uint64_t>(n_dst + 1), std::vector<uint64_t>((size_t)n_src * n_dst + 1)};
+    check(scanrs_host_plan_gather(indptr, n_outer, src_bounds.data(), n_src, idx.data(), idx.size(), n_dst, p.indptr.data(), p.bounds.data(),
+                                  p.moved.data()));
+    p.moved.resize((size_t)n_src * n_dst);
     return p;
 }
 

@@ -1281,18 +1281,70 @@ class MultiMat:
         return MultiMat._from_handle(h.value)
 
     def select_rows(self, idx) -> "MultiMat":
-        """`scanrs_multi_select_rows`: a new MultiMat on the same devices (shards not rebalanced). A list along the sharded dimension
-        (the rows of a CSR matrix, the columns of a CSC one) must not descend; along the other any order, repeats allowed."""
+        """`scanrs_multi_select_rows`: a new MultiMat on the same devices (shards not rebalanced: `.rebalance(consume=True)` on the
+        result does that). A list along the sharded dimension (the rows of a CSR matrix, the columns of a CSC one) must not descend
+        (any order: `gather_outer`); along the other any order, repeats allowed."""
         return self._select(_lib.scanrs_multi_select_rows, idx)
 
     def select_cols(self, idx) -> "MultiMat":
         """`scanrs_multi_select_cols` (see `select_rows`)."""
         return self._select(_lib.scanrs_multi_select_cols, idx)
 
+    def gather_outer(self, idx, n_shards: Optional[int] = None, devices=None) -> "MultiMat":
+        """`scanrs_multi_gather_outer`: the outer vectors `idx` of the WHOLE matrix (positions along the sharded
+        dimension: the rows of a CSR matrix, the columns of a CSC one; any order, repeats allowed), in list order, as a freshly
+        balanced MultiMat over `n_shards` shards (None: as many as this one) on `devices` (None: this one's when the shard count
+        stays, else 0 .. n_shards-1). It equals `MultiMat(...)` of the selected triplet bit for bit; no nonzero crosses the host link."""
+        idx = np.ascontiguousarray(np.asarray(idx).reshape(-1), dtype=np.int64)
+        if idx.size and int(idx.min()) < 0:
+            raise ScanrsError(6, "idx: index out of range: negative index")
+        idx = idx.astype(np.uint64)
+        if n_shards is None:
+            n_shards = self.n_shards
+            if devices is None:
+                devices = [dev for dev, _lo, _hi in self.shard_ranges()]
+        h = ctypes.c_void_p()
+        _check(_lib.scanrs_multi_gather_outer(self._h, _p(idx), ctypes.c_uint64(idx.shape[0]), ctypes.c_uint32(int(n_shards)),
+                                              self._devices_arg(n_shards, devices), ctypes.byref(h)))
+        return MultiMat._from_handle(h.value)
+
+    def rebalance(self, n_shards: Optional[int] = None, devices=None, consume: bool = False) -> "MultiMat":
+        """`scanrs_multi_rebalance`: the same matrix cut anew by nonzeros (the identity list of `gather_outer`), e.g. after a filter
+        left the shards unequal. n_shards=None: as many shards as this one, on its devices. consume=True: this MultiMat - the
+        unbalanced intermediate of `mm.partition_on_thresholds(rt, ct)[0].rebalance(consume=True)` - is closed once the call
+        returns or fails."""
+        n = 0 if n_shards is None else int(n_shards)
+        if n_shards is not None and n == 0:
+            raise ScanrsError(6, "n_shards: 1 <= n_shards <= 16 is required (0 given)")
+        h = ctypes.c_void_p()
+        try:
+            _check(_lib.scanrs_multi_rebalance(self._h, ctypes.c_uint32(n), None if n == 0 else self._devices_arg(n, devices), ctypes.byref(h)))
+        finally:
+            if consume:
+                self.close()
+        return MultiMat._from_handle(h.value)
+
+    def balance(self) -> dict:
+        """`scanrs_multi_balance`: {"shard_nnz": nonzeros per shard, "imbalance": max / mean of them (1.0 without nonzeros)}."""
+        nnz, imb = np.zeros(max(self.n_shards, 1), dtype=np.uint64), ctypes.c_double()
+        _check(_lib.scanrs_multi_balance(self._h, _p(nnz), ctypes.byref(imb)))
+        return {"shard_nnz": nnz[: self.n_shards], "imbalance": float(imb.value)}
+
+    def gather_info(self) -> dict:
+        """`scanrs_multi_gather_info`: what the `gather_outer` / `rebalance` that made this MultiMat did. bounds (n_shards + 1), moved
+        (n_src x n_shards nonzeros, from source shard s to shard d) and host_bytes per shard (metadata only: the sources' indptr down,
+        the list up). ScanrsError on a MultiMat these calls did not make."""
+        n, n_src = self.n_shards, ctypes.c_uint32()
+        _check(_lib.scanrs_multi_gather_info(self._h, ctypes.byref(n_src), None, None, None))
+        bd, mv, hb = np.zeros(n + 1, dtype=np.uint64), np.zeros((max(n_src.value, 1), max(n, 1)), dtype=np.uint64), np.zeros(max(n, 1), dtype=np.uint64)
+        _check(_lib.scanrs_multi_gather_info(self._h, None, _p(bd), _p(mv), _p(hb)))
+        return {"n_src": int(n_src.value), "bounds": bd, "moved": mv[: n_src.value, :n], "host_bytes": hb[:n]}
+
     def partition_on_thresholds(self, row_threshold: Optional[float], col_threshold: Optional[float], filtered: bool = True,
                                 residual: bool = True):
         """`scanrs_multi_partition_on_thresholds`: (filtered, residual, selected_rows, selected_cols) as `AdaptiveMat.partition_on_thresholds`
-        gives them, the two matrices as MultiMat objects; every output equals the unsharded call's."""
+        gives them, the two matrices as MultiMat objects; every output equals the unsharded call's. The shards keep what the filter
+        left them: `.rebalance(consume=True)` on a result cuts it anew and frees the unbalanced intermediate."""
         rows, cols = self.shape()
         sel_r, sel_c = np.zeros(max(rows, 1), dtype=np.uint64), np.zeros(max(cols, 1), dtype=np.uint64)
         n_r, n_c = ctypes.c_uint64(), ctypes.c_uint64()
@@ -1624,6 +1676,27 @@ def host_plan_inner(indptr, indices, n_inner: int, world: int):
     return sb, bd, mv
 
 
+def host_plan_gather(indptr, src_bounds, idx, n_dst: int):
+    """`scanrs_host_plan_gather` (host only, no device): the plan of `MultiMat.gather_outer` / `rebalance` from the source's global
+    indptr, its shard bounds (n_src + 1 entries) and the list. Returns (indptr, bounds, moved): the selected matrix's indptr
+    (len(idx) + 1), the shard ranges scanrs_plan_shards gives for it (n_dst + 1) and the n_src x n_dst table of nonzeros that go
+    from source shard s to shard d."""
+    ip = np.ascontiguousarray(indptr, dtype=np.uint64)
+    sb = np.ascontiguousarray(src_bounds, dtype=np.uint64)
+    idx = np.ascontiguousarray(np.asarray(idx).reshape(-1), dtype=np.int64)
+    if ip.shape[0] < 1 or sb.shape[0] < 1:
+        raise ScanrsError(6, "indptr and src_bounds need at least one entry")
+    if idx.size and int(idx.min()) < 0:
+        raise ScanrsError(6, "idx: index out of range: negative index")
+    idx = idx.astype(np.uint64)
+    n_src, n_dst = sb.shape[0] - 1, int(n_dst)
+    tip, bd = np.zeros(idx.shape[0] + 1, dtype=np.uint64), np.zeros(max(n_dst, 0) + 1, dtype=np.uint64)
+    mv = np.zeros((max(n_src, 1), max(n_dst, 1)), dtype=np.uint64)
+    _check(_lib.scanrs_host_plan_gather(_p(ip), ctypes.c_uint64(ip.shape[0] - 1), _p(sb), ctypes.c_uint32(n_src), _p(idx),
+                                        ctypes.c_uint64(idx.shape[0]), ctypes.c_uint32(n_dst), _p(tip), _p(bd), _p(mv)))
+    return tip, bd, mv
+
+
 def host_chol_upper(g):
     g = _f64(g).copy()
     _check(_lib.scanrs_host_chol_upper(_p(g), ctypes.c_int(g.shape[0])))
@@ -1663,7 +1736,7 @@ EXPORTED_SYMBOLS = [
     "scanrs_pca_bk", "scanrs_pca_rand", "scanrs_pca_irlba", "scanrs_pca_result_device", "scanrs_knn_device", "scanrs_knn_sharded", "scanrs_multi_knn", "scanrs_host_knn_merge", "scanrs_omega_fill", "scanrs_mat_set_shard", "scanrs_mat_set_shard_comm", "scanrs_comm_get_unique_id", "scanrs_comm_create", "scanrs_comm_free",
     "scanrs_multi_create", "scanrs_multi_free", "scanrs_multi_n_shards", "scanrs_multi_shard", "scanrs_multi_normalize", "scanrs_multi_pca_bk", "scanrs_multi_pca_rand", "scanrs_multi_pca_irlba", "scanrs_multi_log_normalize", "scanrs_multi_sseq_params", "scanrs_multi_group_sums", "scanrs_multi_sseq_de", "scanrs_multi_comm_info",
     "scanrs_sseq_de_pairs_sharded", "scanrs_merge_clusters_sharded", "scanrs_cluster_medoids_sharded", "scanrs_multi_sseq_de_pairs", "scanrs_multi_merge_clusters", "scanrs_multi_cluster_medoids",
-    "scanrs_plan_shards", "scanrs_multi_create_inner", "scanrs_multi_create_adaptive_inner", "scanrs_multi_create_from_file", "scanrs_multi_create_info", "scanrs_host_plan_inner", "scanrs_profile_enable", "scanrs_profile_reset", "scanrs_profile_get", "scanrs_mat_sync", "scanrs_mat_set_spmm_path", "scanrs_mat_set_option", "scanrs_set_global_option", "scanrs_mat_set_panel_precision",
+    "scanrs_plan_shards", "scanrs_multi_create_inner", "scanrs_multi_create_adaptive_inner", "scanrs_multi_create_from_file", "scanrs_multi_create_info", "scanrs_host_plan_inner", "scanrs_multi_gather_outer", "scanrs_multi_rebalance", "scanrs_multi_balance", "scanrs_multi_gather_info", "scanrs_host_plan_gather", "scanrs_profile_enable", "scanrs_profile_reset", "scanrs_profile_get", "scanrs_mat_sync", "scanrs_mat_set_spmm_path", "scanrs_mat_set_option", "scanrs_set_global_option", "scanrs_mat_set_panel_precision",
     "scanrs_mat_chol_rinv", "scanrs_mat_get_counter", "scanrs_host_chol_upper", "scanrs_host_inv_upper", "scanrs_host_sym_eig", "scanrs_host_sym_eig_topk", "scanrs_debug_wait_never", "scanrs_debug_barrier_alone", "scanrs_debug_arena_selftest", "scanrs_debug_dense_route", "scanrs_debug_dense_gram", "scanrs_debug_dense_gemm", "scanrs_debug_weighted_colsum", "scanrs_debug_knn_filter", "scanrs_debug_knn_last_stats", "scanrs_debug_knn_filter_params", "scanrs_init", "scanrs_release_cached_memory", "scanrs_cached_memory_bytes", "scanrs_reserve_device_memory", "scanrs_device_memory_in_use",
     "scanrs_h5_read_csc_matrix", "scanrs_h5_read_adaptive_csr_matrix", "scanrs_h5_read_matrix_metadata", "scanrs_h5_matrix_free",
     "scanrs_h5_matrix_shape", "scanrs_h5_matrix_arrays", "scanrs_h5_matrix_n_strings", "scanrs_h5_matrix_string", "scanrs_h5_matrix_removed",

@@ -1509,6 +1509,10 @@ int scanrs_mat_get_counter(scanrs_mat *m, const char *key, uint64_t *value) {
                 if (k == std::string("reshard_") + phases[i] + "_us") which = i;
             if (which < 0) fail(SCANRS_ERR_ARGUMENT, "unknown counter '%s'", key);
             *value = m->st->reshard_us[which];
+        } else if (k == "regather_plan_us" || k == "regather_pull_us" || k == "regather_finish_us") {
+            // a shard made by scanrs_multi_gather_outer / _rebalance (multi.cpp): wall clock of the plan (the sources' lengths to the host and
+            // the host plan: one phase, the same on every shard) and of the shard's own thread in pull and finish
+            *value = m->st->regather_us[k == "regather_plan_us" ? 0 : k == "regather_pull_us" ? 1 : 2];
         } else if (k == "t_layout_us") // first-call accounting: host time of the calling thread in tile layout builds ...
             *value = m->st->t_layout_us;
         else if (k == "t_side_wait_us") // ... waiting for the helper thread that builds the second orientation

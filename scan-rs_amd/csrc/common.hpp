@@ -404,6 +404,7 @@ struct Storage {
     uint64_t de_shard_tests = 0, de_shard_allreduces = 0; // the last DE call on this handle: tests this rank launched on the device, exchange steps (scanrs_mat_get_counter)
     uint64_t de_pairs_passes = 0, de_pairs_literal = 0; // the last scanrs_sseq_de_pairs on this handle: passes over the nonzeros, pairs on the literal route (scanrs_mat_get_counter)
     uint64_t reshard_us[5] = {0, 0, 0, 0, 0}; // a shard of scanrs_multi_create_inner and kin: its thread's wall clock in upload, count, split, exchange, transpose (scanrs_mat_get_counter)
+    uint64_t regather_us[3] = {0, 0, 0};  // a shard of scanrs_multi_gather_outer / _rebalance: wall clock of the plan (one phase of the calling thread, the same on every shard) and of its own thread in pull and finish (scanrs_mat_get_counter)
     int subset_scatter = 1;               // integer sums over a column list when only the other orientation exists: 1 = scattered into the result with 64-bit integer atomics from the copy that exists, 0 = the missing copy is built (subset_host.cpp)
     uint64_t subset_masked_passes = 0, subset_scatter_passes = 0; // sums over a column list made so far on this handle: from the copy whose outer dimension is the result axis / through the integer scatter (scanrs_mat_get_counter)
     uint64_t knn_blocks = 0, knn_allreduces = 0; // the last scanrs_knn_sharded on this handle: blocks of the point set searched, exchange steps (an unsharded one: 0)
@@ -672,6 +673,32 @@ void launch_reshard_pull(hipStream_t s, const uint64_t *d_from, const uint64_t *
 void reshard_check_frame(uint64_t n_outer, uint64_t n_inner, const uint64_t *indptr, const uint32_t *indices, bool values_given);
 void reshard_host_plan(const uint64_t *indptr, const uint32_t *indices, uint64_t n_outer, uint64_t n_inner, uint32_t world, uint64_t *slab_bounds,
                        uint64_t *bounds, uint64_t *moved);
+// regather.hip / regather_host.cpp: scanrs_multi_gather_outer and scanrs_multi_rebalance (multi.cpp). The sources of a
+// pull as the kernels take them, by value: shard s holds the outer vectors [bounds[s], bounds[s + 1]) of the source matrix in its own
+// arrays (nnz[s] entries; on the destination's device or a peer's).
+constexpr uint32_t REGATHER_TILE = 2048;   // output elements a workgroup of the pull owns
+constexpr uint32_t REGATHER_MAX_SHARDS = 16;
+struct RegatherSources {
+    uint32_t n = 0, _pad = 0;
+    uint64_t bounds[REGATHER_MAX_SHARDS + 1] = {};
+    uint64_t nnz[REGATHER_MAX_SHARDS] = {};
+    const uint64_t *indptr[REGATHER_MAX_SHARDS] = {};
+    const uint32_t *indices[REGATHER_MAX_SHARDS] = {};
+    const uint32_t *values[REGATHER_MAX_SHARDS] = {};
+};
+// d_len (n_vec + 1 entries): the length of source vector d_list[j] for every output vector j (+ the scan's spare entry);
+// d_place[j]: its source shard and where it begins in that shard's arrays
+void launch_regather_len(hipStream_t s, const RegatherSources &src, const uint32_t *d_list, uint64_t n_vec, unsigned long long *d_len, uint64_t *d_place);
+// the nnz entries of the destination (d_indptr: its n_vec + 1 offsets), every one read at its place in a source's arrays
+void launch_regather_pull(hipStream_t s, const RegatherSources &src, const uint64_t *d_indptr, const uint64_t *d_place, uint64_t n_vec, uint64_t nnz,
+                          uint32_t *d_out_idx, uint32_t *d_out_val);
+// the plan on host arrays (scanrs_host_plan_gather; the device path runs the same function on the indptr it assembled from the shards):
+// out_indptr (n_idx + 1): the selected matrix's; bounds (n_dst + 1): scanrs_plan_shards over it; moved (n_src x n_dst, source-major).
+// Any output may be null. Refusals: a null list, shard counts outside 1 .. 16, source bounds that do not tile the outer extent
+// (SCANRS_ERR_ARGUMENT); an index beyond the outer extent (SCANRS_ERR_INVALID).
+void regather_host_plan(const uint64_t *indptr, uint64_t n_outer, const uint64_t *src_bounds, uint32_t n_src, const uint64_t *idx, uint64_t n_idx,
+                        uint32_t n_dst, uint64_t *out_indptr, uint64_t *bounds, uint64_t *moved);
+void regather_check_list(const uint64_t *idx, uint64_t n_idx, uint64_t n_outer);
 // capi.cpp: a registered Storage with its main stream on the current device (what every handle starts from)
 SCANRS_LOCAL std::shared_ptr<Storage> new_storage(uint64_t rows, uint64_t cols, int storage);
 // comm.cpp

@@ -4,7 +4,8 @@
 // ordinary scanrs_mat handle on its own device driven by its own host thread for the duration of a call, and the
 // exchange steps go through the library's single-process group (comm.cpp). Several shards may share one device
 // (`devices` repeats an id): that is how a 1-GPU box exercises the whole path. A matrix that arrives feature-major (the reference's
-// own orientation) is sharded over its INNER dimension by the constructors further down (scanrs_multi_create_inner).
+// own orientation) is sharded over its INNER dimension by the constructors further down (scanrs_multi_create_inner); an
+// existing scanrs_multi is cut anew, reordered or moved to other devices by scanrs_multi_gather_outer / _rebalance at the end (§7n).
 #include <functional>
 #include <thread>
 
@@ -23,6 +24,12 @@ struct scanrs_multi {
         std::vector<uint64_t> slab_bounds, moved, uploaded;
     };
     std::shared_ptr<InnerInfo> inner;
+    // what scanrs_multi_gather_outer / _rebalance did (scanrs_multi_gather_info); null on every other scanrs_multi
+    struct GatherInfo {
+        uint32_t n_src = 0;
+        std::vector<uint64_t> bounds, moved, host_bytes;
+    };
+    std::shared_ptr<GatherInfo> gather;
 };
 
 using namespace scanrs;
@@ -982,6 +989,235 @@ int scanrs_multi_partition_on_thresholds(scanrs_multi *mm, const double *row_thr
     }
     if (filtered) *filtered = hf;
     if (residual) *residual = hr;
+    return SCANRS_OK;
+}
+
+// ---- gather_outer / rebalance: outer vectors move between shards -----------------------------------------------------------
+// "The outer vectors idx[0 .. n) of the whole matrix, in that order, as a freshly balanced scanrs_multi": the identity list is a
+// rebalance, another shard count or other devices a re-sharding. The result equals scanrs_multi_create of the selected triplet, and no
+// nonzero crosses the host link:
+//   plan    every SOURCE shard sends the indptr of its own vectors to the host; regather_host_plan (the code of scanrs_host_plan_gather)
+//           makes the selected matrix's indptr, cuts it with scanrs_plan_shards and counts `moved`;
+//   pull    every DESTINATION uploads its slice of the list, finds each vector's length and place in the sources' indptr arrays, scans
+//           the lengths into its own indptr and copies the entries tile by tile out of the sources' arrays, in place (regather.hip);
+//   finish  the handle adopts the arrays as they are and is finished as scanrs_mat_create finishes one: the largest count, the work
+//           items, its communicator and range.
+// The phases are separate fan_outs (the join of the shard threads is the barrier, a failing shard ends its phase for all); no wait
+// inside a phase depends on another shard, and the source's arrays are only read.
+} // extern "C"
+
+namespace {
+
+// `from` maps the memory of `to` (a destination reads a source's arrays in place)
+void enable_peer(int from, int to) {
+    if (from == to) return;
+    int can = 0;
+    SCANRS_HIP(hipDeviceCanAccessPeer(&can, from, to));
+    if (!can) fail(SCANRS_ERR_DEVICE, "devices %d and %d cannot map each other's memory", from, to);
+    SCANRS_HIP(hipSetDevice(from));
+    const hipError_t e = hipDeviceEnablePeerAccess(to, 0);
+    if (e != hipSuccess && e != hipErrorPeerAccessAlreadyEnabled) SCANRS_HIP(e);
+    (void)hipGetLastError();
+}
+
+int gather_outer(scanrs_multi *src, const uint64_t *idx, uint64_t n_idx, uint32_t n_shards, const int *devices, scanrs_multi **out) {
+    if (!out) return bad_argument("out: null output handle");
+    *out = nullptr;
+    if (!src) return bad_argument("mm: null handle");
+    const uint32_t n_src = (uint32_t)src->shards.size();
+    const uint64_t n_outer = src->bounds.back(), n_inner = src->storage == SCANRS_CSR ? src->cols : src->rows;
+    std::unique_ptr<scanrs_multi> mm;
+    int rc = guard([&] {
+        // everything that can be refused is refused here, before any device work
+        if (n_shards == 0 || n_shards > REGATHER_MAX_SHARDS) fail(SCANRS_ERR_ARGUMENT, "n_shards: 1 <= n_shards <= 16 is required (%u given)", n_shards);
+        if (n_src > REGATHER_MAX_SHARDS) fail(SCANRS_ERR_ARGUMENT, "mm: a source of more than 16 shards is not served");
+        regather_check_list(idx, n_idx, n_outer);
+        if (n_outer >= 0x7FFFFFFFull || n_inner >= 0x7FFFFFFFull) fail(SCANRS_ERR_SHAPE, "gather_outer needs dimensions below 2^31 - 1");
+        for (const scanrs_mat *h : src->shards) {
+            bool raw_map = h && !h->transposed;
+            for (size_t o = 0; raw_map && o < h->ops.size(); o++) raw_map = h->ops[o].kind == OP_INTO;
+            if (!raw_map)
+                fail(SCANRS_ERR_ARGUMENT, "gather_outer: the handle's map is not the identity (a scaling or a function has been composed); call scanrs_mat_reset_map first");
+            if (h->off_rank)
+                fail(SCANRS_ERR_ARGUMENT, "gather_outer: the handle has a low-rank offset (center / scale_and_center / normalize); call scanrs_mat_reset_map first");
+        }
+        mm = std::make_unique<scanrs_multi>();
+        mm->rows = src->storage == SCANRS_CSR ? n_idx : src->rows;
+        mm->cols = src->storage == SCANRS_CSR ? src->cols : n_idx;
+        mm->storage = src->storage;
+        bind_devices(mm.get(), n_shards, devices);
+        for (uint32_t d = 0; d < n_shards; d++)
+            for (uint32_t s = 0; s < n_src; s++) enable_peer(mm->devices[d], src->devices[s]);
+        mm->bounds.assign(n_shards + 1, 0);
+        mm->gather = std::make_shared<scanrs_multi::GatherInfo>();
+        mm->gather->n_src = n_src;
+        mm->gather->moved.assign((size_t)n_src * n_shards, 0);
+        mm->gather->host_bytes.assign(n_shards, 0);
+    });
+    if (rc != SCANRS_OK) {
+        if (mm) {
+            const std::string msg = scanrs_last_error();
+            scanrs_multi_free(mm.release());
+            set_error("%s", msg.c_str());
+        }
+        return rc;
+    }
+    scanrs_multi *raw = mm.get();
+    scanrs_multi::GatherInfo &info = *raw->gather;
+    jump_tables_prefetch(); // as scanrs_mat_create does
+    const auto t_plan = std::chrono::steady_clock::now();
+
+    // plan, 1: the lengths. Every source shard's indptr goes down (8 bytes per vector), charged to destination s mod n_shards.
+    std::vector<std::vector<uint64_t>> src_ip(n_src);
+    rc = fan_out(src, [&](size_t s) {
+        return guard([&] {
+            need_device();
+            Storage &st = *src->shards[s]->st;
+            CurrentHandle cur(&st);
+            const SparseCopy &cp = st.primary;
+            if (cp.n_outer != src->bounds[s + 1] - src->bounds[s]) fail(SCANRS_ERR_DEVICE, "internal: a source shard does not hold its range");
+            src_ip[s].assign(cp.n_outer + 1, 0);
+            SCANRS_D2H(src_ip[s].data(), cp.indptr.p, (cp.n_outer + 1) * 8, st.stream);
+            SCANRS_SYNC(st.stream); // whatever was queued on the source before this call is done before a destination reads its arrays
+        });
+    });
+    // plan, 2: on the host, the code of scanrs_host_plan_gather
+    std::vector<uint64_t> tip(n_idx + 1, 0);
+    if (rc == SCANRS_OK)
+        rc = guard([&] {
+            std::vector<uint64_t> gip(n_outer + 1, 0);
+            uint64_t first = 0;
+            for (uint32_t s = 0; s < n_src; s++) {
+                const uint64_t lo = src->bounds[s], n = src->bounds[s + 1] - lo;
+                for (uint64_t o = 0; o <= n; o++) gip[lo + o] = first + src_ip[s][o];
+                first += src_ip[s][n];
+                info.host_bytes[s % n_shards] += 8 * (n + 1);
+                std::vector<uint64_t>().swap(src_ip[s]);
+            }
+            regather_host_plan(gip.data(), n_outer, src->bounds.data(), n_src, idx, n_idx, n_shards, tip.data(), raw->bounds.data(), info.moved.data());
+        });
+    info.bounds = raw->bounds;
+    const uint64_t plan_us = (uint64_t)std::chrono::duration<double, std::micro>(std::chrono::steady_clock::now() - t_plan).count();
+
+    // pull: every destination reads its vectors out of the sources' arrays
+    if (rc == SCANRS_OK)
+        rc = fan_out(raw, [&](size_t d) {
+            return guard([&] {
+                need_device();
+                const uint64_t lo = raw->bounds[d], n_loc = raw->bounds[d + 1] - lo, nnz = tip[lo + n_loc] - tip[lo];
+                auto stp = new_storage(raw->storage == SCANRS_CSR ? n_loc : raw->rows, raw->storage == SCANRS_CSR ? raw->cols : n_loc, raw->storage);
+                auto *h = new scanrs_mat();
+                h->st = stp;
+                raw->shards[d] = h; // from here on scanrs_multi_free takes the storage down
+                Storage &st = *h->st;
+                CurrentHandle cur(&st);
+                st.regather_us[0] = plan_us; // (the plan is one phase for all shards)
+                PhaseClock clock(st.regather_us[1]);
+                RegatherSources from;
+                from.n = n_src;
+                for (uint32_t s = 0; s < n_src; s++) {
+                    const SparseCopy &cp = src->shards[s]->st->primary;
+                    from.bounds[s] = src->bounds[s];
+                    from.nnz[s] = cp.nnz;
+                    from.indptr[s] = cp.indptr.p;
+                    from.indices[s] = cp.indices.p;
+                    from.values[s] = cp.values.p;
+                }
+                from.bounds[n_src] = n_outer;
+                SparseCopy &cp = st.primary;
+                cp.n_outer = n_loc;
+                cp.n_inner = n_inner;
+                cp.nnz = nnz;
+                std::vector<uint32_t> list(n_loc);
+                for (uint64_t j = 0; j < n_loc; j++) list[j] = (uint32_t)idx[lo + j];
+                DevBuf<uint32_t> d_list(std::max<uint64_t>(1, n_loc));
+                DevBuf<uint64_t> d_place(std::max<uint64_t>(1, n_loc));
+                if (n_loc) SCANRS_HIP(hipMemcpyAsync(d_list.p, list.data(), n_loc * 4, hipMemcpyHostToDevice, st.stream));
+                cp.indptr.alloc(n_loc + 1);
+                launch_regather_len(st.stream, from, d_list.p, n_loc, reinterpret_cast<unsigned long long *>(cp.indptr.p), d_place.p);
+                select_scan_offsets(st.stream, reinterpret_cast<unsigned long long *>(cp.indptr.p), n_loc);
+                // the one value that comes back: the device's lengths add up to the plan's
+                const uint64_t got = SCANRS_D2H_VALUE(cp.indptr.p + n_loc, st.stream);
+                if (got != nnz)
+                    fail(SCANRS_ERR_DEVICE, "internal: the gathered lengths (%llu entries) do not match the plan (%llu)", (unsigned long long)got, (unsigned long long)nnz);
+                info.host_bytes[d] += 4 * n_loc + 8;
+                cp.indices.alloc(std::max<uint64_t>(1, nnz));
+                cp.values.alloc(std::max<uint64_t>(1, nnz));
+                launch_regather_pull(st.stream, from, cp.indptr.p, d_place.p, n_loc, nnz, cp.indices.p, cp.values.p);
+                SCANRS_SYNC(st.stream); // the list and the places are released on return
+            });
+        });
+
+    // finish: what scanrs_mat_create leaves behind on a validated copy, then the shard's communicator and range
+    if (rc == SCANRS_OK)
+        rc = fan_out(raw, [&](size_t d) {
+            return guard([&] {
+                scanrs_mat *h = raw->shards[d];
+                Storage &st = *h->st;
+                CurrentHandle cur(&st);
+                PhaseClock clock(st.regather_us[2]);
+                SparseCopy &cp = st.primary;
+                cp.max_value = cp.nnz ? std::max(sseq_max_count(st, cp), 1u) : 0u; // validate_copy's: the largest stored count
+                cp.build_items(st.stream);
+                device_free_flush(); // the stream is idle here
+                if (const int rc2 = scanrs_mat_set_shard_comm(h, raw->comms[d], (uint32_t)d, n_shards, raw->bounds[d], n_idx)) throw Failure{rc2};
+            });
+        });
+
+    if (rc != SCANRS_OK) {
+        const std::string msg = scanrs_last_error(); // (freeing handles must not replace the message)
+        scanrs_multi_free(mm.release());
+        set_error("%s", msg.c_str());
+        return rc;
+    }
+    *out = mm.release();
+    return SCANRS_OK;
+}
+
+} // namespace
+
+extern "C" {
+
+int scanrs_multi_gather_outer(scanrs_multi *mm, const uint64_t *idx, uint64_t n_idx, uint32_t n_shards, const int *devices, scanrs_multi **out) {
+    return gather_outer(mm, idx, n_idx, n_shards, devices, out);
+}
+
+int scanrs_multi_rebalance(scanrs_multi *mm, uint32_t n_shards, const int *devices, scanrs_multi **out) {
+    if (!out) return bad_argument("out: null output handle");
+    *out = nullptr;
+    if (!mm) return bad_argument("mm: null handle");
+    std::vector<uint64_t> all;
+    const int rc = guard([&] {
+        all.resize(mm->bounds.back());
+        for (uint64_t o = 0; o < all.size(); o++) all[o] = o;
+    });
+    if (rc != SCANRS_OK) return rc;
+    if (n_shards == 0) return gather_outer(mm, all.data(), all.size(), (uint32_t)mm->shards.size(), mm->devices.data(), out);
+    return gather_outer(mm, all.data(), all.size(), n_shards, devices, out);
+}
+
+int scanrs_multi_balance(const scanrs_multi *mm, uint64_t *shard_nnz, double *imbalance) {
+    if (!mm) return bad_argument("mm: null handle");
+    uint64_t total = 0, most = 0;
+    for (size_t i = 0; i < mm->shards.size(); i++) {
+        uint64_t x = 0;
+        if (const int rc = scanrs_mat_nnz(mm->shards[i], &x)) return rc;
+        if (shard_nnz) shard_nnz[i] = x;
+        total += x;
+        most = std::max(most, x);
+    }
+    if (imbalance) *imbalance = total ? (double)most * (double)mm->shards.size() / (double)total : 1.0; // (no nonzeros: nothing to balance)
+    return SCANRS_OK;
+}
+
+int scanrs_multi_gather_info(const scanrs_multi *mm, uint32_t *n_src, uint64_t *bounds, uint64_t *moved, uint64_t *host_bytes) {
+    if (!mm) return bad_argument("mm: null handle");
+    if (!mm->gather) return bad_argument("gather_info: this scanrs_multi was not made by scanrs_multi_gather_outer or scanrs_multi_rebalance");
+    const scanrs_multi::GatherInfo &info = *mm->gather;
+    if (n_src) *n_src = info.n_src;
+    if (bounds) std::copy(info.bounds.begin(), info.bounds.end(), bounds);
+    if (moved) std::copy(info.moved.begin(), info.moved.end(), moved);
+    if (host_bytes) std::copy(info.host_bytes.begin(), info.host_bytes.end(), host_bytes);
     return SCANRS_OK;
 }
 
