@@ -131,6 +131,30 @@ def _f64(a):
     return np.ascontiguousarray(a, dtype=np.float64)
 
 
+def _index_list(idx, prefix: str = ""):
+    """An index list for the C ABI: flattened to int64, negatives refused (`prefix` names the argument in the message), as uint64."""
+    idx = np.ascontiguousarray(np.asarray(idx).reshape(-1), dtype=np.int64)
+    if idx.size and int(idx.min()) < 0:
+        raise ScanrsError(6, prefix + "index out of range: negative index")
+    return idx.astype(np.uint64)
+
+
+def _partition_on_thresholds(fn, handle, shape, wrap, row_threshold, col_threshold, filtered, residual):
+    """The three `partition_on_thresholds` methods: `fn` is the C entry point, `shape` the [rows, cols] the kept lists are sized
+    from, `wrap` makes the object of a returned handle."""
+    rows, cols = shape
+    sel_r, sel_c = np.zeros(max(rows, 1), dtype=np.uint64), np.zeros(max(cols, 1), dtype=np.uint64)
+    n_r, n_c = ctypes.c_uint64(), ctypes.c_uint64()
+    rt = None if row_threshold is None else ctypes.byref(ctypes.c_double(row_threshold))
+    ct = None if col_threshold is None else ctypes.byref(ctypes.c_double(col_threshold))
+    hf, hr = ctypes.c_void_p(), ctypes.c_void_p()
+    _check(fn(handle, rt, ct, ctypes.byref(hf) if filtered else None, ctypes.byref(hr) if residual else None, _p(sel_r), ctypes.byref(n_r),
+              _p(sel_c), ctypes.byref(n_c)))
+    f = wrap(hf.value) if filtered else None
+    r = wrap(hr.value) if residual else None
+    return f, r, sel_r[: n_r.value].astype(np.int64), sel_c[: n_c.value].astype(np.int64)
+
+
 class AtomicSnoop:
     """`snoop::AtomicSnoop` (snoop/src/lib.rs:117-226): cancel flag + progress fraction."""
 
@@ -416,13 +440,9 @@ class AdaptiveMat:
         return out
 
     # -- statistics over a list of columns (mat.rs:279-282, 333-374, 414-583) ---------------
-    @staticmethod
-    def _col_list(cols):
-        cols = np.ascontiguousarray(np.asarray(cols).reshape(-1), dtype=np.int64)
-        if cols.size and int(cols.min()) < 0:
-            raise ScanrsError(6, "index out of range: negative index")
-        return cols.astype(np.uint64)
-
+    # One implementation per statistic serves the plain, the *_sharded and the MultiMat methods. `head`: the leading arguments of the
+    # C call (the handle; MultiMat adds `transposed`); n_rows / n_out: where the length of a result comes from, read after the lists
+    # have been checked.
     @staticmethod
     def _sum_dtype(dtype):
         dt = np.dtype(dtype)
@@ -439,45 +459,58 @@ class AdaptiveMat:
             raise OverflowError(f"a sum of {int(out.max())} does not fit in uint32")
         return out.astype(np.uint32)
 
-    def _sums_over(self, fn_u64, fn_f64, cols, dtype, n_out):
-        dt, cols = self._sum_dtype(dtype), self._col_list(cols)
-        out = np.zeros(n_out(cols), dtype=np.float64 if dt == np.dtype(np.float64) else np.uint64)
-        _check((fn_f64 if dt == np.dtype(np.float64) else fn_u64)(self._h, _p(cols), ctypes.c_uint64(cols.shape[0]), _p(out)))
-        return self._narrow(out, dt)
+    @staticmethod
+    def _sums_over(head, fn_u64, fn_f64, cols, dtype, n_out):
+        dt, cols = AdaptiveMat._sum_dtype(dtype), _index_list(cols)
+        is_f = dt == np.dtype(np.float64)
+        out = np.zeros(n_out(cols), dtype=np.float64 if is_f else np.uint64)
+        _check((fn_f64 if is_f else fn_u64)(*head, _p(cols), ctypes.c_uint64(cols.shape[0]), _p(out)))
+        return AdaptiveMat._narrow(out, dt)
+
+    @staticmethod
+    def _sum_rows_dual(head, fn_u64, fn_f64, n_rows, cols1, cols2, dtype, snoop):
+        dt, c1, c2 = AdaptiveMat._sum_dtype(dtype), _index_list(cols1), _index_list(cols2)
+        is_f = dt == np.dtype(np.float64)
+        o1, o2 = (np.zeros(n_rows(), dtype=np.float64 if is_f else np.uint64) for _ in range(2))
+        sn, _keep = _snoop_arg(snoop)
+        _check((fn_f64 if is_f else fn_u64)(*head, _p(c1), ctypes.c_uint64(c1.shape[0]), _p(c2), ctypes.c_uint64(c2.shape[0]), sn, _p(o1), _p(o2)))
+        return AdaptiveMat._narrow(o1, dt), AdaptiveMat._narrow(o2, dt)
+
+    @staticmethod
+    def _mean_rows(head, fn, n_rows, cols):
+        cols = _index_list(cols)
+        out = np.zeros(n_rows())
+        _check(fn(*head, _p(cols), ctypes.c_uint64(cols.shape[0]), _p(out)))
+        return out
+
+    @staticmethod
+    def _mean_var_rows(head, fn, n_rows, cols):
+        cols = _index_list(cols)
+        mean, var = np.zeros(n_rows()), np.zeros(n_rows())
+        _check(fn(*head, _p(cols), ctypes.c_uint64(cols.shape[0]), _p(mean), _p(var)))
+        return mean, var
 
     def sum_rows(self, cols, dtype=np.float64):
         """`sum_rows::<O>(cols)` (mat.rs:449-481): per row, the sum over the listed columns (strictly ascending). Integer dtypes read
         the raw counts (exact), float64 the mapped values."""
-        return self._sums_over(_lib.scanrs_mat_sum_rows_u64, _lib.scanrs_mat_sum_rows_f64, cols, dtype, lambda c: self.rows())
+        return self._sums_over((self._h,), _lib.scanrs_mat_sum_rows_u64, _lib.scanrs_mat_sum_rows_f64, cols, dtype, lambda c: self.rows())
 
     def sum_cols(self, cols, dtype=np.float64):
         """`sum_cols::<O>(cols)` (mat.rs:414-446): per listed column, in list order, the sum over all rows."""
-        return self._sums_over(_lib.scanrs_mat_sum_cols_u64, _lib.scanrs_mat_sum_cols_f64, cols, dtype, lambda c: c.shape[0])
+        return self._sums_over((self._h,), _lib.scanrs_mat_sum_cols_u64, _lib.scanrs_mat_sum_cols_f64, cols, dtype, lambda c: c.shape[0])
 
     def sum_rows_dual(self, cols1, cols2, dtype=np.float64, snoop=None):
         """`sum_rows_dual` / `sum_rows_dual_with_cancellation` (mat.rs:484-583): `sum_rows` over two lists from one walk; the lists
         may overlap."""
-        dt, c1, c2 = self._sum_dtype(dtype), self._col_list(cols1), self._col_list(cols2)
-        is_f = dt == np.dtype(np.float64)
-        o1, o2 = (np.zeros(self.rows(), dtype=np.float64 if is_f else np.uint64) for _ in range(2))
-        sn, _keep = _snoop_arg(snoop)
-        fn = _lib.scanrs_mat_sum_rows_dual_f64 if is_f else _lib.scanrs_mat_sum_rows_dual_u64
-        _check(fn(self._h, _p(c1), ctypes.c_uint64(c1.shape[0]), _p(c2), ctypes.c_uint64(c2.shape[0]), sn, _p(o1), _p(o2)))
-        return self._narrow(o1, dt), self._narrow(o2, dt)
+        return self._sum_rows_dual((self._h,), _lib.scanrs_mat_sum_rows_dual_u64, _lib.scanrs_mat_sum_rows_dual_f64, self.rows, cols1, cols2, dtype, snoop)
 
     def mean_rows(self, cols):
         """`mean_rows(cols)` (mat.rs:279-282); an empty list gives NaN."""
-        cols = self._col_list(cols)
-        out = np.zeros(self.rows())
-        _check(_lib.scanrs_mat_mean_rows(self._h, _p(cols), ctypes.c_uint64(cols.shape[0]), _p(out)))
-        return out
+        return self._mean_rows((self._h,), _lib.scanrs_mat_mean_rows, self.rows, cols)
 
     def mean_var_rows(self, cols):
         """`mean_var_rows(cols)` (mat.rs:333-374): per row, mean and E[x^2] - E[x]^2 of the mapped values over the listed columns."""
-        cols = self._col_list(cols)
-        mean, var = np.zeros(self.rows()), np.zeros(self.rows())
-        _check(_lib.scanrs_mat_mean_var_rows(self._h, _p(cols), ctypes.c_uint64(cols.shape[0]), _p(mean), _p(var)))
-        return mean, var
+        return self._mean_var_rows((self._h,), _lib.scanrs_mat_mean_var_rows, self.rows, cols)
 
     # -- the same over a sharded handle: collective, global lists, complete outputs on every rank (DESIGN §7k) ----
     def _rows_all(self) -> int:
@@ -486,35 +519,26 @@ class AdaptiveMat:
 
     def sum_rows_sharded(self, cols, dtype=np.float64):
         """`scanrs_mat_sum_rows_*_sharded`: `sum_rows` over a sharded handle; every rank calls it with the same (global) list."""
-        return self._sums_over(_lib.scanrs_mat_sum_rows_u64_sharded, _lib.scanrs_mat_sum_rows_f64_sharded, cols, dtype, lambda c: self._rows_all())
+        return self._sums_over((self._h,), _lib.scanrs_mat_sum_rows_u64_sharded, _lib.scanrs_mat_sum_rows_f64_sharded, cols, dtype,
+                               lambda c: self._rows_all())
 
     def sum_cols_sharded(self, cols, dtype=np.float64):
         """`scanrs_mat_sum_cols_*_sharded` (see `sum_rows_sharded`)."""
-        return self._sums_over(_lib.scanrs_mat_sum_cols_u64_sharded, _lib.scanrs_mat_sum_cols_f64_sharded, cols, dtype, lambda c: c.shape[0])
+        return self._sums_over((self._h,), _lib.scanrs_mat_sum_cols_u64_sharded, _lib.scanrs_mat_sum_cols_f64_sharded, cols, dtype,
+                               lambda c: c.shape[0])
 
     def sum_rows_dual_sharded(self, cols1, cols2, dtype=np.float64, snoop=None):
         """`scanrs_mat_sum_rows_dual_*_sharded` (see `sum_rows_sharded`)."""
-        dt, c1, c2 = self._sum_dtype(dtype), self._col_list(cols1), self._col_list(cols2)
-        is_f = dt == np.dtype(np.float64)
-        o1, o2 = (np.zeros(self._rows_all(), dtype=np.float64 if is_f else np.uint64) for _ in range(2))
-        sn, _keep = _snoop_arg(snoop)
-        fn = _lib.scanrs_mat_sum_rows_dual_f64_sharded if is_f else _lib.scanrs_mat_sum_rows_dual_u64_sharded
-        _check(fn(self._h, _p(c1), ctypes.c_uint64(c1.shape[0]), _p(c2), ctypes.c_uint64(c2.shape[0]), sn, _p(o1), _p(o2)))
-        return self._narrow(o1, dt), self._narrow(o2, dt)
+        return self._sum_rows_dual((self._h,), _lib.scanrs_mat_sum_rows_dual_u64_sharded, _lib.scanrs_mat_sum_rows_dual_f64_sharded, self._rows_all,
+                                   cols1, cols2, dtype, snoop)
 
     def mean_rows_sharded(self, cols):
         """`scanrs_mat_mean_rows_sharded` (see `sum_rows_sharded`)."""
-        cols = self._col_list(cols)
-        out = np.zeros(self._rows_all())
-        _check(_lib.scanrs_mat_mean_rows_sharded(self._h, _p(cols), ctypes.c_uint64(cols.shape[0]), _p(out)))
-        return out
+        return self._mean_rows((self._h,), _lib.scanrs_mat_mean_rows_sharded, self._rows_all, cols)
 
     def mean_var_rows_sharded(self, cols):
         """`scanrs_mat_mean_var_rows_sharded` (see `sum_rows_sharded`)."""
-        cols = self._col_list(cols)
-        mean, var = np.zeros(self._rows_all()), np.zeros(self._rows_all())
-        _check(_lib.scanrs_mat_mean_var_rows_sharded(self._h, _p(cols), ctypes.c_uint64(cols.shape[0]), _p(mean), _p(var)))
-        return mean, var
+        return self._mean_var_rows((self._h,), _lib.scanrs_mat_mean_var_rows_sharded, self._rows_all, cols)
 
     def to_dense(self):
         r, c = self.shape()
@@ -524,10 +548,7 @@ class AdaptiveMat:
 
     # -- select / partition / download (mat.rs:207-241, 766-888, 1004-1071) --------------
     def _select(self, fn, idx) -> "AdaptiveMat":
-        idx = np.ascontiguousarray(np.asarray(idx).reshape(-1), dtype=np.int64)
-        if idx.size and int(idx.min()) < 0:
-            raise ScanrsError(6, "index out of range: negative index")
-        idx = idx.astype(np.uint64)
+        idx = _index_list(idx)
         h = ctypes.c_void_p()
         _check(fn(self._h, _p(idx), ctypes.c_uint64(idx.shape[0]), ctypes.byref(h)))
         return AdaptiveMat(h.value)
@@ -544,18 +565,8 @@ class AdaptiveMat:
                                 residual: bool = True):
         """`partition_on_thresholds` (mat.rs:774-888): (filtered, residual, selected_rows, selected_cols); a threshold may be None.
         filtered=False / residual=False: that matrix is not built (None in its place)."""
-        rows, cols = self.shape()
-        sel_r, sel_c = np.zeros(max(rows, 1), dtype=np.uint64), np.zeros(max(cols, 1), dtype=np.uint64)
-        n_r, n_c = ctypes.c_uint64(), ctypes.c_uint64()
-        rt = None if row_threshold is None else ctypes.byref(ctypes.c_double(row_threshold))
-        ct = None if col_threshold is None else ctypes.byref(ctypes.c_double(col_threshold))
-        hf, hr = ctypes.c_void_p(), ctypes.c_void_p()
-        _check(_lib.scanrs_mat_partition_on_thresholds(self._h, rt, ct, ctypes.byref(hf) if filtered else None,
-                                                       ctypes.byref(hr) if residual else None, _p(sel_r), ctypes.byref(n_r), _p(sel_c),
-                                                       ctypes.byref(n_c)))
-        f = AdaptiveMat(hf.value) if filtered else None
-        r = AdaptiveMat(hr.value) if residual else None
-        return f, r, sel_r[: n_r.value].astype(np.int64), sel_c[: n_c.value].astype(np.int64)
+        return _partition_on_thresholds(_lib.scanrs_mat_partition_on_thresholds, self._h, self.shape(), AdaptiveMat, row_threshold, col_threshold,
+                                        filtered, residual)
 
     def partition_on_threshold(self, threshold: float):
         """`partition_on_threshold` (mat.rs:768-770)."""
@@ -593,18 +604,8 @@ class AdaptiveMat:
                                         residual: bool = True):
         """`scanrs_mat_partition_on_thresholds_sharded`: collective `partition_on_thresholds` of a sharded handle. The kept lists are
         those of the whole matrix, the same on every rank; the two matrices are this rank's shards of the results."""
-        rows, cols = self._global_shape()
-        sel_r, sel_c = np.zeros(max(rows, 1), dtype=np.uint64), np.zeros(max(cols, 1), dtype=np.uint64)
-        n_r, n_c = ctypes.c_uint64(), ctypes.c_uint64()
-        rt = None if row_threshold is None else ctypes.byref(ctypes.c_double(row_threshold))
-        ct = None if col_threshold is None else ctypes.byref(ctypes.c_double(col_threshold))
-        hf, hr = ctypes.c_void_p(), ctypes.c_void_p()
-        _check(_lib.scanrs_mat_partition_on_thresholds_sharded(self._h, rt, ct, ctypes.byref(hf) if filtered else None,
-                                                               ctypes.byref(hr) if residual else None, _p(sel_r), ctypes.byref(n_r), _p(sel_c),
-                                                               ctypes.byref(n_c)))
-        f = self._bound_like_self(AdaptiveMat(hf.value)) if filtered else None
-        r = self._bound_like_self(AdaptiveMat(hr.value)) if residual else None
-        return f, r, sel_r[: n_r.value].astype(np.int64), sel_c[: n_c.value].astype(np.int64)
+        return _partition_on_thresholds(_lib.scanrs_mat_partition_on_thresholds_sharded, self._h, self._global_shape(),
+                                        lambda h: self._bound_like_self(AdaptiveMat(h)), row_threshold, col_threshold, filtered, residual)
 
     def to_csmat(self):
         """`to_csmat` of the stored counts (mat.rs:207-241): (indptr u64, indices u32, data u32) in the handle's storage flag."""
@@ -1231,10 +1232,15 @@ class MultiMat:
         _check(_lib.scanrs_multi_create_info(self._h, _p(sb), _p(mv), _p(up)))
         return {"slab_bounds": sb, "moved": mv, "uploaded_bytes": up}
 
-    def shard_csmat(self, i: int):
-        """`scanrs_mat_to_csmat` of shard i: (indptr u64, indices u32, data u32) of its own outer vectors."""
+    def _shard_handle(self, i: int) -> ctypes.c_void_p:
+        """The `scanrs_mat` handle of shard i (`scanrs_multi_shard`); it stays the MultiMat's own."""
         h = ctypes.c_void_p()
         _check(_lib.scanrs_multi_shard(self._h, ctypes.c_uint32(i), ctypes.byref(h), None, None, None))
+        return h
+
+    def shard_csmat(self, i: int):
+        """`scanrs_mat_to_csmat` of shard i: (indptr u64, indices u32, data u32) of its own outer vectors."""
+        h = self._shard_handle(i)
         r, c, nnz = ctypes.c_uint64(), ctypes.c_uint64(), ctypes.c_uint64()
         _check(_lib.scanrs_mat_shape(h, ctypes.byref(r), ctypes.byref(c)))
         _check(_lib.scanrs_mat_nnz(h, ctypes.byref(nnz)))
@@ -1272,10 +1278,7 @@ class MultiMat:
         return cls((data, indices.astype(np.int64), indptr.astype(np.int64)), shape=tuple(self.shape()))
 
     def _select(self, fn, idx) -> "MultiMat":
-        idx = np.ascontiguousarray(np.asarray(idx).reshape(-1), dtype=np.int64)
-        if idx.size and int(idx.min()) < 0:
-            raise ScanrsError(6, "index out of range: negative index")
-        idx = idx.astype(np.uint64)
+        idx = _index_list(idx)
         h = ctypes.c_void_p()
         _check(fn(self._h, _p(idx), ctypes.c_uint64(idx.shape[0]), ctypes.byref(h)))
         return MultiMat._from_handle(h.value)
@@ -1295,10 +1298,7 @@ class MultiMat:
         dimension: the rows of a CSR matrix, the columns of a CSC one; any order, repeats allowed), in list order, as a freshly
         balanced MultiMat over `n_shards` shards (None: as many as this one) on `devices` (None: this one's when the shard count
         stays, else 0 .. n_shards-1). It equals `MultiMat(...)` of the selected triplet bit for bit; no nonzero crosses the host link."""
-        idx = np.ascontiguousarray(np.asarray(idx).reshape(-1), dtype=np.int64)
-        if idx.size and int(idx.min()) < 0:
-            raise ScanrsError(6, "idx: index out of range: negative index")
-        idx = idx.astype(np.uint64)
+        idx = _index_list(idx, "idx: ")
         if n_shards is None:
             n_shards = self.n_shards
             if devices is None:
@@ -1345,18 +1345,8 @@ class MultiMat:
         """`scanrs_multi_partition_on_thresholds`: (filtered, residual, selected_rows, selected_cols) as `AdaptiveMat.partition_on_thresholds`
         gives them, the two matrices as MultiMat objects; every output equals the unsharded call's. The shards keep what the filter
         left them: `.rebalance(consume=True)` on a result cuts it anew and frees the unbalanced intermediate."""
-        rows, cols = self.shape()
-        sel_r, sel_c = np.zeros(max(rows, 1), dtype=np.uint64), np.zeros(max(cols, 1), dtype=np.uint64)
-        n_r, n_c = ctypes.c_uint64(), ctypes.c_uint64()
-        rt = None if row_threshold is None else ctypes.byref(ctypes.c_double(row_threshold))
-        ct = None if col_threshold is None else ctypes.byref(ctypes.c_double(col_threshold))
-        hf, hr = ctypes.c_void_p(), ctypes.c_void_p()
-        _check(_lib.scanrs_multi_partition_on_thresholds(self._h, rt, ct, ctypes.byref(hf) if filtered else None,
-                                                         ctypes.byref(hr) if residual else None, _p(sel_r), ctypes.byref(n_r), _p(sel_c),
-                                                         ctypes.byref(n_c)))
-        f = MultiMat._from_handle(hf.value) if filtered else None
-        r = MultiMat._from_handle(hr.value) if residual else None
-        return f, r, sel_r[: n_r.value].astype(np.int64), sel_c[: n_c.value].astype(np.int64)
+        return _partition_on_thresholds(_lib.scanrs_multi_partition_on_thresholds, self._h, self.shape(), MultiMat._from_handle, row_threshold,
+                                        col_threshold, filtered, residual)
 
     def partition_on_threshold(self, threshold: float):
         return self.partition_on_thresholds(threshold, threshold)
@@ -1366,42 +1356,26 @@ class MultiMat:
     def _view_rows(self, transposed: bool) -> int:
         return self.shape()[1 if transposed else 0]
 
-    def _sums_over(self, fn_u64, fn_f64, cols, dtype, n_out, transposed):
-        dt, cols = AdaptiveMat._sum_dtype(dtype), AdaptiveMat._col_list(cols)
-        is_f = dt == np.dtype(np.float64)
-        out = np.zeros(n_out(cols), dtype=np.float64 if is_f else np.uint64)
-        _check((fn_f64 if is_f else fn_u64)(self._h, ctypes.c_int(int(transposed)), _p(cols), ctypes.c_uint64(cols.shape[0]), _p(out)))
-        return AdaptiveMat._narrow(out, dt)
+    def _head(self, transposed: bool):
+        return (self._h, ctypes.c_int(int(transposed)))
 
     def sum_rows(self, cols, dtype=np.float64, transposed: bool = False):
-        return self._sums_over(_lib.scanrs_multi_sum_rows_u64, _lib.scanrs_multi_sum_rows_f64, cols, dtype,
-                               lambda c: self._view_rows(transposed), transposed)
+        return AdaptiveMat._sums_over(self._head(transposed), _lib.scanrs_multi_sum_rows_u64, _lib.scanrs_multi_sum_rows_f64, cols, dtype,
+                                      lambda c: self._view_rows(transposed))
 
     def sum_cols(self, cols, dtype=np.float64, transposed: bool = False):
-        return self._sums_over(_lib.scanrs_multi_sum_cols_u64, _lib.scanrs_multi_sum_cols_f64, cols, dtype, lambda c: c.shape[0], transposed)
+        return AdaptiveMat._sums_over(self._head(transposed), _lib.scanrs_multi_sum_cols_u64, _lib.scanrs_multi_sum_cols_f64, cols, dtype,
+                                      lambda c: c.shape[0])
 
     def sum_rows_dual(self, cols1, cols2, dtype=np.float64, snoop=None, transposed: bool = False):
-        dt, c1, c2 = AdaptiveMat._sum_dtype(dtype), AdaptiveMat._col_list(cols1), AdaptiveMat._col_list(cols2)
-        is_f = dt == np.dtype(np.float64)
-        o1, o2 = (np.zeros(self._view_rows(transposed), dtype=np.float64 if is_f else np.uint64) for _ in range(2))
-        sn, _keep = _snoop_arg(snoop)
-        fn = _lib.scanrs_multi_sum_rows_dual_f64 if is_f else _lib.scanrs_multi_sum_rows_dual_u64
-        _check(fn(self._h, ctypes.c_int(int(transposed)), _p(c1), ctypes.c_uint64(c1.shape[0]), _p(c2), ctypes.c_uint64(c2.shape[0]), sn,
-                  _p(o1), _p(o2)))
-        return AdaptiveMat._narrow(o1, dt), AdaptiveMat._narrow(o2, dt)
+        return AdaptiveMat._sum_rows_dual(self._head(transposed), _lib.scanrs_multi_sum_rows_dual_u64, _lib.scanrs_multi_sum_rows_dual_f64,
+                                          lambda: self._view_rows(transposed), cols1, cols2, dtype, snoop)
 
     def mean_rows(self, cols, transposed: bool = False):
-        cols = AdaptiveMat._col_list(cols)
-        out = np.zeros(self._view_rows(transposed))
-        _check(_lib.scanrs_multi_mean_rows(self._h, ctypes.c_int(int(transposed)), _p(cols), ctypes.c_uint64(cols.shape[0]), _p(out)))
-        return out
+        return AdaptiveMat._mean_rows(self._head(transposed), _lib.scanrs_multi_mean_rows, lambda: self._view_rows(transposed), cols)
 
     def mean_var_rows(self, cols, transposed: bool = False):
-        cols = AdaptiveMat._col_list(cols)
-        mean, var = np.zeros(self._view_rows(transposed)), np.zeros(self._view_rows(transposed))
-        _check(_lib.scanrs_multi_mean_var_rows(self._h, ctypes.c_int(int(transposed)), _p(cols), ctypes.c_uint64(cols.shape[0]), _p(mean),
-                                               _p(var)))
-        return mean, var
+        return AdaptiveMat._mean_var_rows(self._head(transposed), _lib.scanrs_multi_mean_var_rows, lambda: self._view_rows(transposed), cols)
 
     def compose_scale_axis(self, axis: int, factors):
         """`compose_map(ScaleAxis::new(Axis(axis), factors))` on every shard (`scanrs_mat_compose_scale_axis`); `factors` spans the whole
@@ -1411,8 +1385,7 @@ class MultiMat:
             raise ScanrsError(1, "Dimension mismatch")
         sharded_axis = 0 if self.storage == CSR else 1
         for i, (_dev, lo, hi) in enumerate(self.shard_ranges()):
-            h = ctypes.c_void_p()
-            _check(_lib.scanrs_multi_shard(self._h, ctypes.c_uint32(i), ctypes.byref(h), None, None, None))
+            h = self._shard_handle(i)
             part = np.ascontiguousarray(f[lo:hi]) if axis == sharded_axis else f
             if part.shape[0] == 0:
                 part = np.zeros(1)  # (a shard without vectors: nothing is read)
@@ -1421,9 +1394,7 @@ class MultiMat:
 
     def _with_shard(self, i: int, fn):
         """fn(shard i as an AdaptiveMat); the handle stays the MultiMat's own."""
-        h = ctypes.c_void_p()
-        _check(_lib.scanrs_multi_shard(self._h, ctypes.c_uint32(i), ctypes.byref(h), None, None, None))
-        b = AdaptiveMat(h.value)
+        b = AdaptiveMat(self._shard_handle(i).value)
         try:
             return fn(b)
         finally:
@@ -1441,9 +1412,7 @@ class MultiMat:
     def reset_map(self):
         """`scanrs_mat_reset_map` on every shard."""
         for i in range(self.n_shards):
-            h = ctypes.c_void_p()
-            _check(_lib.scanrs_multi_shard(self._h, ctypes.c_uint32(i), ctypes.byref(h), None, None, None))
-            _check(_lib.scanrs_mat_reset_map(h))
+            _check(_lib.scanrs_mat_reset_map(self._shard_handle(i)))
         return self
 
     def shard_ranges(self):
@@ -1504,17 +1473,14 @@ class MultiMat:
 
     def counter(self, key: str, shard: int = 0) -> int:
         """`scanrs_mat_get_counter` of shard `shard` (e.g. "de_shard_tests", "de_shard_allreduces")."""
-        h, v = ctypes.c_void_p(), ctypes.c_uint64()
-        _check(_lib.scanrs_multi_shard(self._h, ctypes.c_uint32(shard), ctypes.byref(h), None, None, None))
-        _check(_lib.scanrs_mat_get_counter(h, key.encode(), ctypes.byref(v)))
+        v = ctypes.c_uint64()
+        _check(_lib.scanrs_mat_get_counter(self._shard_handle(shard), key.encode(), ctypes.byref(v)))
         return int(v.value)
 
     def set_option(self, key: str, value: float):
         """`scanrs_mat_set_option` on every shard (e.g. "merge_fused")."""
         for i in range(self.n_shards):
-            h = ctypes.c_void_p()
-            _check(_lib.scanrs_multi_shard(self._h, ctypes.c_uint32(i), ctypes.byref(h), None, None, None))
-            _check(_lib.scanrs_mat_set_option(h, key.encode(), ctypes.c_double(value)))
+            _check(_lib.scanrs_mat_set_option(self._shard_handle(i), key.encode(), ctypes.c_double(value)))
         return self
 
     def run_pca_irlba(self, k: int, tol: float = 1e-4, max_iter: int = 50, v0=None):

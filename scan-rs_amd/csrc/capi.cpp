@@ -67,12 +67,6 @@ DevMap scanrs_mat::dev_map(bool outer_is_view_row) const {
 
 namespace scanrs {
 
-static bool map_is_raw(const scanrs_mat *m) {
-    for (const auto &op : m->ops)
-        if (op.kind != OP_INTO) return false;
-    return true;
-}
-
 // the copy whose outer dimension is the view's rows (true) or cols (false)
 static SparseCopy &copy_outer_view_rows(scanrs_mat *m, bool view_rows) {
     return m->st->copy_with_outer_rows(view_rows != m->transposed);

@@ -16,11 +16,6 @@
 
 namespace scanrs {
 
-template <typename T>
-static void h2d(T *d, const T *h, size_t n, hipStream_t s) {
-    if (n) SCANRS_HIP(hipMemcpyAsync(d, h, n * sizeof(T), hipMemcpyHostToDevice, s));
-}
-
 // ---- linkage.rs -------------------------------------------------------------------------------------------------------------------
 void cluster_pdist(const double *x, uint64_t m, uint32_t d, double *out) {
     uint64_t k = 0;
@@ -472,7 +467,7 @@ void merge_clusters_run(Storage &st, const SparseCopy &cp, bool gene_major, uint
             const uint32_t leaf0 = (uint32_t)z[i * 4], leaf1 = (uint32_t)z[i * 4 + 1];
             if (!seen_pairs.insert({members[leaf0], members[leaf1]}).second) continue;
             // CancelProgress::check (snoop/src/lib.rs:37-58) before every candidate
-            if (snoop && snoop->cancel && __atomic_load_n(snoop->cancel, __ATOMIC_RELAXED)) fail(SCANRS_ERR_CANCELLED, "cancellation error");
+            snoop_check(snoop);
             Candidate cd;
             if (fused)
                 from_sums(leaf0, leaf1, cd);

@@ -508,6 +508,29 @@ struct scanrs_mat {
 
 namespace scanrs {
 
+// no link of the handle's map changes a value: it still shows the stored counts
+SCANRS_LOCAL inline bool map_is_raw(const scanrs_mat *m) {
+    for (const auto &op : m->ops)
+        if (op.kind != OP_INTO) return false;
+    return true;
+}
+
+// CancelProgress::check (snoop/src/lib.rs:37-58): fails with SCANRS_ERR_CANCELLED once the flag is set (sn may be null)
+SCANRS_LOCAL inline void snoop_check(const scanrs_snoop *sn) {
+    if (sn && sn->cancel && __atomic_load_n(sn->cancel, __ATOMIC_RELAXED)) fail(SCANRS_ERR_CANCELLED, "cancellation error");
+}
+// CancelProgress::set_progress_check (snoop/src/lib.rs:45-57): the cancel test, then the progress report
+SCANRS_LOCAL inline void snoop_poll(const scanrs_snoop *sn, double progress) {
+    snoop_check(sn);
+    if (sn && sn->progress) sn->progress(sn->ctx, progress);
+}
+
+// n values host -> device on stream s (nothing is queued for n == 0; `h` must outlive the copy)
+template <typename T>
+SCANRS_LOCAL inline void h2d(T *d, const T *h, size_t n, hipStream_t s) {
+    if (n) SCANRS_HIP(hipMemcpyAsync(d, h, n * sizeof(T), hipMemcpyHostToDevice, s));
+}
+
 // ---- kernels.hip launchers ----------------------------------------------------------------
 // out[n_outer x l] = S * X (+ a * w) where S is `cp` seen through `map`.
 // off_a: n_outer x rank (row-major) or null; off_w: rank x l (ld = ldw).

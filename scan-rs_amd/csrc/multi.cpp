@@ -82,6 +82,32 @@ int bad_argument(const char *msg) {
     return SCANRS_ERR_ARGUMENT;
 }
 
+// ---- the constructor frame: what everything that makes a scanrs_multi shares ------------------------------------
+// 1 <= n_shards <= 16 in the words of the entry point (`msg` may print the count with %u)
+void check_shard_count(uint32_t n_shards, const char *msg) {
+    if (n_shards == 0 || n_shards > REGATHER_MAX_SHARDS) fail(SCANRS_ERR_ARGUMENT, msg, n_shards);
+}
+
+// the checks of scanrs_multi_create, which every inner-sharding constructor inherits (a missing triplet is refused in the words of a bad count)
+void check_frame(bool have_triplet, uint32_t n_shards, int storage, scanrs_multi **out) {
+    if (!out) fail(SCANRS_ERR_ARGUMENT, "null output handle");
+    *out = nullptr;
+    check_shard_count(have_triplet ? n_shards : 0, "1 <= n_shards <= 16 and a triplet are required");
+    if (storage != SCANRS_CSR && storage != SCANRS_CSC) fail(SCANRS_ERR_ARGUMENT, "storage must be 0 (CSR) or 1 (CSC)");
+}
+
+// `from` maps the memory of `to` (the one-shot all-reduce reads peers' partial sums in place, a destination of gather_outer a source's arrays)
+void enable_peer(int from, int to) {
+    if (from == to) return;
+    int can = 0;
+    SCANRS_HIP(hipDeviceCanAccessPeer(&can, from, to));
+    if (!can) fail(SCANRS_ERR_DEVICE, "devices %d and %d cannot map each other's memory", from, to);
+    SCANRS_HIP(hipSetDevice(from));
+    const hipError_t e = hipDeviceEnablePeerAccess(to, 0);
+    if (e != hipSuccess && e != hipErrorPeerAccessAlreadyEnabled) SCANRS_HIP(e);
+    (void)hipGetLastError();
+}
+
 // the devices of a new scanrs_multi (`devices` null: 0 .. n_shards-1; ids may repeat), peer access between every pair of distinct ones,
 // the group and one communicator per shard
 void bind_devices(scanrs_multi *mm, uint32_t n_shards, const int *devices) {
@@ -92,21 +118,121 @@ void bind_devices(scanrs_multi *mm, uint32_t n_shards, const int *devices) {
         if (d < 0 || d >= n_dev) fail(SCANRS_ERR_ARGUMENT, "device %d of shard %u does not exist (%d visible)", d, i, n_dev);
         mm->devices.push_back(d);
     }
-    // peer access between every pair of distinct devices (the one-shot all-reduce reads peers' partial sums in place)
     for (uint32_t i = 0; i < n_shards; i++)
-        for (uint32_t j = 0; j < n_shards; j++) {
-            if (mm->devices[i] == mm->devices[j]) continue;
-            int can = 0;
-            SCANRS_HIP(hipDeviceCanAccessPeer(&can, mm->devices[i], mm->devices[j]));
-            if (!can) fail(SCANRS_ERR_DEVICE, "devices %d and %d cannot map each other's memory", mm->devices[i], mm->devices[j]);
-            SCANRS_HIP(hipSetDevice(mm->devices[i]));
-            const hipError_t e = hipDeviceEnablePeerAccess(mm->devices[j], 0);
-            if (e != hipSuccess && e != hipErrorPeerAccessAlreadyEnabled) SCANRS_HIP(e);
-            (void)hipGetLastError();
-        }
+        for (uint32_t j = 0; j < n_shards; j++) enable_peer(mm->devices[i], mm->devices[j]);
     mm->group = local_group_make(n_shards);
     mm->shards.assign(n_shards, nullptr);
     for (uint32_t i = 0; i < n_shards; i++) mm->comms.push_back(comm_make_local(mm->group, i));
+}
+
+// shard i's empty handle of the given local shape, made on the current device and published: from here on scanrs_multi_free takes the
+// storage down
+scanrs_mat *make_shard(scanrs_multi *mm, size_t i, uint64_t rows, uint64_t cols) {
+    auto stp = new_storage(rows, cols, mm->storage);
+    auto *h = new scanrs_mat();
+    h->st = stp;
+    mm->shards[i] = h;
+    return h;
+}
+
+// Finishes shard d over a validated copy as scanrs_mat_create finishes a handle: the largest stored count (validate_copy's), the work
+// items (of an empty copy only with `items_always`), then() for what the constructor still builds from the copy, the flush on the
+// idle stream, and the shard's communicator and range out of `outer_global`.
+template <typename F>
+void finish_shard(scanrs_multi *mm, size_t d, SparseCopy &cp, bool items_always, uint64_t outer_global, F &&then) {
+    scanrs_mat *h = mm->shards[d];
+    Storage &st = *h->st;
+    cp.max_value = cp.nnz ? std::max(sseq_max_count(st, cp), 1u) : 0u;
+    if (cp.nnz || items_always) cp.build_items(st.stream);
+    then();
+    device_free_flush();
+    if (const int rc = scanrs_mat_set_shard_comm(h, mm->comms[d], (uint32_t)d, (uint32_t)mm->shards.size(), mm->bounds[d], outer_global)) throw Failure{rc};
+}
+
+extern "C" { // (free_shards and shard_snoop have C names in the library's symbol table, which this file leaves as it found it)
+
+void free_shards(scanrs_multi *mm, std::vector<scanrs_mat *> &made) {
+    for (size_t i = 0; i < made.size(); i++) {
+        if (!made[i]) continue;
+        (void)hipSetDevice(mm->devices[i]);
+        scanrs_mat_free(made[i]);
+        made[i] = nullptr;
+    }
+}
+
+// the snoop of shard i: every shard polls the cancel flag at the same points; only shard 0 reports progress
+const scanrs_snoop *shard_snoop(const scanrs_snoop *snoop, size_t i, scanrs_snoop &sn) {
+    if (!snoop) return nullptr;
+    sn = *snoop;
+    if (i != 0) sn.progress = nullptr;
+    return &sn;
+}
+
+} // extern "C"
+
+// the failure path of everything that makes handles: free_all() takes down what was made, and freeing handles must not replace the
+// message of the failure
+template <typename F>
+int failed(int rc, F &&free_all) {
+    const std::string msg = scanrs_last_error();
+    free_all();
+    set_error("%s", msg.c_str());
+    return rc;
+}
+
+// ---- the collective frame: one call of the handle on every shard at once ---------------------------------------------------
+// Every shard gets the same global arguments and computes the same complete outputs; shard 0 writes the caller's arrays, the others
+// write into scratch of the call. Every shard polls the cancel flag at the same points; only shard 0 reports progress.
+struct ShardView { // the handle a shard's call runs on: the shard itself, or its transposed view for the length of the call
+    scanrs_mat *h = nullptr;
+    bool owned = false;
+    int open(scanrs_multi *mm, size_t i, int transposed) {
+        if (!transposed) {
+            h = mm->shards[i];
+            return SCANRS_OK;
+        }
+        owned = true;
+        return scanrs_mat_t(mm->shards[i], &h);
+    }
+    ~ShardView() {
+        if (owned && h) scanrs_mat_free(h);
+    }
+};
+
+// the outputs of one shard's call: the caller's array on shard 0, a zeroed array of the call's own on every other shard
+class ShardOutputs {
+    struct Block {
+        std::unique_ptr<void, void (*)(void *)> mem;
+    };
+    const bool first;
+    std::vector<Block> owned; // each a separate allocation, released with the call
+
+  public:
+    explicit ShardOutputs(size_t shard) : first(shard == 0) {}
+    // an output of n elements (one more is allocated: never an empty array)
+    template <typename T>
+    T *out(T *callers, size_t n) {
+        if (first) return callers;
+        owned.push_back(Block{{new T[n + 1](), [](void *p) { delete[] static_cast<T *>(p); }}});
+        return static_cast<T *>(owned.back().mem.get());
+    }
+    // an output the caller may leave out, which only shard 0 fills
+    template <typename T>
+    T *optional(T *callers) const {
+        return first ? callers : nullptr;
+    }
+};
+
+// body(i, handle, snoop, outputs) on every shard, on its transposed view where `transposed`, with the snoop narrowed for the shard
+template <typename F>
+int collective(scanrs_multi *mm, int transposed, const scanrs_snoop *snoop, F &&body) {
+    return fan_out(mm, [&](size_t i) {
+        ShardView v;
+        if (const int rc = v.open(mm, i, transposed)) return rc;
+        scanrs_snoop sn;
+        ShardOutputs o(i);
+        return (int)body(i, v.h, shard_snoop(snoop, i, sn), o);
+    });
 }
 
 } // namespace
@@ -115,11 +241,8 @@ extern "C" {
 
 int scanrs_multi_create(uint64_t rows, uint64_t cols, int storage, const uint64_t *indptr, const uint32_t *indices,
                         const uint32_t *values, uint32_t n_shards, const int *devices, scanrs_multi **out) {
-    try {
-        if (!out) fail(SCANRS_ERR_ARGUMENT, "null output handle");
-        *out = nullptr;
-        if (!indptr || n_shards == 0 || n_shards > 16) fail(SCANRS_ERR_ARGUMENT, "1 <= n_shards <= 16 and a triplet are required");
-        if (storage != SCANRS_CSR && storage != SCANRS_CSC) fail(SCANRS_ERR_ARGUMENT, "storage must be 0 (CSR) or 1 (CSC)");
+    return guard([&] {
+        check_frame(indptr != nullptr, n_shards, storage, out);
         auto mm = std::make_unique<scanrs_multi>();
         mm->rows = rows;
         mm->cols = cols;
@@ -138,18 +261,9 @@ int scanrs_multi_create(uint64_t rows, uint64_t cols, int storage, const uint64_
             if (rc2 != SCANRS_OK) return rc2;
             return scanrs_mat_set_shard_comm(raw->shards[i], raw->comms[i], (uint32_t)i, (uint32_t)raw->shards.size(), lo, n_outer);
         });
-        if (rc != SCANRS_OK) {
-            scanrs_multi_free(mm.release());
-            return rc;
-        }
+        if (rc != SCANRS_OK) throw Failure{failed(rc, [&] { scanrs_multi_free(mm.release()); })};
         *out = mm.release();
-        return SCANRS_OK;
-    } catch (const Failure &e) {
-        return e.code;
-    } catch (const std::exception &e) {
-        set_error("internal error: %s", e.what());
-        return SCANRS_ERR_DEVICE;
-    }
+    });
 }
 
 // ---- the inner-sharding constructors (mat.rs:68-124, hdf5-io/src/matrix.rs:119-192, mtx.rs:10-51, cmd.rs:61-70) -----------
@@ -216,11 +330,7 @@ int create_inner(uint64_t rows, uint64_t cols, int storage, const std::vector<ui
     int rc = fan_out(raw, [&](size_t s) {
         return guard([&] {
             need_device();
-            auto stp = new_storage(0, 0, out_storage); // (its shape is known once `bounds` is)
-            auto *h = new scanrs_mat();
-            h->st = stp;
-            raw->shards[s] = h; // from here on scanrs_multi_free takes the storage down
-            Storage &st = *h->st;
+            Storage &st = *make_shard(raw, s, 0, 0)->st; // (its shape is known once `bounds` is)
             CurrentHandle cur(&st);
             InnerShard &w = work[s];
             w.slab.n_outer = slab_bounds[s + 1] - slab_bounds[s];
@@ -312,49 +422,40 @@ int create_inner(uint64_t rows, uint64_t cols, int storage, const std::vector<ui
     if (rc == SCANRS_OK)
         rc = fan_out(raw, [&](size_t d) {
             return guard([&] {
-                scanrs_mat *h = raw->shards[d];
-                Storage &st = *h->st;
+                Storage &st = *raw->shards[d]->st;
                 CurrentHandle cur(&st);
                 InnerShard &w = work[d];
                 PhaseClock clock(st.reshard_us[4]);
                 w.drop_slab();
                 device_free_flush(); // the stream is idle here
-                SparseCopy &pc = w.piece;
-                pc.max_value = pc.nnz ? std::max(sseq_max_count(st, pc), 1u) : 0u; // sizes the sort keys of the transposition
-                if (pc.nnz) pc.build_items(st.stream);
-                build_transposed_copy(st, pc, st.primary);
-                w.piece = SparseCopy();
-                const uint64_t lo = raw->bounds[d], n_loc = raw->bounds[d + 1] - lo;
-                st.rows = out_storage == SCANRS_CSR ? n_loc : rows;
-                st.cols = out_storage == SCANRS_CSR ? cols : n_loc;
-                device_free_flush();
-                if (const int rc2 = scanrs_mat_set_shard_comm(h, raw->comms[d], (uint32_t)d, n_shards, lo, n_inner)) throw Failure{rc2};
+                // (the largest count sizes the sort keys of the transposition)
+                finish_shard(raw, d, w.piece, false, n_inner, [&] {
+                    build_transposed_copy(st, w.piece, st.primary);
+                    w.piece = SparseCopy();
+                    const uint64_t n_loc = raw->bounds[d + 1] - raw->bounds[d];
+                    st.rows = out_storage == SCANRS_CSR ? n_loc : rows;
+                    st.cols = out_storage == SCANRS_CSR ? cols : n_loc;
+                });
             });
         });
 
     // whatever is left of the temporaries goes back under the handle that made it (a failure; nothing after a success)
-    const std::string msg = rc == SCANRS_OK ? std::string() : std::string(scanrs_last_error());
-    for (uint32_t s = 0; s < n_shards; s++) {
-        (void)hipSetDevice(raw->devices[s]);
-        CurrentHandle cur(raw->shards[s] && raw->shards[s]->st ? raw->shards[s]->st.get() : nullptr, true);
-        work[s].drop_slab();
-        work[s].piece = SparseCopy();
-    }
-    if (rc != SCANRS_OK) {
-        scanrs_multi_free(mm.release());
-        set_error("%s", msg.c_str());
-        return rc;
-    }
+    const auto drop_work = [&] {
+        for (uint32_t s = 0; s < n_shards; s++) {
+            (void)hipSetDevice(raw->devices[s]);
+            CurrentHandle cur(raw->shards[s] && raw->shards[s]->st ? raw->shards[s]->st.get() : nullptr, true);
+            work[s].drop_slab();
+            work[s].piece = SparseCopy();
+        }
+    };
+    if (rc != SCANRS_OK)
+        return failed(rc, [&] {
+            drop_work();
+            scanrs_multi_free(mm.release());
+        });
+    drop_work();
     *out = mm.release();
     return SCANRS_OK;
-}
-
-// the checks every inner-sharding constructor inherits from scanrs_multi_create
-void check_inner_frame(uint32_t n_shards, int storage, scanrs_multi **out) {
-    if (!out) fail(SCANRS_ERR_ARGUMENT, "null output handle");
-    *out = nullptr;
-    if (n_shards == 0 || n_shards > 16) fail(SCANRS_ERR_ARGUMENT, "1 <= n_shards <= 16 and a triplet are required");
-    if (storage != SCANRS_CSR && storage != SCANRS_CSC) fail(SCANRS_ERR_ARGUMENT, "storage must be 0 (CSR) or 1 (CSC)");
 }
 
 } // namespace
@@ -364,7 +465,7 @@ extern "C" {
 int scanrs_multi_create_inner(uint64_t rows, uint64_t cols, int storage, const uint64_t *indptr, const uint32_t *indices, const uint32_t *values,
                               uint32_t n_shards, const int *devices, scanrs_multi **out) {
     return guard([&] {
-        check_inner_frame(n_shards, storage, out);
+        check_frame(true, n_shards, storage, out);
         const uint64_t n_outer = storage == SCANRS_CSR ? rows : cols, n_inner = storage == SCANRS_CSR ? cols : rows;
         reshard_check_frame(n_outer, n_inner, indptr, indices, values != nullptr);
         std::vector<uint64_t> sb(n_shards + 1);
@@ -392,7 +493,7 @@ int scanrs_multi_create_inner(uint64_t rows, uint64_t cols, int storage, const u
 int scanrs_multi_create_adaptive_inner(uint64_t rows, uint64_t cols, int storage, const scanrs_adaptive_vec *vecs, uint64_t n_vecs, uint32_t n_shards,
                                        const int *devices, scanrs_multi **out) {
     return guard([&] {
-        check_inner_frame(n_shards, storage, out);
+        check_frame(true, n_shards, storage, out);
         const uint64_t n_outer = storage == SCANRS_CSR ? rows : cols, n_inner = storage == SCANRS_CSR ? cols : rows;
         if (n_outer > 0xFFFFFFFFull || n_inner > 0xFFFFFFFFull) fail(SCANRS_ERR_SHAPE, "dimensions must fit in u32 (AdaptiveVec limit)");
         if (n_vecs != n_outer) fail(SCANRS_ERR_SHAPE, "one AdaptiveVec per outer vector is required");
@@ -486,13 +587,14 @@ int scanrs_multi_normalize(scanrs_multi *mm, int normalization, const uint32_t *
 
 // u: rows x k, s: k, v: cols x k (row-major, caller-allocated; u and/or v may be null). The factor on the sharded side
 // is assembled from the shards' rows, the replicated one is taken from shard 0.
-static int multi_pca(scanrs_multi *mm, uint32_t k, double *u, double *s, double *v, const std::function<int(size_t, double *, double *, double *)> &call) {
+// call(i, handle, snoop, outputs, u_i, s_i, v_i) under the collective frame; u_i / v_i are null where the shard has nothing to write.
+namespace {
+extern "C++" template <typename F>
+int multi_pca(scanrs_multi *mm, uint32_t k, const scanrs_snoop *snoop, double *u, double *s, double *v, F &&call) {
     if (!mm || !s) return SCANRS_ERR_ARGUMENT;
     const bool cols_sharded = mm->storage == SCANRS_CSC;
-    std::vector<std::vector<double>> s_each(mm->shards.size(), std::vector<double>(k));
-    std::vector<double> dummy_rep; // replicated factor of shards > 0 is not downloaded
-    return fan_out(mm, [&](size_t i) {
-        double *ui = nullptr, *vi = nullptr;
+    return collective(mm, 0, snoop, [&](size_t i, scanrs_mat *h, const scanrs_snoop *sn, ShardOutputs &o) {
+        double *ui = nullptr, *vi = nullptr; // (the replicated factor of shards > 0 is not downloaded)
         if (cols_sharded) {
             ui = (i == 0) ? u : nullptr;
             vi = v ? v + mm->bounds[i] * k : nullptr;
@@ -500,28 +602,22 @@ static int multi_pca(scanrs_multi *mm, uint32_t k, double *u, double *s, double 
             ui = u ? u + mm->bounds[i] * k : nullptr;
             vi = (i == 0) ? v : nullptr;
         }
-        return call(i, ui, i == 0 ? s : s_each[i].data(), vi);
+        return call(i, h, sn, o, ui, o.out(s, k), vi);
     });
 }
+} // namespace
 
 int scanrs_multi_pca_bk(scanrs_multi *mm, uint32_t k, double k_multiplier, uint32_t n_iter, uint64_t seed, const double *omega,
                         const scanrs_snoop *snoop, double *u, double *s, double *v) {
-    return multi_pca(mm, k, u, s, v, [&](size_t i, double *ui, double *si, double *vi) {
-        scanrs_snoop sn;
-        const scanrs_snoop *psn = nullptr;
-        if (snoop) { // every shard polls the cancel flag at the same points; only shard 0 reports progress
-            sn = *snoop;
-            if (i != 0) sn.progress = nullptr;
-            psn = &sn;
-        }
-        return scanrs_pca_bk(mm->shards[i], k, k_multiplier, n_iter, seed, omega, psn, ui, si, vi);
+    return multi_pca(mm, k, snoop, u, s, v, [&](size_t, scanrs_mat *h, const scanrs_snoop *sn, ShardOutputs &, double *ui, double *si, double *vi) {
+        return scanrs_pca_bk(h, k, k_multiplier, n_iter, seed, omega, sn, ui, si, vi);
     });
 }
 
 int scanrs_multi_pca_rand(scanrs_multi *mm, uint32_t k, double l_multiplier, uint32_t n_iter, uint64_t seed, const double *omega,
                           double *u, double *s, double *v) {
-    return multi_pca(mm, k, u, s, v, [&](size_t i, double *ui, double *si, double *vi) {
-        return scanrs_pca_rand(mm->shards[i], k, l_multiplier, n_iter, seed, omega, ui, si, vi);
+    return multi_pca(mm, k, nullptr, u, s, v, [&](size_t, scanrs_mat *h, const scanrs_snoop *, ShardOutputs &, double *ui, double *si, double *vi) {
+        return scanrs_pca_rand(h, k, l_multiplier, n_iter, seed, omega, ui, si, vi);
     });
 }
 
@@ -530,28 +626,14 @@ int scanrs_multi_pca_irlba(scanrs_multi *mm, uint32_t nu, double tol, uint32_t m
                            double *u, double *s, double *v, uint32_t *mprod) {
     if (!u || !v) return SCANRS_ERR_ARGUMENT;
     std::vector<uint32_t> mp(mm ? mm->shards.size() : 0, 0);
-    const int rc = multi_pca(mm, nu, u, s, v, [&](size_t i, double *ui, double *si, double *vi) {
-        scanrs_snoop sn;
-        const scanrs_snoop *psn = nullptr;
-        if (snoop) {
-            sn = *snoop;
-            if (i != 0) sn.progress = nullptr;
-            psn = &sn;
-        }
+    const int rc = multi_pca(mm, nu, snoop, u, s, v, [&](size_t i, scanrs_mat *h, const scanrs_snoop *sn, ShardOutputs &o, double *ui, double *si, double *vi) {
         const bool cols_sharded = mm->storage == SCANRS_CSC;
         const uint64_t n_loc = mm->bounds[i + 1] - mm->bounds[i];
         // scanrs_pca_irlba wants both factors: the replicated one of shards > 0 goes to a scratch array
-        std::vector<double> spare;
-        if (!ui) {
-            spare.resize((size_t)(cols_sharded ? mm->rows : n_loc) * nu);
-            ui = spare.data();
-        }
-        if (!vi) {
-            spare.resize((size_t)(cols_sharded ? n_loc : mm->cols) * nu);
-            vi = spare.data();
-        }
+        if (!ui) ui = o.out(ui, (size_t)(cols_sharded ? mm->rows : n_loc) * nu);
+        if (!vi) vi = o.out(vi, (size_t)(cols_sharded ? n_loc : mm->cols) * nu);
         const double *v0i = v0 ? (cols_sharded ? v0 + mm->bounds[i] : v0) : nullptr;
-        return scanrs_pca_irlba(mm->shards[i], nu, tol, max_iter, v0i, psn, ui, si, vi, &mp[i]);
+        return scanrs_pca_irlba(h, nu, tol, max_iter, v0i, sn, ui, si, vi, &mp[i]);
     });
     if (mprod && !mp.empty()) *mprod = mp[0];
     return rc;
@@ -570,46 +652,17 @@ int scanrs_multi_log_normalize(scanrs_multi *mm, double umi_count_sum, int log_f
 // ---- sSeq differential expression over the shards -----------------------------------------------------------------
 // The calls of the handle (scanrs_sseq_params, scanrs_mat_group_sums, scanrs_sseq_de_backend) on every shard at once. The cells must
 // be the sharded dimension: a genes x cells CSC matrix, or a cells x genes CSR one with transposed = 1 (every shard then goes through
-// scanrs_mat_t). Every shard gets the same global arguments and computes the same complete outputs; shard 0 writes the caller's
-// arrays, the others write into scratch of the call.
-namespace {
-
-struct ShardView { // the handle a shard's DE call runs on: the shard itself, or its transposed view for the length of the call
-    scanrs_mat *h = nullptr;
-    bool owned = false;
-    int open(scanrs_multi *mm, size_t i, int transposed) {
-        if (!transposed) {
-            h = mm->shards[i];
-            return SCANRS_OK;
-        }
-        owned = true;
-        return scanrs_mat_t(mm->shards[i], &h);
-    }
-    ~ShardView() {
-        if (owned && h) scanrs_mat_free(h);
-    }
-};
-
-} // namespace
-
+// scanrs_mat_t). Each is one call under the collective frame above.
 int scanrs_multi_sseq_params(scanrs_multi *mm, int transposed, double zeta_quintile, const uint64_t *cell_indices, uint64_t n_sel,
                              const double *umi_counts, double *size_factors, double *gene_means, double *gene_variances, uint8_t *use_genes,
                              double *gene_moment_phi, double *zeta_hat, double *delta, double *gene_phi) {
     if (!mm || !size_factors || !gene_means || !gene_variances || !use_genes || !gene_moment_phi || !zeta_hat || !delta || !gene_phi)
         return bad_argument("null argument");
     const uint64_t genes = transposed ? mm->cols : mm->rows, cells = transposed ? mm->rows : mm->cols;
-    return fan_out(mm, [&](size_t i) {
-        ShardView v;
-        if (const int rc = v.open(mm, i, transposed)) return rc;
-        if (i == 0)
-            return scanrs_sseq_params(v.h, zeta_quintile, cell_indices, n_sel, umi_counts, size_factors, gene_means, gene_variances, use_genes,
-                                      gene_moment_phi, zeta_hat, delta, gene_phi);
-        const uint64_t gs = genes + 1; // never an empty vector
-        std::vector<double> sf(cells + 1), f64(4 * gs);
-        std::vector<uint8_t> use(gs);
-        double zh = 0.0, dl = 0.0;
-        return scanrs_sseq_params(v.h, zeta_quintile, cell_indices, n_sel, umi_counts, sf.data(), &f64[0], &f64[gs], use.data(), &f64[2 * gs], &zh,
-                                  &dl, &f64[3 * gs]);
+    return collective(mm, transposed, nullptr, [&](size_t, scanrs_mat *h, const scanrs_snoop *, ShardOutputs &o) {
+        return scanrs_sseq_params(h, zeta_quintile, cell_indices, n_sel, umi_counts, o.out(size_factors, cells), o.out(gene_means, genes),
+                                  o.out(gene_variances, genes), o.out(use_genes, genes), o.out(gene_moment_phi, genes), o.out(zeta_hat, 1),
+                                  o.out(delta, 1), o.out(gene_phi, genes));
     });
 }
 
@@ -617,12 +670,8 @@ int scanrs_multi_group_sums(scanrs_multi *mm, int transposed, const int16_t *lab
     if (!mm || !labels || !sums) return bad_argument("null argument");
     if (n_groups == 0 || n_groups > SSEQ_MAX_GROUPS) return bad_argument("n_groups must be in 1 .. 8192");
     const uint64_t genes = transposed ? mm->cols : mm->rows;
-    return fan_out(mm, [&](size_t i) {
-        ShardView v;
-        if (const int rc = v.open(mm, i, transposed)) return rc;
-        if (i == 0) return scanrs_mat_group_sums(v.h, labels, n_groups, sums, cells_per_group);
-        std::vector<uint64_t> spare(genes * n_groups + 1);
-        return scanrs_mat_group_sums(v.h, labels, n_groups, spare.data(), nullptr);
+    return collective(mm, transposed, nullptr, [&](size_t, scanrs_mat *h, const scanrs_snoop *, ShardOutputs &o) {
+        return scanrs_mat_group_sums(h, labels, n_groups, o.out(sums, genes * n_groups), o.optional(cells_per_group));
     });
 }
 
@@ -640,41 +689,15 @@ int scanrs_multi_sseq_de(scanrs_multi *mm, int transposed, const int16_t *labels
     if (n_groups == 0 || n_groups > SSEQ_MAX_GROUPS) return bad_argument("n_groups must be in 1 .. 8192");
     const uint64_t genes = transposed ? mm->cols : mm->rows;
     const uint64_t total = genes * (mode == 0 ? n_groups : mode == 1 ? 1 : n_groups - 1);
-    return fan_out(mm, [&](size_t i) {
-        ShardView v;
-        if (const int rc = v.open(mm, i, transposed)) return rc;
-        scanrs_snoop sn;
-        const scanrs_snoop *psn = nullptr;
-        if (snoop) { // every shard polls the cancel flag at the same points; only shard 0 reports progress
-            sn = *snoop;
-            if (i != 0) sn.progress = nullptr;
-            psn = &sn;
-        }
-        if (i == 0)
-            return scanrs_sseq_de_backend(v.h, labels, n_groups, mode, size_factors, gene_means, gene_phi, use_genes, big_count, backend, psn, sums_in,
-                                          sums_out, p, p_adj, log2fc, mean_in, mean_out);
-        std::vector<uint64_t> u64(2 * total + 2);
-        std::vector<double> f64(5 * total + 5);
-        return scanrs_sseq_de_backend(v.h, labels, n_groups, mode, size_factors, gene_means, gene_phi, use_genes, big_count, backend, psn, &u64[0],
-                                      &u64[total + 1], &f64[0], &f64[total + 1], &f64[2 * (total + 1)], &f64[3 * (total + 1)], &f64[4 * (total + 1)]);
+    return collective(mm, transposed, snoop, [&](size_t, scanrs_mat *h, const scanrs_snoop *sn, ShardOutputs &o) {
+        return scanrs_sseq_de_backend(h, labels, n_groups, mode, size_factors, gene_means, gene_phi, use_genes, big_count, backend, sn,
+                                      o.out(sums_in, total), o.out(sums_out, total), o.out(p, total), o.out(p_adj, total), o.out(log2fc, total),
+                                      o.out(mean_in, total), o.out(mean_out, total));
     });
 }
 
 // ---- sseq_de_pairs, merge_clusters and the medoids over the shards ------------------------------------------------------
-// The collective calls of the handle (scanrs_*_sharded) on every shard at once, under §7g's convention: global arguments, complete
-// outputs on every shard, shard 0 writes the caller's arrays (and the trace), the others write into scratch of the call.
-namespace {
-
-// every shard polls the cancel flag at the same points; only shard 0 reports progress
-const scanrs_snoop *shard_snoop(const scanrs_snoop *snoop, size_t i, scanrs_snoop &sn) {
-    if (!snoop) return nullptr;
-    sn = *snoop;
-    if (i != 0) sn.progress = nullptr;
-    return &sn;
-}
-
-} // namespace
-
+// The collective calls of the handle (scanrs_*_sharded) under the same frame; the pair parameters and the trace are shard 0's alone.
 int scanrs_multi_sseq_de_pairs(scanrs_multi *mm, int transposed, const int16_t *labels, uint32_t n_groups, const uint32_t *pair_a,
                                const uint32_t *pair_b, uint32_t n_pairs, double zeta_quintile, uint64_t big_count, int backend,
                                const scanrs_snoop *snoop, uint64_t *sums_in, uint64_t *sums_out, double *p, double *p_adj, double *log2fc,
@@ -688,19 +711,10 @@ int scanrs_multi_sseq_de_pairs(scanrs_multi *mm, int transposed, const int16_t *
     if (n_groups == 0 || n_groups > SSEQ_MAX_GROUPS) return bad_argument("n_groups must be in 1 .. 8192");
     const uint64_t genes = transposed ? mm->cols : mm->rows;
     const uint64_t total = genes * n_pairs;
-    return fan_out(mm, [&](size_t i) {
-        ShardView v;
-        if (const int rc = v.open(mm, i, transposed)) return rc;
-        scanrs_snoop sn;
-        const scanrs_snoop *psn = shard_snoop(snoop, i, sn);
-        if (i == 0)
-            return scanrs_sseq_de_pairs_sharded(v.h, labels, n_groups, pair_a, pair_b, n_pairs, zeta_quintile, big_count, backend, psn, sums_in,
-                                                sums_out, p, p_adj, log2fc, mean_in, mean_out, params);
-        std::vector<uint64_t> u64(2 * total + 2);
-        std::vector<double> f64(5 * total + 5);
-        return scanrs_sseq_de_pairs_sharded(v.h, labels, n_groups, pair_a, pair_b, n_pairs, zeta_quintile, big_count, backend, psn, &u64[0],
-                                            &u64[total + 1], &f64[0], &f64[total + 1], &f64[2 * (total + 1)], &f64[3 * (total + 1)],
-                                            &f64[4 * (total + 1)], nullptr);
+    return collective(mm, transposed, snoop, [&](size_t, scanrs_mat *h, const scanrs_snoop *sn, ShardOutputs &o) {
+        return scanrs_sseq_de_pairs_sharded(h, labels, n_groups, pair_a, pair_b, n_pairs, zeta_quintile, big_count, backend, sn, o.out(sums_in, total),
+                                            o.out(sums_out, total), o.out(p, total), o.out(p_adj, total), o.out(log2fc, total), o.out(mean_in, total),
+                                            o.out(mean_out, total), o.optional(params));
     });
 }
 
@@ -710,12 +724,8 @@ int scanrs_multi_cluster_medoids(scanrs_multi *mm, int transposed, const double 
     const uint64_t cells = transposed ? mm->rows : mm->cols;
     if (cells && (!pca || !labels || (!centers && d))) return bad_argument("null argument");
     if (ld < d) return bad_argument("ld must be at least d");
-    return fan_out(mm, [&](size_t i) {
-        ShardView v;
-        if (const int rc = v.open(mm, i, transposed)) return rc;
-        if (i == 0) return scanrs_cluster_medoids_sharded(v.h, pca, 0, ld, d, labels, k, centers);
-        std::vector<double> spare((size_t)k * d + 1);
-        return scanrs_cluster_medoids_sharded(v.h, pca, 0, ld, d, labels, k, spare.data());
+    return collective(mm, transposed, nullptr, [&](size_t, scanrs_mat *h, const scanrs_snoop *, ShardOutputs &o) {
+        return scanrs_cluster_medoids_sharded(h, pca, 0, ld, d, labels, k, o.out(centers, (size_t)k * d));
     });
 }
 
@@ -726,14 +736,8 @@ int scanrs_multi_merge_clusters(scanrs_multi *mm, int transposed, const double *
     if (cells && (!pca || !labels || !labels_out)) return bad_argument("null argument");
     if (trace && trace->capacity && (!trace->leaf0 || !trace->leaf1 || !trace->n_de || !trace->min_p_adj)) return bad_argument("trace arrays are null");
     if (ld < d) return bad_argument("ld must be at least d");
-    return fan_out(mm, [&](size_t i) {
-        ShardView v;
-        if (const int rc = v.open(mm, i, transposed)) return rc;
-        scanrs_snoop sn;
-        const scanrs_snoop *psn = shard_snoop(snoop, i, sn);
-        if (i == 0) return scanrs_merge_clusters_sharded(v.h, pca, 0, ld, d, labels, labels_out, psn, trace);
-        std::vector<int16_t> spare(cells + 1);
-        return scanrs_merge_clusters_sharded(v.h, pca, 0, ld, d, labels, spare.data(), psn, nullptr);
+    return collective(mm, transposed, snoop, [&](size_t, scanrs_mat *h, const scanrs_snoop *sn, ShardOutputs &o) {
+        return scanrs_merge_clusters_sharded(h, pca, 0, ld, d, labels, o.out(labels_out, cells), sn, o.optional(trace));
     });
 }
 
@@ -747,13 +751,11 @@ int scanrs_multi_knn(scanrs_multi *mm, const double *points, uint32_t ld, uint32
     const uint64_t cells = mm->bounds.back();
     if (cells && k && !out) return bad_argument("null argument");
     const int transposed = mm->storage == SCANRS_CSR;
-    return fan_out(mm, [&](size_t i) {
-        ShardView v;
-        if (const int rc = v.open(mm, i, transposed)) return rc;
+    return collective(mm, transposed, nullptr, [&](size_t i, scanrs_mat *h, const scanrs_snoop *, ShardOutputs &) {
         const uint64_t lo = mm->bounds[i], n_loc = mm->bounds[i + 1] - lo;
         uint32_t *o = out ? out + lo * k : nullptr;
         double *sq = sq_dist ? sq_dist + lo * k : nullptr;
-        if (points) return scanrs_knn_sharded(v.h, points, 0, ld, d, k, o, sq);
+        if (points) return scanrs_knn_sharded(h, points, 0, ld, d, k, o, sq);
         const double *du = nullptr, *dv = nullptr;
         uint32_t ldu = 0, ldv = 0, kk = 0;
         if (const int rc = scanrs_pca_result_device(mm->shards[i], &du, &ldu, &dv, &ldv, &kk)) return rc; // "no PCA result on this handle yet"
@@ -764,7 +766,7 @@ int scanrs_multi_knn(scanrs_multi *mm, const double *points, uint32_t ld, uint32
                       (unsigned long long)rows, (unsigned long long)n_loc);
             return (int)SCANRS_ERR_ARGUMENT;
         }
-        return scanrs_knn_sharded(v.h, transposed ? du : dv, 1, transposed ? ldu : ldv, kk, k, o, sq);
+        return scanrs_knn_sharded(h, transposed ? du : dv, 1, transposed ? ldu : ldv, kk, k, o, sq);
     });
 }
 
@@ -774,18 +776,9 @@ int scanrs_multi_knn(scanrs_multi *mm, const double *points, uint32_t ld, uint32
 // own: the source and its results may be freed in either order.
 namespace {
 
-void free_shards(scanrs_multi *mm, std::vector<scanrs_mat *> &made) {
-    for (size_t i = 0; i < made.size(); i++) {
-        if (!made[i]) continue;
-        (void)hipSetDevice(mm->devices[i]);
-        scanrs_mat_free(made[i]);
-        made[i] = nullptr;
-    }
-}
-
 // takes over `made` (one result handle per shard of src, bound to src's communicators); on failure everything in it is freed
 int multi_adopt(scanrs_multi *src, std::vector<scanrs_mat *> &made, scanrs_multi **out) {
-    try {
+    const int rc = guard([&] {
         auto mm = std::make_unique<scanrs_multi>();
         const uint32_t n = (uint32_t)made.size();
         mm->storage = src->storage;
@@ -815,15 +808,8 @@ int multi_adopt(scanrs_multi *src, std::vector<scanrs_mat *> &made, scanrs_multi
         mm->shards = std::move(made);
         made.clear();
         *out = mm.release();
-        return SCANRS_OK;
-    } catch (const Failure &e) {
-        free_shards(src, made);
-        return e.code;
-    } catch (const std::exception &e) {
-        free_shards(src, made);
-        set_error("internal error: %s", e.what());
-        return SCANRS_ERR_DEVICE;
-    }
+    });
+    return rc == SCANRS_OK ? rc : failed(rc, [&] { free_shards(src, made); });
 }
 
 int multi_select(scanrs_multi *mm, bool rows_axis, const uint64_t *idx, uint64_t n_idx, scanrs_multi **out) {
@@ -834,35 +820,24 @@ int multi_select(scanrs_multi *mm, bool rows_axis, const uint64_t *idx, uint64_t
     const int rc = fan_out(mm, [&](size_t i) {
         return rows_axis ? scanrs_mat_select_rows_sharded(mm->shards[i], idx, n_idx, &made[i]) : scanrs_mat_select_cols_sharded(mm->shards[i], idx, n_idx, &made[i]);
     });
-    if (rc != SCANRS_OK) {
-        const std::string msg = scanrs_last_error(); // (freeing handles must not replace the message)
-        free_shards(mm, made);
-        set_error("%s", msg.c_str());
-        return rc;
-    }
+    if (rc != SCANRS_OK) return failed(rc, [&] { free_shards(mm, made); });
     return multi_adopt(mm, made, out);
 }
 
 } // namespace
 
 // ---- the statistics over a list of columns over the shards ----------------------------------------------------------------
-// The collective calls of the handle (scanrs_mat_sum_rows_u64_sharded and kin) on every shard at once: global lists, complete outputs
-// on every shard; shard 0 writes the caller's arrays, the others write into scratch of the call.
+// The collective calls of the handle (scanrs_mat_sum_rows_u64_sharded and kin) under the collective frame: global lists, complete
+// outputs on every shard.
 namespace {
 
-// f(handle, out_a, out_b, snoop) on every shard; n_res: the entries (8 bytes each) of an output
-extern "C++" template <typename F>
-int multi_subset(scanrs_multi *mm, int transposed, void *out_a, void *out_b, bool two, uint64_t n_res, const scanrs_snoop *snoop, F &&f) {
+// f(handle, out_a, out_b, snoop) on every shard; n_res: the entries of an output (out_b: null unless `two`; its type follows out_a's)
+extern "C++" template <typename T, typename F>
+int multi_subset(scanrs_multi *mm, int transposed, T *out_a, std::common_type_t<T> *out_b, bool two, uint64_t n_res, const scanrs_snoop *snoop, F &&f) {
     if (!mm) return bad_argument("null handle");
     if (n_res && (!out_a || (two && !out_b))) return bad_argument("null argument");
-    return fan_out(mm, [&](size_t i) {
-        ShardView v;
-        if (const int rc = v.open(mm, i, transposed)) return rc;
-        scanrs_snoop sn;
-        const scanrs_snoop *psn = shard_snoop(snoop, i, sn);
-        if (i == 0) return (int)f(v.h, out_a, out_b, psn);
-        std::vector<uint64_t> spare(2 * (n_res + 1));
-        return (int)f(v.h, static_cast<void *>(&spare[0]), static_cast<void *>(&spare[n_res + 1]), psn);
+    return collective(mm, transposed, snoop, [&](size_t, scanrs_mat *h, const scanrs_snoop *sn, ShardOutputs &o) {
+        return f(h, o.out(out_a, n_res), two ? o.out(out_b, n_res) : nullptr, sn);
     });
 }
 uint64_t view_rows(const scanrs_multi *mm, int transposed) { return !mm ? 0 : transposed ? mm->cols : mm->rows; }
@@ -870,45 +845,45 @@ uint64_t view_rows(const scanrs_multi *mm, int transposed) { return !mm ? 0 : tr
 } // namespace
 
 int scanrs_multi_sum_rows_u64(scanrs_multi *mm, int transposed, const uint64_t *cols, uint64_t n, uint64_t *out) {
-    return multi_subset(mm, transposed, out, nullptr, false, view_rows(mm, transposed), nullptr, [&](scanrs_mat *h, void *a, void *, const scanrs_snoop *) {
-        return scanrs_mat_sum_rows_u64_sharded(h, cols, n, static_cast<uint64_t *>(a));
+    return multi_subset(mm, transposed, out, nullptr, false, view_rows(mm, transposed), nullptr, [&](scanrs_mat *h, uint64_t *a, uint64_t *, const scanrs_snoop *) {
+        return scanrs_mat_sum_rows_u64_sharded(h, cols, n, a);
     });
 }
 int scanrs_multi_sum_rows_f64(scanrs_multi *mm, int transposed, const uint64_t *cols, uint64_t n, double *out) {
-    return multi_subset(mm, transposed, out, nullptr, false, view_rows(mm, transposed), nullptr, [&](scanrs_mat *h, void *a, void *, const scanrs_snoop *) {
-        return scanrs_mat_sum_rows_f64_sharded(h, cols, n, static_cast<double *>(a));
+    return multi_subset(mm, transposed, out, nullptr, false, view_rows(mm, transposed), nullptr, [&](scanrs_mat *h, double *a, double *, const scanrs_snoop *) {
+        return scanrs_mat_sum_rows_f64_sharded(h, cols, n, a);
     });
 }
 int scanrs_multi_sum_cols_u64(scanrs_multi *mm, int transposed, const uint64_t *cols, uint64_t n, uint64_t *out) {
-    return multi_subset(mm, transposed, out, nullptr, false, n, nullptr, [&](scanrs_mat *h, void *a, void *, const scanrs_snoop *) {
-        return scanrs_mat_sum_cols_u64_sharded(h, cols, n, static_cast<uint64_t *>(a));
+    return multi_subset(mm, transposed, out, nullptr, false, n, nullptr, [&](scanrs_mat *h, uint64_t *a, uint64_t *, const scanrs_snoop *) {
+        return scanrs_mat_sum_cols_u64_sharded(h, cols, n, a);
     });
 }
 int scanrs_multi_sum_cols_f64(scanrs_multi *mm, int transposed, const uint64_t *cols, uint64_t n, double *out) {
-    return multi_subset(mm, transposed, out, nullptr, false, n, nullptr, [&](scanrs_mat *h, void *a, void *, const scanrs_snoop *) {
-        return scanrs_mat_sum_cols_f64_sharded(h, cols, n, static_cast<double *>(a));
+    return multi_subset(mm, transposed, out, nullptr, false, n, nullptr, [&](scanrs_mat *h, double *a, double *, const scanrs_snoop *) {
+        return scanrs_mat_sum_cols_f64_sharded(h, cols, n, a);
     });
 }
 int scanrs_multi_sum_rows_dual_u64(scanrs_multi *mm, int transposed, const uint64_t *cols1, uint64_t n1, const uint64_t *cols2, uint64_t n2,
                                    const scanrs_snoop *snoop, uint64_t *out1, uint64_t *out2) {
-    return multi_subset(mm, transposed, out1, out2, true, view_rows(mm, transposed), snoop, [&](scanrs_mat *h, void *a, void *b, const scanrs_snoop *sn) {
-        return scanrs_mat_sum_rows_dual_u64_sharded(h, cols1, n1, cols2, n2, sn, static_cast<uint64_t *>(a), static_cast<uint64_t *>(b));
+    return multi_subset(mm, transposed, out1, out2, true, view_rows(mm, transposed), snoop, [&](scanrs_mat *h, uint64_t *a, uint64_t *b, const scanrs_snoop *sn) {
+        return scanrs_mat_sum_rows_dual_u64_sharded(h, cols1, n1, cols2, n2, sn, a, b);
     });
 }
 int scanrs_multi_sum_rows_dual_f64(scanrs_multi *mm, int transposed, const uint64_t *cols1, uint64_t n1, const uint64_t *cols2, uint64_t n2,
                                    const scanrs_snoop *snoop, double *out1, double *out2) {
-    return multi_subset(mm, transposed, out1, out2, true, view_rows(mm, transposed), snoop, [&](scanrs_mat *h, void *a, void *b, const scanrs_snoop *sn) {
-        return scanrs_mat_sum_rows_dual_f64_sharded(h, cols1, n1, cols2, n2, sn, static_cast<double *>(a), static_cast<double *>(b));
+    return multi_subset(mm, transposed, out1, out2, true, view_rows(mm, transposed), snoop, [&](scanrs_mat *h, double *a, double *b, const scanrs_snoop *sn) {
+        return scanrs_mat_sum_rows_dual_f64_sharded(h, cols1, n1, cols2, n2, sn, a, b);
     });
 }
 int scanrs_multi_mean_rows(scanrs_multi *mm, int transposed, const uint64_t *cols, uint64_t n, double *out) {
-    return multi_subset(mm, transposed, out, nullptr, false, view_rows(mm, transposed), nullptr, [&](scanrs_mat *h, void *a, void *, const scanrs_snoop *) {
-        return scanrs_mat_mean_rows_sharded(h, cols, n, static_cast<double *>(a));
+    return multi_subset(mm, transposed, out, nullptr, false, view_rows(mm, transposed), nullptr, [&](scanrs_mat *h, double *a, double *, const scanrs_snoop *) {
+        return scanrs_mat_mean_rows_sharded(h, cols, n, a);
     });
 }
 int scanrs_multi_mean_var_rows(scanrs_multi *mm, int transposed, const uint64_t *cols, uint64_t n, double *mean, double *var) {
-    return multi_subset(mm, transposed, mean, var, true, view_rows(mm, transposed), nullptr, [&](scanrs_mat *h, void *a, void *b, const scanrs_snoop *) {
-        return scanrs_mat_mean_var_rows_sharded(h, cols, n, static_cast<double *>(a), static_cast<double *>(b));
+    return multi_subset(mm, transposed, mean, var, true, view_rows(mm, transposed), nullptr, [&](scanrs_mat *h, double *a, double *b, const scanrs_snoop *) {
+        return scanrs_mat_mean_var_rows_sharded(h, cols, n, a, b);
     });
 }
 
@@ -961,32 +936,25 @@ int scanrs_multi_partition_on_thresholds(scanrs_multi *mm, const double *row_thr
     if (!selected_rows || !n_selected_rows || !selected_cols || !n_selected_cols) return bad_argument("null argument");
     const size_t n = mm->shards.size();
     std::vector<scanrs_mat *> made_f(n, nullptr), made_r(n, nullptr);
-    int rc = fan_out(mm, [&](size_t i) {
-        scanrs_mat **pf = filtered ? &made_f[i] : nullptr, **pr = residual ? &made_r[i] : nullptr;
-        if (i == 0)
-            return scanrs_mat_partition_on_thresholds_sharded(mm->shards[i], row_threshold, col_threshold, pf, pr, selected_rows, n_selected_rows,
-                                                              selected_cols, n_selected_cols);
-        std::vector<uint64_t> sr(mm->rows + 1), sc(mm->cols + 1); // every shard computes the same complete lists
-        uint64_t nr = 0, nc = 0;
-        return scanrs_mat_partition_on_thresholds_sharded(mm->shards[i], row_threshold, col_threshold, pf, pr, sr.data(), &nr, sc.data(), &nc);
+    int rc = collective(mm, 0, nullptr, [&](size_t i, scanrs_mat *h, const scanrs_snoop *, ShardOutputs &o) {
+        // every shard computes the same complete lists
+        return scanrs_mat_partition_on_thresholds_sharded(h, row_threshold, col_threshold, filtered ? &made_f[i] : nullptr, residual ? &made_r[i] : nullptr,
+                                                          o.out(selected_rows, mm->rows), o.out(n_selected_rows, 1), o.out(selected_cols, mm->cols),
+                                                          o.out(n_selected_cols, 1));
     });
-    if (rc != SCANRS_OK) {
-        const std::string msg = scanrs_last_error();
-        free_shards(mm, made_f);
-        free_shards(mm, made_r);
-        set_error("%s", msg.c_str());
-        return rc;
-    }
+    if (rc != SCANRS_OK)
+        return failed(rc, [&] {
+            free_shards(mm, made_f);
+            free_shards(mm, made_r);
+        });
     scanrs_multi *hf = nullptr, *hr = nullptr;
     if (filtered) rc = multi_adopt(mm, made_f, &hf);
     if (rc == SCANRS_OK && residual) rc = multi_adopt(mm, made_r, &hr);
-    if (rc != SCANRS_OK) {
-        const std::string msg = scanrs_last_error();
-        scanrs_multi_free(hf);
-        free_shards(mm, made_r);
-        set_error("%s", msg.c_str());
-        return rc;
-    }
+    if (rc != SCANRS_OK)
+        return failed(rc, [&] {
+            scanrs_multi_free(hf);
+            free_shards(mm, made_r);
+        });
     if (filtered) *filtered = hf;
     if (residual) *residual = hr;
     return SCANRS_OK;
@@ -1008,18 +976,6 @@ int scanrs_multi_partition_on_thresholds(scanrs_multi *mm, const double *row_thr
 
 namespace {
 
-// `from` maps the memory of `to` (a destination reads a source's arrays in place)
-void enable_peer(int from, int to) {
-    if (from == to) return;
-    int can = 0;
-    SCANRS_HIP(hipDeviceCanAccessPeer(&can, from, to));
-    if (!can) fail(SCANRS_ERR_DEVICE, "devices %d and %d cannot map each other's memory", from, to);
-    SCANRS_HIP(hipSetDevice(from));
-    const hipError_t e = hipDeviceEnablePeerAccess(to, 0);
-    if (e != hipSuccess && e != hipErrorPeerAccessAlreadyEnabled) SCANRS_HIP(e);
-    (void)hipGetLastError();
-}
-
 int gather_outer(scanrs_multi *src, const uint64_t *idx, uint64_t n_idx, uint32_t n_shards, const int *devices, scanrs_multi **out) {
     if (!out) return bad_argument("out: null output handle");
     *out = nullptr;
@@ -1029,14 +985,12 @@ int gather_outer(scanrs_multi *src, const uint64_t *idx, uint64_t n_idx, uint32_
     std::unique_ptr<scanrs_multi> mm;
     int rc = guard([&] {
         // everything that can be refused is refused here, before any device work
-        if (n_shards == 0 || n_shards > REGATHER_MAX_SHARDS) fail(SCANRS_ERR_ARGUMENT, "n_shards: 1 <= n_shards <= 16 is required (%u given)", n_shards);
+        check_shard_count(n_shards, "n_shards: 1 <= n_shards <= 16 is required (%u given)");
         if (n_src > REGATHER_MAX_SHARDS) fail(SCANRS_ERR_ARGUMENT, "mm: a source of more than 16 shards is not served");
         regather_check_list(idx, n_idx, n_outer);
         if (n_outer >= 0x7FFFFFFFull || n_inner >= 0x7FFFFFFFull) fail(SCANRS_ERR_SHAPE, "gather_outer needs dimensions below 2^31 - 1");
         for (const scanrs_mat *h : src->shards) {
-            bool raw_map = h && !h->transposed;
-            for (size_t o = 0; raw_map && o < h->ops.size(); o++) raw_map = h->ops[o].kind == OP_INTO;
-            if (!raw_map)
+            if (!h || h->transposed || !map_is_raw(h))
                 fail(SCANRS_ERR_ARGUMENT, "gather_outer: the handle's map is not the identity (a scaling or a function has been composed); call scanrs_mat_reset_map first");
             if (h->off_rank)
                 fail(SCANRS_ERR_ARGUMENT, "gather_outer: the handle has a low-rank offset (center / scale_and_center / normalize); call scanrs_mat_reset_map first");
@@ -1054,14 +1008,8 @@ int gather_outer(scanrs_multi *src, const uint64_t *idx, uint64_t n_idx, uint32_
         mm->gather->moved.assign((size_t)n_src * n_shards, 0);
         mm->gather->host_bytes.assign(n_shards, 0);
     });
-    if (rc != SCANRS_OK) {
-        if (mm) {
-            const std::string msg = scanrs_last_error();
-            scanrs_multi_free(mm.release());
-            set_error("%s", msg.c_str());
-        }
-        return rc;
-    }
+    const auto give_up = [&] { scanrs_multi_free(mm.release()); }; // (of a null handle: nothing)
+    if (rc != SCANRS_OK) return failed(rc, give_up);
     scanrs_multi *raw = mm.get();
     scanrs_multi::GatherInfo &info = *raw->gather;
     jump_tables_prefetch(); // as scanrs_mat_create does
@@ -1105,11 +1053,7 @@ int gather_outer(scanrs_multi *src, const uint64_t *idx, uint64_t n_idx, uint32_
             return guard([&] {
                 need_device();
                 const uint64_t lo = raw->bounds[d], n_loc = raw->bounds[d + 1] - lo, nnz = tip[lo + n_loc] - tip[lo];
-                auto stp = new_storage(raw->storage == SCANRS_CSR ? n_loc : raw->rows, raw->storage == SCANRS_CSR ? raw->cols : n_loc, raw->storage);
-                auto *h = new scanrs_mat();
-                h->st = stp;
-                raw->shards[d] = h; // from here on scanrs_multi_free takes the storage down
-                Storage &st = *h->st;
+                Storage &st = *make_shard(raw, d, raw->storage == SCANRS_CSR ? n_loc : raw->rows, raw->storage == SCANRS_CSR ? raw->cols : n_loc)->st;
                 CurrentHandle cur(&st);
                 st.regather_us[0] = plan_us; // (the plan is one phase for all shards)
                 PhaseClock clock(st.regather_us[1]);
@@ -1152,24 +1096,14 @@ int gather_outer(scanrs_multi *src, const uint64_t *idx, uint64_t n_idx, uint32_
     if (rc == SCANRS_OK)
         rc = fan_out(raw, [&](size_t d) {
             return guard([&] {
-                scanrs_mat *h = raw->shards[d];
-                Storage &st = *h->st;
+                Storage &st = *raw->shards[d]->st;
                 CurrentHandle cur(&st);
                 PhaseClock clock(st.regather_us[2]);
-                SparseCopy &cp = st.primary;
-                cp.max_value = cp.nnz ? std::max(sseq_max_count(st, cp), 1u) : 0u; // validate_copy's: the largest stored count
-                cp.build_items(st.stream);
-                device_free_flush(); // the stream is idle here
-                if (const int rc2 = scanrs_mat_set_shard_comm(h, raw->comms[d], (uint32_t)d, n_shards, raw->bounds[d], n_idx)) throw Failure{rc2};
+                finish_shard(raw, d, st.primary, true, n_idx, [] {});
             });
         });
 
-    if (rc != SCANRS_OK) {
-        const std::string msg = scanrs_last_error(); // (freeing handles must not replace the message)
-        scanrs_multi_free(mm.release());
-        set_error("%s", msg.c_str());
-        return rc;
-    }
+    if (rc != SCANRS_OK) return failed(rc, give_up);
     *out = mm.release();
     return SCANRS_OK;
 }

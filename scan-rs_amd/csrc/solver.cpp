@@ -187,14 +187,6 @@ void omega_fill(uint64_t seed, uint64_t count, double *out) {
     for (uint64_t i = 0; i < count; i++) out[i] = rng.uniform_m1_1();
 }
 
-// ---- snoop -------------------------------------------------------------------------------------------------
-static void progress_check(const scanrs_snoop *sn, double p) {
-    // CancelProgress::set_progress_check (snoop/src/lib.rs:45-57)
-    if (!sn) return;
-    if (sn->cancel && __atomic_load_n(sn->cancel, __ATOMIC_RELAXED)) fail(SCANRS_ERR_CANCELLED, "cancellation error");
-    if (sn->progress) sn->progress(sn->ctx, p);
-}
-
 // ---- panel helpers --------------------------------------------------------------------------------------------
 struct Ctx {
     scanrs_mat *m;
@@ -1020,17 +1012,17 @@ static int pca_bk_impl(scanrs_mat *m, uint32_t k, double k_multiplier, uint32_t 
         for (uint32_t i = 0; i < qe; i++) eye[(size_t)i * qe + i] = 1.0;
         SCANRS_HIP(hipMemsetAsync(Ke, 0, (size_t)ds * ldqe * 8, c.s));
         upload_panel(c, eye.data(), ds, qe, Ke, ldqe);
-        for (uint32_t i = 0; i < n_iter; i++) progress_check(snoop, (double)i / (double)n_iter * 0.8); // the reference's poll points
+        for (uint32_t i = 0; i < n_iter; i++) snoop_poll(snoop, (double)i / (double)n_iter * 0.8); // the reference's poll points
         mat_apply(m, to_t_transpose, Ke, ldqe, qe, Te, ldqe);
         c.sync();
-        progress_check(snoop, 0.93);
+        snoop_poll(snoop, 0.93);
         if (rows_ge) {
             ritz_finish(c, Ke, ldqe, qe, ds, Te, ldqe, dt, t_sharded, k, v, s, u);
             pca_dev_swap(c.st);
         } else {
             ritz_finish(c, Ke, ldqe, qe, ds, Te, ldqe, dt, t_sharded, k, u, s, v);
         }
-        progress_check(snoop, 1.0);
+        snoop_poll(snoop, 1.0);
         return SCANRS_OK;
     }
     // the copy / tile layout of the SECOND product on a helper thread, beside everything up to the end of the first pass
@@ -1219,7 +1211,7 @@ static int pca_bk_impl(scanrs_mat *m, uint32_t k, double k_multiplier, uint32_t 
         } else {
             c.sync();
         }
-        progress_check(snoop, (double)i / (double)n_iter * 0.8);
+        snoop_poll(snoop, (double)i / (double)n_iter * 0.8);
     }
     // the last block (and everything, when there was no iteration to hide behind) on the main stream
     {
@@ -1251,7 +1243,7 @@ static int pca_bk_impl(scanrs_mat *m, uint32_t k, double k_multiplier, uint32_t 
             c.sync();
         }
     }
-    progress_check(snoop, 0.82);
+    snoop_poll(snoop, 0.82);
     // T' = (op(A) K) C amplifies the rounding of op(A) K by |C|. Columns of Q whose coefficient column stays
     // small (<= 1e5: error <= ~1e-11) take the cheap dense route; the others — directions in which the Krylov
     // blocks are numerically dependent — are recomputed directly as a (narrow) sparse product op(A) Q[:, bad].
@@ -1374,7 +1366,7 @@ static int pca_bk_impl(scanrs_mat *m, uint32_t k, double k_multiplier, uint32_t 
         stage_mark("bk projection synced");
     }
     Tick tk_fin("bk: ritz_finish");
-    progress_check(snoop, 0.93);
+    snoop_poll(snoop, 0.93);
     // m >= n: T = A Q (m x q): U = T E S^-1, V = Q E.   n > m: T^T = A^T Q (n x q): U = Q E, V = T E S^-1.
     if (rows_ge) {
         ritz_finish(c, K, ldq, q, ds, Tfin, ldq, dt, t_sharded, k, v, s, u);
@@ -1382,7 +1374,7 @@ static int pca_bk_impl(scanrs_mat *m, uint32_t k, double k_multiplier, uint32_t 
     } else {
         ritz_finish(c, K, ldq, q, ds, Tfin, ldq, dt, t_sharded, k, u, s, v);
     }
-    progress_check(snoop, 1.0);
+    snoop_poll(snoop, 1.0);
     return SCANRS_OK;
 }
 
@@ -1662,7 +1654,7 @@ int pca_irlba(scanrs_mat *m, uint32_t nu, double tol, uint32_t maxit, const doub
         }
         it++;
         c.sync();
-        progress_check(snoop, (double)it / (double)maxit);
+        snoop_poll(snoop, (double)it / (double)maxit);
     }
     {
         std::vector<double> Wm((size_t)m_b * nu);

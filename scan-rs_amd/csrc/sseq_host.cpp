@@ -15,18 +15,6 @@
 
 namespace scanrs {
 
-static void sseq_progress(const scanrs_snoop *sn, double p) {
-    // CancelProgress::set_progress_check (snoop/src/lib.rs:45-57)
-    if (!sn) return;
-    if (sn->cancel && __atomic_load_n(sn->cancel, __ATOMIC_RELAXED)) fail(SCANRS_ERR_CANCELLED, "cancellation error");
-    if (sn->progress) sn->progress(sn->ctx, p);
-}
-
-template <typename T>
-static void h2d(T *d, const T *h, size_t n, hipStream_t s) {
-    if (n) SCANRS_HIP(hipMemcpyAsync(d, h, n * sizeof(T), hipMemcpyHostToDevice, s));
-}
-
 // ---- sharded handles ---------------------------------------------------------------------------------------------
 // The cells are the sharded dimension: the copy holds the cells [begin, begin + n_local) of `global`, and every per-cell argument
 // spans the whole matrix. All sums that cross the shards are integers and go through allreduce_u64: they come out bit for bit as
@@ -449,7 +437,7 @@ void sseq_de_sums_strided(hipStream_t s, uint64_t genes, uint32_t n_tests, const
         SCANRS_SYNC(s);
         for (const uint64_t o : elsewhere) p[o] = pd[o];
     }
-    sseq_progress(snoop, 0.75);
+    snoop_poll(snoop, 0.75);
     // BH over the tested genes only
     std::vector<double> pv, q;
     for (uint32_t j = 0; j < n_tests; j++) {
@@ -464,20 +452,20 @@ void sseq_de_sums_strided(hipStream_t s, uint64_t genes, uint32_t n_tests, const
         for (uint64_t g = 0; g < genes; g++)
             if (use_genes[at(g, j)]) p_adj[g * n_tests + j] = q[k++];
     }
-    sseq_progress(snoop, 0.9);
+    snoop_poll(snoop, 0.9);
     for (uint64_t g = 0; g < genes; g++)
         for (uint32_t j = 0; j < n_tests; j++) {
             const uint64_t o = g * n_tests + j;
             log2fc[o] = std::log2((double)(1 + sums_a[o]) / (1.0 + sf_a[j])) - std::log2((double)(1 + sums_b[o]) / (1.0 + sf_b[j]));
         }
-    sseq_progress(snoop, 0.95);
+    snoop_poll(snoop, 0.95);
     for (uint64_t g = 0; g < genes; g++)
         for (uint32_t j = 0; j < n_tests; j++) {
             const uint64_t o = g * n_tests + j;
             mean_in[o] = sf_a[j] == 0.0 ? 0.0 : (double)sums_a[o] / sf_a[j];
             mean_out[o] = sf_b[j] == 0.0 ? 0.0 : (double)sums_b[o] / sf_b[j];
         }
-    sseq_progress(snoop, 1.0);
+    snoop_poll(snoop, 1.0);
 }
 
 void sseq_de_sums(hipStream_t s, uint64_t genes, uint32_t n_tests, const uint64_t *sums_a, const uint64_t *sums_b, const double *sf_a,
@@ -503,7 +491,7 @@ void sseq_de_matrix(Storage &st, const SparseCopy &cp, bool gene_major, uint64_t
     cells = cell_range(st, cells_local).global; // labels and size_factors span the whole matrix; the folds below run replicated
     check_labels(labels, cells, n_groups);
     const uint32_t n_tests = mode == 0 ? n_groups : mode == 1 ? 1 : n_groups - 1;
-    sseq_progress(snoop, 0.0);
+    snoop_poll(snoop, 0.0);
     // the size factors of each side: sums over its cells in cell order (the reference's fold over cond_a / cond_b)
     std::vector<double> fa(n_tests, 0.0), fb(n_tests, 0.0);
     if (mode == 2) {
@@ -530,7 +518,7 @@ void sseq_de_matrix(Storage &st, const SparseCopy &cp, bool gene_major, uint64_t
             }
         }
     }
-    sseq_progress(snoop, 0.1);
+    snoop_poll(snoop, 0.1);
     std::vector<uint64_t> sums(genes * n_groups);
     sseq_group_sums(st, cp, gene_major, genes, cells_local, labels, n_groups, sums.data(), nullptr);
     for (uint64_t g = 0; g < genes; g++) {
@@ -552,7 +540,7 @@ void sseq_de_matrix(Storage &st, const SparseCopy &cp, bool gene_major, uint64_t
             }
         }
     }
-    sseq_progress(snoop, 0.6);
+    snoop_poll(snoop, 0.6);
     sseq_de_sums_strided(st.stream, genes, n_tests, sums_in, sums_out, fa.data(), fb.data(), gene_means, gene_phi, use_genes, 1, 0, big_count, snoop,
                          p, p_adj, log2fc, mean_in, mean_out, backend, &st);
 }

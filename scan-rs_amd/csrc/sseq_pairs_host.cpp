@@ -18,18 +18,6 @@
 
 namespace scanrs {
 
-static void pairs_progress(const scanrs_snoop *sn, double p) {
-    // CancelProgress::set_progress_check (snoop/src/lib.rs:45-57)
-    if (!sn) return;
-    if (sn->cancel && __atomic_load_n(sn->cancel, __ATOMIC_RELAXED)) fail(SCANRS_ERR_CANCELLED, "cancellation error");
-    if (sn->progress) sn->progress(sn->ctx, p);
-}
-
-template <typename T>
-static void pairs_h2d(T *d, const T *h, size_t n, hipStream_t s) {
-    if (n) SCANRS_HIP(hipMemcpyAsync(d, h, n * sizeof(T), hipMemcpyHostToDevice, s));
-}
-
 // percentile_of_sorted(.., 50) (stat.rs:140-162) of the union of two ascending lists, selecting the two ranks it reads
 double sseq_union_median(const double *a, uint64_t na, const double *b, uint64_t nb) {
     const uint64_t len = na + nb;
@@ -126,7 +114,7 @@ void sseq_de_pairs(Storage &st, const SparseCopy &cp, bool gene_major, uint64_t 
     const hipStream_t s = st.stream;
     st.de_pairs_passes = st.de_pairs_literal = 0;
     uint64_t passes = 0;
-    pairs_progress(snoop, 0.0);
+    snoop_poll(snoop, 0.0);
 
     // pass 1: per-cell totals; then every group's sorted totals and integer sums, and the pairs' headers
     // (the scale comes from the GLOBAL cell count: every rank of a sharded handle rounds every term to the same quantum)
@@ -138,21 +126,21 @@ void sseq_de_pairs(Storage &st, const SparseCopy &cp, bool gene_major, uint64_t 
     if (collective) sseq_exchange_u64(st, d_tot, cells); // one contributor per element: the sum is a copy
     passes++;
     int16_t *d_lab = st.scratch.get<int16_t>("sseq_labels", std::max<uint64_t>(1, cells_local));
-    pairs_h2d(d_lab, labels + cr.begin, cells_local, s);
+    h2d(d_lab, labels + cr.begin, cells_local, s);
     DevBuf<uint32_t> d_perm(perm.size()), d_off(off.size()), d_pa(n_pairs), d_pb(n_pairs);
     DevBuf<unsigned long long> d_gathered(perm.size()), d_sorted(perm.size()), d_stats((size_t)n_groups * 3);
     DevBuf<SseqPairHeader> d_hdr(n_pairs);
     DevBuf<char> sort_tmp;
-    pairs_h2d(d_perm.p, perm.data(), perm.size(), s);
-    pairs_h2d(d_off.p, off.data(), off.size(), s);
-    pairs_h2d(d_pa.p, pair_a, n_pairs, s);
-    pairs_h2d(d_pb.p, pair_b, n_pairs, s);
+    h2d(d_perm.p, perm.data(), perm.size(), s);
+    h2d(d_off.p, off.data(), off.size(), s);
+    h2d(d_pa.p, pair_a, n_pairs, s);
+    h2d(d_pb.p, pair_b, n_pairs, s);
     launch_pairs_group_stats(s, d_tot, d_perm.p, d_off.p, n_groups, n_lab, scale, d_gathered.p, d_sorted.p, d_stats.p, sort_tmp);
     launch_pairs_headers(s, d_sorted.p, d_off.p, d_stats.p, d_pa.p, d_pb.p, n_pairs, scale, d_hdr.p);
     std::vector<SseqPairHeader> hdr(n_pairs);
     SCANRS_D2H(hdr.data(), d_hdr.p, n_pairs * sizeof(SseqPairHeader), s);
     SCANRS_SYNC(s);
-    pairs_progress(snoop, 0.1);
+    snoop_poll(snoop, 0.1);
 
     // pass 2: the grouped pass (one per tile of groups from the gene-major copy), then the parameters of every pair
     DevBuf<unsigned long long> d_acc(std::max<uint64_t>(1, (uint64_t)n_groups * genes * 5));
@@ -215,7 +203,7 @@ void sseq_de_pairs(Storage &st, const SparseCopy &cp, bool gene_major, uint64_t 
             lit_tests += st.de_shard_tests;
         }
     }
-    pairs_progress(snoop, 0.6);
+    snoop_poll(snoop, 0.6);
 
     std::vector<double> fa(n_pairs), fb(n_pairs);
     for (uint32_t j = 0; j < n_pairs; j++) {

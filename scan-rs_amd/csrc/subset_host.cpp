@@ -31,19 +31,6 @@ namespace scanrs {
 
 namespace {
 
-void subset_progress(const scanrs_snoop *sn, double p) {
-    // CancelProgress::set_progress_check (snoop/src/lib.rs:45-57)
-    if (!sn) return;
-    if (sn->cancel && __atomic_load_n(sn->cancel, __ATOMIC_RELAXED)) fail(SCANRS_ERR_CANCELLED, "cancellation error");
-    if (sn->progress) sn->progress(sn->ctx, p);
-}
-
-bool map_is_raw(const scanrs_mat *m) {
-    for (const auto &op : m->ops)
-        if (op.kind != OP_INTO) return false;
-    return true;
-}
-
 // "must be sorted" (mat.rs:413, 448); as scanrs_sseq_params' cell list, a repeated index is refused too
 void check_list(const uint64_t *l, uint64_t n, uint64_t extent, const char *name) {
     if (n && !l) fail(SCANRS_ERR_ARGUMENT, "%s: null index list", name);
@@ -119,7 +106,7 @@ void subset_sums(scanrs_mat *m, bool per_column, int mode, const List *lists, in
     const uint64_t n_result = per_column ? local[0].n : rows; // results this rank computes
     uint64_t n_all = 0;
     for (int k = 0; k < n_lists; k++) n_all += local[k].n;
-    subset_progress(snoop, 0.0); // (a flag that is already set: nothing has been queued, the outputs are untouched)
+    snoop_poll(snoop, 0.0); // (a flag that is already set: nothing has been queued, the outputs are untouched)
 
     CurrentHandle cur(&st);
     hipStream_t s = st.stream;
@@ -190,15 +177,15 @@ void subset_sums(scanrs_mat *m, bool per_column, int mode, const List *lists, in
                 unsigned long long *d_slab = st.scratch.get<unsigned long long>("subset_slab_fx", 5 * std::max<uint64_t>(1, cp.n_slab));
                 launch_subset_reduce_max(st, cp, map, d_code, d_max);
                 agree_on_scales(d_max);
-                subset_progress(snoop, 0.1);
+                snoop_poll(snoop, 0.1);
                 launch_subset_reduce_fx(st, cp, map, mode, n_lists, d_code, scale[0], scale[1], d_fx, d_bad, d_slab);
-                subset_progress(snoop, 0.9);
+                snoop_poll(snoop, 0.9);
             } else {
                 void *d_slab = st.scratch.get<unsigned long long>("subset_slab", 2 * std::max<uint64_t>(1, cp.n_slab));
                 if (cp.n_outer == 0 || cp.n_items == 0) SCANRS_HIP(hipMemsetAsync(d_out, 0, 2 * stride * 8, s));
-                subset_progress(snoop, 0.1);
+                snoop_poll(snoop, 0.1);
                 launch_subset_reduce(st, cp, map, mode, n_lists, d_code, d_out, stride, d_slab);
-                subset_progress(snoop, 0.9);
+                snoop_poll(snoop, 0.9);
                 launch_subset_finish(st, cp, mode, n_out, d_slab, d_out, stride);
             }
         } else {
@@ -221,7 +208,7 @@ void subset_sums(scanrs_mat *m, bool per_column, int mode, const List *lists, in
         // the listed vectors of the column copy, scattered into the rows (u64 only): one walk per list
         SCANRS_HIP(hipMemsetAsync(d_out, 0, 2 * stride * 8, s));
         for (int k = 0; k < n_lists; k++) {
-            subset_progress(snoop, n_all ? (double)(k ? local[0].n : 0) / (double)n_all : 0.0);
+            snoop_poll(snoop, n_all ? (double)(k ? local[0].n : 0) / (double)n_all : 0.0);
             launch_subset_listed_scatter(st, cp, d_list[k], local[k].n, d_out + (uint64_t)k * stride);
         }
     }
@@ -250,7 +237,7 @@ void subset_sums(scanrs_mat *m, bool per_column, int mode, const List *lists, in
         res_stride = n_final;
     }
     SCANRS_SYNC(s);
-    subset_progress(snoop, 1.0); // (a cancellation up to here leaves the outputs untouched)
+    snoop_poll(snoop, 1.0); // (a cancellation up to here leaves the outputs untouched)
     if (fixed) {
         std::vector<unsigned long long> h_fx(4 * n_final);
         std::vector<uint32_t> h_bad(n_final);
