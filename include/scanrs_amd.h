@@ -952,7 +952,15 @@ enum { SCANRS_NB_EXACT_LOGSPACE = 0, SCANRS_NB_EXACT_RATIO = 1 };
  * observed term U[x_a] is 0 or not finite; here a test whose U[x_a] is not finite or below 2^-970 falls back, in the same call,
  * and gets exactly the p-value that backend = LogSpace gives it. For 0 < U[x_a] < 2^-970 the terms at and below U[x_a] sink
  * into the denormals and the serial partition loses its bits (at U[x_a] = 4.9e-324 the serial restatement returns 5.9e-323
- * where LogSpace returns 0). Elsewhere the device sums the reference's terms in a fixed tree rather than serially. */
+ * where LogSpace returns 0). Elsewhere the device sums the reference's terms in a fixed tree rather than serially.
+ * Both backends differ from the reference in one more deliberate way, on the device and in the host forms below. With
+ * sf_a / phi == sf_b / phi bit for bit the terms k and n - k are equal in exact arithmetic, so the mirror n - x_a of the observed
+ * term belongs to the extreme set; the reference leaves that to `<=` on two differently rounded numbers and loses the mirror in
+ * some cases (measured on its formulas in double precision: (x_a, x_b, sf, mu, phi) = (30, 2000, 50, 20, 0.5) LogSpace 4.86e-89
+ * for 7.83e-89; (450, 440, 5e5, 1e-3, 0.13) Ratio 0.7377 for 0.7629; (120, 80, 7, 10, 0.3) Ratio 0.2175 for 0.2292). Here LogSpace
+ * forms a term as the sum of one number per side, which the mirror term adds in the other order (the same bits), and Ratio takes
+ * the mirror term by its index. LogSpace also takes ln Gamma(sf/phi + k) - ln Gamma(sf/phi) as one quantity (no cancellation of
+ * two values of size (sf/phi) ln(sf/phi)); at sf/phi = 2e8 the reference's formula in double precision is off by 1e-7 to 2e-6 of p. */
 int scanrs_sseq_de_backend(scanrs_mat *m, const int16_t *labels, uint32_t n_groups, int mode, const double *size_factors,
                            const double *gene_means, const double *gene_phi, const uint8_t *use_genes, uint64_t big_count, int backend,
                            const scanrs_snoop *snoop, uint64_t *sums_in, uint64_t *sums_out, double *p, double *p_adj, double *log2fc,
@@ -1018,12 +1026,14 @@ int scanrs_multi_sseq_de_pairs(scanrs_multi *mm, int transposed, const int16_t *
 /* percentile_of_sorted(.., 50) (stat.rs:140-162) of the union of two ascending lists; host only */
 int scanrs_host_union_median(const double *a, uint64_t n_a, const double *b, uint64_t n_b, double *out);
 /* the shared math on the host (no device needed; the kernels run the same special functions): `nb_exact_test`
- * (dist.rs:74-118), `nb_asymptotic_test` (:226-257), `log_prob_all` (:259-310, n + 1 values), `adjusted_pvalue_bh` (:22-50,
- * out[i] belongs to p[i]), and the regularised incomplete beta function and its inverse in p */
+ * (dist.rs:74-118), `nb_asymptotic_test` (:226-257), `log_prob_all` (:259-310, n + 1 values: the terms scanrs_host_nb_exact_test
+ * sums), `adjusted_pvalue_bh` (:22-50, out[i] belongs to p[i]), and the regularised incomplete beta function and its
+ * inverse in p */
 int scanrs_host_nb_exact_test(uint64_t x_a, uint64_t x_b, double sf_a, double sf_b, double mu, double phi, double *p);
 int scanrs_host_nb_asymptotic_test(uint64_t x_a, uint64_t x_b, double sf_a, double sf_b, double mu, double phi, double *p);
 /* `nb_exact_test_ratio` (dist.rs:155-215), host only, line for line: the three guards (exactly 1.0), the scan for the anchor, the
- * two sweeps, the serial sums, and the fallback to scanrs_host_nb_exact_test when the observed term is 0 or not finite. */
+ * two sweeps, the serial sums, and the fallback to scanrs_host_nb_exact_test when the observed term is 0 or not finite. One line is
+ * added: with sa_r == sb_r the mirror term n - x_a is extreme whatever its rounding (see scanrs_sseq_de_backend). */
 int scanrs_host_nb_exact_test_ratio(uint64_t x_a, uint64_t x_b, double sf_a, double sf_b, double mu, double phi, double *p);
 /* `nb_exact_ratio_step` (dist.rs:124-126), host only: T(k+1)/T(k) = (sa_r + k)(n - k) / ((k + 1)(sb_r + n - k - 1)) */
 int scanrs_host_nb_exact_ratio_step(double k, double n, double sa_r, double sb_r, double *out);

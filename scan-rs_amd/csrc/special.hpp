@@ -10,6 +10,7 @@
 //                   the mean where it converges, the symmetry I_x(a,b) = 1 - I_{1-x}(b,a) on the other
 //   betaincinv      x with I_x(a, b) = p: Newton steps on the density, kept inside a shrinking bracket (bisection when a
 //                   step would leave it; geometric halving while the lower end is still 0)
+//   lgamma_rise     ln Γ(y + k) - ln Γ(y) as one quantity, without the cancellation of two large ln Γ values
 //   nb_term         ln of one term of the exact test's conditional distribution (dist.rs:259-310, written per term)
 //   nb_asymptotic   the beta approximation of the exact test (dist.rs:226-257)
 //
@@ -168,15 +169,38 @@ SCANRS_HD inline double betaincinv(double a, double b, double p) {
     return x;
 }
 
-// ln of term k of the exact test's distribution of x_a given x_a + x_b = n (dist.rs:259-310 per term: the reference's running
-// recurrence written directly, so that every term - the observed one included - is the same function of its own k)
-SCANRS_HD inline double nb_term(uint64_t k, uint64_t n, double sar, double sbr, double add_total) {
-    const double kk = (double)k, jj = (double)(n - k);
-    return lgamma_pos(sar + kk) + lgamma_pos(sbr + jj) - lgamma_pos(kk + 1.0) - lgamma_pos(jj + 1.0) + add_total;
+// ln Γ(y + k) - ln Γ(y), y > 0, k = 0, 1, 2, ..., as one quantity: exactly 0 at k = 0. Below 15 the argument is raised, ln Γ(y + k) - ln Γ(y) =
+// ln[y (y+1) ... (y+m-1)] + ln Γ(y + k) - ln Γ(y + m), and the product alone serves k <= m; from 15 on Stirling's series gives the difference
+// (lgamma_diff_large). Two rounded ln Γ values of size y ln y would leave an ulp of THAT in a difference of size k ln y: at y = sf / φ = 2e8
+// (the rest side of a one-vs-rest test) 4.8e-7 in the logarithm of every term, independently per term.
+SCANRS_HD inline double lgamma_rise(double y, double k) {
+    if (y >= STIRLING_MIN) return -lgamma_diff_large(y, k);
+    double prod = 1.0;
+    while (y < STIRLING_MIN && k > 0.0) {
+        prod *= y;
+        y += 1.0;
+        k -= 1.0;
+    }
+    const double head = log(prod); // log(1.0) = 0 where nothing was raised
+    return k > 0.0 ? head - lgamma_diff_large(y, k) : head;
 }
-// the constant of log_prob_all (dist.rs:264), literal: (sa + sb) ln(r/(r+μ)) as the reference writes it
+
+// ln of term k of the exact test's distribution of x_a given x_a + x_b = n (dist.rs:259-310 per term: the reference's running
+// recurrence written directly, so that every term - the observed one included - is the same function of its own k):
+//   [ln Γ(sar + k) - ln Γ(sar) - ln k!] + [ln Γ(sbr + n-k) - ln Γ(sbr) - ln (n-k)!] + add_total
+// Each side is one number of its own count; with sar == sbr the mirror term n - k adds the same two numbers in the other order and has the
+// same bits, so `<=` against the observed term includes it. Nothing here is contracted: a fused multiply-add across the two sides would
+// round one of them and not the other.
+SCANRS_HD inline double nb_side(double sr, double count) { return lgamma_rise(sr, count) - lgamma_pos(count + 1.0); }
+SCANRS_HD inline double nb_term(uint64_t k, uint64_t n, double sar, double sbr, double add_total) {
+#pragma clang fp contract(off)
+    const double a = nb_side(sar, (double)k), b = nb_side(sbr, (double)(n - k));
+    return (a + b) + add_total;
+}
+// the constant of log_prob_all (dist.rs:264) without its two ln Γ(s r), which nb_term's differences hold: n ln(μ/(r+μ)) + (sa + sb) ln(r/(r+μ)),
+// literal as the reference writes it
 SCANRS_HD inline double nb_add_total(uint64_t n, double sa, double sb, double mu, double r) {
-    return (double)n * log(mu / (r + mu)) + (sa + sb) * log(r / (r + mu)) - lgamma_pos(sa * r) - lgamma_pos(sb * r);
+    return (double)n * log(mu / (r + mu)) + (sa + sb) * log(r / (r + mu));
 }
 
 // dist.rs:226-257

@@ -144,12 +144,22 @@ double sseq_host_exact_test_ratio(uint64_t xa, uint64_t xb, double sf_a, double 
     for (uint64_t k = mode; k-- > 0;) u[k] = u[k + 1] / ratio_step((double)k, nn, sa_r, sb_r);
     const double u_obs = u[xa];
     if (u_obs == 0.0 || !std::isfinite(u_obs)) return sseq_host_exact_test(xa, xb, sf_a, sf_b, mu, phi);
+    // sa_r == sb_r: the terms k and n - k are equal in exact arithmetic, and the two sweeps round them apart. The mirror of the observed term
+    // belongs to the extreme set whichever way that went (the reference leaves it to `<=` and drops it in some cases)
+    const uint64_t mirror = sa_r == sb_r ? n - xa : xa;
     double sum_all = 0.0, sum_ext = 0.0;
-    for (double v : u) {
-        sum_all += v;
-        if (v <= u_obs) sum_ext += v;
+    for (uint64_t k = 0; k <= n; k++) {
+        sum_all += u[k];
+        if (u[k] <= u_obs || k == mirror) sum_ext += u[k];
     }
     return sum_ext / sum_all;
+}
+
+// log_prob_all (dist.rs:259-310): the terms the exact test sums, from the same rounded sf r it passes to them
+static void sseq_host_log_prob_all(uint64_t n, double sf_a, double sf_b, double mu, double r, double *out) {
+    const double sar = sf_a * r, sbr = sf_b * r;
+    const double add = special::nb_add_total(n, sf_a, sf_b, mu, r);
+    for (uint64_t k = 0; k <= n; k++) out[k] = special::nb_term(k, n, sar, sbr, add);
 }
 
 // The anchor of nb_exact_test_ratio (dist.rs:178-184: the first k in 0 .. n-1 with step(k) < 1, else n) without the scan.
@@ -571,7 +581,7 @@ void sseq_refuse_sharded(const scanrs_mat *m, const char *what) {
 } // namespace scanrs
 
 // ---- the extern "C" entry points. NOT under this file's contract(off): special.hpp's inline functions are compiled with the default contraction
-// (included above the pragma); a wrapper that feeds them a product (scanrs_host_nb_log_prob_all: sf * r) must contract with them as the device code does
+// (included above the pragma), as in the device code
 #pragma clang fp contract(fast)
 using namespace scanrs;
 extern "C" {
@@ -683,8 +693,7 @@ int scanrs_host_nb_asymptotic_test(uint64_t x_a, uint64_t x_b, double sf_a, doub
 int scanrs_host_nb_log_prob_all(uint64_t n, double sf_a, double sf_b, double mu, double r, double *out) {
     return guard([&] {
         if (!out) fail(SCANRS_ERR_ARGUMENT, "null argument");
-        const double add = special::nb_add_total(n, sf_a, sf_b, mu, r);
-        for (uint64_t k = 0; k <= n; k++) out[k] = special::nb_term(k, n, sf_a * r, sf_b * r, add);
+        sseq_host_log_prob_all(n, sf_a, sf_b, mu, r, out);
     });
 }
 int scanrs_host_adjusted_pvalue_bh(const double *p, uint64_t n, double *out) {

@@ -15,6 +15,9 @@
 //                             the terms with ratio_chunk_terms, so U <= U[x_a] holds with equality at k = x_a
 //   sseq_ratio_combine_kernel one thread per test adds its chunks in chunk order: p = Σ_ext / Σ_all, or SSEQ_RATIO_FALLBACK
 //
+// One rule is the library's own: with sar == sbr bit for bit the terms k and n - k are equal in exact arithmetic, and the mirror n - x_a
+// of the observed term is extreme whatever the roundings of the two sweeps made of it (the reference's `<=` drops it in some cases).
+//
 // Range: in the unimodal case every outward factor is <= 1, so every partial product is <= 1 and a product that underflows
 // does so where the serial sweep's term does; in the U-shaped case (sa_r, sb_r < 1) the anchor is a boundary and the terms
 // stay within N^|sa_r - sb_r| < N of it (dist.rs:136-146). A test whose U[x_a] is not finite or below 2^-970 is not
@@ -172,12 +175,17 @@ __global__ __launch_bounds__(SSEQ_CHUNK_THREADS) void sseq_ratio_terms_kernel(co
             const SseqRatioTest t = tests[i];
             const RatioChunk ch = ratio_chunk_of(t, c - t.chunk0);
             ratio_chunk_terms(t, ch, scale[c], wtot, v);
+            // sar == sbr: the mirror n - x_a of the observed term equals it in exact arithmetic and is extreme whatever the two sweeps' roundings
+            // made of it; its local index on this chunk's side, or 0 (no term: t >= 1) when it lies on the other side or at the anchor
+            const uint64_t mk = t.n - t.xa;
+            const uint64_t mt = t.sar != t.sbr ? 0 : ch.up ? (mk > t.anchor ? mk - t.anchor : 0) : (mk < t.anchor ? t.anchor - mk : 0);
             double s_all = 0.0, s_ext = 0.0;
 #pragma unroll
             for (uint32_t j = 0; j < SSEQ_TERMS_PER_THREAD; j++) {
-                if (tid * SSEQ_TERMS_PER_THREAD + j < ch.cnt) {
+                const uint32_t l = tid * SSEQ_TERMS_PER_THREAD + j;
+                if (l < ch.cnt) {
                     s_all += v[j];
-                    if (v[j] <= o) s_ext += v[j];
+                    if (v[j] <= o || ch.t0 + l + 1 == mt) s_ext += v[j];
                 }
             }
             s_all = wave_sum(s_all);
@@ -210,7 +218,8 @@ __global__ void sseq_ratio_combine_kernel(const SseqRatioTest *__restrict__ test
     double p = SSEQ_RATIO_FALLBACK;
     if (isfinite(o) && o >= SSEQ_RATIO_MIN_OBS) {
         const uint64_t c0 = tests[i].chunk0, c1 = i + 1 < n_tests ? tests[i + 1].chunk0 : n_chunks;
-        double s_all = 1.0, s_ext = 1.0 <= o ? 1.0 : 0.0;
+        // the anchor's own term: extreme when it is the observed one's mirror too
+        double s_all = 1.0, s_ext = (1.0 <= o || (tests[i].sar == tests[i].sbr && tests[i].n - tests[i].xa == tests[i].anchor)) ? 1.0 : 0.0;
         for (uint64_t c = c0; c < c1; c++) {
             const double2 q = part[c];
             s_all += q.x;

@@ -5,6 +5,10 @@ of the library's Ratio kernels.
 `nb_exact_test_ratio` give the same bits with numpy's sequential accumulations (`multiply.accumulate`, `divide.accumulate` and
 `add.accumulate` run strictly left to right, and adding 0.0 to a partial sum leaves it unchanged); tests/test_sseq_ratio_cpu.py
 asserts that the two agree bit for bit, so that the GPU battery can afford n = 1e6.
+
+One rule is the library's and not the reference's: when sf_a / phi == sf_b / phi bit for bit, the terms k and n - k are equal in exact
+arithmetic, and the mirror term n - x_a belongs to the extreme set whatever the rounding of the two sweeps made of it. The reference leaves
+that to `<=` on the rounded terms and drops the mirror in some cases (p 3 to 38 % low; tests/test_sseq_exact_cpu.py has the measured rows).
 """
 from __future__ import annotations
 
@@ -51,9 +55,10 @@ def nb_exact_test_ratio_loop(x_a, x_b, sf_a, sf_b, mu, phi):
         return sseq_ref.nb_exact_test(x_a, x_b, sf_a, sf_b, mu, phi)
     sum_all = 0.0
     sum_ext = 0.0
-    for v in u:
+    mirror = n - int(x_a) if sa_r == sb_r else -1  # the library's rule for the exact tie (see the module docstring)
+    for k, v in enumerate(u):
         sum_all += v
-        if v <= u_obs:
+        if v <= u_obs or k == mirror:
             sum_ext += v
     return sum_ext / sum_all
 
@@ -101,7 +106,11 @@ def nb_exact_test_ratio(x_a, x_b, sf_a, sf_b, mu, phi):
     if o == 0.0 or not math.isfinite(o):
         return sseq_ref.nb_exact_test(x_a, x_b, sf_a, sf_b, mu, phi)
     sum_all = np.add.accumulate(u)[-1]
-    sum_ext = np.add.accumulate(np.where(u <= o, u, 0.0))[-1]
+    ext = u <= o
+    r = 1.0 / phi
+    if sf_a * r == sf_b * r:
+        ext[int(x_b)] = True  # the mirror term n - x_a
+    sum_ext = np.add.accumulate(np.where(ext, u, 0.0))[-1]
     return float(sum_ext / sum_all)
 
 

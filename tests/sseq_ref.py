@@ -1,6 +1,7 @@
 """CPU restatement of the reference's sSeq differential expression (diff-exp/src/{dist,stat,diff_exp,utils}.rs) with
 numpy and scipy, the checker of the library's DE. Matrices are scipy.sparse, genes x cells. The exact test is evaluated
-with gammaln term by term (the reference's running recurrence written directly)."""
+term by term (the reference's running recurrence written directly), its ln Γ differences without the cancellation of two large gammaln
+values (gammaln_rise); `direct=True` gives the formula with gammaln of every argument."""
 from __future__ import annotations
 
 import numpy as np
@@ -26,19 +27,44 @@ def adjusted_pvalue_bh(p):
     return out
 
 
-def log_prob_all(count, sa, sb, mu, r):
-    """dist.rs:259-310, term by term (k = 0 .. count)."""
+def _stirling_tail(z):
+    """ln Γ(z) - [(z - 1/2) ln z - z + 1/2 ln 2π] for z >= 15: the series B_2m / (2m (2m-1) z^(2m-1)), 8 terms"""
+    t = 1.0 / (z * z)
+    s = np.zeros_like(t)
+    for c in (-3617.0 / 122400.0, 1.0 / 156.0, -691.0 / 360360.0, 1.0 / 1188.0, -1.0 / 1680.0, 1.0 / 1260.0, -1.0 / 360.0, 1.0 / 12.0):
+        s = s * t + c
+    return s / z
+
+
+def gammaln_rise(y, k):
+    """ln Γ(y + k) - ln Γ(y) for a scalar y > 0 and an array k >= 0 as one quantity. From y = 15 on Stirling's series gives the difference itself;
+    gammaln(y + k) - gammaln(y) would carry an ulp of ln Γ(y) ~ y ln y, 5e-7 at y = 2e8, where the difference is of size k ln y. Below 15
+    ln Γ(y) is small and the plain difference loses nothing."""
+    k = np.asarray(k, dtype=np.float64)
+    if y < 15.0:
+        return gammaln(y + k) - gammaln(y)
+    z = y + k
+    return (y - 0.5) * np.log1p(k / y) + k * np.log(z) - k + _stirling_tail(z) - _stirling_tail(np.float64(y))
+
+
+def log_prob_all(count, sa, sb, mu, r, direct=False):
+    """dist.rs:259-310, term by term (k = 0 .. count). direct: with gammaln of every argument, as the reference writes the constant; otherwise
+    (what the tests check the library with) the two ln Γ differences are taken as such, see gammaln_rise. tests/test_sseq_exact_cpu.py holds
+    this form to the high-precision reference."""
     k = np.arange(count + 1, dtype=np.float64)
     j = count - k
-    add_total = count * np.log(mu / (r + mu)) + (sa + sb) * np.log(r / (r + mu)) - gammaln(sa * r) - gammaln(sb * r)
-    return gammaln(sa * r + k) + gammaln(sb * r + j) - gammaln(k + 1.0) - gammaln(j + 1.0) + add_total
+    const = count * np.log(mu / (r + mu)) + (sa + sb) * np.log(r / (r + mu))
+    if direct:
+        add_total = const - gammaln(sa * r) - gammaln(sb * r)
+        return gammaln(sa * r + k) + gammaln(sb * r + j) - gammaln(k + 1.0) - gammaln(j + 1.0) + add_total
+    return (gammaln_rise(sa * r, k) - gammaln(k + 1.0)) + (gammaln_rise(sb * r, j) - gammaln(j + 1.0)) + const
 
 
-def nb_exact_test(x_a, x_b, sf_a, sf_b, mu, phi):
+def nb_exact_test(x_a, x_b, sf_a, sf_b, mu, phi, direct=False):
     """dist.rs:74-118."""
     if x_a + x_b == 0 or phi == 0.0 or sf_a == 0.0 or sf_b == 0.0:
         return 1.0
-    lp = log_prob_all(int(x_a + x_b), sf_a, sf_b, mu, 1.0 / phi)
+    lp = log_prob_all(int(x_a + x_b), sf_a, sf_b, mu, 1.0 / phi, direct)
     return _p_from_terms(lp, lp <= lp[int(x_a)])
 
 
