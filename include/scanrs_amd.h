@@ -668,6 +668,8 @@ int scanrs_mat_set_spmm_path(scanrs_mat *m, int path);
  *   "merge_fused" (1)   scanrs_merge_clusters: per-cell totals plus ONE grouped pass over the nonzeros per call (per gene-major tile of
  *                       1536 clusters), every candidate from those sums; 0: compute_sseq_params on the union and the pairwise DE for
  *                       every candidate, as the reference calls them (A/B and test baseline). Same labels; p-values agree to ~1e-12
+ *   "sseq_grid_cap" (16384) workgroups of the sSeq group / moment pass and of its class walk at most (1 .. 16384). Results do not depend
+ *                       on it; a small cap makes every wave take several genes or cells in turn, which tests use on small matrices
  *   "subset_scatter" (1) integer sums over a column list (scanrs_mat_sum_rows_u64, _sum_cols_u64, _sum_rows_dual_u64) whose result axis is
  *                       the outer dimension of a copy that does not exist yet: 1 = scattered into the result with 64-bit integer atomics
  *                       from the copy that exists (exact in any order; no transposed copy is built); 0 = the missing copy is built
@@ -915,7 +917,16 @@ int scanrs_host_sym_eig_topk(const double *a, int n, int k, double *w, double *z
 /* `compute_sseq_params` (diff_exp.rs:458-500). cell_indices (n_sel entries, or NULL for every cell): only those cells get a
  * size factor, the rest 0. umi_counts (one per selected cell, or NULL): replaces the per-cell totals. Size factors are the
  * totals over their interpolated median (stat.rs:116). Outputs: size_factors (cols), gene_means, gene_variances, use_genes,
- * gene_moment_phi, gene_phi (rows each), zeta_hat and delta (one each). */
+ * gene_moment_phi, gene_phi (rows each), zeta_hat and delta (one each).
+ * The moments. Σ x/sf_c and Σ (x/sf_c)² are exact integer sums of the f64 terms, each rounded once to a power-of-two quantum
+ * (128-bit fixed point: no floating-point atomics, the same bits from either copy, any arrival order and any sharding). For EVERY
+ * gene the mean is within 1e-12 of its exact value relative and the variance within 1e-10 S2 / m absolute (S2 the gene's own
+ * Σ (x/sf_c)², m the number of selected cells), whatever the spread of the counts and of the size factors (terms x/sf_c between
+ * 2^-440 and 2^440). One quantum serves all genes - chosen from the bound m max_count max(1/sf) of the largest sum - when a count
+ * of 1 under the largest factor keeps 40 bits of its own below it, and 33 bits of its square below the second sum's; otherwise one
+ * more walk over the nonzeros finds every gene's largest term (an integer maximum; on a sharded handle one more u64 all-reduce of
+ * genes x world entries) and every gene is rounded to a quantum of its own. tests/test_gpu_sseq_moments.py holds this to exact
+ * rational sums. */
 int scanrs_sseq_params(scanrs_mat *m, double zeta_quintile, const uint64_t *cell_indices, uint64_t n_sel, const double *umi_counts,
                        double *size_factors, double *gene_means, double *gene_variances, uint8_t *use_genes, double *gene_moment_phi,
                        double *zeta_hat, double *delta, double *gene_phi);
@@ -986,16 +997,20 @@ int scanrs_sseq_de_from_sums_backend(uint64_t n_genes, uint32_t n_tests, const u
  * group index >= n_groups, pair_a[j] == pair_b[j], a pair whose union has no cell, n_pairs = 0, a bad backend, a sharded handle. A
  * pair with exactly one empty side is valid: that side's size factor is 0 and every p is 1, as in the reference. A pair whose
  * union has a median total of 0 (no finite size factor) runs the two reference calls themselves in the same call (`literal`).
+ * So does a pair whose union holds a cell total u so large that a count of 1 in that cell would lose its bits under the call's one
+ * quantum (terms x/u_c <= 1 under 2^(ilogb(cells) - 123): literal when (1/u)² keeps fewer than 33 bits, u above 2^35 at 2^20 cells):
+ * scanrs_sseq_params gives every gene a quantum of its own there, and the moments of every pair keep the bounds stated with it.
  * Checkpoints of `snoop`: 0.0, 0.1 (totals and pair headers), 0.6 (grouped pass and parameters), 0.75, 0.9, 0.95, 1.0.
  * Counters (scanrs_mat_get_counter): "de_pairs_passes" = passes over the nonzeros in the last call (2, or 1 + the tiles of groups of a
- * gene-major copy, plus 4 per literal pair); "de_pairs_literal" = pairs that took the literal route.
+ * gene-major copy, plus 4 per literal pair, 5 where that pair's scanrs_sseq_params walks the nonzeros once more for a quantum per
+ * gene); "de_pairs_literal" = pairs that took the literal route.
  * `params` (may be NULL) receives what each pair was tested with. */
 typedef struct {            /* every pointer may be NULL; arrays genes x n_pairs row-major, or n_pairs */
     double *gene_means, *gene_variances, *gene_moment_phi, *gene_phi;
     uint8_t *use_genes;
     double *zeta_hat, *delta, *sf_a, *sf_b, *median_total, *sum_size_factors;
     uint64_t *n_cells_a, *n_cells_b;
-    uint8_t *literal;       /* 1: the pair took the literal route (median total 0) */
+    uint8_t *literal;       /* 1: the pair took the literal route (median total 0, or a cell total beyond the shared quantum) */
 } scanrs_sseq_pair_params;
 int scanrs_sseq_de_pairs(scanrs_mat *m, const int16_t *labels, uint32_t n_groups, const uint32_t *pair_a, const uint32_t *pair_b,
                          uint32_t n_pairs, double zeta_quintile, uint64_t big_count, int backend, const scanrs_snoop *snoop,
@@ -1012,7 +1027,7 @@ int scanrs_sseq_de_pairs(scanrs_mat *m, const int16_t *labels, uint32_t n_groups
  * the bit patterns of the p-values, whose tests are split over the ranks by gene as in scanrs_sseq_de. The group statistics, the pair
  * headers and the per-pair parameters run replicated on every rank from the reduced integers; a literal pair runs the sharded
  * scanrs_sseq_params + scanrs_sseq_de calls on every rank. Counters: "de_shard_allreduces" = the exchange steps of the last call
- * (2 + the accumulator tiles + 5 per literal pair), "de_shard_tests" = the tests this rank launched. On an unsharded handle the call
+ * (2 + the accumulator tiles + 5 per literal pair, 6 where its moments take a quantum per gene: the genes' classes), "de_shard_tests" = the tests this rank launched. On an unsharded handle the call
  * is scanrs_sseq_de_pairs. scanrs_multi_sseq_de_pairs runs the collective call on every shard of a scanrs_multi from one process
  * (transposed != 0: the matrix was created cells x genes); shard 0 writes the caller's arrays and reports progress. */
 int scanrs_sseq_de_pairs_sharded(scanrs_mat *m, const int16_t *labels, uint32_t n_groups, const uint32_t *pair_a, const uint32_t *pair_b,
@@ -1085,7 +1100,8 @@ typedef struct {
  * (SCANRS_ERR_CANCELLED; no progress is reported, as in the reference). trace may be NULL.
  * Handle option "merge_fused" (default 1): the per-cell totals, then ONE pass over the nonzeros that gathers per (gene, cluster)
  * Σ x, Σ x/u_c and Σ (x/u_c)² (u_c the cell's total; 128-bit fixed point) makes each candidate's params and sums an O(genes)
- * combination (a union whose median total is 0 takes the literal route); 0: every candidate runs compute_sseq_params on the union
+ * combination (a union whose median total is 0, or which holds a cell total beyond the shared quantum as in scanrs_sseq_de_pairs,
+ * takes the literal route); 0: every candidate runs compute_sseq_params on the union
  * and the pairwise DE on the device, call for call as the reference (the A/B baseline). */
 int scanrs_merge_clusters(scanrs_mat *m, const double *pca, int pca_is_device, uint32_t ld, uint32_t d, const int16_t *labels,
                           int16_t *labels_out, const scanrs_snoop *snoop, scanrs_merge_trace *trace);

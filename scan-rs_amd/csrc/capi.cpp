@@ -1444,6 +1444,8 @@ int scanrs_mat_set_option(scanrs_mat *m, const char *key, double value) {
             st.col_moments = (int)as_u32(0, 2);
         } else if (k == "device_factor") {
             st.device_factor = value != 0.0;
+        } else if (k == "sseq_grid_cap") {
+            st.sseq_grid_cap = as_u32(1, 16384);
         } else if (k == "merge_fused") {
             st.merge_fused = (int)as_u32(0, 1);
         } else if (k == "subset_scatter") {

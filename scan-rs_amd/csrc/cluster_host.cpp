@@ -411,7 +411,7 @@ void merge_clusters_run(Storage &st, const SparseCopy &cp, bool gene_major, uint
         std::vector<uint64_t> si(genes * 1), so(genes * 1);
         sseq_de_matrix(st, cp, gene_major, genes, cells_local, lab3.data(), 2, 1, sf.data(), mean.data(), phi.data(), use.data(), BIG_COUNT, nullptr,
                        si.data(), so.data(), p.data(), padj.data(), l2.data(), mi.data(), mo.data());
-        passes += 4; // totals, max count, moments, group sums
+        passes += 3 + st.sseq_moment_walks; // totals, max count, moments (the class walk first where every gene gets its quantum), group sums
         shard_tests += st.de_shard_tests;
         summarize(padj, cd);
     };
@@ -420,6 +420,10 @@ void merge_clusters_run(Storage &st, const SparseCopy &cp, bool gene_major, uint
         const FusedCluster &A = fc[l0], &B = fc[l1];
         const double m_s = union_median(A.totals, B.totals);
         if (m_s == 0.0) return literal(l0, l1, cd); // size factors are not finite: the literal route keeps that case's handling
+        // a cell total so large that a count of 1 in that cell would not keep its bits under the pass's quantum (fixed128.hpp): the
+        // literal route's moments choose a quantum per gene
+        const double top = std::max(A.totals.empty() ? 0.0 : A.totals.back(), B.totals.empty() ? 0.0 : B.totals.back());
+        if (!fixed_totals_quantum_keeps((unsigned long long)top, scale)) return literal(l0, l1, cd);
         const double n_s = (double)(n_cells[l0] + n_cells[l1]);
         U128 inv = A.inv;
         add128(inv, B.inv);

@@ -409,6 +409,8 @@ struct Storage {
     uint64_t subset_masked_passes = 0, subset_scatter_passes = 0; // sums over a column list made so far on this handle: from the copy whose outer dimension is the result axis / through the integer scatter (scanrs_mat_get_counter)
     uint64_t knn_blocks = 0, knn_allreduces = 0; // the last scanrs_knn_sharded on this handle: blocks of the point set searched, exchange steps (an unsharded one: 0)
     uint64_t subset_allreduces = 0;       // exchange steps of the last scanrs_mat_sum_rows_*_sharded (and kin) on this handle (an unsharded one: 0)
+    uint64_t sseq_moment_walks = 0;       // the last sseq_params on this handle: walks over the nonzeros for the moments, 1 under one quantum, 2 with a quantum per gene (the class walk first)
+    uint32_t sseq_grid_cap = 16384;       // workgroups of the moment / group pass and the class walk at most (option "sseq_grid_cap": a small cap makes every wave take several outer vectors, for tests)
     int merge_fused = 1;                  // merge_clusters: 1 = one grouped pass per call, candidates from its sums; 0 = params + pairwise DE per candidate (the reference's calls)
     size_t l2_tile_bytes = 3584u << 10;   // panel slice per step of the L2-blocked gather (4 MB L2 per XCD): whole 1024-row base tiles up to 3.5 MB — 4 tiles (3.2 MB) at 100 columns, 3 (2.9 MB) at 122; measured 40.55 / 39.71 ms per pass against 41.30 / 40.23 with 3 tiles and 40.86 / 39.61 with 5, and 4 tiles of 122 columns (3.9 MB) lose 1.8 ms
     int spmm_order = 1;                   // L2-blocked gather: launch outer vectors longest first: 0 never, 1 auto, 2 always (SCANRS_SPMM_ORDER)
@@ -758,10 +760,14 @@ struct SseqRatioTest {       // one exact test of the Ratio backend (sseq_ratio.
 constexpr double SSEQ_RATIO_FALLBACK = -1.0; // written in place of a p-value: the test has to go through the LogSpace kernels
 uint32_t sseq_max_count(Storage &st, const SparseCopy &cp);
 void launch_sseq_cell_totals(Storage &st, const SparseCopy &cp, bool gene_major, uint64_t n_cells, unsigned long long *d_tot);
-// sums: genes x n_groups; with d_mom also Σ x/sf and Σ (x/sf)² over the labelled cells as 128-bit fixed point (genes x 4 u64)
+// sums: genes x n_groups; with d_mom also Σ x/sf and Σ (x/sf)² over the labelled cells as 128-bit fixed point (genes x 4 u64), under
+// scale1 / scale2, or with d_cls under every gene's own scales (fixed128.hpp: its class and log2m, 2^log2m >= the number of labelled cells)
 void launch_sseq_group_pass(Storage &st, const SparseCopy &cp, bool gene_major, uint64_t n_genes, const int16_t *d_labels, uint32_t n_groups,
                             unsigned long long *d_sums, const double *d_sf, double scale1, double scale2, unsigned long long *d_mom,
-                            uint32_t *d_bad);
+                            uint32_t *d_bad, const uint32_t *d_cls = nullptr, int log2m = 0);
+// per gene the class of its largest finite x/sf_c over the labelled cells of this copy (0: none)
+void launch_sseq_term_class(Storage &st, const SparseCopy &cp, bool gene_major, uint64_t n_genes, const int16_t *d_labels, const double *d_sf,
+                            uint32_t *d_cls);
 // sharded handles: the two 128-bit sums and the bad flag of every gene as u64 limbs (genes x SSEQ_LIMB_STRIDE) for the u64 all-reduce, and back
 constexpr uint32_t SSEQ_LIMB_STRIDE = 9;
 void launch_sseq_mom_split(Storage &st, const unsigned long long *d_mom, const uint32_t *d_bad, uint64_t n_genes, unsigned long long *d_limbs);

@@ -12,9 +12,12 @@
 //   sseq_ratio_*_kernel      the Ratio backend of the exact test (dist.rs:116-215): sseq_ratio.inc
 //
 // No float atomics. The moments are accumulated as 128-bit FIXED-POINT integers (two u64 words, carry counted
-// with an integer atomic): every term x/sf_c is rounded once to a quantum of 2^-E (E chosen per launch from a bound of the
-// sums, so that every sum fits below 2^126), and the integer sum is exact, so the result depends neither on the order in
-// which the waves arrive nor on which copy of the matrix was walked: both orientations give the same bits.
+// with an integer atomic): every term x/sf_c is rounded once to a quantum of 2^-E, and the integer sum is exact, so the result
+// depends neither on the order in which the waves arrive nor on which copy of the matrix was walked: both orientations give the
+// same bits. E is chosen per launch from a bound of the sums (every sum fits below 2^124) where the smallest possible term keeps
+// its bits under that quantum, and per gene otherwise, from the class of the gene's largest term (sseq_term_class_kernel, one
+// more walk; fixed128.hpp has the rule and sseq_host.cpp the choice): every gene's mean comes back within 1e-12 relative and its
+// variance within 1e-10 of its own Σ (x/sf_c)² / m, whatever the other genes hold.
 #include "common.hpp"
 #include "fixed128.hpp"
 #include "special.hpp"
@@ -22,13 +25,14 @@
 namespace scanrs {
 
 // d_mom (rows x 4 u64): [lo, hi] of Σ x/sf, [lo, hi] of Σ (x/sf)²; d_bad: per gene, a term was not finite (sf = 0 with x > 0)
-template <bool MOM>
+// MOM: 0 the group sums only; 1 the moments under the launch's two scales; 2 under every gene's own scales, from its class gcls[g]
+template <int MOM>
 __global__ __launch_bounds__(256) void sseq_gene_major_kernel(const uint64_t *__restrict__ indptr, const uint32_t *__restrict__ indices,
                                                               const uint32_t *__restrict__ values, uint64_t n_genes,
                                                               const int16_t *__restrict__ labels, uint32_t n_groups,
                                                               unsigned long long *__restrict__ sums, const double *__restrict__ sf,
                                                               double scale1, double scale2, unsigned long long *__restrict__ mom,
-                                                              uint32_t *__restrict__ bad) {
+                                                              uint32_t *__restrict__ bad, const uint32_t *__restrict__ gcls, int log2m) {
     extern __shared__ unsigned long long gm_acc[]; // [wave][group]
     const uint32_t lane = threadIdx.x & 63u, wave = threadIdx.x >> 6, n_waves = blockDim.x >> 6;
     unsigned long long *acc = gm_acc + (size_t)wave * n_groups;
@@ -40,6 +44,10 @@ __global__ __launch_bounds__(256) void sseq_gene_major_kernel(const uint64_t *__
         uint32_t nonfinite = 0;
         if (g < n_genes) {
             const uint64_t p0 = indptr[g], p1 = indptr[g + 1];
+            if (MOM == 2) { // uniform over the wave
+                scale1 = fixed_class_scale1(gcls[g], log2m);
+                scale2 = fixed_class_scale2(gcls[g], log2m);
+            }
             for (uint64_t p = p0 + lane; p < p1; p += 64) {
                 const uint32_t c = indices[p];
                 const int l = labels[c];
@@ -79,13 +87,13 @@ __global__ __launch_bounds__(256) void sseq_gene_major_kernel(const uint64_t *__
 }
 
 // sums and mom are zeroed by the launcher
-template <bool MOM>
+template <int MOM>
 __global__ __launch_bounds__(256) void sseq_cell_major_kernel(const uint64_t *__restrict__ indptr, const uint32_t *__restrict__ indices,
                                                               const uint32_t *__restrict__ values, uint64_t n_cells,
                                                               const int16_t *__restrict__ labels, uint32_t n_groups,
                                                               unsigned long long *__restrict__ sums, const double *__restrict__ sf,
                                                               double scale1, double scale2, unsigned long long *__restrict__ mom,
-                                                              uint32_t *__restrict__ bad) {
+                                                              uint32_t *__restrict__ bad, const uint32_t *__restrict__ gcls, int log2m) {
     const uint32_t lane = threadIdx.x & 63u, n_waves = blockDim.x >> 6;
     for (uint64_t c = (uint64_t)blockIdx.x * n_waves + (threadIdx.x >> 6); c < n_cells; c += (uint64_t)gridDim.x * n_waves) {
         const int l = labels[c];
@@ -100,6 +108,11 @@ __global__ __launch_bounds__(256) void sseq_cell_major_kernel(const uint64_t *__
                 if (!isfinite(t)) {
                     bad[g] = 1u;
                     continue;
+                }
+                if (MOM == 2) {
+                    const uint32_t k = gcls[g];
+                    scale1 = fixed_class_scale1(k, log2m);
+                    scale2 = fixed_class_scale2(k, log2m);
                 }
                 atomic_add128(&mom[(uint64_t)g * 4 + 0], to_fixed(t, scale1));
                 atomic_add128(&mom[(uint64_t)g * 4 + 2], to_fixed(t * t, scale2));
@@ -125,6 +138,35 @@ __global__ __launch_bounds__(256) void sseq_cell_totals_kernel(const uint64_t *_
         if (outer_is_cell) {
             for (int off = 32; off > 0; off >>= 1) s += (unsigned long long)__shfl_down((long long)s, off);
             if (lane == 0) tot[o] = s;
+        }
+    }
+}
+
+// The class of every gene's moment sums (fixed128.hpp: from the largest finite x/sf_c over its labelled cells), from either copy: a
+// wave owns an outer vector; a gene's wave reduces and stores, a cell's wave scatters with an integer atomicMax. cls is zeroed by the
+// launcher. The squares need no class of their own: the largest square is the square of the largest term.
+__global__ __launch_bounds__(256) void sseq_term_class_kernel(const uint64_t *__restrict__ indptr, const uint32_t *__restrict__ indices,
+                                                              const uint32_t *__restrict__ values, uint64_t n_outer, int outer_is_gene,
+                                                              const int16_t *__restrict__ labels, const double *__restrict__ sf,
+                                                              uint32_t *__restrict__ cls) {
+    const uint32_t lane = threadIdx.x & 63u, n_waves = blockDim.x >> 6;
+    for (uint64_t o = (uint64_t)blockIdx.x * n_waves + (threadIdx.x >> 6); o < n_outer; o += (uint64_t)gridDim.x * n_waves) {
+        if (!outer_is_gene && labels[o] < 0) continue; // uniform over the wave
+        const uint64_t p0 = indptr[o], p1 = indptr[o + 1];
+        uint32_t k = 0;
+        for (uint64_t p = p0 + lane; p < p1; p += 64) {
+            const uint32_t i = indices[p];
+            if (outer_is_gene && labels[i] < 0) continue;
+            const double t = (double)values[p] / sf[outer_is_gene ? i : o];
+            if (!isfinite(t)) continue;
+            if (outer_is_gene)
+                k = max(k, fixed_term_class(t));
+            else
+                atomicMax(&cls[i], fixed_term_class(t));
+        }
+        if (outer_is_gene) {
+            for (int off = 32; off > 0; off >>= 1) k = max(k, (uint32_t)__shfl_xor((int)k, off));
+            if (lane == 0) cls[o] = k;
         }
     }
 }
@@ -321,7 +363,7 @@ void launch_sseq_cell_totals(Storage &st, const SparseCopy &cp, bool gene_major,
 
 void launch_sseq_group_pass(Storage &st, const SparseCopy &cp, bool gene_major, uint64_t n_genes, const int16_t *d_labels, uint32_t n_groups,
                             unsigned long long *d_sums, const double *d_sf, double scale1, double scale2, unsigned long long *d_mom,
-                            uint32_t *d_bad) {
+                            uint32_t *d_bad, const uint32_t *d_cls, int log2m) {
     const bool mom = d_mom != nullptr;
     if (mom) {
         SCANRS_HIP(hipMemsetAsync(d_mom, 0, std::max<uint64_t>(1, n_genes) * 32, st.stream));
@@ -331,25 +373,40 @@ void launch_sseq_group_pass(Storage &st, const SparseCopy &cp, bool gene_major, 
         // a wave's LDS row holds n_groups u64: up to 4 waves per workgroup within 64 KB
         const uint32_t waves = (uint32_t)std::max<uint64_t>(1, std::min<uint64_t>(4, 8192 / std::max<uint32_t>(1, n_groups)));
         const size_t lds = (size_t)waves * n_groups * 8;
-        const dim3 grid(blocks_for(n_genes, waves, 16384)), block(64 * waves);
-        if (mom)
-            hipLaunchKernelGGL(sseq_gene_major_kernel<true>, grid, block, lds, st.stream, cp.indptr.p, cp.indices.p, cp.values.p, n_genes, d_labels,
-                               n_groups, d_sums, d_sf, scale1, scale2, d_mom, d_bad);
+        const dim3 grid(blocks_for(n_genes, waves, st.sseq_grid_cap)), block(64 * waves);
+        if (mom && d_cls)
+            hipLaunchKernelGGL(sseq_gene_major_kernel<2>, grid, block, lds, st.stream, cp.indptr.p, cp.indices.p, cp.values.p, n_genes, d_labels,
+                               n_groups, d_sums, d_sf, scale1, scale2, d_mom, d_bad, d_cls, log2m);
+        else if (mom)
+            hipLaunchKernelGGL(sseq_gene_major_kernel<1>, grid, block, lds, st.stream, cp.indptr.p, cp.indices.p, cp.values.p, n_genes, d_labels,
+                               n_groups, d_sums, d_sf, scale1, scale2, d_mom, d_bad, d_cls, log2m);
         else
-            hipLaunchKernelGGL(sseq_gene_major_kernel<false>, grid, block, lds, st.stream, cp.indptr.p, cp.indices.p, cp.values.p, n_genes, d_labels,
-                               n_groups, d_sums, d_sf, scale1, scale2, d_mom, d_bad);
+            hipLaunchKernelGGL(sseq_gene_major_kernel<0>, grid, block, lds, st.stream, cp.indptr.p, cp.indices.p, cp.values.p, n_genes, d_labels,
+                               n_groups, d_sums, d_sf, scale1, scale2, d_mom, d_bad, d_cls, log2m);
     } else {
         SCANRS_HIP(hipMemsetAsync(d_sums, 0, std::max<uint64_t>(1, n_genes * n_groups) * 8, st.stream));
-        const dim3 grid(blocks_for(cp.n_outer, 4, 16384)), block(256);
+        const dim3 grid(blocks_for(cp.n_outer, 4, st.sseq_grid_cap)), block(256);
         if (cp.n_outer) {
-            if (mom)
-                hipLaunchKernelGGL(sseq_cell_major_kernel<true>, grid, block, 0, st.stream, cp.indptr.p, cp.indices.p, cp.values.p, cp.n_outer, d_labels,
-                                   n_groups, d_sums, d_sf, scale1, scale2, d_mom, d_bad);
+            if (mom && d_cls)
+                hipLaunchKernelGGL(sseq_cell_major_kernel<2>, grid, block, 0, st.stream, cp.indptr.p, cp.indices.p, cp.values.p, cp.n_outer, d_labels,
+                                   n_groups, d_sums, d_sf, scale1, scale2, d_mom, d_bad, d_cls, log2m);
+            else if (mom)
+                hipLaunchKernelGGL(sseq_cell_major_kernel<1>, grid, block, 0, st.stream, cp.indptr.p, cp.indices.p, cp.values.p, cp.n_outer, d_labels,
+                                   n_groups, d_sums, d_sf, scale1, scale2, d_mom, d_bad, d_cls, log2m);
             else
-                hipLaunchKernelGGL(sseq_cell_major_kernel<false>, grid, block, 0, st.stream, cp.indptr.p, cp.indices.p, cp.values.p, cp.n_outer,
-                                   d_labels, n_groups, d_sums, d_sf, scale1, scale2, d_mom, d_bad);
+                hipLaunchKernelGGL(sseq_cell_major_kernel<0>, grid, block, 0, st.stream, cp.indptr.p, cp.indices.p, cp.values.p, cp.n_outer,
+                                   d_labels, n_groups, d_sums, d_sf, scale1, scale2, d_mom, d_bad, d_cls, log2m);
         }
     }
+    SCANRS_HIP(hipGetLastError());
+}
+
+void launch_sseq_term_class(Storage &st, const SparseCopy &cp, bool gene_major, uint64_t n_genes, const int16_t *d_labels, const double *d_sf,
+                            uint32_t *d_cls) {
+    SCANRS_HIP(hipMemsetAsync(d_cls, 0, std::max<uint64_t>(1, n_genes) * 4, st.stream));
+    if (cp.n_outer)
+        hipLaunchKernelGGL(sseq_term_class_kernel, dim3(blocks_for(cp.n_outer, 4, st.sseq_grid_cap)), dim3(256), 0, st.stream, cp.indptr.p, cp.indices.p,
+                           cp.values.p, cp.n_outer, gene_major ? 1 : 0, d_labels, d_sf, d_cls);
     SCANRS_HIP(hipGetLastError());
 }
 

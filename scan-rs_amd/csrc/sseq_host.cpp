@@ -287,14 +287,24 @@ void sseq_params(Storage &st, const SparseCopy &cp, bool gene_major, uint64_t ge
     if (cell_indices)
         for (uint64_t i = 0; i < n_sel; i++) lab[cell_indices[i]] = 0;
     std::vector<double> sf_dev(cells);
-    double max_inv = 0.0;
+    double max_inv = 0.0, min_inv = INFINITY;
     for (uint64_t c = 0; c < cells; c++) {
         sf_dev[c] = std::isnan(sf[c]) ? 0.0 : sf[c];
-        if (lab[c] == 0 && sf_dev[c] > 0.0) max_inv = std::max(max_inv, 1.0 / sf_dev[c]);
+        if (lab[c] == 0 && sf_dev[c] > 0.0 && std::isfinite(sf_dev[c])) { // an infinite factor (a median of 0) makes terms of exactly 0
+            max_inv = std::max(max_inv, 1.0 / sf_dev[c]);
+            min_inv = std::min(min_inv, 1.0 / sf_dev[c]);
+        }
     }
+    // One quantum for all genes, from a bound of the largest sum (m terms of the largest count over the smallest factor), when the
+    // smallest term any gene can hold (a count of 1 over the largest factor) keeps its bits under it (fixed128.hpp); else a quantum per
+    // gene from the class of its largest term, which costs one more walk over the nonzeros. Everything the choice reads spans ALL cells
+    // (m, the factors, the all-reduced maximum count), so every rank of a sharded handle takes the same route.
     const double max_count = (double)sseq_max_count_global(st, cp);
     const double b1 = (double)m * max_count * max_inv;
     const double scale1 = fixed_scale(b1), scale2 = fixed_scale(b1 * max_count * max_inv);
+    const bool per_gene = !fixed_single_quantum_keeps(min_inv, scale1, scale2);
+    const int log2m = fixed_log2_ceil(m);
+    st.sseq_moment_walks = per_gene ? 2 : 1;
     int16_t *d_lab = st.scratch.get<int16_t>("sseq_labels", std::max<uint64_t>(1, cr.n_local));
     double *d_sf = st.scratch.get<double>("sseq_sf", std::max<uint64_t>(1, cr.n_local));
     unsigned long long *d_sums = st.scratch.get<unsigned long long>("sseq_sums", std::max<uint64_t>(1, genes));
@@ -302,10 +312,40 @@ void sseq_params(Storage &st, const SparseCopy &cp, bool gene_major, uint64_t ge
     uint32_t *d_bad = st.scratch.get<uint32_t>("sseq_bad", std::max<uint64_t>(1, genes));
     h2d(d_lab, lab.data() + cr.begin, cr.n_local, st.stream);
     h2d(d_sf, sf_dev.data() + cr.begin, cr.n_local, st.stream);
-    launch_sseq_group_pass(st, cp, gene_major, genes, d_lab, 1, d_sums, d_sf, scale1, scale2, d_mom, d_bad);
+    std::vector<uint32_t> cls;
+    uint32_t *d_cls = nullptr;
+    if (per_gene) {
+        d_cls = st.scratch.get<uint32_t>("sseq_cls", std::max<uint64_t>(1, genes));
+        launch_sseq_term_class(st, cp, gene_major, genes, d_lab, d_sf, d_cls);
+        cls.resize(genes);
+        if (genes) SCANRS_D2H(cls.data(), d_cls, genes * 4, st.stream);
+        SCANRS_SYNC(st.stream);
+        if (st.shard.active() && genes) {
+            // a gene's class over all cells is the maximum of the ranks' classes; the all-reduce only sums, so every rank puts its
+            // classes into its own row of a zeroed table (as sseq_max_count_global does), and all round to the same quanta
+            const uint64_t world = st.shard.world;
+            unsigned long long *d_rows = st.scratch.get<unsigned long long>("sseq_cls_world", world * genes);
+            std::vector<unsigned long long> rows(world * genes, 0ull);
+            for (uint64_t g = 0; g < genes; g++) rows[st.shard.rank * genes + g] = cls[g];
+            h2d(d_rows, rows.data(), rows.size(), st.stream);
+            SCANRS_SYNC(st.stream); // `rows` is pageable
+            exchange_u64(st, d_rows, world * genes);
+            SCANRS_D2H(rows.data(), d_rows, rows.size() * 8, st.stream);
+            SCANRS_SYNC(st.stream);
+            for (uint64_t g = 0; g < genes; g++) {
+                unsigned long long k = 0;
+                for (uint64_t r = 0; r < world; r++) k = std::max(k, rows[r * genes + g]);
+                cls[g] = (uint32_t)k;
+            }
+            h2d(d_cls, cls.data(), genes, st.stream);
+            SCANRS_SYNC(st.stream); // `cls` is pageable
+        }
+    }
+    launch_sseq_group_pass(st, cp, gene_major, genes, d_lab, 1, d_sums, d_sf, scale1, scale2, d_mom, d_bad, d_cls, log2m);
     if (st.shard.active() && genes) {
-        // the scales come from bounds of the sums over ALL cells (m, the global maximum count, the global 1 / sf): every rank rounds its
-        // terms to the same quantum and the joined limbs are the 128-bit sums of the unsharded pass
+        // the scales come from bounds of the sums over ALL cells (m, the global maximum count, the global 1 / sf; or m and the genes'
+        // classes over all ranks): every rank rounds its terms to the same quanta and the joined limbs are the 128-bit sums of the
+        // unsharded pass
         unsigned long long *d_limbs = st.scratch.get<unsigned long long>("sseq_limbs", genes * SSEQ_LIMB_STRIDE);
         launch_sseq_mom_split(st, d_mom, d_bad, genes, d_limbs);
         exchange_u64(st, d_limbs, genes * SSEQ_LIMB_STRIDE);
@@ -322,8 +362,9 @@ void sseq_params(Storage &st, const SparseCopy &cp, bool gene_major, uint64_t ge
     std::vector<double> mean(genes), var(genes);
     for (uint64_t g = 0; g < genes; g++) {
         // V[X] = E[X^2] - E[X]^2 (sqz/src/mat.rs:333-380)
-        mean[g] = from_fixed(&mom[g * 4], scale1) / md;
-        var[g] = from_fixed(&mom[g * 4 + 2], scale2) / md - mean[g] * mean[g];
+        const double s1 = per_gene ? fixed_class_scale1(cls[g], log2m) : scale1, s2 = per_gene ? fixed_class_scale2(cls[g], log2m) : scale2;
+        mean[g] = from_fixed(&mom[g * 4], s1) / md;
+        var[g] = from_fixed(&mom[g * 4 + 2], s2) / md - mean[g] * mean[g];
         if (bad[g]) {
             mean[g] = INFINITY;
             var[g] = NAN;

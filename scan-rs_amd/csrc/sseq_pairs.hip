@@ -106,7 +106,10 @@ __global__ __launch_bounds__(64) void pairs_header_kernel(const unsigned long lo
     h.n_b = nb;
     h.a = ga;
     h.b = gb;
-    h.literal = m_s == 0.0 ? 1u : 0u;
+    // the literal route: no finite size factor, or a cell total of the union so large that a count of 1 in that cell would not keep its
+    // bits under the call's quantum (fixed128.hpp): the reference's own calls give every gene a quantum of its own there
+    const unsigned long long top_a = na ? a[na - 1] : 0ull, top_b = nb ? b[nb - 1] : 0ull;
+    h.literal = (m_s == 0.0 || !fixed_totals_quantum_keeps(top_a > top_b ? top_a : top_b, scale)) ? 1u : 0u;
     h.pad = 0u;
     hdr[j] = h;
 }

@@ -199,7 +199,7 @@ void sseq_de_pairs(Storage &st, const SparseCopy &cp, bool gene_major, uint64_t 
                 if (lab3[c] == 1) L.fb += sf[c];
                 if (sf[c] != 0.0) L.sum_sf += 1.0 / sf[c];
             }
-            passes += 4; // totals, max count, moments, group sums
+            passes += 3 + st.sseq_moment_walks; // totals, max count, moments (the class walk first where every gene gets its quantum), group sums
             lit_tests += st.de_shard_tests;
         }
     }

@@ -249,8 +249,8 @@ def sseq_de_pairs(mat, labels, pairs, zeta_quintile: float = ZETA_QUINTILE_DEFAU
     nonzeros; each pair's parameters are combined on the device from its two groups' integer sums. Returns
     `(List[DiffExpResult], List[SSeqParams])`, one of each per pair; `size_factors` is left empty, as in
     `sseq_params_from_moments`, and the pair's scalars are attached to its params: `size_factor_a`, `size_factor_b`,
-    `median_total`, `sum_size_factors`, `num_cells_a`, `num_cells_b`, `literal` (the union's median total was 0 and the pair ran
-    the two reference calls themselves). labels: per cell, the group 0 .. n_groups - 1 or -1 (in no group).
+    `median_total`, `sum_size_factors`, `num_cells_a`, `num_cells_b`, `literal` (the union's median total was 0, or it holds a cell total too
+    large for the call's shared fixed-point quantum, and the pair ran the two reference calls themselves). labels: per cell, the group 0 .. n_groups - 1 or -1 (in no group).
     mat: an AdaptiveMat, or a MultiMat whose cells are the sharded dimension (`transposed=True` for one created cells x genes): labels
     then span the whole matrix and every output equals the unsharded call's bit for bit. A sharded AdaptiveMat is
     refused; `sseq_de_pairs_sharded` is the collective form for one."""
