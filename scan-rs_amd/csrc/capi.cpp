@@ -7,6 +7,7 @@
 
 #include "common.hpp"
 #include "col_moments_plan.hpp"
+#include "shard_exchange.hpp"
 
 namespace scanrs {
 
@@ -27,6 +28,32 @@ static void allreduce_any(Storage &st, void *d, uint64_t count, int dtype) {
 }
 void allreduce_f64(Storage &st, double *d, uint64_t count) { allreduce_any(st, d, count, 0); }
 void allreduce_u64(Storage &st, unsigned long long *d, uint64_t count) { allreduce_any(st, d, count, 1); }
+std::vector<unsigned long long> ShardExchange::gather_from(const unsigned long long *mine, uint64_t per_rank, bool on_host) {
+    const hipStream_t s = st.stream;
+    std::vector<unsigned long long> all((active() ? st.shard.world : 1) * per_rank);
+    if (!active()) {
+        if (on_host) {
+            std::copy(mine, mine + per_rank, all.begin());
+        } else {
+            SCANRS_D2H(all.data(), mine, per_rank * 8, s);
+            SCANRS_SYNC(s);
+        }
+        return all;
+    }
+    unsigned long long *d_all = st.scratch.get<unsigned long long>("shard_gather", all.size());
+    unsigned long long *d_slot = d_all + st.shard.rank * per_rank;
+    SCANRS_HIP(hipMemsetAsync(d_all, 0, all.size() * 8, s));
+    if (on_host) {
+        h2d(d_slot, mine, per_rank, s);
+        SCANRS_SYNC(s); // `mine` may be pageable: it has been read before a step that fails can unwind the frame that holds it
+    } else {
+        SCANRS_HIP(hipMemcpyAsync(d_slot, mine, per_rank * 8, hipMemcpyDeviceToDevice, s));
+    }
+    sum(d_all, all.size());
+    SCANRS_D2H(all.data(), d_all, all.size() * 8, s);
+    SCANRS_SYNC(s);
+    return all;
+}
 // primary's outer dimension is the sharded one: base rows when CSR, base cols when CSC
 static bool base_rows_sharded(const Storage &st) { return st.shard.active() && st.storage == SCANRS_CSR; }
 static bool base_cols_sharded(const Storage &st) { return st.shard.active() && st.storage == SCANRS_CSC; }
@@ -1733,7 +1760,6 @@ static void partition_entry(scanrs_mat *m, const double *row_threshold, const do
         st.partition_rounds = partition_on_thresholds(st, st.primary, outer_is_view_rows ? row_threshold : col_threshold,
                                                       outer_is_view_rows ? col_threshold : row_threshold, outer_is_view_rows, ex_outer, ex_inner,
                                                       filtered ? &f : nullptr, residual ? &r : nullptr, sharded ? &ps : nullptr);
-        st.partition_allreduces = ps.allreduces;
         device_free_flush();
     }
     const std::vector<uint8_t> &ex_outer_all = sharded ? ps.excl_outer_all : ex_outer;

@@ -3,6 +3,7 @@
 // nonzeros, the medians and the tests run on the device (cluster.hip, sseq.hip).
 #include "common.hpp"
 #include "fixed128.hpp"
+#include "shard_exchange.hpp"
 
 #include <algorithm>
 #include <cmath>
@@ -168,7 +169,7 @@ static uint32_t medoid_cols_per_tile(uint64_t n, uint32_t d) {
 struct MedoidScratch {
     DevBuf<uint32_t> perm;
     DevBuf<uint64_t> off, len;
-    DevBuf<unsigned long long> keys, nan_cell, state, hist, slots;
+    DevBuf<unsigned long long> keys, nan_cell, state, hist;
     DevBuf<double> out;
 };
 
@@ -203,7 +204,7 @@ static void medoids_on(hipStream_t s, MedoidScratch &ms, const double *d_scores,
 // The medoids of a sharded handle: d_scores holds the rank's own cells [cr.begin, cr.begin + cr.n_local), labels span the
 // whole matrix. Every rank walks the same column tiles, pair tiles and rounds (they depend on the global sizes only), so the exchange
 // steps pair up; the centers come out complete on every rank.
-static void medoids_dist(Storage &st, MedoidScratch &ms, const double *d_scores, const SseqCellRange &cr, uint32_t ld, uint32_t d,
+static void medoids_dist(Storage &st, MedoidScratch &ms, const double *d_scores, const CellRange &cr, uint32_t ld, uint32_t d,
                          const int16_t *labels, uint32_t k, double *centers) {
     if (cr.global == 0 || d == 0) return;
     const hipStream_t s = st.stream;
@@ -221,14 +222,13 @@ static void medoids_dist(Storage &st, MedoidScratch &ms, const double *d_scores,
     }
     const uint32_t cpt = medoid_cols_per_tile(cr.global, d); // from the global count: the same tiles on every rank
     const uint32_t hist_pairs = (uint32_t)std::min<uint64_t>(MEDOID_HIST_PAIRS, (uint64_t)k * cpt);
-    const uint32_t world = st.shard.world;
+    ShardExchange ex{st, st.de_shard_allreduces}; // (the counter of the DE calls, which the merge loop goes on to make)
     if (ms.perm.n < perm.size()) ms.perm.alloc(perm.size());
     if (ms.off.n < k + 1) ms.off.alloc(k + 1);
     if (ms.len.n < k) ms.len.alloc(k);
     if (ms.keys.n < std::max<uint64_t>(1, n * cpt)) ms.keys.alloc(std::max<uint64_t>(1, n * cpt));
     if (ms.state.n < (size_t)k * cpt * 4) ms.state.alloc((size_t)k * cpt * 4);
     if (ms.hist.n < (size_t)hist_pairs * 512) ms.hist.alloc((size_t)hist_pairs * 512);
-    if (ms.slots.n < world) ms.slots.alloc(world);
     if (ms.nan_cell.n < 1) ms.nan_cell.alloc(1);
     if (ms.out.n < (size_t)k * d) ms.out.alloc((size_t)k * d);
     h2d(ms.perm.p, perm.data(), n, s);
@@ -243,21 +243,17 @@ static void medoids_dist(Storage &st, MedoidScratch &ms, const double *d_scores,
             for (uint32_t p0 = 0; p0 < n_pairs; p0 += hist_pairs) {
                 const uint32_t np = std::min(hist_pairs, n_pairs - p0);
                 launch_medoid_dist_hist(s, ms.keys.p, n, ms.off.p, k, p0, np, shift, ms.state.p, ms.hist.p);
-                sseq_exchange_u64(st, ms.hist.p, (uint64_t)np * 512);
+                ex.sum(ms.hist.p, (uint64_t)np * 512);
                 launch_medoid_dist_pick(s, ms.hist.p, p0, np, shift, ms.state.p);
             }
         launch_medoid_dist_finish(s, ms.state.p, ms.len.p, k, j0, jt, ms.out.p, d);
     }
-    // the first cell holding a NaN: the transport only sums, so every rank puts its own first one (+ 1; 0 = none) into its slot
+    // the first cell holding a NaN: every rank's own first one (+ 1; 0 = none)
     unsigned long long nan_local = 0;
     SCANRS_D2H(&nan_local, ms.nan_cell.p, 8, s);
     SCANRS_SYNC(s);
-    std::vector<unsigned long long> slots(world, 0ull);
-    slots[st.shard.rank] = nan_local == ~0ull ? 0ull : cr.begin + nan_local + 1;
-    h2d(ms.slots.p, slots.data(), world, s);
-    SCANRS_SYNC(s); // `slots` is pageable and is overwritten below
-    sseq_exchange_u64(st, ms.slots.p, world);
-    SCANRS_D2H(slots.data(), ms.slots.p, world * 8, s);
+    const unsigned long long nan_mine = nan_local == ~0ull ? 0ull : cr.begin + nan_local + 1;
+    const std::vector<unsigned long long> slots = ex.gather_host(&nan_mine, 1);
     SCANRS_D2H(centers, ms.out.p, (size_t)k * d * 8, s);
     SCANRS_SYNC(s);
     unsigned long long nan_cell = ~0ull;
@@ -337,7 +333,7 @@ void merge_clusters_run(Storage &st, const SparseCopy &cp, bool gene_major, uint
     if (trace) trace->n_candidates = trace->n_rounds = trace->n_merges = trace->n_passes = 0;
     // a sharded handle (collective only): the copy and d_scores hold the cells [cr.begin, cr.begin + cr.n_local); `cells` is from
     // here on the whole matrix: labels span it and the loop below runs replicated on every rank, on identical data
-    const SseqCellRange cr = collective ? sseq_cell_range(st, cells) : SseqCellRange{0, cells, cells};
+    const CellRange cr = collective ? cell_range(st, cells) : CellRange{0, cells, cells};
     const uint64_t cells_local = cr.n_local;
     const bool dist = collective && st.shard.active();
     cells = cr.global;
@@ -359,7 +355,7 @@ void merge_clusters_run(Storage &st, const SparseCopy &cp, bool gene_major, uint
         unsigned long long *d_tot = st.scratch.get<unsigned long long>("merge_totals", cells + 1);
         if (dist) SCANRS_HIP(hipMemsetAsync(d_tot, 0, cells * 8, s)); // the other ranks' slices
         launch_sseq_cell_totals(st, cp, gene_major, cells_local, d_tot + cr.begin);
-        if (dist) sseq_exchange_u64(st, d_tot, cells); // one contributor per element: the sum is a copy
+        if (dist) ShardExchange{st, st.de_shard_allreduces}.sum(d_tot, cells); // one contributor per element: the sum is a copy
         passes++;
         int16_t *d_lab = st.scratch.get<int16_t>("merge_labels", std::max<uint64_t>(1, cells_local));
         h2d(d_lab, labels.data() + cr.begin, cells_local, s);
@@ -607,7 +603,7 @@ int scanrs_merge_clusters_sharded(scanrs_mat *m, const double *pca, int pca_is_d
         bool gm = false;
         SparseCopy &cp = sseq_resident_copy(m, &gm); // refuses a handle sharded over the genes
         Storage &st = *m->st;
-        const SseqCellRange cr = sseq_cell_range(st, m->cols());
+        const CellRange cr = cell_range(st, m->cols());
         if (cr.global && (!pca || !labels || !labels_out)) fail(SCANRS_ERR_ARGUMENT, "null argument");
         if (trace && trace->capacity && (!trace->leaf0 || !trace->leaf1 || !trace->n_de || !trace->min_p_adj))
             fail(SCANRS_ERR_ARGUMENT, "trace arrays are null");
@@ -632,7 +628,7 @@ int scanrs_cluster_medoids_sharded(scanrs_mat *m, const double *pca, int pca_is_
         bool gm = false;
         (void)sseq_resident_copy(m, &gm); // refuses a handle sharded over the genes
         Storage &st = *m->st;
-        const SseqCellRange cr = sseq_cell_range(st, m->cols());
+        const CellRange cr = cell_range(st, m->cols());
         if (cr.global && (!pca || !labels || (!centers && d))) fail(SCANRS_ERR_ARGUMENT, "null argument");
         if (ld < d) fail(SCANRS_ERR_ARGUMENT, "ld must be at least d");
         if (cr.global > 0xFFFFFFFFull) fail(SCANRS_ERR_ARGUMENT, "at most 2^32 - 1 cells");

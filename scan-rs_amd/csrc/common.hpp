@@ -738,6 +738,14 @@ void allreduce_u64(Storage &st, unsigned long long *d, uint64_t count);
 // is the view-row dimension the sharded one?
 bool rows_sharded(const scanrs_mat *m);
 bool cols_sharded(const scanrs_mat *m);
+// the cells of a handle as its collective calls see them: [begin, begin + n_local) of `global` (an unsharded handle: all of them)
+struct CellRange {
+    uint64_t begin, n_local, global;
+};
+inline CellRange cell_range(const Storage &st, uint64_t cells_local) {
+    if (!st.shard.active()) return CellRange{0, cells_local, cells_local};
+    return CellRange{st.shard.outer_begin, cells_local, st.shard.outer_global};
+}
 
 // ---- sseq.hip / sseq_host.cpp: sSeq differential expression (diff-exp/src/diff_exp.rs, dist.rs) --------------------------------
 constexpr uint32_t SSEQ_CHUNK_THREADS = 256, SSEQ_TERMS_PER_THREAD = 8, SSEQ_CHUNK = SSEQ_CHUNK_THREADS * SSEQ_TERMS_PER_THREAD;
@@ -841,13 +849,6 @@ constexpr uint64_t SSEQ_ACC_TILE = 1ull << 20;
 void launch_pairs_acc_split(hipStream_t s, const unsigned long long *d_acc_tile, uint64_t ne, unsigned long long *d_planes);
 void launch_pairs_acc_join(hipStream_t s, const unsigned long long *d_planes, uint64_t ne, unsigned long long *d_acc_tile);
 uint64_t sseq_reduce_group_acc(Storage &st, unsigned long long *d_acc, uint64_t n_entries);
-// the cells of a handle as its DE calls see them: [begin, begin + n_local) of `global` (an unsharded handle: all of them)
-struct SseqCellRange {
-    uint64_t begin, n_local, global;
-};
-SseqCellRange sseq_cell_range(const Storage &st, uint64_t cells_local);
-// one u64 all-reduce of a sharded handle, counted in de_shard_allreduces (nothing on an unsharded handle)
-void sseq_exchange_u64(Storage &st, unsigned long long *d, uint64_t count);
 // the batched pairwise DE (sseq_pairs_host.cpp). collective: a sharded handle is served (cells = the rank's own), labels span the whole matrix
 void sseq_de_pairs(Storage &st, const SparseCopy &cp, bool gene_major, uint64_t genes, uint64_t cells, const int16_t *labels, uint32_t n_groups,
                    const uint32_t *pair_a, const uint32_t *pair_b, uint32_t n_pairs, double zeta_quintile, uint64_t big_count, int backend,
@@ -913,10 +914,10 @@ void select_inner(Storage &st, const SparseCopy &cp, const uint64_t *idx, uint64
 // thr_outer / thr_inner: nullable thresholds of the two axes of cp; cols_inner: the view's columns are cp's inner positions (their
 // step comes first in a round). excl_outer / excl_inner: the final masks (host). filtered / residual may be null (not built).
 // Returns the number of rounds. sh (a sharded handle): cp is the rank's shard; excl_outer, filtered and residual stay
-// local, excl_inner is replicated, and sh receives what the call learned about the whole outer dimension.
+// local, excl_inner is replicated, sh receives what the call learned about the whole outer dimension, and the exchange steps are added
+// to st.partition_allreduces.
 struct PartitionShard {
     std::vector<uint8_t> excl_outer_all; // the outer mask of the whole matrix (outer_global entries), the same on every rank
-    uint64_t allreduces = 0;             // exchange steps of the call
 };
 uint64_t partition_on_thresholds(Storage &st, const SparseCopy &cp, const double *thr_outer, const double *thr_inner, bool cols_inner,
                                  std::vector<uint8_t> &excl_outer, std::vector<uint8_t> &excl_inner, SparseCopy *filtered, SparseCopy *residual,

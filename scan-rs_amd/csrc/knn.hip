@@ -27,6 +27,7 @@
 
 #include "common.hpp"
 #include "knn_merge.hpp"
+#include "shard_exchange.hpp"
 
 namespace scanrs {
 
@@ -838,11 +839,10 @@ __global__ __launch_bounds__(256) void ks_scan_kernel(const double *__restrict__
         if (!(fabs(x) <= DBL_MAX)) atomicMin(first, (unsigned long long)r);
     }
 }
-// what the ranks agree on before the first block: four slots per rank of a zeroed array, n, d, k and (first bad global row + 1)
-__global__ void ks_header_kernel(unsigned long long *__restrict__ slots, uint32_t rank, uint64_t n, uint32_t d, uint32_t k, uint64_t begin,
+// what the ranks agree on before the first block: this rank's four words, n, d, k and (first bad global row + 1)
+__global__ void ks_header_kernel(unsigned long long *__restrict__ mine, uint64_t n, uint32_t d, uint32_t k, uint64_t begin,
                                  const unsigned long long *__restrict__ first) {
     if (blockIdx.x != 0 || threadIdx.x != 0) return;
-    unsigned long long *mine = slots + 4ull * rank;
     mine[0] = n;
     mine[1] = d;
     mine[2] = k;
@@ -884,24 +884,17 @@ void knn_sharded(Storage &st, const double *d_pts, uint32_t ld, uint64_t begin, 
                  uint32_t *out, double *sq_dist) {
     const hipStream_t s = st.stream;
     const uint32_t world = st.shard.world, rank = st.shard.rank;
-    auto exchange = [&](unsigned long long *p, uint64_t count) {
-        allreduce_u64(st, p, count);
-        st.knn_allreduces++;
-    };
+    ShardExchange ex{st, st.knn_allreduces};
     // 1. The ranks agree: the same n, d, k everywhere (a rank that differs would bring another count to a later exchange), and no
     //    coordinate that is not finite (with a NaN the order is not total and a blockwise merge could differ from one pass).
     const bool scannable = n_local && d && ld >= d && d_pts;
-    DevBuf<unsigned long long> first(1), slots(4ull * world);
+    DevBuf<unsigned long long> first(1), hdr(4);
     SCANRS_HIP(hipMemsetAsync(first.p, 0xFF, 8, s));
-    SCANRS_HIP(hipMemsetAsync(slots.p, 0, 32ull * world, s));
     if (scannable)
         hipLaunchKernelGGL(ks_scan_kernel, dim3((unsigned)std::min<uint64_t>((n_local * d + 255) / 256, 2048)), dim3(256), 0, s, d_pts, ld, n_local, d,
                            first.p);
-    hipLaunchKernelGGL(ks_header_kernel, dim3(1), dim3(64), 0, s, slots.p, rank, n, d, k, begin, first.p);
-    exchange(slots.p, 4ull * world);
-    std::vector<unsigned long long> h(4ull * world);
-    SCANRS_D2H(h.data(), slots.p, 32ull * world, s);
-    SCANRS_SYNC(s);
+    hipLaunchKernelGGL(ks_header_kernel, dim3(1), dim3(64), 0, s, hdr.p, n, d, k, begin, first.p);
+    const std::vector<unsigned long long> h = ex.gather(hdr.p, 4);
     unsigned long long bad = 0;
     for (uint32_t r = 0; r < world; r++) {
         if (h[4 * r] != n || h[4 * r + 1] != d || h[4 * r + 2] != k)
@@ -942,7 +935,7 @@ void knn_sharded(Storage &st, const double *d_pts, uint32_t ld, uint64_t begin, 
         if (lo < hi)
             hipLaunchKernelGGL(ks_pack_kernel, dim3((unsigned)(((hi - lo) * d + 255) / 256)), dim3(256), 0, s, d_pts + (lo - begin) * ld, ld, d, hi - lo,
                                xbuf.p + (lo - b0) * d);
-        exchange(xbuf.p, rows * d);
+        ex.sum(xbuf.p, rows * d);
         st.knn_blocks++;
         if (!n_local) continue;
         const double *blk = reinterpret_cast<const double *>(xbuf.p);

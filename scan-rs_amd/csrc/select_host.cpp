@@ -2,6 +2,7 @@
 // the per-round flag, and the small index tables. Kernels: select.hip. All of it works on the copy it is given (the handle's own
 // storage) and queues on the handle's main stream.
 #include "common.hpp"
+#include "shard_exchange.hpp"
 
 #include <algorithm>
 
@@ -108,12 +109,8 @@ uint64_t partition_on_thresholds(Storage &st, const SparseCopy &cp, const double
     // replicated: every rank marks them from the same reduced sums. The outer vectors, their sums and their mask stay local.
     const uint64_t no_all = sh ? st.shard.outer_global : no;
     if (no_all >= 0x7FFFFFFFull || ni >= 0x7FFFFFFFull) fail(SCANRS_ERR_SHAPE, "partition_on_thresholds needs dimensions below 2^31 - 1");
-    if (sh) sh->allreduces = 0;
-    auto exchange = [&](unsigned long long *d, uint64_t count) {
-        if (!count) return;
-        allreduce_u64(st, d, count);
-        sh->allreduces++;
-    };
+    // (the counts of the three exchanges below are the same on every rank: the inner extent, one flag, the global outer extent)
+    ShardExchange ex{st, st.partition_allreduces};
     DevBuf<uint8_t> d_eo(std::max<uint64_t>(1, no)), d_ei(std::max<uint64_t>(1, ni)), d_no(std::max<uint64_t>(1, no)), d_ni(std::max<uint64_t>(1, ni));
     DevBuf<unsigned long long> d_so(std::max<uint64_t>(1, no)), d_si(std::max<uint64_t>(1, ni));
     DevBuf<unsigned long long> d_sr; // sharded: the reduced copy of the inner sums (d_si keeps this rank's own, for the subtraction)
@@ -143,8 +140,10 @@ uint64_t partition_on_thresholds(Storage &st, const SparseCopy &cp, const double
         SCANRS_HIP(hipMemsetAsync(d_no.p, 0, d_no.n, s));
         const unsigned long long *sums = d_si.p;
         if (sh) {
-            if (ni) SCANRS_HIP(hipMemcpyAsync(d_sr.p, d_si.p, ni * 8, hipMemcpyDeviceToDevice, s));
-            exchange(d_sr.p, ni);
+            if (ni) {
+                SCANRS_HIP(hipMemcpyAsync(d_sr.p, d_si.p, ni * 8, hipMemcpyDeviceToDevice, s));
+                ex.sum(d_sr.p, ni);
+            }
             sums = d_sr.p;
         }
         launch_sel_mark(s, sums, ni, *thr_inner, d_ei.p, d_ni.p, d_flag.p);
@@ -162,7 +161,7 @@ uint64_t partition_on_thresholds(Storage &st, const SparseCopy &cp, const double
         rounds++;
         // the outer marks are local news: the ranks agree on the flag before they read it, and so stop in the same round (the inner
         // marks come from replicated sums and set the same flag everywhere)
-        if (sh && thr_outer) exchange(reinterpret_cast<unsigned long long *>(d_flag.p), 1);
+        if (sh && thr_outer) ex.sum(reinterpret_cast<unsigned long long *>(d_flag.p), 1);
         if (!SCANRS_D2H_VALUE(d_flag.p, s)) break; // the one value a round sends back
     }
     excl_outer.assign(no, 0);
@@ -177,7 +176,7 @@ uint64_t partition_on_thresholds(Storage &st, const SparseCopy &cp, const double
         DevBuf<unsigned long long> d_all(std::max<uint64_t>(1, words));
         SCANRS_HIP(hipMemsetAsync(d_all.p, 0, words * 8, s));
         if (no) SCANRS_HIP(hipMemcpyAsync(reinterpret_cast<uint8_t *>(d_all.p) + st.shard.outer_begin, d_eo.p, no, hipMemcpyDeviceToDevice, s));
-        exchange(d_all.p, words);
+        if (words) ex.sum(d_all.p, words);
         sh->excl_outer_all.assign(no_all, 0);
         if (no_all) SCANRS_D2H(sh->excl_outer_all.data(), d_all.p, no_all, s);
         SCANRS_SYNC(s);

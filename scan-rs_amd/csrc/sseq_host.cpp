@@ -3,6 +3,7 @@
 // The passes over the nonzeros and the tests themselves run on the device (sseq.hip).
 #include "common.hpp"
 #include "fixed128.hpp"
+#include "shard_exchange.hpp"
 #include "special.hpp"
 
 #include <algorithm>
@@ -17,40 +18,15 @@ namespace scanrs {
 
 // ---- sharded handles ---------------------------------------------------------------------------------------------
 // The cells are the sharded dimension: the copy holds the cells [begin, begin + n_local) of `global`, and every per-cell argument
-// spans the whole matrix. All sums that cross the shards are integers and go through allreduce_u64: they come out bit for bit as
-// the sums of the unsharded handle, whatever the number of shards and whichever transport carries them.
-struct CellRange {
-    uint64_t begin, n_local, global;
-};
-static CellRange cell_range(const Storage &st, uint64_t cells_local) {
-    if (!st.shard.active()) return CellRange{0, cells_local, cells_local};
-    return CellRange{st.shard.outer_begin, cells_local, st.shard.outer_global};
-}
-// one exchange step (counter "de_shard_allreduces")
-static void exchange_u64(Storage &st, unsigned long long *d, uint64_t count) {
-    if (!st.shard.active() || count == 0) return;
-    allreduce_u64(st, d, count);
-    st.de_shard_allreduces++;
-}
-SseqCellRange sseq_cell_range(const Storage &st, uint64_t cells_local) {
-    const CellRange cr = cell_range(st, cells_local);
-    return SseqCellRange{cr.begin, cr.n_local, cr.global};
-}
-void sseq_exchange_u64(Storage &st, unsigned long long *d, uint64_t count) { exchange_u64(st, d, count); }
-// the largest count of the whole matrix: the all-reduce only sums, so every rank puts its maximum into its own slot of a zeroed array
+// spans the whole matrix (cell_range). All sums that cross the shards are integers and go through the exchange steps of
+// shard_exchange.hpp, counted in "de_shard_allreduces": they come out bit for bit as the sums of the unsharded handle, whatever the
+// number of shards and whichever transport carries them.
+static ShardExchange de_exchange(Storage &st) { return ShardExchange{st, st.de_shard_allreduces}; }
+// the largest count of the whole matrix
 static uint32_t sseq_max_count_global(Storage &st, const SparseCopy &cp) {
-    const uint32_t mine = sseq_max_count(st, cp);
-    if (!st.shard.active()) return mine;
-    const uint32_t world = st.shard.world;
-    unsigned long long *d = st.scratch.get<unsigned long long>("sseq_max_world", world);
-    std::vector<unsigned long long> slots(world, 0ull);
-    slots[st.shard.rank] = mine;
-    h2d(d, slots.data(), world, st.stream);
-    SCANRS_SYNC(st.stream); // `slots` is pageable and goes out of use below
-    exchange_u64(st, d, world);
-    SCANRS_D2H(slots.data(), d, world * 8, st.stream);
-    SCANRS_SYNC(st.stream);
-    return (uint32_t)*std::max_element(slots.begin(), slots.end());
+    const unsigned long long mine = sseq_max_count(st, cp);
+    const std::vector<unsigned long long> all = de_exchange(st).gather_host(&mine, 1);
+    return (uint32_t)*std::max_element(all.begin(), all.end());
 }
 
 // ---- stat.rs ----------------------------------------------------------------------------------------------------------------
@@ -242,8 +218,10 @@ void sseq_group_sums(Storage &st, const SparseCopy &cp, bool gene_major, uint64_
     unsigned long long *d_sums = st.scratch.get<unsigned long long>("sseq_sums", std::max<uint64_t>(1, genes * n_groups));
     h2d(d_lab, labels + cr.begin, cr.n_local, st.stream);
     launch_sseq_group_pass(st, cp, gene_major, genes, d_lab, n_groups, d_sums, nullptr, 1.0, 1.0, nullptr, nullptr);
-    exchange_u64(st, d_sums, genes * n_groups);
-    if (genes) SCANRS_D2H(sums, d_sums, genes * n_groups * 8, st.stream);
+    if (genes) { // (the genes are not sharded: none on one rank is none on every rank, and then no step)
+        de_exchange(st).sum(d_sums, genes * n_groups);
+        SCANRS_D2H(sums, d_sums, genes * n_groups * 8, st.stream);
+    }
     SCANRS_SYNC(st.stream);
     if (cells_per_group) {
         std::fill(cells_per_group, cells_per_group + n_groups, 0);
@@ -273,7 +251,7 @@ void sseq_params(Storage &st, const SparseCopy &cp, bool gene_major, uint64_t ge
         unsigned long long *d_tot = st.scratch.get<unsigned long long>("sseq_totals", std::max<uint64_t>(1, cells));
         if (st.shard.active()) SCANRS_HIP(hipMemsetAsync(d_tot, 0, std::max<uint64_t>(1, cells) * 8, st.stream)); // the other ranks' slices
         launch_sseq_cell_totals(st, cp, gene_major, cr.n_local, d_tot + cr.begin);
-        exchange_u64(st, d_tot, cells);
+        de_exchange(st).sum(d_tot, cells); // one contributor per element: the sum is a copy (m != 0 above: there are cells)
         std::vector<unsigned long long> tot(cells);
         if (cells) SCANRS_D2H(tot.data(), d_tot, cells * 8, st.stream);
         SCANRS_SYNC(st.stream);
@@ -321,20 +299,13 @@ void sseq_params(Storage &st, const SparseCopy &cp, bool gene_major, uint64_t ge
         if (genes) SCANRS_D2H(cls.data(), d_cls, genes * 4, st.stream);
         SCANRS_SYNC(st.stream);
         if (st.shard.active() && genes) {
-            // a gene's class over all cells is the maximum of the ranks' classes; the all-reduce only sums, so every rank puts its
-            // classes into its own row of a zeroed table (as sseq_max_count_global does), and all round to the same quanta
-            const uint64_t world = st.shard.world;
-            unsigned long long *d_rows = st.scratch.get<unsigned long long>("sseq_cls_world", world * genes);
-            std::vector<unsigned long long> rows(world * genes, 0ull);
-            for (uint64_t g = 0; g < genes; g++) rows[st.shard.rank * genes + g] = cls[g];
-            h2d(d_rows, rows.data(), rows.size(), st.stream);
-            SCANRS_SYNC(st.stream); // `rows` is pageable
-            exchange_u64(st, d_rows, world * genes);
-            SCANRS_D2H(rows.data(), d_rows, rows.size() * 8, st.stream);
-            SCANRS_SYNC(st.stream);
+            // a gene's class over all cells is the maximum of the ranks' classes (one row of the gathered table per rank), and all
+            // ranks round to the same quanta
+            const std::vector<unsigned long long> mine(cls.begin(), cls.end());
+            const std::vector<unsigned long long> rows = de_exchange(st).gather_host(mine.data(), genes);
             for (uint64_t g = 0; g < genes; g++) {
                 unsigned long long k = 0;
-                for (uint64_t r = 0; r < world; r++) k = std::max(k, rows[r * genes + g]);
+                for (uint64_t r = 0; r < st.shard.world; r++) k = std::max(k, rows[r * genes + g]);
                 cls[g] = (uint32_t)k;
             }
             h2d(d_cls, cls.data(), genes, st.stream);
@@ -348,7 +319,7 @@ void sseq_params(Storage &st, const SparseCopy &cp, bool gene_major, uint64_t ge
         // unsharded pass
         unsigned long long *d_limbs = st.scratch.get<unsigned long long>("sseq_limbs", genes * SSEQ_LIMB_STRIDE);
         launch_sseq_mom_split(st, d_mom, d_bad, genes, d_limbs);
-        exchange_u64(st, d_limbs, genes * SSEQ_LIMB_STRIDE);
+        de_exchange(st).sum(d_limbs, genes * SSEQ_LIMB_STRIDE);
         launch_sseq_mom_join(st, d_limbs, genes, d_mom, d_bad);
     }
     std::vector<unsigned long long> mom(genes * 4);
@@ -481,8 +452,7 @@ void sseq_de_sums_strided(hipStream_t s, uint64_t genes, uint32_t n_tests, const
     }
     if (sharded && total) {
         static_assert(sizeof(double) == sizeof(unsigned long long), "p-values travel as their bit patterns");
-        allreduce_u64(*shard, reinterpret_cast<unsigned long long *>(d_p.p), total);
-        shard->de_shard_allreduces++;
+        de_exchange(*shard).sum(reinterpret_cast<unsigned long long *>(d_p.p), total);
         std::vector<double> pd(total);
         SCANRS_D2H(pd.data(), d_p.p, total * 8, s);
         SCANRS_SYNC(s);

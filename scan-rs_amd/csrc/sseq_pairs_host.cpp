@@ -7,6 +7,7 @@
 // the sums over S are the exact integer sums of the two groups' fixed-point accumulators.
 #include "common.hpp"
 #include "fixed128.hpp"
+#include "shard_exchange.hpp"
 
 #include <algorithm>
 #include <cmath>
@@ -54,7 +55,7 @@ uint64_t sseq_reduce_group_acc(Storage &st, unsigned long long *d_acc, uint64_t 
     for (uint64_t e0 = 0; e0 < n_entries; e0 += SSEQ_ACC_TILE, steps++) {
         const uint64_t ne = std::min<uint64_t>(SSEQ_ACC_TILE, n_entries - e0), ne_pad = (ne + 1) & ~1ull;
         launch_pairs_acc_split(st.stream, d_acc + e0 * 5, ne, d_planes);
-        sseq_exchange_u64(st, d_planes, SSEQ_ACC_PLANES * ne_pad);
+        ShardExchange{st, st.de_shard_allreduces}.sum(d_planes, SSEQ_ACC_PLANES * ne_pad);
         launch_pairs_acc_join(st.stream, d_planes, ne, d_acc + e0 * 5);
     }
     return steps;
@@ -85,7 +86,7 @@ void sseq_de_pairs(Storage &st, const SparseCopy &cp, bool gene_major, uint64_t 
                    double *mean_out, scanrs_sseq_pair_params *params, bool collective) {
     // a sharded handle (collective only): the copy holds the cells [cr.begin, cr.begin + cr.n_local) and `cells` is from here on
     // the whole matrix: labels span it, the host folds run replicated, the device gets this rank's slice of the labels
-    const SseqCellRange cr = collective ? sseq_cell_range(st, cells) : SseqCellRange{0, cells, cells};
+    const CellRange cr = collective ? cell_range(st, cells) : CellRange{0, cells, cells};
     const uint64_t cells_local = cr.n_local;
     cells = cr.global;
     if (backend != SCANRS_NB_EXACT_LOGSPACE && backend != SCANRS_NB_EXACT_RATIO)
@@ -123,7 +124,8 @@ void sseq_de_pairs(Storage &st, const SparseCopy &cp, bool gene_major, uint64_t 
     unsigned long long *d_tot = st.scratch.get<unsigned long long>("sseq_totals", cells + 1);
     if (cells_local != cells) SCANRS_HIP(hipMemsetAsync(d_tot, 0, cells * 8, s)); // the other ranks' slices
     launch_sseq_cell_totals(st, cp, gene_major, cells_local, d_tot + cr.begin);
-    if (collective) sseq_exchange_u64(st, d_tot, cells); // one contributor per element: the sum is a copy
+    // one contributor per element: the sum is a copy (every pair has a cell, so there are cells)
+    if (collective) ShardExchange{st, st.de_shard_allreduces}.sum(d_tot, cells);
     passes++;
     int16_t *d_lab = st.scratch.get<int16_t>("sseq_labels", std::max<uint64_t>(1, cells_local));
     h2d(d_lab, labels + cr.begin, cells_local, s);

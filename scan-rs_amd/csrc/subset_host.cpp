@@ -22,6 +22,7 @@
 //                                                  quantum, the 128-bit sums cross as 32-bit limbs (step 2), the host converts
 #include "common.hpp"
 #include "fixed128.hpp"
+#include "shard_exchange.hpp"
 
 #include <algorithm>
 #include <cmath>
@@ -110,10 +111,7 @@ void subset_sums(scanrs_mat *m, bool per_column, int mode, const List *lists, in
 
     CurrentHandle cur(&st);
     hipStream_t s = st.stream;
-    auto exchange = [&](unsigned long long *d, uint64_t count) {
-        allreduce_u64(st, d, count);
-        st.subset_allreduces++;
-    };
+    ShardExchange ex{st, st.subset_allreduces};
     // the copy whose outer dimension is the result axis: does it exist? (other_settled, not has_other: the route must not depend on
     // how far a helper thread has come)
     const bool want_base_rows = (!per_column) != m->transposed;
@@ -143,16 +141,8 @@ void subset_sums(scanrs_mat *m, bool per_column, int mode, const List *lists, in
     uint32_t *d_bad = nullptr;
     double scale[2] = {1.0, 1.0};
     auto agree_on_scales = [&](unsigned long long *d_max) {
-        // rank r's largest |term| travels in slot r of a zeroed world-long array (as the largest count of the sharded sSeq calls); the
-        // maximum of the bit patterns is the maximum of the values
-        const uint32_t world = st.shard.world;
-        unsigned long long *d_slots = st.scratch.get<unsigned long long>("subset_max_slots", world);
-        SCANRS_HIP(hipMemsetAsync(d_slots, 0, (size_t)world * 8, s));
-        SCANRS_HIP(hipMemcpyAsync(d_slots + st.shard.rank, d_max, 8, hipMemcpyDeviceToDevice, s));
-        exchange(d_slots, world);
-        std::vector<unsigned long long> h(world);
-        SCANRS_D2H(h.data(), d_slots, (size_t)world * 8, s);
-        SCANRS_SYNC(s);
+        // every rank's largest |term|: the maximum of the bit patterns is the maximum of the values
+        const std::vector<unsigned long long> h = ex.gather(d_max, 1);
         const unsigned long long bits = *std::max_element(h.begin(), h.end());
         double mx;
         memcpy(&mx, &bits, 8);
@@ -220,10 +210,10 @@ void subset_sums(scanrs_mat *m, bool per_column, int mode, const List *lists, in
     if (fixed) {
         unsigned long long *d_limbs = st.scratch.get<unsigned long long>("subset_limbs", n_final * 5 * n_sums);
         launch_subset_fx_split(st, d_fx, d_bad, n_final, n_sums, d_limbs);
-        exchange(d_limbs, n_final * 5 * n_sums);
+        ex.sum(d_limbs, n_final * 5 * n_sums);
         launch_subset_fx_join(st, d_limbs, n_final, n_sums, d_fx, d_bad);
     } else if (crossing && n_final) {
-        exchange(d_out, (uint64_t)(n_out - 1) * stride + n_result); // exact partial sums
+        ex.sum(d_out, (uint64_t)(n_out - 1) * stride + n_result); // exact partial sums
     } else if (result_global && n_final) {
         // one contributor per element: the sum of the bit patterns is a copy
         const uint64_t at = per_column ? below : st.shard.outer_begin;
@@ -232,7 +222,7 @@ void subset_sums(scanrs_mat *m, bool per_column, int mode, const List *lists, in
         if (n_result)
             for (int k = 0; k < n_out; k++)
                 SCANRS_HIP(hipMemcpyAsync(d_all + (uint64_t)k * n_final + at, d_out + (uint64_t)k * stride, n_result * 8, hipMemcpyDeviceToDevice, s));
-        exchange(d_all, (uint64_t)n_out * n_final);
+        ex.sum(d_all, (uint64_t)n_out * n_final);
         d_res = d_all;
         res_stride = n_final;
     }

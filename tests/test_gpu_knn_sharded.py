@@ -8,7 +8,6 @@ thread per rank, with a host hook that sums the ranks' buffers and records the d
 import contextlib
 import os
 import sys
-import threading
 
 import numpy as np
 import pytest
@@ -21,6 +20,7 @@ for p in (TESTS, os.path.join(os.path.dirname(TESTS), "oracle")):
         sys.path.insert(0, p)
 import knn_oracle  # noqa: E402
 import knn_sharded_ref as ref  # noqa: E402
+from shard_ring import Ring, run_ranks  # noqa: E402
 
 DEFAULT_BLOCK_ROWS = 262144
 U32MAX = ref.U32MAX
@@ -78,40 +78,6 @@ def cell_matrix(n_cells):
     return np.arange(n_cells + 1, dtype=np.uint64), np.zeros(n_cells, dtype=np.uint32), np.ones(n_cells, dtype=np.uint32)
 
 
-class Ring:
-    """The host hook of `world` ranks: every rank brings its device buffer, the buffers are summed on the host (u64 wraps, as the
-    device sum does) and every rank takes the sum back. A rank that waits in vain fails its call instead of hanging."""
-
-    def __init__(self, world):
-        import torch
-
-        self.torch, self.world = torch, world
-        self.barrier = threading.Barrier(world, timeout=60)
-        self.bufs = [None] * world
-        self.dtypes, self.calls = set(), 0
-
-    def hook(self, rank):
-        def allreduce(ptr, count, dtype):
-            import scanrs_amd
-
-            torch = self.torch
-            self.dtypes.add(dtype)
-            if rank == 0:
-                self.calls += 1
-            t = torch.as_tensor(scanrs_amd.DevArray(ptr, count, "<i8" if dtype == 1 else "<f8"), device="cuda:0")
-            self.bufs[rank] = t.cpu().numpy()
-            self.barrier.wait()
-            total = self.bufs[0].copy()
-            for b in self.bufs[1:]:
-                total += b  # (int64 wraps like uint64)
-            self.barrier.wait()
-            t.copy_(torch.from_numpy(total))
-            torch.cuda.synchronize()
-            return 0
-
-        return allreduce
-
-
 class Hooked:
     """Handles bound with set_shard to explicit cuts, one thread per rank."""
 
@@ -126,20 +92,8 @@ class Hooked:
 
     def on_all(self, fn):
         """[result or exception] per rank"""
-        out = [None] * self.world
-
-        def work(r):
-            try:
-                out[r] = fn(r, self.hs[r])
-            except BaseException as e:  # noqa: BLE001
-                out[r] = e
-
-        threads = [threading.Thread(target=work, args=(r,)) for r in range(self.world)]
-        for t in threads:
-            t.start()
-        for t in threads:
-            t.join()
-        return out
+        out, err = run_ranks(self.world, lambda r: fn(r, self.hs[r]))
+        return [o if e is None else e for o, e in zip(out, err)]
 
     def knn(self, pts, k, per_rank_k=None):
         out = self.on_all(lambda r, h: h.knn_sharded(pts, per_rank_k[r] if per_rank_k else k, return_sq_dist=True))

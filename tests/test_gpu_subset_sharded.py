@@ -9,7 +9,6 @@ cells x genes stored CSR, and the transposed view of the latter; the cells are t
 import ctypes
 import os
 import sys
-import threading
 
 import numpy as np
 import pytest
@@ -22,6 +21,7 @@ if TESTS not in sys.path:
 import subset_ref as ref  # noqa: E402
 import subset_sharded_case as sc  # noqa: E402
 import subset_sharded_ref as fx  # noqa: E402
+from shard_ring import Ring, run_ranks  # noqa: E402
 
 SHARDS = (1, 2, 3, 5)
 FORMS = ("multi", "hook")
@@ -56,40 +56,6 @@ def same_bits(a, b):
 
 
 # ---- the three forms behind one set of calls ------------------------------------------------------------------------------------------
-class Ring:
-    """The host hook of `world` ranks: every rank brings its device buffer, the buffers are summed on the host (u64 wraps, as the
-    device sum does) and every rank takes the sum back. A rank that waits in vain fails its call instead of hanging."""
-
-    def __init__(self, world):
-        import torch
-
-        self.torch, self.world = torch, world
-        self.barrier = threading.Barrier(world, timeout=60)
-        self.bufs = [None] * world
-        self.dtypes, self.calls = set(), 0
-
-    def hook(self, rank):
-        def allreduce(ptr, count, dtype):
-            import scanrs_amd
-
-            torch = self.torch
-            self.dtypes.add(dtype)
-            if rank == 0:
-                self.calls += 1
-            t = torch.as_tensor(scanrs_amd.DevArray(ptr, count, "<i8" if dtype == 1 else "<f8"), device="cuda:0")
-            self.bufs[rank] = t.cpu().numpy()
-            self.barrier.wait()
-            total = self.bufs[0].copy()
-            for b in self.bufs[1:]:
-                total += b  # (int64 wraps like uint64)
-            self.barrier.wait()
-            t.copy_(torch.from_numpy(total))
-            torch.cuda.synchronize()
-            return 0
-
-        return allreduce
-
-
 def _genes_by_cells_views(sa, triplet, n_local, orientation):
     """(the genes x cells view the maps are composed on, a function that gives the view of the orientation)"""
     ip, ix, vv = triplet
@@ -153,19 +119,7 @@ class Hooked:
             self.hs.append(view(g))
 
     def on_all(self, fn):
-        out, err = [None] * self.world, [None] * self.world
-
-        def work(r):
-            try:
-                out[r] = fn(self.hs[r])
-            except BaseException as e:  # noqa: BLE001
-                err[r] = e
-
-        threads = [threading.Thread(target=work, args=(r,)) for r in range(self.world)]
-        for t in threads:
-            t.start()
-        for t in threads:
-            t.join()
+        out, err = run_ranks(self.world, lambda r: fn(self.hs[r]))
         for e in err:
             if e is not None:
                 raise e
