@@ -725,6 +725,8 @@ int scanrs_mat_set_spmm_path(scanrs_mat *m, int path);
  *                       overflow part (0: max(4 M, nnz / 64)); a matrix with more of them is built by the two-walk form instead.
  *   "tile_emit_staged" (1)  dense tile layout, diagnostic: 0 makes the emission of the record streams search its per-visit tables in global
  *                       memory instead of LDS - the form taken by itself when a part has more than 4 000 tiles. Same layout.
+ *   "tile_poison_slack" (0)  test hook: 1 = the rows behind the end of the tile kernel's compact panel copy (the slack its staging may
+ *                       read, never an index or record array) are filled with NaN before every tile kernel launch. Same products bit for bit.
  *   "tile_builder" (1)  1: wave-level builder of the tile layout (default tile shape); 0: per-thread walk (reference form)
  *   "tile_build_waves" (0)   cap on the waves per CU of that builder (0: as many as fit)
  *   "sync_timeout_s" (120)  PROCESS-WIDE (same as scanrs_set_global_option): deadline of every host-side wait for the device

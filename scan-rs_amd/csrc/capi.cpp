@@ -1483,6 +1483,8 @@ int scanrs_mat_set_option(scanrs_mat *m, const char *key, double value) {
             set_sync_timeout_checked(value);
         } else if (k == "tile_spare_cus") {
             st.tile_spare_cus = value != 0.0;
+        } else if (k == "tile_poison_slack") {
+            st.tile_poison_slack = value != 0.0;
         } else if (k == "spmv_row_table") {
             st.spmv_row_table = value != 0.0;
         } else if (k == "gemm_direct") {

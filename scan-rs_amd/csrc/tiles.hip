@@ -366,8 +366,10 @@ __global__ __launch_bounds__(64) void tile_assign_wave_kernel(const uint64_t *__
     auto emit = [&](uint32_t v) { // the row of visit v: whole 64-byte runs per group and position
         if (FILL && g < n_groups) {
             const uint64_t row = (g * sh.nt + v) * 64u;
-            const uint32_t e0 = a.w00 ? a.w00 : (KU > 0 ? B * T : (v & 3u) * T); // an unused unit position reads the row of zeros behind the ring,
-            const uint32_t e1 = a.w01 ? a.w01 : (v & 3u) * T;                    // an unused general one row 0 of the visit's own tile (weight 0)
+            // an unused position, unit or general, reads the row of zeros behind the ring: a panel row no nonzero refers to (it may
+            // hold anything, NaN and infinities included) is never multiplied, not even by a weight of 0
+            const uint32_t e0 = a.w00 ? a.w00 : B * T;
+            const uint32_t e1 = a.w01 ? a.w01 : B * T;
             prow[row + q] = (uint16_t)e0;
             prow[row + 32u + q] = (uint16_t)e1;
             pcnt[row + q] = (uint8_t)(e0 >> 16);
@@ -522,20 +524,13 @@ __global__ __launch_bounds__(256) void tile_ov_compact_kernel(const uint64_t *__
     }
 }
 
-// An unused general position reads a row that is certainly in the ring at its visit — row 0 of the visit's own tile — with
-// weight 0; an unused unit position (no weight) reads the row of zeros that the kernel keeps behind the ring (row B T).
+// An unused position — general (weight 0) or unit (no weight) — reads the row of zeros that the kernel keeps behind the ring
+// (row B T), never a panel row: 0 x a NaN or infinite panel entry cannot occur.
 __global__ void tile_init_rows_kernel(uint16_t *__restrict__ prow, uint64_t n_rec, TileShape sh) {
     // 4 records per step, grid-stride (a dispatch holds fewer than 2^32 work-items)
-    for (uint64_t e = (uint64_t)blockIdx.x * blockDim.x + threadIdx.x; e * 4u < n_rec; e += (uint64_t)gridDim.x * blockDim.x) {
-        const uint32_t v = (uint32_t)((e * 4u / (sh.nset * 64u)) % sh.nt);
-        const uint32_t own = (v % sh.B) * sh.T, zero = sh.B * sh.T;
-        uint32_t word[2] = {0u, 0u};
-        for (uint32_t i = 0; i < 4u; i++) {
-            const uint32_t lane = (uint32_t)((e * 4u + i) & 63u);
-            word[i >> 1] |= ((lane / sh.sps) < sh.KU ? zero : own) << (16u * (i & 1u));
-        }
-        reinterpret_cast<uint2 *>(prow)[e] = make_uint2(word[0], word[1]);
-    }
+    const uint32_t zero = sh.B * sh.T, pair = zero | (zero << 16);
+    for (uint64_t e = (uint64_t)blockIdx.x * blockDim.x + threadIdx.x; e * 4u < n_rec; e += (uint64_t)gridDim.x * blockDim.x)
+        reinterpret_cast<uint2 *>(prow)[e] = make_uint2(pair, pair);
 }
 
 // pw[rec] = the map chain at the record's (count, outer, inner), 0 for an unused position. One work-item per position that
@@ -695,7 +690,10 @@ __global__ __launch_bounds__(256) void tile_weights_unit_kernel(const uint16_t *
 // The factor of the weight of a count-1 nonzero that depends on one side only (outer or inner position): the chain run on
 // x = 1 with the links of the other side left out; the side that owns the links in front of the nonlinear links also owns
 // those (nl_outer). uo[o] * vi[i] == f(1, o, i) up to rounding for the chains tile_map_separable() accepts.
-__global__ void tile_unit_factor_kernel(DevMap map, int side_outer, int nl_outer, uint64_t n, double *__restrict__ out) {
+// indptr (outer side only): an EMPTY outer vector gets the factor 0 when its own is not finite (the infinite column scale of an empty
+// barcode, normalization.rs:138-178): the reference never applies it (sqz/src/prod.rs:138-146 sums stored nonzeros), and the
+// products multiply a vector's sum by this factor - 0 x inf would make the empty vector's row NaN.
+__global__ void tile_unit_factor_kernel(DevMap map, int side_outer, int nl_outer, uint64_t n, double *__restrict__ out, const uint64_t *__restrict__ indptr) {
     const uint64_t idx = (uint64_t)blockIdx.x * blockDim.x + threadIdx.x;
     if (idx >= n) return;
     double x = 1.0;
@@ -722,6 +720,7 @@ __global__ void tile_unit_factor_kernel(DevMap map, int side_outer, int nl_outer
             break;
         }
     }
+    if (indptr && !isfinite(x) && indptr[idx + 1] == indptr[idx]) x = 0.0;
     out[idx] = x;
 }
 
@@ -774,6 +773,12 @@ __global__ void tile_scale_panel_kernel(const double *__restrict__ X, uint32_t l
     const uint64_t r = e / ldc;
     const uint32_t c = (uint32_t)(e - r * ldc);
     Xc[e] = c < l ? vi[r] * X[r * ldx + c] : 0.0;
+}
+
+// test hook ("tile_poison_slack"): NaN into the n doubles of slack behind the compact panel copy
+__global__ void tile_poison_slack_kernel(double *__restrict__ slack, uint64_t n) {
+    const uint64_t e = (uint64_t)blockIdx.x * blockDim.x + threadIdx.x;
+    if (e < n) slack[e] = __builtin_nan("");
 }
 
 __global__ void tile_gather_slots_kernel(const double *__restrict__ per_vec, const uint32_t *__restrict__ slot_vec, uint64_t n_slots, double *__restrict__ per_slot) {
@@ -838,6 +843,7 @@ struct TileLayout {
     uint32_t dn_wgg = 0, dn_items = 0;
     uint64_t dn_chunks = 0;        // chunks of 16 positions in drec / pw (cmeta: one entry each)
     uint64_t dn_served = 0;        // nonzeros that own a record
+    uint64_t src_nnz = 0;          // nonzeros of the copy the layout was built from
     DevBuf<uint32_t> drec;         // 4 x slot-in-group | raw count << 8 | ring row << 16
     DevBuf<uint64_t> cmeta;        // group << 32 | visit of a chunk (weight refresh)
     DevBuf<char> ditems;           // DenseItem per workgroup item
@@ -891,6 +897,9 @@ void tile_layout_stats(const TileLayout *t, uint64_t out[3]) {
         out[1] = t->dn_served;
     } else {
         out[0] = t->prow.n;
+        // fixed positions: every nonzero that is not overflow owns one. DERIVED from the two totals, not counted from the records: a
+        // builder that lost a nonzero would not show here (the exact products of tests/test_gpu_spmm_routes.py would)
+        out[1] = t->n_slots ? t->src_nnz - t->ov.nnz : 0;
     }
 }
 
@@ -921,6 +930,7 @@ TileLayout *tile_layout_build(Storage &st, const SparseCopy &cp, double max_over
     sh.sps = 64u / sh.K;
     sh.nset = (sh.S + sh.sps - 1) / sh.sps;
     sh.nt = (uint32_t)((cp.n_inner + sh.T - 1) / sh.T);
+    tl->src_nnz = cp.nnz;
     hipStream_t s = stream ? stream : st.stream;
     auto lap = [&](const char *what) { // SCANRS_TRACE: where a build spends its time (forces a sync per phase)
         static thread_local std::chrono::steady_clock::time_point t_prev;
@@ -1160,8 +1170,8 @@ static void tile_layout_weights(Storage &st, TileLayout &tl, const SparseCopy &c
     if (tl.unit_mode) {
         if (tl.uo.n != cp.n_outer) tl.uo.alloc(std::max<uint64_t>(cp.n_outer, 1));
         if (tl.vi.n != cp.n_inner) tl.vi.alloc(std::max<uint64_t>(cp.n_inner, 1));
-        hipLaunchKernelGGL(tile_unit_factor_kernel, dim3((unsigned)((cp.n_outer + 255) / 256)), dim3(256), 0, st.stream, map, 1, nl_outer, cp.n_outer, tl.uo.p);
-        hipLaunchKernelGGL(tile_unit_factor_kernel, dim3((unsigned)((cp.n_inner + 255) / 256)), dim3(256), 0, st.stream, map, 0, nl_outer, cp.n_inner, tl.vi.p);
+        hipLaunchKernelGGL(tile_unit_factor_kernel, dim3((unsigned)((cp.n_outer + 255) / 256)), dim3(256), 0, st.stream, map, 1, nl_outer, cp.n_outer, tl.uo.p, cp.indptr.p);
+        hipLaunchKernelGGL(tile_unit_factor_kernel, dim3((unsigned)((cp.n_inner + 255) / 256)), dim3(256), 0, st.stream, map, 0, nl_outer, cp.n_inner, tl.vi.p, (const uint64_t *)nullptr);
         if (tl.uo_slot.n != std::max<uint64_t>(tl.n_slots, 1)) tl.uo_slot.alloc(std::max<uint64_t>(tl.n_slots, 1));
         if (tl.n_slots)
             hipLaunchKernelGGL(tile_gather_slots_kernel, grid_1d(tl.n_slots), dim3(256), 0, st.stream, tl.uo.p, tl.slot_vec.p, tl.n_slots, tl.uo_slot.p);
@@ -1219,7 +1229,7 @@ struct TileArgs {
 // parts[part][outer][:] = sum over the part's visits of weight * X[inner, :]
 // KU > 0 (unit mode): position j < KU of every (slot, visit) pair holds a count-1 nonzero or nothing: its row is ADDED (no
 // weight, no v_readlane of one: the panel staged here was scaled by the per-inner factor, the sums are scaled by the
-// per-outer factor at the end); an unused unit position reads a row of zeros kept behind the ring.
+// per-outer factor at the end). An unused position, unit or general, reads a row of zeros kept behind the ring.
 template <int K, int S, int KU>
 __device__ __forceinline__ void spmm_tile_body(const TileArgs &ta, const double *__restrict__ X, uint32_t ldx, uint32_t l,
                                                double *__restrict__ parts, uint32_t ldo, uint64_t part_stride, uint32_t n_items) {
@@ -1241,7 +1251,7 @@ __device__ __forceinline__ void spmm_tile_body(const TileArgs &ta, const double 
     const uint32_t n_wgg = (uint32_t)((ta.n_groups + TL_NW - 1) / TL_NW);
     const char *Xb = reinterpret_cast<const char *>(X);
     const uint32_t lds0 = (uint32_t)(uintptr_t)(lds_ptr_t)lds;
-    if (ta.sh.KU) { // the row of zeros behind the ring (unused unit positions); visible to everybody after the first barrier
+    { // the row of zeros behind the ring (unused positions); visible to everybody after the first barrier
         const uint32_t zoff = nbuf * tile_bytes;
         for (uint32_t i = threadIdx.x * 16u; i < rowbytes; i += blockDim.x * 16u) *reinterpret_cast<d2 *>(lds + zoff + i) = (d2){0.0, 0.0};
     }
@@ -1553,7 +1563,7 @@ __global__ __launch_bounds__(256) void tile_finish_kernel(const double *__restri
 template <int K, int S, int KU>
 void launch_tile_kernel(Storage &st, const TileArgs &ta, const double *X, uint32_t ldx, uint32_t l, double *parts, uint32_t ldo,
                         uint64_t part_stride, uint32_t n_items, uint32_t grid) {
-    const size_t shmem = ((size_t)ta.sh.B * ta.sh.T + (ta.sh.KU ? 1u : 0u)) * ldx * 8; // the ring (+ the row of zeros)
+    const size_t shmem = ((size_t)ta.sh.B * ta.sh.T + 1u) * ldx * 8; // the ring + the row of zeros (spmm_tiles_ok keeps room for it)
     if constexpr (S <= 28) {
         SCANRS_HIP(hipFuncSetAttribute((const void *)spmm_tile_kernel_r168<K, S, KU>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)shmem));
         hipLaunchKernelGGL((spmm_tile_kernel_r168<K, S, KU>), dim3(grid), dim3(64 * TL_NW), shmem, st.stream, ta, X, ldx, l, parts, ldo, part_stride,
@@ -1690,6 +1700,12 @@ void launch_spmm_tiles(Storage &st, SparseCopy &cp, const DevMap &map, const dou
     } else {
         if (!copied) launch_copy_cols(st, X, ldx, xc, ldc, cp.n_inner, l);
         if (ldx != ldc) Xov = xc;
+    }
+    if (st.tile_poison_slack) { // test hook: the slack rows hold NaN instead of whatever the allocator left there
+        const uint64_t n = 3ull * sh.T * ldc;
+        if (st.prof.on) st.prof.begin(st.stream, "tile_poison_slack", (double)n * 8.0);
+        hipLaunchKernelGGL(tile_poison_slack_kernel, grid_1d(n), dim3(256), 0, st.stream, xc + (size_t)cp.n_inner * ldc, n);
+        if (st.prof.on) st.prof.end(st.stream);
     }
     X = xc;
     ldx = ldc;

@@ -579,6 +579,17 @@ def test_blocked_kernel_matches_gather_and_oracle(sa, storage):
             assert_close(a1, a2, rtol=1e-11, atol=1e-10)
 
 
+def _tile_kernel_served(g):
+    """The hybrid product really ran on this handle since its profile was last reset: the tile kernel is in the profile AND the
+    records of the handle's layouts serve nonzeros (`set_spmm_path(3)` alone is a wish: launch_spmm_f64 takes a gather kernel for
+    panels under 16 columns or shapes the tile kernel refuses, and a layout may leave every nonzero to the overflow gather)."""
+    return any(k.startswith("spmm_tile_kernel") for k in g.profile_get()) and g.counter("tile_served_nonzeros") > 0
+
+
+# (shape, l) pairs of the tile tests below that cannot reach the tile kernel: panels narrower than 16 columns, every shape
+TILE_UNREACHED_L = (8,)
+
+
 @pytest.mark.parametrize("storage", [so.CSR, so.CSC])
 @pytest.mark.parametrize("tile_k,tile_s,tile_t,tile_b,tile_ku", [(2, 28, 48, 4, 1), (2, 32, 48, 4, 1), (2, 32, 48, 4, 0), (2, 28, 48, 4, 0), (2, 32, 24, 8, 1), (3, 32, 64, 3, 0),
                                                                  (4, 32, 96, 2, 0), (4, 28, 40, 3, 0), (2, 32, 48, 4, -1)])
@@ -601,6 +612,7 @@ def test_lds_staged_product_matches_gather_and_oracle(sa, storage, tile_k, tile_
         g3.set_spmm_path(3).set_option("tile_k", tile_k).set_option("tile_s", tile_s).set_option("tile_t", tile_t).set_option("tile_b", tile_b)
         # tile_ku -1: the dense record layout of round 5 (the default for this shape); the others: round 4's fixed positions per (slot, visit)
         g3.set_option("tile_ku", max(tile_ku, 0)).set_option("tile_dense", 1 if tile_ku < 0 else 0)
+        g3.profile_enable(True)
         f = rng.random(cols) + 0.5
         fr = rng.random(rows) + 0.5
         for gm in (g1, g3):
@@ -615,12 +627,16 @@ def test_lds_staged_product_matches_gather_and_oracle(sa, storage, tile_k, tile_
                 ref_m = so.LowRankOffset(o, u, v)
             for l in (16, 17, 50, 100, 104, 105, 230, 8):
                 q = rng.standard_normal((cols, l))
+                g3.profile_reset()
                 a1, a3, ref = g1.dot(q), g3.dot(q), ref_m.dot(q)
+                assert _tile_kernel_served(g3) == (l not in TILE_UNREACHED_L), (rows, cols, l)  # "route 3 equals route 1" is not the gather against itself
                 assert_close(a3, ref, rtol=1e-10, atol=1e-9)
                 assert_close(a1, a3, rtol=1e-11, atol=1e-10)
                 assert np.array_equal(a3, g3.dot(q))  # bitwise repeatable
                 ql = rng.standard_normal((l, rows))
+                g3.profile_reset()
                 a1, a3, ref = g1.rdot(ql), g3.rdot(ql), ref_m.rdot(ql)
+                assert _tile_kernel_served(g3) == (l not in TILE_UNREACHED_L), (rows, cols, l)
                 assert_close(a3, ref, rtol=1e-10, atol=1e-9)
                 assert_close(a1, a3, rtol=1e-11, atol=1e-10)
 
@@ -647,7 +663,9 @@ def test_wave_level_layout_builder_equals_the_per_thread_walk(sa, tile_ku):
                 g.compose_scale_axis(1, np.linspace(0.5, 1.5, cols)).apply(sa.FN_LOG2_1P)
                 q = np.cos(np.arange(cols * 40, dtype=np.float64)).reshape(cols, 40)
                 ql = np.sin(np.arange(rows * 24, dtype=np.float64)).reshape(24, rows)
+                g.profile_enable(True)
                 outs.append((g.dot(q), g.rdot(ql)))
+                assert _tile_kernel_served(g), (rows, cols, storage)  # every shape here reaches the tile kernel (40 and 24 columns)
             assert np.array_equal(outs[0][0], outs[1][0]) and np.array_equal(outs[0][1], outs[1][1]), (rows, cols, fill, storage)
 
 
@@ -671,7 +689,9 @@ def test_one_pass_layout_build_equals_count_then_fill(sa):
                 g.compose_scale_axis(1, np.linspace(0.5, 1.5, cols)).apply(sa.FN_LOG2_1P)
                 q = np.cos(np.arange(cols * 40, dtype=np.float64)).reshape(cols, 40)
                 ql = np.sin(np.arange(rows * 24, dtype=np.float64)).reshape(24, rows)
+                g.profile_enable(True)
                 outs.append((g.dot(q), g.rdot(ql)))
+                assert _tile_kernel_served(g), (rows, cols, storage)  # every shape here reaches the tile kernel (40 and 24 columns)
             assert np.array_equal(outs[0][0], outs[1][0]) and np.array_equal(outs[0][1], outs[1][1]), (rows, cols, fill, storage)
 
 
@@ -691,7 +711,9 @@ def test_wide_weight_refresh_equals_the_one_position_form(sa):
                 g.compose_scale_axis(1, np.linspace(0.5, 1.5, cols)).apply(sa.FN_LOG2_1P).compose_scale_axis(0, np.linspace(0.7, 1.3, rows))
                 q = np.cos(np.arange(cols * 40, dtype=np.float64)).reshape(cols, 40)
                 ql = np.sin(np.arange(rows * 24, dtype=np.float64)).reshape(24, rows)
+                g.profile_enable(True)
                 outs.append((g.dot(q), g.rdot(ql)))
+                assert _tile_kernel_served(g), (rows, cols, storage)  # every shape here reaches the tile kernel (40 and 24 columns)
             assert np.array_equal(outs[0][0], outs[1][0]) and np.array_equal(outs[0][1], outs[1][1]), (rows, cols, fill, storage)
 
 
@@ -725,7 +747,9 @@ def test_dense_record_layout_equals_round4_layout_and_is_placement_independent(s
                 g.compose_scale_axis(1, np.linspace(0.5, 1.5, cols)).apply(sa.FN_LOG2_1P).compose_scale_axis(0, np.linspace(0.7, 1.3, rows))
                 q = np.cos(np.arange(cols * 40, dtype=np.float64)).reshape(cols, 40)
                 ql = np.sin(np.arange(rows * 24, dtype=np.float64)).reshape(24, rows)
+                g.profile_enable(True)
                 outs.append((g.dot(q), g.rdot(ql)))
+                assert _tile_kernel_served(g), (rows, cols, storage)  # every shape here reaches the tile kernel (40 and 24 columns)
                 assert np.array_equal(outs[-1][0], g.dot(q))  # repeatable
             assert_close(outs[1][0], outs[0][0], rtol=1e-12, atol=1e-11)
             assert_close(outs[1][1], outs[0][1], rtol=1e-12, atol=1e-11)
@@ -759,6 +783,7 @@ def test_map_evaluated_inside_the_tile_kernel_equals_the_weight_stream_and_the_o
                 for wtab in (1, 0):  # (table gathers, and the weight stream of the same layout)
                     g, o = pair(sa, dense, storage)
                     g.set_spmm_path(3).set_option("tile_wtab", wtab).set_option("tile_split_min", 0.3)
+                    g.profile_enable(True)
                     hs.append(g)
                 fa, fb = np.linspace(0.5, 1.5, cols if log_axis == 1 else rows), np.linspace(0.7, 1.3, rows if log_axis == 1 else cols)
                 if log_axis is not None:
@@ -766,6 +791,7 @@ def test_map_evaluated_inside_the_tile_kernel_equals_the_weight_stream_and_the_o
                         g.compose_scale_axis(log_axis, fa).apply(sa.FN_LOG2_1P).compose_scale_axis(1 - log_axis, fb)
                     o = o.compose_map(so.MapOp(so.OP_SCALE_AXIS, axis=log_axis, a=fa)).apply(so.OP_LOG2_1P).compose_map(so.MapOp(so.OP_SCALE_AXIS, axis=1 - log_axis, a=fb))
                 outs = [(g.dot(q), g.rdot(ql)) for g in hs]
+                assert all(_tile_kernel_served(g) for g in hs), (rows, cols, storage, log_axis)  # every shape here reaches the tile kernel
                 ref = (o.dot(q), o.rdot(ql))
                 for k in (0, 1):
                     assert_close(outs[0][k], ref[k], rtol=1e-10, atol=1e-9)
