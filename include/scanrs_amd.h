@@ -734,7 +734,16 @@ int scanrs_mat_set_spmm_path(scanrs_mat *m, int path);
  * SCANRS_TRACE and SCANRS_TRACE_EIG (phase timings on stderr). */
 int scanrs_mat_set_option(scanrs_mat *m, const char *key, double value);
 /* Event counters of the handle (diagnostics): "bk_host_retries" = svd_bk calls whose device-side factorizations did not
- * converge within the queued passes and that were run again with host factorizations. First-call accounting, host microseconds of
+ * converge within the queued passes and that were run again with host factorizations. The decisions of the last svd_bk on the
+ * handle about its reused projection (host-side stores; a retry on the host path overwrites them with its own): "bk_q" / "bk_b" =
+ * columns of the Krylov basis and of one block; "bk_coef_valid" = 1 when the coefficient bookkeeping Q = K C held (no panel was
+ * completed with random directions); "bk_flagged_older" = columns of the blocks before the last whose max |C| reaches "reuse_cmax",
+ * counted before any raise; "bk_limit_branch" = 0 none flagged, 1 they fit the repair pass, 2 bound raised to the largest flagged,
+ * 3 raised to the largest that has to stay dense, 4 bound unchanged and a pass wider than 104 columns; "bk_limit_bits" = the f64 bit
+ * pattern of the bound finally used; "bk_direct_columns" = columns recomputed by a sparse product (the last block included when
+ * "bk_last_direct" is 1); "bk_full_direct" = 1 when the whole projection was one sparse product of Q; "bk_early_projections" = dense
+ * projections queued beside the iterations; "bk_cmax_dense_bits" = f64 bits of the largest max |C| among the columns that took the
+ * dense route (0.0 when none did). First-call accounting, host microseconds of
  * the calling thread since the handle was made: "t_layout_us" (tile layout builds), "t_side_wait_us" (waiting for the helper
  * thread of "side_build"), "t_start_panel_us", "t_delivery_us" (U, V to host arrays); process-wide: "t_alloc_us" / "alloc_calls"
  * (hipMalloc). The tile layouts of the handle (both orientations, summed): "tile_positions" = record positions the tile kernel works

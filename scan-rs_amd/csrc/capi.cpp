@@ -1503,7 +1503,38 @@ int scanrs_mat_get_counter(scanrs_mat *m, const char *key, uint64_t *value) {
         const std::string k(key);
         if (k == "bk_host_retries")
             *value = m->st->bk_host_retries;
-        else if (k == "partition_rounds") // rounds of the last scanrs_mat_partition_on_thresholds[_sharded] on this handle
+        else if (k.rfind("bk_", 0) == 0) { // what the last svd_bk on this handle decided about its reused projection (Storage::BkDecisions)
+            const Storage::BkDecisions &d = m->st->bk;
+            auto bits = [](double x) {
+                uint64_t u;
+                memcpy(&u, &x, sizeof(u));
+                return u;
+            };
+            if (k == "bk_q")
+                *value = d.q;
+            else if (k == "bk_b")
+                *value = d.b;
+            else if (k == "bk_coef_valid")
+                *value = d.coef_valid;
+            else if (k == "bk_flagged_older")
+                *value = d.flagged_older;
+            else if (k == "bk_limit_branch")
+                *value = d.limit_branch;
+            else if (k == "bk_limit_bits")
+                *value = bits(d.limit);
+            else if (k == "bk_direct_columns")
+                *value = d.direct_columns;
+            else if (k == "bk_last_direct")
+                *value = d.last_direct;
+            else if (k == "bk_full_direct")
+                *value = d.full_direct;
+            else if (k == "bk_early_projections")
+                *value = d.early_projections;
+            else if (k == "bk_cmax_dense_bits")
+                *value = bits(d.cmax_dense);
+            else
+                fail(SCANRS_ERR_ARGUMENT, "unknown counter '%s'", key);
+        } else if (k == "partition_rounds") // rounds of the last scanrs_mat_partition_on_thresholds[_sharded] on this handle
             *value = m->st->partition_rounds;
         else if (k == "partition_allreduces") // ... and its exchange steps (an unsharded handle: 0)
             *value = m->st->partition_allreduces;

@@ -423,6 +423,14 @@ struct Storage {
     const int *skip_flag = nullptr;       // device flag the dense kernels launched now test first (nonzero: return at once) — set around the queued passes of a device-side orthonormalisation
     uint64_t orth_fallbacks = 0;          // orthonormalisations that ended in the host Gram-Schmidt for rank-deficient panels (solver.cpp)
     uint64_t bk_host_retries = 0;         // svd_bk calls that fell back from the device-side factorizations to the host path (scanrs_mat_get_counter)
+    // what the last svd_bk on this handle decided about its reused projection (host-side stores, scanrs_mat_get_counter "bk_*"; a retry
+    // on the host path overwrites them): limit_branch 0 = no older column flagged, 1 = the flagged ones fit the repair pass, 2 = bound
+    // raised to the largest flagged, 3 = raised to `need`, 4 = bound unchanged and a pass wider than 104 columns
+    struct BkDecisions {
+        uint64_t q = 0, b = 0, coef_valid = 0, flagged_older = 0, limit_branch = 0, direct_columns = 0, last_direct = 0, full_direct = 0,
+                 early_projections = 0;
+        double limit = 0.0, cmax_dense = 0.0; // the bound finally used; the largest max|C| among the columns that took the dense route
+    } bk;
     int col_moments = 1;                  // per-axis sums of a log-normalized map from the copy whose OUTER vectors are summed over (per-cell table + LDS fixed-point scatter) when eligible; 0: always the ordinary pass
     int device_factor = 1;                // svd_bk: CholeskyQR factors and the coefficient bookkeeping on the device, no host round trip per orthonormalisation (0: host)
     unsigned d2h_threads = 4;             // host threads that empty the pinned ring of a large result download

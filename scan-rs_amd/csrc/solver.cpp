@@ -990,6 +990,8 @@ static int pca_bk_impl(scanrs_mat *m, uint32_t k, double k_multiplier, uint32_t 
     uint32_t b = (uint32_t)std::ceil((double)k * k_multiplier); // bk_svd.rs:49
     b = (uint32_t)std::min<uint64_t>(std::min(Mg, Ng), b);     // bk_svd.rs:81
     if (b < k) fail(SCANRS_ERR_INVALID_K, "invalid k");
+    c.st.bk = Storage::BkDecisions{}; // the decisions of THIS run (a retry on the host path starts them again)
+    c.st.bk.b = b;
 
     const bool rows_ge = Mg >= Ng; // bk_svd.rs:89 `if m >= n`
     // S = the side the Krylov panel lives on (the shorter one): cols when m >= n, rows otherwise.
@@ -1006,6 +1008,7 @@ static int pca_bk_impl(scanrs_mat *m, uint32_t k, double k_multiplier, uint32_t 
         // panels: antibody / targeted-gene matrices, k close to min(m, n)). Any orthonormal basis of the whole space gives
         // the same singular triplets, so Q = I: one sparse product with the identity panel, then the Rayleigh-Ritz finish.
         const uint32_t qe = (uint32_t)ds, ldqe = even_up(qe);
+        c.st.bk.q = qe;
         double *Ke = c.dev("bk_K", (size_t)ds * ldqe);
         double *Te = c.dev("bk_T", (size_t)dt * ldqe);
         std::vector<double> eye((size_t)ds * qe, 0.0);
@@ -1028,6 +1031,7 @@ static int pca_bk_impl(scanrs_mat *m, uint32_t k, double k_multiplier, uint32_t 
     // the copy / tile layout of the SECOND product on a helper thread, beside everything up to the end of the first pass
     prepare_second_orientation(m, !to_t_transpose);
     const uint32_t ldb = even_up(b), q = b * n_iter, ldq = even_up(q);
+    c.st.bk.q = q;
     double *P = c.dev("bk_P", (size_t)ds * ldb);
     double *Ptmp = c.dev("bk_Ptmp", (size_t)ds * ldb);
     double *Y = c.dev("bk_Y", (size_t)dt * ldb);
@@ -1158,6 +1162,7 @@ static int pca_bk_impl(scanrs_mat *m, uint32_t k, double k_multiplier, uint32_t 
         SCANRS_HIP(hipEventRecord(ev_proj[it].e, cx.s));
         last_proj = (int)it;
         projected[j] = 1;
+        c.st.bk.early_projections++;
     };
     for (uint32_t i = 0; i < n_iter; i++) {
         Tick tk("bk: iteration");
@@ -1244,39 +1249,49 @@ static int pca_bk_impl(scanrs_mat *m, uint32_t k, double k_multiplier, uint32_t 
         }
     }
     snoop_poll(snoop, 0.82);
-    // T' = (op(A) K) C amplifies the rounding of op(A) K by |C|. Columns of Q whose coefficient column stays
-    // small (<= 1e5: error <= ~1e-11) take the cheap dense route; the others — directions in which the Krylov
-    // blocks are numerically dependent — are recomputed directly as a (narrow) sparse product op(A) Q[:, bad].
+    // T' = (op(A) K) C amplifies the rounding of op(A) K by |C|. Columns of Q whose coefficient column stays below
+    // the bound L ("reuse_cmax", 1e5) take the cheap dense route; the others — directions in which the Krylov blocks
+    // are numerically dependent — are recomputed directly as a (narrow) sparse product op(A) Q[:, bad]. What is held
+    // (tests/test_gpu_bk_reuse.py): every returned triplet has max |op(A) x_i - s_i y_i| <=
+    // sqrt(q) L 2^-53 s_1, L the bound finally used (1.1e-11 sqrt(q) s_1 at 1e5).
     double cmax_limit = c.st.reuse_cmax;
     std::vector<uint32_t> bad;
     const bool c_valid = c.st.orth_fallbacks == fallbacks0;
+    c.st.bk.coef_valid = c_valid;
+    std::vector<double> colmax(q, 0.0); // max |C| per column of Q (filled when the bookkeeping is used)
     if (reuse && !c_valid) {
         for (uint32_t j = 0; j < q; j++) bad.push_back(j); // everything directly: one q-wide product below
         if (trace_on()) fprintf(stderr, "[scanrs trace] bk: rank-deficient panels were completed on the host: the projection is computed directly\n");
     }
     if (reuse && c_valid) {
-        std::vector<double> colmax(q, 0.0);
         for (uint32_t r = 0; r < q; r++)
             for (uint32_t j = 0; j < q; j++) colmax[j] = std::max(colmax[j], std::fabs(cfull[(size_t)r * q + j]));
         // The repair pass carries the last block (b columns) plus the flagged columns of the older blocks. A pass of up to 104
         // columns runs through the hybrid LDS-tile product, a wider one through the gather kernels at about twice the time: when
         // a few flagged columns too many stand in the way (22 on the 1 M-cell benchmark), the bound is raised — by at most two
-        // decades, error <= ~1e-9 instead of 1e-11 on those columns, far inside every tolerance — until the pass fits.
+        // decades: the same residual bound with the raised L, at most 1.1e-9 sqrt(q) s_1 — until the pass fits.
         // The rule looks at b and the coefficients only — not at whether this handle (or this shard) happens to run the hybrid product:
         // the flagged set, and with it the rounding of the result, is the same on every rank of a sharded run and under any memory
         // pressure (it used to depend on mat_tiles_ready).
+        std::vector<double> flagged; // the older blocks' columns at or above the bound, before any raise
+        for (uint32_t j = 0; j < (n_iter - 1) * b; j++)
+            if (!(colmax[j] < cmax_limit)) flagged.push_back(colmax[j]);
+        c.st.bk.flagged_older = flagged.size();
+        c.st.bk.limit_branch = flagged.empty() ? 0 : 4; // 4 unless the flagged columns fit or one of the two raises applies
         if (n_iter >= 2 && b <= 104u) {
-            const uint32_t last_lo = (n_iter - 1) * b, room = 104u - b;
-            std::vector<double> flagged;
-            for (uint32_t j = 0; j < last_lo; j++)
-                if (!(colmax[j] < cmax_limit)) flagged.push_back(colmax[j]);
+            const uint32_t room = 104u - b;
             if (flagged.size() > room) {
                 std::sort(flagged.begin(), flagged.end(), std::greater<double>());
                 const double need = flagged[room]; // the largest coefficient that has to take the dense route
-                if (flagged[0] < 100.0 * cmax_limit) // all of them within the two decades: the pass carries the last block alone (100 columns run 9 % faster than 104)
+                if (flagged[0] < 100.0 * cmax_limit) { // all of them within the two decades: the pass carries the last block alone (100 columns run 9 % faster than 104)
                     cmax_limit = std::nextafter(flagged[0], INFINITY);
-                else if (need < 100.0 * cmax_limit && (room == 0 || flagged[room - 1] > need))
+                    c.st.bk.limit_branch = 2;
+                } else if (need < 100.0 * cmax_limit && (room == 0 || flagged[room - 1] > need)) {
                     cmax_limit = std::nextafter(need, INFINITY);
+                    c.st.bk.limit_branch = 3;
+                }
+            } else if (!flagged.empty()) {
+                c.st.bk.limit_branch = 1;
             }
         }
         for (uint32_t j = 0; j < q; j++)
@@ -1319,6 +1334,9 @@ static int pca_bk_impl(scanrs_mat *m, uint32_t k, double k_multiplier, uint32_t 
         }
         if (trace_on()) fprintf(stderr, "[scanrs trace] bk: last block %s\n", last_direct ? "computed directly with the repair pass" : "through its half-product");
     }
+    c.st.bk.limit = cmax_limit;
+    c.st.bk.direct_columns = bad.size();
+    c.st.bk.last_direct = last_direct;
     double *Tfin = T; // the panel the Rayleigh-Ritz step reads
     {
         Tick tk("bk: projection");
@@ -1344,6 +1362,12 @@ static int pca_bk_impl(scanrs_mat *m, uint32_t k, double k_multiplier, uint32_t 
             for (uint32_t j = 1; j < n_iter; j++) any_early = any_early || projected[j];
             if (any_early && last_proj >= 0) SCANRS_HIP(hipStreamWaitEvent(c.s, ev_proj[last_proj].e, 0)); // the last early GEMM (they are ordered on their stream)
             Tfin = T2;
+            {
+                std::vector<char> is_bad(q, 0);
+                for (uint32_t j : bad) is_bad[j] = 1;
+                for (uint32_t j = 0; j < q; j++)
+                    if (!is_bad[j]) c.st.bk.cmax_dense = std::max(c.st.bk.cmax_dense, colmax[j]);
+            }
             if (!bad.empty()) {
                 const uint32_t nbad = (uint32_t)bad.size(), ldbad = even_up(nbad);
                 uint32_t *d_idx = c.st.scratch.get<uint32_t>("bk_badidx", nbad);
@@ -1360,6 +1384,7 @@ static int pca_bk_impl(scanrs_mat *m, uint32_t k, double k_multiplier, uint32_t 
             for (uint32_t j = 1; j < n_iter; j++) any_early = any_early || projected[j];
             if (any_early && last_proj >= 0) SCANRS_HIP(hipStreamWaitEvent(c.s, ev_proj[last_proj].e, 0)); // they read T, which is overwritten now
             mat_apply(m, to_t_transpose, K, ldq, q, T, ldq);
+            c.st.bk.full_direct = 1;
         }
         stage_mark("bk projection sync");
         c.sync();
