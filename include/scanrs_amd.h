@@ -758,7 +758,28 @@ int scanrs_mat_set_option(scanrs_mat *m, const char *key, double value);
  * integer scatter from the other copy ("subset_scatter"); "subset_allreduces" = the exchange steps of the last
  * scanrs_mat_sum_rows_u64_sharded or kin on this handle (0 on an unsharded one). "regather_plan_us" / "regather_pull_us" /
  * "regather_finish_us" = on a shard made by scanrs_multi_gather_outer / scanrs_multi_rebalance, the wall clock of the plan (one phase,
- * the same on every shard) and of the shard's own thread in pull and finish. */
+ * the same on every shard) and of the shard's own thread in pull and finish.
+ * The route of the LAST sparse product A X on this handle (host-side stores, overwritten by every product; a solver's last pass):
+ * "spmm_route" = its kernel family, one of SCANRS_SPMM_* below; "spmm_form" = the form within the family -
+ *   tiles:               bit 0 dense records (0: fixed positions), bit 1 unit mode (0: the weighted kernel), bits 2-3 where a
+ *                        position's weight comes from: 0 the weight stream, 1 the table by place, 2 the table by inner position;
+ *                        bits 4-5 the factor kept out of the weights: 0 none, 1 the inner side's (it rides in the staged panel),
+ *                        2 the outer side's (applied to the finished sums)
+ *   spmv_lds:            0 the map evaluated per nonzero, 1 materialized values, 2 a table per row
+ *   slice_walk, spmv2d:  bit 0 materialized values are read, bit 1 the first link's scale is interleaved with the vector (spmv2d),
+ *                        bit 2 that scale is staged in LDS beside the vector (slice_walk)
+ *   every other family:  0
+ * "spmm_chunks" = the column chunks the panel went through in (1 outside the tile route), with SCANRS_SPMM_SLIVER set when a last
+ * chunk under 16 columns went to the plain gather instead. */
+#define SCANRS_SPMM_TILES 1        /* hybrid: LDS-staged tiles + gather of the overflow part */
+#define SCANRS_SPMM_GATHER2D 2     /* L2-blocked gather */
+#define SCANRS_SPMM_GATHER2D_F32 3 /* ... over an f32 copy of the panel (panel precision 1) */
+#define SCANRS_SPMM_SLICE_WALK 4   /* 1 column, few long outer vectors: the vector in LDS slices */
+#define SCANRS_SPMM_SPMV2D 5       /* 1 or 2 columns, a vector beyond L2: walked in 2 MB slices */
+#define SCANRS_SPMM_SPMV_LDS 6     /* 1 column, many outer vectors: the vector in LDS parts */
+#define SCANRS_SPMM_SPMV 7         /* 1 or 2 columns, a wave per item */
+#define SCANRS_SPMM_GATHER 8       /* plain gather */
+#define SCANRS_SPMM_SLIVER (1u << 16)
 int scanrs_mat_get_counter(scanrs_mat *m, const char *key, uint64_t *value);
 /* Process-wide options of the entry points that take no handle:
  *   "h5_threads" (8)               threads that inflate the chunks of a large filtered HDF5 read
@@ -1192,6 +1213,21 @@ int scanrs_host_knn_merge(uint32_t k, const double *da, const uint32_t *ia, cons
 int scanrs_host_col_moments_plan(uint32_t max_count, uint32_t n_links, const int *kinds, const int *on_summed_axis, const double *fmin_pos,
                                  const double *fmax, uint64_t n_outer, uint64_t n_inner, uint32_t n_wg, int mode, int *accept, int *e1,
                                  int *e2);
+
+/* ---- the route of a sparse product (host only, no device): csrc/spmm_route.hpp, the source launch_spmm_f64 decides by --------------
+ * options: 18 values in this order - spmm_path, panel precision, "tile_auto", "tile_k", "tile_s", "tile_t", "tile_b", "tile_ku",
+ * "tile_dense", "tile_builder", "blocked_min_nnz", "slice_walk", "spmv_lds", "spmv_row_table", "spmm_order", "materialize",
+ * "tile_wtab", "tile_fold"; n_outer, n_inner, nnz: the copy the product walks; l columns of a panel with leading dimension ldx; the map
+ * as seen from that copy: kinds[i] = 1 ScaleAxis, 2 / 3 / 4 ln / log2 / log10 of 1 + x, 5 square, 6 / 7 the binomial deviance / Pearson
+ * residuals, a_outer[i] != 0 when link i indexes its array by the outer position. flags stand for the two steps that need a device:
+ * SCANRS_SPMM_TILES_AVAILABLE = a tile layout exists or was built (auto path: the size, the free memory and the overflow limit
+ * allowed it), SCANRS_SPMM_NO_VALUES_ROOM = no memory for materialized map values. out[6]: the family (SCANRS_SPMM_*), the form and
+ * the chunks as the counters "spmm_route" / "spmm_form" / "spmm_chunks" give them, the chunk width (tiles), 1 when the family
+ * refuses odd leading dimensions, 1 when the product is a candidate for the tile route before the layout is asked for. */
+#define SCANRS_SPMM_TILES_AVAILABLE 1u
+#define SCANRS_SPMM_NO_VALUES_ROOM 2u
+int scanrs_host_spmm_route(const double *options, uint64_t n_outer, uint64_t n_inner, uint64_t nnz, uint32_t l, uint32_t ldx,
+                           uint32_t n_links, const int *kinds, const int *a_outer, uint32_t flags, uint64_t *out);
 
 /* ---- 10x HDF5 ingestion (hdf5-io/src/matrix.rs, analysis.rs). Host-side; no device needed.
  * The files are parsed by the library's own reader (csrc/h5lite.cpp) — no libhdf5 dependency. Failures are

@@ -1571,6 +1571,32 @@ def host_col_moments_plan(max_count: int, links, n_outer: int, n_inner: int, n_w
     return bool(acc.value), int(e1.value), int(e2.value)
 
 
+# kernel families of a sparse product (counter "spmm_route", host_spmm_route; SCANRS_SPMM_* of scanrs_amd.h)
+SPMM_TILES, SPMM_GATHER2D, SPMM_GATHER2D_F32, SPMM_SLICE_WALK, SPMM_SPMV2D, SPMM_SPMV_LDS, SPMM_SPMV, SPMM_GATHER = range(1, 9)
+SPMM_SLIVER = 1 << 16
+SPMM_ROUTE_OPTIONS = ("spmm_path", "panel_precision", "tile_auto", "tile_k", "tile_s", "tile_t", "tile_b", "tile_ku", "tile_dense", "tile_builder",
+                      "blocked_min_nnz", "slice_walk", "spmv_lds", "spmv_row_table", "spmm_order", "materialize", "tile_wtab", "tile_fold")
+_SPMM_ROUTE_DEFAULTS = (0, 0, 1, 2, 32, 48, 4, 1, 1, 1, 1 << 22, 1, 1, 1, 1, 1, 1, 1)
+
+
+def host_spmm_route(n_outer: int, n_inner: int, nnz: int, l: int, ldx: int, links=(), tiles_available: bool = False, values_room: bool = True,
+                    **options):
+    """The route of a sparse product on the host (`scanrs_host_spmm_route`; scan-rs_amd/csrc/spmm_route.hpp, the source kernels.hip
+    decides by). `links`: the map as the walked copy sees it, `(kind, a_outer)` per link; `options`: any of SPMM_ROUTE_OPTIONS, the
+    library's defaults otherwise. Returns (family, form, chunks, chunk_width, even_ld, tile_candidate) as scanrs_amd.h documents."""
+    unknown = set(options) - set(SPMM_ROUTE_OPTIONS)
+    if unknown:
+        raise ScanrsError(6, f"unknown options {sorted(unknown)}")
+    vals = [float(options.get(k, d)) for k, d in zip(SPMM_ROUTE_OPTIONS, _SPMM_ROUTE_DEFAULTS)]
+    n = len(links)
+    opts = (ctypes.c_double * len(vals))(*vals)
+    ka, oa = (ctypes.c_int * max(n, 1))(*[int(k) for k, _ in links]), (ctypes.c_int * max(n, 1))(*[int(bool(a)) for _, a in links])
+    out = (ctypes.c_uint64 * 6)()
+    _check(_lib.scanrs_host_spmm_route(opts, ctypes.c_uint64(int(n_outer)), ctypes.c_uint64(int(n_inner)), ctypes.c_uint64(int(nnz)), ctypes.c_uint32(int(l)),
+                                       ctypes.c_uint32(int(ldx)), ctypes.c_uint32(n), ka, oa, ctypes.c_uint32((1 if tiles_available else 0) | (0 if values_room else 2)), out))
+    return tuple(int(v) for v in out)
+
+
 def knn_device(d_points: int, n: int, ld: int, d: int, k: int):
     """`nn::knn` on scores that already live in device memory (e.g. PcaResultDevice.d_v / ld_v): (n x k) u32 host array."""
     out = np.zeros((n, k), dtype=np.uint32)
@@ -1718,7 +1744,7 @@ EXPORTED_SYMBOLS = [
     "scanrs_mat_select_rows_sharded", "scanrs_mat_select_cols_sharded", "scanrs_mat_partition_on_thresholds_sharded", "scanrs_mat_shard_info",
     "scanrs_multi_shape", "scanrs_multi_to_csmat", "scanrs_multi_select_rows", "scanrs_multi_select_cols", "scanrs_multi_partition_on_thresholds",
     "scanrs_mat_to_adaptive", "scanrs_adaptive_export_info", "scanrs_adaptive_export_vecs", "scanrs_adaptive_export_free",
-    "scanrs_host_choose_storage", "scanrs_host_col_moments_plan",
+    "scanrs_host_choose_storage", "scanrs_host_col_moments_plan", "scanrs_host_spmm_route",
     "scanrs_mat_sum_rows_u64", "scanrs_mat_sum_rows_f64", "scanrs_mat_sum_cols_u64", "scanrs_mat_sum_cols_f64", "scanrs_mat_sum_rows_dual_u64",
     "scanrs_mat_sum_rows_dual_f64", "scanrs_mat_mean_rows", "scanrs_mat_mean_var_rows", "scanrs_mat_var_axis",
     "scanrs_mat_sum_rows_u64_sharded", "scanrs_mat_sum_rows_f64_sharded", "scanrs_mat_sum_cols_u64_sharded", "scanrs_mat_sum_cols_f64_sharded",

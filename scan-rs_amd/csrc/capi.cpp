@@ -7,6 +7,7 @@
 
 #include "common.hpp"
 #include "col_moments_plan.hpp"
+#include "spmm_route.hpp"
 #include "shard_exchange.hpp"
 
 namespace scanrs {
@@ -99,12 +100,6 @@ static SparseCopy &copy_outer_view_rows(scanrs_mat *m, bool view_rows) {
     return m->st->copy_with_outer_rows(view_rows != m->transposed);
 }
 
-// does the product V * X (transpose: V^T * X) of this handle currently run through the hybrid tile product?
-bool mat_tiles_ready(scanrs_mat *m, bool transpose) {
-    SparseCopy &cp = copy_outer_view_rows(m, !transpose);
-    return cp.tiles != nullptr && (m->st->spmm_path == 3 || (m->st->spmm_path == 0 && m->st->tile_auto && m->st->panel_precision == 0));
-}
-
 // A solver alternates V x and V^T y. What the SECOND product of its first iteration needs — the transposed copy when it does not
 // exist yet, and that orientation's tile layout when the auto path will take it — is built by a helper thread on a stream of its
 // own while the main thread builds the first product's layout and runs the first pass (the only call Cell Ranger ever makes is the
@@ -119,8 +114,15 @@ void prepare_second_orientation(scanrs_mat *m, bool transpose_second, bool solve
     const bool second_outer_rows = (!transpose_second) != m->transposed; // the base-matrix dimension the second product's outer vectors run over
     const bool second_is_primary = second_outer_rows == (st.storage == SCANRS_CSR);
     SparseCopy *second = second_is_primary ? &st.primary : &st.other, *first = second_is_primary ? &st.other : &st.primary;
-    const bool tiles_wanted = st.spmm_path == 0 && st.tile_auto && st.panel_precision == 0 && (st.tile_hint > 0 || solver_follows) &&
-                              st.primary.nnz >= std::max<uint64_t>(st.blocked_min_nnz, 1ull << 24);
+    // Against tiles_static_candidate, the launch's own test:
+    //  - the auto path only: a forced path 3 builds its layout inside the product, whatever the overflow, and the helper's
+    //    tile_layout_build_auto would apply the overflow limit to it;
+    //  - a solver is running or follows (this site's own term: one product alone builds nothing ahead);
+    //  - the size of `primary` stands for both copies (the transposed one may not exist yet; the nonzeros are the same);
+    //  - no tile_shape_ok and no tile_visits_fit: the helper's tile_layout_build_auto tests both before it builds anything;
+    //  - no panel terms: the widths are the solver's.
+    const SpmmOptions o = spmm_options(st);
+    const bool tiles_wanted = path_auto(o) && o.tile_auto && f64_panels(o) && (st.tile_hint > 0 || solver_follows) && tile_auto_size(o, st.primary.nnz);
     auto exists = [&](const SparseCopy *c) { return c == &st.primary || st.has_other; };
     // the first product's layout too (the helper builds it FIRST, alone on the device, while the caller normalizes; the transposition
     // then runs beside the first pass, which is bound by the vector pipe, not by memory) — but only from normalize on: inside a solver
@@ -1197,6 +1199,29 @@ int scanrs_host_col_moments_plan(uint32_t max_count, uint32_t n_links, const int
         *e2 = p.e2;
     });
 }
+int scanrs_host_spmm_route(const double *options, uint64_t n_outer, uint64_t n_inner, uint64_t nnz, uint32_t l, uint32_t ldx, uint32_t n_links,
+                           const int *kinds, const int *a_outer, uint32_t flags, uint64_t *out) {
+    return guard([&] {
+        if (!options || !out || (n_links && (!kinds || !a_outer))) fail(SCANRS_ERR_ARGUMENT, "null argument");
+        if (n_links > (uint32_t)MAX_OPS) fail(SCANRS_ERR_ARGUMENT, "spmm_route: at most %d links", MAX_OPS);
+        SpmmQuery q;
+        SpmmOptions &o = q.o;
+        int i = 0;
+        o.spmm_path = (int)options[i++], o.panel_precision = (int)options[i++], o.tile_auto = (int)options[i++];
+        o.tile_k = (uint32_t)options[i++], o.tile_s = (uint32_t)options[i++], o.tile_t = (uint32_t)options[i++], o.tile_b = (uint32_t)options[i++];
+        o.tile_ku = (uint32_t)options[i++], o.tile_dense = (int)options[i++], o.tile_builder = (int)options[i++];
+        o.blocked_min_nnz = (uint64_t)options[i++];
+        o.slice_walk = (int)options[i++], o.spmv_lds = (int)options[i++], o.spmv_row_table = (int)options[i++], o.spmm_order = (int)options[i++];
+        o.materialize = (int)options[i++], o.tile_wtab = (int)options[i++], o.tile_fold = (int)options[i++];
+        q.n_outer = n_outer, q.n_inner = n_inner, q.nnz = nnz, q.l = l, q.ldx = ldx;
+        q.n_links = (int)n_links;
+        for (uint32_t j = 0; j < n_links; j++) q.kind[j] = kinds[j], q.a_outer[j] = a_outer[j] != 0;
+        q.values_room = (flags & SCANRS_SPMM_NO_VALUES_ROOM) == 0;
+        const SpmmRoute r = spmm_route(q, (flags & SCANRS_SPMM_TILES_AVAILABLE) != 0);
+        out[0] = (uint64_t)r.family, out[1] = r.form_bits(), out[2] = r.chunk_bits(), out[3] = r.family == SPMM_TILES ? r.chunk_width : 0, out[4] = r.even_ld ? 1 : 0;
+        out[5] = tiles_static_candidate(q) ? 1 : 0;
+    });
+}
 int scanrs_debug_knn_filter(const double *queries, uint64_t n_q, const double *points, uint64_t n_p, uint32_t d, const double *tau,
                             uint64_t stride, uint32_t *cnt, uint32_t *cand) {
     return guard([&] {
@@ -1534,7 +1559,13 @@ int scanrs_mat_get_counter(scanrs_mat *m, const char *key, uint64_t *value) {
                 *value = bits(d.cmax_dense);
             else
                 fail(SCANRS_ERR_ARGUMENT, "unknown counter '%s'", key);
-        } else if (k == "partition_rounds") // rounds of the last scanrs_mat_partition_on_thresholds[_sharded] on this handle
+        } else if (k == "spmm_route") // the last sparse product on this handle (Storage::SpmmDecision): its kernel family, SCANRS_SPMM_* ...
+            *value = m->st->spmm.family;
+        else if (k == "spmm_form") // ... the form within the family ...
+            *value = m->st->spmm.form;
+        else if (k == "spmm_chunks") // ... and its column chunks, SCANRS_SPMM_SLIVER set when a last narrow one went to the plain gather
+            *value = m->st->spmm.chunks;
+        else if (k == "partition_rounds") // rounds of the last scanrs_mat_partition_on_thresholds[_sharded] on this handle
             *value = m->st->partition_rounds;
         else if (k == "partition_allreduces") // ... and its exchange steps (an unsharded handle: 0)
             *value = m->st->partition_allreduces;

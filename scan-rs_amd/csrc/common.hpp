@@ -440,6 +440,11 @@ struct Storage {
     int gemm_direct = 1;                  // dense X W: operands straight from memory into the MFMA registers (0: the LDS-tiled kernels)
     double reuse_cmax = 1e5;              // svd_bk: coefficient bound above which a projection column is recomputed directly
     int materialize = 1;                  // keep the map prefix's values per nonzero on the short-outer copy (SCANRS_MATERIALIZE=0: off)
+    // the route of the last sparse product on this handle (host-side stores by launch_spmm_f64, overwritten on every call;
+    // scanrs_mat_get_counter "spmm_route" / "spmm_form" / "spmm_chunks", packed as scanrs_amd.h documents; spmm_route.hpp)
+    struct SpmmDecision {
+        uint64_t family = 0, form = 0, chunks = 0;
+    } spmm;
     ~Storage();
     // the copy whose outer dimension is the base matrix's rows (true) or cols (false)
     SparseCopy &copy_with_outer_rows(bool outer_rows);
@@ -549,9 +554,7 @@ void launch_spmm_f64(Storage &st, SparseCopy &cp, const DevMap &map, const doubl
                      double *out, uint32_t ldo, const double *off_a, uint32_t rank, const double *off_w, uint32_t ldw);
 void launch_spmm_u32(Storage &st, const SparseCopy &cp, const uint32_t *X, uint32_t ldx, uint32_t l, uint32_t *out,
                      uint32_t ldo);
-// tiles.hip
-bool spmm_tiles_ok(const Storage &st, const SparseCopy &cp, uint32_t ldx, uint32_t l);
-bool tile_shape_ok(uint32_t K, uint32_t S, uint32_t T, uint32_t B);
+// tiles.hip (whether a product is a candidate for them at all: spmm_route.hpp)
 bool spmm_tiles_auto(Storage &st, SparseCopy &cp, const DevMap &map);
 // the structure of the layout (no weights) when the auto path would take it for this copy: built on stream s; false when the copy
 // is not eligible or its layout is not worth having (then remembered in cp.tile_rejected_shape)
@@ -658,7 +661,6 @@ void jump_tables_prefetch(); // starts the background computation of the start p
 // operator-level helpers shared by capi.cpp and solver.cpp
 // out[rows_v x l] = V * X  (transpose: out[cols_v x l] = V^T * X), offsets and shard reduction included.
 void mat_apply(scanrs_mat *m, bool transpose, const double *dX, uint32_t ldx, uint32_t l, double *dOut, uint32_t ldo);
-bool mat_tiles_ready(scanrs_mat *m, bool transpose);
 void prepare_second_orientation(scanrs_mat *m, bool transpose_second, bool solver_follows = false);
 void sort_outer_vectors(Storage &st, SparseCopy &cp);
 void launch_scale_rows(Storage &st, const double *X, uint32_t ldx, uint64_t rows, uint32_t l, const double *a, double *Xs);

@@ -13,6 +13,7 @@
 #include "common.hpp"
 #include "device_map.hpp"
 #include "col_moments_plan.hpp"
+#include "spmm_route.hpp"
 
 #include <algorithm>
 #include <rocprim/rocprim.hpp>
@@ -1598,36 +1599,16 @@ static uint32_t count_at_least(const SparseCopy &cp, uint64_t min_len) {
 // (8 B per nonzero beside the 8 B of index + count) and the products apply only the trailing links, which are uniform
 // over an outer vector. Identity is by MapOp id (never reused), so a re-normalized handle or another view never sees
 // stale values. Same arithmetic in the same order as the lazy evaluation: results are bit-identical.
-static int fvals_prefix_len(const DevMap &map) {
-    int n = map.n;
-    while (n > 0 && map.ops[n - 1].kind == OP_SCALE_AXIS && map.ops[n - 1].a_outer) n--;
-    return n;
-}
-static bool fvals_wanted(Storage &st, const SparseCopy &cp, const DevMap &map, int n) {
-    if (!st.materialize || n <= 0 || n > MAX_OPS || cp.n_outer >= cp.n_inner || cp.nnz < st.blocked_min_nnz) return false;
-    bool inner_indexed = false;
-    for (int i = 0; i < n; i++)
-        inner_indexed = inner_indexed || (map.ops[i].a && !map.ops[i].a_outer) || (map.ops[i].b && !map.ops[i].b_outer);
-    if (!inner_indexed) return false;
+// (which links, and when the values are wanted: values_prefix_len / values_wanted / values_wanted_for_alu, spmm_route.hpp)
+// the values exist already, or the device has room for them beside the solver's panels
+static bool fvals_room(const SparseCopy &cp) {
     if (cp.fvals.n == cp.nnz) return true; // already allocated
     size_t free_b = 0, total_b = 0;
     if (hipMemGetInfo(&free_b, &total_b) != hipSuccess) return false;
-    return free_b > cp.nnz * 8 + (size_t(8) << 30); // leave room for the solver's panels
-}
-// the same store on a copy of any shape when the reason is arithmetic, not a gather: the chain holds a logarithm (or a
-// residual map) and the caller is a product that runs many times on a bandwidth budget (the Ix1 products of IRLBA)
-static bool fvals_wanted_for_alu(Storage &st, const SparseCopy &cp, const DevMap &map, int n) {
-    if (!st.materialize || n <= 0 || n > MAX_OPS || cp.nnz < st.blocked_min_nnz) return false;
-    bool heavy = false;
-    for (int i = 0; i < n; i++) {
-        const int k = map.ops[i].kind;
-        heavy = heavy || k == OP_LN_1P || k == OP_LOG2_1P || k == OP_LOG10_1P || k == OP_BINOM_DEV || k == OP_BINOM_PEARSON;
-    }
-    if (!heavy) return false;
-    if (cp.fvals.n == cp.nnz) return true;
-    size_t free_b = 0, total_b = 0;
-    if (hipMemGetInfo(&free_b, &total_b) != hipSuccess) return false;
     return free_b > cp.nnz * 8 + (size_t(8) << 30);
+}
+static bool fvals_wanted(Storage &st, const SparseCopy &cp, const DevMap &map, int n) {
+    return values_wanted(spmm_query(st, cp, map, 0, 0), n) && fvals_room(cp);
 }
 static bool fvals_match(const SparseCopy &cp, const DevMap &map, int n) {
     if (cp.fsig_n != n || cp.fvals.n != cp.nnz) return false;
@@ -1666,20 +1647,6 @@ static const double *ensure_fvals(Storage &st, SparseCopy &cp, const DevMap &map
 }
 
 // ---- slice walk (slice_walk_kernel): eligibility and launch --------------------------------------------------------
-// chain shapes the slice walk evaluates: no inner-indexed link at all, or exactly one — a ScaleAxis in first position
-static bool slice_walk_chain(const DevMap &map, int from, bool &lazy_scale) {
-    lazy_scale = false;
-    for (int i = from; i < map.n; i++) {
-        const bool inner = (map.ops[i].a && !map.ops[i].a_outer) || (map.ops[i].b && !map.ops[i].b_outer);
-        if (!inner) continue;
-        if (i == 0 && from == 0 && map.ops[0].kind == OP_SCALE_AXIS && !map.ops[0].a_outer)
-            lazy_scale = true;
-        else
-            return false;
-    }
-    return true;
-}
-
 // MODE 1: out_a = sums, out_b = sums of squares (may be null), fout optional.  MODE 0: out_a[row * ld_a] = product (+ offset)
 template <int MODE>
 static void launch_slice_walk(Storage &st, SparseCopy &cp, const DevMap &map, const double *fvals, int fstart, bool lazy_scale,
@@ -1725,9 +1692,9 @@ static void launch_spmm_2d(Storage &st, SparseCopy &cp, const DevMap &map, const
     lc = (lc + 1u) & ~1u;
     // Longest-first pays when a launch is only a few rounds of waves (33 k genes = 1 round of the chip's 8192 wave slots:
     // -8 % per step); with ~10^6 vectors there is no tail to hide and the permuted rows only scatter the streaming reads (+3 %).
-    const bool ordered = st.spmm_order == 2 || (st.spmm_order == 1 && cp.n_outer <= 65536u);
+    const bool ordered = launch_longest_first(spmm_options(st), cp.n_outer);
     if (ordered) ensure_order(st, cp);
-    const int fstart = fvals_prefix_len(map);
+    const int fstart = values_prefix_len(spmm_query(st, cp, map, l, ldx));
     const double *fvals = fvals_wanted(st, cp, map, fstart) ? ensure_fvals(st, cp, map, fstart) : nullptr;
     const dim3 block(256);
     for (uint32_t c0 = 0; c0 < l; c0 += lc) {
@@ -1953,131 +1920,111 @@ void launch_scale_rows(Storage &st, const double *X, uint32_t ldx, uint64_t rows
     SCANRS_HIP(hipGetLastError());
 }
 
+// Ix1 / Ix2 product against a vector that does not fit an XCD's L2: walked in 2 MB slices (base tiles of 1024 positions x ldx x 8 B)
+static void launch_spmv2d(Storage &st, SparseCopy &cp, const DevMap &map, bool fuse, const double *X, uint32_t ldx, uint32_t l, double *out,
+                          uint32_t ldo, const double *off_a, uint32_t rank, const double *off_w, uint32_t ldw) {
+    const uint32_t nb = ensure_bounds(st, cp);
+    const uint32_t m = std::max(1u, 256u / ldx);
+    const uint32_t steps = (nb + m - 1u) / m;
+    const bool ordered = launch_longest_first(spmm_options(st), cp.n_outer);
+    if (ordered) ensure_order(st, cp);
+    const dim3 grid((unsigned)((cp.n_outer + 3) / 4)), block(256);
+    const double bytes = ((double)cp.nnz * 8.0 + (double)(cp.n_outer + 1) * 8.0 + (double)(cp.n_inner + cp.n_outer) * l * 8.0) / steps;
+    const double *Xk = X;
+    if (fuse) { // the map's first link reads a[inner] per nonzero (the barcode scale): paired with x[inner] in one 16-byte slot
+        double *z = st.scratch.get<double>("spmv_z", (size_t)cp.n_inner * 2);
+        hipLaunchKernelGGL(interleave_kernel, grid1(cp.n_inner, 256), block, 0, st.stream, X, map.ops[0].a, cp.n_inner, z);
+        Xk = z;
+    }
+    for (uint32_t sidx = 0; sidx < steps; sidx++) {
+        const uint32_t b0 = sidx * m, b1 = std::min(nb, b0 + m);
+        ProfScope ps(st, cp.n_outer >= cp.n_inner ? "spmv2d_kernel/long-outer" : "spmv2d_kernel/short-outer", bytes);
+        hipLaunchKernelGGL(spmv2d_kernel, grid, block, 0, st.stream, cp.indptr.p, cp.indices.p, cp.values.p, cp.bounds.p, nb, b0, b1,
+                           sidx == 0 ? 1 : 0, sidx + 1 == steps ? 1 : 0, cp.n_outer, ordered ? cp.order.p : nullptr, map, fuse ? 1 : 0, Xk,
+                           ldx, l, out, ldo, off_a, rank, off_w, ldw);
+    }
+    SCANRS_HIP(hipGetLastError());
+}
+
+// Ix1 product of many outer vectors against a vector of 64 KB .. 1.1 MB: LDS-staged parts. VM 0: the map per nonzero, 1: the
+// materialized values fv of its first fstart links, 2: a table per row (a chain of the count and the outer position alone)
+template <int VM>
+static void launch_spmv_lds(Storage &st, SparseCopy &cp, const DevMap &map, const double *fv, int fstart, const double *X, uint32_t ldx,
+                            double *out, uint32_t ldo, const double *off_a, uint32_t rank, const double *off_w, uint32_t ldw) {
+    const uint32_t nb = ensure_bounds(st, cp);
+    const uint32_t n_parts = (uint32_t)((cp.n_inner + SPMV_LDS_PART - 1) / SPMV_LDS_PART);
+    const uint32_t tiles_per_part = (uint32_t)(((cp.n_inner + n_parts - 1) / n_parts + (1u << BT_SHIFT) - 1) >> BT_SHIFT);
+    const size_t shmem = ((size_t)tiles_per_part << BT_SHIFT) * 8;
+    int dev = 0, n_cu = 256;
+    (void)hipGetDevice(&dev);
+    (void)hipDeviceGetAttribute(&n_cu, hipDeviceAttributeMultiprocessorCount, dev);
+    const uint32_t n_blocks = (uint32_t)std::min<uint64_t>((uint64_t)n_cu * 4u, (cp.n_outer + 15) / 16);
+    const uint64_t rows_per_block = (cp.n_outer + n_blocks - 1) / n_blocks;
+    ProfScope ps(st, "spmv_lds_kernel/long-outer", (double)cp.nnz * (fv ? 12.0 : 8.0) + (double)(cp.n_outer + 1) * 8.0 + (double)(cp.n_inner + cp.n_outer) * 8.0);
+    // per device, and handles of one process may live on different devices: set on every use (a cheap call); beside 8 KB of static LDS
+    SCANRS_HIP(hipFuncSetAttribute((const void *)spmv_lds_kernel<VM>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)shmem));
+    hipLaunchKernelGGL(spmv_lds_kernel<VM>, dim3(n_blocks), dim3(1024), shmem, st.stream, cp.indptr.p, cp.indices.p, cp.values.p, cp.bounds.p,
+                       nb, tiles_per_part, n_parts, cp.n_outer, rows_per_block, map, X, ldx, cp.n_inner, out, ldo, off_a, rank, off_w, ldw, fv,
+                       fstart);
+    SCANRS_HIP(hipGetLastError());
+}
+
+// Ix1 / Ix2 product, one wave per item (a run of an outer vector's nonzeros), long vectors through the slab
+static void launch_spmv(Storage &st, SparseCopy &cp, const DevMap &map, const double *X, uint32_t ldx, uint32_t l, double *out, uint32_t ldo,
+                        const double *off_a, uint32_t rank, const double *off_w, uint32_t ldw) {
+    double *slab = nullptr;
+    if (cp.n_slab) slab = st.scratch.get<double>("spmm_slab", (size_t)cp.n_slab * ldo);
+    const dim3 grid((cp.n_items + 3u) / 4u), block(256);
+    {
+        ProfScope ps(st, cp.n_outer >= cp.n_inner ? "spmv_kernel/long-outer" : "spmv_kernel/short-outer", (double)cp.nnz * 8.0 + (double)(cp.n_outer + 1) * 8.0 + (double)(cp.n_inner + cp.n_outer) * l * 8.0);
+        hipLaunchKernelGGL(spmv_kernel, grid, block, 0, st.stream, cp.indices.p, cp.values.p, cp.items.p, cp.n_items, map, X, ldx,
+                           l, out, ldo, slab, off_a, rank, off_w, ldw);
+    }
+    if (cp.n_multi)
+        hipLaunchKernelGGL((slab_reduce_kernel<double, 1>), dim3((cp.n_multi + 3u) / 4u), block, 0, st.stream, cp.multi.p, cp.n_multi,
+                           slab, l, out, ldo, off_a, rank, off_w, ldw);
+    SCANRS_HIP(hipGetLastError());
+}
+
+// The route is decided in spmm_route.hpp; here it is asked for, recorded (Storage::SpmmDecision) and launched.
 void launch_spmm_f64(Storage &st, SparseCopy &cp, const DevMap &map, const double *X, uint32_t ldx, uint32_t l,
                      double *out, uint32_t ldo, const double *off_a, uint32_t rank, const double *off_w, uint32_t ldw) {
-    // hybrid: LDS-staged tiles + gather of the overflow part (tiles.hip). Panels wider than the 104 columns a ring row holds go
-    // through it in column chunks of equal width (200 -> 2 x 100, 500 -> 5 x 100): a chunk pass costs what a 100-column pass
-    // costs, against two gather instructions per nonzero for every 128 columns of the blocked gather.
-    {
-        const uint32_t n_chunks = (l + 103u) / 104u;
-        const uint32_t lc = n_chunks ? even_up((l + n_chunks - 1u) / n_chunks) : 0u;
-        if (l >= 16 && lc >= 16 && spmm_tiles_ok(st, cp, ldx, std::min(lc, l)) && tile_shape_ok(st.tile_k, st.tile_s, st.tile_t, st.tile_b) &&
-            (st.spmm_path == 3 || (st.spmm_path == 0 && st.panel_precision == 0 && spmm_tiles_auto(st, cp, map)))) {
-            for (uint32_t c0 = 0; c0 < l; c0 += lc) {
-                const uint32_t lw = std::min(lc, l - c0);
-                if (lw < 16u) { // a last sliver narrower than the tile kernel takes: the plain gather serves it
-                    launch_spmm_t<double>(st, cp, map, X + c0, ldx, lw, out + c0, ldo, off_a, rank, off_w ? off_w + c0 : nullptr, ldw);
-                    continue;
-                }
-                launch_spmm_tiles(st, cp, map, X + c0, ldx, lw, out + c0, ldo, off_a, rank, off_w ? off_w + c0 : nullptr, ldw);
-            }
-            return;
-        }
+    SpmmQuery q = spmm_query(st, cp, map, l, ldx);
+    // the one impure step of the tile route: on the auto path the layout has to exist or be worth building now (tiles.hip)
+    const bool tiles = tiles_static_candidate(q) && (path_forces_tiles(q.o) || spmm_tiles_auto(st, cp, map));
+    SpmmRoute r = spmm_route(q, tiles);
+    if (r.materialized && !fvals_room(cp)) { // no room for the values the route counted on: decided again without them
+        q.values_room = false;
+        r = spmm_route(q, tiles);
     }
-    const bool want_2d = st.spmm_path == 2 || st.spmm_path == 3 || (st.spmm_path == 0 && cp.nnz >= st.blocked_min_nnz && l >= 16);
-    if (want_2d && l > 0 && cp.n_outer > 0 && cp.n_inner > 0) {
-        if (st.panel_precision == 1)
-            launch_spmm_2d_f32(st, cp, map, X, ldx, l, out, ldo, off_a, rank, off_w, ldw);
-        else
-            launch_spmm_2d(st, cp, map, X, ldx, l, out, ldo, off_a, rank, off_w, ldw);
-        return;
-    }
-    if (l <= 2 && l > 0 && cp.n_outer > 0) {
-        if ((ldx & 1u) || (ldo & 1u)) fail(SCANRS_ERR_ARGUMENT, "panel leading dimensions must be even");
-        const bool long_outer = cp.n_outer >= cp.n_inner;
-        if (st.spmm_path != 1 && st.slice_walk && l == 1 && !long_outer && cp.nnz >= st.blocked_min_nnz && cp.n_inner >= (1ull << 19)) {
-            // few long vectors against an inner-indexed vector far beyond L2: slices of it (and of the barcode scale, unless
-            // the mapped values are materialized) staged in LDS
-            const int fstart = fvals_prefix_len(map);
-            bool lazy = false;
-            const double *fv = fvals_wanted(st, cp, map, fstart) ? ensure_fvals(st, cp, map, fstart) : nullptr;
-            if (fv ? slice_walk_chain(map, fstart, lazy) : slice_walk_chain(map, 0, lazy)) {
-                launch_slice_walk<0>(st, cp, map, fv, fstart, lazy, X, ldx, out, ldo, nullptr, nullptr, off_a, rank, off_w, ldw,
-                                     "slice_walk_spmv/short-outer",
-                                     (double)cp.nnz * (fv ? 12.0 : 8.0) + (double)(cp.n_outer + 1) * 8.0 + (double)(cp.n_inner + cp.n_outer) * 8.0);
-                return;
-            }
-        }
-        if (st.spmm_path != 1 && cp.nnz >= st.blocked_min_nnz && cp.n_inner >= (1ull << 19)) {
-            // the vector does not fit an XCD's L2: walk it in 2 MB slices (base tiles of 1024 positions x ldx x 8 B)
-            const uint32_t nb = ensure_bounds(st, cp);
-            const uint32_t m = std::max(1u, 256u / ldx);
-            const uint32_t steps = (nb + m - 1u) / m;
-            const bool ordered = st.spmm_order == 2 || (st.spmm_order == 1 && cp.n_outer <= 65536u);
-            if (ordered) ensure_order(st, cp);
-            const dim3 grid((unsigned)((cp.n_outer + 3) / 4)), block(256);
-            const double bytes = ((double)cp.nnz * 8.0 + (double)(cp.n_outer + 1) * 8.0 + (double)(cp.n_inner + cp.n_outer) * l * 8.0) / steps;
-            // the map's first link reads a[inner] per nonzero (the barcode scale): pair it with x[inner] in one 16-byte slot
-            const bool fuse = l == 1 && ldx == 2 && map.n >= 1 && map.ops[0].kind == OP_SCALE_AXIS && !map.ops[0].a_outer;
-            const double *Xk = X;
-            if (fuse) {
-                double *z = st.scratch.get<double>("spmv_z", (size_t)cp.n_inner * 2);
-                hipLaunchKernelGGL(interleave_kernel, grid1(cp.n_inner, 256), block, 0, st.stream, X, map.ops[0].a, cp.n_inner, z);
-                Xk = z;
-            }
-            for (uint32_t sidx = 0; sidx < steps; sidx++) {
-                const uint32_t b0 = sidx * m, b1 = std::min(nb, b0 + m);
-                ProfScope ps(st, long_outer ? "spmv2d_kernel/long-outer" : "spmv2d_kernel/short-outer", bytes);
-                hipLaunchKernelGGL(spmv2d_kernel, grid, block, 0, st.stream, cp.indptr.p, cp.indices.p, cp.values.p, cp.bounds.p, nb, b0, b1,
-                                   sidx == 0 ? 1 : 0, sidx + 1 == steps ? 1 : 0, cp.n_outer, ordered ? cp.order.p : nullptr, map, fuse ? 1 : 0, Xk,
-                                   ldx, l, out, ldo, off_a, rank, off_w, ldw);
-            }
-            SCANRS_HIP(hipGetLastError());
-            return;
-        }
-        if (st.spmv_lds && l == 1 && st.spmm_path != 1 && cp.nnz >= st.blocked_min_nnz && cp.n_outer >= (1ull << 16) && cp.n_inner >= 8192 &&
-            cp.n_inner <= 8u * 18432u) {
-            // vector of 64 KB .. 1.1 MB against many outer vectors: LDS-staged parts
-            const uint32_t nb = ensure_bounds(st, cp);
-            const uint32_t n_parts = (uint32_t)((cp.n_inner + 18431) / 18432);
-            const uint32_t tiles_per_part = (uint32_t)(((cp.n_inner + n_parts - 1) / n_parts + (1u << BT_SHIFT) - 1) >> BT_SHIFT);
-            const size_t shmem = ((size_t)tiles_per_part << BT_SHIFT) * 8;
-            // per device, and handles of one process may live on different devices: set on every use (a cheap call)
-
-            int dev = 0, n_cu = 256;
-            (void)hipGetDevice(&dev);
-            (void)hipDeviceGetAttribute(&n_cu, hipDeviceAttributeMultiprocessorCount, dev);
-            const uint32_t n_blocks = (uint32_t)std::min<uint64_t>((uint64_t)n_cu * 4u, (cp.n_outer + 15) / 16);
-            const uint64_t rows_per_block = (cp.n_outer + n_blocks - 1) / n_blocks;
-            const int fstart = fvals_prefix_len(map);
-            // a chain of the count and the outer position alone: looked up by count from a table the wave makes per row — no materialized values
-            bool outer_only = st.spmv_row_table != 0 && map.n > 0 && map_is_simple(map);
-            for (int i = 0; i < map.n && outer_only; i++) outer_only = map.ops[i].kind != OP_SCALE_AXIS || map.ops[i].a_outer;
-            const double *fv = (!outer_only && fvals_wanted_for_alu(st, cp, map, fstart)) ? ensure_fvals(st, cp, map, fstart) : nullptr;
-            ProfScope ps(st, "spmv_lds_kernel/long-outer", (double)cp.nnz * (fv ? 12.0 : 8.0) + (double)(cp.n_outer + 1) * 8.0 + (double)(cp.n_inner + cp.n_outer) * 8.0);
-#define SCANRS_SPMV_LDS(VM)                                                                                                                       \
-    do {                                                                                                                                          \
-        /* per device, and handles of one process may live on different devices: set on every use (a cheap call); beside 8 KB of static LDS */    \
-        SCANRS_HIP(hipFuncSetAttribute((const void *)spmv_lds_kernel<VM>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)shmem));                \
-        hipLaunchKernelGGL(spmv_lds_kernel<VM>, dim3(n_blocks), dim3(1024), shmem, st.stream, cp.indptr.p, cp.indices.p, cp.values.p, cp.bounds.p, \
-                           nb, tiles_per_part, n_parts, cp.n_outer, rows_per_block, map, X, ldx, cp.n_inner, out, ldo, off_a, rank, off_w, ldw, fv, \
-                           fstart);                                                                                                               \
-    } while (0)
-            if (outer_only)
-                SCANRS_SPMV_LDS(2);
-            else if (fv)
-                SCANRS_SPMV_LDS(1);
+    st.spmm = {(uint64_t)r.family, r.form_bits(), r.chunk_bits()};
+    if (r.even_ld && ((ldx & 1u) || (ldo & 1u))) fail(SCANRS_ERR_ARGUMENT, "panel leading dimensions must be even");
+    const double *fv = r.materialized ? ensure_fvals(st, cp, map, r.fstart) : nullptr;
+    switch (r.family) {
+    case SPMM_TILES:
+        // hybrid: LDS-staged tiles + gather of the overflow part (tiles.hip). A chunk pass costs what a 100-column pass costs,
+        // against two gather instructions per nonzero for every 128 columns of the blocked gather.
+        for (uint32_t c0 = 0; c0 < l; c0 += r.chunk_width) {
+            const uint32_t lw = std::min(r.chunk_width, l - c0);
+            if (r.sliver && c0 + lw == l) // a last sliver narrower than the tile kernel takes: the plain gather serves it
+                launch_spmm_t<double>(st, cp, map, X + c0, ldx, lw, out + c0, ldo, off_a, rank, off_w ? off_w + c0 : nullptr, ldw);
             else
-                SCANRS_SPMV_LDS(0);
-#undef SCANRS_SPMV_LDS
-            SCANRS_HIP(hipGetLastError());
-            return;
+                launch_spmm_tiles(st, cp, map, X + c0, ldx, lw, out + c0, ldo, off_a, rank, off_w ? off_w + c0 : nullptr, ldw);
         }
-        double *slab = nullptr;
-        if (cp.n_slab) slab = st.scratch.get<double>("spmm_slab", (size_t)cp.n_slab * ldo);
-        const dim3 grid((cp.n_items + 3u) / 4u), block(256);
-        {
-            ProfScope ps(st, long_outer ? "spmv_kernel/long-outer" : "spmv_kernel/short-outer", (double)cp.nnz * 8.0 + (double)(cp.n_outer + 1) * 8.0 + (double)(cp.n_inner + cp.n_outer) * l * 8.0);
-            hipLaunchKernelGGL(spmv_kernel, grid, block, 0, st.stream, cp.indices.p, cp.values.p, cp.items.p, cp.n_items, map, X, ldx,
-                               l, out, ldo, slab, off_a, rank, off_w, ldw);
-        }
-        if (cp.n_multi)
-            hipLaunchKernelGGL((slab_reduce_kernel<double, 1>), dim3((cp.n_multi + 3u) / 4u), block, 0, st.stream, cp.multi.p, cp.n_multi,
-                               slab, l, out, ldo, off_a, rank, off_w, ldw);
-        SCANRS_HIP(hipGetLastError());
         return;
+    case SPMM_GATHER2D: return launch_spmm_2d(st, cp, map, X, ldx, l, out, ldo, off_a, rank, off_w, ldw);
+    case SPMM_GATHER2D_F32: return launch_spmm_2d_f32(st, cp, map, X, ldx, l, out, ldo, off_a, rank, off_w, ldw);
+    case SPMM_SLICE_WALK:
+        return launch_slice_walk<0>(st, cp, map, fv, r.fstart, r.lazy_scale, X, ldx, out, ldo, nullptr, nullptr, off_a, rank, off_w, ldw, "slice_walk_spmv/short-outer",
+                                    (double)cp.nnz * (fv ? 12.0 : 8.0) + (double)(cp.n_outer + 1) * 8.0 + (double)(cp.n_inner + cp.n_outer) * 8.0);
+    case SPMM_SPMV2D: return launch_spmv2d(st, cp, map, r.fused, X, ldx, l, out, ldo, off_a, rank, off_w, ldw);
+    case SPMM_SPMV_LDS:
+        if (r.vm == 2) return launch_spmv_lds<2>(st, cp, map, fv, r.fstart, X, ldx, out, ldo, off_a, rank, off_w, ldw);
+        if (r.vm == 1) return launch_spmv_lds<1>(st, cp, map, fv, r.fstart, X, ldx, out, ldo, off_a, rank, off_w, ldw);
+        return launch_spmv_lds<0>(st, cp, map, fv, r.fstart, X, ldx, out, ldo, off_a, rank, off_w, ldw);
+    case SPMM_SPMV: return launch_spmv(st, cp, map, X, ldx, l, out, ldo, off_a, rank, off_w, ldw);
+    default: return launch_spmm_t<double>(st, cp, map, X, ldx, l, out, ldo, off_a, rank, off_w, ldw);
     }
-    launch_spmm_t<double>(st, cp, map, X, ldx, l, out, ldo, off_a, rank, off_w, ldw);
 }
 void launch_spmm_u32(Storage &st, const SparseCopy &cp, const uint32_t *X, uint32_t ldx, uint32_t l, uint32_t *out,
                      uint32_t ldo) {
@@ -2092,20 +2039,26 @@ static uint32_t ensure_bounds(Storage &st, SparseCopy &cp, hipStream_t s);
 // copy will run through the hybrid tile product, which keeps its own weights: 8 B per nonzero and 1.7 ms of stores per
 // normalize saved; a gather product that wants them later (RandSvd's 500-column panels) materializes them itself then.
 static bool moments_keep_values(Storage &st, const SparseCopy &cp, const DevMap &map) {
-    const bool tiles = st.panel_precision == 0 && tile_shape_ok(st.tile_k, st.tile_s, st.tile_t, st.tile_b) &&
-                       (st.spmm_path == 3 || (st.spmm_path == 0 && st.tile_auto && cp.nnz >= std::max<uint64_t>(st.blocked_min_nnz, 1ull << 24)));
+    const SpmmOptions o = spmm_options(st);
+    // Against tiles_static_candidate, the launch's own test:
+    //  - no panel terms (l, ldx, LDS room): the pass runs before any product, the width is the solver's to choose;
+    //  - no rejection memory and no layout: at the first normalize nothing has been tried yet;
+    //  - no tile_visits_fit: no reason found (a copy beyond the 32-bit visit index keeps no values and runs the gather without them);
+    //  - f64 panels also under a forced path 3, which itself ignores the precision: no reason found (path 3 with f32 panels runs
+    //    tiles, and the values kept here then serve nothing but a gather product the caller may never make).
+    const bool tiles = f64_panels(o) && tile_shape_ok(o) && (path_forces_tiles(o) || (path_auto(o) && o.tile_auto && tile_auto_size(o, cp.nnz)));
     return !tiles && fvals_wanted(st, cp, map, map.n);
 }
 
 void launch_row_reduce(Storage &st, SparseCopy &cp, const DevMap &map, int mode, uint32_t *out_u32, double *out_sum,
                        double *out_sumsq) {
     if (cp.n_outer == 0) return;
-    if (mode != 0 && cp.nnz >= st.blocked_min_nnz && cp.n_inner >= (1ull << 19)) {
+    const SpmmQuery q = spmm_query(st, cp, map, 0, 0);
+    if (mode != 0 && far_inner(q.o, cp.n_inner, cp.nnz)) {
         bool inner_indexed = false;
-        for (int i = 0; i < map.n; i++)
-            inner_indexed = inner_indexed || (map.ops[i].a && !map.ops[i].a_outer) || (map.ops[i].b && !map.ops[i].b_outer);
+        for (int i = 0; i < map.n; i++) inner_indexed = inner_indexed || link_reads_inner(q, i);
         bool lazy = false;
-        if (inner_indexed && st.slice_walk && cp.n_outer < cp.n_inner && slice_walk_chain(map, 0, lazy) && lazy) {
+        if (inner_indexed && st.slice_walk && cp.n_outer < cp.n_inner && slice_walk_chain(q, 0, lazy) && lazy) {
             // the barcode scale staged in LDS slice by slice instead of gathered from L2 (see slice_walk_kernel)
             double *fout = mode == 2 && moments_keep_values(st, cp, map) ? fvals_claim(st, cp, map, map.n) : nullptr;
             launch_slice_walk<1>(st, cp, map, nullptr, 0, true, nullptr, 0, out_sum, 1, mode == 2 ? out_sumsq : nullptr, fout, nullptr, 0,

@@ -1272,7 +1272,7 @@ static int pca_bk_impl(scanrs_mat *m, uint32_t k, double k_multiplier, uint32_t 
         // decades: the same residual bound with the raised L, at most 1.1e-9 sqrt(q) s_1 — until the pass fits.
         // The rule looks at b and the coefficients only — not at whether this handle (or this shard) happens to run the hybrid product:
         // the flagged set, and with it the rounding of the result, is the same on every rank of a sharded run and under any memory
-        // pressure (it used to depend on mat_tiles_ready).
+        // pressure (it used to depend on whether a tile layout existed).
         std::vector<double> flagged; // the older blocks' columns at or above the bound, before any raise
         for (uint32_t j = 0; j < (n_iter - 1) * b; j++)
             if (!(colmax[j] < cmax_limit)) flagged.push_back(colmax[j]);

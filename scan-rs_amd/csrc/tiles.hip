@@ -28,6 +28,7 @@
 // Sums are bit-reproducible: positions in order, visits ascending, parts and the overflow sum added in a fixed order.
 #include "common.hpp"
 #include "device_map.hpp"
+#include "spmm_route.hpp"
 
 #include <algorithm>
 #include <rocprim/rocprim.hpp>
@@ -40,8 +41,7 @@ namespace {
 #define TL_NW_DEF 8
 #endif
 constexpr uint32_t TL_NW = TL_NW_DEF;  // waves per workgroup (8: 2 per SIMD; 12 with the 168-register kernel: 3 per SIMD, an experiment)
-constexpr uint32_t TL_LMAX = 104;      // widest panel: 192 ring rows x 104 x 8 B = 159744 B of LDS
-constexpr uint32_t TL_LDS = 160u << 10;
+// (TL_LMAX, the widest panel, and TL_LDS: spmm_route.hpp)
 constexpr int TL_W = 6;                // LDS row reads in flight per wave
 #ifndef TL_SROWS
 #define TL_SROWS 1
@@ -816,9 +816,7 @@ __global__ void tile_ovptr_kernel(const unsigned long long *__restrict__ ov_off,
 } // namespace
 
 // the dense record layout serves the default shape (tiles_dense.inc)
-static inline bool tile_dense_wanted(const Storage &st) {
-    return st.tile_dense != 0 && st.tile_builder != 0 && st.tile_k == 2u && st.tile_b == 4u && st.tile_s == 32u && st.tile_t == 48u;
-}
+static inline bool tile_dense_wanted(const Storage &st) { return tile_dense_wanted(spmm_options(st)); }
 // the tile layout of one orientation under one map
 struct TileLayout {
     TileShape sh{};
@@ -869,9 +867,10 @@ struct TileLayout {
         if (dense != tile_dense_wanted(st)) return false;
         if (dense && (slot_order.n != 0) != (st.tile_sort_slots != 0 && n_slots > 1)) return false;
         if (dense && slot_order.n != 0 && slot_mode != st.tile_sort_slots) return false;
-        const bool splittable = st.tile_builder != 0 && sh.K == 2u && sh.B == 4u && sh.S == 32u && sh.T == 48u; // the wave-level builder's shape
+        // the slots are split for the wave-level builder's shape (asked of the options: a layout of another shape than theirs fails below anyway)
+        const bool splittable = default_tile_shape(spmm_options(st));
         const double want_x = splittable && st.tile_split ? st.tile_split_x : 0.0, want_min = splittable && st.tile_split ? st.tile_split_min : 0.0;
-        return sh.K == st.tile_k && sh.S == st.tile_s && sh.T == st.tile_t && sh.B == st.tile_b && sh.KU == (st.tile_k == 2u && st.tile_ku ? 1u : 0u) &&
+        return sh.K == st.tile_k && sh.S == st.tile_s && sh.T == st.tile_t && sh.B == st.tile_b && sh.KU == tile_unit_positions(spmm_options(st)) &&
                split_x == want_x && split_min == want_min;
     }
     bool weights_match(const DevMap &map) const {
@@ -906,12 +905,6 @@ void tile_layout_stats(const TileLayout *t, uint64_t out[3]) {
 uint32_t ensure_bounds_public(Storage &st, SparseCopy &cp, hipStream_t s); // kernels.hip
 void materialize_map_values(Storage &st, SparseCopy &cp, const DevMap &map, double *fout); // kernels.hip
 
-// unit positions exist for K = 2 only (one unit + one general position per visit)
-bool tile_shape_ok(uint32_t K, uint32_t S, uint32_t T, uint32_t B) {
-    const bool ks = (K == 2 && (S == 32 || S == 28)) || (K == 3 && S == 32) || (K == 4 && (S == 32 || S == 28));
-    return ks && B >= 2 && T >= 8 && T <= 24u * K && B * T <= 192;
-}
-
 static TileLayout *dense_layout_build(Storage &st, const SparseCopy &cp, double max_overflow, hipStream_t s, std::unique_ptr<TileLayout> tl,
                                       const std::function<void(const char *)> &lap); // tiles_dense.inc
 // max_overflow > 0: give up (nullptr) when more than that share of the nonzeros would land in the overflow part — known after the
@@ -923,7 +916,7 @@ TileLayout *tile_layout_build(Storage &st, const SparseCopy &cp, double max_over
     auto tl = std::make_unique<TileLayout>();
     TileShape &sh = tl->sh;
     sh.K = st.tile_k;
-    sh.KU = st.tile_k == 2u && st.tile_ku ? 1u : 0u;
+    sh.KU = tile_unit_positions(spmm_options(st));
     sh.S = st.tile_s;
     sh.T = st.tile_t;
     sh.B = st.tile_b;
@@ -1133,27 +1126,13 @@ TileLayout *tile_layout_build(Storage &st, const SparseCopy &cp, double max_over
     return tl.release();
 }
 
-// Is f(1, outer, inner) a product of an outer and an inner factor? Yes when the links in front of the first nonlinear link
-// (log, square) index one side only and no binomial residual link takes part; nl_outer = the side that owns them.
-static bool tile_map_separable(const DevMap &map, int &nl_outer) {
-    bool nonlinear = false, pre_outer = false, pre_inner = false, post_scale = false;
-    for (int i = 0; i < map.n; i++) {
-        const int k = map.ops[i].kind;
-        if (k == OP_BINOM_DEV || k == OP_BINOM_PEARSON) return false;
-        if (k == OP_LN_1P || k == OP_LOG2_1P || k == OP_LOG10_1P || k == OP_SQUARE) {
-            if (post_scale) return false; // a scale between two nonlinear links does not factor out of the second one
-            nonlinear = true;
-        }
-        if (k == OP_SCALE_AXIS) {
-            if (!nonlinear)
-                (map.ops[i].a_outer ? pre_outer : pre_inner) = true;
-            else
-                post_scale = true;
-        }
-    }
-    if (nonlinear && pre_outer && pre_inner) return false;
-    nl_outer = pre_inner ? 0 : 1;
-    return true;
+// the form of the weights under `map` (unit mode, separable, folds, where the kernel takes a weight from): decided in spmm_route.hpp
+static TileForm tile_layout_set_form(const Storage &st, TileLayout &tl, const SparseCopy &cp, const DevMap &map) {
+    const TileForm f = tile_form(spmm_query(st, cp, map, 0, 0), tl.dense, tl.sh.KU > 0);
+    tl.unit_mode = f.unit_mode, tl.separable = f.separable;
+    tl.fold_inner = f.fold_inner, tl.fold_outer = f.fold_outer;
+    tl.wsrc = f.wsrc;
+    return f;
 }
 
 static void dense_layout_weights(Storage &st, TileLayout &tl, const SparseCopy &cp, const DevMap &map); // below
@@ -1165,8 +1144,7 @@ static void tile_layout_weights(Storage &st, TileLayout &tl, const SparseCopy &c
         return;
     }
     const uint64_t n_rec = tl.prow.n;
-    int nl_outer = 1;
-    tl.unit_mode = tl.sh.KU > 0 && tile_map_separable(map, nl_outer);
+    const int nl_outer = tile_layout_set_form(st, tl, cp, map).nl_outer;
     if (tl.unit_mode) {
         if (tl.uo.n != cp.n_outer) tl.uo.alloc(std::max<uint64_t>(cp.n_outer, 1));
         if (tl.vi.n != cp.n_inner) tl.vi.alloc(std::max<uint64_t>(cp.n_inner, 1));
@@ -1563,7 +1541,7 @@ __global__ __launch_bounds__(256) void tile_finish_kernel(const double *__restri
 template <int K, int S, int KU>
 void launch_tile_kernel(Storage &st, const TileArgs &ta, const double *X, uint32_t ldx, uint32_t l, double *parts, uint32_t ldo,
                         uint64_t part_stride, uint32_t n_items, uint32_t grid) {
-    const size_t shmem = ((size_t)ta.sh.B * ta.sh.T + 1u) * ldx * 8; // the ring + the row of zeros (spmm_tiles_ok keeps room for it)
+    const size_t shmem = ((size_t)ta.sh.B * ta.sh.T + 1u) * ldx * 8; // the ring + the row of zeros (tile_panel_ok keeps room for it)
     if constexpr (S <= 28) {
         SCANRS_HIP(hipFuncSetAttribute((const void *)spmm_tile_kernel_r168<K, S, KU>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)shmem));
         hipLaunchKernelGGL((spmm_tile_kernel_r168<K, S, KU>), dim3(grid), dim3(64 * TL_NW), shmem, st.stream, ta, X, ldx, l, parts, ldo, part_stride,
@@ -1577,11 +1555,6 @@ void launch_tile_kernel(Storage &st, const TileArgs &ta, const double *X, uint32
 
 } // namespace
 
-bool spmm_tiles_ok(const Storage &st, const SparseCopy &cp, uint32_t ldx, uint32_t l) {
-    return l >= 16 && l <= TL_LMAX && (ldx & 1u) == 0 && cp.n_outer > 0 && cp.n_inner > 0 && cp.nnz > 0 &&
-           ((size_t)st.tile_b * st.tile_t + 1u) * even_up(l) * 8 <= TL_LDS && (size_t)st.tile_t * even_up(l) * 8 >= 1024u; // (a tile is at least one staging chunk)
-}
-
 // Auto path (spmm_path 0): the hybrid product serves a large matrix once its layout under this map exists — built when a
 // solver announces many products (Storage::tile_hint) or when the same map comes by a second time, and only if the device
 // has room for it (about 16 bytes per nonzero per orientation).
@@ -1589,12 +1562,11 @@ static uint64_t tile_shape_signature(const Storage &st) {
     return 1ull + st.tile_k + 16ull * st.tile_s + 4096ull * st.tile_t + (1ull << 24) * st.tile_b + (1ull << 32) * st.tile_ku +
            (1ull << 34) * (uint64_t)(st.tile_max_overflow * 1000.0);
 }
-// large enough, the visit index fits, and this shape has not been found wanting for this copy before
+// large enough, the visit index fits (tile_auto_copy_ok: the auto clause of tiles_static_candidate without the path, the precision
+// and the panel, which the helper thread's build has none of), and - this site's own term, it needs the copy's memory - this shape
+// has not been found wanting for this copy before
 static bool tile_auto_candidate(const Storage &st, const SparseCopy &cp) {
-    if (!st.tile_auto || cp.nnz < std::max<uint64_t>(st.blocked_min_nnz, 1ull << 24)) return false;
-    if (!tile_shape_ok(st.tile_k, st.tile_s, st.tile_t, st.tile_b)) return false;
-    if (((cp.n_outer + st.tile_s - 1) / st.tile_s) * ((cp.n_inner + st.tile_t - 1) / st.tile_t) > 0xFFFFFFFFull) return false; // 32-bit visit index
-    return cp.tile_rejected_shape != tile_shape_signature(st);
+    return tile_auto_copy_ok(spmm_options(st), cp.n_outer, cp.n_inner, cp.nnz) && cp.tile_rejected_shape != tile_shape_signature(st);
 }
 bool tile_layout_build_auto(Storage &st, SparseCopy &cp, hipStream_t s) {
     if (!tile_auto_candidate(st, cp)) return false;
@@ -1774,8 +1746,12 @@ void launch_spmm_tiles(Storage &st, SparseCopy &cp, const DevMap &map, const dou
 }
 
 double *tile_panel_copy_target(Storage &st, SparseCopy &cp, uint32_t l) {
-    if ((l & 1u) || l < 16u || l > TL_LMAX || !cp.tiles || !cp.tiles->dense || cp.tiles->unit_mode || cp.tiles->fold_inner || !cp.tiles->structure_matches(st)) return nullptr;
-    if (!(st.spmm_path == 3 || (st.spmm_path == 0 && st.tile_auto && st.panel_precision == 0))) return nullptr;
+    if ((l & 1u) || l < TL_LMIN || l > TL_LMAX || !cp.tiles || !cp.tiles->dense || cp.tiles->unit_mode || cp.tiles->fold_inner || !cp.tiles->structure_matches(st)) return nullptr;
+    // Against tiles_static_candidate: the layout exists and matches, so the shape, the sizes and the visit index were tested when
+    // it was built; l even and within the tile kernel's widths stands in for the panel terms (a chunked wide panel is never copied
+    // ahead). f64 panels are asked for on the auto path only, as the launch does.
+    const SpmmOptions o = spmm_options(st);
+    if (!(path_forces_tiles(o) || (path_auto(o) && o.tile_auto && f64_panels(o)))) return nullptr;
     return st.scratch.get<double>("tile_xc", ((size_t)cp.n_inner + 3u * cp.tiles->sh.T) * l); // (the size launch_spmm_tiles asks for: the same buffer)
 }
 

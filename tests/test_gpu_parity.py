@@ -630,6 +630,7 @@ def test_lds_staged_product_matches_gather_and_oracle(sa, storage, tile_k, tile_
                 g3.profile_reset()
                 a1, a3, ref = g1.dot(q), g3.dot(q), ref_m.dot(q)
                 assert _tile_kernel_served(g3) == (l not in TILE_UNREACHED_L), (rows, cols, l)  # "route 3 equals route 1" is not the gather against itself
+                assert (g3.counter("spmm_route") == sa.SPMM_TILES) == (l not in TILE_UNREACHED_L), (rows, cols, l)
                 assert_close(a3, ref, rtol=1e-10, atol=1e-9)
                 assert_close(a1, a3, rtol=1e-11, atol=1e-10)
                 assert np.array_equal(a3, g3.dot(q))  # bitwise repeatable
@@ -666,6 +667,7 @@ def test_wave_level_layout_builder_equals_the_per_thread_walk(sa, tile_ku):
                 g.profile_enable(True)
                 outs.append((g.dot(q), g.rdot(ql)))
                 assert _tile_kernel_served(g), (rows, cols, storage)  # every shape here reaches the tile kernel (40 and 24 columns)
+                assert g.counter("spmm_route") == sa.SPMM_TILES
             assert np.array_equal(outs[0][0], outs[1][0]) and np.array_equal(outs[0][1], outs[1][1]), (rows, cols, fill, storage)
 
 
@@ -692,6 +694,7 @@ def test_one_pass_layout_build_equals_count_then_fill(sa):
                 g.profile_enable(True)
                 outs.append((g.dot(q), g.rdot(ql)))
                 assert _tile_kernel_served(g), (rows, cols, storage)  # every shape here reaches the tile kernel (40 and 24 columns)
+                assert g.counter("spmm_route") == sa.SPMM_TILES
             assert np.array_equal(outs[0][0], outs[1][0]) and np.array_equal(outs[0][1], outs[1][1]), (rows, cols, fill, storage)
 
 
@@ -714,6 +717,7 @@ def test_wide_weight_refresh_equals_the_one_position_form(sa):
                 g.profile_enable(True)
                 outs.append((g.dot(q), g.rdot(ql)))
                 assert _tile_kernel_served(g), (rows, cols, storage)  # every shape here reaches the tile kernel (40 and 24 columns)
+                assert g.counter("spmm_route") == sa.SPMM_TILES
             assert np.array_equal(outs[0][0], outs[1][0]) and np.array_equal(outs[0][1], outs[1][1]), (rows, cols, fill, storage)
 
 
@@ -750,6 +754,7 @@ def test_dense_record_layout_equals_round4_layout_and_is_placement_independent(s
                 g.profile_enable(True)
                 outs.append((g.dot(q), g.rdot(ql)))
                 assert _tile_kernel_served(g), (rows, cols, storage)  # every shape here reaches the tile kernel (40 and 24 columns)
+                assert g.counter("spmm_route") == sa.SPMM_TILES
                 assert np.array_equal(outs[-1][0], g.dot(q))  # repeatable
             assert_close(outs[1][0], outs[0][0], rtol=1e-12, atol=1e-11)
             assert_close(outs[1][1], outs[0][1], rtol=1e-12, atol=1e-11)
@@ -792,6 +797,7 @@ def test_map_evaluated_inside_the_tile_kernel_equals_the_weight_stream_and_the_o
                     o = o.compose_map(so.MapOp(so.OP_SCALE_AXIS, axis=log_axis, a=fa)).apply(so.OP_LOG2_1P).compose_map(so.MapOp(so.OP_SCALE_AXIS, axis=1 - log_axis, a=fb))
                 outs = [(g.dot(q), g.rdot(ql)) for g in hs]
                 assert all(_tile_kernel_served(g) for g in hs), (rows, cols, storage, log_axis)  # every shape here reaches the tile kernel
+                assert all(g.counter("spmm_route") == sa.SPMM_TILES for g in hs)
                 ref = (o.dot(q), o.rdot(ql))
                 for k in (0, 1):
                     assert_close(outs[0][k], ref[k], rtol=1e-10, atol=1e-9)

@@ -3,9 +3,11 @@ through handle options, against the references of tests/spmm_exact_ref.py: bit f
 B = (n + 32) 2**-53 sum|t||x| on logarithm maps, on matrices with empty vectors whose scale factors are infinite, on panels with one
 non-finite row, and with NaN in the slack behind the tile kernel's panel copy (handle option "tile_poison_slack").
 
-Every test first proves its route: the profile must hold the route's kernel (and none of another product route's), and a tile
-route's layout must have served nonzeros (counter "tile_served_nonzeros"); the profile name is the same for all forms of the tile
-kernel, the form follows from the options and the map as noted below.
+Every test first proves its route: the profile must hold the route's kernel (and none of another product route's), a tile
+route's layout must have served nonzeros (counter "tile_served_nonzeros"), and the record the library keeps of its last product
+(counters "spmm_route" / "spmm_form" / "spmm_chunks", csrc/spmm_route.hpp) must name the route's kernel family, the FORM this table
+claims for the (route, map, side) and the number of column chunks. The expected forms are written out below (Route.forms,
+MAP_SCALE_AXIS, the *_FORM tables), not asked of the library's host function.
 
 route (id)            options                                                    profile name that proves it
 gather1               spmm_path 1                                                spmm_gather_kernel<double, N>
@@ -17,25 +19,35 @@ r4_unit               spmm_path 3, tile_dense 0, tile_ku 1                      
                                                                                  map (raw, sq_axis0/1, the logarithm maps); the weighted
                                                                                  kernel on the same layout under sq_both (not separable)
 dense_tab             spmm_path 3 (dense records, the default)                   spmm_tile_kernel/...   table by place ("tabo") when the
-                                                                                 product's outer side owns the nonlinear link, by inner
-                                                                                 position ("tabi") otherwise: map x storage x dot/rdot
-                                                                                 gives both; weight stream under sq_both
-dense_stream          spmm_path 3, tile_wtab 0                                   spmm_tile_kernel/...   folded factors, weight stream
+                                                                                 product's outer side owns the nonlinear link AND under
+                                                                                 raw counts (no nonlinear link: the place table holds the
+                                                                                 counts, on either side), by inner position ("tabi")
+                                                                                 otherwise: map x dot/rdot gives both; weight stream,
+                                                                                 nothing folded, under sq_both
+dense_stream          spmm_path 3, tile_wtab 0                                   spmm_tile_kernel/...   weight stream, the factor of the side
+                                                                                 without the nonlinear link folded out (inner: in the
+                                                                                 panel, outer: on the sums); nothing folded under sq_both
 dense_unfolded        spmm_path 3, tile_fold 0                                   spmm_tile_kernel/...   both factors in every weight
 gather2_3_to_15       spmm_path 3, l in 3, 8, 15                                 spmm_gather2d_kernel<1>/...
 gather1_3_to_15       spmm_path 0, l in 3, 8, 15                                 spmm_gather_kernel<double, N>
 spmv_small            spmm_path 0, l in 1, 2                                     spmv_kernel/...
 slice_walk            48 x 2**19+1, l 1                                          slice_walk_spmv/short-outer
-spmv2d                same, slice_walk 0 (l 1) or l 2                            spmv2d_kernel/short-outer
+spmv2d                same, slice_walk 0 (l 1) or l 2                            spmv2d_kernel/short-outer   l 1 under a chain that starts with the
+                                                                                 inner side's scale: the scale interleaved with the vector;
+                                                                                 this route never reads materialized values
 spmv_big_long         same matrix, rdot (outer 2**19+1)                          spmv_kernel/long-outer
 spmv_lds              2**16 x 18433, l 1, two parts; forms: 0 raw / inner-indexed map evaluated per nonzero, 2 row table (outer-only
                       chain), 1 materialized values (logarithm chain, bounded test) spmv_lds_kernel/long-outer
 
-What the proof does NOT reach: the profile names a kernel, not its form. Which spmv_lds form ran, table by place / by inner
-position / weight stream (TileLayout::wsrc), unit mode against the weighted kernel, and the number of parts of a layout follow from
-reading launch_spmm_f64 / dense_layout_weights for the options and maps above; the library has no counter for them and no test
-asserts them. The exact, bounded, infinite-scale and non-finite-row checks run on every route above, the narrow ones included (the
-two large matrices have empty rows and columns, infinite factors there, and NaN / inf vector entries).
+What is asserted about the form, after every product: which spmv_lds form ran, table by place / by inner position / weight stream
+(TileLayout::wsrc), unit mode against the weighted kernel, folded against unfolded factors, materialized values and the staged /
+interleaved scale of slice_walk and spmv2d, and the column chunks of a wide panel (105 columns: 2). What still is not: the number
+of parts of a layout and the rounds of a visit follow from the shapes alone and have no counter. Two claims an earlier version of
+this text made did not survive the assertions' table: under raw counts dense_tab runs the table by place on BOTH sides (it said
+"by inner position otherwise"), and spmv2d has no materialized-values form at all, so "spmv2d_unmaterialized" below runs exactly
+what "spmv2d" runs (the text said "the same without materialized values"). The exact, bounded, infinite-scale and non-finite-row
+checks run on every route above, the narrow ones included (the two large matrices have empty rows and columns, infinite factors
+there, and NaN / inf vector entries).
 
 Measured on an MI355X: worst |err| / B, and worst |err| / (2**-53 S) in brackets, over all shapes, storages, widths and sides
 (printed by the tests, run with -s). No ratio is above 1; the largest, 0.34, is under normalize(CellRanger), whose gene scales the
@@ -55,8 +67,8 @@ dense_unfolded   0.149 (5.35)   0.319 (10.86)  0.118 (4.24)        0.128 (4.21) 
 gather2_3_to_15  0.130 (4.40)   0.303 (10.21)  0.112 (3.71)        0.128 (4.21)       | 0.025 (3.99)  0.024 (3.53)  0.030 (4.22)  0.025 (3.20)
 gather1_3_to_15  0.130 (4.40)   0.303 (10.21)  0.112 (3.71)        0.128 (4.21)       | 0.025 (3.99)  0.024 (3.53)  0.030 (4.22)  0.025 (3.20)
 spmv_small       0.130 (4.40)   0.299 (10.17)  0.106 (3.49)        0.110 (3.62)       | 0.007 (0.71)  0.018 (2.54)  0.005 (0.66)  0.006 (0.71)
-Large matrices (infinite factors at their empty rows and columns): slice_walk 0.000 (0.03), spmv2d 0.000 (0.07; the same without
-materialized values), spmv_big_long 0.089 (3.28), spmv_lds forms 0 and 1 0.013 (1.18), form 2 0.016 (1.23).
+Large matrices (infinite factors at their empty rows and columns): slice_walk 0.000 (0.03), spmv2d 0.000 (0.07; the same form
+with "materialize" 0), spmv_big_long 0.089 (3.28), spmv_lds forms 0 and 1 0.013 (1.18), form 2 0.016 (1.23).
 Run time of the file on an MI355X: 62 s for its 101 tests (the slowest call under 3 s, the two large matrices 4 s of fixture set-up each)."""
 import os
 import sys
@@ -77,10 +89,43 @@ PRODUCT_KERNELS = ("spmm_gather_kernel<", "spmm_gather2d_kernel<1>/", "spmm_gath
                    "spmv_lds_kernel/", "slice_walk_spmv/")
 
 
+# kernel family (counter "spmm_route", SCANRS_SPMM_* of scanrs_amd.h) by the profile name that proves the route
+FAMILY = {TILE: 1, "spmm_gather2d_kernel<1>/": 2, "spmm_gather2d_f32_kernel/": 3, "slice_walk_spmv/": 4, "spmv2d_kernel/": 5, "spmv_lds_kernel/": 6,
+          "spmv_kernel/": 7, "spmm_gather_kernel<": 8}
+# The axis of the scale in front of a map's nonlinear link (None: no link at all, "N": scales of both axes in front of it - the map
+# does not separate). A product walks the copy whose outer vectors are the rows (dot: axis 0) or the columns (rdot, the transposed
+# view: axis 1); the map is class "O" when that axis owns the nonlinear link or there is none, "I" when the other one does.
+MAP_SCALE_AXIS = {"raw": None, "sq_axis0": 0, "sq_axis1": 1, "sq_both": "N", "log_normalize": 1, "cellranger": 1, "scale0_log2_scale1": 0,
+                  "scale1_log2_scale0": 1, "inf0_log2_inf1": 0, "inf1_log2_inf0": 1}
+# counter "spmm_form" of a tile product: bit 0 dense records, bit 1 unit mode, bits 2-3 the weight's source (0 stream, 1 table by
+# place, 2 table by inner position), bits 4-5 the factor folded out (0 none, 1 the inner side's, 2 the outer side's)
+FIXED_FORMS = {"O": 0, "I": 0, "N": 0}                       # fixed positions, a weight per position
+UNIT_FORMS = {"O": 2, "I": 2, "N": 0}                        # unit mode under a separable map, the weighted kernel otherwise
+TAB_FORMS = {"O": 1 | 1 << 2 | 1 << 4, "I": 1 | 2 << 2 | 2 << 4, "N": 1}   # tabo + the inner factor in the panel, tabi + the outer factor on the sums, the stream
+STREAM_FORMS = {"O": 1 | 1 << 4, "I": 1 | 2 << 4, "N": 1}    # the weight stream, folded
+UNFOLDED_FORMS = {"O": 1, "I": 1, "N": 1}                    # the weight stream, both factors in every weight
+
+
+def map_class(name, side):
+    axis = MAP_SCALE_AXIS[name]
+    if axis is None or axis == "N":
+        return "O" if axis is None else "N"
+    return "O" if axis == (0 if side == "dot" else 1) else "I"
+
+
 class Route:
-    def __init__(self, name, path, prof, opts=(), precision=0, tile_t=0, ls=None):
+    def __init__(self, name, path, prof, opts=(), precision=0, tile_t=0, ls=None, forms=None, form=0):
         self.name, self.path, self.prof, self.opts, self.precision, self.tile_t = name, path, prof, tuple(opts), precision, tile_t
         self.ls = ls  # panel widths of a route that serves narrow panels only (None: the wide widths of the test)
+        self.family = next(v for k, v in FAMILY.items() if prof.startswith(k))
+        self.forms, self.form = forms, form  # a tile route: the form by map class; another one: its one form
+        assert self.tile == (forms is not None)
+
+    def check_form(self, g, name=None, side="dot", l=1):
+        """the last product on g: this route's family, the form claimed for (map, side), the column chunks of an l-wide panel"""
+        want = (self.family, self.forms[map_class(name, side)] if self.tile else self.form, (l + 103) // 104 if self.tile else 1)
+        got = (g.counter("spmm_route"), g.counter("spmm_form"), g.counter("spmm_chunks"))
+        assert got == want, (self.name, name, side, l, got, want)
 
     @property
     def tile(self):
@@ -98,6 +143,7 @@ class Route:
     def check_ran(self, g):
         """the route's kernel ran, no other product kernel did, and (tiles) every layout built so far served nonzeros"""
         names = list(g.profile_get())
+        assert g.counter("spmm_route") == self.family, (self.name, g.counter("spmm_route"))
         assert any(n.startswith(self.prof) for n in names), (self.name, names)
         others = [n for n in names if any(n.startswith(p) for p in PRODUCT_KERNELS) and not n.startswith(self.prof)]
         assert not others, (self.name, others)
@@ -109,16 +155,16 @@ class Route:
 
 
 def _r4(k, s, t, b):
-    return Route(f"r4_{k}_{s}_{t}_{b}", 3, TILE, (("tile_dense", 0), ("tile_ku", 0), ("tile_k", k), ("tile_s", s), ("tile_t", t), ("tile_b", b)), tile_t=t)
+    return Route(f"r4_{k}_{s}_{t}_{b}", 3, TILE, (("tile_dense", 0), ("tile_ku", 0), ("tile_k", k), ("tile_s", s), ("tile_t", t), ("tile_b", b)), tile_t=t, forms=FIXED_FORMS)
 
 
 GATHER_ROUTES = [Route("gather1", 1, "spmm_gather_kernel<double"), Route("gather2", 2, "spmm_gather2d_kernel<1>/")]
 F32_ROUTE = Route("gather2_f32", 2, "spmm_gather2d_f32_kernel/", precision=1)
 TILE_ROUTES = [_r4(2, 32, 48, 4), _r4(2, 28, 48, 4), _r4(3, 32, 64, 3), _r4(4, 32, 96, 2), _r4(4, 28, 40, 3),
-               Route("r4_unit", 3, TILE, (("tile_dense", 0), ("tile_ku", 1)), tile_t=48),
-               Route("dense_tab", 3, TILE, (), tile_t=48),
-               Route("dense_stream", 3, TILE, (("tile_wtab", 0),), tile_t=48),
-               Route("dense_unfolded", 3, TILE, (("tile_fold", 0),), tile_t=48)]
+               Route("r4_unit", 3, TILE, (("tile_dense", 0), ("tile_ku", 1)), tile_t=48, forms=UNIT_FORMS),
+               Route("dense_tab", 3, TILE, (), tile_t=48, forms=TAB_FORMS),
+               Route("dense_stream", 3, TILE, (("tile_wtab", 0),), tile_t=48, forms=STREAM_FORMS),
+               Route("dense_unfolded", 3, TILE, (("tile_fold", 0),), tile_t=48, forms=UNFOLDED_FORMS)]
 F64_ROUTES = GATHER_ROUTES + TILE_ROUTES
 # panels under 16 columns on small matrices: the blocked gather (asked for), the plain gather and spmv_kernel (auto path)
 SMALL_L_ROUTES = [Route("gather2_3_to_15", 3, "spmm_gather2d_kernel<1>/", ls=(3, 8, 15)), Route("gather1_3_to_15", 0, "spmm_gather_kernel<double", ls=(3, 8, 15)),
@@ -245,10 +291,12 @@ def _exact_products(sa, route, dyadic_cases, ls):
                     for l in ls:
                         where = (route.name, case.shape, storage, name, offset, l)
                         got = g.dot(case.x[:, :l])
+                        route.check_form(g, name, "dot", l)
                         assert np.array_equal(er.bits(got), er.bits(refs[name, "dot", offset][:, :l])), where
                         if l == ls[0] and not offset:
                             first = route.check_ran(g)
                         got = g.rdot(case.xl[:l])
+                        route.check_form(g, name, "rdot", l)
                         assert np.array_equal(er.bits(got), er.bits(refs[name, "rdot", offset][:l])), where
                         if l == ls[0] and not offset and route.tile:
                             assert route.check_ran(g)[0] > first[0], where  # the second orientation's layout served nonzeros too
@@ -274,10 +322,12 @@ def _bounded_products(sa, route, cases, ls, storages=None, tag=""):
                 apply(g)
                 g.profile_reset()  # (a normalisation's own passes are not the subject)
                 for l in ls:
-                    sides = [("dot", g.dot(x[:, :l])), ("rdot", g.rdot(xl[:l]))]
+                    sides = [("dot", lambda: g.dot(x[:, :l])), ("rdot", lambda: g.rdot(xl[:l]))]
                     if l == ls[0]:  # the transposed view
-                        sides.append(("t", g.t().dot(xl[:l].T.copy()).T))
-                    for side, got in sides:
+                        sides.append(("t", lambda: g.t().dot(xl[:l].T.copy()).T))
+                    for side, product in sides:
+                        got = product()
+                        route.check_form(g, name, side, l)
                         rb, ru = er.error_ratios(got, _cut(refs[name, "dot" if side == "dot" else "rdot"], "dot" if side == "dot" else "rdot", l))
                         _note(route, tag + name, rb, ru)
                         assert np.isfinite(got).all() and rb <= 1.0, (route.name, dense.shape, storage, name, side, l, rb, ru)
@@ -333,6 +383,7 @@ def test_a_non_finite_panel_row_stays_in_the_vectors_that_store_it(sa, route, va
                     got, clean = g.dot(bad), g.dot(zeroed)
                 else:
                     got, clean = g.rdot(bad.T.copy()).T, g.rdot(zeroed.T.copy()).T
+                route.check_form(g, "log_normalize", side, l)
                 where = (route.name, storage, side, r)
                 nf_cols = ~np.isfinite(bad[r])
                 assert not np.isfinite(got[np.ix_(hit, nf_cols)]).any(), where
@@ -358,6 +409,7 @@ def test_poisoned_panel_slack_changes_nothing(sa, route):
                     g.set_option("tile_poison_slack", poison)
                     g.profile_reset()
                     outs.append((g.dot(case.x[:, :l]), g.rdot(case.xl[:l])))
+                    route.check_form(g, name, "rdot", l)
                     assert ("tile_poison_slack" in g.profile_get()) == bool(poison)  # the hook's kernel ran, and only when asked
                 refs = er.dyadic_ref(case, name, "dot", l, False), er.dyadic_ref(case, name, "rdot", l, False)
                 assert max(int(r.mag.max()) for r in refs) < 2 ** 53
@@ -422,26 +474,31 @@ def _narrow_exact(sa, case, route, name, side, l, refs):
             assert int(ref.mag.max()) < 2 ** 53, key
             refs[key] = ref.want
         got = g.dot(case.x[:, :l]) if side == "dot" else g.rdot(case.xl[:l])
+        route.check_form(g)
         assert np.array_equal(er.bits(got), er.bits(refs[key])), (route.name, key)
     route.check_ran(g)
     return g
 
 
 NARROW_REFS = {}
+SLICE_WALK_FORM = {"raw": 0, "sq_axis1": 1, "sq_axis0": 0}
+SPMV2D_L1_FORM = {"raw": 0, "sq_axis1": 2, "sq_axis0": 0}
+SPMV_LDS_FORM = {"raw": 0, "sq_axis1": 0, "sq_only0": 2}
 
 
 @pytest.mark.parametrize("name", ["raw", "sq_axis1", "sq_axis0"])
 def test_dyadic_slice_walk_and_spmv2d(sa, short_outer_case, name):
     refs = NARROW_REFS.setdefault("short", {})
-    _narrow_exact(sa, short_outer_case, Route("slice_walk", 0, "slice_walk_spmv/"), name, "dot", 1, refs)
-    _narrow_exact(sa, short_outer_case, Route("spmv2d", 0, "spmv2d_kernel/short-outer", (("slice_walk", 0),)), name, "dot", 1, refs)
+    # sq_axis1 starts with the inner side's scale: slice_walk reads materialized values (bit 0), spmv2d interleaves the scale (bit 1)
+    _narrow_exact(sa, short_outer_case, Route("slice_walk", 0, "slice_walk_spmv/", form=SLICE_WALK_FORM[name]), name, "dot", 1, refs)
+    _narrow_exact(sa, short_outer_case, Route("spmv2d", 0, "spmv2d_kernel/short-outer", (("slice_walk", 0),), form=SPMV2D_L1_FORM[name]), name, "dot", 1, refs)
     _narrow_exact(sa, short_outer_case, Route("spmv2d", 0, "spmv2d_kernel/short-outer"), name, "dot", 2, refs)
     _narrow_exact(sa, short_outer_case, Route("spmv_big_long", 0, "spmv_kernel/long-outer"), name, "rdot", 1, refs)
 
 
 @pytest.mark.parametrize("name", ["raw", "sq_axis1", "sq_only0"])  # forms 0, 0 (inner-indexed link per nonzero), 2 (row table)
 def test_dyadic_spmv_lds(sa, long_outer_case, name):
-    _narrow_exact(sa, long_outer_case, Route("spmv_lds", 0, "spmv_lds_kernel/"), name, "dot", 1, NARROW_REFS.setdefault("long", {}))
+    _narrow_exact(sa, long_outer_case, Route("spmv_lds", 0, "spmv_lds_kernel/", form=SPMV_LDS_FORM[name]), name, "dot", 1, NARROW_REFS.setdefault("long", {}))
 
 
 def _narrow_bounded(sa, case, route, side, l, chain):
@@ -485,6 +542,7 @@ def _narrow_bounded(sa, case, route, side, l, chain):
                         np.broadcast_to(counts[:, None].astype(np.float64), (counts.shape[0], l)))
     product = (lambda v: g.dot(v)) if side == "dot" else (lambda v: g.rdot(v.T.copy()).T)
     got = product(x)
+    route.check_form(g)
     rb, ru = er.error_ratios(got, ref)
     print(f"\n{route.name} l={l} {chain}: worst |err|/B {rb:.3f}, worst |err|/(2^-53 S) {ru:.2f}")
     assert np.isfinite(got).all() and rb <= 1.0, (route.name, side, l, chain, rb, ru)
@@ -504,14 +562,14 @@ def _narrow_bounded(sa, case, route, side, l, chain):
 
 def test_logarithm_maps_slice_walk_and_spmv2d_within_the_bound(sa, short_outer_case):
     for chain in ("inner", "inner_outer"):
-        _narrow_bounded(sa, short_outer_case, Route("slice_walk", 0, "slice_walk_spmv/"), "dot", 1, chain)
-        _narrow_bounded(sa, short_outer_case, Route("spmv2d", 0, "spmv2d_kernel/short-outer", (("slice_walk", 0),)), "dot", 1, chain)  # (the scale fused into the vector's slots)
-        _narrow_bounded(sa, short_outer_case, Route("spmv2d_unmaterialized", 0, "spmv2d_kernel/short-outer", (("slice_walk", 0), ("materialize", 0))), "dot", 1, chain)
+        _narrow_bounded(sa, short_outer_case, Route("slice_walk", 0, "slice_walk_spmv/", form=1), "dot", 1, chain)  # materialized values
+        _narrow_bounded(sa, short_outer_case, Route("spmv2d", 0, "spmv2d_kernel/short-outer", (("slice_walk", 0),), form=2), "dot", 1, chain)  # (the scale fused into the vector's slots)
+        _narrow_bounded(sa, short_outer_case, Route("spmv2d_unmaterialized", 0, "spmv2d_kernel/short-outer", (("slice_walk", 0), ("materialize", 0)), form=2), "dot", 1, chain)  # (the same form: spmv2d reads no materialized values)
         _narrow_bounded(sa, short_outer_case, Route("spmv2d", 0, "spmv2d_kernel/short-outer"), "dot", 2, chain)
     _narrow_bounded(sa, short_outer_case, Route("spmv_big_long", 0, "spmv_kernel/long-outer"), "rdot", 1, "inner_outer")
 
 
 def test_logarithm_maps_spmv_lds_within_the_bound(sa, long_outer_case):
-    _narrow_bounded(sa, long_outer_case, Route("spmv_lds_values", 0, "spmv_lds_kernel/"), "dot", 1, "inner_outer")                       # form 1
-    _narrow_bounded(sa, long_outer_case, Route("spmv_lds_lazy", 0, "spmv_lds_kernel/", (("materialize", 0),)), "dot", 1, "inner_outer")  # form 0
-    _narrow_bounded(sa, long_outer_case, Route("spmv_lds_row_table", 0, "spmv_lds_kernel/"), "dot", 1, "outer")                           # form 2
+    _narrow_bounded(sa, long_outer_case, Route("spmv_lds_values", 0, "spmv_lds_kernel/", form=1), "dot", 1, "inner_outer")
+    _narrow_bounded(sa, long_outer_case, Route("spmv_lds_lazy", 0, "spmv_lds_kernel/", (("materialize", 0),), form=0), "dot", 1, "inner_outer")
+    _narrow_bounded(sa, long_outer_case, Route("spmv_lds_row_table", 0, "spmv_lds_kernel/", form=2), "dot", 1, "outer")
