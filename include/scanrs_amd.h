@@ -1162,6 +1162,72 @@ int scanrs_multi_merge_clusters(scanrs_multi *mm, int transposed, const double *
 int scanrs_multi_cluster_medoids(scanrs_multi *mm, int transposed, const double *pca, uint32_t ld, uint32_t d, const int16_t *labels,
                                  uint32_t k, double *centers);
 
+/* ---- hclust: hierarchical clustering with leaf ordering (hclust/src/lib.rs) -------------------------------------------
+ * HierarchicalCluster::new (hclust/src/lib.rs:132-148), leaves (:150-206), merge_clusters_below_distance_threshold (:210-227),
+ * fcluster (:231-239), relabel_vector (:122-125). The metric is Euclidean (the reference's only one, :19-23): each squared distance
+ * is the sum over the dimensions in order of (b_k - a_k)^2, multiply and add rounded separately, then the square root. The
+ * dendrogram is kodama::linkage's: n - 1 steps sorted by dissimilarity (a stable sort of the merges in the order the chain found
+ * them), the cluster made by sorted step i is named n + i, cluster1 < cluster2, size counts observations.
+ * scanrs_hclust_create: x is a HOST array of rows x cols f64, row-major with leading dimension ld >= cols (elements); direction
+ * says whether its rows or its columns are the observations. scanrs_hclust_create_device: the same on an array in device memory,
+ * e.g. *d_u / *ld_u or *d_v / *ld_v of scanrs_pca_result_device. The distance pass and the nearest-neighbour chain run on the device
+ * against a full symmetric n x n f64 matrix (n^2 * 8 bytes, both halves kept current); when that does not fit beside what the
+ * library holds, SCANRS_ERR_DEVICE names n and the bytes. Fewer than two observations: SCANRS_ERR_SHAPE, "Need at least two elements
+ * to do hierarchical clustering" (:134). A NaN or an infinity in x: SCANRS_ERR_ARGUMENT naming the first such element in row-major
+ * order (as scanrs_merge_clusters refuses one). snoop may be NULL: a cancel flag that is already set returns SCANRS_ERR_CANCELLED
+ * before anything is queued; afterwards the flag is read, and progress = merges / (n - 1) reported, between batches of chain steps.
+ * Finite coordinates whose distance is not finite (squared differences overflow beyond about 1.3e154) return SCANRS_ERR_ARGUMENT
+ * naming the first such pair of observations, after the distance pass and before any chain step. A Lance-Williams update whose
+ * result is not finite (Ward on squared distances near the top of the f64 range) returns SCANRS_ERR_NUMERICAL: the update flags it
+ * on the device and every later step returns at once, so no value that is not finite is ever scanned. On any failure *out is NULL
+ * and what the call allocated on the device has been released. A chain that has not finished within 3 n steps returns
+ * SCANRS_ERR_NUMERICAL as well (a chain of finite dissimilarities ends within 3 (n - 1)). Results are bit-reproducible (no floating-point atomics) and equal scanrs_host_hclust_linkage's.
+ * NOT provided: Centroid and Median linkage. They are not reducible: the nearest-neighbour chain does not compute them, and kodama
+ * runs a different algorithm for them. They return SCANRS_ERR_ARGUMENT naming the method. Also not provided: other metrics, optimal
+ * leaf ordering, condensed-matrix input, a sharded form.
+ * scanrs_hclust_from_steps (host only): a handle around a given dendrogram of n observations, n - 1 entries per array. Refused with
+ * SCANRS_ERR_ARGUMENT unless every step's clusters were made by earlier steps (c < n + i), no cluster is merged twice, size[i] is the
+ * sum of its clusters' sizes, and the dissimilarities are sorted and not NaN.
+ * scanrs_hclust_steps fills n - 1 entries of each array that is not NULL. scanrs_hclust_leaves fills the n observations left to right
+ * under SimpleOrdering (:74-116): NAIVE keeps the smaller cluster name on the left (:150-161), MODULAR_SMALLEST the side whose
+ * smallest dissimilarity is <= the other's (:176-193). scanrs_hclust_merge_below unions every step with dissimilarity < threshold
+ * (strictly) and labels the observations 1, 2, .. in order of first appearance. scanrs_hclust_fcluster: all ones for num_clusters
+ * <= 1, otherwise merge_below(steps[n saturating_sub num_clusters].dissimilarity), so num_clusters >= n leaves every observation
+ * alone and tied heights may give more clusters than asked for.
+ * scanrs_hclust_info fills up to 7 values: [0] chain steps taken, [1] kernel launches issued, [2] batches of steps the host waited
+ * for, [3] bytes of the distance matrix, [4] / [5] MICROSECONDS of the distance pass / of the chain between HIP events, [6] merges
+ * made (n - 1). A handle from scanrs_hclust_from_steps reports zeros but [6].
+ * scanrs_host_hclust_linkage (host only; tests and small inputs, n <= 20000): the same chain in plain C++ on n x d compact
+ * observations, with the same tie rule, update formulas (csrc/hclust_lw.hpp) and summation order; the device result equals it bit
+ * for bit. scanrs_debug_hclust_pdist: the device distance pass alone on x (n x d, leading dimension ld), squared or not, as a
+ * condensed array in scanrs_host_pdist's order (n <= 8192). */
+typedef struct scanrs_hclust scanrs_hclust;
+enum { /* kodama::Method's order */
+    SCANRS_LINKAGE_SINGLE = 0,
+    SCANRS_LINKAGE_COMPLETE = 1,
+    SCANRS_LINKAGE_AVERAGE = 2,
+    SCANRS_LINKAGE_WEIGHTED = 3,
+    SCANRS_LINKAGE_WARD = 4,
+    SCANRS_LINKAGE_CENTROID = 5, /* not provided */
+    SCANRS_LINKAGE_MEDIAN = 6    /* not provided */
+};
+enum { SCANRS_CLUSTER_ROWS = 0, SCANRS_CLUSTER_COLUMNS = 1 };       /* ClusterDirection (:30-35) */
+enum { SCANRS_LEAF_NAIVE = 0, SCANRS_LEAF_MODULAR_SMALLEST = 1 }; /* LeafOrdering (:53-59) */
+int scanrs_hclust_create(const double *x, uint64_t rows, uint64_t cols, uint64_t ld, int direction, int method, const scanrs_snoop *snoop,
+                         scanrs_hclust **out);
+int scanrs_hclust_create_device(const double *d_x, uint64_t rows, uint64_t cols, uint64_t ld, int direction, int method,
+                                const scanrs_snoop *snoop, scanrs_hclust **out);
+int scanrs_hclust_from_steps(uint64_t n, const uint32_t *c1, const uint32_t *c2, const double *diss, const uint32_t *size, scanrs_hclust **out);
+void scanrs_hclust_free(scanrs_hclust *h);
+int scanrs_hclust_n(const scanrs_hclust *h, uint64_t *n);
+int scanrs_hclust_steps(const scanrs_hclust *h, uint32_t *c1, uint32_t *c2, double *diss, uint32_t *size);
+int scanrs_hclust_leaves(const scanrs_hclust *h, int ordering, uint32_t *out);
+int scanrs_hclust_merge_below(const scanrs_hclust *h, double threshold, uint32_t *labels);
+int scanrs_hclust_fcluster(const scanrs_hclust *h, uint64_t num_clusters, uint32_t *labels);
+int scanrs_hclust_info(const scanrs_hclust *h, uint64_t *out, uint32_t n_out);
+int scanrs_host_hclust_linkage(const double *x, uint64_t n, uint32_t d, int method, uint32_t *c1, uint32_t *c2, double *diss, uint32_t *size);
+int scanrs_debug_hclust_pdist(const double *x, uint64_t n, uint32_t d, uint64_t ld, int squared, double *out_condensed);
+
 /* ---- knn over sharded and multi-GPU score matrices ----------------------------------------------------------------
  * knn(v, k) / find_nn (nn.rs:38-83) where the scores stay sharded: every rank owns the queries of its own cells, the point set
  * passes by in global blocks of "knn_block_rows" rows (each block reaches every rank through ONE u64 all-reduce of the rows' bit

@@ -1134,6 +1134,95 @@ inline std::vector<double> cluster_medoids(const MultiMat &m, bool transposed, c
 }
 } // namespace cluster
 
+// hclust/src/lib.rs: HierarchicalCluster over a Euclidean dendrogram made on the device
+namespace hclust {
+enum class LinkageMethod : int { Single = 0, Complete = 1, Average = 2, Weighted = 3, Ward = 4, Centroid = 5, Median = 6 }; // kodama::Method
+enum class ClusterDirection : int { Rows = 0, Columns = 1 };                                                              // :30-35
+enum class LeafOrdering : int { Naive = 0, ModularSmallest = 1 };                                                         // :53-59
+
+struct Steps { // kodama::Dendrogram's steps, n - 1 entries each
+    std::vector<uint32_t> cluster1, cluster2, size;
+    std::vector<double> dissimilarity;
+};
+
+class HierarchicalCluster {
+    scanrs_hclust *h_ = nullptr;
+    explicit HierarchicalCluster(scanrs_hclust *h) : h_(h) {}
+
+  public:
+    // HierarchicalCluster::new (:132-148): x is rows x cols, leading dimension ld, in host memory or (x_is_device) in device memory
+    HierarchicalCluster(const double *x, bool x_is_device, uint64_t rows, uint64_t cols, uint64_t ld, LinkageMethod method, ClusterDirection direction,
+                        Snoop *snoop = nullptr) {
+        scanrs_snoop sn = detail::make_snoop(snoop);
+        check((x_is_device ? scanrs_hclust_create_device : scanrs_hclust_create)(x, rows, cols, ld, (int)direction, (int)method, snoop ? &sn : nullptr, &h_));
+    }
+    HierarchicalCluster(const Array2 &a, LinkageMethod method, ClusterDirection direction, Snoop *snoop = nullptr)
+        : HierarchicalCluster(a.data.data(), false, a.rows, a.cols, a.cols, method, direction, snoop) {}
+    static HierarchicalCluster from_steps(const Steps &s) { // a given, already sorted dendrogram (host only)
+        scanrs_hclust *h = nullptr;
+        check(scanrs_hclust_from_steps(s.cluster1.size() + 1, s.cluster1.data(), s.cluster2.data(), s.dissimilarity.data(), s.size.data(), &h));
+        return HierarchicalCluster(h);
+    }
+    HierarchicalCluster(const HierarchicalCluster &) = delete;
+    HierarchicalCluster &operator=(const HierarchicalCluster &) = delete;
+    HierarchicalCluster(HierarchicalCluster &&o) noexcept : h_(o.h_) { o.h_ = nullptr; }
+    HierarchicalCluster &operator=(HierarchicalCluster &&o) noexcept {
+        if (this != &o) {
+            scanrs_hclust_free(h_);
+            h_ = o.h_;
+            o.h_ = nullptr;
+        }
+        return *this;
+    }
+    ~HierarchicalCluster() { scanrs_hclust_free(h_); }
+    scanrs_hclust *raw() const { return h_; }
+    uint64_t observations() const {
+        uint64_t n = 0;
+        check(scanrs_hclust_n(h_, &n));
+        return n;
+    }
+    Steps steps() const {
+        const uint64_t m = observations() - 1;
+        Steps s{std::vector<uint32_t>(m), std::vector<uint32_t>(m), std::vector<uint32_t>(m), std::vector<double>(m)};
+        check(scanrs_hclust_steps(h_, s.cluster1.data(), s.cluster2.data(), s.dissimilarity.data(), s.size.data()));
+        return s;
+    }
+    std::vector<uint32_t> leaves(LeafOrdering ordering) const { // :201-206
+        std::vector<uint32_t> out(observations());
+        check(scanrs_hclust_leaves(h_, (int)ordering, out.data()));
+        return out;
+    }
+    std::vector<uint32_t> merge_clusters_below_distance_threshold(double threshold) const { // :210-227
+        std::vector<uint32_t> out(observations());
+        check(scanrs_hclust_merge_below(h_, threshold, out.data()));
+        return out;
+    }
+    std::vector<uint32_t> fcluster(uint64_t num_clusters) const { // :231-239
+        std::vector<uint32_t> out(observations());
+        check(scanrs_hclust_fcluster(h_, num_clusters, out.data()));
+        return out;
+    }
+    // chain steps, launches, batches, bytes of the matrix, microseconds of the distance pass and of the chain, merges
+    std::array<uint64_t, 7> info() const {
+        std::array<uint64_t, 7> out{};
+        check(scanrs_hclust_info(h_, out.data(), 7));
+        return out;
+    }
+};
+// the host twin of the device chain (tests and small inputs): x is n x d compact
+inline Steps host_linkage(const std::vector<double> &x, uint64_t n, uint32_t d, LinkageMethod method) {
+    const uint64_t m = n ? n - 1 : 0;
+    Steps s{std::vector<uint32_t>(m), std::vector<uint32_t>(m), std::vector<uint32_t>(m), std::vector<double>(m)};
+    check(scanrs_host_hclust_linkage(x.data(), n, d, (int)method, s.cluster1.data(), s.cluster2.data(), s.dissimilarity.data(), s.size.data()));
+    return s;
+}
+inline std::vector<double> debug_pdist(const std::vector<double> &x, uint64_t n, uint32_t d, uint64_t ld, bool squared) {
+    std::vector<double> out(n ? n * (n - 1) / 2 : 0);
+    check(scanrs_debug_hclust_pdist(x.data(), n, d, ld, squared ? 1 : 0, out.data()));
+    return out;
+}
+} // namespace hclust
+
 // nn::knn (nn.rs:38-83) where the scores stay sharded: global indices, equal to `knn` of the whole point set bit for bit
 struct KnnResult {
     std::vector<uint32_t> indices; // rows x k, nearest first, UINT32_MAX padded

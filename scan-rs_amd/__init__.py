@@ -1740,6 +1740,9 @@ EXPORTED_SYMBOLS = [
     "scanrs_host_betainc", "scanrs_host_betaincinv", "scanrs_sseq_de_pairs", "scanrs_host_union_median",
     "scanrs_host_pdist", "scanrs_host_linkage_complete", "scanrs_host_relabel_by_size", "scanrs_cluster_medoids", "scanrs_cluster_medoids_device",
     "scanrs_merge_clusters",
+    "scanrs_hclust_create", "scanrs_hclust_create_device", "scanrs_hclust_from_steps", "scanrs_hclust_free", "scanrs_hclust_n", "scanrs_hclust_steps",
+    "scanrs_hclust_leaves", "scanrs_hclust_merge_below", "scanrs_hclust_fcluster", "scanrs_hclust_info", "scanrs_host_hclust_linkage",
+    "scanrs_debug_hclust_pdist",
     "scanrs_mat_select_rows", "scanrs_mat_select_cols", "scanrs_mat_partition_on_thresholds", "scanrs_mat_to_csmat",
     "scanrs_mat_select_rows_sharded", "scanrs_mat_select_cols_sharded", "scanrs_mat_partition_on_thresholds_sharded", "scanrs_mat_shard_info",
     "scanrs_multi_shape", "scanrs_multi_to_csmat", "scanrs_multi_select_rows", "scanrs_multi_select_cols", "scanrs_multi_partition_on_thresholds",
@@ -1763,4 +1766,9 @@ from .sseq import (  # noqa: E402
 # merge_clusters, linkage and medoids (cluster.py)
 from .cluster import (  # noqa: E402
     MergeTrace, cluster_medoids, cluster_medoids_sharded, linkage, medioids, merge_clusters, merge_clusters_sharded, pdist, relabel_by_size,
+)
+
+# hierarchical clustering with leaf ordering (hclust.py)
+from .hclust import (  # noqa: E402
+    ClusterDirection, DeviceArray2, HierarchicalCluster, LeafOrdering, LinkageMethod,
 )

@@ -35,6 +35,45 @@ static inline uint64_t utidx(uint64_t m, uint64_t a, uint64_t b) {
     return a < b ? m * a - (a * (a + 1) / 2) + b - a - 1 : m * b - (b * (b + 1) / 2) + a - b - 1;
 }
 
+// sort_by_column(z, 2) and relabel (linkage.rs:160-216), which is also kodama's naming of a dendrogram (hclust_host.cpp): the m - 1
+// merges [a, b, distance, .] in discovery order -> rows by (distance, discovery row), the cluster made by sorted row r named m + r,
+// the smaller name first, sizes from the union-find
+void cluster_sort_relabel(const double *z, uint64_t m, double *z_out) {
+    // sort_by_column: rows by (distance, original row)
+    std::vector<uint64_t> ord(m - 1);
+    for (uint64_t i = 0; i + 1 < m; i++) ord[i] = i;
+    std::sort(ord.begin(), ord.end(), [&](uint64_t p, uint64_t q) {
+        const double u = z[p * 4 + 2], v = z[q * 4 + 2];
+        return u < v || (u == v && p < q);
+    });
+    // relabel through the union-find
+    std::vector<uint64_t> parents(2 * m - 1), usz(2 * m - 1, 1);
+    for (uint64_t i = 0; i < 2 * m - 1; i++) parents[i] = i;
+    uint64_t next = m;
+    auto find = [&](uint64_t i) {
+        uint64_t p = i;
+        while (parents[i] != i) i = parents[i];
+        while (parents[p] != i) {
+            p = parents[p];
+            parents[p] = i;
+        }
+        return i;
+    };
+    for (uint64_t r = 0; r + 1 < m; r++) {
+        const double *row = &z[ord[r] * 4];
+        const uint64_t pa = find((uint64_t)row[0]), pb = find((uint64_t)row[1]);
+        double *o = &z_out[r * 4];
+        o[0] = (double)std::min(pa, pb);
+        o[1] = (double)std::max(pa, pb);
+        o[2] = row[2];
+        parents[pa] = next;
+        parents[pb] = next;
+        usz[next] = usz[pa] + usz[pb];
+        o[3] = (double)usz[next];
+        next++;
+    }
+}
+
 // nn_chain (linkage.rs:72-158) with max, sort_by_column(z, 2) and relabel (:160-216)
 void cluster_linkage_complete(const double *x, uint64_t m, uint32_t d, double *z_out) {
     if (m == 0) fail(SCANRS_ERR_ARGUMENT, "linkage of no points");
@@ -90,39 +129,7 @@ void cluster_linkage_complete(const double *x, uint64_t m, uint32_t d, double *z
             dist[utidx(m, j, b)] = std::max(ja, jb); // f64::max (no NaN here)
         }
     }
-    // sort_by_column: rows by (distance, original row)
-    std::vector<uint64_t> ord(m - 1);
-    for (uint64_t i = 0; i + 1 < m; i++) ord[i] = i;
-    std::sort(ord.begin(), ord.end(), [&](uint64_t p, uint64_t q) {
-        const double u = z[p * 4 + 2], v = z[q * 4 + 2];
-        return u < v || (u == v && p < q);
-    });
-    // relabel through the union-find
-    std::vector<uint64_t> parents(2 * m - 1), usz(2 * m - 1, 1);
-    for (uint64_t i = 0; i < 2 * m - 1; i++) parents[i] = i;
-    uint64_t next = m;
-    auto find = [&](uint64_t i) {
-        uint64_t p = i;
-        while (parents[i] != i) i = parents[i];
-        while (parents[p] != i) {
-            p = parents[p];
-            parents[p] = i;
-        }
-        return i;
-    };
-    for (uint64_t r = 0; r + 1 < m; r++) {
-        const double *row = &z[ord[r] * 4];
-        const uint64_t pa = find((uint64_t)row[0]), pb = find((uint64_t)row[1]);
-        double *o = &z_out[r * 4];
-        o[0] = (double)std::min(pa, pb);
-        o[1] = (double)std::max(pa, pb);
-        o[2] = row[2];
-        parents[pa] = next;
-        parents[pb] = next;
-        usz[next] = usz[pa] + usz[pb];
-        o[3] = (double)usz[next];
-        next++;
-    }
+    cluster_sort_relabel(z.data(), m, z_out);
 }
 
 // relabel_by_size (merge_clusters.rs:43-56)

@@ -901,6 +901,18 @@ void cluster_medoids(hipStream_t s, const double *d_scores, uint64_t n, uint32_t
 void merge_clusters_run(Storage &st, const SparseCopy &cp, bool gene_major, uint64_t genes, uint64_t cells, const double *d_scores, uint32_t ld,
                         uint32_t d, const int16_t *labels, int16_t *labels_out, const scanrs_snoop *snoop, scanrs_merge_trace *trace,
                         bool collective = false);
+// the m - 1 merges [a, b, distance, .] in discovery order -> rows by (distance, discovery row), named through the union-find
+void cluster_sort_relabel(const double *z, uint64_t m, double *z_out);
+
+// ---- hclust.hip / hclust_host.cpp: hierarchical clustering (hclust/src/lib.rs) -----------------------------------------------------
+// d_obs (n x d compact) from x (rows or columns of it are the observations); *d_bad = the first element of x that is not finite, or all ones
+void launch_hclust_pack(hipStream_t s, const double *d_x, uint64_t n, uint32_t d, uint64_t ld, int by_cols, double *d_obs, unsigned long long *d_bad);
+// d_dist: the full symmetric n x n matrix of (squared) Euclidean distances; *d_bad_pair (may be null) = the first pair i * n + j, i < j,
+// whose distance is not finite, or all ones
+void launch_hclust_pdist(hipStream_t s, const double *d_obs, uint64_t n, uint32_t d, int squared, double *d_dist, unsigned long long *d_bad_pair);
+// one step of the nearest-neighbour chain, two launches: d_ctr = {chain length, merges, steps, error}, d_rec 5 u32
+void launch_hclust_step(hipStream_t s, double *d_dist, uint32_t n, int method, uint32_t *d_chain, uint32_t *d_size, unsigned long long *d_ctr,
+                        uint32_t *d_rec, uint32_t *d_ma, uint32_t *d_mb, double *d_mh, uint32_t *d_msize);
 
 // ---- select.hip / select_host.cpp: select_rows, select_cols, partition_on_thresholds (sqz/src/mat.rs:730-888, 1004-1071) ---------
 void launch_sel_outer_sums(hipStream_t s, const SparseCopy &cp, const uint8_t *excl_outer, const uint8_t *excl_inner, unsigned long long *out);
