@@ -1295,6 +1295,20 @@ int scanrs_host_col_moments_plan(uint32_t max_count, uint32_t n_links, const int
 int scanrs_host_spmm_route(const double *options, uint64_t n_outer, uint64_t n_inner, uint64_t nnz, uint32_t l, uint32_t ldx,
                            uint32_t n_links, const int *kinds, const int *a_outer, uint32_t flags, uint64_t *out);
 
+/* ---- the projection plan of svd_bk (host only, no device): csrc/bk_plan.hpp, the source the solver decides by ---------------------
+ * svd_bk forms its projection as T' = (op(A) K) C from the half-products of its iterations; a column of Q whose coefficient column
+ * reaches the bound "reuse_cmax" is recomputed by a sparse product instead. colmax[n]: max |C| per column of Q, n = b * n_iter
+ * (b the block width, even for the scheme to apply); coef_valid = 0 when a rank-deficient panel was completed on the host, which voids
+ * the coefficients. out[7]: 1 when b is even, the older blocks' columns at or above reuse_cmax (before any raise), the branch of the
+ * raise rule (as the counter "bk_limit_branch"), the number of direct columns, 1 when the whole last block is among them, 1 when the
+ * projection is one n-wide product instead, the blocks projected beside the sparse passes. limit: the bound finally used;
+ * cmax_dense: the largest entry of colmax among the columns that take the dense route (0 without one); direct[n]: the first out[3]
+ * entries are the direct columns in the order the repair pass carries them (older blocks ascending, then the last block).
+ * Refused (SCANRS_ERR_ARGUMENT): b = 0, n_iter = 0, n != b * n_iter, a negative or non-finite entry of colmax, reuse_cmax that is
+ * not positive. */
+int scanrs_host_bk_plan(const double *colmax, uint64_t n, uint32_t b, uint32_t n_iter, double reuse_cmax, int coef_valid, uint64_t *out,
+                        double *limit, double *cmax_dense, uint32_t *direct);
+
 /* ---- 10x HDF5 ingestion (hdf5-io/src/matrix.rs, analysis.rs). Host-side; no device needed.
  * The files are parsed by the library's own reader (csrc/h5lite.cpp) — no libhdf5 dependency. Failures are
  * SCANRS_ERR_IO with the reason in scanrs_last_error(). ------------------------------------------------------------ */

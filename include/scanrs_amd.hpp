@@ -1266,6 +1266,22 @@ inline ColMomentsPlan host_col_moments_plan(uint32_t max_count, const std::vecto
     p.accept = accept != 0;
     return p;
 }
+// the projection plan of svd_bk on the host, from max |C| per column of Q (colmax.size() == b * n_iter)
+struct BkPlan {
+    bool reuse = false, last_direct = false, full_direct = false;
+    uint64_t flagged_older = 0, limit_branch = 0, n_early = 0;
+    double limit = 0.0, cmax_dense = 0.0;
+    std::vector<uint32_t> direct;
+};
+inline BkPlan host_bk_plan(const std::vector<double> &colmax, uint32_t b, uint32_t n_iter, double reuse_cmax = 1e5, bool coef_valid = true) {
+    BkPlan p;
+    uint64_t out[7] = {};
+    p.direct.assign(colmax.size() + 1, 0u);
+    check(scanrs_host_bk_plan(colmax.data(), colmax.size(), b, n_iter, reuse_cmax, coef_valid ? 1 : 0, out, &p.limit, &p.cmax_dense, p.direct.data()));
+    p.reuse = out[0] != 0, p.flagged_older = out[1], p.limit_branch = out[2], p.last_direct = out[4] != 0, p.full_direct = out[5] != 0, p.n_early = out[6];
+    p.direct.resize((size_t)out[3]);
+    return p;
+}
 
 namespace mtx {
 // scan_rs::mtx::load_mtx (scan-rs/src/mtx.rs:10-51): the CSR arrays; `.to_device()` is the AdaptiveMat the reference returns

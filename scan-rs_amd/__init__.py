@@ -1597,6 +1597,21 @@ def host_spmm_route(n_outer: int, n_inner: int, nnz: int, l: int, ldx: int, link
     return tuple(int(v) for v in out)
 
 
+def host_bk_plan(colmax, b: int, n_iter: int, reuse_cmax: float = 1e5, coef_valid: bool = True):
+    """The projection plan of svd_bk on the host (`scanrs_host_bk_plan`; scan-rs_amd/csrc/bk_plan.hpp, the source solver.cpp decides
+    by). `colmax`: max |C| per column of Q, b * n_iter entries. Returns a dict with reuse, flagged_older (before any raise),
+    limit_branch, limit, direct (tuple, in the order the repair pass carries the columns), last_direct, full_direct, n_early and
+    cmax_dense, as scanrs_amd.h documents."""
+    cm = _f64(colmax).reshape(-1)
+    out, limit, dense = (ctypes.c_uint64 * 7)(), ctypes.c_double(), ctypes.c_double()
+    direct = np.zeros(cm.size + 1, dtype=np.uint32)
+    _check(_lib.scanrs_host_bk_plan(_p(cm), ctypes.c_uint64(cm.size), ctypes.c_uint32(int(b)), ctypes.c_uint32(int(n_iter)), ctypes.c_double(float(reuse_cmax)),
+                                    ctypes.c_int(1 if coef_valid else 0), out, ctypes.byref(limit), ctypes.byref(dense), _p(direct)))
+    return dict(reuse=bool(out[0]), flagged_older=int(out[1]), limit_branch=int(out[2]), limit=float(limit.value),
+                direct=tuple(int(j) for j in direct[:int(out[3])]), last_direct=bool(out[4]), full_direct=bool(out[5]), n_early=int(out[6]),
+                cmax_dense=float(dense.value))
+
+
 def knn_device(d_points: int, n: int, ld: int, d: int, k: int):
     """`nn::knn` on scores that already live in device memory (e.g. PcaResultDevice.d_v / ld_v): (n x k) u32 host array."""
     out = np.zeros((n, k), dtype=np.uint32)
@@ -1747,7 +1762,7 @@ EXPORTED_SYMBOLS = [
     "scanrs_mat_select_rows_sharded", "scanrs_mat_select_cols_sharded", "scanrs_mat_partition_on_thresholds_sharded", "scanrs_mat_shard_info",
     "scanrs_multi_shape", "scanrs_multi_to_csmat", "scanrs_multi_select_rows", "scanrs_multi_select_cols", "scanrs_multi_partition_on_thresholds",
     "scanrs_mat_to_adaptive", "scanrs_adaptive_export_info", "scanrs_adaptive_export_vecs", "scanrs_adaptive_export_free",
-    "scanrs_host_choose_storage", "scanrs_host_col_moments_plan", "scanrs_host_spmm_route",
+    "scanrs_host_choose_storage", "scanrs_host_col_moments_plan", "scanrs_host_spmm_route", "scanrs_host_bk_plan",
     "scanrs_mat_sum_rows_u64", "scanrs_mat_sum_rows_f64", "scanrs_mat_sum_cols_u64", "scanrs_mat_sum_cols_f64", "scanrs_mat_sum_rows_dual_u64",
     "scanrs_mat_sum_rows_dual_f64", "scanrs_mat_mean_rows", "scanrs_mat_mean_var_rows", "scanrs_mat_var_axis",
     "scanrs_mat_sum_rows_u64_sharded", "scanrs_mat_sum_rows_f64_sharded", "scanrs_mat_sum_cols_u64_sharded", "scanrs_mat_sum_cols_f64_sharded",

@@ -7,6 +7,7 @@
 
 #include "common.hpp"
 #include "col_moments_plan.hpp"
+#include "bk_plan.hpp"
 #include "spmm_route.hpp"
 #include "shard_exchange.hpp"
 
@@ -1220,6 +1221,22 @@ int scanrs_host_spmm_route(const double *options, uint64_t n_outer, uint64_t n_i
         const SpmmRoute r = spmm_route(q, (flags & SCANRS_SPMM_TILES_AVAILABLE) != 0);
         out[0] = (uint64_t)r.family, out[1] = r.form_bits(), out[2] = r.chunk_bits(), out[3] = r.family == SPMM_TILES ? r.chunk_width : 0, out[4] = r.even_ld ? 1 : 0;
         out[5] = tiles_static_candidate(q) ? 1 : 0;
+    });
+}
+int scanrs_host_bk_plan(const double *colmax, uint64_t n, uint32_t b, uint32_t n_iter, double reuse_cmax, int coef_valid, uint64_t *out,
+                        double *limit, double *cmax_dense, uint32_t *direct) {
+    return guard([&] {
+        if (!colmax || !out || !limit || !cmax_dense || !direct) fail(SCANRS_ERR_ARGUMENT, "null argument");
+        if (b == 0 || n_iter == 0) fail(SCANRS_ERR_ARGUMENT, "bk_plan: b and n_iter must be positive");
+        if (n != (uint64_t)b * n_iter || n > 0xFFFFFFFFull) fail(SCANRS_ERR_ARGUMENT, "bk_plan: colmax must hold b * n_iter entries");
+        for (uint64_t j = 0; j < n; j++)
+            if (!std::isfinite(colmax[j]) || colmax[j] < 0.0) fail(SCANRS_ERR_ARGUMENT, "bk_plan: colmax must be finite and non-negative");
+        if (!(reuse_cmax > 0.0)) fail(SCANRS_ERR_ARGUMENT, "reuse_cmax must be positive");
+        const BkPlan p = bk_plan(colmax, b, n_iter, reuse_cmax, coef_valid != 0);
+        out[0] = p.reuse, out[1] = p.flagged_older, out[2] = (uint64_t)p.limit_branch, out[3] = p.direct.size(), out[4] = p.last_direct;
+        out[5] = p.full_direct, out[6] = p.n_early;
+        *limit = p.limit, *cmax_dense = p.cmax_dense;
+        std::copy(p.direct.begin(), p.direct.end(), direct);
     });
 }
 int scanrs_debug_knn_filter(const double *queries, uint64_t n_q, const double *points, uint64_t n_p, uint32_t d, const double *tau,

@@ -21,6 +21,7 @@
 #include <thread>
 #include <vector>
 
+#include "bk_plan.hpp"
 #include "common.hpp"
 #include "host_team.hpp"
 
@@ -220,6 +221,31 @@ struct StreamSwap {
         st.stream = saved;
         st.scratch.stream = saved_scratch;
     }
+};
+// A solver queues work far ahead of the device: whatever ends its call early (cancellation, a numerical failure) waits for
+// every stream before the scratch buffers change hands
+struct Drain {
+    Storage &st;
+    int n0 = std::uncaught_exceptions();
+    ~Drain() {
+        if (std::uncaught_exceptions() > n0) {
+            try {
+                st.side_join_if(nullptr, true); // the helper thread that builds the second orientation, if it still runs
+            } catch (const Failure &) {
+            }
+            for_each_stream(st, [](const char *, hipStream_t q) { (void)wait_stream_quiet(q); });
+        }
+    }
+};
+struct Ev {
+    hipEvent_t e = nullptr;
+    Ev() { SCANRS_HIP(hipEventCreateWithFlags(&e, hipEventDisableTiming)); }
+    ~Ev() { (void)hipEventDestroy(e); }
+};
+struct AddElapsedUs { // the scope's wall time, added to a counter
+    uint64_t &t;
+    std::chrono::steady_clock::time_point t0 = std::chrono::steady_clock::now();
+    ~AddElapsedUs() { t += (uint64_t)std::chrono::duration<double, std::micro>(std::chrono::steady_clock::now() - t0).count(); }
 };
 
 // upload a compact host matrix (rows x l) into a padded device panel
@@ -959,189 +985,217 @@ static void pca_dev_swap(Storage &st) {
     std::swap(st.pca_dev.rows_u, st.pca_dev.rows_v);
 }
 
-constexpr int BK_RETRY_ON_HOST = -1000; // device-side factorizations did not converge: run again with host factorizations
-static int pca_bk_impl(scanrs_mat *m, uint32_t k, double k_multiplier, uint32_t n_iter, uint64_t seed, const double *omega,
-                       const scanrs_snoop *snoop, double *u, double *s, double *v, bool device_factor) {
-    Tick tk_all("bk: total");
-    Ctx c(m);
-    stage_mark("bk setup");
-    // work is queued far ahead of the device here: whatever ends this call early (cancellation, a numerical failure) waits for
-    // both streams before the scratch buffers change hands
-    struct Drain {
-        Storage &st;
-        int n0 = std::uncaught_exceptions();
-        ~Drain() {
-            if (std::uncaught_exceptions() > n0) {
-                try {
-                    st.side_join_if(nullptr, true); // the helper thread that builds the second orientation, if it still runs
-                } catch (const Failure &) {
-                }
-                for_each_stream(st, [](const char *, hipStream_t q) { (void)wait_stream_quiet(q); });
-            }
-        }
-    } drain{c.st};
-    const uint64_t M = m->rows(), N = m->cols();
-    // global extents decide the branch and the validation, as the reference sees the whole matrix
-    const uint64_t Mg = dim_sharded_rows(m) ? c.st.shard.outer_global : M;
-    const uint64_t Ng = dim_sharded_cols(m) ? c.st.shard.outer_global : N;
+// The ending of svd_bk and svd_rand: Q is orthonormal on side S, T = op(A) Q on the other side. Side S holds V exactly when it is
+// the cols side (s_is_cols: svd_bk's Krylov side for m >= n, svd_rand's Q side for n > m); then the caller's v takes side S and
+// pca_dev's (u, v) are swapped.
+static void ritz_finish_uv(Ctx &c, const double *Q, uint32_t ldq, uint32_t q, uint64_t ds, const double *T, uint32_t ldt, uint64_t dt,
+                           bool t_sharded, uint32_t k, bool s_is_cols, double *u, double *s, double *v) {
+    ritz_finish(c, Q, ldq, q, ds, T, ldt, dt, t_sharded, k, s_is_cols ? v : u, s, s_is_cols ? u : v);
+    if (s_is_cols) pca_dev_swap(c.st);
+}
+
+// global extents decide the branch and the validation, as the reference sees the whole matrix
+struct Extents {
+    uint64_t Mg, Ng;
+};
+static Extents global_extents(scanrs_mat *m, uint32_t k) {
+    const uint64_t Mg = dim_sharded_rows(m) ? m->st->shard.outer_global : m->rows();
+    const uint64_t Ng = dim_sharded_cols(m) ? m->st->shard.outer_global : m->cols();
     if (Mg < 2 || Ng < 2) fail(SCANRS_ERR_SHAPE, "The input matrix must be at least 2x2.");
     if (k > std::min(Mg, Ng)) fail(SCANRS_ERR_INVALID_K, "invalid k");
-    if (k == 0 || n_iter == 0) fail(SCANRS_ERR_ARGUMENT, "k and n_iter must be positive");
-    uint32_t b = (uint32_t)std::ceil((double)k * k_multiplier); // bk_svd.rs:49
-    b = (uint32_t)std::min<uint64_t>(std::min(Mg, Ng), b);     // bk_svd.rs:81
-    if (b < k) fail(SCANRS_ERR_INVALID_K, "invalid k");
-    c.st.bk = Storage::BkDecisions{}; // the decisions of THIS run (a retry on the host path starts them again)
-    c.st.bk.b = b;
+    return {Mg, Ng};
+}
 
-    const bool rows_ge = Mg >= Ng; // bk_svd.rs:89 `if m >= n`
-    // S = the side the Krylov panel lives on (the shorter one): cols when m >= n, rows otherwise.
-    const uint64_t ds = rows_ge ? N : M, dt = rows_ge ? M : N;
-    const bool s_sharded = rows_ge ? dim_sharded_cols(m) : dim_sharded_rows(m);
-    const bool t_sharded = rows_ge ? dim_sharded_rows(m) : dim_sharded_cols(m);
-    if (s_sharded) fail(SCANRS_ERR_ARGUMENT, "shard the longer dimension of the matrix, not the shorter one");
-    // op S->T: A*X when m >= n (X on the cols side), A^T*X otherwise
-    const bool to_t_transpose = !rows_ge;
-
-    if ((uint64_t)b * n_iter > ds) {
-        // The Krylov matrix K (ds x b n_iter) is wider than it is tall: `K.qr()` (bk_svd.rs:98,127) then returns a square Q
-        // spanning the whole side, T = Q^T A loses nothing and the driver returns the exact truncated SVD (small feature
-        // panels: antibody / targeted-gene matrices, k close to min(m, n)). Any orthonormal basis of the whole space gives
-        // the same singular triplets, so Q = I: one sparse product with the identity panel, then the Rayleigh-Ritz finish.
-        const uint32_t qe = (uint32_t)ds, ldqe = even_up(qe);
-        c.st.bk.q = qe;
-        double *Ke = c.dev("bk_K", (size_t)ds * ldqe);
-        double *Te = c.dev("bk_T", (size_t)dt * ldqe);
-        std::vector<double> eye((size_t)ds * qe, 0.0);
-        for (uint32_t i = 0; i < qe; i++) eye[(size_t)i * qe + i] = 1.0;
-        SCANRS_HIP(hipMemsetAsync(Ke, 0, (size_t)ds * ldqe * 8, c.s));
-        upload_panel(c, eye.data(), ds, qe, Ke, ldqe);
-        for (uint32_t i = 0; i < n_iter; i++) snoop_poll(snoop, (double)i / (double)n_iter * 0.8); // the reference's poll points
-        mat_apply(m, to_t_transpose, Ke, ldqe, qe, Te, ldqe);
+// The start panel of svd_bk / svd_rand: l columns on a side of dimension d, seeded or the caller's. Reference order: (d x l)
+// row-major when m >= n, else (l x d) row-major, held transposed here. A given panel has l_src >= l columns (rows): the leading l.
+static void fill_start_panel(Ctx &c, bool rows_ge, uint64_t seed, const double *omega, uint32_t l_src, uint64_t d, uint32_t l, double *P,
+                             uint32_t ld, const char *transpose_key) {
+    if (!omega) {
+        if (rows_ge)
+            omega_fill_device(c.st, seed, d, l, P, ld, false);
+        else
+            omega_fill_device(c.st, seed, l, d, P, ld, true);
+    } else if (rows_ge) {
+        SCANRS_HIP(hipMemcpy2DAsync(P, (size_t)ld * 8, omega, (size_t)l_src * 8, (size_t)l * 8, d, hipMemcpyHostToDevice, c.s));
         c.sync();
-        snoop_poll(snoop, 0.93);
-        if (rows_ge) {
-            ritz_finish(c, Ke, ldqe, qe, ds, Te, ldqe, dt, t_sharded, k, v, s, u);
-            pca_dev_swap(c.st);
-        } else {
-            ritz_finish(c, Ke, ldqe, qe, ds, Te, ldqe, dt, t_sharded, k, u, s, v);
-        }
-        snoop_poll(snoop, 1.0);
-        return SCANRS_OK;
+    } else {
+        double *tmp = c.dev(transpose_key, (size_t)l * d);
+        c.h2d(tmp, omega, (size_t)l * d);
+        launch_transpose(c.st, tmp, l, d, P, ld);
     }
-    // the copy / tile layout of the SECOND product on a helper thread, beside everything up to the end of the first pass
-    prepare_second_orientation(m, !to_t_transpose);
-    const uint32_t ldb = even_up(b), q = b * n_iter, ldq = even_up(q);
-    c.st.bk.q = q;
-    double *P = c.dev("bk_P", (size_t)ds * ldb);
-    double *Ptmp = c.dev("bk_Ptmp", (size_t)ds * ldb);
-    double *Y = c.dev("bk_Y", (size_t)dt * ldb);
-    double *K = c.dev("bk_K", (size_t)ds * ldq);
-    SCANRS_HIP(hipMemsetAsync(P, 0, (size_t)ds * ldb * 8, c.s));
-    SCANRS_HIP(hipMemsetAsync(K, 0, (size_t)ds * ldq * 8, c.s));
+}
 
-    { // start panel: m >= n -> (n x b) as is; n > m -> reference holds (b x m), we hold its transpose
-        Tick tk("bk: start panel");
-        struct Acc {
-            uint64_t &t;
-            std::chrono::steady_clock::time_point t0 = std::chrono::steady_clock::now();
-            ~Acc() { t += (uint64_t)std::chrono::duration<double, std::micro>(std::chrono::steady_clock::now() - t0).count(); }
-        } acc{c.st.t_start_panel_us};
-        if (!omega) {
-            // reference order: (n x b) row-major when m >= n, else (b x m) row-major held transposed here
-            if (rows_ge)
-                omega_fill_device(c.st, seed, ds, b, P, ldb, false);
-            else
-                omega_fill_device(c.st, seed, b, ds, P, ldb, true);
-        } else if (rows_ge) {
-            upload_panel(c, omega, ds, b, P, ldb);
-        } else { // (b x ds) row-major on the host side: transposed on the device
-            double *tmp = c.dev("bk_omega_t", (size_t)b * ds);
-            c.h2d(tmp, omega, (size_t)b * ds);
-            launch_transpose(c.st, tmp, b, ds, P, ldb);
-        }
-    }
+constexpr int BK_RETRY_ON_HOST = -1000; // device-side factorizations did not converge: run again with host factorizations
 
-    // The projection T = Q^T A (bk_svd.rs:104,131) is not recomputed as one q-wide sparse product: with
-    // K = [K_0 .. K_{n-1}] the blocks A^T K_i (resp. A K_i) for i < n-1 are exactly the first half-products of
-    // iterations 1..n-1, so they are written straight into T; one extra b-wide product supplies the last block
-    // and T' = (op(A) K) C with Q = K C (C small, tracked on the host through the orthonormalisation).
-    const bool reuse = (b % 2u) == 0u;
-    const uint64_t fallbacks0 = c.st.orth_fallbacks; // a panel completed with random directions voids Q = K C (orth_host_mgs)
-    double *T = c.dev("bk_T", (size_t)dt * ldq);
-    // Q = qr(K).Q: block i is already orthonormal; orthogonalise it against blocks < i (in block order), tracking
-    // Q = K C in `cfull`
-    std::vector<double> cfull((size_t)q * q, 0.0);
-    for (uint32_t i = 0; i < q; i++) cfull[(size_t)i * q + i] = 1.0;
-    double *Bj = c.dev("bk_Bj", (size_t)ds * ldb);
-    double *Btmp = c.dev("bk_Btmp", (size_t)ds * ldb);
-    uint32_t next_block = 1;
-    // device_factor: the factors and the coefficient matrix stay on the device (orth_*_dev above); the host copy of cfull is
-    // filled once, when the basis is complete
-    const bool dv = device_factor && chol_rinv_ok(b);
-    DevOrth od;
+// One run of svd_bk: the state everything outside the tile kernel shares, and the stages pca_bk_run puts in order.
+//
+// The projection T = Q^T A (bk_svd.rs:104,131) is not recomputed as one q-wide sparse product: with K = [K_0 .. K_{n-1}] the
+// blocks A^T K_i (resp. A K_i) for i < n-1 are exactly the first half-products of iterations 1..n-1, so they are written straight
+// into T; T' = (op(A) K) C with Q = K C (C small, tracked through the orthonormalisation in `cfull`), and bk_plan.hpp decides which
+// columns are recomputed directly instead.
+struct BkRun {
+    scanrs_mat *m;
+    Ctx c;
+    Drain drain{c.st};
+    const scanrs_snoop *snoop;
+    // shape and orientation. S = the side the Krylov panel lives on (the shorter one): cols when m >= n, rows otherwise
+    uint32_t k = 0, n_iter = 0, b = 0, ldb = 0, q = 0, ldq = 0;
+    bool rows_ge = false, t_sharded = false, exact = false, reuse = false;
+    bool to_t_transpose = false; // op S->T: A*X when m >= n (X on the cols side), A^T*X otherwise
+    uint64_t ds = 0, dt = 0;
+    // panels: P the iterated block, K the Krylov matrix and then Q, T the half-products, T2 the projected blocks (reuse)
+    double *P = nullptr, *Ptmp = nullptr, *Y = nullptr, *K = nullptr, *T = nullptr, *T2 = nullptr, *Bj = nullptr, *Btmp = nullptr;
+    // Q = K C. dv: the factors and the coefficient matrix stay on the device (orth_*_dev); the host copy is filled once, when
+    // the basis is complete
+    bool dv = false;
+    std::vector<double> cfull;
     double *cfull_d = nullptr, *coef_d = nullptr, *coef_tmp_d = nullptr;
-    if (dv) {
-        od.init(c, 4u * n_iter + 8u);
-        cfull_d = c.dev("bk_cfull", (size_t)q * ldq);
-        coef_d = c.dev("bk_coef", (size_t)q * ldb);
-        coef_tmp_d = c.dev("bk_coef_tmp", (size_t)q * ldb);
-        SCANRS_HIP(hipMemcpy2DAsync(cfull_d, (size_t)ldq * 8, cfull.data(), (size_t)q * 8, (size_t)q * 8, q, hipMemcpyHostToDevice, c.s));
-        c.sync(); // cfull is pageable host memory
+    DevOrth od;
+    uint64_t fallbacks0 = 0; // a panel completed with random directions voids Q = K C (orth_host_mgs)
+    // one event object per iteration and purpose: an event is never recorded again while a wait on its previous record may still be queued
+    std::vector<Ev> ev_k;    // K block i is in place (main stream)
+    std::vector<Ev> ev_pass; // both passes of iteration i are done (main stream)
+    std::vector<Ev> ev_aux;  // the Gram-Schmidt chain queued in iteration i is done (auxiliary stream)
+    std::vector<Ev> ev_proj; // the projection queued in iteration i is done (projection stream)
+    uint32_t next_block = 1; // the first block of K not yet orthogonalised against its predecessors
+    int last_aux = -1, last_proj = -1;
+    std::vector<char> projected;
+    bool block0_copied = false;
+    std::vector<double> colmax; // max |C| per column of Q (filled when the bookkeeping is used)
+    BkPlan plan;
+
+    BkRun(scanrs_mat *mm, const scanrs_snoop *sn) : m(mm), c(mm), snoop(sn) { stage_mark("bk setup"); }
+
+    void shape(uint32_t k_, double k_multiplier, uint32_t n_iter_) {
+        k = k_, n_iter = n_iter_;
+        const Extents g = global_extents(m, k);
+        if (k == 0 || n_iter == 0) fail(SCANRS_ERR_ARGUMENT, "k and n_iter must be positive");
+        b = bk_block_width(k, k_multiplier, g.Mg, g.Ng);
+        if (b < k) fail(SCANRS_ERR_INVALID_K, "invalid k");
+        c.st.bk = Storage::BkDecisions{}; // the decisions of THIS run (a retry on the host path starts them again)
+        c.st.bk.b = b;
+        rows_ge = g.Mg >= g.Ng; // bk_svd.rs:89 `if m >= n`
+        ds = rows_ge ? m->cols() : m->rows(), dt = rows_ge ? m->rows() : m->cols();
+        t_sharded = rows_ge ? dim_sharded_rows(m) : dim_sharded_cols(m);
+        if (rows_ge ? dim_sharded_cols(m) : dim_sharded_rows(m)) fail(SCANRS_ERR_ARGUMENT, "shard the longer dimension of the matrix, not the shorter one");
+        to_t_transpose = !rows_ge;
+        exact = (uint64_t)b * n_iter > ds;
+        q = exact ? (uint32_t)ds : b * n_iter;
+        ldb = even_up(b), ldq = even_up(q);
+        c.st.bk.q = q;
     }
-    auto orth_block_dev = [&](Ctx &cx, uint32_t i) {
+
+    // The Krylov matrix K (ds x b n_iter) is wider than it is tall: `K.qr()` (bk_svd.rs:98,127) then returns a square Q
+    // spanning the whole side, T = Q^T A loses nothing and the driver returns the exact truncated SVD (small feature
+    // panels: antibody / targeted-gene matrices, k close to min(m, n)). Any orthonormal basis of the whole space gives
+    // the same singular triplets, so Q = I: one sparse product with the identity panel, then the Rayleigh-Ritz finish.
+    void exact_svd(double *u, double *s, double *v) {
+        K = c.dev("bk_K", (size_t)ds * ldq);
+        T = c.dev("bk_T", (size_t)dt * ldq);
+        std::vector<double> eye((size_t)ds * q, 0.0);
+        for (uint32_t i = 0; i < q; i++) eye[(size_t)i * q + i] = 1.0;
+        SCANRS_HIP(hipMemsetAsync(K, 0, (size_t)ds * ldq * 8, c.s));
+        upload_panel(c, eye.data(), ds, q, K, ldq);
+        for (uint32_t i = 0; i < n_iter; i++) snoop_poll(snoop, (double)i / (double)n_iter * 0.8); // the reference's poll points
+        mat_apply(m, to_t_transpose, K, ldq, q, T, ldq);
+        c.sync();
+        ritz(T, u, s, v);
+    }
+
+    void start_panel(uint64_t seed, const double *omega) {
+        // the copy / tile layout of the SECOND product on a helper thread, beside everything up to the end of the first pass
+        prepare_second_orientation(m, !to_t_transpose);
+        P = c.dev("bk_P", (size_t)ds * ldb);
+        Ptmp = c.dev("bk_Ptmp", (size_t)ds * ldb);
+        Y = c.dev("bk_Y", (size_t)dt * ldb);
+        K = c.dev("bk_K", (size_t)ds * ldq);
+        SCANRS_HIP(hipMemsetAsync(P, 0, (size_t)ds * ldb * 8, c.s));
+        SCANRS_HIP(hipMemsetAsync(K, 0, (size_t)ds * ldq * 8, c.s));
+        Tick tk("bk: start panel");
+        AddElapsedUs acc{c.st.t_start_panel_us};
+        fill_start_panel(c, rows_ge, seed, omega, b, ds, b, P, ldb, "bk_omega_t");
+    }
+
+    // the panels and the bookkeeping of Q = qr(K).Q: block i is already orthonormal when it joins K; it is orthogonalised against
+    // blocks < i (in block order), Q = K C tracked in `cfull`
+    void prepare_basis(bool device_factor) {
+        reuse = bk_reuse(b);
+        fallbacks0 = c.st.orth_fallbacks;
+        T = c.dev("bk_T", (size_t)dt * ldq);
+        cfull.assign((size_t)q * q, 0.0);
+        for (uint32_t i = 0; i < q; i++) cfull[(size_t)i * q + i] = 1.0;
+        Bj = c.dev("bk_Bj", (size_t)ds * ldb);
+        Btmp = c.dev("bk_Btmp", (size_t)ds * ldb);
+        dv = device_factor && chol_rinv_ok(b);
+        if (dv) {
+            od.init(c, 4u * n_iter + 8u);
+            cfull_d = c.dev("bk_cfull", (size_t)q * ldq);
+            coef_d = c.dev("bk_coef", (size_t)q * ldb);
+            coef_tmp_d = c.dev("bk_coef_tmp", (size_t)q * ldb);
+            SCANRS_HIP(hipMemcpy2DAsync(cfull_d, (size_t)ldq * 8, cfull.data(), (size_t)q * 8, (size_t)q * 8, q, hipMemcpyHostToDevice, c.s));
+            c.sync(); // cfull is pageable host memory
+        }
+        // Out of place: later blocks still need the half-products in T, so the projected blocks are collected in a second panel T2 of
+        // the same shape, and the Rayleigh-Ritz step reads T2 — nothing is copied back at the end
+        T2 = reuse ? c.dev("bk_T2", (size_t)dt * ldq) : nullptr;
+        ev_k = std::vector<Ev>(n_iter), ev_pass = std::vector<Ev>(n_iter), ev_aux = std::vector<Ev>(n_iter), ev_proj = std::vector<Ev>(n_iter);
+        projected.assign(n_iter, 0);
+    }
+
+    // Block i of K against blocks < i, on cx's stream. Host form: finished (orth_against synchronises) but for the last copies;
+    // device form: queued only, the verdicts are read in finish_basis.
+    void orth_block(Ctx &cx, uint32_t i) {
         launch_copy_cols(cx.st, K + (size_t)i * b, ldq, Bj, ldb, ds, b);
-        launch_copy_cols(cx.st, cfull_d + (size_t)i * b, ldq, coef_d, ldb, q, b); // the identity block
-        orth_against_dev(cx, od, K, ldq, i * b, Bj, Btmp, ldb, b, ds, coef_d, coef_tmp_d, cfull_d, q, ldq);
-        launch_copy_cols(cx.st, Bj, ldb, K + (size_t)i * b, ldq, ds, b);
-        launch_copy_cols(cx.st, coef_d, ldb, cfull_d + (size_t)i * b, ldq, q, b);
+        if (dv) {
+            launch_copy_cols(cx.st, cfull_d + (size_t)i * b, ldq, coef_d, ldb, q, b); // the identity block
+            orth_against_dev(cx, od, K, ldq, i * b, Bj, Btmp, ldb, b, ds, coef_d, coef_tmp_d, cfull_d, q, ldq);
+            launch_copy_cols(cx.st, Bj, ldb, K + (size_t)i * b, ldq, ds, b);
+            launch_copy_cols(cx.st, coef_d, ldb, cfull_d + (size_t)i * b, ldq, q, b);
+        } else {
+            std::vector<double> coef((size_t)q * b, 0.0);
+            for (uint32_t j = 0; j < b; j++) coef[(size_t)(i * b + j) * b + j] = 1.0;
+            orth_against(cx, K, ldq, i * b, Bj, Btmp, ldb, b, ds, false, &coef, &cfull, q);
+            launch_copy_cols(cx.st, Bj, ldb, K + (size_t)i * b, ldq, ds, b);
+            for (uint32_t r = 0; r < q; r++)
+                for (uint32_t j = 0; j < b; j++) cfull[(size_t)r * q + i * b + j] = coef[(size_t)r * b + j];
+        }
         next_block = i + 1;
-    };
-    auto orth_block_on = [&](Ctx &cx, uint32_t i) {
-        std::vector<double> coef((size_t)q * b, 0.0);
-        launch_copy_cols(cx.st, K + (size_t)i * b, ldq, Bj, ldb, ds, b);
-        for (uint32_t j = 0; j < b; j++) coef[(size_t)(i * b + j) * b + j] = 1.0;
-        orth_against(cx, K, ldq, i * b, Bj, Btmp, ldb, b, ds, false, &coef, &cfull, q);
-        launch_copy_cols(cx.st, Bj, ldb, K + (size_t)i * b, ldq, ds, b);
-        for (uint32_t r = 0; r < q; r++)
-            for (uint32_t j = 0; j < b; j++) cfull[(size_t)r * q + i * b + j] = coef[(size_t)r * b + j];
-        next_block = i + 1;
-    };
-    auto orth_block = [&](uint32_t i) { // on the auxiliary stream, finished (host-synchronised) on return
+    }
+    // Block i-1 is complete since the end of iteration i-1, so it is made orthogonal to blocks < i-1 in iteration i, on the
+    // auxiliary stream, while the sparse pass just queued occupies the main one (host round trips of the small factorizations
+    // hidden behind ~40 ms of gather work). Device form: nothing waited for; host form: finished on return.
+    void orth_block_beside(uint32_t i) {
         StreamSwap sw(c.st, c.st.aux());
         Ctx cx(m);
-        orth_block_on(cx, i);
-        cx.sync();
-    };
-    // T'_j = (op(A) K)[:, 0:(j+1)b] * C[0:(j+1)b, block j] for the blocks whose coefficients are known before the end: a
-    // dense MFMA GEMM queued on the auxiliary stream behind the pass that delivers the last half-product it reads, so it
-    // runs in the gaps the sparse passes leave. Out of place: later blocks still need the half-products in T, so the projected
-    // blocks are collected in a second panel T2 of the same shape (block 0, whose projection is the half-product itself, is
-    // copied there by the first early projection), and the Rayleigh-Ritz step reads T2 — nothing is copied back at the end.
-    // The projections have a stream of their own: on the stream of the Gram-Schmidt chains a 3 ms GEMM stood between the main
-    // stream and the chain it was waiting for at the end of the iterations.
-    const uint32_t n_early = (reuse && n_iter >= 3) ? n_iter - 2 : 0; // blocks 1 .. n_iter-2
-    double *T2 = reuse ? c.dev("bk_T2", (size_t)dt * ldq) : nullptr;
-    bool block0_copied = false;
-    struct Ev {
-        hipEvent_t e = nullptr;
-        Ev() { SCANRS_HIP(hipEventCreateWithFlags(&e, hipEventDisableTiming)); }
-        ~Ev() { (void)hipEventDestroy(e); }
-    };
-    // one event object per iteration and purpose: an event is never recorded again while a wait on its previous record may still be queued
-    std::vector<Ev> ev_k(n_iter);    // K block i is in place (main stream)
-    std::vector<Ev> ev_pass(n_iter); // both passes of iteration i are done (main stream)
-    std::vector<Ev> ev_aux(n_iter);  // the Gram-Schmidt chain queued in iteration i is done (auxiliary stream)
-    std::vector<Ev> ev_proj(n_iter); // the projection queued in iteration i is done (projection stream)
-    int last_aux = -1, last_proj = -1;
-    std::vector<char> projected(n_iter, 0);
-    auto project_block_early = [&](uint32_t j, uint32_t it) { // queued in iteration `it`: T block j is ready at ev_pass[it]
-        const uint32_t nr = (j + 1) * b;
-        std::vector<double> W;
-        if (!dv) {
-            W.resize((size_t)nr * b);
-            for (uint32_t r = 0; r < nr; r++)
-                for (uint32_t cc = 0; cc < b; cc++) W[(size_t)r * b + cc] = cfull[(size_t)r * q + j * b + cc];
+        if (dv) SCANRS_HIP(hipStreamWaitEvent(cx.s, ev_k[i - 1].e, 0));
+        orth_block(cx, i - 1);
+        if (dv) {
+            SCANRS_HIP(hipEventRecord(ev_aux[i].e, cx.s));
+            last_aux = (int)i;
+        } else {
+            cx.sync();
         }
+    }
+
+    // T2 block j = T[:, 0:(j+1)b] * C[0:(j+1)b, block j] on cx's stream: a dense MFMA GEMM; wkey: the scratch of the host form's W
+    void project_block(Ctx &cx, uint32_t j, const char *wkey) {
+        const uint32_t nr = (j + 1) * b;
+        if (dv) {
+            launch_gemm_nn(cx.st, T, ldq, nr, cfull_d + (size_t)j * b, ldq, b, dt, 1.0, 0.0, nullptr, 0, T2 + (size_t)j * b, ldq);
+            return;
+        }
+        std::vector<double> W((size_t)nr * b);
+        for (uint32_t r = 0; r < nr; r++)
+            for (uint32_t cc = 0; cc < b; cc++) W[(size_t)r * b + cc] = cfull[(size_t)r * q + j * b + cc];
+        double *dW = cx.dev(wkey, (size_t)nr * b);
+        cx.h2d(dW, W.data(), W.size());
+        launch_gemm_nn(cx.st, T, ldq, nr, dW, b, b, dt, 1.0, 0.0, nullptr, 0, T2 + (size_t)j * b, ldq);
+    }
+    // Block j, whose coefficients are known before the end, queued in iteration `it` behind the pass that delivers the last
+    // half-product it reads (T block j is ready at ev_pass[it]), so it runs in the gaps the sparse passes leave. The first one
+    // copies block 0, whose projection is the half-product itself. The projections have a stream of their own: on the stream of
+    // the Gram-Schmidt chains a 3 ms GEMM stood between the main stream and the chain it was waiting for at the end of the iterations.
+    void project_block_early(uint32_t j, uint32_t it) {
         StreamSwap sw(c.st, c.st.aux2());
         Ctx cx(m);
         SCANRS_HIP(hipStreamWaitEvent(cx.s, ev_pass[it].e, 0));
@@ -1149,229 +1203,129 @@ static int pca_bk_impl(scanrs_mat *m, uint32_t k, double k_multiplier, uint32_t 
             launch_copy_cols(cx.st, T, ldq, T2, ldq, dt, b);
             block0_copied = true;
         }
-        if (dv) { // the coefficients of block j: finished on the auxiliary stream (ev_aux was recorded behind them)
-            SCANRS_HIP(hipStreamWaitEvent(cx.s, ev_aux[it].e, 0));
-            launch_gemm_nn(cx.st, T, ldq, nr, cfull_d + (size_t)j * b, ldq, b, dt, 1.0, 0.0, nullptr, 0, T2 + (size_t)j * b, ldq);
-        } else {
-            char key[32];
-            snprintf(key, sizeof(key), "bk_projw%u", j);
-            double *dW = cx.dev(key, (size_t)nr * b);
-            cx.h2d(dW, W.data(), W.size());
-            launch_gemm_nn(cx.st, T, ldq, nr, dW, b, b, dt, 1.0, 0.0, nullptr, 0, T2 + (size_t)j * b, ldq);
-        }
+        if (dv) SCANRS_HIP(hipStreamWaitEvent(cx.s, ev_aux[it].e, 0)); // the coefficients of block j: finished on the auxiliary stream (ev_aux was recorded behind them)
+        char key[32];
+        snprintf(key, sizeof(key), "bk_projw%u", j);
+        project_block(cx, j, key);
         SCANRS_HIP(hipEventRecord(ev_proj[it].e, cx.s));
         last_proj = (int)it;
         projected[j] = 1;
         c.st.bk.early_projections++;
-    };
-    for (uint32_t i = 0; i < n_iter; i++) {
-        Tick tk("bk: iteration");
-        stage_mark("bk iteration", i);
-        // m >= n: B = qr((A B)^T A)^T .Q  (bk_svd.rs:94);  n > m: T = (B A)^T; B = qr(A T).Q^T  (bk_svd.rs:122-123)
-        double *Yi = (reuse && i >= 1) ? T + (size_t)(i - 1) * b : Y;
-        const uint32_t ldy = (reuse && i >= 1) ? ldq : ldb;
-        mat_apply(m, to_t_transpose, P, ldb, b, Yi, ldy);
-        // Q = qr(K).Q block by block: block i-1 is complete since the end of the previous iteration, so it is made
-        // orthogonal to blocks < i-1 now, on the auxiliary stream, while the sparse pass just queued occupies the
-        // main one (host round trips of the small factorizations hidden behind ~40 ms of gather work).
-        if (i >= 2) {
-            if (dv) { // queued on the auxiliary stream, nothing waited for
-                StreamSwap sw(c.st, c.st.aux());
-                Ctx cx(m);
-                SCANRS_HIP(hipStreamWaitEvent(cx.s, ev_k[i - 1].e, 0));
-                orth_block_dev(cx, i - 1);
-                SCANRS_HIP(hipEventRecord(ev_aux[i].e, cx.s));
-                last_aux = (int)i;
-            } else {
-                orth_block(i - 1);
+    }
+    // the main stream behind the last early GEMM (they are ordered on their stream): they read T and write T2
+    void wait_early_projections() {
+        if (last_proj >= 0) SCANRS_HIP(hipStreamWaitEvent(c.s, ev_proj[last_proj].e, 0));
+    }
+
+    void iterate() {
+        const uint32_t n_early = bk_early_blocks(b, n_iter);
+        for (uint32_t i = 0; i < n_iter; i++) {
+            Tick tk("bk: iteration");
+            stage_mark("bk iteration", i);
+            // m >= n: B = qr((A B)^T A)^T .Q  (bk_svd.rs:94);  n > m: T = (B A)^T; B = qr(A T).Q^T  (bk_svd.rs:122-123)
+            double *Yi = (reuse && i >= 1) ? T + (size_t)(i - 1) * b : Y;
+            const uint32_t ldy = (reuse && i >= 1) ? ldq : ldb;
+            mat_apply(m, to_t_transpose, P, ldb, b, Yi, ldy);
+            if (i >= 2) orth_block_beside(i);
+            mat_apply(m, !to_t_transpose, Yi, ldy, b, P, ldb);
+            if (i >= 2 && n_early && i - 1 <= n_early) {
+                // behind BOTH passes of this iteration: the projection GEMM then shares the device with the chain of small kernels that
+                // orthonormalises the panel (and with the start of the next product, whose workgroups take their items dynamically)
+                // instead of with the overflow gather's tail, which the product waits for
+                SCANRS_HIP(hipEventRecord(ev_pass[i].e, c.s));
+                project_block_early(i - 1, i);
             }
-        }
-        mat_apply(m, !to_t_transpose, Yi, ldy, b, P, ldb);
-        if (i >= 2 && n_early && i - 1 <= n_early) {
-            // behind BOTH passes of this iteration: the projection GEMM then shares the device with the chain of small kernels that
-            // orthonormalises the panel (and with the start of the next product, whose workgroups take their items dynamically)
-            // instead of with the overflow gather's tail, which the product waits for
-            SCANRS_HIP(hipEventRecord(ev_pass[i].e, c.s));
-            project_block_early(i - 1, i);
-        }
-        if (trace_on()) { // separate the wait for the two passes from the factorization in the trace
-            Tick tw("  passes (wait)");
-            c.sync();
-        }
-        if (dv)
-            orth_cholqr_dev(c, od, P, Ptmp, ldb, b, ds);
-        else
-            orth_cholqr(c, P, Ptmp, ldb, b, ds, false);
-        launch_copy_cols(c.st, P, ldb, K + (size_t)i * b, ldq, ds, b);
-        if (dv) {
-            // the host stays one iteration ahead of the device: the queue never runs dry and a cancellation is seen within one iteration
-            SCANRS_HIP(hipEventRecord(ev_k[i].e, c.s));
-            if (trace_on())
+            if (trace_on()) { // separate the wait for the two passes from the factorization in the trace
+                Tick tw("  passes (wait)");
                 c.sync();
-            else if (i >= 1) {
-                stage_mark("bk pacing wait", i - 1);
-                SCANRS_SYNC_EVENT(ev_k[i - 1].e);
-                stage_mark("bk pacing done", i - 1);
             }
-        } else {
-            c.sync();
+            if (dv)
+                orth_cholqr_dev(c, od, P, Ptmp, ldb, b, ds);
+            else
+                orth_cholqr(c, P, Ptmp, ldb, b, ds, false);
+            launch_copy_cols(c.st, P, ldb, K + (size_t)i * b, ldq, ds, b);
+            if (dv) {
+                // the host stays one iteration ahead of the device: the queue never runs dry and a cancellation is seen within one iteration
+                SCANRS_HIP(hipEventRecord(ev_k[i].e, c.s));
+                if (trace_on())
+                    c.sync();
+                else if (i >= 1) {
+                    stage_mark("bk pacing wait", i - 1);
+                    SCANRS_SYNC_EVENT(ev_k[i - 1].e);
+                    stage_mark("bk pacing done", i - 1);
+                }
+            } else {
+                c.sync();
+            }
+            snoop_poll(snoop, (double)i / (double)n_iter * 0.8);
         }
-        snoop_poll(snoop, (double)i / (double)n_iter * 0.8);
     }
-    // the last block (and everything, when there was no iteration to hide behind) on the main stream
-    {
+
+    // The last block (and everything, when there was no iteration to hide behind) on the main stream; then the one look at what
+    // the device-side factorizations did, together with the coefficients. false: they did not converge, run again on the host path.
+    bool finish_basis() {
         Tick tk("bk: orth(K)");
-        if (dv) {
-            if (last_aux >= 0) SCANRS_HIP(hipStreamWaitEvent(c.s, ev_aux[last_aux].e, 0)); // the blocks done beside the passes (one stream: the last record covers them all)
-            for (uint32_t i = next_block; i < n_iter; i++) orth_block_dev(c, i);
-            // the one look at what the device-side factorizations did, together with the coefficients
-            std::vector<int> ctl(2 * (size_t)od.used);
-            std::vector<double> info(2 * (size_t)od.used);
-            stage_mark("bk verdict sync");
-            SCANRS_D2H_2D(cfull.data(), cfull_d, (size_t)ldq * 8, (size_t)q * 8, q, c.s);
-            SCANRS_D2H(ctl.data(), od.ctl, ctl.size() * sizeof(int), c.s);
-            SCANRS_D2H(info.data(), od.info, info.size() * sizeof(double), c.s);
-            stage_mark("bk verdict synced");
-            for (uint32_t sl = 0; sl < od.used; sl++) {
-                if (ctl[2 * sl + 1] == 2) fail(SCANRS_ERR_NUMERICAL, "orthonormalisation: non-finite Gram matrix");
-                if (ctl[2 * sl] != 1 || ctl[2 * sl + 1] != 0) {
-                    if (trace_on())
-                        fprintf(stderr, "[scanrs trace] bk: device factorization %u: done %d status %d (last check %.3e, shift %.3e) -> host path\n", sl,
-                                ctl[2 * sl], ctl[2 * sl + 1], info[2 * sl], info[2 * sl + 1]);
-                    if (c.st.aux_stream) SCANRS_SYNC(c.st.aux_stream);
-                    if (c.st.aux2_stream) SCANRS_SYNC(c.st.aux2_stream);
-                    return BK_RETRY_ON_HOST;
-                }
-            }
-        } else {
-            for (uint32_t i = next_block; i < n_iter; i++) orth_block_on(c, i);
+        if (dv && last_aux >= 0) SCANRS_HIP(hipStreamWaitEvent(c.s, ev_aux[last_aux].e, 0)); // the blocks done beside the passes (one stream: the last record covers them all)
+        for (uint32_t i = next_block; i < n_iter; i++) orth_block(c, i);
+        if (!dv) {
             c.sync();
+            return true;
         }
-    }
-    snoop_poll(snoop, 0.82);
-    // T' = (op(A) K) C amplifies the rounding of op(A) K by |C|. Columns of Q whose coefficient column stays below
-    // the bound L ("reuse_cmax", 1e5) take the cheap dense route; the others — directions in which the Krylov blocks
-    // are numerically dependent — are recomputed directly as a (narrow) sparse product op(A) Q[:, bad]. What is held
-    // (tests/test_gpu_bk_reuse.py): every returned triplet has max |op(A) x_i - s_i y_i| <=
-    // sqrt(q) L 2^-53 s_1, L the bound finally used (1.1e-11 sqrt(q) s_1 at 1e5).
-    double cmax_limit = c.st.reuse_cmax;
-    std::vector<uint32_t> bad;
-    const bool c_valid = c.st.orth_fallbacks == fallbacks0;
-    c.st.bk.coef_valid = c_valid;
-    std::vector<double> colmax(q, 0.0); // max |C| per column of Q (filled when the bookkeeping is used)
-    if (reuse && !c_valid) {
-        for (uint32_t j = 0; j < q; j++) bad.push_back(j); // everything directly: one q-wide product below
-        if (trace_on()) fprintf(stderr, "[scanrs trace] bk: rank-deficient panels were completed on the host: the projection is computed directly\n");
-    }
-    if (reuse && c_valid) {
-        for (uint32_t r = 0; r < q; r++)
-            for (uint32_t j = 0; j < q; j++) colmax[j] = std::max(colmax[j], std::fabs(cfull[(size_t)r * q + j]));
-        // The repair pass carries the last block (b columns) plus the flagged columns of the older blocks. A pass of up to 104
-        // columns runs through the hybrid LDS-tile product, a wider one through the gather kernels at about twice the time: when
-        // a few flagged columns too many stand in the way (22 on the 1 M-cell benchmark), the bound is raised — by at most two
-        // decades: the same residual bound with the raised L, at most 1.1e-9 sqrt(q) s_1 — until the pass fits.
-        // The rule looks at b and the coefficients only — not at whether this handle (or this shard) happens to run the hybrid product:
-        // the flagged set, and with it the rounding of the result, is the same on every rank of a sharded run and under any memory
-        // pressure (it used to depend on whether a tile layout existed).
-        std::vector<double> flagged; // the older blocks' columns at or above the bound, before any raise
-        for (uint32_t j = 0; j < (n_iter - 1) * b; j++)
-            if (!(colmax[j] < cmax_limit)) flagged.push_back(colmax[j]);
-        c.st.bk.flagged_older = flagged.size();
-        c.st.bk.limit_branch = flagged.empty() ? 0 : 4; // 4 unless the flagged columns fit or one of the two raises applies
-        if (n_iter >= 2 && b <= 104u) {
-            const uint32_t room = 104u - b;
-            if (flagged.size() > room) {
-                std::sort(flagged.begin(), flagged.end(), std::greater<double>());
-                const double need = flagged[room]; // the largest coefficient that has to take the dense route
-                if (flagged[0] < 100.0 * cmax_limit) { // all of them within the two decades: the pass carries the last block alone (100 columns run 9 % faster than 104)
-                    cmax_limit = std::nextafter(flagged[0], INFINITY);
-                    c.st.bk.limit_branch = 2;
-                } else if (need < 100.0 * cmax_limit && (room == 0 || flagged[room - 1] > need)) {
-                    cmax_limit = std::nextafter(need, INFINITY);
-                    c.st.bk.limit_branch = 3;
-                }
-            } else if (!flagged.empty()) {
-                c.st.bk.limit_branch = 1;
+        std::vector<int> ctl(2 * (size_t)od.used);
+        std::vector<double> info(2 * (size_t)od.used);
+        stage_mark("bk verdict sync");
+        SCANRS_D2H_2D(cfull.data(), cfull_d, (size_t)ldq * 8, (size_t)q * 8, q, c.s);
+        SCANRS_D2H(ctl.data(), od.ctl, ctl.size() * sizeof(int), c.s);
+        SCANRS_D2H(info.data(), od.info, info.size() * sizeof(double), c.s);
+        stage_mark("bk verdict synced");
+        for (uint32_t sl = 0; sl < od.used; sl++) {
+            if (ctl[2 * sl + 1] == 2) fail(SCANRS_ERR_NUMERICAL, "orthonormalisation: non-finite Gram matrix");
+            if (ctl[2 * sl] != 1 || ctl[2 * sl + 1] != 0) {
+                if (trace_on())
+                    fprintf(stderr, "[scanrs trace] bk: device factorization %u: done %d status %d (last check %.3e, shift %.3e) -> host path\n", sl,
+                            ctl[2 * sl], ctl[2 * sl + 1], info[2 * sl], info[2 * sl + 1]);
+                if (c.st.aux_stream) SCANRS_SYNC(c.st.aux_stream);
+                if (c.st.aux2_stream) SCANRS_SYNC(c.st.aux2_stream);
+                return false;
             }
         }
-        for (uint32_t j = 0; j < q; j++)
-            if (!(colmax[j] < cmax_limit)) bad.push_back(j);
-        if (trace_on()) {
-            fprintf(stderr, "[scanrs trace] bk: %zu of %u projection columns recomputed directly\n", bad.size(), q);
-            for (uint32_t blk = 0; blk < n_iter; blk++) {
-                int cnt = 0;
-                for (uint32_t j = blk * b; j < (blk + 1) * b; j++) cnt += !(colmax[j] < cmax_limit);
-                fprintf(stderr, "[scanrs trace] bk:   block %u: %d\n", blk, cnt);
-            }
-            for (double thr : {1e3, 1e4, 1e5, 1e6, 1e7, 1e8, 1e9, 1e10}) {
-                int cnt = 0;
-                for (uint32_t j = 0; j < q; j++) cnt += !(colmax[j] < thr);
-                fprintf(stderr, "[scanrs trace] bk:   columns with max|C| >= %.0e: %d\n", thr, cnt);
-            }
-        }
+        return true;
     }
-    // The last Krylov block: its half-product op(A) K_{n-1} exists only to feed T'_{n-1}. When (as on every matrix
-    // measured: the newest block is where the numerical dependence shows) most of that block is recomputed directly
-    // anyway, computing ALL of it directly — in the same sparse pass as the other bad columns — costs no more
-    // 128-column passes than the half-product plus the repair pass, and usually one fewer.
-    bool last_direct = false;
-    if (reuse && c_valid) {
-        const uint32_t last_lo = (n_iter - 1) * b;
-        uint32_t bad_other = 0;
-        for (uint32_t j : bad) bad_other += j < last_lo;
-        auto chunks = [](uint32_t x) { return (x + 127u) / 128u; };
-        const uint32_t cost_half = chunks(b) + chunks((uint32_t)bad.size()), cost_direct = chunks(b + bad_other);
-        last_direct = cost_direct <= cost_half && n_iter >= 2;
-        if (last_direct) {
-            std::vector<uint32_t> merged;
-            for (uint32_t j : bad)
-                if (j < last_lo) merged.push_back(j);
-            for (uint32_t j = last_lo; j < q; j++) merged.push_back(j);
-            bad.swap(merged);
-        } else {
+
+    // bk_plan.hpp decides from max |C| per column; what the plan leaves to the half-product of the last block is queued here
+    void make_plan() {
+        snoop_poll(snoop, 0.82);
+        const bool c_valid = c.st.orth_fallbacks == fallbacks0, tracked = reuse && c_valid;
+        colmax.assign(q, 0.0);
+        if (tracked)
+            for (uint32_t r = 0; r < q; r++)
+                for (uint32_t j = 0; j < q; j++) colmax[j] = std::max(colmax[j], std::fabs(cfull[(size_t)r * q + j]));
+        if (reuse && !c_valid && trace_on())
+            fprintf(stderr, "[scanrs trace] bk: rank-deficient panels were completed on the host: the projection is computed directly\n");
+        plan = bk_plan(colmax.data(), b, n_iter, c.st.reuse_cmax, c_valid);
+        bk_record(c.st.bk, plan, c_valid);
+        if (tracked && trace_on()) bk_plan_trace(colmax.data(), b, n_iter, plan);
+        if (tracked && !plan.last_direct) {
             Tick tk("bk: last block product");
             mat_apply(m, to_t_transpose, P, ldb, b, T + (size_t)(n_iter - 1) * b, ldq);
         }
-        if (trace_on()) fprintf(stderr, "[scanrs trace] bk: last block %s\n", last_direct ? "computed directly with the repair pass" : "through its half-product");
     }
-    c.st.bk.limit = cmax_limit;
-    c.st.bk.direct_columns = bad.size();
-    c.st.bk.last_direct = last_direct;
-    double *Tfin = T; // the panel the Rayleigh-Ritz step reads
-    {
+
+    // returns the panel the Rayleigh-Ritz step reads
+    const double *project() {
         Tick tk("bk: projection");
-        if (reuse && (bad.size() * 2 < q || last_direct)) {
-            // T2 block j = T[:, 0:(j+1)b] * C[0:(j+1)b, block j] for the blocks not projected early
-            std::vector<double> W;
-            for (uint32_t j = n_iter - 1 - (last_direct ? 1u : 0u); j >= 1; j--) {
-                if (projected[j]) continue; // done early
-                const uint32_t nr = (j + 1) * b;
-                if (dv) {
-                    launch_gemm_nn(c.st, T, ldq, nr, cfull_d + (size_t)j * b, ldq, b, dt, 1.0, 0.0, nullptr, 0, T2 + (size_t)j * b, ldq);
-                } else {
-                    W.assign((size_t)nr * b, 0.0);
-                    for (uint32_t r = 0; r < nr; r++)
-                        for (uint32_t cc = 0; cc < b; cc++) W[(size_t)r * b + cc] = cfull[(size_t)r * q + j * b + cc];
-                    double *dW = c.dev("bk_projw", (size_t)nr * b);
-                    c.h2d(dW, W.data(), W.size());
-                    launch_gemm_nn(c.st, T, ldq, nr, dW, b, b, dt, 1.0, 0.0, nullptr, 0, T2 + (size_t)j * b, ldq);
-                }
-            }
+        if (plan.full_direct) {
+            wait_early_projections(); // they read T, which is overwritten now
+            mat_apply(m, to_t_transpose, K, ldq, q, T, ldq);
+        } else {
+            for (uint32_t j = n_iter - 1 - (plan.last_direct ? 1u : 0u); j >= 1; j--)
+                if (!projected[j]) project_block(c, j, "bk_projw"); // the blocks not projected early
             if (!block0_copied) launch_copy_cols(c.st, T, ldq, T2, ldq, dt, b);
-            bool any_early = false;
-            for (uint32_t j = 1; j < n_iter; j++) any_early = any_early || projected[j];
-            if (any_early && last_proj >= 0) SCANRS_HIP(hipStreamWaitEvent(c.s, ev_proj[last_proj].e, 0)); // the last early GEMM (they are ordered on their stream)
-            Tfin = T2;
-            {
-                std::vector<char> is_bad(q, 0);
-                for (uint32_t j : bad) is_bad[j] = 1;
-                for (uint32_t j = 0; j < q; j++)
-                    if (!is_bad[j]) c.st.bk.cmax_dense = std::max(c.st.bk.cmax_dense, colmax[j]);
-            }
-            if (!bad.empty()) {
-                const uint32_t nbad = (uint32_t)bad.size(), ldbad = even_up(nbad);
+            wait_early_projections();
+            if (!plan.direct.empty()) { // the repair pass: op(A) Q[:, direct] into those columns of T2
+                const uint32_t nbad = (uint32_t)plan.direct.size(), ldbad = even_up(nbad);
                 uint32_t *d_idx = c.st.scratch.get<uint32_t>("bk_badidx", nbad);
-                SCANRS_HIP(hipMemcpyAsync(d_idx, bad.data(), (size_t)nbad * 4, hipMemcpyHostToDevice, c.s));
+                SCANRS_HIP(hipMemcpyAsync(d_idx, plan.direct.data(), (size_t)nbad * 4, hipMemcpyHostToDevice, c.s));
                 c.sync();
                 double *Qbad = c.dev("bk_Qbad", (size_t)ds * ldbad);
                 double *Tbad = c.dev("bk_Tbad", (size_t)dt * ldbad);
@@ -1379,36 +1333,47 @@ static int pca_bk_impl(scanrs_mat *m, uint32_t k, double k_multiplier, uint32_t 
                 mat_apply(m, to_t_transpose, Qbad, ldbad, nbad, Tbad, ldbad);
                 launch_permute_cols(c.st, Tbad, ldbad, T2, ldq, dt, d_idx, nbad, true);
             }
-        } else {
-            bool any_early = false;
-            for (uint32_t j = 1; j < n_iter; j++) any_early = any_early || projected[j];
-            if (any_early && last_proj >= 0) SCANRS_HIP(hipStreamWaitEvent(c.s, ev_proj[last_proj].e, 0)); // they read T, which is overwritten now
-            mat_apply(m, to_t_transpose, K, ldq, q, T, ldq);
-            c.st.bk.full_direct = 1;
         }
         stage_mark("bk projection sync");
         c.sync();
         stage_mark("bk projection synced");
+        return plan.full_direct ? T : T2;
     }
-    Tick tk_fin("bk: ritz_finish");
-    snoop_poll(snoop, 0.93);
+
     // m >= n: T = A Q (m x q): U = T E S^-1, V = Q E.   n > m: T^T = A^T Q (n x q): U = Q E, V = T E S^-1.
-    if (rows_ge) {
-        ritz_finish(c, K, ldq, q, ds, Tfin, ldq, dt, t_sharded, k, v, s, u);
-        pca_dev_swap(c.st); // side S = cols: it holds V
-    } else {
-        ritz_finish(c, K, ldq, q, ds, Tfin, ldq, dt, t_sharded, k, u, s, v);
+    void ritz(const double *Tfin, double *u, double *s, double *v) {
+        snoop_poll(snoop, 0.93);
+        ritz_finish_uv(c, K, ldq, q, ds, Tfin, ldq, dt, t_sharded, k, rows_ge, u, s, v);
+        snoop_poll(snoop, 1.0);
     }
-    snoop_poll(snoop, 1.0);
+};
+
+static int pca_bk_run(scanrs_mat *m, uint32_t k, double k_multiplier, uint32_t n_iter, uint64_t seed, const double *omega,
+                      const scanrs_snoop *snoop, double *u, double *s, double *v, bool device_factor) {
+    Tick tk_all("bk: total");
+    BkRun r(m, snoop);
+    r.shape(k, k_multiplier, n_iter);
+    if (r.exact) {
+        r.exact_svd(u, s, v);
+        return SCANRS_OK;
+    }
+    r.start_panel(seed, omega);
+    r.prepare_basis(device_factor);
+    r.iterate();
+    if (!r.finish_basis()) return BK_RETRY_ON_HOST;
+    r.make_plan();
+    const double *Tfin = r.project();
+    Tick tk_fin("bk: ritz_finish");
+    r.ritz(Tfin, u, s, v);
     return SCANRS_OK;
 }
 
 int pca_bk(scanrs_mat *m, uint32_t k, double k_multiplier, uint32_t n_iter, uint64_t seed, const double *omega,
            const scanrs_snoop *snoop, double *u, double *s, double *v) {
-    int rc = pca_bk_impl(m, k, k_multiplier, n_iter, seed, omega, snoop, u, s, v, m->st->device_factor != 0);
+    int rc = pca_bk_run(m, k, k_multiplier, n_iter, seed, omega, snoop, u, s, v, m->st->device_factor != 0);
     if (rc == BK_RETRY_ON_HOST) {
         m->st->bk_host_retries++;
-        rc = pca_bk_impl(m, k, k_multiplier, n_iter, seed, omega, snoop, u, s, v, false);
+        rc = pca_bk_run(m, k, k_multiplier, n_iter, seed, omega, snoop, u, s, v, false);
     }
     return rc;
 }
@@ -1417,10 +1382,7 @@ int pca_rand(scanrs_mat *m, uint32_t k, double l_multiplier, uint32_t n_iter, ui
              double *s, double *v) {
     Ctx c(m);
     const uint64_t M = m->rows(), N = m->cols();
-    const uint64_t Mg = dim_sharded_rows(m) ? c.st.shard.outer_global : M;
-    const uint64_t Ng = dim_sharded_cols(m) ? c.st.shard.outer_global : N;
-    if (Mg < 2 || Ng < 2) fail(SCANRS_ERR_SHAPE, "The input matrix must be at least 2x2.");
-    if (k > std::min(Mg, Ng)) fail(SCANRS_ERR_INVALID_K, "invalid k");
+    const auto [Mg, Ng] = global_extents(m, k);
     if (k == 0) fail(SCANRS_ERR_ARGUMENT, "k must be positive");
     const uint32_t l_full = (uint32_t)std::max<uint64_t>(k + 4, (uint64_t)((double)k * l_multiplier)); // rand_svd.rs:46
     // A projection wider than the matrix is short (rand_svd.rs accepts it: qr() of the wide panel returns a basis of the
@@ -1437,22 +1399,8 @@ int pca_rand(scanrs_mat *m, uint32_t k, double l_multiplier, uint32_t n_iter, ui
     double *Qp = c.dev("rs_Q", (size_t)d_q * ldl);
     double *tmp = c.dev("rs_tmp", (size_t)std::max(d_om, d_q) * ldl);
     SCANRS_HIP(hipMemsetAsync(Om, 0, (size_t)d_om * ldl * 8, c.s));
-    {
-        if (om_sharded && !omega) fail(SCANRS_ERR_ARGUMENT, "a sharded start panel must be passed explicitly");
-        if (!omega) {
-            if (rows_ge)
-                omega_fill_device(c.st, seed, d_om, l, Om, ldl, false);
-            else
-                omega_fill_device(c.st, seed, l, d_om, Om, ldl, true);
-        } else if (rows_ge) { // (cols x l_full) row-major: the leading l columns
-            SCANRS_HIP(hipMemcpy2DAsync(Om, (size_t)ldl * 8, omega, (size_t)l_full * 8, (size_t)l * 8, d_om, hipMemcpyHostToDevice, c.s));
-            c.sync();
-        } else { // (l_full x rows) row-major: the leading l rows
-            double *tmp2 = c.dev("rs_omega_t", (size_t)l * d_om);
-            c.h2d(tmp2, omega, (size_t)l * d_om);
-            launch_transpose(c.st, tmp2, l, d_om, Om, ldl);
-        }
-    }
+    if (om_sharded && !omega) fail(SCANRS_ERR_ARGUMENT, "a sharded start panel must be passed explicitly");
+    fill_start_panel(c, rows_ge, seed, omega, l_full, d_om, l, Om, ldl, "rs_omega_t"); // a given panel is l_full wide: its leading l columns / rows
     // Q = qr(A Omega).Q   (rand_svd.rs:87 / :109)
     prepare_second_orientation(m, !om_to_q_transpose);
     mat_apply(m, om_to_q_transpose, Om, ldl, l, Qp, ldl);
@@ -1466,12 +1414,7 @@ int pca_rand(scanrs_mat *m, uint32_t k, double l_multiplier, uint32_t n_iter, ui
     // B = Q^T A  (l x n)  resp. B = A Q: its transpose/ itself lives on the Omega side
     mat_apply(m, !om_to_q_transpose, Qp, ldl, l, Om, ldl);
     c.sync();
-    if (rows_ge) {
-        ritz_finish(c, Qp, ldl, l, d_q, Om, ldl, d_om, om_sharded, k, u, s, v);
-    } else {
-        ritz_finish(c, Qp, ldl, l, d_q, Om, ldl, d_om, om_sharded, k, v, s, u);
-        pca_dev_swap(c.st); // side S (Q) = cols: it holds V
-    }
+    ritz_finish_uv(c, Qp, ldl, l, d_q, Om, ldl, d_om, om_sharded, k, !rows_ge, u, s, v); // side S (Q) = cols when n > m
     return SCANRS_OK;
 }
 
@@ -1566,9 +1509,8 @@ int pca_irlba(scanrs_mat *m, uint32_t nu, double tol, uint32_t maxit, const doub
     // (gram_host), the products that contract over that side are all-reduced inside mat_apply; everything on the other side and
     // the small bidiagonal problem are replicated and deterministic.
     const bool sh_m = dim_sharded_rows(m), sh_n = dim_sharded_cols(m);
-    const uint64_t Mg = sh_m ? c.st.shard.outer_global : M, Ng = sh_n ? c.st.shard.outer_global : N;
-    if (Mg < 2 || Ng < 2) fail(SCANRS_ERR_SHAPE, "The input matrix must be at least 2x2.");
-    if (nu > std::min(Mg, Ng) || nu == 0) fail(SCANRS_ERR_INVALID_K, "invalid k");
+    const uint64_t Ng = global_extents(m, nu).Ng;
+    if (nu == 0) fail(SCANRS_ERR_INVALID_K, "invalid k");
     if (m->off_rank) fail(SCANRS_ERR_ARGUMENT, "irlba: LowRankOffset has no Ix1 Dot impl in the reference (low_rank_offset.rs:68-96)");
     if (maxit == 0) fail(SCANRS_ERR_ARGUMENT, "irlba: max_iter must be positive"); // the epilogue reads the last iteration's factors
     const uint32_t m_b = (uint32_t)std::min<uint64_t>(nu + 20, std::min<uint64_t>(3ull * nu, Ng)); // irlba.rs:87

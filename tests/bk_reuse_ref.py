@@ -2,7 +2,7 @@
 
 svd_bk does not compute the projection T = op(A) Q with a sparse product: it keeps the half-products H = op(A) K of its iterations
 and forms T' = H C, C the coefficient matrix with Q = K C tracked through every CholeskyQR and block Gram-Schmidt step (solver.cpp,
-pca_bk_impl). T' carries the rounding of H amplified by |C|, so every column whose coefficient column reaches
+BkRun; the decisions in bk_plan.hpp). T' carries the rounding of H amplified by |C|, so every column whose coefficient column reaches
 "reuse_cmax" is recomputed by a direct sparse product. This module restates that scheme in f64 numpy (`model`), with the same
 decisions — flagged columns, the raise of the bound, last_direct, the full-direct fallback — and holds the bounds the library is
 tested against:
@@ -50,7 +50,7 @@ DEFAULT_CMAX = 1e5
 ALL_DIRECT = 1e-300  # every column flagged: the control
 NO_GUARD = 1e300     # no column flagged: the teeth
 KAPPA_U = 7.6        # see the module docstring
-MAX_PASS = 104       # widest repair pass the raise rule aims for (solver.cpp)
+MAX_PASS = 104       # widest repair pass the raise rule aims for (bk_plan.hpp, BK_PASS_MAX)
 
 
 # ---- matrices ------------------------------------------------------------------------------------------------------------------
@@ -182,7 +182,7 @@ class ModelResult:
 
 
 def limit_rule(colmax_older, b, n_iter, reuse_cmax):
-    """The raise rule of pca_bk_impl: (flagged count before the raise, branch, bound used)."""
+    """The raise rule of bk_plan.hpp (bk_plan): (flagged count before the raise, branch, bound used)."""
     flagged = sorted((x for x in colmax_older if not x < reuse_cmax), reverse=True)
     limit, branch = reuse_cmax, (4 if flagged else 0)
     if n_iter >= 2 and b <= MAX_PASS:
@@ -198,8 +198,35 @@ def limit_rule(colmax_older, b, n_iter, reuse_cmax):
     return len(flagged), branch, limit
 
 
+def plan_rule(colmax, b, n_iter, reuse_cmax, coef_valid=True):
+    """The projection plan of bk_plan.hpp (bk_plan) from max |C| per column of Q: the fields `scanrs_amd.host_bk_plan` returns.
+    `direct`: the columns recomputed by the sparse product, after the last_direct merge. The cost comparison behind last_direct is
+    kept as it was first written; bk_plan.hpp states why it reduces to n_iter >= 2."""
+    q, last_lo = b * n_iter, (n_iter - 1) * b
+    reuse = b % 2 == 0
+    flagged_older, branch, limit, bad, last_direct = 0, 0, float(reuse_cmax), [], False
+    if reuse and not coef_valid:
+        bad = list(range(q))  # rank-deficient panels were completed on the host: Q = K C no longer holds
+    if reuse and coef_valid:
+        flagged_older, branch, limit = limit_rule(colmax[:last_lo], b, n_iter, float(reuse_cmax))
+        bad = [j for j in range(q) if not colmax[j] < limit]
+        bad_other = sum(j < last_lo for j in bad)
+        chunks = lambda x: (x + 127) // 128
+        last_direct = chunks(b + bad_other) <= chunks(b) + chunks(len(bad)) and n_iter >= 2
+        if last_direct:
+            bad = [j for j in bad if j < last_lo] + list(range(last_lo, q))
+    full_direct = not (reuse and (len(bad) * 2 < q or last_direct))
+    cmax_dense = 0.0
+    if not full_direct:
+        dense_cols = sorted(set(range(q)) - set(bad))
+        cmax_dense = float(np.max(np.asarray(colmax)[dense_cols])) if dense_cols else 0.0
+    n_early = n_iter - 2 if (reuse and n_iter >= 3) else 0
+    return dict(reuse=reuse, flagged_older=flagged_older, limit_branch=branch, limit=limit, direct=tuple(bad), last_direct=last_direct,
+                full_direct=full_direct, n_early=n_early, cmax_dense=cmax_dense)
+
+
 def model(dense, omega, k, mult, n_iter, reuse_cmax=DEFAULT_CMAX):
-    """pca_bk_impl in f64 numpy, host-path form (rounds of project + CholeskyQR until the projection is at rounding level)."""
+    """BkRun (solver.cpp) in f64 numpy, host-path form (rounds of project + CholeskyQR until the projection is at rounding level)."""
     A = np.asarray(dense, dtype=np.float64)
     m, n = A.shape
     rows_ge = m >= n
@@ -235,20 +262,11 @@ def model(dense, omega, k, mult, n_iter, reuse_cmax=DEFAULT_CMAX):
         Q[:, sl], C[:, sl] = Bj, coef
     colmax = np.max(np.abs(C), axis=0)
     last_lo = q - b
-    flagged_older, branch, limit, bad, last_direct = 0, 0, reuse_cmax, [], False
-    if reuse:
-        flagged_older, branch, limit = limit_rule(colmax[:last_lo], b, n_iter, reuse_cmax)
-        bad = [j for j in range(q) if not colmax[j] < limit]
-        bad_other = sum(j < last_lo for j in bad)
-        chunks = lambda x: (x + 127) // 128
-        last_direct = chunks(b + bad_other) <= chunks(b) + chunks(len(bad)) and n_iter >= 2
-        if last_direct:
-            bad = [j for j in bad if j < last_lo] + list(range(last_lo, q))
-        else:
-            H[:, last_lo:] = op(Klast)
-    full_direct = not (reuse and (len(bad) * 2 < q or last_direct))
-    cmax_dense = 0.0
-    if full_direct:
+    pl = plan_rule(colmax, b, n_iter, reuse_cmax)
+    bad, last_direct = list(pl["direct"]), pl["last_direct"]
+    if reuse and not last_direct:
+        H[:, last_lo:] = op(Klast)
+    if pl["full_direct"]:
         T = op(Q)
     else:
         T = np.zeros((dt, q))
@@ -258,8 +276,6 @@ def model(dense, omega, k, mult, n_iter, reuse_cmax=DEFAULT_CMAX):
             T[:, j * b:nr] = H[:, :nr] @ C[:nr, j * b:nr]
         if bad:
             T[:, bad] = op(Q[:, bad])
-        dense_cols = sorted(set(range(q)) - set(bad))
-        cmax_dense = float(np.max(colmax[dense_cols])) if dense_cols else 0.0
     G = T.T @ T
     G = 0.5 * (G + G.T)
     w, Z = np.linalg.eigh(G)
@@ -268,8 +284,8 @@ def model(dense, omega, k, mult, n_iter, reuse_cmax=DEFAULT_CMAX):
     E = Z[:, idx]
     side_s, side_t = Q @ E, (T @ E) / s
     u, v = (side_t, side_s) if rows_ge else (side_s, side_t)
-    n_early = n_iter - 2 if (reuse and n_iter >= 3) else 0
-    return ModelResult(b, q, reuse, colmax, flagged_older, branch, limit, tuple(bad), last_direct, full_direct, n_early, cmax_dense, u, s, v)
+    return ModelResult(b, q, reuse, colmax, pl["flagged_older"], pl["limit_branch"], pl["limit"], pl["direct"], last_direct, pl["full_direct"],
+                       pl["n_early"], pl["cmax_dense"], u, s, v)
 
 
 def pick_threshold(colmax_older, target):
