@@ -173,7 +173,7 @@ int scanrs_mat_to_dense(scanrs_mat *m, double *out);
  * scanrs_multi by scanrs_multi_select_rows / _select_cols / _partition_on_thresholds. Unchanged: the column-list statistics,
  * scanrs_sseq_de_pairs and scanrs_merge_clusters stay refused on a sharded handle (their collective forms are
  * scanrs_sseq_de_pairs_sharded and scanrs_merge_clusters_sharded), and scanrs_mat_to_adaptive exports a rank's own
- * shard only. Transposed views work: rows of the view are columns of the stored matrix,
+ * shard only (the whole matrix of a scanrs_multi, in either orientation: scanrs_multi_to_adaptive). Transposed views work: rows of the view are columns of the stored matrix,
  * and a result's storage flag is the view's (scanrs_mat_storage). Every result is a fresh, independent handle with its own
  * storage, default options and the identity map, made on the device from the handle's own storage (no transposed copy is built, nothing
  * goes through the host); the source may be freed first. Free results with scanrs_mat_free.
@@ -249,7 +249,8 @@ int scanrs_mat_to_csmat(scanrs_mat *m, uint64_t *indptr, uint32_t *indices, uint
  * without atomics: two calls return the same bytes.
  *
  * Like scanrs_mat_to_csmat it reads the stored counts: a composed map or an offset is ignored, a transposed view exports the same
- * vectors under the other storage flag (scanrs_mat_storage), a sharded handle exports its own shard. The export owns two host
+ * vectors under the other storage flag (scanrs_mat_storage), a sharded handle exports its own shard (the whole matrix of a
+ * scanrs_multi: scanrs_multi_to_adaptive, below). The export owns two host
  * arenas (one device-to-host copy each; pinned memory from the library's pool from 1 MB on, plain heap memory below that) and the table of scanrs_adaptive_vec whose pointers lead into them, each aligned for
  * its element type; the device arenas are released before the call returns. */
 typedef struct scanrs_adaptive_export scanrs_adaptive_export;
@@ -258,7 +259,17 @@ typedef struct scanrs_adaptive_export scanrs_adaptive_export;
  * SCANRS_ERR_ARGUMENT. A matrix without outer vectors and empty vectors are valid. Free the result with
  * scanrs_adaptive_export_free. */
 int scanrs_mat_to_adaptive(scanrs_mat *m, int force_kind, scanrs_adaptive_export **out);
-/* n_vecs: the outer dimension. total_bytes: the sum of the reference's mem_size() — data + 8 per fallback entry (+ index bytes + 4
+/* The same with the orientation of the table chosen. SCANRS_EXPORT_STORED is scanrs_mat_to_adaptive: one vector per stored outer
+ * vector. SCANRS_EXPORT_INNER encodes the handle's OTHER copy (the transposed orientation, built on first use as the products build
+ * it and kept by the handle): n_inner vectors of len = n_outer, the table scanrs_mat_create_adaptive(rows, cols, the OTHER storage
+ * flag, ...) takes - for a genes x cells matrix stored cell-major, one vector per gene, the reference's own orientation
+ * (hdf5-io/src/matrix.rs:119-192). Through a transposed view the majors swap nothing else: the vectors are those of the stored
+ * arrays, the flag is the view's. Map and offset are ignored, as above. STORED on a sharded handle exports the rank's own shard;
+ * INNER on a sharded handle is SCANRS_ERR_ARGUMENT (no rank holds a whole inner vector: scanrs_multi_to_adaptive). major outside
+ * 0..1, force_kind outside -1..7 and a null argument are SCANRS_ERR_ARGUMENT, before any device work. */
+enum { SCANRS_EXPORT_STORED = 0, SCANRS_EXPORT_INNER = 1 };
+int scanrs_mat_to_adaptive_major(scanrs_mat *m, int major, int force_kind, scanrs_adaptive_export **out);
+/* n_vecs: the entries of the table (the outer dimension; the inner one for SCANRS_EXPORT_INNER). total_bytes: the sum of the reference's mem_size() — data + 8 per fallback entry (+ index bytes + 4
  * per block start for S*; 8 per entry for V). kind_counts[k]: vectors of encoding k. Each output pointer may be NULL. */
 int scanrs_adaptive_export_info(const scanrs_adaptive_export *e, uint64_t *n_vecs, uint64_t *total_bytes, uint64_t kind_counts[8]);
 /* The table (n_vecs entries), borrowed until scanrs_adaptive_export_free; it can be passed straight to
@@ -550,8 +561,9 @@ int scanrs_plan_shards(const uint64_t *indptr, uint64_t n_outer, uint32_t world,
  * Validation is scanrs_mat_create's (same codes and messages: an index out of range or not strictly ascending, indptr[0] != 0, null
  * arrays, dimensions beyond u32) and runs on every slab before anything is indexed by an inner index; n_shards, devices and peer
  * access are checked as in scanrs_multi_create (`devices` may repeat an id). On any failure nothing is leaked and *out is NULL.
- * Not served: the one-process-per-GPU forms (RCCL, host hook: their only transport is a sum all-reduce) and to_adaptive of a whole
- * scanrs_multi. (An existing scanrs_multi is cut anew by scanrs_multi_rebalance, below.) */
+ * Not served: the one-process-per-GPU forms (RCCL, host hook: their only transport is a sum all-reduce). (An existing scanrs_multi is
+ * cut anew by scanrs_multi_rebalance, below; the way back out in this orientation is scanrs_multi_to_adaptive with
+ * SCANRS_EXPORT_INNER, further down.) */
 /* AdaptiveMat::new from a triplet (sqz/src/mat.rs:68-124), sharded over the inner dimension */
 int scanrs_multi_create_inner(uint64_t rows, uint64_t cols, int storage, const uint64_t *indptr, const uint32_t *indices,
                               const uint32_t *values, uint32_t n_shards, const int *devices, scanrs_multi **out);
@@ -589,8 +601,8 @@ int scanrs_host_plan_inner(const uint64_t *indptr, const uint32_t *indices, uint
  * outside 1 .. 16 or a device that does not exist SCANRS_ERR_ARGUMENT; each message names the argument. On any failure nothing is
  * leaked and *out is NULL. n_idx == 0 gives what scanrs_multi_create gives for a matrix without outer vectors: a valid scanrs_multi
  * of empty shards.
- * Still out of scope: to_adaptive of a whole scanrs_multi, and the one-process-per-GPU forms (RCCL, host hook), whose only transport
- * is a sum all-reduce. */
+ * Still out of scope: the one-process-per-GPU forms (RCCL, host hook), whose only transport is a sum all-reduce. (to_adaptive of a
+ * whole scanrs_multi, which this list used to name, is served: scanrs_multi_to_adaptive, further down.) */
 /* the outer vectors idx[0..n_idx) of the WHOLE matrix (global positions along the sharded = stored outer dimension; any order,
  * repeats allowed), in list order, as a new scanrs_multi over n_shards shards on `devices` (null: 0..n_shards-1; ids may repeat) */
 int scanrs_multi_gather_outer(scanrs_multi *mm, const uint64_t *idx, uint64_t n_idx, uint32_t n_shards, const int *devices,
@@ -612,6 +624,50 @@ int scanrs_multi_gather_info(const scanrs_multi *mm, uint32_t *n_src, uint64_t *
 int scanrs_host_plan_gather(const uint64_t *indptr, uint64_t n_outer, const uint64_t *src_bounds, uint32_t n_src,
                             const uint64_t *idx, uint64_t n_idx, uint32_t n_dst, uint64_t *out_indptr, uint64_t *bounds,
                             uint64_t *moved);
+
+/* ---- to_adaptive of a whole scanrs_multi, in either orientation -----------
+ * scanrs_mat_to_adaptive_major over the shards: the stored counts of the WHOLE matrix as one table of AdaptiveVec encodings, made on
+ * the devices; only the encoded arenas (and, for INNER, 8 (n_inner + 1) bytes of indptr per shard) cross the host link. The export
+ * owns one pair of host arenas per shard and ONE table in global order; scanrs_adaptive_export_info / _vecs / _free work on it
+ * unchanged, kind_counts and total_bytes are over the whole table. Map and offset are ignored, as in scanrs_mat_to_adaptive.
+ *
+ * SCANRS_EXPORT_STORED: every shard encodes its own outer vectors on its own device and thread. outer_global vectors of
+ * len = n_inner, under the scanrs_multi's storage flag; vector by vector and byte for byte scanrs_mat_to_adaptive of an unsharded
+ * handle made from scanrs_multi_to_csmat.
+ *
+ * SCANRS_EXPORT_INNER, the inverse of scanrs_multi_create_adaptive_inner: one AdaptiveVec per INNER position (per gene, for a
+ * cell-sharded genes x cells matrix), each spanning all shards: n_inner vectors of len = outer_global, the table
+ * scanrs_mat_create_adaptive / scanrs_multi_create_adaptive_inner take with the OTHER storage flag. Byte for byte
+ * scanrs_mat_to_adaptive of an unsharded handle made from the host-transposed whole triplet, whatever the number of shards and the
+ * cut. An encoding cannot be concatenated from the shards' pieces (Dense3 packs 21 fields per word, S* has 256-index blocks,
+ * choose_storage looks at the whole vector), so the vectors are made whole on a device first: (1) every shard settles its transposed
+ * copy (kept by the handle, as a product would) and sends its indptr down; (2) the host plan (scanrs_host_plan_export) deals the
+ * inner positions in n_shards contiguous slabs by nonzeros, slab d to shard d's device; (3) every destination assembles the CSR of
+ * its slab over all outer_global positions, reading the sources' transposed copies in place (through the peer mapping where the
+ * devices differ; peer access is enabled from every destination to every source), every index raised by the source's outer_begin;
+ * (4) it encodes the slab, brings the two arenas down and releases the slab - 8 bytes per nonzero of the slab beside the encoder's
+ * temporaries; a destination that cannot hold them returns SCANRS_ERR_DEVICE naming the shard and the bytes (a slab is not split
+ * into rounds). Integer work without atomics: two calls return the same bytes.
+ *
+ * major outside 0..1, force_kind outside -1..7 and a null argument are SCANRS_ERR_ARGUMENT, before any device work. A matrix without
+ * outer vectors, empty shards and empty slabs are valid. On any failure nothing is leaked and *out is NULL. Per shard,
+ * scanrs_mat_get_counter "export_plan_us" / "export_pull_us" / "export_encode_us": wall clock of the phases of the last call.
+ * Not served: the one-process-per-GPU forms (RCCL, host hook). Distinct devices: as for §7m / §7n, no run on several physical GPUs
+ * has exercised the peer path yet. */
+int scanrs_multi_to_adaptive(scanrs_multi *mm, int major, int force_kind, scanrs_adaptive_export **out);
+/* What the multi call did: the shard count, slab_bounds (n_shards + 1: the table entries shard d encoded - INNER: the plan's slabs
+ * of inner positions; STORED: the shards' own ranges), moved (n_shards x n_shards, source-major: moved[s * n_shards + d] = the
+ * nonzeros of source shard s in slab d; STORED: the shards' nonzeros on the diagonal) and arena_bytes (per shard: the bytes of its
+ * two arenas that crossed the host link). Any pointer may be NULL. SCANRS_ERR_ARGUMENT on an export that scanrs_multi_to_adaptive
+ * did not make. */
+int scanrs_adaptive_export_multi_info(const scanrs_adaptive_export *e, uint32_t *n_shards, uint64_t *slab_bounds, uint64_t *moved,
+                                      uint64_t *arena_bytes);
+/* The plan of SCANRS_EXPORT_INNER on the host, no device: counts (n_src x n_inner, source-major) = the stored entries source s holds
+ * of every inner position; out_indptr (n_inner + 1) = the scan of the column sums, the whole matrix's inner-major indptr;
+ * slab_bounds (n_dst + 1) = scanrs_plan_shards over it; moved (n_src x n_dst) = the entries of source s in slab d. Any output may be
+ * NULL. n_src and n_dst outside 1 .. 16 and a null table with n_inner > 0 are SCANRS_ERR_ARGUMENT. */
+int scanrs_host_plan_export(const uint64_t *counts, uint32_t n_src, uint64_t n_inner, uint32_t n_dst, uint64_t *out_indptr,
+                            uint64_t *slab_bounds, uint64_t *moved);
 
 /* ---- measurement ------------------------------------------------------------------------- */
 
@@ -758,7 +814,10 @@ int scanrs_mat_set_option(scanrs_mat *m, const char *key, double value);
  * integer scatter from the other copy ("subset_scatter"); "subset_allreduces" = the exchange steps of the last
  * scanrs_mat_sum_rows_u64_sharded or kin on this handle (0 on an unsharded one). "regather_plan_us" / "regather_pull_us" /
  * "regather_finish_us" = on a shard made by scanrs_multi_gather_outer / scanrs_multi_rebalance, the wall clock of the plan (one phase,
- * the same on every shard) and of the shard's own thread in pull and finish.
+ * the same on every shard) and of the shard's own thread in pull and finish. "export_plan_us" / "export_pull_us" /
+ * "export_encode_us" = on a shard of a scanrs_multi, the last scanrs_multi_to_adaptive: the wall clock of the plan (the transposed
+ * copies, their indptr to the host and the host plan: one phase, the same on every shard; 0 for SCANRS_EXPORT_STORED) and of the
+ * shard's own thread in the pull of its slab (0 for STORED) and in encode + download.
  * The route of the LAST sparse product A X on this handle (host-side stores, overwritten by every product; a solver's last pass):
  * "spmm_route" = its kernel family, one of SCANRS_SPMM_* below; "spmm_form" = the form within the family -
  *   tiles:               bit 0 dense records (0: fixed positions), bit 1 unit mode (0: the weighted kernel), bits 2-3 where a

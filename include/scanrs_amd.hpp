@@ -71,7 +71,10 @@ struct PcaResult { // (u, d, v): dim_red/mod.rs:47
     Array2 v;
 };
 
-// The stored counts as AdaptiveVec encodings (scanrs_mat_to_adaptive): owns the host arenas and the table pointing into them
+enum class ExportMajor { Stored = SCANRS_EXPORT_STORED, Inner = SCANRS_EXPORT_INNER };
+
+// The stored counts as AdaptiveVec encodings (scanrs_mat_to_adaptive[_major], scanrs_multi_to_adaptive): owns the host arenas and the
+// table pointing into them
 class AdaptiveExport {
     scanrs_adaptive_export *e_ = nullptr;
 
@@ -110,6 +113,21 @@ class AdaptiveExport {
         const scanrs_adaptive_vec *v = nullptr;
         check(scanrs_adaptive_export_vecs(e_, &v));
         return v;
+    }
+    // scanrs_adaptive_export_multi_info: what MultiMat::to_adaptive did (slab_bounds n_shards + 1, moved n_shards x n_shards,
+    // arena_bytes per shard). Error on an export of a single handle.
+    struct MultiInfo {
+        uint32_t n_shards = 0;
+        std::vector<uint64_t> slab_bounds, moved, arena_bytes;
+    };
+    MultiInfo multi_info() const {
+        MultiInfo m;
+        check(scanrs_adaptive_export_multi_info(e_, &m.n_shards, nullptr, nullptr, nullptr));
+        m.slab_bounds.resize(m.n_shards + 1);
+        m.moved.resize((size_t)m.n_shards * m.n_shards);
+        m.arena_bytes.resize(m.n_shards);
+        check(scanrs_adaptive_export_multi_info(e_, nullptr, m.slab_bounds.data(), m.moved.data(), m.arena_bytes.data()));
+        return m;
     }
 };
 
@@ -351,6 +369,13 @@ class AdaptiveMat {
     AdaptiveExport to_adaptive(int force_kind = -1) const {
         scanrs_adaptive_export *e = nullptr;
         check(scanrs_mat_to_adaptive(h_, force_kind, &e));
+        return AdaptiveExport(e);
+    }
+    // major Inner: one vector per INNER position, from the handle's transposed copy (the table from_adaptive_vecs takes with the
+    // OTHER storage flag); refused on a sharded handle
+    AdaptiveExport to_adaptive(int force_kind, ExportMajor major) const {
+        scanrs_adaptive_export *e = nullptr;
+        check(scanrs_mat_to_adaptive_major(h_, (int)major, force_kind, &e));
         return AdaptiveExport(e);
     }
     Array2 to_dense() const {
@@ -632,6 +657,13 @@ class MultiMat {
         check(scanrs_multi_gather_info(h_, nullptr, g.bounds.data(), g.moved.data(), g.host_bytes.data()));
         return g;
     }
+    // scanrs_multi_to_adaptive: the whole matrix as one table of AdaptiveVec encodings. Stored: one per outer vector in global order;
+    // Inner (the inverse of from_adaptive_vecs_inner): one per inner position, each spanning all shards
+    AdaptiveExport to_adaptive(int force_kind = -1, ExportMajor major = ExportMajor::Stored) const {
+        scanrs_adaptive_export *e = nullptr;
+        check(scanrs_multi_to_adaptive(h_, (int)major, force_kind, &e));
+        return AdaptiveExport(e);
+    }
     struct Partition;
     Partition partition_on_thresholds(const double *row_threshold, const double *col_threshold) const;
     Partition partition_on_threshold(double threshold) const;
@@ -677,6 +709,17 @@ inline InnerPlan host_plan_inner(const uint64_t *indptr, const uint32_t *indices
     InnerPlan p{std::vector<uint64_t>(world + 1), std::vector<uint64_t>(world + 1), std::vector<uint64_t>((size_t)world * world + 1)};
     check(scanrs_host_plan_inner(indptr, indices, n_outer, n_inner, world, p.slab_bounds.data(), p.bounds.data(), p.moved.data()));
     p.moved.resize((size_t)world * world);
+    return p;
+}
+
+// scanrs_host_plan_export (host only, no device): the plan of MultiMat::to_adaptive(.., ExportMajor::Inner) from counts (n_src x n_inner)
+struct ExportPlan {
+    std::vector<uint64_t> indptr, slab_bounds, moved; // n_inner + 1, n_dst + 1, n_src x n_dst
+};
+inline ExportPlan host_plan_export(const std::vector<uint64_t> &counts, uint32_t n_src, uint64_t n_inner, uint32_t n_dst) {
+    ExportPlan p{std::vector<uint64_t>(n_inner + 1), std::vector<uint64_t>(n_dst + 1), std::vector<uint64_t>((size_t)n_src * n_dst + 1)};
+    check(scanrs_host_plan_export(counts.data(), n_src, n_inner, n_dst, p.indptr.data(), p.slab_bounds.data(), p.moved.data()));
+    p.moved.resize((size_t)n_src * n_dst);
     return p;
 }
 

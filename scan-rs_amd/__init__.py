@@ -218,6 +218,62 @@ class AdaptiveVecDesc(ctypes.Structure):
                 ("n_block_starts", ctypes.c_uint64)]
 
 
+def _export_kind(kind) -> int:
+    """force_kind of the to_adaptive calls: None = choose_storage (-1), a code 0..7, or a name of ADAPTIVE_KINDS."""
+    if isinstance(kind, str):
+        if kind not in ADAPTIVE_KINDS:
+            raise ScanrsError(6, f"unknown AdaptiveVec encoding {kind!r}")
+        return ADAPTIVE_KINDS.index(kind)
+    return -1 if kind is None else int(kind)
+
+
+EXPORT_STORED, EXPORT_INNER = 0, 1  # SCANRS_EXPORT_*
+
+
+def _export_major(major) -> int:
+    """`major` of the to_adaptive calls: "stored" / "inner" or a SCANRS_EXPORT_* code (the library refuses what it does not know)."""
+    if isinstance(major, str):
+        if major not in ("stored", "inner"):
+            raise ScanrsError(6, f"major must be 'stored' or 'inner', not {major!r}")
+        return EXPORT_INNER if major == "inner" else EXPORT_STORED
+    return int(major)
+
+
+def _export_totals(e):
+    """(total_bytes, kind_counts) of a `scanrs_adaptive_export`."""
+    total, counts = ctypes.c_uint64(), (ctypes.c_uint64 * 8)()
+    _check(_lib.scanrs_adaptive_export_info(e, None, ctypes.byref(total), counts))
+    return int(total.value), [int(c) for c in counts]
+
+
+def _export_vecs(e):
+    """The table of a `scanrs_adaptive_export` as the mappings `from_adaptive_vecs` takes (numpy copies)."""
+    n, table = ctypes.c_uint64(), ctypes.POINTER(AdaptiveVecDesc)()
+    _check(_lib.scanrs_adaptive_export_info(e, ctypes.byref(n), None, None))
+    _check(_lib.scanrs_adaptive_export_vecs(e, ctypes.byref(table)))
+
+    def arr(ptr, count, dt):
+        if not count:
+            return np.zeros(0, dtype=dt)
+        return np.ctypeslib.as_array(ctypes.cast(ptr, ctypes.POINTER(np.ctypeslib.as_ctypes_type(dt))), shape=(count,)).copy()
+
+    out = []
+    for i in range(int(n.value)):
+        d = table[i]
+        k = int(d.kind)
+        v = dict(kind=k, len=int(d.len), n_units=int(d.n_units), data=None, index_bytes=None, block_starts=None)
+        v["fallback_indexes"] = arr(d.fallback_indexes, d.n_fallback, np.uint32)
+        v["fallback_values"] = arr(d.fallback_values, d.n_fallback, np.uint32)
+        if k != 4:
+            dt = np.uint64 if k in (0, 5) else np.uint16 if k == 3 else np.uint8
+            v["data"] = arr(d.data, d.data_bytes // np.dtype(dt).itemsize, dt)
+        if k >= 5:
+            v["index_bytes"] = arr(d.index_bytes, d.n_units, np.uint8)
+            v["block_starts"] = arr(d.block_starts, d.n_block_starts, np.uint32)
+        out.append(v)
+    return out
+
+
 def _adaptive_table(vecs):
     """The `scanrs_adaptive_vec` table of one mapping per outer vector (see `AdaptiveMat.from_adaptive_vecs`): (n, table, arrays
     that must outlive the call)."""
@@ -626,58 +682,40 @@ class AdaptiveMat:
         return cls((data, indices.astype(np.int64), indptr.astype(np.int64)), shape=tuple(self.shape()))
 
     # -- back into sqz's own type: the AdaptiveVec encodings (mat.rs:92-124, vec.rs:1086-1160) ----
-    def _export(self, kind):
-        if isinstance(kind, str):
-            if kind not in ADAPTIVE_KINDS:
-                raise ScanrsError(6, f"unknown AdaptiveVec encoding {kind!r}")
-            kind = ADAPTIVE_KINDS.index(kind)
+    def _export(self, kind, major="stored"):
         e = ctypes.c_void_p()
-        _check(_lib.scanrs_mat_to_adaptive(self._h, ctypes.c_int(-1 if kind is None else int(kind)), ctypes.byref(e)))
+        _check(_lib.scanrs_mat_to_adaptive_major(self._h, ctypes.c_int(_export_major(major)), ctypes.c_int(_export_kind(kind)), ctypes.byref(e)))
         return e
 
-    def adaptive_info(self, kind=None):
-        """(total_bytes, kind_counts) of `to_adaptive_vecs(kind)`: the sum of `AdaptiveVec::mem_size` and how many outer vectors
+    def adaptive_info(self, kind=None, major="stored"):
+        """(total_bytes, kind_counts) of `to_adaptive_vecs(kind, major)`: the sum of `AdaptiveVec::mem_size` and how many vectors
         took each of the eight encodings (order of ADAPTIVE_KINDS)."""
-        e = self._export(kind)
+        e = self._export(kind, major)
         try:
-            total, counts = ctypes.c_uint64(), (ctypes.c_uint64 * 8)()
-            _check(_lib.scanrs_adaptive_export_info(e, None, ctypes.byref(total), counts))
-            return int(total.value), [int(c) for c in counts]
+            return _export_totals(e)
         finally:
             _lib.scanrs_adaptive_export_free(e)
 
-    def to_adaptive_vecs(self, kind=None):
+    def to_adaptive_vecs(self, kind=None, major="stored"):
         """`AdaptiveMat::from_csmat` backwards (mat.rs:92-124): the stored counts as one encoded `AdaptiveVec` per outer vector
         (`AdaptiveVec::new`, vec.rs:1086-1160), encoded on the device. kind=None: `choose_storage`; a code 0..7 or a name of
-        ADAPTIVE_KINDS: that encoding for every vector. Returns the mappings `from_adaptive_vecs` takes (kind, len, n_units, data,
-        fallback_indexes, fallback_values, index_bytes, block_starts), numpy copies in the reference's in-memory layout; pieces an
-        encoding does not have are None."""
-        e = self._export(kind)
+        ADAPTIVE_KINDS: that encoding for every vector. major="stored": one vector per stored outer vector; major="inner"
+        (`scanrs_mat_to_adaptive_major`): one per INNER position, from the handle's transposed copy - what `from_adaptive_vecs` takes
+        with the OTHER storage flag; refused on a sharded handle (`MultiMat.to_adaptive_vecs`). Returns the mappings
+        `from_adaptive_vecs` takes (kind, len, n_units, data, fallback_indexes, fallback_values, index_bytes, block_starts), numpy
+        copies in the reference's in-memory layout; pieces an encoding does not have are None."""
+        e = self._export(kind, major)
         try:
-            n, table = ctypes.c_uint64(), ctypes.POINTER(AdaptiveVecDesc)()
-            _check(_lib.scanrs_adaptive_export_info(e, ctypes.byref(n), None, None))
-            _check(_lib.scanrs_adaptive_export_vecs(e, ctypes.byref(table)))
+            return _export_vecs(e)
+        finally:
+            _lib.scanrs_adaptive_export_free(e)
 
-            def arr(ptr, count, dt):
-                if not count:
-                    return np.zeros(0, dtype=dt)
-                return np.ctypeslib.as_array(ctypes.cast(ptr, ctypes.POINTER(np.ctypeslib.as_ctypes_type(dt))), shape=(count,)).copy()
-
-            out = []
-            for i in range(int(n.value)):
-                d = table[i]
-                k = int(d.kind)
-                v = dict(kind=k, len=int(d.len), n_units=int(d.n_units), data=None, index_bytes=None, block_starts=None)
-                v["fallback_indexes"] = arr(d.fallback_indexes, d.n_fallback, np.uint32)
-                v["fallback_values"] = arr(d.fallback_values, d.n_fallback, np.uint32)
-                if k != 4:
-                    dt = np.uint64 if k in (0, 5) else np.uint16 if k == 3 else np.uint8
-                    v["data"] = arr(d.data, d.data_bytes // np.dtype(dt).itemsize, dt)
-                if k >= 5:
-                    v["index_bytes"] = arr(d.index_bytes, d.n_units, np.uint8)
-                    v["block_starts"] = arr(d.block_starts, d.n_block_starts, np.uint32)
-                out.append(v)
-            return out
+    def export_info(self, kind=None, major="stored") -> dict:
+        """`scanrs_adaptive_export_multi_info` of this handle's export: always ScanrsError 6, since only `MultiMat.to_adaptive_vecs`
+        makes an export over shards (the mirror of the C refusal)."""
+        e = self._export(kind, major)
+        try:
+            return _export_multi_info(e)
         finally:
             _lib.scanrs_adaptive_export_free(e)
 
@@ -1277,6 +1315,43 @@ class MultiMat:
         cls = sp.csr_matrix if self.storage == CSR else sp.csc_matrix
         return cls((data, indices.astype(np.int64), indptr.astype(np.int64)), shape=tuple(self.shape()))
 
+    # -- back into sqz's own type: the whole matrix as AdaptiveVec encodings, in either orientation ----
+    def _export(self, kind, major="stored"):
+        e = ctypes.c_void_p()
+        _check(_lib.scanrs_multi_to_adaptive(self._h, ctypes.c_int(_export_major(major)), ctypes.c_int(_export_kind(kind)), ctypes.byref(e)))
+        return e
+
+    def to_adaptive_vecs(self, kind=None, major="stored"):
+        """`scanrs_multi_to_adaptive`: the stored counts of the WHOLE matrix as one list of encoded `AdaptiveVec` mappings (see
+        `AdaptiveMat.to_adaptive_vecs`), made on the devices. major="stored": one per outer vector in global order, what
+        `AdaptiveMat.from_csmat(*mm.to_csmat()).to_adaptive_vecs(kind)` returns. major="inner", the inverse of
+        `from_adaptive_vecs_inner`: one per INNER position (per gene, for a cell-sharded genes x cells matrix), each spanning all
+        shards, with len = the sharded extent - what `from_adaptive_vecs` takes with the OTHER storage flag, byte for byte the export
+        of the host-transposed whole matrix whatever the shards."""
+        e = self._export(kind, major)
+        try:
+            return _export_vecs(e)
+        finally:
+            _lib.scanrs_adaptive_export_free(e)
+
+    def adaptive_info(self, kind=None, major="stored"):
+        """(total_bytes, kind_counts) of `to_adaptive_vecs(kind, major)`, over the whole table."""
+        e = self._export(kind, major)
+        try:
+            return _export_totals(e)
+        finally:
+            _lib.scanrs_adaptive_export_free(e)
+
+    def export_info(self, kind=None, major="inner") -> dict:
+        """`scanrs_adaptive_export_multi_info` of `to_adaptive_vecs(kind, major)`: slab_bounds (n_shards + 1: the table entries shard d
+        encoded), moved (n_shards x n_shards: nonzeros of source shard s in slab d) and arena_bytes per shard (the encoded bytes that
+        crossed the host link)."""
+        e = self._export(kind, major)
+        try:
+            return _export_multi_info(e)
+        finally:
+            _lib.scanrs_adaptive_export_free(e)
+
     def _select(self, fn, idx) -> "MultiMat":
         idx = _index_list(idx)
         h = ctypes.c_void_p()
@@ -1683,6 +1758,32 @@ def host_plan_inner(indptr, indices, n_inner: int, world: int):
     return sb, bd, mv
 
 
+def _export_multi_info(e) -> dict:
+    """What `scanrs_multi_to_adaptive` did for the export `e` (ScanrsError 6 on an export of a single handle)."""
+    n = ctypes.c_uint32()
+    _check(_lib.scanrs_adaptive_export_multi_info(e, ctypes.byref(n), None, None, None))
+    n = int(n.value)
+    sb, mv, ab = np.zeros(n + 1, dtype=np.uint64), np.zeros((max(n, 1), max(n, 1)), dtype=np.uint64), np.zeros(max(n, 1), dtype=np.uint64)
+    _check(_lib.scanrs_adaptive_export_multi_info(e, None, _p(sb), _p(mv), _p(ab)))
+    return {"n_shards": n, "slab_bounds": sb, "moved": mv[:n, :n], "arena_bytes": ab[:n]}
+
+
+def host_plan_export(counts, n_dst: int):
+    """`scanrs_host_plan_export` (host only, no device): the plan of `MultiMat.to_adaptive_vecs(major="inner")` from counts
+    (n_src x n_inner: the stored entries source shard s holds of every inner position). Returns (indptr, slab_bounds, moved): the
+    whole matrix's inner-major indptr (n_inner + 1), the slabs of inner positions scanrs_plan_shards gives for it (n_dst + 1) and the
+    n_src x n_dst table of entries of source s in slab d."""
+    c = np.ascontiguousarray(counts, dtype=np.uint64)
+    if c.ndim != 2:
+        raise ScanrsError(6, "counts: an n_src x n_inner table is required")
+    n_src, n_inner, n_dst = c.shape[0], c.shape[1], int(n_dst)
+    tip, sb = np.zeros(n_inner + 1, dtype=np.uint64), np.zeros(max(n_dst, 0) + 1, dtype=np.uint64)
+    mv = np.zeros((max(n_src, 1), max(n_dst, 1)), dtype=np.uint64)
+    _check(_lib.scanrs_host_plan_export(_p(c) if c.size else None, ctypes.c_uint32(n_src), ctypes.c_uint64(n_inner), ctypes.c_uint32(n_dst), _p(tip),
+                                        _p(sb), _p(mv)))
+    return tip, sb, mv[:n_src, :n_dst]
+
+
 def host_plan_gather(indptr, src_bounds, idx, n_dst: int):
     """`scanrs_host_plan_gather` (host only, no device): the plan of `MultiMat.gather_outer` / `rebalance` from the source's global
     indptr, its shard bounds (n_src + 1 entries) and the list. Returns (indptr, bounds, moved): the selected matrix's indptr
@@ -1761,7 +1862,8 @@ EXPORTED_SYMBOLS = [
     "scanrs_mat_select_rows", "scanrs_mat_select_cols", "scanrs_mat_partition_on_thresholds", "scanrs_mat_to_csmat",
     "scanrs_mat_select_rows_sharded", "scanrs_mat_select_cols_sharded", "scanrs_mat_partition_on_thresholds_sharded", "scanrs_mat_shard_info",
     "scanrs_multi_shape", "scanrs_multi_to_csmat", "scanrs_multi_select_rows", "scanrs_multi_select_cols", "scanrs_multi_partition_on_thresholds",
-    "scanrs_mat_to_adaptive", "scanrs_adaptive_export_info", "scanrs_adaptive_export_vecs", "scanrs_adaptive_export_free",
+    "scanrs_mat_to_adaptive", "scanrs_mat_to_adaptive_major", "scanrs_multi_to_adaptive", "scanrs_adaptive_export_multi_info", "scanrs_host_plan_export",
+    "scanrs_adaptive_export_info", "scanrs_adaptive_export_vecs", "scanrs_adaptive_export_free",
     "scanrs_host_choose_storage", "scanrs_host_col_moments_plan", "scanrs_host_spmm_route", "scanrs_host_bk_plan",
     "scanrs_mat_sum_rows_u64", "scanrs_mat_sum_rows_f64", "scanrs_mat_sum_cols_u64", "scanrs_mat_sum_cols_f64", "scanrs_mat_sum_rows_dual_u64",
     "scanrs_mat_sum_rows_dual_f64", "scanrs_mat_mean_rows", "scanrs_mat_mean_var_rows", "scanrs_mat_var_axis",

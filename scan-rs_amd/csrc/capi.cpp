@@ -1617,6 +1617,10 @@ int scanrs_mat_get_counter(scanrs_mat *m, const char *key, uint64_t *value) {
             // a shard made by scanrs_multi_gather_outer / _rebalance (multi.cpp): wall clock of the plan (the sources' lengths to the host and
             // the host plan: one phase, the same on every shard) and of the shard's own thread in pull and finish
             *value = m->st->regather_us[k == "regather_plan_us" ? 0 : k == "regather_pull_us" ? 1 : 2];
+        } else if (k == "export_plan_us" || k == "export_pull_us" || k == "export_encode_us") {
+            // a shard of the last scanrs_multi_to_adaptive (multi.cpp): wall clock of the plan (one phase, the same on every shard) and of
+            // the shard's own thread in the pull of its slab and in encode + download
+            *value = m->st->export_us[k == "export_plan_us" ? 0 : k == "export_pull_us" ? 1 : 2];
         } else if (k == "t_layout_us") // first-call accounting: host time of the calling thread in tile layout builds ...
             *value = m->st->t_layout_us;
         else if (k == "t_side_wait_us") // ... waiting for the helper thread that builds the second orientation

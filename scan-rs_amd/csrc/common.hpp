@@ -405,6 +405,7 @@ struct Storage {
     uint64_t de_pairs_passes = 0, de_pairs_literal = 0; // the last scanrs_sseq_de_pairs on this handle: passes over the nonzeros, pairs on the literal route (scanrs_mat_get_counter)
     uint64_t reshard_us[5] = {0, 0, 0, 0, 0}; // a shard of scanrs_multi_create_inner and kin: its thread's wall clock in upload, count, split, exchange, transpose (scanrs_mat_get_counter)
     uint64_t regather_us[3] = {0, 0, 0};  // a shard of scanrs_multi_gather_outer / _rebalance: wall clock of the plan (one phase of the calling thread, the same on every shard) and of its own thread in pull and finish (scanrs_mat_get_counter)
+    uint64_t export_us[3] = {0, 0, 0};    // a shard of the last scanrs_multi_to_adaptive: wall clock of the plan (the transposed copies, their indptr to the host and the host plan: one phase, the same on every shard; 0 for major STORED) and of its own thread in pull (0 for STORED) and encode + download (scanrs_mat_get_counter)
     int subset_scatter = 1;               // integer sums over a column list when only the other orientation exists: 1 = scattered into the result with 64-bit integer atomics from the copy that exists, 0 = the missing copy is built (subset_host.cpp)
     uint64_t subset_masked_passes = 0, subset_scatter_passes = 0; // sums over a column list made so far on this handle: from the copy whose outer dimension is the result axis / through the integer scatter (scanrs_mat_get_counter)
     uint64_t knn_blocks = 0, knn_allreduces = 0; // the last scanrs_knn_sharded on this handle: blocks of the point set searched, exchange steps (an unsharded one: 0)
@@ -735,6 +736,33 @@ void launch_regather_pull(hipStream_t s, const RegatherSources &src, const uint6
 void regather_host_plan(const uint64_t *indptr, uint64_t n_outer, const uint64_t *src_bounds, uint32_t n_src, const uint64_t *idx, uint64_t n_idx,
                         uint32_t n_dst, uint64_t *out_indptr, uint64_t *bounds, uint64_t *moved);
 void regather_check_list(const uint64_t *idx, uint64_t n_idx, uint64_t n_outer);
+// export_multi.hip / encode_host.cpp: scanrs_multi_to_adaptive (multi.cpp). The sources of the INNER pull are the shards'
+// TRANSPOSED copies: source s holds all n_inner vectors over its own outer range [bounds[s], bounds[s + 1]), indices local.
+// A destination's slab: the n_vec inner positions from g0 on, over all outer positions.
+// d_len (n_vec + 1 entries): the length of every slab vector over all sources (+ the scan's spare entry)
+void launch_export_len(hipStream_t s, const RegatherSources &src, uint64_t g0, uint64_t n_vec, unsigned long long *d_len);
+// d_start ((src.n + 1) x n_vec): where source s's piece of every slab vector begins in the slab (d_indptr: the slab's n_vec + 1 offsets)
+void launch_export_start(hipStream_t s, const RegatherSources &src, uint64_t g0, uint64_t n_vec, const uint64_t *d_indptr, uint64_t *d_start);
+// the nnz entries of the slab, every one read at its place in a source's arrays, its index raised by the source's outer_begin
+void launch_export_pull(hipStream_t s, const RegatherSources &src, uint64_t g0, const uint64_t *d_indptr, const uint64_t *d_start, uint64_t n_vec,
+                        uint64_t nnz, uint64_t outer_global, uint32_t *d_out_idx, uint32_t *d_out_val);
+// the plan on host arrays (scanrs_host_plan_export; the device path runs the same function on the counts it took from the shards'
+// transposed indptr arrays): counts is n_src x n_inner, source-major. out_indptr (n_inner + 1): the whole matrix's inner-major indptr;
+// slab_bounds (n_dst + 1): scanrs_plan_shards over it; moved (n_src x n_dst, source-major). Any output may be null. Refusals: a null
+// table with entries, shard counts outside 1 .. 16 (SCANRS_ERR_ARGUMENT).
+void export_host_plan(const uint64_t *counts, uint32_t n_src, uint64_t n_inner, uint32_t n_dst, uint64_t *out_indptr, uint64_t *slab_bounds,
+                      uint64_t *moved);
+// The export object as scanrs_multi_to_adaptive fills it (encode_host.cpp): a table of n_vecs entries and n_parts pairs of host arenas.
+// adaptive_export_encode runs the encoders over `cp` on st's stream and the current device, brings the two arenas down into part
+// `part` and fills the table entries [first_vec, first_vec + cp.n_outer); calls on different parts may run on different threads.
+// *arena_bytes: the bytes of the two arenas that crossed the host link. adaptive_export_finish sums the parts' accounting and records
+// what the multi call did (scanrs_adaptive_export_multi_info).
+scanrs_adaptive_export *adaptive_export_new(uint64_t n_vecs, uint32_t n_parts);
+void adaptive_export_encode(scanrs_adaptive_export *e, uint32_t part, Storage &st, const SparseCopy &cp, int force_kind, uint64_t first_vec,
+                            uint64_t *arena_bytes);
+void adaptive_export_finish(scanrs_adaptive_export *e, const std::vector<uint64_t> &slab_bounds, const std::vector<uint64_t> &moved,
+                            const std::vector<uint64_t> &arena_bytes);
+void adaptive_check_export_args(const void *handle, int major, int force_kind, scanrs_adaptive_export **out);
 // capi.cpp: a registered Storage with its main stream on the current device (what every handle starts from)
 SCANRS_LOCAL std::shared_ptr<Storage> new_storage(uint64_t rows, uint64_t cols, int storage);
 // comm.cpp

@@ -5,7 +5,8 @@
 // exchange steps go through the library's single-process group (comm.cpp). Several shards may share one device
 // (`devices` repeats an id): that is how a 1-GPU box exercises the whole path. A matrix that arrives feature-major (the reference's
 // own orientation) is sharded over its INNER dimension by the constructors further down (scanrs_multi_create_inner); an
-// existing scanrs_multi is cut anew, reordered or moved to other devices by scanrs_multi_gather_outer / _rebalance at the end (§7n).
+// existing scanrs_multi is cut anew, reordered or moved to other devices by scanrs_multi_gather_outer / _rebalance (§7n), and the whole
+// matrix leaves as AdaptiveVec encodings, in either orientation, through scanrs_multi_to_adaptive at the end (§7p).
 #include <functional>
 #include <thread>
 
@@ -1153,6 +1154,180 @@ int scanrs_multi_gather_info(const scanrs_multi *mm, uint32_t *n_src, uint64_t *
     if (moved) std::copy(info.moved.begin(), info.moved.end(), moved);
     if (host_bytes) std::copy(info.host_bytes.begin(), info.host_bytes.end(), host_bytes);
     return SCANRS_OK;
+}
+
+// ---- to_adaptive of the whole matrix, in either orientation (mat.rs:92-124 backwards, hdf5-io/src/matrix.rs:119-192) --------
+// STORED: every shard runs the encoders on its own primary copy; one table in global order over one pair of host arenas per shard.
+// INNER, the inverse of scanrs_multi_create_adaptive_inner: one vector per inner position, spanning all shards. An encoding of a
+// vector's slice cannot be concatenated, so the vectors are made whole on a device first:
+//   copies  every shard settles its transposed copy T_s (n_inner vectors over its own outer positions) and sends T_s's indptr down;
+//   plan    export_host_plan (the code of scanrs_host_plan_export): the whole matrix's inner-major indptr from the summed counts, cut
+//           by scanrs_plan_shards into one slab of inner positions per shard, and `moved`;
+//   pull    destination d assembles the CSR of slab d over all outer positions out of the sources' T_s, in place (export_multi.hip);
+//   encode  the encoders run on the slab as on any SparseCopy, the two arenas come down, the slab goes.
+// The phases are separate fan_outs (the join of the shard threads is the barrier, a failing shard ends its phase for all); no wait
+// inside a phase depends on another shard, and the sources' arrays are only read.
+} // extern "C"
+
+namespace {
+
+using ExportPtr = std::unique_ptr<scanrs_adaptive_export, void (*)(scanrs_adaptive_export *)>;
+
+int multi_to_adaptive(scanrs_multi *mm, int major, int force_kind, scanrs_adaptive_export **out) {
+    const uint32_t n = (uint32_t)mm->shards.size();
+    const uint64_t outer_global = mm->bounds.back(), n_inner = mm->storage == SCANRS_CSR ? mm->cols : mm->rows;
+    ExportPtr e(nullptr, scanrs_adaptive_export_free);
+    std::vector<uint64_t> slab_bounds(n + 1, 0), moved((size_t)n * n, 0), arena_bytes(n, 0);
+    const auto shard_storage = [&](size_t i) -> Storage & {
+        need_device();
+        Storage &st = *mm->shards[i]->st;
+        if (st.primary.n_outer != mm->bounds[i + 1] - mm->bounds[i] || st.primary.n_inner != n_inner)
+            fail(SCANRS_ERR_DEVICE, "internal: a shard does not hold its range");
+        return st;
+    };
+
+    if (major == SCANRS_EXPORT_STORED) {
+        int rc = guard([&] { e.reset(adaptive_export_new(outer_global, n)); });
+        slab_bounds = mm->bounds;
+        if (rc == SCANRS_OK)
+            rc = fan_out(mm, [&](size_t i) {
+                return guard([&] {
+                    Storage &st = shard_storage(i);
+                    CurrentHandle cur(&st);
+                    st.export_us[0] = st.export_us[1] = st.export_us[2] = 0;
+                    PhaseClock clock(st.export_us[2]);
+                    adaptive_export_encode(e.get(), (uint32_t)i, st, st.primary, force_kind, mm->bounds[i], &arena_bytes[i]);
+                    moved[i * n + i] = st.primary.nnz;
+                });
+            });
+        if (rc != SCANRS_OK) return rc;
+        if (const int rc2 = guard([&] { adaptive_export_finish(e.get(), slab_bounds, moved, arena_bytes); })) return rc2;
+        *out = e.release();
+        return SCANRS_OK;
+    }
+
+    // copies: T_s on every shard, its indptr to the host (8 (n_inner + 1) bytes: all that crosses the host link before the arenas)
+    const auto t_plan = std::chrono::steady_clock::now();
+    std::vector<uint64_t> counts, tip(n_inner + 1, 0);
+    std::vector<const SparseCopy *> tcopy(n, nullptr);
+    int rc = guard([&] {
+        if (n > REGATHER_MAX_SHARDS) fail(SCANRS_ERR_ARGUMENT, "mm: a scanrs_multi of more than 16 shards is not served");
+        if (outer_global > 0xFFFFFFFFull || n_inner > 0xFFFFFFFFull) fail(SCANRS_ERR_SHAPE, "dimensions must fit in u32 (AdaptiveVec limit)");
+        for (uint32_t d = 0; d < n; d++)
+            for (uint32_t s = 0; s < n; s++) enable_peer(mm->devices[d], mm->devices[s]);
+        counts.assign((size_t)n * n_inner, 0);
+    });
+    if (rc == SCANRS_OK)
+        rc = fan_out(mm, [&](size_t s) {
+            return guard([&] {
+                Storage &st = shard_storage(s);
+                CurrentHandle cur(&st);
+                st.export_us[0] = st.export_us[1] = st.export_us[2] = 0;
+                const SparseCopy &t = st.copy_with_outer_rows(st.storage != SCANRS_CSR); // built as the products build it, and kept
+                if (t.n_outer != n_inner || t.n_inner != st.primary.n_outer || t.nnz != st.primary.nnz)
+                    fail(SCANRS_ERR_DEVICE, "internal: a shard's transposed copy does not match its range");
+                std::vector<uint64_t> ip(n_inner + 1, 0);
+                SCANRS_D2H(ip.data(), t.indptr.p, (n_inner + 1) * 8, st.stream);
+                SCANRS_SYNC(st.stream); // whatever was queued on the source before this call is done before a destination reads its arrays
+                if (ip[n_inner] != t.nnz) fail(SCANRS_ERR_DEVICE, "internal: a shard's transposed indptr does not end at its nonzeros");
+                for (uint64_t g = 0; g < n_inner; g++) counts[s * n_inner + g] = ip[g + 1] - ip[g];
+                tcopy[s] = &t;
+            });
+        });
+    // plan: on the host, the code of scanrs_host_plan_export
+    if (rc == SCANRS_OK)
+        rc = guard([&] {
+            export_host_plan(counts.data(), n, n_inner, n, tip.data(), slab_bounds.data(), moved.data());
+            std::vector<uint64_t>().swap(counts);
+            e.reset(adaptive_export_new(n_inner, n));
+        });
+    const uint64_t plan_us = (uint64_t)std::chrono::duration<double, std::micro>(std::chrono::steady_clock::now() - t_plan).count();
+
+    // pull: every destination assembles the CSR of its slab out of the sources' transposed copies
+    std::vector<SparseCopy> slab(n);
+    if (rc == SCANRS_OK)
+        rc = fan_out(mm, [&](size_t d) {
+            return guard([&] {
+                Storage &st = *mm->shards[d]->st;
+                CurrentHandle cur(&st);
+                st.export_us[0] = plan_us; // (the plan is one phase for all shards)
+                PhaseClock clock(st.export_us[1]);
+                RegatherSources from;
+                from.n = n;
+                for (uint32_t s = 0; s < n; s++) {
+                    from.bounds[s] = mm->bounds[s];
+                    from.nnz[s] = tcopy[s]->nnz;
+                    from.indptr[s] = tcopy[s]->indptr.p;
+                    from.indices[s] = tcopy[s]->indices.p;
+                    from.values[s] = tcopy[s]->values.p;
+                }
+                from.bounds[n] = outer_global;
+                const uint64_t g0 = slab_bounds[d], nv = slab_bounds[d + 1] - g0, nnz = tip[g0 + nv] - tip[g0];
+                SparseCopy &cp = slab[d];
+                cp.n_outer = nv;
+                cp.n_inner = outer_global;
+                cp.nnz = nnz;
+                DevBuf<uint64_t> d_start;
+                try {
+                    cp.indptr.alloc(nv + 1);
+                    cp.indices.alloc(std::max<uint64_t>(1, nnz));
+                    cp.values.alloc(std::max<uint64_t>(1, nnz));
+                    d_start.alloc(std::max<uint64_t>(1, (uint64_t)(n + 1) * nv));
+                } catch (const Failure &f) {
+                    if (f.code != SCANRS_ERR_DEVICE) throw;
+                    const std::string why = scanrs_last_error();
+                    fail(SCANRS_ERR_DEVICE, "shard %zu cannot hold its export slab (%llu vectors, %llu nonzeros: %llu bytes) beside what the library holds: %s", d,
+                         (unsigned long long)nv, (unsigned long long)nnz, (unsigned long long)(8 * nnz + 8 * (nv + 1) * (n + 2)), why.c_str());
+                }
+                launch_export_len(st.stream, from, g0, nv, reinterpret_cast<unsigned long long *>(cp.indptr.p));
+                select_scan_offsets(st.stream, reinterpret_cast<unsigned long long *>(cp.indptr.p), nv);
+                // the one value that comes back: the device's lengths add up to the plan's
+                const uint64_t got = SCANRS_D2H_VALUE(cp.indptr.p + nv, st.stream);
+                if (got != nnz)
+                    fail(SCANRS_ERR_DEVICE, "internal: the lengths of an export slab (%llu entries) do not match the plan (%llu)", (unsigned long long)got, (unsigned long long)nnz);
+                launch_export_start(st.stream, from, g0, nv, cp.indptr.p, d_start.p);
+                launch_export_pull(st.stream, from, g0, cp.indptr.p, d_start.p, nv, nnz, outer_global, cp.indices.p, cp.values.p);
+                SCANRS_SYNC(st.stream); // the start table is released on return
+            });
+        });
+
+    // encode: the slab as any SparseCopy; the arenas come down into the export's own memory, then the slab goes
+    if (rc == SCANRS_OK)
+        rc = fan_out(mm, [&](size_t d) {
+            return guard([&] {
+                Storage &st = *mm->shards[d]->st;
+                CurrentHandle cur(&st);
+                PhaseClock clock(st.export_us[2]);
+                adaptive_export_encode(e.get(), (uint32_t)d, st, slab[d], force_kind, slab_bounds[d], &arena_bytes[d]);
+                slab[d] = SparseCopy();
+                device_free_flush(); // the stream is idle here
+            });
+        });
+
+    // whatever is left of the slabs goes back under the handle that made it (a failure; nothing after a success)
+    const auto drop_slabs = [&] {
+        for (uint32_t d = 0; d < n; d++) {
+            if (!slab[d].indptr.p && !slab[d].indices.p && !slab[d].values.p) continue;
+            (void)hipSetDevice(mm->devices[d]);
+            CurrentHandle cur(mm->shards[d]->st.get(), true);
+            slab[d] = SparseCopy();
+            device_free_flush();
+        }
+    };
+    if (rc == SCANRS_OK) rc = guard([&] { adaptive_export_finish(e.get(), slab_bounds, moved, arena_bytes); });
+    if (rc != SCANRS_OK) return failed(rc, drop_slabs);
+    *out = e.release();
+    return SCANRS_OK;
+}
+
+} // namespace
+
+extern "C" {
+
+int scanrs_multi_to_adaptive(scanrs_multi *mm, int major, int force_kind, scanrs_adaptive_export **out) {
+    // everything that can be refused is refused here, before any device work
+    if (const int rc = guard([&] { adaptive_check_export_args(mm, major, force_kind, out); })) return rc;
+    return multi_to_adaptive(mm, major, force_kind, out);
 }
 
 } // extern "C"

@@ -7,6 +7,14 @@ partition_on_threshold. Per handle one JSON line: bytes over the link, kernel ms
 and the kind histogram.
 
     python tools/adaptive_export_bench.py [--cells 1000000] [--genes 33000] [--density 0.03] [--threshold 2500] [--reps 3]
+
+With --shards N [--major inner|stored] the same matrix is held as a MultiMat over N shards (all on device 0) and ONE JSON line reports
+scanrs_multi_to_adaptive: wall ms (median of --reps calls after the first, which for `inner` also builds the shards'
+transposed copies and is reported on its own), the phase counters export_{plan,pull,encode}_us of the slowest shard, encoded bytes,
+arena_bytes and moved, the byte comparison against the unsharded export, and beside them the route a caller has without it:
+MultiMat.to_csmat(), plus scipy's transposition for `inner`.
+
+    python tools/adaptive_export_bench.py --shards 4 --major inner
 """
 import argparse
 import ctypes
@@ -85,6 +93,143 @@ def measure(name, h, reps):
     }), flush=True)
 
 
+# ---- the whole MultiMat (--shards N, --major inner|stored) ---------------------------------------------------------------
+_OFF = {name: getattr(sa.AdaptiveVecDesc, name).offset // 8 for name, _ in sa.AdaptiveVecDesc._fields_}
+_SIZES = ("len", "n_units", "data_bytes", "n_fallback", "n_block_starts")
+
+
+def export_table(e):
+    """The table of an export as u64 words (n_vecs x words of scanrs_adaptive_vec), borrowed from the export."""
+    n, table = ctypes.c_uint64(), ctypes.POINTER(sa.AdaptiveVecDesc)()
+    sa._check(sa._lib.scanrs_adaptive_export_info(e, ctypes.byref(n), None, None))
+    sa._check(sa._lib.scanrs_adaptive_export_vecs(e, ctypes.byref(table)))
+    words = ctypes.sizeof(sa.AdaptiveVecDesc) // 8
+    if not n.value:
+        return np.zeros((0, words), dtype=np.uint64)
+    return np.ctypeslib.as_array(ctypes.cast(table, ctypes.POINTER(ctypes.c_uint64)), shape=(int(n.value), words))
+
+
+def arena_views(t, bounds):
+    """The two host arenas behind the table rows [bounds[d], bounds[d + 1]) of every part d, as numpy views: a part's pieces lie in
+    vector order, every piece of the byte arena padded to 8 bytes (data, then index_bytes of S*; nothing for V), the word arena
+    holding fallback indexes, fallback values and block_starts. The pointers of the table are checked against that layout."""
+    pad8 = lambda x: (x + np.uint64(7)) & ~np.uint64(7)  # noqa: E731
+    out = []
+    for lo, hi in zip(bounds[:-1], bounds[1:]):
+        r = t[int(lo):int(hi)]
+        if not r.shape[0]:
+            out.append((np.zeros(0, dtype=np.uint8), np.zeros(0, dtype=np.uint32)))
+            continue
+        kind = r[:, _OFF["kind"]] & np.uint64(0xFFFFFFFF)
+        bsz = np.where(kind != 4, pad8(r[:, _OFF["data_bytes"]]), 0).astype(np.uint64) + np.where(kind >= 5, pad8(r[:, _OFF["n_units"]]), 0).astype(np.uint64)
+        wsz = (2 * r[:, _OFF["n_fallback"]] + r[:, _OFF["n_block_starts"]]).astype(np.uint64)
+        boff = np.concatenate([[0], np.cumsum(bsz)]).astype(np.uint64)
+        woff = np.concatenate([[0], np.cumsum(wsz)]).astype(np.uint64)
+        wbase = int(r[0, _OFF["fallback_indexes"]])
+        assert np.array_equal(r[:, _OFF["fallback_indexes"]], np.uint64(wbase) + 4 * woff[:-1]), "the word arena is not laid out in vector order"
+        words = np.ctypeslib.as_array(ctypes.cast(wbase, ctypes.POINTER(ctypes.c_uint32)), shape=(int(woff[-1]),)) if woff[-1] else np.zeros(0, dtype=np.uint32)
+        has = np.nonzero(kind != 4)[0]
+        if has.size and boff[-1]:
+            bbase = int(r[has[0], _OFF["data"]]) - int(boff[has[0]])
+            assert np.array_equal(r[has, _OFF["data"]], np.uint64(bbase) + boff[:-1][has]), "the byte arena is not laid out in vector order"
+            bts = np.ctypeslib.as_array(ctypes.cast(bbase, ctypes.POINTER(ctypes.c_uint8)), shape=(int(boff[-1]),))
+        else:
+            bts = np.zeros(0, dtype=np.uint8)
+        out.append((bts, words))
+    return out
+
+
+def exports_equal(e_multi, slab_bounds, e_single):
+    """Byte comparison of two exports of the same matrix: every size field of the tables, then the arenas, the multi export's parts
+    against the matching stretch of the single one's."""
+    tm, ts = export_table(e_multi), export_table(e_single)
+    if tm.shape != ts.shape:
+        return False
+    cols = [_OFF[k] for k in _SIZES]
+    if not (np.array_equal(tm[:, cols], ts[:, cols]) and np.array_equal(tm[:, _OFF["kind"]] & np.uint64(0xFFFFFFFF), ts[:, _OFF["kind"]] & np.uint64(0xFFFFFFFF))):
+        return False
+    (sb, sw), = arena_views(ts, [0, ts.shape[0]])
+    b_at = w_at = 0
+    for pb, pw in arena_views(tm, slab_bounds):
+        if not (np.array_equal(pb, sb[b_at:b_at + pb.shape[0]]) and np.array_equal(pw, sw[w_at:w_at + pw.shape[0]])):
+            return False
+        b_at, w_at = b_at + pb.shape[0], w_at + pw.shape[0]
+    return b_at == sb.shape[0] and w_at == sw.shape[0]
+
+
+def measure_multi(a, triplet):
+    """MultiMat.to_adaptive_vecs' export (scanrs_multi_to_adaptive) over --shards shards of ONE device against (1) the unsharded
+    export of the same matrix, byte for byte, and (2) the route a caller has without it: MultiMat.to_csmat(), plus scipy's
+    transposition for `inner` (AdaptiveVec::new per vector on the host would still follow: it is not timed). One JSON line."""
+    import scipy.sparse as sp
+
+    n, major = a.shards, a.major
+    hip, hix, hvv = triplet
+    mm = sa.MultiMat(a.genes, a.cells, sa.CSC, hip, hix, hvv, n, devices=[0] * n)
+    single = sa.AdaptiveMat.from_csmat(a.genes, a.cells, sa.CSC, hip, hix, hvv)
+
+    def timed_export(x):
+        t0 = time.perf_counter()
+        e = x._export(None, major)
+        return (time.perf_counter() - t0) * 1e3, e
+
+    first_ms, e = timed_export(mm)  # (inner: settles the shards' transposed copies, which they keep)
+    sa._lib.scanrs_adaptive_export_free(e)
+    runs = []
+    for _ in range(a.reps):
+        ms, e = timed_export(mm)
+        phases = {p: round(max(mm.counter(f"export_{p}_us", i) for i in range(n)) / 1e3, 3) for p in ("plan", "pull", "encode")}
+        runs.append((ms, phases))
+        sa._lib.scanrs_adaptive_export_free(e)
+    multi_ms = float(np.median([r[0] for r in runs]))
+    ms, e = timed_export(mm)
+    info = sa._export_multi_info(e)
+    total, counts = sa._export_totals(e)
+    s_first_ms, es = timed_export(single)
+    sa._lib.scanrs_adaptive_export_free(es)
+    single_runs = []
+    for _ in range(a.reps):
+        s_ms, es = timed_export(single)
+        sa._lib.scanrs_adaptive_export_free(es)
+        single_runs.append(s_ms)
+    single_ms = float(np.median(single_runs))
+    _, es = timed_export(single)
+    equal = exports_equal(e, info["slab_bounds"], es)
+    n_vecs = int(export_table(e).shape[0])
+    sa._lib.scanrs_adaptive_export_free(es)
+    sa._lib.scanrs_adaptive_export_free(e)
+    del single
+    # the route a caller has today
+    t0 = time.perf_counter()
+    wip, wix, wvv = mm.to_csmat()
+    csmat_ms = (time.perf_counter() - t0) * 1e3
+    scipy_ms = 0.0
+    if major == "inner":
+        t1 = time.perf_counter()
+        whole = sp.csc_matrix((wvv, wix.astype(np.int32), wip.astype(np.int64)), shape=(a.genes, a.cells))
+        whole.has_sorted_indices = True
+        by_gene = whole.tocsr()
+        scipy_ms = (time.perf_counter() - t1) * 1e3
+        del whole, by_gene
+    nnz = int(wix.shape[0])
+    moved = info["moved"]
+    print(json.dumps({
+        "matrix": "synthetic", "major": major, "shards": n, "all_shards_on_device": 0, "vectors": n_vecs, "len": a.cells if major == "inner" else a.genes,
+        "nnz": nnz, "reps": a.reps,
+        "multi_to_adaptive": {"wall_ms": round(multi_ms, 2), "first_call_wall_ms": round(first_ms, 2), "phase_ms": runs[-1][1], "encoded_bytes": total,
+                              "arena_bytes": [int(x) for x in info["arena_bytes"]], "moved_total": int(moved.sum()),
+                              "moved_between_shards": int(moved.sum() - np.trace(moved)), "kinds": dict(zip(sa.ADAPTIVE_KINDS, counts))},
+        "unsharded_to_adaptive": {"wall_ms": round(single_ms, 2), "first_call_wall_ms": round(s_first_ms, 2)},
+        "equals_unsharded_export": bool(equal),
+        "host_route": {"to_csmat_ms": round(csmat_ms, 2), "scipy_transpose_ms": round(scipy_ms, 2), "wall_ms": round(csmat_ms + scipy_ms, 2),
+                       "link_bytes": 8 * nnz + 8 * (a.cells + 1), "adaptive_vec_new_on_the_host": "not timed"},
+        "link_bytes_multi_over_host_route": round(float(info["arena_bytes"].sum()) / max(8 * nnz, 1), 4),
+        "multi_faster_than_host_route": bool(multi_ms < csmat_ms + scipy_ms),
+        "wall_ratio_multi_over_host_route": round(multi_ms / max(csmat_ms + scipy_ms, 1e-9), 4),
+    }), flush=True)
+    mm.close()
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--cells", type=int, default=1_000_000)
@@ -93,7 +238,11 @@ def main():
     ap.add_argument("--seed", type=int, default=0)
     ap.add_argument("--threshold", type=float, default=2500.0)
     ap.add_argument("--reps", type=int, default=3)
+    ap.add_argument("--shards", type=int, default=0, help="N > 0: the export of a MultiMat over N shards (all on device 0) instead of one handle's")
+    ap.add_argument("--major", choices=("inner", "stored"), default=None, help="with --shards: the orientation of the table (default stored)")
     a = ap.parse_args()
+    if a.major is not None and a.shards <= 0:
+        ap.error("--major needs --shards N")
     import torch
 
     dev = torch.device("cuda", 0)
@@ -103,6 +252,12 @@ def main():
     base = sa.AdaptiveMat.from_device(a.genes, a.cells, sa.CSC, ip.data_ptr(), ix.data_ptr(), vv.data_ptr())
     del ip, ix, vv
     torch.cuda.empty_cache()
+    if a.shards > 0:
+        a.major = a.major or "stored"
+        triplet = base.to_csmat()  # what a caller hands to MultiMat(...)
+        del base
+        measure_multi(a, triplet)
+        return
     measure("synthetic", base, a.reps)
     f, _, _, _ = base.partition_on_thresholds(a.threshold, a.threshold, residual=False)
     measure(f"partition_on_threshold({a.threshold:g}).filtered", f, a.reps)
