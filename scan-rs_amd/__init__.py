@@ -1621,7 +1621,7 @@ def host_knn_merge(da, ia, db, ib):
 
 def host_col_moments_plan(max_count: int, links, n_outer: int, n_inner: int, n_wg: int, mode: int):
     """The plan of the fixed-point column moments on the host (`scanrs_host_col_moments_plan`; scan-rs_amd/csrc/col_moments_plan.hpp,
-    the source kernels.hip decides by). `links`: the map's links in order, each `(FN_LN_1P | FN_LOG2_1P | FN_LOG10_1P,)` or
+    the source normalize_ops.hip decides by). `links`: the map's links in order, each `(FN_LN_1P | FN_LOG2_1P | FN_LOG10_1P,)` or
     `("scale", fmin_pos, fmax)` / `("scale", fmin_pos, fmax, on_summed_axis)` with the link's smallest positive and its largest
     factor. Returns (accept, e1, e2): the terms are added as rint(f * 2**e1) and rint(f * f * 2**e2)."""
     kinds, on, lo, hi = [], [], [], []

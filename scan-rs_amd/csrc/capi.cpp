@@ -471,7 +471,7 @@ static void axis_sums(scanrs_mat *m, int axis, int mode, double *d_sum, double *
     Storage &st = *m->st;
     CurrentHandle cur(&st);
     const bool outer_view_rows = axis == 1;
-    // From the copy whose outer vectors are the SUMMED-OVER axis when the map allows it (kernels.hip, col_moments_kernel: a
+    // From the copy whose outer vectors are the SUMMED-OVER axis when the map allows it (normalize_ops.hip, col_moments_kernel: a
     // per-outer table instead of one logarithm per nonzero) and that copy exists already; else the ordinary pass over the copy
     // whose outer vectors are the slices.
     bool done = false;

@@ -1,6 +1,6 @@
-// The plan of col_moments_kernel (kernels.hip) as plain host arithmetic: from the numbers the device hands back (the largest
+// The plan of col_moments_kernel (normalize_ops.hip) as plain host arithmetic: from the numbers the device hands back (the largest
 // count, per ScaleAxis link its smallest positive and its largest factor) to "take the fixed-point route or not" and the two
-// binary exponents of its quanta. kernels.hip calls it with what max_u32_kernel / minmax_nonneg_kernel found;
+// binary exponents of its quanta. normalize_ops.hip calls it with what max_u32_kernel / minmax_nonneg_kernel found;
 // scanrs_host_col_moments_plan exposes it to the CPU test-suite, which holds it to an exact emulation of the accumulation.
 //
 // The kernel adds rint(v 2^e1) (and rint(v^2 2^e2)) as 64-bit integers per inner position, so every term is off by at most

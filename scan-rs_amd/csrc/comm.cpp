@@ -141,7 +141,33 @@ struct scanrs_comm {
 
 namespace scanrs {
 
-void launch_local_allreduce(hipStream_t s, void *const *bufs, uint32_t world, uint32_t rank, uint64_t count, int dtype);
+// One-shot all-reduce of the single-process group: rank r sums slice r of every rank's buffer in rank order
+// and writes the sum back into every buffer. Peer buffers are reached through peer-mapped pointers (xGMI) or are on the
+// same device; the caller brackets the launch with group barriers.
+struct PeerTable {
+    void *p[16];
+};
+template <typename T>
+__global__ __launch_bounds__(256) void local_allreduce_kernel(PeerTable tab, uint32_t world, uint64_t lo, uint64_t hi) {
+    for (uint64_t e = lo + (uint64_t)blockIdx.x * blockDim.x + threadIdx.x; e < hi; e += (uint64_t)gridDim.x * blockDim.x) {
+        T acc = static_cast<const T *>(tab.p[0])[e];
+        for (uint32_t r = 1; r < world; r++) acc += static_cast<const T *>(tab.p[r])[e];
+        for (uint32_t r = 0; r < world; r++) static_cast<T *>(tab.p[r])[e] = acc;
+    }
+}
+static void launch_local_allreduce(hipStream_t s, void *const *bufs, uint32_t world, uint32_t rank, uint64_t count, int dtype) {
+    if (world > 16) fail(SCANRS_ERR_ARGUMENT, "single-process groups hold at most 16 shards");
+    PeerTable tab;
+    for (uint32_t r = 0; r < 16; r++) tab.p[r] = r < world ? bufs[r] : nullptr;
+    const uint64_t lo = count * rank / world, hi = count * (rank + 1) / world;
+    if (hi <= lo) return;
+    const unsigned blocks = (unsigned)std::min<uint64_t>(1024, (hi - lo + 255) / 256);
+    if (dtype == 0)
+        hipLaunchKernelGGL(local_allreduce_kernel<double>, dim3(blocks), dim3(256), 0, s, tab, world, lo, hi);
+    else
+        hipLaunchKernelGGL(local_allreduce_kernel<unsigned long long>, dim3(blocks), dim3(256), 0, s, tab, world, lo, hi);
+    SCANRS_HIP(hipGetLastError());
+}
 
 void comm_allreduce(Storage &st, scanrs_comm *c, void *d, uint64_t count, int dtype) {
     if (count == 0) return;

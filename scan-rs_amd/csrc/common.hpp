@@ -548,38 +548,50 @@ SCANRS_LOCAL inline void h2d(T *d, const T *h, size_t n, hipStream_t s) {
     if (n) SCANRS_HIP(hipMemcpyAsync(d, h, n * sizeof(T), hipMemcpyHostToDevice, s));
 }
 
-// ---- kernels.hip launchers ----------------------------------------------------------------
+// ---- kernels.hip: the sparse products and the per-outer-vector reductions ------------------
 // out[n_outer x l] = S * X (+ a * w) where S is `cp` seen through `map`.
 // off_a: n_outer x rank (row-major) or null; off_w: rank x l (ld = ldw).
 void launch_spmm_f64(Storage &st, SparseCopy &cp, const DevMap &map, const double *X, uint32_t ldx, uint32_t l,
                      double *out, uint32_t ldo, const double *off_a, uint32_t rank, const double *off_w, uint32_t ldw);
 void launch_spmm_u32(Storage &st, const SparseCopy &cp, const uint32_t *X, uint32_t ldx, uint32_t l, uint32_t *out,
                      uint32_t ldo);
-// tiles.hip (whether a product is a candidate for them at all: spmm_route.hpp)
+// per-outer-vector reductions. mode 0: sum of raw u32 counts; 1: sum of mapped values; 2: sum and sum of squares.
+void launch_row_reduce(Storage &st, SparseCopy &cp, const DevMap &map, int mode, uint32_t *out_u32, double *out_sum,
+                       double *out_sumsq);
+// cp.bounds: per outer vector the offsets of its nonzeros at multiples of 2^BT_SHIFT = 1024 inner positions (one base tile), built
+// on first use on stream `s` (null: the handle's); returns the number of base tiles
+constexpr uint32_t BT_SHIFT = 10;
+uint32_t ensure_bounds(Storage &st, SparseCopy &cp, hipStream_t s = nullptr);
+// fout[p] = the whole chain of `map` at nonzero p of `cp`
+void materialize_map_values(Storage &st, SparseCopy &cp, const DevMap &map, double *fout);
+// the overflow part of a tile layout through the L2-blocked gather on stream `s` (weights in ov.fvals, no map, no offset)
+void launch_gather2d_ov(Storage &st, hipStream_t s, SparseCopy &ov, const double *X, uint32_t ldx, uint32_t l, double *out, uint32_t ldo);
+void launch_scale_rows(Storage &st, const double *X, uint32_t ldx, uint64_t rows, uint32_t l, const double *a, double *Xs);
+// one empty launch per translation unit that the first create -> normalize -> run_pca reaches (library_warm_up)
+void warm_kernels(hipStream_t s);
+void warm_panel_ops(hipStream_t s);
+void warm_copy_build(hipStream_t s);
+void warm_normalize_ops(hipStream_t s);
+void warm_dense(hipStream_t s);
+void warm_decode(hipStream_t s);
+void warm_knn(hipStream_t s);
+void warm_tiles(hipStream_t s);
+
+// ---- tiles.hip (whether a product is a candidate for the tiles at all: spmm_route.hpp) ----------
 bool spmm_tiles_auto(Storage &st, SparseCopy &cp, const DevMap &map);
 // the structure of the layout (no weights) when the auto path would take it for this copy: built on stream s; false when the copy
 // is not eligible or its layout is not worth having (then remembered in cp.tile_rejected_shape)
 bool tile_layout_build_auto(Storage &st, SparseCopy &cp, hipStream_t s);
 void launch_spmm_tiles(Storage &st, SparseCopy &cp, const DevMap &map, const double *X, uint32_t ldx, uint32_t l, double *out,
                        uint32_t ldo, const double *off_a, uint32_t rank, const double *off_w, uint32_t ldw);
-// per-outer-vector reductions. mode 0: sum of raw u32 counts; 1: sum of mapped values; 2: sum and sum of squares.
-void launch_row_reduce(Storage &st, SparseCopy &cp, const DevMap &map, int mode, uint32_t *out_u32, double *out_sum,
-                       double *out_sumsq);
-// w[rank x l] (ld ldw) = B^T X, B: n x rank row-major, X: n x l (ld ldx)
-void launch_weighted_colsum(Storage &st, const double *B, uint32_t rank, const double *X, uint32_t ldx, uint64_t n,
-                            uint32_t l, double *w, uint32_t ldw, double *Xc = nullptr, uint32_t ldc = 0);
 // where the dense tile product of (cp, l) will stage its compact panel copy from — when the caller can fill it while it reads the
 // panel anyway (mat_apply: the column sums of the offset term) — or nullptr (another path, a layout about to be rebuilt, odd l)
 double *tile_panel_copy_target(Storage &st, SparseCopy &cp, uint32_t l);
-// C[n x m] (row-major, ld = m) = X^T Y over `rows` rows (f64 MFMA, slab + ordered reduce)
-void launch_gram(Storage &st, const double *X, uint32_t ldx, uint32_t n, const double *Y, uint32_t ldy, uint32_t m,
-                 uint64_t rows, double *C);
-// Out[rows x m] = beta * Cin + alpha * X[rows x n] * W[n x m]   (W device, row-major ld = ldw). Cin may equal Out.
-void launch_gemm_nn(Storage &st, const double *X, uint32_t ldx, uint32_t n, const double *W, uint32_t ldw, uint32_t m,
-                    uint64_t rows, double alpha, double beta, const double *Cin, uint32_t ldc, double *Out, uint32_t ldo);
-// Which kernel a dense product goes to, as pure host functions of the shape (dense.hip; the values are the SCANRS_DENSE_* constants of
-// scanrs_amd.h). launch_gram / launch_gemm_nn call them; the *_route launchers take a route (0: the dispatcher's) and refuse a forced
-// kernel whose own preconditions fail (tests: scanrs_debug_dense_*).
+
+// ---- dense.hip: the routes of the dense products, the LDS-tiled and skinny MFMA forms, the factor step --------
+// Which kernel a dense product goes to, as pure host functions of the shape (the values are the SCANRS_DENSE_* constants of
+// scanrs_amd.h). launch_gram / launch_gemm_nn (panel_ops.hip) call them; the *_route launchers take a route (0: the dispatcher's)
+// and refuse a forced kernel whose own preconditions fail (tests: scanrs_debug_dense_*).
 enum GramRoute { GRAM_AUTO = 0, GRAM_WAVE = 1, GRAM_VEC = 2, GRAM_TILED = 3 };
 enum GemmRoute { GEMM_AUTO = 0, GEMM_WAVE = 1, GEMM_TILED = 2, GEMM_SKINNY_LDS = 3, GEMM_DIRECT = 4 };
 struct GemmPlan {
@@ -591,11 +603,7 @@ inline uint32_t gemm_wave_nj(uint32_t m) { return m <= 16u ? 1u : m <= 32u ? 2u 
 // side: the product is queued on a side stream while dense_side_no_lds is set (register-only forms)
 GramRoute gram_route(uint32_t n, uint32_t m, uint64_t rows, uint32_t ldx, uint32_t ldy, bool side, bool skip_flag_set);
 GemmPlan gemm_route(bool x_aligned16, uint32_t ldx, uint32_t n, uint32_t m, uint64_t rows, bool side, bool gemm_direct);
-void launch_gram_route(Storage &st, int route, const double *X, uint32_t ldx, uint32_t n, const double *Y, uint32_t ldy, uint32_t m,
-                       uint64_t rows, double *C);
-void launch_gemm_route(Storage &st, int route, const double *X, uint32_t ldx, uint32_t n, const double *W, uint32_t ldw, uint32_t m,
-                       uint64_t rows, double alpha, double beta, const double *Cin, uint32_t ldc, double *Out, uint32_t ldo);
-// dense.hip: LDS-tiled MFMA versions for big panels
+// LDS-tiled MFMA versions for big panels
 bool gram_tiled_ok(uint32_t n, uint32_t m, uint64_t rows);
 bool gemm_tiled_ok(uint32_t n, uint32_t m, uint64_t rows);
 void launch_gram_tiled(Storage &st, const double *X, uint32_t ldx, uint32_t n, const double *Y, uint32_t ldy, uint32_t m,
@@ -607,6 +615,25 @@ void launch_gemm_tiled(Storage &st, const double *X, uint32_t ldx, uint32_t n, c
                        uint64_t rows, double alpha, double beta, const double *Cin, uint32_t ldc, double *Out, uint32_t ldo);
 void launch_gemm_skinny_lds(Storage &st, const double *X, uint32_t ldx, uint32_t n, const double *W, uint32_t ldw, uint32_t m,
                             uint64_t rows, double alpha, double beta, const double *Cin, uint32_t ldc, double *Out, uint32_t ldo);
+// the factor step of CholeskyQR on the device
+bool chol_rinv_ok(uint32_t n);
+void launch_chol_rinv(Storage &st, const double *G, uint32_t n, uint64_t rows, int pass, bool check_only, int *ctl, double *Rinv, double *info);
+void launch_absmax_flag(Storage &st, const double *C, uint32_t count, double limit, int *ctl, double *info);
+
+// ---- panel_ops.hip: dense panel utilities of the solvers ---------------------------------------------
+// w[rank x l] (ld ldw) = B^T X, B: n x rank row-major, X: n x l (ld ldx)
+void launch_weighted_colsum(Storage &st, const double *B, uint32_t rank, const double *X, uint32_t ldx, uint64_t n,
+                            uint32_t l, double *w, uint32_t ldw, double *Xc = nullptr, uint32_t ldc = 0);
+// C[n x m] (row-major, ld = m) = X^T Y over `rows` rows (f64 MFMA, slab + ordered reduce)
+void launch_gram(Storage &st, const double *X, uint32_t ldx, uint32_t n, const double *Y, uint32_t ldy, uint32_t m,
+                 uint64_t rows, double *C);
+// Out[rows x m] = beta * Cin + alpha * X[rows x n] * W[n x m]   (W device, row-major ld = ldw). Cin may equal Out.
+void launch_gemm_nn(Storage &st, const double *X, uint32_t ldx, uint32_t n, const double *W, uint32_t ldw, uint32_t m,
+                    uint64_t rows, double alpha, double beta, const double *Cin, uint32_t ldc, double *Out, uint32_t ldo);
+void launch_gram_route(Storage &st, int route, const double *X, uint32_t ldx, uint32_t n, const double *Y, uint32_t ldy, uint32_t m,
+                       uint64_t rows, double *C);
+void launch_gemm_route(Storage &st, int route, const double *X, uint32_t ldx, uint32_t n, const double *W, uint32_t ldw, uint32_t m,
+                       uint64_t rows, double alpha, double beta, const double *Cin, uint32_t ldc, double *Out, uint32_t ldo);
 void launch_col_scale_dev(Storage &st, double *dst, uint32_t ldd, const double *src, uint32_t lds, uint64_t rows, const double *nsq);
 void launch_col_axpy_dev(Storage &st, double *y, uint32_t ldy, const double *x, uint32_t ldx, uint64_t rows, const double *nsq);
 void launch_col_scale(Storage &st, double *dst, uint32_t ldd, const double *src, uint32_t lds, uint64_t rows, double alpha);
@@ -619,28 +646,31 @@ void launch_omega_jump(Storage &st, const uint64_t *d_jpow, int n_pow, const uin
 void launch_transpose(Storage &st, const double *src, uint64_t rows, uint64_t cols, double *dst, uint32_t ldd);
 void launch_permute_cols(Storage &st, const double *src, uint32_t lds, double *dst, uint32_t ldd, uint64_t rows,
                          const uint32_t *d_idx, uint32_t n_idx, bool scatter);
+
+// ---- normalize_ops.hip: the small kernels of normalize ------------------------------------------------
+// out_sum[i] (and out_sumsq[i]) over the outer vectors of cp, per INNER position i. false: not eligible (nothing was launched).
+bool launch_col_moments(Storage &st, SparseCopy &cp, const DevMap &map, int mode, double *out_sum, double *out_sumsq);
 void launch_finish_moments(Storage &st, const double *sum, const double *sumsq, uint64_t n, double m, int given_scale,
                            const double *scale_in, double *mean_over_scale_neg, double *inv_scale, double *scale_out);
 void launch_u32_to_scale(Storage &st, const uint32_t *counts, uint64_t n, double target, double *out);
 void launch_hist12(Storage &st, const uint32_t *v, uint64_t n, uint32_t shift, uint32_t digit_mask, uint32_t prefix_mask,
                    uint32_t prefix, unsigned long long *hist);
 void launch_sum_f64(Storage &st, const double *x, uint64_t n, double *out);
-void validate_copy(Storage &st, SparseCopy &cp, uint64_t *zeros, uint64_t *bad);
 void launch_densify(Storage &st, const SparseCopy &cp, const DevMap &map, bool outer_is_view_row, uint64_t cols_v,
                     double *out);
 void launch_binom_uv(Storage &st, int kind, const double *n, uint64_t ncols, const double *rowsum, uint64_t nrows,
                      double total, double *pi, double *u, double *v);
+
+// ---- copy_build.hip: construction of a SparseCopy (with SparseCopy::build_items) -----------------------
+void validate_copy(Storage &st, SparseCopy &cp, uint64_t *zeros, uint64_t *bad);
 // build `dst` = transpose of `src` (stable: inner vectors keep ascending outer order)
 void build_transposed_copy(Storage &st, const SparseCopy &src, SparseCopy &dst, hipStream_t stream = nullptr);
 // drop stored zeros, compact (device). Returns new nnz.
 void compact_nonzeros(Storage &st, SparseCopy &cp);
+void sort_outer_vectors(Storage &st, SparseCopy &cp);
 
 // ---- host_linalg.cpp --------------------------------------------------------------------------
 // Upper Cholesky G = R^T R of an n x n SPD matrix (row-major, in place: upper triangle = R). false if not SPD.
-bool launch_col_moments(Storage &st, SparseCopy &cp, const DevMap &map, int mode, double *out_sum, double *out_sumsq);
-bool chol_rinv_ok(uint32_t n);
-void launch_chol_rinv(Storage &st, const double *G, uint32_t n, uint64_t rows, int pass, bool check_only, int *ctl, double *Rinv, double *info);
-void launch_absmax_flag(Storage &st, const double *C, uint32_t count, double limit, int *ctl, double *info);
 bool chol_upper(double *g, int n);
 // in place inverse of an upper-triangular matrix
 void inv_upper(double *r, int n);
@@ -663,8 +693,6 @@ void jump_tables_prefetch(); // starts the background computation of the start p
 // out[rows_v x l] = V * X  (transpose: out[cols_v x l] = V^T * X), offsets and shard reduction included.
 void mat_apply(scanrs_mat *m, bool transpose, const double *dX, uint32_t ldx, uint32_t l, double *dOut, uint32_t ldo);
 void prepare_second_orientation(scanrs_mat *m, bool transpose_second, bool solver_follows = false);
-void sort_outer_vectors(Storage &st, SparseCopy &cp);
-void launch_scale_rows(Storage &st, const double *X, uint32_t ldx, uint64_t rows, uint32_t l, const double *a, double *Xs);
 // knn.hip
 void knn_host(const double *queries, uint64_t n_q, const double *points, uint64_t n_p, uint32_t d, uint32_t k, bool skip_same_index,
               uint32_t *out);

@@ -1,5 +1,5 @@
 // LDS-tiled tall-skinny dense kernels on v_mfma_f64_16x16x4_f64 (gfx950): the big-panel versions of
-// gram_kernel / gemm_nn_kernel in kernels.hip. They stand where the reference multiplies dense panels
+// gram_kernel / gemm_nn_kernel in panel_ops.hip. They stand where the reference multiplies dense panels
 // through ndarray `dot` -> BLAS (`T = Q^T A` Gram / `Q.dot(&U)`, scan-rs/src/dim_red/bk_svd.rs:134-142).
 //
 // Both compute C_tile(128 x 128) += sum_k A[k][i] * B[k][j] from two LDS images laid out [k][128 + pad]:
@@ -604,7 +604,7 @@ static void gemm_direct_plan(uint32_t m, uint32_t *nt, uint32_t *groups) {
     *nt = ((m + 15u) / 16u + *groups - 1u) / *groups;
 }
 
-// The dispatch of launch_gram (kernels.hip): one vector against a narrow panel streams (gram_vec_kernel; its reducer has no skip test,
+// The dispatch of launch_gram (panel_ops.hip): one vector against a narrow panel streams (gram_vec_kernel; its reducer has no skip test,
 // so not inside a queued orthonormalisation); big panels with even leading dimensions (16-byte pair loads) go through the LDS tiles
 // unless the product runs on a side stream beside the persistent tile kernel, which holds all of every CU's LDS; the rest one wave
 // per 32 x 32 tile.

@@ -1,4 +1,4 @@
-// Device-side pieces shared by the sparse kernels (kernels.hip, quad.hip): vector typedefs, the MatrixMap evaluation
+// Device-side pieces shared by the sparse kernels (kernels.hip, tiles.hip, normalize_ops.hip, subset.hip): vector typedefs, the MatrixMap evaluation
 // (the flattened ComposedMap chain of sqz/src/matrix_map.rs:189-192), wave helpers. gfx950 only.
 #pragma once
 #include "common.hpp"

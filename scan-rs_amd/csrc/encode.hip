@@ -29,6 +29,7 @@
 
 #include "adaptive_choose.hpp"
 #include "common.hpp"
+#include "launch_util.hpp"
 
 #include <rocprim/rocprim.hpp>
 
@@ -266,7 +267,6 @@ __global__ __launch_bounds__(256) void enc_fallback_kernel(const uint64_t *__res
 
 // A launch holds fewer than 2^32 threads: at most 2^24 - 1 blocks of 256 (34e9 stored entries, a 32 GB byte arena, a 16 GB word arena)
 constexpr uint64_t MAX_BLOCKS = 0xFFFFFFull;
-inline dim3 grid1(uint64_t n) { return dim3((unsigned)((n + 255u) / 256u)); }
 
 // in place on the stream, no wait: d[0 .. count) -> its exclusive prefix sums. tmp is shared by the scans of one call
 void scan_in_place(hipStream_t s, DevBuf<char> &tmp, unsigned long long *d, uint64_t count) {
@@ -310,7 +310,7 @@ void encode_adaptive_vectors(Storage &st, const SparseCopy &cp, int force_kind, 
         // arrays before it, a constant that drops out wherever P_w is used, which is always as a difference of two of its values
         scan_in_place(s, tmp, cnt.p, cnt.n);
     }
-    hipLaunchKernelGGL(enc_plan_kernel, grid1(no), dim3(256), 0, s, cp.indptr.p, no, cp.n_inner, n_chunks, cnt.p, part.p, force_kind, desc.p, bsz.p,
+    hipLaunchKernelGGL(enc_plan_kernel, grid1(no, 256), dim3(256), 0, s, cp.indptr.p, no, cp.n_inner, n_chunks, cnt.p, part.p, force_kind, desc.p, bsz.p,
                        wsz.p);
     SCANRS_HIP(hipGetLastError());
     scan_in_place(s, tmp, bsz.p, no + 1);
@@ -327,10 +327,10 @@ void encode_adaptive_vectors(Storage &st, const SparseCopy &cp, int force_kind, 
     if (st.prof.on) st.prof.begin(s, "encode_emit", (double)nnz * 8.0 + (double)n_bytes + (double)n_words * 4.0);
     const uint64_t *boff = reinterpret_cast<const uint64_t *>(bsz.p), *woff = reinterpret_cast<const uint64_t *>(wsz.p);
     if (n_bytes)
-        hipLaunchKernelGGL(enc_bytes_kernel, grid1(n_bytes / 8), dim3(256), 0, s, cp.indptr.p, cp.indices.p, cp.values.p, no, cp.n_inner, desc.p, boff,
+        hipLaunchKernelGGL(enc_bytes_kernel, grid1(n_bytes / 8, 256), dim3(256), 0, s, cp.indptr.p, cp.indices.p, cp.values.p, no, cp.n_inner, desc.p, boff,
                            n_bytes / 8, d_bytes.p);
     if (n_words) {
-        hipLaunchKernelGGL(enc_words_kernel, grid1(n_words), dim3(256), 0, s, cp.indptr.p, cp.indices.p, cp.values.p, no, cp.n_inner, desc.p, woff,
+        hipLaunchKernelGGL(enc_words_kernel, grid1(n_words, 256), dim3(256), 0, s, cp.indptr.p, cp.indices.p, cp.values.p, no, cp.n_inner, desc.p, woff,
                            n_words, d_words.p);
         if (n_chunks)
             hipLaunchKernelGGL(enc_fallback_kernel, dim3((unsigned)n_chunks), dim3(256), 0, s, cp.indptr.p, cp.indices.p, cp.values.p, no, nnz, n_chunks,

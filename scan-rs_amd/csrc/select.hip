@@ -16,6 +16,7 @@
 // A wave reads a vector in aligned 16-byte pieces per lane (4 indices, 4 counts): the walk starts at the vector's start rounded down
 // to a multiple of 4 and masks what lies outside [start, end) — every buffer of a copy has slack behind its end (DevBuf::SLACK).
 #include "common.hpp"
+#include "launch_util.hpp"
 
 #include <rocprim/rocprim.hpp>
 
@@ -24,7 +25,6 @@ namespace scanrs {
 namespace {
 constexpr int WAVES_PER_BLOCK = 4;
 inline dim3 wave_grid(uint64_t n_vec) { return dim3((unsigned)((n_vec + WAVES_PER_BLOCK - 1) / WAVES_PER_BLOCK)); }
-inline dim3 grid1(uint64_t n, uint32_t block) { return dim3((unsigned)((n + block - 1) / block)); }
 
 __device__ __forceinline__ unsigned long long wave_sum_u64(unsigned long long v) {
     for (int o = 32; o > 0; o >>= 1) v += __shfl_xor(v, o, 64);

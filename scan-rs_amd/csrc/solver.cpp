@@ -68,7 +68,7 @@ struct SmallRng {
     }
 };
 
-// ---- GF(2) jump tables for the device-side panel generator (kernels.hip, omega_jump_kernel) ---------------------
+// ---- GF(2) jump tables for the device-side panel generator (panel_ops.hip, omega_jump_kernel) ---------------------
 namespace {
 struct BitMat { // 256 x 256 over GF(2); row i = mask of the input bits that feed output bit i
     uint64_t r[256][4];

@@ -25,19 +25,14 @@
 #include "common.hpp"
 #include "device_map.hpp"
 #include "fixed128.hpp"
+#include "launch_util.hpp"
 
 namespace scanrs {
 
 namespace {
 constexpr uint32_t NOT_LISTED = 0xFFFFFFFFu;
-inline dim3 grid1(uint64_t n, uint32_t block) { return dim3((unsigned)((n + block - 1) / block)); }
 inline dim3 wave_grid(uint64_t n_waves) { return dim3((unsigned)((n_waves + 3) / 4)); }
 
-__device__ __forceinline__ double wave_sum(double v) {
-#pragma unroll
-    for (int off = 32; off > 0; off >>= 1) v += __shfl_xor(v, off, 64);
-    return v;
-}
 __device__ __forceinline__ unsigned long long wave_sum_u64(unsigned long long v) {
 #pragma unroll
     for (int off = 32; off > 0; off >>= 1) v += __shfl_xor(v, off, 64);

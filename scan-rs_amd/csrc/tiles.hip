@@ -902,9 +902,6 @@ void tile_layout_stats(const TileLayout *t, uint64_t out[3]) {
     }
 }
 
-uint32_t ensure_bounds_public(Storage &st, SparseCopy &cp, hipStream_t s); // kernels.hip
-void materialize_map_values(Storage &st, SparseCopy &cp, const DevMap &map, double *fout); // kernels.hip
-
 static TileLayout *dense_layout_build(Storage &st, const SparseCopy &cp, double max_overflow, hipStream_t s, std::unique_ptr<TileLayout> tl,
                                       const std::function<void(const char *)> &lap); // tiles_dense.inc
 // max_overflow > 0: give up (nullptr) when more than that share of the nonzeros would land in the overflow part — known after the
@@ -1114,7 +1111,7 @@ TileLayout *tile_layout_build(Storage &st, const SparseCopy &cp, double max_over
         SCANRS_SYNC(s);
         lap("overflow sort");
     }
-    if (n_ov) ensure_bounds_public(st, ov, s);
+    if (n_ov) ensure_bounds(st, ov, s);
     SCANRS_SYNC(s); // the temporaries are released on return
     lap("overflow bounds");
     if (trace_on())
@@ -1643,8 +1640,6 @@ bool spmm_tiles_auto(Storage &st, SparseCopy &cp, const DevMap &map) {
     st.t_layout_us += (uint64_t)std::chrono::duration<double, std::micro>(std::chrono::steady_clock::now() - t0).count();
     return ok;
 }
-
-void launch_gather2d_ov(Storage &st, hipStream_t s, SparseCopy &ov, const double *X, uint32_t ldx, uint32_t l, double *out, uint32_t ldo); // kernels.hip
 
 void launch_spmm_tiles(Storage &st, SparseCopy &cp, const DevMap &map, const double *X, uint32_t ldx, uint32_t l, double *out,
                        uint32_t ldo, const double *off_a, uint32_t rank, const double *off_w, uint32_t ldw) {

@@ -1,4 +1,4 @@
-"""Inputs, exact references and the case grid for the dense f64-MFMA kernels (scan-rs_amd/csrc/kernels.hip, dense.hip,
+"""Inputs, exact references and the case grid for the dense f64-MFMA kernels (scan-rs_amd/csrc/panel_ops.hip, dense.hip,
 dense_skinny.inc). tests/test_dense_ref_cpu.py checks this file and the dispatch on the host; tests/test_gpu_dense.py walks the
 same grid on the device.
 
@@ -39,7 +39,7 @@ def even_up(v):
     return (v + 1) & ~1
 
 
-# ---- the dispatch rules restated from the comments in dense.hip / kernels.hip ---------------------------------------------------
+# ---- the dispatch rules restated from the comments in dense.hip / panel_ops.hip -------------------------------------------------
 def expected_gram_route(n, m, rows, ldx, ldy, side=False, skip=False):
     if m == 1 and n <= 128 and rows >= 4096 and not skip:
         return GRAM_VEC

@@ -1,4 +1,4 @@
-"""Every dense f64-MFMA kernel on its own (scan-rs_amd/csrc/kernels.hip, dense.hip, dense_skinny.inc) through the test entry points
+"""Every dense f64-MFMA kernel on its own (scan-rs_amd/csrc/panel_ops.hip, dense.hip, dense_skinny.inc) through the test entry points
 scanrs_debug_dense_gram / _gemm / _weighted_colsum, over the grid of tests/dense_ref.py.
 
 Exact class: integer inputs, every partial sum an integer below 2**53, so the result is bit-identical to the int64 reference whatever

@@ -1,5 +1,5 @@
 """The plan of the fixed-point column moments (scanrs_host_col_moments_plan; scan-rs_amd/csrc/col_moments_plan.hpp, the source
-kernels.hip decides by) against an exact emulation of the accumulation (tests/moments_ref.py). No device.
+normalize_ops.hip decides by) against an exact emulation of the accumulation (tests/moments_ref.py). No device.
 
 The contract, for every slice and without an absolute term: |sum - S1| <= 1e-12 S1, the same for the mean, and
 |var - var_ref| <= 1e-10 S2/m; a slice without nonzeros gives exactly 0 and 0."""
