@@ -1318,6 +1318,53 @@ int scanrs_multi_knn(scanrs_multi *mm, const double *points, uint32_t ld, uint32
 int scanrs_host_knn_merge(uint32_t k, const double *da, const uint32_t *ia, const double *db, const uint32_t *ib, double *dout,
                           uint32_t *iout);
 
+/* ---- nearest_neighbors under Euclidean, Pearson and cosine distance (umap-rs/src/knn.rs, dist.rs) -------------------
+ * umap_rs::knn::nearest_neighbors(data, k, distance_type, num_threads) -> (knn_indices, knn_distances): the pair every embedding
+ * stage downstream starts from (umap.rs:89). data: n x d row-major f64. `enum DistanceType` (dist.rs:12-35): */
+enum { SCANRS_DIST_EUCLIDEAN = 0, SCANRS_DIST_PEARSON = 1, SCANRS_DIST_COSINE = 2 };
+/* The value of a pair under pearson and cosine is the reference's own formula, every operation a separate IEEE f64 operation in
+ * coordinate order, nothing fused (dist.rs:73-84, 106-124): cosine folds s_xx, s_yy, s_xy over x and y; pearson first subtracts
+ * mu = fold(acc + x_j) / d from each row; then D = 0 if s_xx == 0 && s_yy == 0, else 1 if s_xy == 0, else
+ * max(1 - s_xy / sqrt(s_xx s_yy), 0) with f64::max (a NaN operand loses: 0). The search orders by key = sqrt(D) and returns
+ * key * key (metric / metric2dist, dist.rs:19-34) - generally not the bits of D. Ties, including the ones sqrt creates, come in
+ * ascending index order, the rule of scanrs_knn (the vp-tree's order among equal keys is a property of that crate). The answer is
+ * reproducible bit for bit: the device search equals scanrs_host_nearest_neighbors in indices and distance bit patterns.
+ * DEVIATION, euclidean only: the reference calls simd_euclidean::Vectorized::distance (dist.rs:86-89), whose summation order is
+ * not in the reference tree. This kind is the library's existing search: ordered by (squared distance as scanrs_knn forms it - one
+ * fma chain in coordinate order -, index), the returned distance the square root of that: a few ulp from the reference's value.
+ * A row is never its own neighbour (knn.rs:155). k_eff = min(k, n - 1) (knn.rs:124-127): the C entry points write n x k and pad
+ * columns k_eff .. k-1 with UINT32_MAX / +inf (the reference's initial fill, knn.rs:139-140; the padding rule of scanrs_knn).
+ * Limits of scanrs_knn: k <= 128, d <= 128, n <= 2^32 - 2. A coordinate that is not finite is refused with SCANRS_ERR_ARGUMENT,
+ * naming the first such row (with a NaN the order is not total). n < 2 or k == 0: nothing beyond padding is written, success.
+ * Routes (pearson, cosine): an exhaustive kernel for every shape, and - from "knn_filter_min_points" points on, d <= 58, k <= 64,
+ * at least 256 rows, no degenerate row (s_xx == 0), every s_xx inside [2^-400, 2^400] - the bf16-MFMA filter of scanrs_knn on the
+ * standardised rows with a threshold converted rigorously from the query's k-th key, every pair that passes ranked by the
+ * reference formula. Options "knn_exhaustive", "knn_filter_min_points", "knn_ratio", "knn_stats" apply;
+ * scanrs_debug_knn_last_stats tells which route the last call took.
+ * NOT provided: the sharded / multi-GPU form, a query set distinct from the point set, and everything after the neighbour lists
+ * (fuzzy graph, layout).
+ * scanrs_nearest_neighbors (knn.rs:112-166): data, indices, distances are host arrays.
+ * scanrs_nearest_neighbors_device (knn.rs:112-166): the points are already in device memory (n x d, leading dimension ld >= d
+ * elements; what lies behind column d is never read), e.g. *d_v / *ld_v of scanrs_pca_result_device; indices / distances host.
+ * scanrs_host_nearest_neighbors (knn.rs:112-166; host only): the same answer by exhaustive search on the host (any k).
+ * scanrs_host_distance (dist.rs:19-34, 73-124; host only): one pair: *key = the rank key (sqrt(D); euclidean: the distance),
+ * *dist = metric2dist(key) (key * key; euclidean: key).
+ * scanrs_host_metric_rows (dist.rs:73-76, 106-115; host only): what the search forms once per row, exactly as the device forms
+ * it: c (n x d) the centred row (pearson) or the row (cosine), s (n) its s_xx, z (n x d, may be null) = c / sqrt(s_xx), the
+ * standardised row only the filter reads (all zero for a degenerate row). distance_type 1 or 2.
+ * scanrs_debug_nearest_neighbors_params (host only; the filtered route's constants): the filter's threshold in the
+ * space of the standardised rows is tau = 2 key_k^2 (1 + *delta) + *e, of which *chain is the allowance for the filter's own
+ * fma chain; [*sxx_min, *sxx_max] is the magnitude window of s_xx outside which the filter declines. */
+int scanrs_nearest_neighbors(const double *data, uint64_t n, uint32_t d, uint32_t k, int distance_type, uint32_t *indices,
+                             double *distances);
+int scanrs_nearest_neighbors_device(const double *d_data, uint64_t n, uint32_t ld, uint32_t d, uint32_t k, int distance_type,
+                                    uint32_t *indices, double *distances);
+int scanrs_host_nearest_neighbors(const double *data, uint64_t n, uint32_t d, uint32_t k, int distance_type, uint32_t *indices,
+                                  double *distances);
+int scanrs_host_distance(int distance_type, const double *x, const double *y, uint32_t d, double *key, double *dist);
+int scanrs_host_metric_rows(int distance_type, const double *data, uint64_t n, uint32_t d, double *c, double *s, double *z);
+int scanrs_debug_nearest_neighbors_params(double *delta, double *e, double *chain, double *sxx_min, double *sxx_max);
+
 /* ---- the plan of the fixed-point column moments (option "col_moments"; host only, no device) -----------------------------------
  * The route adds, per slice, the terms f of the map as 64-bit integers rint(f 2^e1) (and rint(f^2 2^e2)): one quantum q = 2^-e for
  * the whole matrix, so every term is off by at most q/2 ABSOLUTE. The plan decides from global numbers whether that is good enough

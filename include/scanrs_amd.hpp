@@ -1292,6 +1292,55 @@ inline KnnResult knn(const MultiMat &m, uint64_t cells, const double *points, ui
 inline void host_knn_merge(uint32_t k, const double *da, const uint32_t *ia, const double *db, const uint32_t *ib, double *dout, uint32_t *iout) {
     check(scanrs_host_knn_merge(k, da, ia, db, ib, dout, iout));
 }
+// umap_rs::knn::nearest_neighbors (umap-rs/src/knn.rs:112-166) under `DistanceType` (dist.rs:12-35): indices and distances of the k
+// nearest other rows, n x min(k, n - 1) each as the reference returns them (the euclidean kind is the library's search)
+enum class DistanceType : int { Euclidean = SCANRS_DIST_EUCLIDEAN, Pearson = SCANRS_DIST_PEARSON, Cosine = SCANRS_DIST_COSINE };
+struct NearestNeighbors {
+    size_t k = 0;                  // min(k, n - 1)
+    std::vector<uint32_t> indices; // n x k, nearest first
+    std::vector<double> distances; // n x k
+};
+namespace detail {
+template <typename F>
+inline NearestNeighbors nearest_neighbors_call(size_t n, size_t k, F &&call) {
+    std::vector<uint32_t> idx(n * k);
+    std::vector<double> dist(n * k);
+    check(call(idx.data(), dist.data()));
+    NearestNeighbors r;
+    r.k = n ? (k < n - 1 ? k : n - 1) : 0;
+    r.indices.resize(n * r.k);
+    r.distances.resize(n * r.k);
+    for (size_t i = 0; i < n; i++)
+        for (size_t j = 0; j < r.k; j++) r.indices[i * r.k + j] = idx[i * k + j], r.distances[i * r.k + j] = dist[i * k + j];
+    return r;
+}
+} // namespace detail
+inline NearestNeighbors nearest_neighbors(const Array2 &data, size_t k, DistanceType distance_type) {
+    return detail::nearest_neighbors_call(data.rows, k, [&](uint32_t *i, double *d) {
+        return scanrs_nearest_neighbors(data.data.data(), data.rows, (uint32_t)data.cols, (uint32_t)k, (int)distance_type, i, d);
+    });
+}
+// on points that are already in device memory (e.g. PcaResultDevice d_v / ld_v)
+inline NearestNeighbors nearest_neighbors_device(const double *d_data, size_t n, uint32_t ld, uint32_t d, size_t k, DistanceType distance_type) {
+    return detail::nearest_neighbors_call(n, k, [&](uint32_t *i, double *dd) {
+        return scanrs_nearest_neighbors_device(d_data, n, ld, d, (uint32_t)k, (int)distance_type, i, dd);
+    });
+}
+// the host twin: the same answer by exhaustive search on the host, and the pieces the tests of the filtered route read
+inline NearestNeighbors host_nearest_neighbors(const Array2 &data, size_t k, DistanceType distance_type) {
+    return detail::nearest_neighbors_call(data.rows, k, [&](uint32_t *i, double *d) {
+        return scanrs_host_nearest_neighbors(data.data.data(), data.rows, (uint32_t)data.cols, (uint32_t)k, (int)distance_type, i, d);
+    });
+}
+inline void host_distance(DistanceType distance_type, const double *x, const double *y, uint32_t d, double *key, double *dist) {
+    check(scanrs_host_distance((int)distance_type, x, y, d, key, dist));
+}
+inline void host_metric_rows(DistanceType distance_type, const double *data, uint64_t n, uint32_t d, double *c, double *s, double *z) {
+    check(scanrs_host_metric_rows((int)distance_type, data, n, d, c, s, z));
+}
+inline void debug_nearest_neighbors_params(double *delta, double *e, double *chain, double *sxx_min, double *sxx_max) {
+    check(scanrs_debug_nearest_neighbors_params(delta, e, chain, sxx_min, sxx_max));
+}
 // the plan of the fixed-point column moments (option "col_moments") on the host: accepted or not, and the two exponents
 struct ColMomentsPlan {
     bool accept = false;

@@ -1695,6 +1695,83 @@ def knn_device(d_points: int, n: int, ld: int, d: int, k: int):
     return out
 
 
+DISTANCE_TYPES = {"euclidean": 0, "pearson": 1, "cosine": 2}  # `DistanceType` (umap-rs/src/dist.rs:12-35): SCANRS_DIST_*
+
+
+def _distance_type(distance) -> int:
+    if isinstance(distance, str):
+        if distance not in DISTANCE_TYPES:
+            raise ScanrsError(6, f"unknown distance {distance!r}: one of {sorted(DISTANCE_TYPES)}")
+        return DISTANCE_TYPES[distance]
+    return int(distance)
+
+
+def _nearest_neighbors_call(fn, n: int, k: int, *head):
+    """The C entry points write n x k, padded from column min(k, n - 1) on; the reference returns that width (knn.rs:124-127)."""
+    idx = np.full((n, k), 0xFFFFFFFF, dtype=np.uint32)
+    dist = np.full((n, k), np.inf, dtype=np.float64)
+    _check(fn(*head, _p(idx), _p(dist)))
+    k_eff = min(k, max(n - 1, 0))
+    return np.ascontiguousarray(idx[:, :k_eff]), np.ascontiguousarray(dist[:, :k_eff])
+
+
+def nearest_neighbors(data, k: int, distance="euclidean"):
+    """`umap_rs::knn::nearest_neighbors(data, k, distance_type, ..)` (umap-rs/src/knn.rs:112-166) on the device: (indices u32,
+    distances f64), each n x min(k, n - 1), nearest first, under "euclidean", "pearson" or "cosine" distance (dist.rs:12-35, 69-124).
+    pearson / cosine: the reference's formula bit for bit, ordered by (sqrt(D), index), distance = sqrt(D)^2; euclidean: the search of
+    `knn` with the square root of its squared distance. Equal to `host_nearest_neighbors` in every bit."""
+    data = _f64(np.atleast_2d(data))
+    n, d = data.shape
+    return _nearest_neighbors_call(_lib.scanrs_nearest_neighbors, n, int(k), _p(data), ctypes.c_uint64(n), ctypes.c_uint32(d), ctypes.c_uint32(k),
+                                   ctypes.c_int(_distance_type(distance)))
+
+
+def nearest_neighbors_device(d_data: int, n: int, ld: int, d: int, k: int, distance="euclidean"):
+    """`nearest_neighbors` on points that already live in device memory (n x d, leading dimension ld >= d), e.g.
+    PcaResultDevice.d_v / ld_v (`scanrs_nearest_neighbors_device`, knn.rs:112-166): host arrays (indices, distances)."""
+    return _nearest_neighbors_call(_lib.scanrs_nearest_neighbors_device, int(n), int(k), ctypes.c_void_p(d_data), ctypes.c_uint64(n), ctypes.c_uint32(ld),
+                                   ctypes.c_uint32(d), ctypes.c_uint32(k), ctypes.c_int(_distance_type(distance)))
+
+
+def host_nearest_neighbors(data, k: int, distance="euclidean"):
+    """The host twin of `nearest_neighbors` (`scanrs_host_nearest_neighbors`, knn.rs:112-166; no device): exhaustive search."""
+    data = _f64(np.atleast_2d(data))
+    n, d = data.shape
+    return _nearest_neighbors_call(_lib.scanrs_host_nearest_neighbors, n, int(k), _p(data), ctypes.c_uint64(n), ctypes.c_uint32(d), ctypes.c_uint32(k),
+                                   ctypes.c_int(_distance_type(distance)))
+
+
+def host_distance(distance, x, y):
+    """One pair (`scanrs_host_distance`, dist.rs:19-34, 73-124; no device): (key, dist) = (the rank key sqrt(D), key * key); euclidean:
+    both are the distance."""
+    x, y = _f64(np.ravel(x)), _f64(np.ravel(y))
+    if x.shape != y.shape:
+        raise ScanrsError(1, "Dimension mismatch")
+    key, dist = ctypes.c_double(), ctypes.c_double()
+    _check(_lib.scanrs_host_distance(ctypes.c_int(_distance_type(distance)), _p(x), _p(y), ctypes.c_uint32(x.shape[0]), ctypes.byref(key),
+                                     ctypes.byref(dist)))
+    return key.value, dist.value
+
+
+def host_metric_rows(distance, data):
+    """What the search forms once per row, exactly as the device forms it (`scanrs_host_metric_rows`, dist.rs:73-76, 106-115; no device):
+    (c, s, z) = the centred rows (pearson) or the rows (cosine), their s_xx, and the standardised rows c / sqrt(s_xx) the filter reads."""
+    data = _f64(np.atleast_2d(data))
+    n, d = data.shape
+    c, s, z = np.zeros((n, d)), np.zeros(n), np.zeros((n, d))
+    _check(_lib.scanrs_host_metric_rows(ctypes.c_int(_distance_type(distance)), _p(data), ctypes.c_uint64(n), ctypes.c_uint32(d), _p(c), _p(s), _p(z)))
+    return c, s, z
+
+
+def debug_nearest_neighbors_params() -> dict:
+    """The constants of the filtered route of `nearest_neighbors` (`scanrs_debug_nearest_neighbors_params`, host only): the filter's
+    threshold on the standardised rows is 2 key_k^2 (1 + delta) + e, of which `chain` allows for the filter's own fma chain; the filter
+    declines outside sxx_min <= s_xx <= sxx_max."""
+    v = [ctypes.c_double() for _ in range(5)]
+    _check(_lib.scanrs_debug_nearest_neighbors_params(*[ctypes.byref(x) for x in v]))
+    return dict(zip(("delta", "e", "chain", "sxx_min", "sxx_max"), (x.value for x in v)))
+
+
 class RandSvd:
     """`RandSvd` (dim_red/rand_svd.rs:13-50)."""
 
@@ -1859,6 +1936,8 @@ EXPORTED_SYMBOLS = [
     "scanrs_hclust_create", "scanrs_hclust_create_device", "scanrs_hclust_from_steps", "scanrs_hclust_free", "scanrs_hclust_n", "scanrs_hclust_steps",
     "scanrs_hclust_leaves", "scanrs_hclust_merge_below", "scanrs_hclust_fcluster", "scanrs_hclust_info", "scanrs_host_hclust_linkage",
     "scanrs_debug_hclust_pdist",
+    "scanrs_nearest_neighbors", "scanrs_nearest_neighbors_device", "scanrs_host_nearest_neighbors", "scanrs_host_distance", "scanrs_host_metric_rows",
+    "scanrs_debug_nearest_neighbors_params",
     "scanrs_mat_select_rows", "scanrs_mat_select_cols", "scanrs_mat_partition_on_thresholds", "scanrs_mat_to_csmat",
     "scanrs_mat_select_rows_sharded", "scanrs_mat_select_cols_sharded", "scanrs_mat_partition_on_thresholds_sharded", "scanrs_mat_shard_info",
     "scanrs_multi_shape", "scanrs_multi_to_csmat", "scanrs_multi_select_rows", "scanrs_multi_select_cols", "scanrs_multi_partition_on_thresholds",

@@ -8,6 +8,7 @@
 #include "common.hpp"
 #include "col_moments_plan.hpp"
 #include "bk_plan.hpp"
+#include "knn_metric.hpp"
 #include "spmm_route.hpp"
 #include "shard_exchange.hpp"
 
@@ -1185,6 +1186,56 @@ int scanrs_host_knn_merge(uint32_t k, const double *da, const uint32_t *ia, cons
         if (k && (!da || !ia || !db || !ib || !dout || !iout)) fail(SCANRS_ERR_ARGUMENT, "null argument");
         if (k > 128) fail(SCANRS_ERR_ARGUMENT, "knn: k must not exceed 128");
         knn_host_merge(k, da, ia, db, ib, dout, iout);
+    });
+}
+// ---- nearest_neighbors under Euclidean, Pearson and cosine distance (umap-rs/src/knn.rs:112-166, dist.rs) -----------------------
+int scanrs_nearest_neighbors(const double *data, uint64_t n, uint32_t d, uint32_t k, int distance_type, uint32_t *indices, double *distances) {
+    return guard([&] {
+        if ((!data && n) || ((!indices || !distances) && n && k)) fail(SCANRS_ERR_ARGUMENT, "null argument");
+        nearest_neighbors_check_args(n, d, d, k, distance_type);
+        if (k == 0 || n == 0) return;
+        need_device();
+        DevBuf<double> dp(n * d);
+        SCANRS_HIP(hipMemcpy(dp.p, data, n * d * 8, hipMemcpyHostToDevice));
+        nearest_neighbors_device(dp.p, n, d, d, k, distance_type, indices, distances);
+    });
+}
+int scanrs_nearest_neighbors_device(const double *d_data, uint64_t n, uint32_t ld, uint32_t d, uint32_t k, int distance_type, uint32_t *indices,
+                                    double *distances) {
+    return guard([&] {
+        if ((!d_data && n) || ((!indices || !distances) && n && k)) fail(SCANRS_ERR_ARGUMENT, "null argument");
+        nearest_neighbors_check_args(n, ld, d, k, distance_type);
+        if (k == 0 || n == 0) return;
+        need_device();
+        nearest_neighbors_device(d_data, n, ld, d, k, distance_type, indices, distances);
+    });
+}
+int scanrs_host_nearest_neighbors(const double *data, uint64_t n, uint32_t d, uint32_t k, int distance_type, uint32_t *indices, double *distances) {
+    return guard([&] {
+        if ((!data && n) || ((!indices || !distances) && n && k)) fail(SCANRS_ERR_ARGUMENT, "null argument");
+        host_nearest_neighbors(data, n, d, k, distance_type, indices, distances);
+    });
+}
+int scanrs_host_distance(int distance_type, const double *x, const double *y, uint32_t d, double *key, double *dist) {
+    return guard([&] {
+        if (!x || !y || !key || !dist) fail(SCANRS_ERR_ARGUMENT, "null argument");
+        nearest_neighbors_check_args(2, d, d, 1, distance_type);
+        host_distance(distance_type, x, y, d, key, dist);
+    });
+}
+int scanrs_host_metric_rows(int distance_type, const double *data, uint64_t n, uint32_t d, double *c, double *s, double *z) {
+    return guard([&] {
+        if (n && (!data || !c || !s)) fail(SCANRS_ERR_ARGUMENT, "null argument");
+        nearest_neighbors_check_args(n, d, d, 1, distance_type);
+        if (distance_type == knn_metric::EUCLIDEAN) fail(SCANRS_ERR_ARGUMENT, "metric_rows: pearson (1) or cosine (2)");
+        host_metric_rows(distance_type, data, n, d, c, s, z);
+    });
+}
+int scanrs_debug_nearest_neighbors_params(double *delta, double *e, double *chain, double *sxx_min, double *sxx_max) {
+    return guard([&] {
+        if (!delta || !e || !chain || !sxx_min || !sxx_max) fail(SCANRS_ERR_ARGUMENT, "null argument");
+        *delta = knn_metric::KM_DELTA, *e = knn_metric::KM_E, *chain = knn_metric::KM_CHAIN;
+        *sxx_min = knn_metric::KM_SXX_MIN, *sxx_max = knn_metric::KM_SXX_MAX;
     });
 }
 int scanrs_host_col_moments_plan(uint32_t max_count, uint32_t n_links, const int *kinds, const int *on_summed_axis, const double *fmin_pos,

@@ -575,6 +575,7 @@ void warm_normalize_ops(hipStream_t s);
 void warm_dense(hipStream_t s);
 void warm_decode(hipStream_t s);
 void warm_knn(hipStream_t s);
+void warm_knn_metric(hipStream_t s);
 void warm_tiles(hipStream_t s);
 
 // ---- tiles.hip (whether a product is a candidate for the tiles at all: spmm_route.hpp) ----------

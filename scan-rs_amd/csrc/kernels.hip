@@ -1584,6 +1584,7 @@ void library_warm_up() {
     warm_dense(s);
     warm_decode(s);
     warm_knn(s);
+    warm_knn_metric(s);
     warm_tiles(s);
     const hipError_t e = hipGetLastError();
     SCANRS_SYNC(s);

@@ -26,14 +26,13 @@
 #include <vector>
 
 #include "common.hpp"
+#include "knn_filter.hpp"
 #include "knn_merge.hpp"
 #include "shard_exchange.hpp"
 
 namespace scanrs {
 
 namespace {
-
-constexpr uint32_t KMAX = 128;
 
 template <int DMAX, int THREADS>
 __global__ __launch_bounds__(THREADS) void knn_kernel(const double *__restrict__ queries, uint64_t n_q, const double *__restrict__ points,
@@ -175,15 +174,7 @@ void exhaustive(hipStream_t s, const double *dq, uint32_t ldq, uint64_t n_q, con
 // candidate list. tau_q comes from exact searches on nested strided subsets (every 256th point exhaustively, then every
 // 16th and finally all points through the filter): a round passes about k * 16 * (volume inflation of the margin)
 // candidates per query, which the rerank kernel evaluates exactly. A query whose list overflows is redone exhaustively.
-constexpr uint32_t KF_DP = 64;     // operand row: 58 coordinates + 6 augmentation slots
-constexpr uint32_t KF_DMAX = 58;
-constexpr uint32_t KF_CAP = 1024;  // candidates per query and round
-constexpr uint32_t KF_KMAX = 64;   // largest k and smallest query count the filter takes
-constexpr uint64_t KF_NQ_MIN = 256;
-constexpr double KF_GAMMA = 0.00395;
-constexpr double KF_COORD_MIN = 0x1p-48, KF_COORD_MAX = 0x1p46; // the magnitude window of max |coordinate|
-constexpr float KF_SENTINEL = 1e30f; // N of a sentinel point row, -A of a sentinel query row
-constexpr double KF_A_PASS = 9e29;   // A of "everything passes": above every legitimate A, below the sentinel
+// (the constants KF_*, the operands and the statistics of a filtered search: knn_filter.hpp, shared with knn_metric.hip)
 
 typedef __bf16 bf16x8 __attribute__((ext_vector_type(8)));
 typedef float f32x16 __attribute__((ext_vector_type(16)));
@@ -381,7 +372,6 @@ __global__ __launch_bounds__(256, 2) void kf_filter_kernel(const uint16_t *__res
 // exact f64 ranking of a query's candidates: one wave per query, a candidate per lane (the same fma chain over the coordinates as
 // knn_kernel), then k rounds of a wave-wide lexicographic (distance, index) minimum. Writes the k neighbours (UINT32_MAX padded)
 // and tau = the k-th distance (+inf when fewer than k exist). Overflowed lists (cnt > KF_CAP) are left to the exhaustive kernel.
-constexpr uint32_t KF_PER_LANE = KF_CAP / 64u;
 __global__ __launch_bounds__(256) void kf_rerank_kernel(const double *__restrict__ Q, uint32_t ldq, uint64_t n_q, const double *__restrict__ P,
                                                         uint32_t ldp, uint32_t d, uint32_t k, int skip_same_index, uint64_t p_off,
                                                         uint64_t q_off, const uint32_t *__restrict__ cand, const uint32_t *__restrict__ cnt,
@@ -477,16 +467,6 @@ __global__ void kf_tau0_kernel(const double *__restrict__ Q, uint32_t ldq, uint6
     tau[q] = s;
 }
 
-// round 0: every query's candidate list = the whole coarsest subset (rows 0, stride, 2 stride, ...), ranked exactly by kf_rerank_kernel
-__global__ void kf_fill_all_kernel(uint64_t n_q, uint32_t n_sub, uint64_t stride, uint32_t *__restrict__ cand, uint32_t *__restrict__ cnt) {
-    const uint64_t e = (uint64_t)blockIdx.x * blockDim.x + threadIdx.x;
-    if (e >= n_q * n_sub) return;
-    const uint64_t q = e / n_sub;
-    const uint32_t j = (uint32_t)(e % n_sub);
-    cand[q * KF_CAP + j] = (uint32_t)(j * stride);
-    if (j == 0) cnt[q] = n_sub;
-}
-
 __global__ void kf_gather_rows_kernel(const double *__restrict__ src, uint32_t ld, uint32_t d, const uint32_t *__restrict__ rows, uint64_t n,
                                       double *__restrict__ dst) {
     const uint64_t e = (uint64_t)blockIdx.x * blockDim.x + threadIdx.x;
@@ -508,33 +488,10 @@ __global__ void kf_seed_kernel(double *__restrict__ tau, const double *__restric
     tau[q] = fmin(tau[q], seed[q * seed_ld]);
 }
 
-// what the last scanrs_knn* / scanrs_find_nn call of the process did (scanrs_debug_knn_last_stats)
-struct KfRound {
-    uint64_t stride, points, cand_sum;
-    uint32_t cand_max, overflowed;
-};
-struct KnnLastStats {
-    bool filtered = false;
-    uint64_t first_stride = 0; // stride of the subset that round 0 ranks exactly
-    std::vector<KfRound> rounds;
-};
+// what the last scanrs_knn* / scanrs_find_nn / scanrs_nearest_neighbors* call of the process did (KnnLastStats, knn_filter.hpp)
 std::mutex g_stats_mutex;
 KnnLastStats g_last_stats;
 
-// the bf16 operands of one filtered search
-// the query side: prepared with the points for one search, or once for all the blocks a sharded search passes by (kf_prepare_queries)
-struct KfQueries {
-    DevBuf<uint16_t> Qb;
-    DevBuf<double> qn;
-    uint64_t nq_rows = 0;
-    double maxabs = 0.0; // max |coordinate| of the queries (NaN: one of them is not finite)
-};
-struct KfOperands {
-    KfQueries own;
-    const KfQueries *q = nullptr; // &own, or the caller's
-    DevBuf<uint16_t> Pb;
-    double slack = 0.0; // absolute part of the margin, 2^-117 (M + 1)
-};
 // max |coordinate| of up to two matrices in one pass and one wait; NaN when a coordinate is not finite
 double kf_maxabs(hipStream_t s, const double *a, uint32_t lda, uint64_t na, const double *b, uint32_t ldb, uint64_t nb, uint32_t d) {
     DevBuf<unsigned long long> mx(1);
@@ -562,10 +519,12 @@ void kf_prepare_queries(hipStream_t s, const double *dq, uint32_t ldq, uint64_t 
     qs.maxabs = kf_maxabs(s, dq, ldq, n_q, nullptr, 0, 0, d);
     if (qs.maxabs <= KF_COORD_MAX) kf_launch_prep_queries(s, dq, ldq, n_q, d, qs); // (false for NaN: nothing is prepared, no block is filtered)
 }
+} // namespace
+
 // false: a coordinate is not finite or max |coordinate| lies outside the magnitude window; nothing has been prepared.
 // shared: the query side prepared earlier by kf_prepare_queries (nullptr: it is prepared here)
 bool kf_prepare(hipStream_t s, const double *dq, uint32_t ldq, uint64_t n_q, const double *dp, uint32_t ldp, uint64_t n_p, uint32_t d,
-                KfOperands &op, const KfQueries *shared = nullptr) {
+                KfOperands &op, const KfQueries *shared) {
     const bool own_queries = !shared && (dq != dp || ldq != ldp || n_q > n_p);
     double m = kf_maxabs(s, dp, ldp, n_p, dq, ldq, own_queries ? n_q : 0, d);
     if (shared) m = shared->maxabs > m ? shared->maxabs : (shared->maxabs == shared->maxabs ? m : NAN);
@@ -614,6 +573,8 @@ void kf_d2d(hipStream_t s, void *dst, const void *src, size_t bytes) {
     else
         SCANRS_HIP(hipMemcpyAsync(dst, src, bytes, hipMemcpyDeviceToDevice, s));
 }
+
+namespace {
 
 // where a search stands in a larger one (all defaults: the points are the whole set and the queries its rows, as in scanrs_knn)
 struct KnnPlace {
@@ -793,28 +754,45 @@ void knn_filter_debug(const double *queries, uint64_t n_q, const double *points,
     SCANRS_HIP(hipMemcpy(cand, dcand.p, n_q * KF_CAP * 4, hipMemcpyDeviceToHost));
 }
 
-void knn_device(const double *d_queries, uint32_t ld_q, uint64_t n_q, const double *d_points, uint32_t ld_p, uint64_t n_p, uint32_t d,
-                uint32_t k, bool skip_same_index, uint32_t *out, double *sq_dist) {
-    if (k == 0 || n_q == 0) return;
+void knn_publish_stats(KnnLastStats &&stats) {
+    std::lock_guard<std::mutex> lock(g_stats_mutex);
+    g_last_stats = std::move(stats);
+}
+
+namespace {
+void knn_check_args(uint32_t ld_q, uint32_t ld_p, uint64_t n_p, uint32_t d, uint32_t k) {
     if (k > KMAX) fail(SCANRS_ERR_ARGUMENT, "knn: k must not exceed 128");
     if (d == 0 || d > 128) fail(SCANRS_ERR_ARGUMENT, "knn: 1 <= dimensions <= 128");
     if (ld_q < d || ld_p < d) fail(SCANRS_ERR_ARGUMENT, "knn: leading dimension smaller than the number of coordinates");
     if (n_p > 0xFFFFFFFEull) fail(SCANRS_ERR_SHAPE, "knn: too many points for u32 indices");
+}
+} // namespace
+
+void knn_device_into(const double *d_queries, uint32_t ld_q, uint64_t n_q, const double *d_points, uint32_t ld_p, uint64_t n_p, uint32_t d,
+                     uint32_t k, bool skip_same_index, uint32_t *d_out, double *d_sq) {
+    if (k == 0 || n_q == 0) return;
+    knn_check_args(ld_q, ld_p, n_p, d, k);
+    const int skip = skip_same_index ? 1 : 0;
+    KnnLastStats stats;
+    if (!knn_filtered(0, d_queries, ld_q, n_q, d_points, ld_p, n_p, d, k, skip, d_out, d_sq, stats, KnnPlace())) {
+        stats = KnnLastStats(); // declined (possibly after the magnitude check): nothing of the filter ran
+        exhaustive(0, d_queries, ld_q, n_q, d_points, ld_p, n_p, d, k, skip, d_out, 1, 0, 0, d_sq);
+    }
+    SCANRS_HIP(hipGetLastError());
+    knn_publish_stats(std::move(stats));
+}
+
+void knn_device(const double *d_queries, uint32_t ld_q, uint64_t n_q, const double *d_points, uint32_t ld_p, uint64_t n_p, uint32_t d,
+                uint32_t k, bool skip_same_index, uint32_t *out, double *sq_dist) {
+    if (k == 0 || n_q == 0) return;
+    knn_check_args(ld_q, ld_p, n_p, d, k);
     DevBuf<uint32_t> dout;
     DevBuf<double> ddist;
     dout.alloc(n_q * k);
     if (sq_dist) ddist.alloc(n_q * k);
-    const int skip = skip_same_index ? 1 : 0;
-    KnnLastStats stats;
-    if (!knn_filtered(0, d_queries, ld_q, n_q, d_points, ld_p, n_p, d, k, skip, dout.p, ddist.p, stats, KnnPlace())) {
-        stats = KnnLastStats(); // declined (possibly after the magnitude check): nothing of the filter ran
-        exhaustive(0, d_queries, ld_q, n_q, d_points, ld_p, n_p, d, k, skip, dout.p, 1, 0, 0, ddist.p);
-    }
-    SCANRS_HIP(hipGetLastError());
+    knn_device_into(d_queries, ld_q, n_q, d_points, ld_p, n_p, d, k, skip_same_index, dout.p, ddist.p);
     SCANRS_HIP(hipMemcpy(out, dout.p, n_q * k * 4, hipMemcpyDeviceToHost));
     if (sq_dist) SCANRS_HIP(hipMemcpy(sq_dist, ddist.p, n_q * k * 8, hipMemcpyDeviceToHost));
-    std::lock_guard<std::mutex> lock(g_stats_mutex);
-    g_last_stats = std::move(stats);
 }
 
 // ---------------------------------------------------------------------------------------------------------------------

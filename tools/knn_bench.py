@@ -2,6 +2,10 @@
 (bf16 MFMA filter + exact f64 rerank) against the exhaustive f64 kernel (global option "knn_exhaustive"), results compared.
 
     python tools/knn_bench.py N D K [both] [--shards S[,S...]] [--block-rows R]
+    python tools/knn_bench.py N D K --metric euclidean|pearson|cosine
+
+--metric: nearest_neighbors (umap-rs knn.rs:112-166) on the same points instead: the route, the filter rounds with their
+candidates per query, and the time of the call; up to 20000 points the result is compared with the host twin bit for bit.
 
 --shards: the same points through a MultiMat whose S shards share device 0: time per call, the blocks and exchange
 steps, the bytes that went through a shard's communicator, the candidates per query of the last block searched, the share of shard
@@ -23,6 +27,7 @@ ap.add_argument("k", nargs="?", type=int, default=15)
 ap.add_argument("both", nargs="?", default="")
 ap.add_argument("--shards", default="")
 ap.add_argument("--block-rows", type=int, default=0)
+ap.add_argument("--metric", default="", choices=["", "euclidean", "pearson", "cosine"])
 args = ap.parse_args()
 n, d, k = args.n, args.d, args.k
 also_exhaustive = args.both == "both" or n <= 300_000
@@ -30,6 +35,20 @@ rng = np.random.default_rng(0)
 centres = rng.standard_normal((20, d)) * 2.0
 v = (centres[rng.integers(0, 20, size=n)] + rng.standard_normal((n, d))) * np.linspace(1.0, 0.4, d)
 sa.knn(v[:1000], k)
+if args.metric:
+    sa.nearest_neighbors(v[:1000], k, args.metric)
+    t0 = time.perf_counter()
+    idx, dist = sa.nearest_neighbors(v, k, args.metric)
+    dt = time.perf_counter() - t0
+    st = sa.debug_knn_last_stats()
+    rounds = ", ".join(f"stride {r['stride']}: {r['cand_sum'] / n:.1f} (max {r['cand_max']}, {r['overflowed']} overflowed)" for r in st["rounds"])
+    print(f"nearest_neighbors[{args.metric}] n={n} d={d} k={k}: {dt*1e3:.1f} ms incl. PCIe of the points, {n/dt:.0f} cells/s; "
+          f"route {'filtered' if st['filtered'] else 'exhaustive'}, {len(st['rounds'])} filter rounds, candidates per query {rounds or '-'}; "
+          f"first row {idx[0][:5]} {dist[0][:3]}", flush=True)
+    if n <= 20000:
+        hi, hd = sa.host_nearest_neighbors(v, k, args.metric)
+        print("equals the host twin:", bool(np.array_equal(idx, hi) and np.array_equal(dist.view(np.uint64), hd.view(np.uint64))))
+    sys.exit(0)
 res = {}
 for mode in (["filter", "exhaustive"] if also_exhaustive else ["filter"]):
     sa.set_global_option("knn_exhaustive", 1 if mode == "exhaustive" else 0)
