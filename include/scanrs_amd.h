@@ -1341,9 +1341,32 @@ enum { SCANRS_DIST_EUCLIDEAN = 0, SCANRS_DIST_PEARSON = 1, SCANRS_DIST_COSINE = 
  * standardised rows with a threshold converted rigorously from the query's k-th key, every pair that passes ranked by the
  * reference formula. Options "knn_exhaustive", "knn_filter_min_points", "knn_ratio", "knn_stats" apply;
  * scanrs_debug_knn_last_stats tells which route the last call took.
- * NOT provided: the sharded / multi-GPU form, a query set distinct from the point set, and everything after the neighbour lists
- * (fuzzy graph, layout).
+ * NOT provided: everything after the neighbour lists (fuzzy graph, layout).
  * scanrs_nearest_neighbors (knn.rs:112-166): data, indices, distances are host arrays.
+ * scanrs_nearest_neighbors_query (knn.rs:112-166): a query set of its own. queries n_q x d and points n_p x d are host arrays;
+ * indices / distances: n_q x k, the indices are rows of `points`. include_self == 0 drops the point whose index equals the query's
+ * row number (the rule of scanrs_find_nn, meaningful when the two sets coincide); a row with fewer than k admissible points is
+ * padded with UINT32_MAX / +inf. Limits, routes and refusals of scanrs_nearest_neighbors (the filter asks for at least 256 queries
+ * and "knn_filter_min_points" points, and for the s_xx window on both sides); a row that is not finite is named with its set
+ * ("queries" / "points"). With queries == points and include_self == 0 the answer is scanrs_nearest_neighbors' in every bit.
+ * scanrs_nearest_neighbors_query_device (knn.rs:112-166): both sets in device memory, leading dimensions ld_q, ld_p >= d.
+ * scanrs_host_nearest_neighbors_query (knn.rs:112-166; host only): the same answer by exhaustive search on the host (any k).
+ * scanrs_nearest_neighbors_sharded (knn.rs:112-166): COLLECTIVE, over a sharded point set, with the argument conventions of
+ * scanrs_knn_sharded: points is a host array over all outer_global cells, or with points_is_device != 0 the rank's own rows in
+ * device memory; indices / distances: host, n_local x k, GLOBAL indices. The result EQUALS scanrs_nearest_neighbors of the whole
+ * point set in indices and distance bit patterns, for every cut, world size, block size and route; ties, including the ones sqrt
+ * creates, go by ascending global index. The first exchange carries n, d, k, distance_type and (first bad global row + 1) per rank:
+ * ranks that disagree get SCANRS_ERR_ARGUMENT, a coordinate that is not finite is refused on every rank, naming the global row.
+ * Then blocks of "knn_block_rows" RAW rows pass through one u64 all-reduce each; every rank prepares the block's rows itself (the
+ * same bits everywhere), searches it with the query's k-th key so far as a strict seed - through the filter where the shape
+ * conditions hold for (local queries, block) and both sides lie in the s_xx window, exhaustively otherwise - and merges the block's
+ * list into the query's running list by (key, global index). Euclidean: scanrs_knn_sharded, then the square root. On an unsharded
+ * handle the call is scanrs_nearest_neighbors / _device on the given points. Counters (scanrs_mat_get_counter), reset by every call:
+ * "knn_blocks" and "knn_allreduces" as for scanrs_knn_sharded, and "knn_blocks_filtered" = the blocks this rank searched through
+ * the filter (pearson and cosine; the route never changes a bit of the answer, so the ranks need not agree on it).
+ * scanrs_multi_nearest_neighbors (knn.rs:112-166) runs the collective call on every shard of a scanrs_multi from one process, as
+ * scanrs_multi_knn does: indices / distances cover all cells in global order; points == NULL searches the factor the last
+ * scanrs_multi_pca_bk / _rand left on the devices, with the same refusals when there is none.
  * scanrs_nearest_neighbors_device (knn.rs:112-166): the points are already in device memory (n x d, leading dimension ld >= d
  * elements; what lies behind column d is never read), e.g. *d_v / *ld_v of scanrs_pca_result_device; indices / distances host.
  * scanrs_host_nearest_neighbors (knn.rs:112-166; host only): the same answer by exhaustive search on the host (any k).
@@ -1361,6 +1384,17 @@ int scanrs_nearest_neighbors_device(const double *d_data, uint64_t n, uint32_t l
                                     uint32_t *indices, double *distances);
 int scanrs_host_nearest_neighbors(const double *data, uint64_t n, uint32_t d, uint32_t k, int distance_type, uint32_t *indices,
                                   double *distances);
+int scanrs_nearest_neighbors_query(const double *queries, uint64_t n_q, const double *points, uint64_t n_p, uint32_t d, uint32_t k,
+                                   int distance_type, int include_self, uint32_t *indices, double *distances);
+int scanrs_nearest_neighbors_query_device(const double *d_queries, uint64_t n_q, uint32_t ld_q, const double *d_points, uint64_t n_p,
+                                          uint32_t ld_p, uint32_t d, uint32_t k, int distance_type, int include_self, uint32_t *indices,
+                                          double *distances);
+int scanrs_host_nearest_neighbors_query(const double *queries, uint64_t n_q, const double *points, uint64_t n_p, uint32_t d, uint32_t k,
+                                        int distance_type, int include_self, uint32_t *indices, double *distances);
+int scanrs_nearest_neighbors_sharded(scanrs_mat *m, const double *points, int points_is_device, uint32_t ld, uint32_t d, uint32_t k,
+                                     int distance_type, uint32_t *indices, double *distances);
+int scanrs_multi_nearest_neighbors(scanrs_multi *mm, const double *points, uint32_t ld, uint32_t d, uint32_t k, int distance_type,
+                                   uint32_t *indices, double *distances);
 int scanrs_host_distance(int distance_type, const double *x, const double *y, uint32_t d, double *key, double *dist);
 int scanrs_host_metric_rows(int distance_type, const double *data, uint64_t n, uint32_t d, double *c, double *s, double *z);
 int scanrs_debug_nearest_neighbors_params(double *delta, double *e, double *chain, double *sxx_min, double *sxx_max);

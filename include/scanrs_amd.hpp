@@ -10,6 +10,7 @@
 #include <atomic>
 #include <cstdint>
 #include <functional>
+#include <limits>
 #include <stdexcept>
 #include <string>
 #include <utility>
@@ -1330,6 +1331,65 @@ inline NearestNeighbors nearest_neighbors_device(const double *d_data, size_t n,
 inline NearestNeighbors host_nearest_neighbors(const Array2 &data, size_t k, DistanceType distance_type) {
     return detail::nearest_neighbors_call(data.rows, k, [&](uint32_t *i, double *d) {
         return scanrs_host_nearest_neighbors(data.data.data(), data.rows, (uint32_t)data.cols, (uint32_t)k, (int)distance_type, i, d);
+    });
+}
+// A query set of its own: indices into `points`, n_q x min(k, n_p), padded with UINT32_MAX / +inf where a row has
+// fewer admissible points; include_self == false drops the point whose index equals the query's row number.
+namespace detail {
+template <typename F>
+inline NearestNeighbors nearest_neighbors_query_call(size_t n_q, size_t n_p, size_t k, F &&call) {
+    std::vector<uint32_t> idx(n_q * k);
+    std::vector<double> dist(n_q * k);
+    check(call(idx.data(), dist.data()));
+    NearestNeighbors r;
+    r.k = k < n_p ? k : n_p;
+    r.indices.resize(n_q * r.k);
+    r.distances.resize(n_q * r.k);
+    for (size_t i = 0; i < n_q; i++)
+        for (size_t j = 0; j < r.k; j++) r.indices[i * r.k + j] = idx[i * k + j], r.distances[i * r.k + j] = dist[i * k + j];
+    return r;
+}
+} // namespace detail
+inline NearestNeighbors nearest_neighbors_query(const Array2 &queries, const Array2 &points, size_t k, DistanceType distance_type,
+                                                bool include_self = true) {
+    if (queries.cols != points.cols) throw std::invalid_argument("Dimension mismatch");
+    return detail::nearest_neighbors_query_call(queries.rows, points.rows, k, [&](uint32_t *i, double *d) {
+        return scanrs_nearest_neighbors_query(queries.data.data(), queries.rows, points.data.data(), points.rows, (uint32_t)points.cols, (uint32_t)k,
+                                              (int)distance_type, include_self ? 1 : 0, i, d);
+    });
+}
+inline NearestNeighbors nearest_neighbors_query_device(const double *d_queries, size_t n_q, uint32_t ld_q, const double *d_points, size_t n_p,
+                                                       uint32_t ld_p, uint32_t d, size_t k, DistanceType distance_type, bool include_self = true) {
+    return detail::nearest_neighbors_query_call(n_q, n_p, k, [&](uint32_t *i, double *dd) {
+        return scanrs_nearest_neighbors_query_device(d_queries, n_q, ld_q, d_points, n_p, ld_p, d, (uint32_t)k, (int)distance_type,
+                                                     include_self ? 1 : 0, i, dd);
+    });
+}
+inline NearestNeighbors host_nearest_neighbors_query(const Array2 &queries, const Array2 &points, size_t k, DistanceType distance_type,
+                                                     bool include_self = true) {
+    if (queries.cols != points.cols) throw std::invalid_argument("Dimension mismatch");
+    return detail::nearest_neighbors_query_call(queries.rows, points.rows, k, [&](uint32_t *i, double *d) {
+        return scanrs_host_nearest_neighbors_query(queries.data.data(), queries.rows, points.data.data(), points.rows, (uint32_t)points.cols,
+                                                   (uint32_t)k, (int)distance_type, include_self ? 1 : 0, i, d);
+    });
+}
+// Where the points stay sharded: GLOBAL indices, equal to nearest_neighbors of the whole point set in every bit.
+// COLLECTIVE on one sharded handle; the result is n_local x k, padded with UINT32_MAX / +inf from column min(k, n - 1) on
+inline NearestNeighbors nearest_neighbors_sharded(const AdaptiveMat &m, uint64_t n_local, const double *points, bool points_is_device, uint32_t ld,
+                                                  uint32_t d, size_t k, DistanceType distance_type) {
+    NearestNeighbors r;
+    r.k = k;
+    r.indices.assign((size_t)n_local * k, 0xFFFFFFFFu);
+    r.distances.assign((size_t)n_local * k, std::numeric_limits<double>::infinity());
+    check(scanrs_nearest_neighbors_sharded(m.raw(), points, points_is_device ? 1 : 0, ld, d, (uint32_t)k, (int)distance_type, r.indices.data(),
+                                           r.distances.data()));
+    return r;
+}
+// over the shards of a MultiMat from one process; points == nullptr: the scores its last run_pca left on the devices
+inline NearestNeighbors nearest_neighbors(const MultiMat &m, uint64_t cells, const double *points, uint32_t ld, uint32_t d, size_t k,
+                                          DistanceType distance_type) {
+    return detail::nearest_neighbors_call(cells, k, [&](uint32_t *i, double *dd) {
+        return scanrs_multi_nearest_neighbors(m.raw(), points, ld, d, (uint32_t)k, (int)distance_type, i, dd);
     });
 }
 inline void host_distance(DistanceType distance_type, const double *x, const double *y, uint32_t d, double *key, double *dist) {

@@ -825,6 +825,35 @@ class AdaptiveMat:
         del keep
         return (out, sq) if return_sq_dist else out
 
+    def nearest_neighbors_sharded(self, points, k: int, distance="euclidean", device: bool = False):
+        """`nearest_neighbors` over a sharded point set (`scanrs_nearest_neighbors_sharded`, knn.rs:112-166):
+        COLLECTIVE, every rank calls it with the same k and distance. points as for `knn_sharded`. Returns (indices, distances) of the
+        rank's cells, n_local x min(k, n - 1) with n the global number of cells: GLOBAL indices, nearest first - what
+        `nearest_neighbors` of the whole point set returns for those rows, in every bit. On an unsharded handle it is
+        `nearest_neighbors` / `nearest_neighbors_device` of the given points."""
+        n_local = int(self.shape()[1])
+        keep = None
+        if device:
+            if isinstance(points, PcaResultDevice):
+                ptr, ld, d = points.d_v, int(points.ld_v), int(points.k)
+            else:
+                ptr, ld, d = points
+            ptr = ctypes.c_void_p(int(ptr) if ptr else None)
+        elif points is None:
+            ptr, ld, d = None, 0, 0
+        else:
+            keep = _f64(np.atleast_2d(points))
+            ptr, ld, d = _p(keep), int(keep.shape[1]), int(keep.shape[1])
+        k = int(k)
+        idx = np.full((n_local, k), 0xFFFFFFFF, dtype=np.uint32)
+        dist = np.full((n_local, k), np.inf, dtype=np.float64)
+        _check(_lib.scanrs_nearest_neighbors_sharded(self._h, ptr, ctypes.c_int(1 if device else 0), ctypes.c_uint32(ld), ctypes.c_uint32(d),
+                                                     ctypes.c_uint32(k), ctypes.c_int(_distance_type(distance)), _p(idx), _p(dist)))
+        del keep
+        n = int(getattr(self, "_outer_global", 0) or n_local)
+        k_eff = min(k, max(n - 1, 0))
+        return np.ascontiguousarray(idx[:, :k_eff]), np.ascontiguousarray(dist[:, :k_eff])
+
     def profile_enable(self, on: bool = True):
         _check(_lib.scanrs_profile_enable(self._h, ctypes.c_int(int(on))))
 
@@ -1539,6 +1568,19 @@ class MultiMat:
         _check(_lib.scanrs_multi_knn(self._h, _p(pts), ctypes.c_uint32(d), ctypes.c_uint32(d), ctypes.c_uint32(k), _p(out), _p(sq)))
         return (out, sq) if return_sq_dist else out
 
+    def nearest_neighbors(self, k: int, points=None, distance="euclidean"):
+        """`nearest_neighbors` over the shards (`scanrs_multi_nearest_neighbors`, knn.rs:112-166): (indices u32,
+        distances f64), each cells x min(k, cells - 1), global indices, nearest first, equal to `nearest_neighbors` of the whole point
+        set in every bit. points: a host array over all cells, or None: every shard searches the scores its last run_pca_bk /
+        run_pca_rand left on its device."""
+        cells = self.cols if self.storage == CSC else self.rows
+        pts = None if points is None else _f64(np.atleast_2d(points))
+        d = 0 if pts is None else int(pts.shape[1])
+        if pts is not None and pts.shape[0] != cells:
+            raise ScanrsError(6, f"the points have {pts.shape[0]} rows for {cells} cells")
+        return _nearest_neighbors_call(_lib.scanrs_multi_nearest_neighbors, int(cells), int(k), self._h, _p(pts), ctypes.c_uint32(d),
+                                       ctypes.c_uint32(d), ctypes.c_uint32(k), ctypes.c_int(_distance_type(distance)))
+
     def comm_info(self, shard: int = 0) -> dict:
         """`scanrs_comm_info` of shard `shard`'s communicator: the sum all-reduces that went through it so far."""
         n, r = ctypes.c_uint32(), ctypes.c_uint32()
@@ -1741,6 +1783,53 @@ def host_nearest_neighbors(data, k: int, distance="euclidean"):
                                    ctypes.c_int(_distance_type(distance)))
 
 
+def _nearest_neighbors_query_call(fn, n_q: int, n_p: int, k: int, *args):
+    """The C entry points write n_q x k; the width returned is min(k, n_p), padded with UINT32_MAX / +inf where a row has fewer."""
+    idx = np.full((n_q, k), 0xFFFFFFFF, dtype=np.uint32)
+    dist = np.full((n_q, k), np.inf, dtype=np.float64)
+    _check(fn(*args, _p(idx), _p(dist)))
+    k_eff = min(k, n_p)
+    return np.ascontiguousarray(idx[:, :k_eff]), np.ascontiguousarray(dist[:, :k_eff])
+
+
+def _query_sets(queries, points):
+    queries, points = _f64(np.atleast_2d(queries)), _f64(np.atleast_2d(points))
+    if queries.shape[1] != points.shape[1]:
+        raise ScanrsError(1, "Dimension mismatch")
+    return queries, points
+
+
+def nearest_neighbors_query(queries, points, k: int, distance="euclidean", include_self: bool = True):
+    """`nearest_neighbors` with a query set of its own (`scanrs_nearest_neighbors_query`, knn.rs:112-166): (indices
+    u32 into `points`, distances f64), each n_q x min(k, n_p), nearest first. include_self=False drops the point whose index equals
+    the query's row number (the rule of `find_nn`); a row with fewer admissible points is padded with UINT32_MAX / +inf. With
+    queries is points and include_self=False it is `nearest_neighbors` in every bit. Equal to `host_nearest_neighbors_query`."""
+    queries, points = _query_sets(queries, points)
+    (n_q, d), n_p = queries.shape, points.shape[0]
+    return _nearest_neighbors_query_call(_lib.scanrs_nearest_neighbors_query, n_q, n_p, int(k), _p(queries), ctypes.c_uint64(n_q), _p(points),
+                                         ctypes.c_uint64(n_p), ctypes.c_uint32(d), ctypes.c_uint32(k), ctypes.c_int(_distance_type(distance)),
+                                         ctypes.c_int(1 if include_self else 0))
+
+
+def nearest_neighbors_query_device(d_queries: int, n_q: int, ld_q: int, d_points: int, n_p: int, ld_p: int, d: int, k: int, distance="euclidean",
+                                   include_self: bool = True):
+    """`nearest_neighbors_query` on sets that already live in device memory, leading dimensions ld_q, ld_p >= d
+    (`scanrs_nearest_neighbors_query_device`, knn.rs:112-166): host arrays (indices, distances)."""
+    return _nearest_neighbors_query_call(_lib.scanrs_nearest_neighbors_query_device, int(n_q), int(n_p), int(k), ctypes.c_void_p(d_queries),
+                                         ctypes.c_uint64(n_q), ctypes.c_uint32(ld_q), ctypes.c_void_p(d_points), ctypes.c_uint64(n_p),
+                                         ctypes.c_uint32(ld_p), ctypes.c_uint32(d), ctypes.c_uint32(k), ctypes.c_int(_distance_type(distance)),
+                                         ctypes.c_int(1 if include_self else 0))
+
+
+def host_nearest_neighbors_query(queries, points, k: int, distance="euclidean", include_self: bool = True):
+    """The host twin of `nearest_neighbors_query` (`scanrs_host_nearest_neighbors_query`, knn.rs:112-166; no device, any k)."""
+    queries, points = _query_sets(queries, points)
+    (n_q, d), n_p = queries.shape, points.shape[0]
+    return _nearest_neighbors_query_call(_lib.scanrs_host_nearest_neighbors_query, n_q, n_p, int(k), _p(queries), ctypes.c_uint64(n_q), _p(points),
+                                         ctypes.c_uint64(n_p), ctypes.c_uint32(d), ctypes.c_uint32(k), ctypes.c_int(_distance_type(distance)),
+                                         ctypes.c_int(1 if include_self else 0))
+
+
 def host_distance(distance, x, y):
     """One pair (`scanrs_host_distance`, dist.rs:19-34, 73-124; no device): (key, dist) = (the rank key sqrt(D), key * key); euclidean:
     both are the distance."""
@@ -1936,7 +2025,9 @@ EXPORTED_SYMBOLS = [
     "scanrs_hclust_create", "scanrs_hclust_create_device", "scanrs_hclust_from_steps", "scanrs_hclust_free", "scanrs_hclust_n", "scanrs_hclust_steps",
     "scanrs_hclust_leaves", "scanrs_hclust_merge_below", "scanrs_hclust_fcluster", "scanrs_hclust_info", "scanrs_host_hclust_linkage",
     "scanrs_debug_hclust_pdist",
-    "scanrs_nearest_neighbors", "scanrs_nearest_neighbors_device", "scanrs_host_nearest_neighbors", "scanrs_host_distance", "scanrs_host_metric_rows",
+    "scanrs_nearest_neighbors", "scanrs_nearest_neighbors_device", "scanrs_host_nearest_neighbors",
+    "scanrs_nearest_neighbors_query", "scanrs_nearest_neighbors_query_device", "scanrs_host_nearest_neighbors_query",
+    "scanrs_nearest_neighbors_sharded", "scanrs_multi_nearest_neighbors", "scanrs_host_distance", "scanrs_host_metric_rows",
     "scanrs_debug_nearest_neighbors_params",
     "scanrs_mat_select_rows", "scanrs_mat_select_cols", "scanrs_mat_partition_on_thresholds", "scanrs_mat_to_csmat",
     "scanrs_mat_select_rows_sharded", "scanrs_mat_select_cols_sharded", "scanrs_mat_partition_on_thresholds_sharded", "scanrs_mat_shard_info",

@@ -1216,6 +1216,85 @@ int scanrs_host_nearest_neighbors(const double *data, uint64_t n, uint32_t d, ui
         host_nearest_neighbors(data, n, d, k, distance_type, indices, distances);
     });
 }
+// a query set of its own
+int scanrs_nearest_neighbors_query(const double *queries, uint64_t n_q, const double *points, uint64_t n_p, uint32_t d, uint32_t k,
+                                   int distance_type, int include_self, uint32_t *indices, double *distances) {
+    return guard([&] {
+        if ((!queries && n_q) || (!points && n_p) || ((!indices || !distances) && n_q && k)) fail(SCANRS_ERR_ARGUMENT, "null argument");
+        nearest_neighbors_check_args(n_p, d, d, k, distance_type);
+        nearest_neighbors_check_args(n_q, d, d, k, distance_type);
+        if (k == 0 || n_q == 0) return;
+        need_device();
+        const bool same = queries == points && n_q == n_p;
+        DevBuf<double> dp(std::max<uint64_t>(1, n_p * d)), dq;
+        if (n_p) SCANRS_HIP(hipMemcpy(dp.p, points, n_p * d * 8, hipMemcpyHostToDevice));
+        if (!same) {
+            dq.alloc(n_q * d);
+            SCANRS_HIP(hipMemcpy(dq.p, queries, n_q * d * 8, hipMemcpyHostToDevice));
+        }
+        nearest_neighbors_query_device(same ? dp.p : dq.p, n_q, d, dp.p, n_p, d, d, k, distance_type, include_self != 0, indices, distances);
+    });
+}
+int scanrs_nearest_neighbors_query_device(const double *d_queries, uint64_t n_q, uint32_t ld_q, const double *d_points, uint64_t n_p, uint32_t ld_p,
+                                          uint32_t d, uint32_t k, int distance_type, int include_self, uint32_t *indices, double *distances) {
+    return guard([&] {
+        if ((!d_queries && n_q) || (!d_points && n_p) || ((!indices || !distances) && n_q && k)) fail(SCANRS_ERR_ARGUMENT, "null argument");
+        nearest_neighbors_check_args(n_p, ld_p, d, k, distance_type);
+        nearest_neighbors_check_args(n_q, ld_q, d, k, distance_type);
+        if (k == 0 || n_q == 0) return;
+        need_device();
+        nearest_neighbors_query_device(d_queries, n_q, ld_q, d_points, n_p, ld_p, d, k, distance_type, include_self != 0, indices, distances);
+    });
+}
+int scanrs_host_nearest_neighbors_query(const double *queries, uint64_t n_q, const double *points, uint64_t n_p, uint32_t d, uint32_t k,
+                                        int distance_type, int include_self, uint32_t *indices, double *distances) {
+    return guard([&] {
+        if ((!queries && n_q) || (!points && n_p) || ((!indices || !distances) && n_q && k)) fail(SCANRS_ERR_ARGUMENT, "null argument");
+        host_nearest_neighbors_query(queries, n_q, points, n_p, d, k, distance_type, include_self != 0, indices, distances);
+    });
+}
+// nearest_neighbors over a sharded handle: COLLECTIVE, the argument conventions of scanrs_knn_sharded
+int scanrs_nearest_neighbors_sharded(scanrs_mat *m, const double *points, int points_is_device, uint32_t ld, uint32_t d, uint32_t k,
+                                     int distance_type, uint32_t *indices, double *distances) {
+    return guard([&] {
+        if (!m) fail(SCANRS_ERR_ARGUMENT, "null handle");
+        CurrentHandle cur(m->st.get());
+        Storage &st = *m->st;
+        st.knn_blocks = st.knn_allreduces = st.knn_blocks_filtered = 0;
+        const uint64_t n_local = m->cols();
+        if (!st.shard.active()) { // scanrs_nearest_neighbors / _device on the given points
+            if ((!points && n_local) || ((!indices || !distances) && n_local && k)) fail(SCANRS_ERR_ARGUMENT, "null argument");
+            nearest_neighbors_check_args(n_local, ld, d, k, distance_type);
+            if (k == 0 || n_local == 0) return;
+            need_device();
+            if (points_is_device) {
+                nearest_neighbors_device(points, n_local, ld, d, k, distance_type, indices, distances);
+            } else {
+                DevBuf<double> dp(n_local * ld);
+                SCANRS_HIP(hipMemcpy(dp.p, points, ((n_local - 1) * ld + d) * 8, hipMemcpyHostToDevice));
+                nearest_neighbors_device(dp.p, n_local, ld, d, k, distance_type, indices, distances);
+            }
+            return;
+        }
+        if (!cols_sharded(m))
+            fail(SCANRS_ERR_ARGUMENT, "nearest_neighbors_sharded: the cells (the columns of this view) must be the sharded dimension");
+        const uint64_t begin = st.shard.outer_begin, n = st.shard.outer_global;
+        if ((!points && (points_is_device ? n_local : n)) || ((!indices || !distances) && n_local && k)) fail(SCANRS_ERR_ARGUMENT, "null argument");
+        // host points span all the cells and only this rank's rows go to the device; device points are the rank's own rows already
+        DevBuf<double> d_pts;
+        const double *pts = points;
+        if (!points_is_device) {
+            d_pts.alloc(std::max<uint64_t>(1, n_local * ld));
+            if (n_local && ld >= d) {
+                SCANRS_HIP(hipMemcpyAsync(d_pts.p, points + begin * ld, ((n_local - 1) * ld + d) * 8, hipMemcpyHostToDevice, st.stream));
+                SCANRS_SYNC(st.stream); // the caller's array may be pageable
+            }
+            pts = d_pts.p;
+        }
+        nearest_neighbors_sharded(st, pts, ld, begin, n_local, n, d, k, distance_type, indices, distances);
+        device_free_flush();
+    });
+}
 int scanrs_host_distance(int distance_type, const double *x, const double *y, uint32_t d, double *key, double *dist) {
     return guard([&] {
         if (!x || !y || !key || !dist) fail(SCANRS_ERR_ARGUMENT, "null argument");
@@ -1653,6 +1732,8 @@ int scanrs_mat_get_counter(scanrs_mat *m, const char *key, uint64_t *value) {
             *value = m->st->knn_blocks;
         else if (k == "knn_allreduces") // ... and its exchange steps (an unsharded handle: 0)
             *value = m->st->knn_allreduces;
+        else if (k == "knn_blocks_filtered") // the last scanrs_nearest_neighbors_sharded: blocks this rank searched through the filter
+            *value = m->st->knn_blocks_filtered;
         else if (k == "subset_allreduces") // the exchange steps of the last sharded sum over a column list (an unsharded handle: 0)
             *value = m->st->subset_allreduces;
         else if (k.rfind("reshard_", 0) == 0 && k.size() > 11 && k.compare(k.size() - 3, 3, "_us") == 0) {

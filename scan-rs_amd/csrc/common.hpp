@@ -408,7 +408,8 @@ struct Storage {
     uint64_t export_us[3] = {0, 0, 0};    // a shard of the last scanrs_multi_to_adaptive: wall clock of the plan (the transposed copies, their indptr to the host and the host plan: one phase, the same on every shard; 0 for major STORED) and of its own thread in pull (0 for STORED) and encode + download (scanrs_mat_get_counter)
     int subset_scatter = 1;               // integer sums over a column list when only the other orientation exists: 1 = scattered into the result with 64-bit integer atomics from the copy that exists, 0 = the missing copy is built (subset_host.cpp)
     uint64_t subset_masked_passes = 0, subset_scatter_passes = 0; // sums over a column list made so far on this handle: from the copy whose outer dimension is the result axis / through the integer scatter (scanrs_mat_get_counter)
-    uint64_t knn_blocks = 0, knn_allreduces = 0; // the last scanrs_knn_sharded on this handle: blocks of the point set searched, exchange steps (an unsharded one: 0)
+    uint64_t knn_blocks = 0, knn_allreduces = 0; // the last scanrs_knn_sharded / scanrs_nearest_neighbors_sharded on this handle: blocks of the point set searched, exchange steps (an unsharded one: 0)
+    uint64_t knn_blocks_filtered = 0;     // the last scanrs_nearest_neighbors_sharded on this handle: blocks this rank searched through the filter (pearson / cosine)
     uint64_t subset_allreduces = 0;       // exchange steps of the last scanrs_mat_sum_rows_*_sharded (and kin) on this handle (an unsharded one: 0)
     uint64_t sseq_moment_walks = 0;       // the last sseq_params on this handle: walks over the nonzeros for the moments, 1 under one quantum, 2 with a quantum per gene (the class walk first)
     uint32_t sseq_grid_cap = 16384;       // workgroups of the moment / group pass and the class walk at most (option "sseq_grid_cap": a small cap makes every wave take several outer vectors, for tests)

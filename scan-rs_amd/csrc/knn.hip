@@ -28,6 +28,7 @@
 #include "common.hpp"
 #include "knn_filter.hpp"
 #include "knn_merge.hpp"
+#include "knn_shard.hpp"
 #include "shard_exchange.hpp"
 
 namespace scanrs {
@@ -514,12 +515,13 @@ void kf_launch_prep_queries(hipStream_t s, const double *dq, uint32_t ldq, uint6
     hipLaunchKernelGGL(kf_prep_queries_kernel, dim3((unsigned)((qs.nq_rows + 255) / 256)), dim3(256), 0, s, dq, ldq, n_q, qs.nq_rows, d, qs.Qb.p,
                        qs.qn.p);
 }
+} // namespace
+
 // the query side alone, for a search whose points arrive in blocks: its max-abs pass and its operands are made once
 void kf_prepare_queries(hipStream_t s, const double *dq, uint32_t ldq, uint64_t n_q, uint32_t d, KfQueries &qs) {
     qs.maxabs = kf_maxabs(s, dq, ldq, n_q, nullptr, 0, 0, d);
     if (qs.maxabs <= KF_COORD_MAX) kf_launch_prep_queries(s, dq, ldq, n_q, d, qs); // (false for NaN: nothing is prepared, no block is filtered)
 }
-} // namespace
 
 // false: a coordinate is not finite or max |coordinate| lies outside the magnitude window; nothing has been prepared.
 // shared: the query side prepared earlier by kf_prepare_queries (nullptr: it is prepared here)
@@ -583,9 +585,6 @@ struct KnnPlace {
     uint64_t seed_ld = 0;
     const KfQueries *queries = nullptr; // the query side prepared once for all blocks
 };
-// Round 0 of a seeded search only tightens a threshold the earlier blocks have set already, and it is paid once per block: its
-// exactly ranked subset is a quarter of what an unseeded search ranks, one more filter round in exchange.
-constexpr uint64_t KF_SEED_N0 = KF_CAP / 4;
 
 bool knn_filtered(hipStream_t s, const double *dq, uint32_t ldq, uint64_t n_q, const double *dp, uint32_t ldp, uint64_t n_p, uint32_t d,
                   uint32_t k, int skip, uint32_t *dout, double *ddist, KnnLastStats &stats, const KnnPlace &pl) {
@@ -800,91 +799,39 @@ void knn_device(const double *d_queries, uint32_t ld_q, uint64_t n_q, const doub
 // global blocks that one u64 all-reduce hands to every rank (each slot of the zeroed buffer has one writer, so the sum is the bit
 // pattern itself), each block is searched with the machinery above, seeded with what the query already holds, and its list is merged
 // into the query's running list by (squared distance, global index). The result does not depend on the cut: it is the k smallest
-// pairs under that total order, and the distance is the same fma chain everywhere.
-namespace {
-
-__global__ void ks_fill_kernel(double *__restrict__ x, uint64_t n, double v) {
-    const uint64_t e = (uint64_t)blockIdx.x * blockDim.x + threadIdx.x;
-    if (e < n) x[e] = v;
-}
-// the first local row that holds a coordinate which is not finite (an integer minimum; ~0 stays when there is none)
-__global__ __launch_bounds__(256) void ks_scan_kernel(const double *__restrict__ X, uint32_t ld, uint64_t n, uint32_t d,
-                                                      unsigned long long *__restrict__ first) {
-    const uint64_t total = n * d, step = (uint64_t)gridDim.x * blockDim.x;
-    for (uint64_t e = (uint64_t)blockIdx.x * blockDim.x + threadIdx.x; e < total; e += step) {
-        const uint64_t r = e / d;
-        const double x = X[r * ld + (e % d)];
-        if (!(fabs(x) <= DBL_MAX)) atomicMin(first, (unsigned long long)r);
-    }
-}
-// what the ranks agree on before the first block: this rank's four words, n, d, k and (first bad global row + 1)
-__global__ void ks_header_kernel(unsigned long long *__restrict__ mine, uint64_t n, uint32_t d, uint32_t k, uint64_t begin,
-                                 const unsigned long long *__restrict__ first) {
-    if (blockIdx.x != 0 || threadIdx.x != 0) return;
-    mine[0] = n;
-    mine[1] = d;
-    mine[2] = k;
-    mine[3] = *first == ~0ull ? 0ull : begin + *first + 1ull;
-}
-// the bit patterns of n_rows rows of this rank into their place of the block buffer (rows x d, no padding)
-__global__ void ks_pack_kernel(const double *__restrict__ src, uint32_t ld, uint32_t d, uint64_t n_rows, unsigned long long *__restrict__ dst) {
-    const uint64_t e = (uint64_t)blockIdx.x * blockDim.x + threadIdx.x;
-    if (e >= n_rows * d) return;
-    dst[e] = (unsigned long long)__double_as_longlong(src[(e / d) * ld + (e % d)]);
-}
-// running list (+) block list -> running list: one wave per query, both lists staged in LDS (the block's indices become global
-// there), every lane places its entries by the rule of knn_merge.hpp. No atomics, nothing that depends on an order of arrival.
-__global__ __launch_bounds__(256) void ks_merge_kernel(uint64_t n_q, uint32_t k, const double *__restrict__ rd, const uint32_t *__restrict__ ri,
-                                                       const double *__restrict__ bd, const uint32_t *__restrict__ bi, uint32_t b_off,
-                                                       double *__restrict__ od, uint32_t *__restrict__ oi) {
-    __shared__ double sd[4][2 * KMAX];
-    __shared__ uint32_t si[4][2 * KMAX];
-    const uint32_t lane = threadIdx.x & 63u, w = threadIdx.x >> 6;
-    const uint64_t q = (uint64_t)blockIdx.x * 4u + w;
-    const bool live = q < n_q;
-    if (live)
-        for (uint32_t e = lane; e < k; e += 64u) {
-            sd[w][e] = rd[q * k + e];
-            si[w][e] = ri[q * k + e];
-            const uint32_t t = bi[q * k + e];
-            sd[w][KMAX + e] = bd[q * k + e];
-            si[w][KMAX + e] = t == 0xFFFFFFFFu ? t : t + b_off;
-        }
-    __syncthreads();
-    if (!live) return;
-    for (uint32_t e = lane; e < 2u * k; e += 64u)
-        knn_merge::place(k, sd[w], si[w], sd[w] + KMAX, si[w] + KMAX, e, od + q * k, oi + q * k);
-}
-
-} // namespace
-
-void knn_sharded(Storage &st, const double *d_pts, uint32_t ld, uint64_t begin, uint64_t n_local, uint64_t n, uint32_t d, uint32_t k,
-                 uint32_t *out, double *sq_dist) {
+// pairs under that total order, and the distance is the same fma chain everywhere. The walk (its kernels are in knn_shard.hpp) is
+// shared with nearest_neighbors_sharded of knn_metric.hip, which brings its own search of one block (KnnBlockSearch).
+void knn_sharded_blocks(Storage &st, const double *d_pts, uint32_t ld, uint64_t begin, uint64_t n_local, uint64_t n, uint32_t d, uint32_t k,
+                        const KnnBlockSearch &bs, uint32_t *out, double *keys) {
     const hipStream_t s = st.stream;
     const uint32_t world = st.shard.world, rank = st.shard.rank;
     ShardExchange ex{st, st.knn_allreduces};
-    // 1. The ranks agree: the same n, d, k everywhere (a rank that differs would bring another count to a later exchange), and no
-    //    coordinate that is not finite (with a NaN the order is not total and a blockwise merge could differ from one pass).
+    // 1. The ranks agree: the same n, d, k and kind of search everywhere (a rank that differs would bring another count to a later
+    //    exchange), and no coordinate that is not finite (with a NaN the order is not total and a blockwise merge could differ from
+    //    one pass).
     const bool scannable = n_local && d && ld >= d && d_pts;
     DevBuf<unsigned long long> first(1), hdr(4);
     SCANRS_HIP(hipMemsetAsync(first.p, 0xFF, 8, s));
     if (scannable)
         hipLaunchKernelGGL(ks_scan_kernel, dim3((unsigned)std::min<uint64_t>((n_local * d + 255) / 256, 2048)), dim3(256), 0, s, d_pts, ld, n_local, d,
                            first.p);
-    hipLaunchKernelGGL(ks_header_kernel, dim3(1), dim3(64), 0, s, hdr.p, n, d, k, begin, first.p);
+    hipLaunchKernelGGL(ks_header_kernel, dim3(1), dim3(64), 0, s, hdr.p, n, d, k, bs.kind, begin, first.p);
     const std::vector<unsigned long long> h = ex.gather(hdr.p, 4);
+    const unsigned long long kword = (unsigned long long)k | ((unsigned long long)(uint32_t)bs.kind << 32);
     unsigned long long bad = 0;
     for (uint32_t r = 0; r < world; r++) {
-        if (h[4 * r] != n || h[4 * r + 1] != d || h[4 * r + 2] != k)
-            fail(SCANRS_ERR_ARGUMENT, "knn_sharded: the ranks disagree (rank %u: n %llu, d %llu, k %llu; rank %u: n %llu, d %u, k %u)", r, h[4 * r],
-                 h[4 * r + 1], h[4 * r + 2], rank, (unsigned long long)n, d, k);
+        if (h[4 * r] != n || h[4 * r + 1] != d || h[4 * r + 2] != kword)
+            fail(SCANRS_ERR_ARGUMENT,
+                 "%s: the ranks disagree (rank %u: n %llu, d %llu, k %llu, distance %llu; rank %u: n %llu, d %u, k %u, distance %d)", bs.name, r,
+                 h[4 * r], h[4 * r + 1], h[4 * r + 2] & 0xFFFFFFFFull, h[4 * r + 2] >> 32, rank, (unsigned long long)n, d, k, bs.kind);
         if (h[4 * r + 3] && (!bad || h[4 * r + 3] < bad)) bad = h[4 * r + 3];
     }
-    if (k > KMAX) fail(SCANRS_ERR_ARGUMENT, "knn: k must not exceed 128");
-    if (d == 0 || d > 128) fail(SCANRS_ERR_ARGUMENT, "knn: 1 <= dimensions <= 128");
-    if (n > 0xFFFFFFFEull) fail(SCANRS_ERR_SHAPE, "knn: too many points for u32 indices");
-    if (bad) fail(SCANRS_ERR_ARGUMENT, "knn_sharded: row %llu of the points holds a coordinate that is not finite", bad - 1);
-    if (ld < d) fail(SCANRS_ERR_ARGUMENT, "knn: leading dimension smaller than the number of coordinates");
+    if (bs.kind < 0 || bs.kind > 2) fail(SCANRS_ERR_ARGUMENT, "%s: distance type %d (0 euclidean, 1 pearson, 2 cosine)", bs.check, bs.kind);
+    if (k > KMAX) fail(SCANRS_ERR_ARGUMENT, "%s: k must not exceed 128", bs.check);
+    if (d == 0 || d > 128) fail(SCANRS_ERR_ARGUMENT, "%s: 1 <= dimensions <= 128", bs.check);
+    if (n > 0xFFFFFFFEull) fail(SCANRS_ERR_SHAPE, "%s: too many points for u32 indices", bs.check);
+    if (bad) fail(SCANRS_ERR_ARGUMENT, "%s: row %llu of the points holds a coordinate that is not finite", bs.name, bad - 1);
+    if (ld < d) fail(SCANRS_ERR_ARGUMENT, "%s: leading dimension smaller than the number of coordinates", bs.check);
     if (k == 0 || n == 0) return;
 
     // 2. The running lists, sorted, padded with (+inf, UINT32_MAX); two copies: a merge reads one and writes the other.
@@ -900,7 +847,8 @@ void knn_sharded(Storage &st, const double *d_pts, uint32_t ld, uint64_t begin, 
     const uint64_t block_rows = std::max<uint64_t>(1, go.knn_block_rows);
     const uint64_t largest = std::min(block_rows, n);
     KfQueries qs;
-    const bool may_filter = !go.knn_exhaustive && d <= KF_DMAX && k <= KF_KMAX && n_local >= KF_NQ_MIN && largest >= go.knn_filter_min_points;
+    const bool may_filter =
+        !bs.search && !go.knn_exhaustive && d <= KF_DMAX && k <= KF_KMAX && n_local >= KF_NQ_MIN && largest >= go.knn_filter_min_points;
     if (may_filter) kf_prepare_queries(s, d_pts, ld, n_local, d, qs);
 
     // 4. The blocks. The cut is global, so every rank walks the same blocks and the exchange steps pair up.
@@ -918,16 +866,20 @@ void knn_sharded(Storage &st, const double *d_pts, uint32_t ld, uint64_t begin, 
         if (!n_local) continue;
         const double *blk = reinterpret_cast<const double *>(xbuf.p);
         if (st.prof.on) st.prof.begin(s, "knn_search", (double)(rows + n_local) * d * 8.0);
-        KnnPlace pl;
-        pl.p_off = b0;
-        pl.q_off = begin;
-        pl.seed = rd[cur].p + (k - 1);
-        pl.seed_ld = k;
-        pl.queries = may_filter ? &qs : nullptr;
         stats = KnnLastStats();
-        if (!knn_filtered(s, d_pts, ld, n_local, blk, d, rows, d, k, 1, bidx.p, bdist.p, stats, pl)) {
-            stats = KnnLastStats();
-            exhaustive(s, d_pts, ld, n_local, blk, d, rows, d, k, 1, bidx.p, 1, b0, begin, bdist.p);
+        if (bs.search) {
+            bs.search(s, blk, rows, b0, rd[cur].p + (k - 1), bidx.p, bdist.p, stats);
+        } else {
+            KnnPlace pl;
+            pl.p_off = b0;
+            pl.q_off = begin;
+            pl.seed = rd[cur].p + (k - 1);
+            pl.seed_ld = k;
+            pl.queries = may_filter ? &qs : nullptr;
+            if (!knn_filtered(s, d_pts, ld, n_local, blk, d, rows, d, k, 1, bidx.p, bdist.p, stats, pl)) {
+                stats = KnnLastStats();
+                exhaustive(s, d_pts, ld, n_local, blk, d, rows, d, k, 1, bidx.p, 1, b0, begin, bdist.p);
+            }
         }
         if (st.prof.on) st.prof.end(s);
         if (st.prof.on) st.prof.begin(s, "knn_merge", (double)n_local * k * 36.0);
@@ -938,14 +890,20 @@ void knn_sharded(Storage &st, const double *d_pts, uint32_t ld, uint64_t begin, 
         cur = 1 - cur;
     }
     if (n_local) {
+        if (bs.finish && keys) bs.finish(s, rd[cur].p, n_local * k);
         SCANRS_D2H(out, ri[cur].p, n_local * k * 4, s);
-        if (sq_dist) SCANRS_D2H(sq_dist, rd[cur].p, n_local * k * 8, s);
+        if (keys) SCANRS_D2H(keys, rd[cur].p, n_local * k * 8, s);
     }
     SCANRS_SYNC(s);
     if (n_local) {
         std::lock_guard<std::mutex> lock(g_stats_mutex);
         g_last_stats = std::move(stats);
     }
+}
+
+void knn_sharded(Storage &st, const double *d_pts, uint32_t ld, uint64_t begin, uint64_t n_local, uint64_t n, uint32_t d, uint32_t k,
+                 uint32_t *out, double *sq_dist) {
+    knn_sharded_blocks(st, d_pts, ld, begin, n_local, n, d, k, KnnBlockSearch(), out, sq_dist);
 }
 
 void knn_host_merge(uint32_t k, const double *da, const uint32_t *ia, const double *db, const uint32_t *ib, double *dout, uint32_t *iout) {

@@ -23,6 +23,9 @@ constexpr double KF_COORD_MIN = 0x1p-48, KF_COORD_MAX = 0x1p46; // the magnitude
 constexpr float KF_SENTINEL = 1e30f; // N of a sentinel point row, -A of a sentinel query row
 constexpr double KF_A_PASS = 9e29;   // A of "everything passes": above every legitimate A, below the sentinel
 constexpr uint32_t KF_PER_LANE = KF_CAP / 64u; // candidates a lane of the rerank kernels holds
+// Round 0 of a seeded search only tightens a threshold the earlier blocks have set already, and it is paid once per block: its
+// exactly ranked subset is a quarter of what an unseeded search ranks, one more filter round in exchange.
+constexpr uint64_t KF_SEED_N0 = KF_CAP / 4;
 
 // what the last search of the process did (scanrs_debug_knn_last_stats)
 struct KfRound {
@@ -54,6 +57,8 @@ struct KfOperands {
 // shared: the query side prepared earlier by kf_prepare_queries (nullptr: it is prepared here)
 bool kf_prepare(hipStream_t s, const double *dq, uint32_t ldq, uint64_t n_q, const double *dp, uint32_t ldp, uint64_t n_p, uint32_t d,
                 KfOperands &op, const KfQueries *shared = nullptr);
+// the query side alone, for a search whose points arrive in blocks: its max-abs pass and its operands are made once
+void kf_prepare_queries(hipStream_t s, const double *dq, uint32_t ldq, uint64_t n_q, uint32_t d, KfQueries &qs);
 // one pass of the filter over rows 0, st, 2 st, ... of the points with the thresholds tau: cnt (n_q) and the lists cand (n_q x KF_CAP).
 // Every point whose fma-chain squared distance to the query is <= tau[q] is in the query's list (or the list has overflowed).
 void kf_filter_pass(hipStream_t s, const KfOperands &op, const double *tau, uint64_t n_q, uint64_t n_p, uint64_t st, uint32_t *cand,

@@ -57,7 +57,17 @@ KM_HD inline double prepare_row(int kind, const double *x, uint32_t d, double *c
 // knn_metric.hip: indices / distances are host arrays, n x k, padded with UINT32_MAX / +inf from column min(k, n - 1) on
 void nearest_neighbors_device(const double *d_data, uint64_t n, uint32_t ld, uint32_t d, uint32_t k, int kind, uint32_t *indices,
                               double *distances);
+// a query set of its own: n_q x k; include_self == false drops the point whose index equals the query's row number
+void nearest_neighbors_query_device(const double *d_queries, uint64_t n_q, uint32_t ld_q, const double *d_points, uint64_t n_p, uint32_t ld_p,
+                                    uint32_t d, uint32_t k, int kind, bool include_self, uint32_t *indices, double *distances);
+// COLLECTIVE, over a sharded point set: d_pts are the rank's own rows [begin, begin + n_local) of the n global ones; indices /
+// distances are host arrays over the rank's rows and hold GLOBAL indices. Counts st.knn_blocks / knn_allreduces / knn_blocks_filtered.
+struct Storage;
+void nearest_neighbors_sharded(Storage &st, const double *d_pts, uint32_t ld, uint64_t begin, uint64_t n_local, uint64_t n, uint32_t d,
+                               uint32_t k, int kind, uint32_t *indices, double *distances);
 // knn_metric_host.cpp
+void host_nearest_neighbors_query(const double *queries, uint64_t n_q, const double *points, uint64_t n_p, uint32_t d, uint32_t k, int kind,
+                                  bool include_self, uint32_t *indices, double *distances);
 void host_nearest_neighbors(const double *data, uint64_t n, uint32_t d, uint32_t k, int kind, uint32_t *indices, double *distances);
 void host_distance(int kind, const double *x, const double *y, uint32_t d, double *key, double *dist);
 void host_metric_rows(int kind, const double *data, uint64_t n, uint32_t d, double *c, double *s, double *z);

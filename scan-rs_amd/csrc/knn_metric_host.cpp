@@ -40,11 +40,11 @@ inline double dot(const double *x, const double *y, uint32_t d) {
     for (uint32_t j = 0; j < d; j++) s = s + x[j] * y[j];
     return s;
 }
-void refuse_not_finite(const double *data, uint64_t n, uint32_t d) {
+void refuse_not_finite(const double *data, uint64_t n, uint32_t d, const char *what) {
     for (uint64_t r = 0; r < n; r++)
         for (uint32_t j = 0; j < d; j++)
             if (!std::isfinite(data[r * d + j]))
-                fail(SCANRS_ERR_ARGUMENT, "nearest_neighbors: row %llu of the data holds a coordinate that is not finite", (unsigned long long)r);
+                fail(SCANRS_ERR_ARGUMENT, "nearest_neighbors: row %llu of the %s holds a coordinate that is not finite", (unsigned long long)r, what);
 }
 
 } // namespace
@@ -65,26 +65,35 @@ void host_metric_rows(int kind, const double *data, uint64_t n, uint32_t d, doub
     for (uint64_t r = 0; r < n; r++) s[r] = prepare_row(kind, data + r * d, d, c + r * d, z ? z + r * d : nullptr);
 }
 
-void host_nearest_neighbors(const double *data, uint64_t n, uint32_t d, uint32_t k, int kind, uint32_t *indices, double *distances) {
-    nearest_neighbors_check_args(n, d, d, k, kind, false);
-    if (k == 0 || n == 0) return;
-    refuse_not_finite(data, n, d);
-    std::vector<double> c, s;
-    const double *rows = data;
+namespace {
+
+// every query row against every point row, the point whose index is the query's row number left out when `skip`; both finite
+void host_search(const double *queries, uint64_t n_q, const double *points, uint64_t n_p, uint32_t d, uint32_t k, int kind, bool skip,
+                 uint32_t *indices, double *distances) {
+    std::vector<double> cq, sq, cp, sp;
+    const double *qrows = queries, *prows = points;
+    const bool same = queries == points && n_q == n_p;
     if (kind != EUCLIDEAN) {
-        c.resize(n * d);
-        s.resize(n);
-        host_metric_rows(kind, data, n, d, c.data(), s.data(), nullptr);
-        rows = c.data();
+        cp.resize(n_p * d);
+        sp.resize(n_p);
+        host_metric_rows(kind, points, n_p, d, cp.data(), sp.data(), nullptr);
+        prows = cp.data();
+        if (!same) {
+            cq.resize(n_q * d);
+            sq.resize(n_q);
+            host_metric_rows(kind, queries, n_q, d, cq.data(), sq.data(), nullptr);
+        }
+        qrows = same ? cp.data() : cq.data();
     }
+    const double *s_q = same ? sp.data() : sq.data(), *s_p = sp.data();
     auto search = [&](uint64_t q) {
         uint32_t *bi = indices + q * k;
         double *bd = distances + q * k; // the rank key while the list is built (squared distance, or sqrt(D))
         uint32_t have = 0;
-        for (uint64_t p = 0; p < n; p++) {
-            if (p == q) continue; // query.idx != idx, knn.rs:155
-            const double key = kind == EUCLIDEAN ? sq_dist(rows + q * d, rows + p * d, d)
-                                                 : std::sqrt(pair_value(s[q], s[p], dot(rows + q * d, rows + p * d, d)));
+        for (uint64_t p = 0; p < n_p; p++) {
+            if (skip && p == q) continue; // query.idx != idx, knn.rs:155
+            const double key = kind == EUCLIDEAN ? sq_dist(qrows + q * d, prows + p * d, d)
+                                                 : std::sqrt(pair_value(s_q[q], s_p[p], dot(qrows + q * d, prows + p * d, d)));
             if (have == k && !(key < bd[k - 1])) continue;
             // sorted insertion; equal keys stay in index order because candidates arrive in index order
             uint32_t pos = have < k ? have : k - 1u;
@@ -103,11 +112,11 @@ void host_nearest_neighbors(const double *data, uint64_t n, uint32_t d, uint32_t
             bd[i] = INFINITY;
         }
     };
-    int T = (int)std::min<uint64_t>({8, std::max(1u, std::thread::hardware_concurrency()), n * n * d / (1u << 22) + 1});
+    int T = (int)std::min<uint64_t>({8, std::max(1u, std::thread::hardware_concurrency()), n_q * n_p * d / (1u << 22) + 1});
     HostTeam *team = T > 1 ? HostTeam::acquire(T) : nullptr;
     if (!team) T = 1;
     auto part = [&](int t) {
-        for (uint64_t q = (uint64_t)t; q < n; q += (uint64_t)T) search(q);
+        for (uint64_t q = (uint64_t)t; q < n_q; q += (uint64_t)T) search(q);
     };
     if (team) team->start(T, part);
     part(0);
@@ -116,5 +125,25 @@ void host_nearest_neighbors(const double *data, uint64_t n, uint32_t d, uint32_t
         team->release();
     }
 }
+
+} // namespace
+
+void host_nearest_neighbors(const double *data, uint64_t n, uint32_t d, uint32_t k, int kind, uint32_t *indices, double *distances) {
+    nearest_neighbors_check_args(n, d, d, k, kind, false);
+    if (k == 0 || n == 0) return;
+    refuse_not_finite(data, n, d, "data");
+    host_search(data, n, data, n, d, k, kind, true, indices, distances);
+}
+
+void host_nearest_neighbors_query(const double *queries, uint64_t n_q, const double *points, uint64_t n_p, uint32_t d, uint32_t k, int kind,
+                                  bool include_self, uint32_t *indices, double *distances) {
+    nearest_neighbors_check_args(n_p, d, d, k, kind, false);
+    nearest_neighbors_check_args(n_q, d, d, k, kind, false);
+    if (k == 0 || n_q == 0) return;
+    refuse_not_finite(queries, n_q, d, "queries");
+    refuse_not_finite(points, n_p, d, "points");
+    host_search(queries, n_q, points, n_p, d, k, kind, !include_self, indices, distances);
+}
+
 
 } // namespace scanrs

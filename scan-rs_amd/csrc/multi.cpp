@@ -771,6 +771,33 @@ int scanrs_multi_knn(scanrs_multi *mm, const double *points, uint32_t ld, uint32
     });
 }
 
+// scanrs_nearest_neighbors_sharded on every shard at once (knn.rs:112-166): the conventions of scanrs_multi_knn, points ==
+// NULL included.
+int scanrs_multi_nearest_neighbors(scanrs_multi *mm, const double *points, uint32_t ld, uint32_t d, uint32_t k, int distance_type,
+                                   uint32_t *indices, double *distances) {
+    if (!mm) return bad_argument("null handle");
+    const uint64_t cells = mm->bounds.back();
+    if (cells && k && (!indices || !distances)) return bad_argument("null argument");
+    const int transposed = mm->storage == SCANRS_CSR;
+    return collective(mm, transposed, nullptr, [&](size_t i, scanrs_mat *h, const scanrs_snoop *, ShardOutputs &) {
+        const uint64_t lo = mm->bounds[i], n_loc = mm->bounds[i + 1] - lo;
+        uint32_t *o = indices ? indices + lo * k : nullptr;
+        double *od = distances ? distances + lo * k : nullptr;
+        if (points) return scanrs_nearest_neighbors_sharded(h, points, 0, ld, d, k, distance_type, o, od);
+        const double *du = nullptr, *dv = nullptr;
+        uint32_t ldu = 0, ldv = 0, kk = 0;
+        if (const int rc = scanrs_pca_result_device(mm->shards[i], &du, &ldu, &dv, &ldv, &kk)) return rc; // "no PCA result on this handle yet"
+        const Storage::PcaDev &r = mm->shards[i]->st->pca_dev;
+        const uint64_t rows = transposed ? r.rows_u : r.rows_v;
+        if (rows != n_loc) {
+            set_error("multi_nearest_neighbors: the factor along the sharded dimension is not kept per shard (%llu rows on the device for %llu cells): pass the scores as a host array",
+                      (unsigned long long)rows, (unsigned long long)n_loc);
+            return (int)SCANRS_ERR_ARGUMENT;
+        }
+        return scanrs_nearest_neighbors_sharded(h, transposed ? du : dv, 1, transposed ? ldu : ldv, kk, k, distance_type, o, od);
+    });
+}
+
 // ---- select_rows / select_cols / partition_on_thresholds over the shards -------------------------------------------------
 // The collective entry points of the handle (scanrs_mat_*_sharded) on every shard at once. Every result is a new scanrs_multi on the
 // same devices with as many shards, the ranges its shards ended up with (nothing is rebalanced), and a group and communicators of its

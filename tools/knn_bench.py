@@ -2,10 +2,12 @@
 (bf16 MFMA filter + exact f64 rerank) against the exhaustive f64 kernel (global option "knn_exhaustive"), results compared.
 
     python tools/knn_bench.py N D K [both] [--shards S[,S...]] [--block-rows R]
-    python tools/knn_bench.py N D K --metric euclidean|pearson|cosine
+    python tools/knn_bench.py N D K --metric euclidean|pearson|cosine [--shards S[,S...]] [--block-rows R]
 
 --metric: nearest_neighbors (umap-rs knn.rs:112-166) on the same points instead: the route, the filter rounds with their
-candidates per query, and the time of the call; up to 20000 points the result is compared with the host twin bit for bit.
+candidates per query, and the time of the call; up to 20000 points the result is compared with the host twin bit for bit. With
+--shards also MultiMat.nearest_neighbors on S shards of device 0: time, blocks, blocks searched through the filter per shard,
+exchange steps, communicator bytes, shard 0's device time by scope, and the bit comparison with the unsharded call.
 
 --shards: the same points through a MultiMat whose S shards share device 0: time per call, the blocks and exchange
 steps, the bytes that went through a shard's communicator, the candidates per query of the last block searched, the share of shard
@@ -48,6 +50,29 @@ if args.metric:
     if n <= 20000:
         hi, hd = sa.host_nearest_neighbors(v, k, args.metric)
         print("equals the host twin:", bool(np.array_equal(idx, hi) and np.array_equal(dist.view(np.uint64), hd.view(np.uint64))))
+    if args.block_rows:
+        sa.set_global_option("knn_block_rows", args.block_rows)
+    for shards in [int(x) for x in args.shards.split(",") if x]:  # the same call through a MultiMat whose shards share device 0 (§7q)
+        mm = sa.MultiMat(1, n, sa.CSC, np.arange(n + 1, dtype=np.uint64), np.zeros(n, dtype=np.uint32), np.ones(n, dtype=np.uint32), shards,
+                         devices=[0] * shards)
+        before = mm.comm_info(0)
+        mm.profile_enable(True)
+        t0 = time.perf_counter()
+        sidx, sdist = mm.nearest_neighbors(k, v, args.metric)
+        dt = time.perf_counter() - t0
+        prof = {name: c["total_ms"] for name, c in mm.profile_get(0).items()}
+        after = mm.comm_info(0)
+        total = sum(prof.values()) or 1.0
+        share = ", ".join(f"{name} {prof.get(name, 0.0):.1f} ms ({100.0 * prof.get(name, 0.0) / total:.0f} %)"
+                          for name in ("allreduce_u64", "knn_search", "knn_merge"))
+        equal = bool(np.array_equal(sidx, idx) and np.array_equal(sdist.view(np.uint64), dist.view(np.uint64)))
+        print(f"nearest_neighbors[{args.metric}, sharded x{shards}] n={n} d={d} k={k}: {dt*1e3:.1f} ms incl. PCIe of the points, {n/dt:.0f} cells/s; "
+              f"knn_blocks {mm.counter('knn_blocks')}, knn_blocks_filtered {[mm.counter('knn_blocks_filtered', shard=i) for i in range(shards)]}, "
+              f"knn_allreduces {mm.counter('knn_allreduces')}, "
+              f"communicator of shard 0: {after['allreduce_calls'] - before['allreduce_calls']} all-reduces, "
+              f"{(after['allreduce_bytes'] - before['allreduce_bytes']) / 2**20:.1f} MiB; "
+              f"shard 0 device time: {share}; equals the unsharded call in indices and distance bits: {equal}", flush=True)
+        mm.close()
     sys.exit(0)
 res = {}
 for mode in (["filter", "exhaustive"] if also_exhaustive else ["filter"]):
