@@ -818,6 +818,8 @@ int scanrs_mat_set_option(scanrs_mat *m, const char *key, double value);
  * "export_encode_us" = on a shard of a scanrs_multi, the last scanrs_multi_to_adaptive: the wall clock of the plan (the transposed
  * copies, their indptr to the host and the host plan: one phase, the same on every shard; 0 for SCANRS_EXPORT_STORED) and of the
  * shard's own thread in the pull of its slab (0 for STORED) and in encode + download.
+ * "transpose_route" = the sort the handle's transposed copy was built through (scanrs_host_transpose_plan gives the same decision
+ * on the host): 0 no transposed copy built yet, or one without nonzeros; 1 one packed 64-bit key per nonzero; 2 the pair sort.
  * The route of the LAST sparse product A X on this handle (host-side stores, overwritten by every product; a solver's last pass):
  * "spmm_route" = its kernel family, one of SCANRS_SPMM_* below; "spmm_form" = the form within the family -
  *   tiles:               bit 0 dense records (0: fixed positions), bit 1 unit mode (0: the weighted kernel), bits 2-3 where a
@@ -1448,6 +1450,12 @@ int scanrs_host_spmm_route(const double *options, uint64_t n_outer, uint64_t n_i
  * not positive. */
 int scanrs_host_bk_plan(const double *colmax, uint64_t n, uint32_t b, uint32_t n_iter, double reuse_cmax, int coef_valid, uint64_t *out,
                         double *limit, double *cmax_dense, uint32_t *direct);
+/* Which sort the transposed copy of a matrix is built through (csrc/transpose_plan.hpp, the source copy_build.hip decides by), on the
+ * host: n_outer x n_inner are the dimensions of the copy that is transposed, max_value its largest stored count (0: not known, the
+ * count takes 32 bits). ib / ob / cb: the bits that hold 0 .. n_inner - 1, 0 .. n_outer - 1 and 0 .. max_value (at least 1 each);
+ * route: 1 (one packed 64-bit key per nonzero) when ib + ob + cb <= 64, else 2 (a u32 key with a u64 value). The counter
+ * "transpose_route" of a handle gives the route a build took. Refused (SCANRS_ERR_SHAPE): a dimension beyond 2^32 - 1. */
+int scanrs_host_transpose_plan(uint64_t n_outer, uint64_t n_inner, uint32_t max_value, int *route, uint32_t *ib, uint32_t *ob, uint32_t *cb);
 
 /* ---- 10x HDF5 ingestion (hdf5-io/src/matrix.rs, analysis.rs). Host-side; no device needed.
  * The files are parsed by the library's own reader (csrc/h5lite.cpp) — no libhdf5 dependency. Failures are

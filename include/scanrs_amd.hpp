@@ -1434,6 +1434,16 @@ inline BkPlan host_bk_plan(const std::vector<double> &colmax, uint32_t b, uint32
     p.direct.resize((size_t)out[3]);
     return p;
 }
+// which sort the transposed copy of an n_outer x n_inner copy with the largest count max_value is built through (counter "transpose_route")
+struct TransposePlan {
+    int route = 0; // 1 packed 64-bit key, 2 pair sort
+    uint32_t ib = 0, ob = 0, cb = 0;
+};
+inline TransposePlan host_transpose_plan(uint64_t n_outer, uint64_t n_inner, uint32_t max_value) {
+    TransposePlan p;
+    check(scanrs_host_transpose_plan(n_outer, n_inner, max_value, &p.route, &p.ib, &p.ob, &p.cb));
+    return p;
+}
 
 namespace mtx {
 // scan_rs::mtx::load_mtx (scan-rs/src/mtx.rs:10-51): the CSR arrays; `.to_device()` is the AdaptiveMat the reference returns

@@ -1729,6 +1729,20 @@ def host_bk_plan(colmax, b: int, n_iter: int, reuse_cmax: float = 1e5, coef_vali
                 cmax_dense=float(dense.value))
 
 
+TRANSPOSE_NONE, TRANSPOSE_PACKED_KEY, TRANSPOSE_PAIR_SORT = 0, 1, 2  # counter "transpose_route", host_transpose_plan
+
+
+def host_transpose_plan(n_outer: int, n_inner: int, max_value: int):
+    """Which sort the transposed copy of an n_outer x n_inner copy is built through (`scanrs_host_transpose_plan`;
+    scan-rs_amd/csrc/transpose_plan.hpp, the source copy_build.hip decides by). `max_value`: the largest stored count, 0 = not known.
+    Returns (route, ib, ob, cb): TRANSPOSE_PACKED_KEY when the bits of inner index, outer id and count sum to at most 64, else
+    TRANSPOSE_PAIR_SORT; `AdaptiveMat.counter("transpose_route")` is the route a build took."""
+    route, ib, ob, cb = ctypes.c_int(), ctypes.c_uint32(), ctypes.c_uint32(), ctypes.c_uint32()
+    _check(_lib.scanrs_host_transpose_plan(ctypes.c_uint64(int(n_outer)), ctypes.c_uint64(int(n_inner)), ctypes.c_uint32(int(max_value)),
+                                           ctypes.byref(route), ctypes.byref(ib), ctypes.byref(ob), ctypes.byref(cb)))
+    return int(route.value), int(ib.value), int(ob.value), int(cb.value)
+
+
 def knn_device(d_points: int, n: int, ld: int, d: int, k: int):
     """`nn::knn` on scores that already live in device memory (e.g. PcaResultDevice.d_v / ld_v): (n x k) u32 host array."""
     out = np.zeros((n, k), dtype=np.uint32)
@@ -2034,7 +2048,7 @@ EXPORTED_SYMBOLS = [
     "scanrs_multi_shape", "scanrs_multi_to_csmat", "scanrs_multi_select_rows", "scanrs_multi_select_cols", "scanrs_multi_partition_on_thresholds",
     "scanrs_mat_to_adaptive", "scanrs_mat_to_adaptive_major", "scanrs_multi_to_adaptive", "scanrs_adaptive_export_multi_info", "scanrs_host_plan_export",
     "scanrs_adaptive_export_info", "scanrs_adaptive_export_vecs", "scanrs_adaptive_export_free",
-    "scanrs_host_choose_storage", "scanrs_host_col_moments_plan", "scanrs_host_spmm_route", "scanrs_host_bk_plan",
+    "scanrs_host_choose_storage", "scanrs_host_col_moments_plan", "scanrs_host_spmm_route", "scanrs_host_bk_plan", "scanrs_host_transpose_plan",
     "scanrs_mat_sum_rows_u64", "scanrs_mat_sum_rows_f64", "scanrs_mat_sum_cols_u64", "scanrs_mat_sum_cols_f64", "scanrs_mat_sum_rows_dual_u64",
     "scanrs_mat_sum_rows_dual_f64", "scanrs_mat_mean_rows", "scanrs_mat_mean_var_rows", "scanrs_mat_var_axis",
     "scanrs_mat_sum_rows_u64_sharded", "scanrs_mat_sum_rows_f64_sharded", "scanrs_mat_sum_cols_u64_sharded", "scanrs_mat_sum_cols_f64_sharded",

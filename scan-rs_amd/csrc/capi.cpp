@@ -10,6 +10,7 @@
 #include "bk_plan.hpp"
 #include "knn_metric.hpp"
 #include "spmm_route.hpp"
+#include "transpose_plan.hpp"
 #include "shard_exchange.hpp"
 
 namespace scanrs {
@@ -1369,6 +1370,14 @@ int scanrs_host_bk_plan(const double *colmax, uint64_t n, uint32_t b, uint32_t n
         std::copy(p.direct.begin(), p.direct.end(), direct);
     });
 }
+int scanrs_host_transpose_plan(uint64_t n_outer, uint64_t n_inner, uint32_t max_value, int *route, uint32_t *ib, uint32_t *ob, uint32_t *cb) {
+    return guard([&] {
+        if (!route || !ib || !ob || !cb) fail(SCANRS_ERR_ARGUMENT, "null argument");
+        if (n_outer > 0xFFFFFFFFull || n_inner > 0xFFFFFFFFull) fail(SCANRS_ERR_SHAPE, "dimensions must fit in u32 (AdaptiveVec limit)");
+        const TransposePlan p = transpose_plan(n_outer, n_inner, max_value);
+        *route = (int)p.route, *ib = p.ib, *ob = p.ob, *cb = p.cb;
+    });
+}
 int scanrs_debug_knn_filter(const double *queries, uint64_t n_q, const double *points, uint64_t n_p, uint32_t d, const double *tau,
                             uint64_t stride, uint32_t *cnt, uint32_t *cand) {
     return guard([&] {
@@ -1712,6 +1721,8 @@ int scanrs_mat_get_counter(scanrs_mat *m, const char *key, uint64_t *value) {
             *value = m->st->spmm.form;
         else if (k == "spmm_chunks") // ... and its column chunks, SCANRS_SPMM_SLIVER set when a last narrow one went to the plain gather
             *value = m->st->spmm.chunks;
+        else if (k == "transpose_route") // the sort the handle's transposed copy was built through (transpose_plan.hpp): 0 none built or no nonzeros, 1 packed key, 2 pair sort
+            m->st->side_join_if(&m->st->other, false), *value = m->st->transpose_route; // (a helper thread may be building the copy right now)
         else if (k == "partition_rounds") // rounds of the last scanrs_mat_partition_on_thresholds[_sharded] on this handle
             *value = m->st->partition_rounds;
         else if (k == "partition_allreduces") // ... and its exchange steps (an unsharded handle: 0)

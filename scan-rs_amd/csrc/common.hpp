@@ -400,6 +400,7 @@ struct Storage {
     int tile_overlap = 1;                 // hybrid product: 1 = the overflow gather runs beside the tile kernel (own stream); 0 = after it (measurement)
     int panel_precision = 0;              // 0: f64 panels (default); 1: gathered panels rounded to f32, f64 sums (opt-in)
     uint64_t partition_allreduces = 0;    // exchange steps of the last scanrs_mat_partition_on_thresholds_sharded on this handle (an unsharded one: 0)
+    uint64_t transpose_route = 0;         // the sort the last build_transposed_copy on this handle ran through: TransposeRoute of transpose_plan.hpp, 0 when none was built or it had no nonzeros (scanrs_mat_get_counter)
     uint64_t partition_rounds = 0;        // rounds of the last scanrs_mat_partition_on_thresholds on this handle, the final one that changes nothing included (scanrs_mat_get_counter)
     uint64_t de_shard_tests = 0, de_shard_allreduces = 0; // the last DE call on this handle: tests this rank launched on the device, exchange steps (scanrs_mat_get_counter)
     uint64_t de_pairs_passes = 0, de_pairs_literal = 0; // the last scanrs_sseq_de_pairs on this handle: passes over the nonzeros, pairs on the literal route (scanrs_mat_get_counter)

@@ -2,6 +2,7 @@
 // of unsorted or zero-holding input, and the transposed copy (key pack / unpack around rocprim's radix sort).
 #include "common.hpp"
 #include "launch_util.hpp"
+#include "transpose_plan.hpp"
 
 #include <algorithm>
 #include <rocprim/rocprim.hpp>
@@ -308,25 +309,23 @@ void build_transposed_copy(Storage &st, const SparseCopy &src, SparseCopy &dst, 
     if (nnz == 0) {
         SCANRS_HIP(hipMemsetAsync(dst.indptr.p, 0, (dst.n_outer + 1) * 8, s));
         dst.build_items(s);
+        st.transpose_route = (uint64_t)TRANSPOSE_NONE; // nothing to sort
         return;
     }
-    auto bits_for = [](uint64_t maxv) { // bits that hold 0 .. maxv
-        uint32_t b = 1;
-        while (b < 64 && (maxv >> b) != 0) b++;
-        return b;
-    };
-    const uint32_t ib = bits_for(src.n_inner ? src.n_inner - 1 : 0), ob = bits_for(src.n_outer ? src.n_outer - 1 : 0);
-    const uint32_t cb = src.max_value ? bits_for(src.max_value) : 32u; // max_value is known for every copy that went through validation
+    // which sort: transpose_plan.hpp (max_value is known for every copy that went through validation; an adopted copy carries a bound)
+    const TransposePlan plan = transpose_plan(src.n_outer, src.n_inner, src.max_value);
+    const uint32_t ob = plan.ob, cb = plan.cb;
     dst.max_value = src.max_value;
-    if (ib + ob + cb <= 64u) {
-        // one packed 64-bit key per nonzero, sorted on its inner-index bits (see pack_key_kernel)
+    st.transpose_route = (uint64_t)plan.route;
+    if (plan.route == TRANSPOSE_PACKED_KEY) {
+        // one packed 64-bit key per nonzero, sorted on its inner-index bits (see pack_key_kernel; a key of all 64 bits: transpose_plan.hpp)
         DevBuf<unsigned long long> ka(nnz), kb2(nnz);
         hipLaunchKernelGGL(pack_key_kernel, dim3((src.n_items + 3u) / 4u), dim3(256), 0, s, src.items.p, src.n_items, src.indices.p, src.values.p, ob, cb, ka.p);
         rocprim::double_buffer<unsigned long long> kb(ka.p, kb2.p);
         size_t tmp_bytes = 0;
-        SCANRS_HIP(rocprim::radix_sort_keys(nullptr, tmp_bytes, kb, (size_t)nnz, ob + cb, ob + cb + ib, s));
+        SCANRS_HIP(rocprim::radix_sort_keys(nullptr, tmp_bytes, kb, (size_t)nnz, plan.sort_begin, plan.sort_end, s));
         DevBuf<char> tmp(std::max<size_t>(tmp_bytes, 16));
-        SCANRS_HIP(rocprim::radix_sort_keys(tmp.p, tmp_bytes, kb, (size_t)nnz, ob + cb, ob + cb + ib, s));
+        SCANRS_HIP(rocprim::radix_sort_keys(tmp.p, tmp_bytes, kb, (size_t)nnz, plan.sort_begin, plan.sort_end, s));
         hipLaunchKernelGGL(unpack_key_kernel, grid1(nnz, 256), dim3(256), 0, s, kb.current(), nnz, ob, cb, dst.indices.p, dst.values.p);
         hipLaunchKernelGGL(lower_bound_key_kernel, grid1(dst.n_outer + 1, 256), dim3(256), 0, s, kb.current(), nnz, dst.n_outer, ob + cb, dst.indptr.p);
         SCANRS_HIP(hipGetLastError());
