@@ -817,7 +817,10 @@ int scanrs_mat_set_option(scanrs_mat *m, const char *key, double value);
  * the same on every shard) and of the shard's own thread in pull and finish. "export_plan_us" / "export_pull_us" /
  * "export_encode_us" = on a shard of a scanrs_multi, the last scanrs_multi_to_adaptive: the wall clock of the plan (the transposed
  * copies, their indptr to the host and the host plan: one phase, the same on every shard; 0 for SCANRS_EXPORT_STORED) and of the
- * shard's own thread in the pull of its slab (0 for STORED) and in encode + download.
+ * shard's own thread in the pull of its slab (0 for STORED) and in encode + download. "reshard_upload_us" / "reshard_count_us" /
+ * "reshard_split_us" / "reshard_exchange_us" / "reshard_transpose_us" = on a shard made by an inner-sharding constructor
+ * (scanrs_multi_create_inner and kin), the wall clock of its thread in the phases upload, count (validation and the histogram),
+ * split, exchange and transpose.
  * "transpose_route" = the sort the handle's transposed copy was built through (scanrs_host_transpose_plan gives the same decision
  * on the host): 0 no transposed copy built yet, or one without nonzeros; 1 one packed 64-bit key per nonzero; 2 the pair sort.
  * The route of the LAST sparse product A X on this handle (host-side stores, overwritten by every product; a solver's last pass):
@@ -860,6 +863,8 @@ int scanrs_mat_get_counter(scanrs_mat *m, const char *key, uint64_t *value);
  *                                  reused or freed before the process exits. The handle must then be freed (its queued
  *                                  work never finished); start over in a fresh process — a process whose device stopped
  *                                  answering cannot be repaired from inside, and must not exec() another program either.
+ *   (a value that is not finite is refused; "h5_threads", "eig_threads" and "knn_block_rows" below 1, "knn_ratio" below 2 and
+ *   "knn_filter_min_points" below 0 are raised to that bound)
  *   "device_cache_fraction" (0.5)  device blocks of 1 MB and more that the library releases are kept for its next allocation of about
  *                                  their size, up to this share of the device's memory, instead of going back to the driver (VRAM
  *                                  that was just freed is scrubbed in the background; an allocation that lands on it waits:
@@ -1423,9 +1428,10 @@ int scanrs_host_col_moments_plan(uint32_t max_count, uint32_t n_links, const int
                                  int *e2);
 
 /* ---- the route of a sparse product (host only, no device): csrc/spmm_route.hpp, the source launch_spmm_f64 decides by --------------
- * options: 18 values in this order - spmm_path, panel precision, "tile_auto", "tile_k", "tile_s", "tile_t", "tile_b", "tile_ku",
+ * options: 18 values in this order - "spmm_path" (scanrs_mat_set_spmm_path), "panel_precision" (scanrs_mat_set_panel_precision), "tile_auto", "tile_k", "tile_s", "tile_t", "tile_b", "tile_ku",
  * "tile_dense", "tile_builder", "blocked_min_nnz", "slice_walk", "spmv_lds", "spmv_row_table", "spmm_order", "materialize",
- * "tile_wtab", "tile_fold"; n_outer, n_inner, nnz: the copy the product walks; l columns of a panel with leading dimension ldx; the map
+ * "tile_wtab", "tile_fold", each checked like the option of its name ("blocked_min_nnz", default 2^22 and no key of
+ * scanrs_mat_set_option: a whole number in [0, 2^63)) - a value an option would refuse returns SCANRS_ERR_ARGUMENT; n_outer, n_inner, nnz: the copy the product walks; l columns of a panel with leading dimension ldx; the map
  * as seen from that copy: kinds[i] = 1 ScaleAxis, 2 / 3 / 4 ln / log2 / log10 of 1 + x, 5 square, 6 / 7 the binomial deviance / Pearson
  * residuals, a_outer[i] != 0 when link i indexes its array by the outer position. flags stand for the two steps that need a device:
  * SCANRS_SPMM_TILES_AVAILABLE = a tile layout exists or was built (auto path: the size, the free memory and the overflow limit
@@ -1436,6 +1442,23 @@ int scanrs_host_col_moments_plan(uint32_t max_count, uint32_t n_links, const int
 #define SCANRS_SPMM_NO_VALUES_ROOM 2u
 int scanrs_host_spmm_route(const double *options, uint64_t n_outer, uint64_t n_inner, uint64_t nnz, uint32_t l, uint32_t ldx,
                            uint32_t n_links, const int *kinds, const int *a_outer, uint32_t flags, uint64_t *out);
+
+/* ---- the tables of options and counters (host only, no device): csrc/options.cpp, the source the setters and the getter decide by
+ * scanrs_host_option_info: row `index` of the options of a handle (scope 0) or of the process (scope 1); SCANRS_ERR_ARGUMENT past
+ * the end. name: the key; dflt: the default, in the key's own unit; lo, hi: the bounds (of a flag: 0 and 1; hi may be infinite);
+ * flags: SCANRS_OPTION_OPEN_LO = lo itself is refused, SCANRS_OPTION_SETTABLE = a key of scanrs_mat_set_option /
+ * scanrs_set_global_option (the three rows without it are read by the route decision and set elsewhere or never), and from bit
+ * SCANRS_OPTION_ROUTE_SHIFT on the option's position + 1 in the `options` array of scanrs_host_spmm_route (0: not in it).
+ * scanrs_host_option_parse: what the setter of that scope would store for `value` under the key `name` (bytes for the keys in KB,
+ * 0 / 1 for a flag, the clamped number for a global option that clamps) - or the setter's refusal, SCANRS_ERR_ARGUMENT: an unknown
+ * or unsettable key, a value that is not finite, outside the bounds or not whole where the key takes whole numbers. Nothing is stored.
+ * scanrs_host_counter_name: key `index` of scanrs_mat_get_counter; SCANRS_ERR_ARGUMENT past the end. */
+#define SCANRS_OPTION_OPEN_LO 1u
+#define SCANRS_OPTION_SETTABLE 2u
+#define SCANRS_OPTION_ROUTE_SHIFT 8
+int scanrs_host_option_info(int scope, uint32_t index, const char **name, double *dflt, double *lo, double *hi, uint32_t *flags);
+int scanrs_host_option_parse(int scope, const char *name, double value, double *stored);
+int scanrs_host_counter_name(uint32_t index, const char **name);
 
 /* ---- the projection plan of svd_bk (host only, no device): csrc/bk_plan.hpp, the source the solver decides by ---------------------
  * svd_bk forms its projection as T' = (op(A) K) C from the half-products of its iterations; a column of Q whose coefficient column

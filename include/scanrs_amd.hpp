@@ -1444,6 +1444,37 @@ inline TransposePlan host_transpose_plan(uint64_t n_outer, uint64_t n_inner, uin
     check(scanrs_host_transpose_plan(n_outer, n_inner, max_value, &p.route, &p.ib, &p.ob, &p.cb));
     return p;
 }
+// the tables of options (scope 0: of a handle, 1: of the process) and of counters, as the library holds them
+struct OptionInfo {
+    std::string name;
+    double dflt = 0.0, lo = 0.0, hi = 0.0;
+    bool open_lo = false, settable = false;
+    uint32_t route_position = 0; // position + 1 in the options array of scanrs_host_spmm_route, 0: not in it
+};
+inline std::vector<OptionInfo> option_info(int scope) {
+    std::vector<OptionInfo> all;
+    const char *name = nullptr;
+    OptionInfo o;
+    uint32_t flags = 0;
+    for (uint32_t i = 0; scanrs_host_option_info(scope, i, &name, &o.dflt, &o.lo, &o.hi, &flags) == SCANRS_OK; i++) {
+        o.name = name, o.open_lo = (flags & SCANRS_OPTION_OPEN_LO) != 0, o.settable = (flags & SCANRS_OPTION_SETTABLE) != 0;
+        o.route_position = flags >> SCANRS_OPTION_ROUTE_SHIFT;
+        all.push_back(o);
+    }
+    return all;
+}
+// what the setter of that scope would store for `value` under `name`; throws where the setter refuses
+inline double host_option_parse(int scope, const std::string &name, double value) {
+    double stored = 0.0;
+    check(scanrs_host_option_parse(scope, name.c_str(), value, &stored));
+    return stored;
+}
+inline std::vector<std::string> counter_names() {
+    std::vector<std::string> all;
+    const char *name = nullptr;
+    for (uint32_t i = 0; scanrs_host_counter_name(i, &name) == SCANRS_OK; i++) all.push_back(name);
+    return all;
+}
 
 namespace mtx {
 // scan_rs::mtx::load_mtx (scan-rs/src/mtx.rs:10-51): the CSR arrays; `.to_device()` is the AdaptiveMat the reference returns

@@ -1691,9 +1691,42 @@ def host_col_moments_plan(max_count: int, links, n_outer: int, n_inner: int, n_w
 # kernel families of a sparse product (counter "spmm_route", host_spmm_route; SCANRS_SPMM_* of scanrs_amd.h)
 SPMM_TILES, SPMM_GATHER2D, SPMM_GATHER2D_F32, SPMM_SLICE_WALK, SPMM_SPMV2D, SPMM_SPMV_LDS, SPMM_SPMV, SPMM_GATHER = range(1, 9)
 SPMM_SLIVER = 1 << 16
-SPMM_ROUTE_OPTIONS = ("spmm_path", "panel_precision", "tile_auto", "tile_k", "tile_s", "tile_t", "tile_b", "tile_ku", "tile_dense", "tile_builder",
-                      "blocked_min_nnz", "slice_walk", "spmv_lds", "spmv_row_table", "spmm_order", "materialize", "tile_wtab", "tile_fold")
-_SPMM_ROUTE_DEFAULTS = (0, 0, 1, 2, 32, 48, 4, 1, 1, 1, 1 << 22, 1, 1, 1, 1, 1, 1, 1)
+
+
+def option_info(scope: int = 0):
+    """The library's table of options (`scanrs_host_option_info`): of a handle (scope 0) or of the process (scope 1). One dict per
+    key: name, default, lo, hi, open_lo, settable, route_position (position + 1 in the options array of host_spmm_route, 0: not in it)."""
+    rows, i = [], 0
+    name, d, lo, hi, flags = ctypes.c_char_p(), ctypes.c_double(), ctypes.c_double(), ctypes.c_double(), ctypes.c_uint32()
+    if scope not in (0, 1):
+        raise ScanrsError(6, "scope must be 0 (per handle) or 1 (global)")
+    while _lib.scanrs_host_option_info(ctypes.c_int(scope), ctypes.c_uint32(i), ctypes.byref(name), ctypes.byref(d), ctypes.byref(lo), ctypes.byref(hi),
+                                       ctypes.byref(flags)) == 0:
+        rows.append(dict(name=name.value.decode(), default=d.value, lo=lo.value, hi=hi.value, open_lo=bool(flags.value & 1),
+                         settable=bool(flags.value & 2), route_position=flags.value >> 8))
+        i += 1
+    return rows
+
+
+def host_option_parse(name: str, value: float, scope: int = 0) -> float:
+    """What `set_option` (scope 0) or `set_global_option` (scope 1) would store for `value` under the key `name`, or its refusal
+    (`scanrs_host_option_parse`): the parser alone, nothing is stored."""
+    out = ctypes.c_double()
+    _check(_lib.scanrs_host_option_parse(ctypes.c_int(scope), name.encode(), ctypes.c_double(value), ctypes.byref(out)))
+    return float(out.value)
+
+
+def counter_names():
+    """The keys of `counter` (`scanrs_host_counter_name`)."""
+    names, name = [], ctypes.c_char_p()
+    while _lib.scanrs_host_counter_name(ctypes.c_uint32(len(names)), ctypes.byref(name)) == 0:
+        names.append(name.value.decode())
+    return names
+
+
+# the options host_spmm_route takes, in the order of the library's array, and their defaults
+_SPMM_ROUTE_ROWS = sorted((o for o in option_info() if o["route_position"]), key=lambda o: o["route_position"])
+SPMM_ROUTE_OPTIONS = tuple(o["name"] for o in _SPMM_ROUTE_ROWS)
 
 
 def host_spmm_route(n_outer: int, n_inner: int, nnz: int, l: int, ldx: int, links=(), tiles_available: bool = False, values_room: bool = True,
@@ -1704,7 +1737,7 @@ def host_spmm_route(n_outer: int, n_inner: int, nnz: int, l: int, ldx: int, link
     unknown = set(options) - set(SPMM_ROUTE_OPTIONS)
     if unknown:
         raise ScanrsError(6, f"unknown options {sorted(unknown)}")
-    vals = [float(options.get(k, d)) for k, d in zip(SPMM_ROUTE_OPTIONS, _SPMM_ROUTE_DEFAULTS)]
+    vals = [float(options.get(o["name"], o["default"])) for o in _SPMM_ROUTE_ROWS]
     n = len(links)
     opts = (ctypes.c_double * len(vals))(*vals)
     ka, oa = (ctypes.c_int * max(n, 1))(*[int(k) for k, _ in links]), (ctypes.c_int * max(n, 1))(*[int(bool(a)) for _, a in links])
@@ -2049,6 +2082,7 @@ EXPORTED_SYMBOLS = [
     "scanrs_mat_to_adaptive", "scanrs_mat_to_adaptive_major", "scanrs_multi_to_adaptive", "scanrs_adaptive_export_multi_info", "scanrs_host_plan_export",
     "scanrs_adaptive_export_info", "scanrs_adaptive_export_vecs", "scanrs_adaptive_export_free",
     "scanrs_host_choose_storage", "scanrs_host_col_moments_plan", "scanrs_host_spmm_route", "scanrs_host_bk_plan", "scanrs_host_transpose_plan",
+    "scanrs_host_option_info", "scanrs_host_option_parse", "scanrs_host_counter_name",
     "scanrs_mat_sum_rows_u64", "scanrs_mat_sum_rows_f64", "scanrs_mat_sum_cols_u64", "scanrs_mat_sum_cols_f64", "scanrs_mat_sum_rows_dual_u64",
     "scanrs_mat_sum_rows_dual_f64", "scanrs_mat_mean_rows", "scanrs_mat_mean_var_rows", "scanrs_mat_var_axis",
     "scanrs_mat_sum_rows_u64_sharded", "scanrs_mat_sum_rows_f64_sharded", "scanrs_mat_sum_cols_u64_sharded", "scanrs_mat_sum_cols_f64_sharded",

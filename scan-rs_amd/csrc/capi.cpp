@@ -112,7 +112,7 @@ static SparseCopy &copy_outer_view_rows(scanrs_mat *m, bool view_rows) {
 // helper then also runs beside the normalisation passes ("side_build" 0: nothing is built before a product asks for it).
 void prepare_second_orientation(scanrs_mat *m, bool transpose_second, bool solver_follows) {
     Storage &st = *m->st;
-    if (st.side || !st.side_build) return;
+    if (st.side || !st.opt.side_build) return;
     if (st.primary.nnz < (1ull << 22)) return; // small matrices: the builds take less than starting a thread
     const bool second_outer_rows = (!transpose_second) != m->transposed; // the base-matrix dimension the second product's outer vectors run over
     const bool second_is_primary = second_outer_rows == (st.storage == SCANRS_CSR);
@@ -124,7 +124,7 @@ void prepare_second_orientation(scanrs_mat *m, bool transpose_second, bool solve
     //  - the size of `primary` stands for both copies (the transposed one may not exist yet; the nonzeros are the same);
     //  - no tile_shape_ok and no tile_visits_fit: the helper's tile_layout_build_auto tests both before it builds anything;
     //  - no panel terms: the widths are the solver's.
-    const SpmmOptions o = spmm_options(st);
+    const Options &o = st.opt;
     const bool tiles_wanted = path_auto(o) && o.tile_auto && f64_panels(o) && (st.tile_hint > 0 || solver_follows) && tile_auto_size(o, st.primary.nnz);
     auto exists = [&](const SparseCopy *c) { return c == &st.primary || st.has_other; };
     // the first product's layout too (the helper builds it FIRST, alone on the device, while the caller normalizes; the transposition
@@ -477,14 +477,14 @@ static void axis_sums(scanrs_mat *m, int axis, int mode, double *d_sum, double *
     // per-outer table instead of one logarithm per nonzero) and that copy exists already; else the ordinary pass over the copy
     // whose outer vectors are the slices.
     bool done = false;
-    if (st.col_moments && mode != 0) {
+    if (st.opt.col_moments && mode != 0) {
         const bool other_outer_rows = (!outer_view_rows) != m->transposed;
         // (other_settled, not has_other: whether the helper thread has finished the transposed copy by now depends on its speed, and the
         // two passes round differently: the moments - and the PCA behind them - must not change from run to run)
         const bool exists = other_outer_rows == (st.storage == SCANRS_CSR) || st.other_settled;
         if (exists) {
             SparseCopy &co = copy_outer_view_rows(m, !outer_view_rows);
-            if (st.col_moments == 2 || co.nnz >= st.blocked_min_nnz) done = launch_col_moments(st, co, m->dev_map(!outer_view_rows), mode, d_sum, d_sumsq);
+            if (st.opt.col_moments == 2 || co.nnz >= st.opt.blocked_min_nnz) done = launch_col_moments(st, co, m->dev_map(!outer_view_rows), mode, d_sum, d_sumsq);
         }
     }
     SparseCopy &cp = done ? copy_outer_view_rows(m, !outer_view_rows) : copy_outer_view_rows(m, outer_view_rows);
@@ -1028,7 +1028,7 @@ int scanrs_normalize(scanrs_mat *m, int normalization, const uint32_t *size_fact
         stage_mark("normalize enter"); // normalize / normalize_with_size_factor, scan-rs/src/normalization.rs:46-102
         if (!m) fail(SCANRS_ERR_ARGUMENT, "null handle");
         const bool pca_next = normalization >= SCANRS_NORM_CELLRANGER && normalization <= SCANRS_NORM_LOG_TRANSFORM;
-        if (pca_next && m->st->side_build == 1) prefetch_for_pca(m); // 1: beside the normalisation passes; 2: right behind them
+        if (pca_next && m->st->opt.side_build == 1) prefetch_for_pca(m); // 1: beside the normalisation passes; 2: right behind them
         switch (normalization) {
         case SCANRS_NORM_CELLRANGER:
             log_normalize_impl(m, -1.0, OP_LOG2_1P, nullptr);
@@ -1063,7 +1063,7 @@ int scanrs_normalize(scanrs_mat *m, int normalization, const uint32_t *size_fact
         default:
             fail(SCANRS_ERR_ARGUMENT, "Normalization not recognized: %d", normalization);
         }
-        if (pca_next && m->st->side_build == 2) prefetch_for_pca(m);
+        if (pca_next && m->st->opt.side_build == 2) prefetch_for_pca(m);
     });
 }
 int scanrs_mat_target_umi(const scanrs_mat *m, double *target) {
@@ -1337,14 +1337,7 @@ int scanrs_host_spmm_route(const double *options, uint64_t n_outer, uint64_t n_i
         if (!options || !out || (n_links && (!kinds || !a_outer))) fail(SCANRS_ERR_ARGUMENT, "null argument");
         if (n_links > (uint32_t)MAX_OPS) fail(SCANRS_ERR_ARGUMENT, "spmm_route: at most %d links", MAX_OPS);
         SpmmQuery q;
-        SpmmOptions &o = q.o;
-        int i = 0;
-        o.spmm_path = (int)options[i++], o.panel_precision = (int)options[i++], o.tile_auto = (int)options[i++];
-        o.tile_k = (uint32_t)options[i++], o.tile_s = (uint32_t)options[i++], o.tile_t = (uint32_t)options[i++], o.tile_b = (uint32_t)options[i++];
-        o.tile_ku = (uint32_t)options[i++], o.tile_dense = (int)options[i++], o.tile_builder = (int)options[i++];
-        o.blocked_min_nnz = (uint64_t)options[i++];
-        o.slice_walk = (int)options[i++], o.spmv_lds = (int)options[i++], o.spmv_row_table = (int)options[i++], o.spmm_order = (int)options[i++];
-        o.materialize = (int)options[i++], o.tile_wtab = (int)options[i++], o.tile_fold = (int)options[i++];
+        options_from_route_array(options, q.o);
         q.n_outer = n_outer, q.n_inner = n_inner, q.nnz = nnz, q.l = l, q.ldx = ldx;
         q.n_links = (int)n_links;
         for (uint32_t j = 0; j < n_links; j++) q.kind[j] = kinds[j], q.a_outer[j] = a_outer[j] != 0;
@@ -1522,278 +1515,6 @@ int scanrs_mat_create_from_file(const char *path, const char *retain_feature_lik
     else
         scanrs_h5_matrix_free(h);
     return rc;
-}
-int scanrs_mat_set_spmm_path(scanrs_mat *m, int path) {
-    return guard([&] {
-        if (!m) fail(SCANRS_ERR_ARGUMENT, "null handle");
-        if (path < 0 || path > 3)
-            fail(SCANRS_ERR_ARGUMENT, "path must be 0 (auto), 1 (plain gather), 2 (L2-blocked gather) or 3 (LDS-staged tiles + gather)");
-        m->st->spmm_path = path;
-    });
-}
-static void set_sync_timeout_checked(double value) {
-    if (!(value > 0.0) || !std::isfinite(value)) fail(SCANRS_ERR_ARGUMENT, "sync_timeout_s must be a positive number of seconds");
-    set_sync_timeout_s(value);
-}
-int scanrs_set_global_option(const char *key, double value) {
-    return guard([&] {
-        if (!key) fail(SCANRS_ERR_ARGUMENT, "null key");
-        GlobalOptions &go = global_options();
-        const std::string k(key);
-        if (k == "h5_threads")
-            go.h5_threads = (int)std::max(1.0, value);
-        else if (k == "eig_threads")
-            go.eig_threads = (int)std::max(1.0, value);
-        else if (k == "knn_exhaustive")
-            go.knn_exhaustive = value != 0.0;
-        else if (k == "knn_filter_min_points")
-            go.knn_filter_min_points = (unsigned long long)std::max(0.0, value);
-        else if (k == "knn_ratio")
-            go.knn_ratio = (unsigned long long)std::max(2.0, value);
-        else if (k == "knn_block_rows")
-            go.knn_block_rows = (unsigned long long)std::max(1.0, value);
-        else if (k == "knn_stats")
-            go.knn_stats = value != 0.0;
-        else if (k == "device_cache_fraction") { // share of the device's memory that released blocks may occupy while they wait for reuse
-            if (!(value >= 0.0) || value > 1.0) fail(SCANRS_ERR_ARGUMENT, "device_cache_fraction must be in [0, 1]");
-            device_cache_set_fraction(value);
-        } else if (k == "sync_timeout_s") { // deadline of every host-side wait for the device (common.hpp, "bounded waits")
-            set_sync_timeout_checked(value);
-        } else
-            fail(SCANRS_ERR_ARGUMENT, "unknown global option '%s'", key);
-    });
-}
-int scanrs_mat_set_option(scanrs_mat *m, const char *key, double value) {
-    return guard([&] {
-        if (!m || !key) fail(SCANRS_ERR_ARGUMENT, "null handle or key");
-        Storage &st = *m->st;
-        const std::string k(key);
-        // every value arrives as a double: nothing is cast before it is known to be finite and in range (a NaN or a negative
-        // number through (uint32_t) is undefined behaviour)
-        if (!std::isfinite(value)) fail(SCANRS_ERR_ARGUMENT, "option '%s': the value must be finite", key);
-        auto as_u32 = [&](double lo, double hi) -> uint32_t {
-            if (!(value >= lo) || !(value <= hi) || value != std::floor(value)) fail(SCANRS_ERR_ARGUMENT, "option '%s' must be an integer in [%g, %g]", key, lo, hi);
-            return (uint32_t)value;
-        };
-        // the four shape options are usually set one after the other: a combination is checked as a whole when the product runs
-        // (launch_spmm_tiles / tile_layout_build refuse an unsupported shape); each value alone must be one some shape uses
-        if (k == "tile_k") {
-            st.tile_k = as_u32(2, 4);
-        } else if (k == "tile_s") {
-            const uint32_t v = as_u32(28, 32);
-            if (v != 28u && v != 32u) fail(SCANRS_ERR_ARGUMENT, "tile_s must be 28 or 32");
-            st.tile_s = v;
-        } else if (k == "tile_ku") {
-            st.tile_ku = as_u32(0, 1);
-        } else if (k == "tile_t") {
-            st.tile_t = as_u32(8, 96);
-        } else if (k == "tile_b") {
-            st.tile_b = as_u32(2, 24);
-        } else if (k == "dense_side_no_lds") {
-            st.dense_side_no_lds = value != 0.0;
-        } else if (k == "side_build") {
-            st.side_build = (int)as_u32(0, 2);
-        } else if (k == "tile_split") {
-            st.tile_split = value != 0.0;
-        } else if (k == "tile_split_x") {
-            if (!(value > 0.05) || value > 16.0) fail(SCANRS_ERR_ARGUMENT, "tile_split_x must be in (0.05, 16]");
-            st.tile_split_x = value;
-        } else if (k == "tile_split_min") {
-            if (!(value >= 0.0) || value > 16.0) fail(SCANRS_ERR_ARGUMENT, "tile_split_min must be in [0, 16]");
-            st.tile_split_min = value;
-        } else if (k == "tile_build_one_pass") {
-            st.tile_build_one_pass = value != 0.0;
-        } else if (k == "tile_weights_wide") {
-            st.tile_weights_wide = value != 0.0;
-        } else if (k == "tile_dense") {
-            st.tile_dense = value != 0.0;
-        } else if (k == "tile_sort_slots") {
-            st.tile_sort_slots = value == 2.0 ? 2 : (value != 0.0 ? 1 : 0);
-        } else if (k == "tile_wtab" || k == "tile_fold") {
-            (k == "tile_wtab" ? st.tile_wtab : st.tile_fold) = value != 0.0;
-            tile_layout_forget_weights(st.primary.tiles.get()); // (the form of the weights follows these two)
-            tile_layout_forget_weights(st.other.tiles.get());
-        } else if (k == "tile_big_list_cap") {
-            if (!(value >= 0.0) || value > 4.0e9) fail(SCANRS_ERR_ARGUMENT, "tile_big_list_cap must be in 0..4e9");
-            st.tile_big_list_cap = (uint64_t)value;
-        } else if (k == "tile_one_walk") {
-            st.tile_one_walk = value != 0.0;
-        } else if (k == "tile_emit_staged") {
-            st.tile_emit_staged = value != 0.0;
-        } else if (k == "tile_builder") {
-            st.tile_builder = value != 0.0;
-        } else if (k == "tile_build_waves") {
-            if (!(value >= 0.0) || value > 32.0) fail(SCANRS_ERR_ARGUMENT, "tile_build_waves must be in 0..32");
-            st.tile_build_waves = (uint32_t)value;
-        } else if (k == "ov_tile_kb") {
-            st.ov_tile_bytes = (size_t)as_u32(0, 4194304.0) << 10;
-        } else if (k == "tile_max_overflow") {
-            if (!(value > 0.0) || value > 1.0) fail(SCANRS_ERR_ARGUMENT, "tile_max_overflow must be in (0, 1]");
-            st.tile_max_overflow = value;
-        } else if (k == "tile_auto") {
-            st.tile_auto = value != 0.0;
-        } else if (k == "tile_overlap") {
-            st.tile_overlap = value != 0.0;
-        } else if (k == "l2_tile_kb") {
-            st.l2_tile_bytes = (size_t)as_u32(64, 4194304.0) << 10;
-        } else if (k == "spmm_order") {
-            st.spmm_order = (int)as_u32(0, 2);
-        } else if (k == "materialize") {
-            st.materialize = value != 0.0;
-        } else if (k == "hot_segment") {
-            st.hot_segment = as_u32(0, 4294967295.0);
-        } else if (k == "slice_walk") {
-            st.slice_walk = value != 0.0;
-        } else if (k == "spmv_lds") {
-            st.spmv_lds = value != 0.0;
-        } else if (k == "overlap") {
-            st.overlap = value != 0.0;
-        } else if (k == "col_moments") {
-            st.col_moments = (int)as_u32(0, 2);
-        } else if (k == "device_factor") {
-            st.device_factor = value != 0.0;
-        } else if (k == "sseq_grid_cap") {
-            st.sseq_grid_cap = as_u32(1, 16384);
-        } else if (k == "merge_fused") {
-            st.merge_fused = (int)as_u32(0, 1);
-        } else if (k == "subset_scatter") {
-            st.subset_scatter = (int)as_u32(0, 1);
-        } else if (k == "d2h_threads") {
-            st.d2h_threads = as_u32(1, 256);
-        } else if (k == "sync_timeout_s") { // process-wide (the waits have no handle): same as scanrs_set_global_option
-            set_sync_timeout_checked(value);
-        } else if (k == "tile_spare_cus") {
-            st.tile_spare_cus = value != 0.0;
-        } else if (k == "tile_poison_slack") {
-            st.tile_poison_slack = value != 0.0;
-        } else if (k == "spmv_row_table") {
-            st.spmv_row_table = value != 0.0;
-        } else if (k == "gemm_direct") {
-            st.gemm_direct = value != 0.0;
-        } else if (k == "reuse_cmax") {
-            if (!(value > 0.0)) fail(SCANRS_ERR_ARGUMENT, "reuse_cmax must be positive");
-            st.reuse_cmax = value;
-        } else {
-            fail(SCANRS_ERR_ARGUMENT, "unknown option '%s'", key);
-        }
-    });
-}
-int scanrs_mat_get_counter(scanrs_mat *m, const char *key, uint64_t *value) {
-    return guard([&] {
-        if (!m || !key || !value) fail(SCANRS_ERR_ARGUMENT, "null argument");
-        const std::string k(key);
-        if (k == "bk_host_retries")
-            *value = m->st->bk_host_retries;
-        else if (k.rfind("bk_", 0) == 0) { // what the last svd_bk on this handle decided about its reused projection (Storage::BkDecisions)
-            const Storage::BkDecisions &d = m->st->bk;
-            auto bits = [](double x) {
-                uint64_t u;
-                memcpy(&u, &x, sizeof(u));
-                return u;
-            };
-            if (k == "bk_q")
-                *value = d.q;
-            else if (k == "bk_b")
-                *value = d.b;
-            else if (k == "bk_coef_valid")
-                *value = d.coef_valid;
-            else if (k == "bk_flagged_older")
-                *value = d.flagged_older;
-            else if (k == "bk_limit_branch")
-                *value = d.limit_branch;
-            else if (k == "bk_limit_bits")
-                *value = bits(d.limit);
-            else if (k == "bk_direct_columns")
-                *value = d.direct_columns;
-            else if (k == "bk_last_direct")
-                *value = d.last_direct;
-            else if (k == "bk_full_direct")
-                *value = d.full_direct;
-            else if (k == "bk_early_projections")
-                *value = d.early_projections;
-            else if (k == "bk_cmax_dense_bits")
-                *value = bits(d.cmax_dense);
-            else
-                fail(SCANRS_ERR_ARGUMENT, "unknown counter '%s'", key);
-        } else if (k == "spmm_route") // the last sparse product on this handle (Storage::SpmmDecision): its kernel family, SCANRS_SPMM_* ...
-            *value = m->st->spmm.family;
-        else if (k == "spmm_form") // ... the form within the family ...
-            *value = m->st->spmm.form;
-        else if (k == "spmm_chunks") // ... and its column chunks, SCANRS_SPMM_SLIVER set when a last narrow one went to the plain gather
-            *value = m->st->spmm.chunks;
-        else if (k == "transpose_route") // the sort the handle's transposed copy was built through (transpose_plan.hpp): 0 none built or no nonzeros, 1 packed key, 2 pair sort
-            m->st->side_join_if(&m->st->other, false), *value = m->st->transpose_route; // (a helper thread may be building the copy right now)
-        else if (k == "partition_rounds") // rounds of the last scanrs_mat_partition_on_thresholds[_sharded] on this handle
-            *value = m->st->partition_rounds;
-        else if (k == "partition_allreduces") // ... and its exchange steps (an unsharded handle: 0)
-            *value = m->st->partition_allreduces;
-        else if (k == "de_pairs_passes") // the last scanrs_sseq_de_pairs on this handle: passes over the nonzeros ...
-            *value = m->st->de_pairs_passes;
-        else if (k == "de_pairs_literal") // ... and pairs that took the literal route
-            *value = m->st->de_pairs_literal;
-        else if (k == "de_shard_tests") // the last scanrs_sseq_de* on this handle: the tests this rank launched on the device (unsharded: all of them) ...
-            *value = m->st->de_shard_tests;
-        else if (k == "de_shard_allreduces") // ... and the exchange steps of the last params / group sums / DE call (unsharded: 0)
-            *value = m->st->de_shard_allreduces;
-        else if (k == "subset_masked_passes") // sums over a column list on this handle: made from the copy whose outer dimension is the result axis ...
-            *value = m->st->subset_masked_passes;
-        else if (k == "subset_scatter_passes") // ... and through the integer scatter from the other copy
-            *value = m->st->subset_scatter_passes;
-        else if (k == "knn_blocks") // the last scanrs_knn_sharded on this handle: the blocks of the point set it searched ...
-            *value = m->st->knn_blocks;
-        else if (k == "knn_allreduces") // ... and its exchange steps (an unsharded handle: 0)
-            *value = m->st->knn_allreduces;
-        else if (k == "knn_blocks_filtered") // the last scanrs_nearest_neighbors_sharded: blocks this rank searched through the filter
-            *value = m->st->knn_blocks_filtered;
-        else if (k == "subset_allreduces") // the exchange steps of the last sharded sum over a column list (an unsharded handle: 0)
-            *value = m->st->subset_allreduces;
-        else if (k.rfind("reshard_", 0) == 0 && k.size() > 11 && k.compare(k.size() - 3, 3, "_us") == 0) {
-            // a shard made by an inner-sharding constructor (multi.cpp): wall clock of its thread in the phases upload, count (validation
-            // and the histogram), split, exchange, transpose
-            static const char *const phases[5] = {"upload", "count", "split", "exchange", "transpose"};
-            int which = -1;
-            for (int i = 0; i < 5; i++)
-                if (k == std::string("reshard_") + phases[i] + "_us") which = i;
-            if (which < 0) fail(SCANRS_ERR_ARGUMENT, "unknown counter '%s'", key);
-            *value = m->st->reshard_us[which];
-        } else if (k == "regather_plan_us" || k == "regather_pull_us" || k == "regather_finish_us") {
-            // a shard made by scanrs_multi_gather_outer / _rebalance (multi.cpp): wall clock of the plan (the sources' lengths to the host and
-            // the host plan: one phase, the same on every shard) and of the shard's own thread in pull and finish
-            *value = m->st->regather_us[k == "regather_plan_us" ? 0 : k == "regather_pull_us" ? 1 : 2];
-        } else if (k == "export_plan_us" || k == "export_pull_us" || k == "export_encode_us") {
-            // a shard of the last scanrs_multi_to_adaptive (multi.cpp): wall clock of the plan (one phase, the same on every shard) and of
-            // the shard's own thread in the pull of its slab and in encode + download
-            *value = m->st->export_us[k == "export_plan_us" ? 0 : k == "export_pull_us" ? 1 : 2];
-        } else if (k == "t_layout_us") // first-call accounting: host time of the calling thread in tile layout builds ...
-            *value = m->st->t_layout_us;
-        else if (k == "t_side_wait_us") // ... waiting for the helper thread that builds the second orientation
-            *value = m->st->t_side_wait_us;
-        else if (k == "t_start_panel_us") // ... in the seeded start panel (first call: the generator's jump tables)
-            *value = m->st->t_start_panel_us;
-        else if (k == "t_delivery_us") // ... delivering U and V to the caller's host arrays
-            *value = m->st->t_delivery_us;
-        else if (k == "t_alloc_us") // ... in hipMalloc, process-wide
-            *value = device_alloc_us();
-        else if (k == "alloc_calls")
-            *value = device_alloc_calls();
-        else if (k == "tile_positions" || k == "tile_served_nonzeros" || k == "tile_overflow_nonzeros") { // both tile layouts of the handle
-            m->st->side_join_if(nullptr, true);
-            uint64_t a[3], b[3];
-            tile_layout_stats(m->st->primary.tiles.get(), a);
-            tile_layout_stats(m->st->has_other ? m->st->other.tiles.get() : nullptr, b);
-            const int i = k == "tile_positions" ? 0 : k == "tile_served_nonzeros" ? 1 : 2;
-            *value = a[i] + b[i];
-        }
-        else
-            fail(SCANRS_ERR_ARGUMENT, "unknown counter '%s'", key);
-    });
-}
-int scanrs_mat_set_panel_precision(scanrs_mat *m, int precision) {
-    return guard([&] {
-        if (!m) fail(SCANRS_ERR_ARGUMENT, "null handle");
-        if (precision != 0 && precision != 1) fail(SCANRS_ERR_ARGUMENT, "precision must be 0 (f64 panels) or 1 (f32 gather panels)");
-        m->st->panel_precision = precision;
-    });
 }
 int scanrs_mat_sync(scanrs_mat *m) {
     return guard([&] {

@@ -354,7 +354,7 @@ void merge_clusters_run(Storage &st, const SparseCopy &cp, bool gene_major, uint
     uint64_t passes = 0;
 
     // the fused route's one pass: per-cell totals, then per (cluster, gene) sums of the original clustering
-    const bool fused = st.merge_fused != 0;
+    const bool fused = st.opt.merge_fused != 0;
     std::vector<FusedCluster> fc;
     std::vector<double> cell_tot;
     const double scale = fixed_scale((double)cells); // Σ x/u_c, Σ (x/u_c)², Σ 1/u_c of a cluster: at most one per cell

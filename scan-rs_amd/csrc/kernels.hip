@@ -1139,18 +1139,18 @@ static void launch_spmm_2d(Storage &st, SparseCopy &cp, const DevMap &map, const
     lc = (lc + 1u) & ~1u;
     // Longest-first pays when a launch is only a few rounds of waves (33 k genes = 1 round of the chip's 8192 wave slots:
     // -8 % per step); with ~10^6 vectors there is no tail to hide and the permuted rows only scatter the streaming reads (+3 %).
-    const bool ordered = launch_longest_first(spmm_options(st), cp.n_outer);
+    const bool ordered = launch_longest_first(st.opt, cp.n_outer);
     if (ordered) ensure_order(st, cp);
     const int fstart = values_prefix_len(spmm_query(st, cp, map, l, ldx));
     const double *fvals = fvals_wanted(st, cp, map, fstart) ? ensure_fvals(st, cp, map, fstart) : nullptr;
     const dim3 block(256);
     for (uint32_t c0 = 0; c0 < l; c0 += lc) {
         const uint32_t lw = std::min(lc, l - c0);
-        uint32_t m = (uint32_t)(st.l2_tile_bytes / ((size_t)(1u << BT_SHIFT) * lw * 8));
+        uint32_t m = (uint32_t)(st.opt.l2_tile_bytes / ((size_t)(1u << BT_SHIFT) * lw * 8));
         if (m < 1u) m = 1u;
         const uint32_t steps = (nb + m - 1u) / m;
         // hot = a vector whose average segment per step reaches hot_segment nonzeros
-        const uint32_t n_hot = ordered && st.hot_segment ? count_at_least(cp, (uint64_t)st.hot_segment * steps) : 0u;
+        const uint32_t n_hot = ordered && st.opt.hot_segment ? count_at_least(cp, (uint64_t)st.opt.hot_segment * steps) : 0u;
         const dim3 grid((unsigned)(n_hot + (cp.n_outer - n_hot + 3) / 4));
         const double bytes = ((double)cp.nnz * 8.0 + (double)(cp.n_outer + 1) * 8.0 + (double)cp.n_inner * lw * 8.0 +
                               (double)cp.n_outer * lw * 8.0) / steps;
@@ -1293,7 +1293,7 @@ void launch_gather2d_ov(Storage &st, hipStream_t s, SparseCopy &ov, const double
     // the gather is bound by the drain at the end of every step, not by L2 hits: 245 steps of 3.5 MB over the 800 MB gene-major
     // panel end 1 ms later than 123 of 7 MB (pass 21.3 vs 20.5 ms; 10.5 MB: 20.8; the whole panel in one step: 24 ms — its
     // Infinity-Cache / HBM row reads slow the tile kernel's staging down). The 26 MB cell-major panel does not care (20.6 ms).
-    const size_t ovb = st.ov_tile_bytes ? st.ov_tile_bytes : 2 * st.l2_tile_bytes;
+    const size_t ovb = st.opt.ov_tile_bytes ? st.opt.ov_tile_bytes : 2 * st.opt.l2_tile_bytes;
     uint32_t m = (uint32_t)(ovb / ((size_t)(1u << BT_SHIFT) * l * 8));
     if (m < 1u) m = 1u;
     // A small overflow part (the dense tile layout leaves 0.01-3 % of the nonzeros: vectors too sparse to own a slot) is gathered in ONE
@@ -1332,7 +1332,7 @@ static void launch_spmm_2d_f32(Storage &st, SparseCopy &cp, const DevMap &map, c
             hipLaunchKernelGGL(f64_to_f32_panel_kernel, grid1((uint64_t)cp.n_inner * ldf, 256), block, 0, st.stream, X + c0, ldx,
                                cp.n_inner, lw, Xf, ldf);
         }
-        uint32_t m = (uint32_t)(st.l2_tile_bytes / ((size_t)(1u << BT_SHIFT) * ldf * 4));
+        uint32_t m = (uint32_t)(st.opt.l2_tile_bytes / ((size_t)(1u << BT_SHIFT) * ldf * 4));
         if (m < 1u) m = 1u;
         const uint32_t steps = (nb + m - 1u) / m;
         const double bytes = ((double)cp.nnz * 8.0 + (double)(cp.n_outer + 1) * 8.0 + (double)cp.n_inner * lw * 4.0 +
@@ -1372,7 +1372,7 @@ static void launch_spmv2d(Storage &st, SparseCopy &cp, const DevMap &map, bool f
     const uint32_t nb = ensure_bounds(st, cp);
     const uint32_t m = std::max(1u, 256u / ldx);
     const uint32_t steps = (nb + m - 1u) / m;
-    const bool ordered = launch_longest_first(spmm_options(st), cp.n_outer);
+    const bool ordered = launch_longest_first(st.opt, cp.n_outer);
     if (ordered) ensure_order(st, cp);
     const dim3 grid((unsigned)((cp.n_outer + 3) / 4)), block(256);
     const double bytes = ((double)cp.nnz * 8.0 + (double)(cp.n_outer + 1) * 8.0 + (double)(cp.n_inner + cp.n_outer) * l * 8.0) / steps;
@@ -1483,7 +1483,7 @@ void launch_spmm_u32(Storage &st, const SparseCopy &cp, const uint32_t *X, uint3
 // copy will run through the hybrid tile product, which keeps its own weights: 8 B per nonzero and 1.7 ms of stores per
 // normalize saved; a gather product that wants them later (RandSvd's 500-column panels) materializes them itself then.
 static bool moments_keep_values(Storage &st, const SparseCopy &cp, const DevMap &map) {
-    const SpmmOptions o = spmm_options(st);
+    const Options &o = st.opt;
     // Against tiles_static_candidate, the launch's own test:
     //  - no panel terms (l, ldx, LDS room): the pass runs before any product, the width is the solver's to choose;
     //  - no rejection memory and no layout: at the first normalize nothing has been tried yet;
@@ -1502,7 +1502,7 @@ void launch_row_reduce(Storage &st, SparseCopy &cp, const DevMap &map, int mode,
         bool inner_indexed = false;
         for (int i = 0; i < map.n; i++) inner_indexed = inner_indexed || link_reads_inner(q, i);
         bool lazy = false;
-        if (inner_indexed && st.slice_walk && cp.n_outer < cp.n_inner && slice_walk_chain(q, 0, lazy) && lazy) {
+        if (inner_indexed && st.opt.slice_walk && cp.n_outer < cp.n_inner && slice_walk_chain(q, 0, lazy) && lazy) {
             // the barcode scale staged in LDS slice by slice instead of gathered from L2 (see slice_walk_kernel)
             double *fout = mode == 2 && moments_keep_values(st, cp, map) ? fvals_claim(st, cp, map, map.n) : nullptr;
             launch_slice_walk<1>(st, cp, map, nullptr, 0, true, nullptr, 0, out_sum, 1, mode == 2 ? out_sumsq : nullptr, fout, nullptr, 0,

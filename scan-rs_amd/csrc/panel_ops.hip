@@ -387,7 +387,7 @@ void launch_weighted_colsum(Storage &st, const double *B, uint32_t rank, const d
 static bool on_side_stream(const Storage &st) {
     // work queued on a side stream runs beside the persistent tile kernel of a sparse pass, which holds all of every CU's LDS: a
     // kernel that needs LDS waits for the end of the pass; the register-only MFMA kernels fit the registers the tile kernel leaves
-    return st.dense_side_no_lds && ((st.aux_stream && st.stream == st.aux_stream) || (st.aux2_stream && st.stream == st.aux2_stream));
+    return st.opt.dense_side_no_lds && ((st.aux_stream && st.stream == st.aux_stream) || (st.aux2_stream && st.stream == st.aux2_stream));
 }
 
 // one vector against a narrow panel: the streaming form (gram_vec_kernel)
@@ -475,7 +475,7 @@ void launch_gemm_route(Storage &st, int route, const double *X, uint32_t ldx, ui
     if (ldx & 1u) fail(SCANRS_ERR_ARGUMENT, "gemm: ldx must be even");
     const bool aligned = (reinterpret_cast<uintptr_t>(X) & 15u) == 0;
     if (route == GEMM_AUTO) {
-        route = gemm_route(aligned, ldx, n, m, rows, on_side_stream(st), st.gemm_direct != 0).route;
+        route = gemm_route(aligned, ldx, n, m, rows, on_side_stream(st), st.opt.gemm_direct != 0).route;
     } else if (route == GEMM_DIRECT) { // a forced kernel: its own preconditions, not the dispatcher's choice
         if (!gemm_direct_ok(X, ldx, n, m, rows)) fail(SCANRS_ERR_ARGUMENT, "gemm_direct: needs X 16-byte aligned, n >= 16, rows >= 64, m <= 4096");
     } else if (route != GEMM_WAVE && route != GEMM_TILED && route != GEMM_SKINNY_LDS) {

@@ -274,7 +274,7 @@ static void download_panel_staged(Ctx &c, const double *d, uint32_t ld, uint64_t
         const uintptr_t a = ((uintptr_t)h + (2u << 20) - 1) & ~(uintptr_t)((2u << 20) - 1), e = ((uintptr_t)h + (size_t)rows * row_bytes) & ~(uintptr_t)((2u << 20) - 1);
         if (e > a) (void)madvise((void *)a, e - a, MADV_HUGEPAGE);
     }
-    const unsigned T = std::max(1u, std::min(c.st.d2h_threads, std::thread::hardware_concurrency()));
+    const unsigned T = std::max(1u, std::min(c.st.opt.d2h_threads, std::thread::hardware_concurrency()));
     hipEvent_t ev[NS];
     for (auto &e : ev) SCANRS_HIP(hipEventCreateWithFlags(&e, hipEventDisableTiming));
     std::atomic<size_t> ready{0};
@@ -1302,7 +1302,7 @@ struct BkRun {
                 for (uint32_t j = 0; j < q; j++) colmax[j] = std::max(colmax[j], std::fabs(cfull[(size_t)r * q + j]));
         if (reuse && !c_valid && trace_on())
             fprintf(stderr, "[scanrs trace] bk: rank-deficient panels were completed on the host: the projection is computed directly\n");
-        plan = bk_plan(colmax.data(), b, n_iter, c.st.reuse_cmax, c_valid);
+        plan = bk_plan(colmax.data(), b, n_iter, c.st.opt.reuse_cmax, c_valid);
         bk_record(c.st.bk, plan, c_valid);
         if (tracked && trace_on()) bk_plan_trace(colmax.data(), b, n_iter, plan);
         if (tracked && !plan.last_direct) {
@@ -1370,7 +1370,7 @@ static int pca_bk_run(scanrs_mat *m, uint32_t k, double k_multiplier, uint32_t n
 
 int pca_bk(scanrs_mat *m, uint32_t k, double k_multiplier, uint32_t n_iter, uint64_t seed, const double *omega,
            const scanrs_snoop *snoop, double *u, double *s, double *v) {
-    int rc = pca_bk_run(m, k, k_multiplier, n_iter, seed, omega, snoop, u, s, v, m->st->device_factor != 0);
+    int rc = pca_bk_run(m, k, k_multiplier, n_iter, seed, omega, snoop, u, s, v, m->st->opt.device_factor != 0);
     if (rc == BK_RETRY_ON_HOST) {
         m->st->bk_host_retries++;
         rc = pca_bk_run(m, k, k_multiplier, n_iter, seed, omega, snoop, u, s, v, false);

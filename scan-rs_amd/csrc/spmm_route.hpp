@@ -26,15 +26,8 @@ constexpr uint32_t DN_TABK = DN_CMAX + 1u;           // entries per place / plan
 constexpr uint32_t DN_TABI_FRONT = DN_B * DN_T, DN_TABI_PAD = 512; // inner-side table: entries in front of plane 0 (a record of another round may point one ring turn back) and behind every plane (the visits past a part's end)
 
 // ---- the question ---------------------------------------------------------------------------------------------------------------
-struct SpmmOptions {
-    int spmm_path = 0, panel_precision = 0, tile_auto = 1;
-    uint32_t tile_k = 2, tile_s = 32, tile_t = 48, tile_b = 4, tile_ku = 1;
-    int tile_dense = 1, tile_builder = 1;
-    uint64_t blocked_min_nnz = 1ull << 22;
-    int slice_walk = 1, spmv_lds = 1, spmv_row_table = 1, spmm_order = 1, materialize = 1, tile_wtab = 1, tile_fold = 1;
-};
 struct SpmmQuery {
-    SpmmOptions o;
+    Options o;
     uint64_t n_outer = 0, n_inner = 0, nnz = 0; // of the copy
     uint32_t l = 0, ldx = 0;
     int n_links = 0; // the map: kind and "indexes its array by the outer position" per link
@@ -43,19 +36,9 @@ struct SpmmQuery {
     // them. launch_spmm_f64 asks the driver only when the route decided with `true` would materialize (fvals_room, kernels.hip).
     bool values_room = true;
 };
-inline SpmmOptions spmm_options(const Storage &st) {
-    SpmmOptions o;
-    o.spmm_path = st.spmm_path, o.panel_precision = st.panel_precision, o.tile_auto = st.tile_auto;
-    o.tile_k = st.tile_k, o.tile_s = st.tile_s, o.tile_t = st.tile_t, o.tile_b = st.tile_b, o.tile_ku = st.tile_ku;
-    o.tile_dense = st.tile_dense, o.tile_builder = st.tile_builder;
-    o.blocked_min_nnz = st.blocked_min_nnz;
-    o.slice_walk = st.slice_walk, o.spmv_lds = st.spmv_lds, o.spmv_row_table = st.spmv_row_table, o.spmm_order = st.spmm_order;
-    o.materialize = st.materialize, o.tile_wtab = st.tile_wtab, o.tile_fold = st.tile_fold;
-    return o;
-}
 inline SpmmQuery spmm_query(const Storage &st, const SparseCopy &cp, const DevMap &map, uint32_t l, uint32_t ldx) {
     SpmmQuery q;
-    q.o = spmm_options(st);
+    q.o = st.opt;
     q.n_outer = cp.n_outer, q.n_inner = cp.n_inner, q.nnz = cp.nnz;
     q.l = l, q.ldx = ldx;
     q.n_links = map.n;
@@ -100,36 +83,36 @@ struct SpmmRoute {
 };
 
 // ---- predicates, each written once ----------------------------------------------------------------------------------------------
-inline bool path_plain_gather(const SpmmOptions &o) { return o.spmm_path == 1; }
-inline bool path_auto(const SpmmOptions &o) { return o.spmm_path == 0; }
-inline bool path_forces_tiles(const SpmmOptions &o) { return o.spmm_path == 3; }
-inline bool path_forces_blocked(const SpmmOptions &o) { return o.spmm_path == 2 || o.spmm_path == 3; }
-inline bool f64_panels(const SpmmOptions &o) { return o.panel_precision == 0; }
+inline bool path_plain_gather(const Options &o) { return o.spmm_path == 1; }
+inline bool path_auto(const Options &o) { return o.spmm_path == 0; }
+inline bool path_forces_tiles(const Options &o) { return o.spmm_path == 3; }
+inline bool path_forces_blocked(const Options &o) { return o.spmm_path == 2 || o.spmm_path == 3; }
+inline bool f64_panels(const Options &o) { return o.panel_precision == 0; }
 // unit positions exist for K = 2 only (one unit + one general position per visit)
 inline bool tile_shape_ok(uint32_t K, uint32_t S, uint32_t T, uint32_t B) {
     const bool ks = (K == 2 && (S == 32 || S == 28)) || (K == 3 && S == 32) || (K == 4 && (S == 32 || S == 28));
     return ks && B >= 2 && T >= 8 && T <= 24u * K && B * T <= 192;
 }
-inline bool tile_shape_ok(const SpmmOptions &o) { return tile_shape_ok(o.tile_k, o.tile_s, o.tile_t, o.tile_b); }
+inline bool tile_shape_ok(const Options &o) { return tile_shape_ok(o.tile_k, o.tile_s, o.tile_t, o.tile_b); }
 // the default shape with the wave-level builder: what the dense record layout serves and what the slot split is made for
-inline bool default_tile_shape(const SpmmOptions &o) { return o.tile_builder != 0 && o.tile_k == 2u && o.tile_b == 4u && o.tile_s == 32u && o.tile_t == 48u; }
-inline bool tile_dense_wanted(const SpmmOptions &o) { return o.tile_dense != 0 && default_tile_shape(o); }
-inline uint32_t tile_unit_positions(const SpmmOptions &o) { return o.tile_k == 2u && o.tile_ku ? 1u : 0u; }
-inline bool tile_auto_size(const SpmmOptions &o, uint64_t nnz) { return nnz >= std::max<uint64_t>(o.blocked_min_nnz, TILE_AUTO_MIN_NNZ); }
+inline bool default_tile_shape(const Options &o) { return o.tile_builder != 0 && o.tile_k == 2u && o.tile_b == 4u && o.tile_s == 32u && o.tile_t == 48u; }
+inline bool tile_dense_wanted(const Options &o) { return o.tile_dense != 0 && default_tile_shape(o); }
+inline uint32_t tile_unit_positions(const Options &o) { return o.tile_k == 2u && o.tile_ku ? 1u : 0u; }
+inline bool tile_auto_size(const Options &o, uint64_t nnz) { return nnz >= std::max<uint64_t>(o.blocked_min_nnz, TILE_AUTO_MIN_NNZ); }
 // the tile kernel's 32-bit visit index
-inline bool tile_visits_fit(const SpmmOptions &o, uint64_t n_outer, uint64_t n_inner) {
+inline bool tile_visits_fit(const Options &o, uint64_t n_outer, uint64_t n_inner) {
     return ((n_outer + o.tile_s - 1) / o.tile_s) * ((n_inner + o.tile_t - 1) / o.tile_t) <= 0xFFFFFFFFull;
 }
 // the auto path's own terms for a copy (no panel): what tile_layout_build_auto and spmm_tiles_auto test before they look at the
 // layout, the rejection memory and the free memory. Neither the path nor the panel precision: the callers have tested them.
-inline bool tile_auto_copy_ok(const SpmmOptions &o, uint64_t n_outer, uint64_t n_inner, uint64_t nnz) {
+inline bool tile_auto_copy_ok(const Options &o, uint64_t n_outer, uint64_t n_inner, uint64_t nnz) {
     return o.tile_auto && tile_auto_size(o, nnz) && tile_shape_ok(o) && tile_visits_fit(o, n_outer, n_inner);
 }
 // wide panels go through the tile kernel in column chunks of equal, even width (200 -> 2 x 100, 500 -> 5 x 100)
 inline uint32_t tile_chunks(uint32_t l) { return (l + TL_LMAX - 1u) / TL_LMAX; }
 inline uint32_t tile_chunk_width(uint32_t l) { return l ? even_up((l + tile_chunks(l) - 1u) / tile_chunks(l)) : 0u; }
 // a panel of l columns (one chunk) and this copy fit the tile kernel
-inline bool tile_panel_ok(const SpmmOptions &o, uint64_t n_outer, uint64_t n_inner, uint64_t nnz, uint32_t ldx, uint32_t l) {
+inline bool tile_panel_ok(const Options &o, uint64_t n_outer, uint64_t n_inner, uint64_t nnz, uint32_t ldx, uint32_t l) {
     return l >= TL_LMIN && l <= TL_LMAX && (ldx & 1u) == 0 && n_outer > 0 && n_inner > 0 && nnz > 0 &&
            ((size_t)o.tile_b * o.tile_t + 1u) * even_up(l) * 8 <= TL_LDS && (size_t)o.tile_t * even_up(l) * 8 >= 1024u; // (a tile is at least one staging chunk)
 }
@@ -142,9 +125,9 @@ inline bool tiles_static_candidate(const SpmmQuery &q) {
     return path_forces_tiles(q.o) || (path_auto(q.o) && f64_panels(q.o) && tile_auto_copy_ok(q.o, q.n_outer, q.n_inner, q.nnz));
 }
 // L2-blocked gather and spmv2d: outer vectors launched longest first
-inline bool launch_longest_first(const SpmmOptions &o, uint64_t n_outer) { return o.spmm_order == 2 || (o.spmm_order == 1 && n_outer <= ORDERED_MAX_OUTER); }
+inline bool launch_longest_first(const Options &o, uint64_t n_outer) { return o.spmm_order == 2 || (o.spmm_order == 1 && n_outer <= ORDERED_MAX_OUTER); }
 // the row reductions and the Ix1 / Ix2 products walk an inner-indexed array in slices from here on
-inline bool far_inner(const SpmmOptions &o, uint64_t n_inner, uint64_t nnz) { return nnz >= o.blocked_min_nnz && n_inner >= FAR_INNER_MIN; }
+inline bool far_inner(const Options &o, uint64_t n_inner, uint64_t nnz) { return nnz >= o.blocked_min_nnz && n_inner >= FAR_INNER_MIN; }
 
 // ---- the map, as the decision reads it --------------------------------------------------------------------------------------------
 inline bool link_nonlinear(int k) { return k == OP_LN_1P || k == OP_LOG2_1P || k == OP_LOG10_1P || k == OP_SQUARE; }
@@ -241,7 +224,7 @@ inline SpmmRoute tile_route(const SpmmQuery &q) {
 }
 // everything below the tile attempt
 inline SpmmRoute route_below_tiles(const SpmmQuery &q) {
-    const SpmmOptions &o = q.o;
+    const Options &o = q.o;
     SpmmRoute r;
     const bool want_2d = path_forces_blocked(o) || (path_auto(o) && q.nnz >= o.blocked_min_nnz && q.l >= TL_LMIN);
     if (want_2d && q.l > 0 && q.n_outer > 0 && q.n_inner > 0) {

@@ -373,7 +373,7 @@ void launch_sseq_group_pass(Storage &st, const SparseCopy &cp, bool gene_major, 
         // a wave's LDS row holds n_groups u64: up to 4 waves per workgroup within 64 KB
         const uint32_t waves = (uint32_t)std::max<uint64_t>(1, std::min<uint64_t>(4, 8192 / std::max<uint32_t>(1, n_groups)));
         const size_t lds = (size_t)waves * n_groups * 8;
-        const dim3 grid(blocks_for(n_genes, waves, st.sseq_grid_cap)), block(64 * waves);
+        const dim3 grid(blocks_for(n_genes, waves, st.opt.sseq_grid_cap)), block(64 * waves);
         if (mom && d_cls)
             hipLaunchKernelGGL(sseq_gene_major_kernel<2>, grid, block, lds, st.stream, cp.indptr.p, cp.indices.p, cp.values.p, n_genes, d_labels,
                                n_groups, d_sums, d_sf, scale1, scale2, d_mom, d_bad, d_cls, log2m);
@@ -385,7 +385,7 @@ void launch_sseq_group_pass(Storage &st, const SparseCopy &cp, bool gene_major, 
                                n_groups, d_sums, d_sf, scale1, scale2, d_mom, d_bad, d_cls, log2m);
     } else {
         SCANRS_HIP(hipMemsetAsync(d_sums, 0, std::max<uint64_t>(1, n_genes * n_groups) * 8, st.stream));
-        const dim3 grid(blocks_for(cp.n_outer, 4, st.sseq_grid_cap)), block(256);
+        const dim3 grid(blocks_for(cp.n_outer, 4, st.opt.sseq_grid_cap)), block(256);
         if (cp.n_outer) {
             if (mom && d_cls)
                 hipLaunchKernelGGL(sseq_cell_major_kernel<2>, grid, block, 0, st.stream, cp.indptr.p, cp.indices.p, cp.values.p, cp.n_outer, d_labels,
@@ -405,7 +405,7 @@ void launch_sseq_term_class(Storage &st, const SparseCopy &cp, bool gene_major, 
                             uint32_t *d_cls) {
     SCANRS_HIP(hipMemsetAsync(d_cls, 0, std::max<uint64_t>(1, n_genes) * 4, st.stream));
     if (cp.n_outer)
-        hipLaunchKernelGGL(sseq_term_class_kernel, dim3(blocks_for(cp.n_outer, 4, st.sseq_grid_cap)), dim3(256), 0, st.stream, cp.indptr.p, cp.indices.p,
+        hipLaunchKernelGGL(sseq_term_class_kernel, dim3(blocks_for(cp.n_outer, 4, st.opt.sseq_grid_cap)), dim3(256), 0, st.stream, cp.indptr.p, cp.indices.p,
                            cp.values.p, cp.n_outer, gene_major ? 1 : 0, d_labels, d_sf, d_cls);
     SCANRS_HIP(hipGetLastError());
 }

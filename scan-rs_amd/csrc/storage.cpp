@@ -110,7 +110,7 @@ static int stream_priority(int level) {
     return least;
 }
 hipStream_t Storage::aux() {
-    if (!overlap) return stream;
+    if (!opt.overlap) return stream;
     if (!aux_stream) {
         // lowest priority: at the end of a persistent tile kernel the NEXT one (main stream) gets the CUs first and this stream's
         // dense kernels fill what its tail and the overflow gather's tail leave — at equal priority a 2-3 ms projection GEMM that
@@ -120,7 +120,7 @@ hipStream_t Storage::aux() {
     return aux_stream;
 }
 hipStream_t Storage::aux2() {
-    if (!overlap) return stream;
+    if (!opt.overlap) return stream;
     if (!aux2_stream) SCANRS_HIP(hipStreamCreateWithPriority(&aux2_stream, hipStreamDefault, stream_priority(2)));
     return aux2_stream;
 }

@@ -116,7 +116,7 @@ void subset_sums(scanrs_mat *m, bool per_column, int mode, const List *lists, in
     // how far a helper thread has come)
     const bool want_base_rows = (!per_column) != m->transposed;
     const bool exists = want_base_rows == (st.storage == SCANRS_CSR) || st.other_settled;
-    const bool scatter = !exists && mode == 0 && st.subset_scatter != 0;
+    const bool scatter = !exists && mode == 0 && st.opt.subset_scatter != 0;
     SparseCopy &cp = scatter ? st.primary : st.copy_with_outer_rows(want_base_rows);
     const bool outer_is_view_row = scatter ? per_column : !per_column;
     const bool listed_outer = !outer_is_view_row; // the lists name view columns

@@ -815,8 +815,6 @@ __global__ void tile_ovptr_kernel(const unsigned long long *__restrict__ ov_off,
 
 } // namespace
 
-// the dense record layout serves the default shape (tiles_dense.inc)
-static inline bool tile_dense_wanted(const Storage &st) { return tile_dense_wanted(spmm_options(st)); }
 // the tile layout of one orientation under one map
 struct TileLayout {
     TileShape sh{};
@@ -864,13 +862,13 @@ struct TileLayout {
                (double)rtab.n * 4.0 + (double)wtab.n * 8.0 + (double)(w_place.n + w_inner.n) * 8.0;
     }
     bool structure_matches(const Storage &st) const {
-        if (dense != tile_dense_wanted(st)) return false;
-        if (dense && (slot_order.n != 0) != (st.tile_sort_slots != 0 && n_slots > 1)) return false;
-        if (dense && slot_order.n != 0 && slot_mode != st.tile_sort_slots) return false;
+        if (dense != tile_dense_wanted(st.opt)) return false;
+        if (dense && (slot_order.n != 0) != (st.opt.tile_sort_slots != 0 && n_slots > 1)) return false;
+        if (dense && slot_order.n != 0 && slot_mode != st.opt.tile_sort_slots) return false;
         // the slots are split for the wave-level builder's shape (asked of the options: a layout of another shape than theirs fails below anyway)
-        const bool splittable = default_tile_shape(spmm_options(st));
-        const double want_x = splittable && st.tile_split ? st.tile_split_x : 0.0, want_min = splittable && st.tile_split ? st.tile_split_min : 0.0;
-        return sh.K == st.tile_k && sh.S == st.tile_s && sh.T == st.tile_t && sh.B == st.tile_b && sh.KU == tile_unit_positions(spmm_options(st)) &&
+        const bool splittable = default_tile_shape(st.opt);
+        const double want_x = splittable && st.opt.tile_split ? st.opt.tile_split_x : 0.0, want_min = splittable && st.opt.tile_split ? st.opt.tile_split_min : 0.0;
+        return sh.K == st.opt.tile_k && sh.S == st.opt.tile_s && sh.T == st.opt.tile_t && sh.B == st.opt.tile_b && sh.KU == tile_unit_positions(st.opt) &&
                split_x == want_x && split_min == want_min;
     }
     bool weights_match(const DevMap &map) const {
@@ -908,15 +906,15 @@ static TileLayout *dense_layout_build(Storage &st, const SparseCopy &cp, double 
 // counting pass, before anything large is allocated.
 TileLayout *tile_layout_build(Storage &st, const SparseCopy &cp, double max_overflow, hipStream_t stream = nullptr) {
     Tick tick("tile layout build");
-    if (!tile_shape_ok(st.tile_k, st.tile_s, st.tile_t, st.tile_b))
-        fail(SCANRS_ERR_ARGUMENT, "unsupported tile shape K=%u S=%u T=%u B=%u", st.tile_k, st.tile_s, st.tile_t, st.tile_b);
+    if (!tile_shape_ok(st.opt.tile_k, st.opt.tile_s, st.opt.tile_t, st.opt.tile_b))
+        fail(SCANRS_ERR_ARGUMENT, "unsupported tile shape K=%u S=%u T=%u B=%u", st.opt.tile_k, st.opt.tile_s, st.opt.tile_t, st.opt.tile_b);
     auto tl = std::make_unique<TileLayout>();
     TileShape &sh = tl->sh;
-    sh.K = st.tile_k;
-    sh.KU = tile_unit_positions(spmm_options(st));
-    sh.S = st.tile_s;
-    sh.T = st.tile_t;
-    sh.B = st.tile_b;
+    sh.K = st.opt.tile_k;
+    sh.KU = tile_unit_positions(st.opt);
+    sh.S = st.opt.tile_s;
+    sh.T = st.opt.tile_t;
+    sh.B = st.opt.tile_b;
     sh.sps = 64u / sh.K;
     sh.nset = (sh.S + sh.sps - 1) / sh.sps;
     sh.nt = (uint32_t)((cp.n_inner + sh.T - 1) / sh.T);
@@ -932,10 +930,10 @@ TileLayout *tile_layout_build(Storage &st, const SparseCopy &cp, double max_over
     };
     lap(nullptr);
     // the wave-level builder serves the default shape; other shapes (experiments) keep the per-thread walk, one slot per vector
-    const bool wave_builder = st.tile_builder != 0 && sh.K == 2u && sh.B == 4u && sh.T == 48u && sh.S == 32u && sh.nset == 1u;
-    const bool split = wave_builder && st.tile_split != 0;
-    tl->split_x = split ? st.tile_split_x : 0.0;
-    tl->split_min = split ? st.tile_split_min : 0.0;
+    const bool wave_builder = st.opt.tile_builder != 0 && sh.K == 2u && sh.B == 4u && sh.T == 48u && sh.S == 32u && sh.nset == 1u;
+    const bool split = wave_builder && st.opt.tile_split != 0;
+    tl->split_x = split ? st.opt.tile_split_x : 0.0;
+    tl->split_min = split ? st.opt.tile_split_min : 0.0;
     // ---- slots ----
     if (cp.n_outer + 1 > 0xFFFFFFFFull) fail(SCANRS_ERR_SHAPE, "matrix too large for the tile layout's 32-bit slot index");
     DevBuf<uint32_t> mult(cp.n_outer + 1);
@@ -973,12 +971,12 @@ TileLayout *tile_layout_build(Storage &st, const SparseCopy &cp, double max_over
     if (tl->n_groups * sh.nt > 0xFFFFFFFFull || (sh.nset & (sh.nset - 1u))) fail(SCANRS_ERR_SHAPE, "matrix too large for the tile layout's 32-bit visit index");
     const uint64_t n_seg = cp.n_outer * sh.n_parts;
     lap("slots");
-    if (tile_dense_wanted(st)) return dense_layout_build(st, cp, max_overflow, s, std::move(tl), lap);
+    if (tile_dense_wanted(st.opt)) return dense_layout_build(st, cp, max_overflow, s, std::move(tl), lap);
     // ---- count the overflow per (vector, part) ----
     // one_pass (the wave builder's default): no counting pass - the fill pass writes the records AND the overflow nonzeros (into
     // temporaries indexed like the source, counted per segment as they come), a compaction moves them to their places; the
     // max_overflow verdict then comes after the records were written (a rejected layout is rare and costs one fill pass)
-    bool one_pass = wave_builder && st.tile_build_one_pass != 0;
+    bool one_pass = wave_builder && st.opt.tile_build_one_pass != 0;
     DevBuf<uint32_t> tmp_oi, tmp_ovv;
     DevBuf<unsigned long long> ovc(n_seg + 1), ovo(n_seg + 1);
     SCANRS_HIP(hipMemsetAsync(ovc.p, 0, (n_seg + 1) * 8, s)); // the slots of a split vector add up theirs
@@ -987,7 +985,7 @@ TileLayout *tile_layout_build(Storage &st, const SparseCopy &cp, double max_over
     if (wave_builder && n_witems > 0x7FFFFFFFull) fail(SCANRS_ERR_SHAPE, "matrix too large for the tile layout builder's grid");
     // waves per CU of the builder: its lanes read 64 different places of the matrix, so the lines in flight (2 x 128 B per lane) of
     // all resident waves must fit the L2 or they come from HBM several times; a dummy LDS allocation per wave caps the occupancy
-    const size_t wb_lds = st.tile_build_waves ? std::min<size_t>(65536, TL_LDS / st.tile_build_waves) : 0;
+    const size_t wb_lds = st.opt.tile_build_waves ? std::min<size_t>(65536, TL_LDS / st.opt.tile_build_waves) : 0;
 #define SCANRS_ASSIGN(FILLV, KUV, OVC, OFF, CUR, PROW, PCNT, OVI, OVV)                                                                          \
     hipLaunchKernelGGL((tile_assign_wave_kernel<FILLV, 48, KUV>), dim3((unsigned)n_witems), dim3(64), wb_lds, s, cp.indptr.p, cp.indices.p, cp.values.p, \
                        tl->slot_vec.p, tl->slot_first.p, tl->n_slots, tl->n_groups, sh, OVC, OFF, CUR, PROW, PCNT, OVI, OVV)
@@ -1165,7 +1163,7 @@ static void tile_layout_weights(Storage &st, TileLayout &tl, const SparseCopy &c
         const bool vmajor = tl.unit_mode && !nl_outer && tl.sh.nset == 1u && vquads <= 65535u && tl.n_groups <= 0xFFFFFFFFull / 64u;
         dim3 grid((unsigned)std::min<uint64_t>((n_work + 255) / 256, 1u << 23));
         if (vmajor) grid = dim3((unsigned)((tl.n_groups * (64u - skip) + 255) / 256), vquads);
-        if (skip == 32u && st.tile_weights_wide && tl.sh.K == 2u && tl.sh.S == 32u && tl.sh.B == 4u && tl.sh.T == 48u && tl.sh.nset == 1u && (!vmajor || true)) {
+        if (skip == 32u && st.opt.tile_weights_wide && tl.sh.K == 2u && tl.sh.S == 32u && tl.sh.B == 4u && tl.sh.T == 48u && tl.sh.nset == 1u && (!vmajor || true)) {
             // the wide form (four positions per thread): same rows in the same order
             const uint64_t n_rows = n_rec >> 6;
             const uint64_t lin = (vmajor ? tl.n_groups : (n_rows + 3) / 4) * 8u;
@@ -1556,24 +1554,24 @@ void launch_tile_kernel(Storage &st, const TileArgs &ta, const double *X, uint32
 // solver announces many products (Storage::tile_hint) or when the same map comes by a second time, and only if the device
 // has room for it (about 16 bytes per nonzero per orientation).
 static uint64_t tile_shape_signature(const Storage &st) {
-    return 1ull + st.tile_k + 16ull * st.tile_s + 4096ull * st.tile_t + (1ull << 24) * st.tile_b + (1ull << 32) * st.tile_ku +
-           (1ull << 34) * (uint64_t)(st.tile_max_overflow * 1000.0);
+    return 1ull + st.opt.tile_k + 16ull * st.opt.tile_s + 4096ull * st.opt.tile_t + (1ull << 24) * st.opt.tile_b + (1ull << 32) * st.opt.tile_ku +
+           (1ull << 34) * (uint64_t)(st.opt.tile_max_overflow * 1000.0);
 }
 // large enough, the visit index fits (tile_auto_copy_ok: the auto clause of tiles_static_candidate without the path, the precision
 // and the panel, which the helper thread's build has none of), and - this site's own term, it needs the copy's memory - this shape
 // has not been found wanting for this copy before
 static bool tile_auto_candidate(const Storage &st, const SparseCopy &cp) {
-    return tile_auto_copy_ok(spmm_options(st), cp.n_outer, cp.n_inner, cp.nnz) && cp.tile_rejected_shape != tile_shape_signature(st);
+    return tile_auto_copy_ok(st.opt, cp.n_outer, cp.n_inner, cp.nnz) && cp.tile_rejected_shape != tile_shape_signature(st);
 }
 bool tile_layout_build_auto(Storage &st, SparseCopy &cp, hipStream_t s) {
     if (!tile_auto_candidate(st, cp)) return false;
     if (cp.tiles && cp.tiles->structure_matches(st)) return true;
     // room: records (11 B per position: row 2, count 1, weight 8) + overflow + the build's temporaries + the partial-sum buffers, and 8 GB for the solver
-    const double nt = (double)((cp.n_inner + st.tile_t - 1) / st.tile_t);
+    const double nt = (double)((cp.n_inner + st.opt.tile_t - 1) / st.opt.tile_t);
     // (dense layout: 12.5 B per position at about 1.1 positions per nonzero, 4 B per nonzero of build temporaries and the per-(group, visit) tables)
-    const double need = tile_dense_wanted(st)
-                            ? 18.0 * (double)cp.nnz + 40.0 * (double)((cp.n_outer + st.tile_s - 1) / st.tile_s + 8) * (nt + 1.0) + 2.0 * (double)cp.n_outer * 104.0 * 8.0 * 2.0
-                            : 11.0 * 64.0 * (double)((cp.n_outer + st.tile_s - 1) / st.tile_s) * nt * ((st.tile_s + 64 / st.tile_k - 1) / (64 / st.tile_k)) +
+    const double need = tile_dense_wanted(st.opt)
+                            ? 18.0 * (double)cp.nnz + 40.0 * (double)((cp.n_outer + st.opt.tile_s - 1) / st.opt.tile_s + 8) * (nt + 1.0) + 2.0 * (double)cp.n_outer * 104.0 * 8.0 * 2.0
+                            : 11.0 * 64.0 * (double)((cp.n_outer + st.opt.tile_s - 1) / st.opt.tile_s) * nt * ((st.opt.tile_s + 64 / st.opt.tile_k - 1) / (64 / st.opt.tile_k)) +
                                   0.2 * 12.0 * (double)cp.nnz + 32.0 * (double)cp.n_outer * 64.0 + 2.0 * (double)cp.n_outer * 104.0 * 8.0 * 2.0;
     size_t free_b = 0, total_b = 0;
     if (hipMemGetInfo(&free_b, &total_b) != hipSuccess) return false;
@@ -1607,7 +1605,7 @@ bool tile_layout_build_auto(Storage &st, SparseCopy &cp, hipStream_t s) {
     cp.tiles.reset();
     TileLayout *t = nullptr;
     try {
-        t = tile_layout_build(st, cp, st.tile_max_overflow, s);
+        t = tile_layout_build(st, cp, st.opt.tile_max_overflow, s);
     } catch (const Failure &e) {
         // the room check above is an estimate (cached blocks of other devices, blocks carved from a reserve): when the build
         // itself runs out of device memory the product falls back to the gather kernels instead of failing the solver. Other failures pass.
@@ -1668,7 +1666,7 @@ void launch_spmm_tiles(Storage &st, SparseCopy &cp, const DevMap &map, const dou
         if (!copied) launch_copy_cols(st, X, ldx, xc, ldc, cp.n_inner, l);
         if (ldx != ldc) Xov = xc;
     }
-    if (st.tile_poison_slack) { // test hook: the slack rows hold NaN instead of whatever the allocator left there
+    if (st.opt.tile_poison_slack) { // test hook: the slack rows hold NaN instead of whatever the allocator left there
         const uint64_t n = 3ull * sh.T * ldc;
         if (st.prof.on) st.prof.begin(st.stream, "tile_poison_slack", (double)n * 8.0);
         hipLaunchKernelGGL(tile_poison_slack_kernel, grid_1d(n), dim3(256), 0, st.stream, xc + (size_t)cp.n_inner * ldc, n);
@@ -1686,7 +1684,7 @@ void launch_spmm_tiles(Storage &st, SparseCopy &cp, const DevMap &map, const dou
     // Gram-Schmidt chain of the previous Krylov block) DURING the pass instead of behind it, where a workgroup per CU left them no room
     // (option "tile_spare_cus" 0: one workgroup per CU)
     uint32_t grid = std::min<uint32_t>(n_items, (uint32_t)n_cu);
-    if (st.tile_spare_cus && grid == (uint32_t)n_cu) {
+    if (st.opt.tile_spare_cus && grid == (uint32_t)n_cu) {
         const uint32_t rounds = (n_items + grid - 1u) / grid;
         grid = std::max<uint32_t>((n_items + rounds - 1u) / rounds, grid - grid / 16u); // (never more than a sixteenth of the CUs)
     }
@@ -1695,7 +1693,7 @@ void launch_spmm_tiles(Storage &st, SparseCopy &cp, const DevMap &map, const dou
     double *ovout = nullptr;
     if (tl.ov.nnz) { // the overflow part through the texture path, beside the tile kernel
         ovout = st.scratch.get<double>("tile_ovout", (size_t)cp.n_outer * ldc); // the overflow sum per vector
-        if (st.tile_overlap) {
+        if (st.opt.tile_overlap) {
             hipStream_t ovs = st.ov();
             SCANRS_HIP(hipEventRecord(st.ev_in, st.stream)); // the panel (and the scratch zero-fills) are ready
             SCANRS_HIP(hipStreamWaitEvent(ovs, st.ev_in, 0));
@@ -1733,7 +1731,7 @@ void launch_spmm_tiles(Storage &st, SparseCopy &cp, const DevMap &map, const dou
         fail(SCANRS_ERR_ARGUMENT, "unsupported tile shape K=%u S=%u", sh.K, sh.S);
 #undef SCANRS_TILE
     if (st.prof.on) st.prof.end(st.stream);
-    if (ovout && st.tile_overlap) SCANRS_HIP(hipStreamWaitEvent(st.stream, st.ev_ov, 0));
+    if (ovout && st.opt.tile_overlap) SCANRS_HIP(hipStreamWaitEvent(st.stream, st.ev_ov, 0));
     const uint64_t n = cp.n_outer * (uint64_t)((l + 1u) / 2u);
     hipLaunchKernelGGL(tile_finish_kernel, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, st.stream, pbuf, sh.n_parts, part_stride, tl.slot_first.p, tl.slot_pos.p, ovout,
                        cp.n_outer, l, ldc, ldo, out, off_a, rank, off_w, ldw, tl.ov.indptr.p, (tl.dense && tl.fold_outer) ? tl.uo.p : (const double *)nullptr);
@@ -1745,7 +1743,7 @@ double *tile_panel_copy_target(Storage &st, SparseCopy &cp, uint32_t l) {
     // Against tiles_static_candidate: the layout exists and matches, so the shape, the sizes and the visit index were tested when
     // it was built; l even and within the tile kernel's widths stands in for the panel terms (a chunked wide panel is never copied
     // ahead). f64 panels are asked for on the auto path only, as the launch does.
-    const SpmmOptions o = spmm_options(st);
+    const Options &o = st.opt;
     if (!(path_forces_tiles(o) || (path_auto(o) && o.tile_auto && f64_panels(o)))) return nullptr;
     return st.scratch.get<double>("tile_xc", ((size_t)cp.n_inner + 3u * cp.tiles->sh.T) * l); // (the size launch_spmm_tiles asks for: the same buffer)
 }

@@ -1441,6 +1441,35 @@ def test_set_option_refuses_values_that_cannot_be_cast(sa):
         g.chol_rinv(np.eye(4), rows=0)
 
 
+def test_every_option_set_to_its_default_changes_nothing(sa):
+    """The table of options (options.cpp) against the handle it writes: a handle on which every settable key was set to the default
+    the library reports computes the forced tile product of an untouched handle bit for bit and through the same route, every
+    counter key reads on both, and the keys outside the tables are still refused."""
+    dense = random_counts(np.random.default_rng(11), 300, 200, 0.3, 10)  # counts 1 .. 9
+    plain, _ = pair(sa, dense, so.CSR)
+    touched, _ = pair(sa, dense, so.CSR)
+    settable = [o for o in sa.option_info() if o["settable"]]
+    assert len(settable) == 44
+    for o in settable:
+        touched.set_option(o["name"], o["default"])
+    q = np.random.default_rng(12).standard_normal((200, 16))
+    out = [h.set_spmm_path(3).dot(q) for h in (plain, touched)]
+    assert out[0].shape == (300, 16) and np.array_equal(out[0], out[1])
+    assert_close(out[0], dense.astype(np.float64) @ q, rtol=1e-12, atol=1e-10)
+    for key in ("spmm_route", "spmm_form", "spmm_chunks"):
+        assert plain.counter(key) == touched.counter(key)
+    assert plain.counter("spmm_route") == sa.SPMM_TILES
+    names = sa.counter_names()
+    assert len(names) == 48
+    for h in (plain, touched):
+        for key in names:
+            assert h.counter(key) >= 0
+        with pytest.raises(sa.ScanrsError):
+            h.counter("no_such")
+        with pytest.raises(sa.ScanrsError):
+            h.set_option("no_such", 1)
+
+
 def test_released_blocks_are_not_reused_while_queued_work_names_them(sa):
     """a block released while kernels that use it are still queued (a scratch panel that grows between two asynchronous
     products, a tile layout replaced by an option change) must not reach another handle's allocation before those kernels have run.
