@@ -307,6 +307,21 @@ def _adaptive_table(vecs):
     return n, table, keep
 
 
+def _sharded_points(points, device: bool = False, cells=None):
+    """The `points` of the searches over a sharded point set -> (points, ld, d): a device address to pass as it is (device=True),
+    or a host array for `_p` that the caller keeps alive over the call. device=True: the rank's own rows in device memory, a PcaResultDevice (its d_v / ld_v / k) or a tuple (address, ld, d); None: the scores a PCA left
+    on the device (a MultiMat); otherwise a host array over all cells, `cells` rows if given."""
+    if device:
+        ptr, ld, d = (points.d_v, points.ld_v, points.k) if isinstance(points, PcaResultDevice) else points
+        return ctypes.c_void_p(int(ptr) if ptr else None), int(ld), int(d)
+    if points is None:
+        return None, 0, 0
+    pts = _f64(np.atleast_2d(points))
+    if cells is not None and pts.shape[0] != cells:
+        raise ScanrsError(6, f"the points have {pts.shape[0]} rows for {cells} cells")
+    return pts, int(pts.shape[1]), int(pts.shape[1])
+
+
 class AdaptiveMat:
     """Device-resident `sqz::AdaptiveMat<N, D, M>` (sqz/src/mat.rs:34-42). Once a low-rank
     offset is installed (`center`, `scale_and_center`, `normalize`) the same object plays
@@ -806,23 +821,12 @@ class AdaptiveMat:
         point set returns for those rows, bit for bit - and with return_sq_dist also the squared distances (+inf in padded slots).
         On an unsharded handle it is `knn` / `knn_device` of the given points."""
         n_local = int(self.shape()[1])
-        keep = None
-        if device:
-            if isinstance(points, PcaResultDevice):
-                ptr, ld, d = points.d_v, int(points.ld_v), int(points.k)
-            else:
-                ptr, ld, d = points
-            ptr = ctypes.c_void_p(int(ptr) if ptr else None)
-        elif points is None:
-            ptr, ld, d = None, 0, 0
-        else:
-            keep = _f64(np.atleast_2d(points))
-            ptr, ld, d = _p(keep), int(keep.shape[1]), int(keep.shape[1])
+        pts, ld, d = _sharded_points(points, device)
         out = np.zeros((n_local, k), dtype=np.uint32)
         sq = np.zeros((n_local, k)) if return_sq_dist else None
-        _check(_lib.scanrs_knn_sharded(self._h, ptr, ctypes.c_int(1 if device else 0), ctypes.c_uint32(ld), ctypes.c_uint32(d),
+        _check(_lib.scanrs_knn_sharded(self._h, pts if device else _p(pts), ctypes.c_int(1 if device else 0), ctypes.c_uint32(ld), ctypes.c_uint32(d),
                                        ctypes.c_uint32(k), _p(out), _p(sq)))
-        del keep
+        del pts
         return (out, sq) if return_sq_dist else out
 
     def nearest_neighbors_sharded(self, points, k: int, distance="euclidean", device: bool = False):
@@ -832,24 +836,13 @@ class AdaptiveMat:
         `nearest_neighbors` of the whole point set returns for those rows, in every bit. On an unsharded handle it is
         `nearest_neighbors` / `nearest_neighbors_device` of the given points."""
         n_local = int(self.shape()[1])
-        keep = None
-        if device:
-            if isinstance(points, PcaResultDevice):
-                ptr, ld, d = points.d_v, int(points.ld_v), int(points.k)
-            else:
-                ptr, ld, d = points
-            ptr = ctypes.c_void_p(int(ptr) if ptr else None)
-        elif points is None:
-            ptr, ld, d = None, 0, 0
-        else:
-            keep = _f64(np.atleast_2d(points))
-            ptr, ld, d = _p(keep), int(keep.shape[1]), int(keep.shape[1])
+        pts, ld, d = _sharded_points(points, device)
         k = int(k)
         idx = np.full((n_local, k), 0xFFFFFFFF, dtype=np.uint32)
         dist = np.full((n_local, k), np.inf, dtype=np.float64)
-        _check(_lib.scanrs_nearest_neighbors_sharded(self._h, ptr, ctypes.c_int(1 if device else 0), ctypes.c_uint32(ld), ctypes.c_uint32(d),
+        _check(_lib.scanrs_nearest_neighbors_sharded(self._h, pts if device else _p(pts), ctypes.c_int(1 if device else 0), ctypes.c_uint32(ld), ctypes.c_uint32(d),
                                                      ctypes.c_uint32(k), ctypes.c_int(_distance_type(distance)), _p(idx), _p(dist)))
-        del keep
+        del pts
         n = int(getattr(self, "_outer_global", 0) or n_local)
         k_eff = min(k, max(n - 1, 0))
         return np.ascontiguousarray(idx[:, :k_eff]), np.ascontiguousarray(dist[:, :k_eff])
@@ -1559,10 +1552,7 @@ class MultiMat:
         or None: every shard searches the scores its last run_pca_bk / run_pca_rand left on its device (V of a genes x cells CSC
         matrix). With return_sq_dist also the squared distances."""
         cells = self.cols if self.storage == CSC else self.rows
-        pts = None if points is None else _f64(np.atleast_2d(points))
-        d = 0 if pts is None else int(pts.shape[1])
-        if pts is not None and pts.shape[0] != cells:
-            raise ScanrsError(6, f"the points have {pts.shape[0]} rows for {cells} cells")
+        pts, d, _ = _sharded_points(points, cells=cells)
         out = np.zeros((cells, k), dtype=np.uint32)
         sq = np.zeros((cells, k)) if return_sq_dist else None
         _check(_lib.scanrs_multi_knn(self._h, _p(pts), ctypes.c_uint32(d), ctypes.c_uint32(d), ctypes.c_uint32(k), _p(out), _p(sq)))
@@ -1574,10 +1564,7 @@ class MultiMat:
         set in every bit. points: a host array over all cells, or None: every shard searches the scores its last run_pca_bk /
         run_pca_rand left on its device."""
         cells = self.cols if self.storage == CSC else self.rows
-        pts = None if points is None else _f64(np.atleast_2d(points))
-        d = 0 if pts is None else int(pts.shape[1])
-        if pts is not None and pts.shape[0] != cells:
-            raise ScanrsError(6, f"the points have {pts.shape[0]} rows for {cells} cells")
+        pts, d, _ = _sharded_points(points, cells=cells)
         return _nearest_neighbors_call(_lib.scanrs_multi_nearest_neighbors, int(cells), int(k), self._h, _p(pts), ctypes.c_uint32(d),
                                        ctypes.c_uint32(d), ctypes.c_uint32(k), ctypes.c_int(_distance_type(distance)))
 

@@ -1142,6 +1142,26 @@ int scanrs_find_nn(const double *queries, uint64_t n_q, const double *points, ui
         knn_host(queries, n_q, points, n_p, d, k, include_self == 0, out);
     });
 }
+// rows [0, n_rows) of a host array (leading dimension ld >= d) into `buf`, through stream s and waited for: the array may be pageable
+static const double *upload_rows(DevBuf<double> &buf, const double *rows, uint64_t n_rows, uint32_t ld, uint32_t d, hipStream_t s) {
+    buf.alloc(std::max<uint64_t>(1, n_rows * ld));
+    if (n_rows && ld >= d) {
+        SCANRS_HIP(hipMemcpyAsync(buf.p, rows, ((n_rows - 1) * ld + d) * 8, hipMemcpyHostToDevice, s));
+        SCANRS_SYNC(s);
+    }
+    return buf.p;
+}
+// The sharded half of scanrs_knn_sharded and scanrs_nearest_neighbors_sharded before their search: the refusals (`name` is the entry
+// point's in their texts) and the rank's rows of the points in device memory. Host points span all the cells and only this rank's
+// rows [begin, begin + n_local) go to the device (into `buf`); device points are the rank's own rows already.
+static const double *rank_rows(scanrs_mat *m, const char *name, const double *points, int points_is_device, uint32_t ld, uint32_t d, bool no_out,
+                               DevBuf<double> &buf) {
+    const Storage &st = *m->st;
+    const uint64_t n_local = m->cols();
+    if (!cols_sharded(m)) fail(SCANRS_ERR_ARGUMENT, "%s: the cells (the columns of this view) must be the sharded dimension", name);
+    if ((!points && (points_is_device ? n_local : st.shard.outer_global)) || (no_out && n_local)) fail(SCANRS_ERR_ARGUMENT, "null argument");
+    return points_is_device ? points : upload_rows(buf, points + st.shard.outer_begin * ld, n_local, ld, d, st.stream);
+}
 // knn over a sharded handle: COLLECTIVE. The handle carries the transport and the rank's range of cells only.
 int scanrs_knn_sharded(scanrs_mat *m, const double *points, int points_is_device, uint32_t ld, uint32_t d, uint32_t k, uint32_t *out,
                        double *sq_dist) {
@@ -1151,34 +1171,18 @@ int scanrs_knn_sharded(scanrs_mat *m, const double *points, int points_is_device
         Storage &st = *m->st;
         st.knn_blocks = st.knn_allreduces = 0;
         const uint64_t n_local = m->cols();
+        DevBuf<double> buf;
         if (!st.shard.active()) { // scanrs_knn / scanrs_knn_device on the given points
             if ((!points && n_local) || (!out && n_local && k)) fail(SCANRS_ERR_ARGUMENT, "null argument");
             need_device();
-            if (points_is_device || !n_local) {
-                knn_device(points, ld, n_local, points, ld, n_local, d, k, true, out, sq_dist);
-            } else {
-                if (ld < d) fail(SCANRS_ERR_ARGUMENT, "knn: leading dimension smaller than the number of coordinates");
-                DevBuf<double> dp(n_local * ld);
-                SCANRS_HIP(hipMemcpy(dp.p, points, n_local * ld * 8, hipMemcpyHostToDevice));
-                knn_device(dp.p, ld, n_local, dp.p, ld, n_local, d, k, true, out, sq_dist);
-            }
+            const bool upload = !points_is_device && n_local;
+            if (upload && ld < d) fail(SCANRS_ERR_ARGUMENT, "knn: leading dimension smaller than the number of coordinates");
+            const double *pts = upload ? upload_rows(buf, points, n_local, ld, d, 0) : points;
+            knn_device(pts, ld, n_local, pts, ld, n_local, d, k, true, out, sq_dist);
             return;
         }
-        if (!cols_sharded(m)) fail(SCANRS_ERR_ARGUMENT, "knn_sharded: the cells (the columns of this view) must be the sharded dimension");
-        const uint64_t begin = st.shard.outer_begin, n = st.shard.outer_global;
-        if ((!points && (points_is_device ? n_local : n)) || (!out && n_local && k)) fail(SCANRS_ERR_ARGUMENT, "null argument");
-        // host points span all the cells and only this rank's rows go to the device; device points are the rank's own rows already
-        DevBuf<double> d_pts;
-        const double *pts = points;
-        if (!points_is_device) {
-            d_pts.alloc(std::max<uint64_t>(1, n_local * ld));
-            if (n_local && ld >= d) {
-                SCANRS_HIP(hipMemcpyAsync(d_pts.p, points + begin * ld, ((n_local - 1) * ld + d) * 8, hipMemcpyHostToDevice, st.stream));
-                SCANRS_SYNC(st.stream); // the caller's array may be pageable
-            }
-            pts = d_pts.p;
-        }
-        knn_sharded(st, pts, ld, begin, n_local, n, d, k, out, sq_dist);
+        const double *pts = rank_rows(m, "knn_sharded", points, points_is_device, ld, d, !out && k, buf);
+        knn_sharded(st, pts, ld, st.shard.outer_begin, n_local, st.shard.outer_global, d, k, out, sq_dist);
         device_free_flush();
     });
 }
@@ -1263,36 +1267,18 @@ int scanrs_nearest_neighbors_sharded(scanrs_mat *m, const double *points, int po
         Storage &st = *m->st;
         st.knn_blocks = st.knn_allreduces = st.knn_blocks_filtered = 0;
         const uint64_t n_local = m->cols();
+        DevBuf<double> buf;
         if (!st.shard.active()) { // scanrs_nearest_neighbors / _device on the given points
             if ((!points && n_local) || ((!indices || !distances) && n_local && k)) fail(SCANRS_ERR_ARGUMENT, "null argument");
             nearest_neighbors_check_args(n_local, ld, d, k, distance_type);
             if (k == 0 || n_local == 0) return;
             need_device();
-            if (points_is_device) {
-                nearest_neighbors_device(points, n_local, ld, d, k, distance_type, indices, distances);
-            } else {
-                DevBuf<double> dp(n_local * ld);
-                SCANRS_HIP(hipMemcpy(dp.p, points, ((n_local - 1) * ld + d) * 8, hipMemcpyHostToDevice));
-                nearest_neighbors_device(dp.p, n_local, ld, d, k, distance_type, indices, distances);
-            }
+            const double *pts = points_is_device ? points : upload_rows(buf, points, n_local, ld, d, 0);
+            nearest_neighbors_device(pts, n_local, ld, d, k, distance_type, indices, distances);
             return;
         }
-        if (!cols_sharded(m))
-            fail(SCANRS_ERR_ARGUMENT, "nearest_neighbors_sharded: the cells (the columns of this view) must be the sharded dimension");
-        const uint64_t begin = st.shard.outer_begin, n = st.shard.outer_global;
-        if ((!points && (points_is_device ? n_local : n)) || ((!indices || !distances) && n_local && k)) fail(SCANRS_ERR_ARGUMENT, "null argument");
-        // host points span all the cells and only this rank's rows go to the device; device points are the rank's own rows already
-        DevBuf<double> d_pts;
-        const double *pts = points;
-        if (!points_is_device) {
-            d_pts.alloc(std::max<uint64_t>(1, n_local * ld));
-            if (n_local && ld >= d) {
-                SCANRS_HIP(hipMemcpyAsync(d_pts.p, points + begin * ld, ((n_local - 1) * ld + d) * 8, hipMemcpyHostToDevice, st.stream));
-                SCANRS_SYNC(st.stream); // the caller's array may be pageable
-            }
-            pts = d_pts.p;
-        }
-        nearest_neighbors_sharded(st, pts, ld, begin, n_local, n, d, k, distance_type, indices, distances);
+        const double *pts = rank_rows(m, "nearest_neighbors_sharded", points, points_is_device, ld, d, (!indices || !distances) && k, buf);
+        nearest_neighbors_sharded(st, pts, ld, st.shard.outer_begin, n_local, st.shard.outer_global, d, k, distance_type, indices, distances);
         device_free_flush();
     });
 }

@@ -1,19 +1,21 @@
 // knn.hip — exact k-nearest-neighbours of the PCA scores (scan-rs/src/nn.rs:38-83), SURVEY.md §8 f4.
 //
 // The reference builds a ball tree (ball_tree crate) over the rows of a cells x d matrix and asks it for the k+1
-// nearest points of every row, dropping the row itself. Same result here by search over all pairs, in two forms:
-//  * knn_kernel (small point sets, d > 58, k > 64): one thread per query (its d coordinates in registers), the candidate point
-//    wave-uniform in SGPRs (scalar loads), the squared distance as the reference forms it (sum of squared differences,
-//    nn.rs:14-21 — not the |p|^2 + |q|^2 - 2 p.q expansion, whose cancellation would reorder near neighbours), a sorted k-list
-//    per thread in private memory. f64 vector FMA bound: n_q x n x d multiply-adds (8 s at 10^6 x 50).
+// nearest points of every row, dropping the row itself. Same result here by search over all pairs: the search of knn_search.hpp under
+// the policy Euclid below - the squared distance as the reference forms it (sum of squared differences, nn.rs:14-21 — not the
+// |p|^2 + |q|^2 - 2 p.q expansion, whose cancellation would reorder near neighbours). This file holds that policy, the bf16-MFMA
+// filter both policies go through (kf_*, knn_filter.hpp) with the derivation of its margin, and the walk over a sharded point set.
+//  * knn_exhaustive_kernel (small point sets, d > 58, k > 64): one thread per query (its d coordinates in registers), the candidate
+//    point wave-uniform in SGPRs (scalar loads of its zero-padded row), a sorted k-list per thread in private memory. f64 vector FMA
+//    bound: n_q x n x d multiply-adds (8 s at 10^6 x 50).
 //  * the filtered form (>= 32768 points, max |coordinate| inside the magnitude window): the distance matrix is GEMM-shaped, so its bulk runs on the matrix cores
 //    (v_mfma_f32_32x32x16_bf16) as a FILTER with a rigorous error margin, and only the few pairs that pass are ranked, by the
-//    exact f64 distance above (kf_* kernels below: 0.54 s at 10^6 x 50, k = 15, identical output; `python tools/knn_bench.py
+//    exact f64 distance above (knn_rerank_kernel: 0.54 s at 10^6 x 50, k = 15, identical output; `python tools/knn_bench.py
 //    1000000 50 15`, same MI355X: 479 ms with the margin 0.0021 this file had until it was re-derived, 102 candidates per query in
 //    the last round; 536 ms and 158 candidates with 0.00395. Subtracting a common centre before kf_prep_* would shrink the
 //    |q|^2 + |p|^2 the margin is relative to and win that back: not done yet).
-//  * over a sharded point set (knn_sharded at the end of this file): the points pass by in global blocks, each block
-//    searched by the two forms above (seeded with what the query already holds) and merged into a running list per query by
+//  * over a sharded point set (knn_sharded_blocks at the end of this file): the points pass by in global blocks, each
+//    block searched by the two forms above (seeded with what the query already holds) and merged into a running list per query by
 //    (squared distance, global index) - knn_merge.hpp. Equal to the search of the whole set bit for bit, whatever the cut.
 // Ties keep ascending index order (the rule of the reference's own test oracle, `exhaustive_knn`, nn.rs:112-137; the ball
 // tree's order among exactly equidistant points is a property of that crate).
@@ -28,6 +30,7 @@
 #include "common.hpp"
 #include "knn_filter.hpp"
 #include "knn_merge.hpp"
+#include "knn_search.hpp"
 #include "knn_shard.hpp"
 #include "shard_exchange.hpp"
 
@@ -35,100 +38,23 @@ namespace scanrs {
 
 namespace {
 
-template <int DMAX, int THREADS>
-__global__ __launch_bounds__(THREADS) void knn_kernel(const double *__restrict__ queries, uint64_t n_q, const double *__restrict__ points,
-                                                     uint64_t n_p, uint32_t d, uint32_t k, int skip_same_index, uint64_t skip_stride,
-                                                     uint64_t p_off, uint64_t q_off, uint32_t *__restrict__ out,
-                                                     double *__restrict__ out_d) {
-    const uint64_t qi = (uint64_t)blockIdx.x * THREADS + threadIdx.x;
-    const bool live = qi < n_q;
-    double q[DMAX];
-#pragma unroll
-    for (int j = 0; j < DMAX; j++) q[j] = (live && (uint32_t)j < d) ? queries[qi * d + j] : 0.0;
-    double best_d[KMAX];
-    uint32_t best_i[KMAX];
-    uint32_t have = 0;
-    double worst = DBL_MAX; // distance a candidate has to beat once the list is full
-    // `points` is the (n_p x DMAX) zero-padded copy: the candidate's coordinates are wave-uniform, so they arrive through
-    // the scalar cache into SGPRs (s_load_dwordx16) and every lane's VALU work is just subtract + fma per coordinate
-    for (uint64_t pi = 0; pi < n_p; pi++) {
-        const double *__restrict__ pt = points + pi * DMAX;
-        double s = 0.0;
-#pragma unroll
-        for (int j = 0; j < DMAX; j++) {
-            const double t = pt[j] - q[j];
-            s = fma(t, t, s);
-        }
-        // candidate pi is row pi * skip_stride of the point set, whose row 0 is global row p_off; query qi is global row q_off + qi
-        if (!live || (skip_same_index && p_off + pi * skip_stride == q_off + qi)) continue;
-        if (have == k && !(s < worst)) continue;
-        // sorted insertion; equal distances stay in index order because candidates arrive in index order
-        uint32_t pos = have < k ? have : k - 1u;
-        while (pos > 0 && best_d[pos - 1] > s) {
-            best_d[pos] = best_d[pos - 1];
-            best_i[pos] = best_i[pos - 1];
-            pos--;
-        }
-        best_d[pos] = s;
-        best_i[pos] = (uint32_t)pi;
-        if (have < k) have++;
-        if (have == k) worst = best_d[k - 1];
+// The squared Euclidean distance as the reference forms it: the sum of squared differences in coordinate order (nn.rs:14-21). Only a
+// subtraction and an explicit fma, which no compile flag changes.
+struct Euclid {
+    static __device__ __forceinline__ double step(double acc, double q, double p) {
+        const double t = p - q;
+        return fma(t, t, acc);
     }
-    if (!live) return;
-    for (uint32_t i = 0; i < k; i++) out[qi * k + i] = i < have ? best_i[i] : 0xFFFFFFFFu; // T::max_value() padding, nn.rs:66
-    if (out_d)
-        for (uint32_t i = 0; i < k; i++) out_d[qi * k + i] = i < have ? best_d[i] : INFINITY;
-}
+    static __device__ __forceinline__ double finish(double acc, double, double) { return acc; }
+    static __device__ __forceinline__ double threshold(double key) { return key; }
+};
 
-// dst row r = src row r * row_stride, zero-padded to dmax columns
-__global__ void pad_points_kernel(const double *__restrict__ src, uint32_t ld, uint64_t n, uint32_t d, uint32_t dmax,
-                                  double *__restrict__ dst, uint64_t row_stride) {
+// dst = src zero-padded to dmax columns
+__global__ void pad_points_kernel(const double *__restrict__ src, uint32_t ld, uint64_t n, uint32_t d, uint32_t dmax, double *__restrict__ dst) {
     const uint64_t e = (uint64_t)blockIdx.x * blockDim.x + threadIdx.x;
     if (e >= n * dmax) return;
-    const uint64_t r = e / dmax;
     const uint32_t j = (uint32_t)(e % dmax);
-    dst[e] = j < d ? src[r * row_stride * ld + j] : 0.0;
-}
-
-template <int DMAX, int THREADS>
-void launch(const double *dq, uint32_t ldq, uint64_t n_q, const double *dp, uint32_t ldp, uint64_t n_p, uint32_t d, uint32_t k, int skip,
-            uint32_t *dout, hipStream_t s, uint64_t p_stride, uint64_t p_off, uint64_t q_off, double *ddist) {
-    // p_stride > 1: the candidates are rows 0, p_stride, 2 p_stride, ... of dp (n_p of them); indices written are subset-local
-    // zero-padded (n x DMAX) copies: the candidate's coordinates arrive as whole scalar-cache lines, the query's as one run per thread
-    DevBuf<double> pp, qp;
-    pp.alloc(n_p * DMAX ? n_p * DMAX : 1);
-    if (n_p)
-        hipLaunchKernelGGL(pad_points_kernel, dim3((unsigned)((n_p * DMAX + 255) / 256)), dim3(256), 0, s, dp, ldp, n_p, d, (uint32_t)DMAX, pp.p, p_stride);
-    const double *q = pp.p;
-    if (dq != dp || n_q != n_p || ldq != ldp || p_stride != 1) {
-        qp.alloc(n_q * DMAX);
-        hipLaunchKernelGGL(pad_points_kernel, dim3((unsigned)((n_q * DMAX + 255) / 256)), dim3(256), 0, s, dq, ldq, n_q, d, (uint32_t)DMAX, qp.p, (uint64_t)1);
-        q = qp.p;
-    }
-    const dim3 grid((unsigned)((n_q + THREADS - 1) / THREADS)), block(THREADS);
-    hipLaunchKernelGGL((knn_kernel<DMAX, THREADS>), grid, block, 0, s, q, n_q, pp.p, n_p, (uint32_t)DMAX, k, skip, p_stride, p_off, q_off, dout,
-                       ddist);
-    SCANRS_SYNC(s); // the padded copies are released on return
-}
-
-// exhaustive search of every query against rows 0, p_stride, 2 p_stride, ... of the point set (n_sub of them); subset-local indices.
-// p_off / q_off: the global rows of point row 0 and of query 0 (what the self exclusion compares); ddist: the k squared distances
-// beside the indices (+inf in padded slots), or nullptr
-void exhaustive(hipStream_t s, const double *dq, uint32_t ldq, uint64_t n_q, const double *dp, uint32_t ldp, uint64_t n_sub, uint32_t d,
-                uint32_t k, int skip, uint32_t *dout, uint64_t p_stride = 1, uint64_t p_off = 0, uint64_t q_off = 0, double *ddist = nullptr) {
-    if (d <= 8)
-        launch<8, 256>(dq, ldq, n_q, dp, ldp, n_sub, d, k, skip, dout, s, p_stride, p_off, q_off, ddist);
-    else if (d <= 16)
-        launch<16, 256>(dq, ldq, n_q, dp, ldp, n_sub, d, k, skip, dout, s, p_stride, p_off, q_off, ddist);
-    else if (d <= 32)
-        launch<32, 256>(dq, ldq, n_q, dp, ldp, n_sub, d, k, skip, dout, s, p_stride, p_off, q_off, ddist);
-    else if (d <= 52) // top-50 PCA scores, the default of scan-rs-cmd (tools/src/bin/cmd.rs:46-48)
-        launch<52, 256>(dq, ldq, n_q, dp, ldp, n_sub, d, k, skip, dout, s, p_stride, p_off, q_off, ddist);
-    else if (d <= 64)
-        launch<64, 256>(dq, ldq, n_q, dp, ldp, n_sub, d, k, skip, dout, s, p_stride, p_off, q_off, ddist);
-    else
-        launch<128, 64>(dq, ldq, n_q, dp, ldp, n_sub, d, k, skip, dout, s, p_stride, p_off, q_off, ddist);
-    SCANRS_HIP(hipGetLastError());
+    dst[e] = j < d ? src[(e / dmax) * ld + j] : 0.0;
 }
 
 // ---------------------------------------------------------------------------------------------------------------------
@@ -370,125 +296,6 @@ __global__ __launch_bounds__(256, 2) void kf_filter_kernel(const uint16_t *__res
     kf_flush(lane, min(park_n[wave], KF_BUF), park[wave], cand, cnt);
 }
 
-// exact f64 ranking of a query's candidates: one wave per query, a candidate per lane (the same fma chain over the coordinates as
-// knn_kernel), then k rounds of a wave-wide lexicographic (distance, index) minimum. Writes the k neighbours (UINT32_MAX padded)
-// and tau = the k-th distance (+inf when fewer than k exist). Overflowed lists (cnt > KF_CAP) are left to the exhaustive kernel.
-__global__ __launch_bounds__(256) void kf_rerank_kernel(const double *__restrict__ Q, uint32_t ldq, uint64_t n_q, const double *__restrict__ P,
-                                                        uint32_t ldp, uint32_t d, uint32_t k, int skip_same_index, uint64_t p_off,
-                                                        uint64_t q_off, const uint32_t *__restrict__ cand, const uint32_t *__restrict__ cnt,
-                                                        uint32_t *__restrict__ out, double *__restrict__ out_d, double *__restrict__ tau) {
-    const uint32_t lane = threadIdx.x & 63u;
-    const uint64_t q = (uint64_t)blockIdx.x * 4u + (threadIdx.x >> 6);
-    if (q >= n_q) return;
-    const uint32_t c = cnt[q];
-    if (c > KF_CAP) return; // the host reads cnt and redoes this query exhaustively
-    double dist[KF_PER_LANE];
-    uint32_t idx[KF_PER_LANE];
-    const double *__restrict__ qr = Q + q * ldq;
-#pragma unroll
-    for (uint32_t u = 0; u < KF_PER_LANE; u++) {
-        const uint32_t j = u * 64u + lane;
-        dist[u] = DBL_MAX;
-        idx[u] = 0xFFFFFFFFu;
-        if (j < c) {
-            const uint32_t p = cand[q * KF_CAP + j];
-            if (!(skip_same_index && p_off + p == q_off + q)) { // global rows: the offsets are 0 unless the points are one block of a sharded set
-                const double *__restrict__ pr = P + (uint64_t)p * ldp;
-                double s = 0.0;
-                for (uint32_t t = 0; t < d; t++) {
-                    const double df = pr[t] - qr[t];
-                    s = fma(df, df, s);
-                }
-                dist[u] = s;
-                idx[u] = p;
-            }
-        }
-    }
-    double kth = DBL_MAX;
-    for (uint32_t it = 0; it < k; it++) {
-        // lane-local minimum, then the wave's
-        double bd = DBL_MAX;
-        uint32_t bi = 0xFFFFFFFFu;
-#pragma unroll
-        for (uint32_t u = 0; u < KF_PER_LANE; u++)
-            if (dist[u] < bd || (dist[u] == bd && idx[u] < bi)) {
-                bd = dist[u];
-                bi = idx[u];
-            }
-        double wd = bd;
-        uint32_t wi = bi;
-#pragma unroll
-        for (int off = 32; off >= 1; off >>= 1) {
-            const double od = __shfl_xor(wd, off, 64);
-            const uint32_t oi = (uint32_t)__shfl_xor((int)wi, off, 64);
-            if (od < wd || (od == wd && oi < wi)) {
-                wd = od;
-                wi = oi;
-            }
-        }
-        if (lane == 0) out[q * k + it] = wi;
-        if (lane == 0 && out_d) out_d[q * k + it] = wi == 0xFFFFFFFFu ? INFINITY : wd;
-        if (wi == 0xFFFFFFFFu) { // fewer than k candidates: the rest is padding
-            for (uint32_t r2 = it + 1; r2 < k; r2++)
-                if (lane == 0) {
-                    out[q * k + r2] = 0xFFFFFFFFu;
-                    if (out_d) out_d[q * k + r2] = INFINITY;
-                }
-            kth = DBL_MAX;
-            break;
-        }
-        kth = wd;
-        // the owner retires that entry (indices are unique within a list: a point is appended once per round)
-#pragma unroll
-        for (uint32_t u = 0; u < KF_PER_LANE; u++)
-            if (idx[u] == wi) {
-                dist[u] = DBL_MAX;
-                idx[u] = 0xFFFFFFFFu;
-            }
-    }
-    if (lane == 0) tau[q] = kth == DBL_MAX ? INFINITY : kth;
-}
-
-// tau of round 0 from the exhaustive search on the coarsest subset: exact distance to the k-th neighbour found there
-__global__ void kf_tau0_kernel(const double *__restrict__ Q, uint32_t ldq, uint64_t n_q, const double *__restrict__ P, uint32_t ldp,
-                               uint32_t d, uint32_t k, uint64_t stride, const uint32_t *__restrict__ nbr, double *__restrict__ tau) {
-    const uint64_t q = (uint64_t)blockIdx.x * blockDim.x + threadIdx.x;
-    if (q >= n_q) return;
-    const uint32_t t = nbr[q * k + (k - 1u)];
-    if (t == 0xFFFFFFFFu) {
-        tau[q] = INFINITY;
-        return;
-    }
-    const double *pr = P + (uint64_t)t * stride * ldp, *qr = Q + q * ldq;
-    double s = 0.0;
-    for (uint32_t j = 0; j < d; j++) {
-        const double df = pr[j] - qr[j];
-        s = fma(df, df, s);
-    }
-    tau[q] = s;
-}
-
-__global__ void kf_gather_rows_kernel(const double *__restrict__ src, uint32_t ld, uint32_t d, const uint32_t *__restrict__ rows, uint64_t n,
-                                      double *__restrict__ dst) {
-    const uint64_t e = (uint64_t)blockIdx.x * blockDim.x + threadIdx.x;
-    if (e >= n * d) return;
-    dst[e] = src[(uint64_t)rows[e / d] * ld + (e % d)];
-}
-template <typename T>
-__global__ void kf_scatter_result_kernel(const T *__restrict__ res, const uint32_t *__restrict__ rows, uint64_t n, uint32_t k,
-                                         T *__restrict__ out) {
-    const uint64_t e = (uint64_t)blockIdx.x * blockDim.x + threadIdx.x;
-    if (e >= n * k) return;
-    out[(uint64_t)rows[e / k] * k + (e % k)] = res[e];
-}
-// a seeded search (one block of a sharded point set): no threshold above the k-th distance the query already holds
-// from the blocks before (seed[q * seed_ld]; +inf while it holds fewer than k)
-__global__ void kf_seed_kernel(double *__restrict__ tau, const double *__restrict__ seed, uint64_t seed_ld, uint64_t n) {
-    const uint64_t q = (uint64_t)blockIdx.x * blockDim.x + threadIdx.x;
-    if (q >= n) return;
-    tau[q] = fmin(tau[q], seed[q * seed_ld]);
-}
-
 // what the last scanrs_knn* / scanrs_find_nn / scanrs_nearest_neighbors* call of the process did (KnnLastStats, knn_filter.hpp)
 std::mutex g_stats_mutex;
 KnnLastStats g_last_stats;
@@ -569,139 +376,27 @@ void kf_h2d(hipStream_t s, void *dst, const void *src, size_t bytes) {
     SCANRS_HIP(hipMemcpyAsync(dst, src, bytes, hipMemcpyHostToDevice, s));
     SCANRS_SYNC(s); // the source is pageable and the caller's again on return
 }
-void kf_d2d(hipStream_t s, void *dst, const void *src, size_t bytes) {
-    if (!s)
-        SCANRS_HIP(hipMemcpy(dst, src, bytes, hipMemcpyDeviceToDevice));
-    else
-        SCANRS_HIP(hipMemcpyAsync(dst, src, bytes, hipMemcpyDeviceToDevice, s));
-}
 
 namespace {
 
-// where a search stands in a larger one (all defaults: the points are the whole set and the queries its rows, as in scanrs_knn)
-struct KnnPlace {
-    uint64_t p_off = 0, q_off = 0;   // the global rows of point row 0 and of query 0: the self exclusion compares global rows
-    const double *seed = nullptr;    // seeded search: per query the k-th distance it already holds, element q * seed_ld
-    uint64_t seed_ld = 0;
-    const KfQueries *queries = nullptr; // the query side prepared once for all blocks
-};
-
-bool knn_filtered(hipStream_t s, const double *dq, uint32_t ldq, uint64_t n_q, const double *dp, uint32_t ldp, uint64_t n_p, uint32_t d,
-                  uint32_t k, int skip, uint32_t *dout, double *ddist, KnnLastStats &stats, const KnnPlace &pl) {
-    const GlobalOptions &go = global_options(); // scanrs_set_global_option (read per call: tests flip them)
-    const bool off = go.knn_exhaustive != 0;
-    const uint64_t min_points = go.knn_filter_min_points;
-    if (off || d > KF_DMAX || n_p < min_points || k > KF_KMAX || n_q < KF_NQ_MIN) return false;
-    const uint64_t n0_max = pl.seed ? KF_SEED_N0 : KF_CAP;
-    auto seed_tau = [&](double *tau) {
-        if (pl.seed) hipLaunchKernelGGL(kf_seed_kernel, dim3((unsigned)((n_q + 255) / 256)), dim3(256), 0, s, tau, pl.seed, pl.seed_ld, n_q);
+// One Euclidean search (knn_search.hpp) of device rows: queries and points are read where they lie; the zero-padded copy of the points
+// that the exhaustive kernel loads by whole rows is made when that kernel first runs (the filter declined, or a list overflowed).
+// true: the filter answered
+bool euclid_search(hipStream_t s, const double *dq, uint32_t ldq, uint64_t n_q, const double *dp, uint32_t ldp, uint64_t n_p, uint32_t d,
+                   uint32_t k, const KnnPlace &pl, uint32_t *dout, double *ddist, KnnLastStats &stats) {
+    DevBuf<double> pad;
+    KnnRows Q{dq, ldq, nullptr, dq, ldq, n_q, true}, P{dp, ldp, nullptr, dp, ldp, n_p, true};
+    P.padded = [&] {
+        const uint32_t dmax = knn_dmax(d);
+        if (!pad.p) {
+            pad.alloc(std::max<uint64_t>(1, n_p * dmax));
+            if (n_p) hipLaunchKernelGGL(pad_points_kernel, dim3((unsigned)((n_p * dmax + 255) / 256)), dim3(256), 0, s, dp, ldp, n_p, d, dmax, pad.p);
+        }
+        return (const double *)pad.p;
     };
-    // nested strided subsets S_0 < S_1 < ... < all points: S_0 (at most KF_CAP points) is ranked exactly for every query, which gives
-    // an upper bound tau of the k-th distance; every further subset is `ratio` times denser and goes through the filter with the
-    // previous tau, which lets about k * ratio * (volume inflation of the margin) pairs per query through.
-    const uint64_t ratio = std::max<uint64_t>(2, go.knn_ratio); // default 4: 1M x 50, k = 15: 487 ms at 4, 553 at 8, 606 at 16 (fewer passes, but longer candidate lists and the first overflows)
-    const bool print_stats = go.knn_stats != 0;
-    std::vector<uint64_t> strides;
-    uint64_t st0 = 1;
-    while ((n_p + st0 - 1) / st0 > n0_max) st0 *= 2;
-    for (uint64_t st = st0; st > 1;) {
-        st = st / ratio > 0 ? st / ratio : 1;
-        strides.push_back(st);
-    }
-    if (strides.empty()) return false;
-    KfOperands op;
-    if (!kf_prepare(s, dq, ldq, n_q, dp, ldp, n_p, d, op, pl.queries)) return false; // outside the magnitude window: the exhaustive kernel answers
-    stats.first_stride = st0;
-    DevBuf<double> tau(n_q);
-    DevBuf<uint32_t> cnt(n_q), cand(n_q * KF_CAP);
-    { // round 0: exact ranking of the coarsest subset
-        const uint32_t n0 = (uint32_t)((n_p + st0 - 1) / st0);
-        hipLaunchKernelGGL(kf_fill_all_kernel, dim3((unsigned)((n_q * n0 + 255) / 256)), dim3(256), 0, s, n_q, n0, st0, cand.p, cnt.p);
-        hipLaunchKernelGGL(kf_rerank_kernel, dim3((unsigned)((n_q + 3) / 4)), dim3(256), 0, s, dq, ldq, n_q, dp, ldp, d, k, skip, pl.p_off, pl.q_off,
-                           cand.p, cnt.p, dout, ddist, tau.p);
-        seed_tau(tau.p);
-    }
-    std::vector<uint32_t> h_cnt(n_q);
-    for (uint64_t st : strides) {
-        const uint64_t n_sub = (n_p + st - 1) / st;
-        kf_filter_pass(s, op, tau.p, n_q, n_p, st, cand.p, cnt.p);
-        hipLaunchKernelGGL(kf_rerank_kernel, dim3((unsigned)((n_q + 3) / 4)), dim3(256), 0, s, dq, ldq, n_q, dp, ldp, d, k, skip, pl.p_off, pl.q_off,
-                           cand.p, cnt.p, dout, ddist, tau.p);
-        seed_tau(tau.p);
-        SCANRS_HIP(hipGetLastError());
-        // overflowed lists (rare: heavy ties, adversarial clusters): those queries are redone exhaustively on this subset
-        kf_d2h(s, h_cnt.data(), cnt.p, n_q * 4);
-        KfRound rd{st, n_sub, 0, 0, 0};
-        std::vector<uint32_t> rows;
-        for (uint64_t q = 0; q < n_q; q++) {
-            const uint32_t c = h_cnt[q];
-            rd.cand_sum += c; // an overflowed list counts with what its counter reached
-            rd.cand_max = std::max(rd.cand_max, c);
-            if (c > KF_CAP) rows.push_back((uint32_t)q);
-        }
-        rd.overflowed = (uint32_t)rows.size();
-        stats.rounds.push_back(rd);
-        if (print_stats)
-            fprintf(stderr, "[scanrs knn] stride %llu: %llu points, candidates per query mean %.1f max %u, %u lists overflowed\n",
-                    (unsigned long long)st, (unsigned long long)n_sub, (double)rd.cand_sum / (double)n_q, rd.cand_max, rd.overflowed);
-        if (!rows.empty()) {
-            const uint64_t m = rows.size();
-            DevBuf<uint32_t> d_rows(m), res(m * k);
-            DevBuf<double> qsel(m * d), tsel(m);
-            kf_h2d(s, d_rows.p, rows.data(), m * 4);
-            hipLaunchKernelGGL(kf_gather_rows_kernel, dim3((unsigned)((m * d + 255) / 256)), dim3(256), 0, s, dq, ldq, d, d_rows.p, m, qsel.p);
-            // the self-exclusion rule compares row numbers, which the gathered copy has lost: search for k + 1 and drop the query's own row on the host
-            const uint32_t kk = std::min<uint32_t>(k + (skip ? 1u : 0u), KMAX);
-            DevBuf<uint32_t> res2(m * kk);
-            DevBuf<double> dist2, dres;
-            if (ddist) {
-                dist2.alloc(m * kk);
-                dres.alloc(m * k);
-            }
-            exhaustive(s, qsel.p, d, m, dp, ldp, n_sub, d, kk, 0, res2.p, st, 0, 0, dist2.p);
-            std::vector<uint32_t> h_res(m * kk), h_out(m * k);
-            std::vector<double> h_dist(ddist ? m * kk : 0), h_dout(ddist ? m * k : 0);
-            kf_d2h(s, h_res.data(), res2.p, m * kk * 4);
-            if (ddist) kf_d2h(s, h_dist.data(), dist2.p, m * kk * 8);
-            for (uint64_t i = 0; i < m; i++) {
-                uint32_t w = 0;
-                for (uint32_t j = 0; j < kk && w < k; j++) {
-                    const uint32_t t = h_res[i * kk + j];
-                    const uint64_t prow = t == 0xFFFFFFFFu ? 0xFFFFFFFFull : (uint64_t)t * st;
-                    if (skip && t != 0xFFFFFFFFu && pl.p_off + prow == pl.q_off + rows[i]) continue; // the query's own (global) row
-                    if (ddist) h_dout[i * k + w] = t == 0xFFFFFFFFu ? INFINITY : h_dist[i * kk + j];
-                    h_out[i * k + w++] = t == 0xFFFFFFFFu ? 0xFFFFFFFFu : (uint32_t)prow;
-                }
-                for (; w < k; w++) {
-                    if (ddist) h_dout[i * k + w] = INFINITY;
-                    h_out[i * k + w] = 0xFFFFFFFFu;
-                }
-            }
-            kf_h2d(s, res.p, h_out.data(), m * k * 4);
-            hipLaunchKernelGGL(kf_scatter_result_kernel<uint32_t>, dim3((unsigned)((m * k + 255) / 256)), dim3(256), 0, s, res.p, d_rows.p, m, k, dout);
-            if (ddist) {
-                kf_h2d(s, dres.p, h_dout.data(), m * k * 8);
-                hipLaunchKernelGGL(kf_scatter_result_kernel<double>, dim3((unsigned)((m * k + 255) / 256)), dim3(256), 0, s, dres.p, d_rows.p, m, k, ddist);
-            }
-            // their thresholds for the next round: exact distance to the k-th neighbour just found (row indices now)
-            if (st != 1) {
-                DevBuf<uint32_t> nb(n_q * k);
-                kf_d2d(s, nb.p, dout, n_q * k * 4);
-                DevBuf<double> tau2(n_q);
-                hipLaunchKernelGGL(kf_tau0_kernel, dim3((unsigned)((n_q + 255) / 256)), dim3(256), 0, s, dq, ldq, n_q, dp, ldp, d, k, (uint64_t)1, nb.p,
-                                   tau2.p);
-                std::vector<double> h_t(n_q), h_t2(n_q);
-                kf_d2h(s, h_t.data(), tau.p, n_q * 8);
-                kf_d2h(s, h_t2.data(), tau2.p, n_q * 8);
-                for (uint32_t rq : rows) h_t[rq] = h_t2[rq];
-                kf_h2d(s, tau.p, h_t.data(), n_q * 8);
-                seed_tau(tau.p);
-            }
-        }
-    }
-    SCANRS_SYNC(s);
-    stats.filtered = true;
-    return true;
+    const bool filtered = knn_search<Euclid>(s, "knn", Q, P, d, k, pl, dout, ddist, stats);
+    if (pad.p) SCANRS_SYNC(s); // the padded copy is released on return
+    return filtered;
 }
 
 } // namespace
@@ -771,12 +466,10 @@ void knn_device_into(const double *d_queries, uint32_t ld_q, uint64_t n_q, const
                      uint32_t k, bool skip_same_index, uint32_t *d_out, double *d_sq) {
     if (k == 0 || n_q == 0) return;
     knn_check_args(ld_q, ld_p, n_p, d, k);
-    const int skip = skip_same_index ? 1 : 0;
+    KnnPlace pl;
+    pl.skip = skip_same_index ? 1 : 0;
     KnnLastStats stats;
-    if (!knn_filtered(0, d_queries, ld_q, n_q, d_points, ld_p, n_p, d, k, skip, d_out, d_sq, stats, KnnPlace())) {
-        stats = KnnLastStats(); // declined (possibly after the magnitude check): nothing of the filter ran
-        exhaustive(0, d_queries, ld_q, n_q, d_points, ld_p, n_p, d, k, skip, d_out, 1, 0, 0, d_sq);
-    }
+    euclid_search(0, d_queries, ld_q, n_q, d_points, ld_p, n_p, d, k, pl, d_out, d_sq, stats);
     SCANRS_HIP(hipGetLastError());
     knn_publish_stats(std::move(stats));
 }
@@ -842,17 +535,9 @@ void knn_sharded_blocks(Storage &st, const double *d_pts, uint32_t ld, uint64_t 
     hipLaunchKernelGGL(ks_fill_kernel, dim3((unsigned)((n_list + 255) / 256)), dim3(256), 0, s, rd[0].p, n_list, (double)INFINITY);
     SCANRS_HIP(hipMemsetAsync(ri[0].p, 0xFF, n_list * 4, s));
 
-    // 3. The query side of the filter, once for all blocks - when a block can take the filter at all (the tests of knn_filtered).
-    const GlobalOptions &go = global_options();
-    const uint64_t block_rows = std::max<uint64_t>(1, go.knn_block_rows);
-    const uint64_t largest = std::min(block_rows, n);
-    KfQueries qs;
-    const bool may_filter =
-        !bs.search && !go.knn_exhaustive && d <= KF_DMAX && k <= KF_KMAX && n_local >= KF_NQ_MIN && largest >= go.knn_filter_min_points;
-    if (may_filter) kf_prepare_queries(s, d_pts, ld, n_local, d, qs);
-
-    // 4. The blocks. The cut is global, so every rank walks the same blocks and the exchange steps pair up.
-    DevBuf<unsigned long long> xbuf(largest * d);
+    // 3. The blocks. The cut is global, so every rank walks the same blocks and the exchange steps pair up.
+    const uint64_t block_rows = std::max<uint64_t>(1, global_options().knn_block_rows);
+    DevBuf<unsigned long long> xbuf(std::min(block_rows, n) * d);
     KnnLastStats stats;
     for (uint64_t b0 = 0; b0 < n; b0 += block_rows) {
         const uint64_t rows = std::min(block_rows, n - b0);
@@ -867,20 +552,7 @@ void knn_sharded_blocks(Storage &st, const double *d_pts, uint32_t ld, uint64_t 
         const double *blk = reinterpret_cast<const double *>(xbuf.p);
         if (st.prof.on) st.prof.begin(s, "knn_search", (double)(rows + n_local) * d * 8.0);
         stats = KnnLastStats();
-        if (bs.search) {
-            bs.search(s, blk, rows, b0, rd[cur].p + (k - 1), bidx.p, bdist.p, stats);
-        } else {
-            KnnPlace pl;
-            pl.p_off = b0;
-            pl.q_off = begin;
-            pl.seed = rd[cur].p + (k - 1);
-            pl.seed_ld = k;
-            pl.queries = may_filter ? &qs : nullptr;
-            if (!knn_filtered(s, d_pts, ld, n_local, blk, d, rows, d, k, 1, bidx.p, bdist.p, stats, pl)) {
-                stats = KnnLastStats();
-                exhaustive(s, d_pts, ld, n_local, blk, d, rows, d, k, 1, bidx.p, 1, b0, begin, bdist.p);
-            }
-        }
+        bs.search(s, blk, rows, b0, rd[cur].p + (k - 1), bidx.p, bdist.p, stats);
         if (st.prof.on) st.prof.end(s);
         if (st.prof.on) st.prof.begin(s, "knn_merge", (double)n_local * k * 36.0);
         hipLaunchKernelGGL(ks_merge_kernel, dim3((unsigned)((n_local + 3) / 4)), dim3(256), 0, s, n_local, k, rd[cur].p, ri[cur].p, bdist.p, bidx.p,
@@ -901,9 +573,35 @@ void knn_sharded_blocks(Storage &st, const double *d_pts, uint32_t ld, uint64_t 
     }
 }
 
+// The walk with the Euclidean search of one block: the query side of the filter is prepared once, when the first block arrives (the
+// first exchange has checked the arguments by then) and where a block can take the filter at all (the tests of knn_filtered). That
+// preparation - one max-abs pass and one operand pass over the rank's rows - therefore counts in the "knn_search" profile scope of
+// block 0, as it does in nearest_neighbors_sharded.
+void knn_sharded_euclidean(Storage &st, const double *d_pts, uint32_t ld, uint64_t begin, uint64_t n_local, uint64_t n, uint32_t d, uint32_t k,
+                           KnnBlockSearch bs, uint32_t *out, double *keys) {
+    const GlobalOptions &go = global_options();
+    const uint64_t largest = std::min<uint64_t>(std::max<uint64_t>(1, go.knn_block_rows), n);
+    const bool may_filter = !go.knn_exhaustive && d <= KF_DMAX && k <= KF_KMAX && n_local >= KF_NQ_MIN && largest >= go.knn_filter_min_points;
+    KfQueries qs;
+    bool ready = false;
+    bs.search = [&](hipStream_t s, const double *blk, uint64_t rows, uint64_t b0, const double *seed, uint32_t *bidx, double *bkey,
+                    KnnLastStats &stats) {
+        if (may_filter && !ready) kf_prepare_queries(s, d_pts, ld, n_local, d, qs);
+        ready = true;
+        KnnPlace pl;
+        pl.p_off = b0;
+        pl.q_off = begin;
+        pl.seed = seed;
+        pl.seed_ld = k;
+        pl.queries = may_filter ? &qs : nullptr;
+        euclid_search(s, d_pts, ld, n_local, blk, d, rows, d, k, pl, bidx, bkey, stats);
+    };
+    knn_sharded_blocks(st, d_pts, ld, begin, n_local, n, d, k, bs, out, keys);
+}
+
 void knn_sharded(Storage &st, const double *d_pts, uint32_t ld, uint64_t begin, uint64_t n_local, uint64_t n, uint32_t d, uint32_t k,
                  uint32_t *out, double *sq_dist) {
-    knn_sharded_blocks(st, d_pts, ld, begin, n_local, n, d, k, KnnBlockSearch(), out, sq_dist);
+    knn_sharded_euclidean(st, d_pts, ld, begin, n_local, n, d, k, KnnBlockSearch(), out, sq_dist);
 }
 
 void knn_host_merge(uint32_t k, const double *da, const uint32_t *ia, const double *db, const uint32_t *ib, double *dout, uint32_t *iout) {

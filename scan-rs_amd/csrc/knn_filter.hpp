@@ -1,6 +1,7 @@
-// knn_filter.hpp — what the searches built on the bf16-MFMA filter share (knn.hip: squared Euclidean distance; knn_metric.hip:
-// Pearson and cosine distance on standardised rows). The derivation of the margin and the kernels themselves are in knn.hip; this
-// header holds the filter's constants, the operands of one filtered search, its statistics and the host side of one filter pass.
+// knn_filter.hpp — the bf16-MFMA filter under the filtered route of knn_search.hpp (knn.hip: squared Euclidean distance;
+// knn_metric.hip: Pearson and cosine distance on standardised rows). The derivation of the margin and the kernels themselves are in
+// knn.hip; this header holds the filter's constants, the operands of one filtered search, its statistics and the host side of one
+// filter pass.
 #pragma once
 #include <hip/hip_runtime.h>
 
@@ -22,7 +23,7 @@ constexpr double KF_GAMMA = 0.00395;
 constexpr double KF_COORD_MIN = 0x1p-48, KF_COORD_MAX = 0x1p46; // the magnitude window of max |coordinate|
 constexpr float KF_SENTINEL = 1e30f; // N of a sentinel point row, -A of a sentinel query row
 constexpr double KF_A_PASS = 9e29;   // A of "everything passes": above every legitimate A, below the sentinel
-constexpr uint32_t KF_PER_LANE = KF_CAP / 64u; // candidates a lane of the rerank kernels holds
+constexpr uint32_t KF_PER_LANE = KF_CAP / 64u; // candidates a lane of the rerank kernel holds
 // Round 0 of a seeded search only tightens a threshold the earlier blocks have set already, and it is paid once per block: its
 // exactly ranked subset is a quarter of what an unseeded search ranks, one more filter round in exchange.
 constexpr uint64_t KF_SEED_N0 = KF_CAP / 4;
@@ -68,9 +69,8 @@ void kf_filter_pass(hipStream_t s, const KfOperands &op, const double *tau, uint
 // (non-blocking) stream queues them there and waits for that stream alone, bounded like every wait of the library.
 void kf_d2h(hipStream_t s, void *dst, const void *src, size_t bytes);
 void kf_h2d(hipStream_t s, void *dst, const void *src, size_t bytes);
-void kf_d2d(hipStream_t s, void *dst, const void *src, size_t bytes);
 
-// round 0: every query's candidate list = the whole coarsest subset (rows 0, stride, 2 stride, ...), ranked exactly by a rerank kernel
+// round 0: every query's candidate list = the whole coarsest subset (rows 0, stride, 2 stride, ...), ranked exactly by the rerank kernel
 static __global__ void kf_fill_all_kernel(uint64_t n_q, uint32_t n_sub, uint64_t stride, uint32_t *__restrict__ cand, uint32_t *__restrict__ cnt) {
     const uint64_t e = (uint64_t)blockIdx.x * blockDim.x + threadIdx.x;
     if (e >= n_q * n_sub) return;

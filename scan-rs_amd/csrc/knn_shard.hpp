@@ -21,8 +21,7 @@ namespace scanrs {
 // queries: block-LOCAL indices and keys, n_local x k, sorted by (key, index), padded with (UINT32_MAX, +inf). seed[q * k] is the k-th
 // key query q holds from the blocks before (+inf while it holds fewer than k): a search may drop every pair whose key is not below
 // it. Blocks arrive in ascending global index, so such a pair has a larger global index than every entry it could tie with, and the
-// merge would drop it too. `finish` turns the running keys (count of them, padding +inf) into what the caller gets. An empty `search`
-// is the squared Euclidean search of knn.hip.
+// merge would drop it too. `finish` turns the running keys (count of them, padding +inf) into what the caller gets.
 struct KnnBlockSearch {
     const char *name = "knn_sharded"; // of the entry point, for its refusals
     const char *check = "knn";
@@ -35,6 +34,10 @@ struct KnnBlockSearch {
 // knn.hip. out / keys: host arrays over the rank's rows, GLOBAL indices. Counts st.knn_blocks / st.knn_allreduces.
 void knn_sharded_blocks(Storage &st, const double *d_pts, uint32_t ld, uint64_t begin, uint64_t n_local, uint64_t n, uint32_t d, uint32_t k,
                         const KnnBlockSearch &bs, uint32_t *out, double *keys);
+// knn.hip. The walk with the squared Euclidean search of one block as bs.search (knn_sharded; nearest_neighbors_sharded under
+// Euclidean distance, whose `finish` is the square root)
+void knn_sharded_euclidean(Storage &st, const double *d_pts, uint32_t ld, uint64_t begin, uint64_t n_local, uint64_t n, uint32_t d, uint32_t k,
+                           KnnBlockSearch bs, uint32_t *out, double *keys);
 
 static __global__ void ks_fill_kernel(double *__restrict__ x, uint64_t n, double v) {
     const uint64_t e = (uint64_t)blockIdx.x * blockDim.x + threadIdx.x;

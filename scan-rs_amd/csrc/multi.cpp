@@ -743,31 +743,39 @@ int scanrs_multi_merge_clusters(scanrs_multi *mm, int transposed, const double *
 }
 
 // ---- knn over the shards (nn.rs:38-83) -----------------------------------------------------------------------------------
-// scanrs_knn_sharded on every shard at once. The cells are the sharded dimension (the columns of a CSC matrix, the rows of a CSR
-// one, which goes through its transposed view); every shard writes its own rows of the caller's arrays. points == NULL: every shard
-// searches the factor along the sharded dimension that its last scanrs_multi_pca_bk / _rand left on its device (V of a genes x cells
-// CSC matrix, U of a cells x genes CSR one), where that factor has the shard's own rows.
-int scanrs_multi_knn(scanrs_multi *mm, const double *points, uint32_t ld, uint32_t d, uint32_t k, uint32_t *out, double *sq_dist) {
-    if (!mm) return bad_argument("null handle");
-    const uint64_t cells = mm->bounds.back();
-    if (cells && k && !out) return bad_argument("null argument");
+namespace {
+// the points of shard i for a scanrs_*_sharded search: the caller's host array over all cells, or the factor along the sharded
+// dimension that the shard's last PCA left on its device. search(handle, points, points_is_device, ld, d, first cell of the shard)
+int multi_search_points(scanrs_multi *mm, const char *name, const double *points, uint32_t ld, uint32_t d,
+                        const std::function<int(scanrs_mat *, const double *, int, uint32_t, uint32_t, uint64_t)> &search) {
     const int transposed = mm->storage == SCANRS_CSR;
     return collective(mm, transposed, nullptr, [&](size_t i, scanrs_mat *h, const scanrs_snoop *, ShardOutputs &) {
         const uint64_t lo = mm->bounds[i], n_loc = mm->bounds[i + 1] - lo;
-        uint32_t *o = out ? out + lo * k : nullptr;
-        double *sq = sq_dist ? sq_dist + lo * k : nullptr;
-        if (points) return scanrs_knn_sharded(h, points, 0, ld, d, k, o, sq);
+        if (points) return search(h, points, 0, ld, d, lo);
         const double *du = nullptr, *dv = nullptr;
         uint32_t ldu = 0, ldv = 0, kk = 0;
         if (const int rc = scanrs_pca_result_device(mm->shards[i], &du, &ldu, &dv, &ldv, &kk)) return rc; // "no PCA result on this handle yet"
         const Storage::PcaDev &r = mm->shards[i]->st->pca_dev;
         const uint64_t rows = transposed ? r.rows_u : r.rows_v;
         if (rows != n_loc) {
-            set_error("multi_knn: the factor along the sharded dimension is not kept per shard (%llu rows on the device for %llu cells): pass the scores as a host array",
-                      (unsigned long long)rows, (unsigned long long)n_loc);
+            set_error("%s: the factor along the sharded dimension is not kept per shard (%llu rows on the device for %llu cells): pass the scores as a host array",
+                      name, (unsigned long long)rows, (unsigned long long)n_loc);
             return (int)SCANRS_ERR_ARGUMENT;
         }
-        return scanrs_knn_sharded(h, transposed ? du : dv, 1, transposed ? ldu : ldv, kk, k, o, sq);
+        return search(h, transposed ? du : dv, 1, transposed ? ldu : ldv, kk, lo);
+    });
+}
+} // namespace
+
+// scanrs_knn_sharded on every shard at once. The cells are the sharded dimension (the columns of a CSC matrix, the rows of a CSR
+// one, which goes through its transposed view); every shard writes its own rows of the caller's arrays. points == NULL: every shard
+// searches the factor along the sharded dimension that its last scanrs_multi_pca_bk / _rand left on its device (V of a genes x cells
+// CSC matrix, U of a cells x genes CSR one), where that factor has the shard's own rows.
+int scanrs_multi_knn(scanrs_multi *mm, const double *points, uint32_t ld, uint32_t d, uint32_t k, uint32_t *out, double *sq_dist) {
+    if (!mm) return bad_argument("null handle");
+    if (mm->bounds.back() && k && !out) return bad_argument("null argument");
+    return multi_search_points(mm, "multi_knn", points, ld, d, [&](scanrs_mat *h, const double *p, int on_device, uint32_t ldp, uint32_t dp, uint64_t lo) {
+        return scanrs_knn_sharded(h, p, on_device, ldp, dp, k, out ? out + lo * k : nullptr, sq_dist ? sq_dist + lo * k : nullptr);
     });
 }
 
@@ -776,26 +784,13 @@ int scanrs_multi_knn(scanrs_multi *mm, const double *points, uint32_t ld, uint32
 int scanrs_multi_nearest_neighbors(scanrs_multi *mm, const double *points, uint32_t ld, uint32_t d, uint32_t k, int distance_type,
                                    uint32_t *indices, double *distances) {
     if (!mm) return bad_argument("null handle");
-    const uint64_t cells = mm->bounds.back();
-    if (cells && k && (!indices || !distances)) return bad_argument("null argument");
-    const int transposed = mm->storage == SCANRS_CSR;
-    return collective(mm, transposed, nullptr, [&](size_t i, scanrs_mat *h, const scanrs_snoop *, ShardOutputs &) {
-        const uint64_t lo = mm->bounds[i], n_loc = mm->bounds[i + 1] - lo;
-        uint32_t *o = indices ? indices + lo * k : nullptr;
-        double *od = distances ? distances + lo * k : nullptr;
-        if (points) return scanrs_nearest_neighbors_sharded(h, points, 0, ld, d, k, distance_type, o, od);
-        const double *du = nullptr, *dv = nullptr;
-        uint32_t ldu = 0, ldv = 0, kk = 0;
-        if (const int rc = scanrs_pca_result_device(mm->shards[i], &du, &ldu, &dv, &ldv, &kk)) return rc; // "no PCA result on this handle yet"
-        const Storage::PcaDev &r = mm->shards[i]->st->pca_dev;
-        const uint64_t rows = transposed ? r.rows_u : r.rows_v;
-        if (rows != n_loc) {
-            set_error("multi_nearest_neighbors: the factor along the sharded dimension is not kept per shard (%llu rows on the device for %llu cells): pass the scores as a host array",
-                      (unsigned long long)rows, (unsigned long long)n_loc);
-            return (int)SCANRS_ERR_ARGUMENT;
-        }
-        return scanrs_nearest_neighbors_sharded(h, transposed ? du : dv, 1, transposed ? ldu : ldv, kk, k, distance_type, o, od);
-    });
+    if (mm->bounds.back() && k && (!indices || !distances)) return bad_argument("null argument");
+    return multi_search_points(mm, "multi_nearest_neighbors", points, ld, d,
+                               [&](scanrs_mat *h, const double *p, int on_device, uint32_t ldp, uint32_t dp, uint64_t lo) {
+                                   return scanrs_nearest_neighbors_sharded(h, p, on_device, ldp, dp, k, distance_type,
+                                                                           indices ? indices + lo * k : nullptr,
+                                                                           distances ? distances + lo * k : nullptr);
+                               });
 }
 
 // ---- select_rows / select_cols / partition_on_thresholds over the shards -------------------------------------------------

@@ -64,7 +64,7 @@ def _fma_sq_acc(t, s):
 
 
 def exact_d2(q, p, chunk=512):
-    """n_q x n_p squared distances, bit for bit what knn_kernel / kf_rerank_kernel compute: s = fma(p_j - q_j, p_j - q_j, s), j ascending"""
+    """n_q x n_p squared distances, bit for bit what knn_exhaustive_kernel / knn_rerank_kernel compute under knn.hip's Euclid: s = fma(p_j - q_j, p_j - q_j, s), j ascending"""
     q, p = np.asarray(q, dtype=np.float64), np.asarray(p, dtype=np.float64)
     out = np.empty((q.shape[0], p.shape[0]))
     for a in range(0, q.shape[0], chunk):

@@ -4,8 +4,8 @@ fixtures its CPU and GPU tests share.
 The scheme: every rank owns the queries of its own rows; the global rows are cut into blocks of `block_rows` rows (the last one
 short, the cut independent of the shard cut); a query searches one block at a time for the block's k nearest rows other than the
 query's own GLOBAL row and merges them into its running list by (squared distance, global index). Lists are padded with
-(+inf, UINT32_MAX). The squared distance is the library's: t = p_j - q_j, s = fma(t, t, s) in coordinate order (knn_kernel and
-kf_rerank_kernel of scan-rs_amd/csrc/knn.hip), restated here with error-free transformations so that the BITS can be compared."""
+(+inf, UINT32_MAX). The squared distance is the library's: t = p_j - q_j, s = fma(t, t, s) in coordinate order (the policy Euclid of
+scan-rs_amd/csrc/knn.hip under the kernels of knn_search.hpp), restated here with error-free transformations so that the BITS can be compared."""
 import numpy as np
 
 U32MAX = 0xFFFFFFFF

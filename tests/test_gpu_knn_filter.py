@@ -239,3 +239,109 @@ def test_scaling_by_powers_of_two_changes_nothing(sa, params):
             assert np.array_equal(got.astype(np.int64), want), (s, int(np.any(got != want, axis=1).sum()), st)
             if inside:  # the filter stays a filter at every scale inside the window
                 assert all(r["overflowed"] == 0 for r in st["rounds"]), (s, st)
+
+
+# ---- lists that overflow in every round, not only the last --------------------------------------------------------------------------
+# 8192 points, d = 5, k = 10, "knn_filter_min_points" 1024, "knn_ratio" 2: round 0 ranks 1024 rows at stride 8, the filter rounds run at
+# strides 4, 2, 1. Every row r with r % 4 != 3 is one and the same point (6144 rows), so the subset of stride 4 (rows r % 4 == 0) is
+# 2048 coincident rows: every query of the cluster holds more than `cap` candidates at distance 0 and overflows at strides 4, 2 AND 1
+# (and so do the 2048 other queries, whose k-th neighbour so far is the cluster itself). The sharded form below has both kinds of query.
+OVER_N, OVER_D, OVER_K = 8192, 5, 10
+
+
+@contextlib.contextmanager
+def overflow_options(sa):
+    sa.set_global_option("knn_filter_min_points", 1024)
+    sa.set_global_option("knn_ratio", 2)
+    try:
+        yield
+    finally:
+        sa.set_global_option("knn_filter_min_points", 32768)
+        sa.set_global_option("knn_ratio", 4)
+
+
+@pytest.fixture(scope="module")
+def overflow_case():
+    """the points and their float64 reference with one more column: rank(d2, k + 1), the query's own row still in it"""
+    rng = np.random.default_rng(8192)
+    v = rng.standard_normal((OVER_N, OVER_D))
+    v[np.arange(OVER_N) % 4 != 3] = rng.standard_normal(OVER_D)
+    ranked = np.concatenate([kr.rank(kr.exact_d2(v[a:a + 1024], v), OVER_K + 1) for a in range(0, OVER_N, 1024)], axis=0)
+    ranked.setflags(write=False)
+    return v, ranked
+
+
+def reference(ranked, drop_self):
+    """the first k of a row of rank(d2, k + 1), its own index taken out first: what rank(d2, k, drop_self) returns"""
+    if not drop_self:
+        return ranked[:, :OVER_K]
+    keep = ranked != np.arange(ranked.shape[0])[:, None]
+    keep[keep.all(axis=1), OVER_K] = False  # the row itself is not among the k + 1 nearest: the last column goes
+    return ranked[keep].reshape(ranked.shape[0], OVER_K)
+
+
+def overflows_in_every_round(st):
+    return st["filtered"] and [r["stride"] for r in st["rounds"]] == [4, 2, 1] and all(r["overflowed"] > 0 for r in st["rounds"])
+
+
+def test_overflow_in_every_round_knn(sa, overflow_case):
+    v, ranked = overflow_case
+    with overflow_options(sa):
+        got = sa.knn(v, OVER_K)
+        st = sa.debug_knn_last_stats()
+        want = exhaustive(sa, lambda: sa.knn(v, OVER_K))
+    print(st)
+    assert np.array_equal(got, want)
+    assert np.array_equal(got.astype(np.int64), reference(ranked, True))
+    assert overflows_in_every_round(st), st
+
+
+@pytest.mark.parametrize("include_self", (True, False))
+def test_overflow_in_every_round_find_nn(sa, overflow_case, include_self):
+    v, ranked = overflow_case
+    with overflow_options(sa):
+        got = sa.find_nn(v, OVER_K, v, include_self)
+        st = sa.debug_knn_last_stats()
+        want = exhaustive(sa, lambda: sa.find_nn(v, OVER_K, v, include_self))
+    assert np.array_equal(got, want)
+    assert np.array_equal(got.astype(np.int64), reference(ranked, not include_self))
+    assert overflows_in_every_round(st), st
+
+
+def test_overflow_in_every_round_sharded_and_seeded(sa, overflow_case):
+    """two ranks, blocks of 4096 rows: the second block is searched with the seed of the first, and its lists overflow as well"""
+    import test_gpu_knn_sharded as ks
+
+    v, ranked = overflow_case
+    run = ks.make(sa, "hook", OVER_N, [0, OVER_N // 2, OVER_N])
+    plain = sa.AdaptiveMat.from_csmat(1, OVER_N, sa.CSC, *ks.cell_matrix(OVER_N))
+    try:
+        with overflow_options(sa), ks.options(sa, block_rows=4096, min_points=1024):
+            got, dist = run.knn(v, OVER_K)
+            st = sa.debug_knn_last_stats()
+            blocks = run.counters("knn_blocks")
+            want, want_dist = plain.knn_sharded(v, OVER_K, return_sq_dist=True)
+            assert overflows_in_every_round(sa.debug_knn_last_stats())
+    finally:
+        run.close()
+    print(st)
+    assert np.array_equal(got, want) and np.array_equal(got.astype(np.int64), reference(ranked, True))
+    ks.same_bits(dist, want_dist)
+    # a block is 4096 rows and a seeded search ranks 256 of them exactly: strides 8, 4, 2, 1, and from 2048 rows on a list overflows
+    assert blocks == [2, 2] and st["filtered"] and [r["stride"] for r in st["rounds"]] == [8, 4, 2, 1]
+    assert [r["overflowed"] > 0 for r in st["rounds"]] == [False, False, True, True], st
+    # some of the rank's 4096 queries overflow and some take the plain filter path in the same rounds: the list of queries handed to
+    # the exhaustive kernel is a proper subset, not 0 .. n_q - 1 (a query far from the cluster holds k nearer rows after the first block)
+    assert all(0 < r["overflowed"] < OVER_N // 2 for r in st["rounds"][2:]), st
+
+
+def test_overflow_in_every_round_cosine(sa, overflow_case):
+    """the twin under cosine distance: coincident rows standardise to one z, so the same lists overflow in the same rounds"""
+    v, _ = overflow_case
+    with overflow_options(sa):
+        idx, dist = sa.nearest_neighbors(v, OVER_K, "cosine")
+        st = sa.debug_knn_last_stats()
+    want_idx, want_dist = sa.host_nearest_neighbors(v, OVER_K, "cosine")
+    assert np.array_equal(idx, want_idx)
+    assert np.array_equal(np.ascontiguousarray(dist).view(np.uint64), np.ascontiguousarray(want_dist).view(np.uint64))
+    assert overflows_in_every_round(st), st

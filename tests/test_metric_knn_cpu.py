@@ -197,7 +197,7 @@ def test_the_threshold_of_the_filtered_route_covers_every_neighbour(sa, kind, d)
         for p in range(q + 1, n):
             key, _ = sa.host_distance(kind, x[q], x[p])
             kk = key * key
-            tau = 2.0 * kk * (1.0 + delta) + e  # km_tau_kernel, the same IEEE operations
+            tau = 2.0 * kk * (1.0 + delta) + e  # Metric::threshold of knn_metric.hip, the same IEEE operations
             exact = sum((a - b) ** 2 for a, b in zip(zf[q], zf[p]))
             assert exact <= Fraction(tau) - Fraction(chain), (kind, d, q, p, float(exact), tau)
             assert exact <= 2 * Fraction(kk) * (1 + 69 * u) + 500 * u, (kind, d, q, p, float(exact - 2 * Fraction(kk)))
