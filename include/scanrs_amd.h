@@ -1348,7 +1348,7 @@ enum { SCANRS_DIST_EUCLIDEAN = 0, SCANRS_DIST_PEARSON = 1, SCANRS_DIST_COSINE = 
  * standardised rows with a threshold converted rigorously from the query's k-th key, every pair that passes ranked by the
  * reference formula. Options "knn_exhaustive", "knn_filter_min_points", "knn_ratio", "knn_stats" apply;
  * scanrs_debug_knn_last_stats tells which route the last call took.
- * NOT provided: everything after the neighbour lists (fuzzy graph, layout).
+ * NOT provided: the layout after the neighbour lists and their graph (the graph: scanrs_fuzzy_simplicial_set below).
  * scanrs_nearest_neighbors (knn.rs:112-166): data, indices, distances are host arrays.
  * scanrs_nearest_neighbors_query (knn.rs:112-166): a query set of its own. queries n_q x d and points n_p x d are host arrays;
  * indices / distances: n_q x k, the indices are rows of `points`. include_self == 0 drops the point whose index equals the query's
@@ -1405,6 +1405,93 @@ int scanrs_multi_nearest_neighbors(scanrs_multi *mm, const double *points, uint3
 int scanrs_host_distance(int distance_type, const double *x, const double *y, uint32_t d, double *key, double *dist);
 int scanrs_host_metric_rows(int distance_type, const double *data, uint64_t n, uint32_t d, double *c, double *s, double *z);
 int scanrs_debug_nearest_neighbors_params(double *delta, double *e, double *chain, double *sxx_min, double *sxx_max);
+
+/* ---- fuzzy_simplicial_set: the UMAP graph of the neighbour lists (umap-rs/src/fuzzy.rs, embedding.rs) ---------------
+ * umap_rs::fuzzy::fuzzy_simplicial_set(knn_indices, knn_distances, local_connectivity, set_operation_ratio, apply_fuzzy_combine,
+ * n_iter, bandwidth) -> CsMat (fuzzy.rs:30-62, called at umap.rs:92-100), and the pruned edge list of
+ * initialize_simplicial_set_embedding (embedding.rs:29-54) up to but NOT including its shuffle. The reference's formulas literally,
+ * every operation a separate IEEE f64 operation:
+ *  rho (fuzzy.rs:79-99) from the row's distances > 0 in column order (+inf counts); where the reference would index past their end
+ *    (non_zero_dist[index] with index == len, or non_zero_dist[0] of an empty list with floor(local_connectivity) == 0) the call is
+ *    refused, naming the first such row.
+ *  sigma (smooth_knn_dist, fuzzy.rs:117-145): target = log2(k) * bandwidth with k the width of the lists; psum folds
+ *    exp(-(max(max(v, -rho), 0) / mid)) - v, not v - rho, as the reference writes it -; at most n_iter bisection steps.
+ *  The floor (fuzzy.rs:103-111): rows with rho > 0 by their own mean distance, the others by the global mean. DEVIATION: the
+ *    reference's global mean is one sequential fold over all n * k distances; the library adds the rows' left folds in a fixed tree
+ *    whose shape depends on n alone (at most 2 n k 2^-53 relative from the reference's sum; it reaches only sigma of rows whose rho
+ *    is not > 0, and with local_connectivity >= 1 no graph value depends on it).
+ *  Membership (fuzzy.rs:161-178): entries with index UINT32_MAX are skipped; the value is 0 where the column POSITION j equals the
+ *    neighbour's index (`j == knn_indices[[i, j]]`, literally), 1 where d - rho <= 0 or sigma == 0, else exp(-((d - rho) / sigma));
+ *    it is R[index, i]: row = the neighbour, column = i.
+ *  Union (fuzzy.rs:52-58) at every position of the pattern of R and its transpose, a missing operand read as +0.0:
+ *    (r + t - r t) ratio + (r t)(1 - ratio), five operations. Zeros are stored like any other value.
+ *  exp is the library's own (scanrs_host_fuzzy_exp), within 1 ulp like the libm the reference calls, the same source on the host and
+ *    on the device: the device result EQUALS scanrs_host_fuzzy_simplicial_set in every bit of every output.
+ * DEVIATION: an index a row names twice is refused. sprs' TriMat would add the two entries, but no neighbour list of the reference
+ * names a row twice.
+ * Refused with SCANRS_ERR_ARGUMENT: n == 0 or k == 0 (the reference asserts); k > 128; n > 2^32 - 2; local_connectivity not finite
+ * or < 0; set_op_mix_ratio not finite; and per row, naming the first one: a NaN distance, an index that is neither < n nor
+ * UINT32_MAX, the rho cases above, a repeated index. A refused or failed call leaves no handle and no device memory behind.
+ * The sharded and multi-GPU forms are not provided. */
+typedef struct scanrs_graph scanrs_graph;
+typedef struct scanrs_fuzzy_params {
+    double local_connectivity;   /* as in the reference (umap.rs: 1.0) */
+    double set_op_mix_ratio;     /* as in the reference (umap.rs: 1.0) */
+    int32_t apply_fuzzy_combine; /* 0: the graph is R itself (fuzzy.rs:48-50) */
+    uint32_t n_iter;             /* 0 = the reference's 64 (fuzzy.rs:8) */
+    double bandwidth;            /* 0.0 = the reference's 1.0 (fuzzy.rs:7) */
+} scanrs_fuzzy_params;
+/* scanrs_fuzzy_simplicial_set (fuzzy.rs:30-62): knn_indices (u32) / knn_distances (f64): host arrays, n x k, UINT32_MAX / +inf padding
+ * accepted (what scanrs_nearest_neighbors writes). *graph: CSR resident on the device: u64 indptr (n + 1), u32 indices ascending
+ * within a row, f64 values.
+ * scanrs_fuzzy_simplicial_set_device (fuzzy.rs:30-62): the lists in device memory, both with leading dimension ld >= k.
+ * scanrs_umap_graph (umap.rs:89-100): the search of scanrs_nearest_neighbors on host points (n x d), key -> distance, then the
+ * graph, with nothing over the host link in between. The width of the lists is min(k, n - 1) (knn.rs:124-127), and that width is
+ * the k of target. The result EQUALS scanrs_fuzzy_simplicial_set of scanrs_nearest_neighbors' output in every bit; the euclidean
+ * kind inherits that search's stated deviation. Refusals of both.
+ * scanrs_umap_graph_device (umap.rs:89-100): the points in device memory, leading dimension ld >= d.
+ * scanrs_host_fuzzy_simplicial_set (fuzzy.rs:30-62; host only): the twin; its graph lives in host memory and answers the same
+ * accessors (scanrs_graph_device refuses it).
+ * scanrs_graph_info (fuzzy.rs:39): out[0] = n, out[1] = nnz, out[2] = the width of the lists, out[3] = 1 where the graph is resident
+ * on the device; n_out values are written.
+ * scanrs_graph_to_host (fuzzy.rs:47): indptr (n + 1), indices (nnz), values (nnz) into host arrays.
+ * scanrs_graph_sigmas_rhos (fuzzy.rs:43): the pair smooth_knn_distances returns, n each.
+ * scanrs_graph_device (fuzzy.rs:47): the device addresses of the three CSR arrays, valid until scanrs_graph_free.
+ * scanrs_graph_free (fuzzy.rs:47): null is a no-op.
+ * scanrs_graph_edge_count (embedding.rs:38-49): how many entries survive: graph_max = the maximum of the values folded from 0.0; a
+ * value < graph_max / n_epochs becomes 0; values != 0.0 remain. n_epochs must be > 0. The graph is not modified.
+ * scanrs_graph_edges (embedding.rs:38-53, 75-85): those entries in CSR order (rows ascending, columns ascending): tail = row,
+ * head = column, weight, and epochs_per_sample = n_epochs / ((w / max_w) * n_epochs) where that product is > 0, else -1. Host
+ * arrays of scanrs_graph_edge_count entries. The shuffle (embedding.rs:51) is not part of this.
+ * scanrs_host_fuzzy_exp (fuzzy.rs:126, 171; host only): the library's exponential, element by element. exp(+-0) = 1, exp(-inf) = 0,
+ * NaN -> NaN, gradual underflow.
+ * scanrs_host_smooth_knn_dist (fuzzy.rs:117-145; host only): sigma of one row of k distances for a given rho; *iterations (may be
+ * null) = how many times psum was formed. n_iter 0 = 64, bandwidth 0.0 = 1.0.
+ * scanrs_host_membership_strengths (fuzzy.rs:148-181; host only): the COO triple (rows, cols, values; room for n * k each) and
+ * *count of them. Indices are not checked (repeated ones included: the reference's own table has one). */
+int scanrs_fuzzy_simplicial_set(const uint32_t *knn_indices, const double *knn_distances, uint64_t n, uint32_t k,
+                                const scanrs_fuzzy_params *params, scanrs_graph **graph);
+int scanrs_fuzzy_simplicial_set_device(const uint32_t *d_knn_indices, const double *d_knn_distances, uint64_t n, uint32_t ld, uint32_t k,
+                                       const scanrs_fuzzy_params *params, scanrs_graph **graph);
+int scanrs_umap_graph(const double *points, uint64_t n, uint32_t d, uint32_t k, int distance_type, const scanrs_fuzzy_params *params,
+                      scanrs_graph **graph);
+int scanrs_umap_graph_device(const double *d_points, uint64_t n, uint32_t ld, uint32_t d, uint32_t k, int distance_type,
+                             const scanrs_fuzzy_params *params, scanrs_graph **graph);
+int scanrs_host_fuzzy_simplicial_set(const uint32_t *knn_indices, const double *knn_distances, uint64_t n, uint32_t k,
+                                     const scanrs_fuzzy_params *params, scanrs_graph **graph);
+int scanrs_graph_info(const scanrs_graph *graph, uint64_t *out, uint32_t n_out);
+int scanrs_graph_to_host(const scanrs_graph *graph, uint64_t *indptr, uint32_t *indices, double *values);
+int scanrs_graph_sigmas_rhos(const scanrs_graph *graph, double *sigmas, double *rhos);
+int scanrs_graph_device(const scanrs_graph *graph, const uint64_t **d_indptr, const uint32_t **d_indices, const double **d_values);
+void scanrs_graph_free(scanrs_graph *graph);
+int scanrs_graph_edge_count(const scanrs_graph *graph, double n_epochs, uint64_t *count);
+int scanrs_graph_edges(const scanrs_graph *graph, double n_epochs, uint32_t *head, uint32_t *tail, double *weights,
+                       double *epochs_per_sample);
+int scanrs_host_fuzzy_exp(const double *x, uint64_t count, double *out);
+int scanrs_host_smooth_knn_dist(const double *distances, uint32_t k, double rho, double bandwidth, uint32_t n_iter, double *sigma,
+                                uint32_t *iterations);
+int scanrs_host_membership_strengths(const uint32_t *knn_indices, const double *knn_distances, uint64_t n, uint32_t k, const double *sigmas,
+                                     const double *rhos, uint32_t *rows, uint32_t *cols, double *values, uint64_t *count);
 
 /* ---- the plan of the fixed-point column moments (option "col_moments"; host only, no device) -----------------------------------
  * The route adds, per slice, the terms f of the map as 64-bit integers rint(f 2^e1) (and rint(f^2 2^e2)): one quantum q = 2^-e for

@@ -1401,6 +1401,119 @@ inline void host_metric_rows(DistanceType distance_type, const double *data, uin
 inline void debug_nearest_neighbors_params(double *delta, double *e, double *chain, double *sxx_min, double *sxx_max) {
     check(scanrs_debug_nearest_neighbors_params(delta, e, chain, sxx_min, sxx_max));
 }
+
+// umap_rs::fuzzy::fuzzy_simplicial_set (umap-rs/src/fuzzy.rs:30-62) and the pruned edge list of initialize_simplicial_set_embedding
+// (embedding.rs:38-53, 75-85, without the shuffle); DESIGN.md §7r. The defaults are the ones umap.rs passes.
+struct FuzzyParams {
+    double local_connectivity = 1.0, set_op_mix_ratio = 1.0;
+    bool apply_fuzzy_combine = true;
+    uint32_t n_iter = 0;    // 0 = the reference's 64
+    double bandwidth = 0.0; // 0.0 = the reference's 1.0
+    scanrs_fuzzy_params raw() const { return scanrs_fuzzy_params{local_connectivity, set_op_mix_ratio, apply_fuzzy_combine ? 1 : 0, n_iter, bandwidth}; }
+};
+struct GraphEdges {
+    std::vector<uint32_t> head, tail;
+    std::vector<double> weights, epochs_per_sample;
+};
+struct CsrGraph {
+    std::vector<uint64_t> indptr;
+    std::vector<uint32_t> indices;
+    std::vector<double> values;
+};
+class FuzzyGraph {
+    scanrs_graph *h_ = nullptr;
+    explicit FuzzyGraph(scanrs_graph *h) : h_(h) {}
+
+  public:
+    // fuzzy_simplicial_set of host lists (n x k); host_only: the twin (scanrs_host_fuzzy_simplicial_set), no device
+    FuzzyGraph(const uint32_t *knn_indices, const double *knn_distances, uint64_t n, uint32_t k, const FuzzyParams &p = FuzzyParams(),
+               bool host_only = false) {
+        const scanrs_fuzzy_params r = p.raw();
+        check((host_only ? scanrs_host_fuzzy_simplicial_set : scanrs_fuzzy_simplicial_set)(knn_indices, knn_distances, n, k, &r, &h_));
+    }
+    // the lists already in device memory, leading dimension ld >= k
+    static FuzzyGraph from_device_lists(const uint32_t *d_knn_indices, const double *d_knn_distances, uint64_t n, uint32_t ld, uint32_t k,
+                                        const FuzzyParams &p = FuzzyParams()) {
+        const scanrs_fuzzy_params r = p.raw();
+        scanrs_graph *h = nullptr;
+        check(scanrs_fuzzy_simplicial_set_device(d_knn_indices, d_knn_distances, n, ld, k, &r, &h));
+        return FuzzyGraph(h);
+    }
+    // nearest_neighbors and the graph in one go, the lists never leaving the device (umap.rs:89-100)
+    static FuzzyGraph umap_graph(const Array2 &points, size_t k, DistanceType distance_type, const FuzzyParams &p = FuzzyParams()) {
+        const scanrs_fuzzy_params r = p.raw();
+        scanrs_graph *h = nullptr;
+        check(scanrs_umap_graph(points.data.data(), points.rows, (uint32_t)points.cols, (uint32_t)k, (int)distance_type, &r, &h));
+        return FuzzyGraph(h);
+    }
+    static FuzzyGraph umap_graph_device(const double *d_points, uint64_t n, uint32_t ld, uint32_t d, size_t k, DistanceType distance_type,
+                                        const FuzzyParams &p = FuzzyParams()) {
+        const scanrs_fuzzy_params r = p.raw();
+        scanrs_graph *h = nullptr;
+        check(scanrs_umap_graph_device(d_points, n, ld, d, (uint32_t)k, (int)distance_type, &r, &h));
+        return FuzzyGraph(h);
+    }
+    FuzzyGraph(const FuzzyGraph &) = delete;
+    FuzzyGraph &operator=(const FuzzyGraph &) = delete;
+    FuzzyGraph(FuzzyGraph &&o) noexcept : h_(o.h_) { o.h_ = nullptr; }
+    FuzzyGraph &operator=(FuzzyGraph &&o) noexcept {
+        if (this != &o) {
+            scanrs_graph_free(h_);
+            h_ = o.h_;
+            o.h_ = nullptr;
+        }
+        return *this;
+    }
+    ~FuzzyGraph() { scanrs_graph_free(h_); }
+    scanrs_graph *raw() const { return h_; }
+    uint64_t rows() const { return info(0); }
+    uint64_t nnz() const { return info(1); }
+    uint64_t info(uint32_t what) const { // 0: n, 1: nnz, 2: the width of the lists, 3: resident on the device
+        uint64_t v[4] = {0, 0, 0, 0};
+        check(scanrs_graph_info(h_, v, 4));
+        return v[what & 3];
+    }
+    CsrGraph to_csr() const {
+        CsrGraph g{std::vector<uint64_t>(rows() + 1), std::vector<uint32_t>(nnz()), std::vector<double>(nnz())};
+        check(scanrs_graph_to_host(h_, g.indptr.data(), g.indices.data(), g.values.data()));
+        return g;
+    }
+    void sigmas_rhos(std::vector<double> &sigmas, std::vector<double> &rhos) const {
+        sigmas.assign(rows(), 0.0), rhos.assign(rows(), 0.0);
+        check(scanrs_graph_sigmas_rhos(h_, sigmas.data(), rhos.data()));
+    }
+    void device(const uint64_t **d_indptr, const uint32_t **d_indices, const double **d_values) const {
+        check(scanrs_graph_device(h_, d_indptr, d_indices, d_values));
+    }
+    GraphEdges edges(double n_epochs) const { // embedding.rs:38-53, 75-85: tail = row, head = column, in CSR order
+        uint64_t m = 0;
+        check(scanrs_graph_edge_count(h_, n_epochs, &m));
+        GraphEdges e{std::vector<uint32_t>(m), std::vector<uint32_t>(m), std::vector<double>(m), std::vector<double>(m)};
+        check(scanrs_graph_edges(h_, n_epochs, e.head.data(), e.tail.data(), e.weights.data(), e.epochs_per_sample.data()));
+        return e;
+    }
+};
+inline std::vector<double> host_fuzzy_exp(const std::vector<double> &x) {
+    std::vector<double> out(x.size());
+    check(scanrs_host_fuzzy_exp(x.data(), x.size(), out.data()));
+    return out;
+}
+// smooth_knn_dist of one row (fuzzy.rs:117-145): sigma; *iterations = how many times psum was formed
+inline double host_smooth_knn_dist(const std::vector<double> &distances, double rho, double bandwidth = 0.0, uint32_t n_iter = 0,
+                                   uint32_t *iterations = nullptr) {
+    double sigma = 0.0;
+    check(scanrs_host_smooth_knn_dist(distances.data(), (uint32_t)distances.size(), rho, bandwidth, n_iter, &sigma, iterations));
+    return sigma;
+}
+// compute_membership_strengths (fuzzy.rs:148-181): the COO triple; returns its length
+inline uint64_t host_membership_strengths(const uint32_t *knn_indices, const double *knn_distances, uint64_t n, uint32_t k, const double *sigmas,
+                                          const double *rhos, std::vector<uint32_t> &rows, std::vector<uint32_t> &cols, std::vector<double> &values) {
+    rows.assign(n * k, 0), cols.assign(n * k, 0), values.assign(n * k, 0.0);
+    uint64_t m = 0;
+    check(scanrs_host_membership_strengths(knn_indices, knn_distances, n, k, sigmas, rhos, rows.data(), cols.data(), values.data(), &m));
+    rows.resize(m), cols.resize(m), values.resize(m);
+    return m;
+}
 // the plan of the fixed-point column moments (option "col_moments") on the host: accepted or not, and the two exponents
 struct ColMomentsPlan {
     bool accept = false;

@@ -1895,6 +1895,191 @@ def debug_nearest_neighbors_params() -> dict:
     return dict(zip(("delta", "e", "chain", "sxx_min", "sxx_max"), (x.value for x in v)))
 
 
+class _FuzzyParams(ctypes.Structure):
+    _fields_ = [("local_connectivity", ctypes.c_double), ("set_op_mix_ratio", ctypes.c_double), ("apply_fuzzy_combine", ctypes.c_int32),
+                ("n_iter", ctypes.c_uint32), ("bandwidth", ctypes.c_double)]
+
+
+def _fuzzy_params(local_connectivity, set_op_mix_ratio, apply_fuzzy_combine, n_iter, bandwidth):
+    return _FuzzyParams(float(local_connectivity), float(set_op_mix_ratio), 1 if apply_fuzzy_combine else 0, int(n_iter or 0), float(bandwidth or 0.0))
+
+
+_lib.scanrs_graph_free.argtypes = [ctypes.c_void_p]
+_lib.scanrs_graph_free.restype = None
+
+
+class FuzzyGraph:
+    """The UMAP graph of `fuzzy_simplicial_set` (`scanrs_graph`, umap-rs/src/fuzzy.rs:30-62): n x n CSR, resident on the
+    device (or in host memory for `host_fuzzy_simplicial_set`)."""
+
+    def __init__(self, handle):
+        self._h = handle
+        info = (ctypes.c_uint64 * 4)()
+        _check(_lib.scanrs_graph_info(self._hp(), info, ctypes.c_uint32(4)))
+        self._n, self._nnz, self.k, self.on_device = int(info[0]), int(info[1]), int(info[2]), bool(info[3])
+
+    def _hp(self):
+        if not self._h:
+            raise ScanrsError(6, "the graph has been closed")
+        return ctypes.c_void_p(self._h)
+
+    @property
+    def shape(self):
+        return (self._n, self._n)
+
+    @property
+    def nnz(self) -> int:
+        return self._nnz
+
+    def to_csr(self):
+        """(indptr u64, indices u32, values f64); indices ascend within a row, zeros are stored."""
+        indptr, indices, values = np.zeros(self._n + 1, np.uint64), np.zeros(self._nnz, np.uint32), np.zeros(self._nnz, np.float64)
+        _check(_lib.scanrs_graph_to_host(self._hp(), _p(indptr), _p(indices), _p(values)))
+        return indptr, indices, values
+
+    def _sigmas_rhos(self):
+        sigmas, rhos = np.zeros(self._n), np.zeros(self._n)
+        _check(_lib.scanrs_graph_sigmas_rhos(self._hp(), _p(sigmas), _p(rhos)))
+        return sigmas, rhos
+
+    @property
+    def sigmas(self):
+        return self._sigmas_rhos()[0]
+
+    @property
+    def rhos(self):
+        return self._sigmas_rhos()[1]
+
+    def device_pointers(self):
+        """(d_indptr, d_indices, d_values): device addresses, valid until close() (`scanrs_graph_device`)."""
+        a, b, c = ctypes.c_void_p(), ctypes.c_void_p(), ctypes.c_void_p()
+        _check(_lib.scanrs_graph_device(self._hp(), ctypes.byref(a), ctypes.byref(b), ctypes.byref(c)))
+        return a.value, b.value, c.value
+
+    def edge_count(self, n_epochs: float) -> int:
+        count = ctypes.c_uint64()
+        _check(_lib.scanrs_graph_edge_count(self._hp(), ctypes.c_double(n_epochs), ctypes.byref(count)))
+        return int(count.value)
+
+    def edges(self, n_epochs: float):
+        """The pruned edge list of `initialize_simplicial_set_embedding` before its shuffle (embedding.rs:38-53, 75-85):
+        (head u32, tail u32, weights f64, epochs_per_sample f64) in CSR order; tail = row, head = column."""
+        m = self.edge_count(n_epochs)
+        head, tail, w, eps = np.zeros(m, np.uint32), np.zeros(m, np.uint32), np.zeros(m), np.zeros(m)
+        _check(_lib.scanrs_graph_edges(self._hp(), ctypes.c_double(n_epochs), _p(head), _p(tail), _p(w), _p(eps)))
+        return head, tail, w, eps
+
+    def close(self):
+        if self._h:
+            _lib.scanrs_graph_free(ctypes.c_void_p(self._h))
+            self._h = None
+
+    def __enter__(self):
+        return self
+
+    def __exit__(self, *exc):
+        self.close()
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
+
+
+def _knn_lists(indices, distances):
+    indices = np.ascontiguousarray(np.atleast_2d(indices), dtype=np.uint32)
+    distances = _f64(np.atleast_2d(distances))
+    if indices.shape != distances.shape:
+        raise ScanrsError(1, "Dimension mismatch")
+    return indices, distances
+
+
+def _graph_call(fn, *head):
+    h = ctypes.c_void_p()
+    _check(fn(*head, ctypes.byref(h)))
+    return FuzzyGraph(h.value)
+
+
+def fuzzy_simplicial_set(indices, distances, local_connectivity: float = 1.0, set_op_mix_ratio: float = 1.0, apply_fuzzy_combine: bool = True,
+                         n_iter: int = 0, bandwidth: float = 0.0) -> FuzzyGraph:
+    """`umap_rs::fuzzy::fuzzy_simplicial_set` (umap-rs/src/fuzzy.rs:30-62) of the lists `nearest_neighbors` returns (n x k, u32 / f64,
+    UINT32_MAX / +inf padding accepted), on the device (`scanrs_fuzzy_simplicial_set`). n_iter 0 = 64, bandwidth 0 = 1.0.
+    Equal to `host_fuzzy_simplicial_set` in every bit."""
+    indices, distances = _knn_lists(indices, distances)
+    n, k = indices.shape
+    prm = _fuzzy_params(local_connectivity, set_op_mix_ratio, apply_fuzzy_combine, n_iter, bandwidth)
+    return _graph_call(_lib.scanrs_fuzzy_simplicial_set, _p(indices), _p(distances), ctypes.c_uint64(n), ctypes.c_uint32(k), ctypes.byref(prm))
+
+
+def fuzzy_simplicial_set_device(d_indices: int, d_distances: int, n: int, ld: int, k: int, local_connectivity: float = 1.0,
+                                set_op_mix_ratio: float = 1.0, apply_fuzzy_combine: bool = True, n_iter: int = 0, bandwidth: float = 0.0) -> FuzzyGraph:
+    """`fuzzy_simplicial_set` on lists that already live in device memory, leading dimension ld >= k (`scanrs_fuzzy_simplicial_set_device`)."""
+    prm = _fuzzy_params(local_connectivity, set_op_mix_ratio, apply_fuzzy_combine, n_iter, bandwidth)
+    return _graph_call(_lib.scanrs_fuzzy_simplicial_set_device, ctypes.c_void_p(d_indices), ctypes.c_void_p(d_distances), ctypes.c_uint64(n),
+                       ctypes.c_uint32(ld), ctypes.c_uint32(k), ctypes.byref(prm))
+
+
+def host_fuzzy_simplicial_set(indices, distances, local_connectivity: float = 1.0, set_op_mix_ratio: float = 1.0, apply_fuzzy_combine: bool = True,
+                              n_iter: int = 0, bandwidth: float = 0.0) -> FuzzyGraph:
+    """The host twin of `fuzzy_simplicial_set` (`scanrs_host_fuzzy_simplicial_set`, fuzzy.rs:30-62; no device)."""
+    indices, distances = _knn_lists(indices, distances)
+    n, k = indices.shape
+    prm = _fuzzy_params(local_connectivity, set_op_mix_ratio, apply_fuzzy_combine, n_iter, bandwidth)
+    return _graph_call(_lib.scanrs_host_fuzzy_simplicial_set, _p(indices), _p(distances), ctypes.c_uint64(n), ctypes.c_uint32(k), ctypes.byref(prm))
+
+
+def umap_graph(points, k: int, distance="euclidean", local_connectivity: float = 1.0, set_op_mix_ratio: float = 1.0, apply_fuzzy_combine: bool = True,
+               n_iter: int = 0, bandwidth: float = 0.0) -> FuzzyGraph:
+    """`nearest_neighbors` then `fuzzy_simplicial_set` with the lists staying on the device (`scanrs_umap_graph`, umap.rs:89-100):
+    equal to `fuzzy_simplicial_set(*nearest_neighbors(points, k, distance), ...)` in every bit."""
+    points = _f64(np.atleast_2d(points))
+    n, d = points.shape
+    prm = _fuzzy_params(local_connectivity, set_op_mix_ratio, apply_fuzzy_combine, n_iter, bandwidth)
+    return _graph_call(_lib.scanrs_umap_graph, _p(points), ctypes.c_uint64(n), ctypes.c_uint32(d), ctypes.c_uint32(k),
+                       ctypes.c_int(_distance_type(distance)), ctypes.byref(prm))
+
+
+def umap_graph_device(d_points: int, n: int, ld: int, d: int, k: int, distance="euclidean", local_connectivity: float = 1.0,
+                      set_op_mix_ratio: float = 1.0, apply_fuzzy_combine: bool = True, n_iter: int = 0, bandwidth: float = 0.0) -> FuzzyGraph:
+    """`umap_graph` on points that already live in device memory, leading dimension ld >= d (`scanrs_umap_graph_device`)."""
+    prm = _fuzzy_params(local_connectivity, set_op_mix_ratio, apply_fuzzy_combine, n_iter, bandwidth)
+    return _graph_call(_lib.scanrs_umap_graph_device, ctypes.c_void_p(d_points), ctypes.c_uint64(n), ctypes.c_uint32(ld), ctypes.c_uint32(d),
+                       ctypes.c_uint32(k), ctypes.c_int(_distance_type(distance)), ctypes.byref(prm))
+
+
+def host_fuzzy_exp(x):
+    """The library's f64 exponential, element by element (`scanrs_host_fuzzy_exp`; no device): the one both the kernels and the twin use."""
+    x = _f64(x)
+    out = np.zeros_like(x)
+    _check(_lib.scanrs_host_fuzzy_exp(_p(x), ctypes.c_uint64(x.size), _p(out)))
+    return out
+
+
+def host_smooth_knn_dist(distances, rho: float, bandwidth: float = 0.0, n_iter: int = 0):
+    """`smooth_knn_dist` of one row (`scanrs_host_smooth_knn_dist`, fuzzy.rs:117-145; no device): (sigma, iterations)."""
+    distances = _f64(np.ravel(distances))
+    sigma, it = ctypes.c_double(), ctypes.c_uint32()
+    _check(_lib.scanrs_host_smooth_knn_dist(_p(distances), ctypes.c_uint32(distances.shape[0]), ctypes.c_double(rho), ctypes.c_double(bandwidth),
+                                            ctypes.c_uint32(n_iter), ctypes.byref(sigma), ctypes.byref(it)))
+    return sigma.value, int(it.value)
+
+
+def host_membership_strengths(indices, distances, sigmas, rhos):
+    """`compute_membership_strengths` (`scanrs_host_membership_strengths`, fuzzy.rs:148-181; no device): (rows, cols, values)."""
+    indices, distances = _knn_lists(indices, distances)
+    n, k = indices.shape
+    sigmas, rhos = _f64(np.ravel(sigmas)), _f64(np.ravel(rhos))
+    if sigmas.shape[0] < n or rhos.shape[0] < n:
+        raise ScanrsError(1, "Dimension mismatch")
+    rows, cols, values = np.zeros(n * k, np.uint32), np.zeros(n * k, np.uint32), np.zeros(n * k)
+    count = ctypes.c_uint64()
+    _check(_lib.scanrs_host_membership_strengths(_p(indices), _p(distances), ctypes.c_uint64(n), ctypes.c_uint32(k), _p(sigmas), _p(rhos), _p(rows),
+                                                 _p(cols), _p(values), ctypes.byref(count)))
+    m = int(count.value)
+    return rows[:m].copy(), cols[:m].copy(), values[:m].copy()
+
+
 class RandSvd:
     """`RandSvd` (dim_red/rand_svd.rs:13-50)."""
 
@@ -2063,6 +2248,10 @@ EXPORTED_SYMBOLS = [
     "scanrs_nearest_neighbors_query", "scanrs_nearest_neighbors_query_device", "scanrs_host_nearest_neighbors_query",
     "scanrs_nearest_neighbors_sharded", "scanrs_multi_nearest_neighbors", "scanrs_host_distance", "scanrs_host_metric_rows",
     "scanrs_debug_nearest_neighbors_params",
+    "scanrs_fuzzy_simplicial_set", "scanrs_fuzzy_simplicial_set_device", "scanrs_umap_graph", "scanrs_umap_graph_device",
+    "scanrs_host_fuzzy_simplicial_set", "scanrs_graph_info", "scanrs_graph_to_host", "scanrs_graph_sigmas_rhos", "scanrs_graph_device",
+    "scanrs_graph_free", "scanrs_graph_edge_count", "scanrs_graph_edges", "scanrs_host_fuzzy_exp", "scanrs_host_smooth_knn_dist",
+    "scanrs_host_membership_strengths",
     "scanrs_mat_select_rows", "scanrs_mat_select_cols", "scanrs_mat_partition_on_thresholds", "scanrs_mat_to_csmat",
     "scanrs_mat_select_rows_sharded", "scanrs_mat_select_cols_sharded", "scanrs_mat_partition_on_thresholds_sharded", "scanrs_mat_shard_info",
     "scanrs_multi_shape", "scanrs_multi_to_csmat", "scanrs_multi_select_rows", "scanrs_multi_select_cols", "scanrs_multi_partition_on_thresholds",

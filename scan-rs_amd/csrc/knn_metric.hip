@@ -182,12 +182,12 @@ void km_refuse_not_finite(hipStream_t s, const double *X, uint32_t ld, uint64_t 
 }
 
 // n_q queries against n_p >= 1 points in device memory (one array where the pointers, leading dimensions and counts coincide);
-// indices / distances: host arrays, n_q x k
-void km_two_sets(const double *dq, uint64_t n_q, uint32_t ld_q, const double *dp, uint64_t n_p, uint32_t ld_p, uint32_t d, uint32_t k, int kind,
-                 bool skip, uint32_t *indices, double *distances) {
+// dout / ddist: the lists in device memory, n_q x k
+void km_two_sets_resident(const double *dq, uint64_t n_q, uint32_t ld_q, const double *dp, uint64_t n_p, uint32_t ld_p, uint32_t d, uint32_t k,
+                          int kind, bool skip, DevBuf<uint32_t> &dout, DevBuf<double> &ddist) {
     hipStream_t s = 0;
-    DevBuf<uint32_t> dout(n_q * k);
-    DevBuf<double> ddist(n_q * k);
+    dout.alloc(n_q * k);
+    ddist.alloc(n_q * k);
     if (kind == EUCLIDEAN) {
         knn_device_into(dq, ld_q, n_q, dp, ld_p, n_p, d, k, skip, dout.p, ddist.p);
         km_sqrt(s, ddist.p, n_q * k); // +inf padding stays +inf
@@ -204,8 +204,16 @@ void km_two_sets(const double *dq, uint64_t n_q, uint32_t ld_q, const double *dp
         km_search(s, same ? P.rows : Qown.rows, P.rows, d, k, pl, dout.p, ddist.p, stats);
         km_square(s, ddist.p, n_q * k);
         knn_publish_stats(std::move(stats));
+        SCANRS_SYNC(s); // the prepared rows are released on leaving this block
     }
     SCANRS_HIP(hipGetLastError());
+}
+// indices / distances: host arrays, n_q x k
+void km_two_sets(const double *dq, uint64_t n_q, uint32_t ld_q, const double *dp, uint64_t n_p, uint32_t ld_p, uint32_t d, uint32_t k, int kind,
+                 bool skip, uint32_t *indices, double *distances) {
+    DevBuf<uint32_t> dout;
+    DevBuf<double> ddist;
+    km_two_sets_resident(dq, n_q, ld_q, dp, n_p, ld_p, d, k, kind, skip, dout, ddist);
     SCANRS_HIP(hipMemcpy(indices, dout.p, n_q * k * 4, hipMemcpyDeviceToHost));
     SCANRS_HIP(hipMemcpy(distances, ddist.p, n_q * k * 8, hipMemcpyDeviceToHost));
 }
@@ -222,6 +230,14 @@ void nearest_neighbors_device(const double *d_data, uint64_t n, uint32_t ld, uin
         return;
     }
     km_two_sets(d_data, n, ld, d_data, n, ld, d, k, kind, true, indices, distances);
+}
+
+// umap_graph (fuzzy_host.cpp): the same search with the lists left where the graph stage reads them; 1 <= k <= n - 1, so no padding
+void nearest_neighbors_resident(const double *d_data, uint64_t n, uint32_t ld, uint32_t d, uint32_t k, int kind, DevBuf<uint32_t> &idx,
+                                DevBuf<double> &dist) {
+    nearest_neighbors_check_args(n, ld, d, k, kind);
+    km_refuse_not_finite(0, d_data, ld, n, d, "data");
+    km_two_sets_resident(d_data, n, ld, d_data, n, ld, d, k, kind, true, idx, dist);
 }
 
 void nearest_neighbors_query_device(const double *d_queries, uint64_t n_q, uint32_t ld_q, const double *d_points, uint64_t n_p, uint32_t ld_p,
